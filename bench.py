@@ -2,7 +2,7 @@
 """Benchmark of the hot path: 8-bit dual-pol voltages -> coherent-dedispersion filterbank (-F N:D)
 -> detection -> fold, on N MI355X GPUs (one process per GPU).
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--workload target|cfg3|cfg2|cfg4|...]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--workload target|cfg3|cfg2|cfg4|...] [--dump-outputs DIR]
 
 A "step" is one pass of the hot path over one block (parts_per_block overlap-save parts) of synthetic
 8-bit input already resident in HBM.  metric = Msamples/s = unique input time samples per polarisation
@@ -36,6 +36,30 @@ sys.path.insert(0, ROOT)
 
 HBM_PEAK_GBS = 8000.0   # MI355X HBM3E peak, /opt/skills/guides/MI355X_MICROARCH.md
 FP32_VECTOR_PEAK_TFLOPS = 157.3   # MI355X fp32 vector peak (same guide, chip-level parameters)
+DUMP_OUTPUTS_BYTES = 64 * 10 ** 6   # --dump-outputs writes at most this much in all
+
+
+def write_outputs(path, arrays):
+    """--dump-outputs DIR: what the timed path handed its caller after its last timed step, one DIR/<name>.npy per array, in
+    float32 (float32 results and 8/16-bit samples) or float64 (everything else, exactly).  When the arrays exceed
+    DUMP_OUTPUTS_BYTES, the largest are cut to a fixed, seeded sample of their flattened elements: the same indices on every
+    run, so that the files of two builds can be compared element for element."""
+    os.makedirs(path, exist_ok=True)
+    out = {}
+    for name, a in arrays.items():
+        a = np.asarray(a)
+        out[name] = np.ascontiguousarray(a, dtype=np.float32 if a.dtype == np.float32 or a.dtype.itemsize <= 2 else np.float64)
+    total = sum(a.nbytes for a in out.values())
+    for name in sorted(out, key=lambda k: -out[k].nbytes):
+        if total <= DUMP_OUTPUTS_BYTES:
+            break
+        a = out[name].reshape(-1)
+        keep = max(0, DUMP_OUTPUTS_BYTES - (total - a.nbytes)) // a.itemsize
+        idx = np.sort(np.random.default_rng(20100413).choice(a.size, size=keep, replace=False))
+        out[name] = a[idx]
+        total -= a.nbytes - out[name].nbytes
+    for name, a in out.items():
+        np.save(os.path.join(path, name + ".npy"), a)
 
 # name -> (freq MHz, bw MHz, input nchan, ndim, tsamp_us, nchan out, DM, -x freq_res, nbin)
 WORKLOADS = {
@@ -121,7 +145,7 @@ WORKLOADS = {
 }
 
 
-def bench_fold_only(args, wl, torch):
+def bench_fold_only(args, wl, torch, dump_dir=None):
     """Benchmark/fold.csh: one step = one block of `ndat` detected samples (1024 channels x 4 products, FPT floats resident
     in HBM -- the reference's Dummy unpacker does not touch the data either) folded with the vela.polyco predictor:
     phase and period from the polynomial at the block's first sample, the double-precision bin plan on the host
@@ -168,6 +192,8 @@ def bench_fold_only(args, wl, torch):
         step(e)
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
+    if dump_dir:                                               # the PhaseSeries every block of the run was folded into
+        write_outputs(dump_dir, {"profile": fold.synch(), "hits": hits, "integration_length": state["length"]})
     k_ms = sum(a.elapsed_time(b) for a, b in ev) / len(ev)
     # parity gate (one more block on a zeroed profile): every sample in exactly one bin; the profile equals the float64
     # index_add of the same samples by the same plan to float rounding
@@ -218,7 +244,7 @@ def bench_fold_only(args, wl, torch):
     return res
 
 
-def bench_search_mode(args, wl, torch):
+def bench_search_mode(args, wl, torch, dump_dir=None):
     """cfg5: one step = one block of nparts FFT blocks (2*nchan samples each) through digifil's chain
     (dspsr_amd.pipeline.LoadToFil): TFP filterbank + square law + tscrunch [one kernel, the roofline kernel] ->
     Rescale -> PScrunch -> 8-bit SigProcDigitizer, everything resident in HBM."""
@@ -235,7 +261,7 @@ def bench_search_mode(args, wl, torch):
     out = lf.detected
 
     def step():
-        lf.process_block(raw)
+        return lf.process_block(raw)
     for _ in range(args.warmup):
         step()
     torch.cuda.synchronize()
@@ -243,10 +269,12 @@ def bench_search_mode(args, wl, torch):
     t0 = time.perf_counter()
     for a, b in ev:
         a.record()
-        step()
+        packed = step()
         b.record()
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
+    if dump_dir:
+        write_outputs(dump_dir, {"digitised": packed.cpu().numpy()})
     k_ms = sum(a.elapsed_time(b) for a, b in ev) / len(ev)
     samples = npart * 2 * nchan
     # the front-end kernel alone, timed on extra calls (the step above also runs Rescale, PScrunch and the digitizer on
@@ -319,7 +347,7 @@ def make_search_coherent(wl, torch):
     return lf, raw, cfg
 
 
-def bench_search_coherent(args, wl, torch):
+def bench_search_coherent(args, wl, torch, dump_dir=None):
     """cfg5c: one step = one block of nparts overlap-save parts through digifil's convolving branch (dspsr_amd.pipeline.LoadToFilCoherent):
     Filterbank + chirp + Detection::square_law + TScrunch [one launch group, the roofline group] -> Rescale + 8-bit SigProcDigitizer
     [one pass over the 16x smaller scrunched rows], everything resident in HBM."""
@@ -331,9 +359,11 @@ def bench_search_coherent(args, wl, torch):
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        lf.process_block(raw)
+        packed = lf.process_block(raw)
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
+    if dump_dir:
+        write_outputs(dump_dir, {"digitised": packed.cpu().numpy()})
     ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(max(3, args.steps // 2))]
     for a, b in ev:                                   # the filterbank + detection + scrunch launch group alone
         a.record()
@@ -853,10 +883,11 @@ def make_fold_pipeline(name, args, torch, rank, world, local_rank):
     return lt, raw, cfg, info, wl, sharded
 
 
-def run_fold_workload(name, args, torch, dist, rank, world, local_rank, single, steps, warmup, full=True):
+def run_fold_workload(name, args, torch, dist, rank, world, local_rank, single, steps, warmup, full=True, dump_dir=None):
     """One filterbank + detect + fold workload on this process group: the timed region (barrier, `steps` steps with a
     sub-integration dump every args.dump_steps, barrier), then -- outside it -- the unfused roofline blocks and the
-    parity gate.  Returns the result record on rank 0 (None elsewhere).  full: cpu_baseline / --h2d companions too."""
+    parity gate.  Returns the result record on rank 0 (None elsewhere).  full: cpu_baseline / --h2d companions too.
+    dump_dir: write_outputs() of the sub-integration that holds the last timed step, as rank 0 receives it."""
     import dspsr_amd
     from dspsr_amd import pipeline
     lt, raw, cfg, info, wl, sharded = make_fold_pipeline(name, args, torch, rank, world, local_rank)
@@ -881,11 +912,19 @@ def run_fold_workload(name, args, torch, dist, rank, world, local_rank, single, 
             dist.barrier()
         torch.cuda.synchronize()
 
+    last = [None]          # the latest sub-integration with samples in it that reached rank 0
+
+    def keep_last():
+        for sub in lt.subints:
+            if sub["ndat_total"]:
+                last[0] = sub
+        lt.subints.clear()
+
     def dump(wait=False, check=False):
         # (the dump of block i overlaps the kernels of block i+1: snapshot on the compute stream, collective on the
         #  communicator's stream; hits are checked in the parity gate and in the timed dumps of `reduce_ms_per_dump`)
         lt.finish_subint(comm, rank, world, gather, replicas=not sharded, check_hits=check, wait=wait)
-        lt.subints.clear()
+        keep_last()
 
     blocks_done = [0]
 
@@ -908,9 +947,16 @@ def run_fold_workload(name, args, torch, dist, rank, world, local_rank, single, 
         step(i, events[i])
     dump()
     lt.collect_subint()                                                   # the last exchange has arrived on the root
-    lt.subints.clear()
+    keep_last()
     barrier()
     elapsed = time.perf_counter() - t_start
+    if dump_dir and rank == 0:
+        # (before the dumps below: an RCCL sub-integration may be a view of a buffer the next exchange reuses)
+        sub = last[0]
+        write_outputs(dump_dir, {"profile": pipeline.subint_profile(sub).reshape(-1, lt.npol_out, cfg.nbin, cfg.ndim),
+                                 "hits": sub["hits"], "integration_length": sub["integration_length"],
+                                 "ndat_total": sub["ndat_total"]})
+    last[0] = None
     samples = float((lt.nsamples_in - nsamp0) * lt.in_nchan)          # this rank's own samples (per pol)
     if world > 1:
         t = torch.tensor([elapsed], dtype=torch.float64, device="cuda")
@@ -1119,6 +1165,9 @@ def main():
                     help="short-response geometries (cfg4) through the three-pass kernels instead of the two-pass path (A/B runs)")
     ap.add_argument("--no-fused-fold", action="store_true",
                     help="Detection and Fold as separate operations (detected time series through HBM)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps of the result line's workload, write what its last step delivered (the "
+                         "sub-integration that holds it: profile, hits, ...; search mode: the digitised block) as DIR/<name>.npy")
     args = ap.parse_args()
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -1159,9 +1208,9 @@ def main():
         if world > 1:
             sys.exit("bench.py: the %s workload runs as independent replicas; use --gpus 1" % name)
         fn = {"cfg5": bench_search_mode, "cfg5c": bench_search_coherent, "fold": bench_fold_only}[name]
-        return finish(fn(args, WORKLOADS[name], torch))
+        return finish(fn(args, WORKLOADS[name], torch, dump_dir=args.dump_outputs))
     ctx = (torch, dist, rank, world, local_rank, single)
-    out = run_fold_workload(name, args, *ctx, steps=args.steps, warmup=args.warmup, full=True)
+    out = run_fold_workload(name, args, *ctx, steps=args.steps, warmup=args.warmup, full=True, dump_dir=args.dump_outputs)
     if args.workload is None and not args.no_companions and not (args.parts_per_block or args.max_parts):
         # ---- companions of the default line (the scaling curve is quoted on the sub-band sharded
         #      configuration; every BASELINE configuration gets a driver-run number) ---------------------------------

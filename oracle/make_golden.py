@@ -6,6 +6,8 @@
   chirp_kat.npz     first/last 8 phasors per channel + impulse_pos/neg for 3 configurations (oracle)
   e2e_small.npz     tiny end-to-end case: raw bytes, hits, folded sums in float64 and float32 (oracle)
   vela_polyco.json  the numeric content of the reference's Benchmark/vela.polyco (a data file)
+  ref_c_kat.npz     outputs of the same reference C files on the inputs of tests/test_oracle.py
+  header.dada       the reference's Benchmark/header.dada (a data file)
 """
 import ctypes as C
 import json
@@ -74,7 +76,40 @@ def main():
     pc = "/root/reference/Benchmark/vela.polyco"
     if os.path.exists(pc):
         json.dump({"text": open(pc).read()}, open(os.path.join(GOLD, "vela_polyco.json"), "w"))
+    reference_known_answers(ref)
     print("golden fixtures written to", GOLD)
+
+
+def reference_known_answers(ref):
+    """ref_c_kat.npz: what the reference's own cross_detect.c / stokes_detect.c / optimize_fft.c return on the inputs of
+    tests/test_oracle.py (detection with output stride 1 and 4; optimal_fft_length over its nbad x nmax grid, 2^64-1 where it
+    fails), and header.dada: a byte copy of the reference's Benchmark/header.dada (a data file)."""
+    rng = np.random.default_rng(11)
+    ndat = 257
+    p = rng.standard_normal(2 * ndat).astype(np.float32)
+    q = rng.standard_normal(2 * ndat).astype(np.float32)
+    out = {"p": p, "q": q}
+    for name, fn in (("cross", ref.cross_detect), ("stokes", ref.stokes_detect)):
+        for span in (1, 4):
+            buf = np.zeros(4 * ndat, np.float32)
+            if span == 1:
+                r = buf.reshape(4, ndat)
+                fn(ndat, fp(p), fp(q), fp(r[0]), fp(r[1]), fp(r[2]), fp(r[3]), 1)
+                out["%s_span1" % name] = r
+            else:
+                fn(ndat, fp(p), fp(q), fp(buf[0:]), fp(buf[1:]), fp(buf[2:]), fp(buf[3:]), 4)
+                out["%s_span4" % name] = buf.reshape(ndat, 4).T.copy()
+    ref.optimal_fft_length.restype = C.c_uint64
+    ref.optimal_fft_length.argtypes = [C.c_uint64, C.c_uint64, C.c_char]
+    out["fft_nbad"] = np.array([54, 844, 1687, 1909, 6735, 14567, 1, 2, 3, 1024], np.uint64)
+    out["fft_nmax"] = np.array([0, 1 << 16, 1 << 20], np.uint64)
+    out["fft_nopt"] = np.array([[ref.optimal_fft_length(int(nb), int(nm), b"\0") for nm in out["fft_nmax"]]
+                                for nb in out["fft_nbad"]], np.uint64)
+    np.savez(os.path.join(GOLD, "ref_c_kat.npz"), **out)
+    hdr = "/root/reference/Benchmark/header.dada"
+    if os.path.exists(hdr):
+        with open(hdr, "rb") as src, open(os.path.join(GOLD, "header.dada"), "wb") as dst:
+            dst.write(src.read())
 
 
 if __name__ == "__main__":

@@ -1,8 +1,7 @@
 // FUNCTIONAL MINIATURE of the few PSRCHIVE / dsp classes the adaptors touch -- test infrastructure, NOT a build of DSPSR.
-// tests/test_host_adaptor.py type-checks dspsr_amd/host/dspsr_amd_engines.h against the REAL reference headers (with
-// tests/psrchive_stub); these miniatures exist so that the same adaptor header can also be COMPILED AND RUN on the GPU box
-// (where /root/reference does not exist): containers that allocate through dsp::Memory, and a Fold that makes the engine
-// calls in the order of Signal/Pulsar/Fold.C.  Every member cites the reference declaration it mirrors.
+// These miniatures let the adaptor header dspsr_amd/host/dspsr_amd_engines.h be COMPILED AND RUN without DSPSR and PSRCHIVE:
+// containers that allocate through dsp::Memory, and a Fold that makes the engine calls in the order of Signal/Pulsar/Fold.C.
+// Every member cites the reference declaration it mirrors.
 #pragma once
 #include <stdarg.h>
 #include <stddef.h>

@@ -49,3 +49,27 @@ def test_default_bench_line_contract():
     for w in d["other_workloads"]:
         assert w["roofline_traffic_ratio"] is not None and w["roofline_traffic_ratio"] >= 1.0, w["workload"]
     assert {w["workload"] for w in d["other_workloads"]} >= {"cfg1", "cfg1opt", "cfg2", "cfg3", "cfg5"}
+
+
+def test_dump_outputs_dtypes_budget_and_fixed_sample(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: float32 stays float32, 8/16-bit samples become float32 and wider integers float64, both
+    exactly; over the byte budget the largest array is cut to the same seeded sample of its elements on every run."""
+    import numpy as np
+    import bench
+    rng = np.random.default_rng(5)
+    arrays = {"profile": rng.standard_normal((8, 4, 64)).astype(np.float32), "hits": rng.integers(0, 2 ** 32, 64, dtype=np.uint32),
+              "digitised": rng.integers(0, 256, 96, dtype=np.uint8), "integration_length": 0.125}
+    bench.write_outputs(str(tmp_path / "all"), arrays)
+    got = {k: np.load(str(tmp_path / "all" / (k + ".npy"))) for k in arrays}
+    assert got["profile"].dtype == np.float32 and np.array_equal(got["profile"], arrays["profile"])
+    assert got["hits"].dtype == np.float64 and np.array_equal(got["hits"], arrays["hits"])
+    assert got["digitised"].dtype == np.float32 and np.array_equal(got["digitised"], arrays["digitised"])
+    assert got["integration_length"].dtype == np.float64 and got["integration_length"] == 0.125
+    monkeypatch.setattr(bench, "DUMP_OUTPUTS_BYTES", 4096)
+    for run in ("a", "b"):
+        bench.write_outputs(str(tmp_path / run), arrays)
+    sizes = {k: os.path.getsize(str(tmp_path / "a" / (k + ".npy"))) - 128 for k in arrays}     # 128-byte .npy header
+    assert sum(sizes.values()) <= 4096 and sizes["hits"] == 64 * 8 and sizes["digitised"] == 96 * 4
+    a, b = (np.load(str(tmp_path / r / "profile.npy")) for r in ("a", "b"))
+    assert np.array_equal(a, b) and a.size == (4096 - 64 * 8 - 96 * 4 - 8) // 4
+    assert np.isin(a, arrays["profile"]).all() and len(np.unique(a)) == a.size                  # distinct elements of the output

@@ -1,14 +1,11 @@
 """The C++ adaptor header (dspsr_amd/host/dspsr_amd_engines.h) that binds the C-ABI to dsp::Filterbank::Engine /
 dsp::Convolution::Engine / dsp::Detection::Engine / dsp::Fold::Engine / dsp::Memory / dsp::TimeSeries::Engine.
 
-  * build container (where /root/reference exists): every adaptor is type-checked and INSTANTIATED against the REAL
-    reference headers (Kernel/Classes/dsp, Signal/General/dsp, Signal/Pulsar/dsp); only the PSRCHIVE headers those include
-    (Reference.h, Error.h, MJD.h, ... -- an external dependency that is not in the image) are declaration-only stubs from
-    tests/psrchive_stub.  A missing pure virtual or a drifted signature fails the compile.
-  * everywhere: tests/host_adaptor_driver.cpp is built against the functional miniatures of tests/host_mock and run; on a
-    GPU (`-m gpu`) it drives the adaptors in the reference's call order -- Filterbank setup/perform, Detection in place,
-    Fold prepare_output -> set_nbin -> set_ndat -> set_bins -> fold -> synch -> zero -- and checks the sums bit for bit
-    against the CPU loop of Fold.C:835-891; without a device it must stop cleanly (exit code 77).
+tests/host_adaptor_driver.cpp is built against the functional miniatures of tests/host_mock (the reference's interfaces
+restated, virtual signatures as declared there) and run; on a GPU (`-m gpu`) it drives the adaptors in the reference's call
+order -- Filterbank setup/perform, Detection in place, Fold prepare_output -> set_nbin -> set_ndat -> set_bins -> fold ->
+synch -> zero -- and checks the sums bit for bit against the CPU loop of Fold.C:835-891; without a device it must stop
+cleanly (exit code 77).
 """
 import os
 import subprocess
@@ -16,54 +13,6 @@ import subprocess
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-REF = "/root/reference"
-
-INSTANTIATE = r'''
-#include "dspsr_amd_engines.h"
-// complete implementations of the reference's abstract interfaces: instantiation fails to compile otherwise
-dsp::Memory* a (dspsr_amd_ctx* c) { return new HIP::DeviceMemory (c); }
-dsp::TimeSeries::Engine* b (dspsr_amd_ctx* c) { return new HIP::TimeSeriesEngine (c); }
-dsp::Filterbank::Engine* d (dspsr_amd_ctx* c) { return new HIP::FilterbankEngine (c); }
-dsp::Convolution::Engine* e (dspsr_amd_ctx* c) { return new HIP::ConvolutionEngine (c); }
-dsp::Detection::Engine* f (dspsr_amd_ctx* c) { return new HIP::DetectionEngine (c); }
-dsp::Fold::Engine* g (dspsr_amd_ctx* c) { return new HIP::FoldEngine (c); }
-dsp::TScrunch::Engine* ts (dspsr_amd_ctx* c) { return new HIP::TScrunchEngine (c); }
-dsp::FScrunch::Engine* fs (dspsr_amd_ctx* c) { return new HIP::FScrunchEngine (c); }
-// deferred mode: the adaptors of one pipeline thread share a HIP::Chain; the raw-input hand-over against the REAL dsp::BitSeries
-#include "dsp/BitSeries.h"
-void h (dspsr_amd_ctx* c, const dsp::BitSeries* host, dsp::BitSeries* device)
-{
-  HIP::Chain* chain = new HIP::Chain (c);
-  chain->set_deferred (true);
-  HIP::FilterbankEngine* fb = new HIP::FilterbankEngine (c, chain);
-  dsp::Detection::Engine* det = new HIP::DetectionEngine (c, chain);
-  dsp::Fold::Engine* fold = new HIP::FoldEngine (c, chain);
-  dsp::TimeSeries::Engine* ts = new HIP::TimeSeriesEngine (c, chain);
-  HIP::transfer_bitseries (c, host, device, fb, DSPSR_AMD_RAW_GENERIC, 1.0f);
-  (void) det; (void) fold; (void) ts;
-}
-'''
-
-
-def test_adaptors_type_check_against_the_real_reference_headers(tmp_path):
-    if not os.path.isdir(os.path.join(REF, "Signal", "Pulsar", "dsp")):
-        pytest.skip("reference tree not present (GPU box)")
-    src = tmp_path / "t.cpp"
-    src.write_text(INSTANTIATE)
-    inc = [os.path.join(ROOT, "tests", "psrchive_stub"), os.path.join(REF, "Kernel", "Classes"),
-           os.path.join(REF, "Signal", "General"), os.path.join(REF, "Signal", "Pulsar"), os.path.join(REF, "Signal", "Statistics"),
-           os.path.join(ROOT, "dspsr_amd", "host"), os.path.join(ROOT, "include")]
-    cmd = ["g++", "-std=c++11", "-fsyntax-only", "-w"] + [x for i in inc for x in ("-I", i)] + [str(src)]
-    p = subprocess.run(cmd, capture_output=True, text=True)
-    assert p.returncode == 0, p.stderr[-4000:]
-    # the check is real: the same file must FAIL when an interface method is missing from an adaptor
-    broken = tmp_path / "engines_broken"
-    broken.mkdir()
-    text = open(os.path.join(ROOT, "dspsr_amd", "host", "dspsr_amd_engines.h")).read()
-    assert "    uint64_t get_bin_hits (int ibin) { return nbin_hits[ibin]; }\n" in text
-    (broken / "dspsr_amd_engines.h").write_text(text.replace("    uint64_t get_bin_hits (int ibin) { return nbin_hits[ibin]; }\n", ""))
-    cmd2 = [c if c != os.path.join(ROOT, "dspsr_amd", "host") else str(broken) for c in cmd]
-    assert subprocess.run(cmd2, capture_output=True, text=True).returncode != 0
 
 
 def _build_driver(tmp_path):

@@ -1,15 +1,12 @@
 """SURVEY 8f-3, reader side: the PhaseSeries hand-off file written by pipeline.write_phase_series is read back by the C++
-reader a DSPSR maintainer would call before Archiver::unload (dspsr_amd/host/dspsr_amd_phase_series_io.h):
-  * the plain-C++ layer is compiled and run here on a file written by the product (checksums must agree);
-  * the dsp::PhaseSeries layer is type-checked against the REAL reference headers (build container only)."""
+reader a DSPSR maintainer would call before Archiver::unload (dspsr_amd/host/dspsr_amd_phase_series_io.h): the plain-C++
+layer is compiled and run here on a file written by the product (checksums must agree)."""
 import os
 import subprocess
 
 import numpy as np
-import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-REF = "/root/reference"
 
 DRIVER = r'''
 #include "dspsr_amd_phase_series_io.h"
@@ -56,16 +53,3 @@ def test_reader_reads_what_the_product_writes(tmp_path):
     # a truncated file is an error, not garbage
     open(str(tmp_path / "bad.ps"), "wb").write(open(path, "rb").read()[:5000])
     assert subprocess.run([str(exe), str(tmp_path / "bad.ps")], capture_output=True).returncode == 1
-
-
-def test_phase_series_loader_type_checks_against_the_reference(tmp_path):
-    if not os.path.isdir(os.path.join(REF, "Signal", "Pulsar", "dsp")):
-        pytest.skip("reference tree not present (GPU box)")
-    src = tmp_path / "t.cpp"
-    src.write_text('#include "dsp/PhaseSeries.h"\n#include "dspsr_amd_phase_series_io.h"\n'
-                   'void f (dsp::PhaseSeries* p) { HIP::load_phase_series ("x", p); }\n')
-    inc = [os.path.join(ROOT, "tests", "psrchive_stub"), os.path.join(REF, "Kernel", "Classes"), os.path.join(REF, "Signal", "General"),
-           os.path.join(REF, "Signal", "Pulsar"), os.path.join(ROOT, "dspsr_amd", "host")]
-    p = subprocess.run(["g++", "-std=c++11", "-fsyntax-only", "-w"] + [x for i in inc for x in ("-I", i)] + [str(src)],
-                       capture_output=True, text=True)
-    assert p.returncode == 0, p.stderr[-3000:]

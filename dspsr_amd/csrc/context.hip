@@ -131,6 +131,36 @@ __global__ __launch_bounds__(256) void k_copy_fpt(float* __restrict__ to, const 
   }
 }
 
+// Does any of the nchan x npol rows of nfloat floats at `to` share a float with one at `from`?  Exact when both sides have the
+// same strides (the carry moves inside one buffer): row (c, p) of `to` and row (c', p') of `from` meet when
+// |d + dc*cs + dp*ps| < nfloat, d = from - to, for some |dc| < nchan, |dp| < npol -- for each dp, the dc nearest the window.
+// Other strides: the spans [first float, last float] of the two sides must be disjoint.
+static bool fpt_rows_overlap(const float* to, uint64_t tcs, uint64_t tps, const float* from, uint64_t fcs, uint64_t fps,
+                             uint32_t nchan, uint32_t npol, uint64_t nfloat)
+{
+  typedef __int128 i128;
+  if (nchan == 1) tcs = fcs = 0;                                 // (strides of a dimension of one are not used)
+  if (npol == 1) tps = fps = 0;
+  const i128 fsz = (i128)sizeof(float);
+  const i128 d = ((i128)(uintptr_t)from - (i128)(uintptr_t)to) / fsz;   // (rows of floats: both pointers are float aligned)
+  const i128 n = (i128)nfloat;
+  const i128 tspan = (i128)(nchan - 1) * tcs + (i128)(npol - 1) * tps + n, fspan = (i128)(nchan - 1) * fcs + (i128)(npol - 1) * fps + n;
+  if (d >= tspan || -d >= fspan) return false;                   // disjoint spans
+  if (tcs != fcs || tps != fps) return true;
+  auto floor_div = [](const i128 a, const i128 b) { return a >= 0 ? a / b : -((-a + b - 1) / b); };     // (b > 0)
+  for (i128 dp = -(i128)(npol - 1); dp <= (i128)(npol - 1); dp++) {
+    const i128 x = d + dp * (i128)tps;                          // need -n < x + dc*cs < n
+    if (tcs == 0) {
+      if (x > -n && x < n) return true;
+      continue;
+    }
+    i128 dc = floor_div(-n - x, (i128)tcs) + 1;                  // smallest dc with x + dc*cs > -n
+    if (dc < -(i128)(nchan - 1)) dc = -(i128)(nchan - 1);
+    if (dc <= (i128)(nchan - 1) && x + dc * (i128)tcs < n) return true;
+  }
+  return false;
+}
+
 extern "C" int dspsr_amd_copy_fpt(dspsr_amd_ctx* ctx, float* to_dev, uint64_t to_chan_stride, uint64_t to_pol_stride,
                                   const float* from_dev, uint64_t from_chan_stride, uint64_t from_pol_stride,
                                   uint32_t nchan, uint32_t npol, uint64_t nfloat)
@@ -139,6 +169,12 @@ extern "C" int dspsr_amd_copy_fpt(dspsr_amd_ctx* ctx, float* to_dev, uint64_t to
   if (!nfloat || !nchan || !npol) return DSPSR_AMD_OK;
   if (npol > 65535 || nchan > 65535)
     return ctx_fail(ctx, DSPSR_AMD_EINVAL, "dspsr_amd_copy_fpt: nchan=%u npol=%u exceed the grid limits", nchan, npol);
+  if (fpt_rows_overlap(to_dev, to_chan_stride, to_pol_stride, from_dev, from_chan_stride, from_pol_stride, nchan, npol, nfloat))
+    return ctx_fail(ctx, DSPSR_AMD_EINVAL, "dspsr_amd_copy_fpt: rows of `to` overlap rows of `from` (to - from = %lld floats, strides "
+                    "%llu/%llu and %llu/%llu, %llu floats per row): the parallel copy would read what it writes",
+                    (long long)(((intptr_t)to_dev - (intptr_t)from_dev) / (intptr_t)sizeof(float)), (unsigned long long)to_chan_stride,
+                    (unsigned long long)to_pol_stride, (unsigned long long)from_chan_stride, (unsigned long long)from_pol_stride,
+                    (unsigned long long)nfloat);
   uint64_t bx = (nfloat / 4 + 255) / 256;
   if (bx < 1) bx = 1;
   if (bx > 64) bx = 64;

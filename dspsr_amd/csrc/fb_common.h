@@ -142,14 +142,20 @@ DEV void ts_stage(float* __restrict__ stg, const FbOut& out, const TsPart& tp, c
 // carry of row `row` (channel * npol_out + q), read past the L1 (the previous part's store of this workgroup went to L2)
 DEV float ts_carry_load(const FbOut& out, const uint32_t row) { return __hip_atomic_load(out.ts_carry + row, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 // The scrunch of one staged tile: nrow = channels * npol_out staged rows; chan_of(row / npo) = output channel (without chan0).
-// Thread w < nrow takes the FIRST group of row w (the one that may continue the carry, pre-loaded into `carry_pre` by that same
-// thread), the others the remaining (row, group) items.  Sums are sequential in time: out = in[0]; out += in[1]; ...
-template <class ChanOf>
-DEV void ts_reduce(const float* __restrict__ stg, const FbOut& out, const TsPart& tp, const uint32_t nrow, const float carry_pre,
-                   const bool have_pre, const uint32_t tid, const uint32_t nthr, ChanOf&& chan_of)
+// Item w < nrow is the FIRST group of row w (the one that may continue the carry), the others the remaining (row, group) items;
+// thread tid takes items tid, tid + nthr, ...  The open group's carry is both read (first group) and replaced (last group) here,
+// by different threads and waves: so ts_reduce reads no carry.  Item w = tid + k * nthr < nrow takes carry_pre[k], which the
+// caller loaded from row w's carry (when tp.phi) in front of the barrier that precedes this call -- every carry of the tile is read
+// before any is replaced.  The caller guarantees nrow <= NPRE * nthr.  Sums are sequential in time: out = in[0]; out += in[1]; ...
+template <int NPRE, class ChanOf>
+DEV void ts_reduce(const float* __restrict__ stg, const FbOut& out, const TsPart& tp, const uint32_t nrow, const float (&carry_pre)[NPRE],
+                   const uint32_t tid, const uint32_t nthr, ChanOf&& chan_of)
 {
   const uint32_t sf = out.ts_sf, G = out.ts_G, npo = out.state == DSPSR_AMD_PPQQ ? 2u : 1u;
   const uint32_t ng1 = tp.ng - 1, nitem = nrow * tp.ng;
+  float cp[NPRE];                                                  // cp[0] = carry_pre[k] in iteration k (shifted down: static indices only)
+#pragma unroll
+  for (int q = 0; q < NPRE; q++) cp[q] = carry_pre[q];
   for (uint32_t w = tid; w < nitem; w += nthr) {
     uint32_t row, gq;
     if (w < nrow) { row = w; gq = 0; }
@@ -158,8 +164,13 @@ DEV void ts_reduce(const float* __restrict__ stg, const FbOut& out, const TsPart
     uint32_t r = gq == 0 ? tp.phi : 0;
     const float* __restrict__ src = stg + (row * sf) * G + gq;
     float acc;
-    if (gq == 0 && tp.phi) acc = (have_pre && w == tid) ? carry_pre : ts_carry_load(out, (out.chan0 + chan_of(row / npo)) * npo + row % npo);
-    else { acc = src[r * G]; r++; }
+    if (gq == 0 && tp.phi) {
+      // (NPRE 1: nrow <= nthr, so w == tid here and the load is never taken -- the form of the earlier code, which keeps the
+      //  two-stage kernels' instructions as they were)
+      acc = (NPRE > 1 || w == tid) ? cp[0] : ts_carry_load(out, (out.chan0 + chan_of(row / npo)) * npo + row % npo);
+    } else {
+      acc = src[r * G]; r++;
+    }
     for (; r + 4 <= r1; r += 4) {                                  // loads ahead, adds in time order
       const float a0 = src[r * G], a1 = src[(r + 1) * G], a2 = src[(r + 2) * G], a3 = src[(r + 3) * G];
       acc = __fadd_rn(acc, a0); acc = __fadd_rn(acc, a1); acc = __fadd_rn(acc, a2); acc = __fadd_rn(acc, a3);
@@ -168,6 +179,8 @@ DEV void ts_reduce(const float* __restrict__ stg, const FbOut& out, const TsPart
     const uint32_t chan = out.chan0 + chan_of(row / npo), q = row % npo;
     if (r1 < sf) out.ts_carry[chan * npo + q] = acc;                // the group is still open: the next part (or call) continues it
     else out.base[chan * out.chan_stride + q * out.pol_stride + tp.ofirst + gq] = acc;
+#pragma unroll
+    for (int j = 0; j + 1 < NPRE; j++) cp[j] = cp[j + 1];
   }
 }
 

@@ -308,7 +308,7 @@ __global__ __launch_bounds__(512) void k_inv_chan(const FbGeom g, const cf* __re
     const uint32_t tile = item.tile;
     const uint64_t part = part0 + item.lp;
     [[maybe_unused]] TsPart tsp = {0, 0, 0, 0};
-    [[maybe_unused]] float ts_carry_pre = 0.f;
+    [[maybe_unused]] float ts_carry_mid = 0.f;      // SEARCH, two or more stages: the carry of row tid, loaded in mid()
     if constexpr (SEARCH) tsp = ts_part(out, (uint32_t)part, g.nkeep);
     // FOLD: the tile's detected samples are staged UNPADDED, channel after channel (16 bytes per sample), so that the
     // samples of a phase bin's run are read at constant offsets from one base (the padded image cost four integer
@@ -438,9 +438,10 @@ __global__ __launch_bounds__(512) void k_inv_chan(const FbGeom g, const cf* __re
       if constexpr (SEARCH) {
         // the open output sample's partial sum (written by this workgroup at the end of the previous part, two barriers ago)
         const uint32_t npo = out.state == DSPSR_AMD_PPQQ ? 2u : 1u;
-        // (behind the tile's first barrier: that store has been waited for; single-stage transforms load it in ts_reduce)
+        // (behind the tile's first barrier: that store has been waited for.  Single-stage transforms load theirs behind wgfft: their
+        //  mid(1) runs in front of the only barrier that orders the previous tile's carry stores)
         if (FftPlan<LOGF>::NS >= 2 && phase == 2 && tsp.phi && tid < (npo << logT3))
-          ts_carry_pre = ts_carry_load(out, (out.chan0 + tile * T3 + tid / npo) * npo + tid % npo);
+          ts_carry_mid = ts_carry_load(out, (out.chan0 + tile * T3 + tid / npo) * npo + tid % npo);
       }
       if constexpr (PRE) {
         // only when the part's plan entries are in LDS: the accumulator's address then depends on an LDS read alone.  With
@@ -459,9 +460,26 @@ __global__ __launch_bounds__(512) void k_inv_chan(const FbGeom g, const cf* __re
     wgfft<LOGF, +1, EPI != 0>(lds, ltw_off, tid, logT, x, store, mid);
     FB_ST(3, 3);
     if constexpr (SEARCH) {
-      __syncthreads();                       // the tile's detected samples are staged
-      const uint32_t npo = out.state == DSPSR_AMD_PPQQ ? 2u : 1u;
-      ts_reduce((const float*)lds, out, tsp, npo << logT3, ts_carry_pre, FftPlan<LOGF>::NS >= 2, tid, blockDim.x, [&](const uint32_t slo) { return tile * T3 + slo; });
+      const uint32_t npo = out.state == DSPSR_AMD_PPQQ ? 2u : 1u, nrow = npo << logT3;
+      // the carries of the rows w = tid + k * blockDim.x of this tile (ts_reduce).  nrow / blockDim.x = 16 npo / freq_res
+      // (blockDim.x = freq_res * T / 32, nrow = npo * T / 2): one row per thread from freq_res 32 on (two or more stages), up to four
+      // below (freq_res 8 with PPQQ; fb_search_fits refuses more)
+      constexpr int TS_NPRE = FftPlan<LOGF>::NS >= 2 ? 1 : 4;
+      float ts_carry_pre[TS_NPRE] = {};
+      ts_carry_pre[0] = ts_carry_mid;
+      if constexpr (FftPlan<LOGF>::NS < 2) {
+        // single stage: behind wgfft's STAGED barrier (the previous tile's carry stores are done) and in front of the barrier
+        // below (behind which ts_reduce stores this tile's): all rows of the tile, up to TS_NPRE per thread
+        if (tsp.phi) {
+#pragma unroll
+          for (int k = 0; k < TS_NPRE; k++) {
+            const uint32_t w = tid + k * blockDim.x;
+            if (w < nrow) ts_carry_pre[k] = ts_carry_load(out, (out.chan0 + tile * T3 + w / npo) * npo + w % npo);
+          }
+        }
+      }
+      __syncthreads();                       // the tile's detected samples are staged; every carry of the tile has been read
+      ts_reduce((const float*)lds, out, tsp, nrow, ts_carry_pre, tid, blockDim.x, [&](const uint32_t slo) { return tile * T3 + slo; });
       // (the barrier in front of the next tile's first exchange write also ends this read phase)
     }
     if constexpr (FOLD) {

@@ -376,7 +376,8 @@ __global__ __launch_bounds__(512) void k_rows_inv(const FbGeom g, const cf* __re
     const uint32_t tile = item.tile;
     const uint64_t part = part0 + item.lp;
     [[maybe_unused]] TsPart tsp = {0, 0, 0, 0};
-    [[maybe_unused]] float ts_carry_pre = 0.f;
+    // SEARCH: the carry of row tid (ts_reduce).  nrow = npo * Fb <= 32 rows, within the 512 threads: item w < nrow is thread w's first
+    [[maybe_unused]] float ts_carry_pre[1] = {0.f};
     if constexpr (SEARCH) tsp = ts_part(out, (uint32_t)part, g.nkeep);
     const uint32_t fcr = (16u >> logT3) & 15u, fcs_r = ((g.nkeep + 15u - fcr) & ~15u) + fcr;
     const uint32_t fcs = ((2u * fcs_r) << logT3) <= PTS * blockDim.x ? fcs_r : g.nkeep;
@@ -490,7 +491,7 @@ __global__ __launch_bounds__(512) void k_rows_inv(const FbGeom g, const cf* __re
         // exchange in front of the transform has passed two barriers since)
         const uint32_t npo = out.state == DSPSR_AMD_PPQQ ? 2u : 1u;
         if (phase == 1 && tsp.phi && tid < (npo << logT3))
-          ts_carry_pre = ts_carry_load(out, (out.chan0 + chan_of(tile, tid / npo)) * npo + tid % npo);
+          ts_carry_pre[0] = ts_carry_load(out, (out.chan0 + chan_of(tile, tid / npo)) * npo + tid % npo);
       }
       if constexpr (PRE) {
         if (phase == 2 && in_lds && tid < (f_nact << logT3)) {
@@ -513,7 +514,7 @@ __global__ __launch_bounds__(512) void k_rows_inv(const FbGeom g, const cf* __re
     if constexpr (SEARCH) {
       __syncthreads();                       // the tile's detected samples are staged
       const uint32_t npo = out.state == DSPSR_AMD_PPQQ ? 2u : 1u;
-      ts_reduce((const float*)lds, out, tsp, npo << logT3, ts_carry_pre, true, tid, blockDim.x, [&](const uint32_t slo) { return chan_of(tile, slo); });
+      ts_reduce((const float*)lds, out, tsp, npo << logT3, ts_carry_pre, tid, blockDim.x, [&](const uint32_t slo) { return chan_of(tile, slo); });
     }
     if constexpr (FOLD) {
       __syncthreads();

@@ -1143,6 +1143,7 @@ static bool fb_search_fits(const dspsr_amd_filterbank* fb, uint32_t npo, uint32_
   const uint32_t G = (uint32_t)ngmax | 1u;
   const uint64_t floats = ((uint64_t)npo << g.logT3) * sf * G;
   if (floats > 2ull * fb->nt3 * PTS) return false;                       // (the buffer's padding is slack)
+  if (((uint64_t)npo << g.logT3) > 4ull * fb->nt3) return false;         // a thread reads at most four rows' carries (k_inv_chan TS_NPRE)
   if (((uint64_t)g.nkeep + sf) * sf >= (1ull << 32)) return false;       // t / sf by multiplication (ts_magic)
   if (G_out) *G_out = G;
   return true;

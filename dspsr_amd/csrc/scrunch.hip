@@ -96,9 +96,9 @@ extern "C" int dspsr_amd_tscrunch_fpt(dspsr_amd_ctx* ctx, const float* in_dev, u
   if (bx < 1) bx = 1;
   hipLaunchKernelGGL(k_tscrunch_fpt, dim3((uint32_t)bx, (uint32_t)(rows > 65535 ? 65535 : rows)), dim3(256), 0, ctx->stream, in_dev, in_chan_stride,
                      in_pol_stride, out_dev, out_chan_stride, out_pol_stride, npol, ndim, ndat_in, sfactor, *carry_count, carry_dev, *nout, rem, (uint32_t)rows);
-  *carry_count = rem;
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return ctx_fail(ctx, DSPSR_AMD_EHIP, "dspsr_amd_tscrunch_fpt: %s", hipGetErrorString(e));
+  *carry_count = rem;                      // (only once the launch is in: a failed call leaves the caller's carry state as it was)
   return DSPSR_AMD_OK;
 }
 

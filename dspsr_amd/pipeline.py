@@ -23,6 +23,19 @@ from .engine import (Context, ConvolutionEngine, Dedispersion, DspsrAmdError, Fi
                      tfp_filterbank, tscrunch_fpt)
 
 
+def move_tail_fpt(ctx, buf, dst, src, n, unit=1):
+    """InputBuffering's carry inside one buffer: samples [src, src + n) of the rows of `buf` ([nchan][npol][nsample * unit]) go to
+    [dst, dst + n), dst < src.  The ranges overlap when fewer samples were consumed than are carried (a short block of -K):
+    copy_data_fpt is a parallel copy and refuses overlapping rows, so the move is made in ascending, stream-ordered chunks of at
+    most src - dst samples -- each chunk lands on samples that earlier chunks have already moved."""
+    if not 0 <= dst < src:
+        raise DspsrAmdError("dspsr_amd.move_tail_fpt: destination %d must lie in front of the source %d" % (dst, src))
+    shift = src - dst
+    for k in range(0, n, shift):
+        m = min(shift, n - k)
+        copy_data_fpt(ctx, buf[:, :, (dst + k) * unit:(dst + k + m) * unit], buf[:, :, (src + k) * unit:(src + k + m) * unit])
+
+
 @dataclass
 class Config:
     """The dspsr command-line options that matter on this path (dspsr.C:207-510)."""
@@ -1105,7 +1118,7 @@ class LoadToFold:
         # InputBuffering::set_next_start(output_ndat): the unshifted tail goes in front of the next block
         carry = nin - nout
         if carry:
-            copy_data_fpt(self.ctx, self.detected[:, :, (head - carry) * nd:head * nd], rows[:, :, nout * nd:])
+            move_tail_fpt(self.ctx, self.detected, head - carry, off + nout, carry, nd)
         self.sd_carried = carry
         self.ndat_out += nout
         self.nsamples_in += npart * self.nsamp_step
@@ -1604,7 +1617,7 @@ class LoadToFilCoherent:
             nout, self.carry_count = tscrunch_fpt(self.ctx, det, self.scrunched, ts, self.carry, self.carry_count)
         if rows is not None:
             if carry:
-                copy_data_fpt(self.ctx, self.detected[:, :, head - carry:head], rows[:, :, nd:])
+                move_tail_fpt(self.ctx, self.detected, head - carry, off + nd, carry)
             self.sd_carried = carry
         return self.scrunched[:, :, :nout]
 

@@ -63,7 +63,9 @@ int dspsr_amd_copy(dspsr_amd_ctx* ctx, void* dst, const void* src, size_t nbytes
  * Kernel/Classes/TimeSeriesCUDA.cu:20-29,75-200): device-to-device copy of `nfloat` floats of every
  * (channel, polarisation) row -- the overlap carry-over of dsp::InputBuffering (InputBuffering.C:35-126) and
  * TimeSeries::prepend.  Strides in floats between channel rows / polarisation rows; the row pointers already
- * include the start sample.  Rows of `to` and `from` must not overlap. */
+ * include the start sample.  Rows of `to` and `from` must not overlap: DSPSR_AMD_EINVAL (with a message, nothing launched) when
+ * a row of `to` shares a float with a row of `from` -- decided exactly when both sides have the same strides (a move inside one
+ * buffer), and by the spans [first row start, last row end) of the two sides otherwise. */
 int dspsr_amd_copy_fpt(dspsr_amd_ctx* ctx, float* to_dev, uint64_t to_chan_stride, uint64_t to_pol_stride,
                        const float* from_dev, uint64_t from_chan_stride, uint64_t from_pol_stride,
                        uint32_t nchan, uint32_t npol, uint64_t nfloat);

@@ -254,6 +254,37 @@ def test_copy_data_fpt(gpu):
         assert torch.equal(dst[:, :, :n], src[:, :, off:off + n]) and float(dst[:, :, n:].abs().max()) == 0.0
 
 
+def test_copy_data_fpt_refuses_overlapping_rows(gpu):
+    """copy_fpt is a parallel copy: rows of `to` that share floats with rows of `from` would read what it writes.  Refused with
+    DSPSR_AMD_EINVAL and a message, nothing launched -- for the same rows shifted by less than their length, and for row (c, p)
+    reaching into row (c, p + 1) of the other side.  Adjacent rows of one buffer are no overlap: copied."""
+    dspsr_amd, ctx = gpu
+    lib = dspsr_amd.lib
+    nchan, npol, nrow = 3, 2, 1000
+    flat = torch.randn(nchan * npol * nrow + 256, device="cuda")           # (rows reaching past the last one stay in the allocation)
+    base = flat[:nchan * npol * nrow].clone().view(nchan, npol, nrow)
+    buf = flat[:nchan * npol * nrow].view(nchan, npol, nrow)
+    tail = flat[nchan * npol * nrow:].clone()
+    cs, ps = buf.stride(0), buf.stride(1)
+    p = buf.data_ptr()
+    for to_off, from_off, n in ((0, 200, 300), (200, 0, 300), (950, 0, 100), (0, 950, 100), (5, 5, 10)):
+        rc = lib.dspsr_amd_copy_fpt(ctx.handle, p + 4 * to_off, cs, ps, p + 4 * from_off, cs, ps, nchan, npol, n)
+        assert rc == dspsr_amd._lib.EINVAL, (to_off, from_off, n)
+        assert "overlap" in lib.dspsr_amd_last_error(ctx.handle).decode()
+    with pytest.raises(dspsr_amd.DspsrAmdError, match="overlap"):
+        dspsr_amd.copy_data_fpt(ctx, buf[:, :, 100:400], buf[:, :, 399:699])
+    torch.cuda.synchronize()
+    assert torch.equal(buf, base) and torch.equal(flat[nchan * npol * nrow:], tail)          # nothing launched
+    for to_off, from_off, n in ((0, 300, 300), (600, 300, 300), (900, 0, 100)):
+        buf.copy_(base)
+        rc = lib.dspsr_amd_copy_fpt(ctx.handle, p + 4 * to_off, cs, ps, p + 4 * from_off, cs, ps, nchan, npol, n)
+        assert rc == 0, (to_off, from_off, n)
+        torch.cuda.synchronize()
+        want = base.clone()
+        want[:, :, to_off:to_off + n] = base[:, :, from_off:from_off + n]
+        assert torch.equal(buf, want), (to_off, from_off, n)
+
+
 def test_edge_cases_empty_and_ragged(oracle, gpu):
     """npart = 0 is a no-op, an empty fold plan leaves the profile untouched, a ragged last block (fewer parts
     than the block size) folds like the oracle, and perform_fold on a four-pass geometry takes the unfused chain."""
@@ -1004,6 +1035,69 @@ def test_pipeline_interchan_dedispersion(oracle, gpu, ndim):
     for b in range(nblocks):                                                 # the first block comes out `total` short
         n = block_out - (total if b == 0 else 0)
         o.fold(det, fobs, fcfg, ps, idat_start=pos, ndat_fold=n)
+        pos += n
+    assert pos == fbd.shape[2] == lt.ndat_out
+    assert np.array_equal(sub["hits"], ps.hits)
+    assert np.abs(prof - ps.data).max() <= 1e-5 * np.abs(ps.data).max()
+    lt.close()
+
+
+@pytest.mark.parametrize("ndim", [4, 2])
+def test_pipeline_interchan_dedispersion_short_blocks(oracle, gpu, ndim):
+    """dspsr -K over blocks of (1, 1, 3, 1, 2) parts: blocks of fewer kept samples than the total delay -- the first emits nothing, the
+    second moves the carried tail by less than its length (old and new places overlap), and so does the fourth behind a full
+    block.  Hits equal to, and the profile within 1e-5 of, the oracle folded block by block over the same delayed stream."""
+    dspsr_amd, _ = gpu
+    from dspsr_amd import pipeline, synth
+    o = oracle
+    freq, bw, tsamp, dm, period, nchan, nbin = 1382.0, -16.0, 1.0 / 32.0, 30.0, 0.004, 16, 64
+    blocks = (1, 1, 3, 1, 2)
+    cfg = pipeline.Config(nchan=nchan, dispersion_measure=dm, nbin=nbin, folding_period=period, ndim=ndim,
+                          parts_per_block=3, max_parts=2, interchan_dedispersion=True)
+    info = pipeline.InputInfo(centre_frequency=freq, bandwidth=bw, tsamp_us=tsamp, machine="DADA")
+    lt = pipeline.LoadToFold(cfg, info, device=0, stream=torch.cuda.current_stream().cuda_stream)
+    total = lt.sample_delay.total_delay
+    assert not lt.fused_fold and total > 0
+    # samples emitted per block (SampleDelay: input less the total delay), and the edges this case exists for
+    carried, nouts, short, silent = 0, [], False, False
+    for n in blocks:
+        nin = carried + n * lt.nkeep
+        nouts.append(max(0, nin - total))
+        short |= 0 < carried and n * lt.nkeep < min(nin, total)     # the tail moves by less than its length
+        silent |= nin < total                                        # nothing emitted, the whole input carried
+        carried = min(nin, total)
+    assert short and silent and 1 in blocks and lt.nkeep < total
+    step = lt.nsamp_step
+    nparts = sum(blocks)
+    raw = synth.voltages(nparts * step + lt.nsamp_overlap, freq, bw, tsamp, dm, period)
+    d_raw = torch.from_numpy(raw).cuda()
+    p0 = 0
+    for n in blocks:
+        lt.process_block(d_raw[2 * p0 * step: 2 * (p0 * step + n * step + lt.nsamp_overlap)], n)
+        p0 += n
+    lt.finish_subint()
+    lt.synchronize()
+    assert lt.sd_carried == total
+    sub = lt.subints[0]
+    prof = sub["profile_dev"].cpu().numpy().reshape(nchan, 4 // ndim, nbin, ndim)
+    obs = o.Observation(centre_frequency=freq, bandwidth=bw, tsamp_us=tsamp, dispersion_measure=dm)
+    resp = o.Dedispersion()
+    resp.fractional_delay = True
+    resp.match(obs, nchan)
+    plan = o.filterbank_plan(obs, nchan, resp)
+    fb = o.filterbank(o.unpack_8bit(raw, obs), plan, lt.response.kernel, dtype=np.float64)
+    fobs = o.filterbank_output_observation(obs, plan)
+    delays = o.dedispersion_sample_delays(fobs, nchan, fobs.rate)
+    fbd, zero, total_o = o.sample_delay(fb, delays)
+    assert (zero, total_o) == (lt.sample_delay.zero_delay, total)
+    fobs.start_seconds += zero / fobs.rate                                   # SampleDelay.C:159
+    det = o.detect_layout(o.detect_products(fbd, "Coherence"), ndim)
+    ps = o.PhaseSeries(nchan, 4 // ndim, ndim, nbin, data=np.zeros((nchan, 4 // ndim, nbin, ndim), np.float64))
+    fcfg = o.FoldConfig(nbin=nbin, folding_period=period)
+    pos = 0
+    for n in nouts:
+        if n:
+            o.fold(det, fobs, fcfg, ps, idat_start=pos, ndat_fold=n)
         pos += n
     assert pos == fbd.shape[2] == lt.ndat_out
     assert np.array_equal(sub["hits"], ps.hits)

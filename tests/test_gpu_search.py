@@ -197,6 +197,88 @@ def test_perform_search_equals_detection_and_tscrunch_of_the_filterbank_output(o
     fb.close()
 
 
+def _search_parts(nkeep, sf, parts):
+    """TsPart (csrc/fb_common.h ts_part) of every part of a call sequence: (call, phase0, phi, ng, rlast) -- phase0 the carried
+    samples when the call begins, phi the part's first sample within its first scrunch group, ng the groups it touches, rlast the
+    samples it holds of the last one."""
+    out, cc = [], 0
+    for c, npart in enumerate(parts):
+        for p in range(npart):
+            s = cc + p * nkeep
+            phi = s % sf
+            e = phi + nkeep
+            ng = -(-e // sf)
+            out.append((c, cc, phi, ng, e - (ng - 1) * sf))
+        cc = (cc + npart * nkeep) % sf
+    return out
+
+
+def _short_transform_tile(C, M, npo, nkeep, sf):
+    """(threads of the inverse-pass workgroup, staged rows of a tile, fused epilogue fits) of the three-pass geometry of C channels
+    of freq_res M: 2^14-point tiles of M bins x (channel, pol) columns, T3 = min(C, 2^13 / M) channels, 32 points per thread
+    (csrc/filterbank.hip), and the limits of fb_search_fits for this state and factor."""
+    logM = M.bit_length() - 1
+    logT3 = min(C.bit_length() - 1, 13 - logM)
+    nthr = (M << logT3 << 1) // 32
+    nrow = npo << logT3
+    G = ((nkeep + 2 * sf - 2) // sf) | 1
+    fits = nrow * sf * G <= 2 * nthr * 32 and (nkeep + sf) * sf < 2 ** 32 and nrow <= 4 * nthr
+    return nthr, nrow, fits
+
+
+@pytest.mark.parametrize("state_name", ["Intensity", "PPQQ"])
+@pytest.mark.parametrize("C,M,nfilt,sf,parts,maxp", [
+    (512, 16, (2, 1), 3, (5, 3, 7), 2),        # single-stage transform: 2 x 512 staged rows (PPQQ) on 512 threads
+    (512, 16, (2, 1), 5, (3, 5, 1, 7), 3),
+    (512, 16, (2, 1), 7, (7, 5, 3), 4),
+    (512, 16, (4, 4), 9, (5, 3, 7), 2),         # factor longer than a part (nkeep 8): groups span parts and calls
+    (1024, 8, (2, 1), 3, (5, 3, 7), 2),         # freq_res 8: up to four rows per thread (PPQQ: 2048 rows on 512 threads)
+    (1024, 8, (1, 1), 5, (3, 7, 1, 5), 3),
+    (1024, 8, (2, 2), 5, (7, 3, 5), 2),         # factor longer than a part (nkeep 4)
+    (256, 32, (5, 4), 7, (5, 3, 7), 2),         # two stages: as many rows as threads (PPQQ)
+    (128, 64, (9, 6), 5, (3, 5, 7), 2),
+])
+def test_perform_search_short_transforms_carry_the_open_group(oracle, gpu, state_name, C, M, nfilt, sf, parts, maxp):
+    """The fused search epilogue at freq_res 8 ... 64, where a tile's first scrunch group (which continues the carry) and its last
+    open one (which replaces it) are items of different threads and waves -- at freq_res 8 and 16 of different loop iterations, a
+    staged tile holding more rows than the workgroup has threads.  Parts that begin and end inside a group, odd part counts per call
+    (the call begins inside a group), launch groups that split a call: == the oracle's square_law + tscrunch_fpt of the SAME object's
+    complex output, bit for bit.  (One run per case: a pass guards the ordering of the carry reads and writes, it cannot prove it.)"""
+    dspsr_amd, ctx = gpu
+    npo = 1 if state_name == "Intensity" else 2
+    state = dspsr_amd.INTENSITY if npo == 1 else dspsr_amd.PPQQ
+    nkeep = M - sum(nfilt)
+    nthr, nrow, fits = _short_transform_tile(C, M, npo, nkeep, sf)
+    assert fits and nthr >= 256                                        # the fused epilogue, on a tile of several waves
+    assert nrow >= nthr or M >= 32
+    tsp = _search_parts(nkeep, sf, parts)
+    assert any(phi and ng >= 2 and rlast < sf for (_c, _p0, phi, ng, rlast) in tsp)      # reads AND replaces the carry
+    assert any(p0 for (_c, p0, _phi, _ng, _rl) in tsp) and max(parts) > maxp              # calls begin inside a group; split calls
+    krng = np.random.default_rng(1000 * M + sf)
+    kernel = np.exp(1j * krng.uniform(-np.pi, np.pi, C * M)).astype(np.complex64)
+    fb = dspsr_amd.FilterbankEngine(ctx).setup(C, M, nfilt[0], nfilt[1], 1, 2, True, kernel, max_parts=maxp)
+    assert fb.search_is_fused() and fb.nkeep == nkeep
+    carry = torch.zeros((C, npo), dtype=torch.float32, device="cuda")
+    cc, got, dets = 0, [], []
+    for npart in parts:
+        nsamp = npart * fb.nsamp_step + fb.nsamp_overlap
+        raw = torch.from_numpy(np.clip(np.rint(krng.standard_normal(nsamp * 2) * 24.0), -128, 127).astype(np.int8)).cuda()
+        cplx = torch.zeros((C, 2, 2 * npart * nkeep), dtype=torch.float32, device="cuda")
+        fb.perform_raw(raw, dspsr_amd.RAW_GENERIC, 0.0123, cplx, npart)
+        dets.append(oracle.square_law(cplx.cpu().numpy().view(np.complex64), state_name))
+        out = torch.full((C, npo, (cc + npart * nkeep) // sf + 1), -1.0, dtype=torch.float32, device="cuda")
+        nout, cc = fb.perform_search(out, carry, cc, npart, sf, state, raw=raw, layout=dspsr_amd.RAW_GENERIC, scale=0.0123)
+        got.append(out[:, :, :nout].cpu().numpy())
+    fb.close()
+    all_det = np.concatenate(dets, axis=2)
+    want = oracle.tscrunch_fpt(all_det, sf)
+    got = np.concatenate(got, axis=2)
+    assert cc == all_det.shape[2] % sf
+    assert got.shape == want.shape and want.shape[2] > 0
+    bad = np.argwhere(got != want)
+    assert bad.size == 0, "%d of %d samples differ, first (chan, pol, out) %s" % (len(bad), got.size, bad[:4].tolist())
+
+
 @pytest.mark.parametrize("npol,input_nchan,nchan,freq_res,dm", [
     (1, 1, 64, 512, 20.0),            # one polarisation: Intensity = Re^2 + Im^2 of it (Detection.C:218-320 with npol 1)
     (2, 4, 64, 512, 20.0),            # four input channels (a filterbank of 16 channels on each)
@@ -363,6 +445,62 @@ def test_digifil_coherent_other_options_against_the_oracle(oracle, gpu, nbit, np
             assert d.max() <= 1 and (d != 0).mean() < 2e-3, (b, d.max(), (d != 0).mean())
         total += want.size
     assert total > 0
+    lf.close()
+
+
+@pytest.mark.parametrize("nbit,npol,fscrunch", [(8, 1, 0), (2, 2, 2)])
+def test_digifil_coherent_interchan_short_blocks_against_the_oracle(oracle, gpu, nbit, npol, fscrunch):
+    """-K with blocks of fewer kept samples than the total inter-channel delay (a short last block; the first blocks of a stream):
+    SampleDelay re-presents the unshifted tail in front of the next block, and when a block holds fewer samples than that tail the
+    tail's old and new places overlap.  Blocks of (2, 1, 6, 1, 6) parts: the first two emit nothing (their whole input is carried, the
+    second one's over the first's), the fourth emits one part's worth.  Bytes against the oracle's DigifilCoherent fed the
+    matching blocks, with the tolerance of the full-block test."""
+    dspsr_amd, ctx = gpu
+    from dspsr_amd import pipeline
+    rng = np.random.default_rng(51)
+    blocks, ppb, dm, freq_res = (2, 1, 6, 1, 6), 6, 0.5, 1024
+    info = pipeline.InputInfo(centre_frequency=1382.0, bandwidth=-400.0, nchan=1, npol=2, ndim=1, tsamp_us=0.00125, machine="DADA")
+    cfg = pipeline.SearchConfig(nchan=64, tscrunch=16, nbit=nbit, rescale_seconds=2e-4, dispersion_measure=dm, freq_res=freq_res, parts_per_block=ppb,
+                                max_parts=4, npol=npol, fscrunch=fscrunch, dedisperse=True)
+    lf = pipeline.LoadToFilCoherent(cfg, info, device=0, stream=torch.cuda.current_stream().cuda_stream)
+    obs = oracle.Observation(centre_frequency=1382.0, bandwidth=-400.0, dispersion_measure=dm)
+    od = oracle.Dedispersion()
+    od.set_frequency_resolution(freq_res)
+    od.match(obs, 64)
+    plan = oracle.filterbank_plan(obs, 64, od, freq_res=freq_res)
+    assert (plan.nkeep, plan.nsamp_step) == (lf.nkeep, lf.nsamp_step)
+    delays = oracle.dedispersion_sample_delays(obs, 64, lf.fb_rate)
+    total = lf.sample_delay.total_delay
+    assert total == int(max(delays) - min(delays))
+    # the edges this case exists for, from the block sequence: a block shorter than the delay (the carried tail overlaps its new place),
+    # and a block after which nothing is emitted at all
+    carried, short, silent = 0, False, False
+    for n in blocks:
+        nin = carried + n * lf.nkeep
+        short |= 0 < carried and n * lf.nkeep < min(nin, total)      # the tail moves by less than its length
+        silent |= 0 < carried and nin < total                         # SampleDelay emits nothing: the whole input is carried
+        carried = min(nin, total)
+    assert short and silent
+    dig = oracle.DigifilCoherent(tscrunch=16, fscrunch=fscrunch, nbit=nbit, npol_out=npol, rescale_interval=int(2e-4 * lf.out_rate), flip_band=False,
+                                 delays=delays)
+    nparts = sum(blocks)
+    stream = np.clip(np.rint(rng.standard_normal((nparts * lf.nsamp_step + lf.nsamp_overlap) * 2) * 24.0), -128, 127).astype(np.int8)
+    p0, total_out, empty = 0, 0, 0
+    for b, n in enumerate(blocks):
+        raw = stream[p0 * lf.nsamp_step * 2:(p0 * lf.nsamp_step + n * lf.nsamp_step + lf.nsamp_overlap) * 2]
+        got = lf.process_block(torch.from_numpy(raw.copy()).cuda(), n).cpu().numpy()
+        fbo = oracle.filterbank(oracle.unpack_8bit(raw, obs), plan, lf.response.kernel, npart=n, dtype=np.float64).astype(np.complex64)
+        want = dig.process(fbo)
+        assert got.size == want.size, (b, got.size, want.size)
+        got = got.view(want.dtype).reshape(want.shape)
+        d = np.abs(got.astype(np.int64) - want.astype(np.int64))
+        if want.size:
+            assert d.max() <= 1 and (d != 0).mean() < 2e-3, (b, d.max(), (d != 0).mean())
+        else:
+            empty += 1
+        total_out += want.size
+        p0 += n
+    assert empty >= 1 and total_out > 0 and lf.sd_carried == total
     lf.close()
 
 

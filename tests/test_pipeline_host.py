@@ -296,3 +296,29 @@ def test_cheby_predictor_closed_form_and_oracle(oracle):
         pipeline.ChebyPredictor(text).phase(55299, 0.3 * 86400)                    # outside every TIME_RANGE
     with pytest.raises(pipeline.DspsrAmdError):
         pipeline.ChebyPredictor("ChebyModelSet 0 segments\n")
+
+
+@pytest.mark.parametrize("dst,src,n", [(0, 916, 916), (0, 916, 2748), (3, 4, 1000), (0, 5496, 4031), (10, 13, 2)])
+def test_move_tail_fpt_never_copies_overlapping_rows(monkeypatch, dst, src, n):
+    """-K carries the unshifted tail of a block to the front of its buffer (pipeline.move_tail_fpt).  When a block consumed fewer
+    samples than are carried the old and new places overlap; every copy_data_fpt it issues must have disjoint rows (the device copy
+    is parallel and refuses overlap), and the copies in stream order must leave the tail at its new place."""
+    torch = pytest.importorskip("torch")
+    from dspsr_amd import pipeline
+    unit = 2
+    buf = torch.arange(2 * 3 * (src + n + 5) * unit, dtype=torch.float32).reshape(2, 3, -1)
+    want = buf.clone()
+    want[:, :, dst * unit:(dst + n) * unit] = buf[:, :, src * unit:(src + n) * unit].clone()
+    calls = []
+
+    def copy(ctx, to, frm):                                  # a parallel copy: every element read before any is written
+        a = (to.data_ptr() - buf.data_ptr()) // 4
+        b = (frm.data_ptr() - buf.data_ptr()) // 4
+        assert to.shape == frm.shape and to.stride() == frm.stride() == buf.stride()
+        assert a + to.shape[2] <= b or b + frm.shape[2] <= a, "overlapping rows"
+        calls.append((a, b))
+        to.copy_(frm.clone())
+
+    monkeypatch.setattr(pipeline, "copy_data_fpt", copy)
+    pipeline.move_tail_fpt(None, buf, dst, src, n, unit)
+    assert torch.equal(buf, want) and len(calls) == -(-n // (src - dst))

@@ -481,15 +481,24 @@ DEV typename SplitElem<KIND, EB>::type sub_split_load(const SubSplit& p, const u
 {
   if constexpr (KIND == 0) {
     const float* __restrict__ x = (const float*)p.base + p.chan_off + q * p.pol_stride;
-    if constexpr (EB == 8) return *(const uint2*)(x + 2 * t);
+    if constexpr (EB == 8) {
+      // (rows at an odd float offset -- a shifted TimeSeries, odd channel or polarisation strides -- take two 4-byte loads)
+      if (((uintptr_t)x & 7) == 0) return *(const uint2*)(x + 2 * t);
+      return make_uint2(__float_as_uint(x[2 * t]), __float_as_uint(x[2 * t + 1]));
+    }
     else return __float_as_uint(x[t]);
   } else if constexpr (KIND == 2) {
     const uint8_t* __restrict__ b = (const uint8_t*)p.base + (t >> 2) * 8 + (t & 3);
     return (uint32_t)b[0] | ((uint32_t)b[4] << 8);
   } else {
     const uint8_t* __restrict__ b = (const uint8_t*)p.base + (t * p.nchan + p.ichan) * EB;
-    if constexpr (EB == 4) return ((uintptr_t)b & 3) ? ((uint32_t)*(const uint16_t*)b | ((uint32_t)*(const uint16_t*)(b + 2) << 16)) : *(const uint32_t*)b;
-    else if constexpr (EB == 2) return *(const uint16_t*)b;
+    // (loads no wider than the element's address allows: an 8-bit block may start at any byte)
+    if constexpr (EB == 4) {
+      if (((uintptr_t)b & 3) == 0) return *(const uint32_t*)b;
+      if (((uintptr_t)b & 1) == 0) return (uint32_t)*(const uint16_t*)b | ((uint32_t)*(const uint16_t*)(b + 2) << 16);
+      return (uint32_t)b[0] | ((uint32_t)b[1] << 8) | ((uint32_t)b[2] << 16) | ((uint32_t)b[3] << 24);
+    }
+    else if constexpr (EB == 2) return ((uintptr_t)b & 1) ? ((uint32_t)b[0] | ((uint32_t)b[1] << 8)) : (uint32_t)*(const uint16_t*)b;
     else return *b;
   }
 }
@@ -511,7 +520,7 @@ __global__ __launch_bounds__(256) void k_sub_split(const SubSplit p, uint8_t* __
       // 8-bit sources: the thread's 16 R input bytes as whole dwords where the alignment allows (a load per BYTE otherwise)
       bool have = false;
       if constexpr (KIND == 2) {
-        if ((t0 & 3) == 0) {                                        // whole 4-sample groups: 4 B pol0 | 4 B pol1
+        if ((t0 & 3) == 0 && ((uintptr_t)p.base & 7) == 0) {       // whole 4-sample groups: 4 B pol0 | 4 B pol1 (8-byte loads)
           const uint2* __restrict__ gp = (const uint2*)((const uint8_t*)p.base + (t0 >> 2) * 8);
           uint2 grp[2 * RT];
 #pragma unroll

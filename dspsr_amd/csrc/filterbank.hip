@@ -698,6 +698,11 @@ static int fb_run(dspsr_amd_filterbank* fb, FbIn in, FbOut out, uint64_t npart, 
   if (!fb->kernel_set)
     return fb_fail(ctx, DSPSR_AMD_ESTATE, "dspsr_amd_filterbank_perform: set_kernel (Engine::setup) not called");
   if (npart == 0) return DSPSR_AMD_OK;
+  // the CASPSR and UWB loaders read whole 16-bit / 32-bit words relative to the block (fetch_pair, k_fb_plain): a block that
+  // starts inside such a word is not that layout
+  if ((in.kind == 2 && ((uintptr_t)in.base % 2) != 0) || (in.kind == 4 && ((uintptr_t)in.base % 4) != 0))
+    return fb_fail(ctx, DSPSR_AMD_EINVAL, "dspsr_amd_filterbank_perform: a %s block must start at a multiple of %d bytes",
+                   in.kind == 2 ? "CASPSR" : "16-bit UWB", in.kind == 2 ? 2 : 4);
   const FbGeom& g = fb->g;
   if (fb->plain_logC >= 0) {
     if (out.kind != 0 && out.kind != 1 && out.kind != 2)

@@ -1,6 +1,8 @@
 """tests/fuzz_filterbank.py [ncases] [seed] [log2 N min] [log2 N max] : random filterbank geometries against the float64 oracle (test infrastructure:
 uses tests/test_gpu_parity._fb_case).  Every combination the C-ABI accepts is fair game: 1 or 2 polarisations, real or complex
-input, 8-bit or float32 input, generic or CASPSR byte order, 1-3 input channels, three- or four-pass, 1-3 parts per launch."""
+input, 8-bit or float32 input, generic, CASPSR or 16-bit UWB byte order, 1-3 input channels, three- or four-pass, 1-3 parts per
+launch, blocks at any legal address (offset: bytes of a raw block, floats of float rows; row_pad: odd row strides).  The offsets
+and UWB blocks are drawn from a second generator seeded with (seed, case), so every seed keeps the geometries it drew before."""
 import os
 import sys
 import traceback
@@ -22,7 +24,8 @@ from test_gpu_parity import _fb_case
 
 ncases = int(sys.argv[1]) if len(sys.argv) > 1 else 60
 lo, hi = (int(sys.argv[3]), int(sys.argv[4])) if len(sys.argv) > 4 else (7, 21)     # log2 of N = nchan_subband * freq_res
-rng = np.random.default_rng(int(sys.argv[2]) if len(sys.argv) > 2 else 1)
+seed = int(sys.argv[2]) if len(sys.argv) > 2 else 1
+rng = np.random.default_rng(seed)
 ctx = dspsr_amd.Context(0, torch.cuda.current_stream().cuda_stream)
 bad = 0
 for i in range(ncases):
@@ -89,6 +92,22 @@ for i in range(ncases):
         kw = dict(npol=2, real=False, use_raw=False, max_parts=int(rng.integers(1, 5)), seed=int(rng.integers(1, 1000)),
                   input_nchan=int(rng.choice([1, 3, 4, 6, 8, 12, 16, 20, 32, 64] if logM <= 14 else [1, 2, 3, 4, 6, 8] if logM <= 18 else [1, 2, 3])), four_pass=int(rng.choice([0, 0, 0, 2])))
         npart = int(rng.integers(1, 7)) if logM + int(np.log2(kw["input_nchan"])) <= 17 else int(rng.integers(1, 3))
+    # input placement: about a third of the cases at an offset legal for their layout (UWB: whole 32-bit samples; CASPSR: 16-bit
+    # words; generic 8-bit: any byte; float rows: any float, a quarter of them with padded rows); about a quarter of the complex
+    # single-channel raw cases as 16-bit UWB blocks (power-of-two geometries: odd factors refuse them)
+    r2 = np.random.default_rng([seed, i])
+    use_raw = kw.get("use_raw", True)
+    if (use_raw and not kw.get("real", True) and kw.get("input_nchan", 1) == 1 and r2.integers(0, 4) == 0 and (C & (C - 1)) == 0
+            and (M & (M - 1)) == 0):
+        kw["layout"] = "uwb16"
+    if r2.integers(0, 3) == 0:
+        lay = kw.get("layout", "generic")
+        if not use_raw:
+            kw["offset"] = int(r2.integers(0, 4))
+            if r2.integers(0, 4) == 0:
+                kw["row_pad"] = 1
+        else:
+            kw["offset"] = int(r2.integers(0, 4)) * {"uwb16": 4, "caspsr": 2}.get(lay, 1) + (int(r2.integers(0, 2)) * 8 if lay != "generic" else 0)
     desc = "C=%d M=%d nfilt=(%d,%d) npart=%d %s" % (C, M, pos, neg, npart, kw)
     try:
         _fb_case(oracle, (dspsr_amd, ctx), C, M, (pos, neg), npart, **kw)

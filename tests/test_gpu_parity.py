@@ -8,6 +8,7 @@ CPU/FFTW reference; integer/index work bit-exact):
   * hits[], bin plan, fold of identical detected samples: bit-exact
 """
 import math
+import types
 
 import numpy as np
 import pytest
@@ -32,8 +33,48 @@ def _raw(ndat, npol=2, ndim=1, nchan=1, seed=1):
     return np.clip(np.rint(rng.standard_normal(ndat * nchan * npol * ndim) * 24.0), -128, 127).astype(np.int8)
 
 
-def _fb_case(oracle, gpu, C, M, nfilt, npart, npol=2, real=True, input_nchan=1, layout="generic", use_raw=True,
-             max_parts=1, seed=3, four_pass=False):
+# Input blocks away from the allocator's alignment (_fb_case offset / row_pad): guard bytes and row padding hold a sentinel a loader
+# cannot mistake for data.  Raw blocks: 0x7f (above every |value| of _raw's data but one, and wrong where it is read); float rows:
+# NaN, which every output it reaches turns into NaN (the outputs are asserted finite).
+GUARD_RAW, GUARD_ALIGN = 0x7f, 256
+
+
+def _device_block(raw_u8, offset):
+    """raw bytes at `offset` bytes past a 256-byte boundary of a larger device buffer, guard bytes before and behind them"""
+    n = raw_u8.size
+    buf = torch.full((GUARD_ALIGN + offset + n + GUARD_ALIGN,), GUARD_RAW, dtype=torch.uint8, device="cuda")
+    lead = (-buf.data_ptr()) % GUARD_ALIGN
+    blk = buf[lead + offset:lead + offset + n + GUARD_ALIGN]                  # (the tail guard stays inside the view: never read)
+    assert blk.data_ptr() % GUARD_ALIGN == offset % GUARD_ALIGN
+    blk[:n].copy_(torch.from_numpy(raw_u8))
+    return blk.view(torch.int8)
+
+
+def _device_rows(x, offset, row_pad):
+    """float32 [nchan][npol][n] rows as a strided view: `offset` floats past a 256-byte boundary, rows `row_pad` floats longer than
+    their data (channel and polarisation strides n + row_pad), the rest of the buffer NaN"""
+    nchan, npol, n = x.shape
+    w = n + row_pad
+    buf = torch.full((GUARD_ALIGN + offset + nchan * npol * w + GUARD_ALIGN,), float("nan"), dtype=torch.float32, device="cuda")
+    lead = ((-buf.data_ptr()) % GUARD_ALIGN) // 4
+    rows = buf[lead + offset:lead + offset + nchan * npol * w].view(nchan, npol, w)[:, :, :n]
+    assert rows.data_ptr() % GUARD_ALIGN == (4 * offset) % GUARD_ALIGN and rows.stride() == (npol * w, w, 1)
+    rows.copy_(torch.from_numpy(np.ascontiguousarray(x)))
+    return rows
+
+
+def _uwb_raw(ndat, npol, seed):
+    """16-bit offset-binary complex samples in blocks of 2048 per polarisation (whole blocks: ndat rounded up)"""
+    rng = np.random.default_rng(seed)
+    nblk = -(-ndat // 2048)
+    raw = np.clip(np.rint(rng.standard_normal(nblk * 2048 * npol * 2) * 3000.0), -32768, 32767).astype(np.int16)
+    return raw.view(np.uint16) ^ np.uint16(0x8000)
+
+
+def _fb_block(oracle, gpu, C, M, nfilt, npart, npol=2, real=True, input_nchan=1, layout="generic", use_raw=True,
+              max_parts=1, seed=3, four_pass=False, offset=0, row_pad=0, fused_fold=None):
+    """The object, the device block (offset bytes / floats past an aligned address, rows row_pad floats apart) and the float64
+    oracle output of _fb_case; layout "uwb16": complex single-channel 16-bit blocks (RAW_UWB16, scale 1)."""
     dspsr_amd, ctx = gpu
     o = oracle
     nchan = C * input_nchan
@@ -42,6 +83,9 @@ def _fb_case(oracle, gpu, C, M, nfilt, npart, npol=2, real=True, input_nchan=1, 
     rng = np.random.default_rng(seed)
     kernel = np.exp(1j * rng.uniform(-np.pi, np.pi, input_nchan * N)).astype(np.complex64)
     kernel[0] = 0
+    uwb = layout == "uwb16"
+    if uwb:
+        assert not real and input_nchan == 1 and use_raw and offset % 4 == 0, "UWB blocks: complex, one channel, whole 32-bit samples"
     obs = o.Observation(nchan=input_nchan, npol=npol, ndim=1 if real else 2,
                         machine="CASPSR" if layout == "caspsr" else "DADA")
     plan = o.FilterbankPlan(nchan, input_nchan, C, M, N, nfilt_pos, nfilt_neg, nfilt_pos + nfilt_neg,
@@ -49,31 +93,63 @@ def _fb_case(oracle, gpu, C, M, nfilt, npart, npol=2, real=True, input_nchan=1, 
                             M - nfilt_pos - nfilt_neg, float(N) * M, real)
     plan.nsamp_step = plan.nsamp_fft - plan.nsamp_overlap
     ndat = npart * plan.nsamp_step + plan.nsamp_overlap
-    # (the CASPSR byte order comes in whole groups of 4 samples: 4 B pol0 | 4 B pol1)
-    raw = _raw(-(-ndat // 4) * 4 if layout == "caspsr" else ndat, npol, obs.ndim, input_nchan, seed)
-    scale = float(o.S8)
-    unpacked = o.unpack_8bit(raw, obs)
-    ref = o.filterbank(unpacked, plan, kernel, npart=npart, dtype=np.float64)
-
-    eng = dspsr_amd.FilterbankEngine(ctx).setup(C, M, nfilt_pos, nfilt_neg, input_nchan, npol, real, kernel,
-                                                max_parts=max_parts, force_four_pass=four_pass)
-    assert (eng.nsamp_fft, eng.nsamp_overlap, eng.nsamp_step, eng.nkeep) == \
-        (plan.nsamp_fft, plan.nsamp_overlap, plan.nsamp_step, plan.nkeep)
-    out = torch.zeros((nchan, npol, 2 * npart * plan.nkeep), dtype=torch.float32, device="cuda")
-    if use_raw:
-        d_raw = torch.from_numpy(raw).cuda()
-        eng.perform_raw(d_raw, dspsr_amd.RAW_CASPSR if layout == "caspsr" else dspsr_amd.RAW_GENERIC, scale, out,
-                        npart)
+    if uwb:
+        raw = _uwb_raw(ndat, npol, seed)
+        scale = 1.0
+        unpacked = o.unpack_uwb16(raw, npol)
     else:
-        d_in = torch.from_numpy(unpacked).cuda()
-        eng.perform(d_in, out, npart, plan.nsamp_step * obs.ndim, 2 * plan.nkeep)
+        # (the CASPSR byte order comes in whole groups of 4 samples: 4 B pol0 | 4 B pol1)
+        raw = _raw(-(-ndat // 4) * 4 if layout == "caspsr" else ndat, npol, obs.ndim, input_nchan, seed)
+        scale = float(o.S8)
+        unpacked = o.unpack_8bit(raw, obs)
+    b = types.SimpleNamespace()
+    b.ref = o.filterbank(unpacked, plan, kernel, npart=npart, dtype=np.float64)
+    kw = {} if fused_fold is None else dict(fused_fold=fused_fold)
+    b.eng = dspsr_amd.FilterbankEngine(ctx).setup(C, M, nfilt_pos, nfilt_neg, input_nchan, npol, real, kernel,
+                                                  max_parts=max_parts, force_four_pass=four_pass, **kw)
+    assert (b.eng.nsamp_fft, b.eng.nsamp_overlap, b.eng.nsamp_step, b.eng.nkeep) == \
+        (plan.nsamp_fft, plan.nsamp_overlap, plan.nsamp_step, plan.nkeep)
+    b.plan, b.obs, b.scale, b.npart, b.nchan, b.npol = plan, obs, scale, npart, nchan, npol
+    b.layout = dspsr_amd.RAW_UWB16 if uwb else dspsr_amd.RAW_CASPSR if layout == "caspsr" else dspsr_amd.RAW_GENERIC
+    if use_raw:
+        if offset == 0 and not uwb:
+            b.raw = torch.from_numpy(raw).cuda()              # (the allocator's alignment: the form every other test takes)
+        else:
+            b.raw = _device_block(np.ascontiguousarray(raw).view(np.uint8).ravel(), offset)
+        b.inp, b.in_step = None, 0
+    else:
+        b.raw = None
+        b.inp = torch.from_numpy(unpacked).cuda() if offset == 0 and row_pad == 0 else _device_rows(unpacked, offset, row_pad)
+        b.in_step = plan.nsamp_step * obs.ndim
+    return b
+
+
+def _fb_case(oracle, gpu, C, M, nfilt, npart, npol=2, real=True, input_nchan=1, layout="generic", use_raw=True,
+             max_parts=1, seed=3, four_pass=False, offset=0, row_pad=0):
+    """Filterbank output of one block against the float64 oracle.  offset: bytes (raw blocks) or floats (float rows) between a
+    256-byte boundary and the block, guarded by sentinels (see GUARD_RAW); row_pad: floats between the end of a float row and the
+    next (odd channel and polarisation strides); layout "uwb16": 16-bit UWB blocks.  The defaults are the aligned blocks torch
+    allocates.  Returns (output, oracle output)."""
+    dspsr_amd, ctx = gpu
+    b = _fb_block(oracle, gpu, C, M, nfilt, npart, npol, real, input_nchan, layout, use_raw, max_parts, seed, four_pass, offset, row_pad)
+    plan, eng, ref = b.plan, b.eng, b.ref
+    out = torch.zeros((b.nchan, npol, 2 * npart * plan.nkeep), dtype=torch.float32, device="cuda")
+    if use_raw:
+        eng.perform_raw(b.raw, b.layout, b.scale, out, npart)
+    else:
+        eng.perform(b.inp, out, npart, b.in_step, 2 * plan.nkeep)
     eng.finish()
     got = out.cpu().numpy().view(np.complex64).astype(np.complex128)
     eng.close()
+    assert np.isfinite(got).all(), "non-finite output: a loader read the guard around the block"
     err = got - ref
     rms_ref = math.sqrt(np.mean(np.abs(ref) ** 2))
     rms_err = math.sqrt(np.mean(np.abs(err) ** 2))
-    tol = 2e-6 * math.sqrt(math.log2(2 * N))
+    # Loader bugs are caught by the max bound: one input sample of size ~rms(in) read from the wrong place changes every output
+    # sample of its part by about rms(out) / sqrt(N) (a random-phase response spreads it over the part's N-point spectrum).  At
+    # N = 2^22, the largest N tested, that is 4.9e-4 rms(out) against the bound 8 * 2e-6 * sqrt(23) = 7.7e-5 rms(out); at the
+    # N <= 2^18 of tests/test_gpu_input_forms.py 2.0e-3 against 7.0e-5.
+    tol = 2e-6 * math.sqrt(math.log2(2 * C * M))
     assert rms_err / rms_ref <= tol, (rms_err / rms_ref, tol)
     assert np.abs(err).max() <= 8 * tol * rms_ref, (np.abs(err).max() / rms_ref, 8 * tol)
     return got, ref

@@ -63,9 +63,11 @@ constexpr int FOLD_BPT = 4;             // bins per thread (nbin <= FOLD_BPT * b
 // picks the LONG variant for the whole call: every chunk is first reduced, by all threads, to the sums of its aligned
 // FOLD_MB-sample micro-blocks (each summed in time order); a bin's owner then adds, in time order, single samples up to
 // the first micro-block boundary inside its run, whole micro-block sums, and single samples after the last boundary.
-// Deterministic (the association depends on the plan and the chunk grid only), no longer the association of the CPU
-// loop: it agrees with it to float rounding, like the reference's own GPU fold (FoldCUDA.cu:208-269 sums each
-// run from zero and adds the run sums atomically).  Plans of shorter runs keep the exact time-order kernel.
+// Deterministic, no longer the association of the CPU loop: it agrees with it to float rounding, like the reference's own
+// GPU fold (FoldCUDA.cu:208-269 sums each run from zero and adds the run sums atomically).  The association depends on the
+// plan, the chunk grid and the number of time segments, each summed from zero and added to the profile in segment order by
+// k_fold_combine; the segment count follows from the device's compute units and nchan*npol (fold_fold_impl), so the sums
+// are reproducible on one device and row count, not across them.  Plans of shorter runs keep the exact time-order kernel.
 constexpr uint32_t FOLD_MB = 32;
 constexpr uint32_t FOLD_LONG_RUN = FOLD_LONG_RUN_HOST;
 
@@ -800,6 +802,7 @@ static int fold_fold_impl(dspsr_amd_fold* f, const float* in_dev, uint64_t in_ch
   if (f->binplan.empty()) return DSPSR_AMD_OK;             // send_binplan :160-161
   if (f->current_hits) f->binplan.back().hits = f->current_hits;   // :163-164
   f->current_hits = 0;
+  f->current_bin = f->folding_nbin;   // the plan is used up: the next one opens a fresh run (as after set_nbin)
 
   // bucket the time-ordered intervals by phase bin (stable => time order kept inside a bin)
   const uint32_t nbin = f->nbin;
@@ -1005,6 +1008,7 @@ int fold_build_part_plan(dspsr_amd_fold* f, uint32_t nkeep, uint32_t npart, cons
   dspsr_amd_ctx* ctx = f->ctx;
   if (f->current_hits && !f->binplan.empty()) f->binplan.back().hits = f->current_hits;   // FoldCUDA.cu:163-164
   f->current_hits = 0;
+  f->current_bin = f->folding_nbin;                                        // (the next plan opens a fresh run)
   const uint32_t nbin = f->nbin;
   // count the pieces: a run is cut at every multiple of nkeep
   size_t npiece = 0;
@@ -1121,6 +1125,7 @@ int fold_build_segment_plan(dspsr_amd_fold* f, uint64_t ndat, uint32_t seg, bool
   if (expect != ndat) return DSPSR_AMD_OK;
   if (f->current_hits) f->binplan.back().hits = f->current_hits;           // FoldCUDA.cu:163-164
   f->current_hits = 0;
+  f->current_bin = f->folding_nbin;                                        // (the next plan opens a fresh run)
   const uint32_t nbin = f->nbin;
   PlanSlot& sl = f->slot[f->next_slot];
   f->next_slot ^= 1;

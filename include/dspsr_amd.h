@@ -288,7 +288,10 @@ int dspsr_amd_fold_set_nbin(dspsr_amd_fold* fold, uint32_t nbin);               
 int dspsr_amd_fold_set_ndat(dspsr_amd_fold* fold, uint64_t ndat, uint64_t idat_start);   /* FoldCUDA.cu:72-82 */
 int dspsr_amd_fold_set_bin(dspsr_amd_fold* fold, uint64_t idat, double ibin, double bins_per_sample); /* :84-113 */
 /* whole plan at once: the double recurrence of Fold.C:744-787 run inside the library;
- * hits_host[nbin] (may be NULL) is incremented like Fold.C:783; returns ndat folded via *ndat_folded */
+ * hits_host[nbin] (may be NULL) is incremented like Fold.C:783; returns ndat folded via *ndat_folded.
+ * Call order: set_nbin, set_ndat, then set_bin / set_bins (several calls may build one plan: a run left open by one call
+ * goes on in the next), then fold.  A fold (or a fused fold) uses the plan up; a plan built after it without a new set_nbin
+ * opens a fresh run at its first sample, so every sample counted in hits_host and ndat_folded is folded by the next fold. */
 int dspsr_amd_fold_set_bins(dspsr_amd_fold* fold, double phi, double phase_per_sample, uint64_t ndat,
                             uint64_t idat_start, uint32_t* hits_host, uint64_t* ndat_folded);
 /* the same with the weights of the input (Fold.C:686-716,746-763: WeightedTimeSeries, one weight per ndatperweight samples,

@@ -1,0 +1,169 @@
+"""CPU restatement of the stand-alone fold (dspsr_amd_fold_fold, csrc/fold.hip) for the tests: the sums of every kernel in the
+association that kernel uses, in float32, and the host's choice of kernel.
+
+A plan is its list of runs (first sample, phase bin, samples) in time order, as set_bin / set_bins build it; `rows` are the
+detected samples [nchan][npol][ndat][ndim] (sample idat of a row at rows[:, :, idat, :]); `prof` the profile
+[nchan][npol][nbin][ndim] before the fold.  The functions return the profile after it and leave `prof` as it was.
+
+- fold_time_order: the CPU loop of Fold.C:844-852, every (chan, pol, bin, dim) sum in strict time order.  The association of
+  k_fold_direct, k_fold_chunked<., false, .> and k_fold_dense.
+- fold_long_model: the association of k_fold_chunked<., true, .> + k_fold_combine (the LONG path), bit for bit.
+- fold_dispatch: which kernel fold_fold_impl launches for a call, with its template arguments and launch shape.
+"""
+import numpy as np
+
+FOLD_CHUNK = 2048        # samples per chunk (fold.hip FOLD_CHUNK)
+FOLD_MB = 32             # samples per micro-block (fold.hip FOLD_MB)
+FOLD_BPT = 4             # bins per thread (fold.hip FOLD_BPT)
+FOLD_LONG_RUN = 64       # a run this long selects the LONG path (fold_internal.h FOLD_LONG_RUN_HOST)
+
+
+def runs_of_plan(plan, idat_start=0):
+    """The runs set_bin builds from a per-sample bin plan (a new run wherever the bin changes): int64 [nrun][3] of
+    (first sample, bin, samples), samples counted from idat_start."""
+    plan = np.asarray(plan)
+    if plan.size == 0:
+        return np.zeros((0, 3), np.int64)
+    starts = np.concatenate(([0], np.flatnonzero(np.diff(plan)) + 1))
+    lens = np.diff(np.concatenate((starts, [plan.size])))
+    return np.stack([starts + idat_start, plan[starts].astype(np.int64), lens], axis=1).astype(np.int64)
+
+
+def _add_in_order(acc, src, slots, seqs):
+    """acc[..., slots[i], :] += src[..., seqs[i][0], :], then seqs[i][1], ... one float32 addition at a time.  The sequences of
+    different slots are independent; step k of all of them is taken at once (vectorised over slots and the leading axes)."""
+    if not seqs:
+        return acc
+    lens = np.array([len(s) for s in seqs])
+    L = int(lens.max())
+    idx = np.zeros((len(seqs), L), np.int64)
+    for i, s in enumerate(seqs):
+        idx[i, :len(s)] = s
+    slots = np.asarray(slots, np.int64)
+    for k in range(L):
+        m = lens > k
+        sl = slots[m]
+        acc[:, :, sl, :] = acc[:, :, sl, :] + src[:, :, idx[m, k], :]
+    return acc
+
+
+def fold_time_order(rows, runs, prof):
+    """Fold.C:844-852 in float32: per (chan, pol, bin, dim) the samples of the bin's runs, in time order, added one by one to
+    the profile's value."""
+    rows = np.asarray(rows, np.float32)
+    out = np.array(prof, np.float32, copy=True)
+    per_bin = {}
+    for off, b, n in np.asarray(runs, np.int64).reshape(-1, 3):
+        if n:
+            per_bin.setdefault(int(b), []).append(np.arange(off, off + n))
+    bins = sorted(per_bin)
+    return _add_in_order(out, rows, bins, [np.concatenate(per_bin[b]) for b in bins])
+
+
+def long_segments(nchunk, nrow, ncu):
+    """(nseg, chunks per segment) of the LONG path: fold.hip fold_fold_impl, `nseg = (4 * ctx->ncu + nrow - 1) / nrow` ..."""
+    nseg = (4 * ncu + nrow - 1) // nrow
+    nseg = max(1, min(nseg, nchunk, 65535))
+    cps = (nchunk + nseg - 1) // nseg
+    return (nchunk + cps - 1) // cps, cps
+
+
+def plan_span(runs):
+    """[first, last) of the chunk grid: the plan's first sample rounded down to a multiple of 4, one past its last sample"""
+    runs = np.asarray(runs, np.int64).reshape(-1, 3)
+    first = int(runs[0, 0]) - int(runs[0, 0]) % 4
+    return first, int(runs[-1, 0] + runs[-1, 2])
+
+
+def fold_long_model(rows, runs, prof, nrow, ncu):
+    """k_fold_chunked<., true, .> + k_fold_combine, bit for bit.  The chunk grid starts at plan_span's `first`, chunks of
+    FOLD_CHUNK samples, grouped into nseg time segments of cps chunks (long_segments: nrow = nchan * npol, ncu = the device's
+    compute units).  Every aligned FOLD_MB-sample micro-block of a chunk is summed from zero in time order.  Each segment sums
+    every bin from zero: for each run piece inside a chunk, in time order, the single samples up to the first micro-block
+    boundary, the whole micro-blocks, the single samples after the last boundary -- all single samples when no whole
+    micro-block fits.  k_fold_combine then adds the segments' sums to the profile in segment order (every bin, every segment)."""
+    rows = np.asarray(rows, np.float32)
+    runs = np.asarray(runs, np.int64).reshape(-1, 3)
+    out = np.array(prof, np.float32, copy=True)
+    if runs.shape[0] == 0:
+        return out
+    nchan, npol, ndat, ndim = rows.shape
+    nbin = out.shape[2]
+    first, last = plan_span(runs)
+    nchunk = (last - first + FOLD_CHUNK - 1) // FOLD_CHUNK
+    nseg, cps = long_segments(nchunk, nrow, ncu)
+    # the chunk images: samples [first, last), zero behind (the kernel's ragged-end fill)
+    span = nchunk * FOLD_CHUNK
+    img = np.zeros((nchan, npol, span, ndim), np.float32)
+    img[:, :, :last - first, :] = rows[:, :, first:last, :]
+    nmb = span // FOLD_MB
+    blk = img.reshape(nchan, npol, nmb, FOLD_MB, ndim)
+    mbs = np.zeros((nchan, npol, nmb, ndim), np.float32)
+    for h in range(FOLD_MB):
+        mbs = mbs + blk[:, :, :, h, :]
+    src = np.concatenate([img, mbs], axis=2)            # term t < span: sample first + t;  span + m: micro-block m
+    seqs = {}
+    for off, b, n in runs:
+        s, e = int(off) - first, int(off + n) - first
+        while s < e:
+            c = s // FOLD_CHUNK
+            c0 = c * FOLD_CHUNK
+            hi = min(e, c0 + FOLD_CHUNK)
+            s0, s1 = s - c0, hi - c0
+            a0 = -(-s0 // FOLD_MB) * FOLD_MB
+            a1 = s1 // FOLD_MB * FOLD_MB
+            if a0 >= a1:
+                t = list(range(c0 + s0, c0 + s1))
+            else:
+                t = (list(range(c0 + s0, c0 + a0)) + [span + (c0 + a) // FOLD_MB for a in range(a0, a1, FOLD_MB)]
+                     + list(range(c0 + a1, c0 + s1)))
+            seqs.setdefault((c // cps, int(b)), []).extend(t)
+            s = hi
+    part = np.zeros((nchan, npol, nseg * nbin, ndim), np.float32)
+    keys = sorted(seqs)
+    _add_in_order(part, src, [g * nbin + b for g, b in keys], [seqs[k] for k in keys])
+    for g in range(nseg):
+        out = out + part[:, :, g * nbin:(g + 1) * nbin, :]
+    return out
+
+
+def fold_dispatch(addr, chan_stride, pol_stride, nchan, npol, ndim, nbin, runs, ncu):
+    """fold.hip fold_fold_impl's choice for a call: `addr` the input's byte address, strides in floats.  Returns a dict:
+    kernel ('direct' | 'chunked' | 'long' | 'dense'), ndim, nrow (NROW), nsplit (exact kernels, grid.z), nseg and cps (LONG),
+    threads."""
+    runs = np.asarray(runs, np.int64).reshape(-1, 3)
+    first, last = plan_span(runs)
+    aligned = addr % 16 == 0 and chan_stride % 4 == 0 and pol_stride % 4 == 0                      # fold.hip:820
+    fits = nbin <= FOLD_BPT * 1024
+    nchunk = (last - first + FOLD_CHUNK - 1) // FOLD_CHUNK
+    one_per_chunk = aligned and fits                                                                 # :828-835
+    if one_per_chunk:
+        ntab = nchunk * nbin
+        one_per_chunk = ntab <= (1 << 24) and 4 * ntab <= (last - first) * nchan * npol * ndim
+    if one_per_chunk:                                                                                # :836-845
+        lastc = {}
+        for off, b, n in runs:
+            if n == 0:
+                continue
+            c0, c1 = (off - first) // FOLD_CHUNK, (off - first + n - 1) // FOLD_CHUNK
+            if lastc.get(int(b)) == c0:
+                one_per_chunk = False
+                break
+            lastc[int(b)] = c1
+    max_run = int(runs[:, 2].max())
+    lng = aligned and fits and max_run >= FOLD_LONG_RUN                                              # :849
+    dense = one_per_chunk and not lng
+    nrow_all = nchan * npol
+    nsplit = 1
+    if not lng:                                                                                      # :901-902
+        while nsplit < 8 and nrow_all * nsplit < 512 and nbin // (2 * nsplit) >= 64:
+            nsplit *= 2
+    threads = ((nbin + 63) // 64) * 64 if nbin < 1024 else 1024
+    if not (aligned and fits):                                                                       # :962-973
+        return dict(kernel="direct", ndim=ndim, nrow=1, nsplit=nsplit, nseg=1, cps=nchunk, threads=threads)
+    bins_wg = (nbin + nsplit - 1) // nsplit                                                          # :907-910
+    threads = min(1024, max(256, ((bins_wg + FOLD_BPT - 1) // FOLD_BPT + 63) // 64 * 64))
+    nseg, cps = long_segments(nchunk, nrow_all, ncu) if lng else (1, nchunk)                         # :912-920
+    nrw = npol if (ndim * npol == 4 and ndim < 4 and nchan * (nseg if lng else nsplit) >= 2 * ncu) else 1   # :933-934
+    kernel = "dense" if dense else ("long" if lng else "chunked")
+    return dict(kernel=kernel, ndim=ndim, nrow=nrw, nsplit=1 if lng else nsplit, nseg=nseg, cps=cps, threads=threads)

@@ -13,6 +13,8 @@ import types
 import numpy as np
 import pytest
 
+from device_buffers import device_rows
+
 pytestmark = pytest.mark.gpu
 
 torch = pytest.importorskip("torch")
@@ -50,17 +52,7 @@ def _device_block(raw_u8, offset):
     return blk.view(torch.int8)
 
 
-def _device_rows(x, offset, row_pad):
-    """float32 [nchan][npol][n] rows as a strided view: `offset` floats past a 256-byte boundary, rows `row_pad` floats longer than
-    their data (channel and polarisation strides n + row_pad), the rest of the buffer NaN"""
-    nchan, npol, n = x.shape
-    w = n + row_pad
-    buf = torch.full((GUARD_ALIGN + offset + nchan * npol * w + GUARD_ALIGN,), float("nan"), dtype=torch.float32, device="cuda")
-    lead = ((-buf.data_ptr()) % GUARD_ALIGN) // 4
-    rows = buf[lead + offset:lead + offset + nchan * npol * w].view(nchan, npol, w)[:, :, :n]
-    assert rows.data_ptr() % GUARD_ALIGN == (4 * offset) % GUARD_ALIGN and rows.stride() == (npol * w, w, 1)
-    rows.copy_(torch.from_numpy(np.ascontiguousarray(x)))
-    return rows
+_device_rows = device_rows          # (tests/device_buffers.py: shared with the fold tests and tests/fuzz_fold.py)
 
 
 def _uwb_raw(ndat, npol, seed):
@@ -1348,8 +1340,8 @@ def test_phase_series_mixable_and_device_combine(gpu):
 
 @pytest.mark.parametrize("ndim,npol", [(4, 1), (2, 2), (1, 4)])
 def test_fold_long_runs_reassociated(oracle, gpu, ndim, npol):
-    """Phase bins hundreds of samples wide (-F 64:D: 1090 samples per bin): the plan holds runs >= 256 samples and the fold
-    sums aligned 32-sample micro-blocks first (fold.hip FOLD_LONG_RUN).  Same hits, deterministic, equal to the time-order
+    """Phase bins hundreds of samples wide (-F 64:D: 1090 samples per bin): a plan that holds a run of >= 64 samples
+    (fold.hip FOLD_LONG_RUN) makes the fold sum aligned 32-sample micro-blocks first.  Same hits, deterministic, equal to the time-order
     sum to float rounding (<= 2e-6 of the profile maximum against a float64 fold; the CPU float32 loop is no closer)."""
     dspsr_amd, ctx = gpu
     rng = np.random.default_rng(71)

@@ -33,6 +33,21 @@ inline hipError_t dspsr_amd_allow_lds(const void* kern, size_t bytes)
   return e;
 }
 
+// A device buffer that only grows: a larger request waits for the stream (launches in flight may still use the old block),
+// frees it and allocates `need` elements.  false: the allocation failed and the buffer is empty.
+template <typename T>
+static inline bool grow_device_buffer(hipStream_t stream, T*& buf, size_t& count, size_t need)
+{
+  if (need <= count) return true;
+  (void)hipStreamSynchronize(stream);
+  if (buf) (void)hipFree(buf);
+  buf = nullptr;
+  count = 0;
+  if (hipMalloc((void**)&buf, need * sizeof(T)) != hipSuccess) return false;
+  count = need;
+  return true;
+}
+
 static inline void ctx_set_error_v(dspsr_amd_ctx* ctx, const char* fmt, va_list ap)
 {
   if (ctx) vsnprintf(ctx->error, sizeof(ctx->error), fmt, ap);

@@ -243,6 +243,22 @@ struct TimeCombine {
 
 
 [[maybe_unused]] constexpr uint32_t FB_PSL_MAX = 128;   // fused fold: offsets of the parts a workgroup walks (its run of a launch), kept in LDS
+// Host side of the fused-fold inverse kernels' LDS layout (fb_inv_chan.h plan_off / psl): behind the `lds` bytes of the plain
+// kernel, two buffers of `cap` 16-byte plan entries and the FB_PSL_MAX part offsets.  cap: what fits in 160 KB, at most `clamp`
+// (one entry per thread), 0 below 16; lds: the fused kernel's dynamic LDS.
+struct FbPlanLds {
+  uint32_t cap;
+  size_t lds;
+};
+static inline FbPlanLds fb_plan_lds(size_t lds, uint32_t clamp)
+{
+  const size_t psl_bytes = FB_PSL_MAX * sizeof(uint32_t);
+  const size_t spare = 160 * 1024 - 64 - lds - 16 - psl_bytes;
+  uint32_t cap = lds + 64 + 16 + psl_bytes < 160 * 1024 ? (uint32_t)(spare / 32) : 0;
+  if (cap > clamp) cap = clamp;
+  if (cap < 16) cap = 0;
+  return {cap, lds + 16 + (size_t)cap * 32 + psl_bytes};
+}
 
 // (int8 + 0.5) * scale (GenericEightBitUnpackerCUDA.cu:45).  int8 + 0.5 is exact in float, so the one rounding of the product
 // is the rounding of the exact value (v + 0.5)*scale -- which fma(v, scale, scale/2) rounds likewise (scale/2 is exact):

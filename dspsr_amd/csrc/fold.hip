@@ -922,14 +922,8 @@ static int fold_fold_impl(dspsr_amd_fold* f, const float* in_dev, uint64_t in_ch
       cps = (nchunk + nseg - 1) / nseg;
       nseg = (nchunk + cps - 1) / cps;
       const size_t need = (size_t)nseg * nrow * nbin * f->ndim;
-      if (need > f->part_floats) {
-        (void)hipStreamSynchronize(ctx->stream);
-        if (f->part) (void)hipFree(f->part);
-        f->part = nullptr; f->part_floats = 0;
-        if (hipMalloc((void**)&f->part, need * sizeof(float)) != hipSuccess)
-          return ctx_fail(ctx, DSPSR_AMD_ENOMEM, "dspsr_amd_fold_fold: hipMalloc of %zu partial-sum floats failed", need);
-        f->part_floats = need;
-      }
+      if (!grow_device_buffer(ctx->stream, f->part, f->part_floats, need))
+        return ctx_fail(ctx, DSPSR_AMD_ENOMEM, "dspsr_amd_fold_fold: hipMalloc of %zu partial-sum floats failed", need);
     }
     // planes of one channel folded together (ndim < 4): 4 or 2 rows per workgroup when the channels alone fill the chip
     // (one row per workgroup at Benchmark/fold.csh's shape, four times the workgroups: 311-313 against 321-331 Msamples/s, same box)

@@ -3,7 +3,8 @@
 dsp::TimeSeries places its rows at buffer + reserve_nfloat and seek() moves them by whole samples, so float32 rows start at any
 4-byte boundary with any channel and polarisation strides; the raw side channel takes any BitSeries::get_rawptr(), so an 8-bit
 block starts at any byte.  Pass 1 and the dispatcher (csrc/filterbank.hip fb_run) pick their loads from that address and those
-strides.  Every case below names, as a condition at file:line, the branch it is there for; blocks are placed by
+strides.  Every case below names the branch it is there for: a condition of the dispatcher (a function or local of
+filterbank.hip) or of a loader (file:line); blocks are placed by
 test_gpu_parity._fb_case (offset / row_pad, sentinel guards around the block, outputs asserted finite) and compared with the
 float64 oracle at the bounds of test_gpu_parity.py.  Only addresses whose alignment meets the width of the loads of the branch
 they target are built: the byte and half-word branches take any byte offset, UWB blocks multiples of 4, CASPSR multiples of 2.
@@ -33,8 +34,8 @@ def gpu():
 # ---- generic 8-bit blocks, multi-pass convolving filterbank ------------------------------------------------------------------
 # (C, M, nfilt, npart, kwargs, offset): part steps 6880 (real, C=16 M=256), 3488 (complex, C=32 M=128) are multiples of 4
 @pytest.mark.parametrize("C,M,nfilt,npart,kw,offset", [
-    # real dual-pol, one channel: fb_common.h:323 (one 32-bit word, base & 3 == 0; filterbank.hip:753 fast8 + k_raw_transpose),
-    # fb_common.h:325 (half words, base & 1 == 0), fb_common.h:329 (bytes, odd base)
+    # real dual-pol, one channel: fb_common.h:339 (one 32-bit word, base & 3 == 0; fb_pass1 fast8 + k_raw_transpose),
+    # fb_common.h:341 (half words, base & 1 == 0), fb_common.h:345 (bytes, odd base)
     (16, 256, (20, 21), 3, dict(max_parts=2), 0),
     (16, 256, (20, 21), 3, dict(max_parts=2), 1),
     (16, 256, (20, 21), 3, dict(max_parts=2), 2),
@@ -43,27 +44,27 @@ def gpu():
     # the same branches under the four-pass inverse (k_inv_a + k_inv_b)
     (16, 256, (20, 21), 3, dict(max_parts=2, four_pass=True), 1),
     (16, 256, (20, 21), 3, dict(max_parts=2, four_pass=True), 2),
-    # two input channels: fb_common.h:325 (nchan != 1, even base) and :329 (odd base); fast8 off (input_nchan != 1)
+    # two input channels: fb_common.h:341 (nchan != 1, even base) and :345 (odd base); fast8 off (input_nchan != 1)
     (16, 256, (20, 21), 2, dict(input_nchan=2), 0),
     (16, 256, (20, 21), 2, dict(input_nchan=2), 1),
-    # real single-pol at an odd base: fb_common.h:331-333 (one byte per sample, stride skip)
+    # real single-pol at an odd base: fb_common.h:347-349 (one byte per sample, stride skip)
     (16, 256, (20, 21), 2, dict(npol=1), 1),
-    # complex dual-pol, one channel, logR = 5 >= 3: offset 0 filterbank.hip:757 fastc (16-byte base, part step % 4 == 0:
-    # k_raw_transpose); offset 8 fb_common.h:340 (the uint2 load, base & 7 == 0, polarisation picked at :389); offsets 4, 2
-    # fb_common.h:345 (16-bit loads); offsets 1, 3 fb_common.h:349 (bytes)
+    # complex dual-pol, one channel, logR = 5 >= 3: offset 0 fb_pass1 fastc (16-byte base, part step % 4 == 0:
+    # k_raw_transpose); offset 8 fb_common.h:356 (the uint2 load, base & 7 == 0, polarisation picked at :405); offsets 4, 2
+    # fb_common.h:361 (16-bit loads); offsets 1, 3 fb_common.h:365 (bytes)
     (32, 128, (9, 10), 2, dict(real=False), 0),
     (32, 128, (9, 10), 2, dict(real=False), 8),
     (32, 128, (9, 10), 2, dict(real=False), 4),
     (32, 128, (9, 10), 2, dict(real=False), 2),
     (32, 128, (9, 10), 2, dict(real=False), 1),
     (32, 128, (9, 10), 2, dict(real=False), 3),
-    # complex, part step 4096 - 201 * 2 = 3694 = 2 (mod 4) on an aligned block: filterbank.hip:757 fastc off, fb_common.h:340
+    # complex, part step 4096 - 201 * 2 = 3694 = 2 (mod 4) on an aligned block: fb_pass1 fastc off, fb_common.h:356
     (2, 2048, (100, 101), 3, dict(real=False, max_parts=2), 0),
-    # complex with 3 input channels: fb_common.h:345 (even base), :349 (odd base); the uint2 load needs one channel
+    # complex with 3 input channels: fb_common.h:361 (even base), :365 (odd base); the uint2 load needs one channel
     (32, 128, (9, 10), 2, dict(real=False, input_nchan=3), 0),
     (32, 128, (9, 10), 2, dict(real=False, input_nchan=3), 2),
     (32, 128, (9, 10), 2, dict(real=False, input_nchan=3), 1),
-    # complex single-pol at an odd base: fb_common.h:349 (npol 1: no uint2 load at any address)
+    # complex single-pol at an odd base: fb_common.h:365 (npol 1: no uint2 load at any address)
     (32, 128, (9, 10), 2, dict(real=False, npol=1), 1),
 ])
 def test_generic_8bit_blocks_at_every_offset(oracle, gpu, C, M, nfilt, npart, kw, offset):
@@ -72,11 +73,11 @@ def test_generic_8bit_blocks_at_every_offset(oracle, gpu, C, M, nfilt, npart, kw
 
 # ---- two-pass family of short responses (complex dual-pol, nchan_subband * freq_res^2 = 2^27) ----------------------------------
 @pytest.mark.parametrize("input_nchan,offset", [
-    (1, 0),     # filterbank.hip:762 two: one input channel needs a 16-byte base (k_raw_cols' uint4 loads, fb_two_pass.hip:37)
-    (1, 8),     # not 16-byte aligned: two and fastc off, the three-pass kernels with fb_common.h:340 (uint2 loads)
-    (1, 1),     # the three-pass kernels with fb_common.h:349 (bytes)
-    (2, 4),     # filterbank.hip:762 two with k1c: several channels need a 4-byte base (fb_two_pass.hip:52, 32-bit loads)
-    (2, 2),     # 2-byte base: two off, three-pass kernels with fb_common.h:345
+    (1, 0),     # fb_takes_two_pass: one input channel needs a 16-byte base (k_raw_cols' uint4 loads, fb_two_pass.hip:37)
+    (1, 8),     # not 16-byte aligned: two and fastc off, the three-pass kernels with fb_common.h:356 (uint2 loads)
+    (1, 1),     # the three-pass kernels with fb_common.h:365 (bytes)
+    (2, 4),     # fb_takes_two_pass with k1c: several channels need a 4-byte base (fb_two_pass.hip:52, 32-bit loads)
+    (2, 2),     # 2-byte base: two off, three-pass kernels with fb_common.h:361
 ])
 def test_two_pass_family_at_offsets(oracle, gpu, input_nchan, offset):
     _fb_case(oracle, gpu, 512, 512, (27, 27), 2, npol=2, real=False, max_parts=2, input_nchan=input_nchan, offset=offset)
@@ -101,14 +102,14 @@ def test_odd_factor_complex_float_rows_at_odd_offsets(oracle, gpu):
 
 # ---- CASPSR ---------------------------------------------------------------------------------------------------------------
 def test_caspsr_block_at_a_group_boundary_not_16_byte_aligned(oracle, gpu):
-    # offset 8: filterbank.hip:753 fast8 (base % 4 == 0) with k_raw_transpose's CASPSR 32-bit loads (fb_fwd_cols.hip:45)
+    # offset 8: fb_pass1 fast8 (base % 4 == 0) with k_raw_transpose's CASPSR 32-bit loads (fb_fwd_cols.hip:45)
     _fb_case(oracle, gpu, 16, 256, (20, 21), 3, layout="caspsr", max_parts=2, offset=8)
-    # offset 2: fast8 off, fb_common.h:309 (16-bit loads)
+    # offset 2: fast8 off, fb_common.h:325 (16-bit loads)
     _fb_case(oracle, gpu, 16, 256, (20, 21), 3, layout="caspsr", max_parts=2, offset=2)
 
 
 def test_caspsr_part_step_not_a_multiple_of_4(oracle, gpu):
-    # C = 1 real, nfilt sum 601: part step 2 * (4096 - 601) = 6990 = 2 (mod 4): filterbank.hip:766 turns the regroup off
+    # C = 1 real, nfilt sum 601: part step 2 * (4096 - 601) = 6990 = 2 (mod 4): fb_pass1 turns the regroup off
     _fb_case(oracle, gpu, 1, 4096, (300, 301), 3, layout="caspsr", max_parts=2)
 
 
@@ -133,7 +134,7 @@ def test_odd_caspsr_and_uwb_addresses_are_refused(oracle, gpu):
 
 
 # ---- 16-bit UWB blocks in every family that takes them -------------------------------------------------------------------
-# part steps that are not multiples of 2048 and enough parts to cross at least three 2048-sample blocks; fb_common.h:313 reads t and
+# part steps that are not multiples of 2048 and enough parts to cross at least three 2048-sample blocks; fb_common.h:329 reads t and
 # t + 1 through their own block indices
 @pytest.mark.parametrize("C,M,nfilt,npart,npol,kw,offset", [
     (8, 256, (30, 31), 5, 2, dict(max_parts=2), 0),                 # three-pass, part step 1560
@@ -141,11 +142,11 @@ def test_odd_caspsr_and_uwb_addresses_are_refused(oracle, gpu):
     (8, 256, (30, 31), 5, 1, dict(max_parts=3), 12),
     (8, 256, (30, 31), 5, 2, dict(max_parts=2, four_pass=True), 4),  # four-pass (forced)
     (4, 16384, (900, 1100), 2, 2, dict(max_parts=2), 0),            # four-pass by length (freq_res > 8192), part step 57536
-    (512, 512, (27, 27), 2, 2, dict(max_parts=2), 0),               # the two-pass geometry: filterbank.hip:762 two needs kind 1,
+    (512, 512, (27, 27), 2, 2, dict(max_parts=2), 0),               # the two-pass geometry: fb_takes_two_pass needs kind 1,
                                                                     # so UWB takes the three-pass kernels; part step 234496
-    (1, 4096, (300, 301), 3, 2, dict(max_parts=2), 4),              # a conv1 object (nchan_subband 1, M <= 2^13): filterbank.hip:715
+    (1, 4096, (300, 301), 3, 2, dict(max_parts=2), 4),              # a conv1 object (nchan_subband 1, M <= 2^13): fb_run conv_rows
                                                                     # needs float rows, raw input falls back; part step 3495
-    (1, 32768, (3000, 2000), 2, 2, dict(max_parts=2), 0),           # a conv3 object (filterbank.hip:723), part step 27768
+    (1, 32768, (3000, 2000), 2, 2, dict(max_parts=2), 0),           # a conv3 object (fb_run conv_rows), part step 27768
 ])
 def test_uwb16_blocks_in_every_family(oracle, gpu, C, M, nfilt, npart, npol, kw, offset):
     _fb_case(oracle, gpu, C, M, nfilt, npart, npol=npol, real=False, layout="uwb16", offset=offset, **kw)
@@ -159,7 +160,7 @@ def test_uwb16_non_convolving(oracle, gpu, C, npart, npol):
 
 
 def test_uwb16_odd_factor_is_refused(oracle, gpu):
-    """filterbank.hip:815: k_sub_split de-interleaves 8-bit and float32 input only."""
+    """filterbank.hip fb_run_subbands: k_sub_split de-interleaves 8-bit and float32 input only."""
     dspsr_amd, ctx = gpu
     b = _fb_block(oracle, gpu, 96, 256, (20, 21), 2, real=False, layout="uwb16")
     out = torch.full((96, 2, 2 * 2 * b.plan.nkeep), -3.0, dtype=torch.float32, device="cuda")
@@ -199,15 +200,15 @@ def test_plain_filterbank_input_forms(oracle, gpu, C, npart, kw, offset):
 # polarisation strides); the shifted runs must meet the oracle and equal the aligned run to the bound of
 # test_filterbank_float_input_equals_raw.
 FLOAT_OBJECTS = {
-    # filterbank.hip:715 conv1 needs an 8-byte base and even strides: shifted rows fall back to the multi-pass kernels
+    # fb_run conv_rows (conv1) needs an 8-byte base and even strides: shifted rows fall back to the multi-pass kernels
     "conv1": (1, 4096, (300, 301), 3, dict(real=False, max_parts=2)),
     "conv1_3ch": (1, 4096, (300, 301), 2, dict(real=False, input_nchan=3, max_parts=2)),
-    # filterbank.hip:723 conv3 (M = 2^15): the same conditions
+    # fb_run conv_rows (conv3, M = 2^15): the same conditions
     "conv3": (1, 32768, (3000, 2000), 2, dict(real=False, max_parts=2)),
-    # filterbank.hip:749 batch (input_nchan 4, the four-pass kernels) needs an even channel stride, which two polarisation rows
+    # fb_run batch -> fb_run_batched (input_nchan 4, the four-pass kernels) needs an even channel stride, which two polarisation rows
     # keep under row_pad 1; its pass 1 reads 4-byte words, so shifted rows and odd polarisation strides stay on this path
     "batch": (1, 1024, (100, 90), 3, dict(real=False, input_nchan=4, max_parts=2, four_pass=True)),
-    # filterbank.hip:772 pretf (logR >= 6, 1 <= logT1 <= 4): a 16-byte base and strides % 4 == 0
+    # fb_pass1 FB_REGROUP_FLOAT (logR >= 6, 1 <= logT1 <= 4): a 16-byte base and strides % 4 == 0
     "pretf": (64, 1024, (100, 101), 2, dict(max_parts=2)),
     # fb_plain.hip F_FLOAT: scalar loads at any float address
     "plain": (128, 1, (0, 0), 70, dict()),
@@ -225,9 +226,9 @@ def test_float_rows_at_odd_offsets_and_strides(oracle, gpu, obj, offset, row_pad
 
 # ---- epilogues on shifted and UWB blocks ----------------------------------------------------------------------------------
 EPILOGUE_CASES = {
-    "generic_offset1": (16, 256, (20, 21), 4, dict(max_parts=2, offset=1)),                     # fb_common.h:329
-    "complex_offset2": (32, 128, (9, 10), 4, dict(real=False, max_parts=2, offset=2)),          # fb_common.h:345
-    "uwb16": (8, 256, (30, 31), 5, dict(real=False, layout="uwb16", max_parts=2, offset=4)),    # fb_common.h:313
+    "generic_offset1": (16, 256, (20, 21), 4, dict(max_parts=2, offset=1)),                     # fb_common.h:345
+    "complex_offset2": (32, 128, (9, 10), 4, dict(real=False, max_parts=2, offset=2)),          # fb_common.h:361
+    "uwb16": (8, 256, (30, 31), 5, dict(real=False, layout="uwb16", max_parts=2, offset=4)),    # fb_common.h:329
 }
 
 

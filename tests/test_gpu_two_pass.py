@@ -1,4 +1,4 @@
-"""The two-pass path of short responses (csrc/filterbank.hip, FB_HAS(6): k_raw_cols -> k_fwd_col1 -> k_rows_inv).
+"""The two-pass path of short responses (csrc/filterbank.hip fb_run_two_pass: k_raw_cols -> k_fwd_col1 -> k_rows_inv).
 
 Complex dual-pol 8-bit input with nchan_subband * freq_res^2 == 2^27 (BASELINE cfg 4: one 50 MHz sub-band, -F 512:D -x 512):
 the forward transform (2^14-point columns) and rows + chirp + inverse transforms in TWO workgroup tiles instead of three.

@@ -1,4 +1,4 @@
-"""Index model of the two-pass path (csrc/filterbank.hip FB_HAS(6)) in numpy: the decomposition the kernels implement --
+"""Index model of the two-pass path (csrc/filterbank.hip fb_run_two_pass) in numpy: the decomposition the kernels implement --
    n = nb + Fb*na, Fa = 2^14 as even/odd 2^13-point transforms + one radix-2 step (k_fwd_col1), A[a][nb][j] with ka = a*M + j,
    twiddle W_L^{nb*ka}, Fb-point transforms over nb -> kb, channel c = a + (Fa/M)*kb, chirp, inverse M-point transforms
    (k_rows_inv) -- equals the direct formulation of Filterbank.C:561-662 (forward FFT of L points, Response::operate, backward

@@ -361,6 +361,184 @@ __global__ __launch_bounds__(1024) void k_fold_dense(const float* __restrict__ i
         for (int d = 0; d < NDIM; d++) out[r * prof_span + bin[j] * NDIM + d] = acc[j][r][d];
 }
 
+// Several plans over the SAME detected rows (dspsr_amd_fold_fold_many: one Fold per pulsar, LoadToFold1.C:939-960).  Each
+// chunk of the rows is read from HBM into LDS once and folded into every plan of the group while it sits there.  The
+// (plan, bin) pairs of the group are laid end to end as "slots" -- plan k owns slots [slot0, slot0 + nbin) -- and the slots
+// are dealt to threads exactly as k_fold_chunked deals the bins of one plan: thread t of workgroup bz owns slots
+// bz + nz * (t + j * blockDim), j < FOLD_BPT, so a group of P plans costs the registers of ONE plan's walk (no per-plan
+// accumulator arrays, no scratch).  Per slot the plan is either dense (a per-chunk table as k_fold_dense, built over the
+// group's chunk grid, its entries travelling with the chunk prefetch) or a walk (the time-ordered interval list of
+// k_fold_chunked<., false, .>).  Either way one thread owns the (chan, pol, bin, dim) sum, starts it from the profile and adds
+// the samples one by one in time order: every profile is bit-identical to dspsr_amd_fold_fold of that plan alone.  The
+// chunk grid starts at the group's first sample; plans with later spans simply meet their first interval later.
+constexpr uint32_t FOLD_MANY_MAX = DSPSR_AMD_FOLD_MANY_MAX;   // plans per launch (bigger sets are split into several launches)
+struct FoldManyPlan {
+  float* prof;                  // profile, rows `span` floats apart
+  uint64_t span;
+  const uint32_t* bin_start;    // walk: intervals of bin b are iv[bin_start[b] .. bin_start[b+1])
+  const Interval* iv;
+  const uint32_t* tab;          // dense: tab[chunk * nbin + bin] over the group's chunk grid; NULL: walk
+  uint32_t nbin, slot0;
+};
+struct FoldManyArgs { FoldManyPlan p[FOLD_MANY_MAX]; uint32_t nplan, nslot; };
+// (pointers read from LDS are generic: cast to the global address space, or the loads become flat loads whose waits also drain
+//  LDS traffic)
+typedef __attribute__((address_space(1))) const uint64_t* GlobalU64;
+typedef __attribute__((address_space(1))) const uint32_t* GlobalU32;
+
+// (512 threads at most: with FOLD_BPT slots of cursor, table entry and accumulators per thread the 128 VGPRs of a 1024-thread
+//  workgroup spill; a group of many bins takes more workgroups per row instead)
+constexpr uint32_t FOLD_MANY_THREADS = 512;
+template <int NDIM, int NROW>
+__global__ __launch_bounds__(FOLD_MANY_THREADS) void k_fold_many(const float* __restrict__ in, const uint64_t chan_stride,
+                                                    const uint64_t pol_stride, const FoldManyArgs a, const uint64_t first,
+                                                    const uint64_t last)
+{
+  extern __shared__ __attribute__((aligned(16))) float fold_lds[];   // NROW x FOLD_CHUNK * NDIM floats
+  // the plan descriptors, copied once from the kernel arguments with constant indices (a divergent index into the
+  // argument struct could make the compiler copy it to scratch); a slot's plan is then an LDS read away
+  __shared__ FoldManyPlan desc[FOLD_MANY_MAX];
+  const uint32_t bz = blockIdx.x, nz = gridDim.x;
+  const uint32_t ipol = blockIdx.y * NROW, npol = gridDim.y * NROW, ichan = blockIdx.z;
+  constexpr uint32_t RS = FOLD_CHUNK * NDIM;
+  const uint32_t tid = threadIdx.x, nt = blockDim.x;
+  const float* __restrict__ row = in + ichan * chan_stride + ipol * pol_stride;
+  constexpr uint32_t NF4 = FOLD_CHUNK * NDIM / 4;
+  constexpr uint32_t MAXR = NF4 / 256;
+  if (tid == 0) {
+#pragma unroll
+    for (uint32_t k = 0; k < FOLD_MANY_MAX; k++) desc[k] = a.p[k];
+  }
+  __syncthreads();
+  // per owned slot: plan k and bin b (k = FOLD_MANY_MAX: no slot), the walk cursor, the dense table entry
+  uint32_t pk[FOLD_BPT], bin[FOLD_BPT], cur[FOLD_BPT], end[FOLD_BPT], tabn[FOLD_BPT];
+  Interval v0[FOLD_BPT], v1[FOLD_BPT];
+  float acc[FOLD_BPT][NROW][NDIM];
+  bool touched[FOLD_BPT];
+  auto load_iv = [&](const uint32_t k, const uint32_t i, const bool valid) -> Interval {
+    const GlobalU64 p = (GlobalU64)desc[k].iv + 2 * (valid ? i : 0u);   // Interval = {offset, hits | pad << 32}
+    Interval t;
+    t.offset = valid ? p[0] : ~0ull;
+    t.hits = valid ? (uint32_t)p[1] : 0u;
+    t.pad = 0;
+    return t;
+  };
+#pragma unroll
+  for (int j = 0; j < FOLD_BPT; j++) {
+    const uint32_t s = bz + nz * (tid + j * nt);
+    uint32_t k = FOLD_MANY_MAX;
+#pragma unroll
+    for (uint32_t q = 0; q < FOLD_MANY_MAX; q++)
+      if (q < a.nplan && s >= a.p[q].slot0 && s < a.nslot) k = q;      // (slot0 ascending)
+    pk[j] = k;
+    bin[j] = k < FOLD_MANY_MAX ? s - desc[k].slot0 : 0u;
+    cur[j] = end[j] = 0;
+    tabn[j] = 0;
+    const bool dense = k < FOLD_MANY_MAX && desc[k].tab;
+    if (k < FOLD_MANY_MAX && !dense) {
+      const GlobalU32 bs = (GlobalU32)desc[k].bin_start;
+      cur[j] = bs[bin[j]];
+      end[j] = bs[bin[j] + 1];
+    }
+    touched[j] = dense || cur[j] != end[j];
+    const uint32_t kk = k < FOLD_MANY_MAX ? k : 0u;
+    v0[j] = load_iv(kk, cur[j], cur[j] < end[j]);
+    v1[j] = load_iv(kk, cur[j] + 1, cur[j] + 1 < end[j]);
+    const float* __restrict__ out = touched[j] ? desc[k].prof + ((uint64_t)ichan * npol + ipol) * desc[k].span : nullptr;
+#pragma unroll
+    for (int r = 0; r < NROW; r++)
+#pragma unroll
+      for (int d = 0; d < NDIM; d++) acc[j][r][d] = touched[j] ? out[r * desc[k].span + bin[j] * NDIM + d] : 0.f;
+  }
+  const float* __restrict__ src0 = row + first * NDIM;
+  const uint64_t nfl_total = (last - first) * NDIM;
+  const uint32_t nchunk = (uint32_t)((last - first + FOLD_CHUNK - 1) / FOLD_CHUNK);
+  float4 pre[NROW][MAXR];
+  auto fetch = [&](const uint32_t c) {
+#pragma unroll
+    for (int rw = 0; rw < NROW; rw++) {
+      const float4* __restrict__ src = (const float4*)(src0 + rw * pol_stride);
+#pragma unroll
+      for (uint32_t r = 0; r < MAXR; r++) {
+        const uint32_t q = tid + r * nt;
+        const uint64_t k = (uint64_t)c * NF4 + q;
+        float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (q < NF4) {
+          if (4 * k + 4 <= nfl_total) {
+            v = src[k];
+          } else if (4 * k < nfl_total) {                  // ragged end of the span: never read past it
+            const float* t = (const float*)(src + k);
+            const uint32_t n = (uint32_t)(nfl_total - 4 * k);
+            v.x = t[0];
+            if (n > 1) v.y = t[1];
+            if (n > 2) v.z = t[2];
+          }
+        }
+        pre[rw][r] = v;
+      }
+    }
+#pragma unroll
+    for (int j = 0; j < FOLD_BPT; j++) {
+      const bool dense = pk[j] < FOLD_MANY_MAX && desc[pk[j]].tab;
+      tabn[j] = dense ? ((GlobalU32)desc[pk[j]].tab)[(uint64_t)c * desc[pk[j]].nbin + bin[j]] : 0u;
+    }
+  };
+  if (nchunk) fetch(0);
+  for (uint32_t c = 0; c < nchunk; c++) {
+    __syncthreads();                                    // previous chunk fully consumed
+#pragma unroll
+    for (int rw = 0; rw < NROW; rw++)
+#pragma unroll
+      for (uint32_t r = 0; r < MAXR; r++)
+        if (tid + r * nt < NF4) ((float4*)(fold_lds + rw * RS))[tid + r * nt] = pre[rw][r];
+    uint32_t tabc[FOLD_BPT];
+#pragma unroll
+    for (int j = 0; j < FOLD_BPT; j++) tabc[j] = tabn[j];
+    if (c + 1 < nchunk) fetch(c + 1);
+    __syncthreads();
+    const uint64_t c0 = first + (uint64_t)c * FOLD_CHUNK, c1 = c0 + FOLD_CHUNK;
+#pragma unroll
+    for (int j = 0; j < FOLD_BPT; j++) {
+      {                                                 // dense slot: at most one run in this chunk
+        const uint32_t n = tabc[j] >> 11, x0 = (tabc[j] & 2047u) * NDIM;
+#pragma unroll 4
+        for (uint32_t h = 0; h < n; h++)
+#pragma unroll
+          for (int r = 0; r < NROW; r++)
+#pragma unroll
+            for (int d = 0; d < NDIM; d++) acc[j][r][d] += fold_lds[r * RS + x0 + h * NDIM + d];
+      }
+      while (v0[j].offset < c1) {                       // walk slot (`none` has offset ~0 and ends the walk)
+        const Interval v = v0[j];
+        const uint64_t lo = v.offset > c0 ? v.offset : c0;
+        const uint64_t hi = v.offset + v.hits < c1 ? v.offset + v.hits : c1;
+        const uint32_t x0 = (uint32_t)(lo - c0) * NDIM;
+        const uint32_t n = (uint32_t)(hi - lo);
+#pragma unroll 4
+        for (uint32_t h = 0; h < n; h++)
+#pragma unroll
+          for (int r = 0; r < NROW; r++)
+#pragma unroll
+            for (int d = 0; d < NDIM; d++) acc[j][r][d] += fold_lds[r * RS + x0 + h * NDIM + d];
+        if (v.offset + v.hits > c1) break;              // the interval continues in the next chunk
+        cur[j]++;
+        v0[j] = v1[j];
+        v1[j] = load_iv(pk[j], cur[j] + 1, cur[j] + 1 < end[j]);
+      }
+    }
+  }
+#pragma unroll
+  for (int j = 0; j < FOLD_BPT; j++) {
+    if (!touched[j]) continue;
+    const uint32_t k = pk[j];
+    float* __restrict__ out = desc[k].prof + ((uint64_t)ichan * npol + ipol) * desc[k].span;
+#pragma unroll
+    for (int r = 0; r < NROW; r++)
+#pragma unroll
+      for (int d = 0; d < NDIM; d++) out[r * desc[k].span + bin[j] * NDIM + d] = acc[j][r][d];
+  }
+}
+
 // LONG: profile[row][bin][dim] += partial sums of the time segments, in time order
 __global__ __launch_bounds__(256) void k_fold_combine(float* __restrict__ prof, const uint64_t prof_span, const float* __restrict__ part,
                                                       const uint32_t nrow, const uint32_t row_floats, const uint32_t nseg)
@@ -774,6 +952,86 @@ extern "C" int dspsr_amd_fold_zero(dspsr_amd_fold* f)
   return DSPSR_AMD_OK;
 }
 
+// One walk over the runs of the pending plan decides which kernel folds them: the longest run (the return value; re-associated
+// sums, see FOLD_LONG_RUN) and, when try_dense, whether the plan fits the dense per-chunk table of k_fold_dense over the chunk
+// grid that starts at `first` -- at most one run per (chunk, phase bin), runs cut at the chunk ends; a plan with two runs of a
+// bin inside a chunk (a folding period shorter than the chunk) does not.  The table is also refused when it would be more than
+// a quarter of the bytes it helps to fold (few channels, many bins).  (This host code runs once per block next to a kernel of a
+// few hundred microseconds: at Benchmark/fold.csh's shape the three separate walks and the bucket sort below, which the dense
+// kernel does not read, made the host as slow as the device -- profiles/r05_experiments.txt item 6.)
+static uint32_t plan_scan(dspsr_amd_fold* f, bool try_dense, uint64_t first, uint64_t last, size_t* ntab, bool* one_per_chunk)
+{
+  const uint32_t nbin = f->nbin;
+  uint32_t max_run = 0;
+  bool ok = try_dense;
+  *ntab = 0;
+  if (ok) {
+    const uint64_t nchunk = (last - first + FOLD_CHUNK - 1) / FOLD_CHUNK;
+    *ntab = (size_t)nchunk * nbin;
+    const uint64_t data_words = (last - first) * (uint64_t)f->nchan * f->npol * f->ndim;
+    ok = *ntab <= ((size_t)1 << 24) && 4 * (uint64_t)*ntab <= data_words;
+  }
+  if (ok) {
+    f->cursor.assign(nbin, ~0u);                            // (scratch: chunk of the bin's previous piece)
+    uint32_t* const lastc = f->cursor.data();
+    for (const RunBin& r : f->binplan) {
+      if (r.hits > max_run) max_run = r.hits;
+      if (r.hits == 0 || !ok) continue;
+      const uint64_t c0 = (r.offset - first) / FOLD_CHUNK, c1 = (r.offset - first + r.hits - 1) / FOLD_CHUNK;
+      if (lastc[r.ibin] == (uint32_t)c0) ok = false;                       // a second run of this bin in the chunk
+      lastc[r.ibin] = (uint32_t)c1;
+    }
+  } else {
+    for (const RunBin& r : f->binplan) if (r.hits > max_run) max_run = r.hits;
+  }
+  *one_per_chunk = ok;
+  return max_run;
+}
+
+// the intervals bucketed by phase bin (stable => time order kept inside a bin): what the walk kernels and the per-channel hit
+// count of a zeroed input read -- not the dense kernel
+static void plan_bucket(dspsr_amd_fold* f, PlanSlot& sl)
+{
+  const uint32_t nbin = f->nbin;
+  for (uint32_t b = 0; b <= nbin; b++) sl.h_bin_start[b] = 0;
+  for (const RunBin& r : f->binplan) sl.h_bin_start[r.ibin + 1]++;
+  for (uint32_t b = 0; b < nbin; b++) sl.h_bin_start[b + 1] += sl.h_bin_start[b];
+  f->cursor.assign(sl.h_bin_start, sl.h_bin_start + nbin);
+  for (const RunBin& r : f->binplan) {
+    Interval v; v.offset = r.offset; v.hits = r.hits; v.pad = 0;
+    sl.h_iv[f->cursor[r.ibin]++] = v;
+  }
+}
+
+// the dense table tab[chunk][bin] = first sample of the run inside the chunk | samples << 11 (0: none) over the chunk grid that
+// starts at `first`, in the slot's aux buffers; false: allocation failed
+static bool plan_dense_fill(dspsr_amd_fold* f, PlanSlot& sl, uint64_t first, size_t ntab)
+{
+  const uint32_t nbin = f->nbin;
+  if (ntab > sl.aux_cap) {
+    if (sl.h_aux) (void)hipHostFree(sl.h_aux);
+    if (sl.d_aux) (void)hipFree(sl.d_aux);
+    sl.h_aux = nullptr; sl.d_aux = nullptr; sl.aux_cap = 0;
+    const size_t n = ntab + ntab / 4 + 1024;
+    if (hipHostMalloc((void**)&sl.h_aux, n * sizeof(uint32_t)) != hipSuccess || hipMalloc((void**)&sl.d_aux, n * sizeof(uint32_t)) != hipSuccess)
+      return false;
+    sl.aux_cap = n;
+  }
+  ::memset((void*)sl.h_aux, 0, ntab * sizeof(uint32_t));
+  for (const RunBin& r : f->binplan) {
+    uint64_t off = r.offset - first;
+    uint32_t left = r.hits;
+    while (left) {
+      const uint64_t c = off / FOLD_CHUNK;
+      const uint32_t s0 = (uint32_t)(off % FOLD_CHUNK), n = left < FOLD_CHUNK - s0 ? left : FOLD_CHUNK - s0;
+      sl.h_aux[c * nbin + r.ibin] = s0 | (n << 11);
+      off += n;
+      left -= n;
+    }
+  }
+  return true;
+}
+
 static int fold_fold_impl(dspsr_amd_fold* f, const float* in_dev, uint64_t in_chan_stride, uint64_t in_pol_stride,
                           uint32_t* hits_dev);
 
@@ -821,75 +1079,17 @@ static int fold_fold_impl(dspsr_amd_fold* f, const float* in_dev, uint64_t in_ch
   uint64_t first = f->binplan.front().offset, last = f->binplan.back().offset + f->binplan.back().hits;
   first -= first % 4;                                  // keeps 16-byte alignment of the chunk loads for any ndim
   const bool aligned = ((uintptr_t)in_dev % 16 == 0) && (in_chan_stride % 4 == 0) && (in_pol_stride % 4 == 0);
-  // One walk over the runs decides which kernel folds them: the longest run (re-associated sums, see FOLD_LONG_RUN) and whether
-  // the plan fits the dense per-chunk table of k_fold_dense -- at most one run per (chunk, phase bin), runs cut at the chunk ends;
-  // a plan with two runs of a bin inside a chunk (a folding period shorter than the chunk) does not.  The table is also refused
-  // when it would be more than a quarter of the bytes it helps to fold (few channels, many bins).  (This host code runs once per
-  // block next to a kernel of a few hundred microseconds: at Benchmark/fold.csh's shape the three separate walks and the bucket
-  // sort below, which the dense kernel does not read, made the host as slow as the device -- profiles/r05_experiments.txt item 6.)
-  uint32_t max_run = 0;
-  bool one_per_chunk = aligned && nbin <= (uint32_t)FOLD_BPT * 1024;
+  // the longest run and whether the plan fits the dense table (plan_scan)
   size_t ntab = 0;
-  if (one_per_chunk) {
-    const uint64_t nchunk = (last - first + FOLD_CHUNK - 1) / FOLD_CHUNK;
-    ntab = (size_t)nchunk * nbin;
-    const uint64_t data_words = (last - first) * (uint64_t)f->nchan * f->npol * f->ndim;
-    one_per_chunk = ntab <= ((size_t)1 << 24) && 4 * (uint64_t)ntab <= data_words;
-  }
-  if (one_per_chunk) {
-    f->cursor.assign(nbin, ~0u);                            // (scratch: chunk of the bin's previous piece)
-    uint32_t* const lastc = f->cursor.data();
-    for (const RunBin& r : f->binplan) {
-      if (r.hits > max_run) max_run = r.hits;
-      if (r.hits == 0 || !one_per_chunk) continue;
-      const uint64_t c0 = (r.offset - first) / FOLD_CHUNK, c1 = (r.offset - first + r.hits - 1) / FOLD_CHUNK;
-      if (lastc[r.ibin] == (uint32_t)c0) one_per_chunk = false;             // a second run of this bin in the chunk
-      lastc[r.ibin] = (uint32_t)c1;
-    }
-  } else {
-    for (const RunBin& r : f->binplan) if (r.hits > max_run) max_run = r.hits;
-  }
+  bool one_per_chunk = false;
+  const uint32_t max_run = plan_scan(f, aligned && nbin <= (uint32_t)FOLD_BPT * 1024, first, last, &ntab, &one_per_chunk);
   const bool lng = aligned && nbin <= (uint32_t)FOLD_BPT * 1024 && max_run >= FOLD_LONG_RUN;   // re-associated sums (see FOLD_LONG_RUN)
   const bool will_dense = one_per_chunk && !lng;
-  // the intervals bucketed by phase bin (stable => time order kept inside a bin): what the walk kernels and the per-channel hit
-  // count of a zeroed input read -- not the dense kernel
   const bool need_iv = !will_dense || hits_dev;
-  if (need_iv) {
-    for (uint32_t b = 0; b <= nbin; b++) sl.h_bin_start[b] = 0;
-    for (const RunBin& r : f->binplan) sl.h_bin_start[r.ibin + 1]++;
-    for (uint32_t b = 0; b < nbin; b++) sl.h_bin_start[b + 1] += sl.h_bin_start[b];
-    f->cursor.assign(sl.h_bin_start, sl.h_bin_start + nbin);
-    for (const RunBin& r : f->binplan) {
-      Interval v; v.offset = r.offset; v.hits = r.hits; v.pad = 0;
-      sl.h_iv[f->cursor[r.ibin]++] = v;
-    }
-  }
-  bool dense = will_dense;
-  {
-    if (dense) {
-      if (ntab > sl.aux_cap) {
-        if (sl.h_aux) (void)hipHostFree(sl.h_aux);
-        if (sl.d_aux) (void)hipFree(sl.d_aux);
-        sl.h_aux = nullptr; sl.d_aux = nullptr; sl.aux_cap = 0;
-        const size_t n = ntab + ntab / 4 + 1024;
-        if (hipHostMalloc((void**)&sl.h_aux, n * sizeof(uint32_t)) != hipSuccess || hipMalloc((void**)&sl.d_aux, n * sizeof(uint32_t)) != hipSuccess)
-          return ctx_fail(ctx, DSPSR_AMD_ENOMEM, "dspsr_amd_fold_fold: plan allocation failed");
-        sl.aux_cap = n;
-      }
-      ::memset((void*)sl.h_aux, 0, ntab * sizeof(uint32_t));
-      for (const RunBin& r : f->binplan) {
-        uint64_t off = r.offset - first;
-        uint32_t left = r.hits;
-        while (left) {
-          const uint64_t c = off / FOLD_CHUNK;
-          const uint32_t s0 = (uint32_t)(off % FOLD_CHUNK), n = left < FOLD_CHUNK - s0 ? left : FOLD_CHUNK - s0;
-          sl.h_aux[c * nbin + r.ibin] = s0 | (n << 11);
-          off += n;
-          left -= n;
-        }
-      }
-    }
-  }
+  if (need_iv) plan_bucket(f, sl);
+  const bool dense = will_dense;
+  if (dense && !plan_dense_fill(f, sl, first, ntab))
+    return ctx_fail(ctx, DSPSR_AMD_ENOMEM, "dspsr_amd_fold_fold: plan allocation failed");
   {
     const PlanCopy pc[3] = {{sl.d_bin_start, sl.h_bin_start, need_iv ? (nbin + 1) * sizeof(uint32_t) : 0},
                             {sl.d_iv, sl.h_iv, need_iv ? niv * sizeof(Interval) : 0},
@@ -976,6 +1176,151 @@ static int fold_fold_impl(dspsr_amd_fold* f, const float* in_dev, uint64_t in_ch
   if (e != hipSuccess) return ctx_fail(ctx, DSPSR_AMD_EHIP, "dspsr_amd_fold_fold: %s", hipGetErrorString(e));
   sl.pending = true;
   f->binplan.clear();
+  return DSPSR_AMD_OK;
+}
+
+// One launch of k_fold_many over the group g[0 .. n) (n <= FOLD_MANY_MAX), every plan pending, exact order (no LONG run), rows
+// 16-byte aligned and nbin within the chunk kernels: each plan goes through its own double-buffered slot as in fold_fold_impl.
+static int fold_many_group(dspsr_amd_fold* const* g, uint32_t n, const float* in_dev, uint64_t in_chan_stride,
+                           uint64_t in_pol_stride)
+{
+  dspsr_amd_fold* f0 = g[0];
+  dspsr_amd_ctx* ctx = f0->ctx;
+  // the chunk grid of the group starts at the first sample of any plan (rounded down: 16-byte aligned chunk loads) and ends
+  // with the last one
+  uint64_t first = ~0ull, last = 0;
+  for (uint32_t k = 0; k < n; k++) {
+    dspsr_amd_fold* f = g[k];
+    if (f->current_hits) f->binplan.back().hits = f->current_hits;   // FoldCUDA.cu:163-164
+    f->current_hits = 0;
+    f->current_bin = f->folding_nbin;
+    const uint64_t a = f->binplan.front().offset, b = f->binplan.back().offset + f->binplan.back().hits;
+    if (a < first) first = a;
+    if (b > last) last = b;
+  }
+  first -= first % 4;
+  FoldManyArgs args;
+  ::memset((void*)&args, 0, sizeof(args));
+  PlanSlot* used[FOLD_MANY_MAX];
+  uint32_t nslot = 0;
+  for (uint32_t k = 0; k < n; k++) {
+    dspsr_amd_fold* f = g[k];
+    const uint32_t nbin = f->nbin;
+    PlanSlot& sl = f->slot[f->next_slot];
+    f->next_slot ^= 1;
+    if (sl.pending) {            // the fold that last used this slot (two calls ago) must have consumed it
+      const hipError_t e = hipEventSynchronize(sl.done);
+      if (e != hipSuccess) return ctx_fail(ctx, DSPSR_AMD_EHIP, "dspsr_amd_fold_fold_many: %s", hipGetErrorString(e));
+      sl.pending = false;
+    }
+    if (!slot_reserve(sl, nbin + 1, f->binplan.size()))
+      return ctx_fail(ctx, DSPSR_AMD_ENOMEM, "dspsr_amd_fold_fold_many: plan allocation failed");
+    size_t ntab = 0;
+    bool dense = false;
+    (void)plan_scan(f, true, first, last, &ntab, &dense);
+    if (dense) {
+      if (!plan_dense_fill(f, sl, first, ntab)) return ctx_fail(ctx, DSPSR_AMD_ENOMEM, "dspsr_amd_fold_fold_many: plan allocation failed");
+    } else {
+      plan_bucket(f, sl);
+    }
+    const PlanCopy pc[3] = {{sl.d_bin_start, sl.h_bin_start, dense ? 0 : (nbin + 1) * sizeof(uint32_t)},
+                            {sl.d_iv, sl.h_iv, dense ? 0 : f->binplan.size() * sizeof(Interval)},
+                            {sl.d_aux, sl.h_aux, dense ? ntab * sizeof(uint32_t) : 0}};
+    const hipError_t e = plan_upload(f, sl, pc, 3);
+    if (e != hipSuccess) return ctx_fail(ctx, DSPSR_AMD_EHIP, "dspsr_amd_fold_fold_many: plan copy: %s", hipGetErrorString(e));
+    if (fold_plan_wait(f, &sl) != DSPSR_AMD_OK) return DSPSR_AMD_EHIP;
+    FoldManyPlan& p = args.p[k];
+    p.prof = f->profile;
+    p.span = f->span;
+    p.bin_start = sl.d_bin_start;
+    p.iv = sl.d_iv;
+    p.tab = dense ? sl.d_aux : nullptr;
+    p.nbin = nbin;
+    p.slot0 = nslot;
+    nslot += nbin;
+    used[k] = &sl;
+  }
+  args.nplan = n;
+  args.nslot = nslot;
+  // slots dealt to nz workgroups per row: enough for FOLD_BPT slots per thread, and (as fold_fold_impl splits the bins) at least
+  // two workgroups per CU when the band has few rows.  Siblings of a row are neighbours in blockIdx.x and run at the same time,
+  // so that the re-reads of its chunks come from the Infinity Cache.
+  const uint32_t nrow = f0->npol * f0->nchan;
+  uint32_t nz = 1;
+  while ((uint64_t)nz * FOLD_BPT * FOLD_MANY_THREADS < nslot) nz *= 2;
+  while (nz < 8 && (uint64_t)nrow * nz < 512 && nslot / (2 * nz) >= 64) nz *= 2;
+  const uint32_t slots_wg = (nslot + nz - 1) / nz;
+  uint32_t threads = ((slots_wg + FOLD_BPT - 1) / FOLD_BPT + 63) / 64 * 64;
+  if (threads < 256) threads = 256;
+  if (threads > FOLD_MANY_THREADS) threads = FOLD_MANY_THREADS;
+  const uint32_t ndim = f0->ndim, npol = f0->npol;
+  const uint32_t nrw = (ndim * npol == 4 && ndim < 4 && (uint64_t)f0->nchan * nz >= 2 * ctx->ncu) ? npol : 1u;
+  const dim3 grid(nz, npol / nrw, f0->nchan);
+  const size_t lds = (size_t)FOLD_CHUNK * ndim * nrw * sizeof(float);
+#define FOLD_MANY(ND, NR) hipLaunchKernelGGL((k_fold_many<ND, NR>), grid, dim3(threads), lds, ctx->stream, in_dev, in_chan_stride, \
+                                            in_pol_stride, args, first, last)
+  if (ndim == 4) FOLD_MANY(4, 1);
+  else if (ndim == 2 && nrw == 2) FOLD_MANY(2, 2);
+  else if (ndim == 2) FOLD_MANY(2, 1);
+  else if (nrw == 4) FOLD_MANY(1, 4);
+  else FOLD_MANY(1, 1);
+#undef FOLD_MANY
+  hipError_t e = hipGetLastError();
+  for (uint32_t k = 0; k < n && e == hipSuccess; k++) {
+    e = hipEventRecord(used[k]->done, ctx->stream);
+    if (e == hipSuccess) used[k]->pending = true;
+    g[k]->binplan.clear();
+  }
+  if (e != hipSuccess) return ctx_fail(ctx, DSPSR_AMD_EHIP, "dspsr_amd_fold_fold_many: %s", hipGetErrorString(e));
+  return DSPSR_AMD_OK;
+}
+
+extern "C" int dspsr_amd_fold_fold_many(dspsr_amd_fold* const* folds, uint32_t nfold, const float* in_dev,
+                                        uint64_t in_chan_stride, uint64_t in_pol_stride, uint32_t* nshared)
+{
+  if (nshared) *nshared = 0;
+  if (nfold == 0) return DSPSR_AMD_OK;
+  if (!folds || !in_dev) return DSPSR_AMD_EINVAL;
+  // every refusal comes before any plan is touched
+  for (uint32_t i = 0; i < nfold; i++) {
+    dspsr_amd_fold* f = folds[i];
+    if (!f) return DSPSR_AMD_EINVAL;
+    for (uint32_t j = 0; j < i; j++)
+      if (folds[j] == f) return ctx_fail(f->ctx, DSPSR_AMD_EINVAL, "dspsr_amd_fold_fold_many: fold %u given twice", i);
+    if (f->ctx != folds[0]->ctx) return ctx_fail(f->ctx, DSPSR_AMD_EINVAL, "dspsr_amd_fold_fold_many: fold %u of another context", i);
+    if (f->nchan != folds[0]->nchan || f->npol != folds[0]->npol || f->ndim != folds[0]->ndim)
+      return ctx_fail(f->ctx, DSPSR_AMD_EINVAL, "dspsr_amd_fold_fold_many: fold %u has another nchan / npol / ndim", i);
+    if (!f->profile) return ctx_fail(f->ctx, DSPSR_AMD_ESTATE, "dspsr_amd_fold_fold_many: fold %u: set_shape not called", i);
+    if (f->folding_nbin != f->nbin)    // Fold.C:806-809
+      return ctx_fail(f->ctx, DSPSR_AMD_EINVAL, "dsp::Fold::fold folding_nbin != output->nbin (%u != %u), fold %u",
+                      f->folding_nbin, f->nbin, i);
+  }
+  // the rules of fold_fold_impl: exact-order plans of the chunk kernels share the launch; LONG runs and k_fold_direct (unaligned
+  // rows, nbin beyond the chunk kernels) go through the single-fold code; empty plans are skipped
+  const bool aligned = ((uintptr_t)in_dev % 16 == 0) && (in_chan_stride % 4 == 0) && (in_pol_stride % 4 == 0);
+  std::vector<dspsr_amd_fold*> shared;
+  for (uint32_t i = 0; i < nfold; i++) {
+    dspsr_amd_fold* f = folds[i];
+    if (f->binplan.empty()) continue;
+    if (aligned && f->nbin <= (uint32_t)FOLD_BPT * 1024 && fold_plan_max_run(f) < FOLD_LONG_RUN) {
+      shared.push_back(f);
+      continue;
+    }
+    const int rc = fold_fold_impl(f, in_dev, in_chan_stride, in_pol_stride, nullptr);
+    if (rc != DSPSR_AMD_OK) return rc;
+  }
+  // a lone exact-order plan gains nothing from sharing: the single-fold kernels fold it with the same sums, faster
+  if (shared.size() == 1) return fold_fold_impl(shared[0], in_dev, in_chan_stride, in_pol_stride, nullptr);
+  // launches of at most FOLD_MANY_MAX plans, their sizes balanced (9 plans: 5 + 4), so that no launch holds a single plan
+  const size_t ngroup = (shared.size() + FOLD_MANY_MAX - 1) / FOLD_MANY_MAX;
+  for (size_t g = 0, i = 0; g < ngroup; g++) {
+    const size_t end = shared.size() * (g + 1) / ngroup;
+    const uint32_t n = (uint32_t)(end - i);
+    const int rc = fold_many_group(shared.data() + i, n, in_dev, in_chan_stride, in_pol_stride);
+    if (rc != DSPSR_AMD_OK) return rc;
+    if (nshared) *nshared += n;
+    i = end;
+  }
   return DSPSR_AMD_OK;
 }
 

@@ -259,20 +259,20 @@ class DadaFile:
             yield src, npart
 
 
-def fold_file(path, cfg, polyco=None, device=0, stream=None, reference_phase=0.0, dump_before=(), dump_dir="."):
+def fold_file(path, cfg, polyco=None, device=0, stream=None, reference_phase=0.0, dump_before=(), dump_dir=".", targets=None):
     """The reference's `dspsr file.dada -F nchan:D ...` on one GPU: open the file, build the pipeline from its header,
-    feed every block, close the last sub-integration.  Returns the LoadToFold (its .subints hold the results; the caller
-    closes it)."""
+    feed every block, close the last sub-integration.  Returns the LoadToFold (its .subints hold the results -- with several
+    `targets` (pipeline.FoldTarget), .pulsars[k].subints; the caller closes it)."""
     from .pipeline import LoadToFold
     f = DadaFile(path)
     lt = LoadToFold(cfg, f.info, device=device, stream=stream, polyco=polyco, reference_phase=reference_phase,
-                    dump_before=dump_before, dump_dir=dump_dir)
+                    dump_before=dump_before, dump_dir=dump_dir, targets=targets)
     if f.nblocks(lt) == (0, 0):
         lt.close()
         raise DspsrAmdError("dspsr_amd.fold_file: %s holds %d samples, fewer than one overlap-save part (%d)"
                             % (path, f.ndat, lt.nsamp_overlap + lt.nsamp_step))
     lt.process_host_blocks(f.blocks(lt))
-    if lt.ndat_total:
+    if lt.ndat_total or lt.pulsars:
         lt.finish_subint()
     lt.synchronize()
     return lt

@@ -609,6 +609,21 @@ class FoldEngine:
         cs, ps = _strides3(inp)
         _check(self.ctx.handle, lib.dspsr_amd_fold_fold(self.handle, inp.data_ptr(), cs, ps), "dspsr_amd_fold_fold")
 
+    @staticmethod
+    def fold_many(folds, inp) -> int:
+        """fold() of several engines over the same detected rows (one Fold per pulsar): the exact-order plans share launches that
+        read `inp` once (dspsr_amd_fold_fold_many); every profile ends bit-identical to its own fold().  Returns how many engines
+        took a shared launch (two or more exact-order plans share; a lone one is folded by fold())."""
+        folds = list(folds)
+        if not folds:
+            return 0
+        cs, ps = _strides3(inp)
+        handles = (C.c_void_p * len(folds))(*[f.handle for f in folds])
+        n = C.c_uint32(0)
+        _check(folds[0].ctx.handle, lib.dspsr_amd_fold_fold_many(handles, len(folds), inp.data_ptr(), cs, ps, C.byref(n)),
+               "dspsr_amd_fold_fold_many")
+        return n.value
+
     def fold_zeroed(self, inp, hits_dev):
         """fold() of an input with zeroed samples: hits_dev (uint32 device tensor [nchan][nbin]) counts, per channel, the
         planned samples of polarisation 0 whose first float is not zero (Fold.C:853-866)."""

@@ -13,6 +13,7 @@ from __future__ import annotations
 
 import math
 import os
+import dataclasses
 from dataclasses import dataclass
 
 import numpy as np
@@ -65,6 +66,28 @@ class Config:
                                            # alone (no coherent dedispersion)
     record_time: bool = False              # -r: time every operation (Operation.C:90-113); each one then ends with a stream
                                            # synchronisation so that the wall times are honest (FilterbankCUDA.cu:302-303)
+
+
+@dataclass
+class FoldTarget:
+    """One pulsar of a multi-pulsar run (dspsr -P a.polyco -P b.polyco / -c ... -c ...; LoadToFold1.C:917-960 gives each its own
+    Fold, sub-integration divider and unloader)."""
+    name: str = ""
+    polyco: object = None             # Polyco / ChebyPredictor, or None with folding_period
+    folding_period: float = 0.0       # seconds (used when polyco is None)
+    reference_phase: float = 0.0
+    nbin: int = 0                     # 0: dsp::Fold::choose_nbin for this pulsar's period (Fold.C:291-382, per Fold)
+
+
+class _PulsarFold:
+    """The per-pulsar state of a multi-target LoadToFold: the fold engine and the PhaseSeries bookkeeping."""
+
+    def __init__(self, target, nbin, fold):
+        self.target, self.nbin, self.fold = target, nbin, fold
+        self.hits = np.zeros(nbin, dtype=np.uint32)
+        self.integration_length, self.ndat_total = 0.0, 0
+        self.turns = None             # TurnsDivider (-s / -turns: boundaries differ per pulsar)
+        self.subints = []
 
 
 @dataclass
@@ -773,7 +796,32 @@ class LoadToFold:
 
     def __init__(self, cfg: Config, info: InputInfo, device: int = 0, stream: int | None = None,
                  polyco: Polyco | None = None, reference_phase: float = 0.0, subband: int | None = None,
-                 dump_before=(), dump_dir="."):
+                 dump_before=(), dump_dir=".", targets=None):
+        """targets: FoldTarget list, one Fold per pulsar (dspsr -P a -P b / -c p1 -c p2, LoadToFold1.C:917-960).  They replace
+        polyco / reference_phase / cfg.folding_period, and cfg.nbin by each target's nbin, or by Fold::choose_nbin for its period
+        where the target's nbin is 0 (also with a single target).  One target: the single-pulsar path of this class, unchanged.  Several: `pulsars` holds one fold engine, hits, sub-integration divider and `subints` list per
+        target; Detection writes the detected rows and the pulsars fold them with FoldEngine.fold_many (the rows are read once);
+        `subints` / `hits` of the instance itself stay empty.  Multi-GPU exchange (subband, communicators) is single-pulsar only."""
+        targets = list(targets or [])
+        self.pulsars = []
+        if len(targets) > 1 and subband is not None:
+            raise DspsrAmdError("dspsr_amd.LoadToFold: sub-band sharded runs fold one pulsar; %d targets given" % len(targets))
+        for t in targets:                                # (before any device resource is opened)
+            if t.polyco is None and t.folding_period <= 0:
+                raise DspsrAmdError("dsp::Fold::fold no polynomial and no period specified (target %r)" % (t.name,))
+        if targets:
+            t = targets[0]
+            cfg = dataclasses.replace(cfg, folding_period=t.folding_period if t.polyco is None else 0.0)
+            polyco, reference_phase = t.polyco, t.reference_phase
+        self._init_pipeline(cfg, info, device, stream, polyco, reference_phase, subband, dump_before, dump_dir)
+        if targets:
+            try:
+                self._init_targets(targets)
+            except BaseException:
+                self.close()
+                raise
+
+    def _init_pipeline(self, cfg, info, device, stream, polyco, reference_phase, subband, dump_before, dump_dir):
         """subband = g: this instance is rank g of a sub-band sharded run.  `info`/`cfg` still describe the
         WHOLE band (info.nchan input channels, cfg.nchan output channels); the instance processes input channel g only:
         its block holds that channel's bytes alone ([t][pol][dim], what a rank reads from the NCHAN-interleaved file),
@@ -898,6 +946,28 @@ class LoadToFold:
         self.nsamples_in = 0            # unique input samples consumed (per pol)
         self.ndat_out = 0               # output samples produced so far
         self.subints = []               # completed sub-integrations (host copies) on the writer rank
+
+    def _init_targets(self, targets):
+        """nbin per target (Fold::choose_nbin for its period where the target gives none); several targets: one FoldEngine each,
+        the fused fold off (the detected rows are shared)."""
+        cfg, info = self.cfg, self.info
+        nbins = []
+        for t in targets:
+            p = t.folding_period if t.polyco is None else 1.0 / t.polyco.frequency(info.mjd_day, info.mjd_sec + self.out_start)
+            nbins.append(t.nbin or choose_nbin(p, self.out_rate))
+        if len(targets) == 1:
+            if nbins[0] != cfg.nbin:
+                self.cfg = dataclasses.replace(cfg, nbin=nbins[0])
+                self.fold.set_shape(self.nchan_out, self.npol_out, cfg.ndim, nbins[0])
+                self.hits = np.zeros(nbins[0], dtype=np.uint32)
+            return
+        self.fused_mode, self.fused_fold = 0, False
+        self.fold.close()
+        self.fold = None
+        for t, nbin in zip(targets, nbins):
+            fold = FoldEngine(self.ctx)
+            fold.set_shape(self.nchan_out, self.npol_out, cfg.ndim, nbin)
+            self.pulsars.append(_PulsarFold(t, nbin, fold))
 
     def _init_after(self, device, stream, subband, dump_before):
         """`dspsr -F N` (Filterbank::Config::After) and the filterbank without coherent dedispersion (Config::Never): the non-convolving
@@ -1030,13 +1100,21 @@ class LoadToFold:
         following the last (MultiThread.C:120-148 hands whole blocks to the threads in turn)."""
         self.ndat_out = k * self.cfg.parts_per_block * self.nkeep
 
-    def _phase(self, t_seconds):
+    def _ephemeris(self, pulsar=None):
+        """(folding_period, polyco, reference_phase) of the single pulsar, or of `pulsar` of a multi-target run"""
+        if pulsar is None:
+            return self.cfg.folding_period, self.polyco, self.reference_phase
+        t = pulsar.target
+        return (t.folding_period if t.polyco is None else 0.0), t.polyco, t.reference_phase
+
+    def _phase(self, t_seconds, pulsar=None):
         """Fold::get_phi / get_pfold (Fold.C:943-958)."""
-        if self.cfg.folding_period > 0:
-            p = self.cfg.folding_period
-            return math.fmod(t_seconds, p) / p - self.reference_phase, p
+        period, polyco, reference_phase = self._ephemeris(pulsar)
+        if period > 0:
+            p = period
+            return math.fmod(t_seconds, p) / p - reference_phase, p
         day, sec = self.info.mjd_day, self.info.mjd_sec + t_seconds
-        return self.polyco.phase_frac(day, sec) - self.reference_phase, 1.0 / self.polyco.frequency(day, sec)
+        return polyco.phase_frac(day, sec) - reference_phase, 1.0 / polyco.frequency(day, sec)
 
     def process_block(self, raw, npart=None, events=None):
         """raw: device int8 tensor holding npart*nsamp_step + nsamp_overlap samples (the InputBuffering
@@ -1057,7 +1135,7 @@ class LoadToFold:
         if self.sample_delay is not None:
             return self._process_block_interchan(raw, npart, ndat, state, events)
         # Subint<Fold>::transformation: fold piece by piece, emitting a sub-integration at every boundary
-        pieces = self._pieces(ndat)
+        pieces = None if self.pulsars else self._pieces(ndat)
         if self.fused_fold and len(pieces) == 1 and pieces[0][:2] == (0, ndat):
             # one fold call covers the block: filterbank, detection and fold in one launch group.  Same sums in the
             # same order as the unfused chain below (blocks holding a sub-integration boundary take that chain).
@@ -1084,7 +1162,9 @@ class LoadToFold:
             events[1].record()
         if "Fold" in self.dumps:
             self.dumps["Fold"].write(self.detected, ndat, cfg.ndim)
-        for idat_start, ndat_fold, _division, complete in pieces:
+        if self.pulsars:
+            self._fold_pulsars(self.detected, ndat)
+        for idat_start, ndat_fold, _division, complete in pieces or ():
             self._fold_piece(idat_start, ndat_fold)
             if complete:
                 self.finish_subint(*self._subint_comm)
@@ -1107,7 +1187,9 @@ class LoadToFold:
             if nuse > 0 else 0
         if nout and "Fold" in self.dumps:
             self.dumps["Fold"].write(rows, nout, nd)
-        if nout:
+        if nout and self.pulsars:
+            self._fold_pulsars(rows, nout)
+        elif nout:
             for idat_start, ndat_fold, _division, complete in self._pieces(nout):
                 folded = self._set_plan(idat_start, ndat_fold)
                 self._op("Fold", lambda: self.fold.fold(rows))
@@ -1123,43 +1205,92 @@ class LoadToFold:
         self.ndat_out += nout
         self.nsamples_in += npart * self.nsamp_step
 
-    def _pieces(self, ndat):
+    def _pieces(self, ndat, pulsar=None):
         """Subint<Fold>::transformation (Subint.h:234-309): the pieces of the next `ndat` output samples, one per
-        sub-integration they touch -- seconds mode (-L), turns mode (-s / -turns) or one piece."""
+        sub-integration they touch -- seconds mode (-L), turns mode (-s / -turns; per pulsar) or one piece."""
         cfg = self.cfg
         if cfg.subint_seconds > 0:
             return subint_pieces(self.ndat_out, ndat, cfg.subint_seconds, self.out_rate)
         if cfg.subint_turns > 0:
+            if pulsar is not None:
+                if pulsar.turns is None:
+                    pulsar.turns = self._turns_divider(*self._ephemeris(pulsar))
+                return pulsar.turns.pieces(self.ndat_out, ndat)
             if self._turns is None:
-                if cfg.folding_period > 0:
-                    p = cfg.folding_period
-                    phase = lambda t: (int(math.floor(t / p)), t / p - math.floor(t / p))
-                    iphase = lambda ph, guess: (ph[0] + ph[1]) * p
-                    pg = p
-                else:
-                    day, s0 = self.info.mjd_day, self.info.mjd_sec
-                    phase = lambda t: self.polyco.phase(day, s0 + t)
-                    iphase = lambda ph, guess: self.polyco.iphase(ph, day, s0 + guess) - s0
-                    pg = 1.0 / self.polyco.frequency(day, s0 + self.out_start)
-                self._turns = TurnsDivider(phase, iphase, pg, self.out_start, self.out_rate, cfg.subint_turns,
-                                           self.reference_phase, cfg.fractional_pulses)
+                self._turns = self._turns_divider(*self._ephemeris())
             return self._turns.pieces(self.ndat_out, ndat)
         return [(0, ndat, 0, False)]
+
+    def _turns_divider(self, folding_period, polyco, reference_phase):
+        """TimeDivide in turns mode for one pulsar's ephemeris"""
+        cfg = self.cfg
+        if folding_period > 0:
+            p = folding_period
+            phase = lambda t: (int(math.floor(t / p)), t / p - math.floor(t / p))
+            iphase = lambda ph, guess: (ph[0] + ph[1]) * p
+            pg = p
+        else:
+            day, s0 = self.info.mjd_day, self.info.mjd_sec
+            phase = lambda t: polyco.phase(day, s0 + t)
+            iphase = lambda ph, guess: polyco.iphase(ph, day, s0 + guess) - s0
+            pg = 1.0 / polyco.frequency(day, s0 + self.out_start)
+        return TurnsDivider(phase, iphase, pg, self.out_start, self.out_rate, cfg.subint_turns, reference_phase,
+                            cfg.fractional_pulses)
 
     _turns = None
     _subint_comm = (None, 0, 1, None)     # (dist, rank, world, gather_buffer[, replicas]) used at sub-integration dumps
 
     def set_communicator(self, dist, rank, world, gather_buffer=None, replicas=False):
+        self._single_pulsar_only("set_communicator")
         self._subint_comm = (dist, rank, world, gather_buffer, replicas)
 
-    def _set_plan(self, idat_start, ndat_fold):
+    def _single_pulsar_only(self, what):
+        if self.pulsars:
+            raise DspsrAmdError("dspsr_amd.LoadToFold.%s: the multi-GPU exchange folds one pulsar; this run has %d targets"
+                                % (what, len(self.pulsars)))
+
+    def _set_plan(self, idat_start, ndat_fold, pulsar=None):
         """The host plan loop of Fold::fold (Fold.C:650-657,718-787): phase of the first sample, then the bins."""
-        cfg = self.cfg
+        fold, nbin, hits = (self.fold, self.cfg.nbin, self.hits) if pulsar is None else (pulsar.fold, pulsar.nbin, pulsar.hits)
         t0 = self.out_start + (self.ndat_out + idat_start + 0.5) / self.out_rate     # midpoint of first sample
-        phi, pfold = self._phase(t0)
-        self.fold.set_nbin(cfg.nbin)
-        self.fold.set_ndat(ndat_fold, idat_start)
-        return self.fold.set_bins(phi, (1.0 / self.out_rate) / pfold, ndat_fold, idat_start, self.hits)
+        phi, pfold = self._phase(t0, pulsar)
+        fold.set_nbin(nbin)
+        fold.set_ndat(ndat_fold, idat_start)
+        return fold.set_bins(phi, (1.0 / self.out_rate) / pfold, ndat_fold, idat_start, hits)
+
+    def _fold_pulsars(self, rows, ndat):
+        """Several pulsars over the same detected rows.  The pulsars whose share of the block is one piece of a sub-integration
+        fold together (FoldEngine.fold_many: the rows are read once for all of them); a pulsar with a sub-integration boundary
+        inside the block folds piece by piece and emits its sub-integration in between, as _fold_piece does."""
+        pieces = [self._pieces(ndat, p) for p in self.pulsars]
+        group = [(p, pc[0]) for p, pc in zip(self.pulsars, pieces) if len(pc) == 1]
+        folded = [self._set_plan(pc[0], pc[1], p) for p, pc in group]
+        if group:
+            self._op("Fold", lambda: FoldEngine.fold_many([p.fold for p, _ in group], rows))
+        for (p, (_, ndat_fold, _division, complete)), n in zip(group, folded):
+            p.integration_length += n / self.out_rate
+            p.ndat_total += ndat_fold
+            if complete:
+                self._finish_pulsar_subint(p)
+        for p, pc in zip(self.pulsars, pieces):
+            if len(pc) < 2:
+                continue
+            for idat_start, ndat_fold, _division, complete in pc:
+                n = self._set_plan(idat_start, ndat_fold, p)
+                self._op("Fold", lambda: p.fold.fold(rows))
+                p.integration_length += n / self.out_rate
+                p.ndat_total += ndat_fold
+                if complete:
+                    self._finish_pulsar_subint(p)
+
+    def _finish_pulsar_subint(self, p):
+        """Subint<Fold> of one pulsar of a multi-target run: emit its sub-integration and zero its profile."""
+        p.subints.append({"hits": p.hits.copy(), "integration_length": p.integration_length, "ndat_total": p.ndat_total,
+                          "profile_dev": self.profiles_tensor(p).clone()})
+        p.fold.zero()
+        p.hits[:] = 0
+        p.integration_length = 0.0
+        p.ndat_total = 0
 
     def _fold_piece(self, idat_start, ndat_fold):
         """Fold::fold (Fold.C:650-657,718-803) on detected[idat_start : idat_start+ndat_fold]."""
@@ -1168,11 +1299,12 @@ class LoadToFold:
         self.integration_length += folded / self.out_rate
         self.ndat_total += ndat_fold
 
-    def profiles_tensor(self):
-        """Zero-copy torch view of the device-resident PhaseSeries (Fold::Engine::get_profiles)."""
+    def profiles_tensor(self, pulsar=None):
+        """Zero-copy torch view of the device-resident PhaseSeries (Fold::Engine::get_profiles); `pulsar`: one of a multi-target run."""
         torch = self.torch
-        n = self.nchan_out * self.npol_out * self.cfg.nbin * self.cfg.ndim
-        ptr = self.fold.get_profiles_ptr()
+        fold, nbin = (self.fold, self.cfg.nbin) if pulsar is None else (pulsar.fold, pulsar.nbin)
+        n = self.nchan_out * self.npol_out * nbin * self.cfg.ndim
+        ptr = fold.get_profiles_ptr()
 
         class _Holder:
             pass
@@ -1189,6 +1321,7 @@ class LoadToFold:
         """The exchange of a multi-GPU run: a dspsr_amd.Communicator (dspsr_amd_comm_*, csrc/comm.hip -- the same C entry
         points DSPSR's host calls).  Without one, finish_subint falls back to the torch.distributed calls below, which
         exist for the gloo CPU tests and for rehearsing several ranks on one device (RCCL needs one GPU per rank)."""
+        self._single_pulsar_only("set_rccl_communicator")
         self.comm = comm
 
     def collect_subint(self, copy=None):
@@ -1217,7 +1350,13 @@ class LoadToFold:
         snapshot on the compute stream, the collective on the communicator's stream -- the next block's kernels overlap
         it; wait=False leaves it in flight until collect_subint() or the next dump.
         check_hits (default True) adds a MIN/MAX all-reduce of hits[] to the sub-band exchange (two small collectives in the
-        same group; nothing for replicas): pass False inside a timed loop that has checked once."""
+        same group; nothing for replicas): pass False inside a timed loop that has checked once.
+        A multi-target run (one GPU) emits the open sub-integration of every pulsar that has folded samples since its last one."""
+        if self.pulsars:
+            for p in self.pulsars:
+                if p.ndat_total:
+                    self._finish_pulsar_subint(p)
+            return
         if self.comm is not None:
             # (one exchange in flight per communicator.  The result of the previous one is COPIED here even with
             #  copy_subints False: start() below may grow the pinned buffer a view would point into -- a view is only handed
@@ -1328,7 +1467,10 @@ class LoadToFold:
         if self.sample_delay is not None:
             self.sample_delay.close()
         self.fb.close()
-        self.fold.close()
+        if self.fold is not None:
+            self.fold.close()
+        for p in self.pulsars:
+            p.fold.close()
         self.ctx.close()
 
 

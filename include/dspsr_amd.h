@@ -304,6 +304,17 @@ int dspsr_amd_fold_set_bins_weighted(dspsr_amd_fold* fold, double phi, double ph
 /* fold(): accumulate in_dev rows (get_datptr(ichan,ipol) = in_dev + ichan*in_chan_stride + ipol*in_pol_stride)
  * into the device profile using the plan built since the last set_nbin (FoldCUDA.cu:586-697) */
 int dspsr_amd_fold_fold(dspsr_amd_fold* fold, const float* in_dev, uint64_t in_chan_stride, uint64_t in_pol_stride);
+/* Fold::Engine::fold of several Folds whose input is the SAME detected TimeSeries (LoadToFold1.C:939-960: one Fold per
+ * pulsar).  Every fold must have its plan set (set_nbin / set_ndat / set_bins[_weighted]) and share ctx, nchan, npol, ndim;
+ * nbin and the plan may differ.  Each profile ends bit-identical to dspsr_amd_fold_fold(folds[k], ...) alone.
+ * Two or more exact-order plans of the chunk kernels share launches of at most DSPSR_AMD_FOLD_MANY_MAX plans (sizes balanced),
+ * each of which reads the detected rows once; *nshared (may be NULL): how many folds took a shared launch (0 when only one plan
+ * is exact-order); the others (a lone exact-order plan, LONG runs, unaligned rows, nbin beyond the chunk kernels, empty plans)
+ * were folded one by one inside this call.  NULL entries, a fold given twice, or folds
+ * of different contexts or shapes: DSPSR_AMD_EINVAL before any plan is used.  nfold == 0: nothing to do. */
+#define DSPSR_AMD_FOLD_MANY_MAX 8
+int dspsr_amd_fold_fold_many(dspsr_amd_fold* const* folds, uint32_t nfold, const float* in_dev,
+                             uint64_t in_chan_stride, uint64_t in_pol_stride, uint32_t* nshared);
 /* fold() of an input that carries zeroed (RFI-excised) samples -- Fold::Engine::zeroed_samples with hits_nchan == nchan
  * (Fold.C:853-866, fold1bin*hits FoldCUDA.cu:415-576,622): as dspsr_amd_fold_fold, and hits_dev[ichan*nbin + ibin] (device,
  * uint32) is incremented by the number of planned samples of polarisation 0 whose first float is not zero.  The hook the

@@ -8,7 +8,11 @@ dspsr_amd.dada.fold_file for trying the engine on a DADA file; not a re-implemen
                     [--dump Detection] [--dump Fold] [-O out_prefix] file.dada
 
 Every completed sub-integration is written as <prefix>_<n>.ps (the PhaseSeries hand-off file of INTEGRATION.md:
-raw sums + hits; dsp::Archiver's normalisation is the reader's job)."""
+raw sums + hits; dsp::Archiver's normalisation is the reader's job).
+
+Several pulsars from the same data in one pass (dspsr -P a.polyco -P b.polyco): repeat -P and/or -c, one pulsar each (-P files
+first, then -c periods, each in the order given).  Pulsar k writes <prefix>_<k>_<n>.ps with its own folding period in the header.
+One -P, one -c or one of each is today's single pulsar (a -c given with a -P overrides its period)."""
 import argparse
 import os
 import sys
@@ -16,14 +20,14 @@ import sys
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
 
 
-def main():
+def parse_args(argv=None):
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("file")
     ap.add_argument("-F", dest="fb", required=True, help="nchan:D (convolving filterbank, coherent dedispersion During) or nchan (filterbank, then dsp::Convolution: After)")
     ap.add_argument("-D", dest="dm", type=float, default=None, help="dispersion measure (default: DM of the header)")
     ap.add_argument("-b", dest="nbin", type=int, default=0, help="phase bins (default: dsp::Fold::choose_nbin)")
-    ap.add_argument("-c", dest="period", type=float, default=0.0, help="constant folding period in seconds")
-    ap.add_argument("-P", dest="polyco", default=None, help="TEMPO polyco file")
+    ap.add_argument("-c", dest="period", type=float, action="append", default=[], help="constant folding period in seconds (repeat: one pulsar each)")
+    ap.add_argument("-P", dest="polyco", action="append", default=[], help="TEMPO polyco file (repeat: one pulsar each)")
     ap.add_argument("-x", dest="nfft", type=int, default=0, help="response (FFT) length per channel")
     ap.add_argument("-L", dest="subint", type=float, default=0.0, help="sub-integration length in seconds")
     ap.add_argument("-s", dest="single", action="store_true", help="single pulses (one turn per sub-integration)")
@@ -34,7 +38,26 @@ def main():
     ap.add_argument("--dump", action="append", default=[], help="dump the input of this operation (Detection, Fold)")
     ap.add_argument("-O", dest="prefix", default="dspsr_amd", help="output file name prefix")
     ap.add_argument("--cuda", dest="device", type=int, default=0, help="device id (the reference's spelling)")
-    a = ap.parse_args()
+    return ap.parse_args(argv)
+
+
+def fold_targets(a, nbin, out_rate, mjd_day, mjd_sec):
+    """The pulsars of repeated -P / -c as pipeline.FoldTarget (nbin: -b, or Fold::choose_nbin per period); [] = one pulsar."""
+    from dspsr_amd import pipeline
+    if len(a.polyco) < 2 and len(a.period) < 2:
+        return []
+    out = []
+    for path in a.polyco:
+        pc = pipeline.Polyco(open(path).read())
+        out.append(pipeline.FoldTarget(name=os.path.basename(path), polyco=pc,
+                                       nbin=nbin or pipeline.choose_nbin(1.0 / pc.frequency(mjd_day, mjd_sec), out_rate)))
+    for p in a.period:
+        out.append(pipeline.FoldTarget(name="P=%g" % p, folding_period=p, nbin=nbin or pipeline.choose_nbin(p, out_rate)))
+    return out
+
+
+def main(argv=None):
+    a = parse_args(argv)
     when = "during" if a.fb.endswith(":D") else "before" if a.fb.endswith(":B") else "after"
     if ":" in a.fb and when == "after":
         sys.exit("-F nchan:D (coherent dedispersion During the filterbank), -F nchan (After it) or -F nchan:B (Before it) are on this "
@@ -46,27 +69,35 @@ def main():
     dm = a.dm if a.dm is not None else extras["dm"]
     if dm is None:
         sys.exit("no -D and no DM in the header")
-    polyco = pipeline.Polyco(open(a.polyco).read()) if a.polyco else None
-    if polyco is None and a.period <= 0:
-        sys.exit("dsp::Fold::fold no polynomial and no period specified (-c or -P)")
     nchan = int(a.fb.split(":")[0])
-    pfold = a.period if a.period > 0 else 1.0 / polyco.frequency(info.mjd_day, info.mjd_sec)
     out_rate = info.rate / (2 if info.ndim == 1 else 1) / (nchan // info.nchan)
-    nbin = a.nbin or pipeline.choose_nbin(pfold, out_rate)
-    cfg = pipeline.Config(nchan=nchan, dispersion_measure=dm, nbin=nbin, folding_period=a.period, freq_res=a.nfft,
+    targets = fold_targets(a, a.nbin, out_rate, info.mjd_day, info.mjd_sec)
+    period = a.period[0] if len(a.period) == 1 else 0.0
+    polyco = pipeline.Polyco(open(a.polyco[0]).read()) if len(a.polyco) == 1 and not targets else None
+    if not targets and polyco is None and period <= 0:
+        sys.exit("dsp::Fold::fold no polynomial and no period specified (-c or -P)")
+    pfold = period if period > 0 else 1.0 / polyco.frequency(info.mjd_day, info.mjd_sec) if polyco else 0.0
+    nbin = a.nbin or (pipeline.choose_nbin(pfold, out_rate) if pfold else targets[0].nbin)
+    cfg = pipeline.Config(nchan=nchan, dispersion_measure=dm, nbin=nbin, folding_period=period, freq_res=a.nfft,
                           subint_seconds=a.subint, subint_turns=1.0 if a.single else a.turns, ndim=a.ndim,
                           interchan_dedispersion=a.interchan, record_time=a.record,
                           convolve_when="never" if when == "after" and dm == 0.0 else when)
     torch.cuda.set_device(a.device)
     lt = dada.fold_file(a.file, cfg, polyco=polyco, device=a.device, stream=torch.cuda.current_stream().cuda_stream,
-                        dump_before=tuple(a.dump))
+                        dump_before=tuple(a.dump), targets=targets or None)
     for line in lt.vitals():
         print(line, file=sys.stderr)
-    for n, sub in enumerate(lt.subints):
-        path = "%s_%04d.ps" % (a.prefix, n)
-        pipeline.write_phase_series(path, sub, info, cfg, npol=lt.npol_out, scale=lt.scalefac, division=n,
-                                    start_seconds=lt.out_start, folding_period=pfold)
-        print("dspsr_amd: %s  integration %.6f s  %d samples" % (path, sub["integration_length"], sub["ndat_total"]))
+    outputs = [("%s_%%04d.ps" % a.prefix, lt.subints, pfold)]
+    if targets:
+        outputs = [("%s_%d_%%04d.ps" % (a.prefix, k), p.subints,
+                    p.target.folding_period or 1.0 / p.target.polyco.frequency(info.mjd_day, info.mjd_sec))
+                   for k, p in enumerate(lt.pulsars)]
+    for pattern, subints, pf in outputs:
+        for n, sub in enumerate(subints):
+            path = pattern % n
+            pipeline.write_phase_series(path, sub, info, cfg, npol=lt.npol_out, scale=lt.scalefac, division=n,
+                                        start_seconds=lt.out_start, folding_period=pf)
+            print("dspsr_amd: %s  integration %.6f s  %d samples" % (path, sub["integration_length"], sub["ndat_total"]))
     if a.record:
         lt.report()
     lt.close()

@@ -1114,6 +1114,27 @@ static int fb_input(dspsr_amd_filterbank* fb, const char* fn, const float* in_f3
   return DSPSR_AMD_OK;
 }
 
+// The complex output rows of perform / perform_raw (`fn` names the caller in the messages): a part's 2 * nkeep floats must fit
+// its out_step, and the rows of different channels and polarisations must not overlap (a channel's row may not reach into the
+// next channel's first polarisation either).  Any float-aligned address is taken: no writer needs more (tests/test_gpu_output_forms.py).
+static int fb_complex_rows_ok(dspsr_amd_filterbank* fb, const char* fn, const float* out_dev, uint64_t out_chan_stride,
+                              uint64_t out_pol_stride, uint64_t npart, uint64_t out_step)
+{
+  if (!out_dev) return DSPSR_AMD_OK;
+  if (out_step < 2ull * fb_out_nkeep(fb))
+    return fb_fail(fb->ctx, DSPSR_AMD_EINVAL, "%s: out_step=%llu < 2*nkeep=%u", fn, (unsigned long long)out_step, 2 * fb_out_nkeep(fb));
+  const uint64_t nchan_out = (uint64_t)fb->cfg.input_nchan * fb_out_C(fb);
+  const uint64_t row = npart ? (npart - 1) * out_step + 2ull * fb_out_nkeep(fb) : 0;      // floats one output row spans
+  // channel-major (TimeSeries FPT order) or polarisation-major, as the detected rows of perform_detect
+  const uint64_t npol = fb->cfg.npol;
+  const bool chan_major = (npol == 1 || out_pol_stride >= row) && (nchan_out == 1 || out_chan_stride >= (npol - 1) * out_pol_stride + row);
+  const bool pol_major = npol > 1 && (nchan_out == 1 || out_chan_stride >= row) && out_pol_stride >= (nchan_out - 1) * out_chan_stride + row;
+  if (npart && !chan_major && !pol_major)
+    return fb_fail(fb->ctx, DSPSR_AMD_EINVAL, "%s: output rows of %llu floats overlap (chan stride %llu, pol stride %llu)", fn,
+                   (unsigned long long)row, (unsigned long long)out_chan_stride, (unsigned long long)out_pol_stride);
+  return DSPSR_AMD_OK;
+}
+
 extern "C" int dspsr_amd_filterbank_perform(dspsr_amd_filterbank* fb, const float* in_dev, uint64_t in_chan_stride,
                                             uint64_t in_pol_stride, float* out_dev, uint64_t out_chan_stride,
                                             uint64_t out_pol_stride, uint64_t npart, uint64_t in_step,
@@ -1123,15 +1144,8 @@ extern "C" int dspsr_amd_filterbank_perform(dspsr_amd_filterbank* fb, const floa
   FbIn in;
   const int rc = fb_input(fb, "dspsr_amd_filterbank_perform", in_dev, in_pol_stride, in_step, nullptr, 0, 0.0f, &in);
   if (rc != DSPSR_AMD_OK) return rc;
-  if (out_dev && out_step < 2ull * fb_out_nkeep(fb))
-    return fb_fail(fb->ctx, DSPSR_AMD_EINVAL, "dspsr_amd_filterbank_perform: out_step=%llu < 2*nkeep=%u",
-                   (unsigned long long)out_step, 2 * fb_out_nkeep(fb));
-  const uint64_t nchan_out = (uint64_t)fb->cfg.input_nchan * fb_out_C(fb);
-  const uint64_t row = npart ? (npart - 1) * out_step + 2ull * fb_out_nkeep(fb) : 0;      // floats one output row spans
-  if (out_dev && npart && ((fb->cfg.npol > 1 && out_pol_stride < row) || (nchan_out > 1 && out_chan_stride < row)))
-    return fb_fail(fb->ctx, DSPSR_AMD_EINVAL, "dspsr_amd_filterbank_perform: output rows of %llu floats overlap "
-                   "(chan stride %llu, pol stride %llu)", (unsigned long long)row, (unsigned long long)out_chan_stride,
-                   (unsigned long long)out_pol_stride);
+  const int rco = fb_complex_rows_ok(fb, "dspsr_amd_filterbank_perform", out_dev, out_chan_stride, out_pol_stride, npart, out_step);
+  if (rco != DSPSR_AMD_OK) return rco;
   FbOut out = {out_dev ? 1 : 0, out_dev, out_chan_stride, out_pol_stride, out_step, 0, 2, 0};
   return fb_run(fb, in, out, npart, in_chan_stride);
 }
@@ -1144,6 +1158,8 @@ extern "C" int dspsr_amd_filterbank_perform_raw(dspsr_amd_filterbank* fb, const 
   FbIn in;
   const int rc = fb_input(fb, "dspsr_amd_filterbank_perform_raw", nullptr, 0, 0, raw_dev, raw_layout, scale, &in);
   if (rc != DSPSR_AMD_OK) return rc;
+  const int rco = fb_complex_rows_ok(fb, "dspsr_amd_filterbank_perform_raw", out_dev, out_chan_stride, out_pol_stride, npart, out_step);
+  if (rco != DSPSR_AMD_OK) return rco;
   FbOut out = {out_dev ? 1 : 0, out_dev, out_chan_stride, out_pol_stride, out_step, 0, 2, 0};
   return fb_run(fb, in, out, npart, 0);
 }

@@ -128,7 +128,14 @@ int dspsr_amd_filterbank_sizes(const dspsr_amd_filterbank* fb, uint64_t* nsamp_f
  *   in_dev : unpacked float32 rows, in->get_datptr(ichan,ipol) = in_dev + ichan*in_chan_stride + ipol*in_pol_stride (floats)
  *   out_dev: complex float rows, out->get_datptr(ochan,ipol) = out_dev + ochan*out_chan_stride + ipol*out_pol_stride (floats);
  *            NULL => benchmark only (FilterbankCUDA.cu:265)
- *   in_step: floats between parts (= nsamp_step*ndim), out_step: floats between parts (= 2*nkeep) */
+ *   in_step: floats between parts (= nsamp_step*ndim), out_step: floats between parts (= 2*nkeep)
+ * The output (perform and perform_raw alike): part k of row (ochan, ipol) is the 2*nkeep floats at row + k*out_step.  out_dev may be
+ * any float-aligned address -- dsp::TimeSeries rows start at buffer + reserve, as a rule 8-byte and seldom 16-byte aligned -- and the
+ * strides any number of floats; no writer asks for more.  out_step >= 2*nkeep (larger: the floats between two parts are not
+ * written), and the rows must not overlap: with row = (npart-1)*out_step + 2*nkeep either out_pol_stride >= row and
+ * out_chan_stride >= (npol-1)*out_pol_stride + row (FPT order), or out_chan_stride >= row and out_pol_stride >=
+ * (nchan-1)*out_chan_stride + row.  Anything else is refused with DSPSR_AMD_EINVAL before a launch.  Only the floats of the parts are
+ * written: nothing in front of a row, between parts, behind a row (tests/test_gpu_output_forms.py). */
 int dspsr_amd_filterbank_perform(dspsr_amd_filterbank* fb, const float* in_dev, uint64_t in_chan_stride,
                                  uint64_t in_pol_stride, float* out_dev, uint64_t out_chan_stride,
                                  uint64_t out_pol_stride, uint64_t npart, uint64_t in_step, uint64_t out_step);
@@ -142,6 +149,7 @@ int dspsr_amd_filterbank_perform(dspsr_amd_filterbank* fb, const float* in_dev, 
 #define DSPSR_AMD_RAW_UWB16 2    /* 16-bit offset-binary complex, 2048-sample blocks per polarisation, single channel;
                                     value = float(int16(x ^ 0x8000)) * scale   uwb/UWBUnpackerCUDA.cu:24-75,
                                     uwb/UWBUnpacker.C:196-207 (the reference applies no scale: pass 1.0) */
+/* out_dev, its strides and out_step: as dspsr_amd_filterbank_perform, the same checks */
 int dspsr_amd_filterbank_perform_raw(dspsr_amd_filterbank* fb, const int8_t* raw_dev, int raw_layout, float scale,
                                      float* out_dev, uint64_t out_chan_stride, uint64_t out_pol_stride,
                                      uint64_t npart, uint64_t out_step);
@@ -151,7 +159,12 @@ int dspsr_amd_filterbank_perform_raw(dspsr_amd_filterbank* fb, const int8_t* raw
  *     ndim 4: det_dev + chan*det_chan_stride + 4*idat               (npol 1)
  *     ndim 2: det_dev + chan*det_chan_stride + plane*det_pol_stride + 2*idat   (plane0 = PP,QQ plane1 = Re,Im)
  *     ndim 1: det_dev + chan*det_chan_stride + k*det_pol_stride + idat         (k = 0..3)
- *   exactly one of in_f32_dev / raw_dev is non-NULL. */
+ *   exactly one of in_f32_dev / raw_dev is non-NULL.
+ * det_dev may be any float-aligned address and the strides any number of floats (the float4 / float2 samples of ndim 4 / 2 are
+ * written at whatever address that gives).  A detected row is npart*nkeep*ndim floats; the 4/ndim rows of a channel and the
+ * channels must not overlap, in one of two orders: channel-major (TimeSeries FPT order: det_pol_stride >= row, det_chan_stride >=
+ * (4/ndim - 1)*det_pol_stride + row) or plane-major (det_chan_stride >= row, det_pol_stride >= (nchan-1)*det_chan_stride + row).
+ * Anything else is refused with DSPSR_AMD_EINVAL before a launch; nothing outside the rows is written. */
 #define DSPSR_AMD_COHERENCE 0
 #define DSPSR_AMD_STOKES 1
 int dspsr_amd_filterbank_perform_detect(dspsr_amd_filterbank* fb, const float* in_f32_dev, uint64_t in_chan_stride,
@@ -217,7 +230,9 @@ int dspsr_amd_filterbank_perform_fold(dspsr_amd_filterbank* fb, const float* in_
  * input buffering re-presents the ndat % tscrunch left-over samples in front of the next block (TScrunch.C:110-111); here the
  * partial sum of those samples stays in carry_dev -- the same sequential sum, out = in[0]; out += in[1]; ... , bit for bit.
  *   out_state       DSPSR_AMD_INTENSITY (npol_out 1) | DSPSR_AMD_PPQQ (npol_out 2)
- *   out_dev         rows [chan][npol_out] of *nout floats, FPT order like the reference's TimeSeries
+ *   out_dev         rows [chan][npol_out] of *nout floats, FPT order like the reference's TimeSeries: any float-aligned address,
+ *                   out_pol_stride >= *nout and out_chan_stride >= (npol_out-1)*out_pol_stride + *nout (else DSPSR_AMD_EINVAL,
+ *                   nothing launched); only the *nout complete samples of a row are written -- the open one goes to carry_dev
  *   carry_dev       [nchan][npol_out] floats owned by the caller (any content when *carry_count == 0)
  *   carry_count     in: samples already summed into carry_dev (< tscrunch); out: samples left over by this call
  *   nout            out: complete output samples written per row = (carry_in + npart * nkeep) / tscrunch
@@ -249,7 +264,9 @@ int dspsr_amd_fscrunch_fpt(dspsr_amd_ctx* ctx, const float* in_dev, uint64_t in_
 
 /* ---- dsp::Detection::Engine (Detection.h:98-106) ------------------------------------------
  * polarimetry(ndim, in, out): in = complex rows [nchan][2][ndat]; in-place allowed for ndim 2
- * (LoadToFold1.C:545-546 uses input==output).  Layouts as above. */
+ * (LoadToFold1.C:545-546 uses input==output).  Layouts as above.  Rows at any float-aligned address with any strides (ndim 2 on
+ * 16-byte rows, strides that are multiples of 4 floats and an even ndat takes the two-samples-per-thread kernel: the same bits);
+ * any nchan and ndat (the kernels walk over more rows and samples than a grid holds). */
 int dspsr_amd_detect_polarimetry(dspsr_amd_ctx* ctx, int state, uint32_t ndim, const float* in_dev,
                                  uint64_t in_chan_stride, uint64_t in_pol_stride, float* out_dev,
                                  uint64_t out_chan_stride, uint64_t out_pol_stride, uint32_t nchan, uint64_t ndat);

@@ -13,7 +13,7 @@ import types
 import numpy as np
 import pytest
 
-from device_buffers import device_rows
+from device_buffers import SENTINEL, OutputLayout, describe_float, device_rows, sentinel_rows, written_mask
 
 pytestmark = pytest.mark.gpu
 
@@ -510,6 +510,123 @@ def test_square_law(oracle, gpu):
         out = torch.zeros((5, 1 if intensity else 2, 300), dtype=torch.float32, device="cuda")
         dspsr_amd.DetectionEngine(ctx).square_law(torch.from_numpy(x).cuda(), out, intensity)
         np.testing.assert_allclose(out.cpu().numpy(), want, rtol=3e-7, atol=1e-6)
+
+
+# ---- the stand-alone detection kernels at the addresses, strides and sizes the C-ABI accepts (csrc/detect.hip) -----------------
+def _sentinel_rows_written(buf, lay, rows):
+    """asserts that every float of the layout's rows was written and no other float of the buffer; returns the rows' bits"""
+    got = buf.cpu().numpy()
+    mask = written_mask(lay, 1, lay.row, lay.row)
+    bad = np.flatnonzero((got != SENTINEL) != mask)
+    assert bad.size == 0, "%d floats %s; the first: %s" % (bad.size, "never written" if mask[bad[0]] else "written outside the rows",
+                                                          describe_float(lay, int(bad[0]), 1, lay.row, lay.row))
+    return rows.contiguous().view(torch.int32).cpu().numpy()
+
+
+def _placed_detection(dspsr_amd, ctx, x, ndim, state, offset, row_pad, in_offset=None, in_row_pad=None):
+    """polarimetry of x [nchan][2][2 * ndat], placed by device_rows, into output rows cut from a sentinel buffer; the output's bits
+    [nchan][4 / ndim][ndat * ndim]"""
+    nchan, ndat = x.shape[0], x.shape[2] // 2
+    lay = OutputLayout(nchan, 4 // ndim, ndat * ndim, offset, row_pad)
+    buf, rows = sentinel_rows(lay)
+    d_in = device_rows(x, offset if in_offset is None else in_offset, row_pad if in_row_pad is None else in_row_pad)
+    dspsr_amd.DetectionEngine(ctx).polarimetry(ndim, d_in, rows, dspsr_amd.COHERENCE if state == "Coherence" else dspsr_amd.STOKES)
+    ctx.synchronize()
+    return _sentinel_rows_written(buf, lay, rows)
+
+
+@pytest.mark.parametrize("state", ["Coherence", "Stokes"])
+@pytest.mark.parametrize("ndim", [1, 2, 4])
+@pytest.mark.parametrize("ndat", [1000, 1001])
+@pytest.mark.parametrize("offset,row_pad", [(0, 0), (1, 0), (2, 0), (3, 0), (0, 1), (2, 3), (1, 3), (0, 3), (3, 1)])
+def test_detection_engine_placed_rows(oracle, gpu, state, ndim, ndat, offset, row_pad):
+    """k_polarimetry2x (ndim 2, even ndat, 16-byte rows, strides % 4 == 0: the `vec` condition of dspsr_amd_detect_polarimetry) and
+    k_polarimetry (everything else: float4 / float2 stores at rows that are only float aligned) on input and output rows `offset`
+    floats past an aligned address with `row_pad` floats between rows: the float32 products of the oracle (tolerance of
+    test_detection_engine), nothing written outside the rows, and -- ndim 2 -- the bits of the vector kernel on the same data
+    ("identical results", detect.hip)."""
+    dspsr_amd, ctx = gpu
+    rng = np.random.default_rng(5)
+    nchan = 6
+    x = rng.standard_normal((nchan, 2, 2 * ndat)).astype(np.float32)
+    want = oracle.detect_layout(oracle.detect_products(x.view(np.complex64), state), ndim).reshape(nchan, 4 // ndim, ndat * ndim)
+    got = _placed_detection(dspsr_amd, ctx, x, ndim, state, offset, row_pad)
+    np.testing.assert_allclose(got.view(np.float32), want, rtol=3e-7, atol=3e-7 * np.abs(want).max())
+    if ndim == 2 and ndat % 2 == 0 and (offset, row_pad) != (0, 0):
+        vec = _placed_detection(dspsr_amd, ctx, x, ndim, state, 0, 0)             # the aligned form: k_polarimetry2x
+        assert np.array_equal(got, vec), "the scalar ndim-2 branch and k_polarimetry2x differ on the same data"
+
+
+@pytest.mark.parametrize("ndat", [256, 255])
+def test_detection_inplace_ndim2_on_padded_rows(oracle, gpu, ndat):
+    """In place (LoadToFold1.C:545-546) on rows that are 8-byte but not 16-byte aligned, with padded strides: the scalar branch reads
+    its two samples and writes the same elements back; the padding and the guards keep their pattern."""
+    dspsr_amd, ctx = gpu
+    rng = np.random.default_rng(6)
+    x = rng.standard_normal((3, 2, 2 * ndat)).astype(np.float32)
+    want = oracle.detect_layout(oracle.detect_products(x.view(np.complex64), "Stokes"), 2).reshape(3, 2, 2 * ndat)
+    for offset, row_pad in [(2, 2), (2, 1), (0, 4)]:                     # (0, 4): the aligned form, k_polarimetry2x when ndat is even
+        lay = OutputLayout(3, 2, 2 * ndat, offset, row_pad)
+        buf, rows = sentinel_rows(lay)
+        rows.copy_(torch.from_numpy(x))
+        dspsr_amd.DetectionEngine(ctx).polarimetry(2, rows, rows, dspsr_amd.STOKES)
+        ctx.synchronize()
+        got = _sentinel_rows_written(buf, lay, rows)
+        np.testing.assert_allclose(got.view(np.float32), want, rtol=3e-7, atol=3e-7 * np.abs(want).max())
+
+
+@pytest.mark.parametrize("offset,row_pad,ndat", [(0, 0, 300), (1, 0, 300), (2, 1, 301), (3, 3, 299)])
+def test_square_law_placed_rows(oracle, gpu, offset, row_pad, ndat):
+    dspsr_amd, ctx = gpu
+    rng = np.random.default_rng(7)
+    x = rng.standard_normal((5, 2, 2 * ndat)).astype(np.float32)
+    for intensity in (False, True):
+        want = oracle.square_law(x.view(np.complex64), "Intensity" if intensity else "PPQQ")
+        lay = OutputLayout(5, 1 if intensity else 2, ndat, offset, row_pad)
+        buf, rows = sentinel_rows(lay)
+        dspsr_amd.DetectionEngine(ctx).square_law(device_rows(x, offset, row_pad), rows, intensity)
+        ctx.synchronize()
+        got = _sentinel_rows_written(buf, lay, rows)
+        np.testing.assert_allclose(got.view(np.float32), want, rtol=3e-7, atol=1e-6)
+
+
+def test_detection_kernels_beyond_the_grid_limits(oracle, gpu):
+    """More samples than one sweep of the grid holds (at most 4096 workgroups of 256 threads: > 4096 * 256 samples for
+    k_polarimetry / k_square_law, > 2 * 4096 * 256 for k_polarimetry2x) and more channels than gridDim.y holds (65536 = 16 input
+    channels x 8192 sub-band channels): the threads and the blocks walk on (the model: test_fpt_kernels_beyond_the_grid_limits)."""
+    dspsr_amd, ctx = gpu
+    rng = np.random.default_rng(8)
+    ndat = 2 * 4096 * 256 + 2 * 700
+    x = rng.standard_normal((1, 2, 2 * ndat)).astype(np.float32)
+    want = oracle.detect_layout(oracle.detect_products(x.view(np.complex64), "Stokes"), 2).reshape(1, 2, 2 * ndat)
+    vec = _placed_detection(dspsr_amd, ctx, x, 2, "Stokes", 0, 0)                                  # k_polarimetry2x
+    np.testing.assert_allclose(vec.view(np.float32), want, rtol=3e-7, atol=3e-7 * np.abs(want).max())
+    assert np.array_equal(_placed_detection(dspsr_amd, ctx, x, 2, "Stokes", 2, 0), vec)           # k_polarimetry
+    xo = np.ascontiguousarray(x[:, :, :2 * (4096 * 256 + 701)])                                    # odd ndat
+    got = _placed_detection(dspsr_amd, ctx, xo, 4, "Stokes", 1, 0)
+    want4 = oracle.detect_layout(oracle.detect_products(xo.view(np.complex64), "Stokes"), 4).reshape(1, 1, -1)
+    np.testing.assert_allclose(got.view(np.float32), want4, rtol=3e-7, atol=3e-7 * np.abs(want4).max())
+    for intensity in (False, True):
+        lay = OutputLayout(1, 1 if intensity else 2, xo.shape[2] // 2, 1, 1)
+        buf, rows = sentinel_rows(lay)
+        dspsr_amd.DetectionEngine(ctx).square_law(torch.from_numpy(xo).cuda(), rows, intensity)
+        ctx.synchronize()
+        np.testing.assert_allclose(_sentinel_rows_written(buf, lay, rows).view(np.float32),
+                                   oracle.square_law(xo.view(np.complex64), "Intensity" if intensity else "PPQQ"), rtol=3e-7, atol=1e-6)
+    nchan, nd = 65536, 6
+    y = rng.standard_normal((nchan, 2, 2 * nd)).astype(np.float32)
+    prod = oracle.detect_products(y.view(np.complex64), "Coherence")
+    for ndim, offset, row_pad in [(4, 0, 0), (2, 0, 0), (2, 2, 1), (1, 1, 0)]:
+        want = oracle.detect_layout(prod, ndim).reshape(nchan, 4 // ndim, nd * ndim)
+        got = _placed_detection(dspsr_amd, ctx, y, ndim, "Coherence", offset, row_pad, in_offset=0, in_row_pad=0)
+        np.testing.assert_allclose(got.view(np.float32), want, rtol=3e-7, atol=3e-7 * np.abs(want).max())
+    for intensity in (False, True):
+        lay = OutputLayout(nchan, 1 if intensity else 2, nd, 1, 1)
+        buf, rows = sentinel_rows(lay)
+        dspsr_amd.DetectionEngine(ctx).square_law(torch.from_numpy(y).cuda(), rows, intensity)
+        ctx.synchronize()
+        np.testing.assert_allclose(_sentinel_rows_written(buf, lay, rows).view(np.float32),
+                                   oracle.square_law(y.view(np.complex64), "Intensity" if intensity else "PPQQ"), rtol=3e-7, atol=1e-6)
 
 
 @pytest.mark.parametrize("ndim,npol", [(4, 1), (2, 2), (1, 4)])

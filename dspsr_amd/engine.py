@@ -371,6 +371,38 @@ def tscrunch_fpt(ctx: Context, inp, out, sfactor, carry, carry_count=0, ndim=1):
     return int(nout.value), int(cc.value)
 
 
+def unpack_fpt(ctx: Context, raw, out, nchan, npol, ndim, scale=1.0, ndat=None):
+    """The generic 8-bit unpacker on the device (BitUnpacker.C:48-80): raw = device int8 block in DADA order [ndat][nchan][npol][ndim]
+    (any byte address), out = float32 device rows [nchan][npol][>= ndat * ndim] (strided views allowed)."""
+    per = nchan * npol * ndim
+    ndat = raw.numel() // per if ndat is None else ndat
+    if raw.numel() < ndat * per:
+        raise DspsrAmdError("dspsr_amd.unpack_fpt: block holds %d bytes, %d needed" % (raw.numel(), ndat * per))
+    if tuple(out.shape[:2]) != (nchan, npol) or out.shape[2] < ndat * ndim:
+        raise DspsrAmdError("dspsr_amd.unpack_fpt: out is %s, [%d][%d][>= %d] needed" % (tuple(out.shape), nchan, npol, ndat * ndim))
+    ocs, ops = _strides3(out)
+    _check(ctx.handle, lib.dspsr_amd_unpack_fpt(ctx.handle, raw.data_ptr(), scale, nchan, npol, ndim, ndat, out.data_ptr(), ocs, ops),
+           "dspsr_amd_unpack_fpt")
+    return out
+
+
+def detect_raw(ctx: Context, raw, out, carry, carry_count, nchan, npol, tscrunch=1, state=_lib.INTENSITY, scale=1.0, ndat=None):
+    """Unpack -> Detection -> TScrunch of a channelised complex 8-bit block [ndat][nchan][npol][2] in one pass, as a stream: out =
+    float32 device rows [nchan][npol_out][>= nout] (Intensity 1 / PPQQ 2 / Coherence 4: PP, QQ, Re, Im), carry = device
+    [nchan][npol_out] floats (None allowed with tscrunch 1).  Returns (nout, carry_count_after)."""
+    per = nchan * npol * 2
+    ndat = raw.numel() // per if ndat is None else ndat
+    if raw.numel() < ndat * per:
+        raise DspsrAmdError("dspsr_amd.detect_raw: block holds %d bytes, %d needed" % (raw.numel(), ndat * per))
+    ocs, ops = _strides3(out)
+    cc, nout = C.c_uint32(carry_count or 0), C.c_uint64(0)
+    _check(ctx.handle, lib.dspsr_amd_detect_raw(ctx.handle, raw.data_ptr(), scale, nchan, npol, ndat, state, tscrunch, out.data_ptr(), ocs, ops,
+                                                carry.data_ptr() if carry is not None else None,
+                                                C.byref(cc) if carry_count is not None else None, C.byref(nout)),
+           "dspsr_amd_detect_raw")
+    return int(nout.value), int(cc.value)
+
+
 def fscrunch_fpt(ctx: Context, inp, out, sfactor):
     """dsp::FScrunch::fpt_fscrunch on device rows [nchan][npol][nfloat] -> [nchan / sfactor][npol][nfloat]."""
     nchan, npol, nfloat = inp.shape

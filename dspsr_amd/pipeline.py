@@ -20,7 +20,7 @@ import numpy as np
 
 from . import _lib
 from .engine import (Context, ConvolutionEngine, Dedispersion, DspsrAmdError, FilterbankEngine, FoldEngine, Rescale, SampleDelay, add_fpt, copy_data_fpt,
-                     dedispersion_sample_delays, eight_bit_scale, fscrunch_fpt, pscrunch_tfp, sigproc_digitize, sigproc_digitize_fpt,
+                     dedispersion_sample_delays, detect_raw, eight_bit_scale, fscrunch_fpt, pscrunch_tfp, sigproc_digitize, sigproc_digitize_fpt,
                      tfp_filterbank, tscrunch_fpt)
 
 
@@ -105,6 +105,7 @@ class InputInfo:
     mjd_sec: float = 7545.0
     source: str = "unknown"
     telescope: str = "unknown"
+    nbit: int = 8                     # NBIT of the file (every path here reads 8-bit samples)
 
     @property
     def rate(self):
@@ -1795,4 +1796,164 @@ class LoadToFilCoherent:
         if self.rescale is not None:
             self.rescale.close()
         self.fb.close()
+        self.ctx.close()
+
+
+class LoadToFilDirect:
+    """digifil on an already channelised voltage file with NO -F, `digifil file.dada [-K] [-d npol] [-f F] [-t T] [-I s] -b nbit`
+    (Signal/General/LoadToFil.C:233-362): [SampleDelay, -K] -> Detection (Intensity / PPQQ / Coherence with ndim 1) -> [FScrunch] ->
+    [TScrunch] -> [Rescale] -> SigProcDigitizer, FPT order throughout, every stage on the device.  The 8-bit block is detected and
+    time-scrunched in ONE pass (dspsr_amd.detect_raw): the float voltages are never written.  With -f or -K the pass runs at tscrunch 1
+    into a detected block and SampleDelay, FScrunch and TScrunch follow as operations of their own; -K delays the DETECTED rows
+    (sample-by-sample detection commutes with an integer delay), the unshifted tail kept in front of the next block as
+    LoadToFilCoherent does.
+    The channels are those of the file: SearchConfig.nchan (-F) is IGNORED, as are freq_res, max_parts and fused;
+    cfg.parts_per_block is the largest number of time samples one process_block call may bring.
+    process_block(raw, ndat) takes the block of ndat time samples in DADA order [ndat][nchan][npol][2] int8 (any ndat up to
+    parts_per_block, 0 included) and returns the packed bytes [time][pol][chan] of the output samples it completes."""
+
+    def __init__(self, cfg: SearchConfig, info: InputInfo, device: int = 0, stream: int | None = None):
+        import torch
+        self.torch = torch
+        delays = self._plan(cfg, info)                       # every refusal comes from here, before a device is touched
+        self.ctx = Context(device, stream)
+        dev = "cuda:%d" % device
+        ts, head, nmax_in = self.ts, self.sd_head, cfg.parts_per_block
+        self.sample_delay, self.sd_carried = None, 0
+        if delays is not None:
+            self.sample_delay = SampleDelay(self.ctx, delays, cfg.npol)
+        nmax = max(1, (ts - 1 + head + nmax_in) // ts)
+        self.scrunched = torch.empty((self.nchan_out, cfg.npol, nmax), dtype=torch.float32, device=dev)
+        self.carry = torch.zeros((self.nchan_out, cfg.npol), dtype=torch.float32, device=dev)
+        self.carry_count = 0
+        self.detected = self.fscr = None
+        if not self.fused:
+            nd = head + nmax_in
+            self.detected = torch.empty((info.nchan, cfg.npol, nd), dtype=torch.float32, device=dev)
+            self.fscr = torch.empty((self.nchan_out, cfg.npol, nd), dtype=torch.float32, device=dev) if cfg.fscrunch else None
+        self.rescale = None
+        if self.rescale_interval:
+            self.rescale = Rescale(self.ctx, self.nchan_out, cfg.npol, self.rescale_interval, cfg.rescale_constant)
+        self.packed = torch.empty(nmax * self.bytes_per_sample, dtype=torch.uint8, device=dev)
+        self.ndat_out = 0
+
+    def _plan(self, cfg, info):
+        """The host side of the constructor: checks and geometry.  Returns the -K delays per channel (None without -K)."""
+        self.cfg, self.info = cfg, info
+        if info.ndim != 2:
+            raise DspsrAmdError("dspsr_amd.LoadToFilDirect: NDIM=%d; complex (NDIM 2) channelised voltages only" % info.ndim)
+        if getattr(info, "nbit", 8) != 8:
+            raise DspsrAmdError("dspsr_amd.LoadToFilDirect: NBIT=%d; this path reads 8-bit samples" % info.nbit)
+        if info.machine == "CASPSR":
+            raise DspsrAmdError("dspsr_amd.LoadToFilDirect: the CASPSR byte order is not built on this path (generic DADA order only)")
+        if cfg.npol not in (1, 2, 4):
+            raise DspsrAmdError("dspsr_amd.LoadToFilDirect: npol=%d (Intensity 1 / PPQQ 2 / Coherence 4 are built; NthPower 3 is not)" % cfg.npol)
+        if info.npol not in (1, 2):
+            raise DspsrAmdError("dspsr_amd.LoadToFilDirect: NPOL=%d; one or two input polarisations" % info.npol)
+        if cfg.npol >= 2 and info.npol != 2:
+            raise DspsrAmdError("dsp::Detection::checks invalid npol=%d for %s formation" % (info.npol, "PPQQ" if cfg.npol == 2 else "Coherence"))
+        if info.nchan < 1 or cfg.parts_per_block < 1:
+            raise DspsrAmdError("dspsr_amd.LoadToFilDirect: nchan=%d, parts_per_block=%d" % (info.nchan, cfg.parts_per_block))
+        if cfg.fscrunch and info.nchan % cfg.fscrunch:
+            raise DspsrAmdError("dspsr_amd.LoadToFilDirect: nchan=%d is not a multiple of fscrunch=%d" % (info.nchan, cfg.fscrunch))
+        self.ts = ts = max(1, cfg.tscrunch)
+        self.nchan_out = info.nchan // cfg.fscrunch if cfg.fscrunch else info.nchan
+        self.out_rate = info.rate / ts
+        self.out_start = info.start_seconds
+        self.scale8 = eight_bit_scale()
+        self.state = {1: _lib.INTENSITY, 2: _lib.PPQQ, 4: _lib.COHERENCE}[cfg.npol]
+        delays, self.sd_head = None, 0
+        if cfg.dedisperse:
+            # the input comes from a file, not from a filterbank: no swapped halves (Observation.C:420-451)
+            delays = dedispersion_sample_delays(info.centre_frequency, info.bandwidth, cfg.dispersion_measure, info.nchan, info.rate,
+                                                swap=False, nsub_swap=0)
+            zero = int(delays.max())
+            self.sd_head = int((zero - delays).max())                                    # SampleDelay.C:75-99: total_delay
+            if self.sd_head > cfg.parts_per_block:
+                raise DspsrAmdError("dspsr_amd.LoadToFilDirect: inter-channel delay of %d samples exceeds the block of %d"
+                                    % (self.sd_head, cfg.parts_per_block))
+            self.out_start += zero / info.rate                                           # SampleDelay.C:159
+        self.rescale_interval = 0
+        if cfg.rescale_seconds:
+            self.rescale_interval = int(cfg.rescale_seconds * self.out_rate)             # Rescale::init, Rescale.C:102-103
+            if not self.rescale_interval:
+                raise DspsrAmdError("dsp::Rescale::init nsample == 0")
+        # FScrunch sits between Detection and TScrunch, SampleDelay in front of Detection: the one-pass form holds neither
+        self.fused = not cfg.fscrunch and not cfg.dedisperse
+        nbits = 32 if cfg.nbit == -32 else cfg.nbit
+        self.bytes_per_sample = self.nchan_out * cfg.npol * nbits // 8
+        # no filterbank factor here: FScrunch / TScrunch multiply the scale by their factors (TScrunch.C:126, FScrunch.C:103)
+        self.input_scale = float(ts * (cfg.fscrunch or 1))
+        return delays
+
+    def block_bytes(self, ndat=None):
+        ndat = self.cfg.parts_per_block if ndat is None else ndat
+        return ndat * self.info.nchan * self.info.npol * 2
+
+    def detect_scrunch(self, raw, ndat=None):
+        """Detection -> [SampleDelay] -> [FScrunch] -> TScrunch of one block: the scrunched rows [nchan_out][npol][nout] (a view)."""
+        cfg, info = self.cfg, self.info
+        ndat = cfg.parts_per_block if ndat is None else ndat
+        if ndat > cfg.parts_per_block:
+            raise DspsrAmdError("dspsr_amd.LoadToFilDirect.process_block: ndat=%d exceeds parts_per_block=%d" % (ndat, cfg.parts_per_block))
+        if raw.numel() < self.block_bytes(ndat):
+            raise DspsrAmdError("dspsr_amd.LoadToFilDirect.process_block: block holds %d bytes, %d needed" % (raw.numel(), self.block_bytes(ndat)))
+        if self.fused:
+            nout, self.carry_count = detect_raw(self.ctx, raw, self.scrunched, self.carry, self.carry_count, info.nchan, info.npol, self.ts,
+                                                self.state, self.scale8, ndat=ndat)
+            return self.scrunched[:, :, :nout]
+        nd, head = ndat, self.sd_head
+        det = self.detected[:, :, head:head + nd]
+        detect_raw(self.ctx, raw, det, None, None, info.nchan, info.npol, 1, self.state, self.scale8, ndat=ndat)
+        rows = carry = None
+        if self.sample_delay is not None:
+            off, nin = head - self.sd_carried, self.sd_carried + nd
+            rows = self.detected[:, :, off:off + nin]
+            nd = self.sample_delay.transform(rows) if nin else 0                     # in place (LoadToFil.C:240-241)
+            carry = nin - nd                 # InputBuffering::set_next_start: the unshifted tail goes in front of the next block
+            det = rows[:, :, :nd]
+        nout = 0
+        if nd:
+            if cfg.fscrunch:
+                det = fscrunch_fpt(self.ctx, det, self.fscr[:, :, :nd], cfg.fscrunch)
+            nout, self.carry_count = tscrunch_fpt(self.ctx, det, self.scrunched, self.ts, self.carry, self.carry_count)
+        if rows is not None:
+            if carry and off + nd != head - carry:
+                move_tail_fpt(self.ctx, self.detected, head - carry, off + nd, carry)
+            self.sd_carried = carry
+        return self.scrunched[:, :, :nout]
+
+    def process_block(self, raw, ndat=None):
+        cfg = self.cfg
+        scr = self.detect_scrunch(raw, ndat)
+        nout = scr.shape[2]
+        packed = self.packed[:nout * self.bytes_per_sample]
+        flip = self.info.bandwidth > 0
+        if nout:
+            if self.rescale is not None and cfg.nbit != -32:
+                self.rescale.digitize_fpt(scr, packed, cfg.nbit, cfg.scale_fac, flip_band=flip)        # Rescale + digitiser, one pass
+            else:
+                if self.rescale is not None:
+                    self.rescale.transform_fpt(scr)                                                     # in place, LoadToFil.C:312-313
+                sigproc_digitize_fpt(self.ctx, scr, packed, cfg.nbit, use_digi_scales=self.rescale is not None,
+                                     input_scale=1.0 if self.rescale is not None else self.input_scale, scale_fac=cfg.scale_fac,
+                                     flip_band=flip)
+        self.ndat_out += nout
+        return packed
+
+    def header_values(self):
+        nchan, bw = self.nchan_out, -abs(self.info.bandwidth)
+        fch1 = self.info.centre_frequency - 0.5 * bw + 0.5 * bw / nchan
+        nbits = 32 if self.cfg.nbit == -32 else self.cfg.nbit
+        return dict(fch1=fch1, foff=bw / nchan, nchans=nchan, nbits=nbits, tsamp=self.ts / self.info.rate,
+                    tstart_mjd=self.info.mjd_day + (self.info.mjd_sec + self.out_start) / 86400.0, nifs=self.cfg.npol)
+
+    def synchronize(self):
+        self.ctx.synchronize()
+
+    def close(self):
+        if self.rescale is not None:
+            self.rescale.close()
+        if self.sample_delay is not None:
+            self.sample_delay.close()
         self.ctx.close()

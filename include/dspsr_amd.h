@@ -275,6 +275,31 @@ int dspsr_amd_detect_square_law(dspsr_amd_ctx* ctx, int intensity, const float* 
                                 uint64_t in_pol_stride, float* out_dev, uint64_t out_chan_stride,
                                 uint64_t out_pol_stride, uint32_t nchan, uint32_t npol, uint64_t ndat);
 
+/* ---- search mode on already channelised 8-bit voltages: `digifil file.dada` with no -F (LoadToFil.C:233-304) ----------------
+ * The block is generic DADA: byte ((t * nchan + c) * npol + p) * ndim + d, two's-complement int8, value (float(s) + 0.5f) * scale
+ * (BitUnpacker.C:48-80).  raw_dev may be any byte address.
+ *
+ * dspsr_amd_unpack_fpt replaces dsp::GenericEightBitUnpacker on the device (GenericEightBitUnpackerCUDA.cu:24-83): float FPT rows
+ * [nchan][npol] of ndat * ndim floats.  nchan >= 1, npol 1 | 2 | 4, ndim 1 | 2 (so a detected 8-bit file unpacks too).  Rows at any
+ * float-aligned address; out_pol_stride >= ndat * ndim and out_chan_stride >= (npol-1)*out_pol_stride + ndat * ndim (else
+ * DSPSR_AMD_EINVAL, nothing launched); nothing outside the ndat * ndim floats of a row is written.  ndat = 0: nothing to do. */
+int dspsr_amd_unpack_fpt(dspsr_amd_ctx* ctx, const int8_t* raw_dev, float scale, uint32_t nchan, uint32_t npol, uint32_t ndim,
+                         uint64_t ndat, float* out_dev, uint64_t out_chan_stride, uint64_t out_pol_stride);
+/* dspsr_amd_detect_raw replaces the unpacker, dsp::Detection (DetectionCUDA.cu:180-213 sqld_fpt; Detection.C:218-320 square_law,
+ * LoadToFil.C:267-271 Coherence with ndim 1) and dsp::TScrunch (TScrunch.C:148-178) by ONE pass over the block: complex input
+ * (ndim 2), npol 1 | 2, any nchan >= 1; the float voltages are never written.  Bit for bit dspsr_amd_unpack_fpt ->
+ * dspsr_amd_detect_square_law / dspsr_amd_detect_polarimetry(COHERENCE, ndim 1) -> dspsr_amd_tscrunch_fpt.
+ *   out_state       DSPSR_AMD_INTENSITY (npol_out 1) | DSPSR_AMD_PPQQ (2) | DSPSR_AMD_COHERENCE (4 rows: PP, QQ, Re, Im); one input
+ *                   polarisation gives Intensity (= PP) only
+ *   out_dev, carry_dev [nchan][npol_out], carry_count, nout: the stream contract of dspsr_amd_filterbank_perform_search above, with
+ *                   *nout = (carry_in + ndat) / tscrunch; overlapping or too short rows, tscrunch = 0, a null carry_dev or
+ *                   carry_count with tscrunch > 1: DSPSR_AMD_EINVAL, nothing launched, *carry_count and *nout as they were.
+ *                   tscrunch = 1 needs neither carry_dev nor carry_count.  ndat = 0: nothing to do (*nout = 0).
+ * Deterministic: no atomics, the same bits for every split of a stream into calls. */
+int dspsr_amd_detect_raw(dspsr_amd_ctx* ctx, const int8_t* raw_dev, float scale, uint32_t nchan, uint32_t npol, uint64_t ndat,
+                         int out_state, uint32_t tscrunch, float* out_dev, uint64_t out_chan_stride, uint64_t out_pol_stride,
+                         float* carry_dev, uint32_t* carry_count, uint64_t* nout);
+
 /* ---- search mode (digifil): dsp::TFPFilterbank (TFPFilterbank.C:27-101: forward FFT of 2*nchan real
  * samples per pol and part, Re^2+Im^2 of bins 0..nchan-1, TFP order) + optional pol sum + dsp::TScrunch
  * (TScrunch.C:180-206) fused in one launch.  Real dual-pol 8-bit input, raw_dev = first byte of the block.

@@ -712,7 +712,8 @@ extern "C" int dspsr_amd_tfp_filterbank(dspsr_amd_ctx* ctx, const dspsr_amd_tfp_
                     "dspsr_amd_tfp_filterbank: tscrunch=%u must divide or be a multiple of %u parts per workgroup", sf, T);
   if (raw_layout != DSPSR_AMD_RAW_GENERIC && raw_layout != DSPSR_AMD_RAW_CASPSR)
     return ctx_fail(ctx, DSPSR_AMD_EINVAL, "dspsr_amd_tfp_filterbank: unknown raw layout %d", raw_layout);
-  if (raw_layout == DSPSR_AMD_RAW_GENERIC && ((uintptr_t)raw_dev & 1))
+  // both byte orders are read as half words (tfp_word): the (p0, p1) pair of a sample, or two consecutive samples of a CASPSR group
+  if ((uintptr_t)raw_dev & 1)
     return ctx_fail(ctx, DSPSR_AMD_EINVAL, "dspsr_amd_tfp_filterbank: raw pointer must be 2-byte aligned");
   const uint64_t nout = npart / sf;
   if (nout == 0) return DSPSR_AMD_OK;

@@ -302,7 +302,9 @@ int dspsr_amd_detect_raw(dspsr_amd_ctx* ctx, const int8_t* raw_dev, float scale,
 
 /* ---- search mode (digifil): dsp::TFPFilterbank (TFPFilterbank.C:27-101: forward FFT of 2*nchan real
  * samples per pol and part, Re^2+Im^2 of bins 0..nchan-1, TFP order) + optional pol sum + dsp::TScrunch
- * (TScrunch.C:180-206) fused in one launch.  Real dual-pol 8-bit input, raw_dev = first byte of the block.
+ * (TScrunch.C:180-206) fused in one launch.  Real dual-pol 8-bit input, raw_dev = first byte of the block, 2-byte aligned in
+ * either byte order (an odd pointer: DSPSR_AMD_EINVAL; a 16-byte aligned block takes the faster whole-range loads).  npart < tscrunch:
+ * nothing to do.  Rows of out_dev behind npart/tscrunch - 1 are not written.
  *   out_dev: [npart/tscrunch][nchan][pscrunch ? 1 : 2] floats (PPQQ or Intensity, TimeSeries::OrderTFP) */
 typedef struct {
   uint32_t nchan;      /* -F nchan (power of two, 16..8192: both polarisations of one part fill a 2^14-point tile at 8192) */

@@ -1,6 +1,6 @@
 """tests/fuzz_misc.py [ncases] [seed] : invariants between code paths that must give the SAME bits.
   * search-mode front end: a 16-byte aligned block (whole-range loads through LDS) against the same bytes at an offset of
-    2 bytes (element-wise loads); random nchan / tscrunch / parts / byte order / pscrunch;
+    2 bytes (CASPSR order: 8, one group) (element-wise loads); random nchan / tscrunch / parts / byte order / pscrunch;
   * filterbank on float32 rows: aligned rows (regrouped per tile first) against rows shifted by one float (read in place);
   * pipeline: the detected layouts ndim 4 / 2 / 1 fold the same products in the same order -- identical sums, with and
     without -K, with sub-integrations."""
@@ -46,7 +46,7 @@ for i in range(ncases):
     nbytes = npart * L * 2
     buf = torch.randint(-128, 128, (nbytes + 32,), dtype=torch.int8, device="cuda")
     outs = []
-    for off in (0, 16 if caspsr else 2):                    # (a CASPSR stream can only move by whole groups: both aligned)
+    for off in (0, 8 if caspsr else 2):                     # (a CASPSR stream moves by whole groups of 8 bytes: element-wise loads too)
         raw = buf[16:16 + nbytes] if off == 0 else None
         if off:
             shifted = torch.empty(nbytes + 64, dtype=torch.int8, device="cuda")

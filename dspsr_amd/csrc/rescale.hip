@@ -12,8 +12,10 @@
 //       sub-byte samples are packed LSB first; -32 (pack_float, :309-342) writes TPF floats divided by the scale.
 //
 // The reference runs both on the host after a device-to-host transfer; here the block stays in HBM.  The sums are
-// tree reductions in double (the reference adds sample by sample in double): means agree to ~1e-16 relative, so a
-// digitised value can differ by one level only when x*scale falls within that distance of a rounding boundary.
+// tree reductions in double (the reference adds sample by sample in double): the ORDER of the additions is the only
+// difference.  On unquantised data the totals agree to ~1e-16 relative, offset / scale to a float ulp, and a digitised
+// value can differ by one level when x*scale falls within that distance of a rounding boundary; on data whose sums are
+// exact in double in any order every offset, scale, float and byte equals the reference's (tests/test_gpu_search_forms.py).
 #include <math.h>
 
 #include "engine_internal.h"
@@ -485,6 +487,10 @@ extern "C" int dspsr_amd_rescale_pscrunch_digitize(dspsr_amd_rescale* r, const f
   if (nbit < 8 && r->nchan % (8 / nbit))
     return ctx_fail(ctx, DSPSR_AMD_EINVAL, "dspsr_amd_rescale_pscrunch_digitize: nchan=%u not a multiple of %d samples per byte",
                     r->nchan, 8 / nbit);
+  // the kernel reads a channel's two polarisations as one float2: refused like the odd pointers of the TFP front end (a PPQQ sample
+  // is 8 bytes, so a block that starts on a sample of an 8-byte aligned buffer is aligned)
+  if ((uintptr_t)in_tfp_dev % 8)
+    return ctx_fail(ctx, DSPSR_AMD_EINVAL, "dspsr_amd_rescale_pscrunch_digitize: the block must be 8-byte aligned (%p)", (const void*)in_tfp_dev);
   if (!ndat) return DSPSR_AMD_OK;
   const DigiParams d = digi_params(nbit, 1, 1.0, scale_fac);        // behind Rescale the input scale is 1 (Rescale.C:204)
   const uint32_t nchan = r->nchan, spb = nbit >= 8 ? 1 : 8 / nbit, units = nchan / spb;

@@ -449,7 +449,10 @@ int dspsr_amd_rescale_get(dspsr_amd_rescale* r, float* offset_host, float* scale
  * dsp::Rescale (statistics and intervals exactly as dspsr_amd_rescale_transform, Rescale.C:217-388) -> dsp::PScrunch
  * (PScrunch.C:52,72-90) -> dsp::SigProcDigitizer::pack (SigProcDigitizer.C:112-236; nbit 1/2/4/8/16, input scale 1 behind Rescale),
  * the same float operations in the same order as the three separate calls -- identical bytes -- without writing the rescaled
- * and the summed block.  out_dev: [ndat][nchan * nbit / 8] bytes. */
+ * and the summed block.  out_dev: [ndat][nchan * nbit / 8] bytes.
+ * in_tfp_dev must be 8-byte aligned (the two polarisations of a channel are read as one float2; a PPQQ sample is 8 bytes, so any
+ * sample of an 8-byte aligned block qualifies): a block that is only float aligned is refused with DSPSR_AMD_EINVAL before any launch
+ * and the Rescale state stays as it was -- such a block takes the three separate calls, which accept any float address. */
 int dspsr_amd_rescale_pscrunch_digitize(dspsr_amd_rescale* r, const float* in_tfp_dev, uint64_t ndat, int nbit, float scale_fac,
                                         int flip_band, int swap_band, void* out_dev);
 int dspsr_amd_sigproc_digitize(dspsr_amd_ctx* ctx, const float* in_tfp_dev, uint64_t ndat, uint32_t nchan, uint32_t npol,

@@ -114,6 +114,16 @@ SYMBOLS = {
     "dspsr_amd_fold_get_ndat_folded": (_u64, [_vp]),
     "dspsr_amd_fold_zero": (_i, [_vp]),
     "dspsr_amd_fold_synch": (_i, [_vp, _vp]),
+    "dspsr_amd_cyclic_fold_create": (_i, [_vp, _pp]),
+    "dspsr_amd_cyclic_fold_destroy": (None, [_vp]),
+    "dspsr_amd_cyclic_fold_set_shape": (_i, [_vp, _u32, _u32, _u32, _u32, _u32, _u32]),
+    "dspsr_amd_cyclic_fold_set_ndat": (_i, [_vp, _u64, _u64]),
+    "dspsr_amd_cyclic_fold_set_bin": (_i, [_vp, _u64, _d, _d]),
+    "dspsr_amd_cyclic_fold_set_bins": (_i, [_vp, _d, _d, _u64, _u64, _vp, C.POINTER(_u64)]),
+    "dspsr_amd_cyclic_fold_fold": (_i, [_vp, _vp, _u64, _u64]),
+    "dspsr_amd_cyclic_fold_zero": (_i, [_vp]),
+    "dspsr_amd_cyclic_fold_lagdata_dev": (_vp, [_vp]),
+    "dspsr_amd_cyclic_fold_synch_lags": (_i, [_vp, _vp]),
     "dspsr_amd_comm_set_library": (_i, [C.c_char_p]),
     "dspsr_amd_comm_unique_id": (_i, [_vp]),
     "dspsr_amd_comm_create": (_i, [_vp, _i, _i, _vp, _pp]),
@@ -130,6 +140,8 @@ SYMBOLS = {
     "dspsr_amd_eight_bit_scale": (_d, [_d]),
     "dspsr_amd_fold_binplan": (_i, [_d, _d, _u32, _u64, _vp, _vp]),
     "dspsr_amd_fold_binplan_runs": (_i, [_d, _d, _u32, _u64, _vp, _vp, _vp, _u64, _vp, _vp]),
+    "dspsr_amd_cyclic_binplan": (_i, [_d, _d, _u32, _u64, _vp, _vp, _vp]),
+    "dspsr_amd_cyclic_lags_to_spectra": (_i, [_vp, _u32, _u32, _u32, _u32, _u32, _vp]),
 }
 
 

@@ -364,3 +364,82 @@ extern "C" int dspsr_amd_fold_binplan(double phi, double phase_per_sample, uint3
   }
   return DSPSR_AMD_OK;
 }
+
+// ---- cyclic spectra: dsp::CyclicFold (Signal/Pulsar/CyclicFold.C) ---------------------------------------------------------
+// The two bin plans of lag folding (CyclicFoldEngine::set_bin, CyclicFold.C:293-301, fed by the loop of Fold.C:744-787): the
+// phase at the sample and half a sample later.  hits[] counts every sample (Fold.C:783).
+extern "C" int dspsr_amd_cyclic_binplan(double phi, double phase_per_sample, uint32_t nbin, uint64_t ndat, uint32_t* plan0,
+                                        uint32_t* plan1, uint32_t* hits)
+{
+  if (!nbin || ((!plan0 || !plan1) && ndat)) return DSPSR_AMD_EINVAL;
+  const double double_nbin = double(nbin);
+  const double bins_per_sample = phase_per_sample * double_nbin;
+  for (uint64_t idat = 0; idat < ndat; idat++) {
+    phi -= floor(phi);
+    const double double_ibin = phi * double_nbin;
+    const unsigned ibin = unsigned(double_ibin);
+    phi += phase_per_sample;
+    if (ibin >= nbin) return DSPSR_AMD_EINVAL;
+    plan0[idat] = ibin;
+    plan1[idat] = unsigned(double_ibin + 0.5 * bins_per_sample) % nbin;
+    if (hits) hits[ibin]++;
+  }
+  return DSPSR_AMD_OK;
+}
+
+// CyclicFoldEngine::synch (CyclicFold.C:450-555): per (bin, pol, chan) the window of :519-537 when mover > 1, an unnormalised
+// backward complex-to-real transform of nchan_spec = 2 nlag - 2 points (FTransform bcr1d: out[j] = sum over the Hermitian
+// spectrum of z[k] e^{+2 pi i j k / n}; the imaginary parts of z[0] and z[n/2] do not enter), every mover-th point kept.
+//   lags [bin][pol][chan][lag][re, im]  ->  out [chan * nchan_spec / mover + schan][pol][bin]
+// The transform: the Hermitian extension through a radix-2 complex transform in float, twiddles rounded from double.
+extern "C" int dspsr_amd_cyclic_lags_to_spectra(const float* lags, uint32_t nchan, uint32_t npol, uint32_t nbin, uint32_t nlag,
+                                                uint32_t mover, float* out)
+{
+  if (!lags || !out || !nchan || !npol || !nbin || nlag < 2 || !mover) return DSPSR_AMD_EINVAL;
+  const uint32_t n = 2 * nlag - 2;
+  if ((n & (n - 1)) || n % mover) return DSPSR_AMD_EINVAL;
+  const uint32_t nkeep = n / mover;
+  uint32_t logn = 0;
+  while ((1u << logn) < n) logn++;
+  std::vector<std::complex<float>> tw(n / 2 ? n / 2 : 1), z(n);
+  for (uint32_t k = 0; k < n / 2; k++)
+    tw[k] = std::complex<float>((float)cos(2.0 * M_PI * k / n), (float)sin(2.0 * M_PI * k / n));
+  std::vector<uint32_t> rev(n);
+  for (uint32_t i = 0; i < n; i++) {
+    uint32_t r = 0;
+    for (uint32_t b = 0; b < logn; b++) r |= ((i >> b) & 1u) << (logn - 1 - b);
+    rev[i] = r;
+  }
+  std::vector<float> win(nlag, 1.0f);
+  if (mover > 1)
+    for (uint32_t ilag = 1; ilag < nlag; ilag++) {           // CyclicFold.C:523-532
+      const float x = (M_PI / 3) * mover * ilag / ((float)(2 * nlag - 2));
+      const float y = 0.5 * (1 + cos(2 * M_PI * float(ilag) / float(2 * nlag)));
+      win[ilag] = y * sinf(x) / x;
+    }
+  for (uint32_t ibin = 0; ibin < nbin; ibin++)
+    for (uint32_t ipol = 0; ipol < npol; ipol++)
+      for (uint32_t ichan = 0; ichan < nchan; ichan++) {
+        const float* l = lags + 2 * ((((size_t)ibin * npol + ipol) * nchan + ichan) * nlag);
+        z[rev[0]] = std::complex<float>(l[0] * win[0], 0.f);
+        for (uint32_t k = 1; k < nlag - 1; k++) {
+          const std::complex<float> v(l[2 * k] * win[k], l[2 * k + 1] * win[k]);
+          z[rev[k]] = v;
+          z[rev[n - k]] = std::conj(v);
+        }
+        z[rev[nlag - 1]] = std::complex<float>(l[2 * (nlag - 1)] * win[nlag - 1], 0.f);
+        for (uint32_t len = 2; len <= n; len <<= 1) {
+          const uint32_t half = len / 2, step = n / len;
+          for (uint32_t i = 0; i < n; i += len)
+            for (uint32_t j = 0; j < half; j++) {
+              const std::complex<float> w = tw[j * step], a = z[i + j], b = z[i + j + half];
+              const std::complex<float> t(w.real() * b.real() - w.imag() * b.imag(), w.real() * b.imag() + w.imag() * b.real());
+              z[i + j] = a + t;
+              z[i + j + half] = a - t;
+            }
+        }
+        for (uint32_t schan = 0; schan < nkeep; schan++)
+          out[(((size_t)ichan * nkeep + schan) * npol + ipol) * nbin + ibin] = z[schan * mover].real();
+      }
+  return DSPSR_AMD_OK;
+}

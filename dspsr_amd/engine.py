@@ -688,6 +688,99 @@ class FoldEngine:
             pass
 
 
+def cyclic_binplan(phi: float, phase_per_sample: float, nbin: int, ndat: int):
+    """The two plans of lag folding (CyclicFold.C:293-301 fed by Fold.C:744-787) and hits[nbin]."""
+    p0, p1 = np.empty(ndat, dtype=np.uint32), np.empty(ndat, dtype=np.uint32)
+    hits = np.zeros(nbin, dtype=np.uint32)
+    code = lib.dspsr_amd_cyclic_binplan(phi, phase_per_sample, nbin, ndat, p0.ctypes.data_as(C.c_void_p),
+                                        p1.ctypes.data_as(C.c_void_p), hits.ctypes.data_as(C.c_void_p))
+    if code != 0:
+        raise DspsrAmdError("dspsr_amd_cyclic_binplan failed (%d)" % code)
+    return p0, p1, hits
+
+
+def cyclic_lags_to_spectra(lags: np.ndarray, mover: int = 1) -> np.ndarray:
+    """CyclicFoldEngine::synch (CyclicFold.C:450-555): lags float32 [nbin][npol][nchan][nlag][2] -> spectra float32
+    [nchan * (2 nlag - 2) / mover][npol][nbin].  The transform runs inside the library (host code, no numpy)."""
+    lags = np.ascontiguousarray(lags, dtype=np.float32)
+    assert lags.ndim == 5 and lags.shape[4] == 2
+    nbin, npol, nchan, nlag = lags.shape[:4]
+    if nlag < 2 or mover < 1 or (2 * nlag - 2) % mover:
+        raise DspsrAmdError("dspsr_amd_cyclic_lags_to_spectra: nlag=%d, mover=%d" % (nlag, mover))
+    out = np.empty((nchan * ((2 * nlag - 2) // mover), npol, nbin), dtype=np.float32)
+    code = lib.dspsr_amd_cyclic_lags_to_spectra(lags.ctypes.data_as(C.c_void_p), nchan, npol, nbin, nlag, mover,
+                                                out.ctypes.data_as(C.c_void_p))
+    if code != 0:
+        raise DspsrAmdError("dspsr_amd_cyclic_lags_to_spectra failed (%d): 2*nlag-2 = %d must be a power of two and a "
+                            "multiple of mover = %d" % (code, 2 * nlag - 2, mover))
+    return out
+
+
+class CyclicFoldEngine:
+    """dsp::CyclicFoldEngine (Signal/Pulsar/dsp/CyclicFold.h:93-160); owns the device-resident lag data."""
+
+    def __init__(self, ctx: Context):
+        self.ctx = ctx
+        h = C.c_void_p()
+        _check(ctx.handle, lib.dspsr_amd_cyclic_fold_create(ctx.handle, C.byref(h)), "dspsr_amd_cyclic_fold_create")
+        self.handle = h
+        self.shape = None
+        self.mover = 1
+
+    def set_shape(self, nchan, npol_in, npol_out, nlag, mover, nbin):
+        _check(self.ctx.handle, lib.dspsr_amd_cyclic_fold_set_shape(self.handle, nchan, npol_in, npol_out, nlag, mover, nbin),
+               "dspsr_amd_cyclic_fold_set_shape")
+        self.shape = (nbin, npol_out, nchan, nlag, 2)
+        self.mover = mover
+
+    def set_ndat(self, ndat, idat_start=0):
+        _check(self.ctx.handle, lib.dspsr_amd_cyclic_fold_set_ndat(self.handle, ndat, idat_start), "dspsr_amd_cyclic_fold_set_ndat")
+
+    def set_bin(self, idat, ibin, bins_per_sample):
+        _check(self.ctx.handle, lib.dspsr_amd_cyclic_fold_set_bin(self.handle, idat, ibin, bins_per_sample),
+               "dspsr_amd_cyclic_fold_set_bin")
+
+    def set_bins(self, phi, phase_per_sample, ndat, idat_start=0, hits: np.ndarray | None = None):
+        n = C.c_uint64()
+        hp = hits.ctypes.data_as(C.c_void_p) if hits is not None else None
+        _check(self.ctx.handle, lib.dspsr_amd_cyclic_fold_set_bins(self.handle, phi, phase_per_sample, ndat, idat_start, hp,
+                                                                   C.byref(n)), "dspsr_amd_cyclic_fold_set_bins")
+        return n.value
+
+    def fold(self, inp):
+        """inp: float32 device tensor [nchan][npol_in][>= 2 * (idat_start + ndat)] of complex samples (FPT order)."""
+        cs, ps = _strides3(inp)
+        _check(self.ctx.handle, lib.dspsr_amd_cyclic_fold_fold(self.handle, inp.data_ptr(), cs, ps), "dspsr_amd_cyclic_fold_fold")
+
+    def zero(self):
+        _check(self.ctx.handle, lib.dspsr_amd_cyclic_fold_zero(self.handle), "dspsr_amd_cyclic_fold_zero")
+
+    def get_lagdata_ptr(self):
+        return lib.dspsr_amd_cyclic_fold_lagdata_dev(self.handle)
+
+    def synch_lags(self) -> np.ndarray:
+        """The lag data on the host, [nbin][npol_out][nchan][nlag][re, im] (blocks)."""
+        out = np.empty(self.shape, dtype=np.float32)
+        _check(self.ctx.handle, lib.dspsr_amd_cyclic_fold_synch_lags(self.handle, out.ctypes.data_as(C.c_void_p)),
+               "dspsr_amd_cyclic_fold_synch_lags")
+        return out
+
+    def synch(self) -> np.ndarray:
+        """CyclicFoldEngine::synch: spectra [nchan * nchan_spec / mover][npol_out][nbin]."""
+        return cyclic_lags_to_spectra(self.synch_lags(), self.mover)
+
+    def close(self):
+        if self.handle and self.ctx.handle:
+            lib.dspsr_amd_cyclic_fold_destroy(self.handle)
+        self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class Communicator:
     """The sub-integration exchange over RCCL / xGMI behind the C-ABI (dspsr_amd_comm_*, csrc/comm.hip): the same entry
     points DSPSR's C++ host calls.  One per pipeline context.  `unique_id` = the 128 bytes of `Communicator.unique_id()`

@@ -19,7 +19,7 @@ from dataclasses import dataclass
 import numpy as np
 
 from . import _lib
-from .engine import (Context, ConvolutionEngine, Dedispersion, DspsrAmdError, FilterbankEngine, FoldEngine, Rescale, SampleDelay, add_fpt, copy_data_fpt,
+from .engine import (Context, ConvolutionEngine, CyclicFoldEngine, Dedispersion, DspsrAmdError, FilterbankEngine, FoldEngine, Rescale, SampleDelay, add_fpt, copy_data_fpt,
                      dedispersion_sample_delays, detect_raw, eight_bit_scale, fscrunch_fpt, pscrunch_tfp, sigproc_digitize, sigproc_digitize_fpt,
                      tfp_filterbank, tscrunch_fpt)
 
@@ -66,6 +66,11 @@ class Config:
                                            # alone (no coherent dedispersion)
     record_time: bool = False              # -r: time every operation (Operation.C:90-113); each one then ends with a stream
                                            # synchronisation so that the wall times are honest (FilterbankCUDA.cu:302-303)
+    cyclic_nchan: int = 0                  # -cyclic N: cyclic spectra of N channels per filterbank channel; dsp::CyclicFold replaces
+                                           # Detection + Fold (LoadToFold1.C:534-539,999-1044).  0: off -- today's path, untouched
+    cyclic_mover: int = 1                  # -cyclicoversample M: nlag = M * N / 2 + 1 (dsp/CyclicFold.h:66)
+    cyclic_npol: int = 0                   # output polarisations of the cyclic fold (the reference passes config->npol): 1, 2 or 4;
+                                           # 0 = 4 (Coherence) for two input polarisations, 1 for one
 
 
 @dataclass
@@ -790,6 +795,50 @@ class ConvolutionThenFilterbank:
         self.dedispersed = None
 
 
+def cyclic_geometry(cfg: "Config", info: "InputInfo"):
+    """Sizes and state of a cyclic-spectrum run (dsp/CyclicFold.h:66, CyclicFold.C:96-119): nlag, nchan_spec = 2 nlag - 2,
+    nchan_spec / mover output channels per filterbank channel, ndim 1, npol 1 (Intensity; PP for one input polarisation),
+    2 (PPQQ) or 4 (Coherence).  Raises DspsrAmdError for what the reference refuses or this path does not build."""
+    n, m = int(cfg.cyclic_nchan), int(cfg.cyclic_mover)
+    if n <= 0:
+        raise DspsrAmdError("dspsr_amd.cyclic_geometry: cyclic_nchan=%d" % n)
+    if m < 1 or (m * n) % 2:
+        raise DspsrAmdError("dsp::CyclicFold nlag = mover*nchan/2 + 1 needs an even mover*nchan (nchan=%d, mover=%d)" % (n, m))
+    nlag = m * n // 2 + 1
+    nchan_spec = 2 * nlag - 2
+    if nchan_spec & (nchan_spec - 1):
+        raise DspsrAmdError("dspsr_amd.LoadToFold: cyclic spectra of %d x %d points: the backward transform of the lags is built "
+                            "for powers of two" % (n, m))
+    npol = int(cfg.cyclic_npol) or (4 if info.npol == 2 else 1)
+    if npol not in (1, 2, 4):
+        raise DspsrAmdError("dsp::CyclicFold::prepare_output invalid npol=%d" % npol)             # CyclicFold.C:117-119
+    if info.npol == 1 and npol != 1:
+        raise DspsrAmdError("dsp::CyclicFold: one input polarisation gives npol=1 only (asked for %d)" % npol)
+    if info.npol not in (1, 2):
+        raise DspsrAmdError("dsp::CyclicFoldEngine::fold Invalid npol=%d" % info.npol)             # CyclicFold.C:443-445
+    state = {1: "PP" if info.npol == 1 else "Intensity", 2: "PPQQ", 4: "Coherence"}[npol]
+    return {"nlag": nlag, "mover": m, "nchan_spec": nchan_spec, "nchan_per_channel": nchan_spec // m,
+            "nchan": cfg.nchan * (nchan_spec // m), "npol": npol, "ndim": 1, "state": state}
+
+
+def cyclic_check(cfg: "Config", info: "InputInfo", ntargets=0, subband=None, dump_before=()):
+    """What a cyclic run refuses, before any device resource is opened; returns cyclic_geometry."""
+    if cfg.subint_turns == 1.0:
+        raise DspsrAmdError("dsp::LoadToFold::build Single-pulse and cyclic spectrum modes are incompatible")  # LoadToFold1.C:1037-1039
+    if ntargets > 1:
+        raise DspsrAmdError("dspsr_amd.LoadToFold: cyclic spectra fold one pulsar; %d targets given" % ntargets)
+    if cfg.interchan_dedispersion:
+        raise DspsrAmdError("dspsr_amd.LoadToFold: -K is not built for cyclic spectra")
+    if cfg.convolve_when != "during":
+        raise DspsrAmdError("dspsr_amd.LoadToFold: cyclic spectra are built for -F N:D (convolve_when = during), not %r"
+                            % (cfg.convolve_when,))
+    if subband is not None:
+        raise DspsrAmdError("dspsr_amd.LoadToFold: cyclic spectra are not built for sub-band sharded runs / communicators")
+    if tuple(dump_before):
+        raise DspsrAmdError("dspsr_amd.LoadToFold: the dump taps are not built for cyclic spectra")
+    return cyclic_geometry(cfg, info)
+
+
 class LoadToFold:
     """One pipeline instance = one GPU = one stream (SingleThread).  `raw` blocks are int8 torch
     tensors already resident on the device (the PCIe copy is the caller's, as TransferCUDA is a
@@ -805,6 +854,9 @@ class LoadToFold:
         `subints` / `hits` of the instance itself stay empty.  Multi-GPU exchange (subband, communicators) is single-pulsar only."""
         targets = list(targets or [])
         self.pulsars = []
+        self.cyclic = None
+        if cfg.cyclic_nchan > 0:                         # (before any device resource is opened)
+            self._cyclic_geometry = cyclic_check(cfg, info, len(targets), subband, dump_before)
         if len(targets) > 1 and subband is not None:
             raise DspsrAmdError("dspsr_amd.LoadToFold: sub-band sharded runs fold one pulsar; %d targets given" % len(targets))
         for t in targets:                                # (before any device resource is opened)
@@ -837,6 +889,8 @@ class LoadToFold:
             raise DspsrAmdError("dspsr_amd.LoadToFold: subband=%d outside the %d input channels" % (subband, info.nchan))
         if cfg.folding_period <= 0 and polyco is None:
             raise DspsrAmdError("dsp::Fold::fold no polynomial and no period specified")   # Fold.C:638-640
+        if cfg.cyclic_nchan > 0:
+            return self._init_cyclic(device, stream)
         if info.npol != 2:
             raise DspsrAmdError("dsp::Detection::polarimetry Cannot detect polarization when npol != 2")
         if cfg.convolve_when not in ("during", "after", "before", "never"):
@@ -948,6 +1002,83 @@ class LoadToFold:
         self.ndat_out = 0               # output samples produced so far
         self.subints = []               # completed sub-integrations (host copies) on the writer rank
 
+    def _init_cyclic(self, device, stream):
+        """`dspsr -cyclic N`: the convolving filterbank writes its complex rows, dsp::CyclicFold folds their lag products
+        (LoadToFold1.C:534-539,999-1044); Detection and Fold are not built.  At a sub-integration the lag data come to the host
+        and CyclicFoldEngine::synch turns them into spectra (once per sub-integration: host, as in the reference)."""
+        import torch
+        cfg, info, g = self.cfg, self.info, self._cyclic_geometry
+        if cfg.nchan % info.nchan:
+            raise DspsrAmdError("dsp::Filterbank::make_preparations output nchan=%d not a multiple of input nchan=%d"
+                                % (cfg.nchan, info.nchan))
+        self.ctx = Context(device, stream)
+        self.response = Dedispersion(info.centre_frequency, info.bandwidth, cfg.dispersion_measure, input_nchan=info.nchan,
+                                     ndim=info.ndim)
+        if cfg.freq_res:
+            self.response.set_frequency_resolution(cfg.freq_res)
+        self.response.match(cfg.nchan)
+        r = self.response
+        nsub = cfg.nchan // info.nchan
+        self.in_nchan, self.nchan_out = info.nchan, cfg.nchan
+        self.fb = FilterbankEngine(self.ctx).setup(nsub, r.ndat, r.impulse_pos, r.impulse_neg, info.nchan, info.npol, info.ndim == 1,
+                                                   r.kernel, max_parts=cfg.max_parts, force_four_pass=0 if cfg.two_pass else 2,
+                                                   fused_fold=_lib.FUSED_NEVER)
+        self.nkeep, self.nsamp_step, self.nsamp_overlap = self.fb.nkeep, self.fb.nsamp_step, self.fb.nsamp_overlap
+        self.npol_out = g["npol"]
+        self.fold = None
+        self.cyclic = CyclicFoldEngine(self.ctx)
+        self.cyclic.set_shape(self.nchan_out, info.npol, g["npol"], g["nlag"], g["mover"], cfg.nbin)
+        self.scale8 = eight_bit_scale()
+        self.layout = _lib.RAW_CASPSR if info.machine == "CASPSR" else _lib.RAW_GENERIC
+        n_fft = nsub * r.ndat
+        nsamp_fft = 2 * n_fft if info.ndim == 1 else n_fft
+        self.out_rate = info.rate * (float(r.ndat) / float(nsamp_fft))
+        self.out_start = info.start_seconds + r.impulse_pos / self.out_rate
+        self.scalefac = float(n_fft) * float(r.ndat)
+        self.sample_delay, self.sd_carried, self.sd_head = None, 0, 0
+        self.voltages = torch.empty((self.nchan_out, info.npol, 2 * cfg.parts_per_block * self.nkeep), dtype=torch.float32,
+                                    device="cuda:%d" % device)
+        self.fused_mode, self.fused_fold = 0, False
+        self.optime, self.dumps, self._dump_cplx = {}, {}, None
+        self.hits = np.zeros(cfg.nbin, dtype=np.uint32)
+        self.integration_length, self.ndat_total = 0.0, 0
+        self.nsamples_in, self.ndat_out = 0, 0
+        self.subints = []
+
+    def _process_block_cyclic(self, raw, npart, events):
+        """Filterbank -> complex rows -> CyclicFold piece by piece (Subint<CyclicFold>).  Lag products never span two fold
+        calls (CyclicFold.C:390: idat < ndat_fold - nlag), so the last nlag samples of every piece add nothing."""
+        ndat = npart * self.nkeep
+        if events is not None:
+            events[0].record()
+        self._op("Filterbank", lambda: self.fb.perform_raw(raw, self.layout, self.scale8, self.voltages, npart))
+        if events is not None:
+            events[1].record()
+        for idat_start, ndat_fold, _division, complete in self._pieces(ndat):
+            t0 = self.out_start + (self.ndat_out + idat_start + 0.5) / self.out_rate
+            phi, pfold = self._phase(t0)
+            self.cyclic.set_ndat(ndat_fold, idat_start)
+            folded = self.cyclic.set_bins(phi, (1.0 / self.out_rate) / pfold, ndat_fold, idat_start, self.hits)
+            self._op("CyclicFold", lambda: self.cyclic.fold(self.voltages))
+            self.integration_length += folded / self.out_rate
+            self.ndat_total += ndat_fold
+            if complete:
+                self.finish_subint()
+        self.ndat_out += ndat
+        self.nsamples_in += npart * self.nsamp_step
+
+    def _finish_cyclic_subint(self):
+        """CyclicFoldEngine::synch (CyclicFold.C:450-555): spectra [nchan * nchan_spec / mover][npol][nbin][1] on the host"""
+        if not self.ndat_total:                              # nothing folded since the last one (as the multi-pulsar branch)
+            return
+        spectra = self._op("CyclicFold::synch", lambda: self.cyclic.synch())
+        self.subints.append({"hits": self.hits.copy(), "integration_length": self.integration_length,
+                             "ndat_total": self.ndat_total, "profile": spectra[..., None]})
+        self.cyclic.zero()
+        self.hits[:] = 0
+        self.integration_length = 0.0
+        self.ndat_total = 0
+
     def _init_targets(self, targets):
         """nbin per target (Fold::choose_nbin for its period where the target gives none); several targets: one FoldEngine each,
         the fused fold off (the detected rows are shared)."""
@@ -959,7 +1090,11 @@ class LoadToFold:
         if len(targets) == 1:
             if nbins[0] != cfg.nbin:
                 self.cfg = dataclasses.replace(cfg, nbin=nbins[0])
-                self.fold.set_shape(self.nchan_out, self.npol_out, cfg.ndim, nbins[0])
+                if self.cyclic is not None:
+                    g = self._cyclic_geometry
+                    self.cyclic.set_shape(self.nchan_out, info.npol, g["npol"], g["nlag"], g["mover"], nbins[0])
+                else:
+                    self.fold.set_shape(self.nchan_out, self.npol_out, cfg.ndim, nbins[0])
                 self.hits = np.zeros(nbins[0], dtype=np.uint32)
             return
         self.fused_mode, self.fused_fold = 0, False
@@ -1125,6 +1260,8 @@ class LoadToFold:
         if raw.numel() < self.block_bytes(npart):
             raise DspsrAmdError("dspsr_amd.LoadToFold.process_block: block holds %d bytes, %d needed"
                                 % (raw.numel(), self.block_bytes(npart)))
+        if self.cyclic is not None:
+            return self._process_block_cyclic(raw, npart, events)
         ndat = npart * self.nkeep
         state = _lib.STOKES if cfg.stokes else _lib.COHERENCE
         if "Detection" in self.dumps:                        # the filterbank's complex output: one extra pass, taps only
@@ -1243,7 +1380,12 @@ class LoadToFold:
 
     def set_communicator(self, dist, rank, world, gather_buffer=None, replicas=False):
         self._single_pulsar_only("set_communicator")
+        self._no_cyclic("set_communicator")
         self._subint_comm = (dist, rank, world, gather_buffer, replicas)
+
+    def _no_cyclic(self, what):
+        if self.cyclic is not None:
+            raise DspsrAmdError("dspsr_amd.LoadToFold.%s: cyclic spectra are not built for a multi-GPU exchange" % what)
 
     def _single_pulsar_only(self, what):
         if self.pulsars:
@@ -1323,6 +1465,7 @@ class LoadToFold:
         points DSPSR's host calls).  Without one, finish_subint falls back to the torch.distributed calls below, which
         exist for the gloo CPU tests and for rehearsing several ranks on one device (RCCL needs one GPU per rank)."""
         self._single_pulsar_only("set_rccl_communicator")
+        self._no_cyclic("set_rccl_communicator")
         self.comm = comm
 
     def collect_subint(self, copy=None):
@@ -1358,6 +1501,8 @@ class LoadToFold:
                 if p.ndat_total:
                     self._finish_pulsar_subint(p)
             return
+        if self.cyclic is not None:
+            return self._finish_cyclic_subint()
         if self.comm is not None:
             # (one exchange in flight per communicator.  The result of the previous one is COPIED here even with
             #  copy_subints False: start() below may grow the pinned buffer a view would point into -- a view is only handed
@@ -1470,6 +1615,8 @@ class LoadToFold:
         self.fb.close()
         if self.fold is not None:
             self.fold.close()
+        if self.cyclic is not None:
+            self.cyclic.close()
         for p in self.pulsars:
             p.fold.close()
         self.ctx.close()

@@ -7,6 +7,8 @@
  *   dsp::Filterbank::Engine     Signal/General/dsp/FilterbankEngine.h:15-44 (CUDA impl FilterbankCUDA.cu:73-304)
  *   dsp::Detection::Engine      Signal/General/dsp/Detection.h:98-106  (CUDA impl DetectionCUDA.cu:127-322)
  *   dsp::Fold::Engine           Signal/Pulsar/dsp/Fold.h:249-312       (CUDA impl FoldCUDA.cu:64-697)
+ *   dsp::CyclicFoldEngine       Signal/Pulsar/dsp/CyclicFold.h:93-160  (CPU impl CyclicFold.C:173-555: the definition;
+ *                                                                       CUDA impl CyclicFoldEngineCUDA.cu)
  *   host-side preparation       Dedispersion.C:216-556, Response.C:132-344,649-700, optimize_fft.c:63-127,
  *                               Filterbank.C:55-263, Fold.C:650-787
  *
@@ -36,6 +38,7 @@ extern "C" {
 typedef struct dspsr_amd_ctx dspsr_amd_ctx;
 typedef struct dspsr_amd_filterbank dspsr_amd_filterbank;
 typedef struct dspsr_amd_fold dspsr_amd_fold;
+typedef struct dspsr_amd_cyclic_fold dspsr_amd_cyclic_fold;
 
 /* ---- context: one per pipeline thread / GPU, bound to one stream (SingleThread.C:213-290) ---- */
 /* hip_stream: a hipStream_t to enqueue on (NULL = the legacy default stream), or
@@ -370,6 +373,46 @@ uint64_t dspsr_amd_fold_get_ndat_folded(const dspsr_amd_fold* fold);
 int dspsr_amd_fold_zero(dspsr_amd_fold* fold);                                            /* Engine::zero */
 int dspsr_amd_fold_synch(dspsr_amd_fold* fold, float* profile_host);                      /* FoldCUDA.cu:127-152 (blocks) */
 
+/* ---- dsp::CyclicFoldEngine: cyclic spectra, `dspsr -cyclic N [-cyclicoversample M]` (LoadToFold1.C:534-539,999-1044) ----------
+ * Lag-domain folding of the filterbank's complex voltages (Analytic float rows in FPT order: what
+ * dspsr_amd_filterbank_perform[_raw] writes).  The semantics are those of the reference's CPU engine, dsp::CyclicFoldEngine
+ * (Signal/Pulsar/CyclicFold.C); its CUDA engine follows a rounded plan (CyclicFoldEngineCUDA.cu:232-331) that differs from the
+ * CPU engine's per-sample plan, and where the two disagree the CPU engine is the definition here.
+ *   sizes   nlag = mover * nchan_cyclic / 2 + 1 (dsp/CyclicFold.h:66); nchan_spec = 2 nlag - 2; nchan_spec / mover output
+ *           channels per input channel, ndim 1; npol_out 1 (Intensity; PP for one input polarisation), 2 (PPQQ) or 4
+ *           (Coherence) (CyclicFold.C:96-119); one input polarisation allows npol_out = 1 only.
+ *   plan    set_bin (CyclicFold.C:293-301): plan0[i] = unsigned(ibin), plan1[i] = unsigned(ibin + 0.5 bins_per_sample) % nbin,
+ *           i = idat - idat_start; set_bins runs the double recurrence of Fold.C:744-787 (as dspsr_amd_fold_binplan) inside the
+ *           library, hits_host[] and *ndat_folded count EVERY sample of the call (Fold.C:783-784), the last nlag ones included.
+ *   fold    (CyclicFold.C:339-448) ndat_fold <= nlag: nothing is accumulated.  Else for idat < ndat_fold - nlag, ilag < nlag:
+ *             lag[bin][pol][chan][ilag] += x[idat] * conj(y[idat + ilag]),  bin = plan[ilag % 2][idat + ilag / 2]
+ *           (re += a.re b.re + a.im b.im, im += a.im b.re - a.re b.im; :316-321), (x, y) = (p0,p0) + (p1,p1) into one sum for
+ *           npol_out 1; (p0,p0), (p1,p1) for 2; then (p0,p1), (p1,p0) for 4.  Products that would span two calls are dropped, as in
+ *           the reference.  Rows: in_dev + chan * in_chan_stride + pol * in_pol_stride + 2 * idat_start (strides in floats, any
+ *           stride >= the row, rows 8-byte aligned: else DSPSR_AMD_EINVAL before a launch).  Input is only read.
+ * Sums are float, re-associated (per run of a bin and per time segment; the cut depends on the shape alone) and use fused
+ * multiply-adds: no atomics, the same bits run to run and for the same sequence of fold calls.
+ * set_shape allocates the device lag array, nbin * npol_out * nchan * nlag * 2 floats, zeroed (and, for shapes with few
+ * (channel, lag) owners, up to 64 partial arrays of that size within 2 GiB): DSPSR_AMD_ENOMEM if it does not fit.  nlag in
+ * [2, 65536], nchan <= 65535, ndat < 2^31 per call; anything else DSPSR_AMD_EINVAL before a launch.
+ * Call order per Fold::fold (Fold.C:724-829): set_ndat, set_bin x ndat (or set_bins), fold. */
+int dspsr_amd_cyclic_fold_create(dspsr_amd_ctx* ctx, dspsr_amd_cyclic_fold** fold);
+void dspsr_amd_cyclic_fold_destroy(dspsr_amd_cyclic_fold* fold);
+int dspsr_amd_cyclic_fold_set_shape(dspsr_amd_cyclic_fold* fold, uint32_t nchan, uint32_t npol_in, uint32_t npol_out,
+                                    uint32_t nlag, uint32_t mover, uint32_t nbin);
+int dspsr_amd_cyclic_fold_set_ndat(dspsr_amd_cyclic_fold* fold, uint64_t ndat, uint64_t idat_start);   /* CyclicFold.C:234-256 */
+int dspsr_amd_cyclic_fold_set_bin(dspsr_amd_cyclic_fold* fold, uint64_t idat, double ibin, double bins_per_sample);
+int dspsr_amd_cyclic_fold_set_bins(dspsr_amd_cyclic_fold* fold, double phi, double phase_per_sample, uint64_t ndat,
+                                   uint64_t idat_start, uint32_t* hits_host, uint64_t* ndat_folded);
+int dspsr_amd_cyclic_fold_fold(dspsr_amd_cyclic_fold* fold, const float* in_dev, uint64_t in_chan_stride,
+                               uint64_t in_pol_stride);
+int dspsr_amd_cyclic_fold_zero(dspsr_amd_cyclic_fold* fold);                               /* CyclicFold.C:283-291 */
+/* device lag array [bin][pol][chan][lag][re, im] (get_lagdata_ptr, CyclicFold.C:329-337), valid in stream order */
+float* dspsr_amd_cyclic_fold_lagdata_dev(dspsr_amd_cyclic_fold* fold);
+/* copy to the host in the same order and wait (CyclicFoldEngineCUDA.cu:72-107): a C++ caller hands it to
+ * dsp::CyclicFoldEngine::synch, any other to dspsr_amd_cyclic_lags_to_spectra */
+int dspsr_amd_cyclic_fold_synch_lags(dspsr_amd_cyclic_fold* fold, float* lagdata_host);
+
 /* ---- the sub-integration dump over RCCL / xGMI: the ONE exchange of the path -----------------------------------------
  * Reference hook: dsp::Subint<Fold>::transformation emits the finished sub-integration (Signal/Pulsar/dsp/Subint.h:291-303);
  * merging semantics = PhaseSeries::combine (Signal/Pulsar/PhaseSeries.C:442-484); the reference merges its threads' pieces
@@ -518,6 +561,17 @@ int dspsr_amd_fold_binplan(double phi, double phase_per_sample, uint32_t nbin, u
 int dspsr_amd_fold_binplan_runs(double phi, double phase_per_sample, uint32_t nbin, uint64_t ndat, uint64_t* run_offset,
                                 uint32_t* run_bin, uint64_t* run_hits, uint64_t cap, uint64_t* nruns, uint32_t* hits_host);
 
+/* the two plans of lag folding (CyclicFold.C:293-301 fed by Fold.C:744-787): plan0[ndat], plan1[ndat], hits[nbin] += (may be NULL) */
+int dspsr_amd_cyclic_binplan(double phi, double phase_per_sample, uint32_t nbin, uint64_t ndat, uint32_t* plan0_host,
+                             uint32_t* plan1_host, uint32_t* hits_host);
+/* dsp::CyclicFoldEngine::synch (CyclicFold.C:450-555) on the host, once per sub-integration as in the reference: per (bin, pol,
+ * chan), for mover > 1 the window 0.5 (1 + cos(2 pi l / (2 nlag))) sin(x) / x, x = (pi / 3) mover l / (2 nlag - 2), on lags l >= 1
+ * (:519-537, float arithmetic), then an unnormalised backward complex-to-real transform of nchan_spec = 2 nlag - 2 points
+ * (FTransform bcr1d), every mover-th point kept (:539-546):
+ *   lags_host [bin][pol][chan][lag][re, im]  ->  out_host [chan * nchan_spec / mover + schan][pol][bin]
+ * nchan_spec must be a power of two (and a multiple of mover): anything else DSPSR_AMD_EINVAL. */
+int dspsr_amd_cyclic_lags_to_spectra(const float* lags_host, uint32_t nchan, uint32_t npol, uint32_t nbin, uint32_t nlag,
+                                     uint32_t mover, float* out_host);
 #ifdef __cplusplus
 }
 #endif

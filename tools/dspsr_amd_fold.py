@@ -6,6 +6,8 @@ dspsr_amd.dada.fold_file for trying the engine on a DADA file; not a re-implemen
   dspsr_amd_fold.py -F 128 ...   (no `:D`: filterbank, THEN coherent dedispersion per channel -- Filterbank::Config::After; -D 0: none)
   dspsr_amd_fold.py -F 128:B ... (coherent dedispersion of the whole band, THEN the filterbank -- Filterbank::Config::Before)
                     [--dump Detection] [--dump Fold] [-O out_prefix] file.dada
+  dspsr_amd_fold.py -F 64:D -cyclic 256 [-cyclicoversample 4] [-d 1|2|4] ...   (cyclic spectra: dsp::CyclicFold instead of
+                    Detection + Fold; -d is then the number of output polarisations, default 4 -- 1 for single-polarisation input)
 
 Every completed sub-integration is written as <prefix>_<n>.ps (the PhaseSeries hand-off file of INTEGRATION.md:
 raw sums + hits; dsp::Archiver's normalisation is the reader's job).
@@ -33,7 +35,9 @@ def parse_args(argv=None):
     ap.add_argument("-s", dest="single", action="store_true", help="single pulses (one turn per sub-integration)")
     ap.add_argument("-turns", dest="turns", type=float, default=0.0, help="turns per sub-integration")
     ap.add_argument("-K", dest="interchan", action="store_true", help="remove the inter-channel dispersion delay")
-    ap.add_argument("-d", dest="ndim", type=int, default=4, choices=[1, 2, 4], help="detected layout (ndim)")
+    ap.add_argument("-d", dest="ndim", type=int, default=4, choices=[1, 2, 4], help="detected layout (ndim); with -cyclic: output polarisations")
+    ap.add_argument("-cyclic", dest="cyclic", type=int, default=0, help="form cyclic spectra with N channels per filterbank channel")
+    ap.add_argument("-cyclicoversample", dest="cyclic_mover", type=int, default=1, help="use M times as many lags to improve the cyclic channel isolation")
     ap.add_argument("-r", dest="record", action="store_true", help="report the time spent in each operation")
     ap.add_argument("--dump", action="append", default=[], help="dump the input of this operation (Detection, Fold)")
     ap.add_argument("-O", dest="prefix", default="dspsr_amd", help="output file name prefix")
@@ -79,7 +83,8 @@ def main(argv=None):
     pfold = period if period > 0 else 1.0 / polyco.frequency(info.mjd_day, info.mjd_sec) if polyco else 0.0
     nbin = a.nbin or (pipeline.choose_nbin(pfold, out_rate) if pfold else targets[0].nbin)
     cfg = pipeline.Config(nchan=nchan, dispersion_measure=dm, nbin=nbin, folding_period=period, freq_res=a.nfft,
-                          subint_seconds=a.subint, subint_turns=1.0 if a.single else a.turns, ndim=a.ndim,
+                          subint_seconds=a.subint, subint_turns=1.0 if a.single else a.turns, ndim=1 if a.cyclic else a.ndim,
+                          cyclic_nchan=a.cyclic, cyclic_mover=a.cyclic_mover, cyclic_npol=(a.ndim if info.npol == 2 else 1) if a.cyclic else 0,
                           interchan_dedispersion=a.interchan, record_time=a.record,
                           convolve_when="never" if when == "after" and dm == 0.0 else when)
     torch.cuda.set_device(a.device)
@@ -92,11 +97,15 @@ def main(argv=None):
         outputs = [("%s_%d_%%04d.ps" % (a.prefix, k), p.subints,
                     p.target.folding_period or 1.0 / p.target.polyco.frequency(info.mjd_day, info.mjd_sec))
                    for k, p in enumerate(lt.pulsars)]
+    cyc = {}
+    if a.cyclic:                                            # nchan * nchan_spec / mover channels, ndim 1 (CyclicFold.C:96-119)
+        g = pipeline.cyclic_geometry(cfg, info)
+        cyc = {"nchan": g["nchan"], "state": g["state"]}
     for pattern, subints, pf in outputs:
         for n, sub in enumerate(subints):
             path = pattern % n
             pipeline.write_phase_series(path, sub, info, cfg, npol=lt.npol_out, scale=lt.scalefac, division=n,
-                                        start_seconds=lt.out_start, folding_period=pf)
+                                        start_seconds=lt.out_start, folding_period=pf, **cyc)
             print("dspsr_amd: %s  integration %.6f s  %d samples" % (path, sub["integration_length"], sub["ndat_total"]))
     if a.record:
         lt.report()

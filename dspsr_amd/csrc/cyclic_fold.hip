@@ -183,6 +183,7 @@ struct dspsr_amd_cyclic_fold {
   float* lagdata = nullptr;       // their sum (== parts when nparts == 1)
   bool dirty = false;             // parts changed since the last combine
   uint64_t ndat_fold = 0, idat_start = 0;
+  bool block_set = false;         // set_ndat came after the last change of shape: plan[] and ndat_fold belong to this shape
   std::vector<uint32_t> plan[2];  // per-sample plans of the current call (CyclicFold.C:293-301)
   std::vector<uint32_t> host;     // run lists as uploaded
   uint32_t* dev = nullptr;
@@ -238,6 +239,15 @@ extern "C" int dspsr_amd_cyclic_fold_set_shape(dspsr_amd_cyclic_fold* f, uint32_
   const uint64_t cap = CY_PART_BYTES / (need * sizeof(float));
   if (nparts > cap) nparts = (uint32_t)cap;
   if (nparts < 1) nparts = 1;
+  const bool changed = nchan != f->nchan || npol_in != f->npol_in || npol_out != f->npol_out || nlag != f->nlag ||
+                       mover != f->mover || nbin != f->nbin;
+  if (changed) {
+    // the plan of the previous shape holds bins of ITS nbin over ITS block: a fold must not launch with it
+    f->plan[0].clear();
+    f->plan[1].clear();
+    f->ndat_fold = 0;
+    f->block_set = false;
+  }
   if (need != f->lag_floats || nparts != f->nparts) {
     cyclic_release(f);
     if (hipMalloc((void**)&f->parts, need * nparts * sizeof(float)) != hipSuccess) {
@@ -255,8 +265,7 @@ extern "C" int dspsr_amd_cyclic_fold_set_shape(dspsr_amd_cyclic_fold* f, uint32_
     (void)hipMemsetAsync(f->parts, 0, need * nparts * sizeof(float), f->ctx->stream);
     if (f->lagdata != f->parts) (void)hipMemsetAsync(f->lagdata, 0, need * sizeof(float), f->ctx->stream);
     f->dirty = false;
-  } else if (nchan != f->nchan || npol_in != f->npol_in || npol_out != f->npol_out || nlag != f->nlag || mover != f->mover ||
-             nbin != f->nbin) {
+  } else if (changed) {
     // same size, another meaning (nbin and nchan exchanged, say): a new shape starts from zero like a new allocation
     const int rc = dspsr_amd_cyclic_fold_zero(f);
     if (rc != DSPSR_AMD_OK) return rc;
@@ -274,6 +283,7 @@ extern "C" int dspsr_amd_cyclic_fold_set_ndat(dspsr_amd_cyclic_fold* f, uint64_t
   f->plan[1].assign(ndat, 0);
   f->ndat_fold = ndat;
   f->idat_start = idat_start;
+  f->block_set = true;
   return DSPSR_AMD_OK;
 }
 
@@ -317,6 +327,9 @@ extern "C" int dspsr_amd_cyclic_fold_fold(dspsr_amd_cyclic_fold* f, const float*
   if (!f) return DSPSR_AMD_EINVAL;
   const char* who = "dspsr_amd_cyclic_fold_fold";
   if (!f->parts) return ctx_fail(f->ctx, DSPSR_AMD_ESTATE, "%s: no shape", who);
+  if (!f->block_set)
+    return ctx_fail(f->ctx, DSPSR_AMD_ESTATE, "%s: no block: dspsr_amd_cyclic_fold_set_ndat must follow a set_shape that changes the shape",
+                    who);
   if (f->ndat_fold <= f->nlag) return DSPSR_AMD_OK;        // CyclicFold.C:358-367: a short block is ignored
   if (!in_dev) return ctx_fail(f->ctx, DSPSR_AMD_EINVAL, "%s: null input", who);
   const uint64_t row = 2 * (f->idat_start + f->ndat_fold);

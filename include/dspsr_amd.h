@@ -395,7 +395,11 @@ int dspsr_amd_fold_synch(dspsr_amd_fold* fold, float* profile_host);            
  * set_shape allocates the device lag array, nbin * npol_out * nchan * nlag * 2 floats, zeroed (and, for shapes with few
  * (channel, lag) owners, up to 64 partial arrays of that size within 2 GiB): DSPSR_AMD_ENOMEM if it does not fit.  nlag in
  * [2, 65536], nchan <= 65535, ndat < 2^31 per call; anything else DSPSR_AMD_EINVAL before a launch.
- * Call order per Fold::fold (Fold.C:724-829): set_ndat, set_bin x ndat (or set_bins), fold. */
+ * Call order per Fold::fold (Fold.C:724-829): set_ndat, set_bin x ndat (or set_bins), fold.
+ * A set_shape that changes any of nchan, npol_in, npol_out, nlag, mover, nbin starts from zero AND drops the block and its plan
+ * (they hold bins of the old nbin): set_ndat must follow it before set_bin, set_bins or fold -- until then fold returns
+ * DSPSR_AMD_ESTATE, launches nothing and leaves the lag data as they are.  set_shape with the values it already has keeps the
+ * sums, the block and the plan. */
 int dspsr_amd_cyclic_fold_create(dspsr_amd_ctx* ctx, dspsr_amd_cyclic_fold** fold);
 void dspsr_amd_cyclic_fold_destroy(dspsr_amd_cyclic_fold* fold);
 int dspsr_amd_cyclic_fold_set_shape(dspsr_amd_cyclic_fold* fold, uint32_t nchan, uint32_t npol_in, uint32_t npol_out,

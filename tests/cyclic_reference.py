@@ -36,11 +36,52 @@ PAIRS = {(1, 1): [(0, 0, 0)], (2, 1): [(0, 0, 0), (0, 1, 1)], (2, 2): [(0, 0, 0)
          (2, 4): [(0, 0, 0), (1, 1, 1), (2, 0, 1), (3, 1, 0)]}          # (output pol, x pol, y pol)
 
 
-def fold(rows, plan0, plan1, nlag, npol_out, nbin, lags=None, dtype=np.float64):
-    """One fold call on the ndat_fold = rows.shape[2] samples of `rows`; returns the lag array (a new one, `lags` + this call)."""
-    nchan, npol_in, ndat = rows.shape
+def _begin(rows, nlag, npol_out, nbin, lags, dtype):
+    nchan, _npol_in, _ndat = rows.shape
     cdt = np.complex128 if dtype == np.float64 else np.complex64
     out = np.zeros((nbin, npol_out, nchan, nlag), cdt) if lags is None else lags.astype(cdt).copy()
+    return cdt, out
+
+
+def fold(rows, plan0, plan1, nlag, npol_out, nbin, lags=None, dtype=np.float64):
+    """One fold call on the ndat_fold = rows.shape[2] samples of `rows`; returns the lag array (a new one, `lags` + this call).
+
+    The sums of fold_by_sample, bit for bit, in a loop that numpy runs on slices: over u = idat + ilag / 2, where all lags of one
+    parity share a bin.  An accumulator (bin, pol, chan, ilag) still receives its terms one at a time in rising idat (u rises
+    with idat at a fixed lag) and every term is formed by the same rounded operations, so the association is unchanged;
+    tests/test_cyclic_cases_host.py holds the two against each other."""
+    nchan, npol_in, ndat = rows.shape
+    cdt, out = _begin(rows, nlag, npol_out, nbin, lags, dtype)
+    if ndat <= nlag:
+        return out
+    # channel innermost ([bin][pol][lag][chan] and [pol][sample][chan]): the slices below are then rows of whole channels
+    re, im = (np.ascontiguousarray(a.transpose(0, 1, 3, 2)) for a in (out.real, out.imag))
+    xr, xi = (np.ascontiguousarray(a.astype(dtype).transpose(1, 2, 0)) for a in (rows.real, rows.imag))
+    pl = (np.asarray(plan0), np.asarray(plan1))
+    nvalid = ndat - nlag
+    for u in range(nvalid + (nlag - 1) // 2):
+        for par in (0, 1):
+            # lags 2 h + par with idat = u - h in [0, nvalid): h in [h0, h1)
+            h0, h1 = max(0, u - nvalid + 1), min((nlag - par + 1) // 2, u + 1)
+            if h0 >= h1:
+                continue
+            b = pl[par][u]
+            ix = slice(u - h0, u - h1 if u - h1 >= 0 else None, -1)          # x[u - h]
+            iy = slice(u + h0 + par, u + h1 + par)                            # y[u + h + par]
+            il = slice(2 * h0 + par, 2 * h1 + par, 2)
+            for q, px, py in PAIRS[(npol_in, npol_out)]:
+                ar, ai = xr[px, ix], xi[px, ix]
+                br, bi = xr[py, iy], xi[py, iy]
+                re[b, q, il] = re[b, q, il] + (ar * br + ai * bi)
+                im[b, q, il] = im[b, q, il] + (ai * br - ar * bi)
+    return (re + 1j * im).astype(cdt).transpose(0, 1, 3, 2).copy()
+
+
+def fold_by_sample(rows, plan0, plan1, nlag, npol_out, nbin, lags=None, dtype=np.float64):
+    """fold() as the CPU engine's loop is written: sample by sample, every lag of the sample at once.  Slow (an indexed update
+    of the whole [chan][lag] plane per sample); kept as the statement that fold() is held against."""
+    nchan, npol_in, ndat = rows.shape
+    cdt, out = _begin(rows, nlag, npol_out, nbin, lags, dtype)
     if ndat <= nlag:
         return out
     re, im = out.real.copy(), out.imag.copy()

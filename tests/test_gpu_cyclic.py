@@ -3,6 +3,7 @@ exact data bit for bit, noise data within twice the error of the reference's own
 import numpy as np
 import pytest
 
+import cyclic_cases as cc
 import cyclic_reference as cr
 import dspsr_amd
 from device_buffers import SENTINEL, OutputLayout, sentinel_rows
@@ -159,4 +160,135 @@ def test_a_new_shape_of_the_same_size_starts_from_zero(ctx):
     assert eng.synch_lags().any()
     eng.set_shape(4, 2, 2, 33, 1, 2)                        # nbin and nchan exchanged: the same size, another meaning
     assert not eng.synch_lags().any()
+    eng.close()
+
+
+# ---- where a segment walks several tiles (tests/cyclic_cases.py; tests/test_cyclic_cases_host.py proves what each case reaches) ----
+def _first_difference(case, ndat, got, ref):
+    """the first wrong lag value as the kernel sees it: owner lane and the steps of u it covers"""
+    bad = np.argwhere(got != ref)
+    b, q, chan, ilag = (int(v) for v in bad[0])
+    p = cc.partition(case["nchan"], case["npol_out"], case["nlag"], case["nbin"], ndat)
+    return "%d of %d lag values differ, first at bin %d pol %d chan %d lag %d (parity %d, workgroup x %d; %d tiles, %d per segment, %d " \
+           "parts): got %s, reference %s" % (len(bad), ref.size, b, q, chan, ilag, ilag % 2, ilag // (2 * cc.CY_HL), p.ntile, p.tps,
+                                             p.nparts, got[b, q, chan, ilag], ref[b, q, chan, ilag])
+
+
+@pytest.mark.parametrize("name", cc.NAMES)
+def test_table_rows_bit_for_bit(ctx, name):
+    case, index = cc.by_name(name), cc.NAMES.index(name)
+    cr.check_exact(case)
+    nbin = case["nbin"]
+    eng = dspsr_amd.CyclicFoldEngine(ctx)
+    eng.set_shape(case["nchan"], case["npol_in"], case["npol_out"], case["nlag"], 1, nbin)
+    for k, ((ndat, start, phi, pps, zero), (rhits, ref)) in enumerate(zip(case["calls"], cc.reference(name))):
+        buf, before, view = _place(cc.case_rows(name, k), offset=2 * (k + 1) + 2 * index, row_pad=2 * (3 + k))
+        if zero:
+            eng.zero()
+        hits = np.zeros(nbin, np.uint32)
+        eng.set_ndat(ndat, start)
+        if case["placed"][k] is not None:                   # both plans given sample by sample: plan1 = (ibin + k) % nbin
+            p0, p1 = case["placed"][k]
+            for i in range(ndat):
+                eng.set_bin(start + i, float(p0[i]), 2.0 * float((p1[i] - p0[i]) % nbin))
+                hits[p0[i]] += 1
+        elif k % 2:                                         # the per-sample form of the plan, as Fold::fold drives it
+            phase, dn = float(phi), float(nbin)
+            for i in range(ndat):
+                phase -= np.floor(phase)
+                eng.set_bin(start + i, phase * dn, pps * dn)
+                hits[int(phase * dn)] += 1
+                phase += pps
+        else:
+            assert eng.set_bins(phi, pps, ndat, start, hits) == ndat
+        eng.fold(view)
+        got = _lags(eng).astype(np.complex64)
+        assert np.array_equal(hits, rhits), "hits of call %d" % k
+        assert _same_bits(got, ref), "call %d: %s" % (k, _first_difference(case, ndat, got, ref))
+        assert bool((buf == before).all()), "call %d wrote into the input buffer" % k
+        assert int((buf == SENTINEL).sum()) > 0
+        del buf, before, view
+    eng.close()
+
+
+def test_a_new_shape_refuses_the_plan_of_the_old_one(ctx):
+    """set_shape(nbin 64), set_ndat, set_bins, set_shape(nbin 8), fold: the plan holds bins up to 63 and belongs to the old
+    shape.  The fold is refused before anything is launched; set_ndat makes the engine usable again."""
+    ndat, pps = 700, 1.0 / 3.0
+    rows = cr.exact_rows(21, 2, 2, ndat)
+    _, _, view = _place(rows, offset=4, row_pad=2)
+    eng = dspsr_amd.CyclicFoldEngine(ctx)
+    eng.set_shape(2, 2, 2, 33, 1, 64)
+    eng.set_ndat(ndat, 0)
+    eng.set_bins(0.2, pps / 64, ndat, 0)
+    assert cr.plans(0.2, pps / 64, 64, ndat)[0].max() == 63
+    eng.set_shape(2, 2, 2, 33, 1, 8)
+    with pytest.raises(dspsr_amd.DspsrAmdError, match=r"\(-4\).*set_ndat"):        # DSPSR_AMD_ESTATE
+        eng.fold(view)
+    assert not eng.synch_lags().any()
+    with pytest.raises(dspsr_amd.DspsrAmdError):                                    # no block: no sample to plan either
+        eng.set_bins(0.2, pps / 8, ndat, 0)
+    with pytest.raises(dspsr_amd.DspsrAmdError):
+        eng.set_bin(0, 0.0, 0.0)
+    with pytest.raises(dspsr_amd.DspsrAmdError, match="set_ndat"):
+        eng.fold(view)
+    assert not eng.synch_lags().any()
+    p0, p1, rhits = cr.plans(0.2, pps / 8, 8, ndat)
+    ref = cr.fold(rows, p0, p1, 33, 2, 8, dtype=np.float32)
+    hits = np.zeros(8, np.uint32)
+    eng.set_ndat(ndat, 0)
+    eng.set_bins(0.2, pps / 8, ndat, 0, hits)
+    eng.fold(view)
+    assert np.array_equal(hits, rhits) and _same_bits(_lags(eng).astype(np.complex64), ref)
+    eng.set_shape(2, 2, 2, 33, 1, 8)                        # the same shape again keeps the plan, as it keeps the sums
+    eng.fold(view)
+    assert _same_bits(_lags(eng).astype(np.complex64), cr.fold(rows, p0, p1, 33, 2, 8, ref, np.float32))
+    eng.close()
+
+
+MANY_TILES = dict(npol_in=2, npol_out=4, nlag=129, nbin=64, nchan=64, ndat=6000, pps=1.0 / 64 / 11.3)
+
+
+def test_noise_rows_with_several_tiles_per_segment(ctx):
+    """the rule of test_noise_rows_within_twice_the_reference_association, unchanged, where 8 parts walk 12 tiles in pairs: a
+    run's float32 sum is then cut at the segment's ends only, and the combine adds six partial sums that all count"""
+    c = MANY_TILES
+    assert cc.partition(c["nchan"], c["npol_out"], c["nlag"], c["nbin"], c["ndat"]) == (8, 12, 8, 2, 2)
+    test_noise_rows_within_twice_the_reference_association(ctx, c)
+
+
+def test_same_pieces_same_bits_with_several_partial_sums(ctx):
+    """test_same_pieces_same_bits_whatever_comes_between at the shape of "multi-tile": four parts of 3, 3, 3 and 1 tiles, runs of
+    1300 samples -- a bin's sum is in several partial arrays, and the extra combine between the pieces must not change what the
+    second piece adds to"""
+    c = cc.by_name("multi-tile")
+    ndat, pps = 4700, c["calls"][1][3]
+    assert cc.partition(c["nchan"], c["npol_out"], c["nlag"], c["nbin"], ndat) == (4, 10, 4, 3, 0)
+    rows = cr.noise_rows(78, c["nchan"], c["npol_in"], 2 * ndat, 30.0)
+    _, _, view = _place(rows, offset=2, row_pad=4)
+    res = []
+    for variant in range(2):
+        eng = dspsr_amd.CyclicFoldEngine(ctx)
+        eng.set_shape(c["nchan"], c["npol_in"], c["npol_out"], c["nlag"], 1, c["nbin"])
+        for piece in range(2):
+            start = piece * ndat
+            eng.set_ndat(ndat, start)
+            eng.set_bins(0.1 + 0.2 * piece, pps, ndat, start)
+            eng.fold(view)
+            if variant:
+                eng.synch_lags()
+        res.append(eng.synch_lags())
+        eng.close()
+    assert res[0].any() and _same_bits(res[0], res[1])
+
+
+def test_one_lag_more_than_the_largest_is_refused(ctx):
+    """the case "max-nlag" shows CY_MAX_NLAG lags accepted and right; one more is refused, and the engine stays usable"""
+    eng = dspsr_amd.CyclicFoldEngine(ctx)
+    with pytest.raises(dspsr_amd.DspsrAmdError, match="nlag=%d" % (cc.CY_MAX_NLAG + 1)):
+        eng.set_shape(1, 1, 1, cc.CY_MAX_NLAG + 1, 1, 8)
+    with pytest.raises(dspsr_amd.DspsrAmdError, match="nchan=%d" % (cc.MAX_NCHAN + 1)):
+        eng.set_shape(cc.MAX_NCHAN + 1, 1, 1, 2, 1, 2)
+    eng.set_shape(1, 1, 1, cc.CY_MAX_NLAG, 1, 8)
+    assert eng.synch_lags().shape == (8, 1, 1, cc.CY_MAX_NLAG, 2) and not eng.synch_lags().any()
     eng.close()

@@ -114,6 +114,8 @@ SYMBOLS = {
     "dspsr_amd_fold_get_ndat_folded": (_u64, [_vp]),
     "dspsr_amd_fold_zero": (_i, [_vp]),
     "dspsr_amd_fold_synch": (_i, [_vp, _vp]),
+    "dspsr_amd_fourth_moment": (_i, [_vp, _vp, _u64, _vp, _u64, _u32, _u64]),
+    "dspsr_amd_fold_fold_moments": (_i, [_vp, _vp, _u64]),
     "dspsr_amd_cyclic_fold_create": (_i, [_vp, _pp]),
     "dspsr_amd_cyclic_fold_destroy": (None, [_vp]),
     "dspsr_amd_cyclic_fold_set_shape": (_i, [_vp, _u32, _u32, _u32, _u32, _u32, _u32]),

@@ -716,8 +716,11 @@ extern "C" void dspsr_amd_fold_destroy(dspsr_amd_fold* f)
 
 static int fold_check_shape(dspsr_amd_fold* f, const char* who, uint32_t nchan, uint32_t npol, uint32_t ndim, uint32_t nbin)
 {
-  if (ndim != 1 && ndim != 2 && ndim != 4)
-    return ctx_fail(f->ctx, DSPSR_AMD_EINVAL, "%s: ndim=%u not in {1,2,4}", who, ndim);
+  // ndim 14: the fourth moments of the Stokes parameters (FourthMoment.C:39-42: always one polarisation), fold_moments.hip
+  if (ndim == 14 && npol != 1)
+    return ctx_fail(f->ctx, DSPSR_AMD_EINVAL, "%s: ndim=14 (fourth moments) goes with npol=1, not npol=%u", who, npol);
+  if (ndim != 1 && ndim != 2 && ndim != 4 && ndim != 14)
+    return ctx_fail(f->ctx, DSPSR_AMD_EINVAL, "%s: ndim=%u not in {1,2,4} or 14 with npol 1", who, ndim);
   if (!nchan || !npol || !nbin) return ctx_fail(f->ctx, DSPSR_AMD_EINVAL, "%s: zero dimension", who);
   return DSPSR_AMD_OK;
 }
@@ -1032,12 +1035,45 @@ static bool plan_dense_fill(dspsr_amd_fold* f, PlanSlot& sl, uint64_t first, siz
   return true;
 }
 
+// The pending plan closed, bucketed by phase bin and on its way to the device in the next slot: what a walk kernel of another
+// translation unit (fold_moments.hip) reads.  The caller launches, then calls fold_part_plan_submitted.  The plan is consumed.
+int fold_plan_to_device(dspsr_amd_fold* f, const char* who, PlanSlot** slot, uint64_t* first, uint64_t* last, uint32_t* max_run)
+{
+  dspsr_amd_ctx* ctx = f->ctx;
+  if (f->current_hits) f->binplan.back().hits = f->current_hits;   // FoldCUDA.cu:163-164
+  f->current_hits = 0;
+  f->current_bin = f->folding_nbin;   // the plan is used up: the next one opens a fresh run (as after set_nbin)
+  PlanSlot& sl = f->slot[f->next_slot];
+  f->next_slot ^= 1;
+  if (sl.pending) {            // the fold that last used this slot (two calls ago) must have consumed it
+    const hipError_t e = hipEventSynchronize(sl.done);
+    if (e != hipSuccess) return ctx_fail(ctx, DSPSR_AMD_EHIP, "%s: %s", who, hipGetErrorString(e));
+    sl.pending = false;
+  }
+  if (!slot_reserve(sl, (size_t)f->nbin + 1, f->binplan.size())) return ctx_fail(ctx, DSPSR_AMD_ENOMEM, "%s: plan allocation failed", who);
+  *first = f->binplan.front().offset;
+  *last = f->binplan.back().offset + f->binplan.back().hits;
+  *first -= *first % 4;                                // keeps 16-byte alignment of the chunk loads for any ndim
+  *max_run = fold_plan_max_run(f);
+  plan_bucket(f, sl);
+  const PlanCopy pc[2] = {{sl.d_bin_start, sl.h_bin_start, ((size_t)f->nbin + 1) * sizeof(uint32_t)},
+                          {sl.d_iv, sl.h_iv, f->binplan.size() * sizeof(Interval)}};
+  const hipError_t e = plan_upload(f, sl, pc, 2);
+  if (e != hipSuccess) return ctx_fail(ctx, DSPSR_AMD_EHIP, "%s: plan copy: %s", who, hipGetErrorString(e));
+  if (fold_plan_wait(f, &sl) != DSPSR_AMD_OK) return DSPSR_AMD_EHIP;
+  f->binplan.clear();
+  *slot = &sl;
+  return DSPSR_AMD_OK;
+}
+
 static int fold_fold_impl(dspsr_amd_fold* f, const float* in_dev, uint64_t in_chan_stride, uint64_t in_pol_stride,
                           uint32_t* hits_dev);
 
 extern "C" int dspsr_amd_fold_fold(dspsr_amd_fold* f, const float* in_dev, uint64_t in_chan_stride,
                                    uint64_t in_pol_stride)
 {
+  // a 14-shape folds ndim 14 rows, the output of a FourthMoment operation (fold_moments.hip, stream loader)
+  if (f && f->ndim == 14) return fold_moments_run(f, in_dev, in_chan_stride, false, "dspsr_amd_fold_fold");
   return fold_fold_impl(f, in_dev, in_chan_stride, in_pol_stride, nullptr);
 }
 
@@ -1045,6 +1081,8 @@ extern "C" int dspsr_amd_fold_fold_zeroed(dspsr_amd_fold* f, const float* in_dev
                                           uint64_t in_pol_stride, uint32_t* hits_dev)
 {
   if (!hits_dev) return DSPSR_AMD_EINVAL;
+  if (f && f->ndim == 14)
+    return ctx_fail(f->ctx, DSPSR_AMD_EINVAL, "dspsr_amd_fold_fold_zeroed: not built for fourth moments (npol 1 x ndim 14)");
   return fold_fold_impl(f, in_dev, in_chan_stride, in_pol_stride, hits_dev);
 }
 
@@ -1288,6 +1326,8 @@ extern "C" int dspsr_amd_fold_fold_many(dspsr_amd_fold* const* folds, uint32_t n
     for (uint32_t j = 0; j < i; j++)
       if (folds[j] == f) return ctx_fail(f->ctx, DSPSR_AMD_EINVAL, "dspsr_amd_fold_fold_many: fold %u given twice", i);
     if (f->ctx != folds[0]->ctx) return ctx_fail(f->ctx, DSPSR_AMD_EINVAL, "dspsr_amd_fold_fold_many: fold %u of another context", i);
+    if (f->ndim == 14)
+      return ctx_fail(f->ctx, DSPSR_AMD_EINVAL, "dspsr_amd_fold_fold_many: fold %u folds fourth moments (npol 1 x ndim 14): not built for a shared launch", i);
     if (f->nchan != folds[0]->nchan || f->npol != folds[0]->npol || f->ndim != folds[0]->ndim)
       return ctx_fail(f->ctx, DSPSR_AMD_EINVAL, "dspsr_amd_fold_fold_many: fold %u has another nchan / npol / ndim", i);
     if (!f->profile) return ctx_fail(f->ctx, DSPSR_AMD_ESTATE, "dspsr_amd_fold_fold_many: fold %u: set_shape not called", i);

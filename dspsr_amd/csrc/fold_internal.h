@@ -91,3 +91,10 @@ int fold_segment_combine(dspsr_amd_fold* f, const float* msum, uint32_t chan0, u
                          uint32_t nfilt_pos, int logTt, int logMa, int logMb, const uint32_t* d_bin_start, const dspsr_amd::Interval* d_iv);
 // profile += sum of `nseg` partial profiles (packed [seg][chan][npol][nbin][ndim]) in order: segmented fused launches
 int fold_combine_partials(dspsr_amd_fold* f, const float* part, uint32_t nseg, uint32_t chan0, uint32_t nchan);
+
+// Fourth moments (fold_moments.hip).  fold_plan_to_device: the pending plan closed, bucketed by phase bin (bin_start / iv of
+// *slot, as for k_fold_chunked) and uploaded; [*first, *last) its sample span with *first rounded down to a multiple of 4,
+// *max_run its longest run.  The plan is consumed; fold_part_plan_submitted follows the kernels that read it.
+int fold_plan_to_device(dspsr_amd_fold* f, const char* who, PlanSlot** slot, uint64_t* first, uint64_t* last, uint32_t* max_run);
+// Fold::Engine::fold of a profile of npol 1 x ndim 14 from ndim 4 Stokes rows (stokes) or ndim 14 rows
+int fold_moments_run(dspsr_amd_fold* f, const float* in_dev, uint64_t in_chan_stride, bool stokes, const char* who);

@@ -579,6 +579,17 @@ class DetectionEngine:
                                                inp.shape[2] // 2), "dspsr_amd_detect_square_law")
 
 
+def fourth_moment(ctx: Context, inp, out, ndat=None):
+    """dsp::FourthMoment::transformation (FourthMoment.C:29-77): inp float32 [nchan][1][>= ndat*4] Stokes rows, out float32
+    [nchan][1][>= ndat*14]; ndat defaults to the samples inp holds.  Out of place."""
+    ics, _ = _strides3(inp)
+    ocs, _ = _strides3(out)
+    if ndat is None:
+        ndat = inp.shape[2] // 4
+    _check(ctx.handle, lib.dspsr_amd_fourth_moment(ctx.handle, inp.data_ptr(), ics, out.data_ptr(), ocs, inp.shape[0], ndat),
+           "dspsr_amd_fourth_moment")
+
+
 class FoldEngine:
     """dsp::Fold::Engine; owns the device-resident profiles (get_profiles)."""
 
@@ -640,6 +651,13 @@ class FoldEngine:
     def fold(self, inp):
         cs, ps = _strides3(inp)
         _check(self.ctx.handle, lib.dspsr_amd_fold_fold(self.handle, inp.data_ptr(), cs, ps), "dspsr_amd_fold_fold")
+
+    def fold_moments(self, stokes):
+        """fold() of a shape (nchan, 1, 14, nbin) from the ndim 4 Stokes rows themselves, float32 [nchan][1][>= ndat*4]: the ten
+        products of dsp::FourthMoment are formed in registers (dspsr_amd_fold_fold_moments).  Bit-identical to fold() of the
+        rows fourth_moment() writes."""
+        cs, _ps = _strides3(stokes)
+        _check(self.ctx.handle, lib.dspsr_amd_fold_fold_moments(self.handle, stokes.data_ptr(), cs), "dspsr_amd_fold_fold_moments")
 
     @staticmethod
     def fold_many(folds, inp) -> int:

@@ -82,7 +82,9 @@ namespace HIP
     out->set_npol (f.npol);
     out->set_ndim (f.ndim);
     out->set_state (state == "Stokes" ? Signal::Stokes : state == "Coherence" ? Signal::Coherence :
-                    state == "PPQQ" ? Signal::PPQQ : Signal::Intensity);
+                    state == "PPQQ" ? Signal::PPQQ :
+                    // `-4`: npol 1 x ndim 14, what dsp::FourthMoment leaves and Archiver.C:382-405 takes for fourth moments
+                    state == "FourthMoment" ? Signal::FourthMoment : Signal::Intensity);
     out->set_dispersion_measure (f.number ("DM"));
     out->set_scale (f.number ("SCALE"));             // Archiver.C:842: amps = sum / (scale * hits)
     const double sec = f.number ("MJD_SEC") + f.number ("OBS_OFFSET_SECONDS");

@@ -19,7 +19,7 @@ from dataclasses import dataclass
 import numpy as np
 
 from . import _lib
-from .engine import (Context, ConvolutionEngine, CyclicFoldEngine, Dedispersion, DspsrAmdError, FilterbankEngine, FoldEngine, Rescale, SampleDelay, add_fpt, copy_data_fpt,
+from .engine import (Context, ConvolutionEngine, CyclicFoldEngine, Dedispersion, DspsrAmdError, FilterbankEngine, FoldEngine, Rescale, SampleDelay, add_fpt, copy_data_fpt, fourth_moment,
                      dedispersion_sample_delays, detect_raw, eight_bit_scale, fscrunch_fpt, pscrunch_tfp, sigproc_digitize, sigproc_digitize_fpt,
                      tfp_filterbank, tscrunch_fpt)
 
@@ -71,6 +71,12 @@ class Config:
     cyclic_mover: int = 1                  # -cyclicoversample M: nlag = M * N / 2 + 1 (dsp/CyclicFold.h:66)
     cyclic_npol: int = 0                   # output polarisations of the cyclic fold (the reference passes config->npol): 1, 2 or 4;
                                            # 0 = 4 (Coherence) for two input polarisations, 1 for one
+    fourth_moment: bool = False            # -4: fold the Stokes parameters and their ten pairwise products (dsp::FourthMoment,
+                                           # LoadToFold1.C:557-568): detection forced to Stokes with ndim 4 (:1119-1123), the fold has
+                                           # shape (nchan, 1, 14, nbin), the fused fold is off
+    npol: int = 4                          # -d: the reference's config->npol.  This path detects the four products (4); the field
+                                           # decides the branch of LoadToFold1.C:552-568 only: with 1 or 3 it wins over -4, which is
+                                           # then ignored
 
 
 @dataclass
@@ -405,6 +411,30 @@ class TurnsDivider:
         return out
 
 
+MOMENT_PAIRS = tuple((i, j) for i in range(4) for j in range(i, 4))    # FourthMoment.C:67-72 = Archiver.C:747-767
+
+
+def moments_to_central(profile, hits, scale):
+    """The Archiver's treatment of folded fourth moments (Archiver.C:679-713,738-771).  profile: [nchan][1][nbin][14] sums,
+    hits: [nbin].  The four Stokes sums are divided by scale * hits, the ten product sums by scale^2 * hits ("FourthMoments
+    start with Stokes squared", :684), both kept as float32 amps as there; then raw_to_central, in double:
+    (moment - mean_i * mean_j) / hits, the covariance of the mean.  Returns (means float32 [nchan][4][nbin], central float32
+    [nchan][10][nbin]), the ten in the order MOMENT_PAIRS.  Bins without hits: means as normalise_profile (the mean of the
+    others), central moments 0 (the reference divides by hits = 0 there)."""
+    prof = np.asarray(profile, dtype=np.float64)
+    if prof.ndim != 4 or prof.shape[1] != 1 or prof.shape[3] != 14:
+        raise DspsrAmdError("moments_to_central: profile of shape %r is not [nchan][1][nbin][14]" % (prof.shape,))
+    hits = np.asarray(hits, dtype=np.float64)
+    ok = hits > 0
+    means = normalise_profile(prof[..., :4], hits, scale)[:, 0].transpose(0, 2, 1)             # float32 [nchan][4][nbin]
+    raw = normalise_profile(prof[..., 4:], hits, float(scale) * float(scale))[:, 0].transpose(0, 2, 1)
+    central = np.zeros(raw.shape, dtype=np.float32)
+    for k, (i, j) in enumerate(MOMENT_PAIRS):
+        pi, pj = means[:, i, ok].astype(np.float64), means[:, j, ok].astype(np.float64)
+        central[:, k, ok] = ((raw[:, k, ok].astype(np.float64) - pi * pj) / hits[ok]).astype(np.float32)
+    return means, central
+
+
 def normalise_profile(profile, hits, scale):
     """dsp::Archiver::set (Archiver.C:773-893): amps = sum / (scale * hits); bins without hits take the mean
     of the others.  profile: [nchan][npol][nbin][ndim] sums, hits: [nbin]."""
@@ -439,17 +469,21 @@ PHASE_SERIES_HDR_SIZE = 4096
 
 
 def write_phase_series(path, sub, info: "InputInfo", cfg: "Config", *, nchan=None, npol=1, scale=1.0, division=0,
-                       start_seconds=0.0, folding_period=0.0, reference_phase=0.0, state=None):
-    """sub: a dict as LoadToFold.subints holds (hits, integration_length, ndat_total, profile or profile_dev)."""
+                       start_seconds=0.0, folding_period=0.0, reference_phase=0.0, state=None, ndim=None):
+    """sub: a dict as LoadToFold.subints holds (hits, integration_length, ndat_total, profile or profile_dev).  A -4 run
+    (fourth_moment_active(cfg)) writes STATE FourthMoment, NPOL 1, NDIM 14 whatever npol / state say."""
     prof = sub.get("profile")
     if prof is None:
         prof = sub["profile_dev"].cpu().numpy()
     nchan = nchan or cfg.nchan
     nbin = len(sub["hits"])
-    prof = np.ascontiguousarray(np.asarray(prof, dtype="<f4").reshape(nchan, npol, nbin, cfg.ndim))
+    ndim = ndim or cfg.ndim
+    if fourth_moment_active(cfg) and not cfg.cyclic_nchan:
+        npol, ndim, state = 1, 14, "FourthMoment"
+    prof = np.ascontiguousarray(np.asarray(prof, dtype="<f4").reshape(nchan, npol, nbin, ndim))
     keys = [("HDR_MAGIC", PHASE_SERIES_MAGIC), ("HDR_VERSION", "1.0"), ("HDR_SIZE", PHASE_SERIES_HDR_SIZE),
             ("FREQ", repr(float(info.centre_frequency))), ("BW", repr(float(info.bandwidth))), ("NCHAN", nchan),
-            ("NPOL", npol), ("NDIM", cfg.ndim), ("NBIN", nbin),
+            ("NPOL", npol), ("NDIM", ndim), ("NBIN", nbin),
             ("STATE", state or ("Stokes" if cfg.stokes else "Coherence")),
             ("DM", repr(float(cfg.dispersion_measure))), ("SCALE", repr(float(scale))),
             ("MJD_DAY", info.mjd_day), ("MJD_SEC", repr(float(info.mjd_sec))),
@@ -839,6 +873,27 @@ def cyclic_check(cfg: "Config", info: "InputInfo", ntargets=0, subband=None, dum
     return cyclic_geometry(cfg, info)
 
 
+def fourth_moment_active(cfg: "Config") -> bool:
+    """The branch order of LoadToFold1.C:552-568: npol 1 or 3 takes the first branch, -4 only the second."""
+    return bool(cfg.fourth_moment) and cfg.npol not in (1, 3)
+
+
+def fourth_moment_check(cfg: "Config", ntargets=0, subband=None):
+    """What a -4 run refuses, before any device resource is opened; returns the Config the chain is built with -- detection
+    forced to Stokes with ndim 4 (LoadToFold1.C:1119-1123), no fused fold (the fused kernels fold ndim 4 / 2 x 2 only) -- or
+    `cfg` itself when -4 is off or loses to npol 1 / 3."""
+    if not fourth_moment_active(cfg):
+        return cfg
+    if cfg.cyclic_nchan > 0:
+        raise DspsrAmdError("dspsr_amd.LoadToFold: fourth_moment (-4) and cyclic_nchan (-cyclic) exclude each other: the cyclic "
+                            "fold replaces Detection (LoadToFold1.C:534-539)")
+    if ntargets > 1:
+        raise DspsrAmdError("dspsr_amd.LoadToFold: fourth_moment (-4) folds one pulsar; %d targets given" % ntargets)
+    if subband is not None:
+        raise DspsrAmdError("dspsr_amd.LoadToFold: fourth_moment (-4) is not built for sub-band sharded runs / the multi-GPU exchange")
+    return dataclasses.replace(cfg, stokes=True, ndim=4, fused_fold=False, force_fused=False)
+
+
 class LoadToFold:
     """One pipeline instance = one GPU = one stream (SingleThread).  `raw` blocks are int8 torch
     tensors already resident on the device (the PCIe copy is the caller's, as TransferCUDA is a
@@ -855,6 +910,8 @@ class LoadToFold:
         targets = list(targets or [])
         self.pulsars = []
         self.cyclic = None
+        self.moments = fourth_moment_active(cfg)         # -4: the fold is (nchan, 1, 14, nbin), fed by FoldEngine.fold_moments
+        cfg = fourth_moment_check(cfg, len(targets), subband)
         if cfg.cyclic_nchan > 0:                         # (before any device resource is opened)
             self._cyclic_geometry = cyclic_check(cfg, info, len(targets), subband, dump_before)
         if len(targets) > 1 and subband is not None:
@@ -924,7 +981,7 @@ class LoadToFold:
         self.nkeep, self.nsamp_step, self.nsamp_overlap = self.fb.nkeep, self.fb.nsamp_step, self.fb.nsamp_overlap
         self.npol_out = 4 // cfg.ndim
         self.fold = FoldEngine(self.ctx)
-        self.fold.set_shape(self.nchan_out, self.npol_out, cfg.ndim, cfg.nbin)
+        self.fold.set_shape(self.nchan_out, *self._fold_dims(), cfg.nbin)
         self.scale8 = eight_bit_scale()
         self.layout = _lib.RAW_CASPSR if info.machine == "CASPSR" else _lib.RAW_GENERIC
         # output observation (Filterbank::prepare_output, Filterbank.C:265-379)
@@ -986,11 +1043,12 @@ class LoadToFold:
             bw = info.bandwidth if subband is None else chbw
             det = name == "Fold"
             path = os.path.join(dump_dir, "pre_%s%s.dump" % (name, "" if subband is None else ".%d" % subband))
+            fold_npol, fold_ndim = self._fold_dims()        # -4: the input of Fold is the FourthMoment stream
             self.dumps[name] = dada.Dump(
-                path, centre_frequency=fc, bandwidth=bw, nchan=self.nchan_out, npol=self.npol_out if det else 2,
-                ndim=cfg.ndim if det else 2, nbit=32, rate=self.out_rate, mjd_day=info.mjd_day,
+                path, centre_frequency=fc, bandwidth=bw, nchan=self.nchan_out, npol=fold_npol if det else 2,
+                ndim=fold_ndim if det else 2, nbit=32, rate=self.out_rate, mjd_day=info.mjd_day,
                 mjd_sec=info.mjd_sec + self.out_start,
-                state=("Stokes" if cfg.stokes else "Coherence") if det else "Analytic",
+                state=("FourthMoment" if self.moments else "Stokes" if cfg.stokes else "Coherence") if det else "Analytic",
                 source=getattr(info, "source", "unknown"), telescope=getattr(info, "telescope", "unknown"))
         if "Fold" in self.dumps:
             self.fused_mode, self.fused_fold = 0, False          # the detected samples must exist in HBM to be dumped
@@ -1094,7 +1152,7 @@ class LoadToFold:
                     g = self._cyclic_geometry
                     self.cyclic.set_shape(self.nchan_out, info.npol, g["npol"], g["nlag"], g["mover"], nbins[0])
                 else:
-                    self.fold.set_shape(self.nchan_out, self.npol_out, cfg.ndim, nbins[0])
+                    self.fold.set_shape(self.nchan_out, *self._fold_dims(), nbins[0])
                 self.hits = np.zeros(nbins[0], dtype=np.uint32)
             return
         self.fused_mode, self.fused_fold = 0, False
@@ -1143,7 +1201,7 @@ class LoadToFold:
         self.nkeep, self.nsamp_step, self.nsamp_overlap = self.fb.nkeep, self.fb.nsamp_step, self.fb.nsamp_overlap
         self.npol_out = 4 // cfg.ndim
         self.fold = FoldEngine(self.ctx)
-        self.fold.set_shape(self.nchan_out, self.npol_out, cfg.ndim, cfg.nbin)
+        self.fold.set_shape(self.nchan_out, *self._fold_dims(), cfg.nbin)
         self.scale8 = eight_bit_scale()
         self.layout = _lib.RAW_CASPSR if info.machine == "CASPSR" else _lib.RAW_GENERIC
         self.out_rate = info.rate / float(self.fb.nsamp_fft_front)                       # Filterbank.C:338-339: freq_res / nsamp_fft
@@ -1167,7 +1225,7 @@ class LoadToFold:
         self.nkeep, self.nsamp_step, self.nsamp_overlap = self.fb.nkeep, self.fb.nsamp_step, self.fb.nsamp_overlap
         self.npol_out = 4 // cfg.ndim
         self.fold = FoldEngine(self.ctx)
-        self.fold.set_shape(self.nchan_out, self.npol_out, cfg.ndim, cfg.nbin)
+        self.fold.set_shape(self.nchan_out, *self._fold_dims(), cfg.nbin)
         self.scale8 = eight_bit_scale()
         self.layout = _lib.RAW_CASPSR if info.machine == "CASPSR" else _lib.RAW_GENERIC
         conv_rate = info.rate * (0.5 if info.ndim == 1 else 1.0)                           # Convolution.C:266-267
@@ -1183,6 +1241,34 @@ class LoadToFold:
         self.hits = np.zeros(cfg.nbin, dtype=np.uint32)
         self.integration_length, self.ndat_total = 0.0, 0
         self.nsamples_in, self.ndat_out, self.subints = 0, 0, []
+
+    def _fold_dims(self):
+        """(npol, ndim) of the folded PhaseSeries: those of the detected rows, or 1 x 14 for -4 (FourthMoment.C:39-42)"""
+        return (1, 14) if self.moments else (self.npol_out, self.cfg.ndim)
+
+    def _fold_rows(self, rows):
+        """Fold::fold of the pending plan over detected rows.  -4: the Stokes rows go to the moments fold, which forms the products
+        in registers; with a pre_Fold tap the 14-float stream dsp::FourthMoment would write exists (`_moment_stream`) and is
+        folded as it is -- the same bits either way."""
+        if not self.moments:
+            return self.fold.fold(rows)
+        if self._moment_rows is not None:
+            return self.fold.fold(self._moment_rows)
+        return self.fold.fold_moments(rows)
+
+    _moment_rows = None
+
+    def _moment_stream(self, rows, ndat):
+        """dsp::FourthMoment on the first `ndat` samples of the Stokes rows (pre_Fold tap of a -4 run): [nchan][1][ndat*14]"""
+        need = self.nchan_out * 14 * (self.sd_head + self.cfg.parts_per_block * self.nkeep)
+        if self._moment_buf is None or self._moment_buf.numel() < need:
+            self._moment_buf = self.torch.empty(need, dtype=self.torch.float32, device="cuda:%d" % self.ctx.device)
+        out = self._moment_buf[:self.nchan_out * 14 * ndat].view(self.nchan_out, 1, 14 * ndat)
+        self._op("FourthMoment", lambda: fourth_moment(self.ctx, rows, out, ndat))
+        self._moment_rows = out
+        return out
+
+    _moment_buf = None
 
     def _op(self, name, fn):
         """Operation::operate with record_time (Operation.C:90-113): wall time of the operation including its stream
@@ -1299,7 +1385,10 @@ class LoadToFold:
         if events is not None:
             events[1].record()
         if "Fold" in self.dumps:
-            self.dumps["Fold"].write(self.detected, ndat, cfg.ndim)
+            if self.moments:
+                self.dumps["Fold"].write(self._moment_stream(self.detected, ndat), ndat, 14)
+            else:
+                self.dumps["Fold"].write(self.detected, ndat, cfg.ndim)
         if self.pulsars:
             self._fold_pulsars(self.detected, ndat)
         for idat_start, ndat_fold, _division, complete in pieces or ():
@@ -1324,13 +1413,16 @@ class LoadToFold:
         nout = self._op("SampleDelay", lambda: self.sample_delay.transform(rows[:, :, :nuse * nd].unflatten(2, (nuse, nd)))) \
             if nuse > 0 else 0
         if nout and "Fold" in self.dumps:
-            self.dumps["Fold"].write(rows, nout, nd)
+            if self.moments:
+                self.dumps["Fold"].write(self._moment_stream(rows, nout), nout, 14)
+            else:
+                self.dumps["Fold"].write(rows, nout, nd)
         if nout and self.pulsars:
             self._fold_pulsars(rows, nout)
         elif nout:
             for idat_start, ndat_fold, _division, complete in self._pieces(nout):
                 folded = self._set_plan(idat_start, ndat_fold)
-                self._op("Fold", lambda: self.fold.fold(rows))
+                self._op("Fold", lambda: self._fold_rows(rows))
                 self.integration_length += folded / self.out_rate
                 self.ndat_total += ndat_fold
                 if complete:
@@ -1386,6 +1478,8 @@ class LoadToFold:
     def _no_cyclic(self, what):
         if self.cyclic is not None:
             raise DspsrAmdError("dspsr_amd.LoadToFold.%s: cyclic spectra are not built for a multi-GPU exchange" % what)
+        if self.moments:
+            raise DspsrAmdError("dspsr_amd.LoadToFold.%s: fourth_moment (-4) is not built for a multi-GPU exchange" % what)
 
     def _single_pulsar_only(self, what):
         if self.pulsars:
@@ -1438,7 +1532,7 @@ class LoadToFold:
     def _fold_piece(self, idat_start, ndat_fold):
         """Fold::fold (Fold.C:650-657,718-803) on detected[idat_start : idat_start+ndat_fold]."""
         folded = self._set_plan(idat_start, ndat_fold)
-        self._op("Fold", lambda: self.fold.fold(self.detected))                  # (no head room without -K)
+        self._op("Fold", lambda: self._fold_rows(self.detected))                 # (no head room without -K)
         self.integration_length += folded / self.out_rate
         self.ndat_total += ndat_fold
 
@@ -1446,7 +1540,8 @@ class LoadToFold:
         """Zero-copy torch view of the device-resident PhaseSeries (Fold::Engine::get_profiles); `pulsar`: one of a multi-target run."""
         torch = self.torch
         fold, nbin = (self.fold, self.cfg.nbin) if pulsar is None else (pulsar.fold, pulsar.nbin)
-        n = self.nchan_out * self.npol_out * nbin * self.cfg.ndim
+        npol, ndim = self._fold_dims()
+        n = self.nchan_out * npol * nbin * ndim
         ptr = fold.get_profiles_ptr()
 
         class _Holder:

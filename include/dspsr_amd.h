@@ -323,7 +323,8 @@ int dspsr_amd_tfp_filterbank(dspsr_amd_ctx* ctx, const dspsr_amd_tfp_config* cfg
  * (Fold.C:724-829): set_nbin, set_ndat, set_bin x ndat (or set_bins), fold.  synch copies to host. */
 int dspsr_amd_fold_create(dspsr_amd_ctx* ctx, dspsr_amd_fold** fold);
 void dspsr_amd_fold_destroy(dspsr_amd_fold* fold);
-/* shape of the input TimeSeries / output PhaseSeries (Fold::Engine::setup, Fold.C:973-1007) */
+/* shape of the input TimeSeries / output PhaseSeries (Fold::Engine::setup, Fold.C:973-1007): ndim 1, 2 or 4 with any npol, or
+ * ndim 14 with npol 1 and only with it -- the fourth moments of the Stokes parameters, below; same rule in bind_profile */
 int dspsr_amd_fold_set_shape(dspsr_amd_fold* fold, uint32_t nchan, uint32_t npol, uint32_t ndim, uint32_t nbin);
 /* Fold::Engine::setup (Fold.C:968-1011): fold INTO the engine-owned device PhaseSeries -- profile_dev =
  * get_profiles()->get_datptr(0,0), span_floats = get_nfloat_span() (floats between consecutive (chan, pol) rows, each
@@ -372,6 +373,29 @@ float* dspsr_amd_fold_profiles_dev(dspsr_amd_fold* fold);   /* device [nchan][np
 uint64_t dspsr_amd_fold_get_ndat_folded(const dspsr_amd_fold* fold);
 int dspsr_amd_fold_zero(dspsr_amd_fold* fold);                                            /* Engine::zero */
 int dspsr_amd_fold_synch(dspsr_amd_fold* fold, float* profile_host);                      /* FoldCUDA.cu:127-152 (blocks) */
+
+/* ---- fourth-order moments of the Stokes parameters, `dspsr -4` (LoadToFold1.C:552-568; detection forced to Stokes, ndim 4:
+ * :1119-1123) ----
+ * dsp::FourthMoment::transformation (Signal/General/FourthMoment.C:29-77): per channel and sample the four Stokes floats, copied
+ * bit for bit, then in[i] * in[j] for i <= j in the loop order of :67-72 (00 01 02 03 11 12 13 22 23 33), each one float multiply
+ * rounded to nearest: rows of ndat*4 floats `in_chan_stride` apart in, rows of ndat*14 floats `out_chan_stride` apart out (npol
+ * 1, ndim 14, state FourthMoment: :39-42).  Out of place only, as in the reference (:25).  DSPSR_AMD_EINVAL before any launch:
+ * in_dev == out_dev; input rows not 16-byte aligned (in_dev, in_chan_stride % 4) or output rows not 8-byte aligned (out_dev,
+ * out_chan_stride % 2); a stride shorter than its row (ndat*4, ndat*14); nchan > 65535.  ndat == 0: nothing to do (:49-50). */
+int dspsr_amd_fourth_moment(dspsr_amd_ctx* ctx, const float* in_dev, uint64_t in_chan_stride, float* out_dev,
+                            uint64_t out_chan_stride, uint32_t nchan, uint64_t ndat);
+/* Folding the moments (Fold.C:835-891 is a plain sum over whatever ndim arrives; Archiver.C:382-405 takes npol*ndim == 14): a
+ * fold of shape npol 1 x ndim 14.  set_nbin, set_ndat, set_bin, set_bins[_weighted], zero, synch, profiles_dev and
+ * get_ndat_folded work on it as on any shape.  dspsr_amd_fold_fold reads ndim 14 rows, the output of dspsr_amd_fourth_moment
+ * (in_pol_stride is not used: one polarisation).  dspsr_amd_fold_fold_moments reads the ndim 4 Stokes rows themselves (npol 1)
+ * and forms the ten products in registers, so the 14-float stream is never written or read; DSPSR_AMD_EINVAL on a fold of any
+ * other shape.  The two are bit-identical on the same Stokes samples, plan and device: one accumulation, two loaders
+ * (csrc/fold_moments.hip).  Sums as for every fold: no atomics, the same bits run to run; plans of runs shorter than 64 samples
+ * in strict time order (Fold.C:844-852), plans with a longer run re-associated like the long-run fold, deterministically.
+ * Rows at any float-aligned address (16-byte aligned rows load faster).  dspsr_amd_fold_fold_many and
+ * dspsr_amd_fold_fold_zeroed refuse a 14-shape (DSPSR_AMD_EINVAL), and the fused filterbank+fold entry points stay npol 1 x
+ * ndim 4 / npol 2 x ndim 2: `-4` runs perform_detect (Stokes, ndim 4), then fold_moments. */
+int dspsr_amd_fold_fold_moments(dspsr_amd_fold* fold, const float* stokes_dev, uint64_t in_chan_stride);
 
 /* ---- dsp::CyclicFoldEngine: cyclic spectra, `dspsr -cyclic N [-cyclicoversample M]` (LoadToFold1.C:534-539,999-1044) ----------
  * Lag-domain folding of the filterbank's complex voltages (Analytic float rows in FPT order: what

@@ -6,6 +6,8 @@ dspsr_amd.dada.fold_file for trying the engine on a DADA file; not a re-implemen
   dspsr_amd_fold.py -F 128 ...   (no `:D`: filterbank, THEN coherent dedispersion per channel -- Filterbank::Config::After; -D 0: none)
   dspsr_amd_fold.py -F 128:B ... (coherent dedispersion of the whole band, THEN the filterbank -- Filterbank::Config::Before)
                     [--dump Detection] [--dump Fold] [-O out_prefix] file.dada
+  dspsr_amd_fold.py -F 64:D -4 ...   (fourth-order moments: Stokes detection with ndim 4, then the four Stokes parameters and their
+                    ten pairwise products folded into every bin -- files of STATE FourthMoment, NPOL 1, NDIM 14)
   dspsr_amd_fold.py -F 64:D -cyclic 256 [-cyclicoversample 4] [-d 1|2|4] ...   (cyclic spectra: dsp::CyclicFold instead of
                     Detection + Fold; -d is then the number of output polarisations, default 4 -- 1 for single-polarisation input)
 
@@ -36,6 +38,7 @@ def parse_args(argv=None):
     ap.add_argument("-turns", dest="turns", type=float, default=0.0, help="turns per sub-integration")
     ap.add_argument("-K", dest="interchan", action="store_true", help="remove the inter-channel dispersion delay")
     ap.add_argument("-d", dest="ndim", type=int, default=4, choices=[1, 2, 4], help="detected layout (ndim); with -cyclic: output polarisations")
+    ap.add_argument("-4", dest="fourth", action="store_true", help="compute fourth-order moments")
     ap.add_argument("-cyclic", dest="cyclic", type=int, default=0, help="form cyclic spectra with N channels per filterbank channel")
     ap.add_argument("-cyclicoversample", dest="cyclic_mover", type=int, default=1, help="use M times as many lags to improve the cyclic channel isolation")
     ap.add_argument("-r", dest="record", action="store_true", help="report the time spent in each operation")
@@ -85,7 +88,7 @@ def main(argv=None):
     cfg = pipeline.Config(nchan=nchan, dispersion_measure=dm, nbin=nbin, folding_period=period, freq_res=a.nfft,
                           subint_seconds=a.subint, subint_turns=1.0 if a.single else a.turns, ndim=1 if a.cyclic else a.ndim,
                           cyclic_nchan=a.cyclic, cyclic_mover=a.cyclic_mover, cyclic_npol=(a.ndim if info.npol == 2 else 1) if a.cyclic else 0,
-                          interchan_dedispersion=a.interchan, record_time=a.record,
+                          interchan_dedispersion=a.interchan, record_time=a.record, fourth_moment=a.fourth,
                           convolve_when="never" if when == "after" and dm == 0.0 else when)
     torch.cuda.set_device(a.device)
     lt = dada.fold_file(a.file, cfg, polyco=polyco, device=a.device, stream=torch.cuda.current_stream().cuda_stream,

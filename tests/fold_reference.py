@@ -9,6 +9,7 @@ detected samples [nchan][npol][ndat][ndim] (sample idat of a row at rows[:, :, i
   k_fold_direct, k_fold_chunked<., false, .> and k_fold_dense.
 - fold_long_model: the association of k_fold_chunked<., true, .> + k_fold_combine (the LONG path), bit for bit.
 - fold_dispatch: which kernel fold_fold_impl launches for a call, with its template arguments and launch shape.
+- fused_fold_model: the fold inside the last filterbank pass (dspsr_amd_filterbank_perform_fold, fold_is_fused() 1 and 2).
 """
 import numpy as np
 
@@ -167,3 +168,74 @@ def fold_dispatch(addr, chan_stride, pol_stride, nchan, npol, ndim, nbin, runs, 
     nrw = npol if (ndim * npol == 4 and ndim < 4 and nchan * (nseg if lng else nsplit) >= 2 * ncu) else 1   # :933-934
     kernel = "dense" if dense else ("long" if lng else "chunked")
     return dict(kernel=kernel, ndim=ndim, nrow=nrw, nsplit=1 if lng else nsplit, nseg=nseg, cps=cps, threads=threads)
+
+
+# ---- the fold inside the last filterbank pass (k_inv_chan<., FOLD>, k_rows_inv<., ., FOLD>) ------------------------------------
+FUSED_MAX_SEG = 16       # runs of a segmented launch at most (filterbank.hip fb_launch_fused: `if (nseg > 16) nseg = 16`)
+
+
+def fused_nseg(ns, tiles, wgs):
+    """fb_launch_fused's number of runs for a segmented launch of `ns` parts: clamp(wgs / tiles, 1, min(ns, 16)), one when the
+    tiles fill the workgroups (`segmented && tiles < wgs`)"""
+    if tiles >= wgs:
+        return 1
+    return max(1, min(wgs // tiles, ns, FUSED_MAX_SEG))
+
+
+def fused_runs_of_launch(ns, nseg):
+    """the kernel's run arithmetic (fb_inv_chan.h: fpps, fp0, fnp): [(first part, parts)] of runs 0 .. nseg - 1 of a launch of
+    ns parts; trailing runs may hold no part (their workgroups return at once)"""
+    fpps = -(-ns // nseg)
+    return [(s * fpps, max(0, min(ns, (s + 1) * fpps) - s * fpps)) for s in range(nseg)]
+
+
+def clip_runs(runs, first, last):
+    """the pieces of the plan's runs inside samples [first, last)"""
+    out = []
+    for off, b, n in np.asarray(runs, np.int64).reshape(-1, 3):
+        lo, hi = max(int(off), first), min(int(off + n), last)
+        if hi > lo:
+            out.append((lo, int(b), hi - lo))
+    return np.array(out, np.int64).reshape(-1, 3)
+
+
+def fused_launch_sums(rows, runs, out, nkeep, part0, ns, nseg):
+    """One launch of ns parts from part part0 of the call, cut into nseg runs: (`out` with run 0 added in time order, the sums
+    from zero of runs 1 .. nseg - 1 in time order); rows [chan][1][ndat][4], out [chan][1][nbin][4]"""
+    partial = []
+    for s, (p0, np_) in enumerate(fused_runs_of_launch(ns, nseg)):
+        piece = clip_runs(runs, (part0 + p0) * nkeep, (part0 + p0 + np_) * nkeep)
+        if s == 0:
+            out = fold_time_order(rows, piece, out)
+        else:
+            partial.append(fold_time_order(rows, piece, np.zeros_like(out)))
+    return out, partial
+
+
+def fused_fold_model(det, runs, profile, nkeep, launches, mode, nseg_of=None):
+    """The profile after dspsr_amd_filterbank_perform_fold of one call, bit for bit.  det: the detected samples float32
+    [chan][ndat][4] of the call (ndat = parts * nkeep); runs: the call's plan; profile: [chan][npol][nbin][ndim] with
+    npol * ndim = 4 (a bin's four sums are independent: the 2 x 2 profile holds the same bits in another place); launches: the
+    parts of every launch of the fused kernel, in order (fb_group_parts: min(left, max_parts) while the passes stay below 2^31
+    items); mode = fold_is_fused().
+      mode 1: every (chan, bin) sum in strict time order onto the profile -- a launch walks its parts in order, launches are
+              stream ordered: fold_time_order of the whole call.
+      mode 2: the ns parts of a launch are cut into nseg_of(ns) runs (fused_runs_of_launch); run 0 adds onto the profile in
+              time order, every other run sums from zero in time order, and k_fold_combine adds those sums to the profile in
+              run order, every bin of every run: profile = ((profile + p1) + p2) + ..."""
+    det = np.asarray(det, np.float32)
+    rows = det[:, None, :, :]
+    shape = np.shape(profile)
+    nchan, nbin = shape[0], shape[2]
+    assert shape[1] * shape[3] == 4 and det.shape[0] == nchan and det.shape[2] == 4
+    # (chan, pol, bin, dim) -> (chan, 1, bin, 2 * pol + dim): the float4 the kernel keeps per (chan, bin)
+    out = np.array(profile, np.float32).transpose(0, 2, 1, 3).reshape(nchan, 1, nbin, 4)
+    assert mode in (1, 2)
+    part0 = 0
+    for ns in launches:
+        out, partial = fused_launch_sums(rows, runs, out, nkeep, part0, ns, 1 if mode == 1 else nseg_of(ns))
+        for p in partial:
+            out = out + p
+        part0 += ns
+    assert part0 * nkeep == det.shape[1], "the launches do not cover the call"
+    return out.reshape(nchan, nbin, shape[1], shape[3]).transpose(0, 2, 1, 3)

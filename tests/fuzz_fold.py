@@ -2,7 +2,9 @@
 loop (Fold.C:835-891, strict time order) for the exact kernels, fold_long_model for plans that take the long-run fold (the
 kernel fold_reference.fold_dispatch names); hits identical.  The rows sit at a random float offset with padded rows (NaN
 around them), and some cases fold into a profile bound to a padded caller buffer.  Also random LoadToFold configurations,
-fused against Detection + Fold."""
+fused against Detection + Fold, and -- where the fold of every block is one call of the fused kernels (fold_is_fused() 1 or 2) --
+against fold_reference.fused_fold_model bit for bit; each configuration also with the library's own choice (FUSED_AUTO), which is
+where the segmented launches (mode 2) come from."""
 import os
 import sys
 
@@ -15,6 +17,7 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import dspsr_amd
 from dspsr_amd import pipeline, synth
 from device_buffers import device_rows
+from fused_fold_cases import FOLD_FUSED_MAX_RUN, loadtofold_block_model
 from fold_reference import fold_dispatch, fold_long_model, fold_time_order, runs_of_plan
 
 ncases = int(sys.argv[1]) if len(sys.argv) > 1 else 60
@@ -88,11 +91,11 @@ for i in range(max(4, ncases // 3)):
     ppb, mp = int(rng.integers(1, 6)), int(rng.integers(1, 4))
     sub = float(rng.choice([0.0, 0.0, 0.0021]))
     info = pipeline.InputInfo(centre_frequency=freq, bandwidth=bw, tsamp_us=tsamp, machine="DADA")
-    res = []
+    res, modes, exact, modelled = [], [], [], []
     refused = None
-    for fused in (True, False):
+    for fused, forced in ((True, True), (False, False), (True, False)):
         cfg = pipeline.Config(nchan=nchan, dispersion_measure=dm, nbin=nbin, folding_period=period, ndim=4, parts_per_block=ppb,
-                              max_parts=mp, fused_fold=fused, force_fused=fused, subint_seconds=sub)
+                              max_parts=mp, fused_fold=fused, force_fused=forced, subint_seconds=sub)
         try:
             lt = pipeline.LoadToFold(cfg, info, device=0, stream=torch.cuda.current_stream().cuda_stream)
             if 3 * ppb * lt.nsamp_step + lt.nsamp_overlap > (1 << 25):
@@ -103,22 +106,36 @@ for i in range(max(4, ncases // 3)):
             break
         step = ppb * lt.nsamp_step
         raw = torch.from_numpy(synth.voltages(3 * step + lt.nsamp_overlap, freq, bw, tsamp, max(dm, 1.0), period, seed=7 + i)).cuda()
+        # the model: one sub-integration, every block folded by one call of the fused kernels (None as soon as one is not)
+        model = np.zeros((nchan, 1, nbin, 4), np.float32) if sub == 0.0 and lt.fused_mode in (1, 2) else None
         for b in range(3):
-            lt.process_block(raw[2 * b * step: 2 * (b * step + step + lt.nsamp_overlap)])
+            block = raw[2 * b * step: 2 * (b * step + step + lt.nsamp_overlap)]
+            if model is not None:
+                table_mode, _h, model = loadtofold_block_model(lt, block, ppb, model, ncu)
+                if model is None:
+                    print("note  block %d of the %s run has a run of %d samples or more: Detection + Fold there, no exact model for this run"
+                          % (b, "forced" if forced else "auto", FOLD_FUSED_MAX_RUN), flush=True)
+                if table_mode != lt.fused_mode:
+                    bad += 1
+                    print("FAIL  fold_is_fused() %d, the table says %d" % (lt.fused_mode, table_mode), flush=True)
+            lt.process_block(block)
         if lt.ndat_total:
             lt.finish_subint()
         lt.synchronize()
         res.append([(s["hits"].copy(), s["profile_dev"].cpu().numpy(), s["ndat_total"]) for s in lt.subints])
-        mode = lt.fused_mode if fused else mode
+        modes.append(lt.fused_mode)
+        modelled.append(model is not None)
+        exact.append(model is None or (len(res[-1]) == 1 and np.array_equal(res[-1][0][1].reshape(-1), model.reshape(-1))))
         freq_res = lt.response.ndat
         lt.close()
     if refused is not None:
         print("refused pipeline freq=%g bw=%g DM=%g nchan=%d -- %s" % (freq, bw, dm, nchan, refused[:90]), flush=True)
         continue
-    desc = "pipeline freq=%g bw=%g DM=%g nchan=%d freq_res=%d nbin=%d period=%g parts/block=%d max_parts=%d subint=%g (%d sub-integrations, mode %d)" % (
-        freq, bw, dm, nchan, freq_res, nbin, period, ppb, mp, sub, len(res[0]), mode)
-    good = len(res[0]) == len(res[1])
-    for a, b in zip(res[0], res[1]):
+    desc = "pipeline freq=%g bw=%g DM=%g nchan=%d freq_res=%d nbin=%d period=%g parts/block=%d max_parts=%d subint=%g (%d sub-integrations, mode %d, auto %d)" % (
+        freq, bw, dm, nchan, freq_res, nbin, period, ppb, mp, sub, len(res[0]), modes[0], modes[2])
+    desc += " exact model: %s" % "/".join("yes" if m else "-" for m in (modelled[0], modelled[2]))
+    good = len(res[0]) == len(res[1]) == len(res[2]) and all(exact)
+    for a, b in list(zip(res[0], res[1])) + list(zip(res[2], res[1])):
         # (float32 sums of N samples per bin, associated differently by the two paths: the same sqrt(N) allowance as above --
         #  186 000 hits per bin gave 3.8e-6, identical for every launch shape)
         scale = max(np.abs(b[1]).max(), 1e-30) * max(1.0, (float(b[0].max()) / 100.0) ** 0.5)

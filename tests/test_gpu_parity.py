@@ -13,6 +13,7 @@ import types
 import numpy as np
 import pytest
 
+import fused_fold_cases
 from device_buffers import SENTINEL, OutputLayout, describe_float, device_rows, sentinel_rows, written_mask
 
 pytestmark = pytest.mark.gpu
@@ -1595,6 +1596,8 @@ def test_segmented_fused_fold(oracle, gpu, C, M, nfilt, nbin, real):
     rng = np.random.default_rng(81)
     kernel = np.exp(1j * rng.uniform(-np.pi, np.pi, N)).astype(np.complex64)
     res = {}
+    ncu = torch.cuda.get_device_properties(0).multi_processor_count
+    model = np.zeros((C, 1, nbin, 4), np.float32)
     for mode in ("auto", "auto2", "never", "always"):
         pol = {"auto": dspsr_amd.FUSED_AUTO, "auto2": dspsr_amd.FUSED_AUTO, "never": dspsr_amd.FUSED_NEVER, "always": dspsr_amd.FUSED_ALWAYS}[mode]
         eng = dspsr_amd.FilterbankEngine(ctx).setup(C, M, nfilt[0], nfilt[1], 1, 2, real, kernel, max_parts=8, fused_fold=pol)
@@ -1607,11 +1610,21 @@ def test_segmented_fused_fold(oracle, gpu, C, M, nfilt, nbin, real):
             raw = torch.from_numpy(_raw((npart * step + ovl), npol=2, ndim=ndim_in, seed=200 + call)).cuda()
             fold.set_nbin(nbin)
             fold.set_ndat(npart * nkeep, 0)
-            fold.set_bins((0.21 + call * npart * nkeep * pps) % 1.0, pps, npart * nkeep, 0, hits)
+            phi = (0.21 + call * npart * nkeep * pps) % 1.0
+            fold.set_bins(phi, pps, npart * nkeep, 0, hits)
             eng.perform_fold(fold, npart, dspsr_amd.COHERENCE, raw=raw, scale=float(o.S8))
+            if mode == "auto":
+                # the run sums restated (tests/fold_reference.py fused_fold_model): run 0 onto the profile, the others from zero,
+                # added in run order -- bit for bit
+                det = torch.zeros((C, 1, 4 * npart * nkeep), dtype=torch.float32, device="cuda")
+                eng.perform_detect(det, npart, dspsr_amd.COHERENCE, 4, raw=raw, scale=float(o.S8))
+                runs = fused_fold_cases.runs_of(fused_fold_cases.phase_plan(phi, pps, nbin, npart * nkeep), nbin)
+                table_mode, model = fused_fold_cases.model_of_call(eng.cfg, det.view(C, npart * nkeep, 4).cpu().numpy(), runs, model, npart, ncu)
+                assert table_mode == eng.fold_is_fused() == 2 and model is not None
         res[mode] = (hits, fold.synch())
         eng.close()
         fold.close()
+    assert np.array_equal(res["auto"][1], model)                                # the model of the segmented launches
     assert np.array_equal(res["auto"][1], res["auto2"][1])                      # deterministic
     assert np.array_equal(res["never"][1], res["always"][1])                    # the exact paths agree bit for bit
     for m in ("auto2", "never", "always"):

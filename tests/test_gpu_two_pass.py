@@ -14,6 +14,7 @@ import math
 import numpy as np
 import pytest
 
+import fused_fold_cases
 from test_gpu_parity import _fb_case, _raw, gpu  # noqa: F401  (fixture)
 
 pytestmark = pytest.mark.gpu
@@ -133,17 +134,25 @@ def test_two_pass_segmented_fused_fold_and_pipeline(oracle, gpu):
     """The cfg 4 shard as the bench runs it (pipeline.LoadToFold on sub-band g of an NCHAN-8 band, segmented fused fold: the
     32 tiles do not fill the chip) against (a) the same pipeline with Detection and Fold as separate launches (<= 2e-6 of the
     profile maximum: the part runs of the segmented fold are re-associated) and (b) the three-pass pipeline (two_pass=False),
-    identical hits in every case."""
+    identical hits in every case; and (c) the run sums restated (tests/fold_reference.py fused_fold_model, wgs = the compute
+    units: one workgroup of k_rows_inv per unit), bit for bit."""
     dspsr_amd, _ = gpu
+    ncu = torch.cuda.get_device_properties(0).multi_processor_count
     from dspsr_amd import pipeline
     info = pipeline.InputInfo(centre_frequency=1382.0, bandwidth=-400.0, nchan=8, npol=2, ndim=2, tsamp_us=0.02, machine="DADA")
-    res = {}
+    res, model, model_hits = {}, None, None
     for key, kw in (("two_fused", {}), ("two_unfused", {"fused_fold": False}), ("three_fused", {"two_pass": False})):
         cfg = pipeline.Config(nchan=4096, dispersion_measure=1000.0, nbin=1024, folding_period=0.0893, freq_res=512, ndim=4,
                               parts_per_block=24, max_parts=24, **kw)
         lt = pipeline.LoadToFold(cfg, info, device=0, stream=torch.cuda.current_stream().cuda_stream, subband=5)
         raw = torch.from_numpy(_raw(lt.block_bytes() // 4, 2, 2, 1, seed=77)).cuda()
         for _ in range(2):
+            if key == "two_fused":
+                if model is None:
+                    model, model_hits = np.zeros((lt.nchan_out, 1, cfg.nbin, 4), np.float32), np.zeros(cfg.nbin, np.uint32)
+                mode, h, model = fused_fold_cases.loadtofold_block_model(lt, raw, 24, model, ncu)
+                assert mode == lt.fused_mode == 2 and lt.fb.npass(True) == 2 and model is not None
+                model_hits += h
             lt.process_block(raw)
         lt.finish_subint()
         lt.synchronize()
@@ -153,6 +162,7 @@ def test_two_pass_segmented_fused_fold_and_pipeline(oracle, gpu):
     assert res["two_fused"][2] and not res["two_unfused"][2]
     h, p, _ = res["two_fused"]
     assert int(h.sum()) == 2 * 24 * 458 and np.abs(p).max() > 0
+    assert np.array_equal(h, model_hits) and np.array_equal(p, model.reshape(-1))         # the model of the segmented launches
     for key in ("two_unfused", "three_fused"):
         assert np.array_equal(res[key][0], h), key
         assert np.abs(res[key][1] - p).max() <= 2e-6 * np.abs(p).max(), (key, np.abs(res[key][1] - p).max() / np.abs(p).max())

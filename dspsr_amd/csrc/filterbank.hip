@@ -1358,7 +1358,7 @@ extern "C" int dspsr_amd_filterbank_perform_fold(dspsr_amd_filterbank* fb, const
   const bool prof_vec4 = planes2 ? (fold->span % 2 == 0 && ((uintptr_t)fold->profile % 16) == 0)
                                  : (fold->span % 4 == 0 && ((uintptr_t)fold->profile % 16) == 0);
   if (dspsr_amd_filterbank_fold_is_fused(fb) == 3 && !planes2 && prof_vec4 && npart &&
-      fold_plan_max_run(fold) >= FOLD_LONG_RUN_HOST && npart * (uint64_t)fb->g.nkeep < (1ull << 32)) {
+      fold_plan_max_run(fold) >= FOLD_LONG_RUN && npart * (uint64_t)fb->g.nkeep < (1ull << 32)) {
     // Four-pass geometry (dsp::Convolution shapes, -F N:D with a long response) and wide phase bins: the second inverse pass
     // reduces its tile to the sums of the Tt-sample segments it holds and a second kernel adds those in time order -- the
     // detected time series (16 bytes per sample, written and read once) never reaches HBM.  Plans that do not qualify

@@ -55,7 +55,7 @@ __global__ void k_fold_direct(const float* __restrict__ in, const uint64_t chan_
 // therefore happen in time order, as in Fold.C:844-852.  With few (chan, pol) rows the bins of a row are dealt to
 // gridDim.z workgroups (each streams the whole row: the re-reads come from L2 / Infinity Cache), so that the chip
 // is filled without touching the order of any sum.
-constexpr uint32_t FOLD_CHUNK = 2048;   // samples per chunk
+// (FOLD_CHUNK samples per chunk: fold_plan.h, with the host's tables over the same chunk grid)
 constexpr int FOLD_BPT = 4;             // bins per thread (nbin <= FOLD_BPT * blockDim)
 // LONG runs.  A sum in strict time order is one dependent chain of float adds per (chan, pol, bin, dim): with phase bins
 // hundreds of samples wide only a couple of chains are alive per row and the kernel is bound by the add latency (10 ms per
@@ -69,7 +69,6 @@ constexpr int FOLD_BPT = 4;             // bins per thread (nbin <= FOLD_BPT * b
 // k_fold_combine; the segment count follows from the device's compute units and nchan*npol (fold_fold_impl), so the sums
 // are reproducible on one device and row count, not across them.  Plans of shorter runs keep the exact time-order kernel.
 constexpr uint32_t FOLD_MB = 32;
-constexpr uint32_t FOLD_LONG_RUN = FOLD_LONG_RUN_HOST;
 
 // NROW: polarisation rows of one channel folded by the same workgroup (detected data with ndim < 4 lie in 4/ndim planes:
 // the walk through the bin plan -- most of the work with 4-byte samples -- then serves all planes; the sums of every
@@ -647,28 +646,50 @@ static void slot_free(PlanSlot& s)
   s = PlanSlot();
 }
 
-static bool slot_reserve(PlanSlot& s, size_t nbin1, size_t niv)
+// one pinned / device buffer pair of a slot: at least `need` elements, `alloc` of them when it has to grow
+template <class T>
+static bool slot_grow(T*& h, T*& d, size_t& cap, size_t need, size_t alloc)
+{
+  if (need <= cap) return true;
+  if (h) (void)hipHostFree(h);
+  if (d) (void)hipFree(d);
+  h = nullptr; d = nullptr; cap = 0;
+  if (hipHostMalloc((void**)&h, alloc * sizeof(T)) != hipSuccess) return false;
+  if (hipMalloc((void**)&d, alloc * sizeof(T)) != hipSuccess) return false;
+  cap = alloc;
+  return true;
+}
+
+// the words are sized exactly (nbin + 1 hardly ever changes); intervals and aux words follow the plan and grow with headroom
+static bool slot_reserve(PlanSlot& s, size_t nwords, size_t niv, size_t naux)
 {
   if (!s.done && hipEventCreateWithFlags(&s.done, hipEventDisableTiming) != hipSuccess) return false;
   if (!s.ready && hipEventCreateWithFlags(&s.ready, hipEventDisableTiming) != hipSuccess) return false;
-  if (nbin1 > s.bin_cap) {
-    if (s.h_bin_start) (void)hipHostFree(s.h_bin_start);
-    if (s.d_bin_start) (void)hipFree(s.d_bin_start);
-    s.h_bin_start = nullptr; s.d_bin_start = nullptr; s.bin_cap = 0;
-    if (hipHostMalloc((void**)&s.h_bin_start, nbin1 * sizeof(uint32_t)) != hipSuccess) return false;
-    if (hipMalloc((void**)&s.d_bin_start, nbin1 * sizeof(uint32_t)) != hipSuccess) return false;
-    s.bin_cap = nbin1;
+  return slot_grow(s.h_bin_start, s.d_bin_start, s.bin_cap, nwords, nwords) &&
+         slot_grow(s.h_iv, s.d_iv, s.iv_cap, niv, niv + niv / 2 + 16) &&
+         slot_grow(s.h_aux, s.d_aux, s.aux_cap, naux, naux + naux / 4 + 1024);
+}
+
+// FoldCUDA.cu:163-164: the open run gets its hits.  The plan is used up: the next one opens a fresh run (as after set_nbin).
+static void plan_close(dspsr_amd_fold* f)
+{
+  if (f->current_hits && !f->binplan.empty()) f->binplan.back().hits = f->current_hits;
+  f->current_hits = 0;
+  f->current_bin = f->folding_nbin;
+}
+
+// The engine's next slot.  The fold that last used it (two plans ago) must have consumed it before the host rewrites it.
+static int slot_acquire(dspsr_amd_fold* f, const char* who, PlanSlot** out)
+{
+  PlanSlot& sl = f->slot[f->next_slot];
+  f->next_slot ^= 1;
+  if (sl.pending) {
+    const hipError_t e = hipEventSynchronize(sl.done);
+    if (e != hipSuccess) return ctx_fail(f->ctx, DSPSR_AMD_EHIP, "%s: %s", who, hipGetErrorString(e));
+    sl.pending = false;
   }
-  if (niv > s.iv_cap) {
-    const size_t n = niv + niv / 2 + 16;
-    if (s.h_iv) (void)hipHostFree(s.h_iv);
-    if (s.d_iv) (void)hipFree(s.d_iv);
-    s.h_iv = nullptr; s.d_iv = nullptr; s.iv_cap = 0;
-    if (hipHostMalloc((void**)&s.h_iv, n * sizeof(Interval)) != hipSuccess) return false;
-    if (hipMalloc((void**)&s.d_iv, n * sizeof(Interval)) != hipSuccess) return false;
-    s.iv_cap = n;
-  }
-  return true;
+  *out = &sl;
+  return DSPSR_AMD_OK;
 }
 
 // Plans go to the device on the fold's own stream, not in the compute stream: there a pair of small host-to-device copies
@@ -692,6 +713,15 @@ int fold_plan_wait(dspsr_amd_fold* f, PlanSlot* slot)
   if (e != hipSuccess) return ctx_fail(f->ctx, DSPSR_AMD_EHIP, "fold: plan wait: %s", hipGetErrorString(e));
   return DSPSR_AMD_OK;
 }
+// behind the last kernel that reads the plan: pending only once `done` is recorded
+static int slot_submit(dspsr_amd_fold* f, const char* who, PlanSlot& sl)
+{
+  const hipError_t e = hipEventRecord(sl.done, f->ctx->stream);
+  if (e != hipSuccess) return ctx_fail(f->ctx, DSPSR_AMD_EHIP, "%s: %s", who, hipGetErrorString(e));
+  sl.pending = true;
+  return DSPSR_AMD_OK;
+}
+int fold_part_plan_submitted(dspsr_amd_fold* f, PlanSlot* slot) { return slot_submit(f, "fused fold", *slot); }
 
 extern "C" int dspsr_amd_fold_create(dspsr_amd_ctx* ctx, dspsr_amd_fold** out)
 {
@@ -955,114 +985,55 @@ extern "C" int dspsr_amd_fold_zero(dspsr_amd_fold* f)
   return DSPSR_AMD_OK;
 }
 
-// One walk over the runs of the pending plan decides which kernel folds them: the longest run (the return value; re-associated
-// sums, see FOLD_LONG_RUN) and, when try_dense, whether the plan fits the dense per-chunk table of k_fold_dense over the chunk
-// grid that starts at `first` -- at most one run per (chunk, phase bin), runs cut at the chunk ends; a plan with two runs of a
-// bin inside a chunk (a folding period shorter than the chunk) does not.  The table is also refused when it would be more than
-// a quarter of the bytes it helps to fold (few channels, many bins).  (This host code runs once per block next to a kernel of a
-// few hundred microseconds: at Benchmark/fold.csh's shape the three separate walks and the bucket sort below, which the dense
-// kernel does not read, made the host as slow as the device -- profiles/r05_experiments.txt item 6.)
-static uint32_t plan_scan(dspsr_amd_fold* f, bool try_dense, uint64_t first, uint64_t last, size_t* ntab, bool* one_per_chunk)
-{
-  const uint32_t nbin = f->nbin;
-  uint32_t max_run = 0;
-  bool ok = try_dense;
-  *ntab = 0;
-  if (ok) {
-    const uint64_t nchunk = (last - first + FOLD_CHUNK - 1) / FOLD_CHUNK;
-    *ntab = (size_t)nchunk * nbin;
-    const uint64_t data_words = (last - first) * (uint64_t)f->nchan * f->npol * f->ndim;
-    ok = *ntab <= ((size_t)1 << 24) && 4 * (uint64_t)*ntab <= data_words;
-  }
-  if (ok) {
-    f->cursor.assign(nbin, ~0u);                            // (scratch: chunk of the bin's previous piece)
-    uint32_t* const lastc = f->cursor.data();
-    for (const RunBin& r : f->binplan) {
-      if (r.hits > max_run) max_run = r.hits;
-      if (r.hits == 0 || !ok) continue;
-      const uint64_t c0 = (r.offset - first) / FOLD_CHUNK, c1 = (r.offset - first + r.hits - 1) / FOLD_CHUNK;
-      if (lastc[r.ibin] == (uint32_t)c0) ok = false;                       // a second run of this bin in the chunk
-      lastc[r.ibin] = (uint32_t)c1;
-    }
-  } else {
-    for (const RunBin& r : f->binplan) if (r.hits > max_run) max_run = r.hits;
-  }
-  *one_per_chunk = ok;
-  return max_run;
-}
-
-// the intervals bucketed by phase bin (stable => time order kept inside a bin): what the walk kernels and the per-channel hit
-// count of a zeroed input read -- not the dense kernel
-static void plan_bucket(dspsr_amd_fold* f, PlanSlot& sl)
-{
-  const uint32_t nbin = f->nbin;
-  for (uint32_t b = 0; b <= nbin; b++) sl.h_bin_start[b] = 0;
-  for (const RunBin& r : f->binplan) sl.h_bin_start[r.ibin + 1]++;
-  for (uint32_t b = 0; b < nbin; b++) sl.h_bin_start[b + 1] += sl.h_bin_start[b];
-  f->cursor.assign(sl.h_bin_start, sl.h_bin_start + nbin);
-  for (const RunBin& r : f->binplan) {
-    Interval v; v.offset = r.offset; v.hits = r.hits; v.pad = 0;
-    sl.h_iv[f->cursor[r.ibin]++] = v;
-  }
-}
-
-// the dense table tab[chunk][bin] = first sample of the run inside the chunk | samples << 11 (0: none) over the chunk grid that
-// starts at `first`, in the slot's aux buffers; false: allocation failed
-static bool plan_dense_fill(dspsr_amd_fold* f, PlanSlot& sl, uint64_t first, size_t ntab)
-{
-  const uint32_t nbin = f->nbin;
-  if (ntab > sl.aux_cap) {
-    if (sl.h_aux) (void)hipHostFree(sl.h_aux);
-    if (sl.d_aux) (void)hipFree(sl.d_aux);
-    sl.h_aux = nullptr; sl.d_aux = nullptr; sl.aux_cap = 0;
-    const size_t n = ntab + ntab / 4 + 1024;
-    if (hipHostMalloc((void**)&sl.h_aux, n * sizeof(uint32_t)) != hipSuccess || hipMalloc((void**)&sl.d_aux, n * sizeof(uint32_t)) != hipSuccess)
-      return false;
-    sl.aux_cap = n;
-  }
-  ::memset((void*)sl.h_aux, 0, ntab * sizeof(uint32_t));
-  for (const RunBin& r : f->binplan) {
-    uint64_t off = r.offset - first;
-    uint32_t left = r.hits;
-    while (left) {
-      const uint64_t c = off / FOLD_CHUNK;
-      const uint32_t s0 = (uint32_t)(off % FOLD_CHUNK), n = left < FOLD_CHUNK - s0 ? left : FOLD_CHUNK - s0;
-      sl.h_aux[c * nbin + r.ibin] = s0 | (n << 11);
-      off += n;
-      left -= n;
-    }
-  }
-  return true;
-}
-
-// The pending plan closed, bucketed by phase bin and on its way to the device in the next slot: what a walk kernel of another
-// translation unit (fold_moments.hip) reads.  The caller launches, then calls fold_part_plan_submitted.  The plan is consumed.
-int fold_plan_to_device(dspsr_amd_fold* f, const char* who, PlanSlot** slot, uint64_t* first, uint64_t* last, uint32_t* max_run)
+// The closed plan of `f` on its way to the device in the engine's next slot, over the chunk grid [first, last): the dense
+// table of k_fold_dense (aux) when try_dense, the plan fits it (plan_scan) and no run is a LONG one; the intervals bucketed by
+// phase bin (bin_start / iv: the walk kernels, the hit count of a zeroed input) when there is no table or the caller wants
+// them all the same.  Nothing is uploaded that no kernel reads.  The compute stream waits for the copies; the caller
+// launches, calls slot_submit and clears the plan.
+struct SentPlan { PlanSlot* slot; uint32_t max_run; bool dense; };
+static int plan_send(dspsr_amd_fold* f, const char* who, uint64_t first, uint64_t last, bool try_dense, bool want_iv, SentPlan* out)
 {
   dspsr_amd_ctx* ctx = f->ctx;
-  if (f->current_hits) f->binplan.back().hits = f->current_hits;   // FoldCUDA.cu:163-164
-  f->current_hits = 0;
-  f->current_bin = f->folding_nbin;   // the plan is used up: the next one opens a fresh run (as after set_nbin)
-  PlanSlot& sl = f->slot[f->next_slot];
-  f->next_slot ^= 1;
-  if (sl.pending) {            // the fold that last used this slot (two calls ago) must have consumed it
-    const hipError_t e = hipEventSynchronize(sl.done);
-    if (e != hipSuccess) return ctx_fail(ctx, DSPSR_AMD_EHIP, "%s: %s", who, hipGetErrorString(e));
-    sl.pending = false;
-  }
-  if (!slot_reserve(sl, (size_t)f->nbin + 1, f->binplan.size())) return ctx_fail(ctx, DSPSR_AMD_ENOMEM, "%s: plan allocation failed", who);
+  const RunBin* runs = f->binplan.data();
+  const size_t niv = f->binplan.size(), nbin1 = (size_t)f->nbin + 1;
+  size_t ntab = 0;
+  bool one_per_chunk = false;
+  out->max_run = plan_scan(runs, niv, f->nbin, (uint64_t)f->nchan * f->npol * f->ndim, try_dense, first, last, f->cursor, &ntab, &one_per_chunk);
+  out->dense = one_per_chunk && out->max_run < FOLD_LONG_RUN;
+  const bool need_iv = !out->dense || want_iv;
+  const int rc = slot_acquire(f, who, &out->slot);
+  if (rc != DSPSR_AMD_OK) return rc;
+  PlanSlot& sl = *out->slot;
+  if (!slot_reserve(sl, nbin1, niv, out->dense ? ntab : 0)) return ctx_fail(ctx, DSPSR_AMD_ENOMEM, "%s: plan allocation failed", who);
+  if (need_iv) plan_bucket(runs, niv, f->nbin, sl.h_bin_start, sl.h_iv, f->cursor);
+  if (out->dense) plan_dense_fill(runs, niv, f->nbin, first, sl.h_aux, ntab);
+  const PlanCopy pc[3] = {{sl.d_bin_start, sl.h_bin_start, need_iv ? nbin1 * sizeof(uint32_t) : 0},
+                          {sl.d_iv, sl.h_iv, need_iv ? niv * sizeof(Interval) : 0},
+                          {sl.d_aux, sl.h_aux, out->dense ? ntab * sizeof(uint32_t) : 0}};
+  const hipError_t e = plan_upload(f, sl, pc, 3);
+  if (e != hipSuccess) return ctx_fail(ctx, DSPSR_AMD_EHIP, "%s: plan copy: %s", who, hipGetErrorString(e));
+  return fold_plan_wait(f, &sl);
+}
+
+// sample span covered by a closed plan (intervals are time ordered)
+static void plan_span(const dspsr_amd_fold* f, uint64_t* first, uint64_t* last)
+{
   *first = f->binplan.front().offset;
   *last = f->binplan.back().offset + f->binplan.back().hits;
+}
+
+// (fold_internal.h; the plan is not empty: the caller has looked)
+int fold_plan_to_device(dspsr_amd_fold* f, const char* who, PlanSlot** slot, uint64_t* first, uint64_t* last, uint32_t* max_run)
+{
+  plan_close(f);
+  plan_span(f, first, last);
   *first -= *first % 4;                                // keeps 16-byte alignment of the chunk loads for any ndim
-  *max_run = fold_plan_max_run(f);
-  plan_bucket(f, sl);
-  const PlanCopy pc[2] = {{sl.d_bin_start, sl.h_bin_start, ((size_t)f->nbin + 1) * sizeof(uint32_t)},
-                          {sl.d_iv, sl.h_iv, f->binplan.size() * sizeof(Interval)}};
-  const hipError_t e = plan_upload(f, sl, pc, 2);
-  if (e != hipSuccess) return ctx_fail(ctx, DSPSR_AMD_EHIP, "%s: plan copy: %s", who, hipGetErrorString(e));
-  if (fold_plan_wait(f, &sl) != DSPSR_AMD_OK) return DSPSR_AMD_EHIP;
+  SentPlan sp;
+  const int rc = plan_send(f, who, *first, *last, false, true, &sp);
+  if (rc != DSPSR_AMD_OK) return rc;
   f->binplan.clear();
-  *slot = &sl;
+  *slot = sp.slot;
+  *max_run = sp.max_run;
   return DSPSR_AMD_OK;
 }
 
@@ -1096,53 +1067,26 @@ static int fold_fold_impl(dspsr_amd_fold* f, const float* in_dev, uint64_t in_ch
     return ctx_fail(ctx, DSPSR_AMD_EINVAL, "dsp::Fold::fold folding_nbin != output->nbin (%u != %u)",
                     f->folding_nbin, f->nbin);
   if (f->binplan.empty()) return DSPSR_AMD_OK;             // send_binplan :160-161
-  if (f->current_hits) f->binplan.back().hits = f->current_hits;   // :163-164
-  f->current_hits = 0;
-  f->current_bin = f->folding_nbin;   // the plan is used up: the next one opens a fresh run (as after set_nbin)
-
-  // bucket the time-ordered intervals by phase bin (stable => time order kept inside a bin)
+  plan_close(f);
   const uint32_t nbin = f->nbin;
-  const size_t niv = f->binplan.size();
-  PlanSlot& sl = f->slot[f->next_slot];
-  f->next_slot ^= 1;
-  hipError_t e = hipSuccess;
-  if (sl.pending) {            // the fold that last used this slot (two calls ago) must have consumed it
-    e = hipEventSynchronize(sl.done);
-    if (e != hipSuccess) return ctx_fail(ctx, DSPSR_AMD_EHIP, "dspsr_amd_fold_fold: %s", hipGetErrorString(e));
-    sl.pending = false;
-  }
-  if (!slot_reserve(sl, nbin + 1, niv))
-    return ctx_fail(ctx, DSPSR_AMD_ENOMEM, "dspsr_amd_fold_fold: plan allocation failed");
-  // sample span covered by the plan (intervals are time ordered)
-  uint64_t first = f->binplan.front().offset, last = f->binplan.back().offset + f->binplan.back().hits;
+  uint64_t first, last;
+  plan_span(f, &first, &last);
   first -= first % 4;                                  // keeps 16-byte alignment of the chunk loads for any ndim
   const bool aligned = ((uintptr_t)in_dev % 16 == 0) && (in_chan_stride % 4 == 0) && (in_pol_stride % 4 == 0);
-  // the longest run and whether the plan fits the dense table (plan_scan)
-  size_t ntab = 0;
-  bool one_per_chunk = false;
-  const uint32_t max_run = plan_scan(f, aligned && nbin <= (uint32_t)FOLD_BPT * 1024, first, last, &ntab, &one_per_chunk);
-  const bool lng = aligned && nbin <= (uint32_t)FOLD_BPT * 1024 && max_run >= FOLD_LONG_RUN;   // re-associated sums (see FOLD_LONG_RUN)
-  const bool will_dense = one_per_chunk && !lng;
-  const bool need_iv = !will_dense || hits_dev;
-  if (need_iv) plan_bucket(f, sl);
-  const bool dense = will_dense;
-  if (dense && !plan_dense_fill(f, sl, first, ntab))
-    return ctx_fail(ctx, DSPSR_AMD_ENOMEM, "dspsr_amd_fold_fold: plan allocation failed");
-  {
-    const PlanCopy pc[3] = {{sl.d_bin_start, sl.h_bin_start, need_iv ? (nbin + 1) * sizeof(uint32_t) : 0},
-                            {sl.d_iv, sl.h_iv, need_iv ? niv * sizeof(Interval) : 0},
-                            {sl.d_aux, sl.h_aux, dense ? ntab * sizeof(uint32_t) : 0}};
-    e = plan_upload(f, sl, pc, 3);
-  }
-  if (e != hipSuccess) return ctx_fail(ctx, DSPSR_AMD_EHIP, "dspsr_amd_fold_fold: plan copy: %s", hipGetErrorString(e));
-  if (fold_plan_wait(f, &sl) != DSPSR_AMD_OK) return DSPSR_AMD_EHIP;
+  const bool chunked = aligned && nbin <= (uint32_t)FOLD_BPT * 1024;     // else k_fold_direct
+  SentPlan sp;
+  const int rc = plan_send(f, "dspsr_amd_fold_fold", first, last, chunked, hits_dev != nullptr, &sp);
+  if (rc != DSPSR_AMD_OK) return rc;
+  PlanSlot& sl = *sp.slot;
+  const bool lng = chunked && sp.max_run >= FOLD_LONG_RUN;               // re-associated sums (see FOLD_LONG_RUN)
+  const bool dense = sp.dense;
   const uint32_t nrow = f->npol * f->nchan;
   // exact mode: rows x bin groups, at least two workgroups per CU when the band has few channels
   uint32_t nsplit = 1;
   if (!lng)
     while (nsplit < 8 && (uint64_t)nrow * nsplit < 512 && nbin / (2 * nsplit) >= 64) nsplit *= 2;
   uint32_t threads = nbin < 1024 ? ((nbin + 63) / 64) * 64 : 1024;
-  if (aligned && nbin <= (uint32_t)FOLD_BPT * 1024) {
+  if (chunked) {
     // FOLD_BPT bins per thread: 256-thread workgroups for nbin <= 1024, so that four of them share a CU and
     // keep 4 x 32 KiB of chunk loads in flight (the kernel is HBM-latency bound per workgroup)
     const uint32_t bins_wg = (nbin + nsplit - 1) / nsplit;
@@ -1209,10 +1153,9 @@ static int fold_fold_impl(dspsr_amd_fold* f, const float* in_dev, uint64_t in_ch
   if (hits_dev)      // per-channel hits of a zeroed input: polarisation 0, first float of every planned sample
     hipLaunchKernelGGL(k_fold_count_hits, dim3((nbin + 255) / 256, f->nchan), dim3(256), 0, ctx->stream, in_dev, in_chan_stride, f->ndim,
                        hits_dev, nbin, sl.d_bin_start, sl.d_iv);
-  e = hipGetLastError();
-  if (e == hipSuccess) e = hipEventRecord(sl.done, ctx->stream);
+  const hipError_t e = hipGetLastError();
   if (e != hipSuccess) return ctx_fail(ctx, DSPSR_AMD_EHIP, "dspsr_amd_fold_fold: %s", hipGetErrorString(e));
-  sl.pending = true;
+  if (slot_submit(f, "dspsr_amd_fold_fold", sl) != DSPSR_AMD_OK) return DSPSR_AMD_EHIP;
   f->binplan.clear();
   return DSPSR_AMD_OK;
 }
@@ -1229,10 +1172,9 @@ static int fold_many_group(dspsr_amd_fold* const* g, uint32_t n, const float* in
   uint64_t first = ~0ull, last = 0;
   for (uint32_t k = 0; k < n; k++) {
     dspsr_amd_fold* f = g[k];
-    if (f->current_hits) f->binplan.back().hits = f->current_hits;   // FoldCUDA.cu:163-164
-    f->current_hits = 0;
-    f->current_bin = f->folding_nbin;
-    const uint64_t a = f->binplan.front().offset, b = f->binplan.back().offset + f->binplan.back().hits;
+    plan_close(f);
+    uint64_t a, b;
+    plan_span(f, &a, &b);
     if (a < first) first = a;
     if (b > last) last = b;
   }
@@ -1244,35 +1186,16 @@ static int fold_many_group(dspsr_amd_fold* const* g, uint32_t n, const float* in
   for (uint32_t k = 0; k < n; k++) {
     dspsr_amd_fold* f = g[k];
     const uint32_t nbin = f->nbin;
-    PlanSlot& sl = f->slot[f->next_slot];
-    f->next_slot ^= 1;
-    if (sl.pending) {            // the fold that last used this slot (two calls ago) must have consumed it
-      const hipError_t e = hipEventSynchronize(sl.done);
-      if (e != hipSuccess) return ctx_fail(ctx, DSPSR_AMD_EHIP, "dspsr_amd_fold_fold_many: %s", hipGetErrorString(e));
-      sl.pending = false;
-    }
-    if (!slot_reserve(sl, nbin + 1, f->binplan.size()))
-      return ctx_fail(ctx, DSPSR_AMD_ENOMEM, "dspsr_amd_fold_fold_many: plan allocation failed");
-    size_t ntab = 0;
-    bool dense = false;
-    (void)plan_scan(f, true, first, last, &ntab, &dense);
-    if (dense) {
-      if (!plan_dense_fill(f, sl, first, ntab)) return ctx_fail(ctx, DSPSR_AMD_ENOMEM, "dspsr_amd_fold_fold_many: plan allocation failed");
-    } else {
-      plan_bucket(f, sl);
-    }
-    const PlanCopy pc[3] = {{sl.d_bin_start, sl.h_bin_start, dense ? 0 : (nbin + 1) * sizeof(uint32_t)},
-                            {sl.d_iv, sl.h_iv, dense ? 0 : f->binplan.size() * sizeof(Interval)},
-                            {sl.d_aux, sl.h_aux, dense ? ntab * sizeof(uint32_t) : 0}};
-    const hipError_t e = plan_upload(f, sl, pc, 3);
-    if (e != hipSuccess) return ctx_fail(ctx, DSPSR_AMD_EHIP, "dspsr_amd_fold_fold_many: plan copy: %s", hipGetErrorString(e));
-    if (fold_plan_wait(f, &sl) != DSPSR_AMD_OK) return DSPSR_AMD_EHIP;
+    SentPlan sp;                   // the dense table over the group's chunk grid, or the bucketed plan
+    const int rc = plan_send(f, "dspsr_amd_fold_fold_many", first, last, true, false, &sp);
+    if (rc != DSPSR_AMD_OK) return rc;
+    PlanSlot& sl = *sp.slot;
     FoldManyPlan& p = args.p[k];
     p.prof = f->profile;
     p.span = f->span;
     p.bin_start = sl.d_bin_start;
     p.iv = sl.d_iv;
-    p.tab = dense ? sl.d_aux : nullptr;
+    p.tab = sp.dense ? sl.d_aux : nullptr;
     p.nbin = nbin;
     p.slot0 = nslot;
     nslot += nbin;
@@ -1303,13 +1226,13 @@ static int fold_many_group(dspsr_amd_fold* const* g, uint32_t n, const float* in
   else if (nrw == 4) FOLD_MANY(1, 4);
   else FOLD_MANY(1, 1);
 #undef FOLD_MANY
-  hipError_t e = hipGetLastError();
-  for (uint32_t k = 0; k < n && e == hipSuccess; k++) {
-    e = hipEventRecord(used[k]->done, ctx->stream);
-    if (e == hipSuccess) used[k]->pending = true;
-    g[k]->binplan.clear();
-  }
+  const hipError_t e = hipGetLastError();
   if (e != hipSuccess) return ctx_fail(ctx, DSPSR_AMD_EHIP, "dspsr_amd_fold_fold_many: %s", hipGetErrorString(e));
+  for (uint32_t k = 0; k < n; k++) {
+    const int rc = slot_submit(g[k], "dspsr_amd_fold_fold_many", *used[k]);
+    g[k]->binplan.clear();
+    if (rc != DSPSR_AMD_OK) return rc;
+  }
   return DSPSR_AMD_OK;
 }
 
@@ -1379,85 +1302,28 @@ extern "C" int dspsr_amd_fold_synch(dspsr_amd_fold* f, float* profile_host)   //
 int fold_build_part_plan(dspsr_amd_fold* f, uint32_t nkeep, uint32_t npart, const uint32_t** d_start,
                          const Interval** d_iv, PlanSlot** slot)
 {
-  // Layout on the device (one uint32 array + the interval array):
-  //   start[0 .. npart]                  : first active-bin entry of every part (start[npart] = total)
-  //   start[align4(npart+1) + 4*e + 0..3] : entry e = { bin, first interval, count << 16 | hits0, offset0 }
-  // Only the phase bins that receive samples in a part are listed, so a workgroup finds its work with two
-  // dependent loads (entry, then interval + accumulator) instead of walking all nbin bins.
   dspsr_amd_ctx* ctx = f->ctx;
-  if (f->current_hits && !f->binplan.empty()) f->binplan.back().hits = f->current_hits;   // FoldCUDA.cu:163-164
-  f->current_hits = 0;
-  f->current_bin = f->folding_nbin;                                        // (the next plan opens a fresh run)
-  const uint32_t nbin = f->nbin;
-  // count the pieces: a run is cut at every multiple of nkeep
-  size_t npiece = 0;
-  for (const RunBin& r : f->binplan) {
-    if (!r.hits) continue;
-    const uint64_t p0 = r.offset / nkeep, p1 = (r.offset + r.hits - 1) / nkeep;
-    if (p1 >= npart)
-      return ctx_fail(ctx, DSPSR_AMD_EINVAL, "fused fold: plan sample %llu lies beyond the %u parts of this call",
-                      (unsigned long long)(r.offset + r.hits - 1), npart);
-    npiece += (size_t)(p1 - p0 + 1);
-  }
-  auto for_each_piece = [&](auto&& fn) {
-    for (const RunBin& r : f->binplan) {
-      uint64_t off = r.offset, left = r.hits;
-      while (left) {
-        const uint64_t part = off / nkeep, within = off % nkeep;
-        const uint64_t n = left < nkeep - within ? left : nkeep - within;
-        fn((uint32_t)part, r.ibin, within, (uint32_t)n);
-        off += n; left -= n;
-      }
-    }
-  };
-  // bucket the pieces by (part, bin), time order kept inside a bucket
-  const size_t nb1 = (size_t)npart * nbin;
-  std::vector<uint32_t>& cnt = f->cursor;
-  cnt.assign(nb1 + 1, 0u);
-  for_each_piece([&](uint32_t part, uint32_t ibin, uint64_t, uint32_t) { cnt[(size_t)part * nbin + ibin + 1]++; });
-  size_t nentry = 0;
-  for (size_t i = 0; i < nb1; i++) { if (cnt[i + 1]) nentry++; cnt[i + 1] += cnt[i]; }     // cnt[i] = first interval of bucket i
-  PlanSlot& sl = f->slot[f->next_slot];
-  f->next_slot ^= 1;
-  if (sl.pending) {
-    hipError_t e = hipEventSynchronize(sl.done);
-    if (e != hipSuccess) return ctx_fail(ctx, DSPSR_AMD_EHIP, "fused fold: %s", hipGetErrorString(e));
-    sl.pending = false;
-  }
-  const size_t ent_off = ((size_t)npart + 1 + 3) & ~(size_t)3;         // entries are 16-byte aligned uint4
-  const size_t nwords = ent_off + 4 * nentry;
-  if (!slot_reserve(sl, nwords, npiece ? npiece : 1))
+  plan_close(f);
+  const RunBin* runs = f->binplan.data();
+  const size_t nrun = f->binplan.size();
+  PartPlanSize sz;
+  uint64_t beyond = 0;
+  if (!part_plan_count(runs, nrun, nkeep, npart, f->nbin, f->cursor, &sz, &beyond))
+    return ctx_fail(ctx, DSPSR_AMD_EINVAL, "fused fold: plan sample %llu lies beyond the %u parts of this call",
+                    (unsigned long long)beyond, npart);
+  PlanSlot* sl = nullptr;
+  const int rc = slot_acquire(f, "fused fold", &sl);
+  if (rc != DSPSR_AMD_OK) return rc;
+  if (!slot_reserve(*sl, sz.nwords, sz.npiece ? sz.npiece : 1, 0))
     return ctx_fail(ctx, DSPSR_AMD_ENOMEM, "fused fold: plan allocation failed");
-  std::vector<uint32_t> fill(cnt.begin(), cnt.end() - 1);
-  for_each_piece([&](uint32_t part, uint32_t ibin, uint64_t within, uint32_t n) {
-    Interval v; v.offset = within; v.hits = n; v.pad = 0;
-    sl.h_iv[fill[(size_t)part * nbin + ibin]++] = v;
-  });
-  uint32_t* st = sl.h_bin_start;
-  uint32_t* ent = st + ent_off;
-  for (size_t i = npart + 1; i < ent_off; i++) st[i] = 0;
-  size_t e = 0;
-  for (uint32_t part = 0; part < npart; part++) {
-    st[part] = (uint32_t)e;
-    for (uint32_t b = 0; b < nbin; b++) {
-      const size_t i = (size_t)part * nbin + b;
-      const uint32_t n = cnt[i + 1] - cnt[i];
-      if (!n) continue;
-      const Interval& first = sl.h_iv[cnt[i]];
-      // {bin, first interval index, count << 16 | hits of the first interval, offset of the first interval}:
-      // count, hits and offsets are < nkeep <= 8192 on the three-pass path
-      ent[4 * e] = b; ent[4 * e + 1] = cnt[i]; ent[4 * e + 2] = (n << 16) | first.hits; ent[4 * e + 3] = (uint32_t)first.offset;
-      e++;
-    }
-  }
-  st[npart] = (uint32_t)e;
-  const PlanCopy pc[2] = {{sl.d_bin_start, sl.h_bin_start, nwords * sizeof(uint32_t)}, {sl.d_iv, sl.h_iv, npiece * sizeof(Interval)}};
-  const hipError_t er = plan_upload(f, sl, pc, 2);      // the caller waits (fold_plan_wait) in front of the kernel that reads it
-  if (er != hipSuccess) return ctx_fail(ctx, DSPSR_AMD_EHIP, "fused fold: plan copy: %s", hipGetErrorString(er));
+  part_plan_fill(runs, nrun, nkeep, npart, f->nbin, f->cursor, sl->h_bin_start, sl->h_iv);
+  const PlanCopy pc[2] = {{sl->d_bin_start, sl->h_bin_start, sz.nwords * sizeof(uint32_t)}, {sl->d_iv, sl->h_iv, sz.npiece * sizeof(Interval)}};
+  const hipError_t e = plan_upload(f, *sl, pc, 2);      // the caller waits (fold_plan_wait) in front of the kernel that reads it
+  if (e != hipSuccess) return ctx_fail(ctx, DSPSR_AMD_EHIP, "fused fold: plan copy: %s", hipGetErrorString(e));
   f->binplan.clear();
-  *d_start = sl.d_bin_start;
-  *d_iv = sl.d_iv;
-  *slot = &sl;
+  *d_start = sl->d_bin_start;
+  *d_iv = sl->d_iv;
+  *slot = sl;
   return DSPSR_AMD_OK;
 }
 
@@ -1476,83 +1342,31 @@ int fold_combine_partials(dspsr_amd_fold* f, const float* part, uint32_t nseg, u
   return DSPSR_AMD_OK;
 }
 
-int fold_part_plan_submitted(dspsr_amd_fold* f, PlanSlot* slot)
-{
-  hipError_t e = hipEventRecord(slot->done, f->ctx->stream);
-  if (e != hipSuccess) return ctx_fail(f->ctx, DSPSR_AMD_EHIP, "fused fold: %s", hipGetErrorString(e));
-  slot->pending = true;
-  return DSPSR_AMD_OK;
-}
-
 int fold_build_segment_plan(dspsr_amd_fold* f, uint64_t ndat, uint32_t seg, bool* ok, const uint32_t** d_run_off,
                             const uint32_t** d_blk_first, const uint32_t** d_bin_start, const Interval** d_iv, PlanSlot** slot)
 {
   dspsr_amd_ctx* ctx = f->ctx;
   *ok = false;
-  if (f->binplan.empty() || ndat == 0 || ndat >= (1ull << 32)) return DSPSR_AMD_OK;
-  // (the open run's hits are final only once the plan is consumed: look at them without closing it)
   const size_t nrun = f->binplan.size();
-  auto hits_of = [&](size_t i) { return i + 1 == nrun && f->current_hits ? f->current_hits : f->binplan[i].hits; };
-  uint64_t expect = 0;
-  for (size_t i = 0; i < nrun; i++) {
-    const RunBin& r = f->binplan[i];
-    const uint32_t h = hits_of(i);
-    if (r.offset != expect || h == 0) return DSPSR_AMD_OK;                 // a gap (dropped samples) or an offset start
-    if (i > 0 && i + 1 < nrun && h < seg) return DSPSR_AMD_OK;             // an inner interval shorter than a segment
-    expect += h;
-  }
-  if (expect != ndat) return DSPSR_AMD_OK;
-  if (f->current_hits) f->binplan.back().hits = f->current_hits;           // FoldCUDA.cu:163-164
-  f->current_hits = 0;
-  f->current_bin = f->folding_nbin;                                        // (the next plan opens a fresh run)
+  if (!segment_plan_qualifies(f->binplan.data(), nrun, f->current_hits, ndat, seg)) return DSPSR_AMD_OK;
+  plan_close(f);
   const uint32_t nbin = f->nbin;
-  PlanSlot& sl = f->slot[f->next_slot];
-  f->next_slot ^= 1;
-  if (sl.pending) {
-    const hipError_t e = hipEventSynchronize(sl.done);
-    if (e != hipSuccess) return ctx_fail(ctx, DSPSR_AMD_EHIP, "fused fold: %s", hipGetErrorString(e));
-    sl.pending = false;
-  }
-  const size_t nblk = (size_t)(ndat >> 10) + 1, naux = nrun + 1 + nblk;
-  if (!slot_reserve(sl, nbin + 1, nrun)) return ctx_fail(ctx, DSPSR_AMD_ENOMEM, "fused fold: plan allocation failed");
-  if (naux > sl.aux_cap) {
-    if (sl.h_aux) (void)hipHostFree(sl.h_aux);
-    if (sl.d_aux) (void)hipFree(sl.d_aux);
-    sl.h_aux = nullptr; sl.d_aux = nullptr; sl.aux_cap = 0;
-    const size_t n = naux + naux / 2 + 16;
-    if (hipHostMalloc((void**)&sl.h_aux, n * sizeof(uint32_t)) != hipSuccess || hipMalloc((void**)&sl.d_aux, n * sizeof(uint32_t)) != hipSuccess)
-      return ctx_fail(ctx, DSPSR_AMD_ENOMEM, "fused fold: plan allocation failed");
-    sl.aux_cap = n;
-  }
-  uint32_t* off = sl.h_aux;
-  uint32_t* blk = sl.h_aux + nrun + 1;
-  for (size_t i = 0; i < nrun; i++) off[i] = (uint32_t)f->binplan[i].offset;
-  off[nrun] = (uint32_t)ndat;
-  size_t q = 0;
-  for (size_t i = 0; i < nblk; i++) {
-    const uint64_t s0 = (uint64_t)i << 10;
-    while (q + 1 < nrun && off[q + 1] <= s0) q++;
-    blk[i] = (uint32_t)q;
-  }
-  // the same intervals bucketed by phase bin, time order kept inside a bin (as dspsr_amd_fold_fold)
-  for (uint32_t b = 0; b <= nbin; b++) sl.h_bin_start[b] = 0;
-  for (const RunBin& r : f->binplan) sl.h_bin_start[r.ibin + 1]++;
-  for (uint32_t b = 0; b < nbin; b++) sl.h_bin_start[b + 1] += sl.h_bin_start[b];
-  f->cursor.assign(sl.h_bin_start, sl.h_bin_start + nbin);
-  for (const RunBin& r : f->binplan) {
-    Interval v; v.offset = r.offset; v.hits = r.hits; v.pad = 0;
-    sl.h_iv[f->cursor[r.ibin]++] = v;
-  }
-  const PlanCopy pc[3] = {{sl.d_aux, sl.h_aux, naux * sizeof(uint32_t)}, {sl.d_bin_start, sl.h_bin_start, (nbin + 1) * sizeof(uint32_t)},
-                          {sl.d_iv, sl.h_iv, nrun * sizeof(Interval)}};
-  hipError_t e = plan_upload(f, sl, pc, 3);             // the caller waits (fold_plan_wait) in front of the kernel that reads it
+  PlanSlot* sl = nullptr;
+  const int rc = slot_acquire(f, "fused fold", &sl);
+  if (rc != DSPSR_AMD_OK) return rc;
+  const size_t naux = nrun + 1 + segment_plan_nblk(ndat);
+  if (!slot_reserve(*sl, (size_t)nbin + 1, nrun, naux)) return ctx_fail(ctx, DSPSR_AMD_ENOMEM, "fused fold: plan allocation failed");
+  segment_plan_fill(f->binplan.data(), nrun, nbin, ndat, sl->h_aux, sl->h_aux + nrun + 1, sl->h_bin_start, sl->h_iv, f->cursor);
+  const PlanCopy pc[3] = {{sl->d_aux, sl->h_aux, naux * sizeof(uint32_t)}, {sl->d_bin_start, sl->h_bin_start, ((size_t)nbin + 1) * sizeof(uint32_t)},
+                          {sl->d_iv, sl->h_iv, nrun * sizeof(Interval)}};
+  const hipError_t e = plan_upload(f, *sl, pc, 3);      // the caller waits (fold_plan_wait) in front of the kernel that reads it
   if (e != hipSuccess) return ctx_fail(ctx, DSPSR_AMD_EHIP, "fused fold: plan copy: %s", hipGetErrorString(e));
   f->binplan.clear();
-  *d_run_off = sl.d_aux;
-  *d_blk_first = sl.d_aux + nrun + 1;
-  *d_bin_start = sl.d_bin_start;
-  *d_iv = sl.d_iv;
-  *slot = &sl;
+  *d_run_off = sl->d_aux;
+  *d_blk_first = sl->d_aux + nrun + 1;
+  *d_bin_start = sl->d_bin_start;
+  *d_iv = sl->d_iv;
+  *slot = sl;
   *ok = true;
   return DSPSR_AMD_OK;
 }

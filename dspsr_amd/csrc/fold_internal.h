@@ -3,27 +3,35 @@
 #include <vector>
 
 #include "engine_internal.h"
+#include "fold_plan.h"
 
 namespace dspsr_amd {
-struct Interval { uint64_t offset; uint32_t hits; uint32_t pad; };   // sorted by (bin, time)
-struct RunBin { uint32_t ibin, hits; uint64_t offset; };             // FoldCUDA.h:19-24
 // one run of the plan recurrence without walking its samples (host_prep.cpp)
 uint64_t fold_plan_run(double* phi_io, double pps, double double_nbin, uint64_t nmax, uint32_t* ibin_out);
 }  // namespace dspsr_amd
 
-// device plan, double-buffered so that building/uploading the plan of block i+1 never waits for
-// the fold kernel of block i (pinned staging => the H2D copies are truly asynchronous)
+// A plan on the device.  Every consumer of the pending run-length plan (the stand-alone fold, fold_many, the fourth moments,
+// the fused part plan, the four-pass segment plan) takes it through the same steps, each written once in fold.hip:
+//   plan_close      the open run gets its hits; the next plan opens a fresh run
+//   slot_acquire    the engine's next slot; when its last consumer is still pending, the host waits for `done` -- the pinned
+//                   staging and the device copy of a slot are never rewritten before that
+//   slot_reserve    the three buffer pairs, grown where the plan needs more
+//   fold_plan.h     a builder fills the pinned staging
+//   plan_upload     the copies, on the fold's upload stream, then `ready`
+//   fold_plan_wait  the compute stream waits for `ready`, right in front of the first kernel that reads the plan
+//   fold_part_plan_submitted   behind the last such kernel: `done` recorded on the compute stream, then pending = true
+// Two slots, so that building and uploading the plan of block i+1 never waits for the fold kernel of block i (pinned staging
+// => the H2D copies are truly asynchronous).  An empty plan, and a segment plan that does not qualify, take no slot.
 struct PlanSlot {
-  uint32_t* h_bin_start = nullptr;   // pinned
-  dspsr_amd::Interval* h_iv = nullptr;          // pinned
+  uint32_t* h_bin_start = nullptr;   // pinned: bin_start[nbin + 1], or the fused part plan's start[] and entries
   uint32_t* d_bin_start = nullptr;
+  dspsr_amd::Interval* h_iv = nullptr;          // pinned
   dspsr_amd::Interval* d_iv = nullptr;
-  size_t bin_cap = 0, iv_cap = 0;
-  uint32_t* h_aux = nullptr;         // pinned: time-ordered interval offsets + their index per 1024 samples (segment plan)
+  uint32_t* h_aux = nullptr;         // pinned: the dense table, or the segment plan's run_off and blk_first
   uint32_t* d_aux = nullptr;
-  size_t aux_cap = 0;
-  hipEvent_t done = nullptr;
-  bool pending = false;
+  size_t bin_cap = 0, iv_cap = 0, aux_cap = 0;
+  hipEvent_t done = nullptr;         // the last consumer has read the plan
+  bool pending = false;              // `done` is recorded and not yet waited for
   hipEvent_t ready = nullptr;        // the plan's copies (issued on the fold's upload stream) have landed
 };
 
@@ -46,42 +54,28 @@ struct dspsr_amd_fold {
   std::vector<uint32_t> cursor;
 };
 
-
-// Longest run of the pending plan (samples that go to one phase bin in a row).  Runs of FOLD_LONG_RUN samples or more are
-// folded with re-associated sums (fold.hip, k_fold_chunked<., true>); the fused filterbank kernel only has the exact
-// time-order fold, so such plans take the separate Detection + Fold launches.
-constexpr uint32_t FOLD_LONG_RUN_HOST = 64;
 // The fused kernel adds a bin's samples one after the other (exact time order): a run of n samples is a dependent chain of n
 // float4 adds on one thread, about 16 cycles each.  Up to this length that still costs less than the detected round trip
 // through HBM (headline geometry, ms per block fused / separate: 34-sample runs 4.99 / 5.93, 136: 5.14 / 6.01, 545: 5.42 /
 // 5.85, 1090: 6.39 / 5.98; tools/exp_fused_runs.py); beyond it the plan takes the separate launches and the long-run fold.
 constexpr uint32_t FOLD_FUSED_MAX_RUN = 640;
+// Longest run of the pending plan, open or closed (against FOLD_LONG_RUN of fold_plan.h and FOLD_FUSED_MAX_RUN)
 static inline uint32_t fold_plan_max_run(const dspsr_amd_fold* f)
 {
-  uint32_t m = f->current_hits;
-  for (const dspsr_amd::RunBin& r : f->binplan) if (r.hits > m) m = r.hits;
-  return m;
+  return dspsr_amd::plan_max_run(f->binplan.data(), f->binplan.size(), f->current_hits);
 }
 
-// Fused path (filterbank.hip): turns the pending run-length plan into a per-part plan on the device --
-// runs split at multiples of `nkeep`, bucketed by (part, bin), offsets relative to the start of the part.
-// start[0..npart] = first active-bin entry of each part, followed (16-byte aligned) by the entries
-// {bin, first interval, count << 16 | hits0, offset0} indexing `iv`.  nkeep must be < 65536.  The plan is
-// consumed (cleared).
-// fold_part_plan_submitted() must be called after the kernels that read the plan have been enqueued.
+// Fused path (filterbank.hip): the pending plan as the per-part plan of fold_plan.h on the device (*d_start, *d_iv).  The plan
+// is consumed (cleared); fold_part_plan_submitted() must be called after the kernels that read it have been enqueued.
 int fold_build_part_plan(dspsr_amd_fold* f, uint32_t nkeep, uint32_t npart, const uint32_t** d_start,
                          const dspsr_amd::Interval** d_iv, PlanSlot** slot);
 // the compute stream waits until the plan in `slot` has landed (call right in front of the first kernel that reads it)
 int fold_plan_wait(dspsr_amd_fold* f, PlanSlot* slot);
 int fold_part_plan_submitted(dspsr_amd_fold* f, PlanSlot* slot);
 
-// Four-pass fused fold (filterbank.hip k_inv_b<., true>): the pending plan must cover samples [0, ndat) without gaps and
-// every interval but the first and the last must hold at least `seg` samples (so that a `seg`-sample run of the last
-// inverse pass is cut by at most one phase-bin boundary).  *ok = false: the plan does not qualify and is left pending (the
-// caller takes Detection + Fold).  Otherwise the plan is consumed: on the device
-//   run_off[0 .. nrun]            start offsets of the time-ordered intervals, run_off[nrun] = ndat
-//   blk_first[0 .. ndat/1024]     index of the interval that holds sample 1024*i
-//   bin_start / iv                the same intervals bucketed by phase bin (time ordered inside a bin), as for k_fold_chunked
+// Four-pass fused fold (fb_four_pass.hip k_inv_b<., true>): the pending plan as the segment plan of fold_plan.h on the device.
+// *ok = false: the plan does not qualify (segment_plan_qualifies) and is left pending (the caller takes Detection + Fold).
+// Otherwise the plan is consumed.
 int fold_build_segment_plan(dspsr_amd_fold* f, uint64_t ndat, uint32_t seg, bool* ok, const uint32_t** d_run_off,
                             const uint32_t** d_blk_first, const uint32_t** d_bin_start, const dspsr_amd::Interval** d_iv, PlanSlot** slot);
 // profile[chan0 + c][bin] += the segment piece sums of the bin's intervals, in time order (c < nchan).

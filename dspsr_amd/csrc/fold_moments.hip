@@ -306,7 +306,7 @@ int fold_moments_run(dspsr_amd_fold* f, const float* in_dev, uint64_t in_chan_st
   int rc = fold_plan_to_device(f, who, &sl, &first, &last, &max_run);
   if (rc != DSPSR_AMD_OK) return rc;
   const uint32_t nbin = f->nbin, nchan = f->nchan;
-  const bool lng = max_run >= FOLD_LONG_RUN_HOST;
+  const bool lng = max_run >= FOLD_LONG_RUN;
   const uint32_t vec = ((uintptr_t)in_dev % 16 == 0 && in_chan_stride % 4 == 0) ? 1u : 0u;
   // bin groups: enough for MOM_BPT bins per thread, and (as fold_fold_impl splits the bins) more when the band has few channels
   uint32_t ngroup = (nbin + MOM_BPT * MOM_THREADS - 1) / (MOM_BPT * MOM_THREADS);

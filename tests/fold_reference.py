@@ -13,10 +13,10 @@ detected samples [nchan][npol][ndat][ndim] (sample idat of a row at rows[:, :, i
 """
 import numpy as np
 
-FOLD_CHUNK = 2048        # samples per chunk (fold.hip FOLD_CHUNK)
+FOLD_CHUNK = 2048        # samples per chunk (fold_plan.h FOLD_CHUNK)
 FOLD_MB = 32             # samples per micro-block (fold.hip FOLD_MB)
 FOLD_BPT = 4             # bins per thread (fold.hip FOLD_BPT)
-FOLD_LONG_RUN = 64       # a run this long selects the LONG path (fold_internal.h FOLD_LONG_RUN_HOST)
+FOLD_LONG_RUN = 64       # a run this long selects the LONG path (fold_plan.h FOLD_LONG_RUN)
 
 
 def runs_of_plan(plan, idat_start=0):
@@ -129,19 +129,20 @@ def fold_long_model(rows, runs, prof, nrow, ncu):
 
 
 def fold_dispatch(addr, chan_stride, pol_stride, nchan, npol, ndim, nbin, runs, ncu):
-    """fold.hip fold_fold_impl's choice for a call: `addr` the input's byte address, strides in floats.  Returns a dict:
+    """fold.hip fold_fold_impl's choice for a call (the comments name its variables; plan_scan is fold_plan.h's): `addr` the
+    input's byte address, strides in floats.  Returns a dict:
     kernel ('direct' | 'chunked' | 'long' | 'dense'), ndim, nrow (NROW), nsplit (exact kernels, grid.z), nseg and cps (LONG),
     threads."""
     runs = np.asarray(runs, np.int64).reshape(-1, 3)
     first, last = plan_span(runs)
-    aligned = addr % 16 == 0 and chan_stride % 4 == 0 and pol_stride % 4 == 0                      # fold.hip:820
+    aligned = addr % 16 == 0 and chan_stride % 4 == 0 and pol_stride % 4 == 0                      # `aligned`
     fits = nbin <= FOLD_BPT * 1024
     nchunk = (last - first + FOLD_CHUNK - 1) // FOLD_CHUNK
-    one_per_chunk = aligned and fits                                                                 # :828-835
+    one_per_chunk = aligned and fits                                                                 # plan_scan: the table's size
     if one_per_chunk:
         ntab = nchunk * nbin
         one_per_chunk = ntab <= (1 << 24) and 4 * ntab <= (last - first) * nchan * npol * ndim
-    if one_per_chunk:                                                                                # :836-845
+    if one_per_chunk:                                                                                # plan_scan: the walk
         lastc = {}
         for off, b, n in runs:
             if n == 0:
@@ -152,20 +153,20 @@ def fold_dispatch(addr, chan_stride, pol_stride, nchan, npol, ndim, nbin, runs, 
                 break
             lastc[int(b)] = c1
     max_run = int(runs[:, 2].max())
-    lng = aligned and fits and max_run >= FOLD_LONG_RUN                                              # :849
+    lng = aligned and fits and max_run >= FOLD_LONG_RUN                                              # `lng`
     dense = one_per_chunk and not lng
     nrow_all = nchan * npol
     nsplit = 1
-    if not lng:                                                                                      # :901-902
+    if not lng:                                                                                      # `nsplit`
         while nsplit < 8 and nrow_all * nsplit < 512 and nbin // (2 * nsplit) >= 64:
             nsplit *= 2
     threads = ((nbin + 63) // 64) * 64 if nbin < 1024 else 1024
-    if not (aligned and fits):                                                                       # :962-973
+    if not (aligned and fits):                                                                       # k_fold_direct
         return dict(kernel="direct", ndim=ndim, nrow=1, nsplit=nsplit, nseg=1, cps=nchunk, threads=threads)
-    bins_wg = (nbin + nsplit - 1) // nsplit                                                          # :907-910
+    bins_wg = (nbin + nsplit - 1) // nsplit                                                          # `threads`
     threads = min(1024, max(256, ((bins_wg + FOLD_BPT - 1) // FOLD_BPT + 63) // 64 * 64))
-    nseg, cps = long_segments(nchunk, nrow_all, ncu) if lng else (1, nchunk)                         # :912-920
-    nrw = npol if (ndim * npol == 4 and ndim < 4 and nchan * (nseg if lng else nsplit) >= 2 * ncu) else 1   # :933-934
+    nseg, cps = long_segments(nchunk, nrow_all, ncu) if lng else (1, nchunk)                         # `nseg`, `cps`
+    nrw = npol if (ndim * npol == 4 and ndim < 4 and nchan * (nseg if lng else nsplit) >= 2 * ncu) else 1   # `nrw`
     kernel = "dense" if dense else ("long" if lng else "chunked")
     return dict(kernel=kernel, ndim=ndim, nrow=nrw, nsplit=1 if lng else nsplit, nseg=nseg, cps=cps, threads=threads)
 

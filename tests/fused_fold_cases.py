@@ -1,6 +1,6 @@
 """The fold inside the last filterbank pass (dspsr_amd_filterbank_perform_fold: k_inv_chan<., FOLD> of csrc/fb_inv_chan.h, its
-two-pass twin k_rows_inv<., ., FOLD> of csrc/fb_two_pass.hip, fb_launch_fused of csrc/filterbank.hip, fold_build_part_plan and
-fold_combine_partials of csrc/fold.hip): the host's geometry and launch arithmetic restated, and the cases of
+two-pass twin k_rows_inv<., ., FOLD> of csrc/fb_two_pass.hip, fb_launch_fused of csrc/filterbank.hip, the part plan of csrc/fold_plan.h
+and fold_combine_partials of csrc/fold.hip): the host's geometry and launch arithmetic restated, and the cases of
 tests/test_gpu_fused_fold.py as plain data with a computed record of the branches each one reaches.  No torch: the host test
 tests/test_fused_fold_cases_host.py checks on a machine without a GPU that every case reaches what its name says.
 
@@ -156,8 +156,8 @@ def hand_runs(pieces):
 
 
 def part_plan(runs, nkeep, npart, nbin):
-    """fold.hip fold_build_part_plan restated: per part the list of active bins, each with its intervals (offset in the part,
-    hits) in time order -- runs cut at every multiple of nkeep, bucketed by (part, bin)"""
+    """fold_plan.h part_plan_count / part_plan_fill restated (tests/test_fold_plan_host.py compares the two): per part the
+    list of active bins, each with its intervals (offset in the part, hits) in time order -- runs cut at every multiple of nkeep, bucketed by (part, bin)"""
     parts = [dict() for _ in range(npart)]
     for off, b, n in np.asarray(runs, np.int64).reshape(-1, 3):
         off, left = int(off), int(n)

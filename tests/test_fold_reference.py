@@ -121,7 +121,7 @@ def _periodic(nbin, spb, ndat, start=0):
 
 
 def test_dispatch_worked_cases():
-    # longest run 63 / 64 (fold.hip:849)
+    # longest run 63 / 64 (fold_fold_impl `lng`)
     r63 = [(0, 0, 63), (63, 1, 10), (73, 0, 5000)]
     assert _case(64, [(0, 0, 63), (63, 1, 1)] * 1)["kernel"] != "long"
     assert _case(64, r63)["kernel"] == "long"
@@ -129,26 +129,26 @@ def test_dispatch_worked_cases():
     longr = short[:-1] + [(short[-1][0], short[-1][1], 64)]
     assert _case(40, short, nchan=64)["kernel"] in ("chunked", "dense")
     assert _case(40, longr, nchan=64)["kernel"] == "long"
-    # nbin 4096 / 4097 (:828, :849, :904)
+    # nbin 4096 / 4097 (`chunked`)
     runs = _periodic(4097, 2, 40000)
     assert _case(4096, [(o, b % 4096, n) for o, b, n in runs], nchan=600)["kernel"] in ("chunked", "dense")
     assert _case(4097, runs, nchan=600)["kernel"] == "direct"
-    # one run per (chunk, bin) or two (:836-845): period 64 x 40 = 2560 > FOLD_CHUNK, and 64 x 20 = 1280 < FOLD_CHUNK
+    # one run per (chunk, bin) or two (plan_scan): period 64 x 40 = 2560 > FOLD_CHUNK, and 64 x 20 = 1280 < FOLD_CHUNK
     assert _case(64, _periodic(64, 40, 30000), nchan=8)["kernel"] == "dense"
     assert _case(64, _periodic(64, 20, 30000), nchan=8)["kernel"] == "chunked"
-    # dense table size (:834): 4 * ntab <= data words -- 10 chunks x 512 bins against 20480 / 20479 samples of one row
+    # dense table size (plan_scan): 4 * ntab <= data words -- 10 chunks x 512 bins against 20480 / 20479 samples of one row
     assert _case(512, _periodic(512, 20, 20480), nchan=1, ndim=1)["kernel"] == "dense"
     assert _case(512, _periodic(512, 20, 20479), nchan=1, ndim=1, ps=20480)["kernel"] == "chunked"
-    # ... and ntab <= 2^24 (:834): 4096 chunks x 4096 bins fit, one more chunk does not
+    # ... and ntab <= 2^24 (plan_scan): 4096 chunks x 4096 bins fit, one more chunk does not
     assert _case(4096, _periodic(4096, 63, 4096 * FOLD_CHUNK), nchan=4)["kernel"] == "dense"
     assert _case(4096, _periodic(4096, 63, 4096 * FOLD_CHUNK + 1), nchan=4)["kernel"] == "chunked"
-    # alignment (:820): address, channel stride, polarisation stride
+    # alignment (`aligned`): address, channel stride, polarisation stride
     base = _periodic(64, 40, 30000)
     assert _case(64, base, nchan=8, addr=4)["kernel"] == "direct"
     assert _case(64, base, nchan=8, addr=16)["kernel"] == "dense"
     assert _case(64, base, nchan=8, cs=30000 * 4 + 2)["kernel"] == "direct"
     assert _case(64, base, nchan=8, npol=2, ndim=2, ps=30000 * 2 + 1)["kernel"] == "direct"
-    # bin split and threads (:900-910)
+    # bin split and threads (`nsplit`, `threads`)
     assert _case(512, _periodic(512, 3, 8000), nchan=2)["nsplit"] == 8
     assert _case(512, _periodic(512, 3, 8000), nchan=2)["threads"] == 256
     c = _case(4096, _periodic(4096, 1, 8000), nchan=130, npol=2, ndim=2)
@@ -156,12 +156,12 @@ def test_dispatch_worked_cases():
     c = _case(4096, _periodic(4096, 1, 8000), nchan=600, npol=1, ndim=4)
     assert (c["nsplit"], c["threads"]) == (1, 1024)
     assert _case(100, _periodic(100, 3, 8000), nchan=2)["nsplit"] == 1          # 100 / 2 < 64
-    # rows per workgroup (:933): nchan * nsplit >= 2 ncu
+    # rows per workgroup (`nrw`): nchan * nsplit >= 2 ncu
     assert _case(200, _periodic(200, 3, 4000), nchan=512, npol=2, ndim=2)["nrow"] == 2
     assert _case(200, _periodic(200, 3, 4000), nchan=511, npol=2, ndim=2)["nrow"] == 1
     assert _case(200, _periodic(200, 3, 4000), nchan=520, npol=4, ndim=1)["nrow"] == 4
     assert _case(200, _periodic(200, 3, 4000), nchan=520, npol=4, ndim=1, ncu=304)["nrow"] == 1
-    # LONG segments (:912-920): nseg from ncu and nchan * npol, rows per workgroup against nchan * nseg
+    # LONG segments (`nseg`, `cps`): nseg from ncu and nchan * npol, rows per workgroup against nchan * nseg
     c = _case(16, _periodic(16, 100, 20000), nchan=3)
     assert (c["kernel"], c["nseg"], c["cps"]) == ("long", 10, 1)
     c = _case(16, _periodic(16, 100, 40000), nchan=200)

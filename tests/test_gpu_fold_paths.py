@@ -1,9 +1,9 @@
 """Every kernel of the stand-alone fold (dspsr_amd_fold_fold / _fold_zeroed, csrc/fold.hip) at the addresses, strides, plans and
 profiles the C-ABI accepts, bit for bit against tests/fold_reference.py.
 
-fold_fold_impl picks its kernel from the call: the input's alignment and strides (fold.hip:820), nbin (:828, :904), the longest
-run (:849), the dense table (:828-845), the bin split (:900-910), the rows per workgroup (:933) and, for LONG runs, the time
-segments (:912-920).  Each case states the branch it is there for, and fold_reference.fold_dispatch -- the same choice restated
+fold_fold_impl picks its kernel from the call: the input's alignment and strides (`aligned`), nbin (`chunked`), the longest
+run (`lng`, FOLD_LONG_RUN), the dense table (plan_scan of fold_plan.h), the bin split (`nsplit`, `threads`), the rows per
+workgroup (`nrw`) and, for LONG runs, the time segments (`nseg`, `cps`).  Each case states the branch it is there for, and fold_reference.fold_dispatch -- the same choice restated
 -- asserts that it reaches it.  Rows are placed by device_buffers.device_rows (an offset from a 256-byte boundary, padded rows,
 NaN everywhere else) and the profiles are asserted finite.  k_fold_direct, k_fold_chunked<., false, .> and k_fold_dense add in
 time order (fold_time_order); the LONG path (k_fold_chunked<., true, .> + k_fold_combine) adds in the association fold_long_model
@@ -123,9 +123,9 @@ def _run(gpu, oracle, nchan, npol, ndim, nbin, ndat, idat_start, spec, expect, o
     return runs, disp
 
 
-# ---- 1. k_fold_direct<1|2|4> with nbin <= 4096: unaligned rows (fold.hip:820 false), :962-973 -----------------------------------
+# ---- 1. k_fold_direct<1|2|4> with nbin <= 4096: unaligned rows (fold_fold_impl: `aligned` false, the k_fold_direct branch) ----------
 # (offset, row_pad, ndim, npol, nchan, nbin, samples per bin, nsplit): offsets 1-3 break the 16-byte address, row_pad 1 and 3
-# the strides; nsplit > 1 where few rows meet nbin >= 128 (:902); runs shorter and longer than FOLD_LONG_RUN (always time order)
+# the strides; nsplit > 1 where few rows meet nbin >= 128 (`nsplit`); runs shorter and longer than FOLD_LONG_RUN (always time order)
 @pytest.mark.parametrize("offset,row_pad,ndim,npol,nchan,nbin,spb,nsplit", [
     (1, 0, 4, 1, 3, 256, 9.3, 4),
     (2, 0, 2, 2, 5, 64, 200.5, 1),
@@ -141,9 +141,9 @@ def test_direct_unaligned_rows(oracle, gpu, offset, row_pad, ndim, npol, nchan, 
     assert (runs[:, 2].max() >= 64) == (spb > 64)
 
 
-# ---- 2. k_fold_chunked<., false, .>: aligned, longest run < 64 (:849 false), not dense (:836-845 false) ---------------------------
-# every instantiation (NDIM, NROW) = (4,1) (2,1) (2,2) (1,1) (1,4); nsplit 1/2/4/8 and 256/512/1024 threads (:900-910); hand-made
-# plans with a longest run of exactly 63, runs across chunk ends, a first sample that is not a multiple of 4 (:819) and a ragged
+# ---- 2. k_fold_chunked<., false, .>: aligned, longest run < 64 (`lng` false), not dense (plan_scan refuses) ----------------------
+# every instantiation (NDIM, NROW) = (4,1) (2,1) (2,2) (1,1) (1,4); nsplit 1/2/4/8 and 256/512/1024 threads (`nsplit`, `threads`); hand-made
+# plans with a longest run of exactly 63, runs across chunk ends, a first sample that is not a multiple of 4 (`first -= first % 4`) and a ragged
 # last chunk ((last - first) * ndim not a multiple of 4: the scalar tail of the chunk loads)
 @pytest.mark.parametrize("name,nchan,npol,ndim,nbin,ndat,i0,plan,nrow,nsplit,threads", [
     ("4x1-split8-hand63", 2, 1, 4, 512, 20000, 13, ("hand", 1, 63), 1, 8, 256),
@@ -169,7 +169,7 @@ def test_chunked_exact_instantiations(oracle, gpu, name, nchan, npol, ndim, nbin
         assert (last - first) * ndim % 4 != 0
 
 
-# ---- 3. k_fold_dense (one run per (chunk, bin), :836-845), every instantiation; and the neighbours it refuses ------------------
+# ---- 3. k_fold_dense (one run per (chunk, bin): plan_scan), every instantiation; and the neighbours it refuses ------------------
 @pytest.mark.parametrize("nchan,npol,ndim,ndat,nrow", [
     (6, 1, 4, 20000, 1), (4, 1, 2, 20000, 1), (520, 2, 2, 4100, 2), (3, 1, 1, 20000, 1), (520, 4, 1, 4100, 4)])
 def test_dense_instantiations(oracle, gpu, nchan, npol, ndim, ndat, nrow):
@@ -179,7 +179,7 @@ def test_dense_instantiations(oracle, gpu, nchan, npol, ndim, ndat, nrow):
 
 
 def test_dense_refuses_a_second_run_in_a_chunk(oracle, gpu):
-    """the same plan with two samples of one run moved to a bin that already has a run in that chunk (:843): chunked, and both
+    """the same plan with two samples of one run moved to a bin that already has a run in that chunk (plan_scan's `lastc`): chunked, and both
     sides in time order"""
     nchan, npol, ndim, nbin, ndat, i0 = 6, 1, 4, 64, 20000, 7
     base = oracle.fold_binplan(0.52, 1.0 / (40.3 * nbin), nbin, ndat - 9)
@@ -194,14 +194,14 @@ def test_dense_refuses_a_second_run_in_a_chunk(oracle, gpu):
 
 @pytest.mark.parametrize("nchan,kernel", [(1, "chunked"), (2, "dense")])
 def test_dense_refuses_a_table_larger_than_a_quarter_of_the_data(oracle, gpu, nchan, kernel):
-    """one row of one float per sample, 600 bins of 4 samples (a period of 2400 > FOLD_CHUNK): 4 * ntab > data words (:834)
+    """one row of one float per sample, 600 bins of 4 samples (a period of 2400 > FOLD_CHUNK): 4 * ntab > data words (plan_scan)
     refuses the table; two rows take it"""
     _run(gpu, oracle, nchan, 1, 1, 600, 24000, 4, ("bins", 0.1, 1.0 / (4.0 * 600), 23990), dict(kernel=kernel, ndim=1))
 
 
-# ---- 4. LONG: k_fold_chunked<., true, .> + k_fold_combine (:849 true), every instantiation --------------------------------------
+# ---- 4. LONG: k_fold_chunked<., true, .> + k_fold_combine (`lng` true), every instantiation ------------------------------------
 # hand-made plans with a longest run of exactly 64 (FOLD_LONG_RUN), folded twice (the second into a profile holding sums: the order
-# of k_fold_combine shows even with one segment); nseg == 1 and nseg >= 3 (:912-920), runs across segment ends, bins that get
+# of k_fold_combine shows even with one segment); nseg == 1 and nseg >= 3 (`nseg`, `cps`), runs across segment ends, bins that get
 # nothing in some segment
 @pytest.mark.parametrize("nchan,npol,ndim,ndat,nrow,nseg", [
     (3, 1, 4, 12000, 1, 6),
@@ -234,7 +234,7 @@ def test_long_wide_bins_bit_exact(oracle, gpu):
     _run(gpu, oracle, 3, 1, 4, 16, ndat, i0, ("bins", 0.13, 1.0 / (16 * 1090.7), ndat - 100), dict(kernel="long", ndim=4), nfold=2)
 
 
-# ---- 5. nbin 4096 (aligned: dense or chunked) against 4097 (:828, :904: direct) -------------------------------------------------
+# ---- 5. nbin 4096 (aligned: dense or chunked) against 4097 (`chunked` false: direct) --------------------------------------------
 @pytest.mark.parametrize("nbin,kernel", [(4096, "dense"), (4097, "direct")])
 def test_nbin_4096_and_4097(oracle, gpu, nbin, kernel):
     ndat = 20000
@@ -250,7 +250,7 @@ FAMILIES = {
 }
 
 
-# ---- 6. fold_zeroed through each family: k_fold_count_hits next to the fold (:974-976) -------------------------------------------
+# ---- 6. fold_zeroed through each family: k_fold_count_hits next to the fold (end of fold_fold_impl) ------------------------------
 @pytest.mark.parametrize("family", list(FAMILIES))
 def test_fold_zeroed_each_family(oracle, gpu, family):
     """hits per channel = planned samples whose first float of polarisation 0 is not zero; the profile is the plain fold's"""
@@ -285,7 +285,7 @@ def test_fold_zeroed_each_family(oracle, gpu, family):
     p.close()
 
 
-# ---- 7. profiles bound to a caller's buffer (dspsr_amd_fold_bind_profile, :575-598): padded rows at an odd float offset ---------
+# ---- 7. profiles bound to a caller's buffer (dspsr_amd_fold_bind_profile): padded rows at an odd float offset ---------
 @pytest.mark.parametrize("family", list(FAMILIES))
 def test_bound_profile_each_family(oracle, gpu, family):
     dspsr_amd, ctx, ncu = gpu
@@ -340,9 +340,9 @@ def test_bound_profile_each_family(oracle, gpu, family):
     eng.close()
 
 
-# ---- 8. several folds on one engine, no host sync between them: both plan slots (:807-816) and the LONG partial sums (:921-929) ---
+# ---- 8. several folds on one engine, no host sync between them: both plan slots (slot_acquire) and the LONG partial sums (f->part) ---
 def _slot_cap(niv):
-    """the interval capacity slot_reserve gives a slot it grows for niv intervals (fold.hip:483)"""
+    """the interval capacity slot_reserve gives a slot it grows for niv intervals (fold.hip slot_reserve)"""
     return niv + niv // 2 + 16
 
 
@@ -431,7 +431,7 @@ def test_plan_from_two_set_bins_calls(oracle, gpu, spb, family):
 @pytest.mark.parametrize("spb,family", [(5.0, "chunked"), (300.0, "long")])
 def test_plan_after_a_fold_without_set_nbin(oracle, gpu, spb, family):
     """fold, then a plan that continues the phase without set_nbin and starts inside the bin the last plan ended in: the new
-    plan opens a fresh run (fold.hip:805), so every sample counted in hits and ndat_folded is folded"""
+    plan opens a fresh run (fold.hip plan_close), so every sample counted in hits and ndat_folded is folded"""
     dspsr_amd, ctx, ncu = gpu
     nchan, npol, ndim, nbin, ndat, i0 = 4, 1, 4, 32, 30000, 3
     pps, phi = 1.0 / (spb * nbin), 0.21
@@ -463,8 +463,8 @@ def test_plan_after_a_fold_without_set_nbin(oracle, gpu, spb, family):
     _check_f64(got, x, runs_of_plan(full, i0), np.zeros_like(got), 1)
 
 
-# fused folds (dspsr_amd_filterbank_perform_fold) use up their plan in fold_build_part_plan (fold.hip:1011, fold_is_fused() 1
-# and 2) and fold_build_segment_plan (:1128, fold_is_fused() 3): (C, M, nfilt, nbin, samples per bin, fused_fold, mode)
+# fused folds (dspsr_amd_filterbank_perform_fold) use up their plan in fold_build_part_plan (fold.hip, fold_is_fused() 1
+# and 2) and fold_build_segment_plan (fold_is_fused() 3): (C, M, nfilt, nbin, samples per bin, fused_fold, mode)
 @pytest.mark.parametrize("C,M,nfilt,nbin,spb,force,mode", [
     (64, 128, (9, 10), 100, 12.345, True, 1),
     (4, 16384, (301, 212), 64, 700.3, False, 3),
@@ -511,3 +511,141 @@ def test_fused_fold_then_a_plan_without_set_nbin(oracle, gpu, C, M, nfilt, nbin,
     eng.close()
     cont.close()
     doc.close()
+
+
+# ---- 10. one engine's two plan slots refilled by different consumers with different buffer layouts ---------------------------------
+def _slot_growth(steps):
+    """slot_reserve restated for a sequence of plans (consumer, slot, words, intervals, aux words): the words are sized exactly,
+    intervals as _slot_cap, aux words n + n / 4 + 1024.  Returns (step, buffer pair, consumer that sized it before) for every
+    step that regrows a pair (None: the pair was never sized)."""
+    cap, events = {}, []
+    for k, (who, slot, words, niv, naux) in enumerate(steps, 1):
+        for pair, need, alloc in (("words", words, words), ("iv", niv, _slot_cap(niv)), ("aux", naux, naux + naux // 4 + 1024)):
+            have, by = cap.get((slot, pair), (0, None))
+            if need > have:
+                events.append((k, pair, by))
+                cap[(slot, pair)] = (alloc, who)
+    return events
+
+
+@pytest.mark.parametrize("C,M,nfilt,nbin,spb,force,mode", [
+    (64, 128, (9, 10), 100, 12.345, True, 1),
+    (4, 16384, (301, 212), 64, 700.3, False, 3),
+])
+def test_slots_shared_by_every_plan_consumer(oracle, gpu, C, M, nfilt, nbin, spb, force, mode):
+    """six plans back to back on ONE engine bound to a caller's buffer, nothing in between waits for the device: a stand-alone
+    dense fold (slot 0), a fused perform_fold (slot 1: the part plan of fold_is_fused() 1, the segment plan of 3), a chunked fold
+    of short runs (slot 0), a second fused perform_fold (slot 1), fold_many with a second engine (slot 0: this engine's dense
+    table over the group's grid; the other engine walks), a LONG fold (slot 1).  From the run counts: the chunked fold regrows
+    the intervals the dense fold sized, fold_many regrows the table (aux) the dense fold sized, the LONG fold regrows the
+    intervals the fused plan sized -- while it finds the part plan's words (fold_is_fused() 1) larger than its own.  (The words
+    of a stand-alone plan are nbin + 1 in every consumer: only the part plan sizes them otherwise, and in this order of steps it
+    meets a slot no one sized.)
+    The reference is the same six steps, each on a FRESH engine -- both slots never used, every buffer sized for this plan alone --
+    bound to a second buffer: the same sums in the same order, so the two buffers hold the same bits."""
+    import fused_fold_cases as fc
+    dspsr_amd, ctx, ncu = gpu
+    o = oracle
+    N, nkeep = C * M, M - sum(nfilt)
+    step, ovl = 2 * (N - sum(nfilt) * C), 2 * sum(nfilt) * C
+    npart = 5
+    ndat_f = npart * nkeep
+    rng = np.random.default_rng(43)
+    kernel = np.exp(1j * rng.uniform(-np.pi, np.pi, N)).astype(np.complex64)
+    fb = dspsr_amd.FilterbankEngine(ctx).setup(C, M, nfilt[0], nfilt[1], 1, 2, True, kernel, max_parts=2,
+                                               fused_fold=dspsr_amd.FUSED_ALWAYS if force else dspsr_amd.FUSED_AUTO)
+    assert fb.fold_is_fused() == mode
+    raws = [torch.from_numpy(np.clip(np.rint(rng.standard_normal(2 * (npart * step + ovl)) * 24.0), -128, 127).astype(np.int8)).cuda()
+            for _ in range(2)]
+    ndat = 80000
+    gen = torch.Generator(device="cuda")
+    gen.manual_seed(44)
+    rows = torch.rand((C, 1, ndat * 4), dtype=torch.float32, device="cuda", generator=gen) + 0.5
+    nbin2 = 64                                                   # the second engine of fold_many
+    i0 = 4
+    #        kind     nbin   phi   samples per bin       samples
+    plans = [("fold", nbin, 0.52, 40.3, 20000),                  # 1. dense: a period above FOLD_CHUNK samples, runs under 64
+             ("fused", nbin, 0.37, spb, ndat_f),                 # 2.
+             ("fold", nbin, 0.70, 3.0, 20000),                   # 3. chunked: short runs, more intervals than step 1
+             ("fused", nbin, 0.61, spb, ndat_f),                 # 4.
+             ("many", nbin, 0.33, 40.3, ndat - 10),              # 5. dense over a longer grid: a larger table than step 1
+             ("fold", nbin, 0.45, 70.3, 20000)]                  # 6. LONG
+    many2 = (nbin2, 0.21, 5.0, ndat - 10)                        #    ... with a walk plan of the second engine
+    per_sample = [o.fold_binplan(phi, 1.0 / (s * nb), nb, n) for _k, nb, phi, s, n in plans]
+    runs = [runs_of_plan(p, 0 if k[0] == "fused" else i0) for k, p in zip(plans, per_sample)]
+    plan2 = o.fold_binplan(many2[1], 1.0 / (many2[2] * nbin2), nbin2, many2[3])
+    disp = [fold_dispatch(rows.data_ptr(), rows.stride(0), rows.stride(1), C, 1, 4, nbin, r, ncu)["kernel"] for r in runs]
+    assert [disp[0], disp[2], disp[4], disp[5]] == ["dense", "chunked", "dense", "long"]
+    assert fold_dispatch(rows.data_ptr(), rows.stride(0), rows.stride(1), C, 1, 4, nbin2, runs_of_plan(plan2, i0), ncu)["kernel"] == "chunked"
+    assert plan_span(runs[4]) == plan_span(runs_of_plan(plan2, i0))          # the group's chunk grid is this engine's own
+
+    def ntab(r):
+        first, last = plan_span(r)
+        return -(-(last - first) // FOLD_CHUNK) * nbin
+    if mode == 1:
+        def fused_need(r):
+            pp = fc.part_plan(r, nkeep, npart, nbin)
+            return ("part", ((npart + 4) & ~3) + 4 * sum(len(p) for p in pp), sum(len(iv) for p in pp for _b, iv in p), 0)
+    else:
+        def fused_need(r):
+            assert int(r[:, 2].max()) >= 64 and (r[1:-1, 2] >= 32).all()     # the segment plan qualifies
+            return ("segment", nbin + 1, len(r), len(r) + 1 + (ndat_f >> 10) + 1)
+    needs = [("fold", 0, nbin + 1, len(runs[0]), ntab(runs[0])), fused_need(runs[1])[:1] + (1,) + fused_need(runs[1])[1:],
+             ("fold", 0, nbin + 1, len(runs[2]), 0), fused_need(runs[3])[:1] + (1,) + fused_need(runs[3])[1:],
+             ("fold_many", 0, nbin + 1, len(runs[4]), ntab(runs[4])), ("fold", 1, nbin + 1, len(runs[5]), 0)]
+    grew = _slot_growth(needs)
+    assert {(3, "iv", "fold"), (5, "aux", "fold"), (6, "iv", needs[1][0])} <= set(grew), grew
+    assert (mode == 1) == (needs[1][2] > nbin + 1)               # the LONG fold meets the part plan's larger words
+
+    def run(bufs, fresh):
+        """the six steps into bufs = (bound buffer, second engine's buffer); fresh: a new engine for every step"""
+        hits, engines = [], []
+
+        def engine(buf, nb):
+            e = dspsr_amd.FoldEngine(ctx)
+            e.bind_profile(buf, C, 1, 4, nb)
+            engines.append(e)
+            return e
+        eng = None
+        for (kind, nb, phi, s, n), r in zip(plans, runs):
+            if fresh or eng is None:
+                eng = engine(bufs[0], nbin)
+            start = 0 if kind == "fused" else i0
+            h = np.zeros(nb, np.uint32)
+            eng.set_nbin(nb)
+            eng.set_ndat(n, start)
+            assert eng.set_bins(phi, 1.0 / (s * nb), n, start, h) == n
+            hits.append(h)
+            if kind == "fused":
+                fb.perform_fold(eng, npart, dspsr_amd.COHERENCE, raw=raws[len(hits) // 2 - 1], scale=float(o.S8))
+            elif kind == "many":
+                other = engine(bufs[1], nbin2)
+                h2 = np.zeros(nbin2, np.uint32)
+                other.set_nbin(nbin2)
+                other.set_ndat(many2[3], i0)
+                other.set_bins(many2[1], 1.0 / (many2[2] * nbin2), many2[3], i0, h2)
+                hits.append(h2)
+                assert dspsr_amd.FoldEngine.fold_many([eng, other], rows) == 2
+            else:
+                eng.fold(rows)
+        torch.cuda.synchronize()
+        for e in engines:
+            e.close()
+        return hits
+
+    span = nbin * 4 + 4                                          # (padded rows, float4 aligned: the fused kernels take them)
+    bufs = [(torch.zeros((C, span), dtype=torch.float32, device="cuda"), torch.zeros((C, nbin2 * 4), dtype=torch.float32, device="cuda"))
+            for _ in range(2)]
+    torch.cuda.synchronize()                                     # inputs and the zeroed profiles are in place
+    hits = run(bufs[0], False)
+    hits_ref = run(bufs[1], True)
+    want_hits = [np.bincount(p, minlength=nb).astype(np.uint32) for (_k, nb, *_), p in zip(plans, per_sample)]
+    want_hits.insert(5, np.bincount(plan2, minlength=nbin2).astype(np.uint32))
+    for k, w in enumerate(want_hits):
+        assert np.array_equal(hits[k], w) and np.array_equal(hits_ref[k], w), k
+    for got, ref in zip(bufs[0], bufs[1]):
+        got, ref = got.cpu().numpy(), ref.cpu().numpy()
+        assert np.isfinite(got).all() and np.abs(got).max() > 0
+        assert np.array_equal(got, ref)
+    assert (bufs[0][0].cpu().numpy()[:, nbin * 4:] == 0).all()   # the padding of the bound rows is never written
+    fb.close()

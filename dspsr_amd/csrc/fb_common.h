@@ -23,6 +23,7 @@
 #include <vector>
 
 #include "engine_internal.h"
+#include "fb_rt_layout.h"
 #include "fold_internal.h"
 #include "stamps.h"
 
@@ -64,7 +65,18 @@ struct FbIn {
   // chan_stride_c complex samples behind `base`; 0: off
   uint32_t batch;
   uint64_t chan_stride_c;
+  // kinds 3 and 5: elements from one tile, sequence and part of the regrouped image to the next (fb_rt_layout.h: one window per
+  // part, or one row grid shared by the parts of the launch group) -- pass 1 adds the three products, whatever the layout
+  uint64_t rt_tile_stride = 0, rt_seq_stride = 0, rt_part_stride = 0;
 };
+static inline void fb_set_rt(FbIn& in, int kind, const void* base, const RtLayout& l)
+{
+  in.kind = kind;
+  in.base = base;
+  in.rt_tile_stride = l.tile_stride;
+  in.rt_seq_stride = l.seq_stride;
+  in.rt_part_stride = l.part_stride;
+}
 
 struct FbOut {
   int kind;  // 0: none (benchmark), 1: complex filterbank rows, 2: detected, 3: detected and folded in the same
@@ -578,7 +590,9 @@ void fb_launch_sub_split(hipStream_t stream, const SubSplit& p, uint8_t* out, ui
 cf* fb_launch_sub_combine(hipStream_t stream, const FbGeom& g, cf* X, uint32_t nseqs, uint32_t ncu, cf* Xalt, cf* Xout = nullptr, uint32_t mo = 0,
                           uint32_t rm = 1);
 void fb_launch_time_combine(hipStream_t stream, const TimeCombine& p, const FbOut& out, uint32_t R, uint32_t ncu);
-void fb_launch_raw_transpose(dim3 grid, hipStream_t stream, const FbGeom& g, const FbIn& in, uint16_t* Rt, uint64_t part0);
+// the 8-bit regroup of nb parts (of nseq sequences each) from part0 on into the image `lay`
+void fb_launch_raw_transpose(hipStream_t stream, const FbGeom& g, const FbIn& in, uint16_t* Rt, uint64_t part0, uint32_t nb, uint32_t nseq,
+                             const RtLayout& lay);
 void fb_launch_float_transpose(dim3 grid, hipStream_t stream, const FbGeom& g, const FbIn& in, cf* Rt, uint64_t part0);
 // dsp::Convolution with n_fft <= 8192 in one tile pass (fb_conv1.hip): complex float32 rows, two polarisations
 int fb_conv1_check(int logM, size_t* lds_bytes);

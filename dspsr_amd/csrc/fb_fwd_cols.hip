@@ -9,25 +9,31 @@ namespace dspsr_amd {
 // per 8 useful bytes and per lane, so for 8-bit real dual-pol input the window of each part is first
 // regrouped (2 bytes per sample pair, coalesced both ways through LDS) into
 //   Rt[part][tile][na][T1]  (pol0,pol1) byte pairs
+// or, when the parts of the launch group start whole rows apart, into ONE row grid Rt[tile][row][T1] that all parts read their
+// windows from -- the rows neighbouring parts share are regrouped once (fb_rt_layout.h; lay.rows rows from the first row of part
+// part0 on, blockIdx.z = the sequence alone).
 // Both the generic order and the CASPSR 4-sample interleave are accepted.
 __global__ __launch_bounds__(256) void k_raw_transpose(const FbGeom g, const FbIn in, uint16_t* __restrict__ Rt,
-                                                       const uint64_t part0)
+                                                       const uint64_t part0, const RtLayout lay)
 {
   // block: 64 rows (na) x 256 columns (nb) of byte pairs; rows are read as 16-byte pieces (8 samples),
   // written as T-sample (2T-byte) pieces of 64 consecutive rows = 128*T contiguous bytes per tile
   constexpr uint32_t ROWS = 64, COLS = 256, PITCH = COLS / 2 + 1;       // 32-bit words per LDS row (+1: bank skew)
   __shared__ uint32_t sm[ROWS * PITCH];
   const uint32_t tid = threadIdx.x;
-  const uint32_t M = 1u << g.logM, Rr = 1u << g.logR;
+  static_assert(ROWS == RT_ROW_BLOCK, "k_raw_transpose: the layout pads the rows of a tile to whole blocks");
+  const uint32_t Rr = 1u << g.logR;
   const int logT = g.logT1;
   const uint32_t nb0 = blockIdx.x * COLS, na0 = blockIdx.y * ROWS;
   // complex dual-pol input (generic order, 4 bytes per sample: p0 re, p0 im, p1 re, p1 im): one polarisation = one
   // sequence per blockIdx.z, its (re, im) byte pairs take the place of the (pol0, pol1) pairs of real input
   const uint32_t nsq = g.real_input ? 1u : g.npol;
-  const uint64_t part = blockIdx.z / nsq;
+  const uint64_t part = blockIdx.z / nsq;                 // (shared row grid: gridDim.z == nsq, part 0)
   const uint32_t seq = blockIdx.z % nsq;
   const uint64_t t0 = (part0 + part) * in.part_step;
-  const uint32_t ncol = Rr - nb0 < COLS ? Rr - nb0 : COLS, nrow = M - na0 < ROWS ? M - na0 : ROWS;
+  // (the ragged last block stops at the last row: the last part's window ends where the caller's block may end)
+  const uint32_t ncol = Rr - nb0 < COLS ? Rr - nb0 : COLS, nrow = lay.rows - na0 < ROWS ? lay.rows - na0 : ROWS;
+  const uint32_t rpad = lay.rows_padded;                  // rows from one tile to the next
   if (ncol % 8 == 0) {
     for (uint32_t q = tid; q < nrow * (ncol / 8); q += 256) {       // 8 samples (16 bytes) per thread and step
       const uint32_t r = q / (ncol / 8), c8 = (q % (ncol / 8)) * 8;
@@ -74,7 +80,7 @@ __global__ __launch_bounds__(256) void k_raw_transpose(const FbGeom g, const FbI
     }
   }
   __syncthreads();
-  uint32_t* __restrict__ dst = (uint32_t*)(Rt + (part * nsq + seq) * ((uint64_t)M << g.logR));
+  uint32_t* __restrict__ dst = (uint32_t*)(Rt + part * lay.part_stride + seq * lay.seq_stride);
   const int logW = logT - 1;                        // 32-bit words per (row, tile) piece
   const uint32_t ntl = ncol >> logT, W = 1u << logW;
   if (logW == 1 && (nrow & 1) == 0) {
@@ -86,7 +92,7 @@ __global__ __launch_bounds__(256) void k_raw_transpose(const FbGeom g, const FbI
       const uint32_t r = (q % nr2) * 2, tl = q / nr2;
       const uint32_t* s0 = &sm[r * PITCH + 2 * tl];
       const uint32_t* s1 = s0 + PITCH;
-      *(uint4*)&dst[((((uint64_t)((nb0 >> logT) + tl) << g.logM) + na0 + r) << 1)] = make_uint4(s0[0], s0[1], s1[0], s1[1]);
+      *(uint4*)&dst[(((uint64_t)((nb0 >> logT) + tl) * rpad + na0 + r) << 1)] = make_uint4(s0[0], s0[1], s1[0], s1[1]);
     }
     return;
   }
@@ -95,13 +101,13 @@ __global__ __launch_bounds__(256) void k_raw_transpose(const FbGeom g, const FbI
     for (uint32_t q = tid; q < (ntl * nrow) << logV; q += 256) {
       const uint32_t v4 = q & ((1u << logV) - 1), r = (q >> logV) % nrow, tl = (q >> logV) / nrow;
       const uint32_t* s0 = &sm[r * PITCH + (tl << logW) + 4 * v4];
-      *(uint4*)&dst[((((uint64_t)((nb0 >> logT) + tl) << g.logM) + na0 + r) << logW) + 4 * v4] = make_uint4(s0[0], s0[1], s0[2], s0[3]);
+      *(uint4*)&dst[(((uint64_t)((nb0 >> logT) + tl) * rpad + na0 + r) << logW) + 4 * v4] = make_uint4(s0[0], s0[1], s0[2], s0[3]);
     }
     return;
   }
   for (uint32_t q = tid; q < ntl * nrow * W; q += 256) {           // [tile][row][word]: runs of nrow*T pairs
     const uint32_t wd = q & (W - 1), r = (q >> logW) % nrow, tl = (q >> logW) / nrow;
-    dst[((((uint64_t)((nb0 >> logT) + tl) << g.logM) + na0 + r) << logW) + wd] = sm[r * PITCH + (tl << logW) + wd];
+    dst[(((uint64_t)((nb0 >> logT) + tl) * rpad + na0 + r) << logW) + wd] = sm[r * PITCH + (tl << logW) + wd];
   }
 }
 
@@ -182,8 +188,8 @@ __global__ __launch_bounds__(512) void k_fwd_cols(const FbGeom g, const FbIn in,
     const uint32_t tile = item & (ntile - 1);
     const uint32_t rest = item >> logNt;
     uint32_t seq = seq_of(rest);
-    const bool pret = in.kind == 3 || in.kind == 5;   // pre-transposed: [part][tile][na][T] pairs, contiguous per tile
-    uint64_t t0 = pret ? ((uint64_t)rest * ntile + tile) * ((uint64_t)T << LOGF)       // rest = part*nseq + seq
+    const bool pret = in.kind == 3 || in.kind == 5;   // pre-transposed: [na][T] pairs, contiguous per tile (fb_rt_layout.h)
+    uint64_t t0 = pret ? part_of(rest) * in.rt_part_stride + seq * in.rt_seq_stride + tile * in.rt_tile_stride
                        : (part0 + part_of(rest)) * in.part_step + tile * T;
     if constexpr (RAWW == 4) {
       // channel-batched convolution (FbIn::batch, float32 complex rows): `rest` = (part * npol + pol) * batch + channel
@@ -354,7 +360,7 @@ __global__ __launch_bounds__(512) void k_fwd_cols_dual(const FbGeom g, const FbI
   const int logL = LOGF + g.logR;
   const uint64_t L = 1ull << logL;
   const int logNp = g.logR - LOGT - 1;                  // pairs of tiles per sequence
-  const uint32_t npair = 1u << logNp, ntile = npair << 1;
+  const uint32_t npair = 1u << logNp;
   const uint32_t total = npair * nseq * nparts;
   auto seq_of = [&](const uint32_t rest) { return nseq == 2 ? (rest & 1u) : 0u; };
   auto part_of = [&](const uint32_t rest) { return nseq == 2 ? (rest >> 1) : rest; };
@@ -362,8 +368,9 @@ __global__ __launch_bounds__(512) void k_fwd_cols_dual(const FbGeom g, const FbI
     const uint32_t tile = ((item & (npair - 1)) << 1) | sub;
     const uint32_t rest = item >> logNp;
     const uint32_t seq = seq_of(rest);
-    const bool pret = in.kind == 3 || in.kind == 5;   // pre-transposed: [part][tile][na][T] pairs, contiguous per tile
-    const uint64_t t0 = pret ? ((uint64_t)rest * ntile + tile) * ((uint64_t)T << LOGF) : (part0 + part_of(rest)) * in.part_step + tile * T;
+    const bool pret = in.kind == 3 || in.kind == 5;   // pre-transposed: [na][T] pairs, contiguous per tile (fb_rt_layout.h)
+    const uint64_t t0 = pret ? part_of(rest) * in.rt_part_stride + seq * in.rt_seq_stride + tile * in.rt_tile_stride
+                             : (part0 + part_of(rest)) * in.part_step + tile * T;
     constexpr uint32_t MS = 1u << (LOGF - P::LOGR1);
     const uint64_t step = pret ? ((uint64_t)MS << LOGT) : ((uint64_t)MS << g.logR);
 #pragma unroll
@@ -651,9 +658,11 @@ k1_t fb_pick1(int logf, int raww, bool full) { return pick1(logf, raww, full, se
 // (8-bit input only: with float32 input the two tiles' prefetch alone is 128 registers)
 k1_t fb_pick1_dual(int raww) { return raww == 1 ? k_fwd_cols_dual<1> : nullptr; }
 
-void fb_launch_raw_transpose(dim3 grid, hipStream_t stream, const FbGeom& g, const FbIn& in, uint16_t* Rt, uint64_t part0)
+void fb_launch_raw_transpose(hipStream_t stream, const FbGeom& g, const FbIn& in, uint16_t* Rt, uint64_t part0, uint32_t nb, uint32_t nseq,
+                             const RtLayout& lay)
 {
-  hipLaunchKernelGGL(k_raw_transpose, grid, dim3(256), 0, stream, g, in, Rt, part0);
+  const dim3 grid(((1u << g.logR) + 255) / 256, (lay.rows + RT_ROW_BLOCK - 1) / RT_ROW_BLOCK, lay.shared ? nseq : nb * nseq);
+  hipLaunchKernelGGL(k_raw_transpose, grid, dim3(256), 0, stream, g, in, Rt, part0, lay);
 }
 void fb_launch_float_transpose(dim3 grid, hipStream_t stream, const FbGeom& g, const FbIn& in, cf* Rt, uint64_t part0)
 {

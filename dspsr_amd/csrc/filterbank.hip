@@ -855,15 +855,17 @@ static int fb_subband_group(dspsr_amd_filterbank* fb, const FbIn& in, uint32_t i
     k1_t k1s = p1.raww == 1 ? fb->k1_w1 : fb->k1_w4;
     if (!k1s) return fb_fail(ctx, DSPSR_AMD_EINVAL, "dspsr_amd_filterbank_perform: no kernel for this geometry");
     FbIn cr = cs;
+    // (one window per part: the sub-groups' parts are windows of their own)
+    const RtLayout lay = rt_layout_per_part(g.logM, g.logR, g.logT1, fb->nseq);
     if (p1.regroup == FB_REGROUP_RAW) {
-      fb_launch_raw_transpose(dim3((Rr + 255) / 256, (M + 63) / 64, nb * fb->nseq), ctx->stream, g, cs, fb->Rt, 0);
-      cr.kind = 3; cr.base = fb->Rt;
+      fb_launch_raw_transpose(ctx->stream, g, cs, fb->Rt, 0, nb, fb->nseq, lay);
+      fb_set_rt(cr, 3, fb->Rt, lay);
     } else if (p1.regroup == FB_REGROUP_FLOAT) {
       // (the float regroup buffer is the X scratch in the power-of-two path; X holds finished sub-spectra here: use Rt's
       //  place in A's idle upper half -- A needs nseq * L' of its nseq * L elements per part)
       cf* ft = fb->A + (size_t)nb * fb->nseq * Ls;
       fb_launch_float_transpose(dim3((Rr + FB_FT_COLS - 1) / FB_FT_COLS, (M + FB_FT_ROWS - 1) / FB_FT_ROWS, nb * fb->nseq), ctx->stream, g, cs, ft, 0);
-      cr.kind = 5; cr.base = ft;
+      fb_set_rt(cr, 5, ft, lay);
     }
     const uint64_t n1s = (uint64_t)(Rr >> g.logT1) * fb->nseq * nb, n2s = (uint64_t)(M >> g.logT2) * fb->nseq * nb;
     hipLaunchKernelGGL(k1s, dim3(grid_for(n1s, fb->ncu * fb->wg1)), dim3(fb->nt1), fb->lds1, ctx->stream, g, cr, fb->A, ctx->tw, 0ull,
@@ -948,8 +950,9 @@ static int fb_run_two_pass(dspsr_amd_filterbank* fb, const FbIn& in, const FbOut
       hipLaunchKernelGGL(fb->k1c, dim3(grid_for(n1c, fb->ncu)), dim3(512), fb->lds1c, ctx->stream, g, cr, fb->A, ctx->tw, nb, 2u, 32u);
     } else {
       const FbGeom& q = fb->g1t;
-      const uint32_t Fa = 1u << q.logM;
-      fb_launch_raw_transpose(dim3((Fb + 255) / 256, (Fa + 63) / 64, nb * 2), ctx->stream, q, ci, fb->Rt, part0);
+      const RtLayout lay = rt_layout_per_part(q.logM, q.logR, q.logT1, 2);
+      fb_launch_raw_transpose(ctx->stream, q, ci, fb->Rt, part0, nb, 2, lay);
+      fb_set_rt(cr, 3, fb->Rt, lay);
       const uint64_t n1t = (uint64_t)(Fb >> q.logT1) * 2 * nb;
       hipLaunchKernelGGL(fb->k1t, dim3(grid_for(n1t, fb->ncu)), dim3(fb->nt1t), fb->lds1t, ctx->stream, q, cr, fb->A, ctx->tw, part0,
                          nb, 2u, 32u);
@@ -981,13 +984,18 @@ static int fb_run_tiles(dspsr_amd_filterbank* fb, const FbIn& in, const FbOut& o
     // XCD dealing of the persistent items (wgfft.h persistent_item): runs of consecutive items per XCD
     const uint32_t run1 = 32, run2 = 4, run3 = nb;
     FbIn c1 = ci;
+    RtLayout lay = rt_layout_per_part(g.logM, g.logR, g.logT1, fb->nseq);
     if (p1.regroup == FB_REGROUP_RAW) {
-      fb_launch_raw_transpose(dim3((Rr + 255) / 256, (M + 63) / 64, nb * fb->nseq), ctx->stream, g, ci, fb->Rt, part0);
-      c1.kind = 3; c1.base = fb->Rt;
+      // parts that start whole rows apart read their windows from ONE regrouped row grid: the rows neighbours share are
+      // regrouped once (headline: 104908 rows instead of 131072 per 32 parts); never larger than the per-part image Rt is
+      // allocated for (rt_takes_shared)
+      if (rt_takes_shared(g.logM, g.logR, nb, ci.part_step)) lay = rt_layout_shared(g.logM, g.logR, g.logT1, nb, ci.part_step >> g.logR);
+      fb_launch_raw_transpose(ctx->stream, g, ci, fb->Rt, part0, nb, fb->nseq, lay);
+      fb_set_rt(c1, 3, fb->Rt, lay);
     } else if (p1.regroup == FB_REGROUP_FLOAT) {
       // (into the idle X scratch)
       fb_launch_float_transpose(dim3((Rr + FB_FT_COLS - 1) / FB_FT_COLS, (M + FB_FT_ROWS - 1) / FB_FT_ROWS, nb * fb->nseq), ctx->stream, g, ci, fb->X, part0);
-      c1.kind = 5; c1.base = fb->X;
+      fb_set_rt(c1, 5, fb->X, lay);
     }
     if (k.k1d)
       hipLaunchKernelGGL(k.k1d, dim3(grid_for(n1 / 2, fb->ncu * fb->wg1)), dim3(fb->nt1), fb->lds1, ctx->stream, g, c1, fb->A, ctx->tw,

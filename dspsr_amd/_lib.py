@@ -24,7 +24,7 @@ class FilterbankConfig(C.Structure):
     _fields_ = [("nchan_subband", C.c_uint32), ("freq_res", C.c_uint32), ("nfilt_pos", C.c_uint32),
                 ("nfilt_neg", C.c_uint32), ("input_nchan", C.c_uint32), ("npol", C.c_uint32),
                 ("real_input", C.c_uint32), ("max_parts", C.c_uint32), ("force_four_pass", C.c_uint32),
-                ("fused_fold", C.c_uint32)]
+                ("fused_fold", C.c_uint32), ("split_in_inverse", C.c_uint32)]
 
 
 class TfpConfig(C.Structure):
@@ -70,6 +70,7 @@ SYMBOLS = {
                                                  _u64]),
     "dspsr_amd_filterbank_fold_is_fused": (_i, [_vp]),
     "dspsr_amd_filterbank_npass": (_i, [_vp, _i]),
+    "dspsr_amd_filterbank_presplit": (_i, [_vp]),
     "dspsr_amd_filterbank_perform_fold": (_i, [_vp, _vp, _u64, _u64, _u64, _vp, _i, _f, _i, _vp, _u64]),
     "dspsr_amd_filterbank_perform_search": (_i, [_vp, _vp, _u64, _u64, _u64, _vp, _i, _f, _i, _u32, _vp, _u64, _u64, _vp,
                                                  C.POINTER(_u32), _u64, C.POINTER(_u64)]),

@@ -16,6 +16,11 @@
 //   Scratch between passes is stored blocked so every global access is a >=128-byte run:
 //     A[(ka/T2)][nb][ka%T2]   (written by P1 as T1*T2-element runs, read contiguously by P2)
 //     X[(s'/T3)][m][s'%T3]    (written by P2 as T2*T3-element runs, read contiguously by P3)
+//   Pre-split form (real dual-polarisation input, three passes; fb_row_map.h): the rows of A in mirror-paired blocks, so that P2
+//   holds every element together with its Hermitian mirror and stores the split spectrum
+//     X'[(c/T3)][p(m)][c%T3][pol]   (16-byte elements (X_pol0, X_pol1), c < C: the size of X, aligned runs of (T2/2)*T3 elements;
+//                                    p(m): the bins above M/2 one place down, bin M/2 last -- rm_xrow)
+//   which P3 loads with one ascending 16-byte stream per thread.
 #pragma once
 #include <math.h>
 #include <stdlib.h>
@@ -23,6 +28,7 @@
 #include <vector>
 
 #include "engine_internal.h"
+#include "fb_row_map.h"
 #include "fb_rt_layout.h"
 #include "fold_internal.h"
 #include "stamps.h"
@@ -473,16 +479,11 @@ template <int NT, typename IDX> DEV void twiddles_big(cf (&t)[NT], const IDX (&j
   }
 }
 
-// v[k] *= W_L^{nb*(k*pstride + p)} for the column pair (nb, nb+1), k < R : base and the powers 1,2,4,8 of
-// the step from the (coarse x fine) tables, the rest by the ladder
-template <int R> DEV void apply_pass_twiddle(cx2 (&v)[R], const uint32_t nb, const uint32_t p, const uint32_t pstride,
-                                             const int logL, const cf* __restrict__ tw, const cf* __restrict__ tw_lo)
+// v[k] *= W_L^{a + k*d} per column of the pair, given the table indices a0, a1 (k = 0) and d0, d1 (the step), all mod L
+template <int R> DEV void apply_pass_twiddle_idx(cx2 (&v)[R], const uint32_t a0, const uint32_t a1, const uint32_t d0, const uint32_t d1,
+                                                 const int logL, const cf* __restrict__ tw, const cf* __restrict__ tw_lo)
 {
-  // 32-bit index arithmetic: nb < Fb and k*pstride + p < Fa with both factors <= 2^MAX_LOGF = 2^13, so every product is
-  // below 2^26 and its multiples up to 8 below 2^29
   const uint32_t Lm = (uint32_t)((1ull << logL) - 1);
-  const uint32_t a0 = (nb * p) & Lm, d0 = (nb * pstride) & Lm;
-  const uint32_t a1 = (a0 + p) & Lm, d1 = (d0 + pstride) & Lm;             // column nb + 1
   constexpr int NP = R >= 16 ? 4 : R >= 8 ? 3 : R >= 4 ? 2 : R >= 2 ? 1 : 0;   // powers 1, 2, 4, 8 of the step
   uint32_t j[2 + 2 * (NP ? NP : 1)];
   cf t[2 + 2 * (NP ? NP : 1)];
@@ -515,6 +516,27 @@ template <int R> DEV void apply_pass_twiddle(cx2 (&v)[R], const uint32_t nb, con
 #pragma unroll
     for (int k = 0; k < R; k++) v[k] = cmul(v[k], u[k]);
   }
+}
+
+// v[k] *= W_L^{nb*(k*pstride + p)} for the column pair (nb, nb+1), k < R : base and the powers 1,2,4,8 of
+// the step from the (coarse x fine) tables, the rest by the ladder
+template <int R> DEV void apply_pass_twiddle(cx2 (&v)[R], const uint32_t nb, const uint32_t p, const uint32_t pstride,
+                                             const int logL, const cf* __restrict__ tw, const cf* __restrict__ tw_lo)
+{
+  // 32-bit index arithmetic: nb < Fb and k*pstride + p < Fa with both factors <= 2^MAX_LOGF = 2^13, so every product is
+  // below 2^26 and its multiples up to 8 below 2^29
+  const uint32_t Lm = (uint32_t)((1ull << logL) - 1);
+  const uint32_t a0 = (nb * p) & Lm, d0 = (nb * pstride) & Lm;
+  const uint32_t a1 = (a0 + p) & Lm, d1 = (d0 + pstride) & Lm;             // column nb + 1
+  apply_pass_twiddle_idx<R>(v, a0, a1, d0, d1, logL, tw, tw_lo);
+}
+// the same for a pair of columns that are ANY two rows nb0, nb1 (pass 2 on the mirror-paired row order, fb_row_map.h): the same
+// table indices as the adjacent form gives for nb1 = nb0 + 1, hence the same twiddles
+template <int R> DEV void apply_pass_twiddle2(cx2 (&v)[R], const uint32_t nb0, const uint32_t nb1, const uint32_t p, const uint32_t pstride,
+                                              const int logL, const cf* __restrict__ tw, const cf* __restrict__ tw_lo)
+{
+  const uint32_t Lm = (uint32_t)((1ull << logL) - 1);
+  apply_pass_twiddle_idx<R>(v, (nb0 * p) & Lm, (nb1 * p) & Lm, (nb0 * pstride) & Lm, (nb1 * pstride) & Lm, logL, tw, tw_lo);
 }
 
 // v[k] *= conj(W_L^{nb*(k*pstride + p)}) for BOTH columns of the pair (the two polarisations of one column
@@ -570,12 +592,15 @@ constexpr int full_logt(int logf) { return 14 - logf >= 1 ? 14 - logf : -1; }
 constexpr int MAX_LOGF = 13;    // every pass keeps >= 2 columns per workgroup
 typedef mkseq<MAX_LOGF + 1>::type seq_t;
 // kernel tables live in the translation unit that instantiates the kernels
+// presplit: the kernels of the pre-split spectrum (real dual-polarisation input: pass 1 leaves the rows of A in the mirror-paired
+// order of fb_row_map.h, pass 2 forms the Hermitian split and stores the two polarisations, the inverse pass loads them ready)
 k1_t fb_pick1(int logf, int raww, bool full);
+k1_t fb_pick1_rm(int logf, int raww, bool full);      // presplit
 k1_t fb_pick1_dual(int raww);      // pass 1 on pairs of two-column tiles (2^13-point columns), or null
-k2_t fb_pick2(int logf, bool full);
-k3_t fb_pick3(int logf, bool full);       // plain
-k3_t fb_pick3f(int logf, bool full);      // fused fold
-k3_t fb_pick3s(int logf, bool full);      // search mode (detection + time scrunch)
+k2_t fb_pick2(int logf, bool full, bool presplit = false);
+k3_t fb_pick3(int logf, bool full, bool presplit = false);       // plain
+k3_t fb_pick3f(int logf, bool full, bool presplit = false);      // fused fold
+k3_t fb_pick3s(int logf, bool full, bool presplit = false);      // search mode (detection + time scrunch)
 k3a_t fb_pick3a(int logf, bool blocked, bool real, bool full);
 k3b_t fb_pick3b(int logf, bool foldb, bool full);
 // two-pass path (fb_two_pass.hip): pass 1 on whole columns, rows + inverse pass (M = 2^logm, Fb = 2^(13 - logm)), the 8-bit regroup

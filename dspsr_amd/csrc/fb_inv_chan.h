@@ -7,11 +7,17 @@ namespace dspsr_amd {
 
 // ------------------------------------------------------------------------------------ P3
 
-// T3 output channels (both polarisations) of one part: Hermitian split of spectrum rows s and
-// Rr-1-s into the two polarisations (real input), x chirp, inverse M-point FFT, keep window,
-// complex output or fused detection.  Columns are (channel, pol) pairs: col = 2*slo + pol, so
+// T3 output channels (both polarisations) of one part: the two polarisations of every (channel, bin) x chirp, inverse M-point
+// FFT, keep window, complex output or fused detection.  Columns are (channel, pol) pairs: col = 2*slo + pol, so
 // the two butterflies a thread owns are the two polarisations of the same (channel, bin):
-// one (a, b, chirp) load serves both and detection needs no cross-lane traffic.
+// one load (and one chirp factor) serves both and detection needs no cross-lane traffic.
+// Where the two polarisations come from:
+//   PRESPLIT (real dual-polarisation input, the default where the host's condition holds -- filterbank.hip fb_takes_presplit):
+//     pass 2 has already formed the Hermitian split and left X'[c/T3][p(m)][c%T3][pol] (fb_row_map.h).  One ascending 16-byte load
+//     per element; x = (pol0, pol1) * chirp.  No mirror stream, no lane exchange, no split arithmetic in this pass.
+//   otherwise: from X.  Real input: Hermitian split of spectrum rows s and Rr-1-s, a second, descending load stream (a, b) --
+//     in aligned 16-byte pairs exchanged between lane pairs where a tile is two channels (PAIR16); complex input: the rows of
+//     the two sequences.  This is the form of complex input, odd-factor lengths and of split_in_inverse = 1.
 // Items: part fastest, so one XCD re-reads a tile's chirp rows from its L2 for every part.
 // FOLD: the detected samples of the tile (T3 channels x nkeep samples, one float4 each) are staged in the
 // exchange buffer instead of being written out, and folded at once: thread b owns phase bins b, b + blockDim, ...
@@ -23,12 +29,18 @@ namespace dspsr_amd {
 // EPI: 0 = complex or detected output written by the last stage; 1 (FOLD) = fused fold; 2 = search mode (FbOut kind 5): square-law
 // detection + time scrunch of the detected stream (digifil -F N:D, LoadToFil.C:185-222,250-304), staged like the fold's samples and
 // reduced by ts_reduce (fb_common.h).  Both walk the parts of a tile in order (the fold's profile, the scrunch's carry).
-template <int LOGF, int EPI, int LOGT>
+// EPIP = EPI + 4 * PRESPLIT: the pre-split forms are k_inv_chan<., 4 | 5 | 6, .>, the others keep the names they had.  (As a
+// fourth template parameter the flag renames every instantiation; as a device body behind two kernels the fused pre-split form
+// came out with 12 bytes of scratch: profiles/r07_experiments.txt.)
+constexpr int FB_EPI_PRESPLIT = 4;
+template <int LOGF, int EPIP, int LOGT>
 __global__ __launch_bounds__(512) void k_inv_chan(const FbGeom g, const cf* __restrict__ X,
                                                   const cf* __restrict__ kernel, const FbOut out,
                                                   const cf* __restrict__ tw, const uint64_t part0,
                                                   const uint32_t nparts, const uint32_t run)
 {
+  constexpr int EPI = EPIP & 3;
+  constexpr bool PRESPLIT = (EPIP & FB_EPI_PRESPLIT) != 0;
   typedef FftPlan<LOGF> P;
   constexpr bool FOLD = EPI == 1, SEARCH = EPI == 2;
   extern __shared__ __attribute__((aligned(16))) cf lds[];
@@ -44,7 +56,7 @@ __global__ __launch_bounds__(512) void k_inv_chan(const FbGeom g, const cf* __re
   auto xi = [&](const uint32_t row, const uint32_t m) -> uint64_t {
     return ((((uint64_t)(row >> logX3) << LOGF) + m) << logX3) | (row & (X3 - 1));
   };
-  struct Abk { cf a, b; };   // the chirp is fetched at the start of the item (keeps the prefetch at 64 registers)
+  struct Abk { cf a, b; };   // the chirp is fetched at the start of the item (keeps the prefetch at 64 registers); PRESPLIT: (pol0, pol1)
 
   // chunk < 0: all elements; otherwise the elements i with i % NCHUNK == chunk (the prefetch of the next tile is
   // issued in NCHUNK groups spread over the transform, see wgfft_stage)
@@ -53,7 +65,7 @@ __global__ __launch_bounds__(512) void k_inv_chan(const FbGeom g, const cf* __re
   // the halves exchanged between the lane pair.  -3.7 % where the detected or complex output is written; in the fused
   // kernel it cost 1.6 % while the chirp was still loaded per part (round 1) and gains 5.7 % now that it stays in registers
   // (profiles/r02_experiments.txt, item 23)
-  constexpr bool PAIR16 = LOGT == 2 && P::G1 == 2;
+  constexpr bool PAIR16 = !PRESPLIT && LOGT == 2 && P::G1 == 2;
   const bool pair16 = PAIR16 && g.real_input && logX3 == 1;
   cf special = make_float2(0.f, 0.f);                   // mirror element of bin 0 (pair16 path)
   // a work item = (tile of channels, part of the launch), kept as two 32-bit numbers: a combined 64-bit index costs a
@@ -67,6 +79,31 @@ __global__ __launch_bounds__(512) void k_inv_chan(const FbGeom g, const cf* __re
     // divergent code between the loads (the m = 0 mirror element, the only irregular one, can only be i = 0)
     constexpr uint32_t MS = 1u << (LOGF - P::LOGR1);
     const int64_t step = (int64_t)MS << logX3;
+    if constexpr (PRESPLIT) {
+      // X' holds (pol0, pol1) of (channel s, bin m) as the 16-byte element xi(s, rm_xrow(m)): L/2 of them per part.  The bins
+      // m = mb + i*MS of a thread are below M/2 for i < R1/2 and above it -- one place down -- for the others; bin M/2 itself
+      // (mb = 0, i = R1/2), the only irregular one, has the last place
+      // (a uniform base and 32-bit element offsets within the part -- L / 2 <= 2^25 elements: two address registers per pair
+      //  of columns; as three pointers the fused form spilled 12 bytes)
+      const float4* __restrict__ X4 = (const float4*)X + (uint64_t)item.lp * (L >> 1);
+      const uint32_t step4 = MS << logX3;
+#pragma unroll
+      for (int g2 = 0; g2 < P::G1; g2 += 2) {
+        const uint32_t eb = P::G1 * tid + g2, s = tile * T3 + ((eb & (T - 1)) >> 1), mb = eb >> logT;
+        const uint32_t o0 = (uint32_t)xi(s, mb);
+        const uint32_t omid = mb ? o0 + (P::R1 / 2) * step4 - X3 : (uint32_t)xi(s, M - 1);
+#pragma unroll
+        for (int i = 0; i < P::R1; i++) {
+          if (chunk >= 0 && i % NCHUNK != chunk) continue;
+          const float4 v = ld_stream(i < P::R1 / 2 ? X4 + i * step4 + o0 : i == P::R1 / 2 ? X4 + omid : (X4 + (i * step4 - X3)) + o0);
+          Abk r;
+          r.a = make_float2(v.x, v.y);
+          r.b = make_float2(v.z, v.w);
+          raw[(g2 / 2) * P::R1 + i] = r;
+        }
+      }
+      return;
+    }
     if constexpr (PAIR16) {
       if (pair16) {
         // Two channels per tile and X3 = 2: the elements of lanes 2j (channel 0) and 2j+1 (channel 1) for the same bin
@@ -277,7 +314,10 @@ __global__ __launch_bounds__(512) void k_inv_chan(const FbGeom g, const cf* __re
         }
       }
       // (the uniform real/complex choice is made once, outside the unrolled loops: no branch per element)
-      if (g.real_input) {
+      if constexpr (PRESPLIT) {
+#pragma unroll
+        for (int q = 0; q < PTS / 2; q++) x[q] = cmuls(make_cx2(raw[q].a, raw[q].b), kk[q]);          // Response::operate, Response.C:429-441
+      } else if (g.real_input) {
 #pragma unroll
         for (int q = 0; q < PTS / 2; q++) {
           const Abk r = raw[q];

@@ -58,13 +58,15 @@ __global__ __launch_bounds__(256) void k_time_combine(const TimeCombine p, const
   }
 }
 
-template <int... I> static k3_t pick3(int logf, bool full, iseq<I...>)
+template <int... I> static k3_t pick3(int logf, bool full, bool presplit, iseq<I...>)
 {
   static const k3_t t[] = {k_inv_chan<I, 0, -1>...};
   static const k3_t f[] = {k_inv_chan<I, 0, full_logt(I)>...};
-  return full ? f[logf] : t[logf];
+  static const k3_t tp[] = {k_inv_chan<I, FB_EPI_PRESPLIT + 0, -1>...};
+  static const k3_t fp[] = {k_inv_chan<I, FB_EPI_PRESPLIT + 0, full_logt(I)>...};
+  return presplit ? (full ? fp[logf] : tp[logf]) : (full ? f[logf] : t[logf]);
 }
-k3_t fb_pick3(int logf, bool full) { return pick3(logf, full, seq_t()); }
+k3_t fb_pick3(int logf, bool full, bool presplit) { return pick3(logf, full, presplit, seq_t()); }
 void fb_launch_time_combine(hipStream_t stream, const TimeCombine& p, const FbOut& out, uint32_t R, uint32_t ncu)
 {
   switch (R) {

@@ -3,13 +3,15 @@
 
 namespace dspsr_amd {
 
-template <int... I> static k3_t pick3f(int logf, bool full, iseq<I...>)
+template <int... I> static k3_t pick3f(int logf, bool full, bool presplit, iseq<I...>)
 {
   static const k3_t t[] = {k_inv_chan<I, 1, -1>...};
   static const k3_t f[] = {k_inv_chan<I, 1, full_logt(I)>...};
-  return full ? f[logf] : t[logf];
+  static const k3_t tp[] = {k_inv_chan<I, FB_EPI_PRESPLIT + 1, -1>...};
+  static const k3_t fp[] = {k_inv_chan<I, FB_EPI_PRESPLIT + 1, full_logt(I)>...};
+  return presplit ? (full ? fp[logf] : tp[logf]) : (full ? f[logf] : t[logf]);
 }
-k3_t fb_pick3f(int logf, bool full) { return pick3f(logf, full, seq_t()); }
+k3_t fb_pick3f(int logf, bool full, bool presplit) { return pick3f(logf, full, presplit, seq_t()); }
 
 }  // namespace dspsr_amd
 

@@ -44,6 +44,7 @@ struct dspsr_amd_filterbank_impl {
   uint8_t* dsub = nullptr;    // nsub > 1: the launch group's samples de-interleaved into nsub blocks (k_sub_split)
   size_t dsub_bytes = 0;
   bool two_pass = false;
+  bool presplit = false;      // three-pass path on the pre-split spectrum (fb_takes_presplit): k1_*, k2, k3* are the kernels of that form
   FbGeom g1t;                 // ... pass 1 of Fa < 2^14 through k_raw_transpose + k_fwd_cols: their geometry (M = Fa, Rr = Fb, T2 = freq_res)
   k1_t k1t = nullptr;
   uint32_t nt1t = 0;
@@ -289,29 +290,44 @@ static int fb_tile(dspsr_amd_filterbank* fb)
   return DSPSR_AMD_OK;
 }
 
+// Pre-split spectrum (fb_row_map.h): pass 1 leaves the rows of A in mirror-paired blocks, pass 2 forms the Hermitian
+// split and stores the two polarisations, the inverse pass loads them ready.  Taken for real dual-polarisation input on the
+// three-pass path of a power-of-two geometry (nsub == 1, no odd factor of freq_res either: those spectra pass through
+// k_sub_combine in the X layout), unless pass 1 runs on pairs of tiles (k_fwd_cols_dual stages its image itself) or the caller
+// asked for the split in the inverse pass.  The tile arithmetic needs no more: a pass-2 tile holds T2 >= 2 rows, i.e. T2 / 2 >= 1
+// mirror pairs, and its T2 * Rr / 2 outputs of 16 bytes are the 16 per thread the copy-out writes.
+static bool fb_takes_presplit(const dspsr_amd_filterbank* fb, bool dual)
+{
+  const FbGeom& g = fb->g;
+  return fb->cfg.split_in_inverse == 0 && g.real_input && g.npol == 2 && g.nsub == 1 && !fb->msub && !g.four_pass && !dual &&
+         g.logT2 >= 1 && g.logT2 <= g.logM;
+}
+
 // kernels of this geometry and their dynamic-LDS limits (once; perform only launches)
 static int fb_pick_kernels(dspsr_amd_filterbank* fb)
 {
   const FbGeom& g = fb->g;
   const bool full1 = g.logT1 == full_logt(g.logM), full2 = g.logT2 == full_logt(g.logR),
              full3 = !g.four_pass && g.logT3 + 1 == full_logt(g.logM);
-  fb->k1_w1 = fb_pick1(g.logM, 1, full1);
-  fb->k1_w4 = fb_pick1(g.logM, 4, full1);
   // two-column tiles of 2^13 rows whose A runs would be half cache lines: transformed in pairs (k_fwd_cols_dual)
-  if (full1 && g.logM == 13 && g.logT1 == 1 && g.logT1 + g.logT2 < 4 && g.logR >= 2) {
+  const bool dual = full1 && g.logM == 13 && g.logT1 == 1 && g.logT1 + g.logT2 < 4 && g.logR >= 2;
+  const bool ps = fb->presplit = fb_takes_presplit(fb, dual);
+  fb->k1_w1 = ps ? fb_pick1_rm(g.logM, 1, full1) : fb_pick1(g.logM, 1, full1);
+  fb->k1_w4 = ps ? fb_pick1_rm(g.logM, 4, full1) : fb_pick1(g.logM, 4, full1);
+  if (dual) {
     fb->k1d_w1 = fb_pick1_dual(1);
     fb->k1d_w4 = fb_pick1_dual(4);
   }
-  fb->k2 = fb_pick2(g.logR, full2);
+  fb->k2 = fb_pick2(g.logR, full2, ps);
   if (g.four_pass) {
     fb->k3a = fb_pick3a(g.logMa, g.xblocked != 0, g.real_input != 0, g.logTm == 13 - g.logMa && g.logMa <= 12 && fb->nt3 == 512);
     const bool full4 = g.logTt == 13 - g.logMb && g.logMb <= 12 && fb->nt4 == 512;
     fb->k3b = fb_pick3b(g.logMb, false, full4);
     fb->k3bf = fb_pick3b(g.logMb, true, full4);
   } else {
-    fb->k3 = fb_pick3(g.logM, full3);
-    fb->k3f = fb_pick3f(g.logM, full3);
-    fb->k3s = fb_pick3s(g.logM, full3);
+    fb->k3 = fb_pick3(g.logM, full3, ps);
+    fb->k3f = fb_pick3f(g.logM, full3, ps);
+    fb->k3s = fb_pick3s(g.logM, full3, ps);
     // fused fold: the LDS left over behind the twiddle tables holds the part's fold plan (two buffers)
     const FbPlanLds pl = fb_plan_lds(fb->lds3, fb->nt3);   // one plan entry per thread of the workgroup (nt3 <= 512)
     fb->plan_cap = pl.cap;
@@ -319,6 +335,9 @@ static int fb_pick_kernels(dspsr_amd_filterbank* fb)
   }
   if (!((fb->k1_w1 || fb->k1_w4) && fb->k2 && (g.four_pass ? (fb->k3a && fb->k3b) : (fb->k3 != nullptr))))
     return fb_fail(fb->ctx, DSPSR_AMD_EINVAL, "dspsr_amd_filterbank_create: no kernel for this geometry");
+  // (the three passes of the pre-split form only work together: X' is not the X layout; it takes the L elements per part X has)
+  if (ps && !(fb->k1_w1 && fb->k1_w4 && fb->k3f && fb->k3s && fb->nseq == 1 && g.xstride == fb->L))
+    return fb_fail(fb->ctx, DSPSR_AMD_EINVAL, "dspsr_amd_filterbank_create: no kernels for the pre-split spectrum of this geometry");
   const hipError_t e = allow_lds({{fb->k1_w1, fb->lds1}, {fb->k1_w4, fb->lds1}, {fb->k1d_w1, fb->lds1}, {fb->k1d_w4, fb->lds1},
                                   {fb->k2, fb->lds2}, {fb->k3, fb->lds3}, {fb->k3f, fb->lds3f}, {fb->k3s, fb->lds3},
                                   {fb->k3a, fb->lds3}, {fb->k3b, fb->lds4}, {fb->k3bf, fb->lds4}});
@@ -1288,6 +1307,8 @@ extern "C" int dspsr_amd_filterbank_perform_search(dspsr_amd_filterbank* fb, con
   return dspsr_amd_tscrunch_fpt(ctx, det, npo * drow, drow, out_dev, out_chan_stride, out_pol_stride, (uint32_t)nchan_out, npo, 1, ndat,
                                 tscrunch, carry_dev, carry_count, nout);
 }
+
+extern "C" int dspsr_amd_filterbank_presplit(const dspsr_amd_filterbank* fb) { return fb && fb->presplit ? 1 : 0; }
 
 extern "C" int dspsr_amd_filterbank_npass(const dspsr_amd_filterbank* fb, int raw_input)
 {

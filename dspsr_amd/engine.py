@@ -157,12 +157,15 @@ class FilterbankEngine:
 
     def setup(self, nchan_subband, freq_res, nfilt_pos, nfilt_neg, input_nchan=1, npol=2, real_input=True,
               kernel: np.ndarray | None = None, max_parts: int = 1, force_four_pass: bool | int = False,
-              fused_fold: int = _lib.FUSED_AUTO):
+              fused_fold: int = _lib.FUSED_AUTO, split_in_inverse: bool = False):
         """force_four_pass: False / 0 = passes chosen from the geometry, True / 1 = two-pass inverse everywhere, 2 = never the
-        two-pass path of short responses (dspsr_amd_filterbank_config::force_four_pass)."""
+        two-pass path of short responses (dspsr_amd_filterbank_config::force_four_pass).
+        split_in_inverse: True keeps the Hermitian split of real dual-polarisation input in the inverse pass
+        (dspsr_amd_filterbank_config::split_in_inverse); see presplit()."""
         self.close()
         cfg = _lib.FilterbankConfig(nchan_subband, freq_res, nfilt_pos, nfilt_neg, input_nchan, npol,
-                                    1 if real_input else 0, max_parts, int(force_four_pass), fused_fold)
+                                    1 if real_input else 0, max_parts, int(force_four_pass), fused_fold,
+                                    1 if split_in_inverse else 0)
         h = C.c_void_p()
         _check(self.ctx.handle, lib.dspsr_amd_filterbank_create(self.ctx.handle, C.byref(cfg), C.byref(h)),
                "dspsr_amd_filterbank_create")
@@ -282,6 +285,10 @@ class FilterbankEngine:
     def npass(self, raw_input: bool = True) -> int:
         """Transform passes of a call: 2 (short responses on the 8-bit block), 3, or 4 (two-pass inverse)."""
         return int(lib.dspsr_amd_filterbank_npass(self.handle, 1 if raw_input else 0))
+
+    def presplit(self) -> bool:
+        """True: the forward row pass splits the polarisations and the inverse pass loads them ready."""
+        return bool(lib.dspsr_amd_filterbank_presplit(self.handle))
 
     def fold_is_fused(self) -> int:
         """0: perform_fold runs Detection + Fold launches; 1: it folds inside the last filterbank pass with exact time-order

@@ -264,6 +264,7 @@ namespace HIP
       cfg.max_parts = max_parts;
       cfg.force_four_pass = 0;
       cfg.fused_fold = fused_fold;
+      cfg.split_in_inverse = 0;
       const float* kernel = 0;
       uint64_t ncomplex = 0;
       if (chain) chain->flush ();
@@ -390,6 +391,7 @@ namespace HIP
       cfg.max_parts = 0;
       cfg.force_four_pass = 0;
       cfg.fused_fold = DSPSR_AMD_FUSED_AUTO;
+      cfg.split_in_inverse = 0;
       const uint64_t nsamp_step = convolution->get_minimum_samples () - convolution->get_minimum_samples_lost ();
       in_step = nsamp_step * (cfg.real_input ? 1 : 2);             // floats between parts (Convolution.C:386)
       out_step = in_step;                                          // the output is written at the same float offset (:441)

@@ -113,6 +113,10 @@ typedef struct {
                                three-pass convolution or the grouping of a convolution's channels; same results to rounding in every case */
   uint32_t fused_fold;      /* dspsr_amd_filterbank_perform_fold: DSPSR_AMD_FUSED_AUTO (fold inside the last filterbank
                                pass when the channel tiles fill the chip), _ALWAYS, _NEVER -- same sums bit for bit */
+  uint32_t split_in_inverse; /* 0 => real dual-polarisation input on the three-pass path: the forward row pass forms the Hermitian
+                               split and stores the two polarisations, the inverse pass loads them ready
+                               (dspsr_amd_filterbank_presplit() == 1); 1: the inverse pass splits, as it does for every other
+                               input and path (comparison runs and tests) -- the same numbers bit for bit */
 } dspsr_amd_filterbank_config;
 #define DSPSR_AMD_FUSED_AUTO 0
 #define DSPSR_AMD_FUSED_ALWAYS 1
@@ -222,6 +226,8 @@ int dspsr_amd_filterbank_fold_is_fused(const dspsr_amd_filterbank* fb);
  * over the spectrum (k_sub_combine); freq_res = R * 2^k a radix-R pass over the pseudo-channels' time series as well
  * (k_time_combine, with Detection and Fold as launches of their own: fold_is_fused() == 0). */
 int dspsr_amd_filterbank_npass(const dspsr_amd_filterbank* fb, int raw_input);
+/* 1: the object's three passes run on the pre-split spectrum (dspsr_amd_filterbank_config::split_in_inverse), else 0 */
+int dspsr_amd_filterbank_presplit(const dspsr_amd_filterbank* fb);
 int dspsr_amd_filterbank_perform_fold(dspsr_amd_filterbank* fb, const float* in_f32_dev, uint64_t in_chan_stride,
                                       uint64_t in_pol_stride, uint64_t in_step, const int8_t* raw_dev, int raw_layout,
                                       float scale, int state, dspsr_amd_fold* fold, uint64_t npart);

@@ -7,7 +7,7 @@ id=$1
 cd "$(dirname "$0")/../dspsr_amd/csrc"
 make --no-print-directory BBENCH= >/dev/null
 case $id in
-  1) u="fb_fwd_cols";; 2) u="fb_fwd_rows";; 3) u="fb_inv_chan fb_inv_chan_fold";; 4) u="fb_four_pass";; 6|7) u="fb_two_pass";; 8) u="tfp";;
+  1) u="fb_fwd_cols fb_fwd_cols_rm";; 2) u="fb_fwd_rows";; 3) u="fb_inv_chan fb_inv_chan_fold";; 4) u="fb_four_pass";; 6|7) u="fb_two_pass";; 8) u="tfp";;
   *) echo "unknown kernel id $id"; exit 1;;
 esac
 o=../../build/obj_st$id

@@ -127,6 +127,15 @@ SYMBOLS = {
     "dspsr_amd_cyclic_fold_zero": (_i, [_vp]),
     "dspsr_amd_cyclic_fold_lagdata_dev": (_vp, [_vp]),
     "dspsr_amd_cyclic_fold_synch_lags": (_i, [_vp, _vp]),
+    "dspsr_amd_plfb_check_shape": (_i, [_u32, _u32, _u32, _u32, _u32, _u32, C.c_char_p, _sz]),
+    "dspsr_amd_plfb_check_windows": (_i, [_u32, _u32, _u32, _u32, _u32, _u64, _u64, _u64, _u64, _u64, _vp, _vp, C.c_char_p, _sz]),
+    "dspsr_amd_plfb_create": (_i, [_vp, _pp]),
+    "dspsr_amd_plfb_destroy": (None, [_vp]),
+    "dspsr_amd_plfb_set_shape": (_i, [_vp, _u32, _u32, _u32, _u32, _u32, _u32]),
+    "dspsr_amd_plfb_accumulate": (_i, [_vp, _vp, _u64, _u64, _u64, _u64, _vp, _vp]),
+    "dspsr_amd_plfb_zero": (_i, [_vp]),
+    "dspsr_amd_plfb_profile_dev": (_vp, [_vp]),
+    "dspsr_amd_plfb_synch": (_i, [_vp, _vp]),
     "dspsr_amd_comm_set_library": (_i, [C.c_char_p]),
     "dspsr_amd_comm_unique_id": (_i, [_vp]),
     "dspsr_amd_comm_create": (_i, [_vp, _i, _i, _vp, _pp]),

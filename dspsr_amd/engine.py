@@ -806,6 +806,79 @@ class CyclicFoldEngine:
             pass
 
 
+def plfb_check_shape(nchan_in, npol_in, ndim_in, nchan, npol_out, nbin):
+    """The refusals of PhaseLockedFilterbankEngine.set_shape, on the host alone (no device)."""
+    msg = C.create_string_buffer(400)
+    code = lib.dspsr_amd_plfb_check_shape(nchan_in, npol_in, ndim_in, nchan, npol_out, nbin, msg, len(msg))
+    if code != _lib.OK:
+        raise DspsrAmdError(msg.value.decode())
+
+
+def plfb_check_windows(nchan_in, npol_in, ndim_in, nchan, nbin, in_addr, chan_stride, pol_stride, ndat, idat_start, bins):
+    """The refusals of PhaseLockedFilterbankEngine.accumulate, on the host alone (no device)."""
+    st = np.ascontiguousarray(idat_start, dtype=np.uint64)
+    bn = np.ascontiguousarray(bins, dtype=np.uint32)
+    if st.shape != bn.shape or st.ndim != 1:
+        raise DspsrAmdError("plfb: idat_start and bin must be one-dimensional and of one length")
+    msg = C.create_string_buffer(400)
+    code = lib.dspsr_amd_plfb_check_windows(nchan_in, npol_in, ndim_in, nchan, nbin, in_addr, chan_stride, pol_stride, ndat, st.size,
+                                            st.ctypes.data_as(C.c_void_p), bn.ctypes.data_as(C.c_void_p), msg, len(msg))
+    if code != _lib.OK:
+        raise DspsrAmdError(msg.value.decode())
+
+
+class PhaseLockedFilterbankEngine:
+    """The loop body of dsp::PhaseLockedFilterbank::transformation (Signal/Pulsar/PhaseLockedFilterbank.C:254-297) on the device;
+    owns the device-resident profile [nchan_in * nchan][npol_out][nbin]."""
+
+    def __init__(self, ctx: Context):
+        self.ctx = ctx
+        h = C.c_void_p()
+        _check(ctx.handle, lib.dspsr_amd_plfb_create(ctx.handle, C.byref(h)), "dspsr_amd_plfb_create")
+        self.handle = h
+        self.shape = None
+
+    def set_shape(self, nchan_in, npol_in, ndim_in, nchan, npol_out, nbin):
+        _check(self.ctx.handle, lib.dspsr_amd_plfb_set_shape(self.handle, nchan_in, npol_in, ndim_in, nchan, npol_out, nbin),
+               "dspsr_amd_plfb_set_shape")
+        self.shape = (nchan_in * nchan, npol_out, nbin)
+
+    def accumulate(self, inp, ndat, idat_start, bins):
+        """inp: float32 device tensor [nchan_in][npol_in][>= ndat * ndim_in] (FPT order); windows (idat_start[w], bins[w]) in
+        time order."""
+        st = np.ascontiguousarray(idat_start, dtype=np.uint64)
+        bn = np.ascontiguousarray(bins, dtype=np.uint32)
+        if st.shape != bn.shape or st.ndim != 1:
+            raise DspsrAmdError("plfb: idat_start and bin must be one-dimensional and of one length")
+        cs, ps = _strides3(inp)
+        _check(self.ctx.handle, lib.dspsr_amd_plfb_accumulate(self.handle, inp.data_ptr(), cs, ps, ndat, st.size,
+                                                              st.ctypes.data_as(C.c_void_p), bn.ctypes.data_as(C.c_void_p)),
+               "dspsr_amd_plfb_accumulate")
+
+    def zero(self):
+        _check(self.ctx.handle, lib.dspsr_amd_plfb_zero(self.handle), "dspsr_amd_plfb_zero")
+
+    def get_profile_ptr(self):
+        return lib.dspsr_amd_plfb_profile_dev(self.handle)
+
+    def synch(self) -> np.ndarray:
+        """The profile on the host, [nchan_in * nchan][npol_out][nbin] (blocks)."""
+        out = np.empty(self.shape, dtype=np.float32)
+        _check(self.ctx.handle, lib.dspsr_amd_plfb_synch(self.handle, out.ctypes.data_as(C.c_void_p)), "dspsr_amd_plfb_synch")
+        return out
+
+    def close(self):
+        if self.handle and self.ctx.handle:
+            lib.dspsr_amd_plfb_destroy(self.handle)
+        self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class Communicator:
     """The sub-integration exchange over RCCL / xGMI behind the C-ABI (dspsr_amd_comm_*, csrc/comm.hip): the same entry
     points DSPSR's C++ host calls.  One per pipeline context.  `unique_id` = the 128 bytes of `Communicator.unique_id()`

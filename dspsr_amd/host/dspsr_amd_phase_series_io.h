@@ -94,6 +94,9 @@ namespace HIP
     const double period = f.number ("FOLDING_PERIOD");
     if (period > 0) out->set_folding_period (period);
     out->set_reference_phase (f.number ("REFERENCE_PHASE"));
+    // `-G`: spectra per second and the band-swap bookkeeping of dsp::PhaseLockedFilterbank (PhaseLockedFilterbank.C:146-159)
+    if (!f.text ("RATE").empty ()) out->set_rate (f.number ("RATE"));
+    if (!f.text ("NSUB_SWAP").empty ()) out->set_nsub_swap (unsigned (f.number ("NSUB_SWAP")));
     out->increment_integration_length (f.number ("INTEGRATION_LENGTH"));
     out->set_ndat_expected (uint64_t (f.number ("NDAT_TOTAL")));
     out->set_end_time (out->get_start_time () + f.number ("INTEGRATION_LENGTH"));

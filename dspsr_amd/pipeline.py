@@ -19,7 +19,7 @@ from dataclasses import dataclass
 import numpy as np
 
 from . import _lib
-from .engine import (Context, ConvolutionEngine, CyclicFoldEngine, Dedispersion, DspsrAmdError, FilterbankEngine, FoldEngine, Rescale, SampleDelay, add_fpt, copy_data_fpt, fourth_moment,
+from .engine import (Context, ConvolutionEngine, CyclicFoldEngine, Dedispersion, DspsrAmdError, FilterbankEngine, FoldEngine, PhaseLockedFilterbankEngine, plfb_check_shape, Rescale, SampleDelay, add_fpt, copy_data_fpt, fourth_moment,
                      dedispersion_sample_delays, detect_raw, eight_bit_scale, fscrunch_fpt, pscrunch_tfp, sigproc_digitize, sigproc_digitize_fpt,
                      tfp_filterbank, tscrunch_fpt)
 
@@ -74,6 +74,10 @@ class Config:
     fourth_moment: bool = False            # -4: fold the Stokes parameters and their ten pairwise products (dsp::FourthMoment,
                                            # LoadToFold1.C:557-568): detection forced to Stokes with ndim 4 (:1119-1123), the fold has
                                            # shape (nchan, 1, 14, nbin), the fused fold is off
+    plfb_nbin: int = 0                     # -G nbin: phase-locked filterbank (dsp::PhaseLockedFilterbank replaces Detection + Fold,
+                                           # LoadToFold1.C:386-456): pulse-phase-resolved spectra in nbin phase bins.  0: off
+    plfb_nchan: int = 0                    # channels per window of -G; 0 = the reference's choice, the largest power of two <=
+                                           # period * rate / nbin (PhaseLockedFilterbank.C:65-73); output polarisations = npol (:425)
     npol: int = 4                          # -d: the reference's config->npol.  This path detects the four products (4); the field
                                            # decides the branch of LoadToFold1.C:552-568 only: with 1 or 3 it wins over -4, which is
                                            # then ignored
@@ -469,16 +473,18 @@ PHASE_SERIES_HDR_SIZE = 4096
 
 
 def write_phase_series(path, sub, info: "InputInfo", cfg: "Config", *, nchan=None, npol=1, scale=1.0, division=0,
-                       start_seconds=0.0, folding_period=0.0, reference_phase=0.0, state=None, ndim=None):
+                       start_seconds=0.0, folding_period=0.0, reference_phase=0.0, state=None, ndim=None, rate=None, nsub_swap=None):
     """sub: a dict as LoadToFold.subints holds (hits, integration_length, ndat_total, profile or profile_dev).  A -4 run
-    (fourth_moment_active(cfg)) writes STATE FourthMoment, NPOL 1, NDIM 14 whatever npol / state say."""
+    (fourth_moment_active(cfg)) writes STATE FourthMoment, NPOL 1, NDIM 14 whatever npol / state say.  rate / nsub_swap (a -G run:
+    spectra per second, and the input channels whose raw transform order the output channels keep) add the keys RATE and
+    NSUB_SWAP; without them the header is what it always was."""
     prof = sub.get("profile")
     if prof is None:
         prof = sub["profile_dev"].cpu().numpy()
     nchan = nchan or cfg.nchan
     nbin = len(sub["hits"])
     ndim = ndim or cfg.ndim
-    if fourth_moment_active(cfg) and not cfg.cyclic_nchan:
+    if fourth_moment_active(cfg) and not cfg.cyclic_nchan and not cfg.plfb_nbin:
         npol, ndim, state = 1, 14, "FourthMoment"
     prof = np.ascontiguousarray(np.asarray(prof, dtype="<f4").reshape(nchan, npol, nbin, ndim))
     keys = [("HDR_MAGIC", PHASE_SERIES_MAGIC), ("HDR_VERSION", "1.0"), ("HDR_SIZE", PHASE_SERIES_HDR_SIZE),
@@ -490,6 +496,10 @@ def write_phase_series(path, sub, info: "InputInfo", cfg: "Config", *, nchan=Non
             ("OBS_OFFSET_SECONDS", repr(float(start_seconds))), ("DIVISION", division),
             ("INTEGRATION_LENGTH", repr(float(sub["integration_length"]))), ("NDAT_TOTAL", int(sub["ndat_total"])),
             ("FOLDING_PERIOD", repr(float(folding_period))), ("REFERENCE_PHASE", repr(float(reference_phase)))]
+    if rate is not None:
+        keys.append(("RATE", repr(float(rate))))
+    if nsub_swap is not None:
+        keys.append(("NSUB_SWAP", int(nsub_swap)))
     text = "".join("%-20s %s\n" % (k, v) for k, v in keys)
     if len(text) >= PHASE_SERIES_HDR_SIZE:
         raise DspsrAmdError("write_phase_series: header does not fit %d bytes" % PHASE_SERIES_HDR_SIZE)
@@ -873,6 +883,87 @@ def cyclic_check(cfg: "Config", info: "InputInfo", ntargets=0, subband=None, dum
     return cyclic_geometry(cfg, info)
 
 
+def plfb_choose_nchan(period, rate, nbin):
+    """PhaseLockedFilterbank::prepare (PhaseLockedFilterbank.C:65-73): the largest power of two <= the samples per phase bin."""
+    samples_per_bin = period * rate / nbin
+    return int(math.pow(2.0, math.floor(math.log(samples_per_bin) / math.log(2.0))))
+
+
+class PlfbPlan:
+    """The windows of dsp::PhaseLockedFilterbank for ONE transformation call over the whole stream (PhaseLockedFilterbank.C:
+    208-235): `divider` is a TurnsDivider with D = 1 / nbin (:36-40).  Every division yields a window at its first sample --
+    max(its lower boundary, the end of the division before), as TimeDivide::set_bounds chains them (TimeDivide.C:146-211) --
+    with the phase bin of TimeDivide.C:486-492: profile_phase = division start phase - reference_phase + D / 2,
+    bin = unsigned(frac / D).  A window is kept iff ndat_fft samples from there exist (:224-228).
+    The plan is a function of the stream, not of how it is cut into blocks: take(avail) hands out, once each and in time order,
+    the windows whose last sample lies in front of stream sample `avail`; what does not fit yet waits for the next call."""
+
+    def __init__(self, divider, nbin, reference_phase, ndat_fft):
+        self.div, self.nbin, self.ref, self.ndat_fft = divider, int(nbin), float(reference_phase), int(ndat_fft)
+        self.k, self.pos, self._cur = 0, 0, None
+
+    def phase_bin(self, k):
+        d = self.div.D
+        x = self.div.start_phase[1] + k * d - self.ref + 0.5 * d
+        return int((x - math.floor(x)) / d)
+
+    def _window(self):
+        """(first sample, bin, end) of the next division that has samples"""
+        if self._cur is None:
+            while self.div.bounds(self.k)[1] <= self.pos:
+                self.k += 1
+            lo, hi = self.div.bounds(self.k)
+            self._cur = (max(lo, self.pos), self.phase_bin(self.k), hi)
+        return self._cur
+
+    def next_start(self):
+        """first sample of the first window not handed out yet"""
+        return self._window()[0]
+
+    def take(self, avail):
+        """(idat_start uint64[], bin uint32[]) in stream samples"""
+        starts, bins = [], []
+        while True:
+            s, b, hi = self._window()
+            if s + self.ndat_fft > avail:
+                break
+            starts.append(s)
+            bins.append(b)
+            self.pos, self.k, self._cur = hi, self.k + 1, None
+        return np.array(starts, dtype=np.uint64), np.array(bins, dtype=np.uint32)
+
+
+def plfb_check(cfg: "Config", info: "InputInfo", ntargets=0, subband=None, dump_before=()):
+    """What a -G run refuses, before any device resource is opened."""
+    who = "dspsr_amd.LoadToFold: the phase-locked filterbank (-G)"
+    if cfg.subint_seconds > 0 or cfg.subint_turns > 0:
+        # Subint<PhaseLockedFilterbank> limits only the END of each piece (dsp/Subint.h:312-318) while transformation re-walks the
+        # block from its first sample (PhaseLockedFilterbank.C:166-185): every piece after the first counts its windows twice
+        raise DspsrAmdError("%s is not built for sub-integrations (-L, -s, -turns): the reference's Subint<PhaseLockedFilterbank> "
+                            "re-walks each block from its start and counts windows twice" % who)
+    if cfg.interchan_dedispersion:
+        raise DspsrAmdError("%s is not built for -K" % who)
+    if ntargets > 1:
+        raise DspsrAmdError("%s folds one pulsar; %d targets given" % (who, ntargets))
+    if cfg.cyclic_nchan > 0:
+        raise DspsrAmdError("%s and cyclic spectra (-cyclic) exclude each other" % who)
+    if cfg.fourth_moment:
+        raise DspsrAmdError("%s and fourth moments (-4) exclude each other: it replaces Detection" % who)
+    if cfg.convolve_when != "during":
+        raise DspsrAmdError("%s is built for -F N:D (convolve_when = during), not %r" % (who, cfg.convolve_when))
+    if subband is not None:
+        raise DspsrAmdError("%s is not built for sub-band sharded runs / communicators" % who)
+    if tuple(dump_before):
+        raise DspsrAmdError("%s: the dump taps are not built for it" % who)
+    if cfg.npol not in (1, 2, 4):
+        raise DspsrAmdError("dsp::PhaseLockedFilterbank::set_npol Invalid npol (%d)" % cfg.npol)      # PhaseLockedFilterbank.C:44-46
+    if info.npol < 2 and cfg.npol > 1:                                                                 # :138-141
+        raise DspsrAmdError("dsp::PhaseLockedFilterbank::transformation Not enough input polns (%d) for output npol (%d)"
+                            % (info.npol, cfg.npol))
+    if cfg.plfb_nchan < 0 or cfg.plfb_nbin < 1 or (cfg.plfb_nchan == 1 and cfg.plfb_nbin < 2):
+        raise DspsrAmdError("dsp::PhaseLockedFilterbank::prepare invalid dimensions.  nchan=%d nbin=%d" % (cfg.plfb_nchan, cfg.plfb_nbin))
+
+
 def fourth_moment_active(cfg: "Config") -> bool:
     """The branch order of LoadToFold1.C:552-568: npol 1 or 3 takes the first branch, -4 only the second."""
     return bool(cfg.fourth_moment) and cfg.npol not in (1, 3)
@@ -910,6 +1001,9 @@ class LoadToFold:
         targets = list(targets or [])
         self.pulsars = []
         self.cyclic = None
+        self.plfb = None
+        if cfg.plfb_nbin > 0:                            # (before any device resource is opened)
+            plfb_check(cfg, info, len(targets), subband, dump_before)
         self.moments = fourth_moment_active(cfg)         # -4: the fold is (nchan, 1, 14, nbin), fed by FoldEngine.fold_moments
         cfg = fourth_moment_check(cfg, len(targets), subband)
         if cfg.cyclic_nchan > 0:                         # (before any device resource is opened)
@@ -948,6 +1042,8 @@ class LoadToFold:
             raise DspsrAmdError("dsp::Fold::fold no polynomial and no period specified")   # Fold.C:638-640
         if cfg.cyclic_nchan > 0:
             return self._init_cyclic(device, stream)
+        if cfg.plfb_nbin > 0:
+            return self._init_plfb(device, stream)
         if info.npol != 2:
             raise DspsrAmdError("dsp::Detection::polarimetry Cannot detect polarization when npol != 2")
         if cfg.convolve_when not in ("during", "after", "before", "never"):
@@ -1137,10 +1233,116 @@ class LoadToFold:
         self.integration_length = 0.0
         self.ndat_total = 0
 
+    def _init_plfb(self, device, stream):
+        """`dspsr -G nbin`: the convolving filterbank writes its complex rows and dsp::PhaseLockedFilterbank consumes them
+        (LoadToFold1.C:386-456); Detection and Fold are not built.  One integration over the whole stream: the windows are those
+        of ONE transformation call (PlfbPlan), whatever the block size.  The rows of a block sit behind a head room that holds the
+        carried tail -- the samples from the first window that does not fit yet -- so that a window may span two blocks."""
+        import torch
+        cfg, info = self.cfg, self.info
+        if cfg.nchan % info.nchan:
+            raise DspsrAmdError("dsp::Filterbank::make_preparations output nchan=%d not a multiple of input nchan=%d"
+                                % (cfg.nchan, info.nchan))
+        self.response = Dedispersion(info.centre_frequency, info.bandwidth, cfg.dispersion_measure, input_nchan=info.nchan,
+                                     ndim=info.ndim)
+        if cfg.freq_res:
+            self.response.set_frequency_resolution(cfg.freq_res)
+        self.response.match(cfg.nchan)
+        r = self.response
+        nsub = cfg.nchan // info.nchan
+        self.in_nchan, self.nchan_out = info.nchan, cfg.nchan
+        n_fft = nsub * r.ndat
+        nsamp_fft = 2 * n_fft if info.ndim == 1 else n_fft
+        self.out_rate = info.rate * (float(r.ndat) / float(nsamp_fft))
+        self.out_start = info.start_seconds + r.impulse_pos / self.out_rate
+        self.scalefac = float(n_fft) * float(r.ndat)
+        # PhaseLockedFilterbank::prepare (:59-83), all on the host
+        period, polyco, reference_phase = self._ephemeris()
+        if period <= 0:
+            period = 1.0 / polyco.frequency(info.mjd_day, info.mjd_sec + self.out_start)
+        nmax = plfb_choose_nchan(period, self.out_rate, cfg.plfb_nbin)
+        nchan = cfg.plfb_nchan if cfg.plfb_nchan >= 2 else nmax
+        if nchan > nmax:
+            import warnings
+            warnings.warn("dsp::PhaseLockedFilterbank::prepare warning selected nchan=%d > suggested max=%d" % (nchan, nmax))
+        plfb_check_shape(cfg.nchan, info.npol, 2, nchan, cfg.npol, cfg.plfb_nbin)       # the rows are Analytic: ndat_fft = nchan
+        state = {1: "Intensity", 2: "PPQQ", 4: "Coherence"}[cfg.npol]                  # :128-133
+        self.plfb_geometry = {"nchan_fft": nchan, "ndat_fft": nchan, "nchan": cfg.nchan * nchan, "npol": cfg.npol, "ndim": 1,
+                              "nbin": cfg.plfb_nbin, "state": state, "rate": self.out_rate / nchan, "nsub_swap": cfg.nchan,
+                              "scale": self.scalefac * nchan}                          # :143-149
+        self.ctx = Context(device, stream)
+        self.fb = FilterbankEngine(self.ctx).setup(nsub, r.ndat, r.impulse_pos, r.impulse_neg, info.nchan, info.npol, info.ndim == 1,
+                                                   r.kernel, max_parts=cfg.max_parts, force_four_pass=0 if cfg.two_pass else 2,
+                                                   fused_fold=_lib.FUSED_NEVER)
+        self.nkeep, self.nsamp_step, self.nsamp_overlap = self.fb.nkeep, self.fb.nsamp_step, self.fb.nsamp_overlap
+        self.npol_out = cfg.npol
+        self.fold = None
+        self.plfb = PhaseLockedFilterbankEngine(self.ctx)
+        self.plfb.set_shape(cfg.nchan, info.npol, 2, nchan, cfg.npol, cfg.plfb_nbin)
+        self.plfb_plan = PlfbPlan(self._turns_divider(*self._ephemeris(), turns=1.0 / cfg.plfb_nbin), cfg.plfb_nbin, reference_phase,
+                                  nchan)
+        self.plfb_head, self.plfb_tail = nchan, 0           # head room (samples) in front of a block's rows; samples carried in it
+        self.scale8 = eight_bit_scale()
+        self.layout = _lib.RAW_CASPSR if info.machine == "CASPSR" else _lib.RAW_GENERIC
+        self.sample_delay, self.sd_carried, self.sd_head = None, 0, 0
+        self.voltages = torch.empty((self.nchan_out, info.npol, 2 * (self.plfb_head + cfg.parts_per_block * self.nkeep)),
+                                    dtype=torch.float32, device="cuda:%d" % device)
+        self.fused_mode, self.fused_fold = 0, False
+        self.optime, self.dumps, self._dump_cplx = {}, {}, None
+        self.hits = np.zeros(cfg.plfb_nbin, dtype=np.uint32)
+        self.integration_length, self.ndat_total = 0.0, 0
+        self.nsamples_in, self.ndat_out = 0, 0
+        self.subints = []
+
+    def _process_block_plfb(self, raw, npart, events):
+        """Filterbank -> complex rows behind the carried tail -> every window of the plan that now lies inside the rows, in one
+        accumulate call; then the samples from the next window's start on are carried in front of the next block's rows."""
+        ndat, head, tail = npart * self.nkeep, self.plfb_head, self.plfb_tail
+        if events is not None:
+            events[0].record()
+        self._op("Filterbank", lambda: self.fb.perform_raw(raw, self.layout, self.scale8, self.voltages[:, :, 2 * head:], npart))
+        if events is not None:
+            events[1].record()
+        base, avail = self.ndat_out - tail, self.ndat_out + ndat     # stream samples of the first row sample / behind the last
+        starts, bins = self.plfb_plan.take(avail)
+        if len(starts):
+            rows = self.voltages[:, :, 2 * (head - tail):]
+            rel = (starts.astype(np.int64) - base).astype(np.uint64)
+            self._op("PhaseLockedFilterbank", lambda: self.plfb.accumulate(rows, tail + ndat, rel, bins))
+            time_per_fft = float(self.plfb_geometry["ndat_fft"]) / self.out_rate
+            for b in bins:                                            # PhaseLockedFilterbank.C:233-235, window by window
+                self.hits[b] += 1
+                self.ndat_total += 1
+                self.integration_length += time_per_fft
+        nxt = self.plfb_plan.next_start()
+        keep = avail - nxt if nxt < avail else 0                      # (< ndat_fft: the window at nxt does not fit)
+        if keep:
+            move_tail_fpt(self.ctx, self.voltages, head - keep, head + ndat - keep, keep, unit=2)
+        self.plfb_tail = keep
+        self.ndat_out += ndat
+        self.nsamples_in += npart * self.nsamp_step
+
+    def _finish_plfb_subint(self):
+        """The integration so far: profile [nchan * nchan_fft][npol][nbin][1] on the host, with the members
+        PhaseLockedFilterbank.C:123-159 sets on its output"""
+        if not self.ndat_total:
+            return
+        g = self.plfb_geometry
+        prof = self._op("PhaseLockedFilterbank::synch", lambda: self.plfb.synch())
+        self.subints.append({"hits": self.hits.copy(), "integration_length": self.integration_length, "ndat_total": self.ndat_total,
+                             "profile": prof[..., None], "state": g["state"], "rate": g["rate"], "nsub_swap": g["nsub_swap"],
+                             "scale": g["scale"]})
+        self.plfb.zero()
+        self.hits[:] = 0
+        self.integration_length = 0.0
+        self.ndat_total = 0
+
     def _init_targets(self, targets):
         """nbin per target (Fold::choose_nbin for its period where the target gives none); several targets: one FoldEngine each,
         the fused fold off (the detected rows are shared)."""
         cfg, info = self.cfg, self.info
+        if self.plfb is not None:                        # -G: the phase bins are plfb_nbin; -b plays no part
+            return
         nbins = []
         for t in targets:
             p = t.folding_period if t.polyco is None else 1.0 / t.polyco.frequency(info.mjd_day, info.mjd_sec + self.out_start)
@@ -1348,6 +1550,8 @@ class LoadToFold:
                                 % (raw.numel(), self.block_bytes(npart)))
         if self.cyclic is not None:
             return self._process_block_cyclic(raw, npart, events)
+        if self.plfb is not None:
+            return self._process_block_plfb(raw, npart, events)
         ndat = npart * self.nkeep
         state = _lib.STOKES if cfg.stokes else _lib.COHERENCE
         if "Detection" in self.dumps:                        # the filterbank's complex output: one extra pass, taps only
@@ -1451,8 +1655,8 @@ class LoadToFold:
             return self._turns.pieces(self.ndat_out, ndat)
         return [(0, ndat, 0, False)]
 
-    def _turns_divider(self, folding_period, polyco, reference_phase):
-        """TimeDivide in turns mode for one pulsar's ephemeris"""
+    def _turns_divider(self, folding_period, polyco, reference_phase, turns=None):
+        """TimeDivide in turns mode for one pulsar's ephemeris (turns: the division length when it is not -s / -turns)"""
         cfg = self.cfg
         if folding_period > 0:
             p = folding_period
@@ -1464,8 +1668,8 @@ class LoadToFold:
             phase = lambda t: polyco.phase(day, s0 + t)
             iphase = lambda ph, guess: polyco.iphase(ph, day, s0 + guess) - s0
             pg = 1.0 / polyco.frequency(day, s0 + self.out_start)
-        return TurnsDivider(phase, iphase, pg, self.out_start, self.out_rate, cfg.subint_turns, reference_phase,
-                            cfg.fractional_pulses)
+        return TurnsDivider(phase, iphase, pg, self.out_start, self.out_rate, cfg.subint_turns if turns is None else turns,
+                            reference_phase, cfg.fractional_pulses)
 
     _turns = None
     _subint_comm = (None, 0, 1, None)     # (dist, rank, world, gather_buffer[, replicas]) used at sub-integration dumps
@@ -1476,6 +1680,8 @@ class LoadToFold:
         self._subint_comm = (dist, rank, world, gather_buffer, replicas)
 
     def _no_cyclic(self, what):
+        if self.plfb is not None:
+            raise DspsrAmdError("dspsr_amd.LoadToFold.%s: the phase-locked filterbank is not built for a multi-GPU exchange" % what)
         if self.cyclic is not None:
             raise DspsrAmdError("dspsr_amd.LoadToFold.%s: cyclic spectra are not built for a multi-GPU exchange" % what)
         if self.moments:
@@ -1598,6 +1804,8 @@ class LoadToFold:
             return
         if self.cyclic is not None:
             return self._finish_cyclic_subint()
+        if self.plfb is not None:
+            return self._finish_plfb_subint()
         if self.comm is not None:
             # (one exchange in flight per communicator.  The result of the previous one is COPIED here even with
             #  copy_subints False: start() below may grow the pinned buffer a view would point into -- a view is only handed
@@ -1712,6 +1920,8 @@ class LoadToFold:
             self.fold.close()
         if self.cyclic is not None:
             self.cyclic.close()
+        if self.plfb is not None:
+            self.plfb.close()
         for p in self.pulsars:
             p.fold.close()
         self.ctx.close()

@@ -39,6 +39,7 @@ typedef struct dspsr_amd_ctx dspsr_amd_ctx;
 typedef struct dspsr_amd_filterbank dspsr_amd_filterbank;
 typedef struct dspsr_amd_fold dspsr_amd_fold;
 typedef struct dspsr_amd_cyclic_fold dspsr_amd_cyclic_fold;
+typedef struct dspsr_amd_plfb dspsr_amd_plfb;
 
 /* ---- context: one per pipeline thread / GPU, bound to one stream (SingleThread.C:213-290) ---- */
 /* hip_stream: a hipStream_t to enqueue on (NULL = the legacy default stream), or
@@ -446,6 +447,47 @@ float* dspsr_amd_cyclic_fold_lagdata_dev(dspsr_amd_cyclic_fold* fold);
 /* copy to the host in the same order and wait (CyclicFoldEngineCUDA.cu:72-107): a C++ caller hands it to
  * dsp::CyclicFoldEngine::synch, any other to dspsr_amd_cyclic_lags_to_spectra */
 int dspsr_amd_cyclic_fold_synch_lags(dspsr_amd_cyclic_fold* fold, float* lagdata_host);
+
+/* ---- dsp::PhaseLockedFilterbank: pulse-phase-resolved spectra, `dspsr -G nbin` (LoadToFold1.C:386-456) ---------------------
+ * Replaces the loop body of Signal/Pulsar/PhaseLockedFilterbank.C:254-297 (the reference has a CPU implementation only).  The
+ * caller walks its own bin_divider (:208-235) and hands every accepted division over as a WINDOW (idat_start, bin), in time order.
+ *   input   float rows as the filterbank and dspsr_amd_unpack_fpt write them: element (chan, pol, t) at
+ *           in_dev + chan * chan_stride + pol * pol_stride + t * ndim_in floats; ndim_in 2 = Analytic, 1 = Nyquist (:100-110);
+ *           ndat samples per row.  Analytic rows 8-byte aligned (pointer, even strides), Nyquist rows float aligned.
+ *   window  ndat_fft = nchan (Analytic) or 2 nchan (Nyquist) samples from idat_start; X_p[k] = sum_n x_p[idat_start + n]
+ *           exp(-2 pi i k n / ndat_fft), k < nchan, unnormalised (fcc1d / bins 0 .. nchan-1 of frc1d, :263-266; the Nyquist
+ *           form is one nchan-point complex transform of the packed pairs plus the Hermitian split).
+ *   output  profile [nchan_in * nchan][npol_out][nbin] floats, channel chan * nchan + k in raw transform order, DC first (the
+ *           reference records nsub_swap = nchan_in instead of reordering, :149,159).  npol_out 1: += |X_0|^2 + |X_1|^2 over the
+ *           input polarisations present; 2: plane p += |X_p|^2; 4: also plane 2 += re0 re1 + im0 im1, plane 3 += re0 im1 - im0 re1
+ *           (:269-295).
+ *   limits  nchan a power of two in [2, 8192] (the reference takes any length); nchan < 2 && nbin < 2 refused (:61-63);
+ *           npol_out in {1, 2, 4} (:44-46); npol_in 1 allows npol_out 1 only (:138-141); nchan_in <= 65535; ndat and nwin
+ *           < 2^31 per call; every window inside the rows (idat_start + ndat_fft <= ndat), bin < nbin, idat_start
+ *           non-decreasing.  Anything else: DSPSR_AMD_EINVAL with a message, nothing launched.
+ * Sums are float and deterministic, without atomics: the windows of a call are grouped by bin and cut into segments (the cut
+ * depends on the call's arguments alone); the windows of a bin are added in time order within a segment, segments in segment
+ * order, and every profile element has one owner per launch.  Bins without a window in a call are not written.  The profile
+ * accumulates over calls until dspsr_amd_plfb_zero; set_shape with a new shape allocates (DSPSR_AMD_ENOMEM) and zeroes, with the
+ * values it already has it keeps the sums.
+ * The two check functions are the refusals alone, on the host, with the message in msg (no device, no context): set_shape and
+ * accumulate call them first. */
+int dspsr_amd_plfb_check_shape(uint32_t nchan_in, uint32_t npol_in, uint32_t ndim_in, uint32_t nchan, uint32_t npol_out,
+                               uint32_t nbin, char* msg, size_t msg_len);
+int dspsr_amd_plfb_check_windows(uint32_t nchan_in, uint32_t npol_in, uint32_t ndim_in, uint32_t nchan, uint32_t nbin,
+                                 uint64_t in_addr, uint64_t chan_stride, uint64_t pol_stride, uint64_t ndat, uint64_t nwin,
+                                 const uint64_t* idat_start_host, const uint32_t* bin_host, char* msg, size_t msg_len);
+int dspsr_amd_plfb_create(dspsr_amd_ctx* ctx, dspsr_amd_plfb** plfb);
+void dspsr_amd_plfb_destroy(dspsr_amd_plfb* plfb);
+int dspsr_amd_plfb_set_shape(dspsr_amd_plfb* plfb, uint32_t nchan_in, uint32_t npol_in, uint32_t ndim_in, uint32_t nchan,
+                             uint32_t npol_out, uint32_t nbin);
+int dspsr_amd_plfb_accumulate(dspsr_amd_plfb* plfb, const float* in_dev, uint64_t chan_stride, uint64_t pol_stride, uint64_t ndat,
+                              uint64_t nwin, const uint64_t* idat_start_host, const uint32_t* bin_host);
+int dspsr_amd_plfb_zero(dspsr_amd_plfb* plfb);                                             /* PhaseLockedFilterbank.C:151-152 */
+/* device profile [nchan_in * nchan][npol_out][nbin], valid in stream order */
+float* dspsr_amd_plfb_profile_dev(dspsr_amd_plfb* plfb);
+/* copy it to the host and wait */
+int dspsr_amd_plfb_synch(dspsr_amd_plfb* plfb, float* profile_host);
 
 /* ---- the sub-integration dump over RCCL / xGMI: the ONE exchange of the path -----------------------------------------
  * Reference hook: dsp::Subint<Fold>::transformation emits the finished sub-integration (Signal/Pulsar/dsp/Subint.h:291-303);

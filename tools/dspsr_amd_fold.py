@@ -10,6 +10,9 @@ dspsr_amd.dada.fold_file for trying the engine on a DADA file; not a re-implemen
                     ten pairwise products folded into every bin -- files of STATE FourthMoment, NPOL 1, NDIM 14)
   dspsr_amd_fold.py -F 64:D -cyclic 256 [-cyclicoversample 4] [-d 1|2|4] ...   (cyclic spectra: dsp::CyclicFold instead of
                     Detection + Fold; -d is then the number of output polarisations, default 4 -- 1 for single-polarisation input)
+  dspsr_amd_fold.py -F 16:D -G 256 [-d 1|2|4] ...   (phase-locked filterbank: dsp::PhaseLockedFilterbank instead of Detection + Fold;
+                    pulse-phase-resolved spectra in 256 phase bins, one file of NDIM 1 with RATE and NSUB_SWAP; -d is the number of
+                    output polarisations, default 4)
 
 Every completed sub-integration is written as <prefix>_<n>.ps (the PhaseSeries hand-off file of INTEGRATION.md:
 raw sums + hits; dsp::Archiver's normalisation is the reader's job).
@@ -41,6 +44,7 @@ def parse_args(argv=None):
     ap.add_argument("-4", dest="fourth", action="store_true", help="compute fourth-order moments")
     ap.add_argument("-cyclic", dest="cyclic", type=int, default=0, help="form cyclic spectra with N channels per filterbank channel")
     ap.add_argument("-cyclicoversample", dest="cyclic_mover", type=int, default=1, help="use M times as many lags to improve the cyclic channel isolation")
+    ap.add_argument("-G", dest="plfb_nbin", type=int, default=0, help="create phase-locked filterbank with nbin phase bins")
     ap.add_argument("-r", dest="record", action="store_true", help="report the time spent in each operation")
     ap.add_argument("--dump", action="append", default=[], help="dump the input of this operation (Detection, Fold)")
     ap.add_argument("-O", dest="prefix", default="dspsr_amd", help="output file name prefix")
@@ -86,7 +90,8 @@ def main(argv=None):
     pfold = period if period > 0 else 1.0 / polyco.frequency(info.mjd_day, info.mjd_sec) if polyco else 0.0
     nbin = a.nbin or (pipeline.choose_nbin(pfold, out_rate) if pfold else targets[0].nbin)
     cfg = pipeline.Config(nchan=nchan, dispersion_measure=dm, nbin=nbin, folding_period=period, freq_res=a.nfft,
-                          subint_seconds=a.subint, subint_turns=1.0 if a.single else a.turns, ndim=1 if a.cyclic else a.ndim,
+                          subint_seconds=a.subint, subint_turns=1.0 if a.single else a.turns, ndim=1 if a.cyclic or a.plfb_nbin else a.ndim,
+                          plfb_nbin=a.plfb_nbin, npol=a.ndim if a.plfb_nbin else 4,
                           cyclic_nchan=a.cyclic, cyclic_mover=a.cyclic_mover, cyclic_npol=(a.ndim if info.npol == 2 else 1) if a.cyclic else 0,
                           interchan_dedispersion=a.interchan, record_time=a.record, fourth_moment=a.fourth,
                           convolve_when="never" if when == "after" and dm == 0.0 else when)
@@ -104,10 +109,13 @@ def main(argv=None):
     if a.cyclic:                                            # nchan * nchan_spec / mover channels, ndim 1 (CyclicFold.C:96-119)
         g = pipeline.cyclic_geometry(cfg, info)
         cyc = {"nchan": g["nchan"], "state": g["state"]}
+    if a.plfb_nbin:                                         # PhaseLockedFilterbank.C:123-159: what it sets on its output
+        g = lt.plfb_geometry
+        cyc = {"nchan": g["nchan"], "state": g["state"], "rate": g["rate"], "nsub_swap": g["nsub_swap"]}
     for pattern, subints, pf in outputs:
         for n, sub in enumerate(subints):
             path = pattern % n
-            pipeline.write_phase_series(path, sub, info, cfg, npol=lt.npol_out, scale=lt.scalefac, division=n,
+            pipeline.write_phase_series(path, sub, info, cfg, npol=lt.npol_out, scale=sub.get("scale", lt.scalefac), division=n,
                                         start_seconds=lt.out_start, folding_period=pf, **cyc)
             print("dspsr_amd: %s  integration %.6f s  %d samples" % (path, sub["integration_length"], sub["ndat_total"]))
     if a.record:

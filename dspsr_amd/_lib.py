@@ -63,6 +63,8 @@ SYMBOLS = {
     "dspsr_amd_filterbank_create": (_i, [_vp, C.POINTER(FilterbankConfig), _pp]),
     "dspsr_amd_filterbank_destroy": (None, [_vp]),
     "dspsr_amd_filterbank_set_kernel": (_i, [_vp, _vp, _u64]),
+    "dspsr_amd_filterbank_set_response_matrix": (_i, [_vp, _vp, _u64]),
+    "dspsr_amd_filterbank_response_ndim": (_i, [_vp]),
     "dspsr_amd_filterbank_sizes": (_i, [_vp, C.POINTER(_u64), C.POINTER(_u64), C.POINTER(_u64), C.POINTER(_u32)]),
     "dspsr_amd_filterbank_perform": (_i, [_vp, _vp, _u64, _u64, _vp, _u64, _u64, _u64, _u64, _u64]),
     "dspsr_amd_filterbank_perform_raw": (_i, [_vp, _vp, _i, _f, _vp, _u64, _u64, _u64, _u64]),

@@ -601,6 +601,7 @@ k2_t fb_pick2(int logf, bool full, bool presplit = false);
 k3_t fb_pick3(int logf, bool full, bool presplit = false);       // plain
 k3_t fb_pick3f(int logf, bool full, bool presplit = false);      // fused fold
 k3_t fb_pick3s(int logf, bool full, bool presplit = false);      // search mode (detection + time scrunch)
+k3_t fb_pick3m(int logf, bool full, bool presplit = false);      // matrix response, plain output (fb_inv_chan_matrix.hip)
 k3a_t fb_pick3a(int logf, bool blocked, bool real, bool full);
 k3b_t fb_pick3b(int logf, bool foldb, bool full);
 // two-pass path (fb_two_pass.hip): pass 1 on whole columns, rows + inverse pass (M = 2^logm, Fb = 2^(13 - logm)), the 8-bit regroup

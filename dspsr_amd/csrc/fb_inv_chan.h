@@ -32,7 +32,36 @@ namespace dspsr_amd {
 // EPIP = EPI + 4 * PRESPLIT: the pre-split forms are k_inv_chan<., 4 | 5 | 6, .>, the others keep the names they had.  (As a
 // fourth template parameter the flag renames every instantiation; as a device body behind two kernels the fused pre-split form
 // came out with 12 bytes of scratch: profiles/r07_experiments.txt.)
+// EPIP bit 8 (FB_EPI_MATRIX, plain output only: k_inv_chan<., 8 | 12, .>, fb_inv_chan_matrix.hip): the response is one Jones matrix
+// per bin (Response::operate(data1, data2), Response.C:515-585) -- `kernel` then points at 32 bytes per bin, [channel][bin], as two
+// 16-byte halves (f11, f21) and (f22, f12): the host's array as it stands (Response.C:614-640).  A tile's matrices would be 128
+// registers per thread, so they are not kept: every item streams them in groups of FB_MATRIX_GROUP elements, one group ahead of
+// the group being multiplied, and a workgroup always walks the parts of a tile one after the other so that the re-reads find the
+// tile's rows warm.
 constexpr int FB_EPI_PRESPLIT = 4;
+constexpr int FB_EPI_MATRIX = 8;
+constexpr int FB_MATRIX_GROUP = 4;     // elements per response load group: 32 registers, two groups live at a time
+
+// (d1', d2') = J (d1, d2) for the two polarisations a cx2 holds, h0 = (f11, f21), h1 = (f22, f12).  Each output is the scalar
+// path's complex multiply of its own polarisation with the diagonal element (cmul on a cx2 rounds like cmuls), then the two
+// real products of the other polarisation's term added one after the other as Response.C:570-582 writes them -- with
+// f12 = f21 = 0 every one of those adds 0 * d through an fma, so diag(k, k) gives the bits of the scalar response k.
+// (The reference forms d2' as f21 d1 + f22 d2; here the sum starts from f22 d2 for that equality to hold on both outputs.)
+DEV cx2 cmatmul(const cx2 d, const float4 h0, const float4 h1)
+{
+  const cx2 dg = make_cx2(make_float2(h0.x, h0.y), make_float2(h1.x, h1.y));    // (f11, f22)
+  const cx2 of = make_cx2(make_float2(h1.z, h1.w), make_float2(h0.z, h0.w));    // (f12, f21)
+  cx2 sw;                                                                        // (d2, d1)
+  sw.x = (v2f){d.x[1], d.x[0]};
+  sw.y = (v2f){d.y[1], d.y[0]};
+  cx2 r = cmul(d, dg);
+  r.x = r.x + of.x * sw.x;
+  r.x = r.x - of.y * sw.y;
+  r.y = r.y + of.y * sw.x;
+  r.y = r.y + of.x * sw.y;
+  return r;
+}
+
 template <int LOGF, int EPIP, int LOGT>
 __global__ __launch_bounds__(512) void k_inv_chan(const FbGeom g, const cf* __restrict__ X,
                                                   const cf* __restrict__ kernel, const FbOut out,
@@ -41,6 +70,8 @@ __global__ __launch_bounds__(512) void k_inv_chan(const FbGeom g, const cf* __re
 {
   constexpr int EPI = EPIP & 3;
   constexpr bool PRESPLIT = (EPIP & FB_EPI_PRESPLIT) != 0;
+  constexpr bool MATRIX = (EPIP & FB_EPI_MATRIX) != 0;
+  static_assert(!MATRIX || EPI == 0, "the matrix response has the plain epilogue only");
   typedef FftPlan<LOGF> P;
   constexpr bool FOLD = EPI == 1, SEARCH = EPI == 2;
   extern __shared__ __attribute__((aligned(16))) cf lds[];
@@ -148,7 +179,8 @@ __global__ __launch_bounds__(512) void k_inv_chan(const FbGeom g, const cf* __re
     }
   };
   // chirp of a tile (fetched at the start of the item: keeps the prefetch at 64 registers)
-  auto load_chirp = [&](const Item item, cf (&kk)[PTS / 2]) {
+  auto load_chirp = [&](const Item item, cf (&kk)[MATRIX ? 1 : PTS / 2]) {
+    if constexpr (MATRIX) return;
     const uint32_t ktile = item.tile;
     if (kernel) {                                 // uniform; outside the unrolled loads (no per-load branch / vmcnt(0))
       constexpr uint32_t MS = 1u << (LOGF - P::LOGR1);
@@ -213,7 +245,9 @@ __global__ __launch_bounds__(512) void k_inv_chan(const FbGeom g, const cf* __re
   // Without the fold the order of the items is free.  When every workgroup gets the same number of tiles it also walks the
   // parts of a tile one after the other, so that the tile's chirp stays in registers (one chirp read per launch, not per
   // part); otherwise the items are dealt XCD-wise as in the other passes.
-  const bool tile_major = EPI != 0 || (ntile >= gridDim.x && ntile % gridDim.x == 0);
+  // (MATRIX: tile after tile whenever the tiles alone occupy every workgroup, also with a remainder -- the response is re-read
+  //  per part, from the cache while the tile's rows are warm; fewer tiles than workgroups keep the dealing below, part fastest)
+  const bool tile_major = EPI != 0 || (ntile >= gridDim.x && (MATRIX || ntile % gridDim.x == 0));
   auto next_item = [&](const uint32_t jj, Item& it) -> bool {
     if (EPI != 0 || tile_major) {
       const uint32_t q = jj / fnp;                     // (32-bit; jj counts this workgroup's items)
@@ -241,7 +275,7 @@ __global__ __launch_bounds__(512) void k_inv_chan(const FbGeom g, const cf* __re
   if (!next_item(j, item)) return;
   Abk raw[PTS / 2];
   fetch(item, raw, -1);
-  cf kk[PTS / 2];                       // chirp of the current tile
+  cf kk[MATRIX ? 1 : PTS / 2];          // chirp of the current tile (MATRIX: none, the response is streamed per item)
   uint32_t kk_tile = ~0u;
   // FOLD: plan entry of this thread for the item about to be processed (tid < number of active bins of the part)
   uint32_t fe0_cur = 0, fn_cur = 0;
@@ -280,9 +314,11 @@ __global__ __launch_bounds__(512) void k_inv_chan(const FbGeom g, const cf* __re
     {
       // FOLD: a workgroup walks the parts of ITS tile, so consecutive items share the chirp rows: they are loaded when
       // the tile changes and stay in registers (the load and its latency were 22 % of the tile, profiles/r02c_*)
-      if (item.tile != kk_tile) {
-        load_chirp(item, kk);
-        kk_tile = item.tile;
+      if constexpr (!MATRIX) {
+        if (item.tile != kk_tile) {
+          load_chirp(item, kk);
+          kk_tile = item.tile;
+        }
       }
       if constexpr (FOLD) {
         // this part's active-bin entries travel with the chirp loads and are parked in LDS (double buffered: slower
@@ -313,8 +349,52 @@ __global__ __launch_bounds__(512) void k_inv_chan(const FbGeom g, const cf* __re
           if ((tid >> 1) == 0) raw[0].b = special;
         }
       }
+      // MATRIX: x[q] = J[q] (pol0, pol1)[q], Response.C:543-584.  `operand(q)` is what the scalar forms hand to cmuls.  The matrices
+      // of element q are the two float4 at rm_at(q) (the bins of load_chirp); group gq + 1 is requested in front of the
+      // multiplies of group gq, whose raw[] registers die as its x[] are formed: 64 + 2 * 32 registers live, never more
+      // (the schedule barriers keep the scheduler from hoisting all sixteen elements' loads to the top: 128 registers)
+      [[maybe_unused]] auto matrix_apply = [&](auto&& operand) {
+        constexpr uint32_t MS = 1u << (LOGF - P::LOGR1);
+        constexpr int MG = PRESPLIT ? FB_MATRIX_GROUP : FB_MATRIX_GROUP / 2, NMG = PTS / 2 / MG;
+        const float4* __restrict__ rm = (const float4*)kernel;
+        auto rm_at = [&](const int q) -> const float4* {
+          const uint32_t eb = P::G1 * tid + 2 * (q / P::R1);
+          return rm + 2 * (((uint64_t)(item.tile * T3 + ((eb & (T - 1)) >> 1)) << LOGF) + (eb >> logT) + (uint32_t)(q % P::R1) * MS);
+        };
+        float4 f[2][MG][2];
+#pragma unroll
+        for (int e = 0; e < MG; e++) {
+          const float4* __restrict__ p = rm_at(e);
+          f[0][e][0] = p[0]; f[0][e][1] = p[1];
+        }
+#pragma unroll
+        for (int gq = 0; gq < NMG; gq++) {
+          if (gq + 1 < NMG) {
+#pragma unroll
+            for (int e = 0; e < MG; e++) {
+              const float4* __restrict__ p = rm_at((gq + 1) * MG + e);
+              f[(gq + 1) & 1][e][0] = p[0]; f[(gq + 1) & 1][e][1] = p[1];
+            }
+          }
+          __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+          for (int e = 0; e < MG; e++) x[gq * MG + e] = cmatmul(operand(gq * MG + e), f[gq & 1][e][0], f[gq & 1][e][1]);
+          __builtin_amdgcn_sched_barrier(0);
+        }
+      };
       // (the uniform real/complex choice is made once, outside the unrolled loops: no branch per element)
-      if constexpr (PRESPLIT) {
+      if constexpr (MATRIX) {
+        if (PRESPLIT || !g.real_input) {            // (two polarisations always: set_response_matrix refuses npol == 1)
+          matrix_apply([&](const int q) { return make_cx2(raw[q].a, raw[q].b); });
+        } else {
+          matrix_apply([&](const int q) {
+            const Abk r = raw[q];
+            const cf x0 = make_float2(0.5f * (r.a.x + r.b.x), 0.5f * (r.a.y - r.b.y));
+            const cf x1 = make_float2(0.5f * (r.a.y + r.b.y), 0.5f * (r.b.x - r.a.x));
+            return make_cx2(x0, x1);
+          });
+        }
+      } else if constexpr (PRESPLIT) {
 #pragma unroll
         for (int q = 0; q < PTS / 2; q++) x[q] = cmuls(make_cx2(raw[q].a, raw[q].b), kk[q]);          // Response::operate, Response.C:429-441
       } else if (g.real_input) {

@@ -30,6 +30,8 @@ struct dspsr_amd_filterbank_impl {
   float* det = nullptr;     // detected block of perform_fold when the fused kernel would not fill the chip
   size_t det_floats = 0;
   bool kernel_set = false;
+  float4* rmatrix = nullptr;  // matrix response (set_response_matrix): nchan_subband * freq_res bins of two float4, (f11, f21) (f22, f12)
+  k3_t k3m = nullptr;         // ... its inverse pass (fb_pick3m; LDS limit set by the first set_response_matrix)
   // kernels of this geometry, chosen and given their dynamic-LDS limit once, at create time
   k1_t k1_w1 = nullptr, k1_w4 = nullptr;                     // pass 1: one word per sample pair / generic loads
   k2_t k2 = nullptr;
@@ -488,7 +490,7 @@ static void fb_setup_conv(dspsr_amd_filterbank* fb)
 // frees the device buffers and the object (create's failures come here directly: nothing of theirs was launched)
 static void fb_release(dspsr_amd_filterbank* fb)
 {
-  for (void* p : {(void*)fb->A, (void*)fb->X, (void*)fb->kernel, (void*)fb->kernel_nat, (void*)fb->S1, (void*)fb->S2, (void*)fb->Rt,
+  for (void* p : {(void*)fb->A, (void*)fb->X, (void*)fb->kernel, (void*)fb->rmatrix, (void*)fb->kernel_nat, (void*)fb->S1, (void*)fb->S2, (void*)fb->Rt,
                   (void*)fb->det, (void*)fb->fpart, (void*)fb->msum, (void*)fb->dsub, (void*)fb->Xp, (void*)fb->Y, (void*)fb->tw_lo,
                   (void*)fb->tw_lo_m})
     if (p) (void)hipFree(p);
@@ -527,12 +529,20 @@ extern "C" void dspsr_amd_filterbank_destroy(dspsr_amd_filterbank* fb)
   fb_release(fb);
 }
 
+// set_kernel replaces a matrix response
+static void fb_drop_matrix(dspsr_amd_filterbank* fb)
+{
+  if (fb->rmatrix) (void)hipFree(fb->rmatrix);
+  fb->rmatrix = nullptr;
+}
+
 extern "C" int dspsr_amd_filterbank_set_kernel(dspsr_amd_filterbank* fb, const float* kernel_host, uint64_t ncomplex)
 {
   if (!fb) return DSPSR_AMD_EINVAL;
   if (!kernel_host) {  // no response: plain filterbank
     if (fb->kernel) (void)hipFree(fb->kernel);
     fb->kernel = nullptr;
+    fb_drop_matrix(fb);
     fb->kernel_set = true;
     return DSPSR_AMD_OK;
   }
@@ -587,7 +597,67 @@ extern "C" int dspsr_amd_filterbank_set_kernel(dspsr_amd_filterbank* fb, const f
   if (e != hipSuccess)
     return fb_fail(fb->ctx, DSPSR_AMD_EHIP, "dspsr_amd_filterbank_set_kernel: %s", hipGetErrorString(e));
   fb->kernel_set = true;
+  fb_drop_matrix(fb);
   return DSPSR_AMD_OK;
+}
+
+// Matrix response (Response::operate(data1, data2), Response.C:515-585): the three-pass path of a power-of-two geometry only;
+// every limit is checked before anything is allocated or changed
+extern "C" int dspsr_amd_filterbank_set_response_matrix(dspsr_amd_filterbank* fb, const float* response_host, uint64_t nmatrix)
+{
+  if (!fb || !response_host) return DSPSR_AMD_EINVAL;
+  const dspsr_amd_filterbank_config& c = fb->cfg;
+  const char* fn = "dspsr_amd_filterbank_set_response_matrix";
+  if (c.npol != 2)
+    return fb_fail(fb->ctx, DSPSR_AMD_EINVAL, "%s: matrix convolution needs npol == 2 (npol=%u)", fn, c.npol);
+  if (c.input_nchan != 1)
+    return fb_fail(fb->ctx, DSPSR_AMD_EINVAL, "dsp::Filterbank::make_preparations matrix convolution untested for > one input channel "
+                   "(input_nchan=%u)", c.input_nchan);
+  if (c.freq_res < 2)
+    return fb_fail(fb->ctx, DSPSR_AMD_EINVAL, "%s: the non-convolving filterbank (freq_res=%u) takes no matrix response: freq_res >= 2", fn,
+                   c.freq_res);
+  if (c.nchan_subband < 2)
+    return fb_fail(fb->ctx, DSPSR_AMD_EINVAL, "%s: nchan_subband=%u (dsp::Convolution shapes) takes no matrix response: nchan_subband >= 2",
+                   fn, c.nchan_subband);
+  if (!ispow2(c.freq_res) || !ispow2(c.nchan_subband))
+    return fb_fail(fb->ctx, DSPSR_AMD_EINVAL, "%s: nchan_subband=%u and freq_res=%u must be powers of two (no odd factor) for a matrix "
+                   "response", fn, c.nchan_subband, c.freq_res);
+  if (c.force_four_pass == 1)
+    return fb_fail(fb->ctx, DSPSR_AMD_EINVAL, "%s: force_four_pass=1: the four-pass inverse takes no matrix response", fn);
+  if (fb->g.four_pass || c.freq_res > 8192)
+    return fb_fail(fb->ctx, DSPSR_AMD_EINVAL, "%s: freq_res=%u > 8192 (the four-pass inverse) takes no matrix response", fn, c.freq_res);
+  if (nmatrix != fb->N)
+    return fb_fail(fb->ctx, DSPSR_AMD_EINVAL, "%s: response has %llu matrices, expected nchan_subband*freq_res = %llu", fn,
+                   (unsigned long long)nmatrix, (unsigned long long)fb->N);
+  if (!fb->k3m) {
+    const FbGeom& g = fb->g;
+    k3_t k = fb_pick3m(g.logM, g.logT3 + 1 == full_logt(g.logM), fb->presplit);
+    if (!k) return fb_fail(fb->ctx, DSPSR_AMD_EINVAL, "%s: no kernel for this geometry", fn);
+    const hipError_t e = allow_lds({{k, fb->lds3}});
+    if (e != hipSuccess) return fb_fail(fb->ctx, DSPSR_AMD_EHIP, "%s: hipFuncSetAttribute: %s", fn, hipGetErrorString(e));
+    fb->k3m = k;
+  }
+  const size_t bytes = (size_t)fb->N * 2 * sizeof(float4);
+  float4* dev = fb->rmatrix;
+  if (!dev && hipMalloc((void**)&dev, bytes) != hipSuccess)
+    return fb_fail(fb->ctx, DSPSR_AMD_ENOMEM, "%s: hipMalloc of %zu response bytes failed", fn, bytes);
+  // (the device image is the host array: bin k's eight floats are its two 16-byte halves)
+  hipError_t e = hipMemcpyAsync(dev, response_host, bytes, hipMemcpyHostToDevice, fb->ctx->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(fb->ctx->stream);
+  if (e != hipSuccess) {
+    if (!fb->rmatrix) (void)hipFree(dev);
+    return fb_fail(fb->ctx, DSPSR_AMD_EHIP, "%s: %s", fn, hipGetErrorString(e));
+  }
+  fb->rmatrix = dev;
+  if (fb->kernel) (void)hipFree(fb->kernel);
+  fb->kernel = nullptr;
+  fb->kernel_set = true;
+  return DSPSR_AMD_OK;
+}
+
+extern "C" int dspsr_amd_filterbank_response_ndim(const dspsr_amd_filterbank* fb)
+{
+  return !fb || !fb->kernel_set ? 0 : fb->rmatrix ? 8 : fb->kernel ? 2 : 0;
 }
 
 extern "C" int dspsr_amd_filterbank_sizes(const dspsr_amd_filterbank* fb, uint64_t* nsamp_fft,
@@ -780,7 +850,7 @@ static int fb_run_conv3(dspsr_amd_filterbank* fb, const FbIn& in, const FbOut& o
 static bool fb_takes_two_pass(const dspsr_amd_filterbank* fb, const FbIn& in, const FbOut& out)
 {
   const FbGeom& g = fb->g;
-  return fb->two_pass && in.kind == 1 && !g.real_input && g.npol == 2 && out.kind != 4 && (in.part_step % 4) == 0 &&
+  return fb->two_pass && !fb->rmatrix && in.kind == 1 && !g.real_input && g.npol == 2 && out.kind != 4 && (in.part_step % 4) == 0 &&
          (fb->k1c ? ((uintptr_t)in.base % (fb->cfg.input_nchan == 1 ? 16 : 4)) == 0
                   : (fb->cfg.input_nchan == 1 && ((uintptr_t)in.base % 16) == 0));
 }
@@ -830,7 +900,8 @@ static int fb_each_group(dspsr_amd_filterbank* fb, const FbIn& in, const FbOut& 
     ci.nchan = fb->cfg.input_nchan;
     FbOut co = out;
     co.chan0 = ichan * g.C;
-    const cf* kern = fb->kernel ? fb->kernel + (uint64_t)ichan * fb->N : nullptr;
+    // (matrix response: input_nchan == 1; the inverse pass k3m reads the pointer as 32-byte bins)
+    const cf* kern = fb->rmatrix ? (const cf*)fb->rmatrix : fb->kernel ? fb->kernel + (uint64_t)ichan * fb->N : nullptr;
     uint32_t nb = 0;
     for (uint64_t part0 = 0; part0 < npart; part0 += nb) {
       nb = fb_group_parts(npart - part0, fb->max_parts, g, fb->nseq, g);
@@ -1108,7 +1179,11 @@ static int fb_run(dspsr_amd_filterbank* fb, const FbIn& in, const FbOut& out, ui
   const int rc = fb_pass1(fb, in, chan_stride, two, false, &p1);
   if (rc != DSPSR_AMD_OK) return rc;
   const FbPassKernels k = {p1.raww == 1 ? fb->k1_w1 : fb->k1_w4, p1.raww == 1 ? fb->k1d_w1 : fb->k1d_w4,
-                           out.kind == 3 ? fb->k3f : out.kind == 5 ? fb->k3s : fb->k3, out.kind == 4 ? fb->k3bf : fb->k3b};
+                           out.kind == 3 ? fb->k3f : out.kind == 5 ? fb->k3s : fb->rmatrix ? fb->k3m : fb->k3,
+                           out.kind == 4 ? fb->k3bf : fb->k3b};
+  // (set_response_matrix admits the three-pass path of a power-of-two geometry only; fold and search detour through kind 2 / 1)
+  if (fb->rmatrix && (out.kind > 2 || g.four_pass || g.nsub > 1 || fb->msub))
+    return fb_fail(ctx, DSPSR_AMD_EINVAL, "dspsr_amd_filterbank_perform: output kind %d has no matrix-response form", out.kind);
   if (!k.k1 || !fb->k2 || (g.four_pass ? (!fb->k3a || !k.k3b) : !k.k3))
     return fb_fail(ctx, DSPSR_AMD_EINVAL, "dspsr_amd_filterbank_perform: no kernel for this geometry");
   if (g.nsub > 1) return fb_run_subbands(fb, in, out, npart, chan_stride, k.k3);
@@ -1229,7 +1304,7 @@ extern "C" int dspsr_amd_filterbank_perform_detect(dspsr_amd_filterbank* fb, con
 static bool fb_search_fits(const dspsr_amd_filterbank* fb, uint32_t npo, uint32_t sf, uint32_t* G_out)
 {
   const FbGeom& g = fb->g;
-  if (g.four_pass || fb->msub || !fb->k3s || g.nkeep >= 65536 || sf >= 32768) return false;
+  if (g.four_pass || fb->msub || fb->rmatrix || !fb->k3s || g.nkeep >= 65536 || sf >= 32768) return false;
   const uint64_t ngmax = ((uint64_t)g.nkeep + 2ull * sf - 2) / sf;
   const uint32_t G = (uint32_t)ngmax | 1u;
   const uint64_t floats = ((uint64_t)npo << g.logT3) * sf * G;
@@ -1317,7 +1392,7 @@ extern "C" int dspsr_amd_filterbank_npass(const dspsr_amd_filterbank* fb, int ra
   if (fb->conv1_logM >= 0 && !raw_input) return 1;
   if (fb->conv3_logM >= 0 && !raw_input) return 3;
   if (fb->g.four_pass) return 4;
-  return fb->two_pass && raw_input ? 2 : 3;
+  return fb->two_pass && raw_input && !fb->rmatrix ? 2 : 3;
 }
 
 extern "C" int dspsr_amd_filterbank_fold_is_fused(const dspsr_amd_filterbank* fb)
@@ -1325,6 +1400,7 @@ extern "C" int dspsr_amd_filterbank_fold_is_fused(const dspsr_amd_filterbank* fb
   // (short responses of dsp::Convolution shapes: Detection inside the one-pass kernel, Fold as a launch of its own -- the segment-sum
   //  fold belongs to the four-pass kernels)
   if (fb && (fb->conv1_logM >= 0 || fb->conv3_logM >= 0)) return 0;     // (the three-pass convolution likewise: Detection in pass C, Fold behind it)
+  if (fb && fb->rmatrix) return 0;                                      // (matrix response: no fused instantiation; Detection + Fold)
   if (!fb || fb->msub || fb->plain_logC >= 0) return 0;            // (freq_res = 3 * 2^k / 5 * 2^k: the last step is a pass of its own, k_time_combine)
   // (segment sums pay when most of the transform is kept: at -F 64:D -x 16384 only 1817 of 16384 samples are, the unfused pass
   //  writes just those, and the fused one measured 541 against 458 us per 8 parts)

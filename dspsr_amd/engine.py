@@ -157,11 +157,16 @@ class FilterbankEngine:
 
     def setup(self, nchan_subband, freq_res, nfilt_pos, nfilt_neg, input_nchan=1, npol=2, real_input=True,
               kernel: np.ndarray | None = None, max_parts: int = 1, force_four_pass: bool | int = False,
-              fused_fold: int = _lib.FUSED_AUTO, split_in_inverse: bool = False):
+              fused_fold: int = _lib.FUSED_AUTO, split_in_inverse: bool = False, response_matrix: np.ndarray | None = None):
         """force_four_pass: False / 0 = passes chosen from the geometry, True / 1 = two-pass inverse everywhere, 2 = never the
         two-pass path of short responses (dspsr_amd_filterbank_config::force_four_pass).
         split_in_inverse: True keeps the Hermitian split of real dual-polarisation input in the inverse pass
-        (dspsr_amd_filterbank_config::split_in_inverse); see presplit()."""
+        (dspsr_amd_filterbank_config::split_in_inverse); see presplit().
+        response_matrix: float32 [nchan_subband * freq_res][8], one Jones matrix per bin as f11, f21, f22, f12 (`dspsr -pac`,
+        dspsr_amd_filterbank_set_response_matrix); mutually exclusive with kernel.  When the library refuses it the object
+        stays created, without a response: set_kernel() may still be called."""
+        if kernel is not None and response_matrix is not None:
+            raise DspsrAmdError("dspsr_amd.FilterbankEngine.setup: kernel and response_matrix are mutually exclusive")
         self.close()
         cfg = _lib.FilterbankConfig(nchan_subband, freq_res, nfilt_pos, nfilt_neg, input_nchan, npol,
                                     1 if real_input else 0, max_parts, int(force_four_pass), fused_fold,
@@ -171,16 +176,38 @@ class FilterbankEngine:
                "dspsr_amd_filterbank_create")
         self.handle = h
         self.cfg = cfg
-        if kernel is not None:
-            k = np.ascontiguousarray(kernel, dtype=np.complex64)
-            _check(self.ctx.handle, lib.dspsr_amd_filterbank_set_kernel(h, k.ctypes.data_as(C.c_void_p), k.size),
-                   "dspsr_amd_filterbank_set_kernel")
-        else:
-            _check(self.ctx.handle, lib.dspsr_amd_filterbank_set_kernel(h, None, 0), "dspsr_amd_filterbank_set_kernel")
         a, b, c, d = C.c_uint64(), C.c_uint64(), C.c_uint64(), C.c_uint32()
         lib.dspsr_amd_filterbank_sizes(h, C.byref(a), C.byref(b), C.byref(c), C.byref(d))
         self.nsamp_fft, self.nsamp_overlap, self.nsamp_step, self.nkeep = a.value, b.value, c.value, d.value
+        if response_matrix is not None:
+            self.set_response_matrix(response_matrix)
+        else:
+            self.set_kernel(kernel)
         return self
+
+    def set_kernel(self, kernel: np.ndarray | None):
+        """The scalar response (complex64, input_nchan * nchan_subband * freq_res bins), or None for no response; replaces a
+        matrix response."""
+        if kernel is not None:
+            k = np.ascontiguousarray(kernel, dtype=np.complex64)
+            _check(self.ctx.handle, lib.dspsr_amd_filterbank_set_kernel(self.handle, k.ctypes.data_as(C.c_void_p), k.size),
+                   "dspsr_amd_filterbank_set_kernel")
+        else:
+            _check(self.ctx.handle, lib.dspsr_amd_filterbank_set_kernel(self.handle, None, 0), "dspsr_amd_filterbank_set_kernel")
+
+    def set_response_matrix(self, response_matrix: np.ndarray):
+        """One Jones matrix per bin, float32 [nchan_subband * freq_res][8] in the order f11, f21, f22, f12 (Response.C:614-640);
+        replaces a scalar response.  Refused (DspsrAmdError naming the limit) for npol 1, several input channels, freq_res 1 or
+        above 8192, nchan_subband 1, odd factors, force_four_pass = 1 and a wrong number of matrices."""
+        m = np.ascontiguousarray(response_matrix, dtype=np.float32)
+        if m.ndim != 2 or m.shape[1] != 8:
+            raise DspsrAmdError("dspsr_amd.FilterbankEngine.set_response_matrix: the response must be float32 [nmatrix][8]")
+        _check(self.ctx.handle, lib.dspsr_amd_filterbank_set_response_matrix(self.handle, m.ctypes.data_as(C.c_void_p), m.shape[0]),
+               "dspsr_amd_filterbank_set_response_matrix")
+
+    def response_ndim(self) -> int:
+        """Response::get_ndim of what the object holds: 0 none, 2 complex (kernel), 8 Jones (response_matrix)."""
+        return int(lib.dspsr_amd_filterbank_response_ndim(self.handle))
 
     def _need(self, what, have, need):
         if have < need:

@@ -230,6 +230,10 @@ namespace HIP
   };
 
   //! dsp::Filterbank::Engine (FilterbankEngine.h:15-44)
+  //! Response::get_ndim () where the class has it (dsp::Response does: 2 complex, 8 Jones), else 2
+  template <class R> auto response_ndim_of (const R* r, int) -> decltype (unsigned (r->get_ndim ())) { return r->get_ndim (); }
+  template <class R> unsigned response_ndim_of (const R*, long) { return 2; }
+
   class FilterbankEngine : public dsp::Filterbank::Engine
   {
   public:
@@ -271,6 +275,10 @@ namespace HIP
       if (filterbank->has_response ())
       {
         const dsp::Response* response = filterbank->get_response ();
+        // (a matrix response, Filterbank.C:186-206, is 8 floats per bin: never handed on as a chirp -- dspsr_amd_matrix_engine.h)
+        if (response_ndim_of (response, 0) != 2)
+          throw Error (InvalidState, "HIP::FilterbankEngine::setup", "response ndim=%u != 2: a matrix response needs "
+                       "HIP::MatrixFilterbankEngine", response_ndim_of (response, 0));
         cfg.nfilt_pos = response->get_impulse_pos ();
         cfg.nfilt_neg = response->get_impulse_neg ();
         kernel = response->get_datptr (0, 0);   // host-built, already swapped (Response.C:132-181)

@@ -78,6 +78,10 @@ class Config:
                                            # LoadToFold1.C:386-456): pulse-phase-resolved spectra in nbin phase bins.  0: off
     plfb_nchan: int = 0                    # channels per window of -G; 0 = the reference's choice, the largest power of two <=
                                            # period * rate / nbin (PhaseLockedFilterbank.C:65-73); output polarisations = npol (:425)
+    calibrator: object = None              # -pac: phase-coherent polarimetric calibration (LoadToFold1.C:270-289).  A path to an .npz
+                                           # with `freq` (MHz) and `jones` [n][2][2], or a (freq, jones) pair (polcal.load_calibrator):
+                                           # the Jones matrix of every response bin times the chirp goes to the filterbank as a matrix
+                                           # response (calibrator_response below says what it works with and what it refuses)
     npol: int = 4                          # -d: the reference's config->npol.  This path detects the four products (4); the field
                                            # decides the branch of LoadToFold1.C:552-568 only: with 1 or 3 it wins over -4, which is
                                            # then ignored
@@ -964,6 +968,47 @@ def plfb_check(cfg: "Config", info: "InputInfo", ntargets=0, subband=None, dump_
         raise DspsrAmdError("dsp::PhaseLockedFilterbank::prepare invalid dimensions.  nchan=%d nbin=%d" % (cfg.plfb_nchan, cfg.plfb_nbin))
 
 
+def calibrator_response(cfg: "Config", info: "InputInfo", subband=None):
+    """`dspsr -pac`: the matrix response of a run with cfg.calibrator -- (Dedispersion response, float32 [N][8]) -- or None without
+    one.  Host work only: LoadToFold calls it before it opens any device resource, and every limit raises DspsrAmdError by name.
+
+    The product PolnCalibration x Dedispersion (LoadToFold1.C:270-289) is applied inside the convolving filterbank, so:
+      * convolve_when must be "during" (-F N:D): the reference builds the ResponseProduct for that filterbank only;
+      * one input channel (Filterbank.C:199-201 throws for more; sub-band sharded runs read several) and two polarisations;
+      * a geometry the library takes: nchan and freq_res powers of two, nchan >= 2, 2 <= freq_res <= 8192.
+    Detection, Fold, -K, -L / -s, several pulsars and -4 consume the filterbank's detected output as before and work with a
+    calibrator (the fold is never fused into the inverse pass then: FilterbankEngine.fold_is_fused() == 0).  -cyclic and -G
+    read the complex rows of filterbank objects of their own: refused with a calibrator, by name."""
+    if cfg.calibrator is None:
+        return None
+    from . import polcal
+    if cfg.cyclic_nchan > 0:
+        raise DspsrAmdError("dspsr_amd.LoadToFold: -pac (calibrator) with -cyclic is not built")
+    if cfg.plfb_nbin > 0:
+        raise DspsrAmdError("dspsr_amd.LoadToFold: -pac (calibrator) with -G (phase-locked filterbank) is not built")
+    if cfg.convolve_when != "during":
+        raise DspsrAmdError("dspsr_amd.LoadToFold: -pac (calibrator) needs convolve_when='during' (-F N:D), not %r: the matrix "
+                            "response is applied inside the convolving filterbank" % (cfg.convolve_when,))
+    if info.nchan != 1 or subband is not None:
+        raise DspsrAmdError("dsp::Filterbank::make_preparations matrix convolution untested for > one input channel (input nchan=%d)"
+                            % info.nchan)
+    if info.npol != 2:
+        raise DspsrAmdError("dspsr_amd.LoadToFold: -pac (calibrator) needs two polarisations (npol=%d)" % info.npol)
+    freq, jones = polcal.load_calibrator(cfg.calibrator) if isinstance(cfg.calibrator, (str, bytes, os.PathLike)) \
+        else polcal._check_calibrator(*cfg.calibrator)
+    response = Dedispersion(info.centre_frequency, info.bandwidth, cfg.dispersion_measure, input_nchan=1, ndim=info.ndim,
+                            fractional_delay=cfg.interchan_dedispersion)
+    if cfg.freq_res:
+        response.set_frequency_resolution(cfg.freq_res)
+    response.match(cfg.nchan)
+    pow2 = lambda v: v >= 1 and not (v & (v - 1))
+    if cfg.nchan < 2 or not pow2(cfg.nchan) or not pow2(response.ndat) or not 2 <= response.ndat <= 8192:
+        raise DspsrAmdError("dspsr_amd.LoadToFold: -pac (calibrator) needs nchan=%d >= 2 and freq_res=%d in [2, 8192], both powers of "
+                            "two (the three-pass filterbank)" % (cfg.nchan, response.ndat))
+    matrix = polcal.response_product(polcal.jones_response(freq, jones, info, cfg.nchan, response.ndat), response.kernel)
+    return response, matrix
+
+
 def fourth_moment_active(cfg: "Config") -> bool:
     """The branch order of LoadToFold1.C:552-568: npol 1 or 3 takes the first branch, -4 only the second."""
     return bool(cfg.fourth_moment) and cfg.npol not in (1, 3)
@@ -1002,6 +1047,7 @@ class LoadToFold:
         self.pulsars = []
         self.cyclic = None
         self.plfb = None
+        self._calibrated = calibrator_response(cfg, info, subband)      # -pac (before any device resource is opened)
         if cfg.plfb_nbin > 0:                            # (before any device resource is opened)
             plfb_check(cfg, info, len(targets), subband, dump_before)
         self.moments = fourth_moment_active(cfg)         # -4: the fold is (nchan, 1, 14, nbin), fed by FoldEngine.fold_moments
@@ -1065,6 +1111,10 @@ class LoadToFold:
         # engines --------------------------------------------------------------------------
         nsub = cfg.nchan // info.nchan
         kernel = r.kernel
+        # -pac: chirp x Jones per bin as a matrix response instead of the chirp (calibrator_response)
+        matrix = self._calibrated[1] if getattr(self, "_calibrated", None) else None
+        if matrix is not None:
+            kernel = None
         if subband is not None:
             kernel = kernel[subband * nsub * r.ndat:(subband + 1) * nsub * r.ndat]
         self.in_nchan = 1 if subband is not None else info.nchan         # input channels in this instance's blocks
@@ -1073,7 +1123,8 @@ class LoadToFold:
                                                    self.in_nchan, info.npol, info.ndim == 1, kernel,
                                                    max_parts=cfg.max_parts, force_four_pass=0 if cfg.two_pass else 2,
                                                    fused_fold=(_lib.FUSED_NEVER if not cfg.fused_fold else
-                                                               _lib.FUSED_ALWAYS if cfg.force_fused else _lib.FUSED_AUTO))
+                                                               _lib.FUSED_ALWAYS if cfg.force_fused else _lib.FUSED_AUTO),
+                                                   response_matrix=matrix)
         self.nkeep, self.nsamp_step, self.nsamp_overlap = self.fb.nkeep, self.fb.nsamp_step, self.fb.nsamp_overlap
         self.npol_out = 4 // cfg.ndim
         self.fold = FoldEngine(self.ctx)

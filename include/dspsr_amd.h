@@ -128,6 +128,25 @@ int dspsr_amd_filterbank_create(dspsr_amd_ctx* ctx, const dspsr_amd_filterbank_c
 void dspsr_amd_filterbank_destroy(dspsr_amd_filterbank* fb);
 /* host kernel: input_nchan*nchan_subband*freq_res complex floats (response->get_datptr(0,0)); NULL => no response */
 int dspsr_amd_filterbank_set_kernel(dspsr_amd_filterbank* fb, const float* kernel_host, uint64_t ncomplex);
+/* Matrix response (`dspsr -pac`: PolnCalibration x Dedispersion as a ResponseProduct, LoadToFold1.C:270-289; Filterbank.C:186-206
+ * matrix_convolution = response->get_ndim() == 8): one Jones matrix per bin, applied to the spectra d1, d2 of the two polarisations
+ * inside the inverse pass, where the scalar response multiplies them (Response::operate(data1, data2), Response.C:515-585):
+ *     d1' = f11*d1 + f12*d2      d2' = f21*d1 + f22*d2
+ * response_host: nmatrix = nchan_subband*freq_res matrices of 8 floats in the reference's element order f11, f21, f22, f12
+ * (Response::set(vector<Jones>), Response.C:614-640), bin k of output channel k / freq_res -- response->get_datptr(0,0) of an
+ * ndim 8 Response.  The product with the dedispersion chirp is the caller's (Response::operator*=, Response.C:73-104).
+ * Each output is the scalar path's complex multiply of its own polarisation with the diagonal element, then the other
+ * polarisation's two real products added one after the other (Response.C:570-582), so diag(k, k) gives the bits of set_kernel(k).
+ * set_response_matrix and set_kernel replace each other; set_kernel(fb, NULL, 0) clears either.
+ * Accepted objects (else DSPSR_AMD_EINVAL with the limit's name, before any allocation; the object keeps what it had):
+ *   npol == 2; input_nchan == 1 (the reference throws for more, Filterbank.C:199-201); nchan_subband >= 2 and
+ *   2 <= freq_res <= 8192, both powers of two; force_four_pass != 1; real or complex input, split_in_inverse 0 or 1.
+ * With a matrix response every perform entry point works; a geometry of the two-pass path takes the three passes
+ * (dspsr_amd_filterbank_npass() == 3), and perform_fold / perform_search run through the object's internal detected block
+ * (fold_is_fused() == 0, search_is_fused() == 0).  The response is streamed per part by the inverse pass: 32 bytes per bin. */
+int dspsr_amd_filterbank_set_response_matrix(dspsr_amd_filterbank* fb, const float* response_host, uint64_t nmatrix);
+/* Response::get_ndim of what the object holds: 0 none (or not set), 2 complex (set_kernel), 8 Jones (set_response_matrix) */
+int dspsr_amd_filterbank_response_ndim(const dspsr_amd_filterbank* fb);
 /* derived sizes, same arithmetic as Filterbank::make_preparations (Filterbank.C:107-155) */
 int dspsr_amd_filterbank_sizes(const dspsr_amd_filterbank* fb, uint64_t* nsamp_fft, uint64_t* nsamp_overlap,
                                uint64_t* nsamp_step, uint32_t* nkeep);

@@ -13,6 +13,8 @@ dspsr_amd.dada.fold_file for trying the engine on a DADA file; not a re-implemen
   dspsr_amd_fold.py -F 16:D -G 256 [-d 1|2|4] ...   (phase-locked filterbank: dsp::PhaseLockedFilterbank instead of Detection + Fold;
                     pulse-phase-resolved spectra in 256 phase bins, one file of NDIM 1 with RATE and NSUB_SWAP; -d is the number of
                     output polarisations, default 4)
+  dspsr_amd_fold.py -F 64:D -pac cal.npz ...   (phase-coherent polarimetric calibration, dspsr.C:372: the Jones matrix of every
+                    response bin times the chirp, applied inside the filterbank; cal.npz holds `freq` in MHz and `jones` [n][2][2])
 
 Every completed sub-integration is written as <prefix>_<n>.ps (the PhaseSeries hand-off file of INTEGRATION.md:
 raw sums + hits; dsp::Archiver's normalisation is the reader's job).
@@ -45,6 +47,7 @@ def parse_args(argv=None):
     ap.add_argument("-cyclic", dest="cyclic", type=int, default=0, help="form cyclic spectra with N channels per filterbank channel")
     ap.add_argument("-cyclicoversample", dest="cyclic_mover", type=int, default=1, help="use M times as many lags to improve the cyclic channel isolation")
     ap.add_argument("-G", dest="plfb_nbin", type=int, default=0, help="create phase-locked filterbank with nbin phase bins")
+    ap.add_argument("-pac", dest="pac", default=None, help="phase-coherent polarimetric calibration: .npz with freq (MHz) and jones [n][2][2]")
     ap.add_argument("-r", dest="record", action="store_true", help="report the time spent in each operation")
     ap.add_argument("--dump", action="append", default=[], help="dump the input of this operation (Detection, Fold)")
     ap.add_argument("-O", dest="prefix", default="dspsr_amd", help="output file name prefix")
@@ -93,7 +96,7 @@ def main(argv=None):
                           subint_seconds=a.subint, subint_turns=1.0 if a.single else a.turns, ndim=1 if a.cyclic or a.plfb_nbin else a.ndim,
                           plfb_nbin=a.plfb_nbin, npol=a.ndim if a.plfb_nbin else 4,
                           cyclic_nchan=a.cyclic, cyclic_mover=a.cyclic_mover, cyclic_npol=(a.ndim if info.npol == 2 else 1) if a.cyclic else 0,
-                          interchan_dedispersion=a.interchan, record_time=a.record, fourth_moment=a.fourth,
+                          interchan_dedispersion=a.interchan, record_time=a.record, fourth_moment=a.fourth, calibrator=a.pac,
                           convolve_when="never" if when == "after" and dm == 0.0 else when)
     torch.cuda.set_device(a.device)
     lt = dada.fold_file(a.file, cfg, polyco=polyco, device=a.device, stream=torch.cuda.current_stream().cuda_stream,

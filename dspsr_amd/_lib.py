@@ -138,6 +138,17 @@ SYMBOLS = {
     "dspsr_amd_plfb_zero": (_i, [_vp]),
     "dspsr_amd_plfb_profile_dev": (_vp, [_vp]),
     "dspsr_amd_plfb_synch": (_i, [_vp, _vp]),
+    "dspsr_amd_bandpass_check_shape": (_i, [_u32, _u32, _u32, _u32, _u32, C.c_char_p, _sz]),
+    "dspsr_amd_bandpass_check_input": (_i, [_u32, _u32, _u32, _u32, _i, _u64, _u64, _u64, _u64, C.POINTER(_u32), C.POINTER(_u32),
+                                            C.POINTER(_u32), C.c_char_p, _sz]),
+    "dspsr_amd_bandpass_create": (_i, [_vp, _pp]),
+    "dspsr_amd_bandpass_destroy": (None, [_vp]),
+    "dspsr_amd_bandpass_set_shape": (_i, [_vp, _u32, _u32, _u32, _u32, _u32]),
+    "dspsr_amd_bandpass_accumulate": (_i, [_vp, _vp, _u64, _u64, _u64]),
+    "dspsr_amd_bandpass_accumulate_raw": (_i, [_vp, _vp, _i, _f, _u64]),
+    "dspsr_amd_bandpass_zero": (_i, [_vp]),
+    "dspsr_amd_bandpass_pass_dev": (_vp, [_vp]),
+    "dspsr_amd_bandpass_synch": (_i, [_vp, _vp, C.POINTER(_d)]),
     "dspsr_amd_comm_set_library": (_i, [C.c_char_p]),
     "dspsr_amd_comm_unique_id": (_i, [_vp]),
     "dspsr_amd_comm_create": (_i, [_vp, _i, _i, _vp, _pp]),
@@ -156,6 +167,10 @@ SYMBOLS = {
     "dspsr_amd_fold_binplan_runs": (_i, [_d, _d, _u32, _u64, _vp, _vp, _vp, _u64, _vp, _vp]),
     "dspsr_amd_cyclic_binplan": (_i, [_d, _d, _u32, _u64, _vp, _vp, _vp]),
     "dspsr_amd_cyclic_lags_to_spectra": (_i, [_vp, _u32, _u32, _u32, _u32, _u32, _vp]),
+    "dspsr_amd_rfi_mask_calculate": (_i, [_vp, _vp, _u32, _u32, _i, _vp, C.POINTER(_u32), C.POINTER(_u32)]),
+    "dspsr_amd_rfi_mask_calculate_log": (_i, [_vp, _vp, _u32, _u32, _i, _vp, C.POINTER(_u32), C.POINTER(_u32), _vp, _u32]),
+    "dspsr_amd_rfi_mask_expand": (_i, [_vp, _u32, _u64, _vp]),
+    "dspsr_amd_response_multiply": (_i, [_vp, _vp, _u64]),
 }
 
 

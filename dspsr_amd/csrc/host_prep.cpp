@@ -443,3 +443,122 @@ extern "C" int dspsr_amd_cyclic_lags_to_spectra(const float* lags, uint32_t ncha
       }
   return DSPSR_AMD_OK;
 }
+
+// ---- dspsr -R: dsp::RFIFilter (Signal/General/RFIFilter.C) on the host, as in the reference --------------------------------------
+//
+// fft::median_smooth is PSRCHIVE's and not part of the reference tree; restated: the window size is made odd, the result is
+// computed from the unmodified data, the window at i is data[max(0, i - h) .. min(n - 1, i + h)] with h = wsize / 2, truncated at
+// the edges, and the result is element len / 2 of the sorted window.
+static void median_smooth(std::vector<float>& data, unsigned wsize)
+{
+  if (wsize % 2 == 0) wsize++;
+  const long n = (long)data.size(), h = wsize / 2;
+  const std::vector<float> in(data);
+  std::vector<float> win;
+  for (long i = 0; i < n; i++) {
+    const long lo = std::max(0l, i - h), hi = std::min(n - 1, i + h);
+    win.assign(in.begin() + lo, in.begin() + hi + 1);
+    std::sort(win.begin(), win.end());
+    data[i] = win[win.size() / 2];
+  }
+}
+
+// RFIFilter::calculate (RFIFilter.C:105-162), operation by operation.  keep_zapped = 0 is the literal loop: a channel that does not
+// trigger in a round gets 1 whatever happened to it before, and the loop ends only after a round without a trigger, so the mask
+// it leaves is all ones and only the zeros in p0 / p1 survive.  keep_zapped = 1: a channel zapped in any round stays 0.
+// cutoffs (may be NULL): the cutoff of each round, at most cutoff_cap stored -- what the reference prints as "round k cutoff = ...".
+// A round whose triggers are all re-zaps (possible only with a cutoff below zero, where every zeroed channel triggers again and
+// `variance -= 0` changes nothing) repeats for ever in the reference: DSPSR_AMD_ESTATE, the outputs as that round left them.
+extern "C" int dspsr_amd_rfi_mask_calculate_log(float* p0ptr, float* p1ptr, uint32_t nchan_bp, uint32_t median_window,
+                                                int keep_zapped, float* ptr, uint32_t* total_zapped_out, uint32_t* rounds_out,
+                                                float* cutoffs, uint32_t cutoff_cap)
+{
+  if (!p0ptr || !p1ptr || !ptr || !nchan_bp || !median_window) return DSPSR_AMD_EINVAL;
+  std::vector<float> spectrum(nchan_bp);
+  unsigned ichan = 0;
+  for (ichan = 0; ichan < nchan_bp; ichan++) spectrum[ichan] = p0ptr[ichan] + p1ptr[ichan];      // :116-117
+  median_smooth(spectrum, median_window);                                                         // :119
+  double variance = 0.0;
+  for (ichan = 0; ichan < nchan_bp; ichan++) {                                                    // :122-128
+    spectrum[ichan] -= (p0ptr[ichan] + p1ptr[ichan]);
+    spectrum[ichan] *= spectrum[ichan];
+    variance += spectrum[ichan];
+  }
+  variance /= nchan_bp;                                                                           // :130
+  std::vector<char> ever(nchan_bp, 0);
+  for (ichan = 0; ichan < nchan_bp; ichan++) ptr[ichan] = 1;
+  bool zapped = true;
+  unsigned round = 1, total_zapped = 0;
+  int rc = DSPSR_AMD_OK;
+  while (zapped) {                                                                                // :139-158
+    const float cutoff = 16.0 * variance;
+    if (cutoffs && round <= cutoff_cap) cutoffs[round - 1] = cutoff;
+    zapped = false;
+    round++;
+    bool fresh = false;
+    for (ichan = 0; ichan < nchan_bp; ichan++) {
+      if (spectrum[ichan] > cutoff || (ichan && fabs(spectrum[ichan] - spectrum[ichan - 1]) > 2 * cutoff)) {
+        variance -= spectrum[ichan] / nchan_bp;
+        spectrum[ichan] = p0ptr[ichan] = p1ptr[ichan] = ptr[ichan] = 0.0;
+        total_zapped++;
+        zapped = true;
+        if (!ever[ichan]) fresh = true;
+        ever[ichan] = 1;
+      } else if (!(keep_zapped && ever[ichan])) {
+        ptr[ichan] = 1;
+      }
+    }
+    if (zapped && !fresh) {
+      rc = DSPSR_AMD_ESTATE;
+      break;
+    }
+  }
+  if (total_zapped_out) *total_zapped_out = total_zapped;
+  if (rounds_out) *rounds_out = round - 1;
+  return rc;
+}
+
+extern "C" int dspsr_amd_rfi_mask_calculate(float* p0, float* p1, uint32_t n, uint32_t median_window, int keep_zapped, float* mask,
+                                            uint32_t* total_zapped, uint32_t* rounds)
+{
+  return dspsr_amd_rfi_mask_calculate_log(p0, p1, n, median_window, keep_zapped, mask, total_zapped, rounds, nullptr, 0);
+}
+
+// RFIFilter::match (const Response*) (RFIFilter.C:165-206), quirks included: expand = required / n in integers, elements past
+// n * expand stay 1; with required < n the shrink loop runs `ip < expand` with expand == 0, so nothing is ever zapped and the
+// result is all ones.  phasors: `required` complex floats with zero imaginary part.
+extern "C" int dspsr_amd_rfi_mask_expand(const float* data, uint32_t ndat, uint64_t required, float* phasors)
+{
+  if (!data || !ndat || !phasors) return DSPSR_AMD_EINVAL;
+  const uint64_t expand = required / ndat, shrink = required ? ndat / required : 0;
+  for (uint64_t i = 0; i < required; i++) {
+    phasors[2 * i] = 1.0f;
+    phasors[2 * i + 1] = 0.0f;
+  }
+  if (expand) {
+    for (uint64_t idat = 0; idat < ndat; idat++)
+      for (uint64_t ip = 0; ip < expand; ip++) phasors[2 * (idat * expand + ip)] = data[idat];
+  } else if (shrink) {
+    for (uint64_t idat = 0; idat < required; idat++)
+      for (uint64_t ip = 0; ip < expand; ip++)
+        if (data[idat * shrink + ip] == 0.0) phasors[2 * idat] = 0.0f;
+  }
+  return DSPSR_AMD_OK;
+}
+
+// Response::operator *= (Response.C:73-104) through Response::operate (:429-441): kernel[i] = phasors[i] * kernel[i], complex.
+// (One product or difference per statement: nothing here may be contracted into a fused multiply-add.)
+extern "C" int dspsr_amd_response_multiply(float* kernel, const float* phasors, uint64_t ncomplex)
+{
+  if (!kernel || !phasors) return DSPSR_AMD_EINVAL;
+  for (uint64_t i = 0; i < ncomplex; i++) {
+    const float d_r = kernel[2 * i], d_i = kernel[2 * i + 1], f_r = phasors[2 * i], f_i = phasors[2 * i + 1];
+    const float rr = f_r * d_r;
+    const float ii = f_i * d_i;
+    const float ir = f_i * d_r;
+    const float ri = f_r * d_i;
+    kernel[2 * i] = rr - ii;
+    kernel[2 * i + 1] = ir + ri;
+  }
+  return DSPSR_AMD_OK;
+}

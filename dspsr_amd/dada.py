@@ -259,7 +259,27 @@ class DadaFile:
             yield src, npart
 
 
-def fold_file(path, cfg, polyco=None, device=0, stream=None, reference_phase=0.0, dump_before=(), dump_dir=".", targets=None):
+def rfi_filter_from_file(f, lt, log=None, chunk_blocks=4096, **kw):
+    """`dspsr -R`: dsp::RFIFilter::match (RFIFilter.C:76-102) -- the passband of the first `interval` (1 s) of DadaFile `f`, read in
+    the reference's 8192-sample blocks (here `chunk_blocks` of them per copy), integrated on LoadToFold `lt`'s device and stream.
+    Returns the calculated dspsr_amd.rfi.RfiFilter; `log`: where the reference's lines go (round k cutoff = ..., zapped N channels)."""
+    import torch
+    from . import rfi
+    filt = rfi.RfiFilter(lt.ctx, f.info, log=log, **kw)
+    pos, chunk = 0, chunk_blocks * rfi.BLOCK
+    while not filt.complete and pos + rfi.BLOCK <= f.ndat:
+        n = min(chunk, ((f.ndat - pos) // rfi.BLOCK) * rfi.BLOCK)
+        host = torch.from_numpy(np.array(f._map[pos * f.bytes_per_sample:(pos + n) * f.bytes_per_sample]))
+        dev = host.to("cuda:%d" % lt.ctx.device)
+        torch.cuda.synchronize(lt.ctx.device)               # the copy ran on torch's stream, the kernel runs on the pipeline's
+        pos += filt.integrate_raw(dev, n) or n
+        lt.ctx.synchronize()                                 # the block is freed on return: drain the stream first
+    filt.calculate()
+    return filt
+
+
+def fold_file(path, cfg, polyco=None, device=0, stream=None, reference_phase=0.0, dump_before=(), dump_dir=".", targets=None,
+              rfi_log=None):
     """The reference's `dspsr file.dada -F nchan:D ...` on one GPU: open the file, build the pipeline from its header,
     feed every block, close the last sub-integration.  Returns the LoadToFold (its .subints hold the results -- with several
     `targets` (pipeline.FoldTarget), .pulsars[k].subints; the caller closes it)."""
@@ -267,6 +287,14 @@ def fold_file(path, cfg, polyco=None, device=0, stream=None, reference_phase=0.0
     f = DadaFile(path)
     lt = LoadToFold(cfg, f.info, device=device, stream=stream, polyco=polyco, reference_phase=reference_phase,
                     dump_before=dump_before, dump_dir=dump_dir, targets=targets)
+    if cfg.zap_rfi:
+        try:
+            filt = rfi_filter_from_file(f, lt, log=rfi_log)
+            lt.set_rfi_filter(filt)
+            filt.close()                                     # the device passband; the mask and the result are host data
+        except BaseException:
+            lt.close()
+            raise
     if f.nblocks(lt) == (0, 0):
         lt.close()
         raise DspsrAmdError("dspsr_amd.fold_file: %s holds %d samples, fewer than one overlap-save part (%d)"

@@ -906,6 +906,83 @@ class PhaseLockedFilterbankEngine:
             pass
 
 
+def bandpass_check_shape(nchan_in, npol_in, ndim_in, resolution, npol_out):
+    """The refusals of BandpassEngine.set_shape, on the host alone (no device)."""
+    msg = C.create_string_buffer(400)
+    code = lib.dspsr_amd_bandpass_check_shape(nchan_in, npol_in, ndim_in, resolution, npol_out, msg, len(msg))
+    if code != _lib.OK:
+        raise DspsrAmdError(msg.value.decode())
+
+
+def bandpass_check_input(nchan_in, npol_in, ndim_in, resolution, raw_layout, in_addr, chan_stride, pol_stride, ndat):
+    """The refusals of BandpassEngine.accumulate (raw_layout -1) / accumulate_raw, on the host alone (no device).  Returns the launch
+    arithmetic: (parts per workgroup tile, tiles per segment, segments)."""
+    msg = C.create_string_buffer(400)
+    tp, tps, nseg = C.c_uint32(), C.c_uint32(), C.c_uint32()
+    code = lib.dspsr_amd_bandpass_check_input(nchan_in, npol_in, ndim_in, resolution, raw_layout, in_addr, chan_stride, pol_stride,
+                                              ndat, C.byref(tp), C.byref(tps), C.byref(nseg), msg, len(msg))
+    if code != _lib.OK:
+        raise DspsrAmdError(msg.value.decode())
+    return tp.value, tps.value, nseg.value
+
+
+class BandpassEngine:
+    """dsp::Bandpass::transformation (Signal/General/Bandpass.C:50-175) on the device; owns the device-resident passband
+    [npol_out][nchan_in][resolution]."""
+
+    def __init__(self, ctx: Context):
+        self.ctx = ctx
+        h = C.c_void_p()
+        _check(ctx.handle, lib.dspsr_amd_bandpass_create(ctx.handle, C.byref(h)), "dspsr_amd_bandpass_create")
+        self.handle = h
+        self.shape = None
+        self.integration_samples = 0.0
+
+    def set_shape(self, nchan_in, npol_in, ndim_in, resolution, npol_out):
+        _check(self.ctx.handle, lib.dspsr_amd_bandpass_set_shape(self.handle, nchan_in, npol_in, ndim_in, resolution, npol_out),
+               "dspsr_amd_bandpass_set_shape")
+        self.shape = (npol_out, nchan_in, resolution)
+
+    def accumulate(self, inp, ndat):
+        """inp: float32 device tensor [nchan_in][npol_in][>= ndat * ndim_in] (FPT order), any float-aligned address and strides."""
+        cs, ps = _strides3(inp)
+        _check(self.ctx.handle, lib.dspsr_amd_bandpass_accumulate(self.handle, inp.data_ptr(), cs, ps, ndat),
+               "dspsr_amd_bandpass_accumulate")
+
+    def accumulate_raw(self, raw, ndat, layout=_lib.RAW_GENERIC, scale=1.0):
+        """raw: the 8-bit block on the device (int8 / uint8 tensor) holding at least ndat samples in `layout` order."""
+        _check(self.ctx.handle, lib.dspsr_amd_bandpass_accumulate_raw(self.handle, raw.data_ptr(), layout, scale, ndat),
+               "dspsr_amd_bandpass_accumulate_raw")
+
+    def zero(self):
+        _check(self.ctx.handle, lib.dspsr_amd_bandpass_zero(self.handle), "dspsr_amd_bandpass_zero")
+
+    def get_pass_ptr(self):
+        return lib.dspsr_amd_bandpass_pass_dev(self.handle)
+
+    def synch(self) -> np.ndarray:
+        """The passband on the host, [npol_out][nchan_in][resolution] (blocks); integration_samples = samples integrated per row."""
+        if self.shape is None:
+            raise DspsrAmdError("dspsr_amd_bandpass_synch: no shape")
+        out = np.empty(self.shape, dtype=np.float32)
+        n = C.c_double()
+        _check(self.ctx.handle, lib.dspsr_amd_bandpass_synch(self.handle, out.ctypes.data_as(C.c_void_p), C.byref(n)),
+               "dspsr_amd_bandpass_synch")
+        self.integration_samples = n.value
+        return out
+
+    def close(self):
+        if self.handle and self.ctx.handle:
+            lib.dspsr_amd_bandpass_destroy(self.handle)
+        self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class Communicator:
     """The sub-integration exchange over RCCL / xGMI behind the C-ABI (dspsr_amd_comm_*, csrc/comm.hip): the same entry
     points DSPSR's C++ host calls.  One per pipeline context.  `unique_id` = the 128 bytes of `Communicator.unique_id()`

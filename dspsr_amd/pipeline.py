@@ -82,6 +82,9 @@ class Config:
                                            # with `freq` (MHz) and `jones` [n][2][2], or a (freq, jones) pair (polcal.load_calibrator):
                                            # the Jones matrix of every response bin times the chirp goes to the filterbank as a matrix
                                            # response (calibrator_response below says what it works with and what it refuses)
+    zap_rfi: bool = False                  # -R: the narrow-band RFI filter (dsp::RFIFilter, LoadToFold1.C:248-266): a 0/1 mask from the
+                                           # passband of the first second, multiplied into the dedispersion kernel.  The pipeline wants
+                                           # its filter before the first block: LoadToFold.set_rfi_filter (dada.fold_file does it)
     npol: int = 4                          # -d: the reference's config->npol.  This path detects the four products (4); the field
                                            # decides the branch of LoadToFold1.C:552-568 only: with 1 or 3 it wins over -4, which is
                                            # then ignored
@@ -968,6 +971,27 @@ def plfb_check(cfg: "Config", info: "InputInfo", ntargets=0, subband=None, dump_
         raise DspsrAmdError("dsp::PhaseLockedFilterbank::prepare invalid dimensions.  nchan=%d nbin=%d" % (cfg.plfb_nchan, cfg.plfb_nbin))
 
 
+def rfi_check(cfg: "Config", info: "InputInfo", subband=None):
+    """What a -R run refuses, before any device resource is opened."""
+    who = "dspsr_amd.LoadToFold: the RFI filter (-R)"
+    if cfg.calibrator is not None:
+        raise DspsrAmdError("%s with -pac (calibrator) is not built: the product of the mask, the chirp and a matrix response is open" % who)
+    if info.nchan > 1:
+        # the reference takes the mask from input channel 0 and stretches it over all channels (get_datptr(0, .), RFIFilter.C:109-110)
+        raise DspsrAmdError("%s is built for one input channel (info.nchan=%d): the reference stretches channel 0's mask over "
+                            "all of them, which is not reproduced" % (who, info.nchan))
+    if info.npol != 2:
+        raise DspsrAmdError("%s reads the passbands of two polarisations (info.npol=%d): dsp::RFIFilter::calculate takes "
+                            "get_datptr(0, 0) and get_datptr(0, 1)" % (who, info.npol))
+    if cfg.convolve_when == "never" or cfg.dispersion_measure == 0:
+        raise DspsrAmdError("%s needs a dedispersion kernel to multiply into (convolve_when=%r, dispersion_measure=%g)"
+                            % (who, cfg.convolve_when, cfg.dispersion_measure))
+    if subband is not None:
+        raise DspsrAmdError("%s is not built for sub-band sharded runs (subband=%d)" % (who, subband))
+    if getattr(info, "nbit", 8) != 8:
+        raise DspsrAmdError("%s reads 8-bit input (info.nbit=%d): 16-bit input is not built" % (who, info.nbit))
+
+
 def calibrator_response(cfg: "Config", info: "InputInfo", subband=None):
     """`dspsr -pac`: the matrix response of a run with cfg.calibrator -- (Dedispersion response, float32 [N][8]) -- or None without
     one.  Host work only: LoadToFold calls it before it opens any device resource, and every limit raises DspsrAmdError by name.
@@ -1047,6 +1071,9 @@ class LoadToFold:
         self.pulsars = []
         self.cyclic = None
         self.plfb = None
+        self.rfi_filter = None
+        if cfg.zap_rfi:                                  # (before any device resource is opened)
+            rfi_check(cfg, info, subband)
         self._calibrated = calibrator_response(cfg, info, subband)      # -pac (before any device resource is opened)
         if cfg.plfb_nbin > 0:                            # (before any device resource is opened)
             plfb_check(cfg, info, len(targets), subband, dump_before)
@@ -1495,6 +1522,27 @@ class LoadToFold:
         self.integration_length, self.ndat_total = 0.0, 0
         self.nsamples_in, self.ndat_out, self.subints = 0, 0, []
 
+    def _response_engine(self):
+        """the engine that holds the dedispersion response: the convolving filterbank (-F N:D), or the Convolution of -F N / -F N:B"""
+        if self.cyclic is not None or self.plfb is not None:
+            return self.fb
+        return self.fb if self.cfg.convolve_when == "during" else self.fb.conv
+
+    def set_rfi_filter(self, filt):
+        """`dspsr -R`: multiply the filter's mask into the dedispersion kernel (ResponseProduct, LoadToFold1.C:248-266) and hand the
+        product to the engine through set_kernel -- between blocks: the stream is drained first.  filt: dspsr_amd.rfi.RfiFilter
+        (calculated here if it has not been), or None to restore the dedispersion kernel alone.  The reference matches the
+        response once (Filterbank.C:84, Convolution.C:115): call this once, before the first block."""
+        rfi_check(self.cfg, self.info, self.subband)
+        r = getattr(self, "response", None)
+        eng = self._response_engine()
+        if r is None or eng is None:
+            raise DspsrAmdError("dspsr_amd.LoadToFold: the RFI filter (-R) needs a dedispersion kernel to multiply into")
+        kernel = r.kernel if filt is None else filt.product(r.kernel, r.kernel.size // r.ndat, r.ndat)
+        self.ctx.synchronize()
+        eng.set_kernel(kernel)
+        self.rfi_filter = filt
+
     def _fold_dims(self):
         """(npol, ndim) of the folded PhaseSeries: those of the detected rows, or 1 x 14 for -4 (FourthMoment.C:39-42)"""
         return (1, 14) if self.moments else (self.npol_out, self.cfg.ndim)
@@ -1599,6 +1647,9 @@ class LoadToFold:
         if raw.numel() < self.block_bytes(npart):
             raise DspsrAmdError("dspsr_amd.LoadToFold.process_block: block holds %d bytes, %d needed"
                                 % (raw.numel(), self.block_bytes(npart)))
+        if cfg.zap_rfi and self.rfi_filter is None:
+            raise DspsrAmdError("dspsr_amd.LoadToFold.process_block: zap_rfi (-R) is set and no filter has been given: "
+                                "call set_rfi_filter before the first block")
         if self.cyclic is not None:
             return self._process_block_cyclic(raw, npart, events)
         if self.plfb is not None:

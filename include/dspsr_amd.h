@@ -508,6 +508,45 @@ float* dspsr_amd_plfb_profile_dev(dspsr_amd_plfb* plfb);
 /* copy it to the host and wait */
 int dspsr_amd_plfb_synch(dspsr_amd_plfb* plfb, float* profile_host);
 
+/* ---- passband integration: dsp::Bandpass on the device (Signal/General/Bandpass.C:50-175) ---------------------------------
+ * The operator behind dspsr -R (dsp::RFIFilter integrates one second of undetected input through it, RFIFilter.C:76-95) and
+ * the reference's passband tool.  Per input channel the ndat samples of a call are cut into npart = ndat / nsamp_fft whole,
+ * contiguous transforms (nsamp_fft = 2 * resolution real samples, ndim_in 1, or resolution complex samples, ndim_in 2); trailing
+ * samples that do not fill a transform are not read.  Forward, unnormalised; Nyquist input keeps bins 0 .. resolution-1 of the
+ * real-to-complex transform.  pass[npol_out][nchan_in][resolution] +=  re*re + im*im per polarisation (npol_out = npol_in,
+ * Response.C:456-492), or PP, QQ, Re P*Q, Im P*Q (npol_out = 4 with npol_in = 2, cross_detect_int, Response.C:587-612).
+ * resolution: a power of two in [2, 8192]; nchan_in <= 65535 and nchan_in * resolution <= 2^24 (the per-segment sums of a launch,
+ * counted for four output polarisations, stay within 256 MiB).  Not built, refused by name: apodization, Bandpass::set_response, detected input.
+ * Every refusal is DSPSR_AMD_EINVAL with the limit's name (dspsr_amd_last_error) before any launch or allocation.
+ *   accumulate     : float rows, element (chan, pol, t) = in + chan*chan_stride + pol*pol_stride + t*ndim_in; any float-aligned
+ *                    address, strides >= the row
+ *   accumulate_raw : the 8-bit block, DSPSR_AMD_RAW_GENERIC (any nchan_in / npol_in / ndim_in) or DSPSR_AMD_RAW_CASPSR (one channel,
+ *                    two real polarisations, block on an 8-byte group); value = (int8 + 0.5) * scale; DSPSR_AMD_RAW_UWB16 is refused
+ *   zero           : Bandpass::reset_output -- the passband and the integration length
+ *   synch          : the passband on the host (waits) and the samples integrated per row so far, npart * nsamp_fft summed over
+ *                    the calls (Bandpass.C:164: integration_length = that / rate)
+ * The same sequence of calls gives the same bits (no atomics; the work is cut by (npart, nchan_in, resolution) alone).
+ * check_shape / check_input: the device-free halves of set_shape / accumulate (raw_layout < 0: float rows); check_input also
+ * returns the launch arithmetic: parts per workgroup tile, tiles per segment, segments. */
+typedef struct dspsr_amd_bandpass dspsr_amd_bandpass;
+int dspsr_amd_bandpass_check_shape(uint32_t nchan_in, uint32_t npol_in, uint32_t ndim_in, uint32_t resolution, uint32_t npol_out,
+                                   char* msg, size_t msg_len);
+int dspsr_amd_bandpass_check_input(uint32_t nchan_in, uint32_t npol_in, uint32_t ndim_in, uint32_t resolution, int raw_layout,
+                                   uint64_t in_addr, uint64_t chan_stride, uint64_t pol_stride, uint64_t ndat,
+                                   uint32_t* parts_per_tile, uint32_t* tiles_per_segment, uint32_t* nsegment, char* msg,
+                                   size_t msg_len);
+int dspsr_amd_bandpass_create(dspsr_amd_ctx* ctx, dspsr_amd_bandpass** out);
+void dspsr_amd_bandpass_destroy(dspsr_amd_bandpass* bp);
+int dspsr_amd_bandpass_set_shape(dspsr_amd_bandpass* bp, uint32_t nchan_in, uint32_t npol_in, uint32_t ndim_in, uint32_t resolution,
+                                 uint32_t npol_out);
+int dspsr_amd_bandpass_accumulate(dspsr_amd_bandpass* bp, const float* in_dev, uint64_t chan_stride, uint64_t pol_stride,
+                                  uint64_t ndat);
+int dspsr_amd_bandpass_accumulate_raw(dspsr_amd_bandpass* bp, const void* raw_dev, int raw_layout, float scale, uint64_t ndat);
+int dspsr_amd_bandpass_zero(dspsr_amd_bandpass* bp);
+/* device passband [npol_out][nchan_in][resolution], valid in stream order */
+float* dspsr_amd_bandpass_pass_dev(dspsr_amd_bandpass* bp);
+int dspsr_amd_bandpass_synch(dspsr_amd_bandpass* bp, float* pass_host, double* integration_samples);
+
 /* ---- the sub-integration dump over RCCL / xGMI: the ONE exchange of the path -----------------------------------------
  * Reference hook: dsp::Subint<Fold>::transformation emits the finished sub-integration (Signal/Pulsar/dsp/Subint.h:291-303);
  * merging semantics = PhaseSeries::combine (Signal/Pulsar/PhaseSeries.C:442-484); the reference merges its threads' pieces
@@ -667,6 +706,30 @@ int dspsr_amd_cyclic_binplan(double phi, double phase_per_sample, uint32_t nbin,
  * nchan_spec must be a power of two (and a multiple of mover): anything else DSPSR_AMD_EINVAL. */
 int dspsr_amd_cyclic_lags_to_spectra(const float* lags_host, uint32_t nchan, uint32_t npol, uint32_t nbin, uint32_t nlag,
                                      uint32_t mover, float* out_host);
+
+/* ---- dspsr -R: dsp::RFIFilter (Signal/General/RFIFilter.C) -- host code, no device call ------------------------------------
+ * rfi_mask_calculate : RFIFilter::calculate (:105-162) on the integrated passband of the two polarisations, p0[n] and p1[n] (both
+ *                      zeroed where zapped, as the reference does); mask[n] receives the 0/1 response.
+ *                      keep_zapped = 0 is the reference's loop to the letter: every round sets a channel that does not trigger
+ *                      to 1, also one zapped earlier, and the loop ends after a round without a trigger -- the mask is all ones
+ *                      whatever the data.  keep_zapped = 1: a channel zapped in any round stays 0.
+ *                      total_zapped counts re-zaps as the reference does; rounds = rounds run.
+ *                      DSPSR_AMD_ESTATE: a round re-zapped channels and zapped no new one -- with a cutoff below zero the
+ *                      reference's loop repeats that round for ever.
+ *                      fft::median_smooth is PSRCHIVE's, restated: odd window, computed from the unmodified data, truncated at the
+ *                      edges, element len/2 of the sorted window.
+ * _log               : the same, and the cutoff of every round (at most cutoff_cap stored): "round k cutoff = ..." of :142
+ * rfi_mask_expand    : RFIFilter::match (const Response*) (:165-206): expand = required / n in integers, elements past n*expand
+ *                      stay 1; required < n leaves all ones (the shrink loop's bound is `expand`, which is 0 there).
+ *                      phasors: `required` complex floats, imaginary part 0
+ * response_multiply  : Response::operator *= (Response.C:73-104, :429-441): kernel[i] = phasors[i] * kernel[i]; a phasor (1, 0)
+ *                      leaves a finite kernel unchanged bit for bit, except for the sign of a zero */
+int dspsr_amd_rfi_mask_calculate(float* p0, float* p1, uint32_t n, uint32_t median_window, int keep_zapped, float* mask,
+                                 uint32_t* total_zapped, uint32_t* rounds);
+int dspsr_amd_rfi_mask_calculate_log(float* p0, float* p1, uint32_t n, uint32_t median_window, int keep_zapped, float* mask,
+                                     uint32_t* total_zapped, uint32_t* rounds, float* cutoffs, uint32_t cutoff_cap);
+int dspsr_amd_rfi_mask_expand(const float* mask, uint32_t n, uint64_t required, float* phasors);
+int dspsr_amd_response_multiply(float* kernel, const float* phasors, uint64_t ncomplex);
 #ifdef __cplusplus
 }
 #endif

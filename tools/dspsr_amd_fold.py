@@ -16,6 +16,11 @@ dspsr_amd.dada.fold_file for trying the engine on a DADA file; not a re-implemen
   dspsr_amd_fold.py -F 64:D -pac cal.npz ...   (phase-coherent polarimetric calibration, dspsr.C:372: the Jones matrix of every
                     response bin times the chirp, applied inside the filterbank; cal.npz holds `freq` in MHz and `jones` [n][2][2])
 
+  dspsr_amd_fold.py -F 16:D -R ...   (narrow-band RFI filter, dspsr.C:369: the passband of the first second of the file is
+                    integrated on the device in 1024 channels, dsp::RFIFilter's mask is multiplied into the dedispersion kernel; the
+                    reference's lines `round k cutoff = ...` and `zapped N channels` go to stderr.  A channel zapped in any round
+                    stays zapped -- the reference's own loop leaves a mask of all ones)
+
 Every completed sub-integration is written as <prefix>_<n>.ps (the PhaseSeries hand-off file of INTEGRATION.md:
 raw sums + hits; dsp::Archiver's normalisation is the reader's job).
 
@@ -48,6 +53,7 @@ def parse_args(argv=None):
     ap.add_argument("-cyclicoversample", dest="cyclic_mover", type=int, default=1, help="use M times as many lags to improve the cyclic channel isolation")
     ap.add_argument("-G", dest="plfb_nbin", type=int, default=0, help="create phase-locked filterbank with nbin phase bins")
     ap.add_argument("-pac", dest="pac", default=None, help="phase-coherent polarimetric calibration: .npz with freq (MHz) and jones [n][2][2]")
+    ap.add_argument("-R", dest="zap_rfi", action="store_true", help="apply time-variable narrow-band RFI filter")
     ap.add_argument("-r", dest="record", action="store_true", help="report the time spent in each operation")
     ap.add_argument("--dump", action="append", default=[], help="dump the input of this operation (Detection, Fold)")
     ap.add_argument("-O", dest="prefix", default="dspsr_amd", help="output file name prefix")
@@ -96,11 +102,11 @@ def main(argv=None):
                           subint_seconds=a.subint, subint_turns=1.0 if a.single else a.turns, ndim=1 if a.cyclic or a.plfb_nbin else a.ndim,
                           plfb_nbin=a.plfb_nbin, npol=a.ndim if a.plfb_nbin else 4,
                           cyclic_nchan=a.cyclic, cyclic_mover=a.cyclic_mover, cyclic_npol=(a.ndim if info.npol == 2 else 1) if a.cyclic else 0,
-                          interchan_dedispersion=a.interchan, record_time=a.record, fourth_moment=a.fourth, calibrator=a.pac,
+                          interchan_dedispersion=a.interchan, record_time=a.record, fourth_moment=a.fourth, calibrator=a.pac, zap_rfi=a.zap_rfi,
                           convolve_when="never" if when == "after" and dm == 0.0 else when)
     torch.cuda.set_device(a.device)
     lt = dada.fold_file(a.file, cfg, polyco=polyco, device=a.device, stream=torch.cuda.current_stream().cuda_stream,
-                        dump_before=tuple(a.dump), targets=targets or None)
+                        dump_before=tuple(a.dump), targets=targets or None, rfi_log=sys.stderr)
     for line in lt.vitals():
         print(line, file=sys.stderr)
     outputs = [("%s_%%04d.ps" % a.prefix, lt.subints, pfold)]

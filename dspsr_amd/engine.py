@@ -503,6 +503,12 @@ class SampleDelay:
             lib.dspsr_amd_sample_delay_destroy(self.handle)
         self.handle = None
 
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
 
 class Rescale:
     """Mirror of dsp::Rescale for TFP-ordered detected data (Signal/General/Rescale.C): offset/scale per (pol, chan)."""

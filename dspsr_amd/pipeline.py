@@ -563,7 +563,7 @@ class PhaseSeries:
         dev = sub.get("profile_dev")
         if dev is None:
             import torch
-            dev = torch.from_numpy(np.ascontiguousarray(subint_profile(sub)).reshape(-1)).to("cuda:%d" % ctx.device)
+            dev = torch.from_numpy(np.ascontiguousarray(subint_profile(sub)).reshape(-1)).to(_device(ctx))
         ps.profile = dev.view(obs["nchan"], obs["npol"], ps.nbin * obs["ndim"])
         ps.hits = np.array(sub["hits"], dtype=np.uint32)
         ps.integration_length, ps.ndat_total = float(sub["integration_length"]), int(sub["ndat_total"])
@@ -584,13 +584,12 @@ class PhaseSeries:
         count of dropped samples ndat_total survives); otherwise the observations must be combinable and nbin equal, and
         the time span is extended."""
         if self.integration_length == 0.0:
-            import torch
             self.obs = {k: obs.get(k) for k in self.OBS_KEYS}
             keep = self.ndat_total
             self.nbin = nbin
             shape = (obs["nchan"], obs["npol"], nbin * obs["ndim"])
             if self.profile is None or tuple(self.profile.shape) != shape:
-                self.profile = torch.empty(shape, dtype=torch.float32, device="cuda:%d" % self.ctx.device)
+                self.profile = _device_empty(self.ctx, shape)
             self.hits = np.zeros(nbin, np.uint32)
             self.zero()
             self.ndat_total = keep
@@ -718,8 +717,7 @@ class FilterbankThenConvolution:
 
     def __init__(self, ctx, nsub, input_nchan, npol, real_input, response, max_parts=1, parts_per_block=1,
                  fused_fold=_lib.FUSED_AUTO):
-        import torch
-        self.torch, self.ctx = torch, ctx
+        self.ctx = ctx
         self.front = FilterbankEngine(ctx).setup(nsub, 1, 0, 0, input_nchan, npol, real_input, None)
         self.nchan, self.npol = nsub * input_nchan, npol
         self.nsamp_fft_front = self.front.nsamp_fft                      # input samples per filterbank output sample
@@ -745,8 +743,7 @@ class FilterbankThenConvolution:
         if self.channelised is None or self.channelised.shape[2] < 2 * ndat:
             n = max(ndat, self._cap * self.part_out + self.ovl_out)
             n += (-n) % 64                                  # rows start on 512-byte boundaries: the filterbank's runs of 32 samples are whole lines
-            self.channelised = self.torch.empty((self.nchan, self.npol, 2 * n), dtype=self.torch.float32,
-                                                device="cuda:%d" % self.ctx.device)
+            self.channelised = _device_empty(self.ctx, (self.nchan, self.npol, 2 * n))
         self.front.perform_raw(raw, layout, scale, self.channelised, ndat)
         return self.channelised
 
@@ -794,8 +791,7 @@ class ConvolutionThenFilterbank:
     parts of the convolution, which hold a whole number of filterbank transforms -- no remainder, same samples."""
 
     def __init__(self, ctx, nsub, input_nchan, npol, real_input, response, max_parts=1, parts_per_block=1):
-        import torch
-        self.torch, self.ctx = torch, ctx
+        self.ctx = ctx
         self.conv = ConvolutionEngine(ctx).setup(1, response.ndat, response.impulse_pos, response.impulse_neg, input_nchan, npol, real_input,
                                                  response.kernel, max_parts=max_parts)
         self.back = FilterbankEngine(ctx).setup(nsub, 1, 0, 0, input_nchan, npol, False, None)
@@ -814,8 +810,7 @@ class ConvolutionThenFilterbank:
         ndat = ncv * self.conv.nkeep
         if self.dedispersed is None or self.dedispersed.shape[2] < 2 * ndat:
             n = max(ndat, self._cap * self.P * self.conv.nkeep)
-            self.dedispersed = self.torch.empty((self.in_nchan, self.npol, 2 * n), dtype=self.torch.float32,
-                                                device="cuda:%d" % self.ctx.device)
+            self.dedispersed = _device_empty(self.ctx, (self.in_nchan, self.npol, 2 * n))
         self.conv.perform_raw(raw, layout, scale, self.dedispersed, ncv)
         return self.dedispersed, ndat // self.nsub
 
@@ -1020,11 +1015,8 @@ def calibrator_response(cfg: "Config", info: "InputInfo", subband=None):
         raise DspsrAmdError("dspsr_amd.LoadToFold: -pac (calibrator) needs two polarisations (npol=%d)" % info.npol)
     freq, jones = polcal.load_calibrator(cfg.calibrator) if isinstance(cfg.calibrator, (str, bytes, os.PathLike)) \
         else polcal._check_calibrator(*cfg.calibrator)
-    response = Dedispersion(info.centre_frequency, info.bandwidth, cfg.dispersion_measure, input_nchan=1, ndim=info.ndim,
-                            fractional_delay=cfg.interchan_dedispersion)
-    if cfg.freq_res:
-        response.set_frequency_resolution(cfg.freq_res)
-    response.match(cfg.nchan)
+    response = matched_response(info, cfg.dispersion_measure, cfg.freq_res, cfg.nchan, input_nchan=1, ndim=info.ndim,
+                                fractional_delay=cfg.interchan_dedispersion)
     pow2 = lambda v: v >= 1 and not (v & (v - 1))
     if cfg.nchan < 2 or not pow2(cfg.nchan) or not pow2(response.ndat) or not 2 <= response.ndat <= 8192:
         raise DspsrAmdError("dspsr_amd.LoadToFold: -pac (calibrator) needs nchan=%d >= 2 and freq_res=%d in [2, 8192], both powers of "
@@ -1054,10 +1046,127 @@ def fourth_moment_check(cfg: "Config", ntargets=0, subband=None):
     return dataclasses.replace(cfg, stokes=True, ndim=4, fused_fold=False, force_fused=False)
 
 
+def _device(ctx):
+    return "cuda:%d" % ctx.device
+
+
+def _device_empty(ctx, shape, dtype="float32", zero=False):
+    """Every device allocation of the drivers: an uninitialised (zero: zeroed) tensor on the context's device."""
+    import torch
+    return (torch.zeros if zero else torch.empty)(shape, dtype=getattr(torch, dtype), device=_device(ctx))
+
+
+def matched_response(info, dispersion_measure, freq_res, nchan, *, input_nchan, ndim, dual_sideband=-1, dc_centred=False, swap=False,
+                     fractional_delay=False):
+    """dsp::Dedispersion over the band of `info`, its frequency resolution set where -x gives one, matched to `nchan` channels."""
+    r = Dedispersion(info.centre_frequency, info.bandwidth, dispersion_measure, input_nchan=input_nchan, ndim=ndim,
+                     dual_sideband=dual_sideband, dc_centred=dc_centred, swap=swap, fractional_delay=fractional_delay)
+    if freq_res:
+        r.set_frequency_resolution(freq_res)
+    r.match(nchan)
+    return r
+
+
+def filterbank_output(info, r, nsub):
+    """The output observation of the convolving filterbank of -F N:D (Filterbank::prepare_output, Filterbank.C:265-379), host
+    arithmetic: (rate, start in seconds, scale)."""
+    n_fft = nsub * r.ndat
+    nsamp_fft = 2 * n_fft if info.ndim == 1 else n_fft
+    rate = info.rate * (float(r.ndat) / float(nsamp_fft))
+    return rate, info.start_seconds + r.impulse_pos / rate, float(n_fft) * float(r.ndat)
+
+
+def _adopt_front(drv, fb):
+    """`fb` (a FilterbankEngine, or one of the two wrappers above) becomes the front end of the driver: what every path reads of it."""
+    drv.fb = fb
+    drv.nkeep, drv.nsamp_step, drv.nsamp_overlap = fb.nkeep, fb.nsamp_step, fb.nsamp_overlap
+    drv.scale8 = eight_bit_scale()
+    drv.layout = _lib.RAW_CASPSR if drv.info.machine == "CASPSR" else _lib.RAW_GENERIC
+
+
+def _open_convolving_front(drv, r, nsub, in_nchan, kernel, **setup):
+    """The convolving filterbank of -F N:D with the response `r` on the driver's context, `in_nchan` input channels per block."""
+    info = drv.info
+    _adopt_front(drv, FilterbankEngine(drv.ctx).setup(nsub, r.ndat, r.impulse_pos, r.impulse_neg, in_nchan, info.npol, info.ndim == 1,
+                                                      kernel, **setup))
+
+
+class DelayCarry:
+    """The head room of -K in front of a block of detected rows, and the tail carried in it.  dsp::SampleDelay gives up its
+    total_delay at the end of every block and InputBuffering re-presents those samples in front of the next one (SampleDelay.C:117,
+    146): a block's new samples are written behind `head` samples of room, the `carried` ones of the block before sit right in
+    front of them.  `short`: samples a sub-band rank gives up on top of its own delay, so that all ranks emit the same ones.
+    `delays` (relative, per channel): SampleDelay::build on the host (SampleDelay.C:75-99) -- zero = the largest delay, head = the
+    largest applied one, dsp::SampleDelay's zero_delay and total_delay."""
+
+    def __init__(self, delays=None):
+        self.zero = self.head = self.carried = self.short = 0
+        if delays is not None:
+            d = np.asarray(delays, np.int64)
+            self.zero = int(d.max())
+            self.head = int((self.zero - d).max())
+
+    def check_block(self, who, block):
+        if self.head > block:
+            raise DspsrAmdError("dspsr_amd.%s: inter-channel delay of %d samples exceeds the block of %d" % (who, self.head, block))
+
+    def rows(self, buf, ndat, ndim=1):
+        """the samples to transform, `ndat` new ones lying behind the head room of buf [chan][pol][sample * ndim]: the carried tail
+        and the new samples less `short` (empty when nothing is left: no transform then)"""
+        off, nuse = self.head - self.carried, self.carried + ndat - self.short
+        return buf[:, :, off * ndim:(off + max(nuse, 0)) * ndim]
+
+    def keep_tail(self, ctx, buf, ndat, nout, ndim=1):
+        """InputBuffering::set_next_start(output_ndat): the transform delivered `nout` samples; the unshifted tail goes in front of
+        the next block (nothing to move when it lies there already)"""
+        off, nin = self.head - self.carried, self.carried + ndat
+        carry = nin - nout
+        if carry and off + nout != self.head - carry:
+            move_tail_fpt(ctx, buf, self.head - carry, off + nout, carry, ndim)
+        self.carried = carry
+
+
+def _carry_view(name):
+    return property(lambda self: getattr(self.sd, name))
+
+
+def _accumulate(acc, folded, ndat_fold, rate):
+    """The books of one fold call on an accumulator (hits, integration_length, ndat_total, subints: a LoadToFold or a _PulsarFold);
+    hits[] were counted by the plan (Fold.C:744-803)."""
+    acc.integration_length += folded / rate
+    acc.ndat_total += ndat_fold
+
+
+def _books(acc, **profile):
+    """The entry of `subints` for the integration the accumulator holds"""
+    return {"hits": acc.hits.copy(), "integration_length": acc.integration_length, "ndat_total": acc.ndat_total, **profile}
+
+
+def _emit(acc, entry, zero):
+    """Subint<Fold> (Subint.h:291-303): hand over the sub-integration (entry None: it went another way) and start the next one"""
+    if entry is not None:
+        acc.subints.append(entry)
+    zero()
+    acc.hits[:] = 0
+    acc.integration_length = 0.0
+    acc.ndat_total = 0
+
+
+def _close_all(*objs):
+    for o in objs:
+        if o is not None:
+            o.close()
+
+
 class LoadToFold:
     """One pipeline instance = one GPU = one stream (SingleThread).  `raw` blocks are int8 torch
     tensors already resident on the device (the PCIe copy is the caller's, as TransferCUDA is a
-    separate Operation in the reference)."""
+    separate Operation in the reference).
+
+    Construction is `_plan` -- host code: every refusal that needs no device, every derived number -- then `_open`, which only opens
+    things; whatever raises in it, close() releases what was opened so far."""
+
+    sd_head, sd_carried, sd_short = _carry_view("head"), _carry_view("carried"), _carry_view("short")
 
     def __init__(self, cfg: Config, info: InputInfo, device: int = 0, stream: int | None = None,
                  polyco: Polyco | None = None, reference_phase: float = 0.0, subband: int | None = None,
@@ -1066,46 +1175,64 @@ class LoadToFold:
         polyco / reference_phase / cfg.folding_period, and cfg.nbin by each target's nbin, or by Fold::choose_nbin for its period
         where the target's nbin is 0 (also with a single target).  One target: the single-pulsar path of this class, unchanged.  Several: `pulsars` holds one fold engine, hits, sub-integration divider and `subints` list per
         target; Detection writes the detected rows and the pulsars fold them with FoldEngine.fold_many (the rows are read once);
-        `subints` / `hits` of the instance itself stay empty.  Multi-GPU exchange (subband, communicators) is single-pulsar only."""
+        `subints` / `hits` of the instance itself stay empty.  Multi-GPU exchange (subband, communicators) is single-pulsar only.
+
+        subband = g: this instance is rank g of a sub-band sharded run.  `info`/`cfg` still describe the
+        WHOLE band (info.nchan input channels, cfg.nchan output channels); the instance processes input channel g only:
+        its block holds that channel's bytes alone ([t][pol][dim], what a rank reads from the NCHAN-interleaved file),
+        its kernel is the g-th slice of the ONE full-band kernel (Filterbank.C:563, FilterbankCUDA.cu:249-251) with the
+        COMMON nfilt_pos/neg, so all ranks stay sample aligned and fold with identical hits."""
         targets = list(targets or [])
-        self.pulsars = []
-        self.cyclic = None
-        self.plfb = None
-        self.rfi_filter = None
-        if cfg.zap_rfi:                                  # (before any device resource is opened)
+        self._defaults()
+        self._plan(cfg, info, polyco, reference_phase, subband, tuple(dump_before), targets)
+        try:
+            self._open(device, stream, dump_dir)
+            if targets:
+                self._init_targets(targets)
+        except BaseException:
+            self.close()
+            raise
+
+    def _defaults(self):
+        """Every field the class reads later; a path overrides only what differs."""
+        import torch
+        self.torch = torch
+        self.pulsars, self.cyclic, self.plfb, self.rfi_filter = [], None, None, None
+        self.ctx = self.fb = self.fold = self.response = self.sample_delay = self.detected = self.voltages = None
+        self.sd = DelayCarry()              # -K: head room in front of `detected` and the tail carried in it
+        self.fused_mode, self.fused_fold = 0, False
+        self.optime = {}                    # record_time: operation name -> [seconds, calls]
+        self.dumps, self._dump_cplx = {}, None
+        self._turns, self._moment_rows, self._moment_buf = None, None, None
+        self._calibrated, self._delays, self._taps = None, None, ()
+        self._closed = False
+        # fold bookkeeping (PhaseSeries)
+        self.hits = np.zeros(0, dtype=np.uint32)
+        self.integration_length, self.ndat_total = 0.0, 0
+        self.nsamples_in = 0                # unique input samples consumed (per pol)
+        self.ndat_out = 0                   # output samples produced so far
+        self.subints = []                   # completed sub-integrations (host copies) on the writer rank
+
+    def _plan(self, cfg, info, polyco, reference_phase, subband, dump_before, targets):
+        """The host side of the constructor: what the run refuses, in the order it always has, and every number that needs no device."""
+        if cfg.zap_rfi:
             rfi_check(cfg, info, subband)
-        self._calibrated = calibrator_response(cfg, info, subband)      # -pac (before any device resource is opened)
-        if cfg.plfb_nbin > 0:                            # (before any device resource is opened)
+        self._calibrated = calibrator_response(cfg, info, subband)      # -pac
+        if cfg.plfb_nbin > 0:
             plfb_check(cfg, info, len(targets), subband, dump_before)
         self.moments = fourth_moment_active(cfg)         # -4: the fold is (nchan, 1, 14, nbin), fed by FoldEngine.fold_moments
         cfg = fourth_moment_check(cfg, len(targets), subband)
-        if cfg.cyclic_nchan > 0:                         # (before any device resource is opened)
+        if cfg.cyclic_nchan > 0:
             self._cyclic_geometry = cyclic_check(cfg, info, len(targets), subband, dump_before)
         if len(targets) > 1 and subband is not None:
             raise DspsrAmdError("dspsr_amd.LoadToFold: sub-band sharded runs fold one pulsar; %d targets given" % len(targets))
-        for t in targets:                                # (before any device resource is opened)
+        for t in targets:
             if t.polyco is None and t.folding_period <= 0:
                 raise DspsrAmdError("dsp::Fold::fold no polynomial and no period specified (target %r)" % (t.name,))
         if targets:
             t = targets[0]
             cfg = dataclasses.replace(cfg, folding_period=t.folding_period if t.polyco is None else 0.0)
             polyco, reference_phase = t.polyco, t.reference_phase
-        self._init_pipeline(cfg, info, device, stream, polyco, reference_phase, subband, dump_before, dump_dir)
-        if targets:
-            try:
-                self._init_targets(targets)
-            except BaseException:
-                self.close()
-                raise
-
-    def _init_pipeline(self, cfg, info, device, stream, polyco, reference_phase, subband, dump_before, dump_dir):
-        """subband = g: this instance is rank g of a sub-band sharded run.  `info`/`cfg` still describe the
-        WHOLE band (info.nchan input channels, cfg.nchan output channels); the instance processes input channel g only:
-        its block holds that channel's bytes alone ([t][pol][dim], what a rank reads from the NCHAN-interleaved file),
-        its kernel is the g-th slice of the ONE full-band kernel (Filterbank.C:563, FilterbankCUDA.cu:249-251) with the
-        COMMON nfilt_pos/neg, so all ranks stay sample aligned and fold with identical hits."""
-        import torch
-        self.torch = torch
         self.cfg, self.info, self.polyco = cfg, info, polyco
         self.reference_phase = reference_phase
         self.subband = subband
@@ -1113,228 +1240,97 @@ class LoadToFold:
             raise DspsrAmdError("dspsr_amd.LoadToFold: subband=%d outside the %d input channels" % (subband, info.nchan))
         if cfg.folding_period <= 0 and polyco is None:
             raise DspsrAmdError("dsp::Fold::fold no polynomial and no period specified")   # Fold.C:638-640
-        if cfg.cyclic_nchan > 0:
-            return self._init_cyclic(device, stream)
-        if cfg.plfb_nbin > 0:
-            return self._init_plfb(device, stream)
-        if info.npol != 2:
-            raise DspsrAmdError("dsp::Detection::polarimetry Cannot detect polarization when npol != 2")
-        if cfg.convolve_when not in ("during", "after", "before", "never"):
-            raise DspsrAmdError("dspsr_amd.LoadToFold: convolve_when=%r is not one of during / after / before / never" % (cfg.convolve_when,))
+        convolving = cfg.cyclic_nchan > 0 or cfg.plfb_nbin > 0           # -cyclic and -G read the complex rows of -F N:D
+        if not convolving:
+            if info.npol != 2:
+                raise DspsrAmdError("dsp::Detection::polarimetry Cannot detect polarization when npol != 2")
+            if cfg.convolve_when not in ("during", "after", "before", "never"):
+                raise DspsrAmdError("dspsr_amd.LoadToFold: convolve_when=%r is not one of during / after / before / never" % (cfg.convolve_when,))
         if cfg.nchan % info.nchan:
             raise DspsrAmdError("dsp::Filterbank::make_preparations output nchan=%d not a multiple of input nchan=%d"
                                 % (cfg.nchan, info.nchan))
-        if cfg.convolve_when != "during":
-            return self._init_after(device, stream, subband, dump_before)
-        self.ctx = Context(device, stream)
-        # kernel (host) --------------------------------------------------------------------
-        self.response = Dedispersion(info.centre_frequency, info.bandwidth, cfg.dispersion_measure,
-                                     input_nchan=info.nchan, ndim=info.ndim,
-                                     fractional_delay=cfg.interchan_dedispersion)       # LoadToFold1.C:620-621
-        if cfg.freq_res:
-            self.response.set_frequency_resolution(cfg.freq_res)
-        self.response.match(cfg.nchan)
-        r = self.response
-        # engines --------------------------------------------------------------------------
-        nsub = cfg.nchan // info.nchan
-        kernel = r.kernel
-        # -pac: chirp x Jones per bin as a matrix response instead of the chirp (calibrator_response)
-        matrix = self._calibrated[1] if getattr(self, "_calibrated", None) else None
-        if matrix is not None:
-            kernel = None
-        if subband is not None:
-            kernel = kernel[subband * nsub * r.ndat:(subband + 1) * nsub * r.ndat]
         self.in_nchan = 1 if subband is not None else info.nchan         # input channels in this instance's blocks
-        self.nchan_out = nsub * self.in_nchan                              # output channels this instance produces
-        self.fb = FilterbankEngine(self.ctx).setup(nsub, r.ndat, r.impulse_pos, r.impulse_neg,
-                                                   self.in_nchan, info.npol, info.ndim == 1, kernel,
-                                                   max_parts=cfg.max_parts, force_four_pass=0 if cfg.two_pass else 2,
-                                                   fused_fold=(_lib.FUSED_NEVER if not cfg.fused_fold else
-                                                               _lib.FUSED_ALWAYS if cfg.force_fused else _lib.FUSED_AUTO),
-                                                   response_matrix=matrix)
-        self.nkeep, self.nsamp_step, self.nsamp_overlap = self.fb.nkeep, self.fb.nsamp_step, self.fb.nsamp_overlap
+        self.nchan_out = (cfg.nchan // info.nchan) * self.in_nchan       # output channels this instance produces
         self.npol_out = 4 // cfg.ndim
-        self.fold = FoldEngine(self.ctx)
-        self.fold.set_shape(self.nchan_out, *self._fold_dims(), cfg.nbin)
-        self.scale8 = eight_bit_scale()
-        self.layout = _lib.RAW_CASPSR if info.machine == "CASPSR" else _lib.RAW_GENERIC
-        # output observation (Filterbank::prepare_output, Filterbank.C:265-379)
-        n_fft = (cfg.nchan // info.nchan) * r.ndat
-        nsamp_fft = 2 * n_fft if info.ndim == 1 else n_fft
-        self.out_rate = info.rate * (float(r.ndat) / float(nsamp_fft))
-        self.out_start = info.start_seconds + r.impulse_pos / self.out_rate
-        self.scalefac = float(n_fft) * float(r.ndat)
-        # -K: dsp::SampleDelay on the filterbank output.  Detection acts sample by sample, so delaying the detected rows
-        # gives the same numbers as delaying the complex rows first (the reference's order) and keeps the fused
-        # filterbank+detect launch group.  The last `total_delay` samples of a block are re-presented in front of the
-        # next one (InputBuffering, SampleDelay.C:117,146): they live in the head room in front of `detected`.
-        self.sample_delay, self.sd_carried, head = None, 0, 0
-        if cfg.interchan_dedispersion:
-            dual = info.ndim == 2                              # Observation.C:80-87; Filterbank.C:358-364
-            delays = dedispersion_sample_delays(info.centre_frequency, info.bandwidth, cfg.dispersion_measure, cfg.nchan,
-                                                self.out_rate, swap=dual and info.nchan == 1,
-                                                nsub_swap=info.nchan if dual and info.nchan > 1 else 0)
-            self.sd_short = 0
-            if subband is None:
-                self.sample_delay = SampleDelay(self.ctx, delays, self.npol_out)
-                head, zero = self.sample_delay.total_delay, self.sample_delay.zero_delay
-            else:
-                # a sub-band rank applies ITS channels' delays relative to the zero of the WHOLE band and gives up the
-                # whole band's total delay per block, so that every rank emits the same samples with the same start time
-                # (SampleDelay.C:75-99 on the full band; the rank's slice goes in as absolute delays)
-                d = np.asarray(delays, np.int64)
-                zero = int(d.max())
-                applied = zero - d
-                head = int(applied.max())
-                mine = applied[subband * nsub:(subband + 1) * nsub]
-                self.sample_delay = SampleDelay(self.ctx, mine, self.npol_out, absolute=True)
-                self.sd_short = head - self.sample_delay.total_delay       # samples this rank must NOT emit
-            if head > cfg.parts_per_block * self.nkeep:
-                raise DspsrAmdError("dspsr_amd.LoadToFold: inter-channel delay of %d samples exceeds the block of %d"
-                                    % (head, cfg.parts_per_block * self.nkeep))
-            self.out_start += zero / self.out_rate                               # SampleDelay.C:159
-        self.sd_head = head
-        self.detected = torch.empty((self.nchan_out, self.npol_out, (head + cfg.parts_per_block * self.nkeep) * cfg.ndim),
-                                    dtype=torch.float32, device="cuda:%d" % device)
-        # fused filterbank+detect+fold (no detected time series in HBM): ndim 4, three-pass geometries
-        # (the library decides whether fusing pays for this geometry; when it does not, this driver keeps the
-        # separate Detection and Fold operations on its own `detected` block)
-        self.fused_mode = self.fb.fold_is_fused() if (cfg.fused_fold and cfg.ndim == 4 and self.sample_delay is None) else 0
-        self.fused_fold = self.fused_mode != 0      # fused_mode 2: sums re-associated per run of parts (engine.fold_is_fused)
-        # stage capture (dspsr --dump <Operation>, SingleThread.C:315-346): pre_Detection.dump / pre_Fold.dump ------------
-        self.optime = {}                    # record_time: operation name -> [seconds, calls]
-        self.dumps, self._dump_cplx = {}, None
+        if cfg.convolve_when != "during":
+            return self._plan_after(subband, dump_before)
+        # -F N:D: the response inside the filterbank (LoadToFold1.C:318-323; -K: the fractional delays with it, :620-621)
+        self.response = r = matched_response(info, cfg.dispersion_measure, cfg.freq_res, cfg.nchan, input_nchan=info.nchan, ndim=info.ndim,
+                                             fractional_delay=cfg.interchan_dedispersion)
+        self.out_rate, self.out_start, self.scalefac = filterbank_output(info, r, cfg.nchan // info.nchan)
+        if cfg.cyclic_nchan > 0:
+            self.npol_out = self._cyclic_geometry["npol"]
+        elif cfg.plfb_nbin > 0:
+            self._plan_plfb()
+        else:
+            self._plan_delays()
+            self._plan_taps(dump_before)
+
+    def _plan_after(self, subband, dump_before):
+        """`dspsr -F N` (Filterbank::Config::After) and the filterbank without coherent dedispersion (Config::Never): the non-convolving
+        filterbank (freq_res = 1) followed by dsp::Convolution on its output channels (LoadToFold1.C:296-380).  The response is matched
+        to the FILTERBANK'S OUTPUT observation (Convolution.C:105-130 -> Dedispersion::match(input)): cfg.nchan channels, complex,
+        dual sideband and DC centred (Filterbank.C:341-348: freq_res = 1), band swapped when the input was single-channel dual
+        sideband (:358-364; a multi-channel dual-sideband input sets nsub_swap, which Response::match does not read, Response.C:132-181).
+        `dspsr -F N:B` (Config::Before): Convolution::prepare -> Dedispersion::match(input), ONE response per input channel, over
+        its whole width."""
+        cfg, info = self.cfg, self.info
+        if subband is not None:
+            raise DspsrAmdError("dspsr_amd.LoadToFold: sub-band sharded runs are built for -F N:D (convolve_when = during)")
+        if cfg.interchan_dedispersion or dump_before:
+            raise DspsrAmdError("dspsr_amd.LoadToFold: -K and the dump taps are built for -F N:D (convolve_when = during)")
+        nsub = cfg.nchan // info.nchan
+        if cfg.convolve_when == "before":
+            self.response = r = matched_response(info, cfg.dispersion_measure, cfg.freq_res, info.nchan, input_nchan=info.nchan, ndim=info.ndim)
+            conv_rate = info.rate * (0.5 if info.ndim == 1 else 1.0)                           # Convolution.C:266-267
+            self.out_rate = conv_rate / float(nsub)                                            # Filterbank.C:338-339
+            self.out_start = info.start_seconds + r.impulse_pos / conv_rate                   # Convolution.C:300
+            nsamp_fft = 2 * r.ndat if info.ndim == 1 else r.ndat
+            self.scalefac = float(nsamp_fft) * float(r.ndat) * float(nsub)                    # Convolution.C:305, Filterbank.C:124-125
+            return
+        r = None
+        if cfg.convolve_when == "after":
+            r = matched_response(info, cfg.dispersion_measure, cfg.freq_res, cfg.nchan, input_nchan=cfg.nchan, ndim=2, dual_sideband=1,
+                                 dc_centred=True, swap=(info.ndim == 2 and info.nchan == 1))
+        self.response = r
+        nsamp_fft_front = 2 * nsub if info.ndim == 1 else nsub                           # input samples per filterbank output sample
+        self.out_rate = info.rate / float(nsamp_fft_front)                               # Filterbank.C:338-339: freq_res / nsamp_fft
+        ndat = r.ndat if r is not None else 1
+        self.out_start = info.start_seconds + (r.impulse_pos if r is not None else 0) / self.out_rate   # Convolution.C:300
+        self.scalefac = float(nsub) * (float(ndat) * float(ndat) if r is not None else 1.0)            # Filterbank.C:124-125, Convolution.C:305
+
+    def _plan_delays(self):
+        """-K: dsp::SampleDelay on the filterbank output.  Detection acts sample by sample, so delaying the detected rows
+        gives the same numbers as delaying the complex rows first (the reference's order) and keeps the fused
+        filterbank+detect launch group.  The last `total_delay` samples of a block are re-presented in front of the
+        next one (InputBuffering, SampleDelay.C:117,146): they live in the head room in front of `detected` (DelayCarry)."""
+        cfg, info = self.cfg, self.info
+        if not cfg.interchan_dedispersion:
+            return
+        dual = info.ndim == 2                              # Observation.C:80-87; Filterbank.C:358-364
+        self._delays = dedispersion_sample_delays(info.centre_frequency, info.bandwidth, cfg.dispersion_measure, cfg.nchan, self.out_rate,
+                                                  swap=dual and info.nchan == 1, nsub_swap=info.nchan if dual and info.nchan > 1 else 0)
+        self.sd = DelayCarry(self._delays)
+        self.out_start += self.sd.zero / self.out_rate                               # SampleDelay.C:159
+
+    def _plan_taps(self, dump_before):
+        """stage capture (dspsr --dump <Operation>, SingleThread.C:315-346): pre_Detection.dump / pre_Fold.dump"""
         for name in dump_before:
             if name not in ("Detection", "Fold"):
                 raise DspsrAmdError("dsp::SingleThread::insert_dump_point no operation named '%s' on this path "
                                     "(Detection, Fold)" % name)
-            if name == "Detection" and self.sample_delay is not None:
+            if name == "Detection" and self.cfg.interchan_dedispersion:
                 raise DspsrAmdError("dspsr_amd.LoadToFold: the pre_Detection tap is not built for -K (the delay is applied "
                                     "to the detected rows here); tap pre_Fold instead")
-            from . import dada
-            chbw = info.bandwidth / info.nchan
-            fc = info.centre_frequency if subband is None else info.centre_frequency - 0.5 * info.bandwidth + (subband + 0.5) * chbw
-            bw = info.bandwidth if subband is None else chbw
-            det = name == "Fold"
-            path = os.path.join(dump_dir, "pre_%s%s.dump" % (name, "" if subband is None else ".%d" % subband))
-            fold_npol, fold_ndim = self._fold_dims()        # -4: the input of Fold is the FourthMoment stream
-            self.dumps[name] = dada.Dump(
-                path, centre_frequency=fc, bandwidth=bw, nchan=self.nchan_out, npol=fold_npol if det else 2,
-                ndim=fold_ndim if det else 2, nbit=32, rate=self.out_rate, mjd_day=info.mjd_day,
-                mjd_sec=info.mjd_sec + self.out_start,
-                state=("FourthMoment" if self.moments else "Stokes" if cfg.stokes else "Coherence") if det else "Analytic",
-                source=getattr(info, "source", "unknown"), telescope=getattr(info, "telescope", "unknown"))
-        if "Fold" in self.dumps:
-            self.fused_mode, self.fused_fold = 0, False          # the detected samples must exist in HBM to be dumped
-        # fold bookkeeping (PhaseSeries) ---------------------------------------------------
-        self.hits = np.zeros(cfg.nbin, dtype=np.uint32)
-        self.integration_length = 0.0
-        self.ndat_total = 0
-        self.nsamples_in = 0            # unique input samples consumed (per pol)
-        self.ndat_out = 0               # output samples produced so far
-        self.subints = []               # completed sub-integrations (host copies) on the writer rank
+        self._taps = dump_before
 
-    def _init_cyclic(self, device, stream):
-        """`dspsr -cyclic N`: the convolving filterbank writes its complex rows, dsp::CyclicFold folds their lag products
-        (LoadToFold1.C:534-539,999-1044); Detection and Fold are not built.  At a sub-integration the lag data come to the host
-        and CyclicFoldEngine::synch turns them into spectra (once per sub-integration: host, as in the reference)."""
-        import torch
-        cfg, info, g = self.cfg, self.info, self._cyclic_geometry
-        if cfg.nchan % info.nchan:
-            raise DspsrAmdError("dsp::Filterbank::make_preparations output nchan=%d not a multiple of input nchan=%d"
-                                % (cfg.nchan, info.nchan))
-        self.ctx = Context(device, stream)
-        self.response = Dedispersion(info.centre_frequency, info.bandwidth, cfg.dispersion_measure, input_nchan=info.nchan,
-                                     ndim=info.ndim)
-        if cfg.freq_res:
-            self.response.set_frequency_resolution(cfg.freq_res)
-        self.response.match(cfg.nchan)
-        r = self.response
-        nsub = cfg.nchan // info.nchan
-        self.in_nchan, self.nchan_out = info.nchan, cfg.nchan
-        self.fb = FilterbankEngine(self.ctx).setup(nsub, r.ndat, r.impulse_pos, r.impulse_neg, info.nchan, info.npol, info.ndim == 1,
-                                                   r.kernel, max_parts=cfg.max_parts, force_four_pass=0 if cfg.two_pass else 2,
-                                                   fused_fold=_lib.FUSED_NEVER)
-        self.nkeep, self.nsamp_step, self.nsamp_overlap = self.fb.nkeep, self.fb.nsamp_step, self.fb.nsamp_overlap
-        self.npol_out = g["npol"]
-        self.fold = None
-        self.cyclic = CyclicFoldEngine(self.ctx)
-        self.cyclic.set_shape(self.nchan_out, info.npol, g["npol"], g["nlag"], g["mover"], cfg.nbin)
-        self.scale8 = eight_bit_scale()
-        self.layout = _lib.RAW_CASPSR if info.machine == "CASPSR" else _lib.RAW_GENERIC
-        n_fft = nsub * r.ndat
-        nsamp_fft = 2 * n_fft if info.ndim == 1 else n_fft
-        self.out_rate = info.rate * (float(r.ndat) / float(nsamp_fft))
-        self.out_start = info.start_seconds + r.impulse_pos / self.out_rate
-        self.scalefac = float(n_fft) * float(r.ndat)
-        self.sample_delay, self.sd_carried, self.sd_head = None, 0, 0
-        self.voltages = torch.empty((self.nchan_out, info.npol, 2 * cfg.parts_per_block * self.nkeep), dtype=torch.float32,
-                                    device="cuda:%d" % device)
-        self.fused_mode, self.fused_fold = 0, False
-        self.optime, self.dumps, self._dump_cplx = {}, {}, None
-        self.hits = np.zeros(cfg.nbin, dtype=np.uint32)
-        self.integration_length, self.ndat_total = 0.0, 0
-        self.nsamples_in, self.ndat_out = 0, 0
-        self.subints = []
-
-    def _process_block_cyclic(self, raw, npart, events):
-        """Filterbank -> complex rows -> CyclicFold piece by piece (Subint<CyclicFold>).  Lag products never span two fold
-        calls (CyclicFold.C:390: idat < ndat_fold - nlag), so the last nlag samples of every piece add nothing."""
-        ndat = npart * self.nkeep
-        if events is not None:
-            events[0].record()
-        self._op("Filterbank", lambda: self.fb.perform_raw(raw, self.layout, self.scale8, self.voltages, npart))
-        if events is not None:
-            events[1].record()
-        for idat_start, ndat_fold, _division, complete in self._pieces(ndat):
-            t0 = self.out_start + (self.ndat_out + idat_start + 0.5) / self.out_rate
-            phi, pfold = self._phase(t0)
-            self.cyclic.set_ndat(ndat_fold, idat_start)
-            folded = self.cyclic.set_bins(phi, (1.0 / self.out_rate) / pfold, ndat_fold, idat_start, self.hits)
-            self._op("CyclicFold", lambda: self.cyclic.fold(self.voltages))
-            self.integration_length += folded / self.out_rate
-            self.ndat_total += ndat_fold
-            if complete:
-                self.finish_subint()
-        self.ndat_out += ndat
-        self.nsamples_in += npart * self.nsamp_step
-
-    def _finish_cyclic_subint(self):
-        """CyclicFoldEngine::synch (CyclicFold.C:450-555): spectra [nchan * nchan_spec / mover][npol][nbin][1] on the host"""
-        if not self.ndat_total:                              # nothing folded since the last one (as the multi-pulsar branch)
-            return
-        spectra = self._op("CyclicFold::synch", lambda: self.cyclic.synch())
-        self.subints.append({"hits": self.hits.copy(), "integration_length": self.integration_length,
-                             "ndat_total": self.ndat_total, "profile": spectra[..., None]})
-        self.cyclic.zero()
-        self.hits[:] = 0
-        self.integration_length = 0.0
-        self.ndat_total = 0
-
-    def _init_plfb(self, device, stream):
+    def _plan_plfb(self):
         """`dspsr -G nbin`: the convolving filterbank writes its complex rows and dsp::PhaseLockedFilterbank consumes them
         (LoadToFold1.C:386-456); Detection and Fold are not built.  One integration over the whole stream: the windows are those
         of ONE transformation call (PlfbPlan), whatever the block size.  The rows of a block sit behind a head room that holds the
-        carried tail -- the samples from the first window that does not fit yet -- so that a window may span two blocks."""
-        import torch
+        carried tail -- the samples from the first window that does not fit yet -- so that a window may span two blocks.
+        PhaseLockedFilterbank::prepare (:59-83), all on the host."""
         cfg, info = self.cfg, self.info
-        if cfg.nchan % info.nchan:
-            raise DspsrAmdError("dsp::Filterbank::make_preparations output nchan=%d not a multiple of input nchan=%d"
-                                % (cfg.nchan, info.nchan))
-        self.response = Dedispersion(info.centre_frequency, info.bandwidth, cfg.dispersion_measure, input_nchan=info.nchan,
-                                     ndim=info.ndim)
-        if cfg.freq_res:
-            self.response.set_frequency_resolution(cfg.freq_res)
-        self.response.match(cfg.nchan)
-        r = self.response
-        nsub = cfg.nchan // info.nchan
-        self.in_nchan, self.nchan_out = info.nchan, cfg.nchan
-        n_fft = nsub * r.ndat
-        nsamp_fft = 2 * n_fft if info.ndim == 1 else n_fft
-        self.out_rate = info.rate * (float(r.ndat) / float(nsamp_fft))
-        self.out_start = info.start_seconds + r.impulse_pos / self.out_rate
-        self.scalefac = float(n_fft) * float(r.ndat)
-        # PhaseLockedFilterbank::prepare (:59-83), all on the host
         period, polyco, reference_phase = self._ephemeris()
         if period <= 0:
             period = 1.0 / polyco.frequency(info.mjd_day, info.mjd_sec + self.out_start)
@@ -1348,39 +1344,127 @@ class LoadToFold:
         self.plfb_geometry = {"nchan_fft": nchan, "ndat_fft": nchan, "nchan": cfg.nchan * nchan, "npol": cfg.npol, "ndim": 1,
                               "nbin": cfg.plfb_nbin, "state": state, "rate": self.out_rate / nchan, "nsub_swap": cfg.nchan,
                               "scale": self.scalefac * nchan}                          # :143-149
-        self.ctx = Context(device, stream)
-        self.fb = FilterbankEngine(self.ctx).setup(nsub, r.ndat, r.impulse_pos, r.impulse_neg, info.nchan, info.npol, info.ndim == 1,
-                                                   r.kernel, max_parts=cfg.max_parts, force_four_pass=0 if cfg.two_pass else 2,
-                                                   fused_fold=_lib.FUSED_NEVER)
-        self.nkeep, self.nsamp_step, self.nsamp_overlap = self.fb.nkeep, self.fb.nsamp_step, self.fb.nsamp_overlap
         self.npol_out = cfg.npol
-        self.fold = None
-        self.plfb = PhaseLockedFilterbankEngine(self.ctx)
-        self.plfb.set_shape(cfg.nchan, info.npol, 2, nchan, cfg.npol, cfg.plfb_nbin)
         self.plfb_plan = PlfbPlan(self._turns_divider(*self._ephemeris(), turns=1.0 / cfg.plfb_nbin), cfg.plfb_nbin, reference_phase,
                                   nchan)
         self.plfb_head, self.plfb_tail = nchan, 0           # head room (samples) in front of a block's rows; samples carried in it
-        self.scale8 = eight_bit_scale()
-        self.layout = _lib.RAW_CASPSR if info.machine == "CASPSR" else _lib.RAW_GENERIC
-        self.sample_delay, self.sd_carried, self.sd_head = None, 0, 0
-        self.voltages = torch.empty((self.nchan_out, info.npol, 2 * (self.plfb_head + cfg.parts_per_block * self.nkeep)),
-                                    dtype=torch.float32, device="cuda:%d" % device)
-        self.fused_mode, self.fused_fold = 0, False
-        self.optime, self.dumps, self._dump_cplx = {}, {}, None
-        self.hits = np.zeros(cfg.plfb_nbin, dtype=np.uint32)
-        self.integration_length, self.ndat_total = 0.0, 0
-        self.nsamples_in, self.ndat_out = 0, 0
-        self.subints = []
+
+    def _open(self, device, stream, dump_dir):
+        """The device side of the constructor: the context, the front end, the fold of the mode, the block the two share."""
+        cfg, info = self.cfg, self.info
+        self.ctx = Context(device, stream)
+        r, nsub, rows = self.response, cfg.nchan // info.nchan, cfg.parts_per_block
+        fused = _lib.FUSED_NEVER if not cfg.fused_fold else _lib.FUSED_ALWAYS if cfg.force_fused else _lib.FUSED_AUTO
+        setup = dict(max_parts=cfg.max_parts, force_four_pass=0 if cfg.two_pass else 2)
+        if cfg.cyclic_nchan > 0:
+            # `dspsr -cyclic N`: the convolving filterbank writes its complex rows, dsp::CyclicFold folds their lag products
+            # (LoadToFold1.C:534-539,999-1044); Detection and Fold are not built.  At a sub-integration the lag data come to the
+            # host and CyclicFoldEngine::synch turns them into spectra (once per sub-integration: host, as in the reference).
+            g = self._cyclic_geometry
+            _open_convolving_front(self, r, nsub, info.nchan, r.kernel, fused_fold=_lib.FUSED_NEVER, **setup)
+            self.cyclic = CyclicFoldEngine(self.ctx)
+            self.cyclic.set_shape(self.nchan_out, info.npol, g["npol"], g["nlag"], g["mover"], cfg.nbin)
+            self.voltages = _device_empty(self.ctx, (self.nchan_out, info.npol, 2 * rows * self.nkeep))
+            self.hits = np.zeros(cfg.nbin, dtype=np.uint32)
+            return
+        if cfg.plfb_nbin > 0:
+            _open_convolving_front(self, r, nsub, info.nchan, r.kernel, fused_fold=_lib.FUSED_NEVER, **setup)
+            self.plfb = PhaseLockedFilterbankEngine(self.ctx)
+            self.plfb.set_shape(cfg.nchan, info.npol, 2, self.plfb_geometry["nchan_fft"], cfg.npol, cfg.plfb_nbin)
+            self.voltages = _device_empty(self.ctx, (self.nchan_out, info.npol, 2 * (self.plfb_head + rows * self.nkeep)))
+            self.hits = np.zeros(cfg.plfb_nbin, dtype=np.uint32)
+            return
+        if cfg.convolve_when == "during":
+            # -pac: chirp x Jones per bin as a matrix response instead of the chirp (calibrator_response)
+            matrix = self._calibrated[1] if self._calibrated else None
+            kernel = None if matrix is not None else r.kernel
+            if self.subband is not None:
+                kernel = kernel[self.subband * nsub * r.ndat:(self.subband + 1) * nsub * r.ndat]
+            _open_convolving_front(self, r, nsub, self.in_nchan, kernel, fused_fold=fused, response_matrix=matrix, **setup)
+        elif cfg.convolve_when == "before":
+            _adopt_front(self, ConvolutionThenFilterbank(self.ctx, nsub, info.nchan, info.npol, info.ndim == 1, r, max_parts=cfg.max_parts,
+                                                         parts_per_block=rows))
+        else:
+            _adopt_front(self, FilterbankThenConvolution(self.ctx, nsub, info.nchan, info.npol, info.ndim == 1, r, max_parts=cfg.max_parts,
+                                                         parts_per_block=rows, fused_fold=fused))
+        self.fold = FoldEngine(self.ctx)
+        self.fold.set_shape(self.nchan_out, *self._fold_dims(), cfg.nbin)
+        if cfg.interchan_dedispersion:
+            if self.subband is None:
+                self.sample_delay = SampleDelay(self.ctx, self._delays, self.npol_out)
+            else:
+                # a sub-band rank applies ITS channels' delays relative to the zero of the WHOLE band and gives up the
+                # whole band's total delay per block, so that every rank emits the same samples with the same start time
+                # (SampleDelay.C:75-99 on the full band; the rank's slice goes in as absolute delays)
+                applied = self.sd.zero - np.asarray(self._delays, np.int64)
+                self.sample_delay = SampleDelay(self.ctx, applied[self.subband * nsub:(self.subband + 1) * nsub], self.npol_out, absolute=True)
+                self.sd.short = self.sd.head - self.sample_delay.total_delay       # samples this rank must NOT emit
+            self.sd.check_block("LoadToFold", rows * self.nkeep)
+        self.detected = _device_empty(self.ctx, (self.nchan_out, self.npol_out, (self.sd.head + rows * self.nkeep) * cfg.ndim))
+        # fused filterbank+detect+fold (no detected time series in HBM): ndim 4, three-pass geometries
+        # (the library decides whether fusing pays for this geometry; when it does not, this driver keeps the
+        # separate Detection and Fold operations on its own `detected` block; -F N:B never fuses)
+        if cfg.fused_fold and cfg.ndim == 4 and self.sample_delay is None and cfg.convolve_when != "before":
+            self.fused_mode = self.fb.fold_is_fused()
+        self.fused_fold = self.fused_mode != 0      # fused_mode 2: sums re-associated per run of parts (engine.fold_is_fused)
+        for name in self._taps:
+            from . import dada
+            chbw = info.bandwidth / info.nchan
+            sub = self.subband
+            fc = info.centre_frequency if sub is None else info.centre_frequency - 0.5 * info.bandwidth + (sub + 0.5) * chbw
+            bw = info.bandwidth if sub is None else chbw
+            det = name == "Fold"
+            path = os.path.join(dump_dir, "pre_%s%s.dump" % (name, "" if sub is None else ".%d" % sub))
+            fold_npol, fold_ndim = self._fold_dims()        # -4: the input of Fold is the FourthMoment stream
+            self.dumps[name] = dada.Dump(
+                path, centre_frequency=fc, bandwidth=bw, nchan=self.nchan_out, npol=fold_npol if det else 2,
+                ndim=fold_ndim if det else 2, nbit=32, rate=self.out_rate, mjd_day=info.mjd_day,
+                mjd_sec=info.mjd_sec + self.out_start,
+                state=("FourthMoment" if self.moments else "Stokes" if cfg.stokes else "Coherence") if det else "Analytic",
+                source=getattr(info, "source", "unknown"), telescope=getattr(info, "telescope", "unknown"))
+        if "Fold" in self.dumps:
+            self.fused_mode, self.fused_fold = 0, False          # the detected samples must exist in HBM to be dumped
+        self.hits = np.zeros(cfg.nbin, dtype=np.uint32)
+
+    def _filterbank_op(self, name, fn, events):
+        """The filterbank step of a block as an operation, between the caller's two HIP events (bench.py's roofline brackets the
+        FFT + chirp launch group with them)."""
+        if events is not None:
+            events[0].record()
+        self._op(name, fn)
+        if events is not None:
+            events[1].record()
+
+    def _process_block_cyclic(self, raw, npart, events):
+        """Filterbank -> complex rows -> CyclicFold piece by piece (Subint<CyclicFold>).  Lag products never span two fold
+        calls (CyclicFold.C:390: idat < ndat_fold - nlag), so the last nlag samples of every piece add nothing."""
+        ndat = npart * self.nkeep
+        self._filterbank_op("Filterbank", lambda: self.fb.perform_raw(raw, self.layout, self.scale8, self.voltages, npart), events)
+        for idat_start, ndat_fold, _division, complete in self._pieces(ndat):
+            t0 = self.out_start + (self.ndat_out + idat_start + 0.5) / self.out_rate
+            phi, pfold = self._phase(t0)
+            self.cyclic.set_ndat(ndat_fold, idat_start)
+            folded = self.cyclic.set_bins(phi, (1.0 / self.out_rate) / pfold, ndat_fold, idat_start, self.hits)
+            self._op("CyclicFold", lambda: self.cyclic.fold(self.voltages))
+            _accumulate(self, folded, ndat_fold, self.out_rate)
+            if complete:
+                self.finish_subint()
+        self.ndat_out += ndat
+        self.nsamples_in += npart * self.nsamp_step
+
+    def _finish_cyclic_subint(self):
+        """CyclicFoldEngine::synch (CyclicFold.C:450-555): spectra [nchan * nchan_spec / mover][npol][nbin][1] on the host"""
+        if not self.ndat_total:                              # nothing folded since the last one (as the multi-pulsar branch)
+            return
+        spectra = self._op("CyclicFold::synch", lambda: self.cyclic.synch())
+        _emit(self, _books(self, profile=spectra[..., None]), self.cyclic.zero)
 
     def _process_block_plfb(self, raw, npart, events):
         """Filterbank -> complex rows behind the carried tail -> every window of the plan that now lies inside the rows, in one
         accumulate call; then the samples from the next window's start on are carried in front of the next block's rows."""
         ndat, head, tail = npart * self.nkeep, self.plfb_head, self.plfb_tail
-        if events is not None:
-            events[0].record()
-        self._op("Filterbank", lambda: self.fb.perform_raw(raw, self.layout, self.scale8, self.voltages[:, :, 2 * head:], npart))
-        if events is not None:
-            events[1].record()
+        self._filterbank_op("Filterbank", lambda: self.fb.perform_raw(raw, self.layout, self.scale8, self.voltages[:, :, 2 * head:], npart),
+                            events)
         base, avail = self.ndat_out - tail, self.ndat_out + ndat     # stream samples of the first row sample / behind the last
         starts, bins = self.plfb_plan.take(avail)
         if len(starts):
@@ -1407,13 +1491,8 @@ class LoadToFold:
             return
         g = self.plfb_geometry
         prof = self._op("PhaseLockedFilterbank::synch", lambda: self.plfb.synch())
-        self.subints.append({"hits": self.hits.copy(), "integration_length": self.integration_length, "ndat_total": self.ndat_total,
-                             "profile": prof[..., None], "state": g["state"], "rate": g["rate"], "nsub_swap": g["nsub_swap"],
-                             "scale": g["scale"]})
-        self.plfb.zero()
-        self.hits[:] = 0
-        self.integration_length = 0.0
-        self.ndat_total = 0
+        _emit(self, _books(self, profile=prof[..., None], state=g["state"], rate=g["rate"], nsub_swap=g["nsub_swap"], scale=g["scale"]),
+              self.plfb.zero)
 
     def _init_targets(self, targets):
         """nbin per target (Fold::choose_nbin for its period where the target gives none); several targets: one FoldEngine each,
@@ -1439,88 +1518,8 @@ class LoadToFold:
         self.fold.close()
         self.fold = None
         for t, nbin in zip(targets, nbins):
-            fold = FoldEngine(self.ctx)
-            fold.set_shape(self.nchan_out, self.npol_out, cfg.ndim, nbin)
-            self.pulsars.append(_PulsarFold(t, nbin, fold))
-
-    def _init_after(self, device, stream, subband, dump_before):
-        """`dspsr -F N` (Filterbank::Config::After) and the filterbank without coherent dedispersion (Config::Never): the non-convolving
-        filterbank (freq_res = 1) followed by dsp::Convolution on its output channels (LoadToFold1.C:296-380).  The response is matched
-        to the FILTERBANK'S OUTPUT observation (Convolution.C:105-130 -> Dedispersion::match(input)): cfg.nchan channels, complex,
-        dual sideband and DC centred (Filterbank.C:341-348: freq_res = 1), band swapped when the input was single-channel dual
-        sideband (:358-364; a multi-channel dual-sideband input sets nsub_swap, which Response::match does not read, Response.C:132-181)."""
-        torch, cfg, info = self.torch, self.cfg, self.info
-        if subband is not None:
-            raise DspsrAmdError("dspsr_amd.LoadToFold: sub-band sharded runs are built for -F N:D (convolve_when = during)")
-        if cfg.interchan_dedispersion or dump_before:
-            raise DspsrAmdError("dspsr_amd.LoadToFold: -K and the dump taps are built for -F N:D (convolve_when = during)")
-        self.ctx = Context(device, stream)
-        r = None
-        if cfg.convolve_when == "after":
-            r = Dedispersion(info.centre_frequency, info.bandwidth, cfg.dispersion_measure, input_nchan=cfg.nchan, ndim=2,
-                             dual_sideband=1, dc_centred=True, swap=(info.ndim == 2 and info.nchan == 1))
-            if cfg.freq_res:
-                r.set_frequency_resolution(cfg.freq_res)
-            r.match(cfg.nchan)
-        if cfg.convolve_when == "before":
-            # Convolution::prepare -> Dedispersion::match(input): ONE response per input channel, over its whole width
-            r = Dedispersion(info.centre_frequency, info.bandwidth, cfg.dispersion_measure, input_nchan=info.nchan, ndim=info.ndim)
-            if cfg.freq_res:
-                r.set_frequency_resolution(cfg.freq_res)
-            r.match(info.nchan)
-        self.response = r
-        nsub = cfg.nchan // info.nchan
-        self.in_nchan, self.nchan_out = info.nchan, cfg.nchan
-        if cfg.convolve_when == "before":
-            self._init_before(device, r, nsub)
-            return
-        self.fb = FilterbankThenConvolution(self.ctx, nsub, info.nchan, info.npol, info.ndim == 1, r, max_parts=cfg.max_parts,
-                                            parts_per_block=cfg.parts_per_block,
-                                            fused_fold=(_lib.FUSED_NEVER if not cfg.fused_fold else
-                                                        _lib.FUSED_ALWAYS if cfg.force_fused else _lib.FUSED_AUTO))
-        self.nkeep, self.nsamp_step, self.nsamp_overlap = self.fb.nkeep, self.fb.nsamp_step, self.fb.nsamp_overlap
-        self.npol_out = 4 // cfg.ndim
-        self.fold = FoldEngine(self.ctx)
-        self.fold.set_shape(self.nchan_out, *self._fold_dims(), cfg.nbin)
-        self.scale8 = eight_bit_scale()
-        self.layout = _lib.RAW_CASPSR if info.machine == "CASPSR" else _lib.RAW_GENERIC
-        self.out_rate = info.rate / float(self.fb.nsamp_fft_front)                       # Filterbank.C:338-339: freq_res / nsamp_fft
-        ndat = r.ndat if r is not None else 1
-        self.out_start = info.start_seconds + (r.impulse_pos if r is not None else 0) / self.out_rate   # Convolution.C:300
-        self.scalefac = float(nsub) * (float(ndat) * float(ndat) if r is not None else 1.0)            # Filterbank.C:124-125, Convolution.C:305
-        self.sample_delay, self.sd_carried, self.sd_head, self.sd_short = None, 0, 0, 0
-        self.detected = torch.empty((self.nchan_out, self.npol_out, cfg.parts_per_block * self.nkeep * cfg.ndim),
-                                    dtype=torch.float32, device="cuda:%d" % device)
-        self.fused_mode = self.fb.fold_is_fused() if (cfg.fused_fold and cfg.ndim == 4) else 0
-        self.fused_fold = self.fused_mode != 0
-        self.optime, self.dumps, self._dump_cplx = {}, {}, None
-        self.hits = np.zeros(cfg.nbin, dtype=np.uint32)
-        self.integration_length, self.ndat_total = 0.0, 0
-        self.nsamples_in, self.ndat_out, self.subints = 0, 0, []
-
-    def _init_before(self, device, r, nsub):
-        torch, cfg, info = self.torch, self.cfg, self.info
-        self.fb = ConvolutionThenFilterbank(self.ctx, nsub, info.nchan, info.npol, info.ndim == 1, r, max_parts=cfg.max_parts,
-                                            parts_per_block=cfg.parts_per_block)
-        self.nkeep, self.nsamp_step, self.nsamp_overlap = self.fb.nkeep, self.fb.nsamp_step, self.fb.nsamp_overlap
-        self.npol_out = 4 // cfg.ndim
-        self.fold = FoldEngine(self.ctx)
-        self.fold.set_shape(self.nchan_out, *self._fold_dims(), cfg.nbin)
-        self.scale8 = eight_bit_scale()
-        self.layout = _lib.RAW_CASPSR if info.machine == "CASPSR" else _lib.RAW_GENERIC
-        conv_rate = info.rate * (0.5 if info.ndim == 1 else 1.0)                           # Convolution.C:266-267
-        self.out_rate = conv_rate / float(nsub)                                            # Filterbank.C:338-339
-        self.out_start = info.start_seconds + r.impulse_pos / conv_rate                   # Convolution.C:300
-        nsamp_fft = 2 * r.ndat if info.ndim == 1 else r.ndat
-        self.scalefac = float(nsamp_fft) * float(r.ndat) * float(nsub)                    # Convolution.C:305, Filterbank.C:124-125
-        self.sample_delay, self.sd_carried, self.sd_head, self.sd_short = None, 0, 0, 0
-        self.detected = torch.empty((self.nchan_out, self.npol_out, cfg.parts_per_block * self.nkeep * cfg.ndim),
-                                    dtype=torch.float32, device="cuda:%d" % device)
-        self.fused_mode, self.fused_fold = 0, False
-        self.optime, self.dumps, self._dump_cplx = {}, {}, None
-        self.hits = np.zeros(cfg.nbin, dtype=np.uint32)
-        self.integration_length, self.ndat_total = 0.0, 0
-        self.nsamples_in, self.ndat_out, self.subints = 0, 0, []
+            self.pulsars.append(_PulsarFold(t, nbin, FoldEngine(self.ctx)))      # (listed first: close() finds it if set_shape raises)
+            self.pulsars[-1].fold.set_shape(self.nchan_out, self.npol_out, cfg.ndim, nbin)
 
     def _response_engine(self):
         """the engine that holds the dedispersion response: the convolving filterbank (-F N:D), or the Convolution of -F N / -F N:B"""
@@ -1557,19 +1556,15 @@ class LoadToFold:
             return self.fold.fold(self._moment_rows)
         return self.fold.fold_moments(rows)
 
-    _moment_rows = None
-
     def _moment_stream(self, rows, ndat):
         """dsp::FourthMoment on the first `ndat` samples of the Stokes rows (pre_Fold tap of a -4 run): [nchan][1][ndat*14]"""
         need = self.nchan_out * 14 * (self.sd_head + self.cfg.parts_per_block * self.nkeep)
         if self._moment_buf is None or self._moment_buf.numel() < need:
-            self._moment_buf = self.torch.empty(need, dtype=self.torch.float32, device="cuda:%d" % self.ctx.device)
+            self._moment_buf = _device_empty(self.ctx, need)
         out = self._moment_buf[:self.nchan_out * 14 * ndat].view(self.nchan_out, 1, 14 * ndat)
         self._op("FourthMoment", lambda: fourth_moment(self.ctx, rows, out, ndat))
         self._moment_rows = out
         return out
-
-    _moment_buf = None
 
     def _op(self, name, fn):
         """Operation::operate with record_time (Operation.C:90-113): wall time of the operation including its stream
@@ -1658,8 +1653,7 @@ class LoadToFold:
         state = _lib.STOKES if cfg.stokes else _lib.COHERENCE
         if "Detection" in self.dumps:                        # the filterbank's complex output: one extra pass, taps only
             if self._dump_cplx is None:
-                self._dump_cplx = self.torch.empty((self.nchan_out, 2, 2 * cfg.parts_per_block * self.nkeep),
-                                                   dtype=self.torch.float32, device="cuda:%d" % self.ctx.device)
+                self._dump_cplx = _device_empty(self.ctx, (self.nchan_out, 2, 2 * cfg.parts_per_block * self.nkeep))
             self.fb.perform_raw(raw, self.layout, self.scale8, self._dump_cplx, npart)
             self.dumps["Detection"].write(self._dump_cplx, ndat, 2)
         if self.sample_delay is not None:
@@ -1671,25 +1665,16 @@ class LoadToFold:
             # same order as the unfused chain below (blocks holding a sub-integration boundary take that chain).
             idat_start, ndat_fold, _division, complete = pieces[0]
             folded = self._set_plan(idat_start, ndat_fold)
-            if events is not None:
-                events[0].record()
-            self._op("Filterbank+Detection+Fold", lambda: self.fb.perform_fold(self.fold, npart, state, raw=raw, layout=self.layout,
-                                                                            scale=self.scale8))
-            if events is not None:
-                events[1].record()
-            self.integration_length += folded / self.out_rate
-            self.ndat_total += ndat_fold
+            self._filterbank_op("Filterbank+Detection+Fold", lambda: self.fb.perform_fold(self.fold, npart, state, raw=raw, layout=self.layout,
+                                                                                       scale=self.scale8), events)
+            _accumulate(self, folded, ndat_fold, self.out_rate)
             if complete:
                 self.finish_subint(*self._subint_comm)
             self.ndat_out += ndat
             self.nsamples_in += npart * self.nsamp_step
             return
-        if events is not None:          # HIP events bracketing the FFT+chirp launch group (bench.py roofline)
-            events[0].record()
-        self._op("Filterbank+Detection", lambda: self.fb.perform_detect(self.detected, npart, state, cfg.ndim, raw=raw,
-                                                                        layout=self.layout, scale=self.scale8))
-        if events is not None:
-            events[1].record()
+        self._filterbank_op("Filterbank+Detection", lambda: self.fb.perform_detect(self.detected, npart, state, cfg.ndim, raw=raw,
+                                                                                   layout=self.layout, scale=self.scale8), events)
         if "Fold" in self.dumps:
             if self.moments:
                 self.dumps["Fold"].write(self._moment_stream(self.detected, ndat), ndat, 14)
@@ -1706,18 +1691,12 @@ class LoadToFold:
 
     def _process_block_interchan(self, raw, npart, ndat, state, events):
         """-K chain: filterbank+detect -> SampleDelay (in place, LoadToFold1.C:617-618) -> fold."""
-        cfg, nd, head = self.cfg, self.cfg.ndim, self.sd_head
-        if events is not None:
-            events[0].record()
-        self._op("Filterbank+Detection", lambda: self.fb.perform_detect(self.detected[:, :, head * nd:], npart, state, nd, raw=raw,
-                                                                        layout=self.layout, scale=self.scale8))
-        if events is not None:
-            events[1].record()
-        off, nin = head - self.sd_carried, self.sd_carried + ndat
-        rows = self.detected[:, :, off * nd:(off + nin) * nd]
-        nuse = nin - self.sd_short              # (sub-band rank: the band's total delay, not just this rank's, is given up)
-        nout = self._op("SampleDelay", lambda: self.sample_delay.transform(rows[:, :, :nuse * nd].unflatten(2, (nuse, nd)))) \
-            if nuse > 0 else 0
+        nd, sd = self.cfg.ndim, self.sd
+        self._filterbank_op("Filterbank+Detection", lambda: self.fb.perform_detect(self.detected[:, :, sd.head * nd:], npart, state, nd, raw=raw,
+                                                                                   layout=self.layout, scale=self.scale8), events)
+        rows = sd.rows(self.detected, ndat, nd)     # (sub-band rank: the band's total delay, not just this rank's, is given up)
+        nuse = rows.shape[2] // nd
+        nout = self._op("SampleDelay", lambda: self.sample_delay.transform(rows.unflatten(2, (nuse, nd)))) if nuse else 0
         if nout and "Fold" in self.dumps:
             if self.moments:
                 self.dumps["Fold"].write(self._moment_stream(rows, nout), nout, 14)
@@ -1729,15 +1708,10 @@ class LoadToFold:
             for idat_start, ndat_fold, _division, complete in self._pieces(nout):
                 folded = self._set_plan(idat_start, ndat_fold)
                 self._op("Fold", lambda: self._fold_rows(rows))
-                self.integration_length += folded / self.out_rate
-                self.ndat_total += ndat_fold
+                _accumulate(self, folded, ndat_fold, self.out_rate)
                 if complete:
                     self.finish_subint(*self._subint_comm)
-        # InputBuffering::set_next_start(output_ndat): the unshifted tail goes in front of the next block
-        carry = nin - nout
-        if carry:
-            move_tail_fpt(self.ctx, self.detected, head - carry, off + nout, carry, nd)
-        self.sd_carried = carry
+        sd.keep_tail(self.ctx, self.detected, ndat, nout, nd)
         self.ndat_out += nout
         self.nsamples_in += npart * self.nsamp_step
 
@@ -1773,7 +1747,6 @@ class LoadToFold:
         return TurnsDivider(phase, iphase, pg, self.out_start, self.out_rate, cfg.subint_turns if turns is None else turns,
                             reference_phase, cfg.fractional_pulses)
 
-    _turns = None
     _subint_comm = (None, 0, 1, None)     # (dist, rank, world, gather_buffer[, replicas]) used at sub-integration dumps
 
     def set_communicator(self, dist, rank, world, gather_buffer=None, replicas=False):
@@ -1813,8 +1786,7 @@ class LoadToFold:
         if group:
             self._op("Fold", lambda: FoldEngine.fold_many([p.fold for p, _ in group], rows))
         for (p, (_, ndat_fold, _division, complete)), n in zip(group, folded):
-            p.integration_length += n / self.out_rate
-            p.ndat_total += ndat_fold
+            _accumulate(p, n, ndat_fold, self.out_rate)
             if complete:
                 self._finish_pulsar_subint(p)
         for p, pc in zip(self.pulsars, pieces):
@@ -1823,26 +1795,19 @@ class LoadToFold:
             for idat_start, ndat_fold, _division, complete in pc:
                 n = self._set_plan(idat_start, ndat_fold, p)
                 self._op("Fold", lambda: p.fold.fold(rows))
-                p.integration_length += n / self.out_rate
-                p.ndat_total += ndat_fold
+                _accumulate(p, n, ndat_fold, self.out_rate)
                 if complete:
                     self._finish_pulsar_subint(p)
 
     def _finish_pulsar_subint(self, p):
         """Subint<Fold> of one pulsar of a multi-target run: emit its sub-integration and zero its profile."""
-        p.subints.append({"hits": p.hits.copy(), "integration_length": p.integration_length, "ndat_total": p.ndat_total,
-                          "profile_dev": self.profiles_tensor(p).clone()})
-        p.fold.zero()
-        p.hits[:] = 0
-        p.integration_length = 0.0
-        p.ndat_total = 0
+        _emit(p, _books(p, profile_dev=self.profiles_tensor(p).clone()), p.fold.zero)
 
     def _fold_piece(self, idat_start, ndat_fold):
         """Fold::fold (Fold.C:650-657,718-803) on detected[idat_start : idat_start+ndat_fold]."""
         folded = self._set_plan(idat_start, ndat_fold)
         self._op("Fold", lambda: self._fold_rows(self.detected))                 # (no head room without -K)
-        self.integration_length += folded / self.out_rate
-        self.ndat_total += ndat_fold
+        _accumulate(self, folded, ndat_fold, self.out_rate)
 
     def profiles_tensor(self, pulsar=None):
         """Zero-copy torch view of the device-resident PhaseSeries (Fold::Engine::get_profiles); `pulsar`: one of a multi-target run."""
@@ -1857,7 +1822,7 @@ class LoadToFold:
         h = _Holder()
         h.__cuda_array_interface__ = {"shape": (n,), "typestr": "<f4", "data": (int(ptr), False), "version": 2,
                                       "strides": None}
-        return torch.as_tensor(h, device="cuda:%d" % self.ctx.device)
+        return torch.as_tensor(h, device=_device(self.ctx))
 
     comm = None                 # dspsr_amd.Communicator (RCCL behind the C-ABI): the product's exchange
     _comm_pending = None
@@ -1918,30 +1883,22 @@ class LoadToFold:
                             self.hits, self.integration_length, self.ndat_total, root=0,
                             check_hits=check_hits and not replicas)
             self._comm_pending = bool(check_hits and not replicas)
-            self.fold.zero()                                            # stream ordered behind the snapshot
-            self.hits[:] = 0
-            self.integration_length = 0.0
-            self.ndat_total = 0
+            _emit(self, None, self.fold.zero)                           # (the zero is stream ordered behind the snapshot)
             if wait:
                 self.collect_subint()
             return
-        prof = self.profiles_tensor()
+        prof, entry = self.profiles_tensor(), None
         if replicas:
             res = reduce_replicas(prof, self.hits, self.integration_length, self.ndat_total, dist, rank, world)
             if rank == 0:
-                self.subints.append({"hits": res[1].copy(), "integration_length": res[2], "ndat_total": res[3],
-                                     "profile_dev": res[0].clone()})
+                entry = {"hits": res[1].copy(), "integration_length": res[2], "ndat_total": res[3], "profile_dev": res[0].clone()}
         else:
             if check_hits:
                 check_identical_hits(self.hits, dist, rank, world)
             result = reduce_subbands(prof, dist, rank, world, gather_buffer)
             if rank == 0:
-                self.subints.append({"hits": self.hits.copy(), "integration_length": self.integration_length,
-                                     "ndat_total": self.ndat_total, "profile_dev": result.clone()})
-        self.fold.zero()
-        self.hits[:] = 0
-        self.integration_length = 0.0
-        self.ndat_total = 0
+                entry = _books(self, profile_dev=result.clone())
+        _emit(self, entry, self.fold.zero)
 
     def process_host_blocks(self, blocks, npart=None):
         """Host hand-over (the role of dsp::TransferCUDA / TransferBitSeriesCUDA, Signal/General/TransferCUDA.C:24-85):
@@ -1979,7 +1936,7 @@ class LoadToFold:
                 if bufs[k] is None or bufs[k].numel() < host.numel():
                     if bufs[k] is not None:
                         bufs[k].record_stream(main)          # still being read by kernels on the main stream
-                    bufs[k] = torch.empty(host.numel(), dtype=torch.int8, device="cuda:%d" % self.ctx.device)
+                    bufs[k] = _device_empty(self.ctx, host.numel(), "int8")
                     bufs[k].record_stream(main)
                 elif used[k]:
                     copy.wait_event(done[k])                 # the kernels that read this buffer have finished
@@ -2011,22 +1968,14 @@ class LoadToFold:
         self.ctx.synchronize()
 
     def close(self):
+        """Release everything opened, the context last; also on an instance whose construction stopped half-way, and once only."""
+        if self._closed:
+            return
+        self._closed = True
         if self._comm_pending is not None:
             self.collect_subint()
-        for d in self.dumps.values():
-            d.close()
-        if self.sample_delay is not None:
-            self.sample_delay.close()
-        self.fb.close()
-        if self.fold is not None:
-            self.fold.close()
-        if self.cyclic is not None:
-            self.cyclic.close()
-        if self.plfb is not None:
-            self.plfb.close()
-        for p in self.pulsars:
-            p.fold.close()
-        self.ctx.close()
+        _close_all(*self.dumps.values(), self.sample_delay, self.fb, self.fold, self.cyclic, self.plfb, *(p.fold for p in self.pulsars),
+                   self.ctx)
 
 
 # ---- search mode: digifil (Signal/General/LoadToFil.C) ------------------------------------------------------------
@@ -2094,40 +2043,97 @@ def write_sigproc_header(f, *, source_name="unknown", rawdatafile="unknown", mac
     send_string("HEADER_END")
 
 
+def _sigproc_header_values(drv, nchan, tsamp, start_seconds, nifs):
+    """fch1/foff/tsamp/tstart as SigProcObservation::unload derives them from the digitizer's output observation
+    (bandwidth forced negative, SigProcDigitizer.C:83-85; channel 0 centred half a channel inside the band edge)."""
+    info, bw = drv.info, -abs(drv.info.bandwidth)
+    fch1 = info.centre_frequency - 0.5 * bw + 0.5 * bw / nchan
+    nbits = 32 if drv.cfg.nbit == -32 else drv.cfg.nbit
+    return dict(fch1=fch1, foff=bw / nchan, nchans=nchan, nbits=nbits, tsamp=tsamp,
+                tstart_mjd=info.mjd_day + (info.mjd_sec + start_seconds) / 86400.0, nifs=nifs)
+
+
+def _digitize_fpt(drv, scr):
+    """[Rescale] -> SigProcDigitizer of the scrunched FPT rows of one block (LoadToFil.C:306-362): the packed bytes
+    [time][pol][chan] of its output samples."""
+    cfg, nout = drv.cfg, scr.shape[2]
+    packed = drv.packed[:nout * drv.bytes_per_sample]
+    flip = drv.info.bandwidth > 0
+    if nout:
+        if drv.rescale is not None and cfg.nbit != -32:
+            drv.rescale.digitize_fpt(scr, packed, cfg.nbit, cfg.scale_fac, flip_band=flip)        # Rescale + digitiser, one pass
+        else:
+            if drv.rescale is not None:
+                drv.rescale.transform_fpt(scr)                                                     # in place, LoadToFil.C:312-313
+            sigproc_digitize_fpt(drv.ctx, scr, packed, cfg.nbit, use_digi_scales=drv.rescale is not None,
+                                 input_scale=1.0 if drv.rescale is not None else drv.input_scale, scale_fac=cfg.scale_fac,
+                                 flip_band=flip)
+    drv.ndat_out += nout
+    return packed
+
+
+def _delay_scrunch(drv, det, nd):
+    """[SampleDelay, in place (LoadToFil.C:240-241)] -> [FScrunch] -> TScrunch behind the detection of a search driver: `det`, the
+    `nd` new samples behind the head room of drv.detected; returns the scrunched rows [nchan_out][npol][nout] (a view)."""
+    cfg, nnew = drv.cfg, nd
+    if drv.sample_delay is not None:
+        det = drv.sd.rows(drv.detected, nnew)
+        nd = drv.sample_delay.transform(det) if det.shape[2] else 0
+        det = det[:, :, :nd]
+    nout = 0
+    if nd:
+        if cfg.fscrunch:
+            det = fscrunch_fpt(drv.ctx, det, drv.fscr[:, :, :nd], cfg.fscrunch)
+        nout, drv.carry_count = tscrunch_fpt(drv.ctx, det, drv.scrunched, drv.ts, drv.carry, drv.carry_count)
+    if drv.sample_delay is not None:
+        drv.sd.keep_tail(drv.ctx, drv.detected, nnew, nd)
+    return drv.scrunched[:, :, :nout]
+
+
+def _rescale_interval(cfg, out_rate):
+    """Rescale::init (Rescale.C:102-103): samples per interval of -I, 0 without Rescale"""
+    if not cfg.rescale_seconds:
+        return 0
+    interval = int(cfg.rescale_seconds * out_rate)
+    if not interval:
+        raise DspsrAmdError("dsp::Rescale::init nsample == 0")
+    return interval
+
+
 class LoadToFil:
     """digifil's chain for 8-bit real dual-polarisation input and one output polarisation, every stage on the device
     (LoadToFil.C:196-362): TFPFilterbank (PPQQ) + TScrunch [one kernel] -> Rescale (per pol and channel, in place)
     -> PScrunch -> SigProcDigitizer.  process_block returns the packed block (device uint8, [time][chan] n-bit)."""
 
     fused_output = True          # Rescale + PScrunch + digitiser as one pass (False: the three operations one after the other)
+    ctx = rescale = None
+    _closed = False
 
     def __init__(self, cfg: SearchConfig, info: InputInfo, device: int = 0, stream: int | None = None):
-        import torch
-        self.torch = torch
         self.cfg, self.info = cfg, info
         if info.npol != 2 or info.ndim != 1 or info.nchan != 1:
             raise DspsrAmdError("dspsr_amd.LoadToFil: 8-bit real dual-polarisation single-channel input only")
         if cfg.parts_per_block % cfg.tscrunch:
             raise DspsrAmdError("dspsr_amd.LoadToFil: parts_per_block=%d is not a multiple of tscrunch=%d"
                                 % (cfg.parts_per_block, cfg.tscrunch))
-        self.ctx = Context(device, stream)
         self.scale8 = eight_bit_scale()
         self.layout = _lib.RAW_CASPSR if info.machine == "CASPSR" else _lib.RAW_GENERIC
         self.out_rate = info.rate / (2.0 * cfg.nchan) / cfg.tscrunch           # TFPFilterbank + TScrunch
-        nout = cfg.parts_per_block // cfg.tscrunch
-        dev = "cuda:%d" % device
-        self.detected = torch.empty((nout, cfg.nchan, 2), dtype=torch.float32, device=dev)      # PPQQ, TFP order
-        self.intensity = torch.empty((nout, cfg.nchan, 1), dtype=torch.float32, device=dev)
-        self.rescale = None
-        if cfg.rescale_seconds:
-            interval = int(cfg.rescale_seconds * self.out_rate)                   # Rescale::init, Rescale.C:102-103
-            if not interval:
-                raise DspsrAmdError("dsp::Rescale::init nsample == 0")
-            self.rescale = Rescale(self.ctx, cfg.nchan, 2, interval, cfg.rescale_constant)
         nbits = 32 if cfg.nbit == -32 else cfg.nbit
         self.bytes_per_sample = cfg.nchan * nbits // 8
-        self.packed = torch.empty(nout * self.bytes_per_sample, dtype=torch.uint8, device=dev)
         self.ndat_out = 0
+        interval = _rescale_interval(cfg, self.out_rate)
+        try:
+            self.ctx = Context(device, stream)
+            nout = cfg.parts_per_block // cfg.tscrunch
+            self.detected = _device_empty(self.ctx, (nout, cfg.nchan, 2))      # PPQQ, TFP order
+            self.intensity = _device_empty(self.ctx, (nout, cfg.nchan, 1))
+            if interval:
+                self.rescale = Rescale(self.ctx, cfg.nchan, 2, interval, cfg.rescale_constant)
+            self.packed = _device_empty(self.ctx, nout * self.bytes_per_sample, "uint8")
+        except BaseException:
+            self.close()
+            raise
 
     def block_bytes(self, npart=None):
         return (npart or self.cfg.parts_per_block) * 2 * self.cfg.nchan * 2
@@ -2161,21 +2167,15 @@ class LoadToFil:
         return packed
 
     def header_values(self):
-        """fch1/foff/tsamp/tstart as SigProcObservation::unload derives them from the digitizer's output observation
-        (bandwidth forced negative, SigProcDigitizer.C:83-85; channel 0 centred half a channel inside the band edge)."""
-        nchan, bw = self.cfg.nchan, -abs(self.info.bandwidth)
-        fch1 = self.info.centre_frequency - 0.5 * bw + 0.5 * bw / nchan
-        nbits = 32 if self.cfg.nbit == -32 else self.cfg.nbit
-        return dict(fch1=fch1, foff=bw / nchan, nchans=nchan, nbits=nbits, tsamp=1.0 / self.out_rate,
-                    tstart_mjd=self.info.mjd_day + (self.info.mjd_sec + self.info.start_seconds) / 86400.0, nifs=1)
+        return _sigproc_header_values(self, self.cfg.nchan, 1.0 / self.out_rate, self.info.start_seconds, 1)
 
     def synchronize(self):
         self.ctx.synchronize()
 
     def close(self):
-        if self.rescale is not None:
-            self.rescale.close()
-        self.ctx.close()
+        if not self._closed:
+            self._closed = True
+            _close_all(self.rescale, self.ctx)
 
 
 class LoadToFilCoherent:
@@ -2186,9 +2186,20 @@ class LoadToFilCoherent:
     output rate.  process_block(raw) takes the 8-bit block of LoadToFold (npart * nsamp_step + nsamp_overlap samples, the overlap
     re-presented by the caller) and returns the packed bytes [time][pol][chan] of the output samples completed by it."""
 
+    sd_head, sd_carried = _carry_view("head"), _carry_view("carried")
+    ctx = fb = rescale = sample_delay = None
+    _closed = False
+
     def __init__(self, cfg: SearchConfig, info: InputInfo, device: int = 0, stream: int | None = None):
-        import torch
-        self.torch = torch
+        delays = self._plan(cfg, info)                       # every refusal that needs no device comes from here
+        try:
+            self._open(device, stream, delays)
+        except BaseException:
+            self.close()
+            raise
+
+    def _plan(self, cfg, info):
+        """The host side of the constructor: checks and geometry.  Returns the -K delays per channel (None without -K)."""
         self.cfg, self.info = cfg, info
         if cfg.npol not in (1, 2, 4):
             raise DspsrAmdError("dspsr_amd.LoadToFilCoherent: npol=%d (Intensity 1 / PPQQ 2 / Coherence 4 are built; NthPower 3 is not)" % cfg.npol)
@@ -2199,82 +2210,67 @@ class LoadToFilCoherent:
         if cfg.dispersion_measure == 0.0 and not cfg.freq_res and cfg.npol <= 2:
             raise DspsrAmdError("dspsr_amd.LoadToFilCoherent: -F N:D with a dispersion measure, -F N -x M, or -d 4 (with none of them "
                                 "digifil takes the TFPFilterbank: dspsr_amd.LoadToFil)")
-        self.ctx = Context(device, stream)
-        nsub = cfg.nchan // info.nchan
         if cfg.dispersion_measure != 0.0:
-            r = Dedispersion(info.centre_frequency, info.bandwidth, cfg.dispersion_measure, input_nchan=info.nchan, ndim=info.ndim)
-            if cfg.freq_res:
-                r.set_frequency_resolution(cfg.freq_res)                               # LoadToFil.C:190-191
-            r.match(cfg.nchan)
-            kernel = r.kernel
+            r = matched_response(info, cfg.dispersion_measure, cfg.freq_res, cfg.nchan, input_nchan=info.nchan, ndim=info.ndim)   # LoadToFil.C:190-191
         else:
             # -F N -x M without :D (LoadToFil.C:199-216): the convolving filterbank with no response -- nothing is discarded
             # (Filterbank.C:139-155: freq_res as set, nfilt 0)
             # -F N -d 4 with neither (LoadToFil.C:205-207: `npol > 2` takes the Filterbank too): its default freq_res = 1, the
             # non-convolving filterbank (Filterbank.C:614-623)
             from types import SimpleNamespace
-            r, kernel = SimpleNamespace(ndat=cfg.freq_res or 1, impulse_pos=0, impulse_neg=0, kernel=None), None
+            r = SimpleNamespace(ndat=cfg.freq_res or 1, impulse_pos=0, impulse_neg=0, kernel=None)
         self.response = r
-        self.fb = FilterbankEngine(self.ctx).setup(nsub, r.ndat, r.impulse_pos, r.impulse_neg, info.nchan, info.npol, info.ndim == 1,
-                                                   kernel, max_parts=cfg.max_parts)
-        self.nkeep, self.nsamp_step, self.nsamp_overlap = self.fb.nkeep, self.fb.nsamp_step, self.fb.nsamp_overlap
-        n_fft = nsub * r.ndat
-        nsamp_fft = 2 * n_fft if info.ndim == 1 else n_fft
-        self.fb_rate = info.rate * (float(r.ndat) / float(nsamp_fft))
-        ts = max(1, cfg.tscrunch)
+        # Filterbank.C:124-128 leaves scale = n_fft * freq_res on its output; FScrunch / TScrunch multiply it by their factors
+        # (TimeSeries::rescale, TScrunch.C:126, FScrunch.C:103); without Rescale the digitiser divides by it (SigProcDigitizer.C:158)
+        self.fb_rate, self.out_start, scale = filterbank_output(info, r, cfg.nchan // info.nchan)
+        self.ts = ts = max(1, cfg.tscrunch)
         self.out_rate = self.fb_rate / ts
-        self.out_start = info.start_seconds + r.impulse_pos / self.fb_rate
-        self.scale8 = eight_bit_scale()
-        self.layout = _lib.RAW_CASPSR if info.machine == "CASPSR" else _lib.RAW_GENERIC
+        self.input_scale = scale * ts * (cfg.fscrunch or 1)
         self.state = {1: _lib.INTENSITY, 2: _lib.PPQQ, 4: _lib.COHERENCE}[cfg.npol]
         self.nchan_out = cfg.nchan // cfg.fscrunch if cfg.fscrunch else cfg.nchan
         if cfg.fscrunch and cfg.nchan % cfg.fscrunch:
             raise DspsrAmdError("dspsr_amd.LoadToFilCoherent: nchan=%d is not a multiple of fscrunch=%d" % (cfg.nchan, cfg.fscrunch))
-        dev = "cuda:%d" % device
-        nmax = (ts - 1 + cfg.parts_per_block * self.nkeep) // ts
+        self.rescale_interval = _rescale_interval(cfg, self.out_rate)
         # -K: dsp::SampleDelay sits between the filterbank and Detection (LoadToFil.C:236-247).  Detection acts sample by sample,
         # so delaying the detected rows gives the reference's numbers; the last total_delay samples of a block are re-presented in
         # front of the next one (InputBuffering, SampleDelay.C:117,146): they live in the head room in front of `detected`.
-        self.sample_delay, self.sd_carried, head = None, 0, 0
+        delays, self.sd = None, DelayCarry()
         if cfg.dedisperse:
             dual = info.ndim == 2                              # Observation.C:80-87; Filterbank.C:358-364
             delays = dedispersion_sample_delays(info.centre_frequency, info.bandwidth, cfg.dispersion_measure, cfg.nchan,
                                                 self.fb_rate, swap=dual and info.nchan == 1,
                                                 nsub_swap=info.nchan if dual and info.nchan > 1 else 0)
-            self.sample_delay = SampleDelay(self.ctx, delays, cfg.npol)
-            head = self.sample_delay.total_delay
-            if head > cfg.parts_per_block * self.nkeep:
-                raise DspsrAmdError("dspsr_amd.LoadToFilCoherent: inter-channel delay of %d samples exceeds the block of %d"
-                                    % (head, cfg.parts_per_block * self.nkeep))
-            self.out_start += self.sample_delay.zero_delay / self.fb_rate               # SampleDelay.C:159
-        self.sd_head = head
+            self.sd = DelayCarry(delays)
+            self.out_start += self.sd.zero / self.fb_rate                               # SampleDelay.C:159
         # FScrunch sits between Detection and TScrunch (LoadToFil.C:286-304) and SampleDelay in front of Detection: the fused launch
         # group holds neither, nor the four Coherence products, so with -f, -K or -d 4 the operations run one after the other
         # (perform_search at tscrunch 1 = filterbank + detection; Coherence: perform_detect with ndim 1)
         self.fused = cfg.fused and not cfg.fscrunch and not cfg.dedisperse and cfg.npol != 4
-        nmax = (ts - 1 + head + cfg.parts_per_block * self.nkeep) // ts
-        self.scrunched = torch.empty((self.nchan_out, cfg.npol, max(1, nmax)), dtype=torch.float32, device=dev)
-        self.carry = torch.zeros((self.nchan_out, cfg.npol), dtype=torch.float32, device=dev)
-        self.carry_count = 0
-        self.detected = None
-        if not self.fused:
-            nd = head + cfg.parts_per_block * self.nkeep
-            self.detected = torch.empty((cfg.nchan, cfg.npol, nd), dtype=torch.float32, device=dev)
-            self.det_carry = torch.zeros((cfg.nchan, cfg.npol), dtype=torch.float32, device=dev)
-            self.fscr = torch.empty((self.nchan_out, cfg.npol, nd), dtype=torch.float32, device=dev) if cfg.fscrunch else None
-        self.rescale = None
-        if cfg.rescale_seconds:
-            interval = int(cfg.rescale_seconds * self.out_rate)                          # Rescale::init, Rescale.C:102-103
-            if not interval:
-                raise DspsrAmdError("dsp::Rescale::init nsample == 0")
-            self.rescale = Rescale(self.ctx, self.nchan_out, cfg.npol, interval, cfg.rescale_constant)
         nbits = 32 if cfg.nbit == -32 else cfg.nbit
         self.bytes_per_sample = self.nchan_out * cfg.npol * nbits // 8
-        self.packed = torch.empty(max(1, nmax) * self.bytes_per_sample, dtype=torch.uint8, device=dev)
-        self.ndat_out = 0
-        # Filterbank.C:124-128 leaves scale = n_fft * freq_res on its output; FScrunch / TScrunch multiply it by their factors
-        # (TimeSeries::rescale, TScrunch.C:126, FScrunch.C:103); without Rescale the digitiser divides by it (SigProcDigitizer.C:158)
-        self.input_scale = float(n_fft) * float(r.ndat) * ts * (cfg.fscrunch or 1)
+        self.carry_count = self.ndat_out = 0
+        return delays
+
+    def _open(self, device, stream, delays):
+        cfg, info, r, ts = self.cfg, self.info, self.response, self.ts
+        self.ctx = Context(device, stream)
+        _open_convolving_front(self, r, cfg.nchan // info.nchan, info.nchan, r.kernel, max_parts=cfg.max_parts)
+        block = cfg.parts_per_block * self.nkeep
+        if delays is not None:
+            self.sample_delay = SampleDelay(self.ctx, delays, cfg.npol)
+            self.sd.check_block("LoadToFilCoherent", block)       # (the block is known with the engine's nkeep)
+        nmax = max(1, (ts - 1 + self.sd.head + block) // ts)
+        self.scrunched = _device_empty(self.ctx, (self.nchan_out, cfg.npol, nmax))
+        self.carry = _device_empty(self.ctx, (self.nchan_out, cfg.npol), zero=True)
+        self.detected = None
+        if not self.fused:
+            nd = self.sd.head + block
+            self.detected = _device_empty(self.ctx, (cfg.nchan, cfg.npol, nd))
+            self.det_carry = _device_empty(self.ctx, (cfg.nchan, cfg.npol), zero=True)
+            self.fscr = _device_empty(self.ctx, (self.nchan_out, cfg.npol, nd)) if cfg.fscrunch else None
+        if self.rescale_interval:
+            self.rescale = Rescale(self.ctx, self.nchan_out, cfg.npol, self.rescale_interval, cfg.rescale_constant)
+        self.packed = _device_empty(self.ctx, nmax * self.bytes_per_sample, "uint8")
 
     def block_bytes(self, npart=None):
         npart = npart or self.cfg.parts_per_block
@@ -2285,72 +2281,35 @@ class LoadToFilCoherent:
 
     def detect_scrunch(self, raw, npart=None):
         """Filterbank -> Detection -> [FScrunch] -> TScrunch of one block: the scrunched rows [nchan_out][npol][nout] (a view)."""
-        cfg = self.cfg
+        cfg, ts = self.cfg, self.ts
         npart = npart or cfg.parts_per_block
         if raw.numel() < self.block_bytes(npart):
             raise DspsrAmdError("dspsr_amd.LoadToFilCoherent.process_block: block holds %d bytes, %d needed" % (raw.numel(), self.block_bytes(npart)))
-        ts = max(1, cfg.tscrunch)
         if self.fused:
             nout, self.carry_count = self.fb.perform_search(self.scrunched, self.carry, self.carry_count, npart, ts, self.state, raw=raw,
                                                             layout=self.layout, scale=self.scale8)
             return self.scrunched[:, :, :nout]
-        nd, head = npart * self.nkeep, self.sd_head
+        nd, head = npart * self.nkeep, self.sd.head
         det = self.detected[:, :, head:head + nd]
         if cfg.npol == 4:
             self.fb.perform_detect(det, npart, self.state, 1, raw=raw, layout=self.layout, scale=self.scale8)
         else:
             self.fb.perform_search(det, self.det_carry, 0, npart, 1, self.state, raw=raw, layout=self.layout, scale=self.scale8)
-        rows = carry = None
-        if self.sample_delay is not None:
-            off, nin = head - self.sd_carried, self.sd_carried + nd
-            rows = self.detected[:, :, off:off + nin]
-            nd = self.sample_delay.transform(rows)                                   # in place (LoadToFil.C:240-241)
-            carry = nin - nd                 # InputBuffering::set_next_start: the unshifted tail goes in front of the next block
-            det = rows[:, :, :nd]
-        nout = 0
-        if nd:
-            if cfg.fscrunch:
-                det = fscrunch_fpt(self.ctx, det, self.fscr[:, :, :nd], cfg.fscrunch)
-            nout, self.carry_count = tscrunch_fpt(self.ctx, det, self.scrunched, ts, self.carry, self.carry_count)
-        if rows is not None:
-            if carry:
-                move_tail_fpt(self.ctx, self.detected, head - carry, off + nd, carry)
-            self.sd_carried = carry
-        return self.scrunched[:, :, :nout]
+        return _delay_scrunch(self, det, nd)
 
     def process_block(self, raw, npart=None):
-        cfg = self.cfg
-        scr = self.detect_scrunch(raw, npart)
-        nout = scr.shape[2]
-        packed = self.packed[:nout * self.bytes_per_sample]
-        flip = self.info.bandwidth > 0
-        if nout:
-            if self.rescale is not None and cfg.nbit != -32:
-                self.rescale.digitize_fpt(scr, packed, cfg.nbit, cfg.scale_fac, flip_band=flip)        # Rescale + digitiser, one pass
-            else:
-                if self.rescale is not None:
-                    self.rescale.transform_fpt(scr)                                                     # in place, LoadToFil.C:312-313
-                sigproc_digitize_fpt(self.ctx, scr, packed, cfg.nbit, use_digi_scales=self.rescale is not None,
-                                     input_scale=1.0 if self.rescale is not None else self.input_scale, scale_fac=cfg.scale_fac,
-                                     flip_band=flip)
-        self.ndat_out += nout
-        return packed
+        return _digitize_fpt(self, self.detect_scrunch(raw, npart))
 
     def header_values(self):
-        nchan, bw = self.nchan_out, -abs(self.info.bandwidth)
-        fch1 = self.info.centre_frequency - 0.5 * bw + 0.5 * bw / nchan
-        nbits = 32 if self.cfg.nbit == -32 else self.cfg.nbit
-        return dict(fch1=fch1, foff=bw / nchan, nchans=nchan, nbits=nbits, tsamp=1.0 / self.out_rate,
-                    tstart_mjd=self.info.mjd_day + (self.info.mjd_sec + self.out_start) / 86400.0, nifs=self.cfg.npol)
+        return _sigproc_header_values(self, self.nchan_out, 1.0 / self.out_rate, self.out_start, self.cfg.npol)
 
     def synchronize(self):
         self.ctx.synchronize()
 
     def close(self):
-        if self.rescale is not None:
-            self.rescale.close()
-        self.fb.close()
-        self.ctx.close()
+        if not self._closed:
+            self._closed = True
+            _close_all(self.rescale, self.sample_delay, self.fb, self.ctx)
 
 
 class LoadToFilDirect:
@@ -2366,30 +2325,34 @@ class LoadToFilDirect:
     process_block(raw, ndat) takes the block of ndat time samples in DADA order [ndat][nchan][npol][2] int8 (any ndat up to
     parts_per_block, 0 included) and returns the packed bytes [time][pol][chan] of the output samples it completes."""
 
+    sd_head, sd_carried = _carry_view("head"), _carry_view("carried")
+    ctx = rescale = sample_delay = None
+    _closed = False
+
     def __init__(self, cfg: SearchConfig, info: InputInfo, device: int = 0, stream: int | None = None):
-        import torch
-        self.torch = torch
         delays = self._plan(cfg, info)                       # every refusal comes from here, before a device is touched
+        try:
+            self._open(device, stream, delays)
+        except BaseException:
+            self.close()
+            raise
+
+    def _open(self, device, stream, delays):
+        cfg, info, ts, head, nmax_in = self.cfg, self.info, self.ts, self.sd.head, self.cfg.parts_per_block
         self.ctx = Context(device, stream)
-        dev = "cuda:%d" % device
-        ts, head, nmax_in = self.ts, self.sd_head, cfg.parts_per_block
-        self.sample_delay, self.sd_carried = None, 0
         if delays is not None:
             self.sample_delay = SampleDelay(self.ctx, delays, cfg.npol)
         nmax = max(1, (ts - 1 + head + nmax_in) // ts)
-        self.scrunched = torch.empty((self.nchan_out, cfg.npol, nmax), dtype=torch.float32, device=dev)
-        self.carry = torch.zeros((self.nchan_out, cfg.npol), dtype=torch.float32, device=dev)
-        self.carry_count = 0
+        self.scrunched = _device_empty(self.ctx, (self.nchan_out, cfg.npol, nmax))
+        self.carry = _device_empty(self.ctx, (self.nchan_out, cfg.npol), zero=True)
         self.detected = self.fscr = None
         if not self.fused:
             nd = head + nmax_in
-            self.detected = torch.empty((info.nchan, cfg.npol, nd), dtype=torch.float32, device=dev)
-            self.fscr = torch.empty((self.nchan_out, cfg.npol, nd), dtype=torch.float32, device=dev) if cfg.fscrunch else None
-        self.rescale = None
+            self.detected = _device_empty(self.ctx, (info.nchan, cfg.npol, nd))
+            self.fscr = _device_empty(self.ctx, (self.nchan_out, cfg.npol, nd)) if cfg.fscrunch else None
         if self.rescale_interval:
             self.rescale = Rescale(self.ctx, self.nchan_out, cfg.npol, self.rescale_interval, cfg.rescale_constant)
-        self.packed = torch.empty(nmax * self.bytes_per_sample, dtype=torch.uint8, device=dev)
-        self.ndat_out = 0
+        self.packed = _device_empty(self.ctx, nmax * self.bytes_per_sample, "uint8")
 
     def _plan(self, cfg, info):
         """The host side of the constructor: checks and geometry.  Returns the -K delays per channel (None without -K)."""
@@ -2416,28 +2379,22 @@ class LoadToFilDirect:
         self.out_start = info.start_seconds
         self.scale8 = eight_bit_scale()
         self.state = {1: _lib.INTENSITY, 2: _lib.PPQQ, 4: _lib.COHERENCE}[cfg.npol]
-        delays, self.sd_head = None, 0
+        delays, self.sd = None, DelayCarry()
         if cfg.dedisperse:
             # the input comes from a file, not from a filterbank: no swapped halves (Observation.C:420-451)
             delays = dedispersion_sample_delays(info.centre_frequency, info.bandwidth, cfg.dispersion_measure, info.nchan, info.rate,
                                                 swap=False, nsub_swap=0)
-            zero = int(delays.max())
-            self.sd_head = int((zero - delays).max())                                    # SampleDelay.C:75-99: total_delay
-            if self.sd_head > cfg.parts_per_block:
-                raise DspsrAmdError("dspsr_amd.LoadToFilDirect: inter-channel delay of %d samples exceeds the block of %d"
-                                    % (self.sd_head, cfg.parts_per_block))
-            self.out_start += zero / info.rate                                           # SampleDelay.C:159
-        self.rescale_interval = 0
-        if cfg.rescale_seconds:
-            self.rescale_interval = int(cfg.rescale_seconds * self.out_rate)             # Rescale::init, Rescale.C:102-103
-            if not self.rescale_interval:
-                raise DspsrAmdError("dsp::Rescale::init nsample == 0")
+            self.sd = DelayCarry(delays)
+            self.sd.check_block("LoadToFilDirect", cfg.parts_per_block)
+            self.out_start += self.sd.zero / info.rate                                   # SampleDelay.C:159
+        self.rescale_interval = _rescale_interval(cfg, self.out_rate)
         # FScrunch sits between Detection and TScrunch, SampleDelay in front of Detection: the one-pass form holds neither
         self.fused = not cfg.fscrunch and not cfg.dedisperse
         nbits = 32 if cfg.nbit == -32 else cfg.nbit
         self.bytes_per_sample = self.nchan_out * cfg.npol * nbits // 8
         # no filterbank factor here: FScrunch / TScrunch multiply the scale by their factors (TScrunch.C:126, FScrunch.C:103)
         self.input_scale = float(ts * (cfg.fscrunch or 1))
+        self.carry_count = self.ndat_out = 0
         return delays
 
     def block_bytes(self, ndat=None):
@@ -2456,58 +2413,20 @@ class LoadToFilDirect:
             nout, self.carry_count = detect_raw(self.ctx, raw, self.scrunched, self.carry, self.carry_count, info.nchan, info.npol, self.ts,
                                                 self.state, self.scale8, ndat=ndat)
             return self.scrunched[:, :, :nout]
-        nd, head = ndat, self.sd_head
-        det = self.detected[:, :, head:head + nd]
+        det = self.detected[:, :, self.sd.head:self.sd.head + ndat]
         detect_raw(self.ctx, raw, det, None, None, info.nchan, info.npol, 1, self.state, self.scale8, ndat=ndat)
-        rows = carry = None
-        if self.sample_delay is not None:
-            off, nin = head - self.sd_carried, self.sd_carried + nd
-            rows = self.detected[:, :, off:off + nin]
-            nd = self.sample_delay.transform(rows) if nin else 0                     # in place (LoadToFil.C:240-241)
-            carry = nin - nd                 # InputBuffering::set_next_start: the unshifted tail goes in front of the next block
-            det = rows[:, :, :nd]
-        nout = 0
-        if nd:
-            if cfg.fscrunch:
-                det = fscrunch_fpt(self.ctx, det, self.fscr[:, :, :nd], cfg.fscrunch)
-            nout, self.carry_count = tscrunch_fpt(self.ctx, det, self.scrunched, self.ts, self.carry, self.carry_count)
-        if rows is not None:
-            if carry and off + nd != head - carry:
-                move_tail_fpt(self.ctx, self.detected, head - carry, off + nd, carry)
-            self.sd_carried = carry
-        return self.scrunched[:, :, :nout]
+        return _delay_scrunch(self, det, ndat)
 
     def process_block(self, raw, ndat=None):
-        cfg = self.cfg
-        scr = self.detect_scrunch(raw, ndat)
-        nout = scr.shape[2]
-        packed = self.packed[:nout * self.bytes_per_sample]
-        flip = self.info.bandwidth > 0
-        if nout:
-            if self.rescale is not None and cfg.nbit != -32:
-                self.rescale.digitize_fpt(scr, packed, cfg.nbit, cfg.scale_fac, flip_band=flip)        # Rescale + digitiser, one pass
-            else:
-                if self.rescale is not None:
-                    self.rescale.transform_fpt(scr)                                                     # in place, LoadToFil.C:312-313
-                sigproc_digitize_fpt(self.ctx, scr, packed, cfg.nbit, use_digi_scales=self.rescale is not None,
-                                     input_scale=1.0 if self.rescale is not None else self.input_scale, scale_fac=cfg.scale_fac,
-                                     flip_band=flip)
-        self.ndat_out += nout
-        return packed
+        return _digitize_fpt(self, self.detect_scrunch(raw, ndat))
 
     def header_values(self):
-        nchan, bw = self.nchan_out, -abs(self.info.bandwidth)
-        fch1 = self.info.centre_frequency - 0.5 * bw + 0.5 * bw / nchan
-        nbits = 32 if self.cfg.nbit == -32 else self.cfg.nbit
-        return dict(fch1=fch1, foff=bw / nchan, nchans=nchan, nbits=nbits, tsamp=self.ts / self.info.rate,
-                    tstart_mjd=self.info.mjd_day + (self.info.mjd_sec + self.out_start) / 86400.0, nifs=self.cfg.npol)
+        return _sigproc_header_values(self, self.nchan_out, self.ts / self.info.rate, self.out_start, self.cfg.npol)
 
     def synchronize(self):
         self.ctx.synchronize()
 
     def close(self):
-        if self.rescale is not None:
-            self.rescale.close()
-        if self.sample_delay is not None:
-            self.sample_delay.close()
-        self.ctx.close()
+        if not self._closed:
+            self._closed = True
+            _close_all(self.rescale, self.sample_delay, self.ctx)

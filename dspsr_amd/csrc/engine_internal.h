@@ -61,3 +61,75 @@ static inline int ctx_fail(dspsr_amd_ctx* ctx, int code, const char* fmt, ...)
   va_end(ap);
   return code;
 }
+
+// The refusal of a device-free check function (dspsr_amd_*_check_*): the text goes to the caller's buffer.
+static inline int msg_fail(char* msg, size_t len, const char* fmt, ...)
+{
+  if (msg && len) {
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(msg, len, fmt, ap);
+    va_end(ap);
+  }
+  return DSPSR_AMD_EINVAL;
+}
+
+// The host shell of the operators that transform tiles and add the detected bins (plfb.hip, bandpass.hip).
+//
+// The cut of a call's tiles into SEGMENTS of whole tiles, one workgroup per (segment, input channel): enough workgroups to fill the
+// chip, at most `cap` segments (the caller's: what its per-segment arrays may take of SEG_BYTES).  Pure: tiles per segment, segments.
+constexpr uint32_t SEG_TARGET_WG = 1024;                  // workgroups wanted per launch
+constexpr uint32_t SEG_MAX = 256;
+constexpr uint64_t SEG_BYTES = 256ull << 20;              // the per-segment arrays of a launch together take at most this
+static inline void segment_cut(const uint32_t ntile, const uint32_t nchan_in, const uint64_t cap, uint32_t& tps, uint32_t& nseg)
+{
+  nseg = SEG_TARGET_WG / nchan_in;
+  if (nseg > SEG_MAX) nseg = SEG_MAX;
+  if (nseg > cap) nseg = (uint32_t)cap;
+  if (nseg > ntile) nseg = ntile;
+  if (nseg < 1) nseg = 1;
+  tps = (ntile + nseg - 1) / nseg;
+  if (tps < 1) tps = 1;
+  nseg = (ntile + tps - 1) / tps;
+}
+
+// The device array of sums such an operator owns.  `who` names the C-ABI function in the error text.
+struct device_sums {
+  float* dev = nullptr;
+  uint64_t floats = 0;
+};
+static inline void sums_release(dspsr_amd_ctx* ctx, device_sums& a)
+{
+  (void)hipStreamSynchronize(ctx->stream);                  // launches in flight may still add to it
+  if (a.dev) (void)hipFree(a.dev);
+  a.dev = nullptr;
+  a.floats = 0;
+}
+// another size: the old array is released and the new one is NOT zeroed; on failure the array is empty
+static inline int sums_resize(dspsr_amd_ctx* ctx, device_sums& a, const uint64_t need, const char* who)
+{
+  if (need == a.floats) return DSPSR_AMD_OK;
+  sums_release(ctx, a);
+  if (hipMalloc((void**)&a.dev, need * sizeof(float)) != hipSuccess) {
+    a.dev = nullptr;
+    return ctx_fail(ctx, DSPSR_AMD_ENOMEM, "%s: hipMalloc(%llu floats) failed", who, (unsigned long long)need);
+  }
+  a.floats = need;
+  return DSPSR_AMD_OK;
+}
+static inline int sums_zero(dspsr_amd_ctx* ctx, device_sums& a, const char* who)
+{
+  if (!a.dev) return DSPSR_AMD_OK;
+  const hipError_t e = hipMemsetAsync(a.dev, 0, a.floats * sizeof(float), ctx->stream);
+  if (e != hipSuccess) return ctx_fail(ctx, DSPSR_AMD_EHIP, "%s: %s", who, hipGetErrorString(e));
+  return DSPSR_AMD_OK;
+}
+// copies the sums to the host and waits
+static inline int sums_synch(dspsr_amd_ctx* ctx, const device_sums& a, float* host, const char* who)
+{
+  if (!a.dev) return ctx_fail(ctx, DSPSR_AMD_ESTATE, "%s: no shape", who);
+  hipError_t e = hipMemcpyAsync(host, a.dev, a.floats * sizeof(float), hipMemcpyDeviceToHost, ctx->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+  if (e != hipSuccess) return ctx_fail(ctx, DSPSR_AMD_EHIP, "%s: %s", who, hipGetErrorString(e));
+  return DSPSR_AMD_OK;
+}

@@ -4,11 +4,9 @@
 // samples (Analytic rows) or 2 nchan real samples (Nyquist rows) of every input channel and polarisation from idat_start on are
 // transformed (forward, unnormalised), square-law detected and added into phase bin `bin` of output channel chan * nchan + k.
 //
-// A workgroup tile is wgfft's 16384 points: C = nchan complex points x T = 16384 / C columns, the columns being the (window,
-// polarisation) pairs of T / 2 windows -- both polarisations of a window are the two halves of a thread's butterfly pair, as
-// in k_tfp.  Nyquist rows are transformed as C complex points z[n] = x[2n] + i x[2n+1] followed by the Hermitian split (k_tfp's),
-// never as a 2 C point transform.  The transform is staged in the exchange buffer; thread t then owns bins t, t + 512, ... (bin
-// pairs (k, C - k) for Nyquist rows) of EVERY window of the tile and adds their detected products to register sums.
+// The tile -- C = nchan complex points x the (window, polarisation) columns of Tp = 8192 / C windows, its staged transform, the
+// Hermitian split of Nyquist rows, detection and the register sums of the bins a thread owns -- is spectral_tile.h's, shared with
+// k_bandpass.  Here: the load of a window from the window list, and where the sums go.
 //
 // Accumulation: the host sorts the call's windows by bin (stable: time order inside a bin) and cuts the sorted list into
 // SEGMENTS of whole tiles; workgroup (segment, input channel) walks its windows in order and keeps a bin's sums in registers
@@ -22,13 +20,10 @@
 #include <vector>
 
 #include "engine_internal.h"
+#include "spectral_tile.h"
 
 namespace dspsr_amd {
 
-constexpr uint32_t PL_THREADS = 512;
-constexpr uint32_t PL_TARGET_WG = 1024;                   // workgroups wanted per launch when the windows have to be cut
-constexpr uint32_t PL_MAX_SEG = 256;
-constexpr uint64_t PL_SLOT_BYTES = 256ull << 20;          // the slots of a launch together take at most this
 constexpr uint32_t PL_SLOT = 0x80000000u;                 // destination flag: a slot, not a bin of the profile
 
 struct PlfbArgs {
@@ -43,160 +38,65 @@ struct PlfbArgs {
 };
 
 template <int LOGC, int NDIM, int NPO>
-__global__ __launch_bounds__(PL_THREADS) void k_plfb(const PlfbArgs a, const cf* __restrict__ tw)
+__global__ __launch_bounds__(ST_THREADS) void k_plfb(const PlfbArgs a, const cf* __restrict__ tw)
 {
-  typedef FftPlan<LOGC> P;
+  // NPO == 1: p0 + p1, two input polarisations give total intensity; the Nyquist twiddles are always held in registers
+  typedef SpectralTile<LOGC, NDIM, NPO, true, 8> T;
   extern __shared__ __attribute__((aligned(16))) cf lds[];
-  uint32_t tid = threadIdx.x;
-  constexpr uint32_t nt = PL_THREADS;
-  constexpr int logT = 14 - LOGC, logTp = logT - 1;
-  constexpr uint32_t Tp = 1u << logTp, C = 1u << LOGC;
-  constexpr uint32_t NK = NDIM == 2 ? C : C / 2;            // bins (Analytic) or bin pairs (Nyquist) of a window
-  constexpr int NB = NK > nt ? NK / nt : 1;                 //   ... of which a thread owns NB
-  constexpr int NE = NDIM == 2 ? 1 : 2;
-  const uint32_t ltw_off = lds_pad(PTS * nt) + 8;
-  ltw_fill<LOGC>(lds, ltw_off, tw, tid, nt);
+  const uint32_t tid = threadIdx.x;
+  const uint32_t ltw_off = T::fill_twiddle_table(lds, tw, tid);
   const uint32_t chan = blockIdx.y, seg = blockIdx.x;
   const uint32_t w_begin = seg * a.wps, w_end = min(w_begin + a.wps, a.nwin);
   const float* const row0 = a.in + chan * a.cs;
   const float* const row1 = row0 + a.ps;
   const bool two = a.npol_in > 1;                           // one input polarisation: the second column of every pair is zero
 
-  float wc[NB], ws[NB];                                     // Nyquist: w^k = exp(-i pi k / C) = (wc, -ws)
-#pragma unroll
-  for (int j = 0; j < NB; j++) {
-    const float x = (float)(threadIdx.x + j * nt) * __uint_as_float((uint32_t)(127 - (LOGC + 1)) << 23);   // k / 2C revolutions, exact
-    wc[j] = __builtin_amdgcn_cosf(x);
-    ws[j] = __builtin_amdgcn_sinf(x);
-  }
-
-  float acc[NB][NE][NPO];
-#pragma unroll
-  for (int j = 0; j < NB; j++)
-#pragma unroll
-    for (int e = 0; e < NE; e++)
-#pragma unroll
-      for (int q = 0; q < NPO; q++) acc[j][e][q] = 0.f;
+  typename T::Tw wc, ws;
+  T::twiddles(wc, ws);
+  typename T::Acc acc;
+  T::zero(acc);
   uint32_t cur = 0xffffffffu;                               // destination of the sums held (uniform); none yet
 
   // adds the sums to their destination -- this workgroup is its only owner in the launch -- and clears them
   auto flush = [&](const uint32_t d) {
-    uint32_t t0 = threadIdx.x;
-    asm volatile("" : "+v"(t0));                            // (loop-invariant addresses: keep them out of the tile loop's registers)
+    T::for_owned([&](const int j, const int e, const uint32_t bin) {
+      const size_t co = (size_t)chan * T::C + bin;
 #pragma unroll
-    for (int j = 0; j < NB; j++) {
-      const uint32_t k = t0 + j * nt;
-      if (k < NK) {
-#pragma unroll
-        for (int e = 0; e < NE; e++) {
-          const uint32_t bin = e == 0 ? k : (k ? C - k : C / 2);
-          const size_t co = (size_t)chan * C + bin;
-#pragma unroll
-          for (int q = 0; q < NPO; q++) {
-            if (d & PL_SLOT) {
-              a.slots[((size_t)(d & ~PL_SLOT) * NPO + q) * a.nchan_out + co] = acc[j][e][q];
-            } else {
-              float* const dst = a.prof + (co * NPO + q) * a.nbin + d;
-              *dst += acc[j][e][q];
-            }
-          }
+      for (int q = 0; q < NPO; q++) {
+        if (d & PL_SLOT) {
+          a.slots[((size_t)(d & ~PL_SLOT) * NPO + q) * a.nchan_out + co] = acc[j][e][q];
+        } else {
+          float* const dst = a.prof + (co * NPO + q) * a.nbin + d;
+          *dst += acc[j][e][q];
         }
       }
-#pragma unroll
-      for (int e = 0; e < NE; e++)
-#pragma unroll
-        for (int q = 0; q < NPO; q++) acc[j][e][q] = 0.f;
-    }
+    });
+    T::zero(acc);
   };
-  // the detected products of one bin: X0, X1 = (re, im) of the two polarisations
-  auto detect = [&](float (&s)[NPO], const float r0, const float i0, const float r1, const float i1, const float sgn) {
-    float p0 = r0 * r0; p0 += i0 * i0;                      // PhaseLockedFilterbank.C:275-276
-    float p1 = r1 * r1; p1 += i1 * i1;
-    if constexpr (NPO == 1) {
-      s[0] += p0 + p1;
+  // window w starts at sample wstart[w]
+  auto load = [&](const uint32_t w, const uint32_t n, float2& v0, float2& v1) {
+    const uint32_t s = a.wstart[w];
+    if constexpr (NDIM == 2) {
+      v0 = reinterpret_cast<const float2*>(row0)[s + n];
+      if (two) v1 = reinterpret_cast<const float2*>(row1)[s + n];
     } else {
-      s[0] += p0;
-      s[1] += p1;
-      if constexpr (NPO == 4) {
-        s[2] += r0 * r1 + i0 * i1;                          // :288-293
-        s[NPO == 4 ? 3 : 0] += sgn * (r0 * i1 - i0 * r1);
-      }
+      const size_t o = (size_t)s + 2 * n;                   // any parity of s: two 4-byte loads
+      v0 = make_float2(row0[o], row0[o + 1]);
+      if (two) v1 = make_float2(row1[o], row1[o + 1]);
     }
   };
 
-  for (uint32_t w0 = w_begin; w0 < w_end; w0 += Tp) {
-    asm volatile("" : "+v"(tid));
-    cx2 x[NPAIR];
-#pragma unroll
-    for (int g2 = 0; g2 < P::G1; g2 += 2)
-#pragma unroll
-      for (int i = 0; i < P::R1; i++) {
-        const uint32_t el = first_stage_elem<LOGC>(tid, logT, g2, i);
-        const uint32_t w = w0 + ((el & ((1u << logT) - 1)) >> 1), n = el >> logT;
-        float2 v0 = make_float2(0.f, 0.f), v1 = make_float2(0.f, 0.f);
-        if (w < w_end) {
-          const uint32_t s = a.wstart[w];
-          if constexpr (NDIM == 2) {
-            v0 = reinterpret_cast<const float2*>(row0)[s + n];
-            if (two) v1 = reinterpret_cast<const float2*>(row1)[s + n];
-          } else {
-            const size_t o = (size_t)s + 2 * n;             // any parity of s: two 4-byte loads
-            v0 = make_float2(row0[o], row0[o + 1]);
-            if (two) v1 = make_float2(row1[o], row1[o + 1]);
-          }
-        }
-        cx2& d = x[(g2 / 2) * P::R1 + i];
-        d.x = (v2f){v0.x, v1.x};
-        d.y = (v2f){v0.y, v1.y};
-      }
-    // staged transform: one plane of C float4 per window, (Re p0, Re p1, Im p0, Im p1) (k_tfp's staging)
-    float4* const stg = (float4*)lds;
-    constexpr uint32_t plane = C + (Tp <= 64 ? 8u : 0u);
-    auto store = [&](const uint32_t col, const uint32_t pp, const uint32_t pstride, auto& v) {
-      constexpr int R = sizeof(v) / sizeof(v[0]);
-      float4* const d = stg + (col >> 1) * plane + pp;
-#pragma unroll
-      for (int k = 0; k < R; k++) d[k * pstride] = make_float4(v[k].x[0], v[k].x[1], v[k].y[0], v[k].y[1]);
-    };
-    wgfft<LOGC, -1, true>(lds, ltw_off, tid, logT, x, store);
-    __syncthreads();
-    const uint32_t nw = min(Tp, w_end - w0);
+  for (uint32_t w0 = w_begin; w0 < w_end; w0 += T::Tp) {
+    uint32_t t = tid;                                       // (a copy: see transform)
+    T::transform(lds, ltw_off, t, w0, w_end, load);
+    const uint32_t nw = min(T::Tp, w_end - w0);
     for (uint32_t c2 = 0; c2 < nw; c2++) {
       const uint32_t d = __builtin_amdgcn_readfirstlane(a.wdst[w0 + c2]);
       if (d != cur) {
         if (cur != 0xffffffffu) flush(cur);
         cur = d;
       }
-      const float4* const pl = stg + c2 * plane;
-      uint32_t t0 = threadIdx.x;
-      asm volatile("" : "+v"(t0));
-#pragma unroll
-      for (int j = 0; j < NB; j++) {
-        const uint32_t k = t0 + j * nt;
-        if (k >= NK) continue;
-        if constexpr (NDIM == 2) {
-          const float4 z = pl[k];
-          detect(acc[j][0], z.x, z.z, z.y, z.w, 1.f);
-        } else {
-          // X[k] = A + w^k B, X[C-k] = conj(A - w^k B); A = (Z[k] + conj Z[C-k]) / 2, B = (Z[k] - conj Z[C-k]) / 2i.  Bins 0 and
-          // C/2 are their own mirrors: X[0] from Z[0] with w = 1, X[C/2] from Z[C/2] with w = -i
-          const float4 zk = pl[k], zm = pl[k ? C - k : 0];
-          const v2f zr = {zk.x, zk.y}, zi = {zk.z, zk.w}, mr = {zm.x, zm.y}, mi = {zm.z, zm.w};
-          const v2f ar = 0.5f * (zr + mr), ai = 0.5f * (zi - mi);
-          const v2f br = 0.5f * (zi + mi), bi = 0.5f * (mr - zr);
-          const float c = wc[j], sn = ws[j];
-          const v2f wr = c * br + sn * bi, wi = c * bi - sn * br;
-          const v2f xr = ar + wr, xi = ai + wi;
-          detect(acc[j][0], xr[0], xi[0], xr[1], xi[1], 1.f);
-          if (k) {
-            const v2f yr = ar - wr, yi = ai - wi;           // X[C-k] = (yr, -yi)
-            detect(acc[j][NE - 1], yr[0], yi[0], yr[1], yi[1], -1.f);
-          } else {
-            const float4 zh = pl[C / 2];                    // X[C/2] = (Re Z, -Im Z)
-            detect(acc[j][NE - 1], zh.x, zh.z, zh.y, zh.w, -1.f);
-          }
-        }
-      }
+      T::add_part(acc, lds, c2, wc, ws);
     }
     __syncthreads();                                        // the next tile's exchanges overwrite the staged image
   }
@@ -234,25 +134,13 @@ static kplfb_t pick_plfb(const int logc, const uint32_t ndim, const uint32_t npo
   return npo == 1 ? pick_plfb2<1, 1>(logc) : npo == 2 ? pick_plfb2<1, 2>(logc) : pick_plfb2<1, 4>(logc);
 }
 
-static int msg_fail(char* msg, size_t len, const char* fmt, ...)
-{
-  if (msg && len) {
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(msg, len, fmt, ap);
-    va_end(ap);
-  }
-  return DSPSR_AMD_EINVAL;
-}
-
 }  // namespace dspsr_amd
 using namespace dspsr_amd;
 
 struct dspsr_amd_plfb {
   dspsr_amd_ctx* ctx = nullptr;
   uint32_t nchan_in = 0, npol_in = 0, ndim_in = 0, nchan = 0, npol_out = 0, nbin = 0;
-  uint64_t prof_floats = 0;
-  float* prof = nullptr;
+  device_sums prof;                 // [nchan_out][npol_out][nbin]
   float* slots = nullptr;
   size_t slot_count = 0;
   std::vector<uint32_t> order, host;
@@ -313,14 +201,6 @@ extern "C" int dspsr_amd_plfb_check_windows(uint32_t nchan_in, uint32_t npol_in,
   return DSPSR_AMD_OK;
 }
 
-static void plfb_release(dspsr_amd_plfb* f)
-{
-  (void)hipStreamSynchronize(f->ctx->stream);
-  if (f->prof) (void)hipFree(f->prof);
-  f->prof = nullptr;
-  f->prof_floats = 0;
-}
-
 extern "C" int dspsr_amd_plfb_create(dspsr_amd_ctx* ctx, dspsr_amd_plfb** out)
 {
   if (!ctx || !out) return DSPSR_AMD_EINVAL;
@@ -333,7 +213,7 @@ extern "C" int dspsr_amd_plfb_create(dspsr_amd_ctx* ctx, dspsr_amd_plfb** out)
 extern "C" void dspsr_amd_plfb_destroy(dspsr_amd_plfb* f)
 {
   if (!f) return;
-  plfb_release(f);
+  sums_release(f->ctx, f->prof);
   if (f->slots) (void)hipFree(f->slots);
   if (f->dev) (void)hipFree(f->dev);
   delete f;
@@ -342,10 +222,7 @@ extern "C" void dspsr_amd_plfb_destroy(dspsr_amd_plfb* f)
 extern "C" int dspsr_amd_plfb_zero(dspsr_amd_plfb* f)
 {
   if (!f) return DSPSR_AMD_EINVAL;
-  if (!f->prof) return DSPSR_AMD_OK;
-  const hipError_t e = hipMemsetAsync(f->prof, 0, f->prof_floats * sizeof(float), f->ctx->stream);
-  if (e != hipSuccess) return ctx_fail(f->ctx, DSPSR_AMD_EHIP, "dspsr_amd_plfb_zero: %s", hipGetErrorString(e));
-  return DSPSR_AMD_OK;
+  return sums_zero(f->ctx, f->prof, "dspsr_amd_plfb_zero");
 }
 
 extern "C" int dspsr_amd_plfb_set_shape(dspsr_amd_plfb* f, uint32_t nchan_in, uint32_t npol_in, uint32_t ndim_in, uint32_t nchan,
@@ -357,15 +234,9 @@ extern "C" int dspsr_amd_plfb_set_shape(dspsr_amd_plfb* f, uint32_t nchan_in, ui
   if (rc != DSPSR_AMD_OK) return ctx_fail(f->ctx, rc, "%s", msg);
   const bool changed = nchan_in != f->nchan_in || npol_in != f->npol_in || ndim_in != f->ndim_in || nchan != f->nchan ||
                        npol_out != f->npol_out || nbin != f->nbin;
-  const uint64_t need = (uint64_t)nchan_in * nchan * npol_out * nbin;
-  if (need != f->prof_floats) {
-    plfb_release(f);
-    if (hipMalloc((void**)&f->prof, need * sizeof(float)) != hipSuccess) {
-      f->prof = nullptr;
-      f->nbin = 0;
-      return ctx_fail(f->ctx, DSPSR_AMD_ENOMEM, "dspsr_amd_plfb_set_shape: hipMalloc(%llu floats) failed", (unsigned long long)need);
-    }
-    f->prof_floats = need;
+  if (sums_resize(f->ctx, f->prof, (uint64_t)nchan_in * nchan * npol_out * nbin, "dspsr_amd_plfb_set_shape") != DSPSR_AMD_OK) {
+    f->nbin = 0;
+    return DSPSR_AMD_ENOMEM;
   }
   f->nchan_in = nchan_in; f->npol_in = npol_in; f->ndim_in = ndim_in; f->nchan = nchan; f->npol_out = npol_out; f->nbin = nbin;
   return changed ? dspsr_amd_plfb_zero(f) : DSPSR_AMD_OK;   // a new shape starts from zero; the same shape keeps its sums
@@ -376,7 +247,7 @@ extern "C" int dspsr_amd_plfb_accumulate(dspsr_amd_plfb* f, const float* in_dev,
 {
   if (!f) return DSPSR_AMD_EINVAL;
   const char* who = "dspsr_amd_plfb_accumulate";
-  if (!f->prof) return ctx_fail(f->ctx, DSPSR_AMD_ESTATE, "%s: no shape", who);
+  if (!f->prof.dev) return ctx_fail(f->ctx, DSPSR_AMD_ESTATE, "%s: no shape", who);
   char msg[400];
   const int rc = dspsr_amd_plfb_check_windows(f->nchan_in, f->npol_in, f->ndim_in, f->nchan, f->nbin, (uint64_t)(uintptr_t)in_dev,
                                               chan_stride, pol_stride, ndat, nwin, idat_start_host, bin_host, msg, sizeof msg);
@@ -388,17 +259,11 @@ extern "C" int dspsr_amd_plfb_accumulate(dspsr_amd_plfb* f, const float* in_dev,
   while ((1u << logc) < f->nchan) logc++;
   const uint32_t tp = 8192u >> logc;                        // windows per tile
   const uint32_t n = (uint32_t)nwin, nchan_out = f->nchan_in * f->nchan;
-  // segments: whole tiles; enough workgroups to fill the chip, within the memory set aside for the slots (two per segment at most)
-  const uint32_t ntile = (n + tp - 1) / tp;
-  uint32_t nseg = PL_TARGET_WG / f->nchan_in;
-  if (nseg > PL_MAX_SEG) nseg = PL_MAX_SEG;
+  // segments within the memory set aside for the slots (two per segment at most)
   const uint64_t slot_floats = (uint64_t)f->npol_out * nchan_out;
-  const uint64_t cap = PL_SLOT_BYTES / (2 * slot_floats * sizeof(float));
-  if (nseg > cap) nseg = (uint32_t)cap;
-  if (nseg > ntile) nseg = ntile;
-  if (nseg < 1) nseg = 1;
-  const uint32_t wps = ((ntile + nseg - 1) / nseg) * tp;
-  nseg = (n + wps - 1) / wps;
+  uint32_t tps, nseg;
+  segment_cut((n + tp - 1) / tp, f->nchan_in, SEG_BYTES / (2 * slot_floats * sizeof(float)), tps, nseg);
+  const uint32_t wps = tps * tp;
 
   // windows by bin, time order inside a bin
   f->order.resize(n);
@@ -438,19 +303,19 @@ extern "C" int dspsr_amd_plfb_accumulate(dspsr_amd_plfb* f, const float* in_dev,
 
   PlfbArgs a;
   a.in = in_dev; a.cs = chan_stride; a.ps = pol_stride;
-  a.prof = f->prof; a.slots = f->slots;
+  a.prof = f->prof.dev; a.slots = f->slots;
   a.wstart = f->dev; a.wdst = f->dev + n;
   a.nwin = n; a.wps = wps; a.nbin = f->nbin; a.nchan_out = nchan_out; a.npol_in = f->npol_in;
   const kplfb_t k = pick_plfb(logc, f->ndim_in, f->npol_out);
   const size_t lds = lds_total_words_host(16384, logc) * sizeof(cf);
   err = dspsr_amd_allow_lds((const void*)k, lds);
   if (err != hipSuccess) return ctx_fail(f->ctx, DSPSR_AMD_EHIP, "%s: %s", who, hipGetErrorString(err));
-  hipLaunchKernelGGL(k, dim3(nseg, f->nchan_in), dim3(PL_THREADS), lds, s, a, f->ctx->tw);
+  hipLaunchKernelGGL(k, dim3(nseg, f->nchan_in), dim3(ST_THREADS), lds, s, a, f->ctx->tw);
   err = hipGetLastError();
   if (err != hipSuccess) return ctx_fail(f->ctx, DSPSR_AMD_EHIP, "%s: launch: %s", who, hipGetErrorString(err));
   if (!ent.empty()) {
     const uint32_t bx = (uint32_t)((slot_floats + 255) / 256);
-    hipLaunchKernelGGL(k_plfb_combine, dim3(bx, (uint32_t)(ent.size() / 3)), dim3(256), 0, s, f->prof, (const float*)f->slots,
+    hipLaunchKernelGGL(k_plfb_combine, dim3(bx, (uint32_t)(ent.size() / 3)), dim3(256), 0, s, f->prof.dev, (const float*)f->slots,
                        (const uint32_t*)(f->dev + ent_off), nchan_out, f->npol_out, f->nbin);
     err = hipGetLastError();
     if (err != hipSuccess) return ctx_fail(f->ctx, DSPSR_AMD_EHIP, "%s: combine launch: %s", who, hipGetErrorString(err));
@@ -458,14 +323,10 @@ extern "C" int dspsr_amd_plfb_accumulate(dspsr_amd_plfb* f, const float* in_dev,
   return DSPSR_AMD_OK;
 }
 
-extern "C" float* dspsr_amd_plfb_profile_dev(dspsr_amd_plfb* f) { return f ? f->prof : nullptr; }
+extern "C" float* dspsr_amd_plfb_profile_dev(dspsr_amd_plfb* f) { return f ? f->prof.dev : nullptr; }
 
 extern "C" int dspsr_amd_plfb_synch(dspsr_amd_plfb* f, float* profile_host)
 {
   if (!f || !profile_host) return DSPSR_AMD_EINVAL;
-  if (!f->prof) return ctx_fail(f->ctx, DSPSR_AMD_ESTATE, "dspsr_amd_plfb_synch: no shape");
-  hipError_t e = hipMemcpyAsync(profile_host, f->prof, f->prof_floats * sizeof(float), hipMemcpyDeviceToHost, f->ctx->stream);
-  if (e == hipSuccess) e = hipStreamSynchronize(f->ctx->stream);
-  if (e != hipSuccess) return ctx_fail(f->ctx, DSPSR_AMD_EHIP, "dspsr_amd_plfb_synch: %s", hipGetErrorString(e));
-  return DSPSR_AMD_OK;
+  return sums_synch(f->ctx, f->prof, profile_host, "dspsr_amd_plfb_synch");
 }

@@ -33,6 +33,41 @@ def _check(ctx_handle, code, where):
         raise DspsrAmdError("%s failed (%d): %s" % (where, code, msg))
 
 
+def _host_check(fn, *args):
+    """One of the C-ABI's device-free check functions: its refusal, with the library's text, as DspsrAmdError."""
+    msg = C.create_string_buffer(400)
+    if fn(*args, msg, len(msg)) != _lib.OK:
+        raise DspsrAmdError(msg.value.decode())
+
+
+class _Owned:
+    """An object the C-ABI makes with <_abi>_create(ctx, ..., &handle) and ends with <_abi>_destroy(handle); dead once its context
+    is closed (a context closed first has already taken its device objects with it)."""
+
+    _abi = None
+
+    def __init__(self, ctx: "Context"):
+        self.ctx = ctx
+        self.handle = None
+
+    def _create(self, *args):
+        h = C.c_void_p()
+        name = self._abi + "_create"
+        _check(self.ctx.handle, getattr(lib, name)(self.ctx.handle, *args, C.byref(h)), name)
+        self.handle = h
+
+    def close(self):
+        if self.handle and self.ctx.handle:
+            getattr(lib, self._abi + "_destroy")(self.handle)
+        self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class Context:
     """One per pipeline thread/GPU, bound to one HIP stream (SingleThread.C:213-290)."""
 
@@ -147,13 +182,11 @@ def _strides3(t):
     return t.stride(0), t.stride(1)
 
 
-class FilterbankEngine:
+class FilterbankEngine(_Owned):
     """dsp::Filterbank::Engine.  setup() takes what CUDA::FilterbankEngine::setup reads from the
     Filterbank (FilterbankCUDA.cu:73-168)."""
 
-    def __init__(self, ctx: Context):
-        self.ctx = ctx
-        self.handle = None
+    _abi = "dspsr_amd_filterbank"
 
     def setup(self, nchan_subband, freq_res, nfilt_pos, nfilt_neg, input_nchan=1, npol=2, real_input=True,
               kernel: np.ndarray | None = None, max_parts: int = 1, force_four_pass: bool | int = False,
@@ -171,10 +204,8 @@ class FilterbankEngine:
         cfg = _lib.FilterbankConfig(nchan_subband, freq_res, nfilt_pos, nfilt_neg, input_nchan, npol,
                                     1 if real_input else 0, max_parts, int(force_four_pass), fused_fold,
                                     1 if split_in_inverse else 0)
-        h = C.c_void_p()
-        _check(self.ctx.handle, lib.dspsr_amd_filterbank_create(self.ctx.handle, C.byref(cfg), C.byref(h)),
-               "dspsr_amd_filterbank_create")
-        self.handle = h
+        self._create(C.byref(cfg))
+        h = self.handle
         self.cfg = cfg
         a, b, c, d = C.c_uint64(), C.c_uint64(), C.c_uint64(), C.c_uint32()
         lib.dspsr_amd_filterbank_sizes(h, C.byref(a), C.byref(b), C.byref(c), C.byref(d))
@@ -347,17 +378,6 @@ class FilterbankEngine:
     def finish(self):
         self.ctx.synchronize()
 
-    def close(self):
-        if self.handle and self.ctx.handle:          # (a context closed first has already taken the device objects with it)
-            lib.dspsr_amd_filterbank_destroy(self.handle)
-        self.handle = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
 
 class ConvolutionEngine(FilterbankEngine):
     """Mirror of dsp::Convolution::Engine (Signal/General/dsp/Convolution.h:158-167; CUDA twin
@@ -472,21 +492,20 @@ def dedispersion_sample_delays(centre_frequency, bandwidth, dispersion_measure, 
     return d
 
 
-class SampleDelay:
+class SampleDelay(_Owned):
     """Mirror of dsp::SampleDelay (Signal/General/SampleDelay.C): delays[ichan][ipol] from a SampleDelayFunction."""
 
+    _abi = "dspsr_amd_sample_delay"
+
     def __init__(self, ctx: Context, delays, npol=1, absolute=False):
-        self.ctx = ctx
+        super().__init__(ctx)
         d = np.ascontiguousarray(np.asarray(delays, np.int64))
         if d.ndim == 1:                                       # per channel, same for every polarisation
             d = np.ascontiguousarray(np.repeat(d[:, None], npol, axis=1))
         self.nchan, self.npol = d.shape
-        h = C.c_void_p()
-        _check(ctx.handle, lib.dspsr_amd_sample_delay_create(ctx.handle, self.nchan, self.npol, d.ctypes.data_as(C.c_void_p),
-                                                             int(absolute), C.byref(h)), "dspsr_amd_sample_delay_create")
-        self.handle = h
-        self.zero_delay = lib.dspsr_amd_sample_delay_zero_delay(h)
-        self.total_delay = lib.dspsr_amd_sample_delay_total_delay(h)
+        self._create(self.nchan, self.npol, d.ctypes.data_as(C.c_void_p), int(absolute))
+        self.zero_delay = lib.dspsr_amd_sample_delay_zero_delay(self.handle)
+        self.total_delay = lib.dspsr_amd_sample_delay_total_delay(self.handle)
 
     def transform(self, inp, out=None):
         """inp/out: float32 device tensors [nchan][npol][ndat][ndim] (the last axis may be absent); returns ndat_out."""
@@ -498,28 +517,16 @@ class SampleDelay:
             inp.shape[2], C.byref(n)), "dspsr_amd_sample_delay_transform")
         return n.value
 
-    def close(self):
-        if self.handle and self.ctx.handle:
-            lib.dspsr_amd_sample_delay_destroy(self.handle)
-        self.handle = None
 
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-class Rescale:
+class Rescale(_Owned):
     """Mirror of dsp::Rescale for TFP-ordered detected data (Signal/General/Rescale.C): offset/scale per (pol, chan)."""
 
+    _abi = "dspsr_amd_rescale"
+
     def __init__(self, ctx: Context, nchan, npol=1, interval_samples=0, constant=False):
-        self.ctx = ctx
+        super().__init__(ctx)
         self.nchan, self.npol = nchan, npol
-        h = C.c_void_p()
-        _check(ctx.handle, lib.dspsr_amd_rescale_create(ctx.handle, nchan, npol, interval_samples, int(constant), C.byref(h)),
-               "dspsr_amd_rescale_create")
-        self.handle = h
+        self._create(nchan, npol, interval_samples, int(constant))
 
     def transform(self, inp, out=None):
         """inp/out: float32 device tensors [ndat][nchan][npol] (out defaults to in place)."""
@@ -569,11 +576,6 @@ class Rescale:
         _check(self.ctx.handle, lib.dspsr_amd_rescale_get(self.handle, off.ctypes.data_as(C.c_void_p), sc.ctypes.data_as(C.c_void_p)),
                "dspsr_amd_rescale_get")
         return off.reshape(self.nchan, self.npol), sc.reshape(self.nchan, self.npol)
-
-    def close(self):
-        if self.handle and self.ctx.handle:
-            lib.dspsr_amd_rescale_destroy(self.handle)
-        self.handle = None
 
 
 def pscrunch_tfp(ctx: Context, inp, out, nchan, npol=2):
@@ -630,14 +632,14 @@ def fourth_moment(ctx: Context, inp, out, ndat=None):
            "dspsr_amd_fourth_moment")
 
 
-class FoldEngine:
+class FoldEngine(_Owned):
     """dsp::Fold::Engine; owns the device-resident profiles (get_profiles)."""
 
+    _abi = "dspsr_amd_fold"
+
     def __init__(self, ctx: Context):
-        self.ctx = ctx
-        h = C.c_void_p()
-        _check(ctx.handle, lib.dspsr_amd_fold_create(ctx.handle, C.byref(h)), "dspsr_amd_fold_create")
-        self.handle = h
+        super().__init__(ctx)
+        self._create()
         self.shape = None
 
     def set_shape(self, nchan, npol, ndim, nbin):
@@ -734,17 +736,6 @@ class FoldEngine:
                "dspsr_amd_fold_synch")
         return out
 
-    def close(self):
-        if self.handle and self.ctx.handle:
-            lib.dspsr_amd_fold_destroy(self.handle)
-        self.handle = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
 
 def cyclic_binplan(phi: float, phase_per_sample: float, nbin: int, ndat: int):
     """The two plans of lag folding (CyclicFold.C:293-301 fed by Fold.C:744-787) and hits[nbin]."""
@@ -774,14 +765,14 @@ def cyclic_lags_to_spectra(lags: np.ndarray, mover: int = 1) -> np.ndarray:
     return out
 
 
-class CyclicFoldEngine:
+class CyclicFoldEngine(_Owned):
     """dsp::CyclicFoldEngine (Signal/Pulsar/dsp/CyclicFold.h:93-160); owns the device-resident lag data."""
 
+    _abi = "dspsr_amd_cyclic_fold"
+
     def __init__(self, ctx: Context):
-        self.ctx = ctx
-        h = C.c_void_p()
-        _check(ctx.handle, lib.dspsr_amd_cyclic_fold_create(ctx.handle, C.byref(h)), "dspsr_amd_cyclic_fold_create")
-        self.handle = h
+        super().__init__(ctx)
+        self._create()
         self.shape = None
         self.mover = 1
 
@@ -827,24 +818,10 @@ class CyclicFoldEngine:
         """CyclicFoldEngine::synch: spectra [nchan * nchan_spec / mover][npol_out][nbin]."""
         return cyclic_lags_to_spectra(self.synch_lags(), self.mover)
 
-    def close(self):
-        if self.handle and self.ctx.handle:
-            lib.dspsr_amd_cyclic_fold_destroy(self.handle)
-        self.handle = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
 
 def plfb_check_shape(nchan_in, npol_in, ndim_in, nchan, npol_out, nbin):
     """The refusals of PhaseLockedFilterbankEngine.set_shape, on the host alone (no device)."""
-    msg = C.create_string_buffer(400)
-    code = lib.dspsr_amd_plfb_check_shape(nchan_in, npol_in, ndim_in, nchan, npol_out, nbin, msg, len(msg))
-    if code != _lib.OK:
-        raise DspsrAmdError(msg.value.decode())
+    _host_check(lib.dspsr_amd_plfb_check_shape, nchan_in, npol_in, ndim_in, nchan, npol_out, nbin)
 
 
 def plfb_check_windows(nchan_in, npol_in, ndim_in, nchan, nbin, in_addr, chan_stride, pol_stride, ndat, idat_start, bins):
@@ -853,22 +830,19 @@ def plfb_check_windows(nchan_in, npol_in, ndim_in, nchan, nbin, in_addr, chan_st
     bn = np.ascontiguousarray(bins, dtype=np.uint32)
     if st.shape != bn.shape or st.ndim != 1:
         raise DspsrAmdError("plfb: idat_start and bin must be one-dimensional and of one length")
-    msg = C.create_string_buffer(400)
-    code = lib.dspsr_amd_plfb_check_windows(nchan_in, npol_in, ndim_in, nchan, nbin, in_addr, chan_stride, pol_stride, ndat, st.size,
-                                            st.ctypes.data_as(C.c_void_p), bn.ctypes.data_as(C.c_void_p), msg, len(msg))
-    if code != _lib.OK:
-        raise DspsrAmdError(msg.value.decode())
+    _host_check(lib.dspsr_amd_plfb_check_windows, nchan_in, npol_in, ndim_in, nchan, nbin, in_addr, chan_stride, pol_stride, ndat, st.size,
+                st.ctypes.data_as(C.c_void_p), bn.ctypes.data_as(C.c_void_p))
 
 
-class PhaseLockedFilterbankEngine:
+class PhaseLockedFilterbankEngine(_Owned):
     """The loop body of dsp::PhaseLockedFilterbank::transformation (Signal/Pulsar/PhaseLockedFilterbank.C:254-297) on the device;
     owns the device-resident profile [nchan_in * nchan][npol_out][nbin]."""
 
+    _abi = "dspsr_amd_plfb"
+
     def __init__(self, ctx: Context):
-        self.ctx = ctx
-        h = C.c_void_p()
-        _check(ctx.handle, lib.dspsr_amd_plfb_create(ctx.handle, C.byref(h)), "dspsr_amd_plfb_create")
-        self.handle = h
+        super().__init__(ctx)
+        self._create()
         self.shape = None
 
     def set_shape(self, nchan_in, npol_in, ndim_in, nchan, npol_out, nbin):
@@ -900,47 +874,30 @@ class PhaseLockedFilterbankEngine:
         _check(self.ctx.handle, lib.dspsr_amd_plfb_synch(self.handle, out.ctypes.data_as(C.c_void_p)), "dspsr_amd_plfb_synch")
         return out
 
-    def close(self):
-        if self.handle and self.ctx.handle:
-            lib.dspsr_amd_plfb_destroy(self.handle)
-        self.handle = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
 
 def bandpass_check_shape(nchan_in, npol_in, ndim_in, resolution, npol_out):
     """The refusals of BandpassEngine.set_shape, on the host alone (no device)."""
-    msg = C.create_string_buffer(400)
-    code = lib.dspsr_amd_bandpass_check_shape(nchan_in, npol_in, ndim_in, resolution, npol_out, msg, len(msg))
-    if code != _lib.OK:
-        raise DspsrAmdError(msg.value.decode())
+    _host_check(lib.dspsr_amd_bandpass_check_shape, nchan_in, npol_in, ndim_in, resolution, npol_out)
 
 
 def bandpass_check_input(nchan_in, npol_in, ndim_in, resolution, raw_layout, in_addr, chan_stride, pol_stride, ndat):
     """The refusals of BandpassEngine.accumulate (raw_layout -1) / accumulate_raw, on the host alone (no device).  Returns the launch
     arithmetic: (parts per workgroup tile, tiles per segment, segments)."""
-    msg = C.create_string_buffer(400)
     tp, tps, nseg = C.c_uint32(), C.c_uint32(), C.c_uint32()
-    code = lib.dspsr_amd_bandpass_check_input(nchan_in, npol_in, ndim_in, resolution, raw_layout, in_addr, chan_stride, pol_stride,
-                                              ndat, C.byref(tp), C.byref(tps), C.byref(nseg), msg, len(msg))
-    if code != _lib.OK:
-        raise DspsrAmdError(msg.value.decode())
+    _host_check(lib.dspsr_amd_bandpass_check_input, nchan_in, npol_in, ndim_in, resolution, raw_layout, in_addr, chan_stride, pol_stride,
+                ndat, C.byref(tp), C.byref(tps), C.byref(nseg))
     return tp.value, tps.value, nseg.value
 
 
-class BandpassEngine:
+class BandpassEngine(_Owned):
     """dsp::Bandpass::transformation (Signal/General/Bandpass.C:50-175) on the device; owns the device-resident passband
     [npol_out][nchan_in][resolution]."""
 
+    _abi = "dspsr_amd_bandpass"
+
     def __init__(self, ctx: Context):
-        self.ctx = ctx
-        h = C.c_void_p()
-        _check(ctx.handle, lib.dspsr_amd_bandpass_create(ctx.handle, C.byref(h)), "dspsr_amd_bandpass_create")
-        self.handle = h
+        super().__init__(ctx)
+        self._create()
         self.shape = None
         self.integration_samples = 0.0
 
@@ -977,24 +934,14 @@ class BandpassEngine:
         self.integration_samples = n.value
         return out
 
-    def close(self):
-        if self.handle and self.ctx.handle:
-            lib.dspsr_amd_bandpass_destroy(self.handle)
-        self.handle = None
 
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-class Communicator:
+class Communicator(_Owned):
     """The sub-integration exchange over RCCL / xGMI behind the C-ABI (dspsr_amd_comm_*, csrc/comm.hip): the same entry
     points DSPSR's C++ host calls.  One per pipeline context.  `unique_id` = the 128 bytes of `Communicator.unique_id()`
     made on rank 0 and handed to every rank by the host (bench.py: torch.distributed's store; DSPSR: its MPI transport).
     The Python host shares PyTorch's ROCm runtime (see _lib.load), so the RCCL opened is the one PyTorch ships."""
 
+    _abi = "dspsr_amd_comm"
     SUM, GATHER = _lib.REDUCE_SUM, _lib.REDUCE_GATHER
 
     @staticmethod
@@ -1018,10 +965,8 @@ class Communicator:
     def __init__(self, ctx: Context, nranks: int, rank: int, unique_id: bytes):
         Communicator._use_torch_rccl()
         assert len(unique_id) == _lib.UNIQUE_ID_BYTES
-        self.ctx = ctx
-        h = C.c_void_p()
-        _check(ctx.handle, lib.dspsr_amd_comm_create(ctx.handle, nranks, rank, unique_id, C.byref(h)), "dspsr_amd_comm_create")
-        self.handle = h
+        super().__init__(ctx)
+        self._create(nranks, rank, unique_id)
         self.nranks, self.rank = nranks, rank
         self._shape = None
 
@@ -1054,14 +999,3 @@ class Communicator:
         ptr = lib.dspsr_amd_reduce_profiles_result(self.handle, C.byref(nf))
         prof = np.ctypeslib.as_array(C.cast(ptr, C.POINTER(C.c_float)), shape=(nf.value,))
         return (prof.copy() if copy else prof), hits, length.value, ndat.value, bool(same.value)
-
-    def close(self):
-        if self.handle and self.ctx.handle:
-            lib.dspsr_amd_comm_destroy(self.handle)
-        self.handle = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass

@@ -732,7 +732,7 @@ static int fb_launch_fused(dspsr_amd_filterbank* fb, k3_t k3, const cf* X, const
   const uint32_t grid = nseg > 1 ? tiles * nseg : grid_for(tiles, wgs);
   hipLaunchKernelGGL(k3, dim3(grid), dim3(two_pass ? 512u : fb->nt3), two_pass ? fb->lds2rf : fb->lds3f, ctx->stream, g, X, kern, co,
                      ctx->tw, part0, ns, ns);
-  if (nseg > 1) return fold_combine_partials(co.fold, fb->fpart, nseg - 1, co.chan0, g.C);
+  if (nseg > 1) return fold_combine_partials(co.fold, "fused fold: combine", fb->fpart, nseg - 1, co.chan0, g.C);
   return DSPSR_AMD_OK;
 }
 

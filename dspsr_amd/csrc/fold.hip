@@ -15,6 +15,7 @@
 
 #include "engine_internal.h"
 #include "fold_internal.h"
+#include "fold_walk.h"
 
 namespace dspsr_amd {
 
@@ -55,8 +56,8 @@ __global__ void k_fold_direct(const float* __restrict__ in, const uint64_t chan_
 // therefore happen in time order, as in Fold.C:844-852.  With few (chan, pol) rows the bins of a row are dealt to
 // gridDim.z workgroups (each streams the whole row: the re-reads come from L2 / Infinity Cache), so that the chip
 // is filled without touching the order of any sum.
-// (FOLD_CHUNK samples per chunk: fold_plan.h, with the host's tables over the same chunk grid)
-constexpr int FOLD_BPT = 4;             // bins per thread (nbin <= FOLD_BPT * blockDim)
+// (FOLD_CHUNK samples per chunk, FOLD_BPT bins per thread: fold_plan.h, with the host's tables and launch shapes; the chunk
+//  stream, the cursor and the adds: fold_walk.h, shared by all kernels below and k_fold_moments)
 // LONG runs.  A sum in strict time order is one dependent chain of float adds per (chan, pol, bin, dim): with phase bins
 // hundreds of samples wide only a couple of chains are alive per row and the kernel is bound by the add latency (10 ms per
 // 4 M samples and row at -F 64:D, profiles/r02j).  When the plan holds a run of FOLD_LONG_RUN samples or more, the host
@@ -66,9 +67,8 @@ constexpr int FOLD_BPT = 4;             // bins per thread (nbin <= FOLD_BPT * b
 // Deterministic, no longer the association of the CPU loop: it agrees with it to float rounding, like the reference's own
 // GPU fold (FoldCUDA.cu:208-269 sums each run from zero and adds the run sums atomically).  The association depends on the
 // plan, the chunk grid and the number of time segments, each summed from zero and added to the profile in segment order by
-// k_fold_combine; the segment count follows from the device's compute units and nchan*npol (fold_fold_impl), so the sums
-// are reproducible on one device and row count, not across them.  Plans of shorter runs keep the exact time-order kernel.
-constexpr uint32_t FOLD_MB = 32;
+// k_fold_combine; the segment count follows from the device's compute units and nchan*npol (fold_plan.h fold_shape), so the
+// sums are reproducible on one device and row count, not across them.  Plans of shorter runs keep the exact time-order kernel.
 
 // NROW: polarisation rows of one channel folded by the same workgroup (detected data with ndim < 4 lie in 4/ndim planes:
 // the walk through the bin plan -- most of the work with 4-byte samples -- then serves all planes; the sums of every
@@ -84,9 +84,9 @@ __global__ __launch_bounds__(1024) void k_fold_chunked(const float* __restrict__
                                                        const uint32_t chunks_per_seg /* LONG: chunks per blockIdx.z */)
 {
   extern __shared__ __attribute__((aligned(16))) float fold_lds[];   // NROW x FOLD_CHUNK * NDIM floats (+ micro-block sums, LONG)
+  typedef FoldImage<NDIM> Img;
+  constexpr uint32_t RS = Img::RS, MS = Img::MS;
   const uint32_t ipol = blockIdx.x * NROW, npol = gridDim.x * NROW, ichan = blockIdx.y;
-  constexpr uint32_t RS = FOLD_CHUNK * NDIM;             // floats per row of the chunk image
-  constexpr uint32_t MS = (FOLD_CHUNK / FOLD_MB) * NDIM;  // micro-block sums per row (LONG)
   const uint32_t tid = threadIdx.x, nt = blockDim.x;
   const float* __restrict__ row = in + ichan * chan_stride + ipol * pol_stride;          // row r: + r * pol_stride
   // LONG: blockIdx.z is a TIME segment of the row (all bins), summed from zero into this segment's partial profile --
@@ -96,41 +96,15 @@ __global__ __launch_bounds__(1024) void k_fold_chunked(const float* __restrict__
                                  : prof + ((uint64_t)ichan * npol + ipol) * prof_span;
   const uint64_t out_rs = LONG ? (uint64_t)nbin * NDIM : prof_span;                        // row r: + r * out_rs
   const uint32_t bz = LONG ? 0u : blockIdx.z, nz = LONG ? 1u : gridDim.z;
-  constexpr uint32_t NF4 = FOLD_CHUNK * NDIM / 4;        // float4 per chunk
-  constexpr uint32_t MAXR = NF4 / 256;                    // float4 per thread at the minimum block size (256)
 
-  // cursor into each owned bin's interval list; the current and the following interval are kept in
-  // registers (loaded long before they are needed) so the chunk loop never waits on global memory
-  uint32_t cur[FOLD_BPT], end[FOLD_BPT];
-  Interval v0[FOLD_BPT], v1[FOLD_BPT];
+  FoldCursor cu[FOLD_BPT];
   float acc[FOLD_BPT][NROW][NDIM];
   bool touched[FOLD_BPT];
-  // "no interval" = offset ~0.  Always load through the global pointer with a clamped index: selecting
-  // between &iv[i] and a local would make the load generic (flat_load + full vmcnt/lgkmcnt drain).
-  auto load_iv = [&](const uint32_t i, const bool valid) -> Interval {
-    Interval t = iv[valid ? i : 0u];
-    if (!valid) { t.offset = ~0ull; t.hits = 0u; }
-    return t;
-  };
 #pragma unroll
   for (int j = 0; j < FOLD_BPT; j++) {
     const uint32_t b = bz + nz * (tid + j * nt);   // bins are dealt to the nz workgroups of a row
-    cur[j] = end[j] = 0;
-    if (b < nbin) { cur[j] = bin_start[b]; end[j] = bin_start[b + 1]; }
-    if constexpr (LONG) {
-      // first interval of the bin that reaches into this segment (intervals are time ordered: binary search)
-      const uint64_t seg0 = first + (uint64_t)blockIdx.z * chunks_per_seg * FOLD_CHUNK;
-      uint32_t lo_i = cur[j], hi_i = end[j];
-      while (lo_i < hi_i) {
-        const uint32_t mid = (lo_i + hi_i) >> 1;
-        const Interval t = iv[mid];
-        if (t.offset + t.hits <= seg0) lo_i = mid + 1; else hi_i = mid;
-      }
-      cur[j] = lo_i;
-    }
-    touched[j] = LONG ? (b < nbin) : (cur[j] != end[j]);
-    v0[j] = load_iv(cur[j], cur[j] < end[j]);
-    v1[j] = load_iv(cur[j] + 1, cur[j] + 1 < end[j]);
+    cu[j].open<LONG>(bin_start, iv, b, b < nbin, first + (uint64_t)blockIdx.z * chunks_per_seg * FOLD_CHUNK);
+    touched[j] = LONG ? (b < nbin) : !cu[j].empty();
 #pragma unroll
     for (int r = 0; r < NROW; r++)
 #pragma unroll
@@ -144,40 +118,12 @@ __global__ __launch_bounds__(1024) void k_fold_chunked(const float* __restrict__
   const uint32_t nchunk_all = (uint32_t)((last - first + FOLD_CHUNK - 1) / FOLD_CHUNK);
   const uint32_t cbeg = LONG ? blockIdx.z * chunks_per_seg : 0u;
   const uint32_t nchunk = LONG ? (cbeg + chunks_per_seg < nchunk_all ? cbeg + chunks_per_seg : nchunk_all) : nchunk_all;
-  float4 pre[NROW][MAXR];
-  auto fetch = [&](uint32_t c) {
-#pragma unroll
-    for (int rw = 0; rw < NROW; rw++) {
-      const float4* __restrict__ src = (const float4*)(src0 + rw * pol_stride);
-#pragma unroll
-      for (uint32_t r = 0; r < MAXR; r++) {
-        const uint32_t q = tid + r * nt;
-        const uint64_t k = (uint64_t)c * NF4 + q;
-        float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (q < NF4) {
-          if (4 * k + 4 <= nfl_total) {
-            v = src[k];
-          } else if (4 * k < nfl_total) {                  // ragged end of the span: never read past it
-            const float* t = (const float*)(src + k);
-            const uint32_t n = (uint32_t)(nfl_total - 4 * k);
-            v.x = t[0];
-            if (n > 1) v.y = t[1];
-            if (n > 2) v.z = t[2];
-          }
-        }
-        pre[rw][r] = v;
-      }
-    }
-  };
-  if (cbeg < nchunk) fetch(cbeg);
+  float4 pre[NROW][Img::MAXR];
+  if (cbeg < nchunk) fold_fetch<Img::NF4>(pre, src0, pol_stride, nfl_total, cbeg, tid, nt);
   for (uint32_t c = cbeg; c < nchunk; c++) {
     __syncthreads();                                    // previous chunk fully consumed
-#pragma unroll
-    for (int rw = 0; rw < NROW; rw++)
-#pragma unroll
-      for (uint32_t r = 0; r < MAXR; r++)
-        if (tid + r * nt < NF4) ((float4*)(fold_lds + rw * RS))[tid + r * nt] = pre[rw][r];
-    if (c + 1 < nchunk) fetch(c + 1);
+    fold_store<Img::NF4>(fold_lds, pre, tid, nt);
+    if (c + 1 < nchunk) fold_fetch<Img::NF4>(pre, src0, pol_stride, nfl_total, c + 1, tid, nt);
     __syncthreads();
     if constexpr (LONG) {                                 // level 1: sums of the aligned micro-blocks of this chunk
       float* mbs = fold_lds + NROW * RS;
@@ -193,69 +139,22 @@ __global__ __launch_bounds__(1024) void k_fold_chunked(const float* __restrict__
     const uint64_t c0 = first + (uint64_t)c * FOLD_CHUNK, c1 = c0 + FOLD_CHUNK;
 #pragma unroll
     for (int j = 0; j < FOLD_BPT; j++) {
-      while (v0[j].offset < c1) {                        // `none` has offset ~0 and ends the walk
-        const Interval v = v0[j];
-        const uint64_t lo = v.offset > c0 ? v.offset : c0;
-        const uint64_t hi = v.offset + v.hits < c1 ? v.offset + v.hits : c1;
-        // index the __shared__ array directly (a generic pointer would turn these into flat loads
-        // whose vmcnt(0) wait also drains the chunk prefetch)
-        const uint32_t x0 = (uint32_t)(lo - c0) * NDIM;
-        const uint32_t n = (uint32_t)(hi - lo);
-        if constexpr (LONG) {
-          const float* mbs = fold_lds + NROW * RS;
-          const uint32_t s0 = (uint32_t)(lo - c0), s1 = s0 + n;                       // samples [s0, s1) of the chunk
-          const uint32_t a0 = (s0 + FOLD_MB - 1) / FOLD_MB * FOLD_MB;                // first micro-block boundary >= s0
-          const uint32_t a1 = s1 / FOLD_MB * FOLD_MB;                                // last boundary <= s1
-          if (a0 >= a1) {                                                            // no whole micro-block inside the run
-#pragma unroll 4
-            for (uint32_t h = s0; h < s1; h++)
-#pragma unroll
-              for (int r = 0; r < NROW; r++)
-#pragma unroll
-                for (int d = 0; d < NDIM; d++) acc[j][r][d] += fold_lds[r * RS + h * NDIM + d];
-          } else {
-#pragma unroll 4
-            for (uint32_t h = s0; h < a0; h++)
-#pragma unroll
-              for (int r = 0; r < NROW; r++)
-#pragma unroll
-                for (int d = 0; d < NDIM; d++) acc[j][r][d] += fold_lds[r * RS + h * NDIM + d];
-#pragma unroll 4
-            for (uint32_t mb = a0 / FOLD_MB; mb < a1 / FOLD_MB; mb++)
-#pragma unroll
-              for (int r = 0; r < NROW; r++)
-#pragma unroll
-                for (int d = 0; d < NDIM; d++) acc[j][r][d] += mbs[r * MS + mb * NDIM + d];
-#pragma unroll 4
-            for (uint32_t h = a1; h < s1; h++)
-#pragma unroll
-              for (int r = 0; r < NROW; r++)
-#pragma unroll
-                for (int d = 0; d < NDIM; d++) acc[j][r][d] += fold_lds[r * RS + h * NDIM + d];
-          }
-        } else {
-#pragma unroll 4
-          for (uint32_t h = 0; h < n; h++)
-#pragma unroll
-            for (int r = 0; r < NROW; r++)
-#pragma unroll
-              for (int d = 0; d < NDIM; d++) acc[j][r][d] += fold_lds[r * RS + x0 + h * NDIM + d];
-        }
-        if (v.offset + v.hits > c1) break;               // interval continues in the next chunk (or segment)
-        cur[j]++;
-        v0[j] = v1[j];
-        v1[j] = load_iv(cur[j] + 1, cur[j] + 1 < end[j]);
+      while (cu[j].before(c1)) {
+        uint32_t s0, n;
+        cu[j].clip(c0, c1, s0, n);
+        if constexpr (LONG)
+          fold_long_piece(s0, s0 + n, [&](const uint32_t h0, const uint32_t h1) { fold_run_add<RS>(acc[j], fold_lds, h0, h1 - h0); },
+                          [&](const uint32_t m0, const uint32_t m1) { fold_run_add<MS>(acc[j], fold_lds + NROW * RS, m0, m1 - m0); });
+        else
+          fold_run_add<RS>(acc[j], fold_lds, s0, n);
+        if (!cu[j].advance(iv, c1)) break;
       }
     }
   }
 #pragma unroll
   for (int j = 0; j < FOLD_BPT; j++) {
     const uint32_t b = bz + nz * (tid + j * nt);
-    if (b < nbin && touched[j])
-#pragma unroll
-      for (int r = 0; r < NROW; r++)
-#pragma unroll
-        for (int d = 0; d < NDIM; d++) out[r * out_rs + b * NDIM + d] = acc[j][r][d];
+    if (b < nbin && touched[j]) fold_acc_store(acc[j], out, out_rs, b * NDIM);
   }
 }
 
@@ -277,14 +176,12 @@ __global__ __launch_bounds__(1024) void k_fold_dense(const float* __restrict__ i
                                                      const uint32_t* __restrict__ tab, const uint64_t first, const uint64_t last)
 {
   extern __shared__ __attribute__((aligned(16))) float fold_lds[];   // NROW x FOLD_CHUNK * NDIM floats
+  typedef FoldImage<NDIM> Img;
   const uint32_t ipol = blockIdx.x * NROW, npol = gridDim.x * NROW, ichan = blockIdx.y;
-  constexpr uint32_t RS = FOLD_CHUNK * NDIM;
   const uint32_t tid = threadIdx.x, nt = blockDim.x;
   const float* __restrict__ row = in + ichan * chan_stride + ipol * pol_stride;
   float* __restrict__ out = prof + ((uint64_t)ichan * npol + ipol) * prof_span;
   const uint32_t bz = blockIdx.z, nz = gridDim.z;
-  constexpr uint32_t NF4 = FOLD_CHUNK * NDIM / 4;
-  constexpr uint32_t MAXR = NF4 / 256;
   uint32_t bin[FOLD_BPT];
   float acc[FOLD_BPT][NROW][NDIM];
 #pragma unroll
@@ -298,31 +195,10 @@ __global__ __launch_bounds__(1024) void k_fold_dense(const float* __restrict__ i
   const float* __restrict__ src0 = row + first * NDIM;
   const uint64_t nfl_total = (last - first) * NDIM;
   const uint32_t nchunk = (uint32_t)((last - first + FOLD_CHUNK - 1) / FOLD_CHUNK);
-  float4 pre[NROW][MAXR];
+  float4 pre[NROW][Img::MAXR];
   uint32_t tabn[FOLD_BPT];
-  auto fetch = [&](const uint32_t c) {
-#pragma unroll
-    for (int rw = 0; rw < NROW; rw++) {
-      const float4* __restrict__ src = (const float4*)(src0 + rw * pol_stride);
-#pragma unroll
-      for (uint32_t r = 0; r < MAXR; r++) {
-        const uint32_t q = tid + r * nt;
-        const uint64_t k = (uint64_t)c * NF4 + q;
-        float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (q < NF4) {
-          if (4 * k + 4 <= nfl_total) {
-            v = src[k];
-          } else if (4 * k < nfl_total) {                  // ragged end of the span: never read past it
-            const float* t = (const float*)(src + k);
-            const uint32_t n = (uint32_t)(nfl_total - 4 * k);
-            v.x = t[0];
-            if (n > 1) v.y = t[1];
-            if (n > 2) v.z = t[2];
-          }
-        }
-        pre[rw][r] = v;
-      }
-    }
+  auto fetch = [&](const uint32_t c) {                    // a chunk and, travelling with it, the thread's table entries for it
+    fold_fetch<Img::NF4>(pre, src0, pol_stride, nfl_total, c, tid, nt);
     const uint32_t* __restrict__ tc = tab + (uint64_t)c * nbin;
 #pragma unroll
     for (int j = 0; j < FOLD_BPT; j++) tabn[j] = bin[j] < nbin ? tc[bin[j]] : 0u;
@@ -330,34 +206,18 @@ __global__ __launch_bounds__(1024) void k_fold_dense(const float* __restrict__ i
   if (nchunk) fetch(0);
   for (uint32_t c = 0; c < nchunk; c++) {
     __syncthreads();                                    // previous chunk fully consumed
-#pragma unroll
-    for (int rw = 0; rw < NROW; rw++)
-#pragma unroll
-      for (uint32_t r = 0; r < MAXR; r++)
-        if (tid + r * nt < NF4) ((float4*)(fold_lds + rw * RS))[tid + r * nt] = pre[rw][r];
+    fold_store<Img::NF4>(fold_lds, pre, tid, nt);
     uint32_t tabc[FOLD_BPT];
 #pragma unroll
     for (int j = 0; j < FOLD_BPT; j++) tabc[j] = tabn[j];
     if (c + 1 < nchunk) fetch(c + 1);
     __syncthreads();
 #pragma unroll
-    for (int j = 0; j < FOLD_BPT; j++) {
-      const uint32_t n = tabc[j] >> 11, x0 = (tabc[j] & 2047u) * NDIM;
-#pragma unroll 4
-      for (uint32_t h = 0; h < n; h++)
-#pragma unroll
-        for (int r = 0; r < NROW; r++)
-#pragma unroll
-          for (int d = 0; d < NDIM; d++) acc[j][r][d] += fold_lds[r * RS + x0 + h * NDIM + d];
-    }
+    for (int j = 0; j < FOLD_BPT; j++) fold_dense_add<Img::RS>(acc[j], fold_lds, tabc[j]);
   }
 #pragma unroll
   for (int j = 0; j < FOLD_BPT; j++)
-    if (bin[j] < nbin)
-#pragma unroll
-      for (int r = 0; r < NROW; r++)
-#pragma unroll
-        for (int d = 0; d < NDIM; d++) out[r * prof_span + bin[j] * NDIM + d] = acc[j][r][d];
+    if (bin[j] < nbin) fold_acc_store(acc[j], out, prof_span, bin[j] * NDIM);
 }
 
 // Several plans over the SAME detected rows (dspsr_amd_fold_fold_many: one Fold per pulsar, LoadToFold1.C:939-960).  Each
@@ -382,12 +242,11 @@ struct FoldManyPlan {
 struct FoldManyArgs { FoldManyPlan p[FOLD_MANY_MAX]; uint32_t nplan, nslot; };
 // (pointers read from LDS are generic: cast to the global address space, or the loads become flat loads whose waits also drain
 //  LDS traffic)
-typedef __attribute__((address_space(1))) const uint64_t* GlobalU64;
+typedef __attribute__((address_space(1))) const Interval* GlobalIv;
 typedef __attribute__((address_space(1))) const uint32_t* GlobalU32;
 
-// (512 threads at most: with FOLD_BPT slots of cursor, table entry and accumulators per thread the 128 VGPRs of a 1024-thread
-//  workgroup spill; a group of many bins takes more workgroups per row instead)
-constexpr uint32_t FOLD_MANY_THREADS = 512;
+// (FOLD_MANY_THREADS = 512 threads at most, fold_plan.h: with FOLD_BPT slots of cursor, table entry and accumulators per thread
+//  the 128 VGPRs of a 1024-thread workgroup spill; a group of many bins takes more workgroups per row instead)
 template <int NDIM, int NROW>
 __global__ __launch_bounds__(FOLD_MANY_THREADS) void k_fold_many(const float* __restrict__ in, const uint64_t chan_stride,
                                                     const uint64_t pol_stride, const FoldManyArgs a, const uint64_t first,
@@ -397,31 +256,21 @@ __global__ __launch_bounds__(FOLD_MANY_THREADS) void k_fold_many(const float* __
   // the plan descriptors, copied once from the kernel arguments with constant indices (a divergent index into the
   // argument struct could make the compiler copy it to scratch); a slot's plan is then an LDS read away
   __shared__ FoldManyPlan desc[FOLD_MANY_MAX];
+  typedef FoldImage<NDIM> Img;
   const uint32_t bz = blockIdx.x, nz = gridDim.x;
   const uint32_t ipol = blockIdx.y * NROW, npol = gridDim.y * NROW, ichan = blockIdx.z;
-  constexpr uint32_t RS = FOLD_CHUNK * NDIM;
   const uint32_t tid = threadIdx.x, nt = blockDim.x;
   const float* __restrict__ row = in + ichan * chan_stride + ipol * pol_stride;
-  constexpr uint32_t NF4 = FOLD_CHUNK * NDIM / 4;
-  constexpr uint32_t MAXR = NF4 / 256;
   if (tid == 0) {
 #pragma unroll
     for (uint32_t k = 0; k < FOLD_MANY_MAX; k++) desc[k] = a.p[k];
   }
   __syncthreads();
   // per owned slot: plan k and bin b (k = FOLD_MANY_MAX: no slot), the walk cursor, the dense table entry
-  uint32_t pk[FOLD_BPT], bin[FOLD_BPT], cur[FOLD_BPT], end[FOLD_BPT], tabn[FOLD_BPT];
-  Interval v0[FOLD_BPT], v1[FOLD_BPT];
+  uint32_t pk[FOLD_BPT], bin[FOLD_BPT], tabn[FOLD_BPT];
+  FoldCursor cu[FOLD_BPT];
   float acc[FOLD_BPT][NROW][NDIM];
   bool touched[FOLD_BPT];
-  auto load_iv = [&](const uint32_t k, const uint32_t i, const bool valid) -> Interval {
-    const GlobalU64 p = (GlobalU64)desc[k].iv + 2 * (valid ? i : 0u);   // Interval = {offset, hits | pad << 32}
-    Interval t;
-    t.offset = valid ? p[0] : ~0ull;
-    t.hits = valid ? (uint32_t)p[1] : 0u;
-    t.pad = 0;
-    return t;
-  };
 #pragma unroll
   for (int j = 0; j < FOLD_BPT; j++) {
     const uint32_t s = bz + nz * (tid + j * nt);
@@ -431,18 +280,11 @@ __global__ __launch_bounds__(FOLD_MANY_THREADS) void k_fold_many(const float* __
       if (q < a.nplan && s >= a.p[q].slot0 && s < a.nslot) k = q;      // (slot0 ascending)
     pk[j] = k;
     bin[j] = k < FOLD_MANY_MAX ? s - desc[k].slot0 : 0u;
-    cur[j] = end[j] = 0;
     tabn[j] = 0;
     const bool dense = k < FOLD_MANY_MAX && desc[k].tab;
-    if (k < FOLD_MANY_MAX && !dense) {
-      const GlobalU32 bs = (GlobalU32)desc[k].bin_start;
-      cur[j] = bs[bin[j]];
-      end[j] = bs[bin[j] + 1];
-    }
-    touched[j] = dense || cur[j] != end[j];
     const uint32_t kk = k < FOLD_MANY_MAX ? k : 0u;
-    v0[j] = load_iv(kk, cur[j], cur[j] < end[j]);
-    v1[j] = load_iv(kk, cur[j] + 1, cur[j] + 1 < end[j]);
+    cu[j].open<false>((GlobalU32)desc[kk].bin_start, (GlobalIv)desc[kk].iv, bin[j], k < FOLD_MANY_MAX && !dense, 0);
+    touched[j] = dense || !cu[j].empty();
     const float* __restrict__ out = touched[j] ? desc[k].prof + ((uint64_t)ichan * npol + ipol) * desc[k].span : nullptr;
 #pragma unroll
     for (int r = 0; r < NROW; r++)
@@ -452,30 +294,9 @@ __global__ __launch_bounds__(FOLD_MANY_THREADS) void k_fold_many(const float* __
   const float* __restrict__ src0 = row + first * NDIM;
   const uint64_t nfl_total = (last - first) * NDIM;
   const uint32_t nchunk = (uint32_t)((last - first + FOLD_CHUNK - 1) / FOLD_CHUNK);
-  float4 pre[NROW][MAXR];
-  auto fetch = [&](const uint32_t c) {
-#pragma unroll
-    for (int rw = 0; rw < NROW; rw++) {
-      const float4* __restrict__ src = (const float4*)(src0 + rw * pol_stride);
-#pragma unroll
-      for (uint32_t r = 0; r < MAXR; r++) {
-        const uint32_t q = tid + r * nt;
-        const uint64_t k = (uint64_t)c * NF4 + q;
-        float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (q < NF4) {
-          if (4 * k + 4 <= nfl_total) {
-            v = src[k];
-          } else if (4 * k < nfl_total) {                  // ragged end of the span: never read past it
-            const float* t = (const float*)(src + k);
-            const uint32_t n = (uint32_t)(nfl_total - 4 * k);
-            v.x = t[0];
-            if (n > 1) v.y = t[1];
-            if (n > 2) v.z = t[2];
-          }
-        }
-        pre[rw][r] = v;
-      }
-    }
+  float4 pre[NROW][Img::MAXR];
+  auto fetch = [&](const uint32_t c) {                    // a chunk and, travelling with it, the dense slots' table entries for it
+    fold_fetch<Img::NF4>(pre, src0, pol_stride, nfl_total, c, tid, nt);
 #pragma unroll
     for (int j = 0; j < FOLD_BPT; j++) {
       const bool dense = pk[j] < FOLD_MANY_MAX && desc[pk[j]].tab;
@@ -485,11 +306,14 @@ __global__ __launch_bounds__(FOLD_MANY_THREADS) void k_fold_many(const float* __
   if (nchunk) fetch(0);
   for (uint32_t c = 0; c < nchunk; c++) {
     __syncthreads();                                    // previous chunk fully consumed
+    // (fold_walk.h's fold_store, written out: called as a function here, k_fold_many<4, 1> copies one prefetched float4 right behind
+    //  its load, and the s_waitcnt vmcnt(0) in front of the copy drains the whole prefetch in every chunk: 7 % at 128 channels x 2^20
+    //  samples, profiles/HISTORY.md)
 #pragma unroll
     for (int rw = 0; rw < NROW; rw++)
 #pragma unroll
-      for (uint32_t r = 0; r < MAXR; r++)
-        if (tid + r * nt < NF4) ((float4*)(fold_lds + rw * RS))[tid + r * nt] = pre[rw][r];
+      for (uint32_t r = 0; r < Img::MAXR; r++)
+        if (tid + r * nt < Img::NF4) ((float4*)(fold_lds + rw * Img::RS))[tid + r * nt] = pre[rw][r];
     uint32_t tabc[FOLD_BPT];
 #pragma unroll
     for (int j = 0; j < FOLD_BPT; j++) tabc[j] = tabn[j];
@@ -498,31 +322,12 @@ __global__ __launch_bounds__(FOLD_MANY_THREADS) void k_fold_many(const float* __
     const uint64_t c0 = first + (uint64_t)c * FOLD_CHUNK, c1 = c0 + FOLD_CHUNK;
 #pragma unroll
     for (int j = 0; j < FOLD_BPT; j++) {
-      {                                                 // dense slot: at most one run in this chunk
-        const uint32_t n = tabc[j] >> 11, x0 = (tabc[j] & 2047u) * NDIM;
-#pragma unroll 4
-        for (uint32_t h = 0; h < n; h++)
-#pragma unroll
-          for (int r = 0; r < NROW; r++)
-#pragma unroll
-            for (int d = 0; d < NDIM; d++) acc[j][r][d] += fold_lds[r * RS + x0 + h * NDIM + d];
-      }
-      while (v0[j].offset < c1) {                       // walk slot (`none` has offset ~0 and ends the walk)
-        const Interval v = v0[j];
-        const uint64_t lo = v.offset > c0 ? v.offset : c0;
-        const uint64_t hi = v.offset + v.hits < c1 ? v.offset + v.hits : c1;
-        const uint32_t x0 = (uint32_t)(lo - c0) * NDIM;
-        const uint32_t n = (uint32_t)(hi - lo);
-#pragma unroll 4
-        for (uint32_t h = 0; h < n; h++)
-#pragma unroll
-          for (int r = 0; r < NROW; r++)
-#pragma unroll
-            for (int d = 0; d < NDIM; d++) acc[j][r][d] += fold_lds[r * RS + x0 + h * NDIM + d];
-        if (v.offset + v.hits > c1) break;              // the interval continues in the next chunk
-        cur[j]++;
-        v0[j] = v1[j];
-        v1[j] = load_iv(pk[j], cur[j] + 1, cur[j] + 1 < end[j]);
+      fold_dense_add<Img::RS>(acc[j], fold_lds, tabc[j]);  // dense slot: at most one run in this chunk (walk slot: entry 0, nothing)
+      while (cu[j].before(c1)) {              // walk slot
+        uint32_t s0, n;
+        cu[j].clip(c0, c1, s0, n);
+        fold_run_add<Img::RS>(acc[j], fold_lds, s0, n);
+        if (!cu[j].advance((GlobalIv)desc[pk[j]].iv, c1)) break;
       }
     }
   }
@@ -530,11 +335,7 @@ __global__ __launch_bounds__(FOLD_MANY_THREADS) void k_fold_many(const float* __
   for (int j = 0; j < FOLD_BPT; j++) {
     if (!touched[j]) continue;
     const uint32_t k = pk[j];
-    float* __restrict__ out = desc[k].prof + ((uint64_t)ichan * npol + ipol) * desc[k].span;
-#pragma unroll
-    for (int r = 0; r < NROW; r++)
-#pragma unroll
-      for (int d = 0; d < NDIM; d++) out[r * desc[k].span + bin[j] * NDIM + d] = acc[j][r][d];
+    fold_acc_store(acc[j], desc[k].prof + ((uint64_t)ichan * npol + ipol) * desc[k].span, desc[k].span, bin[j] * NDIM);
   }
 }
 
@@ -1037,6 +838,19 @@ int fold_plan_to_device(dspsr_amd_fold* f, const char* who, PlanSlot** slot, uin
   return DSPSR_AMD_OK;
 }
 
+// The instantiations <ND, NR> of the chunk kernels (floats per sample, rows per workgroup: fold_plan.h FoldShape nd, nr): fn is
+// called with the pair as a type.
+template <int ND, int NR> struct FoldInstance { static constexpr int nd = ND, nr = NR; };
+template <class Fn>
+static void fold_instance(uint32_t ndim, uint32_t nrw, Fn&& fn)
+{
+  if (ndim == 4) fn(FoldInstance<4, 1>());
+  else if (ndim == 2 && nrw == 2) fn(FoldInstance<2, 2>());
+  else if (ndim == 2) fn(FoldInstance<2, 1>());
+  else if (nrw == 4) fn(FoldInstance<1, 4>());
+  else fn(FoldInstance<1, 1>());
+}
+
 static int fold_fold_impl(dspsr_amd_fold* f, const float* in_dev, uint64_t in_chan_stride, uint64_t in_pol_stride,
                           uint32_t* hits_dev);
 
@@ -1073,84 +887,35 @@ static int fold_fold_impl(dspsr_amd_fold* f, const float* in_dev, uint64_t in_ch
   plan_span(f, &first, &last);
   first -= first % 4;                                  // keeps 16-byte alignment of the chunk loads for any ndim
   const bool aligned = ((uintptr_t)in_dev % 16 == 0) && (in_chan_stride % 4 == 0) && (in_pol_stride % 4 == 0);
-  const bool chunked = aligned && nbin <= (uint32_t)FOLD_BPT * 1024;     // else k_fold_direct
   SentPlan sp;
-  const int rc = plan_send(f, "dspsr_amd_fold_fold", first, last, chunked, hits_dev != nullptr, &sp);
+  int rc = plan_send(f, "dspsr_amd_fold_fold", first, last, fold_takes_chunks(aligned, nbin), hits_dev != nullptr, &sp);
   if (rc != DSPSR_AMD_OK) return rc;
   PlanSlot& sl = *sp.slot;
-  const bool lng = chunked && sp.max_run >= FOLD_LONG_RUN;               // re-associated sums (see FOLD_LONG_RUN)
-  const bool dense = sp.dense;
-  const uint32_t nrow = f->npol * f->nchan;
-  // exact mode: rows x bin groups, at least two workgroups per CU when the band has few channels
-  uint32_t nsplit = 1;
-  if (!lng)
-    while (nsplit < 8 && (uint64_t)nrow * nsplit < 512 && nbin / (2 * nsplit) >= 64) nsplit *= 2;
-  uint32_t threads = nbin < 1024 ? ((nbin + 63) / 64) * 64 : 1024;
-  if (chunked) {
-    // FOLD_BPT bins per thread: 256-thread workgroups for nbin <= 1024, so that four of them share a CU and
-    // keep 4 x 32 KiB of chunk loads in flight (the kernel is HBM-latency bound per workgroup)
-    const uint32_t bins_wg = (nbin + nsplit - 1) / nsplit;
-    threads = ((bins_wg + FOLD_BPT - 1) / FOLD_BPT + 63) / 64 * 64;
-    if (threads < 256) threads = 256;
-    if (threads > 1024) threads = 1024;
-    // LONG: rows x time segments (about four workgroups per CU), every sample read once
-    const uint32_t nchunk = (uint32_t)((last - first + FOLD_CHUNK - 1) / FOLD_CHUNK);
-    uint32_t nseg = 1, cps = nchunk;
-    if (lng) {
-      nseg = (4 * ctx->ncu + nrow - 1) / nrow;
-      if (nseg > nchunk) nseg = nchunk;
-      if (nseg > 65535) nseg = 65535;
-      if (nseg < 1) nseg = 1;
-      cps = (nchunk + nseg - 1) / nseg;
-      nseg = (nchunk + cps - 1) / cps;
-      const size_t need = (size_t)nseg * nrow * nbin * f->ndim;
-      if (!grow_device_buffer(ctx->stream, f->part, f->part_floats, need))
-        return ctx_fail(ctx, DSPSR_AMD_ENOMEM, "dspsr_amd_fold_fold: hipMalloc of %zu partial-sum floats failed", need);
-    }
-    // planes of one channel folded together (ndim < 4): 4 or 2 rows per workgroup when the channels alone fill the chip
-    // (one row per workgroup at Benchmark/fold.csh's shape, four times the workgroups: 311-313 against 321-331 Msamples/s, same box)
-    const uint32_t nrw = (f->ndim * f->npol == 4 && f->ndim < 4 && (uint64_t)f->nchan * (lng ? nseg : nsplit) >= 2 * ctx->ncu)
-                             ? f->npol : 1u;
-    dim3 grid(f->npol / nrw, f->nchan, lng ? nseg : nsplit);
-    const size_t lds = ((size_t)FOLD_CHUNK + (lng ? FOLD_CHUNK / FOLD_MB : 0)) * f->ndim * nrw * sizeof(float);
-#define FOLD_DENSE(ND, NR) hipLaunchKernelGGL((k_fold_dense<ND, NR>), grid, dim3(threads), lds, ctx->stream, in_dev, in_chan_stride, \
-                                             in_pol_stride, f->profile, f->span, nbin, sl.d_aux, first, last)
-#define FOLD_LAUNCH(ND, LG, NR) hipLaunchKernelGGL((k_fold_chunked<ND, LG, NR>), grid, dim3(threads), lds, ctx->stream, in_dev, \
-                                               in_chan_stride, in_pol_stride, f->profile, f->span, nbin, sl.d_bin_start, sl.d_iv, first, last, \
-                                               f->part, cps)
-    if (dense) {
-      if (f->ndim == 4) FOLD_DENSE(4, 1);
-      else if (f->ndim == 2 && nrw == 2) FOLD_DENSE(2, 2);
-      else if (f->ndim == 2) FOLD_DENSE(2, 1);
-      else if (nrw == 4) FOLD_DENSE(1, 4);
-      else FOLD_DENSE(1, 1);
-    } else
-    if (f->ndim == 4) { if (lng) FOLD_LAUNCH(4, true, 1); else FOLD_LAUNCH(4, false, 1); }
-    else if (f->ndim == 2 && nrw == 2) { if (lng) FOLD_LAUNCH(2, true, 2); else FOLD_LAUNCH(2, false, 2); }
-    else if (f->ndim == 2) { if (lng) FOLD_LAUNCH(2, true, 1); else FOLD_LAUNCH(2, false, 1); }
-    else if (nrw == 4) { if (lng) FOLD_LAUNCH(1, true, 4); else FOLD_LAUNCH(1, false, 4); }
-    else { if (lng) FOLD_LAUNCH(1, true, 1); else FOLD_LAUNCH(1, false, 1); }
-#undef FOLD_LAUNCH
-#undef FOLD_DENSE
-    if (lng) {
-      const uint64_t n = (uint64_t)nrow * nbin * f->ndim;
-      uint32_t gx = (uint32_t)((n + 255) / 256);
-      if (gx > 4 * ctx->ncu) gx = 4 * ctx->ncu;
-      hipLaunchKernelGGL(k_fold_combine, dim3(gx), dim3(256), 0, ctx->stream, f->profile, f->span, f->part, nrow, nbin * f->ndim, nseg);
-    }
-  } else {
-    dim3 grid(f->npol, f->nchan, nsplit);
-    if (f->ndim == 4)
-      hipLaunchKernelGGL(k_fold_direct<4>, grid, dim3(threads), 0, ctx->stream, in_dev, in_chan_stride,
-                         in_pol_stride, f->profile, f->span, nbin, sl.d_bin_start, sl.d_iv);
-    else if (f->ndim == 2)
-      hipLaunchKernelGGL(k_fold_direct<2>, grid, dim3(threads), 0, ctx->stream, in_dev, in_chan_stride,
-                         in_pol_stride, f->profile, f->span, nbin, sl.d_bin_start, sl.d_iv);
-    else
-      hipLaunchKernelGGL(k_fold_direct<1>, grid, dim3(threads), 0, ctx->stream, in_dev, in_chan_stride,
-                         in_pol_stride, f->profile, f->span, nbin, sl.d_bin_start, sl.d_iv);
+  const FoldShape s = fold_shape(aligned, f->nchan, f->npol, f->ndim, nbin, first, last, sp.max_run, sp.dense, ctx->ncu);
+  if (s.family == FOLD_LONG) {
+    const size_t need = (size_t)s.nseg * f->npol * f->nchan * nbin * f->ndim;
+    if (!grow_device_buffer(ctx->stream, f->part, f->part_floats, need))
+      return ctx_fail(ctx, DSPSR_AMD_ENOMEM, "dspsr_amd_fold_fold: hipMalloc of %zu partial-sum floats failed", need);
   }
-  if (hits_dev)      // per-channel hits of a zeroed input: polarisation 0, first float of every planned sample
+  const dim3 grid(s.grid[0], s.grid[1], s.grid[2]), block(s.threads);
+  const uint32_t cps = (uint32_t)s.seg_len;
+  fold_instance(s.nd, s.nr, [&](auto inst) {
+    constexpr int ND = decltype(inst)::nd, NR = decltype(inst)::nr;
+    if (s.family == FOLD_DIRECT)                           // (NR is 1)
+      hipLaunchKernelGGL(k_fold_direct<ND>, grid, block, 0, ctx->stream, in_dev, in_chan_stride, in_pol_stride, f->profile, f->span,
+                         nbin, sl.d_bin_start, sl.d_iv);
+    else if (s.family == FOLD_DENSE)
+      hipLaunchKernelGGL((k_fold_dense<ND, NR>), grid, block, s.lds, ctx->stream, in_dev, in_chan_stride, in_pol_stride, f->profile,
+                         f->span, nbin, sl.d_aux, first, last);
+    else if (s.family == FOLD_LONG)
+      hipLaunchKernelGGL((k_fold_chunked<ND, true, NR>), grid, block, s.lds, ctx->stream, in_dev, in_chan_stride, in_pol_stride,
+                         f->profile, f->span, nbin, sl.d_bin_start, sl.d_iv, first, last, f->part, cps);
+    else
+      hipLaunchKernelGGL((k_fold_chunked<ND, false, NR>), grid, block, s.lds, ctx->stream, in_dev, in_chan_stride, in_pol_stride,
+                         f->profile, f->span, nbin, sl.d_bin_start, sl.d_iv, first, last, f->part, cps);
+  });
+  if (s.family == FOLD_LONG && (rc = fold_combine_partials(f, "dspsr_amd_fold_fold", f->part, s.nseg, 0, f->nchan)) != DSPSR_AMD_OK) return rc;
+  if (hits_dev)     // per-channel hits of a zeroed input: polarisation 0, first float of every planned sample
     hipLaunchKernelGGL(k_fold_count_hits, dim3((nbin + 255) / 256, f->nchan), dim3(256), 0, ctx->stream, in_dev, in_chan_stride, f->ndim,
                        hits_dev, nbin, sl.d_bin_start, sl.d_iv);
   const hipError_t e = hipGetLastError();
@@ -1203,29 +968,11 @@ static int fold_many_group(dspsr_amd_fold* const* g, uint32_t n, const float* in
   }
   args.nplan = n;
   args.nslot = nslot;
-  // slots dealt to nz workgroups per row: enough for FOLD_BPT slots per thread, and (as fold_fold_impl splits the bins) at least
-  // two workgroups per CU when the band has few rows.  Siblings of a row are neighbours in blockIdx.x and run at the same time,
-  // so that the re-reads of its chunks come from the Infinity Cache.
-  const uint32_t nrow = f0->npol * f0->nchan;
-  uint32_t nz = 1;
-  while ((uint64_t)nz * FOLD_BPT * FOLD_MANY_THREADS < nslot) nz *= 2;
-  while (nz < 8 && (uint64_t)nrow * nz < 512 && nslot / (2 * nz) >= 64) nz *= 2;
-  const uint32_t slots_wg = (nslot + nz - 1) / nz;
-  uint32_t threads = ((slots_wg + FOLD_BPT - 1) / FOLD_BPT + 63) / 64 * 64;
-  if (threads < 256) threads = 256;
-  if (threads > FOLD_MANY_THREADS) threads = FOLD_MANY_THREADS;
-  const uint32_t ndim = f0->ndim, npol = f0->npol;
-  const uint32_t nrw = (ndim * npol == 4 && ndim < 4 && (uint64_t)f0->nchan * nz >= 2 * ctx->ncu) ? npol : 1u;
-  const dim3 grid(nz, npol / nrw, f0->nchan);
-  const size_t lds = (size_t)FOLD_CHUNK * ndim * nrw * sizeof(float);
-#define FOLD_MANY(ND, NR) hipLaunchKernelGGL((k_fold_many<ND, NR>), grid, dim3(threads), lds, ctx->stream, in_dev, in_chan_stride, \
-                                            in_pol_stride, args, first, last)
-  if (ndim == 4) FOLD_MANY(4, 1);
-  else if (ndim == 2 && nrw == 2) FOLD_MANY(2, 2);
-  else if (ndim == 2) FOLD_MANY(2, 1);
-  else if (nrw == 4) FOLD_MANY(1, 4);
-  else FOLD_MANY(1, 1);
-#undef FOLD_MANY
+  const FoldShape s = fold_many_shape(f0->nchan, f0->npol, f0->ndim, nslot, ctx->ncu);
+  fold_instance(s.nd, s.nr, [&](auto inst) {
+    hipLaunchKernelGGL((k_fold_many<decltype(inst)::nd, decltype(inst)::nr>), dim3(s.grid[0], s.grid[1], s.grid[2]), dim3(s.threads),
+                       s.lds, ctx->stream, in_dev, in_chan_stride, in_pol_stride, args, first, last);
+  });
   const hipError_t e = hipGetLastError();
   if (e != hipSuccess) return ctx_fail(ctx, DSPSR_AMD_EHIP, "dspsr_amd_fold_fold_many: %s", hipGetErrorString(e));
   for (uint32_t k = 0; k < n; k++) {
@@ -1265,7 +1012,7 @@ extern "C" int dspsr_amd_fold_fold_many(dspsr_amd_fold* const* folds, uint32_t n
   for (uint32_t i = 0; i < nfold; i++) {
     dspsr_amd_fold* f = folds[i];
     if (f->binplan.empty()) continue;
-    if (aligned && f->nbin <= (uint32_t)FOLD_BPT * 1024 && fold_plan_max_run(f) < FOLD_LONG_RUN) {
+    if (fold_takes_chunks(aligned, f->nbin) && fold_plan_max_run(f) < FOLD_LONG_RUN) {
       shared.push_back(f);
       continue;
     }
@@ -1327,7 +1074,7 @@ int fold_build_part_plan(dspsr_amd_fold* f, uint32_t nkeep, uint32_t npart, cons
   return DSPSR_AMD_OK;
 }
 
-int fold_combine_partials(dspsr_amd_fold* f, const float* part, uint32_t nseg, uint32_t chan0, uint32_t nchan)
+int fold_combine_partials(dspsr_amd_fold* f, const char* who, const float* part, uint32_t nseg, uint32_t chan0, uint32_t nchan)
 {
   // profile rows [chan0, chan0 + nchan) += partial profiles of the runs 1 .. nseg of a segmented fused launch (packed
   // [seg][chan - chan0][nbin][ndim], npol 1), in run order
@@ -1338,7 +1085,7 @@ int fold_combine_partials(dspsr_amd_fold* f, const float* part, uint32_t nseg, u
   hipLaunchKernelGGL(k_fold_combine, dim3(gx), dim3(256), 0, f->ctx->stream, f->profile + (uint64_t)chan0 * f->npol * f->span, f->span,
                      part, nrow, f->nbin * f->ndim, nseg);
   const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return ctx_fail(f->ctx, DSPSR_AMD_EHIP, "fused fold: combine: %s", hipGetErrorString(e));
+  if (e != hipSuccess) return ctx_fail(f->ctx, DSPSR_AMD_EHIP, "%s: %s", who, hipGetErrorString(e));
   return DSPSR_AMD_OK;
 }
 

@@ -83,8 +83,9 @@ int fold_build_segment_plan(dspsr_amd_fold* f, uint64_t ndat, uint32_t seg, bool
 //   `tile` = output positions tile*Tt + (t2 << logMa) ...); nkeep / nfilt_pos: the kept window of a part
 int fold_segment_combine(dspsr_amd_fold* f, const float* msum, uint32_t chan0, uint32_t nchan, uint32_t npart, uint32_t nkeep,
                          uint32_t nfilt_pos, int logTt, int logMa, int logMb, const uint32_t* d_bin_start, const dspsr_amd::Interval* d_iv);
-// profile += sum of `nseg` partial profiles (packed [seg][chan][npol][nbin][ndim]) in order: segmented fused launches
-int fold_combine_partials(dspsr_amd_fold* f, const float* part, uint32_t nseg, uint32_t chan0, uint32_t nchan);
+// profile += sum of `nseg` partial profiles (packed [seg][chan][npol][nbin][ndim]) in order: segmented fused launches, the LONG
+// folds; `who` names the caller in the text of a launch error (it also reports the error of a launch just in front of it)
+int fold_combine_partials(dspsr_amd_fold* f, const char* who, const float* part, uint32_t nseg, uint32_t chan0, uint32_t nchan);
 
 // Fourth moments (fold_moments.hip).  fold_plan_to_device: the pending plan closed, bucketed by phase bin (bin_start / iv of
 // *slot, as for k_fold_chunked) and uploaded; [*first, *last) its sample span with *first rounded down to a multiple of 4,

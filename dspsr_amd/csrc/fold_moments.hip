@@ -26,6 +26,7 @@
 
 #include "engine_internal.h"
 #include "fold_internal.h"
+#include "fold_walk.h"
 
 namespace dspsr_amd {
 
@@ -35,8 +36,9 @@ constexpr uint32_t MOM_THREADS = 256;         // one workgroup: 4 waves, one per
 // values of the sample in flight, two bins stay near 100 VGPRs -- four workgroups per CU by registers and by LDS (4 x 36 KiB
 // of 160) -- where four bins would take 60 more and halve that.  A row's bins beyond 512 go to further workgroups.
 constexpr int MOM_BPT = 2;
-constexpr uint32_t MOM_MB = 32;               // micro-block of the LONG association (fold.hip FOLD_MB)
-constexpr uint32_t MOM_SEG_UNIT = 2048;       // LONG time segments are multiples of it (fold.hip FOLD_CHUNK)
+constexpr uint32_t MOM_MB = 32;               // micro-block of the LONG association
+constexpr uint32_t MOM_SEG_UNIT = 2048;       // LONG time segments are multiples of it
+static_assert(MOM_MB == FOLD_MB && MOM_SEG_UNIT == FOLD_CHUNK, "the LONG association is fold.hip's (fold_walk.h fold_long_piece, fold_plan.h)");
 constexpr uint32_t MOM_CHUNK_STOKES = 2048;   // samples per chunk image: 32 KiB of ndim 4 ...
 constexpr uint32_t MOM_CHUNK_STREAM = 512;    // ... 28 KiB of ndim 14
 constexpr uint32_t MOM_FM_SAMPLES = 256;      // k_fourth_moment: samples per workgroup
@@ -127,7 +129,9 @@ __global__ __launch_bounds__(MOM_THREADS) void k_fold_moments(const float* __res
   Interval v0[MOM_BPT], v1[MOM_BPT];
   float acc[MOM_BPT][MOM_NDIM];
   bool touched[MOM_BPT];
-  // "no interval" = offset ~0; always a global load with a clamped index (fold.hip load_iv)
+  // (the cursor of fold_walk.h's FoldCursor, kept as its own code: with FoldCursor the stream loader, <false, false>, ran 24 % slower on the
+  //  MI355X, everything else of the kernel unchanged -- profiles/HISTORY.md.)  "no interval" = offset ~0; always a global load with a
+  //  clamped index
   auto load_iv = [&](const uint32_t i, const bool valid) -> Interval {
     Interval t = iv[valid ? i : 0u];
     if (!valid) { t.offset = ~0ull; t.hits = 0u; }
@@ -226,17 +230,12 @@ __global__ __launch_bounds__(MOM_THREADS) void k_fold_moments(const float* __res
         const uint64_t hi = v.offset + v.hits < c1 ? v.offset + v.hits : c1;
         const uint32_t s0 = (uint32_t)(lo - c0), s1 = s0 + (uint32_t)(hi - lo);       // samples [s0, s1) of the chunk
         if constexpr (LONG) {
-          const uint32_t a0 = (s0 + MOM_MB - 1) / MOM_MB * MOM_MB;                    // first micro-block boundary >= s0
-          const uint32_t a1 = s1 / MOM_MB * MOM_MB;                                   // last boundary <= s1
-          if (a0 >= a1) {                                                             // no whole micro-block inside the piece
-            for (uint32_t h = s0; h < s1; h++) add_sample(acc[j], h);
-          } else {
-            for (uint32_t h = s0; h < a0; h++) add_sample(acc[j], h);
-            for (uint32_t mb = a0 / MOM_MB; mb < a1 / MOM_MB; mb++)
+          fold_long_piece(s0, s1, [&](const uint32_t h0, const uint32_t h1) { for (uint32_t h = h0; h < h1; h++) add_sample(acc[j], h); },
+                          [&](const uint32_t m0, const uint32_t m1) {
+                            for (uint32_t mb = m0; mb < m1; mb++)
 #pragma unroll
-              for (uint32_t d = 0; d < MOM_NDIM; d++) acc[j][d] += mbs[mb * MOM_NDIM + d];
-            for (uint32_t h = a1; h < s1; h++) add_sample(acc[j], h);
-          }
+                              for (uint32_t d = 0; d < MOM_NDIM; d++) acc[j][d] += mbs[mb * MOM_NDIM + d];
+                          });
         } else {
 #pragma unroll 2
           for (uint32_t h = s0; h < s1; h++) add_sample(acc[j], h);
@@ -306,38 +305,24 @@ int fold_moments_run(dspsr_amd_fold* f, const float* in_dev, uint64_t in_chan_st
   int rc = fold_plan_to_device(f, who, &sl, &first, &last, &max_run);
   if (rc != DSPSR_AMD_OK) return rc;
   const uint32_t nbin = f->nbin, nchan = f->nchan;
-  const bool lng = max_run >= FOLD_LONG_RUN;
   const uint32_t vec = ((uintptr_t)in_dev % 16 == 0 && in_chan_stride % 4 == 0) ? 1u : 0u;
-  // bin groups: enough for MOM_BPT bins per thread, and (as fold_fold_impl splits the bins) more when the band has few channels
-  uint32_t ngroup = (nbin + MOM_BPT * MOM_THREADS - 1) / (MOM_BPT * MOM_THREADS);
-  if (!lng)
-    while (ngroup < 8 && (uint64_t)nchan * ngroup < 512 && nbin / (2 * ngroup) >= 64) ngroup *= 2;
-  // LONG: time segments of whole MOM_SEG_UNIT-sample units, about four workgroups per CU
-  const uint64_t nunit = (last - first + MOM_SEG_UNIT - 1) / MOM_SEG_UNIT;
-  uint64_t nseg = 1, ups = nunit;
+  const FoldShape s = fold_moments_shape(nchan, nbin, first, last, max_run, ctx->ncu, MOM_NDIM, MOM_THREADS, MOM_BPT * MOM_THREADS);
+  const bool lng = s.family == FOLD_MOMENTS_LONG;
   if (lng) {
-    const uint64_t nrow = (uint64_t)nchan * ngroup;
-    nseg = (4ull * ctx->ncu + nrow - 1) / nrow;
-    if (nseg > nunit) nseg = nunit;
-    if (nseg > 65535) nseg = 65535;
-    if (nseg < 1) nseg = 1;
-    ups = (nunit + nseg - 1) / nseg;
-    nseg = (nunit + ups - 1) / ups;
-    const size_t need = (size_t)nseg * nchan * nbin * MOM_NDIM;
+    const size_t need = (size_t)s.nseg * nchan * nbin * MOM_NDIM;
     if (!grow_device_buffer(ctx->stream, f->part, f->part_floats, need))
       return ctx_fail(ctx, DSPSR_AMD_ENOMEM, "%s: hipMalloc of %zu partial-sum floats failed", who, need);
   }
-  const dim3 grid(ngroup, nchan, (uint32_t)nseg);
-  const uint64_t seg_samples = ups * MOM_SEG_UNIT;
-#define MOM_LAUNCH(ST, LG) hipLaunchKernelGGL((k_fold_moments<ST, LG>), grid, dim3(MOM_THREADS), 0, ctx->stream, in_dev, in_chan_stride, vec, \
-                                             f->profile, f->span, nbin, sl->d_bin_start, sl->d_iv, first, last, f->part, seg_samples)
+  const dim3 grid(s.grid[0], s.grid[1], s.grid[2]);
+#define MOM_LAUNCH(ST, LG) hipLaunchKernelGGL((k_fold_moments<ST, LG>), grid, dim3(s.threads), 0, ctx->stream, in_dev, in_chan_stride, vec, \
+                                             f->profile, f->span, nbin, sl->d_bin_start, sl->d_iv, first, last, f->part, s.seg_len)
   if (stokes) { if (lng) MOM_LAUNCH(true, true); else MOM_LAUNCH(true, false); }
   else { if (lng) MOM_LAUNCH(false, true); else MOM_LAUNCH(false, false); }
 #undef MOM_LAUNCH
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return ctx_fail(ctx, DSPSR_AMD_EHIP, "%s: %s", who, hipGetErrorString(e));
   if (lng) {
-    rc = fold_combine_partials(f, f->part, (uint32_t)nseg, 0, nchan);
+    rc = fold_combine_partials(f, who, f->part, s.nseg, 0, nchan);
     if (rc != DSPSR_AMD_OK) return rc;
   }
   return fold_part_plan_submitted(f, sl);

@@ -1,5 +1,5 @@
-// The fold engine's plan builders: integer arithmetic on the run-length plan, standard headers only (tests/fold_plan_driver.cpp
-// runs them without a GPU).  Each writes straight into the pointers it is given -- the pinned buffers of a PlanSlot -- with
+// The fold engine's plan builders and launch shapes: integer arithmetic on the run-length plan and on the call's dimensions,
+// standard headers only (tests/fold_plan_driver.cpp runs them without a GPU).  Each builder writes straight into the pointers it is given -- the pinned buffers of a PlanSlot -- with
 // `cursor` (dspsr_amd_fold::cursor) as its only scratch.  This code runs once per block next to a kernel of a few hundred
 // microseconds; extra walks and a bucket sort nobody read once made the host as slow as the device (profiles/r05_experiments.txt 6).
 #pragma once
@@ -17,6 +17,9 @@ constexpr uint32_t FOLD_CHUNK = 2048;   // samples per chunk of the chunked / de
 // Runs of FOLD_LONG_RUN samples or more are folded with re-associated sums (fold.hip, k_fold_chunked<., true>); the fused
 // filterbank kernel only has the exact time-order fold, so such plans take the separate Detection + Fold launches.
 constexpr uint32_t FOLD_LONG_RUN = 64;
+constexpr uint32_t FOLD_BPT = 4;        // bins per thread of those kernels (nbin <= FOLD_BPT * blockDim)
+constexpr uint32_t FOLD_MB = 32;        // samples per micro-block of the LONG association (fold.hip, "LONG runs")
+constexpr uint32_t FOLD_MANY_THREADS = 512;   // threads per workgroup of k_fold_many, at most (fold.hip)
 
 // Longest run of a plan (samples that go to one phase bin in a row); open_hits: the samples of the last run while it is
 // still open (its own hits are final only once the plan is closed).
@@ -200,5 +203,138 @@ inline void segment_plan_fill(const RunBin* runs, size_t n, uint32_t nbin, uint6
     blk_first[i] = (uint32_t)q;
   }
   plan_bucket(runs, n, nbin, bin_start, iv, cursor);
+}
+
+// ---- launch shapes: which kernel folds a call, and over which grid.  Each rule once, then one function per entry point. ---------
+
+// the chunk kernels take 16-byte aligned rows and at most FOLD_BPT bins per thread of a 1024-thread workgroup; else k_fold_direct
+inline bool fold_takes_chunks(bool aligned, uint32_t nbin) { return aligned && nbin <= FOLD_BPT * 1024; }
+
+// Exact order: the bins (slots) of a row are dealt to n workgroups, from `n` on doubled until there are two workgroups per CU
+// -- when the band has few rows -- or eight per row, or fewer than 64 bins each
+inline uint32_t fold_bin_split(uint64_t nrow, uint32_t nbin, uint32_t n)
+{
+  while (n < 8 && nrow * n < 512 && nbin / (2 * n) >= 64) n *= 2;
+  return n;
+}
+
+// FOLD_BPT bins per thread: 256-thread workgroups for 1024 bins or fewer, so that four of them share a CU and keep 4 x 32 KiB of
+// chunk loads in flight (the kernels are HBM-latency bound per workgroup)
+inline uint32_t fold_threads(uint32_t bins_wg, uint32_t max_threads)
+{
+  const uint32_t t = ((bins_wg + FOLD_BPT - 1) / FOLD_BPT + 63) / 64 * 64;
+  return t < 256 ? 256 : t > max_threads ? max_threads : t;
+}
+
+// LONG: rows x time segments, about four workgroups per CU, every sample read once.  nunit >= 1 units (chunks) of the span are
+// dealt to nseg segments of `len` units, the last one maybe shorter.
+struct FoldSegments { uint32_t nseg; uint64_t len; };
+inline FoldSegments fold_long_segments(uint64_t nunit, uint64_t nrow, uint32_t ncu)
+{
+  uint64_t nseg = (4ull * ncu + nrow - 1) / nrow;
+  if (nseg > nunit) nseg = nunit;
+  if (nseg > 65535) nseg = 65535;
+  if (nseg < 1) nseg = 1;
+  FoldSegments s;
+  s.len = (nunit + nseg - 1) / nseg;
+  s.nseg = (uint32_t)((nunit + s.len - 1) / s.len);
+  return s;
+}
+
+// planes of one channel folded together (ndim < 4): 4 or 2 rows per workgroup when the channels alone fill the chip, nz
+// workgroups per row (one row per workgroup at Benchmark/fold.csh's shape, four times the workgroups: 311-313 against 321-331
+// Msamples/s, same box)
+inline uint32_t fold_rows_per_wg(uint32_t nchan, uint32_t npol, uint32_t ndim, uint64_t nz, uint32_t ncu)
+{
+  return (ndim * npol == 4 && ndim < 4 && nchan * nz >= 2ull * ncu) ? npol : 1u;
+}
+
+enum FoldFamily { FOLD_DIRECT, FOLD_CHUNKED, FOLD_LONG, FOLD_DENSE, FOLD_MANY, FOLD_MOMENTS, FOLD_MOMENTS_LONG };
+struct FoldShape {
+  FoldFamily family;
+  uint32_t nd, nr;         // the instantiation <ND, NR>: floats per sample, rows per workgroup
+  uint32_t grid[3], threads;
+  size_t lds;              // dynamic LDS bytes
+  uint32_t nseg;           // LONG: time segments (else 1) of ...
+  uint64_t seg_len;        // ... this many chunks (fold) or samples (moments) each
+};
+
+// dspsr_amd_fold_fold: the plan spans samples [first, last), its longest run is max_run, `dense`: plan_scan accepted the table
+inline FoldShape fold_shape(bool aligned, uint32_t nchan, uint32_t npol, uint32_t ndim, uint32_t nbin, uint64_t first, uint64_t last,
+                            uint32_t max_run, bool dense, uint32_t ncu)
+{
+  const bool chunked = fold_takes_chunks(aligned, nbin);
+  const bool lng = chunked && max_run >= FOLD_LONG_RUN;               // re-associated sums (see FOLD_LONG_RUN)
+  const uint64_t nrow = (uint64_t)npol * nchan;
+  const uint32_t nsplit = lng ? 1u : fold_bin_split(nrow, nbin, 1);
+  const uint64_t nchunk = (last - first + FOLD_CHUNK - 1) / FOLD_CHUNK;
+  FoldShape s;
+  s.nd = ndim;
+  s.nseg = 1;
+  s.seg_len = nchunk;
+  if (!chunked) {
+    s.family = FOLD_DIRECT;
+    s.nr = 1;
+    s.grid[0] = npol; s.grid[1] = nchan; s.grid[2] = nsplit;
+    s.threads = nbin < 1024 ? ((nbin + 63) / 64) * 64 : 1024;
+    s.lds = 0;
+    return s;
+  }
+  if (lng) {
+    const FoldSegments g = fold_long_segments(nchunk, nrow, ncu);
+    s.nseg = g.nseg;
+    s.seg_len = g.len;
+  }
+  const uint32_t nz = lng ? s.nseg : nsplit;
+  s.family = dense ? FOLD_DENSE : lng ? FOLD_LONG : FOLD_CHUNKED;
+  s.nr = fold_rows_per_wg(nchan, npol, ndim, nz, ncu);
+  s.grid[0] = npol / s.nr; s.grid[1] = nchan; s.grid[2] = nz;
+  s.threads = fold_threads((nbin + nsplit - 1) / nsplit, 1024);
+  s.lds = ((size_t)FOLD_CHUNK + (lng ? FOLD_CHUNK / FOLD_MB : 0)) * ndim * s.nr * sizeof(float);
+  return s;
+}
+
+// One launch of k_fold_many over nslot (plan, bin) slots: the slots of a row dealt to grid[0] workgroups, enough for FOLD_BPT
+// slots per thread, then as fold_bin_split.  Siblings of a row are neighbours in blockIdx.x and run at the same time, so that the
+// re-reads of its chunks come from the Infinity Cache.
+inline FoldShape fold_many_shape(uint32_t nchan, uint32_t npol, uint32_t ndim, uint32_t nslot, uint32_t ncu)
+{
+  uint32_t nz = 1;
+  while ((uint64_t)nz * FOLD_BPT * FOLD_MANY_THREADS < nslot) nz *= 2;
+  nz = fold_bin_split((uint64_t)npol * nchan, nslot, nz);
+  FoldShape s;
+  s.family = FOLD_MANY;
+  s.nd = ndim;
+  s.nr = fold_rows_per_wg(nchan, npol, ndim, nz, ncu);
+  s.grid[0] = nz; s.grid[1] = npol / s.nr; s.grid[2] = nchan;
+  s.threads = fold_threads((nslot + nz - 1) / nz, FOLD_MANY_THREADS);
+  s.lds = (size_t)FOLD_CHUNK * ndim * s.nr * sizeof(float);
+  s.nseg = 1;
+  s.seg_len = 0;
+  return s;
+}
+
+// k_fold_moments (fold_moments.hip: workgroups of `threads` threads, bins_wg bins each, ndim floats per folded sample), either
+// loader: bin groups (grid[0]) enough for bins_wg bins each, more as fold_bin_split when the band has few channels; LONG: time
+// segments of whole FOLD_CHUNK-sample units (both loaders' chunk grids nest in them)
+inline FoldShape fold_moments_shape(uint32_t nchan, uint32_t nbin, uint64_t first, uint64_t last, uint32_t max_run, uint32_t ncu,
+                                    uint32_t ndim, uint32_t threads, uint32_t bins_wg)
+{
+  const bool lng = max_run >= FOLD_LONG_RUN;
+  uint32_t ngroup = (nbin + bins_wg - 1) / bins_wg;
+  if (!lng) ngroup = fold_bin_split(nchan, nbin, ngroup);
+  const uint64_t nunit = (last - first + FOLD_CHUNK - 1) / FOLD_CHUNK;
+  FoldSegments g = {1u, nunit};
+  if (lng) g = fold_long_segments(nunit, (uint64_t)nchan * ngroup, ncu);
+  FoldShape s;
+  s.family = lng ? FOLD_MOMENTS_LONG : FOLD_MOMENTS;
+  s.nd = ndim;
+  s.nr = 1;
+  s.grid[0] = ngroup; s.grid[1] = nchan; s.grid[2] = g.nseg;
+  s.threads = threads;
+  s.lds = 0;
+  s.nseg = g.nseg;
+  s.seg_len = g.len * FOLD_CHUNK;
+  return s;
 }
 }  // namespace dspsr_amd

@@ -3,7 +3,9 @@
 //   <op> nbin row_words try_dense first last nkeep npart ndat seg open_hits nrun
 //   offset ibin hits                (nrun lines, the runs in time order)
 // op: scan | bucket | dense | part | segment.  Every case prints the tables its builder made, one `name: values` line each,
-// between `begin` and `end`.  Every output buffer is a heap block of exactly the size the builder's count function gives, so
+// between `begin` and `end`.  The launch shapes take one line of plain numbers and no runs:
+//   fold_shape | many_shape | moments_shape   aligned nchan npol ndim nbin first last max_run dense ncu nslot threads bins_wg
+// (threads, bins_wg: k_fold_moments' workgroup) and print `shape: family nd nr grid.x grid.y grid.z threads lds nseg seg_len`.  Every output buffer is a heap block of exactly the size the builder's count function gives, so
 // that a write beyond it is an AddressSanitizer report.
 #include <inttypes.h>
 #include <stdio.h>
@@ -36,8 +38,20 @@ int main()
   uint64_t row_words, first, last, ndat;
   size_t nrun;
   std::vector<uint32_t> cursor;                    // (the engine's scratch: it lives from case to case, as from call to call)
-  while (scanf("%31s %u %" SCNu64 " %u %" SCNu64 " %" SCNu64 " %u %u %" SCNu64 " %u %u %zu", op, &nbin, &row_words, &try_dense, &first,
-               &last, &nkeep, &npart, &ndat, &seg, &open_hits, &nrun) == 12) {
+  while (scanf("%31s", op) == 1) {
+    if (!strcmp(op, "fold_shape") || !strcmp(op, "many_shape") || !strcmp(op, "moments_shape")) {
+      unsigned aligned, nchan, npol, ndim, max_run, dense, ncu, nslot, mom_threads, mom_bins_wg;
+      if (scanf("%u %u %u %u %u %" SCNu64 " %" SCNu64 " %u %u %u %u %u %u", &aligned, &nchan, &npol, &ndim, &nbin, &first, &last, &max_run,
+                &dense, &ncu, &nslot, &mom_threads, &mom_bins_wg) != 13) return 2;
+      const FoldShape s = !strcmp(op, "fold_shape") ? fold_shape(aligned != 0, nchan, npol, ndim, nbin, first, last, max_run, dense != 0, ncu)
+                          : !strcmp(op, "many_shape") ? fold_many_shape(nchan, npol, ndim, nslot, ncu)
+                          : fold_moments_shape(nchan, nbin, first, last, max_run, ncu, ndim, mom_threads, mom_bins_wg);
+      printf("begin %s\nshape: %d %u %u %u %u %u %u %zu %u %" PRIu64 "\nend\n", op, (int)s.family, s.nd, s.nr, s.grid[0], s.grid[1], s.grid[2],
+             s.threads, s.lds, s.nseg, s.seg_len);
+      continue;
+    }
+    if (scanf("%u %" SCNu64 " %u %" SCNu64 " %" SCNu64 " %u %u %" SCNu64 " %u %u %zu", &nbin, &row_words, &try_dense, &first, &last, &nkeep,
+              &npart, &ndat, &seg, &open_hits, &nrun) != 11) return 2;
     std::unique_ptr<RunBin[]> runs(new RunBin[nrun]);
     for (size_t i = 0; i < nrun; i++)
       if (scanf("%" SCNu64 " %u %u", &runs[i].offset, &runs[i].ibin, &runs[i].hits) != 3) return 2;

@@ -8,14 +8,16 @@ detected samples [nchan][npol][ndat][ndim] (sample idat of a row at rows[:, :, i
 - fold_time_order: the CPU loop of Fold.C:844-852, every (chan, pol, bin, dim) sum in strict time order.  The association of
   k_fold_direct, k_fold_chunked<., false, .> and k_fold_dense.
 - fold_long_model: the association of k_fold_chunked<., true, .> + k_fold_combine (the LONG path), bit for bit.
-- fold_dispatch: which kernel fold_fold_impl launches for a call, with its template arguments and launch shape.
+- fold_dispatch: which kernel dspsr_amd_fold_fold launches for a call, with its template arguments and launch shape (fold_plan.h
+  fold_shape); fold_many_dispatch: the shape of a shared launch (fold_many_shape).
 - fused_fold_model: the fold inside the last filterbank pass (dspsr_amd_filterbank_perform_fold, fold_is_fused() 1 and 2).
 """
 import numpy as np
 
 FOLD_CHUNK = 2048        # samples per chunk (fold_plan.h FOLD_CHUNK)
-FOLD_MB = 32             # samples per micro-block (fold.hip FOLD_MB)
-FOLD_BPT = 4             # bins per thread (fold.hip FOLD_BPT)
+FOLD_MB = 32             # samples per micro-block (fold_plan.h FOLD_MB)
+FOLD_BPT = 4             # bins per thread (fold_plan.h FOLD_BPT)
+FOLD_MANY_THREADS = 512  # threads of a k_fold_many workgroup at most (fold_plan.h FOLD_MANY_THREADS)
 FOLD_LONG_RUN = 64       # a run this long selects the LONG path (fold_plan.h FOLD_LONG_RUN)
 
 
@@ -62,7 +64,7 @@ def fold_time_order(rows, runs, prof):
 
 
 def long_segments(nchunk, nrow, ncu):
-    """(nseg, chunks per segment) of the LONG path: fold.hip fold_fold_impl, `nseg = (4 * ctx->ncu + nrow - 1) / nrow` ..."""
+    """(nseg, chunks per segment) of the LONG path: fold_plan.h fold_long_segments, `nseg = (4 * ncu + nrow - 1) / nrow` ..."""
     nseg = (4 * ncu + nrow - 1) // nrow
     nseg = max(1, min(nseg, nchunk, 65535))
     cps = (nchunk + nseg - 1) // nseg
@@ -129,7 +131,7 @@ def fold_long_model(rows, runs, prof, nrow, ncu):
 
 
 def fold_dispatch(addr, chan_stride, pol_stride, nchan, npol, ndim, nbin, runs, ncu):
-    """fold.hip fold_fold_impl's choice for a call (the comments name its variables; plan_scan is fold_plan.h's): `addr` the
+    """fold_plan.h fold_shape's choice for a call of dspsr_amd_fold_fold (the comments name the rules; plan_scan is fold_plan.h's too): `addr` the
     input's byte address, strides in floats.  Returns a dict:
     kernel ('direct' | 'chunked' | 'long' | 'dense'), ndim, nrow (NROW), nsplit (exact kernels, grid.z), nseg and cps (LONG),
     threads."""
@@ -169,6 +171,20 @@ def fold_dispatch(addr, chan_stride, pol_stride, nchan, npol, ndim, nbin, runs, 
     nrw = npol if (ndim * npol == 4 and ndim < 4 and nchan * (nseg if lng else nsplit) >= 2 * ncu) else 1   # `nrw`
     kernel = "dense" if dense else ("long" if lng else "chunked")
     return dict(kernel=kernel, ndim=ndim, nrow=nrw, nsplit=1 if lng else nsplit, nseg=nseg, cps=cps, threads=threads)
+
+
+def fold_many_dispatch(nchan, npol, ndim, nslot, ncu):
+    """fold_plan.h fold_many_shape: one launch of k_fold_many over nslot (plan, bin) slots.  Returns a dict: nz (workgroups per
+    row, grid.x), threads, nrow (NROW)."""
+    nz = 1
+    while nz * FOLD_BPT * FOLD_MANY_THREADS < nslot:                                                 # FOLD_BPT slots per thread
+        nz *= 2
+    while nz < 8 and nchan * npol * nz < 512 and nslot // (2 * nz) >= 64:                           # fold_bin_split
+        nz *= 2
+    slots_wg = (nslot + nz - 1) // nz
+    threads = min(FOLD_MANY_THREADS, max(256, ((slots_wg + FOLD_BPT - 1) // FOLD_BPT + 63) // 64 * 64))
+    nrw = npol if (ndim * npol == 4 and ndim < 4 and nchan * nz >= 2 * ncu) else 1
+    return dict(nz=nz, threads=threads, nrow=nrw)
 
 
 # ---- the fold inside the last filterbank pass (k_inv_chan<., FOLD>, k_rows_inv<., ., FOLD>) ------------------------------------

@@ -10,6 +10,9 @@ functions return, so a builder that writes past its table ends the driver with a
   plan_dense_fill        a direct table built from the runs, s0 | n << 11 per (chunk, bin)
   part_plan_*            fused_fold_cases.part_plan, for every call of every case of fused_fold_cases
   segment_plan_*         the qualification the segsum cases name; run_off / blk_first from np.searchsorted
+  fold_shape             fold_reference.fold_dispatch and long_segments: kernel family, <ND, NR>, grid, threads, LDS, segments
+  fold_many_shape        fold_reference.fold_many_dispatch
+  fold_moments_shape     moments_cases.geometry
 """
 import os
 import subprocess
@@ -18,7 +21,8 @@ import numpy as np
 import pytest
 
 import fused_fold_cases as fc
-from fold_reference import FOLD_CHUNK, FOLD_LONG_RUN, fold_dispatch, plan_span
+import moments_cases as mc
+from fold_reference import FOLD_BPT, FOLD_CHUNK, FOLD_LONG_RUN, FOLD_MANY_THREADS, FOLD_MB, fold_dispatch, fold_many_dispatch, long_segments, plan_span
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -36,6 +40,12 @@ def driver(tmp_path_factory):
         """cases: dicts of the header fields and `runs`; returns one dict of name -> int64 array per case"""
         text = []
         for c in cases:
+            if c["op"].endswith("_shape"):                           # the launch shapes: one line of plain numbers
+                text.append("%s %d %d %d %d %d %d %d %d %d %d %d %d %d" % (
+                    c["op"], c.get("aligned", 1), c["nchan"], c.get("npol", 1), c.get("ndim", 4), c.get("nbin", 0), c.get("first", 0),
+                    c.get("last", 0), c.get("max_run", 0), c.get("dense", 0), c["ncu"], c.get("nslot", 0), mc.MOM_THREADS,
+                    mc.MOM_BPT * mc.MOM_THREADS))
+                continue
             runs = np.asarray(c["runs"], np.int64).reshape(-1, 3)
             text.append("%s %d %d %d %d %d %d %d %d %d %d %d" % (
                 c["op"], c["nbin"], c.get("row_words", 4), c.get("try_dense", 1), c.get("first", 0), c.get("last", 0), c.get("nkeep", 1),
@@ -311,3 +321,130 @@ def test_segment_plan_edges(driver):
             if oh:
                 closed[-1] = (closed[-1][0], closed[-1][1], oh)
             _check_segment(g, closed, 8, ndat, label)
+
+
+# ---- the launch shapes (fold_plan.h fold_shape, fold_many_shape, fold_moments_shape) -------------------------------------------
+FAMILY = {"direct": 0, "chunked": 1, "long": 2, "dense": 3, "many": 4, "moments": 5, "moments-long": 6}      # enum FoldFamily
+NCUS = (256, 8)                                   # the MI355X and a small device: no rule may hide a constant in the other
+
+
+def _short_plan(nbin, nchunk=2, tail=77):
+    """runs of 5 samples sweeping the bins over nchunk chunks and a ragged end: no LONG run; dense or not as plan_scan finds"""
+    return _periodic(nbin, 5, nchunk * C + tail, start=6)
+
+
+def _long_plan(nbin, nsamp):
+    """two runs, the second a LONG one up to sample nsamp"""
+    return [(0, 0, 40), (40, nbin - 1, nsamp - 40)]
+
+
+def _want_fold_shape(disp, nchan, npol, ndim):
+    """the FoldShape line fold_dispatch stands for"""
+    lng, nr = disp["kernel"] == "long", disp["nrow"]
+    if disp["kernel"] == "direct":
+        grid, lds = [npol, nchan, disp["nsplit"]], 0
+    else:
+        grid = [npol // nr, nchan, disp["nseg"] if lng else disp["nsplit"]]
+        lds = (FOLD_CHUNK + (FOLD_CHUNK // FOLD_MB if lng else 0)) * ndim * nr * 4
+    return [FAMILY[disp["kernel"]], ndim, nr] + grid + [disp["threads"], lds, disp["nseg"], disp["cps"]]
+
+
+def _fold_shape_cases():
+    """(label, addr, nchan, npol, ndim, nbin, runs): the edges of every rule of fold_shape"""
+    out = []
+    for nbin in (127, 128, 129, 255, 256, 1023, 1024, 1025, 4096, 4097):        # bin split, threads, the chunk kernels' limit
+        for nchan in (1, 4):
+            out.append(("nbin %d" % nbin, 0, nchan, 1, 4, nbin, _short_plan(nbin)))
+    out.append(("unaligned rows", 4, 4, 1, 4, 256, _short_plan(256)))
+    out.append(("unaligned rows, nbin above 1024", 8, 4, 2, 2, 1500, _short_plan(1500)))
+    # nrow * nsplit at 511 / 512: 73 x 7 rows = 511 and one split more would pass 512; 128 x 4 = 512 rows are not split at all
+    for nchan, npol, ndim in ((73, 7, 1), (511, 1, 4), (512, 1, 4), (128, 4, 1), (255, 2, 2), (256, 2, 2), (127, 4, 1)):
+        out.append(("rows %d x %d" % (nchan, npol), 0, nchan, npol, ndim, 1024, _short_plan(1024, nchunk=1)))
+    # rows per workgroup, exact: nchan * nsplit either side of 2 * ncu (512 and 16), nsplit 1 (many rows) and above
+    for npol, ndim in ((1, 4), (2, 2), (4, 1), (2, 1)):
+        for nchan in (1, 2, 3, 15, 16, 17, 63, 64, 65, 255, 256, 511, 512, 513):
+            for nbin in (512, 256):          # a period of 2560 samples: the dense table; of 1280: two runs of a bin in a chunk, the walk
+                out.append(("nrw exact %d x %d x %d, nbin %d" % (nchan, npol, ndim, nbin), 0, nchan, npol, ndim, nbin, _short_plan(nbin, nchunk=1)))
+    # LONG: fewer chunks than wanted segments, exactly one chunk, many chunks; rows per workgroup with nchan * nseg at 2 * ncu
+    for npol, ndim in ((1, 4), (2, 2), (4, 1), (2, 1)):
+        for nchan in (1, 3, 4, 5, 16, 127, 128, 129, 300, 600):
+            for nsamp in (100, C, C + 1, 3 * C, 40 * C + 5):
+                out.append(("long %d x %d x %d, %d samples" % (nchan, npol, ndim, nsamp), 0, nchan, npol, ndim, 64, _long_plan(64, nsamp)))
+    return out
+
+
+def test_fold_shape_agrees_with_fold_dispatch(driver):
+    cases, want = [], []
+    for ncu in NCUS:
+        for label, addr, nchan, npol, ndim, nbin, runs in _fold_shape_cases():
+            runs = np.asarray(runs, np.int64).reshape(-1, 3)
+            disp = fold_dispatch(addr, 0, 0, nchan, npol, ndim, nbin, runs, ncu)
+            first, last = plan_span(runs)
+            cases.append(dict(op="fold_shape", aligned=int(addr % 16 == 0), nchan=nchan, npol=npol, ndim=ndim, nbin=nbin, first=first,
+                              last=last, max_run=int(runs[:, 2].max()), dense=int(disp["kernel"] == "dense"), ncu=ncu))
+            want.append(("%s, ncu %d" % (label, ncu), _want_fold_shape(disp, nchan, npol, ndim), disp))
+    got = driver(cases)
+    seen = set()
+    for g, (label, w, disp) in zip(got, want):
+        assert g["shape"].tolist() == w, (label, disp)
+        seen.add((disp["kernel"], disp["ndim"], disp["nrow"]))
+    # every instantiation of every chunk kernel is chosen somewhere, and k_fold_direct
+    for kernel in ("chunked", "dense", "long"):
+        assert {(nd, nr) for k, nd, nr in seen if k == kernel} == {(4, 1), (2, 2), (2, 1), (1, 4), (1, 1)}, kernel
+    assert {k for k, _, _ in seen} == {"direct", "chunked", "long", "dense"}
+
+
+def test_fold_shape_long_segments_at_the_clamp(driver):
+    """nseg is clamped to 65535 (grid.z) before the chunks are dealt: a span of 70000 chunks on a device large enough to want
+    more segments than that; and one chunk short of / at / beyond a multiple of the segment length"""
+    cases, want = [], []
+    for ncu, nchan, nchunk in ((1 << 15, 1, 70000), (1 << 15, 1, 65535), (1 << 15, 1, 65536), (1 << 15, 2, 131071), (256, 1, 70000),
+                               (256, 1, 1024), (256, 1, 1025), (8, 1, 33), (8, 3, 11)):
+        last = nchunk * C - 3
+        nseg, cps = long_segments(nchunk, nchan, ncu)
+        cases.append(dict(op="fold_shape", nchan=nchan, npol=1, ndim=4, nbin=64, first=0, last=last, max_run=last - 40, dense=0, ncu=ncu))
+        want.append([FAMILY["long"], 4, 1, 1, nchan, nseg, 256, (C + C // FOLD_MB) * 16, nseg, cps])
+        assert nseg <= 65535 and nseg * cps >= nchunk > (nseg - 1) * cps
+    got = driver(cases)
+    assert [g["shape"].tolist() for g in got] == want
+    assert want[0][5] == 35000 and want[1][5] == 65535 and want[2][5] == 32768          # 70000 chunks: two per segment
+
+
+def test_many_shape_agrees_with_fold_many_dispatch(driver):
+    cases, want = [], []
+    full = FOLD_BPT * FOLD_MANY_THREADS                                   # slots of one workgroup
+    for ncu in NCUS:
+        for npol, ndim in ((1, 4), (2, 2), (4, 1), (2, 1)):
+            for nchan in (1, 3, 7, 8, 9, 127, 128, 129, 255, 256, 257, 512, 520):
+                for nslot in (8, 127, 128, 129, 255, 256, 1023, 1024, 1025, full, full + 1, 2 * full, 2 * full + 1, 4 * full,
+                              4 * full + 1, 8 * full + 1):
+                    d = fold_many_dispatch(nchan, npol, ndim, nslot, ncu)
+                    cases.append(dict(op="many_shape", nchan=nchan, npol=npol, ndim=ndim, nslot=nslot, ncu=ncu))
+                    want.append([FAMILY["many"], ndim, d["nrow"], d["nz"], npol // d["nrow"], nchan, d["threads"],
+                                 FOLD_CHUNK * ndim * d["nrow"] * 4, 1, 0])
+                    assert d["nz"] * full >= nslot and d["threads"] * FOLD_BPT * d["nz"] >= nslot        # every slot has an owner
+    got = driver(cases)
+    assert [g["shape"].tolist() for g in got] == want
+    assert {(w[1], w[2]) for w in want} == {(4, 1), (2, 2), (2, 1), (1, 4), (1, 1)}
+    # FOLD_BPT * 512 * nz slots fit nz workgroups, one more doubles them
+    one = {(c["nslot"], w[3]) for c, w in zip(cases, want) if c["nchan"] == 520 and c["npol"] == 1}
+    assert {(full, 1), (full + 1, 2), (2 * full, 2), (2 * full + 1, 4), (4 * full, 4), (4 * full + 1, 8), (8 * full + 1, 16)} <= one
+
+
+def test_moments_shape_agrees_with_geometry(driver):
+    cases, want = [], []
+    for ncu in NCUS:
+        for nchan in (1, 5, 63, 64, 65, 511, 512, 513):
+            for nbin in (64, 127, 128, 129, 255, 256, 512, 513, 1024, 1025, 4097):
+                plans = [_short_plan(nbin, nchunk=1), _long_plan(nbin, 100), _long_plan(nbin, C), _long_plan(nbin, C + 1),
+                         _long_plan(nbin, 9 * C + 7), _long_plan(nbin, 300 * C)]
+                for runs in plans:
+                    g = mc.geometry(nchan, nbin, runs, ncu)
+                    cases.append(dict(op="moments_shape", nchan=nchan, ndim=mc.MOM_NDIM, nbin=nbin, first=g["first"], last=g["last"],
+                                      max_run=g["max_run"], ncu=ncu))
+                    want.append([FAMILY["moments-long" if g["lng"] else "moments"], mc.MOM_NDIM, 1, g["ngroup"], nchan, g["nseg"],
+                                 mc.MOM_THREADS, 0, g["nseg"], g["seg_samples"]])
+    got = driver(cases)
+    assert [g["shape"].tolist() for g in got] == want
+    assert any(w[0] == FAMILY["moments-long"] and w[9] == C and w[5] == 1 for w in want)            # nunit 1
+    assert {w[3] for w in want} >= {1, 2, 3, 4, 8, 9}                                                # bin groups: split and beyond 512 bins

@@ -14,7 +14,7 @@ import re
 import numpy as np
 import pytest
 
-from fold_reference import fold_dispatch, fold_long_model, fold_time_order, runs_of_plan
+from fold_reference import fold_dispatch, fold_long_model, fold_many_dispatch, fold_time_order, runs_of_plan
 from device_buffers import device_rows
 
 pytestmark = pytest.mark.gpu
@@ -136,7 +136,9 @@ def test_fold_many_bit_identical(gpu, oracle, kinds, nchan, npol, ndim, ndat, of
 @pytest.mark.parametrize("npol,ndim", [(2, 2), (4, 1)])
 def test_fold_many_rows_per_workgroup(gpu, oracle, npol, ndim):
     """NROW > 1: enough channels that a workgroup folds all polarisation rows of its channel"""
-    _case(gpu, oracle, ["dense", "walk", "walk_small"], 520, npol, ndim, 4500, rounds=1)
+    kinds = ["dense", "walk", "walk_small"]
+    assert fold_many_dispatch(520, npol, ndim, sum(SHAPE[k][1] for k in kinds), gpu[2])["nrow"] == npol
+    _case(gpu, oracle, kinds, 520, npol, ndim, 4500, rounds=1)
 
 
 def test_fold_many_refusals_leave_plans(gpu, oracle):

@@ -1,7 +1,9 @@
 """tools/fold_stride_probe.py : Benchmark/fold.csh shape (1024 channels x 4 products x 2^17 samples) with the rows of the detected
 block at their natural power-of-two stride and padded by PAD floats -- does the row stride (512 KB: every workgroup's stream at
-the same offset modulo a large power of two) cost HBM channel conflicts?  Prints ms per block and TB/s."""
-import sys, os, json
+the same offset modulo a large power of two) cost HBM channel conflicts?  Prints ms per block (mean and median) and TB/s.
+--nbin N folds into N bins instead of the pulsar's own choice: --nbin 32 gives about 87 samples per bin, runs of FOLD_LONG_RUN
+samples or more, so that the LONG kernel (k_fold_chunked<., true, .> + k_fold_combine) is the one timed."""
+import sys, os, json, argparse, statistics
 import numpy as np, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import dspsr_amd
@@ -10,7 +12,9 @@ nchan, npol, rate = 1024, 4, 1e6 / 32.0
 text = json.load(open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests", "golden", "vela_polyco.json")))["text"]
 polyco = pipeline.Polyco(text)
 day, sec0 = 55299, 7545.0
-nbin = pipeline.choose_nbin(1.0 / polyco.frequency(day, sec0), rate)
+ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+ap.add_argument("--nbin", type=int, default=0, help="phase bins (default: pipeline.choose_nbin of the folding period)")
+nbin = ap.parse_args().nbin or pipeline.choose_nbin(1.0 / polyco.frequency(day, sec0), rate)
 ctx = dspsr_amd.Context(0, torch.cuda.current_stream().cuda_stream)
 for pad, ndat in ((0, 1 << 17), (2112, 1 << 17), (0, 1 << 15), (0, 1 << 16), (0, 1 << 18), (0, 1 << 19), (0, 1 << 17)):
     fold = dspsr_amd.FoldEngine(ctx)
@@ -30,8 +34,9 @@ for pad, ndat in ((0, 1 << 17), (2112, 1 << 17), (0, 1 << 15), (0, 1 << 16), (0,
         fold.set_bins(0.25, (1.0 / rate) * polyco.frequency(day, sec0), ndat, 0, hits)
         a.record(); fold.fold(det); b.record()
     torch.cuda.synchronize()
-    ms = sum(a.elapsed_time(b) for a, b in ev) / len(ev)
-    print("ndat 2^%d pad %5d floats: %.4f ms per block, %.2f TB/s" % (int(np.log2(ndat)), pad, ms, nchan * npol * ndat * 4 / ms / 1e9), flush=True)
+    t = [a.elapsed_time(b) for a, b in ev]
+    ms = sum(t) / len(t)
+    print("nbin %d ndat 2^%d pad %5d floats: %.4f ms per block, %.2f TB/s, median %.4f ms" % (nbin, int(np.log2(ndat)), pad, ms, nchan * npol * ndat * 4 / ms / 1e9, statistics.median(t)), flush=True)
     fold.close()
     del buf, det
 ctx.close()

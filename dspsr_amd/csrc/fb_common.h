@@ -23,6 +23,7 @@
 //   which P3 loads with one ascending 16-byte stream per thread.
 #pragma once
 #include <math.h>
+#include <stddef.h>
 #include <stdlib.h>
 
 #include <vector>
@@ -57,10 +58,18 @@ struct FbGeom {
   const float2* tw_lo_m; // exp(-2*pi*i*j/freq_res), j < freq_res/TWN : same for the inverse twiddle (four-pass mode)
 };
 
+// What pass 1 (or the one-pass kernels) reads
+enum FbInKind : int {
+  FB_IN_FLOAT = 0,     // float32 rows
+  FB_IN_GENERIC8 = 1,  // int8, generic DADA order
+  FB_IN_CASPSR = 2,    // int8, CASPSR order
+  FB_IN_RT_BYTES = 3,  // (pol0, pol1) byte pairs pre-transposed per tile
+  FB_IN_UWB16 = 4,     // 16-bit offset-binary complex in 2048-sample blocks per polarisation (UWB)
+  FB_IN_RT_FLOAT = 5,  // float32 pairs pre-transposed per tile ((pol0, pol1) of real input or (re, im) of one polarisation)
+};
+
 struct FbIn {
-  int kind;  // 0: float32 rows, 1: int8 generic, 2: int8 caspsr, 3: (pol0,pol1) byte pairs pre-transposed per tile,
-             // 4: 16-bit offset-binary complex in 2048-sample blocks per polarisation (UWB)
-             // 5: float32 pairs pre-transposed per tile ((pol0, pol1) of real input or (re, im) of one polarisation)
+  FbInKind kind;
   const void* base;
   uint64_t pol_stride;  // float32: floats between pol rows
   uint64_t part_step;   // time samples between parts
@@ -71,11 +80,11 @@ struct FbIn {
   // chan_stride_c complex samples behind `base`; 0: off
   uint32_t batch;
   uint64_t chan_stride_c;
-  // kinds 3 and 5: elements from one tile, sequence and part of the regrouped image to the next (fb_rt_layout.h: one window per
-  // part, or one row grid shared by the parts of the launch group) -- pass 1 adds the three products, whatever the layout
+  // RT_BYTES and RT_FLOAT: elements from one tile, sequence and part of the regrouped image to the next (fb_rt_layout.h: one window
+  // per part, or one row grid shared by the parts of the launch group) -- pass 1 adds the three products, whatever the layout
   uint64_t rt_tile_stride = 0, rt_seq_stride = 0, rt_part_stride = 0;
 };
-static inline void fb_set_rt(FbIn& in, int kind, const void* base, const RtLayout& l)
+static inline void fb_set_rt(FbIn& in, FbInKind kind, const void* base, const RtLayout& l)
 {
   in.kind = kind;
   in.base = base;
@@ -84,46 +93,60 @@ static inline void fb_set_rt(FbIn& in, int kind, const void* base, const RtLayou
   in.rt_part_stride = l.part_stride;
 }
 
-struct FbOut {
-  int kind;  // 0: none (benchmark), 1: complex filterbank rows, 2: detected, 3: detected and folded in the same
-             //    kernel (base = device profile [chan][nbin] float4, ndim 4; plan per part, see fold_internal.h)
-             // 4: four-pass geometry, wide phase bins: k_inv_b reduces the detected samples of its tile to the sums of the
-             //    Tt-sample segments it holds (base = segment sums [chan][part][tile][t2][2] float4; pstart = the
-             //    time-ordered interval offsets of the block's bin plan, blk_first = their index per 1024 samples,
-             //    nparts_plan = parts of the block); fold_segment_combine adds them to the profile in time order
-  float* base;
-  uint64_t chan_stride, pol_stride, part_step;  // floats
-  int state;                                    // detected: coherence / stokes
-  uint32_t ndim, chan0;
-  uint32_t nbin;                                // kind 3
-  uint64_t prof_span4;                          // kind 3: float4 between consecutive channel rows of the profile
-  uint32_t prof_planes;                         // kind 3: 1 = one float4 (PP, QQ, Re, Im) per bin (npol 1, ndim 4); 2 = two rows of
-                                                //         float2 per channel, (PP, QQ) and (Re, Im) (npol 2, ndim 2: the layout
-                                                //         the reference's GPU pipeline folds, LoadToFold1.C:1105-1109)
-  uint64_t plane_stride;                        // kind 3, prof_planes 2: floats from the (PP, QQ) row to the (Re, Im) row
-  float* part;                                  // kind 3, nseg > 1: partial profiles of part segments 1 .. nseg-1 for the
-                                                //         nchan_subband channels of this launch, packed
-                                                //         [seg-1][chan - chan0][nbin] float4, zeroed before the launch
-  uint32_t nchan_prof;                          // kind 3: channel rows of the whole profile
-  uint32_t nseg;                                // kind 3: part segments of a launch folded by different workgroups (0/1: one)
-  dspsr_amd_fold* fold;                         // kind 3 (host side only): the engine whose profile `base` is
-  const uint32_t* pstart;                       // kind 3: per-part active-bin plan (fold_internal.h), nparts_plan parts
-  uint32_t nparts_plan;
-  uint32_t plan_cap;                            // kind 3: plan entries per LDS buffer (two buffers behind the twiddles)
-  const Interval* piv;                          // kind 3: intervals (offset within the part, hits), time ordered per bin
-  const uint32_t* blk_first;                    // kind 4: interval that holds sample 1024*i of the block
-  const uint32_t* bin_start;                    // kind 4 (host side only): the intervals bucketed by phase bin (with piv)
-  // kind 5: search mode (digifil -F N:D): square-law detection (state = DSPSR_AMD_INTENSITY | DSPSR_AMD_PPQQ) and the time
-  // scrunch of the detected STREAM inside the inverse pass; base = FPT rows [chan][npol_out] of scrunched samples, chan_stride /
-  // pol_stride in floats.  See ts_part / the search epilogue below.
-  uint32_t ts_sf;                               //   scrunch factor
-  uint32_t ts_magic;                            //   ceil(2^32 / sf): t / sf = umulhi(t, magic) for t * sf < 2^32 (host checks)
-  uint32_t ts_phase0;                           //   samples of output 0 already summed into the carry when the call begins
-  uint32_t ts_G;                                //   groups per staged row (odd, >= the most groups a part can touch)
-  float* ts_carry;                              //   [chan][npol_out] partial sums of the output sample still open
+// What the last pass leaves, and the fields of FbOut each form uses (filterbank.hip builds one with fb_out_*; every field a form
+// does not name is zero).  chan0, the first output channel of a launch, is set per launch group for every form.
+enum FbOutKind : int {
+  FB_OUT_NONE = 0,      // nothing written (benchmark)
+  FB_OUT_COMPLEX = 1,   // complex filterbank rows: base, chan_stride / pol_stride / part_step in floats, ndim 2
+  FB_OUT_DETECTED = 2,  // detected rows (Detection.C:423-474 layouts): base, chan_stride / pol_stride, state = coherence / stokes, ndim
+  FB_OUT_FOLD = 3,      // detected and folded in the same kernel: base = device profile [chan][nbin] float4 of `fold`, state, ndim 4, nbin,
+                        //   the profile's rows prof_span4 / prof_planes / plane_stride / nchan_prof, the per-part active-bin plan pstart /
+                        //   nparts_plan / piv (fold_internal.h); per launch (fb_launch_fused): plan_cap, and nseg / part for part segments
+  FB_OUT_SEGSUM = 4,    // four-pass geometry, wide phase bins: k_inv_b reduces the detected samples of its tile to the sums of the
+                        //   Tt-sample segments it holds (base = segment sums [chan][part][tile][t2][2] float4; pstart = the
+                        //   time-ordered interval offsets of the block's bin plan, blk_first = their index per 1024 samples,
+                        //   nparts_plan = parts of the block); fold_segment_combine adds them to the profile (FOLD's fields) in time order
+  FB_OUT_SEARCH = 5,    // search mode (digifil -F N:D): square-law detection (state = DSPSR_AMD_INTENSITY | DSPSR_AMD_PPQQ) and the
+                        //   time scrunch of the detected STREAM inside the inverse pass; base = FPT rows [chan][npol_out] of
+                        //   scrunched samples, chan_stride / pol_stride in floats, ndim 1, ts_*.  See ts_part / the search epilogue below.
 };
 
-// Search-mode epilogue (FbOut kind 5): the detected samples of a channel form a stream over the parts of a call (and over calls:
+struct FbOut {
+  FbOutKind kind;
+  float* base;
+  uint64_t chan_stride, pol_stride, part_step;  // floats
+  int state;
+  uint32_t ndim, chan0;
+  uint32_t nbin;                                // FOLD
+  uint64_t prof_span4;                          // FOLD: float4 between consecutive channel rows of the profile
+  uint32_t prof_planes;                         // FOLD: 1 = one float4 (PP, QQ, Re, Im) per bin (npol 1, ndim 4); 2 = two rows of
+                                                //       float2 per channel, (PP, QQ) and (Re, Im) (npol 2, ndim 2: the layout
+                                                //       the reference's GPU pipeline folds, LoadToFold1.C:1105-1109)
+  uint64_t plane_stride;                        // FOLD, prof_planes 2: floats from the (PP, QQ) row to the (Re, Im) row
+  float* part;                                  // FOLD, nseg > 1: partial profiles of part segments 1 .. nseg-1 for the
+                                                //       nchan_subband channels of this launch, packed
+                                                //       [seg-1][chan - chan0][nbin] float4, zeroed before the launch
+  uint32_t nchan_prof;                          // FOLD: channel rows of the whole profile
+  uint32_t nseg;                                // FOLD: part segments of a launch folded by different workgroups (0/1: one)
+  dspsr_amd_fold* fold;                         // FOLD (host side only): the engine whose profile `base` is
+  const uint32_t* pstart;                       // FOLD: per-part active-bin plan, nparts_plan parts
+  uint32_t nparts_plan;
+  uint32_t plan_cap;                            // FOLD: plan entries per LDS buffer (two buffers behind the twiddles)
+  const Interval* piv;                          // FOLD: intervals (offset within the part, hits), time ordered per bin
+  const uint32_t* blk_first;                    // SEGSUM: interval that holds sample 1024*i of the block
+  const uint32_t* bin_start;                    // SEGSUM (host side only): the intervals bucketed by phase bin (with piv)
+  uint32_t ts_sf;                               // SEARCH: scrunch factor
+  uint32_t ts_magic;                            // SEARCH: ceil(2^32 / sf): t / sf = umulhi(t, magic) for t * sf < 2^32 (host checks)
+  uint32_t ts_phase0;                           // SEARCH: samples of output 0 already summed into the carry when the call begins
+  uint32_t ts_G;                                // SEARCH: groups per staged row (odd, >= the most groups a part can touch)
+  float* ts_carry;                              // SEARCH: [chan][npol_out] partial sums of the output sample still open
+};
+// FbIn, FbOut and SubSplit travel to the kernels by value: their layout is part of every kernel's argument list
+static_assert(sizeof(FbIn) == 80 && offsetof(FbIn, kind) == 0 && offsetof(FbIn, base) == 8, "FbIn layout");
+static_assert(sizeof(FbOut) == 168 && offsetof(FbOut, kind) == 0 && offsetof(FbOut, base) == 8 && offsetof(FbOut, pstart) == 104 &&
+              offsetof(FbOut, ts_sf) == 144 && offsetof(FbOut, ts_carry) == 160, "FbOut layout");
+
+// Search-mode epilogue (FB_OUT_SEARCH): the detected samples of a channel form a stream over the parts of a call (and over calls:
 // the carry).  Output sample o is the sum, in time order, of stream samples [o*sf, (o+1)*sf) (TScrunch.C:148-178).  A part's nkeep
 // samples start at stream index s = phase0 + part * nkeep: they touch groups ofirst .. ofirst + ng - 1, the first one from its
 // element phi on, the last one up to element rlast - 1.
@@ -204,7 +227,7 @@ DEV void ts_reduce(const float* __restrict__ stg, const FbOut& out, const TsPart
 
 // nchan_subband = 3 * 2^k / 5 * 2^k: arguments of k_sub_split (see the section in front of pass 2)
 struct SubSplit {
-  int kind;                   // FbIn::kind of the source: 0 float rows, 1 generic 8-bit, 2 CASPSR
+  FbInKind kind;              // of the source: FB_IN_FLOAT, FB_IN_GENERIC8 or FB_IN_CASPSR
   const void* base;
   uint64_t chan_off;          // float: floats to this input channel's rows
   uint64_t pol_stride;        // float: floats between polarisation rows
@@ -218,6 +241,7 @@ struct SubSplit {
   uint32_t nwin;
   uint64_t wlen, win_step;
 };
+static_assert(sizeof(SubSplit) == 104 && offsetof(SubSplit, kind) == 0 && offsetof(SubSplit, base) == 8, "SubSplit layout");
 // Twiddles of the radix-R steps outside the tiles (R = 3, 5, 7, 9, 15): exp(-2 pi i t / (R 2^logP)), t < R 2^logP.  With
 // t = a 2^logP + b the twiddle is W_R^a -- R values, built in double on the host and handed over in this table -- times
 // (cos, -sin)(b / 2^logP / R revolutions): b / 2^logP is exact in float for logP <= 24 and the one division by R leaves
@@ -327,10 +351,10 @@ template <int W> DEV RawW<W> fetch_pair(const FbGeom& g, const FbIn& in, const u
     r.w[0] = *(const uint32_t*)((const uint8_t*)in.base + 2 * t);
     return r;
   } else {
-  if (in.kind == 5) {                                   // regrouped float32 pairs: columns t, t+1 are 16 contiguous bytes
+  if (in.kind == FB_IN_RT_FLOAT) {                                   // regrouped float32 pairs: columns t, t+1 are 16 contiguous bytes
     const uint4 v = *(const uint4*)((const cf*)in.base + t);
     r.w[0] = v.x; r.w[1] = v.y; r.w[2] = v.z; r.w[3] = v.w;
-  } else if (in.kind == 0) {                            // float32 rows
+  } else if (in.kind == FB_IN_FLOAT) {                            // float32 rows
     if (g.real_input) {
       const float* x = (const float*)in.base + t;
       r.w[0] = __float_as_uint(x[0]); r.w[1] = __float_as_uint(x[1]);
@@ -340,11 +364,11 @@ template <int W> DEV RawW<W> fetch_pair(const FbGeom& g, const FbIn& in, const u
       r.w[0] = __float_as_uint(x[0]); r.w[1] = __float_as_uint(x[1]);
       r.w[2] = __float_as_uint(x[2]); r.w[3] = __float_as_uint(x[3]);
     }
-  } else if (in.kind == 2) {                            // CASPSR: 4 B pol0, 4 B pol1 (t even)
+  } else if (in.kind == FB_IN_CASPSR) {                            // CASPSR: 4 B pol0, 4 B pol1 (t even)
     const uint8_t* b = (const uint8_t*)in.base + (t >> 2) * 8 + (t & 3);
     r.w[0] = *(const uint16_t*)b;
     r.w[1] = *(const uint16_t*)(b + 4);
-  } else if (in.kind == 4) {                            // UWB: word (block*npol + pol)*2048 + t%2048 = (re, im) int16
+  } else if (in.kind == FB_IN_UWB16) {                            // UWB: word (block*npol + pol)*2048 + t%2048 = (re, im) int16
     const uint32_t* b = (const uint32_t*)in.base;
     const uint64_t t1 = t + 1;
     r.w[0] = b[((t >> 11) * g.npol + seq) * 2048 + (t & 2047)];
@@ -394,10 +418,10 @@ template <int W> DEV void decode_pair(const FbGeom& g, const FbIn& in, const Raw
     b = make_float2(cvt8((int8_t)((r.w[0] >> 16) & 0xff), in.scale), cvt8((int8_t)(r.w[0] >> 24), in.scale));
     return;
   } else {
-  if (in.kind == 5) {
+  if (in.kind == FB_IN_RT_FLOAT) {
     a = make_float2(__uint_as_float(r.w[0]), __uint_as_float(r.w[1]));
     b = make_float2(__uint_as_float(r.w[2]), __uint_as_float(r.w[3]));
-  } else if (in.kind == 0) {
+  } else if (in.kind == FB_IN_FLOAT) {
     if (g.real_input) {
       a = make_float2(__uint_as_float(r.w[0]), g.npol == 2 ? __uint_as_float(r.w[2]) : 0.0f);
       b = make_float2(__uint_as_float(r.w[1]), g.npol == 2 ? __uint_as_float(r.w[3]) : 0.0f);
@@ -405,10 +429,10 @@ template <int W> DEV void decode_pair(const FbGeom& g, const FbIn& in, const Raw
       a = make_float2(__uint_as_float(r.w[0]), __uint_as_float(r.w[1]));
       b = make_float2(__uint_as_float(r.w[2]), __uint_as_float(r.w[3]));
     }
-  } else if (in.kind == 4) {                            // convert_offset_binary, UWBUnpackerCUDA.cu:24
+  } else if (in.kind == FB_IN_UWB16) {                            // convert_offset_binary, UWBUnpackerCUDA.cu:24
     a = make_float2((float)(int16_t)((r.w[0] & 0xffff) ^ 0x8000) * in.scale, (float)(int16_t)((r.w[0] >> 16) ^ 0x8000) * in.scale);
     b = make_float2((float)(int16_t)((r.w[1] & 0xffff) ^ 0x8000) * in.scale, (float)(int16_t)((r.w[1] >> 16) ^ 0x8000) * in.scale);
-  } else if (in.kind == 2) {
+  } else if (in.kind == FB_IN_CASPSR) {
     a = make_float2(cvt8((int8_t)(r.w[0] & 0xff), in.scale), cvt8((int8_t)(r.w[1] & 0xff), in.scale));
     b = make_float2(cvt8((int8_t)((r.w[0] >> 8) & 0xff), in.scale), cvt8((int8_t)((r.w[1] >> 8) & 0xff), in.scale));
   } else {

@@ -23,7 +23,7 @@ struct Conv1Params {
   const float* in;                 // rows: in + chan * chan_stride + pol * pol_stride + part * in_step, (re, im) pairs
   uint64_t chan_stride, pol_stride, in_step;     // floats
   const cf* kern;                  // [nchan][M] or null
-  FbOut out;                       // kind 0 (none), 1 (complex rows), 2 (detected)
+  FbOut out;                       // FB_OUT_NONE, FB_OUT_COMPLEX or FB_OUT_DETECTED
   uint32_t nchan, nfilt_pos, nkeep;
   uint64_t npart;
   uint32_t tiles_per_chan;
@@ -125,12 +125,12 @@ __global__ __launch_bounds__(512) void k_conv1(const Conv1Params p, const cf* __
     const FbOut& out = p.out;
     auto store = [&](const uint32_t col, const uint32_t pos, const uint32_t pstride, auto& v) {
       constexpr int R = sizeof(v) / sizeof(v[0]);
-      if (out.kind == 0) return;
+      if (out.kind == FB_OUT_NONE) return;
       const uint64_t part = (uint64_t)tl * Ts + (col >> 1);
       if (part > last_part) return;
       float* __restrict__ row = out.base + (uint64_t)(out.chan0 + chan) * out.chan_stride;
       const int32_t t0 = (int32_t)pos - (int32_t)p.nfilt_pos;
-      if (out.kind == 1) {
+      if (out.kind == FB_OUT_COMPLEX) {
         float2* __restrict__ o2 = (float2*)(row + part * out.part_step) + t0;
 #pragma unroll
         for (int k = 0; k < R; k++) {

@@ -30,7 +30,7 @@ struct Conv3Params {
   const float* in;                 // rows of the first channel: + chan * chan_stride + pol * pol_stride + part * in_step, (re, im) pairs
   uint64_t chan_stride, pol_stride, in_step;     // floats
   const cf* kern;                  // [nchan][M] of the first channel, every channel in pass-B order (fb_conv3_response_order), or null
-  FbOut out;                       // kind 0 (none), 1 (complex rows), 2 (detected); chan0 = output row of the first channel
+  FbOut out;                       // FB_OUT_NONE, FB_OUT_COMPLEX or FB_OUT_DETECTED; chan0 = output row of the first channel
   cf* S1;
   cf* S2;
   uint32_t nchan, nparts;          // channels and parts of this launch group
@@ -360,7 +360,7 @@ __global__ __launch_bounds__(512) void k_conv3_c(const Conv3Params p, const cf* 
     const uint64_t part = p.part0 + part_l;
     const float* row = out.base + (uint64_t)(out.chan0 + chan) * out.chan_stride;
     constexpr uint32_t ebytes = OF == 1 ? 16u : OF == 3 ? 4u : 8u;            // bytes per sample and plane
-    const uint32_t wbytes = out.kind == 0 ? 0u : p.nkeep * ebytes;
+    const uint32_t wbytes = out.kind == FB_OUT_NONE ? 0u : p.nkeep * ebytes;
     const float* w0 = OF == 0 ? row + part * out.part_step : row + part * p.nkeep * (ebytes / 4);
     const __amdgpu_buffer_rsrc_t r0 = win_rsrc(w0, wbytes), r1 = win_rsrc(w0 + out.pol_stride, OF == 1 ? 0u : wbytes),
                                  r2 = win_rsrc(w0 + 2 * out.pol_stride, OF == 3 ? wbytes : 0u),
@@ -454,7 +454,7 @@ int fb_conv3_launch(dspsr_amd_ctx* ctx, int logM, const float* in, uint64_t chan
   const uint32_t grid = (uint32_t)(total < ctx->ncu ? total : ctx->ncu);
   hipLaunchKernelGGL(k.a, dim3(grid), dim3(512), conv3_lds(la), ctx->stream, p, ctx->tw);
   hipLaunchKernelGGL(k.b, dim3(grid), dim3(512), conv3_lds(lb), ctx->stream, p, ctx->tw);
-  const int of = out.kind == 2 ? (out.ndim == 4 ? 1 : out.ndim == 2 ? 2 : 3) : 0;
+  const int of = out.kind == FB_OUT_DETECTED ? (out.ndim == 4 ? 1 : out.ndim == 2 ? 2 : 3) : 0;
   hipLaunchKernelGGL(k.c[of], dim3(grid), dim3(512), conv3_lds(la), ctx->stream, p, ctx->tw);
   return hipGetLastError() == hipSuccess ? DSPSR_AMD_OK : DSPSR_AMD_EHIP;
 }

@@ -317,7 +317,7 @@ __global__ __launch_bounds__(512) void k_inv_a(const FbGeom g, const cf* __restr
   FB_ST_END(4);
 }
 
-// FOLDB (FbOut kind 4): the tile holds, for one channel, Mb runs of Tt consecutive output samples (run t2 = samples
+// FOLDB (FB_OUT_SEGSUM): the tile holds, for one channel, Mb runs of Tt consecutive output samples (run t2 = samples
 // t1 + Ma*t2, t1 in the tile's block): exactly the micro-blocks the long-run fold (fold.hip, FOLD_LONG_RUN) sums first.
 // The detected samples are staged in the exchange buffer ([t2][t1], XOR-swizzled so that both the stage's writes and the
 // per-run reads are conflict free); thread t2 adds its run in time order, cut at the one phase-bin boundary it may hold
@@ -385,7 +385,7 @@ __global__ __launch_bounds__(512) void k_inv_b(const FbGeom g, const cf* __restr
         }
         return;
       }
-      if (out.kind == 0) return;
+      if (out.kind == FB_OUT_NONE) return;
       const uint32_t chan = out.chan0 + c;
       const uint32_t t1 = (tile << logTt) + (col >> 1);
       float* __restrict__ row = out.base + chan * out.chan_stride;
@@ -397,7 +397,7 @@ __global__ __launch_bounds__(512) void k_inv_b(const FbGeom g, const cf* __restr
           emit(pos - g.nfilt_pos, cx2_lo(v[k]), cx2_hi(v[k]));
         }
       };
-      if (out.kind == 1) {
+      if (out.kind == FB_OUT_COMPLEX) {
         float2* __restrict__ o0 = (float2*)(row + part * out.part_step);
         if (g.npol == 2)
           each([&](const uint32_t t, const cf va, const cf vb) {

@@ -37,7 +37,7 @@ DEV void fwd_cols_body(const FbGeom& g, const FbIn& in, cf* __restrict__ A, cons
     const uint32_t tile = item & (ntile - 1);
     const uint32_t rest = item >> logNt;
     uint32_t seq = seq_of(rest);
-    const bool pret = in.kind == 3 || in.kind == 5;   // pre-transposed: [na][T] pairs, contiguous per tile (fb_rt_layout.h)
+    const bool pret = in.kind == FB_IN_RT_BYTES || in.kind == FB_IN_RT_FLOAT;   // pre-transposed: [na][T] pairs, contiguous per tile (fb_rt_layout.h)
     uint64_t t0 = pret ? part_of(rest) * in.rt_part_stride + seq * in.rt_seq_stride + tile * in.rt_tile_stride
                        : (part0 + part_of(rest)) * in.part_step + tile * T;
     if constexpr (RAWW == 4) {

@@ -47,7 +47,7 @@ __global__ __launch_bounds__(256) void k_raw_transpose(const FbGeom g, const FbI
         w[1] = ((s0.z >> sh) & 0xffffu) | (((s0.w >> sh) & 0xffffu) << 16);
         w[2] = ((s1.x >> sh) & 0xffffu) | (((s1.y >> sh) & 0xffffu) << 16);
         w[3] = ((s1.z >> sh) & 0xffffu) | (((s1.w >> sh) & 0xffffu) << 16);
-      } else if (in.kind == 2) {                                       // CASPSR: 4 B pol0 | 4 B pol1
+      } else if (in.kind == FB_IN_CASPSR) {                                       // CASPSR: 4 B pol0 | 4 B pol1
         const uint32_t* p = (const uint32_t*)((const uint8_t*)in.base + (t >> 2) * 8);
 #pragma unroll
         for (int h = 0; h < 2; h++) {
@@ -70,7 +70,7 @@ __global__ __launch_bounds__(256) void k_raw_transpose(const FbGeom g, const FbI
       if (!g.real_input) {
         const uint32_t* p = (const uint32_t*)((const uint8_t*)in.base + 4 * t);
         w = ((p[0] >> (16 * seq)) & 0xffffu) | (((p[1] >> (16 * seq)) & 0xffffu) << 16);
-      } else if (in.kind == 2) {
+      } else if (in.kind == FB_IN_CASPSR) {
         const uint8_t* b = (const uint8_t*)in.base + (t >> 2) * 8 + (t & 3);
         w = (uint32_t)b[0] | ((uint32_t)b[4] << 8) | ((uint32_t)b[1] << 16) | ((uint32_t)b[5] << 24);
       } else {
@@ -204,7 +204,7 @@ __global__ __launch_bounds__(512) void k_fwd_cols_dual(const FbGeom g, const FbI
     const uint32_t tile = ((item & (npair - 1)) << 1) | sub;
     const uint32_t rest = item >> logNp;
     const uint32_t seq = seq_of(rest);
-    const bool pret = in.kind == 3 || in.kind == 5;   // pre-transposed: [na][T] pairs, contiguous per tile (fb_rt_layout.h)
+    const bool pret = in.kind == FB_IN_RT_BYTES || in.kind == FB_IN_RT_FLOAT;   // pre-transposed: [na][T] pairs, contiguous per tile (fb_rt_layout.h)
     const uint64_t t0 = pret ? part_of(rest) * in.rt_part_stride + seq * in.rt_seq_stride + tile * in.rt_tile_stride
                              : (part0 + part_of(rest)) * in.part_step + tile * T;
     constexpr uint32_t MS = 1u << (LOGF - P::LOGR1);
@@ -312,17 +312,17 @@ __global__ __launch_bounds__(512) void k_fwd_cols_dual(const FbGeom g, const FbI
 //                   float rows), so that passes 0-2 see ordinary inputs
 //   k_sub_combine : the radix-R step in place on the R sub-spectra of every (part, sequence)
 // Element j of sub-sequence c of window lp is input sample t_first + lp*win_step + R*j + c.
-// KIND / EB: source form and bytes per element -- 1: generic 8-bit order, one element = the EB = npol*ndim bytes of a sample;
-// 2: CASPSR (4 B pol0 | 4 B pol1), EB = 2; 0: float32 rows, one element = the ndim floats of one polarisation (EB = 4 ndim).
+// KIND / EB: source form (an FbInKind) and bytes per element -- GENERIC8: generic 8-bit order, one element = the EB = npol*ndim bytes of a sample;
+// CASPSR (4 B pol0 | 4 B pol1), EB = 2; FLOAT: float32 rows,| 4 B pol1), EB = 2; 0: float32 rows, one element = the ndim floats of one polarisation (EB = 4 ndim).
 // Fast form (FAST): a thread takes n*R consecutive input samples (n = 16 / EB) and writes, for every c, the n elements they hold
 // as ONE 16-byte store -- a ninth of the memory instructions of the element-wise form (one load and one store per BYTE), which
 // moved the input at 2.3 TB/s (profiles/r05_experiments.txt item 3).  The element-wise form keeps the tails and odd shapes.
 template <int KIND, int EB> struct SplitElem { typedef uint32_t type; };
-template <> struct SplitElem<0, 8> { typedef uint2 type; };
+template <> struct SplitElem<FB_IN_FLOAT, 8> { typedef uint2 type; };
 template <int KIND, int EB>
 DEV typename SplitElem<KIND, EB>::type sub_split_load(const SubSplit& p, const uint32_t q, const uint64_t t)
 {
-  if constexpr (KIND == 0) {
+  if constexpr (KIND == FB_IN_FLOAT) {
     const float* __restrict__ x = (const float*)p.base + p.chan_off + q * p.pol_stride;
     if constexpr (EB == 8) {
       // (rows at an odd float offset -- a shifted TimeSeries, odd channel or polarisation strides -- take two 4-byte loads)
@@ -330,7 +330,7 @@ DEV typename SplitElem<KIND, EB>::type sub_split_load(const SubSplit& p, const u
       return make_uint2(__float_as_uint(x[2 * t]), __float_as_uint(x[2 * t + 1]));
     }
     else return __float_as_uint(x[t]);
-  } else if constexpr (KIND == 2) {
+  } else if constexpr (KIND == FB_IN_CASPSR) {
     const uint8_t* __restrict__ b = (const uint8_t*)p.base + (t >> 2) * 8 + (t & 3);
     return (uint32_t)b[0] | ((uint32_t)b[4] << 8);
   } else {
@@ -350,7 +350,7 @@ __global__ __launch_bounds__(256) void k_sub_split(const SubSplit p, uint8_t* __
 {
   constexpr uint32_t N = 16 / EB;                                   // elements per 16-byte store
   constexpr uint32_t R = RT;
-  const uint32_t nrow = KIND == 0 ? p.npol : 1u;                    // float: one row of elements per polarisation
+  const uint32_t nrow = KIND == FB_IN_FLOAT ? p.npol : 1u;                    // float: one row of elements per polarisation
   const uint64_t groups = p.wlen / N;                               // whole 16-byte groups per window and sub-sequence
   const uint64_t nunit = (uint64_t)p.nwin * nrow * groups;
   for (uint64_t u = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; u < nunit; u += (uint64_t)gridDim.x * blockDim.x) {
@@ -362,7 +362,7 @@ __global__ __launch_bounds__(256) void k_sub_split(const SubSplit p, uint8_t* __
       typename SplitElem<KIND, EB>::type e[N * RT];
       // 8-bit sources: the thread's 16 R input bytes as whole dwords where the alignment allows (a load per BYTE otherwise)
       bool have = false;
-      if constexpr (KIND == 2) {
+      if constexpr (KIND == FB_IN_CASPSR) {
         if ((t0 & 3) == 0 && ((uintptr_t)p.base & 7) == 0) {       // whole 4-sample groups: 4 B pol0 | 4 B pol1 (8-byte loads)
           const uint2* __restrict__ gp = (const uint2*)((const uint8_t*)p.base + (t0 >> 2) * 8);
           uint2 grp[2 * RT];
@@ -373,7 +373,7 @@ __global__ __launch_bounds__(256) void k_sub_split(const SubSplit p, uint8_t* __
             e[i] = ((grp[i >> 2].x >> (8 * (i & 3))) & 0xffu) | (((grp[i >> 2].y >> (8 * (i & 3))) & 0xffu) << 8);
           have = true;
         }
-      } else if constexpr (KIND == 1) {
+      } else if constexpr (KIND == FB_IN_GENERIC8) {
         const uint8_t* __restrict__ b = (const uint8_t*)p.base + t0 * EB;
         if (p.nchan == 1 && ((uintptr_t)b & 3) == 0) {
           uint32_t w[4 * RT];
@@ -414,7 +414,7 @@ __global__ __launch_bounds__(256) void k_sub_split(const SubSplit p, uint8_t* __
 template <int KIND, int EB>
 __global__ __launch_bounds__(256) void k_sub_split_tail(const SubSplit p, uint8_t* __restrict__ out, const uint64_t m_lo)
 {
-  const uint32_t nrow = KIND == 0 ? p.npol : 1u;
+  const uint32_t nrow = KIND == FB_IN_FLOAT ? p.npol : 1u;
   const uint64_t per = (p.wlen - m_lo) * p.R, n = (uint64_t)p.nwin * nrow * per;
   for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x) {
     const uint64_t w = i % per, rest = i / per;
@@ -569,11 +569,11 @@ static void sub_split_launch(hipStream_t stream, const SubSplit& p, uint8_t* out
 void fb_launch_sub_split(hipStream_t stream, const SubSplit& p, uint8_t* out, uint32_t ncu)
 {
   const uint32_t es = p.npol * p.ndim;
-  if (p.kind == 0) { if (p.ndim == 2) sub_split_launch<0, 8>(stream, p, out, ncu); else sub_split_launch<0, 4>(stream, p, out, ncu); }
-  else if (p.kind == 2) sub_split_launch<2, 2>(stream, p, out, ncu);
-  else if (es == 4) sub_split_launch<1, 4>(stream, p, out, ncu);
-  else if (es == 2) sub_split_launch<1, 2>(stream, p, out, ncu);
-  else sub_split_launch<1, 1>(stream, p, out, ncu);
+  if (p.kind == FB_IN_FLOAT) { if (p.ndim == 2) sub_split_launch<FB_IN_FLOAT, 8>(stream, p, out, ncu); else sub_split_launch<FB_IN_FLOAT, 4>(stream, p, out, ncu); }
+  else if (p.kind == FB_IN_CASPSR) sub_split_launch<FB_IN_CASPSR, 2>(stream, p, out, ncu);
+  else if (es == 4) sub_split_launch<FB_IN_GENERIC8, 4>(stream, p, out, ncu);
+  else if (es == 2) sub_split_launch<FB_IN_GENERIC8, 2>(stream, p, out, ncu);
+  else sub_split_launch<FB_IN_GENERIC8, 1>(stream, p, out, ncu);
 }
 cf* fb_launch_sub_combine(hipStream_t stream, const FbGeom& g, cf* X, uint32_t nseqs, uint32_t ncu, cf* Xalt, cf* Xout, uint32_t mo, uint32_t rm)
 {

@@ -26,7 +26,7 @@ namespace dspsr_amd {
 // order and launches are stream ordered, so every (chan, bin) sum has the association order of the CPU loop
 // Fold.C:844-852, exactly as the stand-alone fold kernel (fold.hip) -- bit-identical results, without the
 // 16 B/sample round trip of the detected time series through HBM.
-// EPI: 0 = complex or detected output written by the last stage; 1 (FOLD) = fused fold; 2 = search mode (FbOut kind 5): square-law
+// EPI: 0 = complex or detected output written by the last stage; 1 (FOLD) = fused fold; 2 = search mode (FB_OUT_SEARCH): square-law
 // detection + time scrunch of the detected stream (digifil -F N:D, LoadToFil.C:185-222,250-304), staged like the fold's samples and
 // reduced by ts_reduce (fb_common.h).  Both walk the parts of a tile in order (the fold's profile, the scrunch's carry).
 // EPIP = EPI + 4 * PRESPLIT: the pre-split forms are k_inv_chan<., 4 | 5 | 6, .>, the others keep the names they had.  (As a
@@ -465,7 +465,7 @@ __global__ __launch_bounds__(512) void k_inv_chan(const FbGeom g, const cf* __re
         }
         return;
       }
-      if (out.kind == 0) return;
+      if (out.kind == FB_OUT_NONE) return;
       const uint32_t chan = out.chan0 + tile * T3 + (col >> 1);
       float* __restrict__ row = out.base + chan * out.chan_stride;
       // output sample of element k: t0 + k*pstride (kept when 0 <= t < nkeep); the addresses are a base plus a
@@ -474,7 +474,7 @@ __global__ __launch_bounds__(512) void k_inv_chan(const FbGeom g, const cf* __re
       float2* __restrict__ o2 = (float2*)(row + part * out.part_step) + t0;
       float4* __restrict__ o4 = (float4*)row + ((int64_t)(part * g.nkeep) + t0);
       // the output kind / layout is uniform: chosen once, outside the unrolled element loop (no branch per element)
-      if (out.kind == 1) {
+      if (out.kind == FB_OUT_COMPLEX) {
         const bool two = g.npol == 2;
 #pragma unroll
         for (int k = 0; k < R; k++) {

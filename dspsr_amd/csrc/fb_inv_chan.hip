@@ -5,7 +5,7 @@ namespace dspsr_amd {
 
 // freq_res = R * 2^k, last step: y[n] = sum_r exp(+2 pi i r n / freq_res) y_r[n mod M'] for the kept samples n of every channel and
 // part, from the pseudo-channels' whole transforms Y[c*R + r][pol][part][M'] (written by the inverse pass as complex rows), into
-// the caller's output: complex rows (kind 1) or detected samples (kind 2; Detection.C:423-474 layouts as in k_inv_chan).
+// the caller's output: complex rows (FB_OUT_COMPLEX) or detected samples (FB_OUT_DETECTED; Detection.C:423-474 layouts as in k_inv_chan).
 // RT = 0: the factor at run time (p.tw.R: any odd number <= ODD_MAX)
 template <int RT>
 __global__ __launch_bounds__(256) void k_time_combine(const TimeCombine p, const FbOut out)
@@ -36,11 +36,11 @@ __global__ __launch_bounds__(256) void k_time_combine(const TimeCombine p, const
     const uint64_t part = p.part0 + (uint64_t)lp * p.part_stride;
     const uint32_t chan = out.chan0 + c;
     float* __restrict__ row = out.base + chan * out.chan_stride;
-    if (out.kind == 1) {
+    if (out.kind == FB_OUT_COMPLEX) {
       float2* __restrict__ o = (float2*)(row + part * out.part_step) + t;
       *o = a;
       if (p.npol == 2) *(float2*)((float*)o + out.pol_stride) = b;
-    } else if (out.kind == 2) {
+    } else if (out.kind == FB_OUT_DETECTED) {
       float q[4];
       detect4(a, b, out.state, q);
       const uint64_t idat = part * p.nkeep + t;

@@ -1,4 +1,4 @@
-// k_inv_chan with the search-mode epilogue: square-law detection + time scrunch inside the inverse pass (FbOut kind 5)
+// k_inv_chan with the search-mode epilogue: square-law detection + time scrunch inside the inverse pass (FB_OUT_SEARCH)
 #include "fb_inv_chan.h"
 
 namespace dspsr_amd {

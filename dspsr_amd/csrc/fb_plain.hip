@@ -20,7 +20,7 @@ namespace dspsr_amd {
 struct PlainParams {
   FbGeom g;                 // (real_input, npol)
   FbIn in;
-  FbOut out;                // kind 0 (none), 1 (complex rows), 2 (detected)
+  FbOut out;                // FB_OUT_NONE, FB_OUT_COMPLEX or FB_OUT_DETECTED
   const cf* kern;           // [input_nchan][C] or null
   uint64_t in_chan_stride;  // float rows: floats from one input channel's rows to the next
   uint64_t npart;
@@ -78,9 +78,9 @@ __global__ __launch_bounds__(512) void k_fb_plain(const PlainParams p, const cf*
 
   // the input form (uniform)
   int form;
-  if (MODE == 0 || MODE == 3) form = p.in.kind == 0 ? F_FLOAT : p.in.kind == 2 ? F_CASPSR : (p.in.nchan == 1 && (((uintptr_t)p.in.base) & 3) == 0) ? F_WORD : F_BYTES;
-  else if (MODE == 1) form = p.in.kind == 0 ? F_FLOAT : F_BYTES;
-  else form = p.in.kind == 0 ? F_FLOAT : p.in.kind == 4 ? F_UWB : (((uintptr_t)p.in.base) & 1) == 0 ? F_HALF : F_BYTES;
+  if (MODE == 0 || MODE == 3) form = p.in.kind == FB_IN_FLOAT ? F_FLOAT : p.in.kind == FB_IN_CASPSR ? F_CASPSR : (p.in.nchan == 1 && (((uintptr_t)p.in.base) & 3) == 0) ? F_WORD : F_BYTES;
+  else if (MODE == 1) form = p.in.kind == FB_IN_FLOAT ? F_FLOAT : F_BYTES;
+  else form = p.in.kind == FB_IN_FLOAT ? F_FLOAT : p.in.kind == FB_IN_UWB16 ? F_UWB : (((uintptr_t)p.in.base) & 1) == 0 ? F_HALF : F_BYTES;
   const uint64_t last_part = p.npart - 1;
   // columns of element (g2, i) of this thread: pair index, position; the parts of a ragged last tile are clamped to the last part
   // (loaded again, never stored), so no load is conditional
@@ -321,12 +321,12 @@ __global__ __launch_bounds__(512) void k_fb_plain(const PlainParams p, const cf*
     // part tile*T + 2j + h (one)
     auto emit = [&](const uint32_t k, const uint32_t j, cf a, cf b) {
       if (kern) { const cf w = kern[k]; a = cmul(a, w); b = cmul(b, w); }            // Response::operate, Response.C:385-444
-      if (out.kind == 0) return;
+      if (out.kind == FB_OUT_NONE) return;
       float* __restrict__ row = out.base + (uint64_t)(chan0 + k) * out.chan_stride;
       if (two_pol) {
         const uint64_t part = (uint64_t)tile * hT + j;
         if (part >= p.npart) return;
-        if (out.kind == 1) {
+        if (out.kind == FB_OUT_COMPLEX) {
           float2* o = (float2*)(row + part * out.part_step);
           *o = a;
           *(float2*)((float*)o + out.pol_stride) = b;
@@ -431,9 +431,9 @@ template <int... I> static kplain_t pick_plain(int logf, int mode, iseq<I...>)
 // (2^14-point tiles hold 4 parts of two polarisations there, 8 parts of one), complex rows only.  Measured per 2^29 samples, two-
 // polarisation / split tiles: 1024 channels 1.95 / 2.00 ms (64 against 128 bytes per row: not what bounds it), 2048 channels 3.34 / 2.59,
 // 8192 channels 11.9 / 8.3 (profiles/r05_experiments.txt item 8)
-static bool plain_pol_split(int logC, bool real_input, uint32_t npol, int out_kind)
+static bool plain_pol_split(int logC, bool real_input, uint32_t npol, FbOutKind out_kind)
 {
-  return real_input && npol == 2 && logC >= 11 && (out_kind == 0 || out_kind == 1);
+  return real_input && npol == 2 && logC >= 11 && (out_kind == FB_OUT_NONE || out_kind == FB_OUT_COMPLEX);
 }
 
 int fb_plain_check(dspsr_amd_ctx* ctx, int logC, bool real_input, uint32_t npol, size_t* lds_bytes)
@@ -445,7 +445,7 @@ int fb_plain_check(dspsr_amd_ctx* ctx, int logC, bool real_input, uint32_t npol,
   const size_t lds = lds_total_words_host(1u << lp, logC) * sizeof(cf);
   if (lds_bytes) *lds_bytes = lds;
   hipError_t e = dspsr_amd_allow_lds((const void*)k, lds);
-  if (e == hipSuccess && plain_pol_split(logC, real_input, npol, 1))
+  if (e == hipSuccess && plain_pol_split(logC, real_input, npol, FB_OUT_COMPLEX))
     e = dspsr_amd_allow_lds((const void*)pick_plain(logC, 3, mkseq<MAX_LOGF>::type()),
                             lds_total_words_host(1u << plain_log_points(logC, 3), logC) * sizeof(cf));
   return e == hipSuccess ? DSPSR_AMD_OK : DSPSR_AMD_EHIP;

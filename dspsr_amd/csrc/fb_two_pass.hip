@@ -406,13 +406,13 @@ __global__ __launch_bounds__(512) void k_rows_inv(const FbGeom g, const cf* __re
         }
         return;
       }
-      if (out.kind == 0) return;
+      if (out.kind == FB_OUT_NONE) return;
       const uint32_t chan = out.chan0 + chan_of(tile, col >> 1);
       float* __restrict__ row = out.base + chan * out.chan_stride;
       const int32_t t0 = (int32_t)p - (int32_t)g.nfilt_pos;
       float2* __restrict__ o2 = (float2*)(row + part * out.part_step) + t0;
       float4* __restrict__ o4 = (float4*)row + ((int64_t)(part * g.nkeep) + t0);
-      if (out.kind == 1) {
+      if (out.kind == FB_OUT_COMPLEX) {
 #pragma unroll
         for (int k = 0; k < R; k++) {
           if ((uint32_t)(t0 + (int32_t)(k * pstride)) >= g.nkeep) continue;

@@ -1,6 +1,7 @@
 // Convolving filterbank (dsp::Filterbank -F N:D), host side: geometry, kernel choice and the launch sequence per call.
 // Kernels: fb_fwd_cols.hip, fb_fwd_rows.hip, fb_inv_chan*.hip, fb_two_pass.hip, fb_four_pass.hip; shared: fb_common.h
 #include "fb_common.h"
+#include "fb_rows.h"
 #include <initializer_list>
 
 namespace dspsr_amd {
@@ -10,14 +11,16 @@ constexpr int LOG_POINTS_DEFAULT = 14;  // points per workgroup (32 per thread, 
 static inline int ilog2(uint64_t v) { int l = 0; while ((1ull << l) < v) l++; return l; }
 static inline bool ispow2(uint64_t v) { return v && !(v & (v - 1)); }
 
+// One pass as the host launches it (fb_launch): the kernel chosen for this geometry (nullptr: there is none), its workgroup, its
+// dynamic LDS and how many of its workgroups a compute unit holds -- the persistent grid is at most ncu * wg_per_cu
+template <class K> struct FbPass { K kern; uint32_t threads; size_t lds; uint32_t wg_per_cu; };
+
 struct dspsr_amd_filterbank_impl {
   dspsr_amd_ctx* ctx;
   dspsr_amd_filterbank_config cfg;
   FbGeom g;
   uint64_t N, L;
-  uint32_t nseq, max_parts;
-  uint32_t nt1, nt2, nt3, nt4 = 0, ncu, wg3 = 1, wg1 = 1;
-  size_t lds1, lds2, lds3, lds4 = 0;
+  uint32_t nseq, max_parts, ncu;
   uint64_t part_elems = 0;    // scratch elements per part
   cf* A = nullptr;
   cf* X = nullptr;
@@ -26,37 +29,32 @@ struct dspsr_amd_filterbank_impl {
   cf* tw_lo_m = nullptr;
   uint16_t* Rt = nullptr;   // pre-transposed 8-bit pairs of the parts of one launch group
   PlanSlot* plan_wait = nullptr;             // fold plan on its way to the device: the first kernel that reads it waits (fold_plan_wait)
-  k1_t k1d_w1 = nullptr, k1d_w4 = nullptr;   // pass 1 on pairs of tiles (64-byte A runs otherwise), see k_fwd_cols_dual
   float* det = nullptr;     // detected block of perform_fold when the fused kernel would not fill the chip
   size_t det_floats = 0;
   bool kernel_set = false;
   float4* rmatrix = nullptr;  // matrix response (set_response_matrix): nchan_subband * freq_res bins of two float4, (f11, f21) (f22, f12)
-  k3_t k3m = nullptr;         // ... its inverse pass (fb_pick3m; LDS limit set by the first set_response_matrix)
-  // kernels of this geometry, chosen and given their dynamic-LDS limit once, at create time
-  k1_t k1_w1 = nullptr, k1_w4 = nullptr;                     // pass 1: one word per sample pair / generic loads
-  k2_t k2 = nullptr;
-  k3_t k3 = nullptr, k3f = nullptr, k3s = nullptr;           // inverse pass: plain, fused fold, search mode (FbOut kind 5)
-  k3a_t k3a = nullptr;
-  k3b_t k3b = nullptr;
+  // the passes of this geometry: shapes from fb_tile, kernels chosen and given their dynamic-LDS limit once, at create time
+  FbPass<k1_t> p1_w1 = {}, p1_w4 = {};       // pass 1: one word per sample pair / generic loads
+  FbPass<k1_t> p1d_w1 = {}, p1d_w4 = {};     // ... on pairs of tiles (64-byte A runs otherwise), see k_fwd_cols_dual
+  FbPass<k2_t> p2 = {};
+  FbPass<k3_t> p3 = {}, p3f = {}, p3s = {};  // inverse pass: plain, fused fold (the plan in LDS behind the tile), search mode
+  FbPass<k3_t> p3m = {};                     // ... with the matrix response (fb_pick3m; set by the first set_response_matrix)
+  FbPass<k3a_t> p3a = {};                    // four-pass geometry: the first inverse pass
+  FbPass<k3b_t> p3b = {}, p3bf = {};         // ... the second one, plain / leaving fold segment sums (FB_OUT_SEGSUM)
   float* fpart = nullptr;    // segmented fused fold: partial profiles of the part runs 1 .. nseg-1 of a launch
   size_t fpart_floats = 0;
   uint32_t plan_cap = 0;     // fused fold: plan entries per LDS buffer behind the twiddle tables
-  size_t lds3f = 0;          // dynamic LDS of the fused inverse pass
   // two-pass path of short responses (complex dual-pol 8-bit input, nchan_subband * freq_res^2 == 2^27): see fb_two_pass.hip
   uint8_t* dsub = nullptr;    // nsub > 1: the launch group's samples de-interleaved into nsub blocks (k_sub_split)
   size_t dsub_bytes = 0;
   bool two_pass = false;
-  bool presplit = false;      // three-pass path on the pre-split spectrum (fb_takes_presplit): k1_*, k2, k3* are the kernels of that form
-  FbGeom g1t;                 // ... pass 1 of Fa < 2^14 through k_raw_transpose + k_fwd_cols: their geometry (M = Fa, Rr = Fb, T2 = freq_res)
-  k1_t k1t = nullptr;
-  uint32_t nt1t = 0;
-  size_t lds1t = 0;
-  k1c_t k1c = nullptr;
-  k3_t k2r = nullptr, k2rf = nullptr, k2rs = nullptr;
-  size_t lds1c = 0, lds2r = 0, lds2rf = 0;
+  bool presplit = false;      // three-pass path on the pre-split spectrum (fb_takes_presplit): p1_*, p2, p3* are the kernels of that form
+  FbPass<k1c_t> p1c = {};     // two-pass path, Fa = 2^14: pass 1 on whole columns
+  FbGeom g1t;                 // ... Fa < 2^14: through k_raw_transpose + k_fwd_cols, their geometry (M = Fa, Rr = Fb, T2 = freq_res)
+  FbPass<k1_t> p1t = {};
+  FbPass<k3_t> p2r = {}, p2rf = {}, p2rs = {};   // ... rows + inverse pass: plain, fused fold, search mode
   uint32_t plan_cap2 = 0;
-  k3b_t k3bf = nullptr;      // four-pass fused fold: second inverse pass that leaves segment sums (FbOut kind 4)
-  float* msum = nullptr;     // ... [chan][part][tile][t2][2] float4 of one input channel's sub-band and one block
+  float* msum = nullptr;     // four-pass fused fold: segment sums [chan][part][tile][t2][2] float4 of one input channel's sub-band and one block
   size_t msum_floats = 0;
   // freq_res = 3 * 2^k / 5 * 2^k (msub = 3, 5; see k_time_combine): g and everything above describe the INNER filterbank of
   // nchan_subband * msub pseudo-channels with freq_res / msub bins and the whole transform kept; cfg and these the caller's
@@ -91,13 +89,11 @@ static int fb_fail(dspsr_amd_ctx* ctx, int code, const char* fmt, ...)
   return code;
 }
 
-// dynamic-LDS limits of a geometry's kernels, set in order up to the first failure; absent kernels (nullptr) are skipped
-struct LdsLimit { const void* kern; size_t bytes; template <typename K> LdsLimit(K k, size_t b) : kern((const void*)k), bytes(b) {} };
-static hipError_t allow_lds(std::initializer_list<LdsLimit> limits)
+// dynamic-LDS limits of a geometry's passes, set in order up to the first failure; absent kernels (nullptr) are skipped
+template <class... K> static hipError_t allow_lds(const FbPass<K>&... passes)
 {
   hipError_t e = hipSuccess;
-  for (const LdsLimit& l : limits)
-    if (l.kern && e == hipSuccess) e = dspsr_amd_allow_lds(l.kern, l.bytes);
+  ((e = passes.kern && e == hipSuccess ? dspsr_amd_allow_lds((const void*)passes.kern, passes.lds) : e), ...);
   return e;
 }
 
@@ -279,16 +275,22 @@ static int fb_tile(dspsr_amd_filterbank* fb)
       g.kblock = (uint32_t)((fb->N >> la) << g.logT2);
     }
   }
-  fb->nt1 = (uint32_t)(p1 / PTS);
-  fb->nt2 = (uint32_t)(p2 / PTS);
-  fb->nt3 = (uint32_t)(p3 / PTS);
-  fb->nt4 = (uint32_t)(p4 / PTS);
-  fb->lds1 = lds_total_words_host((uint32_t)p1, g.logM) * sizeof(cf);
-  fb->lds2 = lds_total_words_host((uint32_t)p2, g.logR) * sizeof(cf);
-  fb->lds3 = lds_total_words_host((uint32_t)p3, g.four_pass ? g.logMa : g.logM) * sizeof(cf);
-  fb->lds4 = g.four_pass ? lds_total_words_host((uint32_t)p4, g.logMb) * sizeof(cf) : 0;
-  fb->wg3 = (!g.four_pass && 2 * fb->lds3 + 1024 <= 160 * 1024) ? 2 : 1;      // workgroups per compute unit (small tiles: two)
-  fb->wg1 = (2 * fb->lds1 + 1024 <= 160 * 1024 && fb->nt1 <= 256) ? 2 : 1;
+  // a tile of `points` points transformed over 2^logn: PTS points per thread; workgroups per compute unit: two of a small tile
+  auto shape = [](auto& pass, uint64_t points, int logn, bool two_fit) {
+    pass = {nullptr, (uint32_t)(points / PTS), lds_total_words_host((uint32_t)points, logn) * sizeof(cf), 1};
+    if (two_fit && 2 * pass.lds + 1024 <= 160 * 1024) pass.wg_per_cu = 2;
+  };
+  shape(fb->p1_w1, p1, g.logM, p1 / PTS <= 256);
+  fb->p1_w4 = fb->p1d_w1 = fb->p1d_w4 = fb->p1_w1;
+  shape(fb->p2, p2, g.logR, false);
+  if (g.four_pass) {
+    shape(fb->p3a, p3, g.logMa, false);
+    shape(fb->p3b, p4, g.logMb, false);
+    fb->p3bf = fb->p3b;
+  } else {
+    shape(fb->p3, p3, g.logM, true);
+    fb->p3f = fb->p3s = fb->p3m = fb->p3;
+  }
   return DSPSR_AMD_OK;
 }
 
@@ -314,35 +316,31 @@ static int fb_pick_kernels(dspsr_amd_filterbank* fb)
   // two-column tiles of 2^13 rows whose A runs would be half cache lines: transformed in pairs (k_fwd_cols_dual)
   const bool dual = full1 && g.logM == 13 && g.logT1 == 1 && g.logT1 + g.logT2 < 4 && g.logR >= 2;
   const bool ps = fb->presplit = fb_takes_presplit(fb, dual);
-  fb->k1_w1 = ps ? fb_pick1_rm(g.logM, 1, full1) : fb_pick1(g.logM, 1, full1);
-  fb->k1_w4 = ps ? fb_pick1_rm(g.logM, 4, full1) : fb_pick1(g.logM, 4, full1);
-  if (dual) {
-    fb->k1d_w1 = fb_pick1_dual(1);
-    fb->k1d_w4 = fb_pick1_dual(4);
-  }
-  fb->k2 = fb_pick2(g.logR, full2, ps);
+  fb->p1_w1.kern = ps ? fb_pick1_rm(g.logM, 1, full1) : fb_pick1(g.logM, 1, full1);
+  fb->p1_w4.kern = ps ? fb_pick1_rm(g.logM, 4, full1) : fb_pick1(g.logM, 4, full1);
+  fb->p1d_w1.kern = dual ? fb_pick1_dual(1) : nullptr;
+  fb->p1d_w4.kern = dual ? fb_pick1_dual(4) : nullptr;
+  fb->p2.kern = fb_pick2(g.logR, full2, ps);
   if (g.four_pass) {
-    fb->k3a = fb_pick3a(g.logMa, g.xblocked != 0, g.real_input != 0, g.logTm == 13 - g.logMa && g.logMa <= 12 && fb->nt3 == 512);
-    const bool full4 = g.logTt == 13 - g.logMb && g.logMb <= 12 && fb->nt4 == 512;
-    fb->k3b = fb_pick3b(g.logMb, false, full4);
-    fb->k3bf = fb_pick3b(g.logMb, true, full4);
+    fb->p3a.kern = fb_pick3a(g.logMa, g.xblocked != 0, g.real_input != 0, g.logTm == 13 - g.logMa && g.logMa <= 12 && fb->p3a.threads == 512);
+    const bool full4 = g.logTt == 13 - g.logMb && g.logMb <= 12 && fb->p3b.threads == 512;
+    fb->p3b.kern = fb_pick3b(g.logMb, false, full4);
+    fb->p3bf.kern = fb_pick3b(g.logMb, true, full4);
   } else {
-    fb->k3 = fb_pick3(g.logM, full3, ps);
-    fb->k3f = fb_pick3f(g.logM, full3, ps);
-    fb->k3s = fb_pick3s(g.logM, full3, ps);
+    fb->p3.kern = fb_pick3(g.logM, full3, ps);
+    fb->p3f.kern = fb_pick3f(g.logM, full3, ps);
+    fb->p3s.kern = fb_pick3s(g.logM, full3, ps);
     // fused fold: the LDS left over behind the twiddle tables holds the part's fold plan (two buffers)
-    const FbPlanLds pl = fb_plan_lds(fb->lds3, fb->nt3);   // one plan entry per thread of the workgroup (nt3 <= 512)
+    const FbPlanLds pl = fb_plan_lds(fb->p3.lds, fb->p3.threads);   // one plan entry per thread of the workgroup (<= 512)
     fb->plan_cap = pl.cap;
-    fb->lds3f = pl.lds;
+    fb->p3f.lds = pl.lds;
   }
-  if (!((fb->k1_w1 || fb->k1_w4) && fb->k2 && (g.four_pass ? (fb->k3a && fb->k3b) : (fb->k3 != nullptr))))
+  if (!((fb->p1_w1.kern || fb->p1_w4.kern) && fb->p2.kern && (g.four_pass ? (fb->p3a.kern && fb->p3b.kern) : (fb->p3.kern != nullptr))))
     return fb_fail(fb->ctx, DSPSR_AMD_EINVAL, "dspsr_amd_filterbank_create: no kernel for this geometry");
   // (the three passes of the pre-split form only work together: X' is not the X layout; it takes the L elements per part X has)
-  if (ps && !(fb->k1_w1 && fb->k1_w4 && fb->k3f && fb->k3s && fb->nseq == 1 && g.xstride == fb->L))
+  if (ps && !(fb->p1_w1.kern && fb->p1_w4.kern && fb->p3f.kern && fb->p3s.kern && fb->nseq == 1 && g.xstride == fb->L))
     return fb_fail(fb->ctx, DSPSR_AMD_EINVAL, "dspsr_amd_filterbank_create: no kernels for the pre-split spectrum of this geometry");
-  const hipError_t e = allow_lds({{fb->k1_w1, fb->lds1}, {fb->k1_w4, fb->lds1}, {fb->k1d_w1, fb->lds1}, {fb->k1d_w4, fb->lds1},
-                                  {fb->k2, fb->lds2}, {fb->k3, fb->lds3}, {fb->k3f, fb->lds3f}, {fb->k3s, fb->lds3},
-                                  {fb->k3a, fb->lds3}, {fb->k3b, fb->lds4}, {fb->k3bf, fb->lds4}});
+  const hipError_t e = allow_lds(fb->p1_w1, fb->p1_w4, fb->p1d_w1, fb->p1d_w4, fb->p2, fb->p3, fb->p3f, fb->p3s, fb->p3a, fb->p3b, fb->p3bf);
   if (e != hipSuccess)
     return fb_fail(fb->ctx, DSPSR_AMD_EHIP, "dspsr_amd_filterbank_create: hipFuncSetAttribute: %s", hipGetErrorString(e));
   return DSPSR_AMD_OK;
@@ -364,10 +362,9 @@ static void fb_setup_two_pass(dspsr_amd_filterbank* fb)
   hipError_t e = hipSuccess;
   bool have1 = false;
   if (lfa == 14) {
-    fb->k1c = fb_pick_col1();
-    fb->lds1c = lds_total_words_host(1u << 14, 12) * sizeof(cf);
-    have1 = fb->k1c != nullptr;
-    if (have1) e = allow_lds({{fb->k1c, fb->lds1c}});
+    fb->p1c = {fb_pick_col1(), 512, lds_total_words_host(1u << 14, 12) * sizeof(cf), 1};
+    have1 = fb->p1c.kern != nullptr;
+    if (have1) e = allow_lds(fb->p1c);
   } else {
     // pass 1 = the ordinary column pass on a geometry of its own: T1 adjacent columns nb per tile, A blocked by T2 = freq_res
     FbGeom& q = fb->g1t;
@@ -376,24 +373,22 @@ static void fb_setup_two_pass(dspsr_amd_filterbank* fb)
     q.logT1 = lfb < LOG_POINTS_DEFAULT - lfa ? lfb : LOG_POINTS_DEFAULT - lfa;
     q.logT2 = logMf;
     const uint64_t p1t = (1ull << lfa) << q.logT1;
-    fb->nt1t = (uint32_t)(p1t / PTS);
-    fb->lds1t = lds_total_words_host((uint32_t)p1t, lfa) * sizeof(cf);
-    fb->k1t = fb_pick1(lfa, 1, q.logT1 == full_logt(lfa));
-    have1 = fb->k1t != nullptr && q.logT1 >= 1 && p1t >= 32;
-    if (have1) e = allow_lds({{fb->k1t, fb->lds1t}});
+    fb->p1t = {fb_pick1(lfa, 1, q.logT1 == full_logt(lfa)), (uint32_t)(p1t / PTS), lds_total_words_host((uint32_t)p1t, lfa) * sizeof(cf), 1};
+    have1 = fb->p1t.kern != nullptr && q.logT1 >= 1 && p1t >= 32;
+    if (have1) e = allow_lds(fb->p1t);
   }
-  fb->k2r = fb_pick_rinv(logMf, 0);
-  fb->k2rf = fb_pick_rinv(logMf, 1);
-  fb->k2rs = fb_pick_rinv(logMf, 2);
-  if (!(have1 && fb->k2r && fb->k2rf)) return;
+  // rows + inverse pass: a full tile, 512 threads, one workgroup per compute unit; the fused fold's plan behind it
+  const size_t lds2r = lds_total_words_host(1u << 14, logMf) * sizeof(cf);
+  const FbPlanLds pl = fb_plan_lds(lds2r, 512);
+  fb->p2r = {fb_pick_rinv(logMf, 0), 512, lds2r, 1};
+  fb->p2rf = {fb_pick_rinv(logMf, 1), 512, pl.lds, 1};
+  fb->p2rs = {fb_pick_rinv(logMf, 2), 512, lds2r, 1};
+  if (!(have1 && fb->p2r.kern && fb->p2rf.kern)) return;
   g.logFb2 = lfb;
   g.logFa2 = lfa;
   fb->g1t.logFb2 = lfb; fb->g1t.logFa2 = lfa;
-  fb->lds2r = lds_total_words_host(1u << 14, logMf) * sizeof(cf);
-  const FbPlanLds pl = fb_plan_lds(fb->lds2r, 512);
   fb->plan_cap2 = pl.cap;
-  fb->lds2rf = pl.lds;
-  if (e == hipSuccess) e = allow_lds({{fb->k2r, fb->lds2r}, {fb->k2rf, fb->lds2rf}, {fb->k2rs, fb->lds2r}});
+  if (e == hipSuccess) e = allow_lds(fb->p2r, fb->p2rf, fb->p2rs);
   fb->two_pass = e == hipSuccess;
 }
 
@@ -464,7 +459,7 @@ static void fb_setup_conv(dspsr_amd_filterbank* fb)
   // per-channel geometry, inverse passes of a `group`-channel filterbank object (natural spectrum order) on the spectra laid side
   // by side.  Complex float32 rows read in place by pass 1; other inputs keep the loop over the channels.
   if (fb->conv1_logM < 0 && fb->conv3_logM < 0 && conv && cfg->input_nchan >= 4 && cfg->force_four_pass != 2 &&
-      g.four_pass && !g.xblocked && !(g.logR >= 6 && g.logT1 <= 4) && fb->k1_w4) {
+      g.four_pass && !g.xblocked && !(g.logR >= 6 && g.logT1 <= 4) && fb->p1_w4.kern) {
     uint32_t ch = 1;
     while (ch < 64 && cfg->input_nchan % (2 * ch) == 0) ch *= 2;
     // (scratch of the group object: max_parts x 2 x ch x freq_res elements per buffer; keep it near 2 GB)
@@ -479,7 +474,7 @@ static void fb_setup_conv(dspsr_amd_filterbank* fb)
       c2.max_parts = fb->max_parts;
       dspsr_amd_filterbank* inv = nullptr;
       if (dspsr_amd_filterbank_create(fb->ctx, &c2, &inv) == DSPSR_AMD_OK && inv) {
-        if (inv->g.four_pass && !inv->g.xblocked && inv->k3a && inv->k3b && inv->g.logMf == g.logMf) fb->batch = inv;
+        if (inv->g.four_pass && !inv->g.xblocked && inv->p3a.kern && inv->p3b.kern && inv->g.logMf == g.logMf) fb->batch = inv;
         else dspsr_amd_filterbank_destroy(inv);
       }
       fb->ctx->error[0] = 0;                   // (a refusal of the group object is not an error of this call)
@@ -629,13 +624,14 @@ extern "C" int dspsr_amd_filterbank_set_response_matrix(dspsr_amd_filterbank* fb
   if (nmatrix != fb->N)
     return fb_fail(fb->ctx, DSPSR_AMD_EINVAL, "%s: response has %llu matrices, expected nchan_subband*freq_res = %llu", fn,
                    (unsigned long long)nmatrix, (unsigned long long)fb->N);
-  if (!fb->k3m) {
+  if (!fb->p3m.kern) {
     const FbGeom& g = fb->g;
-    k3_t k = fb_pick3m(g.logM, g.logT3 + 1 == full_logt(g.logM), fb->presplit);
-    if (!k) return fb_fail(fb->ctx, DSPSR_AMD_EINVAL, "%s: no kernel for this geometry", fn);
-    const hipError_t e = allow_lds({{k, fb->lds3}});
+    FbPass<k3_t> pm = fb->p3m;
+    pm.kern = fb_pick3m(g.logM, g.logT3 + 1 == full_logt(g.logM), fb->presplit);
+    if (!pm.kern) return fb_fail(fb->ctx, DSPSR_AMD_EINVAL, "%s: no kernel for this geometry", fn);
+    const hipError_t e = allow_lds(pm);
     if (e != hipSuccess) return fb_fail(fb->ctx, DSPSR_AMD_EHIP, "%s: hipFuncSetAttribute: %s", fn, hipGetErrorString(e));
-    fb->k3m = k;
+    fb->p3m = pm;
   }
   const size_t bytes = (size_t)fb->N * 2 * sizeof(float4);
   float4* dev = fb->rmatrix;
@@ -674,14 +670,76 @@ extern "C" int dspsr_amd_filterbank_sizes(const dspsr_amd_filterbank* fb, uint64
   return DSPSR_AMD_OK;
 }
 
-static int raw_kind(int raw_layout) { return raw_layout == DSPSR_AMD_RAW_CASPSR ? 2 : raw_layout == DSPSR_AMD_RAW_UWB16 ? 4 : 1; }
+static FbInKind raw_kind(int layout) { return layout == DSPSR_AMD_RAW_CASPSR ? FB_IN_CASPSR : layout == DSPSR_AMD_RAW_UWB16 ? FB_IN_UWB16 : FB_IN_GENERIC8; }
 
+// ---- the output forms (fb_common.h FbOutKind): every field a builder does not name is zero ---------------------------------------
+static FbOut fb_out(FbOutKind kind, float* base, uint64_t chan_stride, uint64_t pol_stride, int state, uint32_t ndim)
+{
+  FbOut o = {};
+  o.kind = kind; o.base = base; o.chan_stride = chan_stride; o.pol_stride = pol_stride; o.state = state; o.ndim = ndim;
+  return o;
+}
+// complex rows, or nothing without a base
+static FbOut fb_out_rows(float* base, uint64_t chan_stride, uint64_t pol_stride, uint64_t part_step)
+{
+  FbOut o = fb_out(base ? FB_OUT_COMPLEX : FB_OUT_NONE, base, chan_stride, pol_stride, 0, 2);
+  o.part_step = part_step;
+  return o;
+}
+static FbOut fb_out_detected(float* base, uint64_t chan_stride, uint64_t pol_stride, int state, uint32_t ndim)
+{
+  return fb_out(FB_OUT_DETECTED, base, chan_stride, pol_stride, state, ndim);
+}
+// fused fold into the profile of `fold`: one float4 per bin, or (planes2) the two float2 rows (PP, QQ) and (Re, Im) per channel
+static FbOut fb_out_fold(dspsr_amd_fold* fold, int state, bool planes2, const uint32_t* pstart, const Interval* piv, uint32_t nparts)
+{
+  FbOut o = fb_out(FB_OUT_FOLD, fold->profile, 0, 0, state, 4);
+  o.nbin = fold->nbin; o.nchan_prof = fold->nchan; o.prof_planes = planes2 ? 2u : 1u; o.plane_stride = fold->span;
+  o.prof_span4 = planes2 ? fold->span / 2 : fold->span / 4;    // (float4 from one channel to the next: both rows of the channel, or one)
+  o.fold = fold; o.pstart = pstart; o.piv = piv; o.nparts_plan = nparts;
+  return o;
+}
+// segment sums of a block of nparts parts into msum: the fold form of a one-plane profile, with the segment plan
+static FbOut fb_out_segsum(float* msum, dspsr_amd_fold* fold, int state, const uint32_t* off, const Interval* siv, const uint32_t* blk_first,
+                           const uint32_t* bin_start, uint32_t nparts)
+{
+  FbOut o = fb_out_fold(fold, state, false, off, siv, nparts);
+  o.kind = FB_OUT_SEGSUM; o.base = msum; o.blk_first = blk_first; o.bin_start = bin_start;
+  return o;
+}
+static FbOut fb_out_search(float* base, uint64_t chan_stride, uint64_t pol_stride, int state, uint32_t tscrunch, uint32_t phase0, uint32_t G,
+                           float* carry)
+{
+  FbOut o = fb_out(FB_OUT_SEARCH, base, chan_stride, pol_stride, state, 1);
+  o.ts_sf = tscrunch; o.ts_phase0 = phase0; o.ts_G = G; o.ts_carry = carry;
+  // (tscrunch 1: 2^32 does not fit -- t / 1 = t is the special case of ts_stage)
+  o.ts_magic = tscrunch == 1 ? 0xffffffffu : (uint32_t)(((1ull << 32) + tscrunch - 1) / tscrunch);
+  return o;
+}
+// the forms every path has: complex or detected rows (or nothing) from the last pass
+static bool fb_out_is_rows(const FbOut& out) { return out.kind == FB_OUT_NONE || out.kind == FB_OUT_COMPLEX || out.kind == FB_OUT_DETECTED; }
+
+// ---- launches ----------------------------------------------------------------------------------------------------------------------
 static uint32_t grid_for(uint64_t items, uint32_t ncu)
 {
   uint64_t gsz = items < ncu ? items : ncu;
   if (gsz >= 8) gsz &= ~7ull;
   return (uint32_t)gsz;
 }
+// one pass on `grid` workgroups, on the object's stream
+template <class K, class... A>
+static void fb_launch_grid(const dspsr_amd_filterbank* fb, const FbPass<K>& p, uint32_t grid, const A&... args)
+{
+  hipLaunchKernelGGL(p.kern, dim3(grid), dim3(p.threads), p.lds, fb->ctx->stream, args...);
+}
+// ... as a persistent grid over `items` work items: the workgroups the chip holds, a multiple of 8 so that the XCD-aware item order applies
+template <class K, class... A>
+static void fb_launch(const dspsr_amd_filterbank* fb, const FbPass<K>& p, uint64_t items, const A&... args)
+{
+  fb_launch_grid(fb, p, grid_for(items, fb->ncu * p.wg_per_cu), args...);
+}
+// items of the inverse pass: a (tile of channels, part) each; search mode: one workgroup per tile walks the parts in order
+static uint64_t fb_inverse_items(const FbOut& out, uint32_t tiles, uint32_t parts) { return out.kind == FB_OUT_SEARCH ? tiles : (uint64_t)tiles * parts; }
 
 static int fb_launch_status(dspsr_amd_ctx* ctx)
 {
@@ -698,18 +756,21 @@ static int fb_plan_ready(dspsr_amd_filterbank* fb, dspsr_amd_fold* fold)
   return rc;
 }
 
+// whether a call's fused fold is the segmented one
+static bool fb_fold_segmented(const dspsr_amd_filterbank* fb, const FbOut& out) { return out.kind == FB_OUT_FOLD && dspsr_amd_filterbank_fold_is_fused(fb) == 2; }
+
 // Fused inverse pass of one launch (ns parts starting at part0).  With fewer channel tiles than compute units the parts
 // are cut into runs folded by different workgroups (k_inv_chan, "Segmented"): partial profiles zeroed before, added to the
-// profile in run order after the launch.  segmented == false: one workgroup owns a tile for all parts (exact time order).
-static int fb_launch_fused(dspsr_amd_filterbank* fb, k3_t k3, const cf* X, const cf* kern, FbOut co, uint64_t part0, uint32_t ns,
-                           bool segmented, bool two_pass = false)
+// profile in run order after the launch.  Not segmented: one workgroup owns a tile for all parts (exact time order).
+static int fb_launch_fused(dspsr_amd_filterbank* fb, const FbPass<k3_t>& p3, const cf* X, const cf* kern, FbOut co, uint64_t part0,
+                           uint32_t ns, bool two_pass = false)
 {
   dspsr_amd_ctx* ctx = fb->ctx;
   const FbGeom& g = fb->g;
-  // (two-pass path: the tile is Fb = 2^logFb2 channels, one 512-thread workgroup per compute unit)
-  const uint32_t tiles = two_pass ? g.C >> g.logFb2 : g.C >> g.logT3, wgs = two_pass ? fb->ncu : fb->ncu * fb->wg3;
+  // (two-pass path: the tile is Fb = 2^logFb2 channels)
+  const uint32_t tiles = two_pass ? g.C >> g.logFb2 : g.C >> g.logT3, wgs = fb->ncu * p3.wg_per_cu;
   uint32_t nseg = 1;
-  if (segmented && tiles < wgs) {
+  if (fb_fold_segmented(fb, co) && tiles < wgs) {
     nseg = wgs / tiles;
     if (nseg > ns) nseg = ns;
     if (nseg > 16) nseg = 16;
@@ -729,11 +790,12 @@ static int fb_launch_fused(dspsr_amd_filterbank* fb, k3_t k3, const cf* X, const
       return fb_fail(ctx, DSPSR_AMD_EHIP, "dspsr_amd_filterbank_perform_fold: hipMemsetAsync failed");
     co.part = fb->fpart;
   }
-  const uint32_t grid = nseg > 1 ? tiles * nseg : grid_for(tiles, wgs);
-  hipLaunchKernelGGL(k3, dim3(grid), dim3(two_pass ? 512u : fb->nt3), two_pass ? fb->lds2rf : fb->lds3f, ctx->stream, g, X, kern, co,
-                     ctx->tw, part0, ns, ns);
-  if (nseg > 1) return fold_combine_partials(co.fold, "fused fold: combine", fb->fpart, nseg - 1, co.chan0, g.C);
-  return DSPSR_AMD_OK;
+  if (nseg == 1) {
+    fb_launch(fb, p3, tiles, g, X, kern, co, ctx->tw, part0, ns, ns);
+    return DSPSR_AMD_OK;
+  }
+  fb_launch_grid(fb, p3, tiles * nseg, g, X, kern, co, ctx->tw, part0, ns, ns);      // (a workgroup per tile and run)
+  return fold_combine_partials(co.fold, "fused fold: combine", fb->fpart, nseg - 1, co.chan0, g.C);
 }
 
 // output channels per input channel / kept samples per part as the caller sees them (freq_res = 3 * 2^k / 5 * 2^k: g describes the
@@ -783,12 +845,11 @@ static int fb_run_batched(dspsr_amd_filterbank* fb, const FbIn& in, const FbOut&
       ci.chan_stride_c = chan_stride / 2;
       ci.nchan = 1; ci.ichan = 0;
       const uint64_t n1 = (uint64_t)(Rr >> gf.logT1) * nvp, n2 = (uint64_t)(M >> gf.logT2) * nvp;
-      hipLaunchKernelGGL(fb->k1_w4, dim3(grid_for(n1, fb->ncu * fb->wg1)), dim3(fb->nt1), fb->lds1, ctx->stream, gf, ci, inv->A, ctx->tw, part0,
-                         nvp, 1u, 32u);
-      hipLaunchKernelGGL(fb->k2, dim3(grid_for(n2, fb->ncu)), dim3(fb->nt2), fb->lds2, ctx->stream, gf, inv->A, inv->X, ctx->tw, nvp, 1u, 4u);
+      fb_launch(fb, fb->p1_w4, n1, gf, ci, inv->A, ctx->tw, part0, nvp, 1u, 32u);
+      fb_launch(fb, fb->p2, n2, gf, inv->A, inv->X, ctx->tw, nvp, 1u, 4u);
       const uint64_t n3a = ((uint64_t)gi.C << (gi.logMb - gi.logTm)) * nb, n3b = ((uint64_t)gi.C << (gi.logMa - gi.logTt)) * nb;
-      hipLaunchKernelGGL(inv->k3a, dim3(grid_for(n3a, fb->ncu)), dim3(inv->nt3), inv->lds3, ctx->stream, gi, inv->X, kern, inv->A, ctx->tw, nb, 8u);
-      hipLaunchKernelGGL(inv->k3b, dim3(grid_for(n3b, fb->ncu)), dim3(inv->nt4), inv->lds4, ctx->stream, gi, inv->A, co, ctx->tw, part0, nb, 8u);
+      fb_launch(fb, inv->p3a, n3a, gi, inv->X, kern, inv->A, ctx->tw, nb, 8u);
+      fb_launch(fb, inv->p3b, n3b, gi, inv->A, co, ctx->tw, part0, nb, 8u);
     }
   }
   return fb_launch_status(ctx);
@@ -797,8 +858,8 @@ static int fb_run_batched(dspsr_amd_filterbank* fb, const FbIn& in, const FbOut&
 // the non-convolving filterbank (fb_plain.hip): one launch per call
 static int fb_run_plain(dspsr_amd_filterbank* fb, const FbIn& in, const FbOut& out, uint64_t npart, uint64_t chan_stride)
 {
-  if (out.kind != 0 && out.kind != 1 && out.kind != 2)
-    return fb_fail(fb->ctx, DSPSR_AMD_EINVAL, "dspsr_amd_filterbank_perform: output kind %d has no non-convolving form", out.kind);
+  if (!fb_out_is_rows(out))
+    return fb_fail(fb->ctx, DSPSR_AMD_EINVAL, "dspsr_amd_filterbank_perform: output kind %d has no non-convolving form", (int)out.kind);
   const int rc = fb_plain_launch(fb->ctx, fb->plain_logC, fb->g.real_input != 0, (uint32_t)fb->g.npol, fb->cfg.input_nchan, fb->kernel, in,
                                  out, chan_stride, npart);
   return rc == DSPSR_AMD_OK ? rc : fb_fail(fb->ctx, rc, "dspsr_amd_filterbank_perform: launch of the non-convolving filterbank failed");
@@ -844,14 +905,14 @@ static int fb_run_conv3(dspsr_amd_filterbank* fb, const FbIn& in, const FbOut& o
   return DSPSR_AMD_OK;
 }
 
-// the two-pass path of short responses takes exactly this input form (and out.kind 0..3; the four-pass segment sums never
+// the two-pass path of short responses takes exactly this input form (and every output form; the four-pass segment sums never
 // apply: freq_res <= 4096)
 // (whole columns, Fa = 2^14: k_raw_cols also takes blocks of several input channels; Fa < 2^14 goes through k_raw_transpose)
 static bool fb_takes_two_pass(const dspsr_amd_filterbank* fb, const FbIn& in, const FbOut& out)
 {
   const FbGeom& g = fb->g;
-  return fb->two_pass && !fb->rmatrix && in.kind == 1 && !g.real_input && g.npol == 2 && out.kind != 4 && (in.part_step % 4) == 0 &&
-         (fb->k1c ? ((uintptr_t)in.base % (fb->cfg.input_nchan == 1 ? 16 : 4)) == 0
+  return fb->two_pass && !fb->rmatrix && in.kind == FB_IN_GENERIC8 && !g.real_input && g.npol == 2 && out.kind != FB_OUT_SEGSUM && (in.part_step % 4) == 0 &&
+         (fb->p1c.kern ? ((uintptr_t)in.base % (fb->cfg.input_nchan == 1 ? 16 : 4)) == 0
                   : (fb->cfg.input_nchan == 1 && ((uintptr_t)in.base % 16) == 0));
 }
 
@@ -866,26 +927,33 @@ static int fb_pass1(dspsr_amd_filterbank* fb, const FbIn& in, uint64_t chan_stri
   const uintptr_t base = (uintptr_t)in.base;
   // 8-bit real dual-pol single-channel input: one 32-bit word per sample pair; regroup it per tile first
   // (k_raw_transpose) unless the rows are already long enough or the layout preconditions fail
-  const bool fast8 = (in.kind == 1 || in.kind == 2) && g.real_input && g.npol == 2 && in.nchan == 1 && (base % 4) == 0;
+  const bool fast8 = (in.kind == FB_IN_GENERIC8 || in.kind == FB_IN_CASPSR) && g.real_input && g.npol == 2 && in.nchan == 1 && (base % 4) == 0;
   // complex dual-pol generic order: the same regroup per polarisation; pass 1 then reads (re, im) byte pairs exactly
   // like the (pol0, pol1) pairs of real input, one aligned word per two columns
-  const bool fastc = in.kind == 1 && !g.real_input && g.npol == 2 && in.nchan == 1 && (base % 16) == 0 && (in.part_step % 4) == 0 &&
+  const bool fastc = in.kind == FB_IN_GENERIC8 && !g.real_input && g.npol == 2 && in.nchan == 1 && (base % 16) == 0 && (in.part_step % 4) == 0 &&
                      g.logR >= 3;
   bool raw = two || ((fast8 || fastc) && g.logR >= 2 && g.logT1 <= 5);   // rows of >= 128 B need no regrouping
   // (CASPSR blocks need a part step % 4 == 0; so do the sub-band path's 8-bit real sub-sequences, generic 8-bit real blocks in
   //  the other paths do not -- the two conditions differ and are kept as they are)
-  if (raw && (in.kind == 2 || sub) && (in.part_step % 4) != 0) raw = false;
+  if (raw && (in.kind == FB_IN_CASPSR || sub) && (in.part_step % 4) != 0) raw = false;
   // float32 rows (what Filterbank::Engine::perform is given): regrouped likewise, 8-byte elements
-  const bool flt = in.kind == 0 && g.npol == 2 && g.logR >= 6 && g.logM >= 1 && g.logT1 >= 1 && g.logT1 <= 4 && (base % 16) == 0 &&
+  const bool flt = in.kind == FB_IN_FLOAT && g.npol == 2 && g.logR >= 6 && g.logM >= 1 && g.logT1 >= 1 && g.logT1 <= 4 && (base % 16) == 0 &&
                    (in.part_step % 4) == 0 && (in.pol_stride % 4) == 0 && (chan_stride % 4) == 0;
-  *p1 = {raw ? FB_REGROUP_RAW : flt ? FB_REGROUP_FLOAT : FB_REGROUP_NONE, (raw || (fast8 && in.kind == 1)) ? 1 : 4};
+  *p1 = {raw ? FB_REGROUP_RAW : flt ? FB_REGROUP_FLOAT : FB_REGROUP_NONE, (raw || (fast8 && in.kind == FB_IN_GENERIC8)) ? 1 : 4};
   if (raw && !fb->Rt && hipMalloc((void**)&fb->Rt, (size_t)fb->max_parts * fb->nseq * fb->L * sizeof(uint16_t)) != hipSuccess)
     return fb_fail(fb->ctx, DSPSR_AMD_ENOMEM, "dspsr_amd_filterbank_perform: hipMalloc of the 8-bit regroup buffer failed");
   return DSPSR_AMD_OK;
 }
 
-// the kernels of the multi-pass paths for a pass-1 load width and output kind (nullptr where the geometry has none)
-struct FbPassKernels { k1_t k1, k1d; k3_t k3; k3b_t k3b; };
+// the passes of the multi-pass paths that depend on the call: pass 1 for its load width, the (last) inverse pass for the output form
+// and the response (kern nullptr where the geometry has none)
+struct FbPassKernels { FbPass<k1_t> p1, p1d; FbPass<k3_t> p3; FbPass<k3b_t> p3b; };
+static FbPassKernels fb_pass_kernels(const dspsr_amd_filterbank* fb, const FbPass1& p1, const FbOut& out)
+{
+  return {p1.raww == 1 ? fb->p1_w1 : fb->p1_w4, p1.raww == 1 ? fb->p1d_w1 : fb->p1d_w4,
+          out.kind == FB_OUT_FOLD ? fb->p3f : out.kind == FB_OUT_SEARCH ? fb->p3s : fb->rmatrix ? fb->p3m : fb->p3,
+          out.kind == FB_OUT_SEGSUM ? fb->p3bf : fb->p3b};
+}
 
 // The loop of the multi-pass paths: the input channels one after the other, each in launch groups of at most max_parts parts;
 // group(ci, co, kern, part0, nb) issues one launch group of channel ci.ichan.
@@ -895,7 +963,7 @@ static int fb_each_group(dspsr_amd_filterbank* fb, const FbIn& in, const FbOut& 
   const FbGeom& g = fb->g;
   for (uint32_t ichan = 0; ichan < fb->cfg.input_nchan; ichan++) {
     FbIn ci = in;
-    if (in.kind == 0) ci.base = (const float*)in.base + ichan * chan_stride;
+    if (in.kind == FB_IN_FLOAT) ci.base = (const float*)in.base + ichan * chan_stride;
     ci.ichan = ichan;
     ci.nchan = fb->cfg.input_nchan;
     FbOut co = out;
@@ -914,7 +982,7 @@ static int fb_each_group(dspsr_amd_filterbank* fb, const FbIn& in, const FbOut& 
 
 // One sub-group of a launch group of the sub-band path: nb parts part0, part0 + rp, part0 + 2 rp, ... of input channel ichan
 static int fb_subband_group(dspsr_amd_filterbank* fb, const FbIn& in, uint32_t ichan, uint64_t chan_stride, const FbOut& co,
-                            const cf* kern, k3_t k3, uint64_t part0, uint32_t nb, uint32_t rp, bool fused_segmented)
+                            const cf* kern, const FbPass<k3_t>& p3, uint64_t part0, uint32_t nb, uint32_t rp)
 {
   dspsr_amd_ctx* ctx = fb->ctx;
   const FbGeom& g = fb->g;
@@ -923,47 +991,45 @@ static int fb_subband_group(dspsr_amd_filterbank* fb, const FbIn& in, uint32_t i
   //  samples per sub-sequence, instead of one contiguous range that would cover the other sub-groups' samples as well)
   const uint64_t step = in.part_step * rp;                                         // (a multiple of R, like L)
   const uint64_t wlen = rp > 1 ? fb->L / R : ((uint64_t)(nb - 1) * step + fb->L) / R, nper = rp > 1 ? (uint64_t)nb * wlen : wlen;
-  const size_t es = in.kind == 0 ? (size_t)g.npol * ndim * sizeof(float) : (size_t)g.npol * ndim;   // bytes per sample, all pols
+  const size_t es = in.kind == FB_IN_FLOAT ? (size_t)g.npol * ndim * sizeof(float) : (size_t)g.npol * ndim;   // bytes per sample, all pols
   const size_t sub_stride = (nper * es + 15) & ~(size_t)15;
   if (!grow_device_buffer(ctx->stream, fb->dsub, fb->dsub_bytes, sub_stride * R))
     return fb_fail(ctx, DSPSR_AMD_ENOMEM, "dspsr_amd_filterbank_perform: hipMalloc of %zu sub-sequence bytes failed", sub_stride * R);
-  SubSplit sp = {in.kind, in.base, in.kind == 0 ? (uint64_t)ichan * chan_stride : 0, in.pol_stride,
+  SubSplit sp = {in.kind, in.base, in.kind == FB_IN_FLOAT ? (uint64_t)ichan * chan_stride : 0, in.pol_stride,
                  fb->cfg.input_nchan, ichan, (uint32_t)g.npol, ndim, part0 * in.part_step, nper, R, sub_stride,
                  rp > 1 ? nb : 1u, wlen, step};
   fb_launch_sub_split(ctx->stream, sp, fb->dsub, fb->ncu);
   const uint64_t Ls = fb->L / R;
   for (uint32_t c = 0; c < R; c++) {
     FbIn cs = in;
-    cs.kind = in.kind == 0 ? 0 : 1;                           // (the split writes the generic byte order)
+    cs.kind = in.kind == FB_IN_FLOAT ? FB_IN_FLOAT : FB_IN_GENERIC8;    // (the split writes the generic byte order)
     cs.base = fb->dsub + (size_t)c * sub_stride;
-    cs.pol_stride = in.kind == 0 ? nper * ndim : 0;
+    cs.pol_stride = in.kind == FB_IN_FLOAT ? nper * ndim : 0;
     cs.part_step = rp > 1 ? wlen : step / R;
     cs.nchan = 1; cs.ichan = 0;
     FbPass1 p1;
     const int rc = fb_pass1(fb, cs, 0, false, true, &p1);
     if (rc != DSPSR_AMD_OK) return rc;
-    k1_t k1s = p1.raww == 1 ? fb->k1_w1 : fb->k1_w4;
-    if (!k1s) return fb_fail(ctx, DSPSR_AMD_EINVAL, "dspsr_amd_filterbank_perform: no kernel for this geometry");
+    const FbPass<k1_t>& p1s = p1.raww == 1 ? fb->p1_w1 : fb->p1_w4;
+    if (!p1s.kern) return fb_fail(ctx, DSPSR_AMD_EINVAL, "dspsr_amd_filterbank_perform: no kernel for this geometry");
     FbIn cr = cs;
     // (one window per part: the sub-groups' parts are windows of their own)
     const RtLayout lay = rt_layout_per_part(g.logM, g.logR, g.logT1, fb->nseq);
     if (p1.regroup == FB_REGROUP_RAW) {
       fb_launch_raw_transpose(ctx->stream, g, cs, fb->Rt, 0, nb, fb->nseq, lay);
-      fb_set_rt(cr, 3, fb->Rt, lay);
+      fb_set_rt(cr, FB_IN_RT_BYTES, fb->Rt, lay);
     } else if (p1.regroup == FB_REGROUP_FLOAT) {
       // (the float regroup buffer is the X scratch in the power-of-two path; X holds finished sub-spectra here: use Rt's
       //  place in A's idle upper half -- A needs nseq * L' of its nseq * L elements per part)
       cf* ft = fb->A + (size_t)nb * fb->nseq * Ls;
       fb_launch_float_transpose(dim3((Rr + FB_FT_COLS - 1) / FB_FT_COLS, (M + FB_FT_ROWS - 1) / FB_FT_ROWS, nb * fb->nseq), ctx->stream, g, cs, ft, 0);
-      fb_set_rt(cr, 5, ft, lay);
+      fb_set_rt(cr, FB_IN_RT_FLOAT, ft, lay);
     }
     const uint64_t n1s = (uint64_t)(Rr >> g.logT1) * fb->nseq * nb, n2s = (uint64_t)(M >> g.logT2) * fb->nseq * nb;
-    hipLaunchKernelGGL(k1s, dim3(grid_for(n1s, fb->ncu * fb->wg1)), dim3(fb->nt1), fb->lds1, ctx->stream, g, cr, fb->A, ctx->tw, 0ull,
-                       nb, fb->nseq, 32u);
-    hipLaunchKernelGGL(fb->k2, dim3(grid_for(n2s, fb->ncu)), dim3(fb->nt2), fb->lds2, ctx->stream, g, fb->A, fb->X + c * Ls,
-                       ctx->tw, nb, fb->nseq, 4u);
+    fb_launch(fb, p1s, n1s, g, cr, fb->A, ctx->tw, 0ull, nb, fb->nseq, 32u);
+    fb_launch(fb, fb->p2, n2s, g, fb->A, fb->X + c * Ls, ctx->tw, nb, fb->nseq, 4u);
   }
-  const uint64_t n3s = (uint64_t)(g.C >> g.logT3) * nb;
+  const uint32_t tiles = g.C >> g.logT3;
   if (fb->msub) {
     // freq_res = R * 2^k: the spectrum in pseudo-channel order (second buffer), the inverse pass on the R * nchan_subband
     // pseudo-channels keeping whole transforms (complex rows into Y), then the radix-R step in time into the caller's output
@@ -975,34 +1041,32 @@ static int fb_subband_group(dspsr_amd_filterbank* fb, const FbIn& in, uint32_t i
       return fb_fail(ctx, DSPSR_AMD_ENOMEM, "dspsr_amd_filterbank_perform: hipMalloc of the pseudo-channel time series failed");
     (void)fb_launch_sub_combine(ctx->stream, g, fb->X, nb * fb->nseq, fb->ncu, nullptr, fb->Xp, fb->out_M, fb->msub);
     // Y[pseudo-channel][pol][part of the group][Mi] complex: rows (pseudo-channel, pol), parts 2*Mi floats apart
-    FbOut yo = {1, (float*)fb->Y, (uint64_t)g.npol * fb->max_parts * Mi * 2, (uint64_t)fb->max_parts * Mi * 2, Mi * 2, 0, 2, 0};
-    hipLaunchKernelGGL(fb->k3, dim3(grid_for(n3s, fb->ncu * fb->wg3)), dim3(fb->nt3), fb->lds3, ctx->stream, g, fb->Xp, kern, yo, ctx->tw,
-                       0ull, nb, nb);
+    const FbOut yo = fb_out_rows((float*)fb->Y, (uint64_t)g.npol * fb->max_parts * Mi * 2, (uint64_t)fb->max_parts * Mi * 2, Mi * 2);
+    fb_launch(fb, fb->p3, fb_inverse_items(yo, tiles, nb), g, fb->Xp, kern, yo, ctx->tw, 0ull, nb, nb);
     TimeCombine tc = {fb->Y, (uint64_t)g.npol * fb->max_parts * Mi, (uint64_t)fb->max_parts * Mi, (uint32_t)g.logM, fb->out_M,
                       fb->out_nfilt_pos, fb->out_nkeep, fb->out_C, (uint32_t)g.npol, part0, nb, rp, make_odd_tw(fb->msub)};
     FbOut cu = co;
     cu.chan0 = ichan * fb->out_C;
-    if (cu.kind == 1 || cu.kind == 2) fb_launch_time_combine(ctx->stream, tc, cu, fb->msub, fb->ncu);
+    if (cu.kind == FB_OUT_COMPLEX || cu.kind == FB_OUT_DETECTED) fb_launch_time_combine(ctx->stream, tc, cu, fb->msub, fb->ncu);
     return DSPSR_AMD_OK;
   }
   if (rp != 1) return fb_fail(ctx, DSPSR_AMD_EINVAL, "dspsr_amd_filterbank_perform: part step %llu is not a multiple of %u",
                               (unsigned long long)in.part_step, R);            // (cannot happen: see fb_run_subbands)
   // (factors without a radix kernel of their own combine out of place, into the A scratch -- idle behind pass 2)
   const cf* Xc = fb_launch_sub_combine(ctx->stream, g, fb->X, nb * fb->nseq, fb->ncu, fb->A);
-  if (co.kind == 3) return fb_launch_fused(fb, k3, Xc, kern, co, part0, nb, fused_segmented);
-  // (search mode: one workgroup per tile of channels, walking the group's parts in order)
-  hipLaunchKernelGGL(k3, dim3(grid_for(co.kind == 5 ? n3s / nb : n3s, fb->ncu * fb->wg3)), dim3(fb->nt3), fb->lds3, ctx->stream, g, Xc,
-                     kern, co, ctx->tw, part0, nb, nb);
+  if (co.kind == FB_OUT_FOLD) return fb_launch_fused(fb, p3, Xc, kern, co, part0, nb);
+  fb_launch(fb, p3, fb_inverse_items(co, tiles, nb), g, Xc, kern, co, ctx->tw, part0, nb, nb);
   return DSPSR_AMD_OK;
 }
 
 // nchan_subband = 3 * 2^k / 5 * 2^k: the group's samples as nsub interleaved sub-sequences, passes 0-2 on each (the
 // power-of-two geometry), one radix-nsub step on the sub-spectra, then the inverse pass on nsub << logR rows; freq_res with
 // an odd factor (msub) adds the radix-msub step in time (k_time_combine)
-static int fb_run_subbands(dspsr_amd_filterbank* fb, const FbIn& in, const FbOut& out, uint64_t npart, uint64_t chan_stride, k3_t k3)
+static int fb_run_subbands(dspsr_amd_filterbank* fb, const FbIn& in, const FbOut& out, uint64_t npart, uint64_t chan_stride,
+                           const FbPass<k3_t>& p3)
 {
   const uint32_t R = fb->g.nsub;
-  if (in.kind == 4)
+  if (in.kind == FB_IN_UWB16)
     return fb_fail(fb->ctx, DSPSR_AMD_EINVAL, "dspsr_amd_filterbank_perform: 16-bit UWB blocks need power-of-two nchan_subband and "
                    "freq_res (k_sub_split de-interleaves 8-bit and float32 input)");
   // The sub-sequences of a launch share ONE de-interleaved block, so its parts must start a multiple of R samples apart.  The
@@ -1012,10 +1076,9 @@ static int fb_run_subbands(dspsr_amd_filterbank* fb, const FbIn& in, const FbOut
   // kernels that amortise ramp-up and tail over 32-256 parts).
   auto gcd = [](uint32_t x, uint32_t y) { while (y) { const uint32_t t = x % y; x = y; y = t; } return x; };
   const uint32_t rp = (in.part_step % R) ? R / gcd((uint32_t)(in.part_step % R), R) : 1u;
-  const bool fused_segmented = out.kind == 3 && dspsr_amd_filterbank_fold_is_fused(fb) == 2;
   return fb_each_group(fb, in, out, npart, chan_stride, [&](const FbIn& ci, const FbOut& co, const cf* kern, uint64_t part0, uint32_t nb) {
     for (uint32_t q = 0; q < rp && q < nb; q++) {
-      const int rc = fb_subband_group(fb, in, ci.ichan, chan_stride, co, kern, k3, part0 + q, (nb - q + rp - 1) / rp, rp, fused_segmented);
+      const int rc = fb_subband_group(fb, in, ci.ichan, chan_stride, co, kern, p3, part0 + q, (nb - q + rp - 1) / rp, rp);
       if (rc != DSPSR_AMD_OK) return rc;
     }
     return DSPSR_AMD_OK;
@@ -1029,31 +1092,22 @@ static int fb_run_two_pass(dspsr_amd_filterbank* fb, const FbIn& in, const FbOut
   dspsr_amd_ctx* ctx = fb->ctx;
   const FbGeom& g = fb->g;
   const uint32_t Fb = 1u << g.logFb2, tiles = g.C >> g.logFb2;
-  const bool fused_segmented = out.kind == 3 && dspsr_amd_filterbank_fold_is_fused(fb) == 2;
   return fb_each_group(fb, in, out, npart, chan_stride, [&](const FbIn& ci, const FbOut& co, const cf* kern, uint64_t part0, uint32_t nb) {
     FbIn cr = ci;
-    cr.kind = 3;
+    cr.kind = FB_IN_RT_BYTES;
     cr.base = fb->Rt;
-    if (fb->k1c) {
+    if (fb->p1c.kern) {
       fb_launch_raw_cols(dim3((uint32_t)(fb->L / 8192), nb), ctx->stream, g, ci, fb->Rt, part0);
-      const uint64_t n1c = (uint64_t)Fb * 2 * nb;
-      hipLaunchKernelGGL(fb->k1c, dim3(grid_for(n1c, fb->ncu)), dim3(512), fb->lds1c, ctx->stream, g, cr, fb->A, ctx->tw, nb, 2u, 32u);
+      fb_launch(fb, fb->p1c, (uint64_t)Fb * 2 * nb, g, cr, fb->A, ctx->tw, nb, 2u, 32u);
     } else {
       const FbGeom& q = fb->g1t;
       const RtLayout lay = rt_layout_per_part(q.logM, q.logR, q.logT1, 2);
       fb_launch_raw_transpose(ctx->stream, q, ci, fb->Rt, part0, nb, 2, lay);
-      fb_set_rt(cr, 3, fb->Rt, lay);
-      const uint64_t n1t = (uint64_t)(Fb >> q.logT1) * 2 * nb;
-      hipLaunchKernelGGL(fb->k1t, dim3(grid_for(n1t, fb->ncu)), dim3(fb->nt1t), fb->lds1t, ctx->stream, q, cr, fb->A, ctx->tw, part0,
-                         nb, 2u, 32u);
+      fb_set_rt(cr, FB_IN_RT_BYTES, fb->Rt, lay);
+      fb_launch(fb, fb->p1t, (uint64_t)(Fb >> q.logT1) * 2 * nb, q, cr, fb->A, ctx->tw, part0, nb, 2u, 32u);
     }
-    if (co.kind == 3) return fb_launch_fused(fb, fb->k2rf, fb->A, kern, co, part0, nb, fused_segmented, true);
-    if (co.kind == 5)
-      hipLaunchKernelGGL(fb->k2rs, dim3(grid_for(tiles, fb->ncu)), dim3(512), fb->lds2r, ctx->stream, g, fb->A, kern, co, ctx->tw, part0,
-                         nb, nb);
-    else
-      hipLaunchKernelGGL(fb->k2r, dim3(grid_for((uint64_t)tiles * nb, fb->ncu)), dim3(512), fb->lds2r, ctx->stream, g, fb->A, kern, co,
-                         ctx->tw, part0, nb, nb);
+    if (co.kind == FB_OUT_FOLD) return fb_launch_fused(fb, fb->p2rf, fb->A, kern, co, part0, nb, true);
+    fb_launch(fb, co.kind == FB_OUT_SEARCH ? fb->p2rs : fb->p2r, fb_inverse_items(co, tiles, nb), g, fb->A, kern, co, ctx->tw, part0, nb, nb);
     return DSPSR_AMD_OK;
   });
 }
@@ -1066,13 +1120,11 @@ static int fb_run_tiles(dspsr_amd_filterbank* fb, const FbIn& in, const FbOut& o
   dspsr_amd_ctx* ctx = fb->ctx;
   const FbGeom& g = fb->g;
   const uint32_t Rr = 1u << g.logR, M = 1u << g.logM;
-  const bool fused_segmented = out.kind == 3 && dspsr_amd_filterbank_fold_is_fused(fb) == 2;
   return fb_each_group(fb, in, out, npart, chan_stride, [&](const FbIn& ci, const FbOut& co, const cf* kern, uint64_t part0, uint32_t nb) {
-    // persistent grids: one workgroup per CU (LDS-limited), a multiple of 8 so the XCD-aware item order applies
-    const uint64_t n1 = (uint64_t)(Rr >> g.logT1) * fb->nseq * nb, n2 = (uint64_t)(M >> g.logT2) * fb->nseq * nb,
-                   n3 = g.four_pass ? 0 : (uint64_t)(g.C >> g.logT3) * nb;
-    // XCD dealing of the persistent items (wgfft.h persistent_item): runs of consecutive items per XCD
-    const uint32_t run1 = 32, run2 = 4, run3 = nb;
+    const uint64_t n1 = (uint64_t)(Rr >> g.logT1) * fb->nseq * nb;
+    const uint32_t tiles = g.C >> g.logT3;                            // (of the one inverse pass of the three-pass geometry)
+    // XCD dealing of the persistent items (wgfft.h persistent_item): runs of consecutive items per XCD (the inverse pass: its parts)
+    const uint32_t run1 = 32, run2 = 4;
     FbIn c1 = ci;
     RtLayout lay = rt_layout_per_part(g.logM, g.logR, g.logT1, fb->nseq);
     if (p1.regroup == FB_REGROUP_RAW) {
@@ -1081,18 +1133,15 @@ static int fb_run_tiles(dspsr_amd_filterbank* fb, const FbIn& in, const FbOut& o
       // allocated for (rt_takes_shared)
       if (rt_takes_shared(g.logM, g.logR, nb, ci.part_step)) lay = rt_layout_shared(g.logM, g.logR, g.logT1, nb, ci.part_step >> g.logR);
       fb_launch_raw_transpose(ctx->stream, g, ci, fb->Rt, part0, nb, fb->nseq, lay);
-      fb_set_rt(c1, 3, fb->Rt, lay);
+      fb_set_rt(c1, FB_IN_RT_BYTES, fb->Rt, lay);
     } else if (p1.regroup == FB_REGROUP_FLOAT) {
       // (into the idle X scratch)
       fb_launch_float_transpose(dim3((Rr + FB_FT_COLS - 1) / FB_FT_COLS, (M + FB_FT_ROWS - 1) / FB_FT_ROWS, nb * fb->nseq), ctx->stream, g, ci, fb->X, part0);
-      fb_set_rt(c1, 5, fb->X, lay);
+      fb_set_rt(c1, FB_IN_RT_FLOAT, fb->X, lay);
     }
-    if (k.k1d)
-      hipLaunchKernelGGL(k.k1d, dim3(grid_for(n1 / 2, fb->ncu * fb->wg1)), dim3(fb->nt1), fb->lds1, ctx->stream, g, c1, fb->A, ctx->tw,
-                         part0, nb, fb->nseq, run1 / 2 ? run1 / 2 : 1u);     // (run is a divisor in persistent_item: never 0)
-    else
-      hipLaunchKernelGGL(k.k1, dim3(grid_for(n1, fb->ncu * fb->wg1)), dim3(fb->nt1), fb->lds1, ctx->stream, g, c1, fb->A, ctx->tw,
-                         part0, nb, fb->nseq, run1);
+    // (the dual pass takes pairs of tiles; run is a divisor in persistent_item: never 0)
+    if (k.p1d.kern) fb_launch(fb, k.p1d, n1 / 2, g, c1, fb->A, ctx->tw, part0, nb, fb->nseq, run1 / 2 ? run1 / 2 : 1u);
+    else fb_launch(fb, k.p1, n1, g, c1, fb->A, ctx->tw, part0, nb, fb->nseq, run1);
     // Pass 2 and the inverse pass run in sub-groups of a few parts, so that
     // part of the spectrum pass 2 has just written is still in the 256 MB Infinity Cache when the inverse pass reads
     // it (measured with whole groups of 8 / 16 / 32 parts: 31.5 / 33.4 / 35.2 µs per part in the inverse pass, pass 2
@@ -1105,47 +1154,31 @@ static int fb_run_tiles(dspsr_amd_filterbank* fb, const FbIn& in, const FbOut& o
     // (segmented fused fold -- geometries with fewer channel tiles than compute units: every launch of the fused kernel
     //  brings a memset and a combine pass over the partial profiles, so whole launches win: 50 MHz sub-band geometry
     //  43.5k -> 46.0k Msamples/s, -F 256:D 60.3k -> 60.6-61.3k, tools/exp_p23.sh)
-    const uint32_t p23sub = (g.four_pass || (co.kind == 3 && fused_segmented)) ? nb : (uint32_t)(p23auto < nb ? p23auto : nb);
-    if (p23sub < nb) {
-      for (uint32_t s0 = 0; s0 < nb; s0 += p23sub) {
-        const uint32_t ns = nb - s0 < p23sub ? nb - s0 : p23sub;
-        const uint64_t off = (uint64_t)s0 * fb->part_elems;
-        const uint64_t n2s = (uint64_t)(M >> g.logT2) * fb->nseq * ns;
-        const uint64_t n3s = co.kind == 5 ? (uint64_t)(g.C >> g.logT3) : (uint64_t)(g.C >> g.logT3) * ns;
-        hipLaunchKernelGGL(fb->k2, dim3(grid_for(n2s, fb->ncu)), dim3(fb->nt2), fb->lds2, ctx->stream, g, fb->A + off,
-                           fb->X + off, ctx->tw, ns, fb->nseq, run2);
-        if (co.kind == 3) {
-          const int rc = fb_launch_fused(fb, k.k3, fb->X + off, kern, co, part0 + s0, ns, fused_segmented);
-          if (rc != DSPSR_AMD_OK) return rc;
-        } else {
-          hipLaunchKernelGGL(k.k3, dim3(grid_for(n3s, fb->ncu * fb->wg3)), dim3(fb->nt3), fb->lds3, ctx->stream, g, fb->X + off, kern, co,
-                             ctx->tw, part0 + s0, ns, ns);
-        }
-      }
-      return DSPSR_AMD_OK;
-    }
-    hipLaunchKernelGGL(fb->k2, dim3(grid_for(n2, fb->ncu)), dim3(fb->nt2), fb->lds2, ctx->stream, g, fb->A, fb->X,
-                       ctx->tw, nb, fb->nseq, run2);
-    if (!g.four_pass) {
+    const uint32_t p23sub = (g.four_pass || fb_fold_segmented(fb, co)) ? nb : (uint32_t)(p23auto < nb ? p23auto : nb);
+    for (uint32_t s0 = 0; s0 < nb; s0 += p23sub) {
+      const uint32_t ns = nb - s0 < p23sub ? nb - s0 : p23sub;
+      const uint64_t off = (uint64_t)s0 * fb->part_elems;
+      fb_launch(fb, fb->p2, (uint64_t)(M >> g.logT2) * fb->nseq * ns, g, fb->A + off, fb->X + off, ctx->tw, ns, fb->nseq, run2);
+      if (g.four_pass) break;                       // (the whole group: its two inverse passes follow)
       // fused fold: one workgroup owns a tile (T3 channels) for all parts of the launch
-      if (co.kind == 3) return fb_launch_fused(fb, k.k3, fb->X, kern, co, part0, nb, fused_segmented);
-      const uint64_t items3 = co.kind == 5 ? (uint64_t)(g.C >> g.logT3) : n3;
-      hipLaunchKernelGGL(k.k3, dim3(grid_for(items3, fb->ncu * fb->wg3)), dim3(fb->nt3), fb->lds3, ctx->stream, g, fb->X, kern, co,
-                         ctx->tw, part0, nb, run3);
-      return DSPSR_AMD_OK;
+      if (co.kind == FB_OUT_FOLD) {
+        const int rc = fb_launch_fused(fb, k.p3, fb->X + off, kern, co, part0 + s0, ns);
+        if (rc != DSPSR_AMD_OK) return rc;
+      } else {
+        fb_launch(fb, k.p3, fb_inverse_items(co, tiles, ns), g, fb->X + off, kern, co, ctx->tw, part0 + s0, ns, ns);
+      }
     }
+    if (!g.four_pass) return DSPSR_AMD_OK;
     // two-pass inverse: X (whole spectrum) -> U (in the A buffer, dead after pass 2) -> output
     const uint64_t n3a = ((uint64_t)g.C << (g.logMb - g.logTm)) * nb, n3b = ((uint64_t)g.C << (g.logMa - g.logTt)) * nb;
-    hipLaunchKernelGGL(fb->k3a, dim3(grid_for(n3a, fb->ncu)), dim3(fb->nt3), fb->lds3, ctx->stream, g, fb->X, kern,
-                       fb->A, ctx->tw, nb, 8u);
-    if (co.kind == 4) {      // the fused second pass reads the segment plan
+    fb_launch(fb, fb->p3a, n3a, g, fb->X, kern, fb->A, ctx->tw, nb, 8u);
+    if (co.kind == FB_OUT_SEGSUM) {      // the fused second pass reads the segment plan
       const int rc = fb_plan_ready(fb, co.fold);
       if (rc != DSPSR_AMD_OK) return rc;
     }
-    hipLaunchKernelGGL(k.k3b, dim3(grid_for(n3b, fb->ncu)), dim3(fb->nt4), fb->lds4, ctx->stream, g, fb->A, co,
-                       ctx->tw, part0, nb, 8u);
+    fb_launch(fb, k.p3b, n3b, g, fb->A, co, ctx->tw, part0, nb, 8u);
     // every part of this sub-band has left its segment sums: add them to the profile in time order
-    if (co.kind == 4 && part0 + nb == npart)
+    if (co.kind == FB_OUT_SEGSUM && part0 + nb == npart)
       return fold_segment_combine(co.fold, fb->msum, co.chan0, g.C, (uint32_t)npart, g.nkeep, g.nfilt_pos, g.logTt, g.logMa,
                                   g.logMb, co.bin_start, co.piv);
     return DSPSR_AMD_OK;
@@ -1162,31 +1195,30 @@ static int fb_run(dspsr_amd_filterbank* fb, const FbIn& in, const FbOut& out, ui
   if (npart == 0) return DSPSR_AMD_OK;
   // the CASPSR and UWB loaders read whole 16-bit / 32-bit words relative to the block (fetch_pair, k_fb_plain): a block that
   // starts inside such a word is not that layout
-  if ((in.kind == 2 && ((uintptr_t)in.base % 2) != 0) || (in.kind == 4 && ((uintptr_t)in.base % 4) != 0))
+  if ((in.kind == FB_IN_CASPSR && ((uintptr_t)in.base % 2) != 0) || (in.kind == FB_IN_UWB16 && ((uintptr_t)in.base % 4) != 0))
     return fb_fail(ctx, DSPSR_AMD_EINVAL, "dspsr_amd_filterbank_perform: a %s block must start at a multiple of %d bytes",
-                   in.kind == 2 ? "CASPSR" : "16-bit UWB", in.kind == 2 ? 2 : 4);
+                   in.kind == FB_IN_CASPSR ? "CASPSR" : "16-bit UWB", in.kind == FB_IN_CASPSR ? 2 : 4);
   if (fb->plain_logC >= 0) return fb_run_plain(fb, in, out, npart, chan_stride);
   // complex float32 rows that the one- and three-pass convolutions read in place: an 8-byte base and even strides
-  const bool conv_rows = in.kind == 0 && (out.kind == 0 || out.kind == 1 || out.kind == 2) && (chan_stride % 2) == 0 &&
-                         (in.pol_stride % 2) == 0 && ((uintptr_t)in.base % 8) == 0;
+  const bool conv_rows = in.kind == FB_IN_FLOAT && fb_out_is_rows(out) && (chan_stride % 2) == 0 && (in.pol_stride % 2) == 0 &&
+                         ((uintptr_t)in.base % 8) == 0;
   if (fb->conv1_logM >= 0 && conv_rows) return fb_run_conv1(fb, in, out, npart, chan_stride);
   if (fb->conv3_logM >= 0 && conv_rows) return fb_run_conv3(fb, in, out, npart, chan_stride);
-  if (fb->batch && in.kind == 0 && (out.kind == 0 || out.kind == 1 || out.kind == 2) && (chan_stride % 2) == 0)
+  if (fb->batch && in.kind == FB_IN_FLOAT && fb_out_is_rows(out) && (chan_stride % 2) == 0)
     return fb_run_batched(fb, in, out, npart, chan_stride);
   // the multi-pass paths: pass 1's regroup of the caller's input (its buffer allocated here) and the kernels
   const bool two = fb_takes_two_pass(fb, in, out);
   FbPass1 p1;
   const int rc = fb_pass1(fb, in, chan_stride, two, false, &p1);
   if (rc != DSPSR_AMD_OK) return rc;
-  const FbPassKernels k = {p1.raww == 1 ? fb->k1_w1 : fb->k1_w4, p1.raww == 1 ? fb->k1d_w1 : fb->k1d_w4,
-                           out.kind == 3 ? fb->k3f : out.kind == 5 ? fb->k3s : fb->rmatrix ? fb->k3m : fb->k3,
-                           out.kind == 4 ? fb->k3bf : fb->k3b};
-  // (set_response_matrix admits the three-pass path of a power-of-two geometry only; fold and search detour through kind 2 / 1)
-  if (fb->rmatrix && (out.kind > 2 || g.four_pass || g.nsub > 1 || fb->msub))
-    return fb_fail(ctx, DSPSR_AMD_EINVAL, "dspsr_amd_filterbank_perform: output kind %d has no matrix-response form", out.kind);
-  if (!k.k1 || !fb->k2 || (g.four_pass ? (!fb->k3a || !k.k3b) : !k.k3))
+  const FbPassKernels k = fb_pass_kernels(fb, p1, out);
+  // (set_response_matrix admits the three-pass path of a power-of-two geometry only; fold and search detour through the detected /
+  //  complex rows)
+  if (fb->rmatrix && (!fb_out_is_rows(out) || g.four_pass || g.nsub > 1 || fb->msub))
+    return fb_fail(ctx, DSPSR_AMD_EINVAL, "dspsr_amd_filterbank_perform: output kind %d has no matrix-response form", (int)out.kind);
+  if (!k.p1.kern || !fb->p2.kern || (g.four_pass ? (!fb->p3a.kern || !k.p3b.kern) : !k.p3.kern))
     return fb_fail(ctx, DSPSR_AMD_EINVAL, "dspsr_amd_filterbank_perform: no kernel for this geometry");
-  if (g.nsub > 1) return fb_run_subbands(fb, in, out, npart, chan_stride, k.k3);
+  if (g.nsub > 1) return fb_run_subbands(fb, in, out, npart, chan_stride, k.p3);
   if (two) return fb_run_two_pass(fb, in, out, npart, chan_stride);
   return fb_run_tiles(fb, in, out, npart, chan_stride, p1, k);
 }
@@ -1201,7 +1233,7 @@ static int fb_input(dspsr_amd_filterbank* fb, const char* fn, const float* in_f3
     const uint32_t idim = c.real_input ? 1 : 2;
     if (in_step % idim)
       return fb_fail(fb->ctx, DSPSR_AMD_EINVAL, "%s: in_step=%llu not a multiple of ndim", fn, (unsigned long long)in_step);
-    *in = {0, in_f32_dev, in_pol_stride, in_step / idim, c.input_nchan, 0, 1.0f};
+    *in = {FB_IN_FLOAT, in_f32_dev, in_pol_stride, in_step / idim, c.input_nchan, 0, 1.0f};
     return DSPSR_AMD_OK;
   }
   if (raw_layout == DSPSR_AMD_RAW_CASPSR && !(c.real_input && c.npol == 2 && c.input_nchan == 1))
@@ -1216,25 +1248,25 @@ static int fb_input(dspsr_amd_filterbank* fb, const char* fn, const float* in_f3
   return DSPSR_AMD_OK;
 }
 
-// The complex output rows of perform / perform_raw (`fn` names the caller in the messages): a part's 2 * nkeep floats must fit
-// its out_step, and the rows of different channels and polarisations must not overlap (a channel's row may not reach into the
+// perform / perform_raw (`fn` names the caller in the messages): the input, then the complex output rows -- a part's 2 * nkeep floats
+// must fit its out_step, and the rows of different channels and polarisations must not overlap (a channel's row may not reach into the
 // next channel's first polarisation either).  Any float-aligned address is taken: no writer needs more (tests/test_gpu_output_forms.py).
-static int fb_complex_rows_ok(dspsr_amd_filterbank* fb, const char* fn, const float* out_dev, uint64_t out_chan_stride,
-                              uint64_t out_pol_stride, uint64_t npart, uint64_t out_step)
+static int fb_perform_rows(dspsr_amd_filterbank* fb, const char* fn, const float* in_f32_dev, uint64_t in_chan_stride, uint64_t in_pol_stride,
+                           uint64_t in_step, const int8_t* raw_dev, int raw_layout, float scale, float* out_dev, uint64_t out_chan_stride,
+                           uint64_t out_pol_stride, uint64_t npart, uint64_t out_step)
 {
-  if (!out_dev) return DSPSR_AMD_OK;
-  if (out_step < 2ull * fb_out_nkeep(fb))
+  FbIn in;
+  const int rc = fb_input(fb, fn, in_f32_dev, in_pol_stride, in_step, raw_dev, raw_layout, scale, &in);
+  if (rc != DSPSR_AMD_OK) return rc;
+  if (out_dev && out_step < 2ull * fb_out_nkeep(fb))
     return fb_fail(fb->ctx, DSPSR_AMD_EINVAL, "%s: out_step=%llu < 2*nkeep=%u", fn, (unsigned long long)out_step, 2 * fb_out_nkeep(fb));
   const uint64_t nchan_out = (uint64_t)fb->cfg.input_nchan * fb_out_C(fb);
   const uint64_t row = npart ? (npart - 1) * out_step + 2ull * fb_out_nkeep(fb) : 0;      // floats one output row spans
   // channel-major (TimeSeries FPT order) or polarisation-major, as the detected rows of perform_detect
-  const uint64_t npol = fb->cfg.npol;
-  const bool chan_major = (npol == 1 || out_pol_stride >= row) && (nchan_out == 1 || out_chan_stride >= (npol - 1) * out_pol_stride + row);
-  const bool pol_major = npol > 1 && (nchan_out == 1 || out_chan_stride >= row) && out_pol_stride >= (nchan_out - 1) * out_chan_stride + row;
-  if (npart && !chan_major && !pol_major)
+  if (out_dev && !fb_rows_ok(npart, nchan_out, fb->cfg.npol, out_chan_stride, out_pol_stride, row, true))
     return fb_fail(fb->ctx, DSPSR_AMD_EINVAL, "%s: output rows of %llu floats overlap (chan stride %llu, pol stride %llu)", fn,
                    (unsigned long long)row, (unsigned long long)out_chan_stride, (unsigned long long)out_pol_stride);
-  return DSPSR_AMD_OK;
+  return fb_run(fb, in, fb_out_rows(out_dev, out_chan_stride, out_pol_stride, out_step), npart, in_chan_stride);
 }
 
 extern "C" int dspsr_amd_filterbank_perform(dspsr_amd_filterbank* fb, const float* in_dev, uint64_t in_chan_stride,
@@ -1243,13 +1275,8 @@ extern "C" int dspsr_amd_filterbank_perform(dspsr_amd_filterbank* fb, const floa
                                             uint64_t out_step)
 {
   if (!fb || !in_dev) return DSPSR_AMD_EINVAL;
-  FbIn in;
-  const int rc = fb_input(fb, "dspsr_amd_filterbank_perform", in_dev, in_pol_stride, in_step, nullptr, 0, 0.0f, &in);
-  if (rc != DSPSR_AMD_OK) return rc;
-  const int rco = fb_complex_rows_ok(fb, "dspsr_amd_filterbank_perform", out_dev, out_chan_stride, out_pol_stride, npart, out_step);
-  if (rco != DSPSR_AMD_OK) return rco;
-  FbOut out = {out_dev ? 1 : 0, out_dev, out_chan_stride, out_pol_stride, out_step, 0, 2, 0};
-  return fb_run(fb, in, out, npart, in_chan_stride);
+  return fb_perform_rows(fb, "dspsr_amd_filterbank_perform", in_dev, in_chan_stride, in_pol_stride, in_step, nullptr, 0, 0.0f, out_dev,
+                         out_chan_stride, out_pol_stride, npart, out_step);
 }
 
 extern "C" int dspsr_amd_filterbank_perform_raw(dspsr_amd_filterbank* fb, const int8_t* raw_dev, int raw_layout,
@@ -1257,13 +1284,8 @@ extern "C" int dspsr_amd_filterbank_perform_raw(dspsr_amd_filterbank* fb, const 
                                                 uint64_t out_pol_stride, uint64_t npart, uint64_t out_step)
 {
   if (!fb || !raw_dev) return DSPSR_AMD_EINVAL;
-  FbIn in;
-  const int rc = fb_input(fb, "dspsr_amd_filterbank_perform_raw", nullptr, 0, 0, raw_dev, raw_layout, scale, &in);
-  if (rc != DSPSR_AMD_OK) return rc;
-  const int rco = fb_complex_rows_ok(fb, "dspsr_amd_filterbank_perform_raw", out_dev, out_chan_stride, out_pol_stride, npart, out_step);
-  if (rco != DSPSR_AMD_OK) return rco;
-  FbOut out = {out_dev ? 1 : 0, out_dev, out_chan_stride, out_pol_stride, out_step, 0, 2, 0};
-  return fb_run(fb, in, out, npart, 0);
+  return fb_perform_rows(fb, "dspsr_amd_filterbank_perform_raw", nullptr, 0, 0, 0, raw_dev, raw_layout, scale, out_dev, out_chan_stride,
+                         out_pol_stride, npart, out_step);
 }
 
 extern "C" int dspsr_amd_filterbank_perform_detect(dspsr_amd_filterbank* fb, const float* in_f32_dev,
@@ -1283,20 +1305,13 @@ extern "C" int dspsr_amd_filterbank_perform_detect(dspsr_amd_filterbank* fb, con
   FbIn in;
   const int rc = fb_input(fb, "dspsr_amd_filterbank_perform_detect", in_f32_dev, in_pol_stride, in_step, raw_dev, raw_layout, scale, &in);
   if (rc != DSPSR_AMD_OK) return rc;
-  {
-    // rows must not overlap: channel-major (TimeSeries FPT order) or plane-major layouts are accepted
-    const uint64_t nchan_out = (uint64_t)fb->cfg.input_nchan * fb_out_C(fb), row = npart * fb_out_nkeep(fb) * ndim, planes = 4 / ndim;
-    const bool chan_major = (planes == 1 || det_pol_stride >= row) &&
-                            (nchan_out == 1 || det_chan_stride >= (planes - 1) * det_pol_stride + row);
-    const bool plane_major = planes > 1 && (nchan_out == 1 || det_chan_stride >= row) &&
-                             det_pol_stride >= (nchan_out - 1) * det_chan_stride + row;
-    if (npart && !chan_major && !plane_major)
-      return fb_fail(fb->ctx, DSPSR_AMD_EINVAL, "dspsr_amd_filterbank_perform_detect: detected rows of %llu floats overlap "
-                     "(chan stride %llu, pol stride %llu)", (unsigned long long)row, (unsigned long long)det_chan_stride,
-                     (unsigned long long)det_pol_stride);
-  }
-  FbOut out = {2, det_dev, det_chan_stride, det_pol_stride, 0, state, ndim, 0};
-  return fb_run(fb, in, out, npart, in_chan_stride);
+  // rows must not overlap: channel-major (TimeSeries FPT order) or plane-major layouts are accepted
+  const uint64_t nchan_out = (uint64_t)fb->cfg.input_nchan * fb_out_C(fb), row = npart * fb_out_nkeep(fb) * ndim, planes = 4 / ndim;
+  if (!fb_rows_ok(npart, nchan_out, planes, det_chan_stride, det_pol_stride, row, true))
+    return fb_fail(fb->ctx, DSPSR_AMD_EINVAL, "dspsr_amd_filterbank_perform_detect: detected rows of %llu floats overlap "
+                   "(chan stride %llu, pol stride %llu)", (unsigned long long)row, (unsigned long long)det_chan_stride,
+                   (unsigned long long)det_pol_stride);
+  return fb_run(fb, in, fb_out_detected(det_dev, det_chan_stride, det_pol_stride, state, ndim), npart, in_chan_stride);
 }
 
 // search mode inside the inverse pass: the staged tile (fb_common.h ts_stage) must fit the exchange buffer and the 32-bit index
@@ -1304,12 +1319,12 @@ extern "C" int dspsr_amd_filterbank_perform_detect(dspsr_amd_filterbank* fb, con
 static bool fb_search_fits(const dspsr_amd_filterbank* fb, uint32_t npo, uint32_t sf, uint32_t* G_out)
 {
   const FbGeom& g = fb->g;
-  if (g.four_pass || fb->msub || fb->rmatrix || !fb->k3s || g.nkeep >= 65536 || sf >= 32768) return false;
+  if (g.four_pass || fb->msub || fb->rmatrix || !fb->p3s.kern || g.nkeep >= 65536 || sf >= 32768) return false;
   const uint64_t ngmax = ((uint64_t)g.nkeep + 2ull * sf - 2) / sf;
   const uint32_t G = (uint32_t)ngmax | 1u;
   const uint64_t floats = ((uint64_t)npo << g.logT3) * sf * G;
-  if (floats > 2ull * fb->nt3 * PTS) return false;                       // (the buffer's padding is slack)
-  if (((uint64_t)npo << g.logT3) > 4ull * fb->nt3) return false;         // a thread reads at most four rows' carries (k_inv_chan TS_NPRE)
+  if (floats > 2ull * fb->p3s.threads * PTS) return false;                       // (the buffer's padding is slack)
+  if (((uint64_t)npo << g.logT3) > 4ull * fb->p3s.threads) return false;         // a thread reads at most four rows' carries (k_inv_chan TS_NPRE)
   if (((uint64_t)g.nkeep + sf) * sf >= (1ull << 32)) return false;       // t / sf by multiplication (ts_magic)
   if (G_out) *G_out = G;
   return true;
@@ -1345,7 +1360,7 @@ extern "C" int dspsr_amd_filterbank_perform_search(dspsr_amd_filterbank* fb, con
   if (!npart) return DSPSR_AMD_OK;
   if ((!out_dev && *nout) || !carry_dev) return DSPSR_AMD_EINVAL;
   const uint64_t nchan_out = (uint64_t)fb->cfg.input_nchan * fb_out_C(fb);
-  if (*nout && ((npo > 1 && out_pol_stride < *nout) || (nchan_out > 1 && out_chan_stride < (npo - 1) * out_pol_stride + *nout)))
+  if (!fb_rows_ok(*nout, nchan_out, npo, out_chan_stride, out_pol_stride, *nout, false))           // (FPT rows: channel-major only)
     return fb_fail(ctx, DSPSR_AMD_EINVAL, "dspsr_amd_filterbank_perform_search: output rows of %llu floats overlap (chan stride %llu, pol "
                    "stride %llu)", (unsigned long long)*nout, (unsigned long long)out_chan_stride, (unsigned long long)out_pol_stride);
   FbIn in;
@@ -1354,12 +1369,7 @@ extern "C" int dspsr_amd_filterbank_perform_search(dspsr_amd_filterbank* fb, con
   uint32_t G = 0;
   if (fb_search_fits(fb, npo, tscrunch, &G)) {
     // Filterbank + Detection::square_law + TScrunch in one launch group: the detected stream never reaches HBM
-    FbOut out = {};
-    out.kind = 5; out.base = out_dev; out.chan_stride = out_chan_stride; out.pol_stride = out_pol_stride;
-    out.state = out_state; out.ndim = 1;
-    out.ts_sf = tscrunch; out.ts_magic = (uint32_t)(((1ull << 32) + tscrunch - 1) / tscrunch); out.ts_phase0 = *carry_count;
-    out.ts_G = G; out.ts_carry = carry_dev;
-    if (tscrunch == 1) out.ts_magic = 0xffffffffu;                       // (2^32 does not fit: t / 1 = t is the special case below)
+    const FbOut out = fb_out_search(out_dev, out_chan_stride, out_pol_stride, out_state, tscrunch, *carry_count, G, carry_dev);
     rc = fb_run(fb, in, out, npart, in_chan_stride);
     if (rc != DSPSR_AMD_OK) return rc;
     *carry_count = rem;
@@ -1373,8 +1383,7 @@ extern "C" int dspsr_amd_filterbank_perform_search(dspsr_amd_filterbank* fb, con
     return fb_fail(ctx, DSPSR_AMD_ENOMEM, "dspsr_amd_filterbank_perform_search: hipMalloc of %zu bytes failed", need * sizeof(float));
   float* cplx = fb->det;
   float* det = fb->det + (size_t)nchan_out * fb->cfg.npol * crow;
-  FbOut cout = {1, cplx, fb->cfg.npol * crow, crow, 2ull * nkeep, 0, 2, 0};
-  rc = fb_run(fb, in, cout, npart, in_chan_stride);
+  rc = fb_run(fb, in, fb_out_rows(cplx, fb->cfg.npol * crow, crow, 2ull * nkeep), npart, in_chan_stride);
   if (rc != DSPSR_AMD_OK) return rc;
   rc = dspsr_amd_detect_square_law(ctx, out_state == DSPSR_AMD_INTENSITY, cplx, fb->cfg.npol * crow, crow, det, npo * drow, drow,
                                    (uint32_t)nchan_out, fb->cfg.npol, ndat);
@@ -1405,7 +1414,7 @@ extern "C" int dspsr_amd_filterbank_fold_is_fused(const dspsr_amd_filterbank* fb
   // (segment sums pay when most of the transform is kept: at -F 64:D -x 16384 only 1817 of 16384 samples are, the unfused pass
   //  writes just those, and the fused one measured 541 against 458 us per 8 parts)
   if (fb->g.four_pass)
-    return fb->cfg.fused_fold != DSPSR_AMD_FUSED_NEVER && fb->k3bf && fb->g.logTt >= 3 &&
+    return fb->cfg.fused_fold != DSPSR_AMD_FUSED_NEVER && fb->p3bf.kern && fb->g.logTt >= 3 &&
            (2ull * fb->g.nkeep >= (1ull << fb->g.logMf) || fb->cfg.fused_fold == DSPSR_AMD_FUSED_ALWAYS) ? 3 : 0;
   if (fb->g.nkeep >= 65536) return 0;
   if (fb->cfg.fused_fold == DSPSR_AMD_FUSED_ALWAYS) return 1;
@@ -1478,8 +1487,7 @@ extern "C" int dspsr_amd_filterbank_perform_fold(dspsr_amd_filterbank* fb, const
       const size_t need = ((size_t)fb->g.C * npart << (fb->g.logMf - fb->g.logTt)) * 8;       // segments x 2 pieces x float4
       if (!grow_device_buffer(ctx->stream, fb->msum, fb->msum_floats, need))
         return fb_fail(ctx, DSPSR_AMD_ENOMEM, "dspsr_amd_filterbank_perform_fold: hipMalloc of %zu segment-sum bytes failed", need * sizeof(float));
-      FbOut sout = {4, fb->msum, 0, 0, 0, state, 4, 0, fold->nbin, fold->span / 4, 1u, fold->span, nullptr, fold->nchan, 0, fold, d_off,
-                    (uint32_t)npart, 0, d_siv, d_blk, d_bs};
+      const FbOut sout = fb_out_segsum(fb->msum, fold, state, d_off, d_siv, d_blk, d_bs, (uint32_t)npart);
       return fb_run_with_plan(fb, fold, sslot, in, sout, npart, in_chan_stride);
     }
   }
@@ -1491,8 +1499,7 @@ extern "C" int dspsr_amd_filterbank_perform_fold(dspsr_amd_filterbank* fb, const
     if (!grow_device_buffer(ctx->stream, fb->det, fb->det_floats, need))
       return fb_fail(ctx, DSPSR_AMD_ENOMEM, "dspsr_amd_filterbank_perform_fold: hipMalloc of %zu bytes failed", need * sizeof(float));
     // (ndim 2: the channel's two rows of npart*nkeep float2 one after the other)
-    FbOut dout = {2, fb->det, row, planes2 ? row / 2 : 0, 0, state, planes2 ? 2u : 4u, 0};
-    rc = fb_run(fb, in, dout, npart, in_chan_stride);
+    rc = fb_run(fb, in, fb_out_detected(fb->det, row, planes2 ? row / 2 : 0, state, planes2 ? 2u : 4u), npart, in_chan_stride);
     if (rc != DSPSR_AMD_OK) return rc;
     return dspsr_amd_fold_fold(fold, fb->det, row, planes2 ? row / 2 : 0);
   }
@@ -1501,9 +1508,6 @@ extern "C" int dspsr_amd_filterbank_perform_fold(dspsr_amd_filterbank* fb, const
   PlanSlot* slot = nullptr;
   rc = fold_build_part_plan(fold, fb->g.nkeep, (uint32_t)npart, &d_start, &d_iv, &slot);
   if (rc != DSPSR_AMD_OK) return rc;
-  // (float4 from one channel to the next: span/4, or both rows of the channel, 2*span/4)
-  FbOut out = {3, fold->profile, 0, 0, 0, state, 4, 0, fold->nbin, planes2 ? fold->span / 2 : fold->span / 4, planes2 ? 2u : 1u,
-               fold->span, nullptr, fold->nchan, 0, fold, d_start, (uint32_t)npart, 0, d_iv};
-  return fb_run_with_plan(fb, fold, slot, in, out, npart, in_chan_stride);
+  return fb_run_with_plan(fb, fold, slot, in, fb_out_fold(fold, state, planes2, d_start, d_iv, (uint32_t)npart), npart, in_chan_stride);
 }
 

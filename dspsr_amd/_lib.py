@@ -14,10 +14,32 @@ LIB_PATH = os.environ.get("DSPSR_AMD_LIB") or os.path.join(_HERE, "libdspsr_amd.
 OK, EINVAL, EHIP, ENOMEM, ESTATE = 0, -1, -2, -3, -4
 H2D, D2H, D2D = 1, 2, 3
 RAW_GENERIC, RAW_CASPSR, RAW_UWB16 = 0, 1, 2
+RAW_MEERKAT, RAW_MEERKAT_SWAP = 3, 4      # heaps of 256 samples per (pol, chan) run; _SWAP: odd and even samples exchanged (MKBFRo)
+HEAP_NSAMP = 256
+HEAP_MACHINES = {"MKBF": RAW_MEERKAT, "MKBFRo": RAW_MEERKAT_SWAP}   # INSTRUMENT -> layout (kat/MeerKATUnpacker.C: sample_swap 2 for MKBFRo)
 COHERENCE, STOKES, INTENSITY, PPQQ = 0, 1, 2, 3
 FUSED_AUTO, FUSED_ALWAYS, FUSED_NEVER = 0, 1, 2
 REDUCE_SUM, REDUCE_GATHER = 0, 1
 UNIQUE_ID_BYTES = 128
+
+
+def raw_at(layout: int, first_sample: int) -> int:
+    """DSPSR_AMD_RAW_AT: the layout word of a block of heaps whose first sample lies at `first_sample` of its first heap."""
+    if layout not in (RAW_MEERKAT, RAW_MEERKAT_SWAP):
+        raise ValueError("raw_at: layout %d is not a heap layout (RAW_MEERKAT, RAW_MEERKAT_SWAP)" % layout)
+    if not 0 <= first_sample < HEAP_NSAMP:
+        raise ValueError("raw_at: first_sample %d is not inside a heap of %d samples" % (first_sample, HEAP_NSAMP))
+    return layout | (first_sample << 8)
+
+
+def is_heaps(layout: int) -> bool:
+    """The layout word names one of the heap layouts (with or without a first sample)."""
+    return layout >= 0 and (layout & 0xff) in (RAW_MEERKAT, RAW_MEERKAT_SWAP)
+
+
+def heap_block_bytes(first_sample: int, nsamp: int, nchan: int, npol: int) -> int:
+    """Bytes of the whole heaps that hold `nsamp` samples from `first_sample` of the first heap on."""
+    return -(-(first_sample + nsamp) // HEAP_NSAMP) * npol * nchan * HEAP_NSAMP * 2
 
 
 class FilterbankConfig(C.Structure):
@@ -73,6 +95,7 @@ SYMBOLS = {
     "dspsr_amd_filterbank_fold_is_fused": (_i, [_vp]),
     "dspsr_amd_filterbank_npass": (_i, [_vp, _i]),
     "dspsr_amd_filterbank_presplit": (_i, [_vp]),
+    "dspsr_amd_filterbank_takes_heaps": (_i, [_vp]),
     "dspsr_amd_filterbank_perform_fold": (_i, [_vp, _vp, _u64, _u64, _u64, _vp, _i, _f, _i, _vp, _u64]),
     "dspsr_amd_filterbank_perform_search": (_i, [_vp, _vp, _u64, _u64, _u64, _vp, _i, _f, _i, _u32, _vp, _u64, _u64, _vp,
                                                  C.POINTER(_u32), _u64, C.POINTER(_u64)]),
@@ -99,6 +122,7 @@ SYMBOLS = {
     "dspsr_amd_detect_polarimetry": (_i, [_vp, _i, _u32, _vp, _u64, _u64, _vp, _u64, _u64, _u32, _u64]),
     "dspsr_amd_detect_square_law": (_i, [_vp, _i, _vp, _u64, _u64, _vp, _u64, _u64, _u32, _u32, _u64]),
     "dspsr_amd_unpack_fpt": (_i, [_vp, _vp, _f, _u32, _u32, _u32, _u64, _vp, _u64, _u64]),
+    "dspsr_amd_unpack_heaps_fpt": (_i, [_vp, _vp, _i, _f, _u32, _u32, _u64, _vp, _u64, _u64]),
     "dspsr_amd_detect_raw": (_i, [_vp, _vp, _f, _u32, _u32, _u64, _i, _u32, _vp, _u64, _u64, _vp, C.POINTER(_u32), C.POINTER(_u64)]),
     "dspsr_amd_tfp_filterbank": (_i, [_vp, C.POINTER(TfpConfig), _vp, _i, _f, _vp, _u64]),
     "dspsr_amd_fold_create": (_i, [_vp, _pp]),

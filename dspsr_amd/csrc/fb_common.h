@@ -66,10 +66,12 @@ enum FbInKind : int {
   FB_IN_RT_BYTES = 3,  // (pol0, pol1) byte pairs pre-transposed per tile
   FB_IN_UWB16 = 4,     // 16-bit offset-binary complex in 2048-sample blocks per polarisation (UWB)
   FB_IN_RT_FLOAT = 5,  // float32 pairs pre-transposed per tile ((pol0, pol1) of real input or (re, im) of one polarisation)
+  FB_IN_HEAPS = 6,     // int8 complex, MeerKAT heaps of 256 samples per (pol, chan) run (unpack_heaps.hip): the one-pass convolution only
 };
 
 struct FbIn {
   FbInKind kind;
+  uint16_t heap_first, heap_swap;   // HEAPS: index inside the block's first heap of the call's first sample; 1 = odd and even samples exchanged
   const void* base;
   uint64_t pol_stride;  // float32: floats between pol rows
   uint64_t part_step;   // time samples between parts
@@ -644,10 +646,13 @@ void fb_launch_time_combine(hipStream_t stream, const TimeCombine& p, const FbOu
 void fb_launch_raw_transpose(hipStream_t stream, const FbGeom& g, const FbIn& in, uint16_t* Rt, uint64_t part0, uint32_t nb, uint32_t nseq,
                              const RtLayout& lay);
 void fb_launch_float_transpose(dim3 grid, hipStream_t stream, const FbGeom& g, const FbIn& in, cf* Rt, uint64_t part0);
-// dsp::Convolution with n_fft <= 8192 in one tile pass (fb_conv1.hip): complex float32 rows, two polarisations
+// dsp::Convolution with n_fft <= 8192 in one tile pass (fb_conv1.hip): two polarisations, complex float32 rows or (heaps != null,
+// `in` and its strides unused) a block of MeerKAT heaps whose parts are `step` samples apart
+struct Conv1Heaps { const void* raw; uint32_t step, first_sample; bool swap; float scale; };
 int fb_conv1_check(int logM, size_t* lds_bytes);
 int fb_conv1_launch(dspsr_amd_ctx* ctx, int logM, const float* in, uint64_t chan_stride, uint64_t pol_stride, uint64_t in_step,
-                    const cf* kern, const FbOut& out, uint32_t nchan, uint32_t nfilt_pos, uint32_t nkeep, uint64_t npart);
+                    const Conv1Heaps* heaps, const cf* kern, const FbOut& out, uint32_t nchan, uint32_t nfilt_pos, uint32_t nkeep,
+                    uint64_t npart);
 // non-convolving filterbank, freq_res = 1 (fb_plain.hip): kernel choice + dynamic-LDS limit at create time, one launch per call
 // dsp::Convolution in three tile passes (fb_conv3.hip): n_fft = 2^14 ... 2^21 on complex float32 rows with two polarisations
 constexpr int CONV3_MIN_LOGM = 14, CONV3_MAX_LOGM = 21;

@@ -27,6 +27,11 @@ struct Conv1Params {
   uint32_t nchan, nfilt_pos, nkeep;
   uint64_t npart;
   uint32_t tiles_per_chan;
+  // HEAPS: a block of MeerKAT heaps instead of `in` (unpack_heaps.hip has the byte order).  Element (chan, pol, part, n) is stream
+  // sample t = first_sample + part * step + n, stored as 16-bit word ((t >> 8) * npol + pol) * nchan + chan) * 256 + ((t & 255) ^ swap)
+  const uint16_t* raw;
+  uint32_t npol, step, first_sample, swap;    // step = nsamp_step; swap 1: odd and even samples exchanged (MKBFRo)
+  float scale;
 };
 
 // the response factors of a thread: one per element the forward transform's last stage hands it, in the order of those calls
@@ -49,8 +54,10 @@ template <int N> struct Conv1Fwd {
 // LOGP: points per tile -- 2^13 (256 threads, two workgroups per compute unit: one's store phase under the other's transforms) up to
 // n_fft = 4096, 2^14 for n_fft = 8192 (two polarisations of one part)
 constexpr int conv1_log_points(int logM) { return logM <= 12 ? 13 : 14; }
-template <int LOGM>
-__global__ __launch_bounds__(512) void k_conv1(const Conv1Params p, const cf* __restrict__ tw)
+// The body of the two kernels below.  HEAPS: the tile's elements come from the 8-bit block, the two bytes of a polarisation's sample
+// in one register between the prefetch and the decode (32 registers a tile instead of 64); everything behind the decode is the float
+// kernel's code
+template <int LOGM, bool HEAPS> DEV void conv1_tiles(const Conv1Params& p, const cf* __restrict__ tw)
 {
   typedef FftPlan<LOGM> P;
   static_assert(P::NS >= 2 && LOGM <= 13, "k_conv1: 64 <= n_fft <= 8192");
@@ -69,9 +76,12 @@ __global__ __launch_bounds__(512) void k_conv1(const Conv1Params p, const cf* __
   if (item >= item_end) return;
   const uint64_t last_part = p.npart - 1;
   struct Pol2 { cf a, b; };
-  auto fetch = [&](const uint32_t it, Pol2 (&raw)[NPAIR]) {
+  struct Raw2 { uint32_t a, b; };                                          // HEAPS: the (re, im) byte pairs of the two polarisations
+  typedef typename std::conditional<HEAPS, Raw2, Pol2>::type RawElem;
+  auto fetch = [&](const uint32_t it, RawElem (&raw)[NPAIR]) {
     const uint32_t chan = it / p.tiles_per_chan, tl = it - chan * p.tiles_per_chan;
     const float* __restrict__ row = p.in + (uint64_t)chan * p.chan_stride;
+    const uint64_t pol_words = (uint64_t)p.nchan << 8;                    // HEAPS: 16-bit words from a run to the other polarisation's
 #pragma unroll
     for (int g2 = 0; g2 < P::G1; g2 += 2)
 #pragma unroll
@@ -80,11 +90,23 @@ __global__ __launch_bounds__(512) void k_conv1(const Conv1Params p, const cf* __
         const uint32_t j = (e & (T - 1)) >> 1, n = e >> logT;
         uint64_t part = (uint64_t)tl * Ts + j;
         part = part < last_part ? part : last_part;                       // (ragged last tile: loaded again, never stored)
-        const float* __restrict__ q = row + part * p.in_step + 2 * n;
-        Pol2 r;
-        r.a = *(const float2*)q;
-        r.b = *(const float2*)(q + p.pol_stride);
-        raw[(g2 / 2) * P::R1 + i] = r;
+        if constexpr (HEAPS) {
+          const uint64_t t = p.first_sample + part * p.step + n;
+          const uint16_t* __restrict__ q = p.raw + ((((t >> 8) * p.npol) * p.nchan + chan) << 8) + (((uint32_t)t & 255u) ^ p.swap);
+          // two independent 16-bit loads, combined only in the decode: the words stay in flight while this tile is transformed
+          // (one register for both would have to be merged here, behind a wait: with SRAM ECC on, gfx950's 16-bit loads into a
+          //  register half do not keep the other half)
+          Raw2 r;
+          r.a = q[0];
+          r.b = q[pol_words];
+          raw[(g2 / 2) * P::R1 + i] = r;
+        } else {
+          const float* __restrict__ q = row + part * p.in_step + 2 * n;
+          Pol2 r;
+          r.a = *(const float2*)q;
+          r.b = *(const float2*)(q + p.pol_stride);
+          raw[(g2 / 2) * P::R1 + i] = r;
+        }
       }
   };
   // forward last stage: radix RL, G = 32 / RL butterflies per thread, pair h = butterflies 2h, 2h + 1: bin k * (M / RL) + pp(h)
@@ -105,7 +127,7 @@ __global__ __launch_bounds__(512) void k_conv1(const Conv1Params p, const cf* __
       for (int k = 0; k < RL; k++) kk[h * RL + k] = kc[((uint32_t)k << logPL) + pp];
     }
   };
-  Pol2 raw[NPAIR];
+  RawElem raw[NPAIR];
   fetch(item, raw);
   for (;;) {
     asm volatile("" : "+v"(tid));
@@ -113,7 +135,15 @@ __global__ __launch_bounds__(512) void k_conv1(const Conv1Params p, const cf* __
     if (chan != kk_chan) { load_response(chan); kk_chan = chan; }
     cx2 x[NPAIR];
 #pragma unroll
-    for (int h = 0; h < NPAIR; h++) x[h] = make_cx2(raw[h].a, raw[h].b);
+    for (int h = 0; h < NPAIR; h++) {
+      if constexpr (HEAPS) {
+        const uint32_t a = raw[h].a, b = raw[h].b;
+        x[h] = make_cx2(make_float2(cvt8((int8_t)(a & 0xff), p.scale), cvt8((int8_t)(a >> 8), p.scale)),
+                        make_float2(cvt8((int8_t)(b & 0xff), p.scale), cvt8((int8_t)(b >> 8), p.scale)));
+      } else {
+        x[h] = make_cx2(raw[h].a, raw[h].b);
+      }
+    }
     const uint32_t next = item + 1;
     const bool more = next < item_end;
     fetch(more ? next : item, raw);          // unconditional: a conditional prefetch is waited for inside its block (fb_inv_chan.h)
@@ -168,11 +198,21 @@ __global__ __launch_bounds__(512) void k_conv1(const Conv1Params p, const cf* __
   }
 }
 
+template <int LOGM> __global__ __launch_bounds__(512) void k_conv1(const Conv1Params p, const cf* __restrict__ tw)
+{
+  conv1_tiles<LOGM, false>(p, tw);
+}
+template <int LOGM> __global__ __launch_bounds__(512) void k_conv1_heaps(const Conv1Params p, const cf* __restrict__ tw)
+{
+  conv1_tiles<LOGM, true>(p, tw);
+}
+
 typedef void (*kconv1_t)(Conv1Params, const cf*);
-template <int... I> static kconv1_t pick_conv1(int logm, iseq<I...>)
+template <int... I> static kconv1_t pick_conv1(int logm, iseq<I...>, bool heaps = false)
 {
   static const kconv1_t t[] = {k_conv1<I + 6>...};
-  return logm >= 6 && logm < 6 + (int)sizeof...(I) ? t[logm - 6] : nullptr;
+  static const kconv1_t th[] = {k_conv1_heaps<I + 6>...};
+  return logm >= 6 && logm < 6 + (int)sizeof...(I) ? (heaps ? th : t)[logm - 6] : nullptr;
 }
 
 int fb_conv1_check(int logM, size_t* lds_bytes)
@@ -181,16 +221,23 @@ int fb_conv1_check(int logM, size_t* lds_bytes)
   if (!k) return DSPSR_AMD_EINVAL;
   const size_t lds = lds_total_words_host(1u << conv1_log_points(logM), logM) * sizeof(cf);
   if (lds_bytes) *lds_bytes = lds;
-  return dspsr_amd_allow_lds((const void*)k, lds) == hipSuccess ? DSPSR_AMD_OK : DSPSR_AMD_EHIP;
+  if (dspsr_amd_allow_lds((const void*)k, lds) != hipSuccess) return DSPSR_AMD_EHIP;
+  return dspsr_amd_allow_lds((const void*)pick_conv1(logM, mkseq<8>::type(), true), lds) == hipSuccess ? DSPSR_AMD_OK : DSPSR_AMD_EHIP;
 }
 
+// heaps != null: the input is a block of heaps (in and its strides unused), else float rows
 int fb_conv1_launch(dspsr_amd_ctx* ctx, int logM, const float* in, uint64_t chan_stride, uint64_t pol_stride, uint64_t in_step,
-                    const cf* kern, const FbOut& out, uint32_t nchan, uint32_t nfilt_pos, uint32_t nkeep, uint64_t npart)
+                    const Conv1Heaps* heaps, const cf* kern, const FbOut& out, uint32_t nchan, uint32_t nfilt_pos, uint32_t nkeep,
+                    uint64_t npart)
 {
-  kconv1_t k = pick_conv1(logM, mkseq<8>::type());
+  kconv1_t k = pick_conv1(logM, mkseq<8>::type(), heaps != nullptr);
   if (!k) return DSPSR_AMD_EINVAL;
   Conv1Params p = {};
   p.in = in; p.chan_stride = chan_stride; p.pol_stride = pol_stride; p.in_step = in_step;
+  if (heaps) {
+    p.raw = (const uint16_t*)heaps->raw; p.npol = 2; p.step = heaps->step; p.first_sample = heaps->first_sample;
+    p.swap = heaps->swap ? 1u : 0u; p.scale = heaps->scale;
+  }
   p.kern = kern; p.out = out; p.nchan = nchan; p.nfilt_pos = nfilt_pos; p.nkeep = nkeep; p.npart = npart;
   const int lp = conv1_log_points(logM);
   const uint32_t Ts = (1u << (lp - logM)) / 2;

@@ -870,8 +870,11 @@ static int fb_run_conv1(dspsr_amd_filterbank* fb, const FbIn& in, const FbOut& o
 {
   const FbGeom& g = fb->g;
   const cf* kern = fb->kernel ? (g.xblocked ? fb->kernel_nat : fb->kernel) : nullptr;
-  const int rc = fb_conv1_launch(fb->ctx, fb->conv1_logM, (const float*)in.base, chan_stride, in.pol_stride, 2 * in.part_step, kern, out,
-                                 fb->cfg.input_nchan, g.nfilt_pos, g.nkeep, npart);
+  const Conv1Heaps heaps = {in.base, (uint32_t)in.part_step, in.heap_first, in.heap_swap != 0, in.scale};
+  const int rc = in.kind == FB_IN_HEAPS
+                     ? fb_conv1_launch(fb->ctx, fb->conv1_logM, nullptr, 0, 0, 0, &heaps, kern, out, fb->cfg.input_nchan, g.nfilt_pos, g.nkeep, npart)
+                     : fb_conv1_launch(fb->ctx, fb->conv1_logM, (const float*)in.base, chan_stride, in.pol_stride, 2 * in.part_step, nullptr, kern,
+                                       out, fb->cfg.input_nchan, g.nfilt_pos, g.nkeep, npart);
   return rc == DSPSR_AMD_OK ? rc : fb_fail(fb->ctx, rc, "dspsr_amd_filterbank_perform: launch of the one-pass convolution failed");
 }
 
@@ -1203,6 +1206,12 @@ static int fb_run(dspsr_amd_filterbank* fb, const FbIn& in, const FbOut& out, ui
   const bool conv_rows = in.kind == FB_IN_FLOAT && fb_out_is_rows(out) && (chan_stride % 2) == 0 && (in.pol_stride % 2) == 0 &&
                          ((uintptr_t)in.base % 8) == 0;
   if (fb->conv1_logM >= 0 && conv_rows) return fb_run_conv1(fb, in, out, npart, chan_stride);
+  // a block of heaps: the one-pass convolution's second loader and nothing else (fb_input has refused every other object)
+  if (in.kind == FB_IN_HEAPS) {
+    if (fb->conv1_logM < 0 || !fb_out_is_rows(out))
+      return fb_fail(ctx, DSPSR_AMD_EINVAL, "dspsr_amd_filterbank_perform: output kind %d has no form that reads MeerKAT heaps", (int)out.kind);
+    return fb_run_conv1(fb, in, out, npart, chan_stride);
+  }
   if (fb->conv3_logM >= 0 && conv_rows) return fb_run_conv3(fb, in, out, npart, chan_stride);
   if (fb->batch && in.kind == FB_IN_FLOAT && fb_out_is_rows(out) && (chan_stride % 2) == 0)
     return fb_run_batched(fb, in, out, npart, chan_stride);
@@ -1233,18 +1242,37 @@ static int fb_input(dspsr_amd_filterbank* fb, const char* fn, const float* in_f3
     const uint32_t idim = c.real_input ? 1 : 2;
     if (in_step % idim)
       return fb_fail(fb->ctx, DSPSR_AMD_EINVAL, "%s: in_step=%llu not a multiple of ndim", fn, (unsigned long long)in_step);
-    *in = {FB_IN_FLOAT, in_f32_dev, in_pol_stride, in_step / idim, c.input_nchan, 0, 1.0f};
+    *in = {FB_IN_FLOAT, 0, 0, in_f32_dev, in_pol_stride, in_step / idim, c.input_nchan, 0, 1.0f};
     return DSPSR_AMD_OK;
+  }
+  // a block of heaps: the layout word carries the index of the call's first sample inside the block's first heap
+  const uint32_t first = raw_layout < 0 ? 0u : (uint32_t)raw_layout >> 8;
+  if (first) raw_layout &= 0xff;
+  const bool heaps = raw_layout == DSPSR_AMD_RAW_MEERKAT || raw_layout == DSPSR_AMD_RAW_MEERKAT_SWAP;
+  if (first && !heaps)
+    return fb_fail(fb->ctx, DSPSR_AMD_EINVAL, "%s: first_sample=%u on raw layout %d: only the heap layouts (DSPSR_AMD_RAW_MEERKAT, "
+                   "DSPSR_AMD_RAW_MEERKAT_SWAP) carry one", fn, first, raw_layout);
+  if (heaps) {
+    if (first > 255)
+      return fb_fail(fb->ctx, DSPSR_AMD_EINVAL, "%s: first_sample=%u is not inside a heap of 256 samples", fn, first);
+    if (fb->conv1_logM < 0)
+      return fb_fail(fb->ctx, DSPSR_AMD_EINVAL, "%s: this object does not read MeerKAT heaps (dspsr_amd_filterbank_takes_heaps() == 0: that "
+                     "needs nchan_subband = 1, complex input, npol = 2, 64 <= freq_res <= 8192 and force_four_pass = 0; here nchan_subband=%u "
+                     "real_input=%u npol=%u freq_res=%u force_four_pass=%u) -- dspsr_amd_unpack_heaps_fpt first, then the float32 entry points",
+                     fn, c.nchan_subband, c.real_input, c.npol, c.freq_res, c.force_four_pass);
+    if (((uintptr_t)raw_dev % 16) != 0)
+      return fb_fail(fb->ctx, DSPSR_AMD_EINVAL, "%s: a block of heaps must start at a multiple of 16 bytes", fn);
   }
   if (raw_layout == DSPSR_AMD_RAW_CASPSR && !(c.real_input && c.npol == 2 && c.input_nchan == 1))
     return fb_fail(fb->ctx, DSPSR_AMD_EINVAL, "%s: CASPSR layout needs real dual-pol single-channel input", fn);
   if (raw_layout == DSPSR_AMD_RAW_UWB16 && (c.real_input || c.input_nchan != 1))
     return fb_fail(fb->ctx, DSPSR_AMD_EINVAL, "%s: UWB 16-bit layout needs complex single-channel input", fn);
-  if (raw_layout != DSPSR_AMD_RAW_CASPSR && raw_layout != DSPSR_AMD_RAW_GENERIC && raw_layout != DSPSR_AMD_RAW_UWB16)
+  if (raw_layout != DSPSR_AMD_RAW_CASPSR && raw_layout != DSPSR_AMD_RAW_GENERIC && raw_layout != DSPSR_AMD_RAW_UWB16 && !heaps)
     return fb_fail(fb->ctx, DSPSR_AMD_EINVAL, "%s: unknown raw layout %d", fn, raw_layout);
   uint64_t step;
   dspsr_amd_filterbank_sizes(fb, nullptr, nullptr, &step, nullptr);
-  *in = {raw_kind(raw_layout), raw_dev, 0, step, c.input_nchan, 0, scale};
+  *in = {heaps ? FB_IN_HEAPS : raw_kind(raw_layout), (uint16_t)first, (uint16_t)(raw_layout == DSPSR_AMD_RAW_MEERKAT_SWAP), raw_dev, 0, step,
+         c.input_nchan, 0, scale};
   return DSPSR_AMD_OK;
 }
 
@@ -1393,6 +1421,8 @@ extern "C" int dspsr_amd_filterbank_perform_search(dspsr_amd_filterbank* fb, con
 }
 
 extern "C" int dspsr_amd_filterbank_presplit(const dspsr_amd_filterbank* fb) { return fb && fb->presplit ? 1 : 0; }
+
+extern "C" int dspsr_amd_filterbank_takes_heaps(const dspsr_amd_filterbank* fb) { return fb && fb->conv1_logM >= 0 ? 1 : 0; }
 
 extern "C" int dspsr_amd_filterbank_npass(const dspsr_amd_filterbank* fb, int raw_input)
 {

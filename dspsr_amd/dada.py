@@ -15,9 +15,39 @@ import time
 
 import numpy as np
 
+from . import _lib
 from .engine import DspsrAmdError
 
 DEFAULT_HEADER_SIZE = 4096            # DADAFile.C:44
+HEAP_NSAMP = _lib.HEAP_NSAMP          # samples of one (pol, chan) run of a MeerKAT heap (kat/MeerKATUnpacker.C:137-230)
+
+
+def heaps_from_tfp(tfp: np.ndarray, swap: bool = False) -> np.ndarray:
+    """int8 [ndat][nchan][npol][2] (generic DADA order, ndat a multiple of 256) -> the MeerKAT beamformer's block of heaps
+    [heap][npol][nchan][256][2]: heap h holds samples 256 h ... 256 h + 255 of every (pol, chan) as one contiguous run; swap
+    (MKBFRo): stream sample t is stored at (t & 255) ^ 1."""
+    tfp = np.asarray(tfp)
+    if tfp.ndim != 4 or tfp.shape[3] != 2 or tfp.shape[0] % HEAP_NSAMP:
+        raise DspsrAmdError("dspsr_amd.dada.heaps_from_tfp: [ndat][nchan][npol][2] with ndat a multiple of %d expected, got %s"
+                            % (HEAP_NSAMP, tfp.shape,))
+    ndat, nchan, npol, _ = tfp.shape
+    x = tfp.reshape(ndat // HEAP_NSAMP, HEAP_NSAMP, nchan, npol, 2)
+    if swap:
+        x = x.reshape(-1, HEAP_NSAMP // 2, 2, nchan, npol, 2)[:, :, ::-1].reshape(x.shape)
+    return np.ascontiguousarray(x.transpose(0, 3, 2, 1, 4))
+
+
+def tfp_from_heaps(heaps: np.ndarray, nchan: int, npol: int, swap: bool = False) -> np.ndarray:
+    """The inverse of heaps_from_tfp: a block of whole heaps (any shape, nheap * npol * nchan * 512 bytes) ->
+    int8 [nheap * 256][nchan][npol][2]."""
+    h = np.asarray(heaps).reshape(-1)
+    per = npol * nchan * HEAP_NSAMP * 2
+    if h.size % per:
+        raise DspsrAmdError("dspsr_amd.dada.tfp_from_heaps: %d bytes are not whole heaps of %d" % (h.size, per))
+    x = h.reshape(-1, npol, nchan, HEAP_NSAMP, 2).transpose(0, 3, 2, 1, 4)          # [heap][s][chan][pol][2]
+    if swap:
+        x = x.reshape(-1, HEAP_NSAMP // 2, 2, nchan, npol, 2)[:, :, ::-1]
+    return np.ascontiguousarray(x).reshape(-1, nchan, npol, 2)
 
 
 def header_find(header: str, keyword: str) -> int:
@@ -231,6 +261,14 @@ class DadaFile:
         self.bytes_per_sample = self.info.nchan * self.info.npol * self.info.ndim
         nbytes = os.path.getsize(path) - self.header_bytes
         self.ndat = nbytes // self.bytes_per_sample                     # File::open_fd: from the file size
+        # MeerKAT beamformer: whole heaps of 256 samples per (pol, chan) run (MeerKATUnpacker::matches: MKBF / MKBFRo, 8 bit)
+        self.heaps = self.info.machine in _lib.HEAP_MACHINES
+        if self.heaps:
+            if self.info.ndim != 2 or self.info.npol not in (1, 2):
+                raise DspsrAmdError("dspsr_amd.DadaFile: INSTRUMENT %s is complex 8-bit with one or two polarisations (NDIM 2, NBIT 8, "
+                                    "NPOL 1 | 2); the header says NDIM=%d NPOL=%d" % (self.info.machine, self.info.ndim, self.info.npol))
+            self.heap_bytes = self.bytes_per_sample * HEAP_NSAMP
+            self.ndat = (nbytes // self.heap_bytes) * HEAP_NSAMP        # whole heaps only
         self._map = np.memmap(path, dtype=np.int8, mode="r", offset=self.header_bytes,
                               shape=(self.ndat * self.bytes_per_sample,)) if self.ndat else np.zeros(0, np.int8)
 
@@ -245,7 +283,10 @@ class DadaFile:
         """Yield (int8 host array, npart) for LoadToFold `lt`; the last block may hold fewer parts.  Samples past the last
         whole overlap-save part are not used (the reference leaves them in the input buffer at end of data).  The arrays
         are views of the memory-mapped file (process_host_blocks stages them through its own pinned buffers).
-        channel = g: only input channel g's bytes ([t][pol][dim]), what rank g of a sub-band sharded run reads."""
+        channel = g: only input channel g's bytes ([t][pol][dim]), what rank g of a sub-band sharded run reads.
+        A file of heaps (MKBF / MKBFRo) yields (the whole heaps that hold the block, npart, first_sample): the block starts at
+        sample first_sample = (b * parts_per_block * nsamp_step) & 255 of its first heap; channel = g: that channel's runs, a block
+        of heaps with nchan = 1."""
         full, rest = self.nblocks(lt)
         ppb, step, ovl, bps = lt.cfg.parts_per_block, lt.nsamp_step, lt.nsamp_overlap, self.bytes_per_sample
         per_chan = self.info.npol * self.info.ndim
@@ -253,6 +294,14 @@ class DadaFile:
             npart = ppb if b < full else rest
             nsamp = npart * step + ovl
             s0 = b * ppb * step
+            if self.heaps:
+                first = s0 % HEAP_NSAMP
+                h0, nheap = s0 // HEAP_NSAMP, -(-(first + nsamp) // HEAP_NSAMP)
+                src = self._map[h0 * self.heap_bytes:(h0 + nheap) * self.heap_bytes]
+                if channel is not None:
+                    src = np.ascontiguousarray(src.reshape(nheap, self.info.npol, self.info.nchan, HEAP_NSAMP * 2)[:, :, channel, :]).reshape(-1)
+                yield src, npart, first
+                continue
             src = self._map[s0 * bps:(s0 + nsamp) * bps]
             if channel is not None:
                 src = np.ascontiguousarray(src.reshape(nsamp, self.info.nchan, per_chan)[:, channel, :]).reshape(-1)

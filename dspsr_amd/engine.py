@@ -190,14 +190,18 @@ class FilterbankEngine(_Owned):
 
     def setup(self, nchan_subband, freq_res, nfilt_pos, nfilt_neg, input_nchan=1, npol=2, real_input=True,
               kernel: np.ndarray | None = None, max_parts: int = 1, force_four_pass: bool | int = False,
-              fused_fold: int = _lib.FUSED_AUTO, split_in_inverse: bool = False, response_matrix: np.ndarray | None = None):
+              fused_fold: int = _lib.FUSED_AUTO, split_in_inverse: bool = False, response_matrix: np.ndarray | None = None,
+              fuse_heaps: bool = True):
         """force_four_pass: False / 0 = passes chosen from the geometry, True / 1 = two-pass inverse everywhere, 2 = never the
         two-pass path of short responses (dspsr_amd_filterbank_config::force_four_pass).
         split_in_inverse: True keeps the Hermitian split of real dual-polarisation input in the inverse pass
         (dspsr_amd_filterbank_config::split_in_inverse); see presplit().
         response_matrix: float32 [nchan_subband * freq_res][8], one Jones matrix per bin as f11, f21, f22, f12 (`dspsr -pac`,
         dspsr_amd_filterbank_set_response_matrix); mutually exclusive with kernel.  When the library refuses it the object
-        stays created, without a response: set_kernel() may still be called."""
+        stays created, without a response: set_kernel() may still be called.
+        fuse_heaps: False keeps blocks of MeerKAT heaps (RAW_MEERKAT / RAW_MEERKAT_SWAP) off the one-pass kernel's own loader even
+        where the object has one (takes_heaps()): the engine unpacks them and hands float rows over, as it does for every other
+        object (tests and comparison runs; the same numbers bit for bit)."""
         if kernel is not None and response_matrix is not None:
             raise DspsrAmdError("dspsr_amd.FilterbankEngine.setup: kernel and response_matrix are mutually exclusive")
         self.close()
@@ -207,6 +211,9 @@ class FilterbankEngine(_Owned):
         self._create(C.byref(cfg))
         h = self.handle
         self.cfg = cfg
+        self.max_parts = max(1, int(max_parts))
+        self.fuse_heaps = bool(fuse_heaps)
+        self._heap_rows = None      # float rows of an unpacked block of heaps: allocated by the first call that needs them
         a, b, c, d = C.c_uint64(), C.c_uint64(), C.c_uint64(), C.c_uint32()
         lib.dspsr_amd_filterbank_sizes(h, C.byref(a), C.byref(b), C.byref(c), C.byref(d))
         self.nsamp_fft, self.nsamp_overlap, self.nsamp_step, self.nkeep = a.value, b.value, c.value, d.value
@@ -247,11 +254,38 @@ class FilterbankEngine(_Owned):
     def _raw_bytes(self, npart, layout=_lib.RAW_GENERIC):
         c = self.cfg
         nsamp = npart * self.nsamp_step + self.nsamp_overlap
+        if _lib.is_heaps(layout):
+            # whole heaps from the one that holds the call's first sample on
+            return _lib.heap_block_bytes(layout >> 8, nsamp, c.input_nchan, c.npol)
         if layout == _lib.RAW_CASPSR:
             # 4 samples of pol0 then 4 of pol1: the block must hold WHOLE 8-byte groups (its last samples' pol1 bytes lie
             # up to 4 bytes behind their pol0 bytes; CASPSRUnpacker.C:132-187 unpacks group by group)
             return ((nsamp + 3) // 4) * 8
         return nsamp * c.input_nchan * c.npol * (1 if c.real_input else 2)
+
+    def takes_heaps(self) -> bool:
+        """True: the raw entry points read a block of MeerKAT heaps inside their one tile pass (dspsr_amd_filterbank_takes_heaps)."""
+        return bool(lib.dspsr_amd_filterbank_takes_heaps(self.handle))
+
+    def _unpacked_heaps(self, raw, layout, scale, npart):
+        """A block of heaps this object does not read itself (or fuse_heaps=False), unpacked into float rows owned by the engine:
+        (rows [input_nchan][npol][2 * nsamp], in_step), or None when the block goes to the library as it is.  The rows are
+        allocated on first use for max_parts parts (a longer call allocates again)."""
+        if raw is None or not _lib.is_heaps(layout) or (self.fuse_heaps and self.takes_heaps()):
+            return None
+        import torch
+        c = self.cfg
+        if c.real_input:
+            raise DspsrAmdError("dspsr_amd.FilterbankEngine: MeerKAT heaps are complex samples; the object was set up for real input")
+        parts = max(npart, self.max_parts)
+        need = 2 * (parts * self.nsamp_step + self.nsamp_overlap)
+        if self._heap_rows is None or self._heap_rows.shape[2] < need or self._heap_rows.device != raw.device:
+            self._heap_rows = torch.empty((c.input_nchan, c.npol, need), dtype=torch.float32, device=raw.device)
+        if npart:
+            self._need("raw block", raw.numel(), self._raw_bytes(npart, layout))
+            unpack_heaps_fpt(self.ctx, raw, self._heap_rows, c.input_nchan, c.npol, layout, scale,
+                             ndat=npart * self.nsamp_step + self.nsamp_overlap)
+        return self._heap_rows, 2 * self.nsamp_step
 
     def perform(self, inp, out, npart, in_step, out_step):
         ics, ips = _strides3(inp)
@@ -271,9 +305,12 @@ class FilterbankEngine(_Owned):
                                                 out_step), "dspsr_amd_filterbank_perform")
 
     def perform_raw(self, raw, layout, scale, out, npart, out_step=None):
-        ocs, ops = _strides3(out) if out is not None else (0, 0)
         if out_step is None:
             out_step = 2 * self.nkeep
+        rows = self._unpacked_heaps(raw, layout, scale, npart)
+        if rows is not None:
+            return self.perform(rows[0], out, npart, rows[1], out_step)
+        ocs, ops = _strides3(out) if out is not None else (0, 0)
         if npart:
             if layout != _lib.RAW_UWB16:
                 self._need("raw block", raw.numel(), self._raw_bytes(npart, layout))
@@ -286,6 +323,9 @@ class FilterbankEngine(_Owned):
 
     def perform_detect(self, det, npart, state=_lib.COHERENCE, ndim=4, inp=None, in_step=0, raw=None,
                        layout=_lib.RAW_GENERIC, scale=1.0):
+        rows = self._unpacked_heaps(raw, layout, scale, npart)
+        if rows is not None:
+            inp, in_step, raw = rows[0], rows[1], None
         dcs, dps = _strides3(det)
         if npart:
             self._need("detected block", det.shape[2], npart * self.nkeep * ndim)
@@ -314,6 +354,9 @@ class FilterbankEngine(_Owned):
         (Intensity / PPQQ) -> TScrunch on the detected stream.  out: device float32 rows [nchan][npol_out][>= nout]; carry:
         device float32 [nchan][npol_out] (the open output sample's partial sums); carry_count: samples already in it.
         Returns (nout, carry_count_after)."""
+        rows = self._unpacked_heaps(raw, layout, scale, npart)
+        if rows is not None:
+            inp, in_step, raw = rows[0], rows[1], None
         ocs, ops = _strides3(out)
         npo = 2 if state == _lib.PPQQ else 1
         if out.shape[1] != npo or carry.numel() < out.shape[0] * npo:
@@ -358,6 +401,9 @@ class FilterbankEngine(_Owned):
                      layout=_lib.RAW_GENERIC, scale=1.0):
         """Fused filterbank -> detection (ndim 4) -> fold into `fold`'s device profile; the bin plan of the
         npart*nkeep output samples must already have been given to `fold` (set_nbin/set_ndat/set_bins)."""
+        rows = self._unpacked_heaps(raw, layout, scale, npart)
+        if rows is not None:
+            inp, in_step, raw = rows[0], rows[1], None
         if npart:
             if raw is not None and layout != _lib.RAW_UWB16:
                 self._need("raw block", raw.numel(), self._raw_bytes(npart, layout))
@@ -437,6 +483,26 @@ def unpack_fpt(ctx: Context, raw, out, nchan, npol, ndim, scale=1.0, ndat=None):
     ocs, ops = _strides3(out)
     _check(ctx.handle, lib.dspsr_amd_unpack_fpt(ctx.handle, raw.data_ptr(), scale, nchan, npol, ndim, ndat, out.data_ptr(), ocs, ops),
            "dspsr_amd_unpack_fpt")
+    return out
+
+
+def unpack_heaps_fpt(ctx: Context, raw, out, nchan, npol, layout, scale=1.0, ndat=None):
+    """dsp::MeerKATUnpacker on the device: raw = device int8 block of whole heaps [heap][npol][nchan][256][2] (16-byte aligned),
+    layout = RAW_MEERKAT / RAW_MEERKAT_SWAP or raw_at(layout, first_sample); out = float32 device rows [nchan][npol][>= 2 * ndat]
+    (strided views allowed) that receive stream samples first_sample ... first_sample + ndat - 1.  ndat=None: all the block holds."""
+    if not _lib.is_heaps(layout):
+        raise DspsrAmdError("dspsr_amd.unpack_heaps_fpt: layout %d is not a heap layout" % layout)
+    first = layout >> 8
+    per = nchan * npol * _lib.HEAP_NSAMP * 2
+    ndat = (raw.numel() // per) * _lib.HEAP_NSAMP - first if ndat is None else ndat
+    need = -(-(first + ndat) // _lib.HEAP_NSAMP) * per if ndat > 0 else 0
+    if ndat < 0 or raw.numel() < need:
+        raise DspsrAmdError("dspsr_amd.unpack_heaps_fpt: block holds %d bytes, %d needed" % (raw.numel(), need))
+    if tuple(out.shape[:2]) != (nchan, npol) or out.shape[2] < 2 * ndat:
+        raise DspsrAmdError("dspsr_amd.unpack_heaps_fpt: out is %s, [%d][%d][>= %d] needed" % (tuple(out.shape), nchan, npol, 2 * ndat))
+    ocs, ops = _strides3(out)
+    _check(ctx.handle, lib.dspsr_amd_unpack_heaps_fpt(ctx.handle, raw.data_ptr(), layout, scale, nchan, npol, ndat, out.data_ptr(), ocs, ops),
+           "dspsr_amd_unpack_heaps_fpt")
     return out
 
 

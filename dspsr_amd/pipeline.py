@@ -85,6 +85,10 @@ class Config:
     zap_rfi: bool = False                  # -R: the narrow-band RFI filter (dsp::RFIFilter, LoadToFold1.C:248-266): a 0/1 mask from the
                                            # passband of the first second, multiplied into the dedispersion kernel.  The pipeline wants
                                            # its filter before the first block: LoadToFold.set_rfi_filter (dada.fold_file does it)
+    fuse_heaps: bool = True                # MeerKAT heaps (INSTRUMENT MKBF / MKBFRo): True = the one-pass convolution reads the 8-bit
+                                           # block itself where the front end has that loader (FilterbankEngine.takes_heaps); False = the
+                                           # engine unpacks into float rows first, as it does for every other geometry (A/B runs,
+                                           # the same numbers bit for bit)
     npol: int = 4                          # -d: the reference's config->npol.  This path detects the four products (4); the field
                                            # decides the branch of LoadToFold1.C:552-568 only: with 1 or 3 it wins over -4, which is
                                            # then ignored
@@ -985,6 +989,7 @@ def rfi_check(cfg: "Config", info: "InputInfo", subband=None):
         raise DspsrAmdError("%s is not built for sub-band sharded runs (subband=%d)" % (who, subband))
     if getattr(info, "nbit", 8) != 8:
         raise DspsrAmdError("%s reads 8-bit input (info.nbit=%d): 16-bit input is not built" % (who, info.nbit))
+    refuse_heaps(who, info, "the Bandpass operator's integrate_raw reads the generic and CASPSR byte orders")
 
 
 def calibrator_response(cfg: "Config", info: "InputInfo", subband=None):
@@ -1076,12 +1081,35 @@ def filterbank_output(info, r, nsub):
     return rate, info.start_seconds + r.impulse_pos / rate, float(n_fft) * float(r.ndat)
 
 
+def machine_layout(machine):
+    """The raw layout of the 8-bit blocks of INSTRUMENT `machine`."""
+    return _lib.HEAP_MACHINES.get(machine, _lib.RAW_CASPSR if machine == "CASPSR" else _lib.RAW_GENERIC)
+
+
+def refuse_heaps(who, info, instead):
+    """Plan-time refusal of a driver that has no reader for MeerKAT heaps."""
+    if info.machine in _lib.HEAP_MACHINES:
+        raise DspsrAmdError("%s: the heap order of INSTRUMENT %s (MeerKAT beamformer: 256-sample runs per polarisation and channel) is not "
+                            "built on this path; %s" % (who, info.machine, instead))
+
+
+def raw_block_bytes(layout, nsamp, nchan, npol, ndim, first_sample=0):
+    """Bytes of a block of `nsamp` samples in `layout` (heaps: from `first_sample` of the first heap on, whole heaps)."""
+    if _lib.is_heaps(layout):
+        return _lib.heap_block_bytes(first_sample, nsamp, nchan, npol)
+    if first_sample:
+        raise DspsrAmdError("dspsr_amd.pipeline: first_sample=%d given for a layout without heaps" % first_sample)
+    if layout == _lib.RAW_CASPSR:
+        return ((nsamp + 3) // 4) * 8          # whole 4-sample groups (4 B pol0 | 4 B pol1)
+    return nsamp * nchan * npol * ndim
+
+
 def _adopt_front(drv, fb):
     """`fb` (a FilterbankEngine, or one of the two wrappers above) becomes the front end of the driver: what every path reads of it."""
     drv.fb = fb
     drv.nkeep, drv.nsamp_step, drv.nsamp_overlap = fb.nkeep, fb.nsamp_step, fb.nsamp_overlap
     drv.scale8 = eight_bit_scale()
-    drv.layout = _lib.RAW_CASPSR if drv.info.machine == "CASPSR" else _lib.RAW_GENERIC
+    drv.layout = machine_layout(drv.info.machine)
 
 
 def _open_convolving_front(drv, r, nsub, in_nchan, kernel, **setup):
@@ -1355,7 +1383,7 @@ class LoadToFold:
         self.ctx = Context(device, stream)
         r, nsub, rows = self.response, cfg.nchan // info.nchan, cfg.parts_per_block
         fused = _lib.FUSED_NEVER if not cfg.fused_fold else _lib.FUSED_ALWAYS if cfg.force_fused else _lib.FUSED_AUTO
-        setup = dict(max_parts=cfg.max_parts, force_four_pass=0 if cfg.two_pass else 2)
+        setup = dict(max_parts=cfg.max_parts, force_four_pass=0 if cfg.two_pass else 2, fuse_heaps=cfg.fuse_heaps)
         if cfg.cyclic_nchan > 0:
             # `dspsr -cyclic N`: the convolving filterbank writes its complex rows, dsp::CyclicFold folds their lag products
             # (LoadToFold1.C:534-539,999-1044); Detection and Fold are not built.  At a sub-integration the lag data come to the
@@ -1606,12 +1634,11 @@ class LoadToFold:
             print(pad(name) + pad("%g" % t) + pad("0"), file=file)
 
     # bytes of one block of `npart` parts
-    def block_bytes(self, npart=None):
+    def block_bytes(self, npart=None, first_sample=0):
+        """first_sample: a block of heaps begins at that sample of its first heap (0 for every other layout)."""
         npart = npart or self.cfg.parts_per_block
         nsamp = npart * self.nsamp_step + self.nsamp_overlap
-        if self.layout == _lib.RAW_CASPSR:
-            return ((nsamp + 3) // 4) * 8          # whole 4-sample groups (4 B pol0 | 4 B pol1)
-        return nsamp * self.in_nchan * self.info.npol * self.info.ndim
+        return raw_block_bytes(self.layout, nsamp, self.in_nchan, self.info.npol, self.info.ndim, first_sample)
 
     def seek_block(self, k):
         """Time-slice replicas: the next block is block k of the stream (blocks of parts_per_block parts), not the one
@@ -1634,14 +1661,17 @@ class LoadToFold:
         day, sec = self.info.mjd_day, self.info.mjd_sec + t_seconds
         return polyco.phase_frac(day, sec) - reference_phase, 1.0 / polyco.frequency(day, sec)
 
-    def process_block(self, raw, npart=None, events=None):
+    def process_block(self, raw, npart=None, events=None, first_sample=0):
         """raw: device int8 tensor holding npart*nsamp_step + nsamp_overlap samples (the InputBuffering
-        tail of the previous block already prepended, Filterbank.C:443-444)."""
+        tail of the previous block already prepended, Filterbank.C:443-444).  A block of MeerKAT heaps holds the whole heaps
+        around those samples; first_sample: where in its first heap the block's first sample lies."""
         cfg = self.cfg
         npart = npart or cfg.parts_per_block
-        if raw.numel() < self.block_bytes(npart):
+        if raw.numel() < self.block_bytes(npart, first_sample):
             raise DspsrAmdError("dspsr_amd.LoadToFold.process_block: block holds %d bytes, %d needed"
-                                % (raw.numel(), self.block_bytes(npart)))
+                                % (raw.numel(), self.block_bytes(npart, first_sample)))
+        if _lib.is_heaps(self.layout):
+            self.layout = _lib.raw_at(self.layout & 0xff, first_sample)      # the layout word of THIS block, for every path below
         if cfg.zap_rfi and self.rfi_filter is None:
             raise DspsrAmdError("dspsr_amd.LoadToFold.process_block: zap_rfi (-R) is set and no filter has been given: "
                                 "call set_rfi_filter before the first block")
@@ -1904,7 +1934,8 @@ class LoadToFold:
         """Host hand-over (the role of dsp::TransferCUDA / TransferBitSeriesCUDA, Signal/General/TransferCUDA.C:24-85):
         `blocks` yields one block each -- a pinned host int8 tensor (copied from where it lies; the caller must not touch
         it again before the call returns), or any other host int8 tensor / numpy array (staged through two pinned buffers
-        owned by this call), optionally as a pair (block, npart) for a ragged last block.  Block i+1 is copied to the
+        owned by this call), optionally as a pair (block, npart) for a ragged last block or, for a file of heaps, a triple
+        (block, npart, first_sample).  Block i+1 is copied to the
         device on a second stream while block i is processed (two device buffers, events both ways).  With the data
         coming over PCIe Gen5 x16 the link, not the GPU, sets the rate.  Returns the number of
         blocks processed."""
@@ -1920,8 +1951,8 @@ class LoadToFold:
             if item is None:
                 return None, None
             if isinstance(item, tuple):
-                return item[0], item[1]
-            return item, npart
+                return item[0], item[1:]                     # (npart,) or, for heaps, (npart, first_sample)
+            return item, (npart,)
 
         def upload(k, host):
             if not (torch.is_tensor(host) and host.is_pinned()):
@@ -1956,7 +1987,7 @@ class LoadToFold:
             if nxt is not None:
                 sizes[k ^ 1], parts[k ^ 1] = upload(k ^ 1, nxt), nxt_parts
             main.wait_event(ready[k])
-            self.process_block(bufs[k][:sizes[k]], parts[k])
+            self.process_block(bufs[k][:sizes[k]], parts[k][0], None, *parts[k][1:])
             done[k].record(main)
             n += 1
             if nxt is None:
@@ -2111,6 +2142,7 @@ class LoadToFil:
 
     def __init__(self, cfg: SearchConfig, info: InputInfo, device: int = 0, stream: int | None = None):
         self.cfg, self.info = cfg, info
+        refuse_heaps("dspsr_amd.LoadToFil", info, "channelised complex voltages take -F N:D (dspsr_amd.LoadToFilCoherent)")
         if info.npol != 2 or info.ndim != 1 or info.nchan != 1:
             raise DspsrAmdError("dspsr_amd.LoadToFil: 8-bit real dual-polarisation single-channel input only")
         if cfg.parts_per_block % cfg.tscrunch:
@@ -2272,19 +2304,21 @@ class LoadToFilCoherent:
             self.rescale = Rescale(self.ctx, self.nchan_out, cfg.npol, self.rescale_interval, cfg.rescale_constant)
         self.packed = _device_empty(self.ctx, nmax * self.bytes_per_sample, "uint8")
 
-    def block_bytes(self, npart=None):
+    def block_bytes(self, npart=None, first_sample=0):
         npart = npart or self.cfg.parts_per_block
         nsamp = npart * self.nsamp_step + self.nsamp_overlap
-        if self.layout == _lib.RAW_CASPSR:
-            return ((nsamp + 3) // 4) * 8
-        return nsamp * self.info.nchan * self.info.npol * self.info.ndim
+        return raw_block_bytes(self.layout, nsamp, self.info.nchan, self.info.npol, self.info.ndim, first_sample)
 
-    def detect_scrunch(self, raw, npart=None):
-        """Filterbank -> Detection -> [FScrunch] -> TScrunch of one block: the scrunched rows [nchan_out][npol][nout] (a view)."""
+    def detect_scrunch(self, raw, npart=None, first_sample=0):
+        """Filterbank -> Detection -> [FScrunch] -> TScrunch of one block: the scrunched rows [nchan_out][npol][nout] (a view).
+        first_sample: a block of MeerKAT heaps begins at that sample of its first heap (LoadToFold.process_block)."""
         cfg, ts = self.cfg, self.ts
         npart = npart or cfg.parts_per_block
-        if raw.numel() < self.block_bytes(npart):
-            raise DspsrAmdError("dspsr_amd.LoadToFilCoherent.process_block: block holds %d bytes, %d needed" % (raw.numel(), self.block_bytes(npart)))
+        need = self.block_bytes(npart, first_sample)
+        if raw.numel() < need:
+            raise DspsrAmdError("dspsr_amd.LoadToFilCoherent.process_block: block holds %d bytes, %d needed" % (raw.numel(), need))
+        if _lib.is_heaps(self.layout):
+            self.layout = _lib.raw_at(self.layout & 0xff, first_sample)
         if self.fused:
             nout, self.carry_count = self.fb.perform_search(self.scrunched, self.carry, self.carry_count, npart, ts, self.state, raw=raw,
                                                             layout=self.layout, scale=self.scale8)
@@ -2297,8 +2331,8 @@ class LoadToFilCoherent:
             self.fb.perform_search(det, self.det_carry, 0, npart, 1, self.state, raw=raw, layout=self.layout, scale=self.scale8)
         return _delay_scrunch(self, det, nd)
 
-    def process_block(self, raw, npart=None):
-        return _digitize_fpt(self, self.detect_scrunch(raw, npart))
+    def process_block(self, raw, npart=None, first_sample=0):
+        return _digitize_fpt(self, self.detect_scrunch(raw, npart, first_sample))
 
     def header_values(self):
         return _sigproc_header_values(self, self.nchan_out, 1.0 / self.out_rate, self.out_start, self.cfg.npol)
@@ -2363,6 +2397,8 @@ class LoadToFilDirect:
             raise DspsrAmdError("dspsr_amd.LoadToFilDirect: NBIT=%d; this path reads 8-bit samples" % info.nbit)
         if info.machine == "CASPSR":
             raise DspsrAmdError("dspsr_amd.LoadToFilDirect: the CASPSR byte order is not built on this path (generic DADA order only)")
+        refuse_heaps("dspsr_amd.LoadToFilDirect", info, "dspsr_amd.unpack_heaps_fpt gives the float rows, and -F N:D "
+                     "(dspsr_amd.LoadToFilCoherent) reads the heaps")
         if cfg.npol not in (1, 2, 4):
             raise DspsrAmdError("dspsr_amd.LoadToFilDirect: npol=%d (Intensity 1 / PPQQ 2 / Coherence 4 are built; NthPower 3 is not)" % cfg.npol)
         if info.npol not in (1, 2):

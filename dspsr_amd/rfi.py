@@ -117,6 +117,10 @@ class RfiFilter:
     def integrate_raw(self, raw_dev, ndat):
         """Adds the 8-bit block (device tensor in the stream's layout, `ndat` samples from its first) until integration_length >=
         interval; excess input is not used.  Returns the samples used, a whole number of 8192-sample blocks."""
+        if self.info.machine in _lib.HEAP_MACHINES:
+            raise DspsrAmdError("dspsr_amd.rfi.RfiFilter.integrate_raw: the heaps of INSTRUMENT %s are not read here (the Bandpass operator "
+                                "takes the generic and CASPSR byte orders): unpack with dspsr_amd.unpack_heaps_fpt and call integrate"
+                                % self.info.machine)
         used = self._take(ndat)
         if used:
             self.bandpass.accumulate_raw(raw_dev, used, self.layout, self.scale8)

@@ -176,6 +176,19 @@ int dspsr_amd_filterbank_perform(dspsr_amd_filterbank* fb, const float* in_dev, 
 #define DSPSR_AMD_RAW_UWB16 2    /* 16-bit offset-binary complex, 2048-sample blocks per polarisation, single channel;
                                     value = float(int16(x ^ 0x8000)) * scale   uwb/UWBUnpackerCUDA.cu:24-75,
                                     uwb/UWBUnpacker.C:196-207 (the reference applies no scale: pass 1.0) */
+/* MeerKAT beamformer heaps (INSTRUMENT MKBF / MKBFRo, kat/MeerKATUnpacker.C:137-230): complex 8-bit, npol 1 | 2, any nchan.  A
+ * block is whole heaps of 256 samples; heap h holds, for pol in order and then chan in order, the 256 consecutive (int8 re, int8 im)
+ * pairs of that (chan, pol) -- 512 contiguous bytes per run:
+ *     byte of stored sample s of heap h = (((h * npol + pol) * nchan + chan) * 256 + s) * 2 + d
+ * Stream sample t of a row is stored at s = t & 255 of heap t >> 8; DSPSR_AMD_RAW_MEERKAT_SWAP (MKBFRo, sample_swap = 2) exchanges
+ * odd and even samples: s = (t & 255) ^ 1.  Overlap-save parts are nsamp_step samples apart and blocks overlap, so a block does
+ * not start on a heap boundary in general: raw_dev points at the first byte of the HEAP that holds the call's first sample, and the
+ * layout word carries first_sample, the index inside that heap of stream sample 0 of the call (stateless; heap layouts only: a
+ * first_sample on any other layout, or one above 255, is DSPSR_AMD_EINVAL).  The block holds ceil((first_sample + nsamp) / 256)
+ * whole heaps.  raw_dev must be 16-byte aligned (every run of a heap then is): anything else is DSPSR_AMD_EINVAL before a launch. */
+#define DSPSR_AMD_RAW_MEERKAT 3
+#define DSPSR_AMD_RAW_MEERKAT_SWAP 4
+#define DSPSR_AMD_RAW_AT(layout, first_sample) ((layout) | ((first_sample) << 8))
 /* out_dev, its strides and out_step: as dspsr_amd_filterbank_perform, the same checks */
 int dspsr_amd_filterbank_perform_raw(dspsr_amd_filterbank* fb, const int8_t* raw_dev, int raw_layout, float scale,
                                      float* out_dev, uint64_t out_chan_stride, uint64_t out_pol_stride,
@@ -246,6 +259,12 @@ int dspsr_amd_filterbank_fold_is_fused(const dspsr_amd_filterbank* fb);
  * over the spectrum (k_sub_combine); freq_res = R * 2^k a radix-R pass over the pseudo-channels' time series as well
  * (k_time_combine, with Detection and Fold as launches of their own: fold_is_fused() == 0). */
 int dspsr_amd_filterbank_npass(const dspsr_amd_filterbank* fb, int raw_input);
+/* 1: perform_raw / _detect / _fold / _search of this object read a block of heaps (DSPSR_AMD_RAW_MEERKAT / _SWAP) inside their one
+ * tile pass (csrc/fb_conv1.hip, the 8-bit load decoded in the tile's first stage) -- the dsp::Convolution shapes that run in one
+ * pass on float32 rows: nchan_subband = 1, complex input, two polarisations, 64 <= freq_res <= 8192, force_four_pass = 0.  Bit for
+ * bit dspsr_amd_unpack_heaps_fpt followed by the float32 entry points.  0: every other object; it refuses heap layouts with
+ * DSPSR_AMD_EINVAL naming the limit -- unpack first and hand the float rows over. */
+int dspsr_amd_filterbank_takes_heaps(const dspsr_amd_filterbank* fb);
 /* 1: the object's three passes run on the pre-split spectrum (dspsr_amd_filterbank_config::split_in_inverse), else 0 */
 int dspsr_amd_filterbank_presplit(const dspsr_amd_filterbank* fb);
 int dspsr_amd_filterbank_perform_fold(dspsr_amd_filterbank* fb, const float* in_f32_dev, uint64_t in_chan_stride,
@@ -314,6 +333,14 @@ int dspsr_amd_detect_square_law(dspsr_amd_ctx* ctx, int intensity, const float* 
  * DSPSR_AMD_EINVAL, nothing launched); nothing outside the ndat * ndim floats of a row is written.  ndat = 0: nothing to do. */
 int dspsr_amd_unpack_fpt(dspsr_amd_ctx* ctx, const int8_t* raw_dev, float scale, uint32_t nchan, uint32_t npol, uint32_t ndim,
                          uint64_t ndat, float* out_dev, uint64_t out_chan_stride, uint64_t out_pol_stride);
+/* dspsr_amd_unpack_heaps_fpt replaces dsp::MeerKATUnpacker on the device (CUDA::MeerKATUnpackerEngine::unpack,
+ * kat/MeerKATUnpackerCUDA.cu): a block of heaps (DSPSR_AMD_RAW_MEERKAT / _SWAP above, raw_layout = DSPSR_AMD_RAW_AT(layout,
+ * first_sample)) -> float FPT rows [nchan][npol] of ndat complex samples, stream samples first_sample ... first_sample + ndat - 1
+ * of the block.  npol 1 | 2, nchan >= 1; unlike the reference's kernel, ndat need not be a multiple of 256.  raw_dev 16-byte
+ * aligned; rows at any float-aligned address, out_pol_stride >= 2 * ndat and out_chan_stride >= (npol-1)*out_pol_stride + 2 * ndat
+ * (else DSPSR_AMD_EINVAL, nothing launched); nothing outside the 2 * ndat floats of a row is written.  ndat = 0: nothing to do. */
+int dspsr_amd_unpack_heaps_fpt(dspsr_amd_ctx* ctx, const int8_t* raw_dev, int raw_layout, float scale, uint32_t nchan, uint32_t npol,
+                               uint64_t ndat, float* out_dev, uint64_t out_chan_stride, uint64_t out_pol_stride);
 /* dspsr_amd_detect_raw replaces the unpacker, dsp::Detection (DetectionCUDA.cu:180-213 sqld_fpt; Detection.C:218-320 square_law,
  * LoadToFil.C:267-271 Coherence with ndim 1) and dsp::TScrunch (TScrunch.C:148-178) by ONE pass over the block: complex input
  * (ndim 2), npol 1 | 2, any nchan >= 1; the float voltages are never written.  Bit for bit dspsr_amd_unpack_fpt ->

@@ -173,6 +173,25 @@ SYMBOLS = {
     "dspsr_amd_bandpass_zero": (_i, [_vp]),
     "dspsr_amd_bandpass_pass_dev": (_vp, [_vp]),
     "dspsr_amd_bandpass_synch": (_i, [_vp, _vp, C.POINTER(_d)]),
+    "dspsr_amd_sk_limits": (_i, [_u32, _u32, C.POINTER(_f), C.POINTER(_f)]),
+    "dspsr_amd_sk_create": (_i, [_vp, _pp]),
+    "dspsr_amd_sk_destroy": (None, [_vp]),
+    "dspsr_amd_sk_set_shape": (_i, [_vp, _u32, _u32, _u32]),
+    "dspsr_amd_sk_set_options": (_i, [_vp, _u32, _u32, _u32, _i, _i, _i]),
+    "dspsr_amd_sk_compute": (_i, [_vp, _vp, _u64, _u64, _u64]),
+    "dspsr_amd_sk_reset_mask": (_i, [_vp]),
+    "dspsr_amd_sk_detect_tscr": (_i, [_vp, _f, _f]),
+    "dspsr_amd_sk_detect_skfb": (_i, [_vp, _f, _f]),
+    "dspsr_amd_sk_detect_fscr": (_i, [_vp]),
+    "dspsr_amd_sk_count_zapped": (_i, [_vp]),
+    "dspsr_amd_sk_mask": (_i, [_vp, _vp, _u64, _u64, _vp, _u64, _u64]),
+    "dspsr_amd_sk_transform": (_i, [_vp, _vp, _u64, _u64, _vp, _u64, _u64, _u64]),
+    "dspsr_amd_sk_npart": (_u64, [_vp]),
+    "dspsr_amd_sk_estimates_dev": (_vp, [_vp]),
+    "dspsr_amd_sk_estimates_tscr_dev": (_vp, [_vp]),
+    "dspsr_amd_sk_zapmask_dev": (_vp, [_vp]),
+    "dspsr_amd_sk_get_statistics": (_i, [_vp, _vp, _vp, _vp, _vp]),
+    "dspsr_amd_sk_reset_count": (_i, [_vp]),
     "dspsr_amd_comm_set_library": (_i, [C.c_char_p]),
     "dspsr_amd_comm_unique_id": (_i, [_vp]),
     "dspsr_amd_comm_create": (_i, [_vp, _i, _i, _vp, _pp]),

@@ -562,3 +562,222 @@ extern "C" int dspsr_amd_response_multiply(float* kernel, const float* phasors, 
   }
   return DSPSR_AMD_OK;
 }
+
+// ---- spectral-kurtosis limits: dsp::SKLimits::calc_limits (Signal/Statistics/SKLimits.C:29-100) ----------------------------
+// The SK estimator of M samples follows a Pearson type IV distribution (PearsonIV.C:28-83: moments, r, m, v, a, lamda and the
+// log of its normalisation); the limits are where its cumulative and complementary cumulative functions equal the one-sided tail
+// of a Gaussian at std_devs sigma, found by Newton's iteration on their logarithms.  Everything that decides convergence is kept:
+// the integrals are Romberg's with a FLOAT precision of 1e-12 compared against a double, 18 refinements and an extrapolation over
+// 5 points that starts one refinement late (Romberg.h:27-58), open (three-fold midpoint) after the change of variable 1/x for the
+// tails and closed (trapezoid) between -1 / +1 and x; Neville's tableau runs n-2 columns (Neville.h:43); Newton is clamped to
+// [1e-4, 10], stops at dx^2 <= (x * 1e-12)^2 and gives up after 100 steps (NewtonRaphson.h:36-54).  An integral or an iteration
+// that gives up makes the reference fall back to the starting guess 1 -+ std_devs * sqrt(4 / M) (SKLimits.C:75-94).
+namespace {
+
+struct sk_failed {};                                        // the reference's Error thrown by Romberg or NewtonRaphson
+
+struct pearson_iv {
+  double m, v, a, lamda, logk;
+
+  explicit pearson_iv(const unsigned sk_m)                  // PearsonIV::prepare
+  {
+    const double M = (double)sk_m;
+    const double mu1 = 1;
+    const double mu2 = (4 * M * M) / ((M - 1) * (M + 2) * (M + 3));
+    double beta1 = (4 * (M + 2) * (M + 3) * (5 * M - 7) * (5 * M - 7));
+    beta1 /= ((M - 1) * (M + 4) * (M + 4) * (M + 5) * (M + 5));
+    double beta2 = 3 * (M + 2) * (M + 3) * (M * M * M + 98 * M * M - 185 * M + 78);
+    beta2 /= ((M - 1) * (M + 4) * (M + 5) * (M + 6) * (M + 7));
+    const double r = (6 * (beta2 - beta1 - 1)) / (2 * beta2 - 3 * beta1 - 6);
+    m = (r + 2) / 2;
+    v = -1 * (r * (r - 2) * sqrt(beta1));
+    v /= sqrt(16 * (r - 1) - beta1 * (r - 2) * (r - 2));
+    a = 0.25 * sqrt(mu2 * ((16 * (r - 1)) - (beta1 * (r - 2) * (r - 2))));
+    lamda = mu1 - 0.25 * (r - 2) * sqrt(mu2) * sqrt(beta1);
+    logk = log_normal();
+  }
+
+  double log_normal() const                                 // PearsonIV.C:117-139
+  {
+    double x = m;
+    const double y = 0.5 * v;
+    const double y2 = y * y;
+    const double xmin = (2 * y2 > 10.0) ? 2 * y2 : 10.0;
+    double logr = 0, s = 1, p = 1, f = 0;
+    while (x < xmin) {
+      const double t = y / x++;
+      logr += log(1 + t * t);
+    }
+    while (p > s * 2.2204460492503131e-16) {                // DBL_EPSILON
+      p *= y2 + f * f;
+      p /= x++ * ++f;
+      s += p;
+    }
+    return log(0.5 * M_2_SQRTPI / a) - (logr + log(s)) + lgamma(m) - lgamma(m - 0.5);
+  }
+
+  double density(const double x) const                      // PearsonIV::operator()
+  {
+    const double a1 = (x - lamda) / a;
+    const double a2 = 1 + a1 * a1;
+    const double a3 = v * atan(a1);
+    return exp(logk - 1 * m * log(a2) - a3);
+  }
+};
+
+// the integrands of PearsonIV::cf / ccf: the density, OneOver(density) and Minus(OneOver(density)) (Romberg.h:64-118)
+enum sk_integrand { SK_PLAIN, SK_ONE_OVER, SK_MINUS_ONE_OVER };
+static double sk_eval(const pearson_iv& p, const sk_integrand kind, const double arg)
+{
+  if (kind == SK_PLAIN) return p.density(arg);
+  if (kind == SK_ONE_OVER) return -p.density(1.0 / arg) / (arg * arg);
+  const double t = -arg;
+  return -(-p.density(1.0 / t) / (t * t));
+}
+
+static void sk_neville(const double* xa, const double* ya, const unsigned n, const double x, double& y, double& dy)
+{
+  unsigned ns = 0;
+  double c[8], d[8];
+  double dif = fabs(x - xa[0]);
+  for (unsigned i = 0; i < n; i++) {
+    const double dift = fabs(x - xa[i]);
+    if (dift < dif) {
+      ns = i;
+      dif = dift;
+    }
+    c[i] = ya[i];
+    d[i] = ya[i];
+  }
+  y = ya[ns];
+  ns--;
+  dy = 0;
+  for (unsigned m = 1; m < n - 1; m++) {                    // (n-2 columns, as the reference)
+    for (unsigned i = 0; i < n - m; i++) {
+      const double ho = xa[i] - x;
+      const double hp = xa[i + m] - x;
+      const double w = c[i + 1] - d[i];
+      double den = ho - hp;
+      den = w / den;
+      d[i] = hp * den;
+      c[i] = ho * den;
+    }
+    if (2 * ns >= (n - m)) {
+      dy = d[ns];
+      ns--;
+    } else
+      dy = c[ns + 1];
+    y += dy;
+  }
+}
+
+// Romberg<Trapezoid> (open == false) or Romberg<MidPoint> (open == true) of the integrand from x1 to x2
+static double sk_romberg(const pearson_iv& p, const sk_integrand kind, const bool open, const double x1, const double x2)
+{
+  const unsigned extrapolate = 5, iterations = 18;
+  const float precision = 1.0e-12;                          // a float, compared against a double below
+  const double order_squared = open ? 9.0 : 4.0;
+  double h[iterations + 1], s[iterations];
+  double rule = 0;                                          // the refinement rule's running estimate (Trapezoid::s, MidPoint::s)
+  h[0] = 1.0;
+  double ss = 0, dss = 0;
+  for (unsigned j = 0; j < iterations; j++) {
+    if (j == 0) {
+      rule = open ? (x2 - x1) * sk_eval(p, kind, 0.5 * (x1 + x2)) : 0.5 * (x2 - x1) * (sk_eval(p, kind, x1) + sk_eval(p, kind, x2));
+    } else {
+      unsigned it = 1;
+      for (unsigned k = 1; k < j; k++) it *= open ? 3 : 2;
+      const double tnm = it;
+      double sum = 0.0;
+      if (open) {                                           // MidPoint.h:34-47
+        const double del = (x2 - x1) / (3.0 * tnm);
+        const double ddel = del + del;
+        double x = x1 + 0.5 * del;
+        for (unsigned k = 0; k < it; k++) {
+          sum += sk_eval(p, kind, x);
+          x += ddel;
+          sum += sk_eval(p, kind, x);
+          x += del;
+        }
+        rule = (rule + (x2 - x1) * sum / tnm) / 3.0;
+      } else {                                              // Trapezoid.h:34-44
+        const double del = (x2 - x1) / tnm;
+        double x = x1 + 0.5 * del;
+        for (unsigned k = 0; k < it; k++) {
+          sum += sk_eval(p, kind, x);
+          x += del;
+        }
+        rule = 0.5 * (rule + (x2 - x1) * sum / tnm);
+      }
+    }
+    s[j] = rule;
+    if (j >= extrapolate) {
+      sk_neville(h + j - extrapolate, s + j - extrapolate, extrapolate, 0.0, ss, dss);
+      if (fabs(dss) <= precision) return ss;
+    }
+    h[j + 1] = h[j] / order_squared;
+  }
+  throw sk_failed();
+}
+
+static double sk_cf(const pearson_iv& p, const double x)    // PearsonIV::cf
+{
+  if (x < -1) return sk_romberg(p, SK_MINUS_ONE_OVER, true, 0., -1 / x);
+  return sk_romberg(p, SK_MINUS_ONE_OVER, true, 0., 1.) + sk_romberg(p, SK_PLAIN, false, -1., x);
+}
+
+static double sk_ccf(const pearson_iv& p, const double x)   // PearsonIV::ccf
+{
+  if (x > 1) return sk_romberg(p, SK_ONE_OVER, true, 1 / x, 0.);
+  return sk_romberg(p, SK_ONE_OVER, true, 1., 0.) + sk_romberg(p, SK_PLAIN, false, x, 1.);
+}
+
+// NewtonRaphson::operator() on log cf (upper == false) or log ccf (upper == true) with limits [1e-4, 10]
+static double sk_newton(const pearson_iv& p, const bool upper, const double y, double guess_x)
+{
+  const double precision = 1e-12, lower_limit = 1e-4, upper_limit = 10;
+  for (unsigned i = 0; i < 100; i++) {
+    const double c = upper ? sk_ccf(p, guess_x) : sk_cf(p, guess_x);     // (log_cf and dlog_cf integrate the same thing twice)
+    const double f = log(c);
+    const double df = upper ? -1 * p.density(guess_x) / c : p.density(guess_x) / c;
+    const double dx = (f - y) / df;
+    guess_x -= dx;
+    if (guess_x < lower_limit) guess_x = lower_limit;
+    if (guess_x > upper_limit) guess_x = upper_limit;
+    if (dx * dx <= (guess_x * precision) * (guess_x * precision)) return guess_x;
+  }
+  throw sk_failed();
+}
+
+}  // namespace
+
+extern "C" int dspsr_amd_sk_limits(uint32_t M, uint32_t std_devs, float* lower, float* upper)
+{
+  if (!lower || !upper) return DSPSR_AMD_EINVAL;
+  *lower = *upper = 0;
+  if (M < 32 || std_devs == 0) return DSPSR_AMD_EINVAL;     // below M = 24 the Pearson IV parameters are not finite
+  const double percent_std_devs = erf((float)std_devs / sqrt(2));
+  const double target = (1 - percent_std_devs) / 2.0;
+  const double one_std_dev = sqrt(4.0 / (double)M);
+  const double factor = one_std_dev * std_devs;
+  double lo, hi;
+  if (M >= 32768) {                                         // SKLimits.C:46-51: the Gaussian limit
+    lo = 1.0f - factor;
+    hi = 1.0f + factor;
+  } else {
+    const pearson_iv p(M);
+    lo = 1 - factor;
+    try {
+      lo = sk_newton(p, false, log(target), lo);
+    } catch (const sk_failed&) {
+    }
+    hi = 1 + factor;
+    try {
+      hi = sk_newton(p, true, log(target), hi);
+    } catch (const sk_failed&) {
+    }
+  }
+  *lower = (float)lo;                                       // SpectralKurtosis.C:390-391
+  *upper = (float)hi;
+  return DSPSR_AMD_OK;
+}

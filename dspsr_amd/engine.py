@@ -1001,6 +1001,117 @@ class BandpassEngine(_Owned):
         return out
 
 
+def sk_limits(M: int, std_devs: int = 3):
+    """dsp::SKLimits(M, std_devs) rounded to float32 (lower, upper): csrc/host_prep.cpp dspsr_amd_sk_limits, no device."""
+    lo, hi = C.c_float(), C.c_float()
+    if lib.dspsr_amd_sk_limits(int(M), int(std_devs), C.byref(lo), C.byref(hi)) != _lib.OK:
+        raise DspsrAmdError("dspsr_amd_sk_limits: M=%d < 32 or std_devs=%d == 0 (dsp::SKLimits::calc_limits invalid inputs)" % (M, std_devs))
+    return np.float32(lo.value), np.float32(hi.value)
+
+
+class SpectralKurtosisEngine(_Owned):
+    """dsp::SpectralKurtosis (Signal/General/SpectralKurtosis.C, the CPU branch) on the device: compute / detect / mask of complex
+    rows [nchan][npol][2 * ndat] (FPT, as the filterbank writes them).  The detection steps are those of
+    SpectralKurtosis::Engine; transform runs them in the reference's order with the limits of sk_limits."""
+
+    _abi = "dspsr_amd_sk"
+    ZAP_ALL, ZAP_SKFB, ZAP_FSCR, ZAP_TSCR = 0, 1, 2, 3
+
+    def __init__(self, ctx: Context):
+        super().__init__(ctx)
+        self._create()
+        self.shape = None
+
+    def _call(self, name, *args):
+        _check(self.ctx.handle, getattr(lib, name)(self.handle, *args), name)
+
+    def set_shape(self, nchan, npol, M):
+        self._call("dspsr_amd_sk_set_shape", nchan, npol, M)
+        self.shape = (nchan, npol, M)
+
+    def set_options(self, std_devs=3, chan_start=0, chan_end=0, no_fscr=False, no_tscr=False, no_ft=False):
+        self._call("dspsr_amd_sk_set_options", std_devs, chan_start, chan_end, int(no_fscr), int(no_tscr), int(no_ft))
+
+    def compute(self, inp, ndat):
+        cs, ps = _strides3(inp)
+        self._call("dspsr_amd_sk_compute", inp.data_ptr(), cs, ps, ndat)
+
+    def reset_mask(self):
+        self._call("dspsr_amd_sk_reset_mask")
+
+    def detect_tscr(self, lower, upper):
+        self._call("dspsr_amd_sk_detect_tscr", lower, upper)
+
+    def detect_skfb(self, lower, upper):
+        self._call("dspsr_amd_sk_detect_skfb", lower, upper)
+
+    def detect_fscr(self):
+        self._call("dspsr_amd_sk_detect_fscr")
+
+    def count_zapped(self):
+        self._call("dspsr_amd_sk_count_zapped")
+
+    def mask(self, inp, out):
+        """out may be inp itself: zeros are then written over the zapped parts only."""
+        ics, ips = _strides3(inp)
+        ocs, ops = _strides3(out)
+        self._call("dspsr_amd_sk_mask", inp.data_ptr(), ics, ips, out.data_ptr(), ocs, ops)
+
+    def transform(self, inp, out, ndat):
+        """compute, detect and mask of ndat samples; returns the samples the output holds, ndat // M * M (it carries zeroed data)."""
+        ics, ips = _strides3(inp)
+        ocs, ops = _strides3(out)
+        self._call("dspsr_amd_sk_transform", inp.data_ptr(), ics, ips, out.data_ptr(), ocs, ops, ndat)
+        return self.npart * self.shape[2]
+
+    def reset_count(self):
+        self._call("dspsr_amd_sk_reset_count")
+
+    @property
+    def npart(self) -> int:
+        return int(lib.dspsr_amd_sk_npart(self.handle))
+
+    def get_estimates_ptr(self):
+        return lib.dspsr_amd_sk_estimates_dev(self.handle)
+
+    def get_estimates_tscr_ptr(self):
+        return lib.dspsr_amd_sk_estimates_tscr_dev(self.handle)
+
+    def get_zapmask_ptr(self):
+        return lib.dspsr_amd_sk_zapmask_dev(self.handle)
+
+    def _fetch(self, ptr, shape, dtype):
+        out = np.empty(shape, dtype)
+        if out.size:
+            _check(self.ctx.handle, lib.dspsr_amd_copy(self.ctx.handle, out.ctypes.data_as(C.c_void_p), ptr, out.nbytes, _lib.D2H), "dspsr_amd_copy")
+        return out
+
+    def estimates(self) -> np.ndarray:
+        """The estimates of the last compute on the host, float32 [npart][nchan][npol] (blocks)."""
+        nchan, npol, _ = self.shape
+        return self._fetch(self.get_estimates_ptr(), (self.npart, nchan, npol), np.float32)
+
+    def estimates_tscr(self) -> np.ndarray:
+        nchan, npol, _ = self.shape
+        return self._fetch(self.get_estimates_tscr_ptr(), (nchan, npol), np.float32)
+
+    def zapmask(self) -> np.ndarray:
+        """The mask of the last detection on the host, uint8 [npart][nchan] (blocks)."""
+        return self._fetch(self.get_zapmask_ptr(), (self.npart, self.shape[0]), np.uint8)
+
+    def get_statistics(self) -> dict:
+        """The counters of SpectralKurtosis (blocks): zap_counts[all, skfb, fscr, tscr], npart_total, unfiltered_hits,
+        filtered_hits[nchan], filtered_sum / unfiltered_sum[nchan][npol]."""
+        if self.shape is None:
+            raise DspsrAmdError("dspsr_amd_sk_get_statistics: no shape")
+        nchan, npol, _ = self.shape
+        counts, hits = np.zeros(6, np.uint64), np.zeros(nchan, np.uint64)
+        fsum, usum = np.zeros((nchan, npol), np.float32), np.zeros((nchan, npol), np.float32)
+        self._call("dspsr_amd_sk_get_statistics", *(a.ctypes.data_as(C.c_void_p) for a in (counts, hits, fsum, usum)))
+        return {"zap_counts": counts[:4].copy(), "npart_total": int(counts[4]), "unfiltered_hits": int(counts[5]),
+                "filtered_hits": hits, "filtered_sum": fsum, "unfiltered_sum": usum}
+
+
 class Communicator(_Owned):
     """The sub-integration exchange over RCCL / xGMI behind the C-ABI (dspsr_amd_comm_*, csrc/comm.hip): the same entry
     points DSPSR's C++ host calls.  One per pipeline context.  `unique_id` = the 128 bytes of `Communicator.unique_id()`

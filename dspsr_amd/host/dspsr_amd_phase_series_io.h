@@ -24,7 +24,8 @@ namespace HIP
   {
     std::map<std::string, std::string> header;   // "KEY value" lines of the 4096-byte ASCII header
     unsigned nchan, npol, ndim, nbin;
-    std::vector<uint32_t> hits;                  // [nbin]
+    unsigned hits_nchan;                         // 0: hits[nbin]; key HITS_NCHAN (a -skz run): hits[hits_nchan][nbin]
+    std::vector<uint32_t> hits;                  // [nbin], or [hits_nchan][nbin]
     std::vector<float> sums;                     // [nchan][npol][nbin][ndim], un-normalised (Archiver divides by scale*hits)
 
     double number (const std::string& key) const
@@ -61,9 +62,10 @@ namespace HIP
     { fclose (fp); throw std::runtime_error (std::string (filename) + " is not a DSPSR_AMD_PHASESERIES file"); }
     f.nchan = unsigned (f.number ("NCHAN")); f.npol = unsigned (f.number ("NPOL"));
     f.ndim = unsigned (f.number ("NDIM")); f.nbin = unsigned (f.number ("NBIN"));
-    f.hits.resize (f.nbin);
+    f.hits_nchan = f.text ("HITS_NCHAN").empty () ? 0 : unsigned (f.number ("HITS_NCHAN"));
+    f.hits.resize (size_t (f.nbin) * (f.hits_nchan ? f.hits_nchan : 1));
     f.sums.resize (size_t (f.nchan) * f.npol * f.nbin * f.ndim);
-    const bool ok = fread (&f.hits[0], sizeof (uint32_t), f.nbin, fp) == f.nbin &&
+    const bool ok = fread (&f.hits[0], sizeof (uint32_t), f.hits.size (), fp) == f.hits.size () &&
                     fread (&f.sums[0], sizeof (float), f.sums.size (), fp) == f.sums.size ();
     fclose (fp);
     if (!ok) throw std::runtime_error (std::string (filename) + " is truncated");
@@ -89,7 +91,9 @@ namespace HIP
     out->set_scale (f.number ("SCALE"));             // Archiver.C:842: amps = sum / (scale * hits)
     const double sec = f.number ("MJD_SEC") + f.number ("OBS_OFFSET_SECONDS");
     out->set_start_time (MJD (int (f.number ("MJD_DAY")), int (sec), sec - int (sec)));
-    out->resize (f.nbin);                            // PhaseSeries.C:83-110: the profile rows and hits[nbin]
+    // `-skz`: one hits row per channel (Fold::Engine::zeroed_samples, PhaseSeries.h:115-118); set before resize sizes hits[]
+    if (f.hits_nchan) out->set_hits_nchan (f.hits_nchan);
+    out->resize (f.nbin);                            // PhaseSeries.C:83-110: the profile rows and hits[hits_nchan * nbin]
     out->zero ();
     const double period = f.number ("FOLDING_PERIOD");
     if (period > 0) out->set_folding_period (period);
@@ -101,7 +105,7 @@ namespace HIP
     out->set_ndat_expected (uint64_t (f.number ("NDAT_TOTAL")));
     out->set_end_time (out->get_start_time () + f.number ("INTEGRATION_LENGTH"));
     unsigned* hits = out->get_hits ();
-    for (unsigned ibin = 0; ibin < f.nbin; ibin++) hits[ibin] = f.hits[ibin];
+    for (size_t ibin = 0; ibin < f.hits.size (); ibin++) hits[ibin] = f.hits[ibin];
     for (unsigned ichan = 0; ichan < f.nchan; ichan++)
       for (unsigned ipol = 0; ipol < f.npol; ipol++)
         memcpy (out->get_datptr (ichan, ipol), &f.sums[(size_t (ichan) * f.npol + ipol) * f.nbin * f.ndim],

@@ -19,7 +19,7 @@ from dataclasses import dataclass
 import numpy as np
 
 from . import _lib
-from .engine import (Context, ConvolutionEngine, CyclicFoldEngine, Dedispersion, DspsrAmdError, FilterbankEngine, FoldEngine, PhaseLockedFilterbankEngine, plfb_check_shape, Rescale, SampleDelay, add_fpt, copy_data_fpt, fourth_moment,
+from .engine import (Context, ConvolutionEngine, CyclicFoldEngine, Dedispersion, DetectionEngine, DspsrAmdError, SpectralKurtosisEngine, FilterbankEngine, FoldEngine, PhaseLockedFilterbankEngine, plfb_check_shape, Rescale, SampleDelay, add_fpt, copy_data_fpt, fourth_moment,
                      dedispersion_sample_delays, detect_raw, eight_bit_scale, fscrunch_fpt, pscrunch_tfp, sigproc_digitize, sigproc_digitize_fpt,
                      tfp_filterbank, tscrunch_fpt)
 
@@ -92,6 +92,16 @@ class Config:
     npol: int = 4                          # -d: the reference's config->npol.  This path detects the four products (4); the field
                                            # decides the branch of LoadToFold1.C:552-568 only: with 1 or 3 it wins over -4, which is
                                            # then ignored
+    sk_zap: bool = False                   # -skz: spectral-kurtosis RFI excision (dsp::SpectralKurtosis between the filterbank and
+                                           # Detection, LoadToFold1.C:458-532; defaults of LoadToFoldConfig.C:71-89).  False: off --
+                                           # today's paths, untouched
+    sk_m: int = 128                        # -skzm: samples per SK estimate
+    sk_std_devs: int = 3                   # -skzs: excision threshold in standard deviations
+    sk_chan_start: int = 0                 # -skz_start / -skz_end: channel range of the tscr and fscr detections; taken only when
+    sk_chan_end: int = 0                   # start > 0 and end < nchan (LoadToFold1.C:527-528); end 0: nchan
+    sk_no_fscr: bool = False               # -skz_no_fscr / -skz_no_tscr / -skz_no_ft: disable one of the three detections
+    sk_no_tscr: bool = False
+    sk_no_ft: bool = False
 
 
 @dataclass
@@ -488,12 +498,14 @@ def write_phase_series(path, sub, info: "InputInfo", cfg: "Config", *, nchan=Non
     """sub: a dict as LoadToFold.subints holds (hits, integration_length, ndat_total, profile or profile_dev).  A -4 run
     (fourth_moment_active(cfg)) writes STATE FourthMoment, NPOL 1, NDIM 14 whatever npol / state say.  rate / nsub_swap (a -G run:
     spectra per second, and the input channels whose raw transform order the output channels keep) add the keys RATE and
-    NSUB_SWAP; without them the header is what it always was."""
+    NSUB_SWAP; without them the header is what it always was.  hits of two dimensions ([nchan][nbin]: a -skz run, whose fold counts
+    per channel) add the key HITS_NCHAN and are written whole; one-dimensional hits leave header and body as they always were."""
     prof = sub.get("profile")
     if prof is None:
         prof = sub["profile_dev"].cpu().numpy()
     nchan = nchan or cfg.nchan
-    nbin = len(sub["hits"])
+    hits = np.asarray(sub["hits"])
+    nbin = hits.shape[-1]
     ndim = ndim or cfg.ndim
     if fourth_moment_active(cfg) and not cfg.cyclic_nchan and not cfg.plfb_nbin:
         npol, ndim, state = 1, 14, "FourthMoment"
@@ -511,17 +523,20 @@ def write_phase_series(path, sub, info: "InputInfo", cfg: "Config", *, nchan=Non
         keys.append(("RATE", repr(float(rate))))
     if nsub_swap is not None:
         keys.append(("NSUB_SWAP", int(nsub_swap)))
+    if hits.ndim == 2:
+        keys.append(("HITS_NCHAN", hits.shape[0]))
     text = "".join("%-20s %s\n" % (k, v) for k, v in keys)
     if len(text) >= PHASE_SERIES_HDR_SIZE:
         raise DspsrAmdError("write_phase_series: header does not fit %d bytes" % PHASE_SERIES_HDR_SIZE)
     with open(path, "wb") as f:
         f.write(text.encode("ascii").ljust(PHASE_SERIES_HDR_SIZE, b"\0"))
-        f.write(np.asarray(sub["hits"], dtype="<u4").tobytes())
+        f.write(np.ascontiguousarray(hits, dtype="<u4").tobytes())
         f.write(prof.tobytes())
 
 
 def read_phase_series(path):
-    """Returns (header dict, hits uint32[nbin], profile float32 [nchan][npol][nbin][ndim])."""
+    """Returns (header dict, hits uint32[nbin] -- [HITS_NCHAN][nbin] where the header has that key --, profile float32
+    [nchan][npol][nbin][ndim])."""
     with open(path, "rb") as f:
         raw = f.read(PHASE_SERIES_HDR_SIZE)
         hdr = {}
@@ -532,10 +547,13 @@ def read_phase_series(path):
         if hdr.get("HDR_MAGIC") != PHASE_SERIES_MAGIC:
             raise DspsrAmdError("read_phase_series: %s is not a %s file" % (path, PHASE_SERIES_MAGIC))
         nchan, npol, nbin, ndim = (int(hdr[k]) for k in ("NCHAN", "NPOL", "NBIN", "NDIM"))
-        hits = np.frombuffer(f.read(4 * nbin), dtype="<u4").copy()
+        hits_nchan = int(hdr.get("HITS_NCHAN", 0))
+        hits = np.frombuffer(f.read(4 * nbin * max(1, hits_nchan)), dtype="<u4").copy()
         body = f.read(4 * nchan * npol * nbin * ndim)
-        if len(hits) != nbin or len(body) != 4 * nchan * npol * nbin * ndim:
+        if len(hits) != nbin * max(1, hits_nchan) or len(body) != 4 * nchan * npol * nbin * ndim:
             raise DspsrAmdError("read_phase_series: %s is truncated" % path)
+        if hits_nchan:
+            hits = hits.reshape(hits_nchan, nbin)
         prof = np.frombuffer(body, dtype="<f4").reshape(nchan, npol, nbin, ndim).copy()
     return hdr, hits, prof
 
@@ -1051,6 +1069,34 @@ def fourth_moment_check(cfg: "Config", ntargets=0, subband=None):
     return dataclasses.replace(cfg, stokes=True, ndim=4, fused_fold=False, force_fused=False)
 
 
+def sk_check(cfg: "Config", info: "InputInfo", ntargets=0, subband=None, dump_before=()):
+    """What a -skz run refuses, on the host, after every refusal the run had without it.  Returns the channel range the engine gets."""
+    who = "dspsr_amd.LoadToFold: spectral kurtosis (-skz)"
+    for on, what in ((cfg.cyclic_nchan > 0, "cyclic_nchan (-cyclic)"), (cfg.plfb_nbin > 0, "plfb_nbin (-G)"),
+                     (fourth_moment_active(cfg), "fourth_moment (-4)"), (cfg.interchan_dedispersion, "interchan_dedispersion (-K)")):
+        if on:
+            raise DspsrAmdError("%s is not built with %s" % (who, what))
+    if ntargets > 1:
+        raise DspsrAmdError("%s folds one pulsar; %d targets given" % (who, ntargets))
+    if subband is not None:
+        raise DspsrAmdError("%s is not built for sub-band sharded runs / the multi-GPU exchange" % who)
+    if cfg.convolve_when != "during":
+        raise DspsrAmdError("%s is built for -F N:D (convolve_when = during), not %r" % (who, cfg.convolve_when))
+    if dump_before:
+        raise DspsrAmdError("%s is not built with the dump taps" % who)
+    if info.npol == 1 and cfg.ndim == 4:
+        raise DspsrAmdError("%s: one input polarisation cannot be detected with ndim 4" % who)
+    if not 32 <= cfg.sk_m <= 65536:
+        raise DspsrAmdError("%s: sk_m=%d outside [32, 65536] (below 32 the Pearson IV limits do not exist)" % (who, cfg.sk_m))
+    if cfg.sk_std_devs < 1:
+        raise DspsrAmdError("%s: sk_std_devs == 0 (SKLimits::calc_limits invalid inputs)" % who)
+    if not (cfg.sk_chan_start > 0 and cfg.sk_chan_end < cfg.nchan):                 # LoadToFold1.C:527-528: no range is set
+        return 0, 0
+    if cfg.sk_chan_start >= (cfg.sk_chan_end or cfg.nchan):
+        raise DspsrAmdError("%s: sk_chan_start=%d >= sk_chan_end=%d" % (who, cfg.sk_chan_start, cfg.sk_chan_end or cfg.nchan))
+    return cfg.sk_chan_start, cfg.sk_chan_end
+
+
 def _device(ctx):
     return "cuda:%d" % ctx.device
 
@@ -1226,6 +1272,7 @@ class LoadToFold:
         import torch
         self.torch = torch
         self.pulsars, self.cyclic, self.plfb, self.rfi_filter = [], None, None, None
+        self.sk, self.sk_statistics = None, None
         self.ctx = self.fb = self.fold = self.response = self.sample_delay = self.detected = self.voltages = None
         self.sd = DelayCarry()              # -K: head room in front of `detected` and the tail carried in it
         self.fused_mode, self.fused_fold = 0, False
@@ -1281,7 +1328,10 @@ class LoadToFold:
         self.nchan_out = (cfg.nchan // info.nchan) * self.in_nchan       # output channels this instance produces
         self.npol_out = 4 // cfg.ndim
         if cfg.convolve_when != "during":
-            return self._plan_after(subband, dump_before)
+            self._plan_after(subband, dump_before)
+            if cfg.sk_zap:
+                sk_check(cfg, info, len(targets), subband, dump_before)
+            return
         # -F N:D: the response inside the filterbank (LoadToFold1.C:318-323; -K: the fractional delays with it, :620-621)
         self.response = r = matched_response(info, cfg.dispersion_measure, cfg.freq_res, cfg.nchan, input_nchan=info.nchan, ndim=info.ndim,
                                              fractional_delay=cfg.interchan_dedispersion)
@@ -1293,6 +1343,11 @@ class LoadToFold:
         else:
             self._plan_delays()
             self._plan_taps(dump_before)
+        if cfg.sk_zap:
+            # -skz: the rows of a block sit behind a head room that holds the carried tail, the < M samples SpectralKurtosis has not
+            # consumed yet (InputBuffering, set_next_start(output_ndat): SpectralKurtosis.C:211-217)
+            self.sk_range = sk_check(cfg, info, len(targets), subband, dump_before)
+            self.sk_head, self.sk_tail = cfg.sk_m - 1, 0
 
     def _plan_after(self, subband, dump_before):
         """`dspsr -F N` (Filterbank::Config::After) and the filterbank without coherent dedispersion (Config::Never): the non-convolving
@@ -1402,6 +1457,8 @@ class LoadToFold:
             self.voltages = _device_empty(self.ctx, (self.nchan_out, info.npol, 2 * (self.plfb_head + rows * self.nkeep)))
             self.hits = np.zeros(cfg.plfb_nbin, dtype=np.uint32)
             return
+        if cfg.sk_zap:
+            return self._open_sk(r, nsub, rows, setup)
         if cfg.convolve_when == "during":
             # -pac: chirp x Jones per bin as a matrix response instead of the chirp (calibrator_response)
             matrix = self._calibrated[1] if self._calibrated else None
@@ -1453,6 +1510,73 @@ class LoadToFold:
         if "Fold" in self.dumps:
             self.fused_mode, self.fused_fold = 0, False          # the detected samples must exist in HBM to be dumped
         self.hits = np.zeros(cfg.nbin, dtype=np.uint32)
+
+    def _open_sk(self, r, nsub, rows, setup):
+        """`dspsr -skz`: the convolving filterbank writes its complex rows, dsp::SpectralKurtosis zeroes what it zaps in place,
+        Detection and Fold follow; the fold counts its hits per channel on the device (Fold::Engine::zeroed_samples with
+        hits_nchan == nchan, LoadToFold1.C:458-532, Fold.C:853-866)."""
+        cfg, info = self.cfg, self.info
+        matrix = self._calibrated[1] if self._calibrated else None
+        _open_convolving_front(self, r, nsub, self.in_nchan, None if matrix is not None else r.kernel, fused_fold=_lib.FUSED_NEVER,
+                               response_matrix=matrix, **setup)
+        self.fold = FoldEngine(self.ctx)
+        self.fold.set_shape(self.nchan_out, self.npol_out, cfg.ndim, cfg.nbin)
+        self.sk = SpectralKurtosisEngine(self.ctx)
+        self.sk.set_shape(self.nchan_out, info.npol, cfg.sk_m)
+        self.sk.set_options(cfg.sk_std_devs, *self.sk_range, cfg.sk_no_fscr, cfg.sk_no_tscr, cfg.sk_no_ft)
+        self.voltages = _device_empty(self.ctx, (self.nchan_out, info.npol, 2 * (self.sk_head + rows * self.nkeep)))
+        self.detected = _device_empty(self.ctx, (self.nchan_out, self.npol_out, (self.sk_head + rows * self.nkeep) * cfg.ndim))
+        self._sk_books(cfg.nbin)
+
+    def _sk_books(self, nbin):
+        """hits per channel: uint32 [nchan][nbin] on the device, on the host at finish_subint"""
+        self.hits_dev = _device_empty(self.ctx, (self.nchan_out, nbin), "int32", zero=True)
+        self.hits = np.zeros((self.nchan_out, nbin), dtype=np.uint32)
+
+    def _process_block_sk(self, raw, npart, events):
+        """Filterbank -> complex rows behind the carried tail -> SpectralKurtosis over the whole parts of M samples (in place: zeros
+        over what it zaps) -> Detection -> Fold piece by piece, hits counted where the detected sample is not zero; the remainder is
+        carried in front of the next block's rows.  The last < M samples of a run are dropped, as the reference drops them."""
+        cfg = self.cfg
+        M, head, tail, ndat = cfg.sk_m, self.sk_head, self.sk_tail, npart * self.nkeep
+        self._filterbank_op("Filterbank", lambda: self.fb.perform_raw(raw, self.layout, self.scale8, self.voltages[:, :, 2 * head:], npart),
+                            events)
+        rows = self.voltages[:, :, 2 * (head - tail):]
+        nuse = (tail + ndat) // M * M
+        if nuse:
+            self._op("SpectralKurtosis", lambda: self.sk.transform(rows, rows, tail + ndat))
+            det = self.detected[:, :, :nuse * cfg.ndim]
+            state = _lib.STOKES if cfg.stokes else _lib.COHERENCE
+            self._op("Detection", lambda: DetectionEngine(self.ctx).polarimetry(cfg.ndim, rows[:, :, :2 * nuse], det, state))
+            for idat_start, ndat_fold, _division, complete in self._pieces(nuse):
+                t0 = self.out_start + (self.ndat_out + idat_start + 0.5) / self.out_rate
+                phi, pfold = self._phase(t0)
+                self.fold.set_nbin(cfg.nbin)
+                self.fold.set_ndat(ndat_fold, idat_start)
+                self.fold.set_bins(phi, (1.0 / self.out_rate) / pfold, ndat_fold, idat_start, None)     # (the hits are the device's)
+                self._op("Fold", lambda: self.fold.fold_zeroed(det, self.hits_dev))
+                self.ndat_total += ndat_fold
+                if complete:
+                    self.finish_subint()
+        keep = tail + ndat - nuse
+        if keep:                                                     # (ndat samples forward: never onto itself)
+            move_tail_fpt(self.ctx, self.voltages, head - keep, head - tail + nuse, keep, unit=2)
+        self.sk_tail = keep
+        self.ndat_out += nuse
+        self.nsamples_in += npart * self.nsamp_step
+
+    def _finish_sk_subint(self):
+        """The hits come to the host; integration_length = hits.sum() / (rate * nchan), once, from the integer total (Fold.C:893-896)"""
+        if not self.ndat_total:
+            return
+        self.hits = self.hits_dev.cpu().numpy().view(np.uint32)
+        self.integration_length = float(int(self.hits.sum(dtype=np.uint64))) / (self.out_rate * self.nchan_out)
+        self.sk_statistics = self.sk.get_statistics()
+
+        def zero():
+            self.fold.zero()
+            self.hits_dev.zero_()
+        _emit(self, _books(self, profile_dev=self.profiles_tensor().clone()), zero)
 
     def _filterbank_op(self, name, fn, events):
         """The filterbank step of a block as an operation, between the caller's two HIP events (bench.py's roofline brackets the
@@ -1541,6 +1665,8 @@ class LoadToFold:
                 else:
                     self.fold.set_shape(self.nchan_out, *self._fold_dims(), nbins[0])
                 self.hits = np.zeros(nbins[0], dtype=np.uint32)
+                if self.cfg.sk_zap:
+                    self._sk_books(nbins[0])
             return
         self.fused_mode, self.fused_fold = 0, False
         self.fold.close()
@@ -1679,6 +1805,8 @@ class LoadToFold:
             return self._process_block_cyclic(raw, npart, events)
         if self.plfb is not None:
             return self._process_block_plfb(raw, npart, events)
+        if cfg.sk_zap:
+            return self._process_block_sk(raw, npart, events)
         ndat = npart * self.nkeep
         state = _lib.STOKES if cfg.stokes else _lib.COHERENCE
         if "Detection" in self.dumps:                        # the filterbank's complex output: one extra pass, taps only
@@ -1791,6 +1919,8 @@ class LoadToFold:
             raise DspsrAmdError("dspsr_amd.LoadToFold.%s: cyclic spectra are not built for a multi-GPU exchange" % what)
         if self.moments:
             raise DspsrAmdError("dspsr_amd.LoadToFold.%s: fourth_moment (-4) is not built for a multi-GPU exchange" % what)
+        if self.cfg.sk_zap:
+            raise DspsrAmdError("dspsr_amd.LoadToFold.%s: spectral kurtosis (-skz) is not built for a multi-GPU exchange" % what)
 
     def _single_pulsar_only(self, what):
         if self.pulsars:
@@ -1903,6 +2033,8 @@ class LoadToFold:
             return self._finish_cyclic_subint()
         if self.plfb is not None:
             return self._finish_plfb_subint()
+        if self.cfg.sk_zap:
+            return self._finish_sk_subint()
         if self.comm is not None:
             # (one exchange in flight per communicator.  The result of the previous one is COPIED here even with
             #  copy_subints False: start() below may grow the pinned buffer a view would point into -- a view is only handed
@@ -2005,7 +2137,7 @@ class LoadToFold:
         self._closed = True
         if self._comm_pending is not None:
             self.collect_subint()
-        _close_all(*self.dumps.values(), self.sample_delay, self.fb, self.fold, self.cyclic, self.plfb, *(p.fold for p in self.pulsars),
+        _close_all(*self.dumps.values(), self.sample_delay, self.fb, self.fold, self.cyclic, self.plfb, self.sk, *(p.fold for p in self.pulsars),
                    self.ctx)
 
 

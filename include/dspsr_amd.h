@@ -397,7 +397,7 @@ int dspsr_amd_fold_set_bins(dspsr_amd_fold* fold, double phi, double phase_per_s
                             uint64_t idat_start, uint32_t* hits_host, uint64_t* ndat_folded);
 /* the same with the weights of the input (Fold.C:686-716,746-763: WeightedTimeSeries, one weight per ndatperweight samples,
  * sample idat belongs to weight (idat + weight_idat) / ndatperweight): samples of a zero weight are left out of the plan,
- * of hits[] and of *ndat_folded.  The hook for flagged / dropped data; spectral kurtosis itself is not part of this path. */
+ * of hits[] and of *ndat_folded.  The hook for flagged / dropped data; spectral kurtosis itself is dspsr_amd_sk below. */
 int dspsr_amd_fold_set_bins_weighted(dspsr_amd_fold* fold, double phi, double phase_per_sample, uint64_t ndat,
                                      uint64_t idat_start, const uint32_t* weights_host, uint64_t nweights,
                                      uint64_t ndatperweight, uint64_t weight_idat, uint32_t* hits_host,
@@ -419,7 +419,7 @@ int dspsr_amd_fold_fold_many(dspsr_amd_fold* const* folds, uint32_t nfold, const
 /* fold() of an input that carries zeroed (RFI-excised) samples -- Fold::Engine::zeroed_samples with hits_nchan == nchan
  * (Fold.C:853-866, fold1bin*hits FoldCUDA.cu:415-576,622): as dspsr_amd_fold_fold, and hits_dev[ichan*nbin + ibin] (device,
  * uint32) is incremented by the number of planned samples of polarisation 0 whose first float is not zero.  The hook the
- * reference's spectral-kurtosis chain needs; the excision itself is not part of this path. */
+ * reference's spectral-kurtosis chain needs; the excision itself is dspsr_amd_sk below. */
 int dspsr_amd_fold_fold_zeroed(dspsr_amd_fold* fold, const float* in_dev, uint64_t in_chan_stride, uint64_t in_pol_stride,
                                uint32_t* hits_dev);
 float* dspsr_amd_fold_profiles_dev(dspsr_amd_fold* fold);   /* device [nchan][npol][nbin][ndim] (get_profiles) */
@@ -573,6 +573,66 @@ int dspsr_amd_bandpass_zero(dspsr_amd_bandpass* bp);
 /* device passband [npol_out][nchan_in][resolution], valid in stream order */
 float* dspsr_amd_bandpass_pass_dev(dspsr_amd_bandpass* bp);
 int dspsr_amd_bandpass_synch(dspsr_amd_bandpass* bp, float* pass_host, double* integration_samples);
+
+/* ---- dsp::SpectralKurtosis (dspsr -skz): estimate, detect, mask ---------------------------------------------------------
+ * Reference: Signal/General/SpectralKurtosis.C, LoadToFold1.C:458-532.  The CPU branch in FPT order is the definition (where the
+ * reference's CUDA engines differ from it, it wins).  Input: complex rows [nchan][npol][ndat], ndim 2, element (chan, pol, t) =
+ * in + chan*chan_stride + pol*pol_stride + 2*t (strides in floats).  npart = ndat / M; the ndat % M samples behind are not touched.
+ *   sk_limits   : host only.  dsp::SKLimits(M, std_devs) rounded to float (SKLimits.C, PearsonIV.C; SpectralKurtosis.C:390-391).
+ *                 M >= 32768: 1 -+ std_devs*sqrt(4/M).  Where the reference's Newton iteration gives up, the limit is its starting
+ *                 guess, the same expression.  M < 32 (the Pearson IV parameters are not finite below 24) or std_devs == 0: EINVAL.
+ *   set_shape   : M in [32, 65536], npol 1 or 2, nchan in [1, 65535].  A new shape zeroes the counters.
+ *   set_options : std_devs (> 0); the channel range [chan_start, chan_end) of tscr, fscr and the counters, chan_end == 0: nchan;
+ *                 the three detections can be disabled (SpectralKurtosis::set_options).  Needs a shape.
+ *   compute     : (:302-371) per (part, chan, pol) S1 = sum |x|^2, S2 = sum |x|^4 in float, one rounding per operation (no fused
+ *                 multiply-add); estimates[(part*nchan + chan)*npol + pol] = M_fac * (M * (S2 / (S1*S1)) - 1), 0 when S1 == 0,
+ *                 M_fac = (M+1)/(M-1) in unsigned integers (:253); unless tscr is disabled estimates_tscr[chan*npol + pol] from the
+ *                 per-part sums added in part order, M_t = float(M*npart), factor (M_t+1)/(M_t-1) in float.  The sums over the M
+ *                 samples of one part run in a fixed tree that depends on M alone (csrc/sk.hip: k_sk_compute); no atomics: the same
+ *                 bits for any npart, launch shape or cut of a stream into calls.  ndat < M: nothing to do.
+ *   reset_mask, detect_tscr, detect_skfb, detect_fscr, count_zapped : the steps of SpectralKurtosis::detect (:413-454) as its Engine
+ *                 interface cuts them, on the estimates of the last compute; comparisons are V > upper || V < lower.
+ *                 detect_tscr: a channel of the range with any polarisation outside the limits is zapped in all parts.
+ *                 detect_skfb: any polarisation outside zaps (part, chan), all channels; counted where chan_start < chan < chan_end.
+ *                 detect_fscr (:684-741): per part and polarisation the sequential float sum, in channel order, of the channels of
+ *                 the range not yet zapped, divided by their count cnt; one_sigma = sqrt(mu2 / float(cnt)), mu2 =
+ *                 4M^2/((M-1)(M+2)(M+3)) in float; outside 1 -+ (1+std_devs)*one_sigma in either polarisation zaps all channels.
+ *                 count_zapped (:605-665): zap_counts[0], filtered / unfiltered sums (float, part order) and hits over the range;
+ *                 also npart_total += npart*nchan (:434) and unfiltered_hits += npart.
+ *   mask        : (:747-797) out = zapmask[part*nchan + chan] ? 0 : in for both polarisations over npart*M samples.  out == in
+ *                 (same strides) writes zeros over the zapped parts only and reads no sample.  The output carries zeroed data:
+ *                 fold it with dspsr_amd_fold_fold_zeroed.
+ *   transform   : compute, reset_mask, detect_tscr, detect_skfb, detect_fscr (each unless disabled), count_zapped, mask, with the
+ *                 limits of sk_limits for M and, cached per distinct M*npart, for the tscr estimate (:476-501).
+ *   get_statistics : waits.  counts[6] = zap_counts[all, skfb, fscr, tscr], npart_total, unfiltered_hits; filtered_hits[nchan];
+ *                 filtered_sum / unfiltered_sum[nchan*npol].  Any pointer may be NULL.  reset_count zeroes them all.
+ * Refused with DSPSR_AMD_EINVAL and the limit's name before any launch: a shape outside the limits above, ndat >= 2^31, rows not
+ * 8-byte aligned, strides shorter than the row, rows that overlap one another, input and output that partly overlap,
+ * std_devs == 0, chan_start >= chan_end, chan_end > nchan. */
+typedef struct dspsr_amd_sk dspsr_amd_sk;
+int dspsr_amd_sk_limits(uint32_t M, uint32_t std_devs, float* lower, float* upper);
+int dspsr_amd_sk_create(dspsr_amd_ctx* ctx, dspsr_amd_sk** out);
+void dspsr_amd_sk_destroy(dspsr_amd_sk* sk);
+int dspsr_amd_sk_set_shape(dspsr_amd_sk* sk, uint32_t nchan, uint32_t npol, uint32_t M);
+int dspsr_amd_sk_set_options(dspsr_amd_sk* sk, uint32_t std_devs, uint32_t chan_start, uint32_t chan_end, int no_fscr, int no_tscr,
+                             int no_ft);
+int dspsr_amd_sk_compute(dspsr_amd_sk* sk, const float* in_dev, uint64_t chan_stride, uint64_t pol_stride, uint64_t ndat);
+int dspsr_amd_sk_reset_mask(dspsr_amd_sk* sk);
+int dspsr_amd_sk_detect_tscr(dspsr_amd_sk* sk, float lower, float upper);
+int dspsr_amd_sk_detect_skfb(dspsr_amd_sk* sk, float lower, float upper);
+int dspsr_amd_sk_detect_fscr(dspsr_amd_sk* sk);
+int dspsr_amd_sk_count_zapped(dspsr_amd_sk* sk);
+int dspsr_amd_sk_mask(dspsr_amd_sk* sk, const float* in_dev, uint64_t in_chan_stride, uint64_t in_pol_stride, float* out_dev,
+                      uint64_t out_chan_stride, uint64_t out_pol_stride);
+int dspsr_amd_sk_transform(dspsr_amd_sk* sk, const float* in_dev, uint64_t in_chan_stride, uint64_t in_pol_stride, float* out_dev,
+                           uint64_t out_chan_stride, uint64_t out_pol_stride, uint64_t ndat);
+/* of the last compute, valid in stream order: parts, estimates [npart][nchan][npol], estimates_tscr [nchan][npol], zapmask [npart][nchan] */
+uint64_t dspsr_amd_sk_npart(dspsr_amd_sk* sk);
+float* dspsr_amd_sk_estimates_dev(dspsr_amd_sk* sk);
+float* dspsr_amd_sk_estimates_tscr_dev(dspsr_amd_sk* sk);
+uint8_t* dspsr_amd_sk_zapmask_dev(dspsr_amd_sk* sk);
+int dspsr_amd_sk_get_statistics(dspsr_amd_sk* sk, uint64_t* counts, uint64_t* filtered_hits, float* filtered_sum, float* unfiltered_sum);
+int dspsr_amd_sk_reset_count(dspsr_amd_sk* sk);
 
 /* ---- the sub-integration dump over RCCL / xGMI: the ONE exchange of the path -----------------------------------------
  * Reference hook: dsp::Subint<Fold>::transformation emits the finished sub-integration (Signal/Pulsar/dsp/Subint.h:291-303);

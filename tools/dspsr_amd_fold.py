@@ -21,6 +21,11 @@ dspsr_amd.dada.fold_file for trying the engine on a DADA file; not a re-implemen
                     reference's lines `round k cutoff = ...` and `zapped N channels` go to stderr.  A channel zapped in any round
                     stays zapped -- the reference's own loop leaves a mask of all ones)
 
+  dspsr_amd_fold.py -F 16:D -skz [-skzm 128] [-skzs 3] [-skz_start c -skz_end c] [-skz_no_fscr] [-skz_no_tscr] [-skz_no_ft] ...
+                    (spectral-kurtosis RFI excision, dspsr.C:289-314: dsp::SpectralKurtosis zeroes what it zaps between the filterbank
+                    and Detection, the fold counts its hits per channel -- files with HITS_NCHAN -- and the reference's line
+                    `Zapped: total=...% skfb=...% tscr=...% fscr=...%` goes to stderr at the end)
+
 Every completed sub-integration is written as <prefix>_<n>.ps (the PhaseSeries hand-off file of INTEGRATION.md:
 raw sums + hits; dsp::Archiver's normalisation is the reader's job).
 
@@ -54,6 +59,14 @@ def parse_args(argv=None):
     ap.add_argument("-G", dest="plfb_nbin", type=int, default=0, help="create phase-locked filterbank with nbin phase bins")
     ap.add_argument("-pac", dest="pac", default=None, help="phase-coherent polarimetric calibration: .npz with freq (MHz) and jones [n][2][2]")
     ap.add_argument("-R", dest="zap_rfi", action="store_true", help="apply time-variable narrow-band RFI filter")
+    ap.add_argument("-skz", dest="skz", action="store_true", help="apply spectral kurtosis filterbank RFI zapping")
+    ap.add_argument("-skzm", dest="skzm", type=int, default=128, help="samples to integrate for spectral kurtosis statistics")
+    ap.add_argument("-skzs", dest="skzs", type=int, default=3, help="number of std deviations to use for spectral kurtosis excisions")
+    ap.add_argument("-skz_start", dest="skz_start", type=int, default=0, help="first channel where signal is expected")
+    ap.add_argument("-skz_end", dest="skz_end", type=int, default=0, help="last channel where signal is expected")
+    ap.add_argument("-skz_no_fscr", dest="skz_no_fscr", action="store_true", help="do not use SKDetector Fscrunch feature")
+    ap.add_argument("-skz_no_tscr", dest="skz_no_tscr", action="store_true", help="do not use SKDetector Tscrunch feature")
+    ap.add_argument("-skz_no_ft", dest="skz_no_ft", action="store_true", help="do not use SKDetector despeckeler")
     ap.add_argument("-r", dest="record", action="store_true", help="report the time spent in each operation")
     ap.add_argument("--dump", action="append", default=[], help="dump the input of this operation (Detection, Fold)")
     ap.add_argument("-O", dest="prefix", default="dspsr_amd", help="output file name prefix")
@@ -103,6 +116,8 @@ def main(argv=None):
                           plfb_nbin=a.plfb_nbin, npol=a.ndim if a.plfb_nbin else 4,
                           cyclic_nchan=a.cyclic, cyclic_mover=a.cyclic_mover, cyclic_npol=(a.ndim if info.npol == 2 else 1) if a.cyclic else 0,
                           interchan_dedispersion=a.interchan, record_time=a.record, fourth_moment=a.fourth, calibrator=a.pac, zap_rfi=a.zap_rfi,
+                          sk_zap=a.skz, sk_m=a.skzm, sk_std_devs=a.skzs, sk_chan_start=a.skz_start, sk_chan_end=a.skz_end, sk_no_fscr=a.skz_no_fscr,
+                          sk_no_tscr=a.skz_no_tscr, sk_no_ft=a.skz_no_ft,
                           convolve_when="never" if when == "after" and dm == 0.0 else when)
     torch.cuda.set_device(a.device)
     lt = dada.fold_file(a.file, cfg, polyco=polyco, device=a.device, stream=torch.cuda.current_stream().cuda_stream,
@@ -127,6 +142,10 @@ def main(argv=None):
             pipeline.write_phase_series(path, sub, info, cfg, npol=lt.npol_out, scale=sub.get("scale", lt.scalefac), division=n,
                                         start_seconds=lt.out_start, folding_period=pf, **cyc)
             print("dspsr_amd: %s  integration %.6f s  %d samples" % (path, sub["integration_length"], sub["ndat_total"]))
+    if a.skz:                                               # SpectralKurtosis.C:53-69, the destructor's line
+        st = lt.sk.get_statistics()
+        pct = [100 * float(z) / float(st["npart_total"]) if st["npart_total"] else 0.0 for z in st["zap_counts"]]
+        print("Zapped:  total=%g%% skfb=%g%% tscr=%g%% fscr=%g%%" % (pct[0], pct[1], pct[3], pct[2]), file=sys.stderr)
     if a.record:
         lt.report()
     lt.close()

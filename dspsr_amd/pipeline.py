@@ -1166,15 +1166,16 @@ def _open_convolving_front(drv, r, nsub, in_nchan, kernel, **setup):
 
 
 class DelayCarry:
-    """The head room of -K in front of a block of detected rows, and the tail carried in it.  dsp::SampleDelay gives up its
-    total_delay at the end of every block and InputBuffering re-presents those samples in front of the next one (SampleDelay.C:117,
-    146): a block's new samples are written behind `head` samples of room, the `carried` ones of the block before sit right in
-    front of them.  `short`: samples a sub-band rank gives up on top of its own delay, so that all ranks emit the same ones.
-    `delays` (relative, per channel): SampleDelay::build on the host (SampleDelay.C:75-99) -- zero = the largest delay, head = the
-    largest applied one, dsp::SampleDelay's zero_delay and total_delay."""
+    """The head room in front of a block's rows, and the tail carried in it (InputBuffering): a block's new samples are written
+    behind `head` samples of room, the `carried` ones that the block before did not consume sit right in front of them.
+    -K: dsp::SampleDelay gives up its total_delay at the end of every block and InputBuffering re-presents those samples in front
+    of the next one (SampleDelay.C:117,146).  `short`: samples a sub-band rank gives up on top of its own delay, so that all ranks
+    emit the same ones.  `delays` (relative, per channel): SampleDelay::build on the host (SampleDelay.C:75-99) -- zero, head =
+    dsp::SampleDelay's zero_delay and total_delay.  -G and -skz give `head` itself: a window, or a part of M samples, waits there."""
 
-    def __init__(self, delays=None):
-        self.zero = self.head = self.carried = self.short = 0
+    def __init__(self, delays=None, head=0):
+        self.zero = self.carried = self.short = 0
+        self.head = head
         if delays is not None:
             d = np.asarray(delays, np.int64)
             self.zero = int(d.max())
@@ -1184,11 +1185,17 @@ class DelayCarry:
         if self.head > block:
             raise DspsrAmdError("dspsr_amd.%s: inter-channel delay of %d samples exceeds the block of %d" % (who, self.head, block))
 
-    def rows(self, buf, ndat, ndim=1):
+    def new(self, buf, ndim=1):
+        """where a block's new samples are written: behind the head room of buf [chan][pol][sample * ndim]"""
+        return buf[:, :, self.head * ndim:]
+
+    def rows(self, buf, ndat=None, ndim=1):
         """the samples to transform, `ndat` new ones lying behind the head room of buf [chan][pol][sample * ndim]: the carried tail
-        and the new samples less `short` (empty when nothing is left: no transform then)"""
-        off, nuse = self.head - self.carried, self.carried + ndat - self.short
-        return buf[:, :, off * ndim:(off + max(nuse, 0)) * ndim]
+        and the new samples less `short` (empty when nothing is left: no transform then).  Without `ndat`: everything from the
+        carried tail on (the caller gives its engine the count)"""
+        off = self.head - self.carried
+        end = None if ndat is None else (off + max(self.carried + ndat - self.short, 0)) * ndim
+        return buf[:, :, off * ndim:end]
 
     def keep_tail(self, ctx, buf, ndat, nout, ndim=1):
         """InputBuffering::set_next_start(output_ndat): the transform delivered `nout` samples; the unshifted tail goes in front of
@@ -1202,13 +1209,6 @@ class DelayCarry:
 
 def _carry_view(name):
     return property(lambda self: getattr(self.sd, name))
-
-
-def _accumulate(acc, folded, ndat_fold, rate):
-    """The books of one fold call on an accumulator (hits, integration_length, ndat_total, subints: a LoadToFold or a _PulsarFold);
-    hits[] were counted by the plan (Fold.C:744-803)."""
-    acc.integration_length += folded / rate
-    acc.ndat_total += ndat_fold
 
 
 def _books(acc, **profile):
@@ -1230,6 +1230,374 @@ def _close_all(*objs):
     for o in objs:
         if o is not None:
             o.close()
+
+
+# ---- the back ends of LoadToFold: what stands behind the front end, one plain class per mode ----------------------------------
+# A back end holds the driver `lt` and owns the mode's share of the host plan (plan), of the device (open), of a block (process:
+# returns the output samples it consumed), of one piece of the shared walk (plan_piece), of a sub-integration (finish), what
+# follows the number of phase bins (shape: at open, and when a single target brings its own), the names of the engines to close (engines) and the words with which the mode
+# refuses a multi-GPU exchange (no_exchange).  The engines stay fields of the driver (lt.fold, lt.cyclic, lt.plfb, lt.sk), read
+# at every call: that is where callers find, and tests replace, them.
+
+def tap_check(cfg: "Config", dump_before):
+    """stage capture (dspsr --dump <Operation>, SingleThread.C:315-346): pre_Detection.dump / pre_Fold.dump"""
+    for name in dump_before:
+        if name not in ("Detection", "Fold"):
+            raise DspsrAmdError("dsp::SingleThread::insert_dump_point no operation named '%s' on this path "
+                                "(Detection, Fold)" % name)
+        if name == "Detection" and cfg.interchan_dedispersion:
+            raise DspsrAmdError("dspsr_amd.LoadToFold: the pre_Detection tap is not built for -K (the delay is applied "
+                                "to the detected rows here); tap pre_Fold instead")
+    return dump_before
+
+
+class DetectFold:
+    """Detection + Fold: fused into the filterbank's last pass or on the detected block, with the dump taps, -4, several pulsars
+    and -K."""
+
+    detects = True                       # dsp::Detection reads the front end: two polarisations, a convolve_when it knows
+    fuses = True                         # the front end may fold in its last pass (cfg.fused_fold)
+    engines = ("fold",)
+    no_exchange = property(lambda self: "fourth_moment (-4) is" if self.lt.moments else None)
+
+    def __init__(self, lt):
+        self.lt = lt
+
+    def plan(self, ntargets, subband, dump_before):
+        """-K: dsp::SampleDelay on the filterbank output.  Detection acts sample by sample, so delaying the detected rows gives the
+        same numbers as delaying the complex rows first (the reference's order) and keeps the fused filterbank+detect launch group.
+        The samples it gives up at the end of a block wait in the head room in front of `detected` (DelayCarry: lt.sd)."""
+        lt, cfg, info = self.lt, self.lt.cfg, self.lt.info
+        if cfg.interchan_dedispersion:
+            dual = info.ndim == 2                              # Observation.C:80-87; Filterbank.C:358-364
+            lt._delays = dedispersion_sample_delays(info.centre_frequency, info.bandwidth, cfg.dispersion_measure, cfg.nchan, lt.out_rate,
+                                                    swap=dual and info.nchan == 1, nsub_swap=info.nchan if dual and info.nchan > 1 else 0)
+            lt.sd = DelayCarry(lt._delays)
+            lt.out_start += lt.sd.zero / lt.out_rate                                 # SampleDelay.C:159
+        lt._taps = tap_check(cfg, dump_before)
+
+    def open(self, rows, dump_dir):
+        lt, cfg, info, nsub = self.lt, self.lt.cfg, self.lt.info, self.lt.cfg.nchan // self.lt.info.nchan
+        lt.fold = FoldEngine(lt.ctx)
+        self.shape(cfg.nbin)
+        if cfg.interchan_dedispersion:
+            if lt.subband is None:
+                lt.sample_delay = SampleDelay(lt.ctx, lt._delays, lt.npol_out)
+            else:
+                # a sub-band rank applies ITS channels' delays relative to the zero of the WHOLE band and gives up the
+                # whole band's total delay per block, so that every rank emits the same samples with the same start time
+                # (SampleDelay.C:75-99 on the full band; the rank's slice goes in as absolute delays)
+                applied = lt.sd.zero - np.asarray(lt._delays, np.int64)
+                lt.sample_delay = SampleDelay(lt.ctx, applied[lt.subband * nsub:(lt.subband + 1) * nsub], lt.npol_out, absolute=True)
+                lt.sd.short = lt.sd.head - lt.sample_delay.total_delay       # samples this rank must NOT emit
+            lt.sd.check_block("LoadToFold", rows * lt.nkeep)
+        lt.detected = _device_empty(lt.ctx, (lt.nchan_out, lt.npol_out, (lt.sd.head + rows * lt.nkeep) * cfg.ndim))
+        # fused filterbank+detect+fold (no detected time series in HBM): ndim 4, three-pass geometries
+        # (the library decides whether fusing pays for this geometry; when it does not, this driver keeps the
+        # separate Detection and Fold operations on its own `detected` block; -F N:B never fuses)
+        if cfg.fused_fold and cfg.ndim == 4 and lt.sample_delay is None and cfg.convolve_when != "before":
+            lt.fused_mode = lt.fb.fold_is_fused()
+        lt.fused_fold = lt.fused_mode != 0      # fused_mode 2: sums re-associated per run of parts (engine.fold_is_fused)
+        for name in lt._taps:
+            from . import dada
+            chbw = info.bandwidth / info.nchan
+            sub = lt.subband
+            fc = info.centre_frequency if sub is None else info.centre_frequency - 0.5 * info.bandwidth + (sub + 0.5) * chbw
+            bw = info.bandwidth if sub is None else chbw
+            det = name == "Fold"
+            path = os.path.join(dump_dir, "pre_%s%s.dump" % (name, "" if sub is None else ".%d" % sub))
+            fold_npol, fold_ndim = lt._fold_dims()        # -4: the input of Fold is the FourthMoment stream
+            lt.dumps[name] = dada.Dump(
+                path, centre_frequency=fc, bandwidth=bw, nchan=lt.nchan_out, npol=fold_npol if det else 2,
+                ndim=fold_ndim if det else 2, nbit=32, rate=lt.out_rate, mjd_day=info.mjd_day,
+                mjd_sec=info.mjd_sec + lt.out_start,
+                state=("FourthMoment" if lt.moments else "Stokes" if cfg.stokes else "Coherence") if det else "Analytic",
+                source=getattr(info, "source", "unknown"), telescope=getattr(info, "telescope", "unknown"))
+        if "Fold" in lt.dumps:
+            lt.fused_mode, lt.fused_fold = 0, False          # the detected samples must exist in HBM to be dumped
+
+    def process(self, raw, npart, events):
+        """One fold call covers the block and the fold is fused: filterbank, detection and fold in one launch group -- the same sums
+        in the same order as the chain every other block takes: filterbank+detect -> [SampleDelay of -K, in place (LoadToFold1.C:
+        617-618)] -> fold, by piece or by pulsar.  Without -K: no head room, nothing carried, every sample delivered."""
+        lt, cfg, nd, sd, ndat = self.lt, self.lt.cfg, self.lt.cfg.ndim, self.lt.sd, npart * self.lt.nkeep
+        state = _lib.STOKES if cfg.stokes else _lib.COHERENCE
+        if "Detection" in lt.dumps:                          # the filterbank's complex output: one extra pass, taps only
+            if lt._dump_cplx is None:
+                lt._dump_cplx = _device_empty(lt.ctx, (lt.nchan_out, 2, 2 * cfg.parts_per_block * lt.nkeep))
+            lt.fb.perform_raw(raw, lt.layout, lt.scale8, lt._dump_cplx, npart)
+            lt.dumps["Detection"].write(lt._dump_cplx, ndat, 2)
+        pieces = lt._pieces(ndat) if lt.fused_fold else None
+        if pieces is not None and len(pieces) == 1 and pieces[0][:2] == (0, ndat):
+            lt._fold_pieces(pieces, lambda: lt._filterbank_op("Filterbank+Detection+Fold", lambda: lt.fb.perform_fold(
+                lt.fold, npart, state, raw=raw, layout=lt.layout, scale=lt.scale8), events))
+            return ndat
+        lt._filterbank_op("Filterbank+Detection", lambda: lt.fb.perform_detect(sd.new(lt.detected, nd), npart, state, nd, raw=raw,
+                                                                               layout=lt.layout, scale=lt.scale8), events)
+        rows, nout = lt.detected, ndat
+        if lt.sample_delay is not None:
+            rows = sd.rows(lt.detected, ndat, nd)   # (sub-band rank: the band's total delay, not just this rank's, is given up)
+            nuse = rows.shape[2] // nd
+            nout = lt._op("SampleDelay", lambda: lt.sample_delay.transform(rows.unflatten(2, (nuse, nd)))) if nuse else 0
+        if nout and "Fold" in lt.dumps:
+            if lt.moments:
+                lt.dumps["Fold"].write(self._moment_stream(rows, nout), nout, 14)
+            else:
+                lt.dumps["Fold"].write(rows, nout, nd)
+        if nout and lt.pulsars:
+            self._fold_pulsars(rows, nout)
+        elif nout:
+            lt._fold_pieces(pieces or lt._pieces(nout), lambda: lt._op("Fold", lambda: self._fold_rows(rows)))
+        sd.keep_tail(lt.ctx, lt.detected, ndat, nout, nd)
+        return nout
+
+    def plan_piece(self, acc, phi, phase_per_sample, ndat_fold, idat_start):
+        """The host plan loop of Fold::fold (Fold.C:718-787) on the accumulator's fold: the driver's, or a pulsar's"""
+        acc.fold.set_nbin(self.lt.cfg.nbin if acc is self.lt else acc.nbin)
+        acc.fold.set_ndat(ndat_fold, idat_start)
+        return acc.fold.set_bins(phi, phase_per_sample, ndat_fold, idat_start, acc.hits)
+
+    def _fold_pulsars(self, rows, ndat):
+        """Several pulsars over the same detected rows.  The pulsars whose share of the block is one piece of a sub-integration
+        fold together (FoldEngine.fold_many: the rows are read once for all of them); a pulsar with a sub-integration boundary
+        inside the block folds piece by piece and emits its sub-integration in between."""
+        lt = self.lt
+        pieces = [lt._pieces(ndat, p) for p in lt.pulsars]
+        group = [(p, pc[0]) for p, pc in zip(lt.pulsars, pieces) if len(pc) == 1]
+        folded = [lt._plan_piece(piece, p) for p, piece in group]
+        if group:
+            lt._op("Fold", lambda: FoldEngine.fold_many([p.fold for p, _ in group], rows))
+        for (p, piece), n in zip(group, folded):
+            lt._book_piece(piece, n, p)
+        for p, pc in zip(lt.pulsars, pieces):
+            if len(pc) > 1:
+                lt._fold_pieces(pc, lambda: lt._op("Fold", lambda: p.fold.fold(rows)), p)
+
+    def _fold_rows(self, rows):
+        """Fold::fold of the pending plan over detected rows.  -4: the Stokes rows go to the moments fold, which forms the products
+        in registers; with a pre_Fold tap the 14-float stream dsp::FourthMoment would write exists (`_moment_stream`) and is
+        folded as it is -- the same bits either way."""
+        lt = self.lt
+        if not lt.moments:
+            return lt.fold.fold(rows)
+        if lt._moment_rows is not None:
+            return lt.fold.fold(lt._moment_rows)
+        return lt.fold.fold_moments(rows)
+
+    def _moment_stream(self, rows, ndat):
+        """dsp::FourthMoment on the first `ndat` samples of the Stokes rows (pre_Fold tap of a -4 run): [nchan][1][ndat*14]"""
+        lt = self.lt
+        need = lt.nchan_out * 14 * (lt.sd_head + lt.cfg.parts_per_block * lt.nkeep)
+        if lt._moment_buf is None or lt._moment_buf.numel() < need:
+            lt._moment_buf = _device_empty(lt.ctx, need)
+        out = lt._moment_buf[:lt.nchan_out * 14 * ndat].view(lt.nchan_out, 1, 14 * ndat)
+        lt._op("FourthMoment", lambda: fourth_moment(lt.ctx, rows, out, ndat))
+        lt._moment_rows = out
+        return out
+
+    def finish(self, *exchange):
+        """Several pulsars (one GPU): the open sub-integration of each that has folded samples since its last; one: the exchange"""
+        lt = self.lt
+        if not lt.pulsars:
+            return lt._exchange_subint(*exchange)
+        for p in lt.pulsars:
+            if p.ndat_total:
+                lt._finish_pulsar_subint(p)
+
+    def shape(self, nbin):
+        self.lt.fold.set_shape(self.lt.nchan_out, *self.lt._fold_dims(), nbin)
+        self.lt.hits = np.zeros(nbin, dtype=np.uint32)
+
+
+class CyclicFold:
+    """`dspsr -cyclic N`: the convolving filterbank writes its complex rows, dsp::CyclicFold folds their lag products
+    (LoadToFold1.C:534-539,999-1044); Detection and Fold are not built.  At a sub-integration the lag data come to the
+    host and CyclicFoldEngine::synch turns them into spectra (once per sub-integration: host, as in the reference)."""
+
+    detects = fuses = False
+    engines = ("cyclic",)
+    no_exchange = "cyclic spectra are"
+
+    def __init__(self, lt):
+        self.lt = lt
+
+    def plan(self, ntargets, subband, dump_before):
+        self.geometry = cyclic_geometry(self.lt.cfg, self.lt.info)
+        self.lt.npol_out = self.geometry["npol"]
+
+    def shape(self, nbin):
+        lt, g = self.lt, self.geometry
+        lt.cyclic.set_shape(lt.nchan_out, lt.info.npol, g["npol"], g["nlag"], g["mover"], nbin)
+        lt.hits = np.zeros(nbin, dtype=np.uint32)
+
+    def open(self, rows, dump_dir):
+        lt = self.lt
+        lt.cyclic = CyclicFoldEngine(lt.ctx)
+        self.shape(lt.cfg.nbin)
+        lt.voltages = _device_empty(lt.ctx, (lt.nchan_out, lt.info.npol, 2 * rows * lt.nkeep))
+
+    def process(self, raw, npart, events):
+        """Filterbank -> complex rows -> CyclicFold piece by piece (Subint<CyclicFold>).  Lag products never span two fold
+        calls (CyclicFold.C:390: idat < ndat_fold - nlag), so the last nlag samples of every piece add nothing."""
+        lt, ndat = self.lt, npart * self.lt.nkeep
+        lt._filterbank_op("Filterbank", lambda: lt.fb.perform_raw(raw, lt.layout, lt.scale8, lt.voltages, npart), events)
+        lt._fold_pieces(lt._pieces(ndat), lambda: lt._op("CyclicFold", lambda: lt.cyclic.fold(lt.voltages)))
+        return ndat
+
+    def plan_piece(self, acc, phi, phase_per_sample, ndat_fold, idat_start):
+        self.lt.cyclic.set_ndat(ndat_fold, idat_start)
+        return self.lt.cyclic.set_bins(phi, phase_per_sample, ndat_fold, idat_start, acc.hits)
+
+    def finish(self, *_exchange):
+        """CyclicFoldEngine::synch (CyclicFold.C:450-555): spectra [nchan * nchan_spec / mover][npol][nbin][1] on the host"""
+        lt = self.lt
+        if not lt.ndat_total:                                # nothing folded since the last one (as the multi-pulsar branch)
+            return
+        spectra = lt._op("CyclicFold::synch", lambda: lt.cyclic.synch())
+        _emit(lt, _books(lt, profile=spectra[..., None]), lt.cyclic.zero)
+
+
+class PhaseLockedFold:
+    """`dspsr -G nbin`: the convolving filterbank writes its complex rows and dsp::PhaseLockedFilterbank consumes them
+    (LoadToFold1.C:386-456); Detection and Fold are not built.  One integration over the whole stream: the windows are those
+    of ONE transformation call (PlfbPlan), whatever the block size.  The rows of a block sit behind a head room that holds the
+    carried tail -- the samples from the first window that does not fit yet -- so that a window may span two blocks.  It has
+    no pieces: no sub-integrations."""
+
+    detects = fuses = False
+    engines = ("plfb",)
+    no_exchange = "the phase-locked filterbank is"
+    shape = None                         # (nothing follows a target's nbin: the phase bins are plfb_nbin; -b plays no part)
+
+    def __init__(self, lt):
+        self.lt = lt
+
+    def plan(self, ntargets, subband, dump_before):
+        """PhaseLockedFilterbank::prepare (:59-83), all on the host."""
+        lt, cfg, info = self.lt, self.lt.cfg, self.lt.info
+        period, polyco, reference_phase = lt._ephemeris()
+        if period <= 0:
+            period = 1.0 / polyco.frequency(info.mjd_day, info.mjd_sec + lt.out_start)
+        nmax = plfb_choose_nchan(period, lt.out_rate, cfg.plfb_nbin)
+        nchan = cfg.plfb_nchan if cfg.plfb_nchan >= 2 else nmax
+        if nchan > nmax:
+            import warnings
+            warnings.warn("dsp::PhaseLockedFilterbank::prepare warning selected nchan=%d > suggested max=%d" % (nchan, nmax))
+        plfb_check_shape(cfg.nchan, info.npol, 2, nchan, cfg.npol, cfg.plfb_nbin)       # the rows are Analytic: ndat_fft = nchan
+        state = {1: "Intensity", 2: "PPQQ", 4: "Coherence"}[cfg.npol]                  # :128-133
+        lt.plfb_geometry = {"nchan_fft": nchan, "ndat_fft": nchan, "nchan": cfg.nchan * nchan, "npol": cfg.npol, "ndim": 1,
+                            "nbin": cfg.plfb_nbin, "state": state, "rate": lt.out_rate / nchan, "nsub_swap": cfg.nchan,
+                            "scale": lt.scalefac * nchan}                              # :143-149
+        lt.npol_out = cfg.npol
+        self.windows = PlfbPlan(lt._turns_divider(*lt._ephemeris(), turns=1.0 / cfg.plfb_nbin), cfg.plfb_nbin, reference_phase, nchan)
+        self.carry = DelayCarry(head=nchan)
+
+    def open(self, rows, dump_dir):
+        lt, cfg, info = self.lt, self.lt.cfg, self.lt.info
+        lt.plfb = PhaseLockedFilterbankEngine(lt.ctx)
+        lt.plfb.set_shape(cfg.nchan, info.npol, 2, lt.plfb_geometry["nchan_fft"], cfg.npol, cfg.plfb_nbin)
+        lt.voltages = _device_empty(lt.ctx, (lt.nchan_out, info.npol, 2 * (self.carry.head + rows * lt.nkeep)))
+        lt.hits = np.zeros(cfg.plfb_nbin, dtype=np.uint32)
+
+    def process(self, raw, npart, events):
+        """Filterbank -> complex rows behind the carried tail -> every window of the plan that now lies inside the rows, in one
+        accumulate call; then the samples from the next window's start on are carried in front of the next block's rows."""
+        lt, carry, ndat = self.lt, self.carry, npart * self.lt.nkeep
+        nin = carry.carried + ndat
+        lt._filterbank_op("Filterbank", lambda: lt.fb.perform_raw(raw, lt.layout, lt.scale8, carry.new(lt.voltages, 2), npart), events)
+        base, avail = lt.ndat_out - carry.carried, lt.ndat_out + ndat     # stream samples of the first row sample / behind the last
+        starts, bins = self.windows.take(avail)
+        if len(starts):
+            rows = carry.rows(lt.voltages, ndim=2)
+            rel = (starts.astype(np.int64) - base).astype(np.uint64)
+            lt._op("PhaseLockedFilterbank", lambda: lt.plfb.accumulate(rows, nin, rel, bins))
+            time_per_fft = float(lt.plfb_geometry["ndat_fft"]) / lt.out_rate
+            for b in bins:                                            # PhaseLockedFilterbank.C:233-235, window by window
+                lt.hits[b] += 1
+                lt.ndat_total += 1
+                lt.integration_length += time_per_fft
+        nxt = self.windows.next_start()
+        keep = avail - nxt if nxt < avail else 0                      # (< ndat_fft: the window at nxt does not fit)
+        carry.keep_tail(lt.ctx, lt.voltages, ndat, nin - keep, 2)
+        return ndat
+
+    def finish(self, *_exchange):
+        """The integration so far: profile [nchan * nchan_fft][npol][nbin][1] on the host, with the members
+        PhaseLockedFilterbank.C:123-159 sets on its output"""
+        lt = self.lt
+        if not lt.ndat_total:
+            return
+        prof = lt._op("PhaseLockedFilterbank::synch", lambda: lt.plfb.synch())
+        _emit(lt, _books(lt, profile=prof[..., None], **{k: lt.plfb_geometry[k] for k in ("state", "rate", "nsub_swap", "scale")}), lt.plfb.zero)
+
+
+class KurtosisFold:
+    """`dspsr -skz`: the convolving filterbank writes its complex rows, dsp::SpectralKurtosis zeroes what it zaps in place,
+    Detection and Fold follow; the fold counts its hits per channel on the device (Fold::Engine::zeroed_samples with
+    hits_nchan == nchan, LoadToFold1.C:458-532, Fold.C:853-866).  The rows of a block sit behind a head room that holds the
+    carried tail, the < M samples SpectralKurtosis has not consumed yet (InputBuffering, set_next_start(output_ndat):
+    SpectralKurtosis.C:211-217)."""
+
+    detects, fuses = True, False
+    engines = ("fold", "sk")
+    no_exchange = "spectral kurtosis (-skz) is"
+
+    def __init__(self, lt):
+        self.lt = lt
+
+    def plan(self, ntargets, subband, dump_before):
+        tap_check(self.lt.cfg, dump_before)                  # (chan_range is sk_check's: the driver's plan asks it last)
+        self.carry = DelayCarry(head=self.lt.cfg.sk_m - 1)
+
+    def open(self, rows, dump_dir):
+        lt, cfg, info = self.lt, self.lt.cfg, self.lt.info
+        lt.fold = FoldEngine(lt.ctx)
+        self.shape(cfg.nbin)
+        lt.sk = SpectralKurtosisEngine(lt.ctx)
+        lt.sk.set_shape(lt.nchan_out, info.npol, cfg.sk_m)
+        lt.sk.set_options(cfg.sk_std_devs, *self.chan_range, cfg.sk_no_fscr, cfg.sk_no_tscr, cfg.sk_no_ft)
+        lt.voltages = _device_empty(lt.ctx, (lt.nchan_out, info.npol, 2 * (self.carry.head + rows * lt.nkeep)))
+        lt.detected = _device_empty(lt.ctx, (lt.nchan_out, lt.npol_out, (self.carry.head + rows * lt.nkeep) * cfg.ndim))
+
+    def shape(self, nbin):
+        lt = self.lt                   # (hits per channel: uint32 [nchan][nbin] on the device, on the host at a sub-integration)
+        lt.fold.set_shape(lt.nchan_out, lt.npol_out, lt.cfg.ndim, nbin)
+        self.hits_dev = _device_empty(lt.ctx, (lt.nchan_out, nbin), "int32", zero=True)
+        lt.hits = np.zeros((lt.nchan_out, nbin), dtype=np.uint32)
+
+    def process(self, raw, npart, events):
+        """Filterbank -> complex rows behind the carried tail -> SpectralKurtosis over the whole parts of M samples (in place: zeros
+        over what it zaps) -> Detection -> Fold piece by piece, hits counted where the detected sample is not zero; the remainder is
+        carried in front of the next block's rows.  The last < M samples of a run are dropped, as the reference drops them."""
+        lt, cfg, carry, ndat = self.lt, self.lt.cfg, self.carry, npart * self.lt.nkeep
+        nin = carry.carried + ndat
+        lt._filterbank_op("Filterbank", lambda: lt.fb.perform_raw(raw, lt.layout, lt.scale8, carry.new(lt.voltages, 2), npart), events)
+        rows = carry.rows(lt.voltages, ndim=2)
+        nuse = nin // cfg.sk_m * cfg.sk_m
+        if nuse:
+            lt._op("SpectralKurtosis", lambda: lt.sk.transform(rows, rows, nin))
+            det = lt.detected[:, :, :nuse * cfg.ndim]
+            state = _lib.STOKES if cfg.stokes else _lib.COHERENCE
+            lt._op("Detection", lambda: DetectionEngine(lt.ctx).polarimetry(cfg.ndim, rows[:, :, :2 * nuse], det, state))
+            lt._fold_pieces(lt._pieces(nuse), lambda: lt._op("Fold", lambda: lt.fold.fold_zeroed(det, self.hits_dev)))
+        carry.keep_tail(lt.ctx, lt.voltages, ndat, nuse, 2)
+        return nuse
+
+    def plan_piece(self, acc, phi, phase_per_sample, ndat_fold, idat_start):
+        fold = self.lt.fold                                  # (the hits are the device's: the books get the samples only)
+        fold.set_nbin(self.lt.cfg.nbin)
+        fold.set_ndat(ndat_fold, idat_start)
+        fold.set_bins(phi, phase_per_sample, ndat_fold, idat_start, None)
+
+    def finish(self, *_exchange):
+        """The hits come to the host; integration_length = hits.sum() / (rate * nchan), once, from the integer total (Fold.C:893-896)"""
+        lt = self.lt
+        if not lt.ndat_total:
+            return
+        lt.hits = self.hits_dev.cpu().numpy().view(np.uint32)
+        lt.integration_length = float(int(lt.hits.sum(dtype=np.uint64))) / (lt.out_rate * lt.nchan_out)
+        lt.sk_statistics = lt.sk.get_statistics()
+        _emit(lt, _books(lt, profile_dev=lt.profiles_tensor().clone()), lambda: (lt.fold.zero(), self.hits_dev.zero_()))
 
 
 class LoadToFold:
@@ -1274,7 +1642,8 @@ class LoadToFold:
         self.pulsars, self.cyclic, self.plfb, self.rfi_filter = [], None, None, None
         self.sk, self.sk_statistics = None, None
         self.ctx = self.fb = self.fold = self.response = self.sample_delay = self.detected = self.voltages = None
-        self.sd = DelayCarry()              # -K: head room in front of `detected` and the tail carried in it
+        self.sd = DelayCarry()               # -K: head room in front of `detected` and the tail carried in it
+        self.mode = DetectFold(self)        # the back end; _plan chooses the one of the run
         self.fused_mode, self.fused_fold = 0, False
         self.optime = {}                    # record_time: operation name -> [seconds, calls]
         self.dumps, self._dump_cplx = {}, None
@@ -1298,7 +1667,7 @@ class LoadToFold:
         self.moments = fourth_moment_active(cfg)         # -4: the fold is (nchan, 1, 14, nbin), fed by FoldEngine.fold_moments
         cfg = fourth_moment_check(cfg, len(targets), subband)
         if cfg.cyclic_nchan > 0:
-            self._cyclic_geometry = cyclic_check(cfg, info, len(targets), subband, dump_before)
+            cyclic_check(cfg, info, len(targets), subband, dump_before)
         if len(targets) > 1 and subband is not None:
             raise DspsrAmdError("dspsr_amd.LoadToFold: sub-band sharded runs fold one pulsar; %d targets given" % len(targets))
         for t in targets:
@@ -1315,8 +1684,10 @@ class LoadToFold:
             raise DspsrAmdError("dspsr_amd.LoadToFold: subband=%d outside the %d input channels" % (subband, info.nchan))
         if cfg.folding_period <= 0 and polyco is None:
             raise DspsrAmdError("dsp::Fold::fold no polynomial and no period specified")   # Fold.C:638-640
-        convolving = cfg.cyclic_nchan > 0 or cfg.plfb_nbin > 0           # -cyclic and -G read the complex rows of -F N:D
-        if not convolving:
+        # the back end of the run: every later question about the mode is put to it
+        self.mode = (CyclicFold if cfg.cyclic_nchan > 0 else PhaseLockedFold if cfg.plfb_nbin > 0 else KurtosisFold if cfg.sk_zap
+                     else DetectFold)(self)
+        if self.mode.detects:                                            # (-cyclic and -G read the complex rows of -F N:D)
             if info.npol != 2:
                 raise DspsrAmdError("dsp::Detection::polarimetry Cannot detect polarization when npol != 2")
             if cfg.convolve_when not in ("during", "after", "before", "never"):
@@ -1329,25 +1700,14 @@ class LoadToFold:
         self.npol_out = 4 // cfg.ndim
         if cfg.convolve_when != "during":
             self._plan_after(subband, dump_before)
-            if cfg.sk_zap:
-                sk_check(cfg, info, len(targets), subband, dump_before)
-            return
-        # -F N:D: the response inside the filterbank (LoadToFold1.C:318-323; -K: the fractional delays with it, :620-621)
-        self.response = r = matched_response(info, cfg.dispersion_measure, cfg.freq_res, cfg.nchan, input_nchan=info.nchan, ndim=info.ndim,
-                                             fractional_delay=cfg.interchan_dedispersion)
-        self.out_rate, self.out_start, self.scalefac = filterbank_output(info, r, cfg.nchan // info.nchan)
-        if cfg.cyclic_nchan > 0:
-            self.npol_out = self._cyclic_geometry["npol"]
-        elif cfg.plfb_nbin > 0:
-            self._plan_plfb()
         else:
-            self._plan_delays()
-            self._plan_taps(dump_before)
-        if cfg.sk_zap:
-            # -skz: the rows of a block sit behind a head room that holds the carried tail, the < M samples SpectralKurtosis has not
-            # consumed yet (InputBuffering, set_next_start(output_ndat): SpectralKurtosis.C:211-217)
-            self.sk_range = sk_check(cfg, info, len(targets), subband, dump_before)
-            self.sk_head, self.sk_tail = cfg.sk_m - 1, 0
+            # -F N:D: the response inside the filterbank (LoadToFold1.C:318-323; -K: the fractional delays with it, :620-621)
+            self.response = r = matched_response(info, cfg.dispersion_measure, cfg.freq_res, cfg.nchan, input_nchan=info.nchan,
+                                                 ndim=info.ndim, fractional_delay=cfg.interchan_dedispersion)
+            self.out_rate, self.out_start, self.scalefac = filterbank_output(info, r, cfg.nchan // info.nchan)
+        self.mode.plan(len(targets), subband, dump_before)
+        if cfg.sk_zap:                           # after every refusal the run had without -skz (with -cyclic or -G: it refuses)
+            self.mode.chan_range = sk_check(cfg, info, len(targets), subband, dump_before)
 
     def _plan_after(self, subband, dump_before):
         """`dspsr -F N` (Filterbank::Config::After) and the filterbank without coherent dedispersion (Config::Never): the non-convolving
@@ -1382,83 +1742,14 @@ class LoadToFold:
         self.out_start = info.start_seconds + (r.impulse_pos if r is not None else 0) / self.out_rate   # Convolution.C:300
         self.scalefac = float(nsub) * (float(ndat) * float(ndat) if r is not None else 1.0)            # Filterbank.C:124-125, Convolution.C:305
 
-    def _plan_delays(self):
-        """-K: dsp::SampleDelay on the filterbank output.  Detection acts sample by sample, so delaying the detected rows
-        gives the same numbers as delaying the complex rows first (the reference's order) and keeps the fused
-        filterbank+detect launch group.  The last `total_delay` samples of a block are re-presented in front of the
-        next one (InputBuffering, SampleDelay.C:117,146): they live in the head room in front of `detected` (DelayCarry)."""
-        cfg, info = self.cfg, self.info
-        if not cfg.interchan_dedispersion:
-            return
-        dual = info.ndim == 2                              # Observation.C:80-87; Filterbank.C:358-364
-        self._delays = dedispersion_sample_delays(info.centre_frequency, info.bandwidth, cfg.dispersion_measure, cfg.nchan, self.out_rate,
-                                                  swap=dual and info.nchan == 1, nsub_swap=info.nchan if dual and info.nchan > 1 else 0)
-        self.sd = DelayCarry(self._delays)
-        self.out_start += self.sd.zero / self.out_rate                               # SampleDelay.C:159
-
-    def _plan_taps(self, dump_before):
-        """stage capture (dspsr --dump <Operation>, SingleThread.C:315-346): pre_Detection.dump / pre_Fold.dump"""
-        for name in dump_before:
-            if name not in ("Detection", "Fold"):
-                raise DspsrAmdError("dsp::SingleThread::insert_dump_point no operation named '%s' on this path "
-                                    "(Detection, Fold)" % name)
-            if name == "Detection" and self.cfg.interchan_dedispersion:
-                raise DspsrAmdError("dspsr_amd.LoadToFold: the pre_Detection tap is not built for -K (the delay is applied "
-                                    "to the detected rows here); tap pre_Fold instead")
-        self._taps = dump_before
-
-    def _plan_plfb(self):
-        """`dspsr -G nbin`: the convolving filterbank writes its complex rows and dsp::PhaseLockedFilterbank consumes them
-        (LoadToFold1.C:386-456); Detection and Fold are not built.  One integration over the whole stream: the windows are those
-        of ONE transformation call (PlfbPlan), whatever the block size.  The rows of a block sit behind a head room that holds the
-        carried tail -- the samples from the first window that does not fit yet -- so that a window may span two blocks.
-        PhaseLockedFilterbank::prepare (:59-83), all on the host."""
-        cfg, info = self.cfg, self.info
-        period, polyco, reference_phase = self._ephemeris()
-        if period <= 0:
-            period = 1.0 / polyco.frequency(info.mjd_day, info.mjd_sec + self.out_start)
-        nmax = plfb_choose_nchan(period, self.out_rate, cfg.plfb_nbin)
-        nchan = cfg.plfb_nchan if cfg.plfb_nchan >= 2 else nmax
-        if nchan > nmax:
-            import warnings
-            warnings.warn("dsp::PhaseLockedFilterbank::prepare warning selected nchan=%d > suggested max=%d" % (nchan, nmax))
-        plfb_check_shape(cfg.nchan, info.npol, 2, nchan, cfg.npol, cfg.plfb_nbin)       # the rows are Analytic: ndat_fft = nchan
-        state = {1: "Intensity", 2: "PPQQ", 4: "Coherence"}[cfg.npol]                  # :128-133
-        self.plfb_geometry = {"nchan_fft": nchan, "ndat_fft": nchan, "nchan": cfg.nchan * nchan, "npol": cfg.npol, "ndim": 1,
-                              "nbin": cfg.plfb_nbin, "state": state, "rate": self.out_rate / nchan, "nsub_swap": cfg.nchan,
-                              "scale": self.scalefac * nchan}                          # :143-149
-        self.npol_out = cfg.npol
-        self.plfb_plan = PlfbPlan(self._turns_divider(*self._ephemeris(), turns=1.0 / cfg.plfb_nbin), cfg.plfb_nbin, reference_phase,
-                                  nchan)
-        self.plfb_head, self.plfb_tail = nchan, 0           # head room (samples) in front of a block's rows; samples carried in it
-
     def _open(self, device, stream, dump_dir):
-        """The device side of the constructor: the context, the front end, the fold of the mode, the block the two share."""
-        cfg, info = self.cfg, self.info
+        """The device side of the constructor: the context, the front end, then what the back end opens -- the fold of the mode,
+        the block the two share."""
+        cfg, info, r = self.cfg, self.info, self.response
         self.ctx = Context(device, stream)
-        r, nsub, rows = self.response, cfg.nchan // info.nchan, cfg.parts_per_block
-        fused = _lib.FUSED_NEVER if not cfg.fused_fold else _lib.FUSED_ALWAYS if cfg.force_fused else _lib.FUSED_AUTO
+        nsub, rows = cfg.nchan // info.nchan, cfg.parts_per_block
         setup = dict(max_parts=cfg.max_parts, force_four_pass=0 if cfg.two_pass else 2, fuse_heaps=cfg.fuse_heaps)
-        if cfg.cyclic_nchan > 0:
-            # `dspsr -cyclic N`: the convolving filterbank writes its complex rows, dsp::CyclicFold folds their lag products
-            # (LoadToFold1.C:534-539,999-1044); Detection and Fold are not built.  At a sub-integration the lag data come to the
-            # host and CyclicFoldEngine::synch turns them into spectra (once per sub-integration: host, as in the reference).
-            g = self._cyclic_geometry
-            _open_convolving_front(self, r, nsub, info.nchan, r.kernel, fused_fold=_lib.FUSED_NEVER, **setup)
-            self.cyclic = CyclicFoldEngine(self.ctx)
-            self.cyclic.set_shape(self.nchan_out, info.npol, g["npol"], g["nlag"], g["mover"], cfg.nbin)
-            self.voltages = _device_empty(self.ctx, (self.nchan_out, info.npol, 2 * rows * self.nkeep))
-            self.hits = np.zeros(cfg.nbin, dtype=np.uint32)
-            return
-        if cfg.plfb_nbin > 0:
-            _open_convolving_front(self, r, nsub, info.nchan, r.kernel, fused_fold=_lib.FUSED_NEVER, **setup)
-            self.plfb = PhaseLockedFilterbankEngine(self.ctx)
-            self.plfb.set_shape(cfg.nchan, info.npol, 2, self.plfb_geometry["nchan_fft"], cfg.npol, cfg.plfb_nbin)
-            self.voltages = _device_empty(self.ctx, (self.nchan_out, info.npol, 2 * (self.plfb_head + rows * self.nkeep)))
-            self.hits = np.zeros(cfg.plfb_nbin, dtype=np.uint32)
-            return
-        if cfg.sk_zap:
-            return self._open_sk(r, nsub, rows, setup)
+        fused = _lib.FUSED_NEVER if not (cfg.fused_fold and self.mode.fuses) else _lib.FUSED_ALWAYS if cfg.force_fused else _lib.FUSED_AUTO
         if cfg.convolve_when == "during":
             # -pac: chirp x Jones per bin as a matrix response instead of the chirp (calibrator_response)
             matrix = self._calibrated[1] if self._calibrated else None
@@ -1472,111 +1763,7 @@ class LoadToFold:
         else:
             _adopt_front(self, FilterbankThenConvolution(self.ctx, nsub, info.nchan, info.npol, info.ndim == 1, r, max_parts=cfg.max_parts,
                                                          parts_per_block=rows, fused_fold=fused))
-        self.fold = FoldEngine(self.ctx)
-        self.fold.set_shape(self.nchan_out, *self._fold_dims(), cfg.nbin)
-        if cfg.interchan_dedispersion:
-            if self.subband is None:
-                self.sample_delay = SampleDelay(self.ctx, self._delays, self.npol_out)
-            else:
-                # a sub-band rank applies ITS channels' delays relative to the zero of the WHOLE band and gives up the
-                # whole band's total delay per block, so that every rank emits the same samples with the same start time
-                # (SampleDelay.C:75-99 on the full band; the rank's slice goes in as absolute delays)
-                applied = self.sd.zero - np.asarray(self._delays, np.int64)
-                self.sample_delay = SampleDelay(self.ctx, applied[self.subband * nsub:(self.subband + 1) * nsub], self.npol_out, absolute=True)
-                self.sd.short = self.sd.head - self.sample_delay.total_delay       # samples this rank must NOT emit
-            self.sd.check_block("LoadToFold", rows * self.nkeep)
-        self.detected = _device_empty(self.ctx, (self.nchan_out, self.npol_out, (self.sd.head + rows * self.nkeep) * cfg.ndim))
-        # fused filterbank+detect+fold (no detected time series in HBM): ndim 4, three-pass geometries
-        # (the library decides whether fusing pays for this geometry; when it does not, this driver keeps the
-        # separate Detection and Fold operations on its own `detected` block; -F N:B never fuses)
-        if cfg.fused_fold and cfg.ndim == 4 and self.sample_delay is None and cfg.convolve_when != "before":
-            self.fused_mode = self.fb.fold_is_fused()
-        self.fused_fold = self.fused_mode != 0      # fused_mode 2: sums re-associated per run of parts (engine.fold_is_fused)
-        for name in self._taps:
-            from . import dada
-            chbw = info.bandwidth / info.nchan
-            sub = self.subband
-            fc = info.centre_frequency if sub is None else info.centre_frequency - 0.5 * info.bandwidth + (sub + 0.5) * chbw
-            bw = info.bandwidth if sub is None else chbw
-            det = name == "Fold"
-            path = os.path.join(dump_dir, "pre_%s%s.dump" % (name, "" if sub is None else ".%d" % sub))
-            fold_npol, fold_ndim = self._fold_dims()        # -4: the input of Fold is the FourthMoment stream
-            self.dumps[name] = dada.Dump(
-                path, centre_frequency=fc, bandwidth=bw, nchan=self.nchan_out, npol=fold_npol if det else 2,
-                ndim=fold_ndim if det else 2, nbit=32, rate=self.out_rate, mjd_day=info.mjd_day,
-                mjd_sec=info.mjd_sec + self.out_start,
-                state=("FourthMoment" if self.moments else "Stokes" if cfg.stokes else "Coherence") if det else "Analytic",
-                source=getattr(info, "source", "unknown"), telescope=getattr(info, "telescope", "unknown"))
-        if "Fold" in self.dumps:
-            self.fused_mode, self.fused_fold = 0, False          # the detected samples must exist in HBM to be dumped
-        self.hits = np.zeros(cfg.nbin, dtype=np.uint32)
-
-    def _open_sk(self, r, nsub, rows, setup):
-        """`dspsr -skz`: the convolving filterbank writes its complex rows, dsp::SpectralKurtosis zeroes what it zaps in place,
-        Detection and Fold follow; the fold counts its hits per channel on the device (Fold::Engine::zeroed_samples with
-        hits_nchan == nchan, LoadToFold1.C:458-532, Fold.C:853-866)."""
-        cfg, info = self.cfg, self.info
-        matrix = self._calibrated[1] if self._calibrated else None
-        _open_convolving_front(self, r, nsub, self.in_nchan, None if matrix is not None else r.kernel, fused_fold=_lib.FUSED_NEVER,
-                               response_matrix=matrix, **setup)
-        self.fold = FoldEngine(self.ctx)
-        self.fold.set_shape(self.nchan_out, self.npol_out, cfg.ndim, cfg.nbin)
-        self.sk = SpectralKurtosisEngine(self.ctx)
-        self.sk.set_shape(self.nchan_out, info.npol, cfg.sk_m)
-        self.sk.set_options(cfg.sk_std_devs, *self.sk_range, cfg.sk_no_fscr, cfg.sk_no_tscr, cfg.sk_no_ft)
-        self.voltages = _device_empty(self.ctx, (self.nchan_out, info.npol, 2 * (self.sk_head + rows * self.nkeep)))
-        self.detected = _device_empty(self.ctx, (self.nchan_out, self.npol_out, (self.sk_head + rows * self.nkeep) * cfg.ndim))
-        self._sk_books(cfg.nbin)
-
-    def _sk_books(self, nbin):
-        """hits per channel: uint32 [nchan][nbin] on the device, on the host at finish_subint"""
-        self.hits_dev = _device_empty(self.ctx, (self.nchan_out, nbin), "int32", zero=True)
-        self.hits = np.zeros((self.nchan_out, nbin), dtype=np.uint32)
-
-    def _process_block_sk(self, raw, npart, events):
-        """Filterbank -> complex rows behind the carried tail -> SpectralKurtosis over the whole parts of M samples (in place: zeros
-        over what it zaps) -> Detection -> Fold piece by piece, hits counted where the detected sample is not zero; the remainder is
-        carried in front of the next block's rows.  The last < M samples of a run are dropped, as the reference drops them."""
-        cfg = self.cfg
-        M, head, tail, ndat = cfg.sk_m, self.sk_head, self.sk_tail, npart * self.nkeep
-        self._filterbank_op("Filterbank", lambda: self.fb.perform_raw(raw, self.layout, self.scale8, self.voltages[:, :, 2 * head:], npart),
-                            events)
-        rows = self.voltages[:, :, 2 * (head - tail):]
-        nuse = (tail + ndat) // M * M
-        if nuse:
-            self._op("SpectralKurtosis", lambda: self.sk.transform(rows, rows, tail + ndat))
-            det = self.detected[:, :, :nuse * cfg.ndim]
-            state = _lib.STOKES if cfg.stokes else _lib.COHERENCE
-            self._op("Detection", lambda: DetectionEngine(self.ctx).polarimetry(cfg.ndim, rows[:, :, :2 * nuse], det, state))
-            for idat_start, ndat_fold, _division, complete in self._pieces(nuse):
-                t0 = self.out_start + (self.ndat_out + idat_start + 0.5) / self.out_rate
-                phi, pfold = self._phase(t0)
-                self.fold.set_nbin(cfg.nbin)
-                self.fold.set_ndat(ndat_fold, idat_start)
-                self.fold.set_bins(phi, (1.0 / self.out_rate) / pfold, ndat_fold, idat_start, None)     # (the hits are the device's)
-                self._op("Fold", lambda: self.fold.fold_zeroed(det, self.hits_dev))
-                self.ndat_total += ndat_fold
-                if complete:
-                    self.finish_subint()
-        keep = tail + ndat - nuse
-        if keep:                                                     # (ndat samples forward: never onto itself)
-            move_tail_fpt(self.ctx, self.voltages, head - keep, head - tail + nuse, keep, unit=2)
-        self.sk_tail = keep
-        self.ndat_out += nuse
-        self.nsamples_in += npart * self.nsamp_step
-
-    def _finish_sk_subint(self):
-        """The hits come to the host; integration_length = hits.sum() / (rate * nchan), once, from the integer total (Fold.C:893-896)"""
-        if not self.ndat_total:
-            return
-        self.hits = self.hits_dev.cpu().numpy().view(np.uint32)
-        self.integration_length = float(int(self.hits.sum(dtype=np.uint64))) / (self.out_rate * self.nchan_out)
-        self.sk_statistics = self.sk.get_statistics()
-
-        def zero():
-            self.fold.zero()
-            self.hits_dev.zero_()
-        _emit(self, _books(self, profile_dev=self.profiles_tensor().clone()), zero)
+        self.mode.open(rows, dump_dir)
 
     def _filterbank_op(self, name, fn, events):
         """The filterbank step of a block as an operation, between the caller's two HIP events (bench.py's roofline brackets the
@@ -1587,99 +1774,26 @@ class LoadToFold:
         if events is not None:
             events[1].record()
 
-    def _process_block_cyclic(self, raw, npart, events):
-        """Filterbank -> complex rows -> CyclicFold piece by piece (Subint<CyclicFold>).  Lag products never span two fold
-        calls (CyclicFold.C:390: idat < ndat_fold - nlag), so the last nlag samples of every piece add nothing."""
-        ndat = npart * self.nkeep
-        self._filterbank_op("Filterbank", lambda: self.fb.perform_raw(raw, self.layout, self.scale8, self.voltages, npart), events)
-        for idat_start, ndat_fold, _division, complete in self._pieces(ndat):
-            t0 = self.out_start + (self.ndat_out + idat_start + 0.5) / self.out_rate
-            phi, pfold = self._phase(t0)
-            self.cyclic.set_ndat(ndat_fold, idat_start)
-            folded = self.cyclic.set_bins(phi, (1.0 / self.out_rate) / pfold, ndat_fold, idat_start, self.hits)
-            self._op("CyclicFold", lambda: self.cyclic.fold(self.voltages))
-            _accumulate(self, folded, ndat_fold, self.out_rate)
-            if complete:
-                self.finish_subint()
-        self.ndat_out += ndat
-        self.nsamples_in += npart * self.nsamp_step
-
-    def _finish_cyclic_subint(self):
-        """CyclicFoldEngine::synch (CyclicFold.C:450-555): spectra [nchan * nchan_spec / mover][npol][nbin][1] on the host"""
-        if not self.ndat_total:                              # nothing folded since the last one (as the multi-pulsar branch)
-            return
-        spectra = self._op("CyclicFold::synch", lambda: self.cyclic.synch())
-        _emit(self, _books(self, profile=spectra[..., None]), self.cyclic.zero)
-
-    def _process_block_plfb(self, raw, npart, events):
-        """Filterbank -> complex rows behind the carried tail -> every window of the plan that now lies inside the rows, in one
-        accumulate call; then the samples from the next window's start on are carried in front of the next block's rows."""
-        ndat, head, tail = npart * self.nkeep, self.plfb_head, self.plfb_tail
-        self._filterbank_op("Filterbank", lambda: self.fb.perform_raw(raw, self.layout, self.scale8, self.voltages[:, :, 2 * head:], npart),
-                            events)
-        base, avail = self.ndat_out - tail, self.ndat_out + ndat     # stream samples of the first row sample / behind the last
-        starts, bins = self.plfb_plan.take(avail)
-        if len(starts):
-            rows = self.voltages[:, :, 2 * (head - tail):]
-            rel = (starts.astype(np.int64) - base).astype(np.uint64)
-            self._op("PhaseLockedFilterbank", lambda: self.plfb.accumulate(rows, tail + ndat, rel, bins))
-            time_per_fft = float(self.plfb_geometry["ndat_fft"]) / self.out_rate
-            for b in bins:                                            # PhaseLockedFilterbank.C:233-235, window by window
-                self.hits[b] += 1
-                self.ndat_total += 1
-                self.integration_length += time_per_fft
-        nxt = self.plfb_plan.next_start()
-        keep = avail - nxt if nxt < avail else 0                      # (< ndat_fft: the window at nxt does not fit)
-        if keep:
-            move_tail_fpt(self.ctx, self.voltages, head - keep, head + ndat - keep, keep, unit=2)
-        self.plfb_tail = keep
-        self.ndat_out += ndat
-        self.nsamples_in += npart * self.nsamp_step
-
-    def _finish_plfb_subint(self):
-        """The integration so far: profile [nchan * nchan_fft][npol][nbin][1] on the host, with the members
-        PhaseLockedFilterbank.C:123-159 sets on its output"""
-        if not self.ndat_total:
-            return
-        g = self.plfb_geometry
-        prof = self._op("PhaseLockedFilterbank::synch", lambda: self.plfb.synch())
-        _emit(self, _books(self, profile=prof[..., None], state=g["state"], rate=g["rate"], nsub_swap=g["nsub_swap"], scale=g["scale"]),
-              self.plfb.zero)
-
     def _init_targets(self, targets):
         """nbin per target (Fold::choose_nbin for its period where the target gives none); several targets: one FoldEngine each,
         the fused fold off (the detected rows are shared)."""
-        cfg, info = self.cfg, self.info
-        if self.plfb is not None:                        # -G: the phase bins are plfb_nbin; -b plays no part
+        if self.mode.shape is None:
             return
         nbins = []
         for t in targets:
-            p = t.folding_period if t.polyco is None else 1.0 / t.polyco.frequency(info.mjd_day, info.mjd_sec + self.out_start)
+            p = t.folding_period if t.polyco is None else 1.0 / t.polyco.frequency(self.info.mjd_day, self.info.mjd_sec + self.out_start)
             nbins.append(t.nbin or choose_nbin(p, self.out_rate))
         if len(targets) == 1:
-            if nbins[0] != cfg.nbin:
-                self.cfg = dataclasses.replace(cfg, nbin=nbins[0])
-                if self.cyclic is not None:
-                    g = self._cyclic_geometry
-                    self.cyclic.set_shape(self.nchan_out, info.npol, g["npol"], g["nlag"], g["mover"], nbins[0])
-                else:
-                    self.fold.set_shape(self.nchan_out, *self._fold_dims(), nbins[0])
-                self.hits = np.zeros(nbins[0], dtype=np.uint32)
-                if self.cfg.sk_zap:
-                    self._sk_books(nbins[0])
+            if nbins[0] != self.cfg.nbin:
+                self.cfg = dataclasses.replace(self.cfg, nbin=nbins[0])
+                self.mode.shape(nbins[0])
             return
         self.fused_mode, self.fused_fold = 0, False
         self.fold.close()
         self.fold = None
         for t, nbin in zip(targets, nbins):
             self.pulsars.append(_PulsarFold(t, nbin, FoldEngine(self.ctx)))      # (listed first: close() finds it if set_shape raises)
-            self.pulsars[-1].fold.set_shape(self.nchan_out, self.npol_out, cfg.ndim, nbin)
-
-    def _response_engine(self):
-        """the engine that holds the dedispersion response: the convolving filterbank (-F N:D), or the Convolution of -F N / -F N:B"""
-        if self.cyclic is not None or self.plfb is not None:
-            return self.fb
-        return self.fb if self.cfg.convolve_when == "during" else self.fb.conv
+            self.pulsars[-1].fold.set_shape(self.nchan_out, self.npol_out, self.cfg.ndim, nbin)
 
     def set_rfi_filter(self, filt):
         """`dspsr -R`: multiply the filter's mask into the dedispersion kernel (ResponseProduct, LoadToFold1.C:248-266) and hand the
@@ -1687,8 +1801,8 @@ class LoadToFold:
         (calculated here if it has not been), or None to restore the dedispersion kernel alone.  The reference matches the
         response once (Filterbank.C:84, Convolution.C:115): call this once, before the first block."""
         rfi_check(self.cfg, self.info, self.subband)
-        r = getattr(self, "response", None)
-        eng = self._response_engine()
+        # the engine that holds the response: the convolving filterbank (-F N:D, every back end), or the Convolution of -F N / -F N:B
+        r, eng = self.response, self.fb if self.cfg.convolve_when == "during" else self.fb.conv
         if r is None or eng is None:
             raise DspsrAmdError("dspsr_amd.LoadToFold: the RFI filter (-R) needs a dedispersion kernel to multiply into")
         kernel = r.kernel if filt is None else filt.product(r.kernel, r.kernel.size // r.ndat, r.ndat)
@@ -1699,26 +1813,6 @@ class LoadToFold:
     def _fold_dims(self):
         """(npol, ndim) of the folded PhaseSeries: those of the detected rows, or 1 x 14 for -4 (FourthMoment.C:39-42)"""
         return (1, 14) if self.moments else (self.npol_out, self.cfg.ndim)
-
-    def _fold_rows(self, rows):
-        """Fold::fold of the pending plan over detected rows.  -4: the Stokes rows go to the moments fold, which forms the products
-        in registers; with a pre_Fold tap the 14-float stream dsp::FourthMoment would write exists (`_moment_stream`) and is
-        folded as it is -- the same bits either way."""
-        if not self.moments:
-            return self.fold.fold(rows)
-        if self._moment_rows is not None:
-            return self.fold.fold(self._moment_rows)
-        return self.fold.fold_moments(rows)
-
-    def _moment_stream(self, rows, ndat):
-        """dsp::FourthMoment on the first `ndat` samples of the Stokes rows (pre_Fold tap of a -4 run): [nchan][1][ndat*14]"""
-        need = self.nchan_out * 14 * (self.sd_head + self.cfg.parts_per_block * self.nkeep)
-        if self._moment_buf is None or self._moment_buf.numel() < need:
-            self._moment_buf = _device_empty(self.ctx, need)
-        out = self._moment_buf[:self.nchan_out * 14 * ndat].view(self.nchan_out, 1, 14 * ndat)
-        self._op("FourthMoment", lambda: fourth_moment(self.ctx, rows, out, ndat))
-        self._moment_rows = out
-        return out
 
     def _op(self, name, fn):
         """Operation::operate with record_time (Operation.C:90-113): wall time of the operation including its stream
@@ -1801,77 +1895,37 @@ class LoadToFold:
         if cfg.zap_rfi and self.rfi_filter is None:
             raise DspsrAmdError("dspsr_amd.LoadToFold.process_block: zap_rfi (-R) is set and no filter has been given: "
                                 "call set_rfi_filter before the first block")
-        if self.cyclic is not None:
-            return self._process_block_cyclic(raw, npart, events)
-        if self.plfb is not None:
-            return self._process_block_plfb(raw, npart, events)
-        if cfg.sk_zap:
-            return self._process_block_sk(raw, npart, events)
-        ndat = npart * self.nkeep
-        state = _lib.STOKES if cfg.stokes else _lib.COHERENCE
-        if "Detection" in self.dumps:                        # the filterbank's complex output: one extra pass, taps only
-            if self._dump_cplx is None:
-                self._dump_cplx = _device_empty(self.ctx, (self.nchan_out, 2, 2 * cfg.parts_per_block * self.nkeep))
-            self.fb.perform_raw(raw, self.layout, self.scale8, self._dump_cplx, npart)
-            self.dumps["Detection"].write(self._dump_cplx, ndat, 2)
-        if self.sample_delay is not None:
-            return self._process_block_interchan(raw, npart, ndat, state, events)
-        # Subint<Fold>::transformation: fold piece by piece, emitting a sub-integration at every boundary
-        pieces = None if self.pulsars else self._pieces(ndat)
-        if self.fused_fold and len(pieces) == 1 and pieces[0][:2] == (0, ndat):
-            # one fold call covers the block: filterbank, detection and fold in one launch group.  Same sums in the
-            # same order as the unfused chain below (blocks holding a sub-integration boundary take that chain).
-            idat_start, ndat_fold, _division, complete = pieces[0]
-            folded = self._set_plan(idat_start, ndat_fold)
-            self._filterbank_op("Filterbank+Detection+Fold", lambda: self.fb.perform_fold(self.fold, npart, state, raw=raw, layout=self.layout,
-                                                                                       scale=self.scale8), events)
-            _accumulate(self, folded, ndat_fold, self.out_rate)
-            if complete:
-                self.finish_subint(*self._subint_comm)
-            self.ndat_out += ndat
-            self.nsamples_in += npart * self.nsamp_step
-            return
-        self._filterbank_op("Filterbank+Detection", lambda: self.fb.perform_detect(self.detected, npart, state, cfg.ndim, raw=raw,
-                                                                                   layout=self.layout, scale=self.scale8), events)
-        if "Fold" in self.dumps:
-            if self.moments:
-                self.dumps["Fold"].write(self._moment_stream(self.detected, ndat), ndat, 14)
-            else:
-                self.dumps["Fold"].write(self.detected, ndat, cfg.ndim)
-        if self.pulsars:
-            self._fold_pulsars(self.detected, ndat)
-        for idat_start, ndat_fold, _division, complete in pieces or ():
-            self._fold_piece(idat_start, ndat_fold)
-            if complete:
-                self.finish_subint(*self._subint_comm)
-        self.ndat_out += ndat
-        self.nsamples_in += npart * self.nsamp_step
-
-    def _process_block_interchan(self, raw, npart, ndat, state, events):
-        """-K chain: filterbank+detect -> SampleDelay (in place, LoadToFold1.C:617-618) -> fold."""
-        nd, sd = self.cfg.ndim, self.sd
-        self._filterbank_op("Filterbank+Detection", lambda: self.fb.perform_detect(self.detected[:, :, sd.head * nd:], npart, state, nd, raw=raw,
-                                                                                   layout=self.layout, scale=self.scale8), events)
-        rows = sd.rows(self.detected, ndat, nd)     # (sub-band rank: the band's total delay, not just this rank's, is given up)
-        nuse = rows.shape[2] // nd
-        nout = self._op("SampleDelay", lambda: self.sample_delay.transform(rows.unflatten(2, (nuse, nd)))) if nuse else 0
-        if nout and "Fold" in self.dumps:
-            if self.moments:
-                self.dumps["Fold"].write(self._moment_stream(rows, nout), nout, 14)
-            else:
-                self.dumps["Fold"].write(rows, nout, nd)
-        if nout and self.pulsars:
-            self._fold_pulsars(rows, nout)
-        elif nout:
-            for idat_start, ndat_fold, _division, complete in self._pieces(nout):
-                folded = self._set_plan(idat_start, ndat_fold)
-                self._op("Fold", lambda: self._fold_rows(rows))
-                _accumulate(self, folded, ndat_fold, self.out_rate)
-                if complete:
-                    self.finish_subint(*self._subint_comm)
-        sd.keep_tail(self.ctx, self.detected, ndat, nout, nd)
+        nout = self.mode.process(raw, npart, events)              # (the pieces were planned from ndat_out as it was)
         self.ndat_out += nout
         self.nsamples_in += npart * self.nsamp_step
+
+    def _plan_piece(self, piece, pulsar=None):
+        """The host plan of Fold::fold (Fold.C:650-657,718-787) for one piece: the phase of its first sample, then the back end's
+        bins.  Returns the samples the plan folds (None where the device counts them)."""
+        idat_start, ndat_fold = piece[:2]
+        t0 = self.out_start + (self.ndat_out + idat_start + 0.5) / self.out_rate     # midpoint of first sample
+        phi, pfold = self._phase(t0, pulsar)
+        return self.mode.plan_piece(pulsar or self, phi, (1.0 / self.out_rate) / pfold, ndat_fold, idat_start)
+
+    def _book_piece(self, piece, folded, pulsar=None):
+        """The books of a folded piece, on the driver or on `pulsar` (hits[] were counted by the plan, Fold.C:744-803); where the
+        piece completes its division, the sub-integration"""
+        acc = pulsar or self
+        if folded is not None:                     # (None: the device counts the hits, the length comes from them)
+            acc.integration_length += folded / self.out_rate
+        acc.ndat_total += piece[1]
+        if piece[3] and pulsar is None:
+            self.finish_subint(*self._subint_comm)
+        elif piece[3]:
+            self._finish_pulsar_subint(pulsar)
+
+    def _fold_pieces(self, pieces, fold, pulsar=None):
+        """Subint<Fold>::transformation (Subint.h:234-309): plan, fold (the back end's call over its rows) and book piece by piece,
+        emitting a sub-integration at every boundary"""
+        for piece in pieces:
+            folded = self._plan_piece(piece, pulsar)
+            fold()
+            self._book_piece(piece, folded, pulsar)
 
     def _pieces(self, ndat, pulsar=None):
         """Subint<Fold>::transformation (Subint.h:234-309): the pieces of the next `ndat` output samples, one per
@@ -1908,66 +1962,20 @@ class LoadToFold:
     _subint_comm = (None, 0, 1, None)     # (dist, rank, world, gather_buffer[, replicas]) used at sub-integration dumps
 
     def set_communicator(self, dist, rank, world, gather_buffer=None, replicas=False):
-        self._single_pulsar_only("set_communicator")
-        self._no_cyclic("set_communicator")
+        self._refuse_exchange("set_communicator")
         self._subint_comm = (dist, rank, world, gather_buffer, replicas)
 
-    def _no_cyclic(self, what):
-        if self.plfb is not None:
-            raise DspsrAmdError("dspsr_amd.LoadToFold.%s: the phase-locked filterbank is not built for a multi-GPU exchange" % what)
-        if self.cyclic is not None:
-            raise DspsrAmdError("dspsr_amd.LoadToFold.%s: cyclic spectra are not built for a multi-GPU exchange" % what)
-        if self.moments:
-            raise DspsrAmdError("dspsr_amd.LoadToFold.%s: fourth_moment (-4) is not built for a multi-GPU exchange" % what)
-        if self.cfg.sk_zap:
-            raise DspsrAmdError("dspsr_amd.LoadToFold.%s: spectral kurtosis (-skz) is not built for a multi-GPU exchange" % what)
-
-    def _single_pulsar_only(self, what):
+    def _refuse_exchange(self, what):
+        """what a multi-GPU exchange refuses: several pulsars first (asked of a bare instance too), then the back end's own words"""
         if self.pulsars:
             raise DspsrAmdError("dspsr_amd.LoadToFold.%s: the multi-GPU exchange folds one pulsar; this run has %d targets"
                                 % (what, len(self.pulsars)))
-
-    def _set_plan(self, idat_start, ndat_fold, pulsar=None):
-        """The host plan loop of Fold::fold (Fold.C:650-657,718-787): phase of the first sample, then the bins."""
-        fold, nbin, hits = (self.fold, self.cfg.nbin, self.hits) if pulsar is None else (pulsar.fold, pulsar.nbin, pulsar.hits)
-        t0 = self.out_start + (self.ndat_out + idat_start + 0.5) / self.out_rate     # midpoint of first sample
-        phi, pfold = self._phase(t0, pulsar)
-        fold.set_nbin(nbin)
-        fold.set_ndat(ndat_fold, idat_start)
-        return fold.set_bins(phi, (1.0 / self.out_rate) / pfold, ndat_fold, idat_start, hits)
-
-    def _fold_pulsars(self, rows, ndat):
-        """Several pulsars over the same detected rows.  The pulsars whose share of the block is one piece of a sub-integration
-        fold together (FoldEngine.fold_many: the rows are read once for all of them); a pulsar with a sub-integration boundary
-        inside the block folds piece by piece and emits its sub-integration in between, as _fold_piece does."""
-        pieces = [self._pieces(ndat, p) for p in self.pulsars]
-        group = [(p, pc[0]) for p, pc in zip(self.pulsars, pieces) if len(pc) == 1]
-        folded = [self._set_plan(pc[0], pc[1], p) for p, pc in group]
-        if group:
-            self._op("Fold", lambda: FoldEngine.fold_many([p.fold for p, _ in group], rows))
-        for (p, (_, ndat_fold, _division, complete)), n in zip(group, folded):
-            _accumulate(p, n, ndat_fold, self.out_rate)
-            if complete:
-                self._finish_pulsar_subint(p)
-        for p, pc in zip(self.pulsars, pieces):
-            if len(pc) < 2:
-                continue
-            for idat_start, ndat_fold, _division, complete in pc:
-                n = self._set_plan(idat_start, ndat_fold, p)
-                self._op("Fold", lambda: p.fold.fold(rows))
-                _accumulate(p, n, ndat_fold, self.out_rate)
-                if complete:
-                    self._finish_pulsar_subint(p)
+        if self.mode.no_exchange:
+            raise DspsrAmdError("dspsr_amd.LoadToFold.%s: %s not built for a multi-GPU exchange" % (what, self.mode.no_exchange))
 
     def _finish_pulsar_subint(self, p):
         """Subint<Fold> of one pulsar of a multi-target run: emit its sub-integration and zero its profile."""
         _emit(p, _books(p, profile_dev=self.profiles_tensor(p).clone()), p.fold.zero)
-
-    def _fold_piece(self, idat_start, ndat_fold):
-        """Fold::fold (Fold.C:650-657,718-803) on detected[idat_start : idat_start+ndat_fold]."""
-        folded = self._set_plan(idat_start, ndat_fold)
-        self._op("Fold", lambda: self._fold_rows(self.detected))                 # (no head room without -K)
-        _accumulate(self, folded, ndat_fold, self.out_rate)
 
     def profiles_tensor(self, pulsar=None):
         """Zero-copy torch view of the device-resident PhaseSeries (Fold::Engine::get_profiles); `pulsar`: one of a multi-target run."""
@@ -1992,8 +2000,7 @@ class LoadToFold:
         """The exchange of a multi-GPU run: a dspsr_amd.Communicator (dspsr_amd_comm_*, csrc/comm.hip -- the same C entry
         points DSPSR's host calls).  Without one, finish_subint falls back to the torch.distributed calls below, which
         exist for the gloo CPU tests and for rehearsing several ranks on one device (RCCL needs one GPU per rank)."""
-        self._single_pulsar_only("set_rccl_communicator")
-        self._no_cyclic("set_rccl_communicator")
+        self._refuse_exchange("set_rccl_communicator")
         self.comm = comm
 
     def collect_subint(self, copy=None):
@@ -2024,17 +2031,10 @@ class LoadToFold:
         check_hits (default True) adds a MIN/MAX all-reduce of hits[] to the sub-band exchange (two small collectives in the
         same group; nothing for replicas): pass False inside a timed loop that has checked once.
         A multi-target run (one GPU) emits the open sub-integration of every pulsar that has folded samples since its last one."""
-        if self.pulsars:
-            for p in self.pulsars:
-                if p.ndat_total:
-                    self._finish_pulsar_subint(p)
-            return
-        if self.cyclic is not None:
-            return self._finish_cyclic_subint()
-        if self.plfb is not None:
-            return self._finish_plfb_subint()
-        if self.cfg.sk_zap:
-            return self._finish_sk_subint()
+        self.mode.finish(dist, rank, world, gather_buffer, replicas, check_hits, wait)
+
+    def _exchange_subint(self, dist, rank, world, gather_buffer, replicas, check_hits, wait):
+        """finish_subint of a single pulsar's Detection + Fold: the sub-integration goes through the exchange of the run"""
         if self.comm is not None:
             # (one exchange in flight per communicator.  The result of the previous one is COPIED here even with
             #  copy_subints False: start() below may grow the pinned buffer a view would point into -- a view is only handed
@@ -2137,8 +2137,7 @@ class LoadToFold:
         self._closed = True
         if self._comm_pending is not None:
             self.collect_subint()
-        _close_all(*self.dumps.values(), self.sample_delay, self.fb, self.fold, self.cyclic, self.plfb, self.sk, *(p.fold for p in self.pulsars),
-                   self.ctx)
+        _close_all(*self.dumps.values(), self.sample_delay, self.fb, *(getattr(self, e) for e in self.mode.engines), *(p.fold for p in self.pulsars), self.ctx)
 
 
 # ---- search mode: digifil (Signal/General/LoadToFil.C) ------------------------------------------------------------

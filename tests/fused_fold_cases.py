@@ -442,7 +442,7 @@ def model_of_call(cfg, det, runs, profile, parts, ncu):
 
 def loadtofold_block_model(lt, raw, npart, profile, ncu):
     """(mode, hits, model) of the block pipeline.LoadToFold `lt` is about to fold with process_block(raw, npart), its fold being
-    one fused call over the whole block: the plan as LoadToFold._set_plan makes it, the detected samples from perform_detect of
+    one fused call over the whole block: the plan as LoadToFold._plan_piece makes it, the detected samples from perform_detect of
     the pipeline's own filterbank object on the same block.  Call it BEFORE process_block.  The phase of the first sample is
     the pipeline's own (lt._phase, out_start, ndat_out): this checks the ORDER of the sums, not the phase law -- that stays with
     the callers' hits comparison against Detection + Fold.  (The one place of this module that

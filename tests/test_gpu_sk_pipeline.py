@@ -1,4 +1,4 @@
-"""`dspsr -skz` through LoadToFold (dspsr_amd/pipeline.py: _process_block_sk) on a 16-channel, 8-bit, dual-polarisation synthetic
+"""`dspsr -skz` through LoadToFold (dspsr_amd/pipeline.py: KurtosisFold) on a 16-channel, 8-bit, dual-polarisation synthetic
 observation: Gaussian noise, a weak pulse, and in one channel a tone that is on for one eighth of every 128 output samples.
 The driver against the same steps made by hand through the public engines, bit for bit; the cleaned rows against the mask; the
 restatement (tests/sk_reference.py) on the device's voltages for what is zapped; the files and the tool."""
@@ -224,7 +224,7 @@ def test_the_pulse_is_not_weaker_with_skz_and_off_means_the_old_path(obs):
     cfg = pipeline.Config(nchan=NCHAN, dispersion_measure=DM, nbin=NBIN, folding_period=PERIOD, ndim=4, parts_per_block=obs["ppb"],
                           max_parts=2)
     lt = pipeline.LoadToFold(cfg, _info(pipeline), stream=torch.cuda.current_stream().cuda_stream)
-    assert lt.sk is None and lt.sk_statistics is None and not hasattr(lt, "sk_head")
+    assert lt.sk is None and lt.sk_statistics is None and lt.voltages is None
     for blk in _blocks(obs):
         lt.process_block(blk)
     lt.finish_subint()

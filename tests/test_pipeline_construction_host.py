@@ -15,6 +15,7 @@ class Log:
         self.opened, self.closed, self.set_shapes = [], [], 0
         self.fail_set_shape = 0                  # the n-th FoldEngine.set_shape raises
         self.fail_rescale = False
+        self.fail_sk_shape = False               # SpectralKurtosisEngine.set_shape raises
 
 
 def _fakes(monkeypatch, with_dump=False):
@@ -51,6 +52,14 @@ def _fakes(monkeypatch, with_dump=False):
             if log.set_shapes == log.fail_set_shape:
                 raise DspsrAmdError("fake FoldEngine.set_shape refuses")
 
+    class Sk(Fake):
+        def set_shape(self, *a):
+            if log.fail_sk_shape:
+                raise DspsrAmdError("fake SpectralKurtosisEngine.set_shape refuses")
+
+        def set_options(self, *a):
+            pass
+
     class Delay(Fake):
         total_delay, zero_delay = 7, 11
 
@@ -62,7 +71,8 @@ def _fakes(monkeypatch, with_dump=False):
 
     for name, cls in (("Context", Context), ("FilterbankEngine", Filterbank), ("ConvolutionEngine", type("Conv", (Filterbank,), {})),
                       ("FoldEngine", Fold), ("CyclicFoldEngine", type("Cyclic", (Fold,), {})),
-                      ("PhaseLockedFilterbankEngine", type("Plfb", (Fold,), {})), ("SampleDelay", Delay), ("Rescale", Rescale)):
+                      ("PhaseLockedFilterbankEngine", type("Plfb", (Fold,), {})), ("SpectralKurtosisEngine", Sk), ("SampleDelay", Delay),
+                      ("Rescale", Rescale)):
         monkeypatch.setattr(pipeline, name, cls)
     monkeypatch.setattr(pipeline, "_device_empty", lambda ctx, shape, dtype="float32", zero=False: np.zeros(shape, dtype=dtype))
     if with_dump:
@@ -104,6 +114,7 @@ BUILDS = {
     "before": (_fold(dict(convolve_when="before", freq_res=32768)), "Context Conv Filterbank Fold"),
     "cyclic": (_fold(dict(nbin=32, cyclic_nchan=16, cyclic_mover=2, cyclic_npol=2)), "Context Filterbank Cyclic"),
     "plfb": (_fold(dict(nchan=8, folding_period=0.0004, plfb_nbin=8, plfb_nchan=64)), "Context Filterbank Plfb"),
+    "sk": (_fold(dict(sk_zap=True)), "Context Filterbank Fold Sk"),
     "two_targets": (_fold(dict(folding_period=0.0), targets=TARGETS), "Context Filterbank Fold Fold Fold"),
     "fourth_moment": (_fold(dict(fourth_moment=True, ndim=2)), "Context Filterbank Fold"),
     "LoadToFil": (lambda: pipeline.LoadToFil(pipeline.SearchConfig(nchan=64, tscrunch=16, nbit=8, rescale_seconds=2e-4, parts_per_block=32),
@@ -137,7 +148,7 @@ def test_construction_completes_and_close_releases_everything_once(monkeypatch, 
 def test_load_to_fold_defaults_are_set_on_every_path(monkeypatch):
     """the fields the class reads later exist whatever the path (sd_short was missing from three of five constructors)"""
     _fakes(monkeypatch)
-    for name in ("during", "during_K", "after", "never", "before", "cyclic", "plfb", "two_targets", "fourth_moment"):
+    for name in ("during", "during_K", "after", "never", "before", "cyclic", "plfb", "sk", "two_targets", "fourth_moment"):
         lt = BUILDS[name][0]()
         assert (lt.sd_carried, lt.sd_short, lt.fused_fold, lt.integration_length, lt.ndat_total, lt.nsamples_in, lt.ndat_out) == \
             (0, 0, lt.fused_mode != 0, 0.0, 0, 0, 0)
@@ -153,6 +164,7 @@ FAILURES = {
                                                                        pipeline.InputInfo(**SEARCH_INFO)), {},
                                     "dspsr_amd.LoadToFilCoherent: inter-channel delay of 2016 samples exceeds the block of 300"),
     "second_target_set_shape": (BUILDS["two_targets"][0], dict(fail_set_shape=3), "fake FoldEngine.set_shape refuses"),
+    "sk_set_shape": (BUILDS["sk"][0], dict(fail_sk_shape=True), "fake SpectralKurtosisEngine.set_shape refuses"),
     "LoadToFil_rescale": (BUILDS["LoadToFil"][0], dict(fail_rescale=True), "fake Rescale refuses"),
     "LoadToFilCoherent_rescale": (BUILDS["LoadToFilCoherent"][0], dict(fail_rescale=True), "fake Rescale refuses"),
     "LoadToFilDirect_rescale": (BUILDS["LoadToFilDirect"][0], dict(fail_rescale=True), "fake Rescale refuses"),
@@ -170,6 +182,8 @@ def test_a_failure_during_construction_releases_what_was_opened(monkeypatch, nam
     assert _released(log)
     if name == "second_target_set_shape":                # context, filterbank, the first fold, both pulsars' folds
         assert [type(o).__name__ for o in log.opened] == ["Context", "Filterbank", "Fold", "Fold", "Fold"]
+    if name == "sk_set_shape":                           # the engine that refused was opened, and is released with the rest
+        assert [type(o).__name__ for o in log.opened] == ["Context", "Filterbank", "Fold", "Sk"]
 
 
 REFUSALS = [
@@ -234,7 +248,7 @@ def test_close_on_an_instance_that_never_opened_a_device():
 # ---- the -K carry ------------------------------------------------------------------------------------------------------
 
 def _site(head, carried, nd, guarded):
-    """The arithmetic the three call sites had, restated: LoadToFold._process_block_interchan and LoadToFilCoherent.detect_scrunch
+    """The arithmetic the three -K call sites had, restated: the -K chain of LoadToFold and LoadToFilCoherent.detect_scrunch
     (guarded False), LoadToFilDirect.detect_scrunch (guarded True: no transform without samples, no move onto itself).
     Returns (off, nin, nout, move or None, carried)."""
     off, nin = head - carried, carried + nd
@@ -269,6 +283,57 @@ def test_delay_carry_against_the_three_call_sites(monkeypatch, head, short, ndim
             assert moves == ([move + (ndim,)] if move else []) and sd.carried == carry
             assert all(dst != src and n > 0 for dst, src, n, _ in moves)
             carried = carry
+
+
+def _site_plfb(head, tail, ndat, keep):
+    """The fourth site, as -G wrote it out by hand before it held a DelayCarry (complex rows: width 2): the new samples go to
+    buf[:, :, 2 * head:], the rows begin at 2 * (head - tail), and the `keep` samples from the next window's start on move to the end
+    of the head room.  Returns (new offset, rows offset, consumed, move or None, tail)."""
+    move = (head - keep, head + ndat - keep, keep) if keep else None
+    return 2 * head, 2 * (head - tail), tail + ndat - keep, move, keep
+
+
+def _site_sk(head, tail, ndat, nuse):
+    """The fifth site, as -skz wrote it out by hand: as -G, with `nuse` samples consumed (whole parts of M)."""
+    keep = tail + ndat - nuse
+    move = (head - keep, head - tail + nuse, keep) if keep else None
+    return 2 * head, 2 * (head - tail), nuse, move, keep
+
+
+@pytest.mark.parametrize("head", [1, 31, 64])
+def test_delay_carry_against_the_plfb_and_sk_call_sites(monkeypatch, head):
+    """-G and -skz hold the class that -K holds: with the three sites above, five.  Three blocks in a row, each consuming nothing
+    (where the head room can hold all of it), a part, or all of what it has; what stays never exceeds the head room, as a window
+    shorter than ndat_fft = head (-G) and a part shorter than M = head + 1 (-skz) never do.  Both sites always bring samples
+    (ndat >= 1), so the class's guard against a move onto itself never fires: the moves are the same, one for one."""
+    moves = []
+    monkeypatch.setattr(pipeline, "move_tail_fpt", lambda ctx, buf, dst, src, n, unit=1: moves.append((dst, src, n, unit)))
+    buf = np.arange(2 * 3 * (2 * head + 3) * 2, dtype=np.float32).reshape(2, 3, -1)
+    seen = set()
+
+    def walk(tail, blocks):
+        if not blocks:
+            return
+        ndat, nin = blocks[0], tail + blocks[0]
+        least = max(0, nin - head)                       # consumed: as little as the head room allows, a part, all
+        for nout in sorted({least, (least + nin) // 2, nin}):
+            seen.add("nothing" if not nout else "all" if nout == nin else "part")
+            want = _site_sk(head, tail, ndat, nout)
+            assert want == _site_plfb(head, tail, ndat, nin - nout)
+            c = pipeline.DelayCarry(head=head)
+            c.carried = tail
+            new, rows = c.new(buf, 2), c.rows(buf, ndim=2)
+            assert (new.shape[2], rows.shape[2]) == (buf.shape[2] - want[0], buf.shape[2] - want[1])
+            assert new[0, 0, 0] == want[0] and rows[0, 0, 0] == want[1]
+            assert c.rows(buf, ndat, 2).shape[2] == 2 * nin and c.rows(buf, ndat, 2)[0, 0, 0] == want[1]
+            del moves[:]
+            c.keep_tail(None, buf, ndat, nout, 2)
+            assert moves == ([want[3] + (2,)] if want[3] else []) and c.carried == want[4] <= head
+            walk(c.carried, blocks[1:])
+
+    for blocks in itertools.product(sorted({1, head, head + 3}), repeat=3):
+        walk(0, blocks)
+    assert seen == {"nothing", "part", "all"}
 
 
 def test_delay_carry_plans_zero_and_head_like_sample_delay():

@@ -1,0 +1,288 @@
+"""The calls LoadToFold makes on its engines, block by block, on the host: every engine, the context, the device allocator, the
+tail move and the profile view of dspsr_amd.pipeline are replaced by recording fakes (as test_pipeline_construction_host does for
+construction), four blocks run through process_block and finish_subint, and the recorded trace of every mode is compared with a
+fixture under tests/golden/pipeline_trace/.  The fixtures pin the host logic -- which engine is called, with which numbers, on
+which part of which buffer, in which order -- through a restructuring of the driver: the test reads only the public surface of
+an instance.
+
+    python tests/test_pipeline_trace_host.py --regenerate
+
+rewrites the fixtures from the code as it stands (nothing else does: not the environment, not a pytest option)."""
+import json
+import os
+import sys
+
+import numpy as np
+import pytest
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+if ROOT not in sys.path:
+    sys.path.insert(0, ROOT)
+
+from dspsr_amd import dada, pipeline                                                # noqa: E402
+
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "pipeline_trace")
+PARTS = (3, 3, 3, 2)                           # four blocks of parts_per_block = 3 parts, the last one ragged
+
+
+def _enc(log, v):
+    """One argument of a recorded call: scalars as they are (floats by repr), tensors by shape and storage offset, host arrays by
+    shape, type and -- the short ones: window starts and bins -- values, engines by their place in the order of opening."""
+    if isinstance(v, torch.Tensor):
+        return {"tensor": list(v.shape), "offset": v.storage_offset()}
+    if isinstance(v, np.ndarray):
+        d = {"array": list(v.shape), "dtype": str(v.dtype)}
+        if v.size <= 16:
+            d["values"] = [int(x) for x in v.reshape(-1)]
+        return d
+    if isinstance(v, (list, tuple)):
+        return [_enc(log, x) for x in v]
+    if isinstance(v, (bool, int, str)) or v is None:
+        return v
+    if isinstance(v, (float, np.floating)):
+        return repr(float(v))
+    if isinstance(v, np.integer):
+        return int(v)
+    if v in log.opened:
+        return log.name(v)
+    raise TypeError("unrecorded argument %r" % (v,))
+
+
+class Log:
+    def __init__(self):
+        self.opened, self.calls = [], []
+
+    def name(self, obj):
+        return "%s#%d" % (type(obj).__name__, self.opened.index(obj))
+
+    def call(self, who, method, *a, **k):
+        self.calls.append([who if isinstance(who, str) else self.name(who), method, [_enc(self, x) for x in a],
+                           {key: _enc(self, k[key]) for key in sorted(k)}])
+
+
+def _fakes(mp):
+    """Engines that record every call and return what the real ones would, as far as the host logic reads it."""
+    log = Log()
+
+    class Fake:
+        def __init__(self, *a, **k):
+            log.opened.append(self)
+
+        def close(self):
+            pass
+
+        def synchronize(self):
+            pass
+
+    def recorded(*names, returns=None):
+        def deco(cls):
+            for n in names:
+                def method(self, *a, _n=n, **k):
+                    log.call(self, _n, *a, **k)
+                    return returns
+                setattr(cls, n, method)
+            return cls
+        return deco
+
+    class Context(Fake):
+        def __init__(self, device=0, stream=None):
+            super().__init__()
+            self.device, self.handle = device, 1
+
+    @recorded("perform", "perform_raw", "perform_detect", "perform_fold", "set_kernel")
+    class Filterbank(Fake):
+        nkeep, nsamp_step, nsamp_overlap, nsamp_fft = 100, 3200, 320, 3520
+
+        def setup(self, *a, **k):
+            return self
+
+        def fold_is_fused(self):
+            return 1
+
+    class Conv(Filterbank):
+        nkeep, nsamp_step, nsamp_overlap, nsamp_fft = 100, 100, 20, 120
+
+    @recorded("set_shape", "set_nbin", "set_ndat", "fold", "fold_moments", "fold_zeroed", "zero")
+    class Fold(Fake):
+        def set_bins(self, phi, phase_per_sample, ndat, idat_start=0, hits=None):
+            log.call(self, "set_bins", phi, phase_per_sample, ndat, idat_start, hits)
+            if hits is not None:
+                hits[(ndat + idat_start) % len(hits)] += ndat             # (a count the books can be checked by)
+            return ndat
+
+        @staticmethod
+        def fold_many(folds, inp):
+            log.call("FoldEngine", "fold_many", folds, inp)
+
+        def get_profiles_ptr(self):
+            return 0
+
+    class Cyclic(Fold):
+        def set_shape(self, nchan, npol_in, npol_out, nlag, mover, nbin):
+            log.call(self, "set_shape", nchan, npol_in, npol_out, nlag, mover, nbin)
+            self.out = (nchan * (2 * nlag - 2) // mover, npol_out, nbin)
+
+        def synch(self):
+            log.call(self, "synch")
+            return np.zeros(self.out, np.float32)
+
+    @recorded("zero")
+    class Plfb(Fake):
+        def set_shape(self, nchan_in, npol_in, ndim_in, nchan, npol_out, nbin):
+            log.call(self, "set_shape", nchan_in, npol_in, ndim_in, nchan, npol_out, nbin)
+            self.out = (nchan_in * nchan, npol_out, nbin)
+
+        def accumulate(self, inp, ndat, idat_start, bins):
+            log.call(self, "accumulate", inp, ndat, idat_start, bins)
+            return len(bins)
+
+        def synch(self):
+            log.call(self, "synch")
+            return np.zeros(self.out, np.float32)
+
+    @recorded("set_shape", "set_options", "transform")
+    class Sk(Fake):
+        def get_statistics(self):
+            log.call(self, "get_statistics")
+            return {"zapped": 0}
+
+    class Delay(Fake):
+        def __init__(self, ctx, delays, npol=1, absolute=False):
+            super().__init__()
+            d = np.asarray(delays, np.int64)
+            self.zero_delay = 0 if absolute else int(d.max())
+            self.total_delay = int(d.max()) if absolute else int((self.zero_delay - d).max())
+
+        def transform(self, inp, out=None):
+            log.call(self, "transform", inp)
+            return max(0, inp.shape[2] - self.total_delay)
+
+    @recorded("polarimetry")
+    class Detection(Fake):
+        pass
+
+    @recorded("write")
+    class Dump(Fake):
+        def __init__(self, path, **k):
+            super().__init__()
+
+    for name, cls in (("Context", Context), ("FilterbankEngine", Filterbank), ("ConvolutionEngine", Conv), ("FoldEngine", Fold),
+                      ("CyclicFoldEngine", Cyclic), ("PhaseLockedFilterbankEngine", Plfb), ("SpectralKurtosisEngine", Sk),
+                      ("SampleDelay", Delay), ("DetectionEngine", Detection)):
+        mp.setattr(pipeline, name, cls)
+    mp.setattr(dada, "Dump", Dump)
+    mp.setattr(pipeline, "_device_empty",
+               lambda ctx, shape, dtype="float32", zero=False: torch.zeros(shape, dtype=getattr(torch, dtype)))
+    mp.setattr(pipeline, "move_tail_fpt", lambda ctx, buf, dst, src, n, unit=1: log.call("pipeline", "move_tail_fpt", buf, dst, src, n, unit))
+    mp.setattr(pipeline, "fourth_moment", lambda ctx, inp, out, ndat=None: log.call("pipeline", "fourth_moment", inp, out, ndat))
+
+    def profiles_tensor(self, pulsar=None):
+        nbin = self.cfg.nbin if pulsar is None else pulsar.nbin
+        log.call("LoadToFold", "profiles_tensor", None if pulsar is None else self.pulsars.index(pulsar))
+        return torch.zeros(self.nchan_out * nbin * (14 if self.moments else 4))
+    mp.setattr(pipeline.LoadToFold, "profiles_tensor", profiles_tensor)
+    return log
+
+
+# 16 channels of a 32 MHz real band: 1 MHz, a block of 3 parts is 300 output samples, -L 450 us puts a boundary inside block 1,
+# one at the end of block 2 and none in blocks 0 and 3
+INFO = dict(centre_frequency=1382.0, bandwidth=-16.0, tsamp_us=1.0 / 32.0, machine="DADA")
+CFG = dict(nchan=16, dispersion_measure=3.0, nbin=64, folding_period=0.004, ndim=4, parts_per_block=3, max_parts=2, subint_seconds=0.00045)
+# -s: turns of 400 and of 230 samples -- in a block of 300, one pulsar has a single piece where the other has two
+TARGETS = [pipeline.FoldTarget("a", folding_period=0.0004, nbin=64), pipeline.FoldTarget("b", folding_period=0.00023, nbin=32)]
+
+
+def _fold(cfg=(), info=INFO, **kw):
+    return lambda: pipeline.LoadToFold(pipeline.Config(**{**CFG, **dict(cfg)}), pipeline.InputInfo(**info), **kw)
+
+
+MODES = {
+    "during": _fold(),
+    "during_K": _fold(dict(interchan_dedispersion=True)),
+    "during_taps": _fold(dump_before=("Detection", "Fold")),
+    "two_targets_s": _fold(dict(folding_period=0.0, subint_seconds=0.0, subint_turns=1.0), targets=TARGETS),
+    "fourth_moment": _fold(dict(fourth_moment=True, ndim=2)),
+    "after": _fold(dict(convolve_when="after")),
+    "before": _fold(dict(convolve_when="before", freq_res=32768)),
+    "cyclic": _fold(dict(nbin=32, cyclic_nchan=16, cyclic_mover=2, cyclic_npol=2)),
+    "plfb": _fold(dict(nchan=8, folding_period=0.0004, plfb_nbin=8, plfb_nchan=64, subint_seconds=0.0)),
+    "sk": _fold(dict(sk_zap=True)),
+}
+
+
+def _books(acc):
+    hits = np.asarray(acc.hits)
+    return {"hits_shape": list(hits.shape), "hits_sum": int(hits.sum(dtype=np.uint64)), "hits_nonzero": [int(i) for i in np.flatnonzero(hits)][:32],
+            "integration_length": repr(float(acc.integration_length)), "ndat_total": int(acc.ndat_total),
+            "subints": [{"keys": sorted(s), "hits_sum": int(np.asarray(s["hits"]).sum(dtype=np.uint64)), "ndat_total": int(s["ndat_total"]),
+                         "integration_length": repr(float(s["integration_length"]))} for s in acc.subints]}
+
+
+def _run(mp, mode):
+    """Four blocks and a finish_subint of `mode`: the trace and the books, as the fixture holds them."""
+    log = _fakes(mp)
+    lt = MODES[mode]()
+    opened = [log.name(o) for o in log.opened]
+    marks = []
+    for npart in PARTS:
+        marks.append(len(log.calls))
+        raw = torch.zeros(lt.block_bytes(npart), dtype=torch.int8)
+        lt.process_block(raw, npart)
+    marks.append(len(log.calls))
+    lt.finish_subint()
+    result = {"opened": opened, "blocks": [log.calls[a:b] for a, b in zip(marks, marks[1:])], "finish": log.calls[marks[-1]:],
+              "books": _books(lt), "pulsars": [_books(p) for p in lt.pulsars], "ndat_out": int(lt.ndat_out), "nsamples_in": int(lt.nsamples_in)}
+    lt.close()
+    return json.loads(json.dumps(result))
+
+
+@pytest.mark.parametrize("mode", sorted(MODES))
+def test_the_trace_of_four_blocks_is_the_recorded_one(monkeypatch, mode):
+    with open(os.path.join(GOLDEN, mode + ".json")) as f:
+        want = json.load(f)
+    got = _run(monkeypatch, mode)
+    assert got["opened"] == want["opened"]
+    for k, (g, w) in enumerate(zip(got["blocks"], want["blocks"])):
+        for i, (cg, cw) in enumerate(zip(g, w)):
+            assert cg == cw, "block %d, call %d" % (k, i)
+        assert len(g) == len(w), "block %d" % k
+    assert got["finish"] == want["finish"]
+    for key in ("books", "pulsars", "ndat_out", "nsamples_in"):
+        assert got[key] == want[key], key
+
+
+def test_the_blocks_chosen_reach_the_branches():
+    """what the fixtures are worth: a block with a boundary inside, one with a boundary at its end, one without; a fused and an
+    unfused block; a pulsar folded with the others and one folded alone; a window and a part of M samples carried over a block"""
+    def fixture(mode):
+        with open(os.path.join(GOLDEN, mode + ".json")) as f:
+            return json.load(f)
+    methods = lambda block: [c[1] for c in block]
+    during = fixture("during")
+    assert [methods(b).count("perform_fold") for b in during["blocks"]] == [1, 0, 1, 1]
+    assert [methods(b).count("profiles_tensor") for b in during["blocks"]] == [0, 1, 1, 0] and len(during["books"]["subints"]) == 3
+    two = fixture("two_targets_s")
+    assert any("fold_many" in methods(b) and "fold" in methods(b) for b in two["blocks"])
+    assert all(len(p["subints"]) >= 2 for p in two["pulsars"])
+    for mode in ("during_K", "plfb", "sk"):
+        assert all("move_tail_fpt" in methods(b) for b in fixture(mode)["blocks"][:3]), mode
+    assert fixture("sk")["ndat_out"] == (1100 // 128) * 128 and fixture("during_K")["ndat_out"] < 1100
+    assert sum(methods(b).count("accumulate") for b in fixture("plfb")["blocks"]) >= 3
+
+
+def regenerate():
+    os.makedirs(GOLDEN, exist_ok=True)
+    for mode in sorted(MODES):
+        with pytest.MonkeyPatch.context() as mp:
+            result = _run(mp, mode)
+        with open(os.path.join(GOLDEN, mode + ".json"), "w") as f:
+            json.dump(result, f, indent=1, sort_keys=True)
+            f.write("\n")
+        print("%s: %d calls" % (mode, sum(len(b) for b in result["blocks"]) + len(result["finish"])))
+
+
+if __name__ == "__main__":
+    if sys.argv[1:] != ["--regenerate"]:
+        sys.exit("usage: python tests/test_pipeline_trace_host.py --regenerate")
+    regenerate()

@@ -12,9 +12,8 @@
 #include <string.h>
 
 #include "dsp/CyclicFold.h"
-#include "Error.h"
 
-#include "dspsr_amd.h"
+#include "dspsr_amd_adaptor_common.h"   // HIP::check, HIP::rows_of
 
 namespace HIP
 {
@@ -62,10 +61,8 @@ namespace HIP
       const dsp::TimeSeries* in = parent->get_input ();
       if (in->get_memory ()->on_host ())
         throw Error (InvalidState, "HIP::CyclicFoldEngine::fold", "the input TimeSeries is not in device memory");
-      const float* base = in->get_datptr (0, 0);
-      const uint64_t cs = nchan > 1 ? uint64_t (in->get_datptr (1, 0) - base) : 0;
-      const uint64_t ps = npol > 1 ? uint64_t (in->get_datptr (0, 1) - base) : 0;
-      status (dspsr_amd_cyclic_fold_fold (handle, base, cs, ps), "HIP::CyclicFoldEngine::fold");
+      const Rows<const float*> rows = rows_of (in, nchan, npol);      // the shape Fold::Engine::setup read from this input
+      status (dspsr_amd_cyclic_fold_fold (handle, rows.base, rows.cs, rows.ps), "HIP::CyclicFoldEngine::fold");
       synchronized = false;
     }
 
@@ -89,11 +86,7 @@ namespace HIP
     uint64_t get_lagdata_size () const { return lagdata_size; }
 
   protected:
-    void status (int code, const char* method)
-    {
-      if (code != DSPSR_AMD_OK)
-        throw Error (code == DSPSR_AMD_EINVAL ? InvalidParam : InvalidState, method, dspsr_amd_last_error (ctx));
-    }
+    void status (int code, const char* method) { check (ctx, code, method); }
     dspsr_amd_ctx* ctx;
     dspsr_amd_cyclic_fold* handle;
   };

@@ -1,6 +1,6 @@
 // Host adaptor classes: bind the C-ABI of include/dspsr_amd.h to DSPSR's Engine plug-in interfaces.
 // A DSPSR maintainer compiles this header inside the dspsr tree (it only needs the dsp headers named
-// below and -ldspsr_amd) and installs the engines where the CUDA ones are installed today
+// below, dspsr_amd_adaptor_common.h and -ldspsr_amd) and installs the engines where the CUDA ones are installed today
 // (INTEGRATION.md).  Each method mirrors the CUDA twin it replaces:
 //   HIP::DeviceMemory      <- CUDA::DeviceMemory      Kernel/Classes/MemoryCUDA.C:47-106
 //   HIP::TimeSeriesEngine  <- CUDA::TimeSeriesEngine  Kernel/Classes/TimeSeriesCUDA.cu:31-200
@@ -8,7 +8,7 @@
 //   HIP::ConvolutionEngine <- CUDA::ConvolutionEngine Signal/General/ConvolutionCUDA.cu:202-800
 //   HIP::DetectionEngine   <- CUDA::DetectionEngine   Signal/General/DetectionCUDA.cu:127-322
 //   HIP::FoldEngine        <- CUDA::FoldEngine        Signal/Pulsar/FoldCUDA.cu:64-697
-// Errors: every non-zero C-ABI status is rethrown as the reference's `Error` with the library's message.
+// Errors: every non-zero C-ABI status is rethrown as the reference's `Error` with the library's message (HIP::check).
 //
 // DEFERRED MODE (HIP::Chain).  The three operations of the hot path are separate Engine calls in DSPSR, made in this order
 // per block: Filterbank::Engine::perform (Filterbank.C:547-553), Detection::Engine::polarimetry (Detection.C:325-334),
@@ -54,26 +54,20 @@
 #include "dsp/Fold.h"               // dsp::Fold::Engine, dsp::PhaseSeries
 #include "dsp/TScrunch.h"           // dsp::TScrunch::Engine
 #include "dsp/FScrunch.h"           // dsp::FScrunch::Engine
-#include "Error.h"
 
-#include "dspsr_amd.h"
+#include "dspsr_amd_adaptor_common.h"   // HIP::check, HIP::rows_of, HIP::DeviceScratch
 
 namespace HIP
 {
-  inline void check (dspsr_amd_ctx* ctx, int status, const char* method)
-  {
-    if (status != DSPSR_AMD_OK)
-      throw Error (status == DSPSR_AMD_EINVAL ? InvalidParam : InvalidState, method,
-                   dspsr_amd_last_error (ctx));
-  }
-
-  //! What the adaptors of one pipeline thread share in deferred mode (see the top of this file)
+  //! What the adaptors of one pipeline thread share in deferred mode, and the owner of its protocol (see the top of this file):
+  //! the engines hand it a filterbank call, a detection call, a fold request or a reader, and it records, fuses, executes,
+  //! drops or refuses
   class Chain : public Reference::Able
   {
   public:
     Chain (dspsr_amd_ctx* _ctx) : ctx (_ctx), deferred (false), fused_blocks (0), eager_blocks (0), dropped_blocks (0),
                                   nfold (0), drop_unfolded (true), consumed_fb (0), consumed_det (0)
-    { fbk.pending = false; det.pending = false; fbk.raw = 0; }
+    { fbk.pending = false; det.pending = false; }
 
     void set_deferred (bool flag) { if (!flag) flush (); deferred = flag; }
     bool get_deferred () const { return deferred; }
@@ -87,21 +81,121 @@ namespace HIP
     void set_drop_unfolded (bool flag) { drop_unfolded = flag; }
     bool get_drop_unfolded () const { return drop_unfolded; }
 
-    //! the fused launch group has consumed the recorded block: its intermediate TimeSeries were never written
-    void mark_consumed () { consumed_fb = fbk.out; consumed_det = det.out; }
-    void clear_consumed () { consumed_fb = 0; consumed_det = 0; }
-    //! throws if `series` is such a never-written intermediate (a reader the fusion could not see)
-    void require_written (const dsp::TimeSeries* series, const char* method) const
-    {
-      if (series && (series == consumed_fb || series == consumed_det))
-        throw Error (InvalidState, method, "this TimeSeries is an intermediate of a block that the deferred HIP::Chain ran as one "
-                     "fused launch group: it was never written (register every FoldEngine on the chain, or do not defer)");
-    }
-
     //! blocks that went through the fused launch group / through the separate launches / recorded and never consumed
     uint64_t get_fused_blocks () const { return fused_blocks; }
     uint64_t get_eager_blocks () const { return eager_blocks; }
     uint64_t get_dropped_blocks () const { return dropped_blocks; }
+
+    // ---- the arguments of FilterbankEngine::perform
+    struct FilterbankCall
+    {
+      dspsr_amd_filterbank* fb;
+      const dsp::TimeSeries* in;
+      dsp::TimeSeries* out;
+      Rows<const float*> i;                       // float input rows (device)
+      Rows<float*> o;                             // complex output rows (device)
+      uint64_t npart, in_step, out_step;
+      const int8_t* raw; int raw_layout; float raw_scale;   // raw != 0: the packed block holds the same samples
+    };
+    // ---- the arguments of DetectionEngine::polarimetry
+    struct DetectionCall
+    {
+      unsigned ndim; int state;
+      const dsp::TimeSeries* in;
+      dsp::TimeSeries* out;
+      Rows<const float*> i;
+      Rows<float*> o;
+      unsigned nchan; uint64_t ndat;
+    };
+    // ---- what FoldEngine::fold is about to fold
+    struct FoldRequest
+    {
+      dspsr_amd_fold* fold;
+      const dsp::TimeSeries* in;                  // Fold::get_input ()
+      uint64_t idat_start, ndat;                  // the piece of it (Fold::Engine::set_ndat)
+      unsigned npol, ndim;
+      bool counts_hits;                           // zeroed samples with per-channel hits: counted from the data
+    };
+
+    //! the launch DSPSR asked for (also what an engine without a chain does)
+    static void run (dspsr_amd_ctx* ctx, const FilterbankCall& c)
+    {
+      if (c.raw)
+        check (ctx, dspsr_amd_filterbank_perform_raw (c.fb, c.raw, c.raw_layout, c.raw_scale, c.o.base, c.o.cs, c.o.ps, c.npart,
+                                                     c.out_step), "HIP::FilterbankEngine::perform");
+      else
+        check (ctx, dspsr_amd_filterbank_perform (c.fb, c.i.base, c.i.cs, c.i.ps, c.o.base, c.o.cs, c.o.ps, c.npart, c.in_step,
+                                                 c.out_step), "HIP::FilterbankEngine::perform");
+    }
+    static void run (dspsr_amd_ctx* ctx, const DetectionCall& c)
+    {
+      check (ctx, dspsr_amd_detect_polarimetry (ctx, c.state, c.ndim, c.i.base, c.i.cs, c.i.ps, c.o.base, c.o.cs, c.o.ps, c.nchan,
+                                                c.ndat), "HIP::DetectionEngine::polarimetry");
+    }
+
+    //! FilterbankEngine::perform: recorded when deferred, executed (and counted) otherwise
+    void filterbank (const FilterbankCall& call)
+    {
+      consumed_fb = 0; consumed_det = 0;          // `out` is about to be written (or recorded) anew
+      if (fbk.pending) unfolded_block ();         // never folded (Subint.h:270): dropped and counted; Error in strict mode
+      fbk.call = call;
+      if (deferred) { fbk.pending = true; return; }
+      run (ctx, call);
+      eager_blocks ++;
+    }
+    //! ~FilterbankEngine: the recorded filterbank call is forgotten (a recorded detection is not)
+    void filterbank_gone () { fbk.pending = false; }
+
+    //! DetectionEngine::polarimetry: recorded only behind a recorded filterbank block whose output it reads, in a shape the
+    //! fused fold writes; otherwise everything recorded runs, then this call
+    void detection (const DetectionCall& call)
+    {
+      if (det.pending) flush ();
+      require_written (call.in, "HIP::DetectionEngine::polarimetry");
+      det.call = call;
+      if (fbk.pending && call.in == fbk.call.out && (call.ndim == 2 || call.ndim == 4)) { det.pending = true; return; }
+      flush ();
+      run (ctx, call);
+    }
+
+    //! FoldEngine::fold, after the profile is bound.  The filterbank and the detection of this block may only have been
+    //! recorded.  If this call folds the WHOLE detected block (no sub-integration boundary inside it: Subint.h:234-309 would
+    //! fold it in pieces) in a shape the fused kernel writes, the three operations run as ONE launch group, the channelised
+    //! data stay on the chip and the answer is true: nothing is left to fold.  Otherwise they run now as the separate launches
+    //! DSPSR asked for, the answer is false and the caller folds their output.
+    //! (one Fold per chain only: a second Fold of the same detected series -- dspsr folding several pulsars,
+    //!  LoadToFold1.C:917-955,1206 -- needs the series itself; zeroed samples with per-channel hits are counted from the data
+    //!  by the eager kernel, Fold.C:853-866)
+    bool fold (const FoldRequest& r)
+    {
+      const FilterbankCall& f = fbk.call;
+      const DetectionCall& d = det.call;
+      const bool whole = fbk.pending && det.pending && r.in == d.out && r.idat_start == 0 && r.ndat == r.in->get_ndat ()
+                         && r.in->get_ndat () == d.ndat
+                         && ((r.npol == 2 && r.ndim == 2 && d.ndim == 2) || (r.npol == 1 && r.ndim == 4 && d.ndim == 4))
+                         && nfold <= 1 && !r.counts_hits;
+      if (!whole)
+      {
+        flush ();
+        require_written (r.in, "HIP::FoldEngine::fold");
+        return false;
+      }
+      // the fused launch group consumes the recorded block: its intermediate TimeSeries are never written
+      consumed_fb = f.out; consumed_det = d.out;
+      fbk.pending = false; det.pending = false;
+      check (ctx, dspsr_amd_filterbank_perform_fold (f.fb, f.raw ? 0 : f.i.base, f.i.cs, f.i.ps, f.in_step, f.raw, f.raw_layout,
+                                                    f.raw_scale, d.state, r.fold, f.npart), "HIP::FoldEngine::fold");
+      fused_blocks ++;
+      return true;
+    }
+
+    //! an engine call outside the protocol reads `series` (and writes `target`): a recorded block that either belongs to is
+    //! executed first; throws if `series` is a never-written intermediate of a fused block (a reader the fusion could not see)
+    void reader (const dsp::TimeSeries* series, const char* method, const dsp::TimeSeries* target = 0)
+    {
+      flush_if (series); flush_if (target);
+      require_written (series, method);
+    }
 
     //! execute, as the separate launches DSPSR asked for, whatever has only been recorded
     void flush ()
@@ -109,18 +203,29 @@ namespace HIP
       if (fbk.pending)
       {
         fbk.pending = false;
-        run_filterbank ();
+        run (ctx, fbk.call);
         eager_blocks ++;
       }
       if (det.pending)
       {
         det.pending = false;
-        run_detection ();
+        run (ctx, det.call);
       }
     }
-    //! the same if `series` is the output of a recorded call (a second reader)
+
+  private:
+    //! flush () if `series` is the output of a recorded call (a second reader), or the input of the recorded detection
     void flush_if (const dsp::TimeSeries* series)
-    { if ((fbk.pending && series == fbk.out) || (det.pending && (series == det.out || series == det.in))) flush (); }
+    {
+      if (series && ((fbk.pending && series == fbk.call.out) || (det.pending && (series == det.call.out || series == det.call.in))))
+        flush ();
+    }
+    void require_written (const dsp::TimeSeries* series, const char* method) const
+    {
+      if (series && (series == consumed_fb || series == consumed_det))
+        throw Error (InvalidState, method, "this TimeSeries is an intermediate of a block that the deferred HIP::Chain ran as one "
+                     "fused launch group: it was never written (register every FoldEngine on the chain, or do not defer)");
+    }
     //! a recorded block is still pending when the next one arrives: DSPSR has refilled its input, it cannot run any more
     void unfolded_block ()
     {
@@ -132,50 +237,13 @@ namespace HIP
       dropped_blocks ++;
     }
 
-    // ---- arguments recorded by FilterbankEngine::perform
-    struct FilterbankCall
-    {
-      bool pending;
-      dspsr_amd_filterbank* fb;
-      const dsp::TimeSeries* in;
-      dsp::TimeSeries* out;
-      const float* ibase; uint64_t ics, ips;      // float input rows (device)
-      float* obase; uint64_t ocs, ops;            // complex output rows (device)
-      uint64_t npart, in_step, out_step;
-      const int8_t* raw; int raw_layout; float raw_scale;   // raw != 0: the packed block holds the same samples
-    } fbk;
-    // ---- arguments recorded by DetectionEngine::polarimetry
-    struct DetectionCall
-    {
-      bool pending;
-      unsigned ndim; int state;
-      const dsp::TimeSeries* in;
-      dsp::TimeSeries* out;
-      const float* ibase; uint64_t ics, ips;
-      float* obase; uint64_t ocs, ops;
-      unsigned nchan; uint64_t ndat;
-    } det;
-
-    void run_filterbank ()
-    {
-      if (fbk.raw)
-        check (ctx, dspsr_amd_filterbank_perform_raw (fbk.fb, fbk.raw, fbk.raw_layout, fbk.raw_scale, fbk.obase, fbk.ocs, fbk.ops,
-                                                     fbk.npart, fbk.out_step), "HIP::FilterbankEngine::perform");
-      else
-        check (ctx, dspsr_amd_filterbank_perform (fbk.fb, fbk.ibase, fbk.ics, fbk.ips, fbk.obase, fbk.ocs, fbk.ops, fbk.npart,
-                                                 fbk.in_step, fbk.out_step), "HIP::FilterbankEngine::perform");
-    }
-    void run_detection ()
-    {
-      check (ctx, dspsr_amd_detect_polarimetry (ctx, det.state, det.ndim, det.ibase, det.ics, det.ips, det.obase, det.ocs,
-                                                det.ops, det.nchan, det.ndat), "HIP::DetectionEngine::polarimetry");
-    }
-
     dspsr_amd_ctx* ctx;
     bool deferred;
     uint64_t fused_blocks, eager_blocks, dropped_blocks;
     unsigned nfold;
     bool drop_unfolded;
+    struct { bool pending; FilterbankCall call; } fbk;    // recorded by filterbank ()
+    struct { bool pending; DetectionCall call; } det;     // recorded by detection ()
     const dsp::TimeSeries* consumed_fb;           // intermediates of the last fused block (never written), until the next perform()
     const dsp::TimeSeries* consumed_det;
   };
@@ -210,18 +278,12 @@ namespace HIP
     //! `from`, starting at idat_start, to the start of the rows of the parent
     void copy_data_fpt (const dsp::TimeSeries* from, uint64_t idat_start = 0, uint64_t ndat = 0)
     {
-      if (chain)
-      {
-        chain->flush_if (from); chain->flush_if (to);                // a reader of a recorded block: execute it first
-        chain->require_written (from, "HIP::TimeSeriesEngine::copy_data_fpt");
-      }
+      if (chain) chain->reader (from, "HIP::TimeSeriesEngine::copy_data_fpt", to);
       const unsigned nchan = to->get_nchan (), npol = to->get_npol (), ndim = to->get_ndim ();
-      float* obase = to->get_datptr (0, 0);
-      const float* ibase = from->get_datptr (0, 0);
-      check (ctx, dspsr_amd_copy_fpt (ctx, obase, nchan > 1 ? to->get_datptr (1, 0) - obase : 0,
-               npol > 1 ? to->get_datptr (0, 1) - obase : 0, ibase + idat_start * ndim,
-               nchan > 1 ? from->get_datptr (1, 0) - ibase : 0, npol > 1 ? from->get_datptr (0, 1) - ibase : 0,
-               nchan, npol, ndat * ndim), "HIP::TimeSeriesEngine::copy_data_fpt");
+      const Rows<float*> o = rows_of (to);
+      const Rows<const float*> i = rows_of (from, nchan, npol);      // the parent's shape for both series (TimeSeriesCUDA.cu:75-200)
+      check (ctx, dspsr_amd_copy_fpt (ctx, o.base, o.cs, o.ps, i.base + idat_start * ndim, i.cs, i.ps, nchan, npol, ndat * ndim),
+             "HIP::TimeSeriesEngine::copy_data_fpt");
     }
   protected:
     dspsr_amd_ctx* ctx;
@@ -229,18 +291,50 @@ namespace HIP
     Reference::To<Chain> chain;
   };
 
-  //! dsp::Filterbank::Engine (FilterbankEngine.h:15-44)
-  //! Response::get_ndim () where the class has it (dsp::Response does: 2 complex, 8 Jones), else 2
-  template <class R> auto response_ndim_of (const R* r, int) -> decltype (unsigned (r->get_ndim ())) { return r->get_ndim (); }
-  template <class R> unsigned response_ndim_of (const R*, long) { return 2; }
+  //! The library's config for a dsp::Filterbank (FilterbankCUDA.cu:73-168) or a dsp::Convolution (nchan_subband 1, freq_res =
+  //! response->get_ndat (), ConvolutionCUDA.cu:208-244), from its input and its response (NULL: none)
+  inline dspsr_amd_filterbank_config filterbank_config (const dsp::TimeSeries* input, const dsp::Response* response,
+                                                        unsigned nchan_subband, unsigned freq_res, unsigned max_parts = 0,
+                                                        int fused_fold = DSPSR_AMD_FUSED_AUTO)
+  {
+    dspsr_amd_filterbank_config cfg;
+    cfg.nchan_subband = nchan_subband;
+    cfg.freq_res = freq_res;
+    cfg.nfilt_pos = response ? response->get_impulse_pos () : 0;
+    cfg.nfilt_neg = response ? response->get_impulse_neg () : 0;
+    cfg.input_nchan = input->get_nchan ();
+    cfg.npol = input->get_npol ();
+    cfg.real_input = input->get_state () == Signal::Nyquist;       // CUFFT_R2C vs C2C (ConvolutionCUDA.cu:219-222)
+    cfg.max_parts = max_parts;
+    cfg.force_four_pass = 0;
+    cfg.fused_fold = fused_fold;
+    cfg.split_in_inverse = 0;
+    return cfg;
+  }
 
+  //! A new library object in the place of `fb`, with the response set: response->get_datptr (0, 0) is host-built and already
+  //! swapped (Response.C:132-181), nchan * ndat complex numbers, or as many Jones matrices when `matrix` (NULL: no response)
+  inline void replace_filterbank (dspsr_amd_ctx* ctx, dspsr_amd_filterbank*& fb, const dspsr_amd_filterbank_config& cfg,
+                                  const dsp::Response* response, bool matrix, const char* method)
+  {
+    const float* data = response ? response->get_datptr (0, 0) : 0;
+    const uint64_t nbin = response ? uint64_t (response->get_nchan ()) * response->get_ndat () : 0;
+    dspsr_amd_filterbank_destroy (fb); fb = 0;
+    check (ctx, dspsr_amd_filterbank_create (ctx, &cfg, &fb), method);
+    if (matrix)
+      check (ctx, dspsr_amd_filterbank_set_response_matrix (fb, data, nbin), method);
+    else
+      check (ctx, dspsr_amd_filterbank_set_kernel (fb, data, nbin), method);
+  }
+
+  //! dsp::Filterbank::Engine (FilterbankEngine.h:15-44)
   class FilterbankEngine : public dsp::Filterbank::Engine
   {
   public:
     FilterbankEngine (dspsr_amd_ctx* _ctx, Chain* _chain = 0)
       : ctx (_ctx), fb (0), chain (_chain), fused_fold (DSPSR_AMD_FUSED_AUTO), max_parts (0)
-    { raw.ptr = 0; }
-    ~FilterbankEngine () { if (chain) chain->fbk.pending = false; dspsr_amd_filterbank_destroy (fb); }
+    { raw.ptr = 0; raw.layout = 0; raw.scale = 0; }
+    ~FilterbankEngine () { if (chain) chain->filterbank_gone (); dspsr_amd_filterbank_destroy (fb); }
 
     //! before setup: DSPSR_AMD_FUSED_AUTO / _ALWAYS / _NEVER (dspsr_amd_filterbank_config::fused_fold) and the number of
     //! overlap-save parts per launch group (0 = library default; the scratch is sized for it)
@@ -258,35 +352,13 @@ namespace HIP
     void setup (dsp::Filterbank* filterbank)
     {
       filterbank->set_passband (NULL);          // the engine does not maintain the passband
-      dspsr_amd_filterbank_config cfg;
-      cfg.nchan_subband = filterbank->get_nchan_subband ();
-      cfg.freq_res = filterbank->get_freq_res ();
-      cfg.input_nchan = filterbank->get_input()->get_nchan ();
-      cfg.npol = filterbank->get_input()->get_npol ();
-      cfg.real_input = filterbank->get_input()->get_state () == Signal::Nyquist;
-      cfg.nfilt_pos = cfg.nfilt_neg = 0;
-      cfg.max_parts = max_parts;
-      cfg.force_four_pass = 0;
-      cfg.fused_fold = fused_fold;
-      cfg.split_in_inverse = 0;
-      const float* kernel = 0;
-      uint64_t ncomplex = 0;
+      const dsp::Response* response = filterbank->has_response () ? filterbank->get_response () : 0;
       if (chain) chain->flush ();
-      if (filterbank->has_response ())
-      {
-        const dsp::Response* response = filterbank->get_response ();
-        // (a matrix response, Filterbank.C:186-206, is 8 floats per bin: never handed on as a chirp -- dspsr_amd_matrix_engine.h)
-        if (response_ndim_of (response, 0) != 2)
-          throw Error (InvalidState, "HIP::FilterbankEngine::setup", "response ndim=%u != 2: a matrix response needs "
-                       "HIP::MatrixFilterbankEngine", response_ndim_of (response, 0));
-        cfg.nfilt_pos = response->get_impulse_pos ();
-        cfg.nfilt_neg = response->get_impulse_neg ();
-        kernel = response->get_datptr (0, 0);   // host-built, already swapped (Response.C:132-181)
-        ncomplex = uint64_t (response->get_nchan ()) * response->get_ndat ();
-      }
-      dspsr_amd_filterbank_destroy (fb); fb = 0;
-      check (ctx, dspsr_amd_filterbank_create (ctx, &cfg, &fb), "HIP::FilterbankEngine::setup");
-      check (ctx, dspsr_amd_filterbank_set_kernel (fb, kernel, ncomplex), "HIP::FilterbankEngine::setup");
+      // (a matrix response, Filterbank.C:186-206, is 8 floats per bin: never handed on as a chirp -- dspsr_amd_matrix_engine.h)
+      if (response && response->get_ndim () != 2)
+        throw Error (InvalidState, "HIP::FilterbankEngine::setup", "response ndim=%u != 2: a matrix response needs "
+                     "HIP::MatrixFilterbankEngine", response->get_ndim ());
+      replace (filterbank, response, false, "HIP::FilterbankEngine::setup");
     }
 
     void set_scratch (float* _scratch) { scratch = _scratch; }   // unused: the library owns its scratch
@@ -295,39 +367,24 @@ namespace HIP
     void perform (const dsp::TimeSeries* in, dsp::TimeSeries* out,
                   uint64_t npart, const uint64_t in_step, const uint64_t out_step)
     {
-      const float* ibase = in->get_datptr (0, 0);
-      const uint64_t ics = in->get_nchan () > 1 ? in->get_datptr (1, 0) - ibase : 0;
-      const uint64_t ips = in->get_npol () > 1 ? in->get_datptr (0, 1) - ibase : 0;
-      float* obase = out ? out->get_datptr (0, 0) : 0;      // out == NULL: benchmark only (:265)
-      const uint64_t ocs = out && out->get_nchan () > 1 ? out->get_datptr (1, 0) - obase : 0;
-      const uint64_t ops = out && out->get_npol () > 1 ? out->get_datptr (0, 1) - obase : 0;
+      Chain::FilterbankCall c;
+      c.fb = fb; c.in = in; c.out = out;
+      c.i = rows_of (in);
+      c.o.base = 0; c.o.cs = 0; c.o.ps = 0;                          // out == NULL: benchmark only (:265)
+      if (out) c.o = rows_of (out);
+      c.npart = npart; c.in_step = in_step; c.out_step = out_step;
       // the packed block may stand in for the float rows only if `in` is exactly its unpacked image
       uint64_t step = 0;
       dspsr_amd_filterbank_sizes (fb, 0, 0, &step, 0);
       const bool use_raw = raw.ptr && in->get_input_sample () == raw.input_sample && in->get_ndat () == raw.ndat
                            && in_step == step * in->get_ndim ();
-      const int8_t* rawp = use_raw ? raw.ptr : 0;
+      c.raw = use_raw && out ? raw.ptr : 0;
+      c.raw_layout = raw.layout; c.raw_scale = raw.scale;
       raw.ptr = 0;
       if (chain && out)
-      {
-        Chain::FilterbankCall& c = chain->fbk;
-        chain->clear_consumed ();                                    // `out` is about to be written (or recorded) anew
-        if (c.pending) chain->unfolded_block ();                     // never folded (Subint.h:270): dropped and counted; Error in strict mode
-        c.fb = fb; c.in = in; c.out = out;
-        c.ibase = ibase; c.ics = ics; c.ips = ips; c.obase = obase; c.ocs = ocs; c.ops = ops;
-        c.npart = npart; c.in_step = in_step; c.out_step = out_step;
-        c.raw = rawp; c.raw_layout = raw.layout; c.raw_scale = raw.scale;
-        if (chain->get_deferred ()) { c.pending = true; return; }
-        chain->run_filterbank ();
-        chain->eager_blocks ++;
-        return;
-      }
-      if (rawp && out)
-        check (ctx, dspsr_amd_filterbank_perform_raw (fb, rawp, raw.layout, raw.scale, obase, ocs, ops, npart, out_step),
-               "HIP::FilterbankEngine::perform");
+        chain->filterbank (c);
       else
-        check (ctx, dspsr_amd_filterbank_perform (fb, ibase, ics, ips, obase, ocs, ops, npart, in_step, out_step),
-               "HIP::FilterbankEngine::perform");
+        Chain::run (ctx, c);
     }
 
     //! Filterbank.C:551,664 (Operation::record_time): what was only recorded runs now, as its own launches
@@ -340,14 +397,18 @@ namespace HIP
     //! direct form of the side channel: 8-bit input straight from the BitSeries (fused unpack), always eager
     void perform_raw (const int8_t* raw, int layout, float scale, dsp::TimeSeries* out, uint64_t npart, uint64_t out_step)
     {
-      float* obase = out->get_datptr (0, 0);
-      const uint64_t ocs = out->get_nchan () > 1 ? out->get_datptr (1, 0) - obase : 0;
-      const uint64_t ops = out->get_npol () > 1 ? out->get_datptr (0, 1) - obase : 0;
-      check (ctx, dspsr_amd_filterbank_perform_raw (fb, raw, layout, scale, obase, ocs, ops, npart, out_step),
+      const Rows<float*> o = rows_of (out);
+      check (ctx, dspsr_amd_filterbank_perform_raw (fb, raw, layout, scale, o.base, o.cs, o.ps, npart, out_step),
              "HIP::FilterbankEngine::perform_raw");
     }
 
   protected:
+    //! the library object for `filterbank`, anew (setup of this class and of HIP::MatrixFilterbankEngine)
+    void replace (dsp::Filterbank* filterbank, const dsp::Response* response, bool matrix, const char* method)
+    {
+      replace_filterbank (ctx, fb, filterbank_config (filterbank->get_input (), response, filterbank->get_nchan_subband (),
+                                                      filterbank->get_freq_res (), max_parts, fused_fold), response, matrix, method);
+    }
     dspsr_amd_ctx* ctx;
     dspsr_amd_filterbank* fb;
     Reference::To<Chain> chain;
@@ -388,38 +449,20 @@ namespace HIP
         throw Error (InvalidState, "HIP::ConvolutionEngine::prepare", "no response");
       const dsp::Response* response = convolution->get_response ();
       const dsp::TimeSeries* input = convolution->get_input ();
-      dspsr_amd_filterbank_config cfg;
-      cfg.nchan_subband = 1;
-      cfg.freq_res = response->get_ndat ();                       // npt_bwd
-      cfg.nfilt_pos = response->get_impulse_pos ();
-      cfg.nfilt_neg = response->get_impulse_neg ();
-      cfg.input_nchan = input->get_nchan ();
-      cfg.npol = input->get_npol ();
-      cfg.real_input = input->get_state () == Signal::Nyquist;    // CUFFT_R2C vs C2C (:219-222)
-      cfg.max_parts = 0;
-      cfg.force_four_pass = 0;
-      cfg.fused_fold = DSPSR_AMD_FUSED_AUTO;
-      cfg.split_in_inverse = 0;
+      const dspsr_amd_filterbank_config cfg = filterbank_config (input, response, 1, response->get_ndat () /* npt_bwd */);
       const uint64_t nsamp_step = convolution->get_minimum_samples () - convolution->get_minimum_samples_lost ();
       in_step = nsamp_step * (cfg.real_input ? 1 : 2);             // floats between parts (Convolution.C:386)
       out_step = in_step;                                          // the output is written at the same float offset (:441)
-      dspsr_amd_filterbank_destroy (fb); fb = 0;
-      check (ctx, dspsr_amd_filterbank_create (ctx, &cfg, &fb), "HIP::ConvolutionEngine::prepare");
-      check (ctx, dspsr_amd_filterbank_set_kernel (fb, response->get_datptr (0, 0),
-               uint64_t (response->get_nchan ()) * response->get_ndat ()), "HIP::ConvolutionEngine::prepare");
+      replace_filterbank (ctx, fb, cfg, response, false, "HIP::ConvolutionEngine::prepare");
     }
 
     //! ConvolutionCUDA.cu:552-800
     void perform (const dsp::TimeSeries* in, dsp::TimeSeries* out, unsigned npart)
     {
       if (npart == 0) return;
-      const float* ibase = in->get_datptr (0, 0);
-      const uint64_t ics = in->get_nchan () > 1 ? in->get_datptr (1, 0) - ibase : 0;
-      const uint64_t ips = in->get_npol () > 1 ? in->get_datptr (0, 1) - ibase : 0;
-      float* obase = out->get_datptr (0, 0);
-      const uint64_t ocs = out->get_nchan () > 1 ? out->get_datptr (1, 0) - obase : 0;
-      const uint64_t ops = out->get_npol () > 1 ? out->get_datptr (0, 1) - obase : 0;
-      check (ctx, dspsr_amd_filterbank_perform (fb, ibase, ics, ips, obase, ocs, ops, npart, in_step, out_step),
+      const Rows<const float*> i = rows_of (in);
+      const Rows<float*> o = rows_of (out);
+      check (ctx, dspsr_amd_filterbank_perform (fb, i.base, i.cs, i.ps, o.base, o.cs, o.ps, npart, in_step, out_step),
              "HIP::ConvolutionEngine::perform");
     }
 
@@ -444,44 +487,27 @@ namespace HIP
     {
       if (in->get_ndat () != out->get_ndat ())
         throw Error (InvalidParam, "HIP::DetectionEngine::polarimetry", "input ndat != output ndat");
-      const float* ibase = in->get_datptr (0, 0);
-      float* obase = out->get_datptr (0, 0);
-      const int state = (stokes >= 0 ? stokes == 1 : out->get_state () == Signal::Stokes) ? DSPSR_AMD_STOKES : DSPSR_AMD_COHERENCE;
+      Chain::DetectionCall c;
+      c.ndim = ndim; c.in = in; c.out = out;
+      c.state = (stokes >= 0 ? stokes == 1 : out->get_state () == Signal::Stokes) ? DSPSR_AMD_STOKES : DSPSR_AMD_COHERENCE;
+      c.i = rows_of (in, in->get_nchan (), 2);                       // polarimetry reads two polarisations, whatever npol says
+      c.o = rows_of (out);
+      if (in == out) c.o.ps = c.i.ps;     // the planes of an in-place detection lie where the polarisation rows were (DetectionCUDA.cu:145-149)
+      c.nchan = in->get_nchan (); c.ndat = in->get_ndat ();
       if (chain)
-      {
-        Chain::DetectionCall& c = chain->det;
-        if (c.pending) chain->flush ();
-        chain->require_written (in, "HIP::DetectionEngine::polarimetry");
-        c.ndim = ndim; c.state = state; c.in = in; c.out = out;
-        c.ibase = ibase; c.ics = in->get_nchan () > 1 ? in->get_datptr (1, 0) - ibase : 0; c.ips = in->get_datptr (0, 1) - ibase;
-        c.obase = obase; c.ocs = out->get_nchan () > 1 ? out->get_datptr (1, 0) - obase : 0;
-        // (the planes of an in-place detection lie where the polarisation rows were, DetectionCUDA.cu:145-149)
-        c.ops = in == out ? c.ips : (out->get_npol () > 1 ? out->get_datptr (0, 1) - obase : 0);
-        c.nchan = in->get_nchan (); c.ndat = in->get_ndat ();
-        // recorded only behind a recorded filterbank block whose output this is, in a shape the fused fold writes
-        if (chain->fbk.pending && in == chain->fbk.out && (ndim == 2 || ndim == 4)) { c.pending = true; return; }
-        chain->flush ();
-        chain->run_detection ();
-        return;
-      }
-      check (ctx, dspsr_amd_detect_polarimetry (ctx, state, ndim, ibase,
-               in->get_nchan () > 1 ? in->get_datptr (1, 0) - ibase : 0, in->get_datptr (0, 1) - ibase,
-               obase, out->get_nchan () > 1 ? out->get_datptr (1, 0) - obase : 0,
-               in == out ? uint64_t (in->get_datptr (0, 1) - ibase) : (out->get_npol () > 1 ? out->get_datptr (0, 1) - obase : 0),
-               in->get_nchan (), in->get_ndat ()), "HIP::DetectionEngine::polarimetry");
+        chain->detection (c);
+      else
+        Chain::run (ctx, c);
     }
 
     void square_law (const dsp::TimeSeries* in, dsp::TimeSeries* out)
     {
-      if (chain) { chain->flush (); chain->require_written (in, "HIP::DetectionEngine::square_law"); }
-      const float* ibase = in->get_datptr (0, 0);
-      float* obase = out->get_datptr (0, 0);
-      check (ctx, dspsr_amd_detect_square_law (ctx, out->get_state () == Signal::Intensity, ibase,
-               in->get_nchan () > 1 ? in->get_datptr (1, 0) - ibase : 0,
-               in->get_npol () > 1 ? in->get_datptr (0, 1) - ibase : 0, obase,
-               out->get_nchan () > 1 ? out->get_datptr (1, 0) - obase : 0,
-               out->get_npol () > 1 ? out->get_datptr (0, 1) - obase : 0,
-               in->get_nchan (), in->get_npol (), in->get_ndat ()), "HIP::DetectionEngine::square_law");
+      // (never fused: whatever is recorded runs first)
+      if (chain) { chain->flush (); chain->reader (in, "HIP::DetectionEngine::square_law"); }
+      const Rows<const float*> i = rows_of (in);
+      const Rows<float*> o = rows_of (out);
+      check (ctx, dspsr_amd_detect_square_law (ctx, out->get_state () == Signal::Intensity, i.base, i.cs, i.ps, o.base, o.cs, o.ps,
+                                               in->get_nchan (), in->get_npol (), in->get_ndat ()), "HIP::DetectionEngine::square_law");
     }
 
   protected:
@@ -500,7 +526,7 @@ namespace HIP
   {
   public:
     FoldEngine (dspsr_amd_ctx* _ctx, Chain* _chain = 0)
-      : ctx (_ctx), fold_handle (0), chain (_chain), plan_ndat (0), plan_idat_start (0), d_hits (0), d_hits_size (0)
+      : ctx (_ctx), fold_handle (0), chain (_chain), plan_ndat (0), plan_idat_start (0), d_hits (_ctx)
     {
       use_set_bins = true;                       // plan built inside the library (Fold.C:730-740)
       check (ctx, dspsr_amd_fold_create (ctx, &fold_handle), "HIP::FoldEngine");
@@ -512,7 +538,7 @@ namespace HIP
     ~FoldEngine ()
     {
       if (chain) chain->unregister_fold ();
-      if (d_hits) dspsr_amd_free (ctx, d_hits);
+      d_hits.release ();
       dspsr_amd_fold_destroy (fold_handle);
     }
 
@@ -542,51 +568,20 @@ namespace HIP
       setup ();                                  // Fold.C:968-1011: input, input_span, output, output_span, nchan, npol, ndim
       check (ctx, dspsr_amd_fold_bind_profile (fold_handle, output, output_span, nchan, npol, ndim, d_profiles->get_nbin ()),
              "HIP::FoldEngine::fold");
-      if (chain && chain->fbk.pending)
+      const bool counts_hits = zeroed_samples && hits_nchan == nchan;
+      if (chain)
       {
-        // Deferred mode: the filterbank and the detection of this block have only been recorded.  If this call folds the
-        // WHOLE detected block (no sub-integration boundary inside it: Subint.h:234-309 would fold it in pieces) in a shape
-        // the fused kernel writes, the three operations run as ONE launch group and the channelised data stay on the chip;
-        // otherwise they run now as the separate launches DSPSR asked for and the fold below reads their output.
-        const Chain::FilterbankCall& f = chain->fbk;
-        const Chain::DetectionCall& d = chain->det;
-        const dsp::TimeSeries* in = parent->get_input ();
-        // (one Fold per chain only: a second Fold of the same detected series -- dspsr folding several pulsars,
-        //  LoadToFold1.C:917-955,1206 -- needs the series itself; zeroed samples with per-channel hits are counted from the
-        //  data by the eager kernel, Fold.C:853-866)
-        const bool whole = d.pending && in == d.out && plan_idat_start == 0 && plan_ndat == in->get_ndat ()
-                           && in->get_ndat () == d.ndat && ((npol == 2 && ndim == 2 && d.ndim == 2) || (npol == 1 && ndim == 4 && d.ndim == 4))
-                           && chain->get_nfold () <= 1 && !(zeroed_samples && hits_nchan == nchan);
-        if (whole)
-        {
-          chain->mark_consumed ();
-          chain->fbk.pending = false; chain->det.pending = false;
-          check (ctx, dspsr_amd_filterbank_perform_fold (f.fb, f.raw ? 0 : f.ibase, f.ics, f.ips, f.in_step, f.raw, f.raw_layout,
-                                                        f.raw_scale, d.state, fold_handle, f.npart), "HIP::FoldEngine::fold");
-          chain->fused_blocks ++;
-          synchronized = false;
-          return;
-        }
-        chain->flush ();
+        const Chain::FoldRequest request = { fold_handle, parent->get_input (), plan_idat_start, plan_ndat, npol, ndim, counts_hits };
+        if (chain->fold (request)) { synchronized = false; return; }        // the whole block, in one launch group (deferred mode)
       }
-      else if (chain)
-        chain->flush ();
-      if (chain) chain->require_written (parent->get_input (), "HIP::FoldEngine::fold");
-      if (zeroed_samples && hits_nchan == nchan)
+      if (counts_hits)
       {
         // the input carries zeroed (RFI-excised) samples: hits[] per channel, counted on the device from the data
         // (Fold.C:853-866; CUDA twin fold1bin*hits, FoldCUDA.cu:415-576,622 with hits_on_gpu).  The counts live in a device
         // buffer of this engine and are added to the host PhaseSeries' hits in synch()
         const uint64_t nhits = uint64_t (nchan) * d_profiles->get_nbin ();
-        if (nhits != d_hits_size)
-        {
-          if (d_hits) check (ctx, dspsr_amd_free (ctx, d_hits), "HIP::FoldEngine::fold");
-          void* p = 0;
-          check (ctx, dspsr_amd_malloc (ctx, nhits * sizeof (uint32_t), &p), "HIP::FoldEngine::fold");
-          check (ctx, dspsr_amd_zero (ctx, p, nhits * sizeof (uint32_t)), "HIP::FoldEngine::fold");
-          d_hits = (uint32_t*) p; d_hits_size = nhits;
-        }
-        check (ctx, dspsr_amd_fold_fold_zeroed (fold_handle, input, uint64_t (npol) * input_span, input_span, d_hits),
+        if (nhits != d_hits.size ()) d_hits.replace (nhits, sizeof (uint32_t), true, "HIP::FoldEngine::fold");
+        check (ctx, dspsr_amd_fold_fold_zeroed (fold_handle, input, uint64_t (npol) * input_span, input_span, (uint32_t*) d_hits.get ()),
                "HIP::FoldEngine::fold");
         synchronized = false;
         return;
@@ -606,9 +601,9 @@ namespace HIP
       out->copy_configuration (d_profiles);
       check (ctx, dspsr_amd_copy (ctx, out->internal_get_buffer (), d_profiles->internal_get_buffer (),
                                   d_profiles->internal_get_size (), DSPSR_AMD_D2H), "HIP::FoldEngine::synch");
-      if (d_hits && out->get_hits_nchan () * uint64_t (out->get_nbin ()) == d_hits_size)
+      if (d_hits.get () && out->get_hits_nchan () * uint64_t (out->get_nbin ()) == d_hits.size ())
         // zeroed samples: the per-channel counts made on the device (TransferPhaseSeriesCUDA with transfer_hits)
-        check (ctx, dspsr_amd_copy (ctx, out->get_hits (0), d_hits, d_hits_size * sizeof (uint32_t), DSPSR_AMD_D2H),
+        check (ctx, dspsr_amd_copy (ctx, out->get_hits (0), d_hits.get (), d_hits.size () * sizeof (uint32_t), DSPSR_AMD_D2H),
                "HIP::FoldEngine::synch");
       check (ctx, dspsr_amd_stream_sync (ctx), "HIP::FoldEngine::synch");
       synchronized = true;
@@ -618,7 +613,7 @@ namespace HIP
     void zero ()
     {
       get_profiles ()->zero ();
-      if (d_hits) check (ctx, dspsr_amd_zero (ctx, d_hits, d_hits_size * sizeof (uint32_t)), "HIP::FoldEngine::zero");
+      if (d_hits.get ()) check (ctx, dspsr_amd_zero (ctx, d_hits.get (), d_hits.size () * sizeof (uint32_t)), "HIP::FoldEngine::zero");
     }
 
   protected:
@@ -628,8 +623,7 @@ namespace HIP
     std::vector<unsigned> nbin_hits;
     Reference::To<Chain> chain;
     uint64_t plan_ndat, plan_idat_start;
-    uint32_t* d_hits;                            // zeroed samples: [nchan][nbin] counts on the device
-    uint64_t d_hits_size;
+    DeviceScratch d_hits;                        // zeroed samples: [nchan][nbin] uint32_t counts on the device
   };
 
   //! dsp::TScrunch::Engine (Signal/General/dsp/TScrunch.h:61-69; the reference's twin: CUDA::TScrunchEngine, TScrunchCUDA.cu:204-300,
@@ -639,8 +633,7 @@ namespace HIP
   class TScrunchEngine : public dsp::TScrunch::Engine
   {
   public:
-    TScrunchEngine (dspsr_amd_ctx* _ctx) : ctx (_ctx), carry (0), carry_floats (0) { }
-    ~TScrunchEngine () { if (carry) dspsr_amd_free (ctx, carry); }
+    TScrunchEngine (dspsr_amd_ctx* _ctx) : ctx (_ctx), carry (_ctx) { }
 
     void fpt_tscrunch (const dsp::TimeSeries* in, dsp::TimeSeries* out, unsigned sfactor)
     {
@@ -655,27 +648,18 @@ namespace HIP
       // (the C-ABI treats the rows as a stream; here every call starts a fresh one: nothing carried in, the left-over partial sums
       //  land in a scratch of [nchan][npol][ndim] floats and are dropped)
       const uint64_t need = uint64_t (nchan) * npol * ndim;
-      if (need > carry_floats)
-      {
-        if (carry) dspsr_amd_free (ctx, carry);
-        void* p = 0;
-        check (ctx, dspsr_amd_malloc (ctx, need * sizeof (float), &p), "HIP::TScrunchEngine::fpt_tscrunch");
-        carry = (float*) p; carry_floats = need;
-      }
-      const float* ibase = in->get_datptr (0, 0);
-      float* obase = out->get_datptr (0, 0);
+      if (need > carry.size ()) carry.replace (need, sizeof (float), false, "HIP::TScrunchEngine::fpt_tscrunch");
+      const Rows<const float*> i = rows_of (in);
+      const Rows<float*> o = rows_of (out, nchan, npol);              // as many rows as the input
       uint32_t count = 0;
       uint64_t nout = 0;
-      check (ctx, dspsr_amd_tscrunch_fpt (ctx, ibase, nchan > 1 ? in->get_datptr (1, 0) - ibase : 0, npol > 1 ? in->get_datptr (0, 1) - ibase : 0,
-                                          obase, nchan > 1 ? out->get_datptr (1, 0) - obase : 0, npol > 1 ? out->get_datptr (0, 1) - obase : 0,
-                                          nchan, npol, ndim, in->get_ndat (), sfactor, carry, &count, &nout),
-             "HIP::TScrunchEngine::fpt_tscrunch");
+      check (ctx, dspsr_amd_tscrunch_fpt (ctx, i.base, i.cs, i.ps, o.base, o.cs, o.ps, nchan, npol, ndim, in->get_ndat (), sfactor,
+                                          (float*) carry.get (), &count, &nout), "HIP::TScrunchEngine::fpt_tscrunch");
     }
 
   protected:
     dspsr_amd_ctx* ctx;
-    float* carry;
-    uint64_t carry_floats;
+    DeviceScratch carry;                         // grows only
   };
 
   //! dsp::FScrunch::Engine (Signal/General/dsp/FScrunch.h:56-64; CUDA::FScrunchEngine, FScrunchCUDA.cu:50-90): output channel c =
@@ -692,13 +676,10 @@ namespace HIP
       if (in->get_ndat () == 0)
         return;
       const unsigned nchan = in->get_nchan (), npol = in->get_npol ();
-      const float* ibase = in->get_datptr (0, 0);
-      float* obase = out->get_datptr (0, 0);
-      check (ctx, dspsr_amd_fscrunch_fpt (ctx, ibase, nchan > 1 ? in->get_datptr (1, 0) - ibase : 0, npol > 1 ? in->get_datptr (0, 1) - ibase : 0,
-                                          obase, nchan / sfactor > 1 ? out->get_datptr (1, 0) - obase : 0,
-                                          npol > 1 ? out->get_datptr (0, 1) - obase : 0, nchan, npol,
-                                          in->get_ndat () * uint64_t (in->get_ndim ()), sfactor),
-             "HIP::FScrunchEngine::fpt_fscrunch");
+      const Rows<const float*> i = rows_of (in);
+      const Rows<float*> o = rows_of (out, nchan / sfactor, npol);    // the channels this call writes
+      check (ctx, dspsr_amd_fscrunch_fpt (ctx, i.base, i.cs, i.ps, o.base, o.cs, o.ps, nchan, npol,
+                                          in->get_ndat () * uint64_t (in->get_ndim ()), sfactor), "HIP::FScrunchEngine::fpt_fscrunch");
     }
 
   protected:

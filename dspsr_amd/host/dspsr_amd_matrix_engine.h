@@ -38,25 +38,8 @@ namespace HIP
       if (input->get_npol () != 2)                                              // Filterbank.C:203-205
         throw Error (InvalidState, "dsp::Filterbank::make_preparations", "matrix convolution and input.npol != 2");
       filterbank->set_passband (NULL);          // the engine does not maintain the passband
-      const dsp::Response* response = filterbank->get_response ();
-      dspsr_amd_filterbank_config cfg;
-      cfg.nchan_subband = filterbank->get_nchan_subband ();
-      cfg.freq_res = filterbank->get_freq_res ();
-      cfg.input_nchan = input->get_nchan ();
-      cfg.npol = input->get_npol ();
-      cfg.real_input = input->get_state () == Signal::Nyquist;
-      cfg.nfilt_pos = response->get_impulse_pos ();
-      cfg.nfilt_neg = response->get_impulse_neg ();
-      cfg.max_parts = max_parts;
-      cfg.force_four_pass = 0;
-      cfg.fused_fold = fused_fold;
-      cfg.split_in_inverse = 0;
       if (chain) chain->flush ();
-      dspsr_amd_filterbank_destroy (fb); fb = 0;
-      check (ctx, dspsr_amd_filterbank_create (ctx, &cfg, &fb), "HIP::MatrixFilterbankEngine::setup");
-      check (ctx, dspsr_amd_filterbank_set_response_matrix (fb, response->get_datptr (0, 0),
-                                                            uint64_t (response->get_nchan ()) * response->get_ndat ()),
-             "HIP::MatrixFilterbankEngine::setup");
+      replace (filterbank, filterbank->get_response (), true, "HIP::MatrixFilterbankEngine::setup");
     }
 
     //! Response::get_ndim of what the library object holds: 0 none, 2 complex, 8 Jones

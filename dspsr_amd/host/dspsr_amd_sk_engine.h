@@ -17,9 +17,8 @@
 #include <vector>
 
 #include "dsp/SpectralKurtosis.h"
-#include "Error.h"
 
-#include "dspsr_amd.h"
+#include "dspsr_amd_adaptor_common.h"   // HIP::check, HIP::rows_of
 
 namespace HIP
 {
@@ -45,9 +44,8 @@ namespace HIP
       nchan = input->get_nchan (); npol = input->get_npol ();
       status (dspsr_amd_sk_set_shape (handle, nchan, npol, tscrunch), "HIP::SpectralKurtosisEngine::compute");
       options ("HIP::SpectralKurtosisEngine::compute");
-      uint64_t cs, ps;
-      const float* base = rows (input, cs, ps);
-      status (dspsr_amd_sk_compute (handle, base, cs, ps, input->get_ndat ()), "HIP::SpectralKurtosisEngine::compute");
+      const Rows<const float*> rows = rows_of (input);
+      status (dspsr_amd_sk_compute (handle, rows.base, rows.cs, rows.ps, input->get_ndat ()), "HIP::SpectralKurtosisEngine::compute");
     }
 
     void reset_mask (dsp::BitSeries*) { status (dspsr_amd_sk_reset_mask (handle), "HIP::SpectralKurtosisEngine::reset_mask"); }
@@ -92,10 +90,10 @@ namespace HIP
     {
       if (in->get_memory ()->on_host () || out->get_memory ()->on_host ())
         throw Error (InvalidState, "HIP::SpectralKurtosisEngine::mask", "the TimeSeries are not in device memory");
-      uint64_t ics, ips, ocs, ops;
-      const float* ibase = rows (in, ics, ips);
-      float* obase = const_cast<float*> (rows (out, ocs, ops));
-      status (dspsr_amd_sk_mask (handle, ibase, ics, ips, obase, ocs, ops), "HIP::SpectralKurtosisEngine::mask");
+      // the shape remembered from compute (), the one the library object holds, for both series
+      const Rows<const float*> i = rows_of (in, nchan, npol);
+      const Rows<float*> o = rows_of (out, nchan, npol);
+      status (dspsr_amd_sk_mask (handle, i.base, i.cs, i.ps, o.base, o.cs, o.ps), "HIP::SpectralKurtosisEngine::mask");
     }
 
     //! the call is commented out in the reference (SpectralKurtosis.C:231)
@@ -104,20 +102,9 @@ namespace HIP
     dspsr_amd_sk* get_handle () const { return handle; }
 
   protected:
-    void status (int code, const char* method)
-    {
-      if (code != DSPSR_AMD_OK)
-        throw Error (code == DSPSR_AMD_EINVAL ? InvalidParam : InvalidState, method, "%s", ctx ? dspsr_amd_last_error (ctx) : "no context");
-    }
+    void status (int code, const char* method) { check (ctx, code, method, "no context"); }
     void options (const char* method)
     { status (dspsr_amd_sk_set_options (handle, std_devs, chan_start, chan_end == nchan ? 0 : chan_end, 0, 0, 0), method); }
-    const float* rows (const dsp::TimeSeries* t, uint64_t& cs, uint64_t& ps) const
-    {
-      const float* base = t->get_datptr (0, 0);
-      cs = nchan > 1 ? uint64_t (t->get_datptr (1, 0) - base) : 0;
-      ps = npol > 1 ? uint64_t (t->get_datptr (0, 1) - base) : 0;
-      return base;
-    }
     void fetch_mask (const char* method)
     {
       host_mask.resize (size_t (dspsr_amd_sk_npart (handle)) * nchan + 1);       // (one spare element: never empty)

@@ -1,18 +1,20 @@
 // FUNCTIONAL MINIATURE (see ../Error.h): dsp::Response / dsp::Filterbank getters and dsp::Filterbank::Engine
-// (Signal/General/dsp/FilterbankEngine.h:15-44, Filterbank.h, Response.h) as the engine's setup() reads them.
+// (Signal/General/dsp/FilterbankEngine.h:15-44, Filterbank.h, Response.h) as the engine's setup() reads them.  Response::get_ndim ()
+// (Shape.h): 2 = complex, 8 = one Jones matrix per bin in the order f11, f21, f22, f12 (Response.C:614-640).
 #pragma once
 #include "dsp/Memory.h"
 namespace dsp {
   class Response : public Reference::Able {
   public:
-    Response () : impulse_pos (0), impulse_neg (0), nchan (1), ndat (1) {}
+    Response () : impulse_pos (0), impulse_neg (0), nchan (1), ndat (1), ndim (2) {}
     unsigned get_impulse_pos () const { return impulse_pos; }
     unsigned get_impulse_neg () const { return impulse_neg; }
     unsigned get_nchan () const { return nchan; }
     unsigned get_ndat () const { return ndat; }
+    unsigned get_ndim () const { return ndim; }
     const float* get_datptr (unsigned, unsigned) const { return kernel.empty () ? 0 : &kernel[0]; }
-    unsigned impulse_pos, impulse_neg, nchan, ndat;
-    std::vector<float> kernel;                              // nchan*ndat complex
+    unsigned impulse_pos, impulse_neg, nchan, ndat, ndim;
+    std::vector<float> kernel;                              // nchan*ndat*ndim floats
   };
   class Filterbank : public Reference::Able {
   public:

@@ -1,5 +1,5 @@
 // Drives HIP::MatrixFilterbankEngine (dspsr_amd/host/dspsr_amd_matrix_engine.h) against the miniature dsp classes of
-// tests/host_mock, with tests/host_mock_matrix in front on the include path (its dsp::Response has get_ndim ()).
+// tests/host_mock (its dsp::Response has get_ndim ()).
 // Without a device: the reference's two errors (Filterbank.C:199-205) and the base engine's refusal of a matrix response are
 // thrown before any library call; exit code 77.  On a GPU: an ndim 8 response reaches dspsr_amd_filterbank_set_response_matrix,
 // an ndim 2 response dspsr_amd_filterbank_set_kernel, each bit-identical to the C-ABI driven directly.

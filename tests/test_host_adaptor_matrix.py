@@ -1,6 +1,6 @@
 """HIP::MatrixFilterbankEngine (dspsr_amd/host/dspsr_amd_matrix_engine.h): the filterbank adaptor for responses that may be
-matrix responses.  tests/matrix_adaptor_driver.cpp is built against the miniatures of tests/host_mock with
-tests/host_mock_matrix in front of them on the include path (a dsp::Response that also has get_ndim ()).  Without a device the
+matrix responses.  tests/matrix_adaptor_driver.cpp is built against the miniatures of tests/host_mock (its dsp::Response has
+get_ndim (), as the real one has through Shape.h).  Without a device the
 driver checks that the reference's two errors (Filterbank.C:199-205) are thrown and that the base engine refuses a matrix
 response, and stops with exit code 77; on a GPU an ndim 8 response must reach the matrix entry point and an ndim 2 response the
 scalar one, each bit-identical to the C-ABI driven directly."""
@@ -14,9 +14,9 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 def _build_driver(tmp_path):
     exe = tmp_path / "matrix_adaptor_driver"
-    cmd = ["g++", "-std=c++11", "-O1", "-Wall", "-Wno-unused-function", "-I", os.path.join(ROOT, "tests", "host_mock_matrix"),
-           "-I", os.path.join(ROOT, "tests", "host_mock"), "-I", os.path.join(ROOT, "dspsr_amd", "host"),
-           "-I", os.path.join(ROOT, "include"), os.path.join(ROOT, "tests", "matrix_adaptor_driver.cpp"), "-o", str(exe),
+    cmd = ["g++", "-std=c++11", "-O1", "-Wall", "-Wno-unused-function", "-I", os.path.join(ROOT, "tests", "host_mock"),
+           "-I", os.path.join(ROOT, "dspsr_amd", "host"), "-I", os.path.join(ROOT, "include"),
+           os.path.join(ROOT, "tests", "matrix_adaptor_driver.cpp"), "-o", str(exe),
            "-L", os.path.join(ROOT, "dspsr_amd"), "-ldspsr_amd", "-Wl,-rpath," + os.path.join(ROOT, "dspsr_amd")]
     p = subprocess.run(cmd, capture_output=True, text=True)
     assert p.returncode == 0, p.stderr[-4000:]

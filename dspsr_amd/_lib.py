@@ -15,8 +15,11 @@ OK, EINVAL, EHIP, ENOMEM, ESTATE = 0, -1, -2, -3, -4
 H2D, D2H, D2D = 1, 2, 3
 RAW_GENERIC, RAW_CASPSR, RAW_UWB16 = 0, 1, 2
 RAW_MEERKAT, RAW_MEERKAT_SWAP = 3, 4      # heaps of 256 samples per (pol, chan) run; _SWAP: odd and even samples exchanged (MKBFRo)
+RAW_TWOBIT = 5                            # two-bit real samples, whole excision windows (FilterbankEngine.set_twobit; not a C-ABI layout)
 HEAP_NSAMP = 256
 HEAP_MACHINES = {"MKBF": RAW_MEERKAT, "MKBFRo": RAW_MEERKAT_SWAP}   # INSTRUMENT -> layout (kat/MeerKATUnpacker.C: sample_swap 2 for MKBFRo)
+TWOBIT_OFFSET_BINARY, TWOBIT_SIGN_MAGNITUDE, TWOBIT_TWOS_COMPLEMENT = 0, 1, 2      # DSPSR_AMD_TWOBIT_*: TwoBitTable's code map
+TWOBIT_MACHINES = {"CPSR2": TWOBIT_OFFSET_BINARY}   # INSTRUMENT -> table type (cpsr2/CPSR2TwoBitCorrection.C: matches, OffsetBinary)
 COHERENCE, STOKES, INTENSITY, PPQQ = 0, 1, 2, 3
 FUSED_AUTO, FUSED_ALWAYS, FUSED_NEVER = 0, 1, 2
 REDUCE_SUM, REDUCE_GATHER = 0, 1
@@ -35,6 +38,18 @@ def raw_at(layout: int, first_sample: int) -> int:
 def is_heaps(layout: int) -> bool:
     """The layout word names one of the heap layouts (with or without a first sample)."""
     return layout >= 0 and (layout & 0xff) in (RAW_MEERKAT, RAW_MEERKAT_SWAP)
+
+
+def twobit_at(first_sample: int) -> int:
+    """The layout word of a two-bit block whose first sample lies at `first_sample` of its first excision window (as raw_at for heaps;
+    RAW_TWOBIT is a form of the Python engine alone: FilterbankEngine unpacks it and calls the float entry points)."""
+    if first_sample < 0:
+        raise ValueError("twobit_at: first_sample %d is negative" % first_sample)
+    return RAW_TWOBIT | (first_sample << 8)
+
+
+def is_twobit(layout: int) -> bool:
+    return layout >= 0 and (layout & 0xff) == RAW_TWOBIT
 
 
 def heap_block_bytes(first_sample: int, nsamp: int, nchan: int, npol: int) -> int:
@@ -123,6 +138,8 @@ SYMBOLS = {
     "dspsr_amd_detect_square_law": (_i, [_vp, _i, _vp, _u64, _u64, _vp, _u64, _u64, _u32, _u32, _u64]),
     "dspsr_amd_unpack_fpt": (_i, [_vp, _vp, _f, _u32, _u32, _u32, _u64, _vp, _u64, _u64]),
     "dspsr_amd_unpack_heaps_fpt": (_i, [_vp, _vp, _i, _f, _u32, _u32, _u64, _vp, _u64, _u64]),
+    "dspsr_amd_twobit_check": (_i, [_u64, _i, _u32, _u32, _u32, _u64, _u32, _u32, _u64, _u64, C.c_char_p, _sz]),
+    "dspsr_amd_twobit_unpack": (_i, [_vp, _vp, _i, _u32, _u32, _u32, _u64, _u32, _u32, _vp, _vp, _u64, _vp, _vp]),
     "dspsr_amd_detect_raw": (_i, [_vp, _vp, _f, _u32, _u32, _u64, _i, _u32, _vp, _u64, _u64, _vp, C.POINTER(_u32), C.POINTER(_u64)]),
     "dspsr_amd_tfp_filterbank": (_i, [_vp, C.POINTER(TfpConfig), _vp, _i, _f, _vp, _u64]),
     "dspsr_amd_fold_create": (_i, [_vp, _pp]),

@@ -53,6 +53,7 @@ extern "C" void dspsr_amd_ctx_destroy(dspsr_amd_ctx* ctx)
   if (!ctx) return;
   (void)hipStreamSynchronize(ctx->stream);
   if (ctx->tw) (void)hipFree(ctx->tw);
+  if (ctx->window_levels) (void)hipFree(ctx->window_levels);
   if (ctx->own_stream) (void)hipStreamDestroy(ctx->stream);
   delete ctx;
 }

@@ -14,6 +14,8 @@ struct dspsr_amd_ctx {
   bool own_stream;
   dspsr_amd::cf* tw;  // exp(-2*pi*i*j/TWN), j < TWN (built in double on the host)
   uint32_t ncu;       // compute units of the device (queried once, at context creation)
+  float2* window_levels = nullptr;   // twobit.hip: the (lo, hi) pair of every (digitiser, window) of a call; only grows
+  size_t window_levels_count = 0;
   char error[512];
 };
 

@@ -249,13 +249,17 @@ def read_dump(path):
 
 
 class DadaFile:
-    """dsp::DADAFile (DADAFile.C:149-180) + the block loop of dsp::IOManager: an 8-bit DADA file cut into the blocks
-    LoadToFold consumes."""
+    """dsp::DADAFile (DADAFile.C:149-180) + the block loop of dsp::IOManager: an 8-bit DADA file, or CPSR2's two-bit one, cut
+    into the blocks LoadToFold consumes."""
 
     def __init__(self, path: str):
         self.path = path
         self.header, self.header_bytes = read_header(path)
         self.info, self.extras = observation(self.header)
+        self.twobit = self.extras["nbit"] == 2
+        if self.twobit:
+            self._open_twobit(path)
+            return
         if self.extras["nbit"] != 8:
             raise DspsrAmdError("dspsr_amd.DadaFile: NBIT=%d; this path reads 8-bit samples" % self.extras["nbit"])
         self.bytes_per_sample = self.info.nchan * self.info.npol * self.info.ndim
@@ -272,11 +276,40 @@ class DadaFile:
         self._map = np.memmap(path, dtype=np.int8, mode="r", offset=self.header_bytes,
                               shape=(self.ndat * self.bytes_per_sample,)) if self.ndat else np.zeros(0, np.int8)
 
+    def _open_twobit(self, path):
+        """NBIT 2: CPSR2's two-bit real samples (CPSR2TwoBitCorrection::matches: INSTRUMENT CPSR2, NBIT 2, Nyquist; offset binary):
+        one channel, one or two digitisers interleaved byte by byte, four samples per byte."""
+        info = self.info
+        if info.machine not in _lib.TWOBIT_MACHINES:
+            raise DspsrAmdError("dspsr_amd.DadaFile: NBIT=2 with INSTRUMENT %s: two-bit samples are read for INSTRUMENT %s alone "
+                                "(the APSR, Mark5, VDIF and sub-byte layouts are not built)" % (info.machine, ", ".join(sorted(_lib.TWOBIT_MACHINES))))
+        if info.ndim != 1 or info.nchan != 1 or info.npol not in (1, 2):
+            raise DspsrAmdError("dspsr_amd.DadaFile: INSTRUMENT %s with NBIT 2 is one channel of real samples from one or two digitisers "
+                                "(NDIM 1, NCHAN 1, NPOL 1 | 2); the header says NDIM=%d NCHAN=%d NPOL=%d"
+                                % (info.machine, info.ndim, info.nchan, info.npol))
+        import dataclasses
+        self.info = dataclasses.replace(info, nbit=2)
+        self.table_type = _lib.TWOBIT_MACHINES[info.machine]
+        self.heaps = False
+        self.bytes_per_sample = None                                    # a quarter of a byte per digitiser
+        nbytes = os.path.getsize(path) - self.header_bytes
+        self.ndat = (nbytes // info.npol) * 4                           # whole bytes of every digitiser
+        self._map = np.memmap(path, dtype=np.int8, mode="r", offset=self.header_bytes,
+                              shape=(self.ndat // 4 * info.npol,)) if self.ndat else np.zeros(0, np.int8)
+
+    def _usable(self, lt):
+        """Samples the block loop reads.  Two-bit: the whole excision windows (Input's resolution: the unpacker takes whole
+        windows, what follows the file's last one is dropped)."""
+        if not self.twobit:
+            return self.ndat
+        return (self.ndat // lt.twobit.nsample) * lt.twobit.nsample
+
     def nblocks(self, lt):
         """(whole blocks, parts of the ragged last block)."""
-        if self.ndat < lt.nsamp_overlap + lt.nsamp_step:
+        ndat = self._usable(lt)
+        if ndat < lt.nsamp_overlap + lt.nsamp_step:
             return 0, 0
-        nparts = (self.ndat - lt.nsamp_overlap) // lt.nsamp_step
+        nparts = (ndat - lt.nsamp_overlap) // lt.nsamp_step
         return divmod(nparts, lt.cfg.parts_per_block)
 
     def blocks(self, lt, channel=None):
@@ -286,7 +319,9 @@ class DadaFile:
         channel = g: only input channel g's bytes ([t][pol][dim]), what rank g of a sub-band sharded run reads.
         A file of heaps (MKBF / MKBFRo) yields (the whole heaps that hold the block, npart, first_sample): the block starts at
         sample first_sample = (b * parts_per_block * nsamp_step) & 255 of its first heap; channel = g: that channel's runs, a block
-        of heaps with nchan = 1."""
+        of heaps with nchan = 1.
+        A two-bit file (NBIT 2) yields (the whole excision windows that hold the block, npart, first_sample) likewise; a file
+        shorter than one window gives no blocks."""
         full, rest = self.nblocks(lt)
         ppb, step, ovl, bps = lt.cfg.parts_per_block, lt.nsamp_step, lt.nsamp_overlap, self.bytes_per_sample
         per_chan = self.info.npol * self.info.ndim
@@ -294,6 +329,15 @@ class DadaFile:
             npart = ppb if b < full else rest
             nsamp = npart * step + ovl
             s0 = b * ppb * step
+            if self.twobit:
+                if channel is not None:
+                    raise DspsrAmdError("dspsr_amd.DadaFile.blocks: a two-bit file holds one channel; channel=%d asked" % channel)
+                # whole windows from the one that holds the block's first sample; first_sample: where in it that sample lies
+                ns = lt.twobit.nsample
+                wb = (ns // 4) * self.info.npol
+                first = s0 % ns
+                yield self._map[(s0 // ns) * wb:-(-(s0 + nsamp) // ns) * wb], npart, first
+                continue
             if self.heaps:
                 first = s0 % HEAP_NSAMP
                 h0, nheap = s0 // HEAP_NSAMP, -(-(first + nsamp) // HEAP_NSAMP)
@@ -347,7 +391,7 @@ def fold_file(path, cfg, polyco=None, device=0, stream=None, reference_phase=0.0
     if f.nblocks(lt) == (0, 0):
         lt.close()
         raise DspsrAmdError("dspsr_amd.fold_file: %s holds %d samples, fewer than one overlap-save part (%d)"
-                            % (path, f.ndat, lt.nsamp_overlap + lt.nsamp_step))
+                            % (path, f._usable(lt), lt.nsamp_overlap + lt.nsamp_step))
     lt.process_host_blocks(f.blocks(lt))
     if lt.ndat_total or lt.pulsars:
         lt.finish_subint()

@@ -214,6 +214,7 @@ class FilterbankEngine(_Owned):
         self.max_parts = max(1, int(max_parts))
         self.fuse_heaps = bool(fuse_heaps)
         self._heap_rows = None      # float rows of an unpacked block of heaps: allocated by the first call that needs them
+        self._twobit = None         # set_twobit: how a RAW_TWOBIT block is unpacked
         a, b, c, d = C.c_uint64(), C.c_uint64(), C.c_uint64(), C.c_uint32()
         lib.dspsr_amd_filterbank_sizes(h, C.byref(a), C.byref(b), C.byref(c), C.byref(d))
         self.nsamp_fft, self.nsamp_overlap, self.nsamp_step, self.nkeep = a.value, b.value, c.value, d.value
@@ -270,7 +271,10 @@ class FilterbankEngine(_Owned):
     def _unpacked_heaps(self, raw, layout, scale, npart):
         """A block of heaps this object does not read itself (or fuse_heaps=False), unpacked into float rows owned by the engine:
         (rows [input_nchan][npol][2 * nsamp], in_step), or None when the block goes to the library as it is.  The rows are
-        allocated on first use for max_parts parts (a longer call allocates again)."""
+        allocated on first use for max_parts parts (a longer call allocates again).  A RAW_TWOBIT block (set_twobit) takes the same
+        way through unpack_twobit; its weights stay in self.twobit_weights."""
+        if raw is not None and _lib.is_twobit(layout):
+            return self.unpack_twobit(raw, layout >> 8, npart)[:2]
         if raw is None or not _lib.is_heaps(layout) or (self.fuse_heaps and self.takes_heaps()):
             return None
         import torch
@@ -286,6 +290,47 @@ class FilterbankEngine(_Owned):
             unpack_heaps_fpt(self.ctx, raw, self._heap_rows, c.input_nchan, c.npol, layout, scale,
                              ndat=npart * self.nsamp_step + self.nsamp_overlap)
         return self._heap_rows, 2 * self.nsamp_step
+
+    def set_twobit(self, nsample, nlow_min, nlow_max, levels, table_type=_lib.TWOBIT_OFFSET_BINARY):
+        """The two-bit form of the raw entry points (layout RAW_TWOBIT, next to the heap form): how a two-bit block is unpacked --
+        the excision window, its limits, the level table float32 [nlow_max - nlow_min + 1][2] (twobit.limits, twobit.levels) and
+        the code table.  One input channel of real samples."""
+        c = self.cfg
+        if not c.real_input or c.input_nchan != 1:
+            raise DspsrAmdError("dspsr_amd.FilterbankEngine.set_twobit: two-bit input is one channel of real samples; the object was set "
+                                "up for %s input of %d channels" % ("real" if c.real_input else "complex", c.input_nchan))
+        twobit_check(0, table_type, c.npol, nsample, 0, 0, nlow_min, nlow_max)
+        import torch
+        lev = np.ascontiguousarray(levels, dtype=np.float32)
+        if lev.shape != (nlow_max - nlow_min + 1, 2):
+            raise DspsrAmdError("dspsr_amd.FilterbankEngine.set_twobit: the level table is %s, [%d][2] needed" % (lev.shape, nlow_max - nlow_min + 1))
+        self._twobit = (int(nsample), int(nlow_min), int(nlow_max), torch.from_numpy(lev).to("cuda:%d" % self.ctx.device), int(table_type))
+        self._twobit_rows = None
+        self.twobit_weights = self.twobit_nlow = None      # per digitiser and window of the last block unpacked, before mask_weights
+
+    def unpack_twobit(self, raw, first_sample, npart):
+        """A RAW_TWOBIT block (the whole windows from the one that holds the call's first sample, `first_sample` inside it) unpacked
+        into float rows owned by the engine: (rows [1][npol][nsamp], in_step, weights) for the float entry points -- weights: device
+        int32 [npol][nwindow], 0 / 1 per digitiser (also self.twobit_weights; n_low in self.twobit_nlow).  The rows are allocated
+        on first use for max_parts parts (a longer call allocates again), and placed so that the unpacker stores whole float4."""
+        import torch
+        if getattr(self, "_twobit", None) is None:
+            raise DspsrAmdError("dspsr_amd.FilterbankEngine: a RAW_TWOBIT block needs set_twobit() first")
+        nsample, nlow_min, nlow_max, levels, table_type = self._twobit
+        c = self.cfg
+        nsamp = npart * self.nsamp_step + self.nsamp_overlap if npart else 0
+        parts = max(npart, self.max_parts)
+        need = (parts * self.nsamp_step + self.nsamp_overlap + 3) // 4 * 4 + 4
+        if self._twobit_rows is None or self._twobit_rows.shape[1] < need or self._twobit_rows.device != raw.device:
+            self._twobit_rows = torch.empty((c.npol, need), dtype=torch.float32, device=raw.device)
+        nwindow = -(-(first_sample + nsamp) // nsample) if nsamp else 0
+        self.twobit_weights = torch.empty((c.npol, nwindow), dtype=torch.int32, device=raw.device)
+        self.twobit_nlow = torch.empty((c.npol, nwindow), dtype=torch.int32, device=raw.device)
+        rows = self._twobit_rows[:, first_sample % 4:first_sample % 4 + nsamp]       # (row + n - first_sample: 16-byte aligned at words)
+        if nsamp:
+            twobit_unpack(self.ctx, raw, rows, levels, self.twobit_weights, nsample, nlow_min, nlow_max, table_type, first_sample, nsamp,
+                          nlow=self.twobit_nlow)
+        return rows.unsqueeze(0), self.nsamp_step, self.twobit_weights
 
     def perform(self, inp, out, npart, in_step, out_step):
         ics, ips = _strides3(inp)
@@ -503,6 +548,48 @@ def unpack_heaps_fpt(ctx: Context, raw, out, nchan, npol, layout, scale=1.0, nda
     ocs, ops = _strides3(out)
     _check(ctx.handle, lib.dspsr_amd_unpack_heaps_fpt(ctx.handle, raw.data_ptr(), layout, scale, nchan, npol, ndat, out.data_ptr(), ocs, ops),
            "dspsr_amd_unpack_heaps_fpt")
+    return out
+
+
+def twobit_block_bytes(first_sample, ndat, nsample, npol):
+    """Bytes of the whole windows that hold `ndat` samples from `first_sample` of the first window on."""
+    return -(-(first_sample + ndat) // nsample) * (nsample // 4) * npol if ndat > 0 else 0
+
+
+def twobit_check(raw_addr, table_type, npol, nsample, first_sample, ndat, nlow_min, nlow_max, out_addr=0, out_pol_stride=None):
+    """dspsr_amd_twobit_check: what dspsr_amd_twobit_unpack refuses, without a device (addresses as integers)."""
+    _host_check(lib.dspsr_amd_twobit_check, raw_addr, table_type, npol, nsample, first_sample, ndat, nlow_min, nlow_max, out_addr,
+                ndat if out_pol_stride is None else out_pol_stride)
+
+
+def twobit_unpack(ctx: Context, raw, out, levels, weights, nsample, nlow_min, nlow_max, table_type=_lib.TWOBIT_OFFSET_BINARY,
+                  first_sample=0, ndat=None, nlow=None):
+    """dsp::TwoBitCorrection on the device: raw = device uint8 / int8 block of whole windows (4-byte aligned; byte k belongs to
+    digitiser k % npol, four samples per byte, first sample in the top bits), out = float32 device rows [npol][>= ndat], levels =
+    device float32 [nlow_max - nlow_min + 1][2] (twobit.levels), weights = device int32 [npol][nwindow] (per digitiser, 0 / 1,
+    before mask_weights), nlow = the same shape or None.  The rows receive samples first_sample ... first_sample + ndat - 1 of the
+    block.  ndat=None: all the block holds behind first_sample."""
+    npol = out.shape[0]
+    assert out.dim() == 2 and out.stride(1) == 1, "rows must be contiguous"
+    per = (nsample // 4) * npol
+    if ndat is None:
+        ndat = (raw.numel() // per) * nsample - first_sample if per else 0
+    need = twobit_block_bytes(first_sample, ndat, nsample, npol) if nsample else 0
+    nwindow = need // per if per else 0
+    if ndat < 0 or raw.numel() < need:
+        raise DspsrAmdError("dspsr_amd.twobit_unpack: block holds %d bytes, %d needed" % (raw.numel(), need))
+    if out.shape[1] < ndat:
+        raise DspsrAmdError("dspsr_amd.twobit_unpack: out is %s, [%d][>= %d] needed" % (tuple(out.shape), npol, ndat))
+    if levels.numel() < 2 * (nlow_max - nlow_min + 1):
+        raise DspsrAmdError("dspsr_amd.twobit_unpack: the level table holds %d floats, %d needed"
+                            % (levels.numel(), 2 * (nlow_max - nlow_min + 1)))
+    for name, t in (("weights", weights), ("nlow", nlow)):
+        if t is not None and (t.element_size() != 4 or not t.is_contiguous() or tuple(t.shape) != (npol, nwindow)):
+            raise DspsrAmdError("dspsr_amd.twobit_unpack: %s must be contiguous 32-bit [%d][%d], got %s" % (name, npol, nwindow, tuple(t.shape)))
+    _check(ctx.handle, lib.dspsr_amd_twobit_unpack(ctx.handle, raw.data_ptr(), table_type, npol, nsample, first_sample, ndat, nlow_min,
+                                                   nlow_max, levels.data_ptr(), out.data_ptr(), out.stride(0) if npol > 1 else ndat,
+                                                   weights.data_ptr(), nlow.data_ptr() if nlow is not None else None),
+           "dspsr_amd_twobit_unpack")
     return out
 
 

@@ -21,7 +21,7 @@ import numpy as np
 from . import _lib
 from .engine import (Context, ConvolutionEngine, CyclicFoldEngine, Dedispersion, DetectionEngine, DspsrAmdError, SpectralKurtosisEngine, FilterbankEngine, FoldEngine, PhaseLockedFilterbankEngine, plfb_check_shape, Rescale, SampleDelay, add_fpt, copy_data_fpt, fourth_moment,
                      dedispersion_sample_delays, detect_raw, eight_bit_scale, fscrunch_fpt, pscrunch_tfp, sigproc_digitize, sigproc_digitize_fpt,
-                     tfp_filterbank, tscrunch_fpt)
+                     tfp_filterbank, tscrunch_fpt, twobit_block_bytes)
 
 
 def move_tail_fpt(ctx, buf, dst, src, n, unit=1):
@@ -102,6 +102,10 @@ class Config:
     sk_no_fscr: bool = False               # -skz_no_fscr / -skz_no_tscr / -skz_no_ft: disable one of the three detections
     sk_no_tscr: bool = False
     sk_no_ft: bool = False
+    excision_nsample: int = 0              # -2n: samples per window of the two-bit unpacker's power estimate (0: 512); two-bit input only
+    excision_threshold: float = -1.0       # -2t: the sampling threshold at record time in sigma (<= 0: 0.9674)
+    excision_cutoff: float = -1.0          # -2c: excision cutoff in standard deviations of n_low (< 0: 10; 0: keep every window)
+                                           # (LoadToFoldConfig.C:22-28, LoadToFold1.C:731-743)
 
 
 @dataclass
@@ -1069,6 +1073,60 @@ def fourth_moment_check(cfg: "Config", ntargets=0, subband=None):
     return dataclasses.replace(cfg, stokes=True, ndim=4, fused_fold=False, force_fused=False)
 
 
+@dataclass
+class TwoBitPlan:
+    """dsp::TwoBitCorrection of a two-bit run (NBIT 2): the excision window, its limits, the level table and the books."""
+    nsample: int
+    threshold: float
+    cutoff: float
+    nlow_min: int
+    nlow_max: int
+    table_type: int
+    levels: object                    # float32 [nlow_max - nlow_min + 1][2]
+    first_sample: int = 0             # of the block in hand, inside its first window
+    discarded_weights: int = 0        # ExcisionUnpacker::unpack: zero weights after mask_weights, summed over the blocks
+    blocks_fused: int = 0             # blocks that folded inside the filterbank's last pass (no zero weight)
+    blocks_weighted: int = 0          # blocks that took Detection + Fold with weights
+
+
+def twobit_check(cfg: "Config", info: "InputInfo", ntargets=0, subband=None, dump_before=()):
+    """What a two-bit run refuses, before any device resource is opened, and its plan (LoadToFold1.C:731-743)."""
+    from . import twobit
+    who = "dspsr_amd.LoadToFold: two-bit input (NBIT 2)"
+    for on, what in ((cfg.cyclic_nchan > 0, "-cyclic"), (cfg.plfb_nbin > 0, "-G"), (fourth_moment_active(cfg), "-4"),
+                     (cfg.interchan_dedispersion, "-K"), (cfg.zap_rfi, "-R"), (cfg.sk_zap, "-skz"), (cfg.calibrator is not None, "-pac")):
+        if on:
+            raise DspsrAmdError("%s with %s is not built: carrying the unpacker's weights through it is open" % (who, what))
+    if ntargets > 1:
+        raise DspsrAmdError("%s folds one pulsar (%d targets given): the weights of several folds are open" % (who, ntargets))
+    if cfg.convolve_when != "during":
+        raise DspsrAmdError("%s is built for -F N:D (convolve_when = during), not %r: the weights of dsp::Convolution are open"
+                            % (who, cfg.convolve_when))
+    if subband is not None:
+        raise DspsrAmdError("%s is not built for sub-band sharded runs (subband=%d)" % (who, subband))
+    if dump_before:
+        raise DspsrAmdError("%s with the dump taps is not built" % who)
+    if info.machine not in _lib.TWOBIT_MACHINES:
+        raise DspsrAmdError("%s is read for INSTRUMENT %s alone, not %s" % (who, ", ".join(sorted(_lib.TWOBIT_MACHINES)), info.machine))
+    if info.ndim != 1 or info.nchan != 1 or info.npol not in (1, 2):
+        raise DspsrAmdError("%s is one channel of real samples from one or two digitisers (ndim=%d nchan=%d npol=%d)"
+                            % (who, info.ndim, info.nchan, info.npol))
+    nsample = cfg.excision_nsample or twobit.NSAMPLE
+    threshold = cfg.excision_threshold if cfg.excision_threshold > 0 else twobit.THRESHOLD
+    cutoff = cfg.excision_cutoff if cfg.excision_cutoff >= 0 else twobit.CUTOFF_SIGMA
+    if nsample % 4 or not 4 <= nsample <= twobit.NSAMPLE_MAX:
+        raise DspsrAmdError("%s: excision_nsample=%d must be a multiple of 4 in [4, %d]" % (who, nsample, twobit.NSAMPLE_MAX))
+    nlow_min, nlow_max = twobit.limits(nsample, threshold, cutoff)
+    return TwoBitPlan(nsample, threshold, cutoff, nlow_min, nlow_max, _lib.TWOBIT_MACHINES[info.machine],
+                      twobit.levels(nsample, nlow_min, nlow_max, threshold))
+
+
+def refuse_twobit(who, info):
+    """Plan-time refusal of a driver that has no two-bit unpacker."""
+    if getattr(info, "nbit", 8) == 2:
+        raise DspsrAmdError("%s: two-bit input (NBIT 2) is not built on this path; dspsr_amd.LoadToFold folds it with -F N:D" % who)
+
+
 def sk_check(cfg: "Config", info: "InputInfo", ntargets=0, subband=None, dump_before=()):
     """What a -skz run refuses, on the host, after every refusal the run had without it.  Returns the channel range the engine gets."""
     who = "dspsr_amd.LoadToFold: spectral kurtosis (-skz)"
@@ -1322,6 +1380,8 @@ class DetectFold:
         617-618)] -> fold, by piece or by pulsar.  Without -K: no head room, nothing carried, every sample delivered."""
         lt, cfg, nd, sd, ndat = self.lt, self.lt.cfg, self.lt.cfg.ndim, self.lt.sd, npart * self.lt.nkeep
         state = _lib.STOKES if cfg.stokes else _lib.COHERENCE
+        if lt.twobit is not None:
+            return self._process_twobit(raw, npart, events, state)
         if "Detection" in lt.dumps:                          # the filterbank's complex output: one extra pass, taps only
             if lt._dump_cplx is None:
                 lt._dump_cplx = _device_empty(lt.ctx, (lt.nchan_out, 2, 2 * cfg.parts_per_block * lt.nkeep))
@@ -1351,10 +1411,46 @@ class DetectFold:
         sd.keep_tail(lt.ctx, lt.detected, ndat, nout, nd)
         return nout
 
+    def _process_twobit(self, raw, npart, events, state):
+        """A two-bit block: dsp::TwoBitCorrection into float rows (the per-digitiser weights come back with them), then the
+        weights' way to the fold on the host -- mask_weights (ExcisionUnpacker.C:243-247), convolve_weights(nsamp_fft, nsamp_step)
+        and scrunch_weights(tres_ratio) (Filterbank.C:279-306) -- and the chain every block takes, on the float entry points.  A
+        block without a zero weight folds like any other (fused where the front end fuses); one with a zero weight takes
+        Detection + Fold, whose plan drops the samples of a zero weight (Fold.C:686-716,746-763).  Blocks overlap by the
+        filterbank's tail, whose windows are unpacked again with the block that follows: the weights of a carried tail are
+        those it had."""
+        from . import twobit
+        lt, cfg, nd, tb, ndat = self.lt, self.lt.cfg, self.lt.cfg.ndim, self.lt.twobit, npart * self.lt.nkeep
+        nsamp = npart * lt.nsamp_step + lt.nsamp_overlap
+        rows, in_step, wdev = lt._op("TwoBitCorrection", lambda: lt.fb.unpack_twobit(raw, tb.first_sample, npart))
+        lt.ctx.synchronize()
+        w = twobit.mask_weights(wdev.cpu().numpy().view(np.uint32))
+        tb.discarded_weights += int((w[0] == 0).sum())                  # get_nzero of the first row
+        row, npw, widat = twobit.convolve_weights(w[0], nsamp, tb.nsample, tb.first_sample, lt.nsamp_step + lt.nsamp_overlap, lt.nsamp_step)
+        row, npw, widat = twobit.scrunch_weights(row, npw, widat, (lt.nsamp_step + lt.nsamp_overlap) // lt.response.ndat, ndat=nsamp)
+        lt._weights = (row, npw, widat) if not row.all() else None
+        try:
+            pieces = lt._pieces(ndat) if lt.fused_fold and lt._weights is None else None
+            if pieces is not None and len(pieces) == 1 and pieces[0][:2] == (0, ndat):
+                lt._fold_pieces(pieces, lambda: lt._filterbank_op("Filterbank+Detection+Fold", lambda: lt.fb.perform_fold(
+                    lt.fold, npart, state, inp=rows, in_step=in_step), events))
+                tb.blocks_fused += 1
+                return ndat
+            lt._filterbank_op("Filterbank+Detection", lambda: lt.fb.perform_detect(lt.detected, npart, state, nd, inp=rows, in_step=in_step),
+                              events)
+            lt._fold_pieces(pieces or lt._pieces(ndat), lambda: lt._op("Fold", lambda: lt.fold.fold(lt.detected)))
+            tb.blocks_weighted += lt._weights is not None
+            return ndat
+        finally:
+            lt._weights = None
+
     def plan_piece(self, acc, phi, phase_per_sample, ndat_fold, idat_start):
         """The host plan loop of Fold::fold (Fold.C:718-787) on the accumulator's fold: the driver's, or a pulsar's"""
         acc.fold.set_nbin(self.lt.cfg.nbin if acc is self.lt else acc.nbin)
         acc.fold.set_ndat(ndat_fold, idat_start)
+        if self.lt._weights is not None:             # two-bit input: samples of a zero weight are not folded
+            row, npw, widat = self.lt._weights
+            return acc.fold.set_bins(phi, phase_per_sample, ndat_fold, idat_start, acc.hits, weights=row, ndatperweight=npw, weight_idat=widat)
         return acc.fold.set_bins(phi, phase_per_sample, ndat_fold, idat_start, acc.hits)
 
     def _fold_pulsars(self, rows, ndat):
@@ -1641,6 +1737,7 @@ class LoadToFold:
         self.torch = torch
         self.pulsars, self.cyclic, self.plfb, self.rfi_filter = [], None, None, None
         self.sk, self.sk_statistics = None, None
+        self.twobit, self._weights = None, None   # NBIT 2: the TwoBitPlan; the weights of the block in hand (row, ndatperweight, weight_idat)
         self.ctx = self.fb = self.fold = self.response = self.sample_delay = self.detected = self.voltages = None
         self.sd = DelayCarry()               # -K: head room in front of `detected` and the tail carried in it
         self.mode = DetectFold(self)        # the back end; _plan chooses the one of the run
@@ -1659,6 +1756,8 @@ class LoadToFold:
 
     def _plan(self, cfg, info, polyco, reference_phase, subband, dump_before, targets):
         """The host side of the constructor: what the run refuses, in the order it always has, and every number that needs no device."""
+        if getattr(info, "nbit", 8) == 2:
+            self.twobit = twobit_check(cfg, info, len(targets), subband, dump_before)
         if cfg.zap_rfi:
             rfi_check(cfg, info, subband)
         self._calibrated = calibrator_response(cfg, info, subband)      # -pac
@@ -1757,6 +1856,9 @@ class LoadToFold:
             if self.subband is not None:
                 kernel = kernel[self.subband * nsub * r.ndat:(self.subband + 1) * nsub * r.ndat]
             _open_convolving_front(self, r, nsub, self.in_nchan, kernel, fused_fold=fused, response_matrix=matrix, **setup)
+            if self.twobit is not None:
+                tb = self.twobit
+                self.fb.set_twobit(tb.nsample, tb.nlow_min, tb.nlow_max, tb.levels, tb.table_type)
         elif cfg.convolve_when == "before":
             _adopt_front(self, ConvolutionThenFilterbank(self.ctx, nsub, info.nchan, info.npol, info.ndim == 1, r, max_parts=cfg.max_parts,
                                                          parts_per_block=rows))
@@ -1851,13 +1953,17 @@ class LoadToFold:
         pad = lambda t: ("%-25s" % t)
         print(pad("Operation") + pad("Time Spent") + pad("Discarded"), file=file)
         for name, (t, _n) in self.optime.items():
-            print(pad(name) + pad("%g" % t) + pad("0"), file=file)
+            discarded = self.twobit.discarded_weights if self.twobit is not None and name == "TwoBitCorrection" else 0
+            print(pad(name) + pad("%g" % t) + pad("%d" % discarded), file=file)
 
     # bytes of one block of `npart` parts
     def block_bytes(self, npart=None, first_sample=0):
         """first_sample: a block of heaps begins at that sample of its first heap (0 for every other layout)."""
         npart = npart or self.cfg.parts_per_block
         nsamp = npart * self.nsamp_step + self.nsamp_overlap
+        tb = getattr(self, "twobit", None)   # (the method is also borrowed by stand-ins that hold the geometry alone)
+        if tb is not None:                   # whole excision windows from the one that holds the block's first sample
+            return twobit_block_bytes(first_sample, nsamp, tb.nsample, self.info.npol)
         return raw_block_bytes(self.layout, nsamp, self.in_nchan, self.info.npol, self.info.ndim, first_sample)
 
     def seek_block(self, k):
@@ -1895,6 +2001,11 @@ class LoadToFold:
         if cfg.zap_rfi and self.rfi_filter is None:
             raise DspsrAmdError("dspsr_amd.LoadToFold.process_block: zap_rfi (-R) is set and no filter has been given: "
                                 "call set_rfi_filter before the first block")
+        if self.twobit is not None:
+            if not 0 <= first_sample < self.twobit.nsample:
+                raise DspsrAmdError("dspsr_amd.LoadToFold.process_block: first_sample=%d is not inside a window of %d samples"
+                                    % (first_sample, self.twobit.nsample))
+            self.twobit.first_sample = first_sample
         nout = self.mode.process(raw, npart, events)              # (the pieces were planned from ndat_out as it was)
         self.ndat_out += nout
         self.nsamples_in += npart * self.nsamp_step
@@ -2273,6 +2384,7 @@ class LoadToFil:
 
     def __init__(self, cfg: SearchConfig, info: InputInfo, device: int = 0, stream: int | None = None):
         self.cfg, self.info = cfg, info
+        refuse_twobit("dspsr_amd.LoadToFil", info)
         refuse_heaps("dspsr_amd.LoadToFil", info, "channelised complex voltages take -F N:D (dspsr_amd.LoadToFilCoherent)")
         if info.npol != 2 or info.ndim != 1 or info.nchan != 1:
             raise DspsrAmdError("dspsr_amd.LoadToFil: 8-bit real dual-polarisation single-channel input only")
@@ -2364,6 +2476,7 @@ class LoadToFilCoherent:
     def _plan(self, cfg, info):
         """The host side of the constructor: checks and geometry.  Returns the -K delays per channel (None without -K)."""
         self.cfg, self.info = cfg, info
+        refuse_twobit("dspsr_amd.LoadToFilCoherent", info)
         if cfg.npol not in (1, 2, 4):
             raise DspsrAmdError("dspsr_amd.LoadToFilCoherent: npol=%d (Intensity 1 / PPQQ 2 / Coherence 4 are built; NthPower 3 is not)" % cfg.npol)
         if cfg.npol >= 2 and info.npol != 2:
@@ -2522,6 +2635,7 @@ class LoadToFilDirect:
     def _plan(self, cfg, info):
         """The host side of the constructor: checks and geometry.  Returns the -K delays per channel (None without -K)."""
         self.cfg, self.info = cfg, info
+        refuse_twobit("dspsr_amd.LoadToFilDirect", info)
         if info.ndim != 2:
             raise DspsrAmdError("dspsr_amd.LoadToFilDirect: NDIM=%d; complex (NDIM 2) channelised voltages only" % info.ndim)
         if getattr(info, "nbit", 8) != 8:

@@ -341,6 +341,36 @@ int dspsr_amd_unpack_fpt(dspsr_amd_ctx* ctx, const int8_t* raw_dev, float scale,
  * (else DSPSR_AMD_EINVAL, nothing launched); nothing outside the 2 * ndat floats of a row is written.  ndat = 0: nothing to do. */
 int dspsr_amd_unpack_heaps_fpt(dspsr_amd_ctx* ctx, const int8_t* raw_dev, int raw_layout, float scale, uint32_t nchan, uint32_t npol,
                                uint64_t ndat, float* out_dev, uint64_t out_chan_stride, uint64_t out_pol_stride);
+/* ---- two-bit voltages: dsp::TwoBitCorrection on the device (TwoBitCorrection.C, ExcisionUnpacker.C, TwoBitFour.h) -------------
+ * One input channel of real samples from npol = 1 | 2 digitisers.  Byte k of the stream belongs to digitiser k % npol and holds four
+ * consecutive samples of it, the first in the two most significant bits (ExcisionUnpacker::get_input_offset / get_input_incr,
+ * BitTable MostToLeast).  table_type is the code -> (+-lo, +-hi) map of TwoBitTable::generate_unique_values, and with it the two
+ * codes that count as low:
+ *     code                       0    1    2    3
+ *     OFFSET_BINARY            -hi  -lo  +lo  +hi
+ *     SIGN_MAGNITUDE           +lo  +hi  -lo  -hi
+ *     TWOS_COMPLEMENT          +lo  +hi  -hi  -lo
+ * Windows of nsample samples are aligned to the STREAM: raw_dev points at the first byte of the window that holds the call's
+ * first sample, first_sample in [0, nsample) says where in that window that sample lies, and the block holds
+ * nwindow = ceil((first_sample + ndat) / nsample) whole windows (nwindow * nsample / 4 * npol bytes).  For every (digitiser,
+ * window) the low states are counted (n_low); the window's weight is 0 where every byte of it is zero, n_low < nlow_min or
+ * n_low > nlow_max (excision_unpack.h:83-85), else 1; its samples become +-lo / +-hi of entry clamp(n_low, nlow_min, nlow_max) -
+ * nlow_min of levels_dev (float [nlow_max - nlow_min + 1][2]: lo, hi; dspsr_amd/twobit.py builds it), or 0 where the weight is 0.
+ * A digitiser's samples are zeroed for its OWN bad windows only; combining the weights (WeightedTimeSeries::mask_weights) is the
+ * caller's.  out_dev: row p at out_dev + p * out_pol_stride receives stream samples first_sample ... first_sample + ndat - 1 of
+ * the block; any float-aligned address; nothing outside the ndat floats of a row is written.  weights_dev: uint32 [npol][nwindow];
+ * nlow_dev: the same shape, or NULL.  ndat = 0: nothing to do.
+ * DSPSR_AMD_EINVAL before any launch, the message naming the limit: nsample not a multiple of 4 in [4, 65536]; nlow_max <= nlow_min
+ * or nlow_max > nsample; first_sample >= nsample; npol not 1 | 2; raw_dev not 4-byte aligned; out_pol_stride < ndat with npol 2;
+ * an unknown table_type.  dspsr_amd_twobit_check gives the same answers without a device (addresses as integers). */
+#define DSPSR_AMD_TWOBIT_OFFSET_BINARY 0
+#define DSPSR_AMD_TWOBIT_SIGN_MAGNITUDE 1
+#define DSPSR_AMD_TWOBIT_TWOS_COMPLEMENT 2
+int dspsr_amd_twobit_check(uint64_t raw_addr, int table_type, uint32_t npol, uint32_t nsample, uint32_t first_sample, uint64_t ndat,
+                           uint32_t nlow_min, uint32_t nlow_max, uint64_t out_addr, uint64_t out_pol_stride, char* msg, size_t msg_len);
+int dspsr_amd_twobit_unpack(dspsr_amd_ctx* ctx, const uint8_t* raw_dev, int table_type, uint32_t npol, uint32_t nsample,
+                            uint32_t first_sample, uint64_t ndat, uint32_t nlow_min, uint32_t nlow_max, const float* levels_dev,
+                            float* out_dev, uint64_t out_pol_stride, uint32_t* weights_dev, uint32_t* nlow_dev);
 /* dspsr_amd_detect_raw replaces the unpacker, dsp::Detection (DetectionCUDA.cu:180-213 sqld_fpt; Detection.C:218-320 square_law,
  * LoadToFil.C:267-271 Coherence with ndim 1) and dsp::TScrunch (TScrunch.C:148-178) by ONE pass over the block: complex input
  * (ndim 2), npol 1 | 2, any nchan >= 1; the float voltages are never written.  Bit for bit dspsr_amd_unpack_fpt ->

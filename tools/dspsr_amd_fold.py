@@ -26,6 +26,10 @@ dspsr_amd.dada.fold_file for trying the engine on a DADA file; not a re-implemen
                     and Detection, the fold counts its hits per channel -- files with HITS_NCHAN -- and the reference's line
                     `Zapped: total=...% skfb=...% tscr=...% fscr=...%` goes to stderr at the end)
 
+  dspsr_amd_fold.py -F 8:D -2 c10 -2 n512 -2 t0.9674 two_bit.dada   (two-bit input, NBIT 2 of INSTRUMENT CPSR2, dspsr.C:280-287:
+                    dsp::TwoBitCorrection's knobs -- excision cutoff in sigma, samples per power estimate, sampling threshold;
+                    windows it excises are dropped by the fold, and -r shows their count in the Discarded column)
+
 Every completed sub-integration is written as <prefix>_<n>.ps (the PhaseSeries hand-off file of INTEGRATION.md:
 raw sums + hits; dsp::Archiver's normalisation is the reader's job).
 
@@ -67,11 +71,38 @@ def parse_args(argv=None):
     ap.add_argument("-skz_no_fscr", dest="skz_no_fscr", action="store_true", help="do not use SKDetector Fscrunch feature")
     ap.add_argument("-skz_no_tscr", dest="skz_no_tscr", action="store_true", help="do not use SKDetector Tscrunch feature")
     ap.add_argument("-skz_no_ft", dest="skz_no_ft", action="store_true", help="do not use SKDetector despeckeler")
+    ap.add_argument("-2", dest="unpack", action="append", default=[], metavar="c<cutoff>|n<samples>|t<threshold>",
+                    help="unpacker options (\"2-bit\" excision): c<cutoff> threshold for impulsive interference excision, n<sample> "
+                         "number of samples used to estimate undigitized power, t<threshold> two-bit sampling threshold at record time")
     ap.add_argument("-r", dest="record", action="store_true", help="report the time spent in each operation")
     ap.add_argument("--dump", action="append", default=[], help="dump the input of this operation (Detection, Fold)")
     ap.add_argument("-O", dest="prefix", default="dspsr_amd", help="output file name prefix")
     ap.add_argument("--cuda", dest="device", type=int, default=0, help="device id (the reference's spelling)")
     return ap.parse_args(argv)
+
+
+def unpacker_options(unpack, log=None):
+    """dspsr.C:530-559: the -2 arguments in order, each tried as n<unsigned>, c<float>, t<float> (what matches none is ignored, as
+    there), with the reference's lines on `log`.  Returns the Config fields they set."""
+    import re
+    out = {}
+    number = r"[+-]?(?:\d+\.?\d*(?:[eE][+-]?\d+)?|\.\d+(?:[eE][+-]?\d+)?)"
+    for arg in unpack:
+        m = re.match(r"n(\d+)", arg)
+        if m:
+            out["excision_nsample"] = int(m.group(1))
+            print("dspsr: Using %d samples to estimate undigitized power" % out["excision_nsample"], file=log or sys.stderr)
+            continue
+        m = re.match("c(%s)" % number, arg)
+        if m:
+            out["excision_cutoff"] = float(m.group(1))
+            print("dspsr: Setting impulsive interference excision threshold to %g" % out["excision_cutoff"], file=log or sys.stderr)
+            continue
+        m = re.match("t(%s)" % number, arg)
+        if m:
+            out["excision_threshold"] = float(m.group(1))
+            print("dspsr: Setting two-bit sampling threshold to %g" % out["excision_threshold"], file=log or sys.stderr)
+    return out
 
 
 def fold_targets(a, nbin, out_rate, mjd_day, mjd_sec):
@@ -117,7 +148,7 @@ def main(argv=None):
                           cyclic_nchan=a.cyclic, cyclic_mover=a.cyclic_mover, cyclic_npol=(a.ndim if info.npol == 2 else 1) if a.cyclic else 0,
                           interchan_dedispersion=a.interchan, record_time=a.record, fourth_moment=a.fourth, calibrator=a.pac, zap_rfi=a.zap_rfi,
                           sk_zap=a.skz, sk_m=a.skzm, sk_std_devs=a.skzs, sk_chan_start=a.skz_start, sk_chan_end=a.skz_end, sk_no_fscr=a.skz_no_fscr,
-                          sk_no_tscr=a.skz_no_tscr, sk_no_ft=a.skz_no_ft,
+                          sk_no_tscr=a.skz_no_tscr, sk_no_ft=a.skz_no_ft, **unpacker_options(a.unpack),
                           convolve_when="never" if when == "after" and dm == 0.0 else when)
     torch.cuda.set_device(a.device)
     lt = dada.fold_file(a.file, cfg, polyco=polyco, device=a.device, stream=torch.cuda.current_stream().cuda_stream,

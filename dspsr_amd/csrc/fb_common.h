@@ -287,7 +287,7 @@ struct TimeCombine {
 
 
 [[maybe_unused]] constexpr uint32_t FB_PSL_MAX = 128;   // fused fold: offsets of the parts a workgroup walks (its run of a launch), kept in LDS
-// Host side of the fused-fold inverse kernels' LDS layout (fb_inv_chan.h plan_off / psl): behind the `lds` bytes of the plain
+// Host side of the fused-fold inverse kernels' LDS layout (plan_off of the kernels, InvPlan of fb_inv_epilogue.h): behind the `lds` bytes of the plain
 // kernel, two buffers of `cap` 16-byte plan entries and the FB_PSL_MAX part offsets.  cap: what fits in 160 KB, at most `clamp`
 // (one entry per thread), 0 below 16; lds: the fused kernel's dynamic LDS.
 struct FbPlanLds {
@@ -600,6 +600,48 @@ DEV void detect4(const cf p, const cf q, const int state, float (&r)[4])
   const float im = p.x * q.y - p.y * q.x;
   if (state == DSPSR_AMD_STOKES) { r[0] = pp + qq; r[1] = pp - qq; r[2] = 2.0f * re; r[3] = 2.0f * im; }
   else { r[0] = pp; r[1] = qq; r[2] = re; r[3] = im; }
+}
+
+// ---- output rows: the one place that writes a sample into the caller's rows ---------------------
+// STREAM: the store kind of the calling pass, st_stream or a plain store.
+template <bool STREAM, class T> DEV void fb_st(T* p, const T v)
+{
+  if constexpr (STREAM) st_stream(p, v);
+  else *p = v;
+}
+// (a, b) detected with out.state at sample idat of channel row `row`, in the layout of Detection.C:423-474: ndim 4 = one float4 per
+// sample; ndim 2 = two float2 rows out.pol_stride floats apart; ndim 1 = four float rows (always plain stores: 4-byte ones).
+// NDIM is the compile-time form for a caller that chooses the layout once per butterfly, outside its unrolled element loop (the
+// compiler does not unswitch the uniform test out of it: k_inv_b, k_inv_chan); fb_put_detected chooses per sample.
+template <int NDIM, bool STREAM>
+DEV void fb_put_detected_as(const FbOut& out, float* __restrict__ row, const uint64_t idat, const cf a, const cf b)
+{
+  float r[4];
+  detect4(a, b, out.state, r);
+  if constexpr (NDIM == 4) {
+    fb_st<STREAM>(&((float4*)row)[idat], make_float4(r[0], r[1], r[2], r[3]));
+  } else if constexpr (NDIM == 2) {
+    fb_st<STREAM>(&((float2*)row)[idat], make_float2(r[0], r[1]));
+    fb_st<STREAM>(&((float2*)(row + out.pol_stride))[idat], make_float2(r[2], r[3]));
+  } else {
+    row[idat] = r[0];
+    row[out.pol_stride + idat] = r[1];
+    row[2 * out.pol_stride + idat] = r[2];
+    row[3 * out.pol_stride + idat] = r[3];
+  }
+}
+template <bool STREAM>
+DEV void fb_put_detected(const FbOut& out, float* __restrict__ row, const uint64_t idat, const cf a, const cf b)
+{
+  if (out.ndim == 4) fb_put_detected_as<4, STREAM>(out, row, idat, a, b);
+  else if (out.ndim == 2) fb_put_detected_as<2, STREAM>(out, row, idat, a, b);
+  else fb_put_detected_as<1, STREAM>(out, row, idat, a, b);
+}
+// the complex pair: a at o, b (where the second polarisation exists) out.pol_stride floats behind it
+template <bool STREAM> DEV void fb_put_complex(const FbOut& out, float2* o, const cf a, const cf b, const bool two)
+{
+  fb_st<STREAM>(o, a);
+  if (two) fb_st<STREAM>((float2*)((float*)o + out.pol_stride), b);
 }
 
 // ------------------------------------------------------------------------------------ host

@@ -165,28 +165,14 @@ template <int LOGM, bool HEAPS> DEV void conv1_tiles(const Conv1Params& p, const
 #pragma unroll
         for (int k = 0; k < R; k++) {
           if ((uint32_t)(t0 + (int32_t)(k * pstride)) >= p.nkeep) continue;
-          float2* o = o2 + k * pstride;
-          st_stream(o, cx2_lo(v[k]));
-          st_stream((float2*)((float*)o + out.pol_stride), cx2_hi(v[k]));
+          fb_put_complex<true>(out, o2 + k * pstride, cx2_lo(v[k]), cx2_hi(v[k]), true);
         }
       } else {
 #pragma unroll
         for (int k = 0; k < R; k++) {
           const int32_t ts = t0 + (int32_t)(k * pstride);
           if ((uint32_t)ts >= p.nkeep) continue;
-          float r[4];
-          detect4(cx2_lo(v[k]), cx2_hi(v[k]), out.state, r);
-          const uint64_t idat = part * p.nkeep + (uint32_t)ts;
-          if (out.ndim == 4) st_stream(&((float4*)row)[idat], make_float4(r[0], r[1], r[2], r[3]));
-          else if (out.ndim == 2) {
-            st_stream(&((float2*)row)[idat], make_float2(r[0], r[1]));
-            st_stream(&((float2*)(row + out.pol_stride))[idat], make_float2(r[2], r[3]));
-          } else {
-            row[idat] = r[0];
-            row[out.pol_stride + idat] = r[1];
-            row[2 * out.pol_stride + idat] = r[2];
-            row[3 * out.pol_stride + idat] = r[3];
-          }
+          fb_put_detected<true>(out, row, part * p.nkeep + (uint32_t)ts, cx2_lo(v[k]), cx2_hi(v[k]));
         }
       }
     };

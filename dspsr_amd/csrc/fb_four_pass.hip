@@ -399,43 +399,14 @@ __global__ __launch_bounds__(512) void k_inv_b(const FbGeom g, const cf* __restr
       };
       if (out.kind == FB_OUT_COMPLEX) {
         float2* __restrict__ o0 = (float2*)(row + part * out.part_step);
-        if (g.npol == 2)
-          each([&](const uint32_t t, const cf va, const cf vb) {
-            st_stream(o0 + t, va);
-            st_stream((float2*)((float*)(o0 + t) + out.pol_stride), vb);
-          });
-        else
-          each([&](const uint32_t t, const cf va, const cf) { st_stream(o0 + t, va); });
+        if (g.npol == 2) each([&](const uint32_t t, const cf va, const cf vb) { fb_put_complex<true>(out, o0 + t, va, vb, true); });
+        else each([&](const uint32_t t, const cf va, const cf vb) { fb_put_complex<true>(out, o0 + t, va, vb, false); });
         return;
       }
       const uint64_t idat0 = part * g.nkeep;
-      if (out.ndim == 4) {
-        float4* __restrict__ o = (float4*)row + idat0;
-        each([&](const uint32_t t, const cf va, const cf vb) {
-          float q[4];
-          detect4(va, vb, out.state, q);
-          st_stream(o + t, make_float4(q[0], q[1], q[2], q[3]));
-        });
-      } else if (out.ndim == 2) {
-        float2* __restrict__ o = (float2*)row + idat0;
-        float2* __restrict__ o1 = (float2*)(row + out.pol_stride) + idat0;
-        each([&](const uint32_t t, const cf va, const cf vb) {
-          float q[4];
-          detect4(va, vb, out.state, q);
-          st_stream(o + t, make_float2(q[0], q[1]));
-          st_stream(o1 + t, make_float2(q[2], q[3]));
-        });
-      } else {
-        float* __restrict__ o = row + idat0;
-        each([&](const uint32_t t, const cf va, const cf vb) {
-          float q[4];
-          detect4(va, vb, out.state, q);
-          o[t] = q[0];
-          o[out.pol_stride + t] = q[1];
-          o[2 * out.pol_stride + t] = q[2];
-          o[3 * out.pol_stride + t] = q[3];
-        });
-      }
+      if (out.ndim == 4) each([&](const uint32_t t, const cf va, const cf vb) { fb_put_detected_as<4, true>(out, row, idat0 + t, va, vb); });
+      else if (out.ndim == 2) each([&](const uint32_t t, const cf va, const cf vb) { fb_put_detected_as<2, true>(out, row, idat0 + t, va, vb); });
+      else each([&](const uint32_t t, const cf va, const cf vb) { fb_put_detected_as<1, true>(out, row, idat0 + t, va, vb); });
     };
     wgfft<LOGF, +1, FOLDB>(lds, ltw_off, tid, logT, x, store);
     if constexpr (FOLDB) {

@@ -1,7 +1,7 @@
 // Convolving filterbank, inverse pass of the three-pass path (k_inv_chan); instantiated by fb_inv_chan.hip (plain output)
 // and fb_inv_chan_fold.hip (fused fold): two translation units so that the two families compile in parallel.
 #pragma once
-#include "fb_common.h"
+#include "fb_inv_epilogue.h"
 
 namespace dspsr_amd {
 
@@ -18,14 +18,10 @@ namespace dspsr_amd {
 //   otherwise: from X.  Real input: Hermitian split of spectrum rows s and Rr-1-s, a second, descending load stream (a, b) --
 //     in aligned 16-byte pairs exchanged between lane pairs where a tile is two channels (PAIR16); complex input: the rows of
 //     the two sequences.  This is the form of complex input, odd-factor lengths and of split_in_inverse = 1.
-// Items: part fastest, so one XCD re-reads a tile's chirp rows from its L2 for every part.
+// Items (fb_inv_walk.h): part fastest, so one XCD re-reads a tile's chirp rows from its L2 for every part; FOLD and search mode walk
+// the parts of a tile in order.
 // FOLD: the detected samples of the tile (T3 channels x nkeep samples, one float4 each) are staged in the
-// exchange buffer instead of being written out, and folded at once: thread b owns phase bins b, b + blockDim, ...
-// of the tile's channels, loads each touched accumulator from the device profile, adds the samples of the
-// bin's intervals one by one in time order and stores it back.  A workgroup processes ALL parts of a tile in
-// order and launches are stream ordered, so every (chan, bin) sum has the association order of the CPU loop
-// Fold.C:844-852, exactly as the stand-alone fold kernel (fold.hip) -- bit-identical results, without the
-// 16 B/sample round trip of the detected time series through HBM.
+// exchange buffer instead of being written out, and folded at once (fb_inv_epilogue.h).
 // EPI: 0 = complex or detected output written by the last stage; 1 (FOLD) = fused fold; 2 = search mode (FB_OUT_SEARCH): square-law
 // detection + time scrunch of the detected stream (digifil -F N:D, LoadToFil.C:185-222,250-304), staged like the fold's samples and
 // reduced by ts_reduce (fb_common.h).  Both walk the parts of a tile in order (the fold's profile, the scrunch's carry).
@@ -99,9 +95,7 @@ __global__ __launch_bounds__(512) void k_inv_chan(const FbGeom g, const cf* __re
   constexpr bool PAIR16 = !PRESPLIT && LOGT == 2 && P::G1 == 2;
   const bool pair16 = PAIR16 && g.real_input && logX3 == 1;
   cf special = make_float2(0.f, 0.f);                   // mirror element of bin 0 (pair16 path)
-  // a work item = (tile of channels, part of the launch), kept as two 32-bit numbers: a combined 64-bit index costs a
-  // software 64-bit division per use (about 300 scalar instructions per tile in the r02c listing)
-  struct Item { uint32_t tile, lp; };
+  typedef InvItem Item;                                  // (tile of channels, part of the launch): fb_inv_walk.h
   auto fetch = [&](const Item item, Abk (&raw)[PTS / 2], const int chunk) {
     const uint32_t tile = item.tile;
     const cf* __restrict__ X0s = X + (uint64_t)item.lp * nseq * L;
@@ -199,112 +193,27 @@ __global__ __launch_bounds__(512) void k_inv_chan(const FbGeom g, const cf* __re
 
   const uint32_t ltw_off = lds_pad(PTS * blockDim.x) + 8;      // behind the exchange buffer (16-byte aligned)
   ltw_fill<LOGF>(lds, ltw_off, tw, tid, blockDim.x);
-  // FOLD: two buffers of out.plan_cap plan entries behind the twiddle tables (cf index, 16-byte aligned), followed by
-  // a copy of the launch's nparts + 1 part offsets into the plan (PSL_MAX words): a part's entries are then found
-  // without a dependent pair of global loads, and are fetched one item ahead (registers) like the tile itself
-  const uint32_t plan_off = (ltw_off + ltw_entries_dev<LOGF>() + 1) & ~1u;
-  uint32_t* psl = nullptr;
-  const uint4* __restrict__ fent_all = nullptr;
-  bool use_psl = false;
-  if constexpr (FOLD) {
-    psl = (uint32_t*)&lds[plan_off + 4 * out.plan_cap];
-    fent_all = (const uint4*)(out.pstart + ((out.nparts_plan + 1 + 3) & ~3u));
-  }
+  const uint32_t plan_off = (ltw_off + ltw_entries_dev<LOGF>() + 1) & ~1u;    // FOLD: the plan's LDS, behind the twiddle tables
   uint32_t jt = 0;                                              // tiles done by this workgroup
   Item item, next;
   uint32_t j = 0;
-  // FOLD: workgroup b takes tiles b, b + grid, ... and walks the parts of each in order.
-  // Segmented (out.nseg > 1, geometries with fewer channel tiles than compute units): the parts of the launch are cut
-  // into nseg runs; workgroup (lane, seg) walks the parts of run `seg` for tiles lane, lane + ntg, ...  Run 0 adds onto
-  // the profile (it continues the sums of earlier launches in time order), the others onto zeroed partial profiles that
-  // are added to the profile, in run order, after the launch -- the sums of a launch are re-associated per run.
-  uint32_t fold_b = blockIdx.x;
-  const uint32_t fnseg = FOLD && out.nseg > 1 ? out.nseg : 1u;
-  const uint32_t fntg = gridDim.x / fnseg;                         // workgroups per run (host: gridDim.x % nseg == 0)
-  const uint32_t fseg = fnseg > 1 ? fold_b / fntg : 0u;
-  const uint32_t fpps = (nparts + fnseg - 1) / fnseg;              // parts per run
-  const uint32_t fp0 = fseg * fpps;
-  const uint32_t fnp = fp0 >= nparts ? 0u : (nparts - fp0 < fpps ? nparts - fp0 : fpps);
-  if (fnseg > 1) fold_b -= fseg * fntg;
+  // (MATRIX and the XCD remap of the fused fold's tiles are this kernel's own parameters of the walk)
+  const InvWalk walk = inv_walk(EPI != 0, MATRIX, FOLD ? out.nseg : 1u, nparts, ntile, run, gridDim.x, blockIdx.x, FOLD ? logX3 - logT3 : 0);
+  const uint32_t fseg = walk.seg;
+  auto next_item = [&](const uint32_t jj, Item& it) -> bool { return inv_walk_item(walk, jj, it); };
+  [[maybe_unused]] InvPlan plan = {};
   if constexpr (FOLD) {
-    if (fnp == 0) return;
-    // the offsets of the parts THIS workgroup walks (its run of a segmented launch: launches of up to 256 parts are cut into
-    // runs of at most FB_PSL_MAX - 1; the whole launch's offsets did not fit, and every entry and accumulator of such launches
-    // -- the sub-band and -F 256:D geometries -- then came from global memory in the fold phase), psl[lp - fp0]
-    use_psl = out.plan_cap > 0 && fnp + 1 <= FB_PSL_MAX;
-    if (use_psl) {
-      for (uint32_t q = tid; q <= fnp; q += blockDim.x) psl[q] = out.pstart[part0 + fp0 + q];
-      __syncthreads();
-    }
-    // tiles that share an X layout block (2^(logX3-logT3) of them) go to blocks b, b+8, ... : one XCD under the
-    // observed round-robin placement, at the same time, so the block's lines are fetched once (speed only)
-    const int lr = logX3 - logT3;
-    if (fnseg == 1 && lr > 0 && (gridDim.x & ((8u << lr) - 1)) == 0)
-      fold_b = ((((fold_b >> (3 + lr)) << 3) | (fold_b & 7)) << lr) | ((fold_b >> 3) & ((1u << lr) - 1));
+    if (walk.np == 0) return;
+    plan = inv_plan_begin<P::NS>(lds, plan_off, out, part0, walk, tid, blockDim.x);
   }
-  // Without the fold the order of the items is free.  When every workgroup gets the same number of tiles it also walks the
-  // parts of a tile one after the other, so that the tile's chirp stays in registers (one chirp read per launch, not per
-  // part); otherwise the items are dealt XCD-wise as in the other passes.
-  // (MATRIX: tile after tile whenever the tiles alone occupy every workgroup, also with a remainder -- the response is re-read
-  //  per part, from the cache while the tile's rows are warm; fewer tiles than workgroups keep the dealing below, part fastest)
-  const bool tile_major = EPI != 0 || (ntile >= gridDim.x && (MATRIX || ntile % gridDim.x == 0));
-  auto next_item = [&](const uint32_t jj, Item& it) -> bool {
-    if (EPI != 0 || tile_major) {
-      const uint32_t q = jj / fnp;                     // (32-bit; jj counts this workgroup's items)
-      it.tile = fold_b + q * fntg;
-      it.lp = fp0 + (jj - q * fnp);
-      return it.tile < ntile;
-    } else {
-      // XCD dealing as persistent_item (wgfft.h) with runs of `run` items; run == nparts (the default) makes the run
-      // index the tile and the position in the run the part, without a division by nparts
-      const uint32_t grid = gridDim.x, b = blockIdx.x;
-      uint32_t hi, lo;
-      if (grid & 7) {
-        const uint32_t lin = b + jj * grid;
-        hi = lin / run; lo = lin - hi * run;
-      } else {
-        const uint32_t q = jj * (grid >> 3) + (b >> 3);
-        const uint32_t qr = q / run;
-        hi = qr * 8 + (b & 7); lo = q - qr * run;
-      }
-      if (run == nparts) { it.tile = hi; it.lp = lo; }
-      else { const uint32_t lin = hi * run + lo; it.tile = lin / nparts; it.lp = lin - it.tile * nparts; }
-      return it.tile < ntile;                          // (lp < nparts by construction)
-    }
-  };
   if (!next_item(j, item)) return;
   Abk raw[PTS / 2];
   fetch(item, raw, -1);
   cf kk[MATRIX ? 1 : PTS / 2];          // chirp of the current tile (MATRIX: none, the response is streamed per item)
   uint32_t kk_tile = ~0u;
-  // FOLD: plan entry of this thread for the item about to be processed (tid < number of active bins of the part)
-  uint32_t fe0_cur = 0, fn_cur = 0;
-  auto plan_fetch = [&](const Item it) {
-    if constexpr (FOLD) {
-      const uint32_t lp = it.lp;
-      if (use_psl) { fe0_cur = psl[lp - fp0]; fn_cur = psl[lp - fp0 + 1] - fe0_cur; }
-      else { fe0_cur = out.pstart[part0 + lp]; fn_cur = out.pstart[part0 + lp + 1] - fe0_cur; }
-    }
-  };
-  // The active-bin entries of a part (16 bytes each, at most plan_cap <= blockDim of them) go from global memory STRAIGHT into
-  // their LDS buffer (global_load_lds_dwordx4: lane l of a wave lands at the wave's base + 16*l), asynchronously and
-  // without passing through registers.  Round 2 fetched them into a register at the top of the tile and stored them to
-  // LDS: the kernel sits at 256 registers, the value was spilled to scratch, and the ISA read `s_waitcnt vmcnt(0);
-  // global_load; s_waitcnt vmcnt(0); scratch_store; ...; scratch_load; s_waitcnt vmcnt(0); ds_write` -- two exposed memory
-  // round trips on the two waves everyone then waits for at the first barrier.  The entries of the NEXT item are now
-  // requested in the middle of the current tile's transform (behind a barrier that the previous readers of that buffer
-  // have passed) and are waited for, together with the prefetched tile, at the top of the next one.
-  // (needs a second stage: the request for the next item is issued from wgfft's `mid` hook behind the first exchange barrier;
-  //  single-stage transforms read their entries from global memory)
-  const bool plan_dma_ok = FOLD && FftPlan<LOGF>::NS >= 2 && use_psl;
-  auto plan_dma = [&](const Item it, const uint32_t buf) {
-    if constexpr (FOLD) {
-      const uint32_t fe0 = psl[it.lp - fp0], fn = psl[it.lp - fp0 + 1] - fe0;
-      if (fn <= out.plan_cap && tid < fn)
-        lds_dma_b128((const void*)(fent_all + fe0 + tid), lds_byte_addr((const uint4*)&lds[plan_off] + buf * out.plan_cap + (tid & ~63u)));
-    }
-  };
-  if (plan_dma_ok) plan_dma(item, 0);
+  if constexpr (FOLD) {
+    if (plan.dma_ok) inv_plan_dma(plan, out, walk, item.lp, 0, tid);
+  }
 
   FB_ST_BEGIN(3);
   for (;;) {
@@ -321,9 +230,7 @@ __global__ __launch_bounds__(512) void k_inv_chan(const FbGeom g, const cf* __re
         }
       }
       if constexpr (FOLD) {
-        // this part's active-bin entries travel with the chirp loads and are parked in LDS (double buffered: slower
-        // waves may still be folding the previous tile from the other half); their offsets come from the LDS copy
-        plan_fetch(item);
+        inv_plan_fetch(plan, out, part0, walk, item.lp);
         // the entries requested during the previous tile (or in front of the loop) have landed once every older load has
         // -- they were issued half a tile ago, behind the prefetch of this tile
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -430,130 +337,21 @@ __global__ __launch_bounds__(512) void k_inv_chan(const FbGeom g, const cf* __re
     [[maybe_unused]] TsPart tsp = {0, 0, 0, 0};
     [[maybe_unused]] float ts_carry_mid = 0.f;      // SEARCH, two or more stages: the carry of row tid, loaded in mid()
     if constexpr (SEARCH) tsp = ts_part(out, (uint32_t)part, g.nkeep);
-    // FOLD: the tile's detected samples are staged UNPADDED, channel after channel (16 bytes per sample), so that the
-    // samples of a phase bin's run are read at constant offsets from one base (the padded image cost four integer
-    // instructions per sample in a phase that only three of eight waves work in).  The channel stride is nkeep rounded up
-    // so that the T3 channels a quarter wave writes at once fall on different LDS banks.
-    // (many channels of a short transform: the rounded stride would not fit the exchange buffer -- 2*T3*nkeep words always do)
-    const uint32_t fcr = (16u >> logT3) & 15u, fcs_r = ((g.nkeep + 15u - fcr) & ~15u) + fcr;
-    const uint32_t fcs = ((2u * fcs_r) << logT3) <= PTS * blockDim.x ? fcs_r : g.nkeep;
+    const uint32_t fcs = inv_fold_stride(logT3, g.nkeep, blockDim.x);
+    auto chan_of = [&](const uint32_t slo) { return tile * T3 + slo; };
     auto store = [&](const uint32_t col, const uint32_t p, const uint32_t pstride, auto& v) {
-      constexpr int R = sizeof(v) / sizeof(v[0]);
-      if constexpr (FOLD) {
-        const uint32_t slo = col >> 1;
-        const int32_t t0 = (int32_t)p - (int32_t)g.nfilt_pos;
-#pragma unroll
-        for (int k = 0; k < R; k++) {
-          const int32_t t = t0 + (int32_t)(k * pstride);
-          if ((uint32_t)t >= g.nkeep) continue;           // outside the kept window (negative t wraps)
-          float r[4];
-          detect4(cx2_lo(v[k]), cx2_hi(v[k]), out.state, r);
-          *(float4*)&lds[2 * (slo * fcs + (uint32_t)t)] = make_float4(r[0], r[1], r[2], r[3]);
-        }
-        return;
-      }
-      if constexpr (SEARCH) {
-        const int32_t t0 = (int32_t)p - (int32_t)g.nfilt_pos;
-#pragma unroll
-        for (int k = 0; k < R; k++) {
-          const int32_t t = t0 + (int32_t)(k * pstride);
-          if ((uint32_t)t >= g.nkeep) continue;
-          // (one polarisation: the pair's second half is not a signal -- for real input the other output of the Hermitian split,
-          //  zero but for rounding, 1e-7 of the spectrum's scale: its power moved the sum by an ulp where a sample is small,
-          //  tests/fuzz_search.py 300 702 case 68)
-          ts_stage((float*)lds, out, tsp, col >> 1, (uint32_t)t, cx2_lo(v[k]), g.npol == 1 ? make_float2(0.f, 0.f) : cx2_hi(v[k]));
-        }
-        return;
-      }
-      if (out.kind == FB_OUT_NONE) return;
-      const uint32_t chan = out.chan0 + tile * T3 + (col >> 1);
-      float* __restrict__ row = out.base + chan * out.chan_stride;
-      // output sample of element k: t0 + k*pstride (kept when 0 <= t < nkeep); the addresses are a base plus a
-      // multiple of a wave-uniform step
-      const int32_t t0 = (int32_t)p - (int32_t)g.nfilt_pos;
-      float2* __restrict__ o2 = (float2*)(row + part * out.part_step) + t0;
-      float4* __restrict__ o4 = (float4*)row + ((int64_t)(part * g.nkeep) + t0);
-      // the output kind / layout is uniform: chosen once, outside the unrolled element loop (no branch per element)
-      if (out.kind == FB_OUT_COMPLEX) {
-        const bool two = g.npol == 2;
-#pragma unroll
-        for (int k = 0; k < R; k++) {
-          if ((uint32_t)(t0 + (int32_t)(k * pstride)) >= g.nkeep) continue;
-          float2* o = o2 + k * pstride;
-          st_stream(o, cx2_lo(v[k]));
-          if (two) st_stream((float2*)((float*)o + out.pol_stride), cx2_hi(v[k]));
-        }
-      } else if (out.ndim == 4) {
-#pragma unroll
-        for (int k = 0; k < R; k++) {
-          if ((uint32_t)(t0 + (int32_t)(k * pstride)) >= g.nkeep) continue;
-          float r[4];
-          detect4(cx2_lo(v[k]), cx2_hi(v[k]), out.state, r);
-          st_stream(o4 + k * pstride, make_float4(r[0], r[1], r[2], r[3]));
-        }
-      } else {
-#pragma unroll
-        for (int k = 0; k < R; k++) {
-          const int32_t ts = t0 + (int32_t)(k * pstride);
-          if ((uint32_t)ts >= g.nkeep) continue;
-          float r[4];
-          detect4(cx2_lo(v[k]), cx2_hi(v[k]), out.state, r);
-          const uint64_t idat = part * g.nkeep + (uint32_t)ts;
-          if (out.ndim == 2) {
-            st_stream(&((float2*)row)[idat], make_float2(r[0], r[1]));
-            st_stream(&((float2*)(row + out.pol_stride))[idat], make_float2(r[2], r[3]));
-          } else {
-            row[idat] = r[0];
-            row[out.pol_stride + idat] = r[1];
-            row[2 * out.pol_stride + idat] = r[2];
-            row[3 * out.pol_stride + idat] = r[3];
-          }
-        }
-      }
+      inv_store<FOLD, SEARCH>(lds, g, out, tsp, fcs, chan_of(col >> 1), part, g.npol == 2, col, p, pstride, v);
     };
-    // FOLD: active phase bins of this part: entries {bin, first interval, count<<16 | hits0, offset0}
-    // (fold_internal.h), copied to LDS at the start of the tile when they fit; one (entry, channel) accumulator per
-    // work item.  The accumulator of a thread's first work item (nearly always its only one) is requested in the
-    // middle of the transform -- behind two barriers, so the previous part's stores of this workgroup are visible --
-    // and arrives while the last stage runs, instead of costing a memory round trip in the fold phase.
-    uint32_t f_e0 = 0, f_nact = 0;
-    const uint4* __restrict__ ent = nullptr;
-    const uint4* planl = nullptr;
-    bool in_lds = false;
-    uint4 en_pre = make_uint4(0, 0, 0, 0);
-    float4 acc_pre = make_float4(0.f, 0.f, 0.f, 0.f);
+    // FOLD: this part's active bins, and the accumulator of the thread's first work item (fb_inv_epilogue.h)
     constexpr bool PRE = FOLD && FftPlan<LOGF>::NS >= 2;
+    [[maybe_unused]] InvFoldPart fpart = {};
+    [[maybe_unused]] InvAcc acc = {};
+    [[maybe_unused]] uint4 en_pre[1] = {make_uint4(0, 0, 0, 0)};
+    [[maybe_unused]] float4 acc_pre[1] = {make_float4(0.f, 0.f, 0.f, 0.f)};
     if constexpr (FOLD) {
-      f_e0 = fe0_cur;
-      f_nact = fn_cur;
-      ent = fent_all + f_e0;
-      planl = (const uint4*)&lds[plan_off] + (jt & 1) * out.plan_cap;
-      in_lds = plan_dma_ok && f_nact <= out.plan_cap;
+      fpart = inv_fold_part(plan, out, jt);
+      acc = inv_acc(out, fseg);
     }
-    // accumulator of (work item w, phase bin b): one float4, or -- profile of npol 2 x ndim 2 -- a float2 in each of the
-    // channel's two rows; the partial profiles of a segmented launch are packed in the same shape (rows of nbin bins)
-    const bool planes2 = FOLD && out.prof_planes == 2;                       // uniform
-    const uint64_t plane = fseg == 0 ? out.plane_stride : 2ull * out.nbin;   // floats between the two rows of a channel
-    auto acc_row = [&](const uint32_t w) -> float* {
-      const uint32_t cl = tile * T3 + (w & (T3 - 1));              // channel within this input channel's sub-band
-      return (float*)(fseg == 0 ? (float4*)out.base + (uint64_t)(out.chan0 + cl) * out.prof_span4
-                                : (float4*)out.part + ((uint64_t)(fseg - 1) * g.C + cl) * out.nbin);
-    };
-    auto acc_load = [&](float* row, const uint32_t b) -> float4 {
-      if (planes2) {
-        const float2 u = *(const float2*)(row + 2 * b), v = *(const float2*)(row + plane + 2 * b);
-        return make_float4(u.x, u.y, v.x, v.y);
-      }
-      return *(const float4*)(row + 4 * b);
-    };
-    auto acc_store = [&](float* row, const uint32_t b, const float4 a) {
-      if (planes2) {
-        *(float2*)(row + 2 * b) = make_float2(a.x, a.y);
-        *(float2*)(row + plane + 2 * b) = make_float2(a.z, a.w);
-      } else {
-        *(float4*)(row + 4 * b) = a;
-      }
-    };
     auto mid = [&](const int phase) {
       if constexpr (SEARCH) {
         // the open output sample's partial sum (written by this workgroup at the end of the previous part, two barriers ago)
@@ -564,17 +362,10 @@ __global__ __launch_bounds__(512) void k_inv_chan(const FbGeom g, const cf* __re
           ts_carry_mid = ts_carry_load(out, (out.chan0 + tile * T3 + tid / npo) * npo + tid % npo);
       }
       if constexpr (PRE) {
-        // only when the part's plan entries are in LDS: the accumulator's address then depends on an LDS read alone.  With
-        // the entry possibly coming from global memory (a select, or two branches that the compiler merges again) the
-        // load below sat behind s_waitcnt vmcnt(0) -- a wait for the whole prefetch of the next tile, in the middle of the
-        // transform, on exactly the three waves that also fold
-        if (phase == 2 && in_lds && tid < (f_nact << logT3)) {
-          en_pre = planl[tid >> logT3];
-          acc_pre = acc_load(acc_row(tid), en_pre.x);
-        }
+        if (phase == 2) inv_acc_preload<1>(g, out, acc, fseg, fpart, logT3, tid, blockDim.x, en_pre, acc_pre, chan_of);
         // every wave is past this tile's first exchange barrier, i.e. has left the previous tile's fold: the other plan
         // buffer is free for the entries of the next item
-        if (phase == 2 && plan_dma_ok && more) plan_dma(next, (jt + 1) & 1);
+        if (phase == 2 && plan.dma_ok && more) inv_plan_dma(plan, out, walk, next.lp, (jt + 1) & 1, tid);
       }
     };
     wgfft<LOGF, +1, EPI != 0>(lds, ltw_off, tid, logT, x, store, mid);
@@ -599,49 +390,12 @@ __global__ __launch_bounds__(512) void k_inv_chan(const FbGeom g, const cf* __re
         }
       }
       __syncthreads();                       // the tile's detected samples are staged; every carry of the tile has been read
-      ts_reduce((const float*)lds, out, tsp, nrow, ts_carry_pre, tid, blockDim.x, [&](const uint32_t slo) { return tile * T3 + slo; });
+      ts_reduce((const float*)lds, out, tsp, nrow, ts_carry_pre, tid, blockDim.x, chan_of);
       // (the barrier in front of the next tile's first exchange write also ends this read phase)
     }
     if constexpr (FOLD) {
       __syncthreads();                       // the tile's detected samples are staged
-      // the samples of an interval are fetched from LDS eight at a time (independent loads) and then added one after
-      // the other, so the sum keeps the time order
-      const bool pre = PRE && in_lds;
-      for (uint32_t w = tid; w < (f_nact << logT3); w += blockDim.x) {
-        const uint32_t slo = w & (T3 - 1);
-        uint4 en;
-        float4 acc;
-        if (pre && w == tid) {
-          en = en_pre;
-          acc = acc_pre;
-        } else {
-          en = in_lds ? planl[w >> logT3] : ent[w >> logT3];
-          acc = acc_load(acc_row(w), en.x);
-        }
-        const uint32_t nint = en.z >> 16;
-        float* __restrict__ pp = acc_row(w);
-        uint32_t off = en.w, hits = en.z & 0xffffu;
-        for (uint32_t i = 0;;) {
-          const float4* __restrict__ src = (const float4*)&lds[2 * (slo * fcs + off)];     // consecutive samples: constant offsets
-          uint32_t h = 0;
-          for (; h + 8 <= hits; h += 8) {
-            float4 sm[8];
-#pragma unroll
-            for (int q = 0; q < 8; q++) sm[q] = src[h + q];
-#pragma unroll
-            for (int q = 0; q < 8; q++) { acc.x += sm[q].x; acc.y += sm[q].y; acc.z += sm[q].z; acc.w += sm[q].w; }
-          }
-          for (; h < hits; h++) {
-            const float4 sm = src[h];
-            acc.x += sm.x; acc.y += sm.y; acc.z += sm.z; acc.w += sm.w;
-          }
-          if (++i >= nint) break;
-          const Interval iv = out.piv[en.y + i];           // further intervals of the bin in this part (rare)
-          off = (uint32_t)iv.offset; hits = iv.hits;
-        }
-        acc_store(pp, en.x, acc);
-      }
-      // the barrier in front of the next tile's first exchange write also ends this read phase
+      inv_fold_phase<1>(lds, g, out, acc, fseg, fpart, PRE && fpart.in_lds, logT3, fcs, tid, blockDim.x, en_pre, acc_pre, chan_of);
     }
     FB_ST(3, 4);
     FB_ST_TILE(3, 5);

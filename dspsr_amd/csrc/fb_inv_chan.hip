@@ -36,25 +36,8 @@ __global__ __launch_bounds__(256) void k_time_combine(const TimeCombine p, const
     const uint64_t part = p.part0 + (uint64_t)lp * p.part_stride;
     const uint32_t chan = out.chan0 + c;
     float* __restrict__ row = out.base + chan * out.chan_stride;
-    if (out.kind == FB_OUT_COMPLEX) {
-      float2* __restrict__ o = (float2*)(row + part * out.part_step) + t;
-      *o = a;
-      if (p.npol == 2) *(float2*)((float*)o + out.pol_stride) = b;
-    } else if (out.kind == FB_OUT_DETECTED) {
-      float q[4];
-      detect4(a, b, out.state, q);
-      const uint64_t idat = part * p.nkeep + t;
-      if (out.ndim == 4) ((float4*)row)[idat] = make_float4(q[0], q[1], q[2], q[3]);
-      else if (out.ndim == 2) {
-        ((float2*)row)[idat] = make_float2(q[0], q[1]);
-        ((float2*)(row + out.pol_stride))[idat] = make_float2(q[2], q[3]);
-      } else {
-        row[idat] = q[0];
-        row[out.pol_stride + idat] = q[1];
-        row[2 * out.pol_stride + idat] = q[2];
-        row[3 * out.pol_stride + idat] = q[3];
-      }
-    }
+    if (out.kind == FB_OUT_COMPLEX) fb_put_complex<false>(out, (float2*)(row + part * out.part_step) + t, a, b, p.npol == 2);
+    else if (out.kind == FB_OUT_DETECTED) fb_put_detected<false>(out, row, part * p.nkeep + t, a, b);
   }
 }
 

@@ -326,6 +326,9 @@ __global__ __launch_bounds__(512) void k_fb_plain(const PlainParams p, const cf*
       if (two_pol) {
         const uint64_t part = (uint64_t)tile * hT + j;
         if (part >= p.npart) return;
+        // (written out, not fb_put_complex / fb_put_detected of fb_common.h: with the two calls -- the same stores, the same
+        //  scratch, VGPRs equal or two fewer -- the `plain` workload ran 2.9 - 3.3 % slower in each of six alternating rounds, profiles/HISTORY.md
+        //  "Inverse passes: one item walk ...")
         if (out.kind == FB_OUT_COMPLEX) {
           float2* o = (float2*)(row + part * out.part_step);
           *o = a;

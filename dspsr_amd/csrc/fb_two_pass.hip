@@ -1,5 +1,5 @@
 // Convolving filterbank, two-pass path of short responses (k_raw_cols, k_fwd_col1q, k_rows_inv); see fb_common.h
-#include "fb_common.h"
+#include "fb_inv_epilogue.h"
 
 namespace dspsr_amd {
 
@@ -186,7 +186,8 @@ __global__ __launch_bounds__(512) void k_fwd_col1q(const FbGeom g, const FbIn in
 
 // P2': see the head of this section.  LOGM + LOGFB == 13: a tile is Fb channels x 2 polarisations x M bins = 2^14 points;
 // a thread holds, for NJ = 16 / Fb bins j = tid + 512*jq, the Fb rows nb of both polarisations (pair = (pol 0, pol 1)).
-// Items, the fused fold (exact time order per tile, or segmented over part runs) and the output forms are k_inv_chan's.
+// Items (fb_inv_walk.h), the fused fold (exact time order per tile, or segmented over part runs) and the output forms
+// (fb_inv_epilogue.h) are k_inv_chan's.
 template <int LOGM, int LOGFB, int EPI>
 __global__ __launch_bounds__(512) void k_rows_inv(const FbGeom g, const cf* __restrict__ A,
                                                   const cf* __restrict__ kernel, const FbOut out,
@@ -200,13 +201,13 @@ __global__ __launch_bounds__(512) void k_rows_inv(const FbGeom g, const cf* __re
   // (the inverse 512-point transforms as even / odd 256-point halves + a radix-2 step in registers measured -3 % fused but +28 %
   //  on the form that writes its output -- 32-byte store runs --: profiles/r04_experiments.txt item 10; not kept)
   constexpr int logT3 = LOGFB, logT = LOGFB + 1;                     // columns: (kb, pol)
-  constexpr uint32_t Fb = 1u << LOGFB, T3 = Fb, NJ = 16 / Fb;
+  constexpr uint32_t Fb = 1u << LOGFB, NJ = 16 / Fb;
   const int logCa = g.logFa2 - LOGM;                                // Fa / M: channel stride between the rows kb of a tile
   const int logL = g.logFa2 + LOGFB;
   const uint64_t L = 1ull << logL;
   const uint32_t ntile = 1u << logCa;
   struct Abk { cf a, b; };
-  struct Item { uint32_t tile, lp; };
+  typedef InvItem Item;
   auto chan_of = [&](const uint32_t tile, const uint32_t kb) { return tile + (kb << logCa); };
   // Loads: the lane pair (2q, 2q + 1) needs bins j = 2q, 2q + 1 of both polarisations.  The even lane loads the two bins of
   // polarisation 0, the odd lane those of polarisation 1 -- one aligned 16-byte load each instead of two 8-byte ones (half the
@@ -244,77 +245,25 @@ __global__ __launch_bounds__(512) void k_rows_inv(const FbGeom g, const cf* __re
   const uint32_t ltw_off = lds_pad(PTS * blockDim.x) + 8;
   ltw_fill<LOGM>(lds, ltw_off, tw, tid, blockDim.x);
   const uint32_t plan_off = (ltw_off + ltw_entries_dev<LOGM>() + 1) & ~1u;     // (the host sizes the tables for LOGM)
-  uint32_t* psl = nullptr;
-  const uint4* __restrict__ fent_all = nullptr;
-  bool use_psl = false;
-  if constexpr (FOLD) {
-    psl = (uint32_t*)&lds[plan_off + 4 * out.plan_cap];
-    fent_all = (const uint4*)(out.pstart + ((out.nparts_plan + 1 + 3) & ~3u));
-  }
   uint32_t jt = 0;
   Item item, next;
   uint32_t j = 0;
-  uint32_t fold_b = blockIdx.x;
-  const uint32_t fnseg = FOLD && out.nseg > 1 ? out.nseg : 1u;
-  const uint32_t fntg = gridDim.x / fnseg;
-  const uint32_t fseg = fnseg > 1 ? fold_b / fntg : 0u;
-  const uint32_t fpps = (nparts + fnseg - 1) / fnseg;
-  const uint32_t fp0 = fseg * fpps;
-  const uint32_t fnp = fp0 >= nparts ? 0u : (nparts - fp0 < fpps ? nparts - fp0 : fpps);
-  if (fnseg > 1) fold_b -= fseg * fntg;
+  const InvWalk walk = inv_walk(EPI != 0, false, FOLD ? out.nseg : 1u, nparts, ntile, run, gridDim.x, blockIdx.x, 0);
+  const uint32_t fseg = walk.seg;
+  auto next_item = [&](const uint32_t jj, Item& it) -> bool { return inv_walk_item(walk, jj, it); };
+  [[maybe_unused]] InvPlan plan = {};
   if constexpr (FOLD) {
-    if (fnp == 0) return;
-    use_psl = out.plan_cap > 0 && fnp + 1 <= FB_PSL_MAX;          // offsets of this workgroup's run of parts: psl[lp - fp0]
-    if (use_psl) {
-      for (uint32_t q = tid; q <= fnp; q += blockDim.x) psl[q] = out.pstart[part0 + fp0 + q];
-      __syncthreads();
-    }
+    if (walk.np == 0) return;
+    plan = inv_plan_begin<FftPlan<LOGM>::NS>(lds, plan_off, out, part0, walk, tid, blockDim.x);
   }
-  const bool tile_major = EPI != 0 || (ntile >= gridDim.x && ntile % gridDim.x == 0);
-  auto next_item = [&](const uint32_t jj, Item& it) -> bool {
-    if (EPI != 0 || tile_major) {
-      const uint32_t q = jj / fnp;
-      it.tile = fold_b + q * fntg;
-      it.lp = fp0 + (jj - q * fnp);
-      return it.tile < ntile;
-    } else {
-      const uint32_t grid = gridDim.x, b = blockIdx.x;
-      uint32_t hi, lo;
-      if (grid & 7) {
-        const uint32_t lin = b + jj * grid;
-        hi = lin / run; lo = lin - hi * run;
-      } else {
-        const uint32_t q = jj * (grid >> 3) + (b >> 3);
-        const uint32_t qr = q / run;
-        hi = qr * 8 + (b & 7); lo = q - qr * run;
-      }
-      if (run == nparts) { it.tile = hi; it.lp = lo; }
-      else { const uint32_t lin = hi * run + lo; it.tile = lin / nparts; it.lp = lin - it.tile * nparts; }
-      return it.tile < ntile;
-    }
-  };
   if (!next_item(j, item)) return;
   Abk raw[PTS / 2];
   fetch(item, raw);
   cf kk[PTS / 2];
   uint32_t kk_tile = ~0u;
-  uint32_t fe0_cur = 0, fn_cur = 0;
-  auto plan_fetch = [&](const Item it) {
-    if constexpr (FOLD) {
-      const uint32_t lp = it.lp;
-      if (use_psl) { fe0_cur = psl[lp - fp0]; fn_cur = psl[lp - fp0 + 1] - fe0_cur; }
-      else { fe0_cur = out.pstart[part0 + lp]; fn_cur = out.pstart[part0 + lp + 1] - fe0_cur; }
-    }
-  };
-  const bool plan_dma_ok = FOLD && FftPlan<LOGM>::NS >= 2 && use_psl;
-  auto plan_dma = [&](const Item it, const uint32_t buf) {
-    if constexpr (FOLD) {
-      const uint32_t fe0 = psl[it.lp - fp0], fn = psl[it.lp - fp0 + 1] - fe0;
-      if (fn <= out.plan_cap && tid < fn)
-        lds_dma_b128((const void*)(fent_all + fe0 + tid), lds_byte_addr((const uint4*)&lds[plan_off] + buf * out.plan_cap + (tid & ~63u)));
-    }
-  };
-  if (plan_dma_ok) plan_dma(item, 0);
+  if constexpr (FOLD) {
+    if (plan.dma_ok) inv_plan_dma(plan, out, walk, item.lp, 0, tid);
+  }
   FB_ST_BEGIN(7);
 
   for (;;) {
@@ -327,7 +276,7 @@ __global__ __launch_bounds__(512) void k_rows_inv(const FbGeom g, const cf* __re
         kk_tile = item.tile;
       }
       if constexpr (FOLD) {
-        plan_fetch(item);
+        inv_plan_fetch(plan, out, part0, walk, item.lp);
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
       }
       // forward transform over the rows nb of this tile, per bin j: x W_L^{nb*ka} (the twiddle between the two forward passes,
@@ -379,112 +328,21 @@ __global__ __launch_bounds__(512) void k_rows_inv(const FbGeom g, const cf* __re
     // SEARCH: the carry of row tid (ts_reduce).  nrow = npo * Fb <= 32 rows, within the 512 threads: item w < nrow is thread w's first
     [[maybe_unused]] float ts_carry_pre[1] = {0.f};
     if constexpr (SEARCH) tsp = ts_part(out, (uint32_t)part, g.nkeep);
-    const uint32_t fcr = (16u >> logT3) & 15u, fcs_r = ((g.nkeep + 15u - fcr) & ~15u) + fcr;
-    const uint32_t fcs = ((2u * fcs_r) << logT3) <= PTS * blockDim.x ? fcs_r : g.nkeep;
+    const uint32_t fcs = inv_fold_stride(logT3, g.nkeep, blockDim.x);
+    auto chan_at = [&](const uint32_t slo) { return chan_of(tile, slo); };
     auto store = [&](const uint32_t col, const uint32_t p, const uint32_t pstride, auto& v) {
-      constexpr int R = sizeof(v) / sizeof(v[0]);
-      if constexpr (FOLD) {
-        const uint32_t slo = col >> 1;
-        const int32_t t0 = (int32_t)p - (int32_t)g.nfilt_pos;
-#pragma unroll
-        for (int k = 0; k < R; k++) {
-          const int32_t t = t0 + (int32_t)(k * pstride);
-          if ((uint32_t)t >= g.nkeep) continue;
-          float r[4];
-          detect4(cx2_lo(v[k]), cx2_hi(v[k]), out.state, r);
-          *(float4*)&lds[2 * (slo * fcs + (uint32_t)t)] = make_float4(r[0], r[1], r[2], r[3]);
-        }
-        return;
-      }
-      if constexpr (SEARCH) {
-        const int32_t t0 = (int32_t)p - (int32_t)g.nfilt_pos;
-#pragma unroll
-        for (int k = 0; k < R; k++) {
-          const int32_t t = t0 + (int32_t)(k * pstride);
-          if ((uint32_t)t >= g.nkeep) continue;
-          ts_stage((float*)lds, out, tsp, col >> 1, (uint32_t)t, cx2_lo(v[k]), cx2_hi(v[k]));
-        }
-        return;
-      }
-      if (out.kind == FB_OUT_NONE) return;
-      const uint32_t chan = out.chan0 + chan_of(tile, col >> 1);
-      float* __restrict__ row = out.base + chan * out.chan_stride;
-      const int32_t t0 = (int32_t)p - (int32_t)g.nfilt_pos;
-      float2* __restrict__ o2 = (float2*)(row + part * out.part_step) + t0;
-      float4* __restrict__ o4 = (float4*)row + ((int64_t)(part * g.nkeep) + t0);
-      if (out.kind == FB_OUT_COMPLEX) {
-#pragma unroll
-        for (int k = 0; k < R; k++) {
-          if ((uint32_t)(t0 + (int32_t)(k * pstride)) >= g.nkeep) continue;
-          float2* o = o2 + k * pstride;
-          st_stream(o, cx2_lo(v[k]));
-          st_stream((float2*)((float*)o + out.pol_stride), cx2_hi(v[k]));
-        }
-      } else if (out.ndim == 4) {
-#pragma unroll
-        for (int k = 0; k < R; k++) {
-          if ((uint32_t)(t0 + (int32_t)(k * pstride)) >= g.nkeep) continue;
-          float r[4];
-          detect4(cx2_lo(v[k]), cx2_hi(v[k]), out.state, r);
-          st_stream(o4 + k * pstride, make_float4(r[0], r[1], r[2], r[3]));
-        }
-      } else {
-#pragma unroll
-        for (int k = 0; k < R; k++) {
-          const int32_t ts = t0 + (int32_t)(k * pstride);
-          if ((uint32_t)ts >= g.nkeep) continue;
-          float r[4];
-          detect4(cx2_lo(v[k]), cx2_hi(v[k]), out.state, r);
-          const uint64_t idat = part * g.nkeep + (uint32_t)ts;
-          if (out.ndim == 2) {
-            st_stream(&((float2*)row)[idat], make_float2(r[0], r[1]));
-            st_stream(&((float2*)(row + out.pol_stride))[idat], make_float2(r[2], r[3]));
-          } else {
-            row[idat] = r[0];
-            row[out.pol_stride + idat] = r[1];
-            row[2 * out.pol_stride + idat] = r[2];
-            row[3 * out.pol_stride + idat] = r[3];
-          }
-        }
-      }
+      inv_store<FOLD, SEARCH>(lds, g, out, tsp, fcs, chan_at(col >> 1), part, true, col, p, pstride, v);
     };
-    uint32_t f_e0 = 0, f_nact = 0;
-    const uint4* __restrict__ ent = nullptr;
-    const uint4* planl = nullptr;
-    bool in_lds = false;
-    uint4 en_pre = make_uint4(0, 0, 0, 0), en_pre2 = make_uint4(0, 0, 0, 0);
-    float4 acc_pre = make_float4(0.f, 0.f, 0.f, 0.f), acc_pre2 = acc_pre;
     constexpr bool PRE = FOLD && FftPlan<LOGM>::NS >= 2;
-    constexpr bool PRE2 = PRE && LOGFB >= 3;              // >= 8 channels per tile: a thread may fold a second item
+    constexpr int NPRE = PRE && LOGFB >= 3 ? 2 : 1;       // >= 8 channels per tile: a thread may fold a second item
+    [[maybe_unused]] InvFoldPart fpart = {};
+    [[maybe_unused]] InvAcc acc = {};
+    [[maybe_unused]] uint4 en_pre[NPRE] = {};
+    [[maybe_unused]] float4 acc_pre[NPRE] = {};
     if constexpr (FOLD) {
-      f_e0 = fe0_cur;
-      f_nact = fn_cur;
-      ent = fent_all + f_e0;
-      planl = (const uint4*)&lds[plan_off] + (jt & 1) * out.plan_cap;
-      in_lds = plan_dma_ok && f_nact <= out.plan_cap;
+      fpart = inv_fold_part(plan, out, jt);
+      acc = inv_acc(out, fseg);
     }
-    const bool planes2 = FOLD && out.prof_planes == 2;
-    const uint64_t plane = fseg == 0 ? out.plane_stride : 2ull * out.nbin;
-    auto acc_row = [&](const uint32_t w) -> float* {
-      const uint32_t cl = chan_of(tile, w & (T3 - 1));
-      return (float*)(fseg == 0 ? (float4*)out.base + (uint64_t)(out.chan0 + cl) * out.prof_span4
-                                : (float4*)out.part + ((uint64_t)(fseg - 1) * g.C + cl) * out.nbin);
-    };
-    auto acc_load = [&](float* row, const uint32_t b) -> float4 {
-      if (planes2) {
-        const float2 u = *(const float2*)(row + 2 * b), v = *(const float2*)(row + plane + 2 * b);
-        return make_float4(u.x, u.y, v.x, v.y);
-      }
-      return *(const float4*)(row + 4 * b);
-    };
-    auto acc_store = [&](float* row, const uint32_t b, const float4 a) {
-      if (planes2) {
-        *(float2*)(row + 2 * b) = make_float2(a.x, a.y);
-        *(float2*)(row + plane + 2 * b) = make_float2(a.z, a.w);
-      } else {
-        *(float4*)(row + 4 * b) = a;
-      }
-    };
     auto mid = [&](const int phase) {
       if constexpr (SEARCH) {
         // the open output sample's partial sum (this workgroup's store at the end of the previous part; FROM_LDS: the rows -> bins
@@ -494,19 +352,11 @@ __global__ __launch_bounds__(512) void k_rows_inv(const FbGeom g, const cf* __re
           ts_carry_pre[0] = ts_carry_load(out, (out.chan0 + chan_of(tile, tid / npo)) * npo + tid % npo);
       }
       if constexpr (PRE) {
-        if (phase == 2 && in_lds && tid < (f_nact << logT3)) {
-          en_pre = planl[tid >> logT3];
-          acc_pre = acc_load(acc_row(tid), en_pre.x);
-        }
-        // (many channels per tile: a part's active bins x Fb channels exceed the workgroup, so a thread folds a second
-        //  item -- its accumulator is requested here as well instead of costing a memory round trip in the fold phase)
-        if constexpr (PRE2) {
-          if (phase == 2 && in_lds && tid + 512u < (f_nact << logT3)) {
-            en_pre2 = planl[(tid + 512u) >> logT3];
-            acc_pre2 = acc_load(acc_row(tid + 512u), en_pre2.x);
-          }
-        }
-        if (phase == 2 && plan_dma_ok && more) plan_dma(next, (jt + 1) & 1);
+        // 512u here and blockDim.x in inv_fold_phase below are one value, the 512 threads this kernel is written for (512u * jq above): the fold phase
+        // takes the second pre-loaded accumulator for item tid + blockDim.x.  (The constant as the fold loop's step spilled in
+        // k_rows_inv<12, 1, 1>, so the loop keeps blockDim.x; the pre-load had the literal at the parent.)
+        if (phase == 2) inv_acc_preload<NPRE>(g, out, acc, fseg, fpart, logT3, tid, 512u, en_pre, acc_pre, chan_at);
+        if (phase == 2 && plan.dma_ok && more) inv_plan_dma(plan, out, walk, next.lp, (jt + 1) & 1, tid);
       }
     };
     wgfft<LOGM, +1, EPI != 0, true>(lds, ltw_off, tid, logT, x, store, mid);
@@ -514,48 +364,11 @@ __global__ __launch_bounds__(512) void k_rows_inv(const FbGeom g, const cf* __re
     if constexpr (SEARCH) {
       __syncthreads();                       // the tile's detected samples are staged
       const uint32_t npo = out.state == DSPSR_AMD_PPQQ ? 2u : 1u;
-      ts_reduce((const float*)lds, out, tsp, npo << logT3, ts_carry_pre, tid, blockDim.x, [&](const uint32_t slo) { return chan_of(tile, slo); });
+      ts_reduce((const float*)lds, out, tsp, npo << logT3, ts_carry_pre, tid, blockDim.x, chan_at);
     }
     if constexpr (FOLD) {
       __syncthreads();
-      const bool pre = PRE && in_lds;
-      for (uint32_t w = tid; w < (f_nact << logT3); w += blockDim.x) {
-        const uint32_t slo = w & (T3 - 1);
-        uint4 en;
-        float4 acc;
-        if (pre && w == tid) {
-          en = en_pre;
-          acc = acc_pre;
-        } else if (PRE2 && pre && w == tid + 512u) {
-          en = en_pre2;
-          acc = acc_pre2;
-        } else {
-          en = in_lds ? planl[w >> logT3] : ent[w >> logT3];
-          acc = acc_load(acc_row(w), en.x);
-        }
-        const uint32_t nint = en.z >> 16;
-        float* __restrict__ pp = acc_row(w);
-        uint32_t off = en.w, hits = en.z & 0xffffu;
-        for (uint32_t i = 0;;) {
-          const float4* __restrict__ src = (const float4*)&lds[2 * (slo * fcs + off)];
-          uint32_t h = 0;
-          for (; h + 8 <= hits; h += 8) {
-            float4 sm[8];
-#pragma unroll
-            for (int q = 0; q < 8; q++) sm[q] = src[h + q];
-#pragma unroll
-            for (int q = 0; q < 8; q++) { acc.x += sm[q].x; acc.y += sm[q].y; acc.z += sm[q].z; acc.w += sm[q].w; }
-          }
-          for (; h < hits; h++) {
-            const float4 sm = src[h];
-            acc.x += sm.x; acc.y += sm.y; acc.z += sm.z; acc.w += sm.w;
-          }
-          if (++i >= nint) break;
-          const Interval iv = out.piv[en.y + i];
-          off = (uint32_t)iv.offset; hits = iv.hits;
-        }
-        acc_store(pp, en.x, acc);
-      }
+      inv_fold_phase<NPRE>(lds, g, out, acc, fseg, fpart, PRE && fpart.in_lds, logT3, fcs, tid, blockDim.x, en_pre, acc_pre, chan_at);
     }
     FB_ST(7, 5);
     FB_ST_TILE(7, 6);

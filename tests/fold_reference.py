@@ -200,7 +200,7 @@ def fused_nseg(ns, tiles, wgs):
 
 
 def fused_runs_of_launch(ns, nseg):
-    """the kernel's run arithmetic (fb_inv_chan.h: fpps, fp0, fnp): [(first part, parts)] of runs 0 .. nseg - 1 of a launch of
+    """the kernel's run arithmetic (fb_inv_walk.h: pps, p0, np): [(first part, parts)] of runs 0 .. nseg - 1 of a launch of
     ns parts; trailing runs may hold no part (their workgroups return at once)"""
     fpps = -(-ns // nseg)
     return [(s * fpps, max(0, min(ns, (s + 1) * fpps) - s * fpps)) for s in range(nseg)]

@@ -1,5 +1,5 @@
 """The fold inside the last filterbank pass (dspsr_amd_filterbank_perform_fold: k_inv_chan<., FOLD> of csrc/fb_inv_chan.h, its
-two-pass twin k_rows_inv<., ., FOLD> of csrc/fb_two_pass.hip, fb_launch_fused of csrc/filterbank.hip, the part plan of csrc/fold_plan.h
+two-pass twin k_rows_inv<., ., FOLD> of csrc/fb_two_pass.hip, their item walk csrc/fb_inv_walk.h and fold csrc/fb_inv_epilogue.h, fb_launch_fused of csrc/filterbank.hip, the part plan of csrc/fold_plan.h
 and fold_combine_partials of csrc/fold.hip): the host's geometry and launch arithmetic restated, and the cases of
 tests/test_gpu_fused_fold.py as plain data with a computed record of the branches each one reaches.  No torch: the host test
 tests/test_fused_fold_cases_host.py checks on a machine without a GPU that every case reaches what its name says.
@@ -103,7 +103,7 @@ def grid_for(items, ncu):
 
 
 def fold_b_permutation(grid, lr):
-    """fb_inv_chan.h: the tile of workgroup b in an exact launch (fnseg == 1): blocks b, b + 8, ... of one X layout block of
+    """fb_inv_walk.h (xcd_lr): the tile of workgroup b in an exact launch (nseg == 1): blocks b, b + 8, ... of one X layout block of
     2^lr tiles; the identity unless lr > 0 and the grid is a multiple of 8 << lr"""
     b = np.arange(grid, dtype=np.int64)
     if lr > 0 and grid & ((8 << lr) - 1) == 0:
@@ -395,7 +395,7 @@ def record(name, ncu=256, wg3=None):
     wgs = ncu * (g["wg3"] if wg3 is None else wg3) if g["passes"] == 3 else ncu
     rec["wgs"] = wgs
     rec["grid_exact"] = grid_for(g["tiles"], wgs)
-    rec["lr"] = g["logX3"] - g["kernel_logT3"]                 # fb_inv_chan.h: lr = logX3 - logT3 with the KERNEL's logT3
+    rec["lr"] = g["logX3"] - g["kernel_logT3"]                 # fb_inv_chan.h (the xcd_lr it hands to inv_walk): lr = logX3 - logT3 with the KERNEL's logT3
     for k, (parts, _plan) in enumerate(c["calls"]):
         runs, _hits, _ndat = call_runs(name, k)
         path, assoc = dispatch(c, g, k, ncu)
@@ -407,7 +407,7 @@ def record(name, ncu=256, wg3=None):
                 nseg = fused_nseg(ns, g["tiles"], wgs) if mode == 2 else 1
                 rr = fused_runs_of_launch(ns, nseg)
                 nact = [len(pp[part0 + p]) for p in range(ns)]
-                # per part: the offsets of its run sit in LDS (use_psl); then, and only then, its entries can (plan_dma_ok)
+                # per part: the offsets of its run sit in LDS (fb_inv_epilogue.h InvPlan::use_psl); then, and only then, its entries can (dma_ok)
                 part_psl = [g["plan_cap"] > 0 and n + 1 <= FB_PSL_MAX for _p0, n in rr for _ in range(n)]
                 in_lds = [g["stages"] >= 2 and u and a <= g["plan_cap"] for u, a in zip(part_psl, nact)]
                 items = [-(-(a * g["T3"]) // g["blockdim"]) for a in nact]

@@ -9,17 +9,17 @@ from device_buffers import OutputLayout
 # name: (C, M, nfilt, npart, _fb_block keywords, calls that reach the family, npass() that proves it ran: (raw_input, value))
 # npart 3 with max_parts 2: a call spans a full launch group and a ragged one
 FAMILIES = {
-    # filterbank.hip fb_run_tiles, one inverse pass: fb_inv_chan.h:354-364 (float2 rows), :355,383-384 (float4 / float2 / planes)
+    # filterbank.hip fb_run_tiles, one inverse pass: inv_store of fb_inv_epilogue.h (float2 rows; float4 / float2 / planes)
     "inv_chan": (16, 256, (20, 21), 3, dict(max_parts=2), ("raw", "rows"), (1, 3)),
-    # fb_run_tiles, four-pass inverse (k_inv_a + k_inv_b), forced: fb_four_pass.hip:401-405 (float2 rows), :413-427 (detected)
+    # fb_run_tiles, four-pass inverse (k_inv_a + k_inv_b), forced: k_inv_b's store of fb_four_pass.hip (float2 rows; detected)
     "four_pass_forced": (16, 256, (20, 21), 3, dict(max_parts=2, four_pass=True), ("raw", "rows"), (1, 4)),
     # the same kernels by length (freq_res > 8192)
     "four_pass_long": (2, 16384, (900, 1100), 3, dict(max_parts=2), ("raw",), (1, 4)),
-    # fb_run_two_pass (complex dual-pol 8-bit block, nchan_subband * freq_res^2 = 2^27): fb_two_pass.hip:413-421, :414,440-441
+    # fb_run_two_pass (complex dual-pol 8-bit block, nchan_subband * freq_res^2 = 2^27): k_rows_inv of fb_two_pass.hip, the same inv_store
     "two_pass": (512, 512, (27, 27), 3, dict(real=False, max_parts=2), ("raw",), (1, 2)),
     # nchan_subband = 3 * 2^k: k_sub_split + k_sub_combine in front of the inverse pass of fb_inv_chan.h
     "odd_channels": (96, 256, (20, 21), 3, dict(max_parts=2), ("raw",), (1, 3)),
-    # freq_res = 5 * 2^k: the last step is k_time_combine, a writer of its own (fb_inv_chan.hip)
+    # freq_res = 5 * 2^k: the last step is k_time_combine (fb_inv_chan.hip), which writes with the row writers of fb_common.h itself
     "odd_freq_res": (16, 5 * 128, (33, 20), 3, dict(max_parts=2), ("raw", "rows"), (1, 3)),
     # fb_run_subbands: two input channels, FbOut::chan0 moves the rows of the second
     "subbands": (16, 256, (20, 21), 3, dict(input_nchan=2, max_parts=2), ("raw",), (1, 3)),

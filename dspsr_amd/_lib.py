@@ -108,6 +108,7 @@ SYMBOLS = {
     "dspsr_amd_filterbank_perform_detect": (_i, [_vp, _vp, _u64, _u64, _u64, _vp, _i, _f, _i, _u32, _vp, _u64, _u64,
                                                  _u64]),
     "dspsr_amd_filterbank_fold_is_fused": (_i, [_vp]),
+    "dspsr_amd_filterbank_fold_is_fused_state": (_i, [_vp, _i]),
     "dspsr_amd_filterbank_npass": (_i, [_vp, _i]),
     "dspsr_amd_filterbank_presplit": (_i, [_vp]),
     "dspsr_amd_filterbank_takes_heaps": (_i, [_vp]),

@@ -668,6 +668,7 @@ k1_t fb_pick1_dual(int raww);      // pass 1 on pairs of two-column tiles (2^13-
 k2_t fb_pick2(int logf, bool full, bool presplit = false);
 k3_t fb_pick3(int logf, bool full, bool presplit = false);       // plain
 k3_t fb_pick3f(int logf, bool full, bool presplit = false);      // fused fold
+k3_t fb_pick3q(int logf, bool full, bool presplit = false);      // fused fold of the square-law states (fb_inv_chan_fold_sq.hip)
 k3_t fb_pick3s(int logf, bool full, bool presplit = false);      // search mode (detection + time scrunch)
 k3_t fb_pick3m(int logf, bool full, bool presplit = false);      // matrix response, plain output (fb_inv_chan_matrix.hip)
 k3a_t fb_pick3a(int logf, bool blocked, bool real, bool full);

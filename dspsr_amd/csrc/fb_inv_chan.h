@@ -25,7 +25,9 @@ namespace dspsr_amd {
 // EPI: 0 = complex or detected output written by the last stage; 1 (FOLD) = fused fold; 2 = search mode (FB_OUT_SEARCH): square-law
 // detection + time scrunch of the detected stream (digifil -F N:D, LoadToFil.C:185-222,250-304), staged like the fold's samples and
 // reduced by ts_reduce (fb_common.h).  Both walk the parts of a tile in order (the fold's profile, the scrunch's carry).
-// EPIP = EPI + 4 * PRESPLIT: the pre-split forms are k_inv_chan<., 4 | 5 | 6, .>, the others keep the names they had.  (As a
+// 3 = fused fold of the square-law states (Intensity, PPQQ: dspsr -d 1, -d 2; fb_inv_chan_fold_sq.hip): FOLD's walk and plan, the
+// samples staged as one or two floats and added to scalar accumulators (fb_inv_epilogue.h, "the fused square-law fold").
+// EPIP = EPI + 4 * PRESPLIT: the pre-split forms are k_inv_chan<., 4 | 5 | 6 | 7, .>, the others keep the names they had.  (As a
 // fourth template parameter the flag renames every instantiation; as a device body behind two kernels the fused pre-split form
 // came out with 12 bytes of scratch: profiles/r07_experiments.txt.)
 // EPIP bit 8 (FB_EPI_MATRIX, plain output only: k_inv_chan<., 8 | 12, .>, fb_inv_chan_matrix.hip): the response is one Jones matrix
@@ -70,6 +72,7 @@ __global__ __launch_bounds__(512) void k_inv_chan(const FbGeom g, const cf* __re
   static_assert(!MATRIX || EPI == 0, "the matrix response has the plain epilogue only");
   typedef FftPlan<LOGF> P;
   constexpr bool FOLD = EPI == 1, SEARCH = EPI == 2;
+  constexpr bool FOLDQ = EPI == 3;          // the fused square-law fold: walks and plans as FOLD, stages and adds floats
   extern __shared__ __attribute__((aligned(16))) cf lds[];
   uint32_t tid = threadIdx.x;
   const int logT3 = LOGT >= 1 ? LOGT - 1 : g.logT3;
@@ -198,11 +201,11 @@ __global__ __launch_bounds__(512) void k_inv_chan(const FbGeom g, const cf* __re
   Item item, next;
   uint32_t j = 0;
   // (MATRIX and the XCD remap of the fused fold's tiles are this kernel's own parameters of the walk)
-  const InvWalk walk = inv_walk(EPI != 0, MATRIX, FOLD ? out.nseg : 1u, nparts, ntile, run, gridDim.x, blockIdx.x, FOLD ? logX3 - logT3 : 0);
+  const InvWalk walk = inv_walk(EPI != 0, MATRIX, FOLD || FOLDQ ? out.nseg : 1u, nparts, ntile, run, gridDim.x, blockIdx.x, FOLD || FOLDQ ? logX3 - logT3 : 0);
   const uint32_t fseg = walk.seg;
   auto next_item = [&](const uint32_t jj, Item& it) -> bool { return inv_walk_item(walk, jj, it); };
   [[maybe_unused]] InvPlan plan = {};
-  if constexpr (FOLD) {
+  if constexpr (FOLD || FOLDQ) {
     if (walk.np == 0) return;
     plan = inv_plan_begin<P::NS>(lds, plan_off, out, part0, walk, tid, blockDim.x);
   }
@@ -211,7 +214,7 @@ __global__ __launch_bounds__(512) void k_inv_chan(const FbGeom g, const cf* __re
   fetch(item, raw, -1);
   cf kk[MATRIX ? 1 : PTS / 2];          // chirp of the current tile (MATRIX: none, the response is streamed per item)
   uint32_t kk_tile = ~0u;
-  if constexpr (FOLD) {
+  if constexpr (FOLD || FOLDQ) {
     if (plan.dma_ok) inv_plan_dma(plan, out, walk, item.lp, 0, tid);
   }
 
@@ -229,7 +232,7 @@ __global__ __launch_bounds__(512) void k_inv_chan(const FbGeom g, const cf* __re
           kk_tile = item.tile;
         }
       }
-      if constexpr (FOLD) {
+      if constexpr (FOLD || FOLDQ) {
         inv_plan_fetch(plan, out, part0, walk, item.lp);
         // the entries requested during the previous tile (or in front of the loop) have landed once every older load has
         // -- they were issued half a tile ago, behind the prefetch of this tile
@@ -339,8 +342,11 @@ __global__ __launch_bounds__(512) void k_inv_chan(const FbGeom g, const cf* __re
     if constexpr (SEARCH) tsp = ts_part(out, (uint32_t)part, g.nkeep);
     const uint32_t fcs = inv_fold_stride(logT3, g.nkeep, blockDim.x);
     auto chan_of = [&](const uint32_t slo) { return tile * T3 + slo; };
+    [[maybe_unused]] uint32_t fcq = 0;              // FOLDQ: samples from one staged channel to the next
+    if constexpr (FOLDQ) fcq = inv_foldq_stride(logT3, g.nkeep, blockDim.x, out.prof_planes);
     auto store = [&](const uint32_t col, const uint32_t p, const uint32_t pstride, auto& v) {
-      inv_store<FOLD, SEARCH>(lds, g, out, tsp, fcs, chan_of(col >> 1), part, g.npol == 2, col, p, pstride, v);
+      if constexpr (FOLDQ) inv_store_sq(lds, g, out, fcq, g.npol == 2, col, p, pstride, v);
+      else inv_store<FOLD, SEARCH>(lds, g, out, tsp, fcs, chan_of(col >> 1), part, g.npol == 2, col, p, pstride, v);
     };
     // FOLD: this part's active bins, and the accumulator of the thread's first work item (fb_inv_epilogue.h)
     constexpr bool PRE = FOLD && FftPlan<LOGF>::NS >= 2;
@@ -352,6 +358,7 @@ __global__ __launch_bounds__(512) void k_inv_chan(const FbGeom g, const cf* __re
       fpart = inv_fold_part(plan, out, jt);
       acc = inv_acc(out, fseg);
     }
+    if constexpr (FOLDQ) fpart = inv_fold_part(plan, out, jt);
     auto mid = [&](const int phase) {
       if constexpr (SEARCH) {
         // the open output sample's partial sum (written by this workgroup at the end of the previous part, two barriers ago)
@@ -365,6 +372,9 @@ __global__ __launch_bounds__(512) void k_inv_chan(const FbGeom g, const cf* __re
         if (phase == 2) inv_acc_preload<1>(g, out, acc, fseg, fpart, logT3, tid, blockDim.x, en_pre, acc_pre, chan_of);
         // every wave is past this tile's first exchange barrier, i.e. has left the previous tile's fold: the other plan
         // buffer is free for the entries of the next item
+        if (phase == 2 && plan.dma_ok && more) inv_plan_dma(plan, out, walk, next.lp, (jt + 1) & 1, tid);
+      }
+      if constexpr (FOLDQ && FftPlan<LOGF>::NS >= 2) {       // (the other plan buffer is free, as above; no accumulator is pre-loaded)
         if (phase == 2 && plan.dma_ok && more) inv_plan_dma(plan, out, walk, next.lp, (jt + 1) & 1, tid);
       }
     };
@@ -396,6 +406,11 @@ __global__ __launch_bounds__(512) void k_inv_chan(const FbGeom g, const cf* __re
     if constexpr (FOLD) {
       __syncthreads();                       // the tile's detected samples are staged
       inv_fold_phase<1>(lds, g, out, acc, fseg, fpart, PRE && fpart.in_lds, logT3, fcs, tid, blockDim.x, en_pre, acc_pre, chan_of);
+    }
+    if constexpr (FOLDQ) {
+      __syncthreads();                       // the tile's detected samples are staged
+      if (out.prof_planes == 2) inv_foldq_phase<2>(lds, g, out, fseg, fpart, logT3, fcq, tid, blockDim.x, chan_of);
+      else inv_foldq_phase<1>(lds, g, out, fseg, fpart, logT3, fcq, tid, blockDim.x, chan_of);
     }
     FB_ST(3, 4);
     FB_ST_TILE(3, 5);

@@ -268,4 +268,100 @@ DEV void inv_fold_phase(const cf* lds, const FbGeom& g, const FbOut& out, const 
   }
 }
 
+// ---- the fused square-law fold (EPI == 3: Intensity, PPQQ; dspsr -d 1, -d 2) -------------------------------------------------------
+// The same plan, the same item walk, the same time order; what differs is the sample.  A kept sample is detected with sqld() and
+// staged as NPO = out.prof_planes floats: PP + QQ (Detection.C:285-300; the power of its one polarisation where the object has one:
+// the pair's second half is no signal, see SEARCH above), or (PP, QQ).  Staged UNPADDED, channel after channel, as the 16-byte
+// samples are: fcs samples from one channel to the next.  A group of lanes stores 128 bytes at once (32 lanes of ds_write_b32, 16
+// of ds_write_b64): the T3 channels x S / T3 consecutive samples of such a group, S = 32 / NPO samples, fall on different banks
+// when the channel stride is S / T3 samples more than a multiple of S.
+// The accumulators are single floats: row (channel c, q) of the profile starts at out.base + (c * NPO + q) * out.chan_stride (the
+// fold's row span in floats, in the field the fold form did not use), a run's partial profile is packed [chan][NPO][nbin].  ANY
+// float-aligned profile fuses: there is no condition on the base address, the span or the padding of a bound profile.
+DEV uint32_t inv_foldq_stride(const int logT3, const uint32_t nkeep, const uint32_t nthreads, const uint32_t npo)
+{
+  const uint32_t S = 32u / npo, fcr = (S >> logT3) & (S - 1u), fcs_r = ((nkeep + S - 1u - fcr) & ~(S - 1u)) + fcr;
+  return ((npo * fcs_r) << logT3) <= 2u * PTS * nthreads ? fcs_r : nkeep;      // (npo * T3 * nkeep words always fit: 4 * T3 * M do)
+}
+
+template <class V>
+DEV void inv_store_sq(cf* lds, const FbGeom& g, const FbOut& out, const uint32_t fcs, const bool two, const uint32_t col, const uint32_t p,
+                      const uint32_t pstride, V& v)
+{
+  constexpr int R = sizeof(v) / sizeof(v[0]);
+  const int32_t t0 = (int32_t)p - (int32_t)g.nfilt_pos;
+  float* __restrict__ row = (float*)lds + (size_t)(col >> 1) * fcs * out.prof_planes;
+  if (out.prof_planes == 2) {                 // uniform: chosen outside the unrolled element loop
+#pragma unroll
+    for (int k = 0; k < R; k++) {
+      const int32_t t = t0 + (int32_t)(k * pstride);
+      if ((uint32_t)t >= g.nkeep) continue;
+      *(float2*)&row[2 * (uint32_t)t] = make_float2(sqld(cx2_lo(v[k])), sqld(cx2_hi(v[k])));
+    }
+    return;
+  }
+#pragma unroll
+  for (int k = 0; k < R; k++) {
+    const int32_t t = t0 + (int32_t)(k * pstride);
+    if ((uint32_t)t >= g.nkeep) continue;
+    const float pp = sqld(cx2_lo(v[k]));
+    row[(uint32_t)t] = two ? __fadd_rn(pp, sqld(cx2_hi(v[k]))) : pp;
+  }
+}
+
+// row q = 0 of channel cl (within this input channel's sub-band), and the floats from it to row q = 1
+DEV float* inv_accq_row(const FbGeom& g, const FbOut& out, const uint32_t seg, const uint32_t cl)
+{
+  return seg == 0 ? out.base + (uint64_t)(out.chan0 + cl) * out.prof_planes * out.chan_stride
+                  : out.part + ((uint64_t)(seg - 1) * g.C + cl) * out.prof_planes * out.nbin;
+}
+
+// The fold phase of inv_fold_phase on NPO floats per sample: a work item is (active bin, staged channel) and carries the NPO
+// accumulators of the channel's rows, so the plan is walked once for PP and QQ and a sample is one LDS read (ds_read_b64).  No
+// accumulator is pre-loaded in the middle of the transform (inv_acc_preload): the item loads its own, at the cost of one
+// memory round trip per part in the waves that fold.
+template <int NPO, class ChanOf>
+DEV void inv_foldq_phase(const cf* lds, const FbGeom& g, const FbOut& out, const uint32_t seg, const InvFoldPart& fp, const int logT3,
+                         const uint32_t fcs, const uint32_t tid, const uint32_t wstep, ChanOf&& chan_of)
+{
+  static_assert(NPO == 1 || NPO == 2, "inv_foldq_phase: one or two floats per sample");
+  const float* __restrict__ stg = (const float*)lds;
+  const uint64_t rs = seg == 0 ? out.chan_stride : out.nbin;           // floats from row q to row q + 1
+  for (uint32_t w = tid; w < (fp.nact << logT3); w += wstep) {
+    const uint32_t slo = w & ((1u << logT3) - 1);
+    const uint4 en = fp.in_lds ? fp.planl[w >> logT3] : fp.ent[w >> logT3];
+    float* __restrict__ pp = inv_accq_row(g, out, seg, chan_of(slo)) + en.x;
+    float acc[NPO];
+#pragma unroll
+    for (int q = 0; q < NPO; q++) acc[q] = pp[q * rs];
+    const uint32_t nint = en.z >> 16;
+    uint32_t off = en.w, hits = en.z & 0xffffu;
+    for (uint32_t i = 0;;) {
+      const float* __restrict__ src = stg + (size_t)(slo * fcs + off) * NPO;            // consecutive samples: constant offsets
+      uint32_t h = 0;
+      for (; h + 8 <= hits; h += 8) {
+        float sm[8][NPO];
+#pragma unroll
+        for (int q = 0; q < 8; q++) {
+          if constexpr (NPO == 2) { const float2 s2 = *(const float2*)&src[2 * (h + q)]; sm[q][0] = s2.x; sm[q][1] = s2.y; }
+          else sm[q][0] = src[h + q];
+        }
+#pragma unroll
+        for (int q = 0; q < 8; q++)
+#pragma unroll
+          for (int d = 0; d < NPO; d++) acc[d] += sm[q][d];
+      }
+      for (; h < hits; h++) {
+        if constexpr (NPO == 2) { const float2 s2 = *(const float2*)&src[2 * h]; acc[0] += s2.x; acc[1] += s2.y; }
+        else acc[0] += src[h];
+      }
+      if (++i >= nint) break;
+      const Interval iv = out.piv[en.y + i];
+      off = (uint32_t)iv.offset; hits = iv.hits;
+    }
+#pragma unroll
+    for (int q = 0; q < NPO; q++) pp[q * rs] = acc[q];
+  }
+}
+
 }  // namespace dspsr_amd

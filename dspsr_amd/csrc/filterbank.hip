@@ -39,6 +39,7 @@ struct dspsr_amd_filterbank_impl {
   FbPass<k2_t> p2 = {};
   FbPass<k3_t> p3 = {}, p3f = {}, p3s = {};  // inverse pass: plain, fused fold (the plan in LDS behind the tile), search mode
   FbPass<k3_t> p3m = {};                     // ... with the matrix response (fb_pick3m; set by the first set_response_matrix)
+  FbPass<k3_t> p3q = {};                     // ... fused fold of the square-law states (Intensity, PPQQ): p3f's LDS and plan
   FbPass<k3a_t> p3a = {};                    // four-pass geometry: the first inverse pass
   FbPass<k3b_t> p3b = {}, p3bf = {};         // ... the second one, plain / leaving fold segment sums (FB_OUT_SEGSUM)
   float* fpart = nullptr;    // segmented fused fold: partial profiles of the part runs 1 .. nseg-1 of a launch
@@ -289,7 +290,7 @@ static int fb_tile(dspsr_amd_filterbank* fb)
     fb->p3bf = fb->p3b;
   } else {
     shape(fb->p3, p3, g.logM, true);
-    fb->p3f = fb->p3s = fb->p3m = fb->p3;
+    fb->p3f = fb->p3q = fb->p3s = fb->p3m = fb->p3;
   }
   return DSPSR_AMD_OK;
 }
@@ -334,13 +335,15 @@ static int fb_pick_kernels(dspsr_amd_filterbank* fb)
     const FbPlanLds pl = fb_plan_lds(fb->p3.lds, fb->p3.threads);   // one plan entry per thread of the workgroup (<= 512)
     fb->plan_cap = pl.cap;
     fb->p3f.lds = pl.lds;
+    fb->p3q.kern = fb_pick3q(g.logM, full3, ps);
+    fb->p3q.lds = pl.lds;
   }
   if (!((fb->p1_w1.kern || fb->p1_w4.kern) && fb->p2.kern && (g.four_pass ? (fb->p3a.kern && fb->p3b.kern) : (fb->p3.kern != nullptr))))
     return fb_fail(fb->ctx, DSPSR_AMD_EINVAL, "dspsr_amd_filterbank_create: no kernel for this geometry");
   // (the three passes of the pre-split form only work together: X' is not the X layout; it takes the L elements per part X has)
   if (ps && !(fb->p1_w1.kern && fb->p1_w4.kern && fb->p3f.kern && fb->p3s.kern && fb->nseq == 1 && g.xstride == fb->L))
     return fb_fail(fb->ctx, DSPSR_AMD_EINVAL, "dspsr_amd_filterbank_create: no kernels for the pre-split spectrum of this geometry");
-  const hipError_t e = allow_lds(fb->p1_w1, fb->p1_w4, fb->p1d_w1, fb->p1d_w4, fb->p2, fb->p3, fb->p3f, fb->p3s, fb->p3a, fb->p3b, fb->p3bf);
+  const hipError_t e = allow_lds(fb->p1_w1, fb->p1_w4, fb->p1d_w1, fb->p1d_w4, fb->p2, fb->p3, fb->p3f, fb->p3q, fb->p3s, fb->p3a, fb->p3b, fb->p3bf);
   if (e != hipSuccess)
     return fb_fail(fb->ctx, DSPSR_AMD_EHIP, "dspsr_amd_filterbank_create: hipFuncSetAttribute: %s", hipGetErrorString(e));
   return DSPSR_AMD_OK;
@@ -699,6 +702,16 @@ static FbOut fb_out_fold(dspsr_amd_fold* fold, int state, bool planes2, const ui
   o.fold = fold; o.pstart = pstart; o.piv = piv; o.nparts_plan = nparts;
   return o;
 }
+static bool fb_state_square_law(int state) { return state == DSPSR_AMD_INTENSITY || state == DSPSR_AMD_PPQQ; }
+// fused fold of a square-law state (k_inv_chan<., 3 | 7, .>) into the profile of `fold`, npol npo x ndim 1: scalar accumulators, row
+// (chan, q) at base + (chan * npo + q) * chan_stride -- the row span travels in the field the float4 form does not use
+static FbOut fb_out_fold_sq(dspsr_amd_fold* fold, int state, uint32_t npo, const uint32_t* pstart, const Interval* piv, uint32_t nparts)
+{
+  FbOut o = fb_out(FB_OUT_FOLD, fold->profile, fold->span, 0, state, 1);
+  o.nbin = fold->nbin; o.nchan_prof = fold->nchan; o.prof_planes = npo;
+  o.fold = fold; o.pstart = pstart; o.piv = piv; o.nparts_plan = nparts;
+  return o;
+}
 // segment sums of a block of nparts parts into msum: the fold form of a one-plane profile, with the segment plan
 static FbOut fb_out_segsum(float* msum, dspsr_amd_fold* fold, int state, const uint32_t* off, const Interval* siv, const uint32_t* blk_first,
                            const uint32_t* bin_start, uint32_t nparts)
@@ -757,7 +770,10 @@ static int fb_plan_ready(dspsr_amd_filterbank* fb, dspsr_amd_fold* fold)
 }
 
 // whether a call's fused fold is the segmented one
-static bool fb_fold_segmented(const dspsr_amd_filterbank* fb, const FbOut& out) { return out.kind == FB_OUT_FOLD && dspsr_amd_filterbank_fold_is_fused(fb) == 2; }
+static bool fb_fold_segmented(const dspsr_amd_filterbank* fb, const FbOut& out)
+{
+  return out.kind == FB_OUT_FOLD && dspsr_amd_filterbank_fold_is_fused_state(fb, out.state) == 2;
+}
 
 // Fused inverse pass of one launch (ns parts starting at part0).  With fewer channel tiles than compute units the parts
 // are cut into runs folded by different workgroups (k_inv_chan, "Segmented"): partial profiles zeroed before, added to the
@@ -782,7 +798,8 @@ static int fb_launch_fused(dspsr_amd_filterbank* fb, const FbPass<k3_t>& p3, con
   co.nseg = nseg;
   co.part = nullptr;
   if (nseg > 1) {
-    const size_t need = (size_t)(nseg - 1) * g.C * co.nbin * 4;
+    // (floats per bin of a channel: the float4, or the npo rows of a square-law state, packed [seg-1][chan][npo][nbin])
+    const size_t need = (size_t)(nseg - 1) * g.C * co.nbin * (fb_state_square_law(co.state) ? co.prof_planes : 4u);
     if (!grow_device_buffer(ctx->stream, fb->fpart, fb->fpart_floats, need))
       return fb_fail(ctx, DSPSR_AMD_ENOMEM, "dspsr_amd_filterbank_perform_fold: hipMalloc of %zu partial-profile bytes failed",
                      need * sizeof(float));
@@ -954,7 +971,7 @@ struct FbPassKernels { FbPass<k1_t> p1, p1d; FbPass<k3_t> p3; FbPass<k3b_t> p3b;
 static FbPassKernels fb_pass_kernels(const dspsr_amd_filterbank* fb, const FbPass1& p1, const FbOut& out)
 {
   return {p1.raww == 1 ? fb->p1_w1 : fb->p1_w4, p1.raww == 1 ? fb->p1d_w1 : fb->p1d_w4,
-          out.kind == FB_OUT_FOLD ? fb->p3f : out.kind == FB_OUT_SEARCH ? fb->p3s : fb->rmatrix ? fb->p3m : fb->p3,
+          out.kind == FB_OUT_FOLD ? (fb_state_square_law(out.state) ? fb->p3q : fb->p3f) : out.kind == FB_OUT_SEARCH ? fb->p3s : fb->rmatrix ? fb->p3m : fb->p3,
           out.kind == FB_OUT_SEGSUM ? fb->p3bf : fb->p3b};
 }
 
@@ -1316,6 +1333,9 @@ extern "C" int dspsr_amd_filterbank_perform_raw(dspsr_amd_filterbank* fb, const 
                          out_pol_stride, npart, out_step);
 }
 
+static int fb_detect_square_law(dspsr_amd_filterbank* fb, const char* fn, const FbIn& in, uint64_t in_chan_stride, int state, float** det,
+                                uint64_t det_chan_stride, uint64_t det_pol_stride, uint64_t npart);      // (behind fb_search_fits)
+
 extern "C" int dspsr_amd_filterbank_perform_detect(dspsr_amd_filterbank* fb, const float* in_f32_dev,
                                                    uint64_t in_chan_stride, uint64_t in_pol_stride, uint64_t in_step,
                                                    const int8_t* raw_dev, int raw_layout, float scale, int state,
@@ -1323,6 +1343,24 @@ extern "C" int dspsr_amd_filterbank_perform_detect(dspsr_amd_filterbank* fb, con
                                                    uint64_t det_pol_stride, uint64_t npart)
 {
   if (!fb || !det_dev || (!in_f32_dev == !raw_dev)) return DSPSR_AMD_EINVAL;
+  if (fb_state_square_law(state)) {
+    // Detection::square_law (dspsr -d 1, -d 2): rows [chan][npol_out] of npart * nkeep floats
+    const char* fn = "dspsr_amd_filterbank_perform_detect";
+    if (ndim != 1)
+      return fb_fail(fb->ctx, DSPSR_AMD_EINVAL, "%s: state=%d (%s) is detected with ndim=1, not ndim=%u", fn, state,
+                     state == DSPSR_AMD_PPQQ ? "PPQQ" : "Intensity", ndim);
+    if (state == DSPSR_AMD_PPQQ && fb->cfg.npol != 2)
+      return fb_fail(fb->ctx, DSPSR_AMD_EINVAL, "%s: PPQQ needs two polarisations (npol=%u)", fn, fb->cfg.npol);
+    FbIn in;
+    const int rc = fb_input(fb, fn, in_f32_dev, in_pol_stride, in_step, raw_dev, raw_layout, scale, &in);
+    if (rc != DSPSR_AMD_OK) return rc;
+    const uint64_t nchan_out = (uint64_t)fb->cfg.input_nchan * fb_out_C(fb), row = npart * fb_out_nkeep(fb);
+    if (!fb_rows_ok(npart, nchan_out, state == DSPSR_AMD_PPQQ ? 2 : 1, det_chan_stride, det_pol_stride, row, true))
+      return fb_fail(fb->ctx, DSPSR_AMD_EINVAL, "%s: detected rows of %llu floats overlap (chan stride %llu, pol stride %llu)", fn,
+                     (unsigned long long)row, (unsigned long long)det_chan_stride, (unsigned long long)det_pol_stride);
+    float* det = det_dev;
+    return fb_detect_square_law(fb, fn, in, in_chan_stride, state, &det, det_chan_stride, det_pol_stride, npart);
+  }
   if (fb->cfg.npol != 2)
     return fb_fail(fb->ctx, DSPSR_AMD_EINVAL,
                    "dspsr_amd_filterbank_perform_detect: Cannot detect polarization when npol != 2");
@@ -1361,6 +1399,39 @@ static bool fb_search_fits(const dspsr_amd_filterbank* fb, uint32_t npo, uint32_
 extern "C" int dspsr_amd_filterbank_search_is_fused(const dspsr_amd_filterbank* fb)
 {
   return fb && fb_search_fits(fb, 2, 1, nullptr) ? 1 : 0;
+}
+
+// Detection::square_law of a call at the filterbank's own rate (perform_detect, and the Detection of perform_fold's separate
+// launches, with DSPSR_AMD_INTENSITY | DSPSR_AMD_PPQQ): rows [chan][npol_out] of npart * nkeep floats at *det + chan *
+// det_chan_stride + q * det_pol_stride.  *det == nullptr: the rows go, packed, to the object's own block and *det is set.
+// Where the search epilogue fits it runs with a scrunch factor of 1 -- it then writes the detected samples themselves and neither
+// reads nor writes a carry -- else the complex rows go to the object's block and dspsr_amd_detect_square_law detects them: the
+// two routes of perform_search, the same bits.
+// floats from one row to the next of the detected rows the object keeps for itself: ndat rounded up to whole float4
+static inline uint64_t fb_sq_own_row(uint64_t ndat) { return (ndat + 3) & ~3ull; }
+static int fb_detect_square_law(dspsr_amd_filterbank* fb, const char* fn, const FbIn& in, uint64_t in_chan_stride, int state, float** det,
+                                uint64_t det_chan_stride, uint64_t det_pol_stride, uint64_t npart)
+{
+  dspsr_amd_ctx* ctx = fb->ctx;
+  const uint32_t npo = state == DSPSR_AMD_PPQQ ? 2u : 1u, npol = fb->cfg.npol;
+  const uint64_t nchan_out = (uint64_t)fb->cfg.input_nchan * fb_out_C(fb), ndat = npart * fb_out_nkeep(fb);
+  if (!ndat) return DSPSR_AMD_OK;
+  uint32_t G = 0;
+  const bool fused = ndat + 1 < (1ull << 32) && fb_search_fits(fb, npo, 1, &G);          // (the epilogue's 32-bit sample index)
+  const uint64_t crow = 2 * ndat;
+  const size_t ncplx = fused ? 0 : ((size_t)nchan_out * npol * crow + 3) & ~(size_t)3, nown = *det ? 0 : (size_t)nchan_out * npo * fb_sq_own_row(ndat);
+  if (ncplx + nown && !grow_device_buffer(ctx->stream, fb->det, fb->det_floats, ncplx + nown))
+    return fb_fail(ctx, DSPSR_AMD_ENOMEM, "%s: hipMalloc of %zu bytes failed", fn, (ncplx + nown) * sizeof(float));
+  if (!*det) {                             // (16-byte aligned rows: the stand-alone fold's chunk kernels take them)
+    *det = fb->det + ncplx;
+    det_chan_stride = npo * fb_sq_own_row(ndat);
+    det_pol_stride = fb_sq_own_row(ndat);
+  }
+  if (fused) return fb_run(fb, in, fb_out_search(*det, det_chan_stride, det_pol_stride, state, 1, 0, G, nullptr), npart, in_chan_stride);
+  int rc = fb_run(fb, in, fb_out_rows(fb->det, npol * crow, crow, 2ull * fb_out_nkeep(fb)), npart, in_chan_stride);
+  if (rc != DSPSR_AMD_OK) return rc;
+  return dspsr_amd_detect_square_law(ctx, state == DSPSR_AMD_INTENSITY, fb->det, npol * crow, crow, *det, det_chan_stride, det_pol_stride,
+                                     (uint32_t)nchan_out, npol, ndat);
 }
 
 extern "C" int dspsr_amd_filterbank_perform_search(dspsr_amd_filterbank* fb, const float* in_f32_dev, uint64_t in_chan_stride,
@@ -1456,6 +1527,18 @@ extern "C" int dspsr_amd_filterbank_fold_is_fused(const dspsr_amd_filterbank* fb
   return tiles >= 8 ? 2 : 0;                // fewer tiles: the parts of a launch are folded in runs (re-associated sums)
 }
 
+extern "C" int dspsr_amd_filterbank_fold_is_fused_state(const dspsr_amd_filterbank* fb, int state)
+{
+  const int mode = dspsr_amd_filterbank_fold_is_fused(fb);
+  if (!fb_state_square_law(state)) return mode;
+  // the square-law states: the three-pass kernel k_inv_chan<., 3 | 7, .> at the tile counts of the float4 fold -- measured at the
+  // headline's freq_res with 8, 16, 32, 128 and 512 tiles, ms per 32 parts fused / Detection + Fold: Intensity 0.215 / 0.477, 0.223 /
+  // 0.499, 0.233 / 0.542, 0.564 / 0.841, 2.098 / 2.436; PPQQ 0.216 / 0.618, 0.223 / 0.641, 0.234 / 0.681, 0.572 / 0.980, 2.077 /
+  // 2.821 (profiles/fold_state_probe.txt): fused wins at every count, so none answers 0.  An object of one polarisation fuses
+  // too (Intensity: the power of its polarisation).  No segment sums: the four-pass plan is not built for these states
+  return (mode == 1 || mode == 2) && fb->p3q.kern ? mode : 0;
+}
+
 // fb_run with the fold plan in `slot` on its way to the device (no consumer launched: drained here), then handed back
 static int fb_run_with_plan(dspsr_amd_filterbank* fb, dspsr_amd_fold* fold, PlanSlot* slot, const FbIn& in, const FbOut& out,
                             uint64_t npart, uint64_t chan_stride)
@@ -1467,6 +1550,48 @@ static int fb_run_with_plan(dspsr_amd_filterbank* fb, dspsr_amd_fold* fold, Plan
   return rc != DSPSR_AMD_OK ? rc : rc2;
 }
 
+// perform_fold of a square-law state (dspsr -d 1, -d 2): the profile is npol 1 x ndim 1 (Intensity; PP of an object of one
+// polarisation) or npol 2 x ndim 1 (PPQQ).  Fused where fold_is_fused_state says 1 or 2, the call does not take the two-pass path
+// (k_rows_inv has no such epilogue) and no run reaches FOLD_FUSED_MAX_RUN; else Detection (fb_detect_square_law, on the
+// object's own rows) and Fold.  The accumulators are scalars: no condition on a bound profile's address or span.
+static int fb_perform_fold_sq(dspsr_amd_filterbank* fb, const float* in_f32_dev, uint64_t in_chan_stride, uint64_t in_pol_stride,
+                              uint64_t in_step, const int8_t* raw_dev, int raw_layout, float scale, int state, dspsr_amd_fold* fold,
+                              uint64_t npart)
+{
+  const char* fn = "dspsr_amd_filterbank_perform_fold";
+  dspsr_amd_ctx* ctx = fb->ctx;
+  const uint32_t npo = state == DSPSR_AMD_PPQQ ? 2u : 1u, nchan = fb->cfg.input_nchan * fb_out_C(fb);
+  const char* sname = state == DSPSR_AMD_PPQQ ? "PPQQ" : fb->cfg.npol == 1 ? "PP" : "Intensity";
+  if (state == DSPSR_AMD_PPQQ && fb->cfg.npol != 2)
+    return fb_fail(ctx, DSPSR_AMD_EINVAL, "%s: PPQQ needs two polarisations (npol=%u)", fn, fb->cfg.npol);
+  if (!fold->profile || fold->nchan != nchan || fold->npol != npo || fold->ndim != 1)
+    return fb_fail(ctx, DSPSR_AMD_EINVAL, "%s: state=%d (%s) folds into a profile of nchan=%u npol=%u ndim=1 (is %u/%u/%u)", fn, state, sname,
+                   nchan, npo, fold->nchan, fold->npol, fold->ndim);
+  if (fold->folding_nbin != fold->nbin)
+    return fb_fail(ctx, DSPSR_AMD_EINVAL, "dsp::Fold::fold folding_nbin != output->nbin (%u != %u)", fold->folding_nbin, fold->nbin);
+  if (npart > 0xffffffffull) return DSPSR_AMD_EINVAL;
+  FbIn in;
+  int rc = fb_input(fb, fn, in_f32_dev, in_pol_stride, in_step, raw_dev, raw_layout, scale, &in);
+  if (rc != DSPSR_AMD_OK) return rc;
+  const int fmode = dspsr_amd_filterbank_fold_is_fused_state(fb, state);
+  FbOut probe = {};
+  probe.kind = FB_OUT_FOLD;
+  if ((fmode != 1 && fmode != 2) || fb_takes_two_pass(fb, in, probe) || fold_plan_max_run(fold) >= FOLD_FUSED_MAX_RUN) {
+    const uint64_t ndat = npart * fb_out_nkeep(fb);
+    if (!ndat) return DSPSR_AMD_OK;
+    float* det = nullptr;
+    rc = fb_detect_square_law(fb, fn, in, in_chan_stride, state, &det, 0, 0, npart);
+    if (rc != DSPSR_AMD_OK) return rc;
+    return dspsr_amd_fold_fold(fold, det, npo * fb_sq_own_row(ndat), fb_sq_own_row(ndat));
+  }
+  const uint32_t* d_start = nullptr;
+  const Interval* d_iv = nullptr;
+  PlanSlot* slot = nullptr;
+  rc = fold_build_part_plan(fold, fb->g.nkeep, (uint32_t)npart, &d_start, &d_iv, &slot);
+  if (rc != DSPSR_AMD_OK) return rc;
+  return fb_run_with_plan(fb, fold, slot, in, fb_out_fold_sq(fold, state, npo, d_start, d_iv, (uint32_t)npart), npart, in_chan_stride);
+}
+
 extern "C" int dspsr_amd_filterbank_perform_fold(dspsr_amd_filterbank* fb, const float* in_f32_dev,
                                                  uint64_t in_chan_stride, uint64_t in_pol_stride, uint64_t in_step,
                                                  const int8_t* raw_dev, int raw_layout, float scale, int state,
@@ -1474,6 +1599,8 @@ extern "C" int dspsr_amd_filterbank_perform_fold(dspsr_amd_filterbank* fb, const
 {
   if (!fb || !fold || (!in_f32_dev == !raw_dev)) return DSPSR_AMD_EINVAL;
   dspsr_amd_ctx* ctx = fb->ctx;
+  if (fb_state_square_law(state))
+    return fb_perform_fold_sq(fb, in_f32_dev, in_chan_stride, in_pol_stride, in_step, raw_dev, raw_layout, scale, state, fold, npart);
   if (fb->cfg.npol != 2)
     return fb_fail(ctx, DSPSR_AMD_EINVAL, "dspsr_amd_filterbank_perform_fold: Cannot detect polarization when npol != 2");
   if (state != DSPSR_AMD_COHERENCE && state != DSPSR_AMD_STOKES)

@@ -372,9 +372,15 @@ class FilterbankEngine(_Owned):
         if rows is not None:
             inp, in_step, raw = rows[0], rows[1], None
         dcs, dps = _strides3(det)
+        square_law = state in (_lib.INTENSITY, _lib.PPQQ)       # dspsr -d 1, -d 2: rows [nchan][1 | 2][npart * nkeep], ndim 1
+        if square_law:
+            ndim, npo = 1, 2 if state == _lib.PPQQ else 1
         if npart:
             self._need("detected block", det.shape[2], npart * self.nkeep * ndim)
-            if det.shape[1] != 4 // ndim:
+            if square_law and det.shape[1] != npo:
+                raise DspsrAmdError("dspsr_amd.FilterbankEngine.perform_detect: %s needs %d polarisation rows per channel, the block "
+                                    "has %d" % ("PPQQ" if npo == 2 else "Intensity", npo, det.shape[1]))
+            if not square_law and det.shape[1] != 4 // ndim:
                 raise DspsrAmdError("dspsr_amd.FilterbankEngine.perform_detect: ndim=%d needs %d planes, the block has %d"
                                     % (ndim, 4 // ndim, det.shape[1]))
             if raw is not None and layout != _lib.RAW_UWB16:
@@ -436,16 +442,18 @@ class FilterbankEngine(_Owned):
         """True: the forward row pass splits the polarisations and the inverse pass loads them ready."""
         return bool(lib.dspsr_amd_filterbank_presplit(self.handle))
 
-    def fold_is_fused(self) -> int:
+    def fold_is_fused(self, state=_lib.COHERENCE) -> int:
         """0: perform_fold runs Detection + Fold launches; 1: it folds inside the last filterbank pass with exact time-order
         sums (one workgroup per channel tile); 2: it folds inside the last pass with the parts of a launch cut into runs
-        (geometries with fewer tiles than compute units): sums re-associated per run, equal to float rounding."""
-        return int(lib.dspsr_amd_filterbank_fold_is_fused(self.handle))
+        (geometries with fewer tiles than compute units): sums re-associated per run, equal to float rounding.
+        state: INTENSITY and PPQQ have a fused kernel of their own and never answer 3 (segment sums)."""
+        return int(lib.dspsr_amd_filterbank_fold_is_fused_state(self.handle, state))
 
     def perform_fold(self, fold, npart, state=_lib.COHERENCE, inp=None, in_step=0, raw=None,
                      layout=_lib.RAW_GENERIC, scale=1.0):
         """Fused filterbank -> detection (ndim 4) -> fold into `fold`'s device profile; the bin plan of the
-        npart*nkeep output samples must already have been given to `fold` (set_nbin/set_ndat/set_bins)."""
+        npart*nkeep output samples must already have been given to `fold` (set_nbin/set_ndat/set_bins).
+        state INTENSITY / PPQQ (dspsr -d 1, -d 2): `fold` has the shape npol 1 x ndim 1 / npol 2 x ndim 1."""
         rows = self._unpacked_heaps(raw, layout, scale, npart)
         if rows is not None:
             inp, in_step, raw = rows[0], rows[1], None

@@ -20,7 +20,8 @@
 // back to eager execution, block by block, whenever the fusion would change what another caller sees:
 //   * Filterbank::Engine::finish() (Operation::record_time, Filterbank.C:551,664) or any synch executes what is pending;
 //   * Fold folds only a piece of the block (a sub-integration boundary inside it, Subint.h:234-309), a Fold input that is
-//     not the Detection output, a detected shape other than (npol 2, ndim 2) / (npol 1, ndim 4), square-law detection;
+//     not the Detection output, a detected shape other than (npol 2, ndim 2) / (npol 1, ndim 4) or -- square_law, recorded like
+//     polarimetry -- an output state other than Intensity, PPQQ or the power of one input polarisation;
 //   * TimeSeriesEngine::copy_data_fpt reads the pending output (a second consumer that goes through an engine).
 //   * more than one FoldEngine is registered on the chain (dspsr folds N pulsars from ONE detected series: every
 //     fold[ifold]->set_input (to_fold), LoadToFold1.C:917-924,948-955,1206): the first fold() of a block executes the recorded
@@ -97,9 +98,11 @@ namespace HIP
       uint64_t npart, in_step, out_step;
       const int8_t* raw; int raw_layout; float raw_scale;   // raw != 0: the packed block holds the same samples
     };
-    // ---- the arguments of DetectionEngine::polarimetry
+    // ---- the arguments of DetectionEngine::polarimetry, or (square_law) of DetectionEngine::square_law: ndim 1, state
+    //      DSPSR_AMD_INTENSITY (also PP of one input polarisation) | DSPSR_AMD_PPQQ when the fused fold knows the output state, else -1
     struct DetectionCall
     {
+      bool square_law; bool intensity; unsigned npol_in;
       unsigned ndim; int state;
       const dsp::TimeSeries* in;
       dsp::TimeSeries* out;
@@ -129,6 +132,12 @@ namespace HIP
     }
     static void run (dspsr_amd_ctx* ctx, const DetectionCall& c)
     {
+      if (c.square_law)
+      {
+        check (ctx, dspsr_amd_detect_square_law (ctx, c.intensity, c.i.base, c.i.cs, c.i.ps, c.o.base, c.o.cs, c.o.ps, c.nchan, c.npol_in,
+                                                 c.ndat), "HIP::DetectionEngine::square_law");
+        return;
+      }
       check (ctx, dspsr_amd_detect_polarimetry (ctx, c.state, c.ndim, c.i.base, c.i.cs, c.i.ps, c.o.base, c.o.cs, c.o.ps, c.nchan,
                                                 c.ndat), "HIP::DetectionEngine::polarimetry");
     }
@@ -146,14 +155,24 @@ namespace HIP
     //! ~FilterbankEngine: the recorded filterbank call is forgotten (a recorded detection is not)
     void filterbank_gone () { fbk.pending = false; }
 
-    //! DetectionEngine::polarimetry: recorded only behind a recorded filterbank block whose output it reads, in a shape the
+    //! DetectionEngine::polarimetry / square_law: recorded only behind a recorded filterbank block whose output it reads, in a
+    //! shape (polarimetry: ndim 2 or 4) or an output state (square_law: Intensity, PPQQ, the power of one polarisation) the
     //! fused fold writes; otherwise everything recorded runs, then this call
     void detection (const DetectionCall& call)
     {
+      if (call.square_law && !(fbk.pending && !det.pending && call.in == fbk.call.out && call.state >= 0 && call.in != call.out))
+      {
+        // (a square law the fused fold does not take: whatever is recorded runs first, as before it could be recorded at all)
+        flush ();
+        reader (call.in, "HIP::DetectionEngine::square_law");
+        run (ctx, call);
+        return;
+      }
       if (det.pending) flush ();
-      require_written (call.in, "HIP::DetectionEngine::polarimetry");
+      require_written (call.in, call.square_law ? "HIP::DetectionEngine::square_law" : "HIP::DetectionEngine::polarimetry");
       det.call = call;
-      if (fbk.pending && call.in == fbk.call.out && (call.ndim == 2 || call.ndim == 4)) { det.pending = true; return; }
+      const bool fusable = call.square_law ? call.state >= 0 && call.in != call.out : (call.ndim == 2 || call.ndim == 4);
+      if (fbk.pending && call.in == fbk.call.out && fusable) { det.pending = true; return; }
       flush ();
       run (ctx, call);
     }
@@ -172,7 +191,8 @@ namespace HIP
       const DetectionCall& d = det.call;
       const bool whole = fbk.pending && det.pending && r.in == d.out && r.idat_start == 0 && r.ndat == r.in->get_ndat ()
                          && r.in->get_ndat () == d.ndat
-                         && ((r.npol == 2 && r.ndim == 2 && d.ndim == 2) || (r.npol == 1 && r.ndim == 4 && d.ndim == 4))
+                         && (d.square_law ? r.ndim == 1 && r.npol == (d.state == DSPSR_AMD_PPQQ ? 2u : 1u)
+                                          : !d.square_law && ((r.npol == 2 && r.ndim == 2 && d.ndim == 2) || (r.npol == 1 && r.ndim == 4 && d.ndim == 4)))
                          && nfold <= 1 && !r.counts_hits;
       if (!whole)
       {
@@ -488,6 +508,7 @@ namespace HIP
       if (in->get_ndat () != out->get_ndat ())
         throw Error (InvalidParam, "HIP::DetectionEngine::polarimetry", "input ndat != output ndat");
       Chain::DetectionCall c;
+      c.square_law = false; c.intensity = false; c.npol_in = 2;
       c.ndim = ndim; c.in = in; c.out = out;
       c.state = (stokes >= 0 ? stokes == 1 : out->get_state () == Signal::Stokes) ? DSPSR_AMD_STOKES : DSPSR_AMD_COHERENCE;
       c.i = rows_of (in, in->get_nchan (), 2);                       // polarimetry reads two polarisations, whatever npol says
@@ -502,12 +523,24 @@ namespace HIP
 
     void square_law (const dsp::TimeSeries* in, dsp::TimeSeries* out)
     {
-      // (never fused: whatever is recorded runs first)
-      if (chain) { chain->flush (); chain->reader (in, "HIP::DetectionEngine::square_law"); }
-      const Rows<const float*> i = rows_of (in);
-      const Rows<float*> o = rows_of (out);
-      check (ctx, dspsr_amd_detect_square_law (ctx, out->get_state () == Signal::Intensity, i.base, i.cs, i.ps, o.base, o.cs, o.ps,
-                                               in->get_nchan (), in->get_npol (), in->get_ndat ()), "HIP::DetectionEngine::square_law");
+      // Recorded, as polarimetry is, when the output state is one the fused fold writes (dspsr -d 1, -d 2, one polarisation:
+      // dspsr_amd_filterbank_perform_fold with DSPSR_AMD_INTENSITY | DSPSR_AMD_PPQQ): Intensity or PPQQ of two polarisations, or
+      // the power of ONE input polarisation (PP_State; Detection.C:119-121 sends every such state here) -- the library's
+      // Intensity on an object of one polarisation.  Every other case: whatever is recorded runs first, then this launch.
+      Chain::DetectionCall c;
+      c.square_law = true; c.ndim = 1; c.in = in; c.out = out;
+      c.intensity = out->get_state () == Signal::Intensity;
+      c.npol_in = in->get_npol ();
+      c.state = c.npol_in == 1 ? DSPSR_AMD_INTENSITY : c.npol_in != 2 ? -1 : c.intensity ? DSPSR_AMD_INTENSITY
+                : out->get_state () == Signal::PPQQ ? DSPSR_AMD_PPQQ : -1;
+      if (in->get_ndat () != out->get_ndat ()) c.state = -1;
+      c.i = rows_of (in);
+      c.o = rows_of (out);
+      c.nchan = in->get_nchan (); c.ndat = in->get_ndat ();
+      if (chain)
+        chain->detection (c);
+      else
+        Chain::run (ctx, c);
     }
 
   protected:

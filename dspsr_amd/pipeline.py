@@ -13,6 +13,7 @@ from __future__ import annotations
 
 import math
 import os
+import sys
 import dataclasses
 from dataclasses import dataclass
 
@@ -89,9 +90,11 @@ class Config:
                                            # block itself where the front end has that loader (FilterbankEngine.takes_heaps); False = the
                                            # engine unpacks into float rows first, as it does for every other geometry (A/B runs,
                                            # the same numbers bit for bit)
-    npol: int = 4                          # -d: the reference's config->npol.  This path detects the four products (4); the field
-                                           # decides the branch of LoadToFold1.C:552-568 only: with 1 or 3 it wins over -4, which is
-                                           # then ignored
+    npol: int = 4                          # -d: the reference's config->npol, Detection's output (LoadToFold1.C:552-568,1098-1134): 4 the
+                                           # four products (Coherence / Stokes, laid out by ndim), 1 Intensity, 2 PPQQ -- rows and profile
+                                           # of npol x ndim 1 --, 3 the reference's refusal of NthPower.  1 or 3 win over -4, which is then
+                                           # ignored.  One input polarisation folds as PP with any npol but the default 4, which keeps
+                                           # its refusal.  -cyclic and -G read it their own way (cyclic_npol, plfb)
     sk_zap: bool = False                   # -skz: spectral-kurtosis RFI excision (dsp::SpectralKurtosis between the filterbank and
                                            # Detection, LoadToFold1.C:458-532; defaults of LoadToFoldConfig.C:71-89).  False: off --
                                            # today's paths, untouched
@@ -510,6 +513,8 @@ def write_phase_series(path, sub, info: "InputInfo", cfg: "Config", *, nchan=Non
     nchan = nchan or cfg.nchan
     hits = np.asarray(sub["hits"])
     nbin = hits.shape[-1]
+    if state is None and ndim is None and square_law_state(cfg, info, strict=False):       # -d 1 / -d 2 / one polarisation: rows of ndim 1
+        state, ndim = square_law_state(cfg, info, strict=False)[0], 1
     ndim = ndim or cfg.ndim
     if fourth_moment_active(cfg) and not cfg.cyclic_nchan and not cfg.plfb_nbin:
         npol, ndim, state = 1, 14, "FourthMoment"
@@ -1052,6 +1057,38 @@ def calibrator_response(cfg: "Config", info: "InputInfo", subband=None):
     return response, matrix
 
 
+def square_law_state(cfg: "Config", info: "InputInfo", strict=True):
+    """`-d 1`, `-d 2` and one-polarisation input on the plain path (Detection + Fold; -cyclic and -G have their own reading of
+    npol): None where Detection forms the four products or -4 folds their moments -- today's path --, else (state name,
+    library state, output polarisations) of Detection::square_law.  The branch order of LoadToFold1.C:552-568 and 1098-1134:
+    npol 1 or 3 first (Intensity; `Detection::transformation` does not know NthPower, Detection.C:112-133), then -4, then 2
+    (PPQQ), then 4.  One input polarisation folds as PP whatever npol asks for (LoadToFold1.C:1112-1116) -- except under the
+    default npol = 4, where this path keeps the refusal it has always had ("Cannot detect polarization when npol != 2")."""
+    if cfg.cyclic_nchan > 0 or cfg.plfb_nbin > 0 or cfg.npol == 4 or fourth_moment_active(cfg):
+        return None
+    if info.npol == 1:
+        return "PP", _lib.INTENSITY, 1
+    if cfg.npol not in (1, 2) and not strict:                       # (a writer asking what a finished run folded)
+        return None
+    if cfg.npol == 3:
+        raise DspsrAmdError("dsp::Detection cannot convert from Analytic to NthPower")
+    if cfg.npol not in (1, 2):
+        raise DspsrAmdError("dspsr_amd.LoadToFold: npol=%d is not one of 1 (Intensity), 2 (PPQQ), 4 (Coherence / Stokes)" % cfg.npol)
+    return ("Intensity", _lib.INTENSITY, 1) if cfg.npol == 1 else ("PPQQ", _lib.PPQQ, 2)
+
+
+def square_law_check(cfg: "Config", info: "InputInfo"):
+    """What a run with npol != 4 refuses by name, before any device resource is opened: the combinations whose detected rows are
+    not formed by Detection::square_law on this path yet (DESIGN.md section 11)."""
+    who = "dspsr_amd.LoadToFold: npol=%d (-d %d)" % (cfg.npol, cfg.npol)
+    for on, what in ((cfg.sk_zap, "spectral kurtosis (-skz): dsp::SpectralKurtosis hands its rows to Detection::polarimetry here"),
+                     (getattr(info, "nbit", 8) == 2, "two-bit input (NBIT 2): the unpacker's weights are carried to the Coherence fold alone"),
+                     (cfg.calibrator is not None, "the calibrator (-pac): the matrix response has no square-law form"),
+                     (cfg.convolve_when != "during", "convolve_when=%r (-F N, -F N:B): built for -F N:D (convolve_when = during)" % (cfg.convolve_when,))):
+        if on:
+            raise DspsrAmdError("%s is not built with %s" % (who, what))
+
+
 def fourth_moment_active(cfg: "Config") -> bool:
     """The branch order of LoadToFold1.C:552-568: npol 1 or 3 takes the first branch, -4 only the second."""
     return bool(cfg.fourth_moment) and cfg.npol not in (1, 3)
@@ -1353,8 +1390,8 @@ class DetectFold:
         # fused filterbank+detect+fold (no detected time series in HBM): ndim 4, three-pass geometries
         # (the library decides whether fusing pays for this geometry; when it does not, this driver keeps the
         # separate Detection and Fold operations on its own `detected` block; -F N:B never fuses)
-        if cfg.fused_fold and cfg.ndim == 4 and lt.sample_delay is None and cfg.convolve_when != "before":
-            lt.fused_mode = lt.fb.fold_is_fused()
+        if cfg.fused_fold and (cfg.ndim == 4 or lt.square_law) and lt.sample_delay is None and cfg.convolve_when != "before":
+            lt.fused_mode = lt.fb.fold_is_fused(lt.detection_state()) if lt.square_law else lt.fb.fold_is_fused()
         lt.fused_fold = lt.fused_mode != 0      # fused_mode 2: sums re-associated per run of parts (engine.fold_is_fused)
         for name in lt._taps:
             from . import dada
@@ -1369,7 +1406,7 @@ class DetectFold:
                 path, centre_frequency=fc, bandwidth=bw, nchan=lt.nchan_out, npol=fold_npol if det else 2,
                 ndim=fold_ndim if det else 2, nbit=32, rate=lt.out_rate, mjd_day=info.mjd_day,
                 mjd_sec=info.mjd_sec + lt.out_start,
-                state=("FourthMoment" if lt.moments else "Stokes" if cfg.stokes else "Coherence") if det else "Analytic",
+                state=lt.state_name() if det else "Analytic",
                 source=getattr(info, "source", "unknown"), telescope=getattr(info, "telescope", "unknown"))
         if "Fold" in lt.dumps:
             lt.fused_mode, lt.fused_fold = 0, False          # the detected samples must exist in HBM to be dumped
@@ -1379,7 +1416,7 @@ class DetectFold:
         in the same order as the chain every other block takes: filterbank+detect -> [SampleDelay of -K, in place (LoadToFold1.C:
         617-618)] -> fold, by piece or by pulsar.  Without -K: no head room, nothing carried, every sample delivered."""
         lt, cfg, nd, sd, ndat = self.lt, self.lt.cfg, self.lt.cfg.ndim, self.lt.sd, npart * self.lt.nkeep
-        state = _lib.STOKES if cfg.stokes else _lib.COHERENCE
+        state = lt.detection_state()
         if lt.twobit is not None:
             return self._process_twobit(raw, npart, events, state)
         if "Detection" in lt.dumps:                          # the filterbank's complex output: one extra pass, taps only
@@ -1737,6 +1774,7 @@ class LoadToFold:
         self.torch = torch
         self.pulsars, self.cyclic, self.plfb, self.rfi_filter = [], None, None, None
         self.sk, self.sk_statistics = None, None
+        self.square_law = None              # (state name, library state, npol_out) of -d 1 / -d 2 / one polarisation; None: the four products
         self.twobit, self._weights = None, None   # NBIT 2: the TwoBitPlan; the weights of the block in hand (row, ndatperweight, weight_idat)
         self.ctx = self.fb = self.fold = self.response = self.sample_delay = self.detected = self.voltages = None
         self.sd = DelayCarry()               # -K: head room in front of `detected` and the tail carried in it
@@ -1786,8 +1824,16 @@ class LoadToFold:
         # the back end of the run: every later question about the mode is put to it
         self.mode = (CyclicFold if cfg.cyclic_nchan > 0 else PhaseLockedFold if cfg.plfb_nbin > 0 else KurtosisFold if cfg.sk_zap
                      else DetectFold)(self)
+        # -d 1, -d 2, one polarisation: Detection::square_law, rows and profile of npol_out x ndim 1 (cfg.ndim, the layout of the
+        # four products, then says 1 wherever this class reads it)
+        self.square_law = square_law_state(cfg, info)
+        if self.square_law:
+            square_law_check(cfg, info)
+            if info.npol == 1:
+                print("Only single polarization detection available", file=sys.stderr)          # LoadToFold1.C:1114
+            self.cfg = cfg = dataclasses.replace(cfg, ndim=1)
         if self.mode.detects:                                            # (-cyclic and -G read the complex rows of -F N:D)
-            if info.npol != 2:
+            if info.npol != 2 and not self.square_law:
                 raise DspsrAmdError("dsp::Detection::polarimetry Cannot detect polarization when npol != 2")
             if cfg.convolve_when not in ("during", "after", "before", "never"):
                 raise DspsrAmdError("dspsr_amd.LoadToFold: convolve_when=%r is not one of during / after / before / never" % (cfg.convolve_when,))
@@ -1796,7 +1842,7 @@ class LoadToFold:
                                 % (cfg.nchan, info.nchan))
         self.in_nchan = 1 if subband is not None else info.nchan         # input channels in this instance's blocks
         self.nchan_out = (cfg.nchan // info.nchan) * self.in_nchan       # output channels this instance produces
-        self.npol_out = 4 // cfg.ndim
+        self.npol_out = self.square_law[2] if self.square_law else 4 // cfg.ndim
         if cfg.convolve_when != "during":
             self._plan_after(subband, dump_before)
         else:
@@ -1911,6 +1957,14 @@ class LoadToFold:
         self.ctx.synchronize()
         eng.set_kernel(kernel)
         self.rfi_filter = filt
+
+    def detection_state(self):
+        """the library's state of the detected rows: INTENSITY (also PP of one polarisation) / PPQQ for -d 1 / -d 2, else STOKES or COHERENCE"""
+        return self.square_law[1] if self.square_law else _lib.STOKES if self.cfg.stokes else _lib.COHERENCE
+
+    def state_name(self):
+        """Observation::get_state of the folded PhaseSeries (the STATE of its files and of the pre_Fold tap)"""
+        return "FourthMoment" if self.moments else self.square_law[0] if self.square_law else "Stokes" if self.cfg.stokes else "Coherence"
 
     def _fold_dims(self):
         """(npol, ndim) of the folded PhaseSeries: those of the detected rows, or 1 x 14 for -4 (FourthMoment.C:39-42)"""

@@ -204,7 +204,13 @@ int dspsr_amd_filterbank_perform_raw(dspsr_amd_filterbank* fb, const int8_t* raw
  * written at whatever address that gives).  A detected row is npart*nkeep*ndim floats; the 4/ndim rows of a channel and the
  * channels must not overlap, in one of two orders: channel-major (TimeSeries FPT order: det_pol_stride >= row, det_chan_stride >=
  * (4/ndim - 1)*det_pol_stride + row) or plane-major (det_chan_stride >= row, det_pol_stride >= (nchan-1)*det_chan_stride + row).
- * Anything else is refused with DSPSR_AMD_EINVAL before a launch; nothing outside the rows is written. */
+ * Anything else is refused with DSPSR_AMD_EINVAL before a launch; nothing outside the rows is written.
+ *   state: DSPSR_AMD_INTENSITY | DSPSR_AMD_PPQQ (dspsr -d 1, -d 2: Detection::square_law, Detection.C:218-320) ; ndim must be 1:
+ *     det_dev + chan*det_chan_stride + q*det_pol_stride + idat    (q < npol_out: 1 for Intensity, 2 for PPQQ)
+ *   in the same two row orders.  An object of ONE polarisation takes Intensity alone and yields PP, the power of its polarisation.
+ *   Three-pass and two-pass geometries detect inside the inverse pass (the search epilogue of perform_search with a scrunch factor
+ *   of 1); the others write their complex rows to a block owned by the object and run dspsr_amd_detect_square_law on it.  Either
+ *   way the rows are bit for bit dspsr_amd_filterbank_perform(_raw) followed by dspsr_amd_detect_square_law. */
 #define DSPSR_AMD_COHERENCE 0
 #define DSPSR_AMD_STOKES 1
 int dspsr_amd_filterbank_perform_detect(dspsr_amd_filterbank* fb, const float* in_f32_dev, uint64_t in_chan_stride,
@@ -235,8 +241,19 @@ int dspsr_amd_filterbank_perform_detect(dspsr_amd_filterbank* fb, const float* i
  *      DSPSR_AMD_FUSED_NEVER, or what the other modes turn down; and every dsp::Convolution object whose float32 rows run in one
  *      or three tile passes -- complex input, two polarisations, 64 <= freq_res <= 2^21: Detection in their last pass).  Three-pass plans with runs of >= 640 samples per bin
  *      take this path too (fold.hip).
- * DSPSR_AMD_FUSED_ALWAYS forces mode 1 on any three-pass geometry. */
+ * DSPSR_AMD_FUSED_ALWAYS forces mode 1 on any three-pass geometry.
+ *
+ * state DSPSR_AMD_INTENSITY | DSPSR_AMD_PPQQ (dspsr -d 1, -d 2): the profile of `fold` is npol 1 x ndim 1 (Intensity; PP of an
+ * object of one polarisation) or npol 2 x ndim 1 (PPQQ: the rows PP and QQ of a channel); any other pairing of state and shape is
+ * DSPSR_AMD_EINVAL with a message that names both.  The sums are those of perform_detect(state) followed by dspsr_amd_fold_fold:
+ * bit for bit in modes 1 and 0, the run-wise re-association above in mode 2.  dspsr_amd_filterbank_fold_is_fused_state(fb, state)
+ * says how the object folds `state`: for Coherence and Stokes what dspsr_amd_filterbank_fold_is_fused says; for the two square-law
+ * states 1, 2 (k_inv_chan<., 3 | 7, .>: a sample is staged as one or two floats and added to scalar accumulators, so a bound
+ * profile fuses at ANY float-aligned address, span and padding) or 0 -- never 3: four-pass objects and calls that take the
+ * two-pass path (generic 8-bit complex blocks, npass(1) == 2) run Detection and Fold as launches of their own.  An object of
+ * one polarisation fuses like one of two. */
 int dspsr_amd_filterbank_fold_is_fused(const dspsr_amd_filterbank* fb);
+int dspsr_amd_filterbank_fold_is_fused_state(const dspsr_amd_filterbank* fb, int state);
 /* How many transform passes (trips of the part through HBM scratch + 1) a call makes -- the role of the plan choice inside
  * CUDA::FilterbankEngine::setup (FilterbankCUDA.cu:92-116: one forward and one batched backward cuFFT plan).  raw_input != 0:
  * the answer for dspsr_amd_filterbank_perform_raw / _detect / _fold on a generic 8-bit block, else for float32 rows.

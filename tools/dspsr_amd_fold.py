@@ -2,7 +2,10 @@
 """tools/dspsr_amd_fold.py : the path behind the reference's own option spellings (dspsr.C:207-510) -- a thin driver over
 dspsr_amd.dada.fold_file for trying the engine on a DADA file; not a re-implementation of the dspsr application.
 
-  dspsr_amd_fold.py -F 1024:D -D 1000 -b 1024 -c 0.0893 [-x 4096] [-L 10 | -s | -turns N] [-P polyco] [-K] [-d 4] [-r]
+  dspsr_amd_fold.py -F 1024:D -D 1000 -b 1024 -c 0.0893 [-x 4096] [-L 10 | -s | -turns N] [-P polyco] [-K] [-d 1|2|4] [-ndim 1|2|4] [-r]
+                    (-d npol, dspsr.C:389: 1 total intensity, 2 PP and QQ -- files of STATE Intensity / PPQQ, NPOL 1 / 2, NDIM 1 --,
+                    4 the four products, the default; -d 3 reports the reference's refusal.  One-polarisation input with -d 1 or 2
+                    folds as STATE PP.  -ndim N, dspsr's -n ndim (dspsr.C:392): the layout of the four products, which -d spelled here before)
   dspsr_amd_fold.py -F 128 ...   (no `:D`: filterbank, THEN coherent dedispersion per channel -- Filterbank::Config::After; -D 0: none)
   dspsr_amd_fold.py -F 128:B ... (coherent dedispersion of the whole band, THEN the filterbank -- Filterbank::Config::Before)
                     [--dump Detection] [--dump Fold] [-O out_prefix] file.dada
@@ -56,7 +59,11 @@ def parse_args(argv=None):
     ap.add_argument("-s", dest="single", action="store_true", help="single pulses (one turn per sub-integration)")
     ap.add_argument("-turns", dest="turns", type=float, default=0.0, help="turns per sub-integration")
     ap.add_argument("-K", dest="interchan", action="store_true", help="remove the inter-channel dispersion delay")
-    ap.add_argument("-d", dest="ndim", type=int, default=4, choices=[1, 2, 4], help="detected layout (ndim); with -cyclic: output polarisations")
+    # (the attribute keeps the name it had when -d spelled the layout; it holds the reference's npol)
+    ap.add_argument("-d", dest="ndim", type=int, default=4, choices=[1, 2, 3, 4],
+                    help="output polarisations (dspsr -d npol): 1 Intensity, 2 PPQQ, 4 the four products; also with -cyclic and -G")
+    # (dspsr spells it -n; here -n<text> must stay an unrecognised argument: -noskz_too is refused that way)
+    ap.add_argument("-ndim", dest="layout", type=int, default=4, choices=[1, 2, 4], help="ndim of the detected rows when npol=4 (dspsr -n ndim, dspsr.C:392)")
     ap.add_argument("-4", dest="fourth", action="store_true", help="compute fourth-order moments")
     ap.add_argument("-cyclic", dest="cyclic", type=int, default=0, help="form cyclic spectra with N channels per filterbank channel")
     ap.add_argument("-cyclicoversample", dest="cyclic_mover", type=int, default=1, help="use M times as many lags to improve the cyclic channel isolation")
@@ -78,7 +85,10 @@ def parse_args(argv=None):
     ap.add_argument("--dump", action="append", default=[], help="dump the input of this operation (Detection, Fold)")
     ap.add_argument("-O", dest="prefix", default="dspsr_amd", help="output file name prefix")
     ap.add_argument("--cuda", dest="device", type=int, default=0, help="device id (the reference's spelling)")
-    return ap.parse_args(argv)
+    a = ap.parse_args(argv)
+    if a.ndim == 3 and (a.cyclic or a.plfb_nbin):              # nothing changed for -cyclic and -G: 1, 2 or 4
+        ap.error("argument -d: invalid choice: 3 (choose from 1, 2, 4)")
+    return a
 
 
 def unpacker_options(unpack, log=None):
@@ -103,6 +113,15 @@ def unpacker_options(unpack, log=None):
             out["excision_threshold"] = float(m.group(1))
             print("dspsr: Setting two-bit sampling threshold to %g" % out["excision_threshold"], file=log or sys.stderr)
     return out
+
+
+def detection_options(a, input_npol=2):
+    """The Config fields -d and -ndim set.  Plain path: -d is the reference's npol (1 Intensity, 2 PPQQ, 3 its refusal, 4 the four
+    products) and -ndim the layout of the four products (dspsr -n, dspsr.C:392) -- until this spelling -d chose that layout here.  With -cyclic
+    and -G nothing changed: -d is their number of output polarisations and the rows have ndim 1."""
+    if a.cyclic or a.plfb_nbin:
+        return dict(ndim=1, npol=a.ndim if a.plfb_nbin else 4, cyclic_npol=(a.ndim if input_npol == 2 else 1) if a.cyclic else 0)
+    return dict(ndim=a.layout, npol=a.ndim, cyclic_npol=0)
 
 
 def fold_targets(a, nbin, out_rate, mjd_day, mjd_sec):
@@ -143,9 +162,8 @@ def main(argv=None):
     pfold = period if period > 0 else 1.0 / polyco.frequency(info.mjd_day, info.mjd_sec) if polyco else 0.0
     nbin = a.nbin or (pipeline.choose_nbin(pfold, out_rate) if pfold else targets[0].nbin)
     cfg = pipeline.Config(nchan=nchan, dispersion_measure=dm, nbin=nbin, folding_period=period, freq_res=a.nfft,
-                          subint_seconds=a.subint, subint_turns=1.0 if a.single else a.turns, ndim=1 if a.cyclic or a.plfb_nbin else a.ndim,
-                          plfb_nbin=a.plfb_nbin, npol=a.ndim if a.plfb_nbin else 4,
-                          cyclic_nchan=a.cyclic, cyclic_mover=a.cyclic_mover, cyclic_npol=(a.ndim if info.npol == 2 else 1) if a.cyclic else 0,
+                          subint_seconds=a.subint, subint_turns=1.0 if a.single else a.turns, plfb_nbin=a.plfb_nbin,
+                          cyclic_nchan=a.cyclic, cyclic_mover=a.cyclic_mover, **detection_options(a, info.npol),
                           interchan_dedispersion=a.interchan, record_time=a.record, fourth_moment=a.fourth, calibrator=a.pac, zap_rfi=a.zap_rfi,
                           sk_zap=a.skz, sk_m=a.skzm, sk_std_devs=a.skzs, sk_chan_start=a.skz_start, sk_chan_end=a.skz_end, sk_no_fscr=a.skz_no_fscr,
                           sk_no_tscr=a.skz_no_tscr, sk_no_ft=a.skz_no_ft, **unpacker_options(a.unpack),

@@ -135,6 +135,9 @@ SYMBOLS = {
     "dspsr_amd_rescale_transform_fpt": (_i, [_vp, _vp, _u64, _u64, _vp, _u64, _u64, _u64]),
     "dspsr_amd_sigproc_digitize_fpt": (_i, [_vp, _vp, _u64, _u64, _u64, _u32, _u32, _i, _i, _d, _f, _i, _i, _vp]),
     "dspsr_amd_rescale_digitize_fpt": (_i, [_vp, _vp, _u64, _u64, _u64, _i, _f, _i, _i, _vp]),
+    "dspsr_amd_fits_digitizer_create": (_i, [_vp, _u32, _u32, _i, _u32, _u32, _i, _i, _i, _pp]),
+    "dspsr_amd_fits_digitizer_destroy": (None, [_vp]),
+    "dspsr_amd_fits_digitizer_pack": (_i, [_vp, _vp, _u64, _u64, _vp, _vp, _vp]),
     "dspsr_amd_detect_polarimetry": (_i, [_vp, _i, _u32, _vp, _u64, _u64, _vp, _u64, _u64, _u32, _u64]),
     "dspsr_amd_detect_square_law": (_i, [_vp, _i, _vp, _u64, _u64, _vp, _u64, _u64, _u32, _u32, _u64]),
     "dspsr_amd_unpack_fpt": (_i, [_vp, _vp, _f, _u32, _u32, _u32, _u64, _vp, _u64, _u64]),

@@ -739,6 +739,39 @@ class Rescale(_Owned):
         return off.reshape(self.nchan, self.npol), sc.reshape(self.nchan, self.npol)
 
 
+class FITSDigitizer(_Owned):
+    """Mirror of dsp::FITSDigitizer with set_rescale_samples(nsblk) (Kernel/Formats/fits/FITSDigitizer.C): the reference spectrum of
+    each block of nsblk samples (a running mean over nblock blocks), applied to that block, digi_sigma 8, MSB-first packing."""
+
+    _abi = "dspsr_amd_fits_digitizer"
+
+    def __init__(self, ctx: Context, nchan, npol=1, nbit=2, nsblk=2048, nblock=1, constant=False, flip_band=False, swap_band=False):
+        super().__init__(ctx)
+        self.nchan, self.npol, self.nbit, self.nsblk, self.nblock = nchan, npol, nbit, nsblk, nblock
+        self._create(nchan, npol, nbit, nsblk, nblock, int(constant), int(flip_band), int(swap_band))
+        self.block_bytes = nsblk * npol * nchan * nbit // 8
+
+    @property
+    def zero_off(self) -> float:
+        """ZERO_OFF of the PSRFITS SUBINT header, 2^(nbit-1) - 0.5"""
+        return 2.0 ** (self.nbit - 1) - 0.5
+
+    def pack(self, inp, out, dat_scl, dat_offs):
+        """rescale_pack() of one block: inp float32 device rows [nchan][npol][nsblk] (strided views allowed), out device uint8
+        [nsblk * npol * nchan * nbit / 8] in TPF order, dat_scl / dat_offs device float32 [npol * nchan].  No synchronisation."""
+        if tuple(inp.shape) != (self.nchan, self.npol, self.nsblk):
+            raise DspsrAmdError("dspsr_amd.FITSDigitizer.pack: rows %s, one block is [%d][%d][%d]"
+                                % (tuple(inp.shape), self.nchan, self.npol, self.nsblk))
+        for name, t, need in (("out", out, self.block_bytes), ("dat_scl", dat_scl, 4 * self.nchan * self.npol),
+                              ("dat_offs", dat_offs, 4 * self.nchan * self.npol)):
+            if t.numel() * t.element_size() < need:
+                raise DspsrAmdError("dspsr_amd.FITSDigitizer.pack: %s holds %d bytes, %d needed" % (name, t.numel() * t.element_size(), need))
+        ics, ips = _strides3(inp)
+        _check(self.ctx.handle, lib.dspsr_amd_fits_digitizer_pack(self.handle, inp.data_ptr(), ics, ips, out.data_ptr(), dat_scl.data_ptr(),
+                                                                 dat_offs.data_ptr()), "dspsr_amd_fits_digitizer_pack")
+        return out
+
+
 def pscrunch_tfp(ctx: Context, inp, out, nchan, npol=2):
     """dsp::PScrunch on TFP-ordered device data: out[t][c] = (p0 + p1) * float(1/sqrt(2)); out of place."""
     ndat = inp.numel() // (nchan * npol)

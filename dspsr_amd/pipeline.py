@@ -20,7 +20,7 @@ from dataclasses import dataclass
 import numpy as np
 
 from . import _lib
-from .engine import (Context, ConvolutionEngine, CyclicFoldEngine, Dedispersion, DetectionEngine, DspsrAmdError, SpectralKurtosisEngine, FilterbankEngine, FoldEngine, PhaseLockedFilterbankEngine, plfb_check_shape, Rescale, SampleDelay, add_fpt, copy_data_fpt, fourth_moment,
+from .engine import (Context, ConvolutionEngine, CyclicFoldEngine, Dedispersion, DetectionEngine, DspsrAmdError, SpectralKurtosisEngine, FilterbankEngine, FITSDigitizer, FoldEngine, PhaseLockedFilterbankEngine, plfb_check_shape, Rescale, SampleDelay, add_fpt, copy_data_fpt, fourth_moment,
                      dedispersion_sample_delays, detect_raw, eight_bit_scale, fscrunch_fpt, pscrunch_tfp, sigproc_digitize, sigproc_digitize_fpt,
                      tfp_filterbank, tscrunch_fpt, twobit_block_bytes)
 
@@ -2765,3 +2765,265 @@ class LoadToFilDirect:
         if not self._closed:
             self._closed = True
             _close_all(self.rescale, self.sample_delay, self.ctx)
+
+
+# ---- search mode: digifits (Signal/General/digifits.C, LoadToFITS.C) -----------------------------------------------------------------
+
+@dataclass
+class FitsConfig:
+    """The digifits options (digifits.C) with LoadToFITS::Config's defaults (LoadToFITS.C:65-100)."""
+    nchan: int = 0                    # -F nchan  (0: the channels of the file)
+    convolve: bool = False            # -F nchan:D  (Filterbank::Config::During)
+    freq_res: int = 0                 # -x  (with the response: times the minimum transform length, LoadToFITS.C:272)
+    dispersion_measure: float = 0.0   # -D
+    coherent_dedisp: bool = False     # -do_dedisp
+    tsamp: float = 64e-6              # -t  seconds
+    npol: int = 4                     # -p  1 Intensity, 2 PPQQ, 4 Coherence
+    nbit: int = 2                     # -b  1, 2, 4, 8
+    nsblk: int = 2048                 # -nsblk  samples per output block
+    rescale_seconds: float = -1.0     # -I  (<= 0: the spectrum of each block alone)
+    rescale_constant: bool = False    # -c
+    dedisperse: bool = False          # -K  remove the inter-channel dispersion delays, behind TScrunch (LoadToFITS.C:486-498)
+    integration_length: float = 0.0   # -L  (file splitting: refused)
+    parts_per_block: int = 64         # -F: parts (FFT blocks) per call; no -F: the most time samples per call
+    max_parts: int = 32               # parts per launch group
+    fused: bool = True                # detection + time scrunch inside the inverse pass where the geometry allows it
+
+
+def _c_round(x):
+    """round() of <cmath> for the non-negative values of LoadToFITS.C:192,201: halves go away from zero"""
+    return int(math.floor(x + 0.5))
+
+
+def fits_plan(cfg: FitsConfig, info: InputInfo):
+    """LoadToFITS.C:178-204 and :539-551 restated: (tres_factor, tsamp the reference prints, nblock).  With multi-channel input and -F
+    the factor counts the file's per-channel rate against ALL output channels, as the reference does: the time resolution of the
+    output is what the chain delivers (LoadToFITS.out_rate -> TBIN), not this tsamp."""
+    rate = info.rate
+    factor = 0.5 if info.ndim == 1 else 1.0                  # Signal::Nyquist
+    if cfg.nchan > 0:
+        samp_per_fb = cfg.tsamp * rate
+        tres_factor = _c_round(factor * samp_per_fb / cfg.nchan)
+        tsamp = tres_factor / factor * cfg.nchan / rate
+    else:
+        tres_factor = _c_round(rate * cfg.tsamp)
+        tsamp = tres_factor / factor * 1 / rate
+    nblock = 1
+    if not cfg.rescale_constant and cfg.rescale_seconds > 0:
+        tblock = cfg.tsamp * cfg.nsblk
+        nblock = max(1, int(cfg.rescale_seconds / tblock + 0.5))
+    return tres_factor, tsamp, nblock
+
+
+SEARCH_BLOCKS_MAGIC = "DSPSR_AMD_SEARCH_BLOCKS"
+SEARCH_BLOCKS_HDR_SIZE = 4096
+POL_TYPES = {1: "AA+BB", 2: "AABB", 4: "AABBCRCI"}           # PSRFITS POL_TYPE of Intensity, PPQQ, Coherence
+
+
+class LoadToFITS:
+    """digifits' chain, CPU branch (Signal/General/LoadToFITS.C:249-553): [Filterbank -F N[:D]] -> Detection straight to the state -p
+    names -> TScrunch(tres_factor) -> [SampleDelay at the scrunched rate, -K] -> FITSDigitizer over blocks of nsblk samples, every
+    stage on the device.  The front end is the search-mode front end of digifil: LoadToFilCoherent.detect_scrunch with -F,
+    LoadToFilDirect.detect_scrunch on channelised complex voltages without; its scrunched rows land straight in the buffer where the
+    blocks collect.  process_block(raw, npart, first_sample) takes the block its front end takes and returns the blocks it completes,
+    a list of (bytes uint8 [nsblk*npol*nchan*nbit/8], DAT_SCL float32 [npol*nchan], DAT_OFFS float32 [npol*nchan]) device tensors
+    that stay valid until the next call.  Samples short of a block at the end of the data are dropped (InputBuffering)."""
+
+    ctx = front = digitizer = sample_delay = None
+    _closed = False
+
+    def __init__(self, cfg: FitsConfig, info: InputInfo, device: int = 0, stream: int | None = None):
+        delays = self._plan(cfg, info)                       # every refusal comes from here, before a device is touched
+        try:
+            self._open(device, stream, delays)
+        except BaseException:
+            self.close()
+            raise
+
+    def _plan(self, cfg, info):
+        who = "dspsr_amd.LoadToFITS"
+        self.cfg, self.info = cfg, info
+        if getattr(info, "detected", False):
+            raise DspsrAmdError("%s: detected input (the PScrunch branch, LoadToFITS.C:501-514) is not built" % who)
+        refuse_twobit(who, info)
+        if cfg.integration_length:
+            raise DspsrAmdError("%s: -L (splitting the output into files of integration_length seconds) is not built" % who)
+        if cfg.npol not in (1, 2, 4):
+            raise DspsrAmdError("dsp::LoadToFITS::construct invalid polarization specified (npol=%d)" % cfg.npol)
+        if cfg.nbit not in (1, 2, 4, 8):
+            raise DspsrAmdError("dsp::FITSDigitizer::set_nbit nbit=%i not understood" % cfg.nbit)
+        if cfg.nsblk < 1:
+            raise DspsrAmdError("%s: nsblk=%d" % (who, cfg.nsblk))
+        if cfg.nchan == 0 and info.nchan == 1:
+            raise DspsrAmdError("dsp::LoadToFITS::construct must specify filterbank scheme if single channel data")      # :254-258
+        if cfg.nchan == 1 or cfg.nchan < 0:
+            raise DspsrAmdError("%s: -F %d (a filterbank of at least two channels, or none)" % (who, cfg.nchan))
+        response = cfg.coherent_dedisp and cfg.dispersion_measure != 0.0                                               # :260
+        if response and not (cfg.nchan > 1 and cfg.convolve):
+            raise DspsrAmdError("%s: -do_dedisp without -F N:D is not built (dsp::Convolution behind the filterbank or on the file's "
+                                "channels, LoadToFITS.C:329-362)" % who)
+        self.tres_factor, self.tsamp, self.nblock = fits_plan(cfg, info)
+        if self.tres_factor < 1:
+            raise DspsrAmdError("dsp::TScrunch::get_factor scrunch factor not set (tsamp=%g s is below the resolution of the chain)" % cfg.tsamp)
+        common = dict(tscrunch=self.tres_factor, nbit=8, rescale_seconds=0.0, npol=cfg.npol, dedisperse=False,
+                      parts_per_block=cfg.parts_per_block, max_parts=cfg.max_parts, fused=cfg.fused)
+        if cfg.nchan:
+            if response:
+                # -x with the response: Dedispersion::set_times_minimum_nfft (:272), not a transform length
+                freq_res = 0
+                if cfg.freq_res:
+                    freq_res = cfg.freq_res * matched_response(info, cfg.dispersion_measure, 0, cfg.nchan, input_nchan=info.nchan,
+                                                               ndim=info.ndim).minimum_ndat
+                scfg = SearchConfig(nchan=cfg.nchan, dispersion_measure=cfg.dispersion_measure, freq_res=freq_res, **common)
+            else:
+                scfg = SearchConfig(nchan=cfg.nchan, dispersion_measure=0.0, freq_res=cfg.freq_res if cfg.freq_res > 1 else 1, **common)   # :318-323
+            front_cls = LoadToFilCoherent
+            dual = info.ndim == 2
+            swap = dict(swap=dual and info.nchan == 1, nsub_swap=info.nchan if dual and info.nchan > 1 else 0)
+        else:
+            scfg = SearchConfig(**common)
+            front_cls = LoadToFilDirect
+            swap = dict(swap=False, nsub_swap=0)
+        # the front end planned but not opened: its own refusals (heaps and the CASPSR order with no -F, ...) and its geometry;
+        # _open() opens it on this driver's device and stream
+        self.front = front = object.__new__(front_cls)
+        front._plan(scfg, info)
+        self.nchan_out, self.out_rate, self.out_start = front.nchan_out, front.out_rate, front.out_start
+        if self.nchan_out % (8 // cfg.nbit):
+            raise DspsrAmdError("%s: nchan=%d not a multiple of %d samples per byte" % (who, self.nchan_out, 8 // cfg.nbit))
+        if self.nchan_out * cfg.npol > 65535:
+            raise DspsrAmdError("%s: nchan*npol=%d exceeds the grid limit" % (who, self.nchan_out * cfg.npol))
+        delays, self.sd = None, DelayCarry()
+        if cfg.dedisperse:
+            delays = dedispersion_sample_delays(info.centre_frequency, info.bandwidth, cfg.dispersion_measure, self.nchan_out,
+                                                self.out_rate, **swap)
+            self.sd = DelayCarry(delays)
+            self.out_start += self.sd.zero / self.out_rate                                  # SampleDelay.C:159
+        self.block_bytes_out = cfg.nsblk * cfg.npol * self.nchan_out * cfg.nbit // 8
+        self.fill = self.nblocks_out = 0
+        return delays
+
+    def _open(self, device, stream, delays):
+        cfg, front, ncol = self.cfg, self.front, self.nchan_out * self.cfg.npol
+        front._open(device, stream, None)
+        self.ctx = front.ctx
+        nmax = front.scrunched.shape[2]                      # the most scrunched samples one call of the front end delivers
+        self.nmax = nmax
+        front.scrunched = None                               # (its rows are placed call by call, below)
+        self.kbuf = None
+        if delays is not None:
+            self.sd.check_block("LoadToFITS", nmax)
+            self.sample_delay = SampleDelay(self.ctx, delays, cfg.npol)
+            self.kbuf = _device_empty(self.ctx, (self.nchan_out, cfg.npol, self.sd.head + nmax))
+        self.rows = _device_empty(self.ctx, (self.nchan_out, cfg.npol, cfg.nsblk - 1 + nmax + self.sd.head))
+        self.digitizer = FITSDigitizer(self.ctx, self.nchan_out, cfg.npol, cfg.nbit, cfg.nsblk, self.nblock, cfg.rescale_constant,
+                                       flip_band=self.info.bandwidth > 0)
+        maxblk = max(1, self.rows.shape[2] // cfg.nsblk)
+        self.packed = _device_empty(self.ctx, (maxblk, self.block_bytes_out), "uint8")
+        self.dat_scl = _device_empty(self.ctx, (maxblk, ncol))
+        self.dat_offs = _device_empty(self.ctx, (maxblk, ncol))
+
+    def block_bytes(self, npart=None, first_sample=0):
+        if isinstance(self.front, LoadToFilDirect):
+            return self.front.block_bytes(npart)
+        return self.front.block_bytes(npart, first_sample)
+
+    def scrunched_rows(self, raw, npart=None, first_sample=0):
+        """The front end and -K of one call: the new rows of the digitiser's input, appended to the collecting buffer; returns how many."""
+        front, sd = self.front, self.sd
+        direct = isinstance(front, LoadToFilDirect)
+        if self.sample_delay is None:
+            front.scrunched = self.rows[:, :, self.fill:self.fill + self.nmax]
+            scr = front.detect_scrunch(raw, npart) if direct else front.detect_scrunch(raw, npart, first_sample)
+            return scr.shape[2]
+        front.scrunched = sd.new(self.kbuf)                  # behind the head room that holds the tail SampleDelay gave up
+        scr = front.detect_scrunch(raw, npart) if direct else front.detect_scrunch(raw, npart, first_sample)
+        nnew = scr.shape[2]
+        rows = sd.rows(self.kbuf, nnew)
+        nd = self.sample_delay.transform(rows) if rows.shape[2] else 0     # in place, LoadToFITS.C:493-494
+        if nd:
+            copy_data_fpt(self.ctx, self.rows[:, :, self.fill:self.fill + nd], rows[:, :, :nd])
+        sd.keep_tail(self.ctx, self.kbuf, nnew, nd)
+        return nd
+
+    def process_block(self, raw, npart=None, first_sample=0):
+        nsblk = self.cfg.nsblk
+        self.fill += self.scrunched_rows(raw, npart, first_sample)
+        out, k = [], 0
+        while self.fill - k * nsblk >= nsblk:                # every complete run of nsblk samples is one pack
+            self.digitizer.pack(self.rows[:, :, k * nsblk:(k + 1) * nsblk], self.packed[k], self.dat_scl[k], self.dat_offs[k])
+            out.append((self.packed[k], self.dat_scl[k], self.dat_offs[k]))
+            k += 1
+        if k:
+            rest = self.fill - k * nsblk
+            if rest:
+                move_tail_fpt(self.ctx, self.rows, 0, k * nsblk, rest)
+            self.fill = rest
+            self.nblocks_out += k
+        return out
+
+    def header_values(self):
+        """What the SUBINT header of the PSRFITS file takes (FITSOutputFile.C:247-250,428-431), keyed by its names."""
+        cfg, info, bw = self.cfg, self.info, -abs(self.info.bandwidth)
+        return dict(NSBLK=cfg.nsblk, TBIN=1.0 / self.out_rate, NBITS=cfg.nbit, ZERO_OFF=2.0 ** (cfg.nbit - 1) - 0.5, NCHAN=self.nchan_out,
+                    NPOL=cfg.npol, POL_TYPE=POL_TYPES[cfg.npol], OBSFREQ=info.centre_frequency, OBSBW=bw, CHAN_BW=bw / self.nchan_out,
+                    STT_IMJD=info.mjd_day, STT_SECONDS=info.mjd_sec + self.out_start, SRC_NAME=info.source)
+
+    def synchronize(self):
+        self.ctx.synchronize()
+
+    def close(self):
+        if not self._closed:
+            self._closed = True
+            front = self.front
+            _close_all(self.digitizer, self.sample_delay)
+            if front is not None and getattr(front, "ctx", None) is not None:
+                front.close()
+
+
+def write_search_blocks(path, header, blocks):
+    """The hand-off file of a digifits run: a fixed-size ASCII header keyed by the PSRFITS names (LoadToFITS.header_values), then one
+    record per block: DAT_OFFS[npol*nchan] float32, DAT_SCL[npol*nchan] float32, DATA[nsblk*npol*nchan*nbit/8].
+    blocks: (bytes, dat_scl, dat_offs) as process_block returns them, on the host (numpy)."""
+    keys = [("HDR_MAGIC", SEARCH_BLOCKS_MAGIC), ("HDR_VERSION", "1.0"), ("HDR_SIZE", SEARCH_BLOCKS_HDR_SIZE)]
+    keys += [(k, repr(float(v)) if isinstance(v, float) else v) for k, v in header.items()]
+    keys.append(("NROWS", len(blocks)))
+    text = "".join("%-20s %s\n" % (k, v) for k, v in keys)
+    if len(text) >= SEARCH_BLOCKS_HDR_SIZE:
+        raise DspsrAmdError("write_search_blocks: header does not fit %d bytes" % SEARCH_BLOCKS_HDR_SIZE)
+    ncol = int(header["NCHAN"]) * int(header["NPOL"])
+    nbytes = int(header["NSBLK"]) * ncol * int(header["NBITS"]) // 8
+    with open(path, "wb") as f:
+        f.write(text.encode("ascii").ljust(SEARCH_BLOCKS_HDR_SIZE, b"\0"))
+        for data, scl, offs in blocks:
+            data, scl, offs = np.ascontiguousarray(data, np.uint8), np.ascontiguousarray(scl, "<f4"), np.ascontiguousarray(offs, "<f4")
+            if data.size != nbytes or scl.size != ncol or offs.size != ncol:
+                raise DspsrAmdError("write_search_blocks: a block of %d bytes and %d / %d scales; the header says %d and %d"
+                                    % (data.size, scl.size, offs.size, nbytes, ncol))
+            f.write(offs.tobytes())
+            f.write(scl.tobytes())
+            f.write(data.tobytes())
+
+
+def read_search_blocks(path):
+    """Returns (header dict of strings, [(bytes uint8, dat_scl float32, dat_offs float32), ...])."""
+    with open(path, "rb") as f:
+        raw = f.read(SEARCH_BLOCKS_HDR_SIZE)
+        hdr = {}
+        for line in raw.split(b"\0", 1)[0].decode("ascii").splitlines():
+            parts = line.split(None, 1)
+            if len(parts) == 2:
+                hdr[parts[0]] = parts[1].strip()
+        if hdr.get("HDR_MAGIC") != SEARCH_BLOCKS_MAGIC:
+            raise DspsrAmdError("read_search_blocks: %s is not a %s file" % (path, SEARCH_BLOCKS_MAGIC))
+        ncol = int(hdr["NCHAN"]) * int(hdr["NPOL"])
+        nbytes = int(hdr["NSBLK"]) * ncol * int(hdr["NBITS"]) // 8
+        blocks = []
+        for _ in range(int(hdr["NROWS"])):
+            rec = f.read(8 * ncol + nbytes)
+            if len(rec) != 8 * ncol + nbytes:
+                raise DspsrAmdError("read_search_blocks: %s is truncated" % path)
+            offs = np.frombuffer(rec, "<f4", ncol).copy()
+            scl = np.frombuffer(rec, "<f4", ncol, 4 * ncol).copy()
+            blocks.append((np.frombuffer(rec, np.uint8, nbytes, 8 * ncol).copy(), scl, offs))
+    return hdr, blocks

@@ -783,6 +783,25 @@ int dspsr_amd_sigproc_digitize_fpt(dspsr_amd_ctx* ctx, const float* in_dev, uint
 int dspsr_amd_rescale_digitize_fpt(dspsr_amd_rescale* r, const float* in_dev, uint64_t in_chan_stride, uint64_t in_pol_stride,
                                    uint64_t ndat, int nbit, float scale_fac, int flip_band, int swap_band, void* out_dev);
 
+/* ---- PSRFITS search-mode output stage: dsp::FITSDigitizer (Kernel/Formats/fits/FITSDigitizer.C), digifits' back half -------------
+ * One object per output stream.  nbit 1/2/4/8; nsblk = samples per output block (set_rescale_samples); nblock >= 1 = blocks of the
+ * running mean (set_rescale_nblock); constant = keep the first block's spectrum (set_rescale_constant); flip_band = input bandwidth
+ * > 0, swap_band = input->get_swap() (ChannelSort :116-145, the map of dspsr_amd_sigproc_digitize_fpt).
+ * dspsr_amd_fits_digitizer_pack: rescale_pack() of ONE block of exactly nsblk samples, FPT rows [nchan][npol] of floats (strides in
+ *   floats): measure_scale (:178-321) over the block, the spectrum applied to the same block, digi_sigma 8, sub-byte samples most
+ *   significant bits first.  out_bytes_dev: nsblk*npol*nchan*nbit/8 bytes, sample idat*nchan*npol + ipol*nchan + ichan;
+ *   dat_scl_dev / dat_offs_dev: [npol*nchan] floats of get_scales (:675-699), index ipol*nchan + ichan (output channel).
+ *   Three launches on the context's stream, no host synchronisation.
+ * Refused with DSPSR_AMD_EINVAL before any launch: any other nbit; nchan not a multiple of 8/nbit (a byte would straddle two
+ *   polarisations); nsblk 0 or > 2^30; nblock 0; nchan*npol > 65535 (the grid limit of the FPT digitiser); rows shorter than nsblk or
+ *   overlapping; pointers that are null or not float aligned. */
+typedef struct dspsr_amd_fits_digitizer dspsr_amd_fits_digitizer;
+int dspsr_amd_fits_digitizer_create(dspsr_amd_ctx* ctx, uint32_t nchan, uint32_t npol, int nbit, uint32_t nsblk, uint32_t nblock,
+                                    int constant, int flip_band, int swap_band, dspsr_amd_fits_digitizer** out);
+void dspsr_amd_fits_digitizer_destroy(dspsr_amd_fits_digitizer* d);
+int dspsr_amd_fits_digitizer_pack(dspsr_amd_fits_digitizer* d, const float* in_dev, uint64_t in_chan_stride, uint64_t in_pol_stride,
+                                  void* out_bytes_dev, float* dat_scl_dev, float* dat_offs_dev);
+
 /* ---- host-side preparation (stays on the host in the reference as well) --------------------- */
 typedef struct {
   double centre_frequency;   /* MHz */

@@ -404,7 +404,7 @@ def search_blocks_file(path, cfg, device=0, stream=None, log=None):
     Returns (header_values, [(bytes, DAT_SCL, DAT_OFFS) on the host, ...]): what pipeline.write_search_blocks takes.  `log`: where the
     reference's `requested tsamp / actual tsamp` line goes."""
     import torch
-    from .pipeline import LoadToFITS, LoadToFilDirect
+    from .pipeline import LoadToFITS
     f = DadaFile(path)
     lt = LoadToFITS(cfg, f.info, device=device, stream=stream)
     if log is not None:
@@ -412,20 +412,11 @@ def search_blocks_file(path, cfg, device=0, stream=None, log=None):
               file=log)
     dev, blocks = "cuda:%d" % device, []
 
-    def run(raw, *args):
-        done = lt.process_block(torch.from_numpy(np.array(raw)).to(dev), *args)
-        lt.synchronize()                                     # the block is freed on return, and the results are read on torch's stream
-        blocks.extend(tuple(t.cpu().numpy().copy() for t in blk) for blk in done)
-
     try:
-        if isinstance(lt.front, LoadToFilDirect):
-            bps, step = f.bytes_per_sample, cfg.parts_per_block
-            for s0 in range(0, f.ndat, step):
-                ndat = min(step, f.ndat - s0)
-                run(f._map[s0 * bps:(s0 + ndat) * bps], ndat)
-        else:
-            for blk in f.blocks(lt.front):
-                run(*blk)
+        for raw, *args in lt.file_calls(f):
+            done = lt.process_block(torch.from_numpy(np.array(raw)).to(dev), *args)
+            lt.synchronize()                                 # the block is freed on return, and the results are read on torch's stream
+            blocks.extend(tuple(t.cpu().numpy().copy() for t in blk) for blk in done)
         return lt.header_values(), blocks
     finally:
         lt.close()

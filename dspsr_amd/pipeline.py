@@ -1270,7 +1270,7 @@ class DelayCarry:
 
     def __init__(self, delays=None, head=0):
         self.zero = self.carried = self.short = 0
-        self.head = head
+        self.head, self.delays = head, delays
         if delays is not None:
             d = np.asarray(delays, np.int64)
             self.zero = int(d.max())
@@ -1300,6 +1300,16 @@ class DelayCarry:
         if carry and off + nout != self.head - carry:
             move_tail_fpt(ctx, buf, self.head - carry, off + nout, carry, ndim)
         self.carried = carry
+
+    def delayed(self, ctx, sample_delay, buf, ndat, use):
+        """The -K step of a block whose `ndat` new samples lie behind the head room of `buf`: SampleDelay in place over the carried
+        tail and the new samples, `use(rows)` on the samples it delivers (they are read before the tail moves over them), the
+        unshifted tail kept for the next block.  Returns what `use` returns."""
+        rows = self.rows(buf, ndat)
+        nout = sample_delay.transform(rows) if rows.shape[2] else 0
+        result = use(rows[:, :, :nout])
+        self.keep_tail(ctx, buf, ndat, nout)
+        return result
 
 
 def _carry_view(name):
@@ -2370,51 +2380,18 @@ def write_sigproc_header(f, *, source_name="unknown", rawdatafile="unknown", mac
     send_string("HEADER_END")
 
 
-def _sigproc_header_values(drv, nchan, tsamp, start_seconds, nifs):
+def sigproc_header_values(info, nbit, nchan, tsamp, start_seconds, nifs):
     """fch1/foff/tsamp/tstart as SigProcObservation::unload derives them from the digitizer's output observation
     (bandwidth forced negative, SigProcDigitizer.C:83-85; channel 0 centred half a channel inside the band edge)."""
-    info, bw = drv.info, -abs(drv.info.bandwidth)
+    bw = -abs(info.bandwidth)
     fch1 = info.centre_frequency - 0.5 * bw + 0.5 * bw / nchan
-    nbits = 32 if drv.cfg.nbit == -32 else drv.cfg.nbit
-    return dict(fch1=fch1, foff=bw / nchan, nchans=nchan, nbits=nbits, tsamp=tsamp,
+    return dict(fch1=fch1, foff=bw / nchan, nchans=nchan, nbits=_nbits(nbit), tsamp=tsamp,
                 tstart_mjd=info.mjd_day + (info.mjd_sec + start_seconds) / 86400.0, nifs=nifs)
 
 
-def _digitize_fpt(drv, scr):
-    """[Rescale] -> SigProcDigitizer of the scrunched FPT rows of one block (LoadToFil.C:306-362): the packed bytes
-    [time][pol][chan] of its output samples."""
-    cfg, nout = drv.cfg, scr.shape[2]
-    packed = drv.packed[:nout * drv.bytes_per_sample]
-    flip = drv.info.bandwidth > 0
-    if nout:
-        if drv.rescale is not None and cfg.nbit != -32:
-            drv.rescale.digitize_fpt(scr, packed, cfg.nbit, cfg.scale_fac, flip_band=flip)        # Rescale + digitiser, one pass
-        else:
-            if drv.rescale is not None:
-                drv.rescale.transform_fpt(scr)                                                     # in place, LoadToFil.C:312-313
-            sigproc_digitize_fpt(drv.ctx, scr, packed, cfg.nbit, use_digi_scales=drv.rescale is not None,
-                                 input_scale=1.0 if drv.rescale is not None else drv.input_scale, scale_fac=cfg.scale_fac,
-                                 flip_band=flip)
-    drv.ndat_out += nout
-    return packed
-
-
-def _delay_scrunch(drv, det, nd):
-    """[SampleDelay, in place (LoadToFil.C:240-241)] -> [FScrunch] -> TScrunch behind the detection of a search driver: `det`, the
-    `nd` new samples behind the head room of drv.detected; returns the scrunched rows [nchan_out][npol][nout] (a view)."""
-    cfg, nnew = drv.cfg, nd
-    if drv.sample_delay is not None:
-        det = drv.sd.rows(drv.detected, nnew)
-        nd = drv.sample_delay.transform(det) if det.shape[2] else 0
-        det = det[:, :, :nd]
-    nout = 0
-    if nd:
-        if cfg.fscrunch:
-            det = fscrunch_fpt(drv.ctx, det, drv.fscr[:, :, :nd], cfg.fscrunch)
-        nout, drv.carry_count = tscrunch_fpt(drv.ctx, det, drv.scrunched, drv.ts, drv.carry, drv.carry_count)
-    if drv.sample_delay is not None:
-        drv.sd.keep_tail(drv.ctx, drv.detected, nnew, nd)
-    return drv.scrunched[:, :, :nout]
+def _nbits(nbit):
+    """bits per output sample of -b (-32: floats)"""
+    return 32 if nbit == -32 else nbit
 
 
 def _rescale_interval(cfg, out_rate):
@@ -2427,17 +2404,327 @@ def _rescale_interval(cfg, out_rate):
     return interval
 
 
-class LoadToFil:
+def _of(part, name):
+    """A driver's view of a value that lives on one of its parts"""
+    return property(lambda self: getattr(getattr(self, part), name))
+
+
+# ---- the parts of the search drivers: one front end per input, one output stage per format ---------------------------------------
+# A front end turns a call's 8-bit block into scrunched rows [nchan_out][npol][nout]: it plans on the host when it is made (every
+# refusal, no device), opens on the context its owner gives it, and writes its rows into a buffer of its own or, where the owner
+# hands a destination in, there.  An output stage turns those rows into what a format takes.  A driver is one of each on one shell.
+
+FRONT_OPTIONS = ("nchan", "tscrunch", "fscrunch", "npol", "dedisperse", "dispersion_measure", "freq_res", "parts_per_block", "max_parts", "fused")
+
+
+class SearchFront:
+    """What the two front ends share: the plan behind their geometry (state, scrunch factors, the -K delays and their head room,
+    whether the one-pass form applies), the buffers, and the chain behind detection: [SampleDelay, in place (LoadToFil.C:240-241)]
+    -> [FScrunch] -> TScrunch.  `cfg` holds the options that concern a front end (FRONT_OPTIONS) and no others."""
+
+    ctx = fb = sample_delay = scrunched = detected = fscr = None
+    tsamp = property(lambda self: 1.0 / self.out_rate)
+
+    def __init__(self, info, **options):
+        from types import SimpleNamespace
+        self.info, self.cfg = info, SimpleNamespace(**options)
+        cfg = self.cfg
+        # the subclass: its refusals; the channels, rate, start and scale of the detected rows; the samples of a full call, where
+        # the host knows them
+        self.nchan, self.rate, self.out_start, scale, self.block = self._geometry()
+        if cfg.fscrunch and self.nchan % cfg.fscrunch:
+            raise DspsrAmdError("%s: nchan=%d is not a multiple of fscrunch=%d" % (self.who, self.nchan, cfg.fscrunch))
+        self.ts = ts = max(1, cfg.tscrunch)
+        self.nchan_out = self.nchan // cfg.fscrunch if cfg.fscrunch else self.nchan
+        self.out_rate = self.rate / ts
+        # FScrunch / TScrunch multiply the scale by their factors (TimeSeries::rescale, TScrunch.C:126, FScrunch.C:103); without
+        # Rescale the digitiser divides by it (SigProcDigitizer.C:158)
+        self.input_scale = scale * ts * (cfg.fscrunch or 1)
+        self.state = {1: _lib.INTENSITY, 2: _lib.PPQQ, 4: _lib.COHERENCE}[cfg.npol]
+        self.scale8 = eight_bit_scale()
+        # -K: dsp::SampleDelay sits in front of Detection (LoadToFil.C:236-247).  Detection acts sample by sample, so delaying the
+        # detected rows gives the reference's numbers; the last total_delay samples of a block are re-presented in front of the
+        # next one (InputBuffering, SampleDelay.C:117,146): they live in the head room in front of `detected`.
+        self.sd = DelayCarry()
+        if cfg.dedisperse:
+            self.sd = DelayCarry(self.channel_delays(cfg.dispersion_measure, self.nchan, self.rate))
+            if self.block is not None:
+                self.sd.check_block(self.name, self.block)
+            self.out_start += self.sd.zero / self.rate                                   # SampleDelay.C:159
+        # FScrunch sits between Detection and TScrunch and SampleDelay in front of Detection: the one-pass form holds neither, so
+        # with -f or -K detection runs at tscrunch 1 into `detected` and the operations follow one after the other
+        self.fused = self._one_pass() and not cfg.fscrunch and not cfg.dedisperse
+        self.carry_count = 0
+
+    def open(self, ctx, own_rows=True):
+        """The engine and the buffers on `ctx`.  own_rows False: every call brings the destination of its scrunched rows."""
+        cfg, shape = self.cfg, (self.nchan_out, self.cfg.npol)
+        self.ctx = ctx
+        self._open_engine()
+        if cfg.dedisperse:
+            self.sample_delay = SampleDelay(ctx, self.sd.delays, cfg.npol)
+            self.sd.check_block(self.name, self.block)       # (-F: the block is known with the engine's nkeep)
+        nd = self.sd.head + self.block
+        self.nmax = max(1, (self.ts - 1 + nd) // self.ts)    # the most scrunched samples one call delivers
+        if own_rows:
+            self.scrunched = _device_empty(ctx, shape + (self.nmax,))
+        self.carry = _device_empty(ctx, shape, zero=True)
+        if not self.fused:
+            self.detected = _device_empty(ctx, (self.nchan, cfg.npol, nd))
+            if cfg.fscrunch:
+                self.fscr = _device_empty(ctx, shape + (nd,))
+
+    def detect_scrunch(self, raw, n=None, first_sample=0, out=None):
+        """Detection -> [SampleDelay] -> [FScrunch] -> TScrunch of one call of `n` parts (-F) or time samples (no -F): the scrunched
+        rows [nchan_out][npol][nout], a view of `out` (default: the front end's own buffer).  first_sample: a block of MeerKAT heaps
+        begins at that sample of its first heap (LoadToFold.process_block)."""
+        n = self._count(n)
+        need = self.block_bytes(n, first_sample)
+        if raw.numel() < need:
+            raise DspsrAmdError("%s.process_block: block holds %d bytes, %d needed" % (self.who, raw.numel(), need))
+        out = self.scrunched if out is None else out
+        if self.fused:
+            nout, self.carry_count = self._detect(raw, n, first_sample, out, self.ts)
+            return out[:, :, :nout]
+        nd, head = n * self.samples_per_count, self.sd.head
+        det = self.detected[:, :, head:head + nd]
+        self._detect(raw, n, first_sample, det, 1)
+        if self.sample_delay is None:
+            return out[:, :, :self._scrunch(det, out)]
+        return out[:, :, :self.sd.delayed(self.ctx, self.sample_delay, self.detected, nd, lambda rows: self._scrunch(rows, out))]
+
+    def _scrunch(self, det, out):
+        """[FScrunch] -> TScrunch of the detected rows into `out`: how many samples that completes"""
+        nd, nout = det.shape[2], 0
+        if nd:
+            if self.cfg.fscrunch:
+                det = fscrunch_fpt(self.ctx, det, self.fscr[:, :, :nd], self.cfg.fscrunch)
+            nout, self.carry_count = tscrunch_fpt(self.ctx, det, out, self.ts, self.carry, self.carry_count)
+        return nout
+
+    def close(self):
+        _close_all(self.sample_delay, self.fb)
+
+
+class ConvolvingFront(SearchFront):
+    """`-F N[:D] [-x M]`, MeerKAT heaps included (LoadToFil.C:176-222,250-304): dsp::Filterbank with the Dedispersion response ->
+    Detection::square_law -> [FScrunch] -> TScrunch.  One launch group runs filterbank, detection and time scrunch
+    (FilterbankEngine.perform_search): the detected rows never exist at the filterbank's output rate.  A call takes the 8-bit block
+    of LoadToFold: n * nsamp_step + nsamp_overlap samples, the overlap re-presented by the caller; no n (or 0): parts_per_block."""
+
+    name, who = "LoadToFilCoherent", "dspsr_amd.LoadToFilCoherent"           # (the driver its refusals have always named)
+    samples_per_count = property(lambda self: self.nkeep)
+
+    def _geometry(self):
+        cfg, info, who = self.cfg, self.info, self.who
+        refuse_twobit(who, info)
+        if cfg.npol not in (1, 2, 4):
+            raise DspsrAmdError("%s: npol=%d (Intensity 1 / PPQQ 2 / Coherence 4 are built; NthPower 3 is not)" % (who, cfg.npol))
+        if cfg.npol >= 2 and info.npol != 2:
+            raise DspsrAmdError("%s: PPQQ / Coherence need two input polarisations" % who)
+        if cfg.nchan % info.nchan:
+            raise DspsrAmdError("dsp::Filterbank::make_preparations output nchan=%d not a multiple of input nchan=%d" % (cfg.nchan, info.nchan))
+        if cfg.dispersion_measure == 0.0 and not cfg.freq_res and cfg.npol <= 2:
+            raise DspsrAmdError("%s: -F N:D with a dispersion measure, -F N -x M, or -d 4 (with none of them "
+                                "digifil takes the TFPFilterbank: dspsr_amd.LoadToFil)" % who)
+        if cfg.dispersion_measure != 0.0:
+            r = matched_response(info, cfg.dispersion_measure, cfg.freq_res, cfg.nchan, input_nchan=info.nchan, ndim=info.ndim)   # LoadToFil.C:190-191
+        else:
+            # -F N -x M without :D (LoadToFil.C:199-216): the convolving filterbank with no response -- nothing is discarded
+            # (Filterbank.C:139-155: freq_res as set, nfilt 0)
+            # -F N -d 4 with neither (LoadToFil.C:205-207: `npol > 2` takes the Filterbank too): its default freq_res = 1, the
+            # non-convolving filterbank (Filterbank.C:614-623)
+            from types import SimpleNamespace
+            r = SimpleNamespace(ndat=cfg.freq_res or 1, impulse_pos=0, impulse_neg=0, kernel=None)
+        self.response = r
+        # Filterbank.C:124-128 leaves scale = n_fft * freq_res on its output
+        self.fb_rate, start, scale = filterbank_output(info, r, cfg.nchan // info.nchan)
+        return cfg.nchan, self.fb_rate, start, scale, None
+
+    def _one_pass(self):
+        """the fused launch group holds the two square-law states, not the four Coherence products (those: perform_detect with ndim 1)"""
+        return self.cfg.fused and self.cfg.npol != 4
+
+    def channel_delays(self, dispersion_measure, nchan, rate):
+        """the -K delays of `nchan` channels of this filterbank's output at `rate` (Observation.C:80-87; Filterbank.C:358-364)"""
+        info, dual = self.info, self.info.ndim == 2
+        return dedispersion_sample_delays(info.centre_frequency, info.bandwidth, dispersion_measure, nchan, rate,
+                                          swap=dual and info.nchan == 1, nsub_swap=info.nchan if dual and info.nchan > 1 else 0)
+
+    def _open_engine(self):
+        cfg, info, r = self.cfg, self.info, self.response
+        _open_convolving_front(self, r, cfg.nchan // info.nchan, info.nchan, r.kernel, max_parts=cfg.max_parts)
+        self.block = cfg.parts_per_block * self.nkeep
+        if not self.fused and cfg.npol != 4:
+            self.det_carry = _device_empty(self.ctx, (cfg.nchan, cfg.npol), zero=True)
+
+    def _count(self, npart):
+        return npart or self.cfg.parts_per_block
+
+    def block_bytes(self, npart=None, first_sample=0):
+        nsamp = (npart or self.cfg.parts_per_block) * self.nsamp_step + self.nsamp_overlap
+        return raw_block_bytes(self.layout, nsamp, self.info.nchan, self.info.npol, self.info.ndim, first_sample)
+
+    def _detect(self, raw, npart, first_sample, out, ts):
+        if _lib.is_heaps(self.layout):
+            self.layout = _lib.raw_at(self.layout & 0xff, first_sample)
+        block = dict(raw=raw, layout=self.layout, scale=self.scale8)
+        if self.fused:
+            return self.fb.perform_search(out, self.carry, self.carry_count, npart, ts, self.state, **block)
+        if self.cfg.npol == 4:
+            return self.fb.perform_detect(out, npart, self.state, 1, **block)
+        return self.fb.perform_search(out, self.det_carry, 0, npart, 1, self.state, **block)
+
+    def file_calls(self, f):
+        """DadaFile `f` cut into this front end's calls: parts with their overlap (DadaFile.blocks)"""
+        return f.blocks(self)
+
+
+class ChannelisedFront(SearchFront):
+    """No -F, on an already channelised complex 8-bit file (LoadToFil.C:233-304): Detection (Intensity / PPQQ / Coherence with
+    ndim 1) -> [FScrunch] -> [TScrunch].  The block is detected and time-scrunched in ONE pass (dspsr_amd.detect_raw): the float
+    voltages are never written.  The channels are those of the file: nchan, freq_res, max_parts and fused are IGNORED;
+    parts_per_block is the largest number of time samples one call may bring.  A call takes n time samples in DADA order
+    [n][nchan][npol][2] int8: any n up to parts_per_block, 0 included; no n: parts_per_block."""
+
+    name, who = "LoadToFilDirect", "dspsr_amd.LoadToFilDirect"
+    samples_per_count = 1
+    tsamp = property(lambda self: self.ts / self.info.rate)                    # (not always the double that 1 / out_rate is)
+
+    def _geometry(self):
+        cfg, info, who = self.cfg, self.info, self.who
+        refuse_twobit(who, info)
+        if info.ndim != 2:
+            raise DspsrAmdError("%s: NDIM=%d; complex (NDIM 2) channelised voltages only" % (who, info.ndim))
+        if getattr(info, "nbit", 8) != 8:
+            raise DspsrAmdError("%s: NBIT=%d; this path reads 8-bit samples" % (who, info.nbit))
+        if info.machine == "CASPSR":
+            raise DspsrAmdError("%s: the CASPSR byte order is not built on this path (generic DADA order only)" % who)
+        refuse_heaps(who, info, "dspsr_amd.unpack_heaps_fpt gives the float rows, and -F N:D (dspsr_amd.LoadToFilCoherent) reads the heaps")
+        if cfg.npol not in (1, 2, 4):
+            raise DspsrAmdError("%s: npol=%d (Intensity 1 / PPQQ 2 / Coherence 4 are built; NthPower 3 is not)" % (who, cfg.npol))
+        if info.npol not in (1, 2):
+            raise DspsrAmdError("%s: NPOL=%d; one or two input polarisations" % (who, info.npol))
+        if cfg.npol >= 2 and info.npol != 2:
+            raise DspsrAmdError("dsp::Detection::checks invalid npol=%d for %s formation" % (info.npol, "PPQQ" if cfg.npol == 2 else "Coherence"))
+        if info.nchan < 1 or cfg.parts_per_block < 1:
+            raise DspsrAmdError("%s: nchan=%d, parts_per_block=%d" % (who, info.nchan, cfg.parts_per_block))
+        return info.nchan, info.rate, info.start_seconds, 1.0, cfg.parts_per_block       # (no filterbank factor in the scale)
+
+    def _one_pass(self):
+        return True
+
+    def channel_delays(self, dispersion_measure, nchan, rate):
+        """the -K delays: the input comes from a file, not from a filterbank -- no swapped halves (Observation.C:420-451)"""
+        return dedispersion_sample_delays(self.info.centre_frequency, self.info.bandwidth, dispersion_measure, nchan, rate, swap=False, nsub_swap=0)
+
+    def _open_engine(self):
+        pass
+
+    def _count(self, ndat):
+        ndat = self.cfg.parts_per_block if ndat is None else ndat
+        if ndat > self.cfg.parts_per_block:
+            raise DspsrAmdError("%s.process_block: ndat=%d exceeds parts_per_block=%d" % (self.who, ndat, self.cfg.parts_per_block))
+        return ndat
+
+    def block_bytes(self, ndat=None, first_sample=0):
+        ndat = self.cfg.parts_per_block if ndat is None else ndat
+        return raw_block_bytes(_lib.RAW_GENERIC, ndat, self.info.nchan, self.info.npol, 2, first_sample)
+
+    def _detect(self, raw, ndat, first_sample, out, ts):
+        carry, count = (self.carry, self.carry_count) if self.fused else (None, None)
+        return detect_raw(self.ctx, raw, out, carry, count, self.info.nchan, self.info.npol, ts, self.state, self.scale8, ndat=ndat)
+
+    def file_calls(self, f):
+        """DadaFile `f` cut into this front end's calls: runs of parts_per_block time samples, the last one shorter"""
+        bps, step = f.bytes_per_sample, self.cfg.parts_per_block
+        for s0 in range(0, f.ndat, step):
+            ndat = min(step, f.ndat - s0)
+            yield f._map[s0 * bps:(s0 + ndat) * bps], ndat
+
+
+class SigprocOutput:
+    """[Rescale] -> SigProcDigitizer of scrunched FPT rows (LoadToFil.C:306-362) and the SIGPROC header that goes with the bytes"""
+
+    ctx = rescale = None
+
+    def __init__(self, cfg, info, nchan, out_rate):
+        self.cfg, self.info, self.nchan = cfg, info, nchan
+        self.rescale_interval = _rescale_interval(cfg, out_rate)
+        self.bytes_per_sample = nchan * cfg.npol * _nbits(cfg.nbit) // 8
+        self.ndat_out = 0
+
+    def open(self, ctx, nmax):
+        """for calls of at most `nmax` samples"""
+        cfg = self.cfg
+        self.ctx = ctx
+        if self.rescale_interval:
+            self.rescale = Rescale(ctx, self.nchan, cfg.npol, self.rescale_interval, cfg.rescale_constant)
+        self.packed = _device_empty(ctx, nmax * self.bytes_per_sample, "uint8")
+
+    def digitize(self, scr, input_scale):
+        """the packed bytes [time][pol][chan] of the rows `scr` [nchan][npol][nout], which carry the scale `input_scale`"""
+        cfg, nout = self.cfg, scr.shape[2]
+        packed = self.packed[:nout * self.bytes_per_sample]
+        flip = self.info.bandwidth > 0
+        if nout:
+            if self.rescale is not None and cfg.nbit != -32:
+                self.rescale.digitize_fpt(scr, packed, cfg.nbit, cfg.scale_fac, flip_band=flip)        # Rescale + digitiser, one pass
+            else:
+                if self.rescale is not None:
+                    self.rescale.transform_fpt(scr)                                                     # in place, LoadToFil.C:312-313
+                sigproc_digitize_fpt(self.ctx, scr, packed, cfg.nbit, use_digi_scales=self.rescale is not None,
+                                     input_scale=1.0 if self.rescale is not None else input_scale, scale_fac=cfg.scale_fac,
+                                     flip_band=flip)
+        self.ndat_out += nout
+        return packed
+
+    def header_values(self, tsamp, start_seconds):
+        return sigproc_header_values(self.info, self.cfg.nbit, self.nchan, tsamp, start_seconds, self.cfg.npol)
+
+    def close(self):
+        _close_all(self.rescale)
+
+
+class _SearchDriver:
+    """The shell of the search drivers: the host plan first (every refusal comes from there, before a device is touched), then the
+    device under try/close; close() releases the parts and then the context, once, also after a construction that stopped half-way.
+    device None: the host plan alone."""
+
+    ctx = None
+    _closed = False
+
+    def __init__(self, cfg, info, device: int | None = 0, stream: int | None = None):
+        self.cfg, self.info = cfg, info
+        self._plan()
+        if device is None:
+            return
+        try:
+            self.ctx = Context(device, stream)
+            self._open()
+        except BaseException:
+            self.close()
+            raise
+
+    def synchronize(self):
+        self.ctx.synchronize()
+
+    def close(self):
+        if not self._closed:
+            self._closed = True
+            _close_all(*self._parts(), self.ctx)
+
+
+class LoadToFil(_SearchDriver):
     """digifil's chain for 8-bit real dual-polarisation input and one output polarisation, every stage on the device
     (LoadToFil.C:196-362): TFPFilterbank (PPQQ) + TScrunch [one kernel] -> Rescale (per pol and channel, in place)
     -> PScrunch -> SigProcDigitizer.  process_block returns the packed block (device uint8, [time][chan] n-bit)."""
 
     fused_output = True          # Rescale + PScrunch + digitiser as one pass (False: the three operations one after the other)
-    ctx = rescale = None
-    _closed = False
+    rescale = None
 
-    def __init__(self, cfg: SearchConfig, info: InputInfo, device: int = 0, stream: int | None = None):
-        self.cfg, self.info = cfg, info
+    def _plan(self):
+        cfg, info = self.cfg, self.info
         refuse_twobit("dspsr_amd.LoadToFil", info)
         refuse_heaps("dspsr_amd.LoadToFil", info, "channelised complex voltages take -F N:D (dspsr_amd.LoadToFilCoherent)")
         if info.npol != 2 or info.ndim != 1 or info.nchan != 1:
@@ -2448,21 +2735,20 @@ class LoadToFil:
         self.scale8 = eight_bit_scale()
         self.layout = _lib.RAW_CASPSR if info.machine == "CASPSR" else _lib.RAW_GENERIC
         self.out_rate = info.rate / (2.0 * cfg.nchan) / cfg.tscrunch           # TFPFilterbank + TScrunch
-        nbits = 32 if cfg.nbit == -32 else cfg.nbit
-        self.bytes_per_sample = cfg.nchan * nbits // 8
+        self.bytes_per_sample = cfg.nchan * _nbits(cfg.nbit) // 8
         self.ndat_out = 0
-        interval = _rescale_interval(cfg, self.out_rate)
-        try:
-            self.ctx = Context(device, stream)
-            nout = cfg.parts_per_block // cfg.tscrunch
-            self.detected = _device_empty(self.ctx, (nout, cfg.nchan, 2))      # PPQQ, TFP order
-            self.intensity = _device_empty(self.ctx, (nout, cfg.nchan, 1))
-            if interval:
-                self.rescale = Rescale(self.ctx, cfg.nchan, 2, interval, cfg.rescale_constant)
-            self.packed = _device_empty(self.ctx, nout * self.bytes_per_sample, "uint8")
-        except BaseException:
-            self.close()
-            raise
+        self.rescale_interval = _rescale_interval(cfg, self.out_rate)
+
+    def _open(self):
+        cfg, nout = self.cfg, self.cfg.parts_per_block // self.cfg.tscrunch
+        self.detected = _device_empty(self.ctx, (nout, cfg.nchan, 2))      # PPQQ, TFP order
+        self.intensity = _device_empty(self.ctx, (nout, cfg.nchan, 1))
+        if self.rescale_interval:
+            self.rescale = Rescale(self.ctx, cfg.nchan, 2, self.rescale_interval, cfg.rescale_constant)
+        self.packed = _device_empty(self.ctx, nout * self.bytes_per_sample, "uint8")
+
+    def _parts(self):
+        return (self.rescale,)
 
     def block_bytes(self, npart=None):
         return (npart or self.cfg.parts_per_block) * 2 * self.cfg.nchan * 2
@@ -2496,275 +2782,52 @@ class LoadToFil:
         return packed
 
     def header_values(self):
-        return _sigproc_header_values(self, self.cfg.nchan, 1.0 / self.out_rate, self.info.start_seconds, 1)
-
-    def synchronize(self):
-        self.ctx.synchronize()
-
-    def close(self):
-        if not self._closed:
-            self._closed = True
-            _close_all(self.rescale, self.ctx)
+        return sigproc_header_values(self.info, self.cfg.nbit, self.cfg.nchan, 1.0 / self.out_rate, self.info.start_seconds, 1)
 
 
-class LoadToFilCoherent:
-    """digifil with the convolving filterbank, `digifil -F N:D [-x M] [-f F] -t T -b nbit` (Signal/General/LoadToFil.C:176-222,250-362):
-    dsp::Filterbank with the Dedispersion response -> Detection::square_law (Intensity / PPQQ: no PScrunch behind it, :281) ->
-    [FScrunch] -> TScrunch -> Rescale -> SigProcDigitizer, FPT order throughout, every stage on the device.  One launch group runs
-    filterbank, detection and time scrunch (FilterbankEngine.perform_search): the detected rows never exist at the filterbank's
-    output rate.  process_block(raw) takes the 8-bit block of LoadToFold (npart * nsamp_step + nsamp_overlap samples, the overlap
-    re-presented by the caller) and returns the packed bytes [time][pol][chan] of the output samples completed by it."""
+class _FrontToFil(_SearchDriver):
+    """digifil in FPT order, every stage on the device: a front end (`front_end`) and the SIGPROC output stage.  process_block takes
+    what the front end's detect_scrunch takes and returns the packed bytes [time][pol][chan] of the output samples it completes."""
 
-    sd_head, sd_carried = _carry_view("head"), _carry_view("carried")
-    ctx = fb = rescale = sample_delay = None
-    _closed = False
+    front = out = None
 
-    def __init__(self, cfg: SearchConfig, info: InputInfo, device: int = 0, stream: int | None = None):
-        delays = self._plan(cfg, info)                       # every refusal that needs no device comes from here
-        try:
-            self._open(device, stream, delays)
-        except BaseException:
-            self.close()
-            raise
+    def _plan(self):
+        cfg = self.cfg
+        self.front = self.front_end(self.info, **{k: getattr(cfg, k) for k in FRONT_OPTIONS})
+        self.out = SigprocOutput(cfg, self.info, self.front.nchan_out, self.front.out_rate)
 
-    def _plan(self, cfg, info):
-        """The host side of the constructor: checks and geometry.  Returns the -K delays per channel (None without -K)."""
-        self.cfg, self.info = cfg, info
-        refuse_twobit("dspsr_amd.LoadToFilCoherent", info)
-        if cfg.npol not in (1, 2, 4):
-            raise DspsrAmdError("dspsr_amd.LoadToFilCoherent: npol=%d (Intensity 1 / PPQQ 2 / Coherence 4 are built; NthPower 3 is not)" % cfg.npol)
-        if cfg.npol >= 2 and info.npol != 2:
-            raise DspsrAmdError("dspsr_amd.LoadToFilCoherent: PPQQ / Coherence need two input polarisations")
-        if cfg.nchan % info.nchan:
-            raise DspsrAmdError("dsp::Filterbank::make_preparations output nchan=%d not a multiple of input nchan=%d" % (cfg.nchan, info.nchan))
-        if cfg.dispersion_measure == 0.0 and not cfg.freq_res and cfg.npol <= 2:
-            raise DspsrAmdError("dspsr_amd.LoadToFilCoherent: -F N:D with a dispersion measure, -F N -x M, or -d 4 (with none of them "
-                                "digifil takes the TFPFilterbank: dspsr_amd.LoadToFil)")
-        if cfg.dispersion_measure != 0.0:
-            r = matched_response(info, cfg.dispersion_measure, cfg.freq_res, cfg.nchan, input_nchan=info.nchan, ndim=info.ndim)   # LoadToFil.C:190-191
-        else:
-            # -F N -x M without :D (LoadToFil.C:199-216): the convolving filterbank with no response -- nothing is discarded
-            # (Filterbank.C:139-155: freq_res as set, nfilt 0)
-            # -F N -d 4 with neither (LoadToFil.C:205-207: `npol > 2` takes the Filterbank too): its default freq_res = 1, the
-            # non-convolving filterbank (Filterbank.C:614-623)
-            from types import SimpleNamespace
-            r = SimpleNamespace(ndat=cfg.freq_res or 1, impulse_pos=0, impulse_neg=0, kernel=None)
-        self.response = r
-        # Filterbank.C:124-128 leaves scale = n_fft * freq_res on its output; FScrunch / TScrunch multiply it by their factors
-        # (TimeSeries::rescale, TScrunch.C:126, FScrunch.C:103); without Rescale the digitiser divides by it (SigProcDigitizer.C:158)
-        self.fb_rate, self.out_start, scale = filterbank_output(info, r, cfg.nchan // info.nchan)
-        self.ts = ts = max(1, cfg.tscrunch)
-        self.out_rate = self.fb_rate / ts
-        self.input_scale = scale * ts * (cfg.fscrunch or 1)
-        self.state = {1: _lib.INTENSITY, 2: _lib.PPQQ, 4: _lib.COHERENCE}[cfg.npol]
-        self.nchan_out = cfg.nchan // cfg.fscrunch if cfg.fscrunch else cfg.nchan
-        if cfg.fscrunch and cfg.nchan % cfg.fscrunch:
-            raise DspsrAmdError("dspsr_amd.LoadToFilCoherent: nchan=%d is not a multiple of fscrunch=%d" % (cfg.nchan, cfg.fscrunch))
-        self.rescale_interval = _rescale_interval(cfg, self.out_rate)
-        # -K: dsp::SampleDelay sits between the filterbank and Detection (LoadToFil.C:236-247).  Detection acts sample by sample,
-        # so delaying the detected rows gives the reference's numbers; the last total_delay samples of a block are re-presented in
-        # front of the next one (InputBuffering, SampleDelay.C:117,146): they live in the head room in front of `detected`.
-        delays, self.sd = None, DelayCarry()
-        if cfg.dedisperse:
-            dual = info.ndim == 2                              # Observation.C:80-87; Filterbank.C:358-364
-            delays = dedispersion_sample_delays(info.centre_frequency, info.bandwidth, cfg.dispersion_measure, cfg.nchan,
-                                                self.fb_rate, swap=dual and info.nchan == 1,
-                                                nsub_swap=info.nchan if dual and info.nchan > 1 else 0)
-            self.sd = DelayCarry(delays)
-            self.out_start += self.sd.zero / self.fb_rate                               # SampleDelay.C:159
-        # FScrunch sits between Detection and TScrunch (LoadToFil.C:286-304) and SampleDelay in front of Detection: the fused launch
-        # group holds neither, nor the four Coherence products, so with -f, -K or -d 4 the operations run one after the other
-        # (perform_search at tscrunch 1 = filterbank + detection; Coherence: perform_detect with ndim 1)
-        self.fused = cfg.fused and not cfg.fscrunch and not cfg.dedisperse and cfg.npol != 4
-        nbits = 32 if cfg.nbit == -32 else cfg.nbit
-        self.bytes_per_sample = self.nchan_out * cfg.npol * nbits // 8
-        self.carry_count = self.ndat_out = 0
-        return delays
+    def _open(self):
+        self.front.open(self.ctx)
+        self.out.open(self.ctx, self.front.nmax)
 
-    def _open(self, device, stream, delays):
-        cfg, info, r, ts = self.cfg, self.info, self.response, self.ts
-        self.ctx = Context(device, stream)
-        _open_convolving_front(self, r, cfg.nchan // info.nchan, info.nchan, r.kernel, max_parts=cfg.max_parts)
-        block = cfg.parts_per_block * self.nkeep
-        if delays is not None:
-            self.sample_delay = SampleDelay(self.ctx, delays, cfg.npol)
-            self.sd.check_block("LoadToFilCoherent", block)       # (the block is known with the engine's nkeep)
-        nmax = max(1, (ts - 1 + self.sd.head + block) // ts)
-        self.scrunched = _device_empty(self.ctx, (self.nchan_out, cfg.npol, nmax))
-        self.carry = _device_empty(self.ctx, (self.nchan_out, cfg.npol), zero=True)
-        self.detected = None
-        if not self.fused:
-            nd = self.sd.head + block
-            self.detected = _device_empty(self.ctx, (cfg.nchan, cfg.npol, nd))
-            self.det_carry = _device_empty(self.ctx, (cfg.nchan, cfg.npol), zero=True)
-            self.fscr = _device_empty(self.ctx, (self.nchan_out, cfg.npol, nd)) if cfg.fscrunch else None
-        if self.rescale_interval:
-            self.rescale = Rescale(self.ctx, self.nchan_out, cfg.npol, self.rescale_interval, cfg.rescale_constant)
-        self.packed = _device_empty(self.ctx, nmax * self.bytes_per_sample, "uint8")
+    def _parts(self):
+        return self.out, self.front
 
-    def block_bytes(self, npart=None, first_sample=0):
-        npart = npart or self.cfg.parts_per_block
-        nsamp = npart * self.nsamp_step + self.nsamp_overlap
-        return raw_block_bytes(self.layout, nsamp, self.info.nchan, self.info.npol, self.info.ndim, first_sample)
-
-    def detect_scrunch(self, raw, npart=None, first_sample=0):
-        """Filterbank -> Detection -> [FScrunch] -> TScrunch of one block: the scrunched rows [nchan_out][npol][nout] (a view).
-        first_sample: a block of MeerKAT heaps begins at that sample of its first heap (LoadToFold.process_block)."""
-        cfg, ts = self.cfg, self.ts
-        npart = npart or cfg.parts_per_block
-        need = self.block_bytes(npart, first_sample)
-        if raw.numel() < need:
-            raise DspsrAmdError("dspsr_amd.LoadToFilCoherent.process_block: block holds %d bytes, %d needed" % (raw.numel(), need))
-        if _lib.is_heaps(self.layout):
-            self.layout = _lib.raw_at(self.layout & 0xff, first_sample)
-        if self.fused:
-            nout, self.carry_count = self.fb.perform_search(self.scrunched, self.carry, self.carry_count, npart, ts, self.state, raw=raw,
-                                                            layout=self.layout, scale=self.scale8)
-            return self.scrunched[:, :, :nout]
-        nd, head = npart * self.nkeep, self.sd.head
-        det = self.detected[:, :, head:head + nd]
-        if cfg.npol == 4:
-            self.fb.perform_detect(det, npart, self.state, 1, raw=raw, layout=self.layout, scale=self.scale8)
-        else:
-            self.fb.perform_search(det, self.det_carry, 0, npart, 1, self.state, raw=raw, layout=self.layout, scale=self.scale8)
-        return _delay_scrunch(self, det, nd)
-
-    def process_block(self, raw, npart=None, first_sample=0):
-        return _digitize_fpt(self, self.detect_scrunch(raw, npart, first_sample))
+    def process_block(self, raw, n=None, first_sample=0):
+        return self.out.digitize(self.front.detect_scrunch(raw, n, first_sample), self.front.input_scale)
 
     def header_values(self):
-        return _sigproc_header_values(self, self.nchan_out, 1.0 / self.out_rate, self.out_start, self.cfg.npol)
-
-    def synchronize(self):
-        self.ctx.synchronize()
-
-    def close(self):
-        if not self._closed:
-            self._closed = True
-            _close_all(self.rescale, self.sample_delay, self.fb, self.ctx)
+        return self.out.header_values(self.front.tsamp, self.front.out_start)
 
 
-class LoadToFilDirect:
+for _name in ("response", "fb", "nkeep", "nsamp_step", "nsamp_overlap", "layout", "scale8", "fb_rate", "fused", "ts", "nchan_out", "out_rate",
+              "out_start", "input_scale", "sd", "sample_delay", "carry_count", "block_bytes", "detect_scrunch", "file_calls"):
+    setattr(_FrontToFil, _name, _of("front", _name))
+for _name in ("bytes_per_sample", "ndat_out", "rescale", "rescale_interval"):
+    setattr(_FrontToFil, _name, _of("out", _name))
+_FrontToFil.sd_head, _FrontToFil.sd_carried = _carry_view("head"), _carry_view("carried")
+
+
+class LoadToFilCoherent(_FrontToFil):
+    """digifil with the convolving filterbank, `digifil -F N:D [-x M] [-f F] [-K] -t T -b nbit` (Signal/General/LoadToFil.C:176-222,
+    250-362): ConvolvingFront -> [Rescale] -> SigProcDigitizer.  process_block(raw, npart, first_sample)."""
+    front_end = ConvolvingFront
+
+
+class LoadToFilDirect(_FrontToFil):
     """digifil on an already channelised voltage file with NO -F, `digifil file.dada [-K] [-d npol] [-f F] [-t T] [-I s] -b nbit`
-    (Signal/General/LoadToFil.C:233-362): [SampleDelay, -K] -> Detection (Intensity / PPQQ / Coherence with ndim 1) -> [FScrunch] ->
-    [TScrunch] -> [Rescale] -> SigProcDigitizer, FPT order throughout, every stage on the device.  The 8-bit block is detected and
-    time-scrunched in ONE pass (dspsr_amd.detect_raw): the float voltages are never written.  With -f or -K the pass runs at tscrunch 1
-    into a detected block and SampleDelay, FScrunch and TScrunch follow as operations of their own; -K delays the DETECTED rows
-    (sample-by-sample detection commutes with an integer delay), the unshifted tail kept in front of the next block as
-    LoadToFilCoherent does.
-    The channels are those of the file: SearchConfig.nchan (-F) is IGNORED, as are freq_res, max_parts and fused;
-    cfg.parts_per_block is the largest number of time samples one process_block call may bring.
-    process_block(raw, ndat) takes the block of ndat time samples in DADA order [ndat][nchan][npol][2] int8 (any ndat up to
-    parts_per_block, 0 included) and returns the packed bytes [time][pol][chan] of the output samples it completes."""
-
-    sd_head, sd_carried = _carry_view("head"), _carry_view("carried")
-    ctx = rescale = sample_delay = None
-    _closed = False
-
-    def __init__(self, cfg: SearchConfig, info: InputInfo, device: int = 0, stream: int | None = None):
-        delays = self._plan(cfg, info)                       # every refusal comes from here, before a device is touched
-        try:
-            self._open(device, stream, delays)
-        except BaseException:
-            self.close()
-            raise
-
-    def _open(self, device, stream, delays):
-        cfg, info, ts, head, nmax_in = self.cfg, self.info, self.ts, self.sd.head, self.cfg.parts_per_block
-        self.ctx = Context(device, stream)
-        if delays is not None:
-            self.sample_delay = SampleDelay(self.ctx, delays, cfg.npol)
-        nmax = max(1, (ts - 1 + head + nmax_in) // ts)
-        self.scrunched = _device_empty(self.ctx, (self.nchan_out, cfg.npol, nmax))
-        self.carry = _device_empty(self.ctx, (self.nchan_out, cfg.npol), zero=True)
-        self.detected = self.fscr = None
-        if not self.fused:
-            nd = head + nmax_in
-            self.detected = _device_empty(self.ctx, (info.nchan, cfg.npol, nd))
-            self.fscr = _device_empty(self.ctx, (self.nchan_out, cfg.npol, nd)) if cfg.fscrunch else None
-        if self.rescale_interval:
-            self.rescale = Rescale(self.ctx, self.nchan_out, cfg.npol, self.rescale_interval, cfg.rescale_constant)
-        self.packed = _device_empty(self.ctx, nmax * self.bytes_per_sample, "uint8")
-
-    def _plan(self, cfg, info):
-        """The host side of the constructor: checks and geometry.  Returns the -K delays per channel (None without -K)."""
-        self.cfg, self.info = cfg, info
-        refuse_twobit("dspsr_amd.LoadToFilDirect", info)
-        if info.ndim != 2:
-            raise DspsrAmdError("dspsr_amd.LoadToFilDirect: NDIM=%d; complex (NDIM 2) channelised voltages only" % info.ndim)
-        if getattr(info, "nbit", 8) != 8:
-            raise DspsrAmdError("dspsr_amd.LoadToFilDirect: NBIT=%d; this path reads 8-bit samples" % info.nbit)
-        if info.machine == "CASPSR":
-            raise DspsrAmdError("dspsr_amd.LoadToFilDirect: the CASPSR byte order is not built on this path (generic DADA order only)")
-        refuse_heaps("dspsr_amd.LoadToFilDirect", info, "dspsr_amd.unpack_heaps_fpt gives the float rows, and -F N:D "
-                     "(dspsr_amd.LoadToFilCoherent) reads the heaps")
-        if cfg.npol not in (1, 2, 4):
-            raise DspsrAmdError("dspsr_amd.LoadToFilDirect: npol=%d (Intensity 1 / PPQQ 2 / Coherence 4 are built; NthPower 3 is not)" % cfg.npol)
-        if info.npol not in (1, 2):
-            raise DspsrAmdError("dspsr_amd.LoadToFilDirect: NPOL=%d; one or two input polarisations" % info.npol)
-        if cfg.npol >= 2 and info.npol != 2:
-            raise DspsrAmdError("dsp::Detection::checks invalid npol=%d for %s formation" % (info.npol, "PPQQ" if cfg.npol == 2 else "Coherence"))
-        if info.nchan < 1 or cfg.parts_per_block < 1:
-            raise DspsrAmdError("dspsr_amd.LoadToFilDirect: nchan=%d, parts_per_block=%d" % (info.nchan, cfg.parts_per_block))
-        if cfg.fscrunch and info.nchan % cfg.fscrunch:
-            raise DspsrAmdError("dspsr_amd.LoadToFilDirect: nchan=%d is not a multiple of fscrunch=%d" % (info.nchan, cfg.fscrunch))
-        self.ts = ts = max(1, cfg.tscrunch)
-        self.nchan_out = info.nchan // cfg.fscrunch if cfg.fscrunch else info.nchan
-        self.out_rate = info.rate / ts
-        self.out_start = info.start_seconds
-        self.scale8 = eight_bit_scale()
-        self.state = {1: _lib.INTENSITY, 2: _lib.PPQQ, 4: _lib.COHERENCE}[cfg.npol]
-        delays, self.sd = None, DelayCarry()
-        if cfg.dedisperse:
-            # the input comes from a file, not from a filterbank: no swapped halves (Observation.C:420-451)
-            delays = dedispersion_sample_delays(info.centre_frequency, info.bandwidth, cfg.dispersion_measure, info.nchan, info.rate,
-                                                swap=False, nsub_swap=0)
-            self.sd = DelayCarry(delays)
-            self.sd.check_block("LoadToFilDirect", cfg.parts_per_block)
-            self.out_start += self.sd.zero / info.rate                                   # SampleDelay.C:159
-        self.rescale_interval = _rescale_interval(cfg, self.out_rate)
-        # FScrunch sits between Detection and TScrunch, SampleDelay in front of Detection: the one-pass form holds neither
-        self.fused = not cfg.fscrunch and not cfg.dedisperse
-        nbits = 32 if cfg.nbit == -32 else cfg.nbit
-        self.bytes_per_sample = self.nchan_out * cfg.npol * nbits // 8
-        # no filterbank factor here: FScrunch / TScrunch multiply the scale by their factors (TScrunch.C:126, FScrunch.C:103)
-        self.input_scale = float(ts * (cfg.fscrunch or 1))
-        self.carry_count = self.ndat_out = 0
-        return delays
-
-    def block_bytes(self, ndat=None):
-        ndat = self.cfg.parts_per_block if ndat is None else ndat
-        return ndat * self.info.nchan * self.info.npol * 2
-
-    def detect_scrunch(self, raw, ndat=None):
-        """Detection -> [SampleDelay] -> [FScrunch] -> TScrunch of one block: the scrunched rows [nchan_out][npol][nout] (a view)."""
-        cfg, info = self.cfg, self.info
-        ndat = cfg.parts_per_block if ndat is None else ndat
-        if ndat > cfg.parts_per_block:
-            raise DspsrAmdError("dspsr_amd.LoadToFilDirect.process_block: ndat=%d exceeds parts_per_block=%d" % (ndat, cfg.parts_per_block))
-        if raw.numel() < self.block_bytes(ndat):
-            raise DspsrAmdError("dspsr_amd.LoadToFilDirect.process_block: block holds %d bytes, %d needed" % (raw.numel(), self.block_bytes(ndat)))
-        if self.fused:
-            nout, self.carry_count = detect_raw(self.ctx, raw, self.scrunched, self.carry, self.carry_count, info.nchan, info.npol, self.ts,
-                                                self.state, self.scale8, ndat=ndat)
-            return self.scrunched[:, :, :nout]
-        det = self.detected[:, :, self.sd.head:self.sd.head + ndat]
-        detect_raw(self.ctx, raw, det, None, None, info.nchan, info.npol, 1, self.state, self.scale8, ndat=ndat)
-        return _delay_scrunch(self, det, ndat)
-
-    def process_block(self, raw, ndat=None):
-        return _digitize_fpt(self, self.detect_scrunch(raw, ndat))
-
-    def header_values(self):
-        return _sigproc_header_values(self, self.nchan_out, self.ts / self.info.rate, self.out_start, self.cfg.npol)
-
-    def synchronize(self):
-        self.ctx.synchronize()
-
-    def close(self):
-        if not self._closed:
-            self._closed = True
-            _close_all(self.rescale, self.sample_delay, self.ctx)
+    (Signal/General/LoadToFil.C:233-362): ChannelisedFront -> [Rescale] -> SigProcDigitizer.  process_block(raw, ndat)."""
+    front_end = ChannelisedFront
 
 
 # ---- search mode: digifits (Signal/General/digifits.C, LoadToFITS.C) -----------------------------------------------------------------
@@ -2820,29 +2883,93 @@ SEARCH_BLOCKS_HDR_SIZE = 4096
 POL_TYPES = {1: "AA+BB", 2: "AABB", 4: "AABBCRCI"}           # PSRFITS POL_TYPE of Intensity, PPQQ, Coherence
 
 
-class LoadToFITS:
+class FitsOutput:
+    """The PSRFITS output stage (LoadToFITS.C:486-553): [SampleDelay at the scrunched rate, -K] -> the rows collect until nsblk of
+    them are there -> FITSDigitizer, block by block.  The front end writes a call's rows where destination() says: straight behind
+    the rows that wait for a block, or with -K behind the head room that holds the tail SampleDelay gave up."""
+
+    ctx = digitizer = sample_delay = kbuf = None
+
+    def __init__(self, cfg, info, front, nblock):
+        who = "dspsr_amd.LoadToFITS"
+        self.cfg, self.info, self.nblock = cfg, info, nblock
+        self.nchan, self.out_start = front.nchan_out, front.out_start
+        if self.nchan % (8 // cfg.nbit):
+            raise DspsrAmdError("%s: nchan=%d not a multiple of %d samples per byte" % (who, self.nchan, 8 // cfg.nbit))
+        if self.nchan * cfg.npol > 65535:
+            raise DspsrAmdError("%s: nchan*npol=%d exceeds the grid limit" % (who, self.nchan * cfg.npol))
+        self.sd = DelayCarry()
+        if cfg.dedisperse:
+            self.sd = DelayCarry(front.channel_delays(cfg.dispersion_measure, self.nchan, front.out_rate))
+            self.out_start += self.sd.zero / front.out_rate                                 # SampleDelay.C:159
+        self.block_bytes = cfg.nsblk * cfg.npol * self.nchan * cfg.nbit // 8
+        self.fill = self.nblocks_out = 0
+
+    def open(self, ctx, nmax):
+        """for calls of at most `nmax` scrunched samples"""
+        cfg, ncol = self.cfg, self.nchan * self.cfg.npol
+        self.ctx, self.nmax = ctx, nmax
+        if cfg.dedisperse:
+            self.sd.check_block("LoadToFITS", nmax)
+            self.sample_delay = SampleDelay(ctx, self.sd.delays, cfg.npol)
+            self.kbuf = _device_empty(ctx, (self.nchan, cfg.npol, self.sd.head + nmax))
+        self.rows = _device_empty(ctx, (self.nchan, cfg.npol, cfg.nsblk - 1 + nmax + self.sd.head))
+        self.digitizer = FITSDigitizer(ctx, self.nchan, cfg.npol, cfg.nbit, cfg.nsblk, self.nblock, cfg.rescale_constant,
+                                       flip_band=self.info.bandwidth > 0)
+        maxblk = max(1, self.rows.shape[2] // cfg.nsblk)
+        self.packed = _device_empty(ctx, (maxblk, self.block_bytes), "uint8")
+        self.dat_scl = _device_empty(ctx, (maxblk, ncol))
+        self.dat_offs = _device_empty(ctx, (maxblk, ncol))
+
+    def destination(self):
+        """where the front end writes the scrunched rows of the next call"""
+        if self.sample_delay is not None:
+            return self.sd.new(self.kbuf)
+        return self.rows[:, :, self.fill:self.fill + self.nmax]
+
+    def _place(self, rows):
+        """the delayed rows of a call, behind the rows that wait"""
+        nd = rows.shape[2]
+        if nd:
+            copy_data_fpt(self.ctx, self.rows[:, :, self.fill:self.fill + nd], rows)
+        return nd
+
+    def blocks(self, nnew):
+        """`nnew` rows have arrived at destination(): the blocks they complete, [(bytes, DAT_SCL, DAT_OFFS), ...]"""
+        nsblk = self.cfg.nsblk
+        if self.sample_delay is not None:                    # in place, LoadToFITS.C:493-494
+            nnew = self.sd.delayed(self.ctx, self.sample_delay, self.kbuf, nnew, self._place)
+        self.fill += nnew
+        out, k = [], 0
+        while self.fill - k * nsblk >= nsblk:                # every complete run of nsblk samples is one pack
+            self.digitizer.pack(self.rows[:, :, k * nsblk:(k + 1) * nsblk], self.packed[k], self.dat_scl[k], self.dat_offs[k])
+            out.append((self.packed[k], self.dat_scl[k], self.dat_offs[k]))
+            k += 1
+        if k:
+            rest = self.fill - k * nsblk
+            if rest:
+                move_tail_fpt(self.ctx, self.rows, 0, k * nsblk, rest)
+            self.fill = rest
+            self.nblocks_out += k
+        return out
+
+    def close(self):
+        _close_all(self.digitizer, self.sample_delay)
+
+
+class LoadToFITS(_SearchDriver):
     """digifits' chain, CPU branch (Signal/General/LoadToFITS.C:249-553): [Filterbank -F N[:D]] -> Detection straight to the state -p
     names -> TScrunch(tres_factor) -> [SampleDelay at the scrunched rate, -K] -> FITSDigitizer over blocks of nsblk samples, every
-    stage on the device.  The front end is the search-mode front end of digifil: LoadToFilCoherent.detect_scrunch with -F,
-    LoadToFilDirect.detect_scrunch on channelised complex voltages without; its scrunched rows land straight in the buffer where the
-    blocks collect.  process_block(raw, npart, first_sample) takes the block its front end takes and returns the blocks it completes,
-    a list of (bytes uint8 [nsblk*npol*nchan*nbit/8], DAT_SCL float32 [npol*nchan], DAT_OFFS float32 [npol*nchan]) device tensors
-    that stay valid until the next call.  Samples short of a block at the end of the data are dropped (InputBuffering)."""
+    stage on the device: the front end of digifil's drivers (ConvolvingFront with -F, ChannelisedFront on channelised complex
+    voltages without) and FitsOutput, in whose collecting buffer the front end's rows land.  process_block(raw, n, first_sample)
+    takes the block its front end takes and returns the blocks it completes, a list of (bytes uint8 [nsblk*npol*nchan*nbit/8],
+    DAT_SCL float32 [npol*nchan], DAT_OFFS float32 [npol*nchan]) device tensors that stay valid until the next call.  Samples
+    short of a block at the end of the data are dropped (InputBuffering)."""
 
-    ctx = front = digitizer = sample_delay = None
-    _closed = False
+    front = out = None
 
-    def __init__(self, cfg: FitsConfig, info: InputInfo, device: int = 0, stream: int | None = None):
-        delays = self._plan(cfg, info)                       # every refusal comes from here, before a device is touched
-        try:
-            self._open(device, stream, delays)
-        except BaseException:
-            self.close()
-            raise
-
-    def _plan(self, cfg, info):
-        who = "dspsr_amd.LoadToFITS"
-        self.cfg, self.info = cfg, info
+    def _plan(self):
+        who, cfg, info = "dspsr_amd.LoadToFITS", self.cfg, self.info
         if getattr(info, "detected", False):
             raise DspsrAmdError("%s: detected input (the PScrunch branch, LoadToFITS.C:501-514) is not built" % who)
         refuse_twobit(who, info)
@@ -2865,102 +2992,28 @@ class LoadToFITS:
         self.tres_factor, self.tsamp, self.nblock = fits_plan(cfg, info)
         if self.tres_factor < 1:
             raise DspsrAmdError("dsp::TScrunch::get_factor scrunch factor not set (tsamp=%g s is below the resolution of the chain)" % cfg.tsamp)
-        common = dict(tscrunch=self.tres_factor, nbit=8, rescale_seconds=0.0, npol=cfg.npol, dedisperse=False,
-                      parts_per_block=cfg.parts_per_block, max_parts=cfg.max_parts, fused=cfg.fused)
+        # the front end: TScrunch by tres_factor, neither -f nor -K (this chain delays the SCRUNCHED rows: FitsOutput)
+        front_end, dm, freq_res = ChannelisedFront, 0.0, 0
         if cfg.nchan:
+            front_end, freq_res = ConvolvingFront, cfg.freq_res if cfg.freq_res > 1 else 1                              # :318-323
             if response:
                 # -x with the response: Dedispersion::set_times_minimum_nfft (:272), not a transform length
-                freq_res = 0
+                dm, freq_res = cfg.dispersion_measure, 0
                 if cfg.freq_res:
-                    freq_res = cfg.freq_res * matched_response(info, cfg.dispersion_measure, 0, cfg.nchan, input_nchan=info.nchan,
-                                                               ndim=info.ndim).minimum_ndat
-                scfg = SearchConfig(nchan=cfg.nchan, dispersion_measure=cfg.dispersion_measure, freq_res=freq_res, **common)
-            else:
-                scfg = SearchConfig(nchan=cfg.nchan, dispersion_measure=0.0, freq_res=cfg.freq_res if cfg.freq_res > 1 else 1, **common)   # :318-323
-            front_cls = LoadToFilCoherent
-            dual = info.ndim == 2
-            swap = dict(swap=dual and info.nchan == 1, nsub_swap=info.nchan if dual and info.nchan > 1 else 0)
-        else:
-            scfg = SearchConfig(**common)
-            front_cls = LoadToFilDirect
-            swap = dict(swap=False, nsub_swap=0)
-        # the front end planned but not opened: its own refusals (heaps and the CASPSR order with no -F, ...) and its geometry;
-        # _open() opens it on this driver's device and stream
-        self.front = front = object.__new__(front_cls)
-        front._plan(scfg, info)
-        self.nchan_out, self.out_rate, self.out_start = front.nchan_out, front.out_rate, front.out_start
-        if self.nchan_out % (8 // cfg.nbit):
-            raise DspsrAmdError("%s: nchan=%d not a multiple of %d samples per byte" % (who, self.nchan_out, 8 // cfg.nbit))
-        if self.nchan_out * cfg.npol > 65535:
-            raise DspsrAmdError("%s: nchan*npol=%d exceeds the grid limit" % (who, self.nchan_out * cfg.npol))
-        delays, self.sd = None, DelayCarry()
-        if cfg.dedisperse:
-            delays = dedispersion_sample_delays(info.centre_frequency, info.bandwidth, cfg.dispersion_measure, self.nchan_out,
-                                                self.out_rate, **swap)
-            self.sd = DelayCarry(delays)
-            self.out_start += self.sd.zero / self.out_rate                                  # SampleDelay.C:159
-        self.block_bytes_out = cfg.nsblk * cfg.npol * self.nchan_out * cfg.nbit // 8
-        self.fill = self.nblocks_out = 0
-        return delays
+                    freq_res = cfg.freq_res * matched_response(info, dm, 0, cfg.nchan, input_nchan=info.nchan, ndim=info.ndim).minimum_ndat
+        self.front = front_end(info, nchan=cfg.nchan, dispersion_measure=dm, freq_res=freq_res, tscrunch=self.tres_factor, fscrunch=0,
+                               npol=cfg.npol, dedisperse=False, parts_per_block=cfg.parts_per_block, max_parts=cfg.max_parts, fused=cfg.fused)
+        self.out = FitsOutput(cfg, info, self.front, self.nblock)
 
-    def _open(self, device, stream, delays):
-        cfg, front, ncol = self.cfg, self.front, self.nchan_out * self.cfg.npol
-        front._open(device, stream, None)
-        self.ctx = front.ctx
-        nmax = front.scrunched.shape[2]                      # the most scrunched samples one call of the front end delivers
-        self.nmax = nmax
-        front.scrunched = None                               # (its rows are placed call by call, below)
-        self.kbuf = None
-        if delays is not None:
-            self.sd.check_block("LoadToFITS", nmax)
-            self.sample_delay = SampleDelay(self.ctx, delays, cfg.npol)
-            self.kbuf = _device_empty(self.ctx, (self.nchan_out, cfg.npol, self.sd.head + nmax))
-        self.rows = _device_empty(self.ctx, (self.nchan_out, cfg.npol, cfg.nsblk - 1 + nmax + self.sd.head))
-        self.digitizer = FITSDigitizer(self.ctx, self.nchan_out, cfg.npol, cfg.nbit, cfg.nsblk, self.nblock, cfg.rescale_constant,
-                                       flip_band=self.info.bandwidth > 0)
-        maxblk = max(1, self.rows.shape[2] // cfg.nsblk)
-        self.packed = _device_empty(self.ctx, (maxblk, self.block_bytes_out), "uint8")
-        self.dat_scl = _device_empty(self.ctx, (maxblk, ncol))
-        self.dat_offs = _device_empty(self.ctx, (maxblk, ncol))
+    def _open(self):
+        self.front.open(self.ctx, own_rows=False)
+        self.out.open(self.ctx, self.front.nmax)
 
-    def block_bytes(self, npart=None, first_sample=0):
-        if isinstance(self.front, LoadToFilDirect):
-            return self.front.block_bytes(npart)
-        return self.front.block_bytes(npart, first_sample)
+    def _parts(self):
+        return self.out, self.front
 
-    def scrunched_rows(self, raw, npart=None, first_sample=0):
-        """The front end and -K of one call: the new rows of the digitiser's input, appended to the collecting buffer; returns how many."""
-        front, sd = self.front, self.sd
-        direct = isinstance(front, LoadToFilDirect)
-        if self.sample_delay is None:
-            front.scrunched = self.rows[:, :, self.fill:self.fill + self.nmax]
-            scr = front.detect_scrunch(raw, npart) if direct else front.detect_scrunch(raw, npart, first_sample)
-            return scr.shape[2]
-        front.scrunched = sd.new(self.kbuf)                  # behind the head room that holds the tail SampleDelay gave up
-        scr = front.detect_scrunch(raw, npart) if direct else front.detect_scrunch(raw, npart, first_sample)
-        nnew = scr.shape[2]
-        rows = sd.rows(self.kbuf, nnew)
-        nd = self.sample_delay.transform(rows) if rows.shape[2] else 0     # in place, LoadToFITS.C:493-494
-        if nd:
-            copy_data_fpt(self.ctx, self.rows[:, :, self.fill:self.fill + nd], rows[:, :, :nd])
-        sd.keep_tail(self.ctx, self.kbuf, nnew, nd)
-        return nd
-
-    def process_block(self, raw, npart=None, first_sample=0):
-        nsblk = self.cfg.nsblk
-        self.fill += self.scrunched_rows(raw, npart, first_sample)
-        out, k = [], 0
-        while self.fill - k * nsblk >= nsblk:                # every complete run of nsblk samples is one pack
-            self.digitizer.pack(self.rows[:, :, k * nsblk:(k + 1) * nsblk], self.packed[k], self.dat_scl[k], self.dat_offs[k])
-            out.append((self.packed[k], self.dat_scl[k], self.dat_offs[k]))
-            k += 1
-        if k:
-            rest = self.fill - k * nsblk
-            if rest:
-                move_tail_fpt(self.ctx, self.rows, 0, k * nsblk, rest)
-            self.fill = rest
-            self.nblocks_out += k
-        return out
+    def process_block(self, raw, n=None, first_sample=0):
+        return self.out.blocks(self.front.detect_scrunch(raw, n, first_sample, out=self.out.destination()).shape[2])
 
     def header_values(self):
         """What the SUBINT header of the PSRFITS file takes (FITSOutputFile.C:247-250,428-431), keyed by its names."""
@@ -2969,16 +3022,12 @@ class LoadToFITS:
                     NPOL=cfg.npol, POL_TYPE=POL_TYPES[cfg.npol], OBSFREQ=info.centre_frequency, OBSBW=bw, CHAN_BW=bw / self.nchan_out,
                     STT_IMJD=info.mjd_day, STT_SECONDS=info.mjd_sec + self.out_start, SRC_NAME=info.source)
 
-    def synchronize(self):
-        self.ctx.synchronize()
 
-    def close(self):
-        if not self._closed:
-            self._closed = True
-            front = self.front
-            _close_all(self.digitizer, self.sample_delay)
-            if front is not None and getattr(front, "ctx", None) is not None:
-                front.close()
+for _name in ("nchan_out", "out_rate", "block_bytes", "file_calls"):
+    setattr(LoadToFITS, _name, _of("front", _name))
+for _name in ("out_start", "sd", "sample_delay", "fill", "nblocks_out"):
+    setattr(LoadToFITS, _name, _of("out", _name))
+LoadToFITS.block_bytes_out = _of("out", "block_bytes")
 
 
 def write_search_blocks(path, header, blocks):

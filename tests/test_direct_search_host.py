@@ -55,9 +55,8 @@ def _info(**kw):
 def _planned(cfg, info):
     """A LoadToFilDirect with the host side of its constructor only (no device)."""
     from dspsr_amd import pipeline
-    lt = pipeline.LoadToFilDirect.__new__(pipeline.LoadToFilDirect)
-    delays = lt._plan(cfg, info)
-    return lt, delays
+    lt = pipeline.LoadToFilDirect(cfg, info, device=None)
+    return lt, lt.sd.delays
 
 
 def test_load_to_fil_direct_refusals_come_before_the_device():

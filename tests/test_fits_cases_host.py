@@ -189,8 +189,7 @@ def test_plan_arithmetic_at_hand_worked_points():
     # per-channel rate against all 16 channels: round(1.0 * 64 / 16) = 4, printed tsamp 64e-6 -- the chain delivers 4 * 4 us = 16 us
     tres, tsamp, _ = p.fits_plan(p.FitsConfig(nchan=16, tsamp=64e-6), chans)
     assert tres == 4 and tsamp == 4 / 1.0 * 16 / chans.rate
-    lt = object.__new__(p.LoadToFITS)
-    lt._plan(p.FitsConfig(nchan=16, tsamp=64e-6, npol=1), chans)
+    lt = p.LoadToFITS(p.FitsConfig(nchan=16, tsamp=64e-6, npol=1), chans, device=None)          # (the host plan alone)
     assert lt.out_rate == chans.rate / 4 / 4 and lt.header_values()["TBIN"] == 16e-6
     # nblock: -I 1 with 64e-6 * 2048 = 0.131072 s blocks: unsigned(7.629 + 0.5) = 8; -I 0.01: max(1, 0) = 1; -c wins over -I
     assert p.fits_plan(p.FitsConfig(nchan=16, rescale_seconds=1.0), real)[2] == 8
@@ -207,9 +206,9 @@ def test_plan_arithmetic_at_hand_worked_points():
 def test_plan_geometry_and_header_values():
     p = _pipeline()
     real = p.InputInfo(**REAL, start_seconds=0.25, mjd_day=55299, mjd_sec=100.0, source="J0437-4715")
-    lt = object.__new__(p.LoadToFITS)
-    assert lt._plan(p.FitsConfig(nchan=16, convolve=True, freq_res=4, dispersion_measure=10.0, coherent_dedisp=True, npol=2, nbit=4,
-                                 nsblk=128), real) is None
+    lt = p.LoadToFITS(p.FitsConfig(nchan=16, convolve=True, freq_res=4, dispersion_measure=10.0, coherent_dedisp=True, npol=2, nbit=4,
+                                   nsblk=128), real, device=None)
+    assert lt.sd.delays is None
     r = lt.front.response
     assert r.ndat == 4 * r.minimum_ndat                                                         # -x times the minimum (LoadToFITS.C:272)
     hv = lt.header_values()
@@ -218,12 +217,13 @@ def test_plan_geometry_and_header_values():
     assert lt.out_rate == 32e6 / 2 / 16 / 64 and lt.out_start == 0.25 + r.impulse_pos / (32e6 / 32)
     assert lt.block_bytes_out == 128 * 2 * 16 // 2
     # no response: -F 16 alone runs the filterbank at freq_res 1, -x 8 at 8; incoherent -D leaves the filterbank without a kernel
-    lt._plan(p.FitsConfig(nchan=16, npol=1), real)
+    lt = p.LoadToFITS(p.FitsConfig(nchan=16, npol=1), real, device=None)
     assert (lt.front.response.ndat, lt.front.response.kernel) == (1, None)
-    lt._plan(p.FitsConfig(nchan=16, freq_res=8, dispersion_measure=10.0, npol=1), real)
+    lt = p.LoadToFITS(p.FitsConfig(nchan=16, freq_res=8, dispersion_measure=10.0, npol=1), real, device=None)
     assert (lt.front.response.ndat, lt.front.response.kernel) == (8, None)
     # -K: delays of the 16 output channels at the scrunched rate; the start moves by the largest
-    delays = lt._plan(p.FitsConfig(nchan=16, freq_res=8, dispersion_measure=300.0, npol=1, dedisperse=True), real)
+    lt = p.LoadToFITS(p.FitsConfig(nchan=16, freq_res=8, dispersion_measure=300.0, npol=1, dedisperse=True), real, device=None)
+    delays = lt.sd.delays
     assert len(delays) == 16 and lt.sd.head == int(delays.max() - delays.min()) > 0
     assert lt.out_start == lt.front.out_start + int(delays.max()) / lt.out_rate
 

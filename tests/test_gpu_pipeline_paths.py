@@ -1,7 +1,8 @@
 """Every path through the pipeline drivers (tools/pipeline_paths.py) against tests/golden/pipeline_paths.json: the host arithmetic
 each path leaves behind -- derived attributes, counters after each block, the books of every sub-integration, the operations timed and
 their call counts -- for exact equality (floats as float.hex()).  The fixture was recorded with the same tool from the commit in front
-of the one that gave LoadToFold a single constructor path; it holds no profile samples (the path tests pin those against the oracle)."""
+of the one that gave LoadToFold a single constructor path (the last four search cases: from the commit in front of the one that
+built the search drivers from front ends and output stages); it holds no profile samples (the path tests pin those against the oracle)."""
 import importlib.util
 import json
 import os
@@ -21,7 +22,7 @@ with open(os.path.join(ROOT, "tests", "golden", "pipeline_paths.json")) as _f:
     GOLDEN = json.load(_f)
 
 CASES = ["during_fused", "during_L", "during_K", "during_subband_K", "after", "never", "before", "cyclic", "plfb", "two_targets_s",
-         "fourth_moment", "coherent_fused", "coherent_K_f", "direct_K"]
+         "fourth_moment", "coherent_fused", "coherent_K_f", "direct_K", "fil", "coherent_d4", "fits_F_D", "fits_direct_K"]
 
 
 def test_the_fixture_holds_every_case():

@@ -126,7 +126,7 @@ def test_block_bytes_of_the_drivers():
     info = pipeline.InputInfo(nchan=4, npol=2, ndim=2, machine="MKBF")
     drv = SimpleNamespace(cfg=SimpleNamespace(parts_per_block=3), nsamp_step=301, nsamp_overlap=211, layout=_lib.RAW_MEERKAT, in_nchan=4,
                           info=info)
-    for cls in (pipeline.LoadToFold, pipeline.LoadToFilCoherent):
+    for cls in (pipeline.LoadToFold, pipeline.ConvolvingFront):             # (LoadToFilCoherent's and LoadToFITS's blocks with -F)
         for npart, first in ((None, 0), (3, 0), (1, 0), (2, 255), (3, 17), (1, 1)):
             nsamp = (npart or 3) * 301 + 211
             assert cls.block_bytes(drv, npart, first) == hc.heap_bytes(-(-(first + nsamp) // 256), 4, 2)

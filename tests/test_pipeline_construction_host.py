@@ -1,4 +1,4 @@
-"""Construction and release of the four pipeline drivers, on the host: every engine, the context and the device allocator of
+"""Construction and release of the five pipeline drivers, on the host: every engine, the context and the device allocator of
 dspsr_amd.pipeline are replaced by recording fakes, so what is opened, what is closed and in which order can be counted here."""
 import itertools
 
@@ -16,6 +16,7 @@ class Log:
         self.fail_set_shape = 0                  # the n-th FoldEngine.set_shape raises
         self.fail_rescale = False
         self.fail_sk_shape = False               # SpectralKurtosisEngine.set_shape raises
+        self.fail_digitizer = False
 
 
 def _fakes(monkeypatch, with_dump=False):
@@ -69,10 +70,16 @@ def _fakes(monkeypatch, with_dump=False):
                 raise DspsrAmdError("fake Rescale refuses")
             super().__init__(*a, **k)
 
+    class Digitizer(Fake):
+        def __init__(self, *a, **k):
+            if log.fail_digitizer:
+                raise DspsrAmdError("fake FITSDigitizer refuses")
+            super().__init__(*a, **k)
+
     for name, cls in (("Context", Context), ("FilterbankEngine", Filterbank), ("ConvolutionEngine", type("Conv", (Filterbank,), {})),
                       ("FoldEngine", Fold), ("CyclicFoldEngine", type("Cyclic", (Fold,), {})),
                       ("PhaseLockedFilterbankEngine", type("Plfb", (Fold,), {})), ("SpectralKurtosisEngine", Sk), ("SampleDelay", Delay),
-                      ("Rescale", Rescale)):
+                      ("Rescale", Rescale), ("FITSDigitizer", Digitizer)):
         monkeypatch.setattr(pipeline, name, cls)
     monkeypatch.setattr(pipeline, "_device_empty", lambda ctx, shape, dtype="float32", zero=False: np.zeros(shape, dtype=dtype))
     if with_dump:
@@ -96,6 +103,10 @@ TARGETS = [pipeline.FoldTarget("a", folding_period=0.004, nbin=64), pipeline.Fol
 SEARCH_INFO = dict(centre_frequency=1382.0, bandwidth=-400.0, nchan=1, npol=2, ndim=1, tsamp_us=0.00125, machine="DADA")
 COHERENT = dict(nchan=64, tscrunch=16, nbit=8, rescale_seconds=2e-4, freq_res=1024, parts_per_block=3, max_parts=4)
 DIRECT_INFO = dict(centre_frequency=1400.0, bandwidth=-8.0, nchan=8, npol=2, ndim=2, tsamp_us=1.0, machine="DADA")
+# digifits on the same inputs: -F 64:D -K at 16 filterbank samples per output sample, and no -F
+FITS_F_K = dict(nchan=64, convolve=True, dispersion_measure=0.03, coherent_dedisp=True, dedisperse=True, tsamp=2.56e-6, npol=2, nbit=8, nsblk=16,
+                parts_per_block=3, max_parts=4)
+FITS_DIRECT = dict(nchan=0, tsamp=4e-6, npol=2, nbit=8, nsblk=16, parts_per_block=2048)
 DIRECT = dict(tscrunch=4, nbit=8, rescale_seconds=256.5 * 4 / 1e6, parts_per_block=2048, dispersion_measure=20.0, dedisperse=True)
 
 
@@ -123,6 +134,9 @@ BUILDS = {
                                                              pipeline.InputInfo(**SEARCH_INFO)), "Context Filterbank Delay Rescale"),
     "LoadToFilDirect": (lambda: pipeline.LoadToFilDirect(pipeline.SearchConfig(**DIRECT), pipeline.InputInfo(**DIRECT_INFO)),
                         "Context Delay Rescale"),
+    "LoadToFITS_F_K": (lambda: pipeline.LoadToFITS(pipeline.FitsConfig(**FITS_F_K), pipeline.InputInfo(**SEARCH_INFO)),
+                       "Context Filterbank Delay Digitizer"),
+    "LoadToFITS_direct": (lambda: pipeline.LoadToFITS(pipeline.FitsConfig(**FITS_DIRECT), pipeline.InputInfo(**DIRECT_INFO)), "Context Digitizer"),
 }
 
 
@@ -136,7 +150,7 @@ def test_construction_completes_and_close_releases_everything_once(monkeypatch, 
         assert len(drv.pulsars) == 2 and drv.fold is None and log.closed == [log.opened[2]]
     if name == "during_subband_K":                       # the band's head room; this rank's SampleDelay (total_delay 7) gives up the rest
         assert drv.sd_short == drv.sd_head - 7 > 0
-    if name not in ("LoadToFil", "LoadToFilDirect", "after", "never", "before"):      # (the two wrappers scale the engine's numbers)
+    if name not in ("LoadToFil", "LoadToFilDirect", "LoadToFITS_F_K", "LoadToFITS_direct", "after", "never", "before"):      # (the two wrappers scale the engine's numbers)
         assert (drv.nkeep, drv.nsamp_step, drv.nsamp_overlap) == (NKEEP, STEP, OVERLAP)
     drv.close()
     assert _released(log)
@@ -168,6 +182,7 @@ FAILURES = {
     "LoadToFil_rescale": (BUILDS["LoadToFil"][0], dict(fail_rescale=True), "fake Rescale refuses"),
     "LoadToFilCoherent_rescale": (BUILDS["LoadToFilCoherent"][0], dict(fail_rescale=True), "fake Rescale refuses"),
     "LoadToFilDirect_rescale": (BUILDS["LoadToFilDirect"][0], dict(fail_rescale=True), "fake Rescale refuses"),
+    "LoadToFITS_digitizer": (BUILDS["LoadToFITS_F_K"][0], dict(fail_digitizer=True), "fake FITSDigitizer refuses"),
 }
 
 
@@ -203,6 +218,11 @@ REFUSALS = [
                                         pipeline.InputInfo(**SEARCH_INFO)), "dsp::Rescale::init nsample == 0"),
     (lambda: pipeline.LoadToFil(pipeline.SearchConfig(nchan=64, tscrunch=16, rescale_seconds=1e-9, parts_per_block=32),
                                 pipeline.InputInfo(**SEARCH_INFO)), "dsp::Rescale::init nsample == 0"),
+    # LoadToFITS: a refusal of its front end, and one of its own
+    (lambda: pipeline.LoadToFITS(pipeline.FitsConfig(**FITS_DIRECT), pipeline.InputInfo(**dict(DIRECT_INFO, machine="CASPSR"))),
+     "dspsr_amd.LoadToFilDirect: the CASPSR byte order is not built on this path"),
+    (lambda: pipeline.LoadToFITS(pipeline.FitsConfig(**dict(FITS_F_K, nbit=3)), pipeline.InputInfo(**SEARCH_INFO)),
+     "dsp::FITSDigitizer::set_nbit nbit=3 not understood"),
 ]
 
 
@@ -232,7 +252,7 @@ def test_a_refusal_that_won_before_still_wins(monkeypatch):
 
 def test_close_on_an_instance_that_never_opened_a_device():
     """close() after a refusal of the host plan, and the communicator setters on a bare instance (test_fold_many_host uses them so)"""
-    for cls in (pipeline.LoadToFil, pipeline.LoadToFilCoherent, pipeline.LoadToFilDirect):
+    for cls in (pipeline.LoadToFil, pipeline.LoadToFilCoherent, pipeline.LoadToFilDirect, pipeline.LoadToFITS):
         drv = cls.__new__(cls)
         drv.close()
         drv.close()

@@ -30,7 +30,7 @@ def _enc(log, v):
     """One argument of a recorded call: scalars as they are (floats by repr), tensors by shape and storage offset, host arrays by
     shape, type and -- the short ones: window starts and bins -- values, engines by their place in the order of opening."""
     if isinstance(v, torch.Tensor):
-        return {"tensor": list(v.shape), "offset": v.storage_offset()}
+        return log.tensor(v)
     if isinstance(v, np.ndarray):
         d = {"array": list(v.shape), "dtype": str(v.dtype)}
         if v.size <= 16:
@@ -56,9 +56,24 @@ class Log:
     def name(self, obj):
         return "%s#%d" % (type(obj).__name__, self.opened.index(obj))
 
+    def tensor(self, v):
+        return {"tensor": list(v.shape), "offset": v.storage_offset()}
+
     def call(self, who, method, *a, **k):
         self.calls.append([who if isinstance(who, str) else self.name(who), method, [_enc(self, x) for x in a],
                            {key: _enc(self, k[key]) for key in sorted(k)}])
+
+
+def recorded(log, *names, returns=None):
+    """Class decorator: the methods `names` write their call into `log` and return `returns`."""
+    def deco(cls):
+        for n in names:
+            def method(self, *a, _n=n, **k):
+                log.call(self, _n, *a, **k)
+                return returns
+            setattr(cls, n, method)
+        return cls
+    return deco
 
 
 def _fakes(mp):
@@ -75,22 +90,12 @@ def _fakes(mp):
         def synchronize(self):
             pass
 
-    def recorded(*names, returns=None):
-        def deco(cls):
-            for n in names:
-                def method(self, *a, _n=n, **k):
-                    log.call(self, _n, *a, **k)
-                    return returns
-                setattr(cls, n, method)
-            return cls
-        return deco
-
     class Context(Fake):
         def __init__(self, device=0, stream=None):
             super().__init__()
             self.device, self.handle = device, 1
 
-    @recorded("perform", "perform_raw", "perform_detect", "perform_fold", "set_kernel")
+    @recorded(log, "perform", "perform_raw", "perform_detect", "perform_fold", "set_kernel")
     class Filterbank(Fake):
         nkeep, nsamp_step, nsamp_overlap, nsamp_fft = 100, 3200, 320, 3520
 
@@ -103,7 +108,7 @@ def _fakes(mp):
     class Conv(Filterbank):
         nkeep, nsamp_step, nsamp_overlap, nsamp_fft = 100, 100, 20, 120
 
-    @recorded("set_shape", "set_nbin", "set_ndat", "fold", "fold_moments", "fold_zeroed", "zero")
+    @recorded(log, "set_shape", "set_nbin", "set_ndat", "fold", "fold_moments", "fold_zeroed", "zero")
     class Fold(Fake):
         def set_bins(self, phi, phase_per_sample, ndat, idat_start=0, hits=None):
             log.call(self, "set_bins", phi, phase_per_sample, ndat, idat_start, hits)
@@ -127,7 +132,7 @@ def _fakes(mp):
             log.call(self, "synch")
             return np.zeros(self.out, np.float32)
 
-    @recorded("zero")
+    @recorded(log, "zero")
     class Plfb(Fake):
         def set_shape(self, nchan_in, npol_in, ndim_in, nchan, npol_out, nbin):
             log.call(self, "set_shape", nchan_in, npol_in, ndim_in, nchan, npol_out, nbin)
@@ -141,7 +146,7 @@ def _fakes(mp):
             log.call(self, "synch")
             return np.zeros(self.out, np.float32)
 
-    @recorded("set_shape", "set_options", "transform")
+    @recorded(log, "set_shape", "set_options", "transform")
     class Sk(Fake):
         def get_statistics(self):
             log.call(self, "get_statistics")
@@ -158,11 +163,11 @@ def _fakes(mp):
             log.call(self, "transform", inp)
             return max(0, inp.shape[2] - self.total_delay)
 
-    @recorded("polarimetry")
+    @recorded(log, "polarimetry")
     class Detection(Fake):
         pass
 
-    @recorded("write")
+    @recorded(log, "write")
     class Dump(Fake):
         def __init__(self, path, **k):
             super().__init__()

@@ -66,11 +66,8 @@ def main(argv=None):
     nsamp = 0
     with open(out, "wb") as f:
         write_header(f, lt, info, a.file)
-        bps = df.bytes_per_sample
-        for s0 in range(0, df.ndat, cfg.parts_per_block):
-            ndat = min(cfg.parts_per_block, df.ndat - s0)
-            host = torch.from_numpy(df._map[s0 * bps:(s0 + ndat) * bps].copy())
-            packed = lt.process_block(host.to("cuda:%d" % a.device), ndat)
+        for raw, ndat in lt.file_calls(df):
+            packed = lt.process_block(torch.from_numpy(raw.copy()).to("cuda:%d" % a.device), ndat)
             packed.cpu().numpy().tofile(f)
             nsamp += packed.numel() // lt.bytes_per_sample
     lt.synchronize()

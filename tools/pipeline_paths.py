@@ -1,13 +1,14 @@
 """One small run of every path through the pipeline drivers, public API only: the host arithmetic each one leaves behind.
 usage: python tools/pipeline_paths.py [--record FILE.json] [--dump DIR] [--case NAME ...]
 
-Every case builds its driver with parts_per_block 3 (LoadToFilDirect: blocks of time samples), feeds three blocks of seeded int8
-noise with record_time on, and calls finish_subint.  What comes out is a record of host numbers -- derived attributes, the counters
+Every fold case builds its driver with parts_per_block 3, feeds three blocks of seeded int8 noise with record_time on, and calls
+finish_subint; every search case feeds the calls listed with it (parts, or time samples where there is no -F).  What comes out is a record of host numbers -- derived attributes, the counters
 after each block, the books of every sub-integration, the operations timed and how often -- with floats as float.hex():
 tests/test_gpu_pipeline_paths.py compares it with tests/golden/pipeline_paths.json for exact equality.  --dump DIR also writes each
 case's profiles and packed bytes as .npy, for a byte comparison of two checkouts.  The geometries are those of the pipeline tests of
 each path (test_gpu_plain, test_gpu_parity, test_gpu_multigpu, test_gpu_cyclic_pipeline, test_gpu_plfb_pipeline, test_gpu_fold_many,
-test_gpu_fourth_moment, test_gpu_search, test_gpu_direct_search)."""
+test_gpu_fourth_moment, test_gpu_search, test_gpu_direct_search, test_gpu_tfp, test_gpu_fits_pipeline).  A LoadToFITS case records the
+blocks each call completes, and dumps their bytes, DAT_SCL and DAT_OFFS."""
 import argparse
 import json
 import os
@@ -98,6 +99,8 @@ def search_cases(pipeline):
     info = P.InputInfo(centre_frequency=1382.0, bandwidth=-400.0, nchan=1, npol=2, ndim=1, tsamp_us=0.00125, machine="DADA")     # test_gpu_search
     direct = P.InputInfo(centre_frequency=1400.0, bandwidth=-8.0, nchan=8, npol=2, ndim=2, tsamp_us=1.0, machine="DADA",
                          start_seconds=0.5, mjd_day=55299, mjd_sec=7545.0)                                                     # test_gpu_direct_search
+    fits_real = P.InputInfo(centre_frequency=1400.0, bandwidth=-16.0, nchan=1, npol=2, ndim=1, tsamp_us=1.0 / 32.0, machine="DADA")
+    fits_direct = P.InputInfo(centre_frequency=1400.0, bandwidth=4.0, nchan=4, npol=2, ndim=2, tsamp_us=1.0, machine="DADA")
     coh = dict(nchan=64, tscrunch=16, nbit=8, rescale_seconds=2e-4, freq_res=1024, parts_per_block=3, max_parts=4)
     return {
         "coherent_fused": lambda: (P.LoadToFilCoherent(P.SearchConfig(dispersion_measure=2.0, **coh), info, stream=_stream()), [3, 3, 3]),
@@ -107,6 +110,17 @@ def search_cases(pipeline):
         "direct_K": lambda: (P.LoadToFilDirect(P.SearchConfig(tscrunch=4, nbit=8, rescale_seconds=256.5 * 4 / 1e6, parts_per_block=2048,
                                                               dispersion_measure=20.0, dedisperse=True), direct, stream=_stream()),
                              [2000, 300, 700]),
+        "fil": lambda: (P.LoadToFil(P.SearchConfig(nchan=64, tscrunch=16, nbit=8, rescale_seconds=2e-4, parts_per_block=64), info,
+                                    stream=_stream()), [64, 64, 32]),
+        "coherent_d4": lambda: (P.LoadToFilCoherent(P.SearchConfig(dispersion_measure=2.0, npol=4, **coh), info, stream=_stream()), [3, 3, 2]),
+        # (the `real` and `direct` shapes of test_gpu_fits_pipeline, in its unequal cuts: a call that completes no block, one that
+        # completes several)
+        "fits_F_D": lambda: (P.LoadToFITS(P.FitsConfig(nchan=16, convolve=True, freq_res=256, dispersion_measure=1.0, coherent_dedisp=True,
+                                                       tsamp=16e-6, parts_per_block=14, npol=4, nbit=4, nsblk=128), fits_real,
+                                          stream=_stream()), [1, 5, 2, 6]),
+        "fits_direct_K": lambda: (P.LoadToFITS(P.FitsConfig(nchan=0, dispersion_measure=100.0, tsamp=16e-6, parts_per_block=16384, npol=2,
+                                                            nbit=8, nsblk=128, dedisperse=True), fits_direct, stream=_stream()),
+                                  [100, 7000, 1, 0, 5887]),
     }
 
 
@@ -157,6 +171,12 @@ def run_search(pipeline, name, seed):
         raw = torch.from_numpy(_noise(seed + b, drv.block_bytes(n))).cuda()
         packed = drv.process_block(raw, n)
         drv.synchronize()
+        if isinstance(packed, list):                      # LoadToFITS: the blocks this call completed
+            rec["blocks"].append([len(packed), int(drv.nblocks_out)])
+            for k, blk in enumerate(packed):
+                for what, t in zip(("bytes", "dat_scl", "dat_offs"), blk):
+                    arrays["%s_call%d_block%d_%s" % (name, b, k, what)] = t.cpu().numpy().copy()
+            continue
         rec["blocks"].append([int(packed.numel()), int(drv.ndat_out)])
         arrays["%s_block%d" % (name, b)] = packed.cpu().numpy().copy()
     drv.close()

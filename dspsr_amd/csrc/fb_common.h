@@ -111,6 +111,8 @@ enum FbOutKind : int {
   FB_OUT_SEARCH = 5,    // search mode (digifil -F N:D): square-law detection (state = DSPSR_AMD_INTENSITY | DSPSR_AMD_PPQQ) and the
                         //   time scrunch of the detected STREAM inside the inverse pass; base = FPT rows [chan][npol_out] of
                         //   scrunched samples, chan_stride / pol_stride in floats, ndim 1, ts_*.  See ts_part / the search epilogue below.
+                        //   state = DSPSR_AMD_COHERENCE (digifits -p 4, digifil -d 4): the four products, npol_out 4, in kernels of
+                        //   their own (k_inv_chan<., 18 | 22, .>, k_rows_inv<., ., 4>) -- the host picks them by this state
 };
 
 struct FbOut {
@@ -170,9 +172,22 @@ DEV float sqld(const cf a) { return __fadd_rn(__fmul_rn(a.x, a.x), __fmul_rn(a.y
 // The tile's detected samples are staged as [channel * npol_out + q][element r of the group][group] floats (G groups per row, G
 // odd): the scrunch then reads element r of consecutive groups from consecutive words (conflict free), and the last stage's writes
 // -- consecutive samples of a lane pair's channels -- fall G words apart.
+// NPO: 0 = the square-law states, told apart by out.state at run time (Intensity: one row per channel, PPQQ: two); 4 = the Coherence
+// products (digifits -p 4, digifil -d 4) as a compile-time form of its own: PP, QQ, Re PQ*, Im PQ* by detect4 -- the function
+// and expression fb_put_detected writes them with, so that the staged floats are the unfused route's bits -- in four rows per channel.
+DEV void detect4(const cf p, const cf q, const int state, float (&r)[4]);      // (below, with the output rows)
+template <int NPO = 0>
 DEV void ts_stage(float* __restrict__ stg, const FbOut& out, const TsPart& tp, const uint32_t slo, const uint32_t t, const cf a, const cf b)
 {
   const uint32_t tr = t + tp.phi, gq = out.ts_sf == 1 ? tr : __umulhi(tr, out.ts_magic), r = tr - gq * out.ts_sf;
+  if constexpr (NPO == 4) {
+    float d[4];
+    detect4(a, b, DSPSR_AMD_COHERENCE, d);
+    const uint32_t base = ((4 * slo) * out.ts_sf + r) * out.ts_G + gq, rs = out.ts_sf * out.ts_G;
+#pragma unroll
+    for (int q = 0; q < 4; q++) stg[base + q * rs] = d[q];
+    return;
+  }
   const float pp = sqld(a), qq = sqld(b);
   if (out.state == DSPSR_AMD_PPQQ) {
     const uint32_t base = ((2 * slo) * out.ts_sf + r) * out.ts_G + gq;
@@ -190,11 +205,20 @@ DEV float ts_carry_load(const FbOut& out, const uint32_t row) { return __hip_ato
 // by different threads and waves: so ts_reduce reads no carry.  Item w = tid + k * nthr < nrow takes carry_pre[k], which the
 // caller loaded from row w's carry (when tp.phi) in front of the barrier that precedes this call -- every carry of the tile is read
 // before any is replaced.  The caller guarantees nrow <= NPRE * nthr.  Sums are sequential in time: out = in[0]; out += in[1]; ...
-template <int NPRE, class ChanOf>
+// NPO as in ts_stage: 0 = npol_out from out.state, 4 = the four Coherence rows (a constant divisor).
+// The Coherence form keeps that order with four carries per channel: a tile's 4 T3 rows are 64 / freq_res per thread, and each
+// caller loads ALL of them where it loaded one or two -- k_inv_chan from freq_res 64 on and k_rows_inv one per thread in the stage hook
+// (rows <= threads), k_inv_chan at freq_res 32 two per thread in the same hook call (rows tid and tid + nthr: same program point, so
+// the same barriers lie between them and the stores on either side), at freq_res 16 four per thread behind the single stage's
+// barrier.  In every form the loads stand behind a barrier that follows the previous part's ts_reduce (its carry stores) and in front of
+// the barrier that precedes this part's ts_reduce; the stores below are the only writes of the carry in the kernel, and a tile's
+// carries belong to the one workgroup that walks its parts (fb_inv_walk.h), so no other workgroup touches them.  freq_res 8 would need
+// eight per thread and is refused on the host (fb_search_fits).  A passing run guards this order; it does not prove it.
+template <int NPO = 0, int NPRE, class ChanOf>
 DEV void ts_reduce(const float* __restrict__ stg, const FbOut& out, const TsPart& tp, const uint32_t nrow, const float (&carry_pre)[NPRE],
                    const uint32_t tid, const uint32_t nthr, ChanOf&& chan_of)
 {
-  const uint32_t sf = out.ts_sf, G = out.ts_G, npo = out.state == DSPSR_AMD_PPQQ ? 2u : 1u;
+  const uint32_t sf = out.ts_sf, G = out.ts_G, npo = NPO ? (uint32_t)NPO : out.state == DSPSR_AMD_PPQQ ? 2u : 1u;
   const uint32_t ng1 = tp.ng - 1, nitem = nrow * tp.ng;
   float cp[NPRE];                                                  // cp[0] = carry_pre[k] in iteration k (shifted down: static indices only)
 #pragma unroll
@@ -670,13 +694,14 @@ k3_t fb_pick3(int logf, bool full, bool presplit = false);       // plain
 k3_t fb_pick3f(int logf, bool full, bool presplit = false);      // fused fold
 k3_t fb_pick3q(int logf, bool full, bool presplit = false);      // fused fold of the square-law states (fb_inv_chan_fold_sq.hip)
 k3_t fb_pick3s(int logf, bool full, bool presplit = false);      // search mode (detection + time scrunch)
+k3_t fb_pick3c(int logf, bool full, bool presplit = false);      // search mode, Coherence products (fb_inv_chan_search_coh.hip)
 k3_t fb_pick3m(int logf, bool full, bool presplit = false);      // matrix response, plain output (fb_inv_chan_matrix.hip)
 k3a_t fb_pick3a(int logf, bool blocked, bool real, bool full);
 k3b_t fb_pick3b(int logf, bool foldb, bool full);
 // two-pass path (fb_two_pass.hip): pass 1 on whole columns, rows + inverse pass (M = 2^logm, Fb = 2^(13 - logm)), the 8-bit regroup
 typedef void (*k1c_t)(FbGeom, FbIn, cf*, const cf*, uint32_t, uint32_t, uint32_t);
 k1c_t fb_pick_col1();
-k3_t fb_pick_rinv(int logm, int epi);      // epilogue: 0 output written, 1 fused fold, 2 search mode
+k3_t fb_pick_rinv(int logm, int epi);      // epilogue: 0 output written, 1 fused fold, 2 search mode, 4 search mode with the Coherence products
 void fb_launch_raw_cols(dim3 grid, hipStream_t stream, const FbGeom& g, const FbIn& in, uint16_t* Rt, uint64_t part0);
 void fb_launch_sub_split(hipStream_t stream, const SubSplit& p, uint8_t* out, uint32_t ncu);
 // radix-nsub step on the sub-spectra in X.  Xout == nullptr: in place where a kernel is instantiated for the factor (3, 5, 7, 9,

@@ -38,6 +38,11 @@ namespace dspsr_amd {
 // tile's rows warm.
 constexpr int FB_EPI_PRESPLIT = 4;
 constexpr int FB_EPI_MATRIX = 8;
+// EPIP bit 16 (FB_EPI_COHERENCE, search mode only: k_inv_chan<., 18 | 22, .>, fb_inv_chan_search_coh.hip): the search epilogue on the
+// four Coherence products PP, QQ, Re PQ*, Im PQ* (digifits -p 4, digifil -d 4) -- four staged rows and four carries per channel,
+// detection and row count compile-time (ts_stage<4>, ts_reduce<4>).  The square-law forms <., 2 | 6, .> do not see the bit: every
+// use of it below is `if constexpr` or a constant that is theirs when it is clear.
+constexpr int FB_EPI_COHERENCE = 16;
 constexpr int FB_MATRIX_GROUP = 4;     // elements per response load group: 32 registers, two groups live at a time
 
 // (d1', d2') = J (d1, d2) for the two polarisations a cx2 holds, h0 = (f11, f21), h1 = (f22, f12).  Each output is the scalar
@@ -70,6 +75,9 @@ __global__ __launch_bounds__(512) void k_inv_chan(const FbGeom g, const cf* __re
   constexpr bool PRESPLIT = (EPIP & FB_EPI_PRESPLIT) != 0;
   constexpr bool MATRIX = (EPIP & FB_EPI_MATRIX) != 0;
   static_assert(!MATRIX || EPI == 0, "the matrix response has the plain epilogue only");
+  constexpr bool COH = (EPIP & FB_EPI_COHERENCE) != 0;
+  static_assert(!COH || EPI == 2, "the Coherence products are a form of the search epilogue");
+  constexpr int TS_NPO = COH ? 4 : 0;       // ts_stage / ts_reduce: 0 = npol_out from out.state (Intensity, PPQQ)
   typedef FftPlan<LOGF> P;
   constexpr bool FOLD = EPI == 1, SEARCH = EPI == 2;
   constexpr bool FOLDQ = EPI == 3;          // the fused square-law fold: walks and plans as FOLD, stages and adds floats
@@ -339,6 +347,9 @@ __global__ __launch_bounds__(512) void k_inv_chan(const FbGeom g, const cf* __re
     const uint64_t part = part0 + item.lp;
     [[maybe_unused]] TsPart tsp = {0, 0, 0, 0};
     [[maybe_unused]] float ts_carry_mid = 0.f;      // SEARCH, two or more stages: the carry of row tid, loaded in mid()
+    // COH at freq_res 32 (two stages, 2 T3 threads, 4 T3 rows): the carry of the thread's second row, tid + blockDim.x
+    constexpr bool TS_MID2 = COH && FftPlan<LOGF>::NS >= 2 && LOGF < 6;
+    [[maybe_unused]] float ts_carry_mid2 = 0.f;
     if constexpr (SEARCH) tsp = ts_part(out, (uint32_t)part, g.nkeep);
     const uint32_t fcs = inv_fold_stride(logT3, g.nkeep, blockDim.x);
     auto chan_of = [&](const uint32_t slo) { return tile * T3 + slo; };
@@ -346,7 +357,7 @@ __global__ __launch_bounds__(512) void k_inv_chan(const FbGeom g, const cf* __re
     if constexpr (FOLDQ) fcq = inv_foldq_stride(logT3, g.nkeep, blockDim.x, out.prof_planes);
     auto store = [&](const uint32_t col, const uint32_t p, const uint32_t pstride, auto& v) {
       if constexpr (FOLDQ) inv_store_sq(lds, g, out, fcq, g.npol == 2, col, p, pstride, v);
-      else inv_store<FOLD, SEARCH>(lds, g, out, tsp, fcs, chan_of(col >> 1), part, g.npol == 2, col, p, pstride, v);
+      else inv_store<FOLD, SEARCH, TS_NPO>(lds, g, out, tsp, fcs, chan_of(col >> 1), part, g.npol == 2, col, p, pstride, v);
     };
     // FOLD: this part's active bins, and the accumulator of the thread's first work item (fb_inv_epilogue.h)
     constexpr bool PRE = FOLD && FftPlan<LOGF>::NS >= 2;
@@ -362,11 +373,16 @@ __global__ __launch_bounds__(512) void k_inv_chan(const FbGeom g, const cf* __re
     auto mid = [&](const int phase) {
       if constexpr (SEARCH) {
         // the open output sample's partial sum (written by this workgroup at the end of the previous part, two barriers ago)
-        const uint32_t npo = out.state == DSPSR_AMD_PPQQ ? 2u : 1u;
+        const uint32_t npo = COH ? 4u : out.state == DSPSR_AMD_PPQQ ? 2u : 1u;
         // (behind the tile's first barrier: that store has been waited for.  Single-stage transforms load theirs behind wgfft: their
         //  mid(1) runs in front of the only barrier that orders the previous tile's carry stores)
         if (FftPlan<LOGF>::NS >= 2 && phase == 2 && tsp.phi && tid < (npo << logT3))
           ts_carry_mid = ts_carry_load(out, (out.chan0 + tile * T3 + tid / npo) * npo + tid % npo);
+        if constexpr (TS_MID2) {
+          // (the same place in the tile, hence the same order against the previous and this tile's carry stores)
+          const uint32_t w = tid + blockDim.x;
+          if (phase == 2 && tsp.phi && w < (npo << logT3)) ts_carry_mid2 = ts_carry_load(out, (out.chan0 + tile * T3 + w / npo) * npo + w % npo);
+        }
       }
       if constexpr (PRE) {
         if (phase == 2) inv_acc_preload<1>(g, out, acc, fseg, fpart, logT3, tid, blockDim.x, en_pre, acc_pre, chan_of);
@@ -381,13 +397,15 @@ __global__ __launch_bounds__(512) void k_inv_chan(const FbGeom g, const cf* __re
     wgfft<LOGF, +1, EPI != 0>(lds, ltw_off, tid, logT, x, store, mid);
     FB_ST(3, 3);
     if constexpr (SEARCH) {
-      const uint32_t npo = out.state == DSPSR_AMD_PPQQ ? 2u : 1u, nrow = npo << logT3;
+      const uint32_t npo = COH ? 4u : out.state == DSPSR_AMD_PPQQ ? 2u : 1u, nrow = npo << logT3;
       // the carries of the rows w = tid + k * blockDim.x of this tile (ts_reduce).  nrow / blockDim.x = 16 npo / freq_res
       // (blockDim.x = freq_res * T / 32, nrow = npo * T / 2): one row per thread from freq_res 32 on (two or more stages), up to four
-      // below (freq_res 8 with PPQQ; fb_search_fits refuses more)
-      constexpr int TS_NPRE = FftPlan<LOGF>::NS >= 2 ? 1 : 4;
+      // below (freq_res 8 with PPQQ; fb_search_fits refuses more).  COH, 64 npo / freq_res = rows per thread: one from freq_res 64 on,
+      // two at freq_res 32 (two stages: both loaded in mid), four at freq_res 16 (single stage, below); freq_res 8 is refused
+      constexpr int TS_NPRE = FftPlan<LOGF>::NS >= 2 ? (TS_MID2 ? 2 : 1) : 4;
       float ts_carry_pre[TS_NPRE] = {};
       ts_carry_pre[0] = ts_carry_mid;
+      if constexpr (TS_MID2) ts_carry_pre[1] = ts_carry_mid2;
       if constexpr (FftPlan<LOGF>::NS < 2) {
         // single stage: behind wgfft's STAGED barrier (the previous tile's carry stores are done) and in front of the barrier
         // below (behind which ts_reduce stores this tile's): all rows of the tile, up to TS_NPRE per thread
@@ -400,7 +418,7 @@ __global__ __launch_bounds__(512) void k_inv_chan(const FbGeom g, const cf* __re
         }
       }
       __syncthreads();                       // the tile's detected samples are staged; every carry of the tile has been read
-      ts_reduce((const float*)lds, out, tsp, nrow, ts_carry_pre, tid, blockDim.x, chan_of);
+      ts_reduce<TS_NPO>((const float*)lds, out, tsp, nrow, ts_carry_pre, tid, blockDim.x, chan_of);
       // (the barrier in front of the next tile's first exchange write also ends this read phase)
     }
     if constexpr (FOLD) {

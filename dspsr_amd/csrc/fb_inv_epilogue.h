@@ -29,7 +29,8 @@ DEV uint32_t inv_fold_stride(const int logT3, const uint32_t nkeep, const uint32
 //   neither complex or detected rows of channel out.chan0 + chan; the addresses are a base plus a multiple of a wave-uniform step, and
 //           the output kind / layout is uniform: chosen once, outside the unrolled element loop (no branch per element)
 // chan: the channel of the staged row, within this input channel's sub-band.  two: the second polarisation exists.
-template <bool FOLD, bool SEARCH, class V>
+// TS_NPO (SEARCH): ts_stage's NPO -- 0 the square-law states, 4 the Coherence products.
+template <bool FOLD, bool SEARCH, int TS_NPO = 0, class V>
 DEV void inv_store(cf* lds, const FbGeom& g, const FbOut& out, const TsPart& tsp, const uint32_t fcs, const uint32_t chan,
                    const uint64_t part, const bool two, const uint32_t col, const uint32_t p, const uint32_t pstride, V& v)
 {
@@ -52,7 +53,7 @@ DEV void inv_store(cf* lds, const FbGeom& g, const FbOut& out, const TsPart& tsp
     for (int k = 0; k < R; k++) {
       const int32_t t = t0 + (int32_t)(k * pstride);
       if ((uint32_t)t >= g.nkeep) continue;
-      ts_stage((float*)lds, out, tsp, col >> 1, (uint32_t)t, cx2_lo(v[k]), two ? cx2_hi(v[k]) : make_float2(0.f, 0.f));
+      ts_stage<TS_NPO>((float*)lds, out, tsp, col >> 1, (uint32_t)t, cx2_lo(v[k]), two ? cx2_hi(v[k]) : make_float2(0.f, 0.f));
     }
     return;
   }

@@ -195,7 +195,11 @@ __global__ __launch_bounds__(512) void k_rows_inv(const FbGeom g, const cf* __re
                                                   const uint32_t nparts, const uint32_t run)
 {
   static_assert(LOGM + LOGFB == 13 && LOGFB >= 1 && LOGFB <= 4, "k_rows_inv: Fb channels x 2 pols x M bins = 2^14 points");
-  constexpr bool FOLD = EPI == 1, SEARCH = EPI == 2;         // (the epilogues of k_inv_chan)
+  // (the epilogues of k_inv_chan; EPI 4 = the search epilogue on the four Coherence products, k_inv_chan's FB_EPI_COHERENCE: instantiations
+  //  of their own, the square-law ones <., ., 2> take TS_NPO = 0 and the run-time npo they had)
+  constexpr bool COH = EPI == 4;
+  constexpr bool FOLD = EPI == 1, SEARCH = EPI == 2 || COH;
+  constexpr int TS_NPO = COH ? 4 : 0;
   extern __shared__ __attribute__((aligned(16))) cf lds[];
   uint32_t tid = threadIdx.x;
   // (the inverse 512-point transforms as even / odd 256-point halves + a radix-2 step in registers measured -3 % fused but +28 %
@@ -325,13 +329,13 @@ __global__ __launch_bounds__(512) void k_rows_inv(const FbGeom g, const cf* __re
     const uint32_t tile = item.tile;
     const uint64_t part = part0 + item.lp;
     [[maybe_unused]] TsPart tsp = {0, 0, 0, 0};
-    // SEARCH: the carry of row tid (ts_reduce).  nrow = npo * Fb <= 32 rows, within the 512 threads: item w < nrow is thread w's first
+    // SEARCH: the carry of row tid (ts_reduce).  nrow = npo * Fb <= 32 rows (64 with the Coherence products), within the 512 threads: item w < nrow is thread w's first
     [[maybe_unused]] float ts_carry_pre[1] = {0.f};
     if constexpr (SEARCH) tsp = ts_part(out, (uint32_t)part, g.nkeep);
     const uint32_t fcs = inv_fold_stride(logT3, g.nkeep, blockDim.x);
     auto chan_at = [&](const uint32_t slo) { return chan_of(tile, slo); };
     auto store = [&](const uint32_t col, const uint32_t p, const uint32_t pstride, auto& v) {
-      inv_store<FOLD, SEARCH>(lds, g, out, tsp, fcs, chan_at(col >> 1), part, true, col, p, pstride, v);
+      inv_store<FOLD, SEARCH, TS_NPO>(lds, g, out, tsp, fcs, chan_at(col >> 1), part, true, col, p, pstride, v);
     };
     constexpr bool PRE = FOLD && FftPlan<LOGM>::NS >= 2;
     constexpr int NPRE = PRE && LOGFB >= 3 ? 2 : 1;       // >= 8 channels per tile: a thread may fold a second item
@@ -347,7 +351,7 @@ __global__ __launch_bounds__(512) void k_rows_inv(const FbGeom g, const cf* __re
       if constexpr (SEARCH) {
         // the open output sample's partial sum (this workgroup's store at the end of the previous part; FROM_LDS: the rows -> bins
         // exchange in front of the transform has passed two barriers since)
-        const uint32_t npo = out.state == DSPSR_AMD_PPQQ ? 2u : 1u;
+        const uint32_t npo = COH ? 4u : out.state == DSPSR_AMD_PPQQ ? 2u : 1u;
         if (phase == 1 && tsp.phi && tid < (npo << logT3))
           ts_carry_pre[0] = ts_carry_load(out, (out.chan0 + chan_of(tile, tid / npo)) * npo + tid % npo);
       }
@@ -363,8 +367,8 @@ __global__ __launch_bounds__(512) void k_rows_inv(const FbGeom g, const cf* __re
     FB_ST(7, 4);
     if constexpr (SEARCH) {
       __syncthreads();                       // the tile's detected samples are staged
-      const uint32_t npo = out.state == DSPSR_AMD_PPQQ ? 2u : 1u;
-      ts_reduce((const float*)lds, out, tsp, npo << logT3, ts_carry_pre, tid, blockDim.x, chan_at);
+      const uint32_t npo = COH ? 4u : out.state == DSPSR_AMD_PPQQ ? 2u : 1u;
+      ts_reduce<TS_NPO>((const float*)lds, out, tsp, npo << logT3, ts_carry_pre, tid, blockDim.x, chan_at);
     }
     if constexpr (FOLD) {
       __syncthreads();
@@ -382,7 +386,7 @@ __global__ __launch_bounds__(512) void k_rows_inv(const FbGeom g, const cf* __re
 k1c_t fb_pick_col1() { return k_fwd_col1q<1>; }
 k3_t fb_pick_rinv(int logm, int epi)
 {
-#define FB_RINV(M, B) (epi == 1 ? k_rows_inv<M, B, 1> : epi == 2 ? k_rows_inv<M, B, 2> : k_rows_inv<M, B, 0>)
+#define FB_RINV(M, B) (epi == 1 ? k_rows_inv<M, B, 1> : epi == 2 ? k_rows_inv<M, B, 2> : epi == 4 ? k_rows_inv<M, B, 4> : k_rows_inv<M, B, 0>)
   switch (logm) {
     case 9: return FB_RINV(9, 4);
     case 10: return FB_RINV(10, 3);

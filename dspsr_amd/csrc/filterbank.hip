@@ -40,6 +40,7 @@ struct dspsr_amd_filterbank_impl {
   FbPass<k3_t> p3 = {}, p3f = {}, p3s = {};  // inverse pass: plain, fused fold (the plan in LDS behind the tile), search mode
   FbPass<k3_t> p3m = {};                     // ... with the matrix response (fb_pick3m; set by the first set_response_matrix)
   FbPass<k3_t> p3q = {};                     // ... fused fold of the square-law states (Intensity, PPQQ): p3f's LDS and plan
+  FbPass<k3_t> p3c = {};                     // ... search mode on the four Coherence products (fb_pick3c): p3s's shape
   FbPass<k3a_t> p3a = {};                    // four-pass geometry: the first inverse pass
   FbPass<k3b_t> p3b = {}, p3bf = {};         // ... the second one, plain / leaving fold segment sums (FB_OUT_SEGSUM)
   float* fpart = nullptr;    // segmented fused fold: partial profiles of the part runs 1 .. nseg-1 of a launch
@@ -54,6 +55,7 @@ struct dspsr_amd_filterbank_impl {
   FbGeom g1t;                 // ... Fa < 2^14: through k_raw_transpose + k_fwd_cols, their geometry (M = Fa, Rr = Fb, T2 = freq_res)
   FbPass<k1_t> p1t = {};
   FbPass<k3_t> p2r = {}, p2rf = {}, p2rs = {};   // ... rows + inverse pass: plain, fused fold, search mode
+  FbPass<k3_t> p2rc = {};                        // ... search mode on the four Coherence products
   uint32_t plan_cap2 = 0;
   float* msum = nullptr;     // four-pass fused fold: segment sums [chan][part][tile][t2][2] float4 of one input channel's sub-band and one block
   size_t msum_floats = 0;
@@ -290,7 +292,7 @@ static int fb_tile(dspsr_amd_filterbank* fb)
     fb->p3bf = fb->p3b;
   } else {
     shape(fb->p3, p3, g.logM, true);
-    fb->p3f = fb->p3q = fb->p3s = fb->p3m = fb->p3;
+    fb->p3f = fb->p3q = fb->p3s = fb->p3c = fb->p3m = fb->p3;
   }
   return DSPSR_AMD_OK;
 }
@@ -331,6 +333,7 @@ static int fb_pick_kernels(dspsr_amd_filterbank* fb)
     fb->p3.kern = fb_pick3(g.logM, full3, ps);
     fb->p3f.kern = fb_pick3f(g.logM, full3, ps);
     fb->p3s.kern = fb_pick3s(g.logM, full3, ps);
+    fb->p3c.kern = fb_pick3c(g.logM, full3, ps);
     // fused fold: the LDS left over behind the twiddle tables holds the part's fold plan (two buffers)
     const FbPlanLds pl = fb_plan_lds(fb->p3.lds, fb->p3.threads);   // one plan entry per thread of the workgroup (<= 512)
     fb->plan_cap = pl.cap;
@@ -343,7 +346,7 @@ static int fb_pick_kernels(dspsr_amd_filterbank* fb)
   // (the three passes of the pre-split form only work together: X' is not the X layout; it takes the L elements per part X has)
   if (ps && !(fb->p1_w1.kern && fb->p1_w4.kern && fb->p3f.kern && fb->p3s.kern && fb->nseq == 1 && g.xstride == fb->L))
     return fb_fail(fb->ctx, DSPSR_AMD_EINVAL, "dspsr_amd_filterbank_create: no kernels for the pre-split spectrum of this geometry");
-  const hipError_t e = allow_lds(fb->p1_w1, fb->p1_w4, fb->p1d_w1, fb->p1d_w4, fb->p2, fb->p3, fb->p3f, fb->p3q, fb->p3s, fb->p3a, fb->p3b, fb->p3bf);
+  const hipError_t e = allow_lds(fb->p1_w1, fb->p1_w4, fb->p1d_w1, fb->p1d_w4, fb->p2, fb->p3, fb->p3f, fb->p3q, fb->p3s, fb->p3c, fb->p3a, fb->p3b, fb->p3bf);
   if (e != hipSuccess)
     return fb_fail(fb->ctx, DSPSR_AMD_EHIP, "dspsr_amd_filterbank_create: hipFuncSetAttribute: %s", hipGetErrorString(e));
   return DSPSR_AMD_OK;
@@ -386,12 +389,13 @@ static void fb_setup_two_pass(dspsr_amd_filterbank* fb)
   fb->p2r = {fb_pick_rinv(logMf, 0), 512, lds2r, 1};
   fb->p2rf = {fb_pick_rinv(logMf, 1), 512, pl.lds, 1};
   fb->p2rs = {fb_pick_rinv(logMf, 2), 512, lds2r, 1};
-  if (!(have1 && fb->p2r.kern && fb->p2rf.kern)) return;
+  fb->p2rc = {fb_pick_rinv(logMf, 4), 512, lds2r, 1};
+  if (!(have1 && fb->p2r.kern && fb->p2rf.kern && fb->p2rs.kern && fb->p2rc.kern)) return;
   g.logFb2 = lfb;
   g.logFa2 = lfa;
   fb->g1t.logFb2 = lfb; fb->g1t.logFa2 = lfa;
   fb->plan_cap2 = pl.cap;
-  if (e == hipSuccess) e = allow_lds(fb->p2r, fb->p2rf, fb->p2rs);
+  if (e == hipSuccess) e = allow_lds(fb->p2r, fb->p2rf, fb->p2rs, fb->p2rc);
   fb->two_pass = e == hipSuccess;
 }
 
@@ -971,7 +975,7 @@ struct FbPassKernels { FbPass<k1_t> p1, p1d; FbPass<k3_t> p3; FbPass<k3b_t> p3b;
 static FbPassKernels fb_pass_kernels(const dspsr_amd_filterbank* fb, const FbPass1& p1, const FbOut& out)
 {
   return {p1.raww == 1 ? fb->p1_w1 : fb->p1_w4, p1.raww == 1 ? fb->p1d_w1 : fb->p1d_w4,
-          out.kind == FB_OUT_FOLD ? (fb_state_square_law(out.state) ? fb->p3q : fb->p3f) : out.kind == FB_OUT_SEARCH ? fb->p3s : fb->rmatrix ? fb->p3m : fb->p3,
+          out.kind == FB_OUT_FOLD ? (fb_state_square_law(out.state) ? fb->p3q : fb->p3f) : out.kind == FB_OUT_SEARCH ? (out.state == DSPSR_AMD_COHERENCE ? fb->p3c : fb->p3s) : fb->rmatrix ? fb->p3m : fb->p3,
           out.kind == FB_OUT_SEGSUM ? fb->p3bf : fb->p3b};
 }
 
@@ -1127,7 +1131,7 @@ static int fb_run_two_pass(dspsr_amd_filterbank* fb, const FbIn& in, const FbOut
       fb_launch(fb, fb->p1t, (uint64_t)(Fb >> q.logT1) * 2 * nb, q, cr, fb->A, ctx->tw, part0, nb, 2u, 32u);
     }
     if (co.kind == FB_OUT_FOLD) return fb_launch_fused(fb, fb->p2rf, fb->A, kern, co, part0, nb, true);
-    fb_launch(fb, co.kind == FB_OUT_SEARCH ? fb->p2rs : fb->p2r, fb_inverse_items(co, tiles, nb), g, fb->A, kern, co, ctx->tw, part0, nb, nb);
+    fb_launch(fb, co.kind == FB_OUT_SEARCH ? (co.state == DSPSR_AMD_COHERENCE ? fb->p2rc : fb->p2rs) : fb->p2r, fb_inverse_items(co, tiles, nb), g, fb->A, kern, co, ctx->tw, part0, nb, nb);
     return DSPSR_AMD_OK;
   });
 }
@@ -1391,6 +1395,15 @@ static bool fb_search_fits(const dspsr_amd_filterbank* fb, uint32_t npo, uint32_
   const uint64_t floats = ((uint64_t)npo << g.logT3) * sf * G;
   if (floats > 2ull * fb->p3s.threads * PTS) return false;                       // (the buffer's padding is slack)
   if (((uint64_t)npo << g.logT3) > 4ull * fb->p3s.threads) return false;         // a thread reads at most four rows' carries (k_inv_chan TS_NPRE)
+  if (npo == 4) {
+    // the Coherence form (k_inv_chan<., 18 | 22, .>, k_rows_inv<., ., 4>): four floats per (channel, sample) in the tile two floats
+    // per (channel, polarisation, sample) came from, so `floats` above is the condition tscrunch * G <= freq_res; and the carries a
+    // thread pre-loads are TS_NPRE of ITS kernel -- four where the transform has one stage (freq_res <= 16: both fuse, freq_res 8
+    // is refused by the line above), two at freq_res 32 (two stages), one from freq_res 64 on
+    if (!fb->p3c.kern) return false;
+    const uint32_t npre = g.logM <= 4 ? 4 : g.logM == 5 ? 2 : 1;
+    if (((uint64_t)npo << g.logT3) > (uint64_t)npre * fb->p3c.threads) return false;
+  }
   if (((uint64_t)g.nkeep + sf) * sf >= (1ull << 32)) return false;       // t / sf by multiplication (ts_magic)
   if (G_out) *G_out = G;
   return true;
@@ -1399,6 +1412,19 @@ static bool fb_search_fits(const dspsr_amd_filterbank* fb, uint32_t npo, uint32_
 extern "C" int dspsr_amd_filterbank_search_is_fused(const dspsr_amd_filterbank* fb)
 {
   return fb && fb_search_fits(fb, 2, 1, nullptr) ? 1 : 0;
+}
+
+// rows per channel of a search-mode state (0: not one)
+static uint32_t fb_search_npol_out(int state)
+{
+  return state == DSPSR_AMD_INTENSITY ? 1u : state == DSPSR_AMD_PPQQ ? 2u : state == DSPSR_AMD_COHERENCE ? 4u : 0u;
+}
+
+extern "C" int dspsr_amd_filterbank_search_is_fused_state(const dspsr_amd_filterbank* fb, int out_state, uint32_t tscrunch)
+{
+  const uint32_t npo = fb_search_npol_out(out_state);
+  if (!fb || !npo || !tscrunch || (npo != 1 && fb->cfg.npol != 2)) return 0;
+  return fb_search_fits(fb, npo, tscrunch, nullptr) ? 1 : 0;
 }
 
 // Detection::square_law of a call at the filterbank's own rate (perform_detect, and the Detection of perform_fold's separate
@@ -1442,32 +1468,38 @@ extern "C" int dspsr_amd_filterbank_perform_search(dspsr_amd_filterbank* fb, con
 {
   if (!fb || (!in_f32_dev == !raw_dev) || !carry_count || !nout) return DSPSR_AMD_EINVAL;
   dspsr_amd_ctx* ctx = fb->ctx;
-  if (out_state != DSPSR_AMD_INTENSITY && out_state != DSPSR_AMD_PPQQ)
-    return fb_fail(ctx, DSPSR_AMD_EINVAL, "dspsr_amd_filterbank_perform_search: out_state=%d is neither Intensity nor PPQQ", out_state);
+  if (out_state == DSPSR_AMD_STOKES)
+    return fb_fail(ctx, DSPSR_AMD_EINVAL, "dspsr_amd_filterbank_perform_search: out_state=%d (Stokes) is not a search-mode state: Intensity, PPQQ "
+                   "or Coherence", out_state);
+  if (out_state != DSPSR_AMD_INTENSITY && out_state != DSPSR_AMD_PPQQ && out_state != DSPSR_AMD_COHERENCE)
+    return fb_fail(ctx, DSPSR_AMD_EINVAL, "dspsr_amd_filterbank_perform_search: out_state=%d is neither Intensity, PPQQ nor Coherence", out_state);
   if (out_state == DSPSR_AMD_PPQQ && fb->cfg.npol != 2)
     return fb_fail(ctx, DSPSR_AMD_EINVAL, "dspsr_amd_filterbank_perform_search: PPQQ needs two polarisations (npol=%u)", fb->cfg.npol);
+  if (out_state == DSPSR_AMD_COHERENCE && fb->cfg.npol != 2)
+    return fb_fail(ctx, DSPSR_AMD_EINVAL, "dspsr_amd_filterbank_perform_search: Coherence needs two polarisations (npol=%u)", fb->cfg.npol);
   if (!tscrunch) return fb_fail(ctx, DSPSR_AMD_EINVAL, "dsp::TScrunch::get_factor scrunch factor not set");
   if (*carry_count >= tscrunch)
     return fb_fail(ctx, DSPSR_AMD_EINVAL, "dspsr_amd_filterbank_perform_search: carry_count=%u must be < tscrunch=%u", *carry_count, tscrunch);
-  const uint32_t npo = out_state == DSPSR_AMD_PPQQ ? 2u : 1u, nkeep = fb_out_nkeep(fb);
+  const uint32_t npo = fb_search_npol_out(out_state), nkeep = fb_out_nkeep(fb);
   const uint64_t ndat = npart * nkeep, total = (uint64_t)*carry_count + ndat;
   if (total + tscrunch >= (1ull << 32))
     return fb_fail(ctx, DSPSR_AMD_EINVAL, "dspsr_amd_filterbank_perform_search: %llu parts x %u samples exceed the 32-bit sample index of a call",
                    (unsigned long long)npart, nkeep);
-  *nout = total / tscrunch;
+  const uint64_t no = total / tscrunch;                     // (*nout is written once the call is accepted: a refusal leaves it alone)
   const uint32_t rem = (uint32_t)(total % tscrunch);
-  if (!npart) return DSPSR_AMD_OK;
-  if ((!out_dev && *nout) || !carry_dev) return DSPSR_AMD_EINVAL;
+  if (!npart) { *nout = no; return DSPSR_AMD_OK; }
+  if ((!out_dev && no) || !carry_dev) return DSPSR_AMD_EINVAL;
   const uint64_t nchan_out = (uint64_t)fb->cfg.input_nchan * fb_out_C(fb);
-  if (!fb_rows_ok(*nout, nchan_out, npo, out_chan_stride, out_pol_stride, *nout, false))           // (FPT rows: channel-major only)
+  if (!fb_rows_ok(no, nchan_out, npo, out_chan_stride, out_pol_stride, no, false))           // (FPT rows: channel-major only)
     return fb_fail(ctx, DSPSR_AMD_EINVAL, "dspsr_amd_filterbank_perform_search: output rows of %llu floats overlap (chan stride %llu, pol "
-                   "stride %llu)", (unsigned long long)*nout, (unsigned long long)out_chan_stride, (unsigned long long)out_pol_stride);
+                   "stride %llu)", (unsigned long long)no, (unsigned long long)out_chan_stride, (unsigned long long)out_pol_stride);
   FbIn in;
   int rc = fb_input(fb, "dspsr_amd_filterbank_perform_search", in_f32_dev, in_pol_stride, in_step, raw_dev, raw_layout, scale, &in);
   if (rc != DSPSR_AMD_OK) return rc;
+  *nout = no;
   uint32_t G = 0;
   if (fb_search_fits(fb, npo, tscrunch, &G)) {
-    // Filterbank + Detection::square_law + TScrunch in one launch group: the detected stream never reaches HBM
+    // Filterbank + Detection (square_law, or the Coherence products) + TScrunch in one launch group: the detected stream never reaches HBM
     const FbOut out = fb_out_search(out_dev, out_chan_stride, out_pol_stride, out_state, tscrunch, *carry_count, G, carry_dev);
     rc = fb_run(fb, in, out, npart, in_chan_stride);
     if (rc != DSPSR_AMD_OK) return rc;
@@ -1477,6 +1509,16 @@ extern "C" int dspsr_amd_filterbank_perform_search(dspsr_amd_filterbank* fb, con
   // Other geometries (freq_res > 8192, freq_res with an odd factor, tiles the staged samples do not fit): the three operations one
   // after the other on a block owned by the object -- complex rows [chan][pol], detected rows behind them
   const uint64_t crow = 2 * ndat, drow = ndat;
+  if (out_state == DSPSR_AMD_COHERENCE) {
+    // the four products as Detection writes them with ndim 1 (rows [chan][4] of ndat floats, in the object's block), then TScrunch
+    const size_t need4 = (size_t)nchan_out * 4 * drow;
+    if (!grow_device_buffer(ctx->stream, fb->det, fb->det_floats, need4))
+      return fb_fail(ctx, DSPSR_AMD_ENOMEM, "dspsr_amd_filterbank_perform_search: hipMalloc of %zu bytes failed", need4 * sizeof(float));
+    rc = fb_run(fb, in, fb_out_detected(fb->det, 4 * drow, drow, DSPSR_AMD_COHERENCE, 1), npart, in_chan_stride);
+    if (rc != DSPSR_AMD_OK) return rc;
+    return dspsr_amd_tscrunch_fpt(ctx, fb->det, 4 * drow, drow, out_dev, out_chan_stride, out_pol_stride, (uint32_t)nchan_out, 4, 1, ndat,
+                                  tscrunch, carry_dev, carry_count, nout);
+  }
   const size_t need = (size_t)nchan_out * (fb->cfg.npol * crow + npo * drow);
   if (!grow_device_buffer(ctx->stream, fb->det, fb->det_floats, need))
     return fb_fail(ctx, DSPSR_AMD_ENOMEM, "dspsr_amd_filterbank_perform_search: hipMalloc of %zu bytes failed", need * sizeof(float));

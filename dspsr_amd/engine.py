@@ -402,14 +402,16 @@ class FilterbankEngine(_Owned):
     def perform_search(self, out, carry, carry_count, npart, tscrunch, state=_lib.INTENSITY, inp=None, in_step=0, raw=None,
                        layout=_lib.RAW_GENERIC, scale=1.0):
         """digifil's convolving branch in one launch group (LoadToFil.C:185-222,250-304): Filterbank -> Detection::square_law
-        (Intensity / PPQQ) -> TScrunch on the detected stream.  out: device float32 rows [nchan][npol_out][>= nout]; carry:
+        (Intensity / PPQQ), or Detection of the four Coherence products PP, QQ, Re PQ*, Im PQ* (state COHERENCE: digifits -p 4,
+        digifil -d 4) -> TScrunch on the detected stream.  out: device float32 rows [nchan][npol_out][>= nout]; carry:
         device float32 [nchan][npol_out] (the open output sample's partial sums); carry_count: samples already in it.
-        Returns (nout, carry_count_after)."""
+        npol_out is 1, 2 or 4.  Returns (nout, carry_count_after).  search_fuses(state, tscrunch) tells whether the call runs
+        inside the inverse pass."""
         rows = self._unpacked_heaps(raw, layout, scale, npart)
         if rows is not None:
             inp, in_step, raw = rows[0], rows[1], None
         ocs, ops = _strides3(out)
-        npo = 2 if state == _lib.PPQQ else 1
+        npo = 4 if state == _lib.COHERENCE else 2 if state == _lib.PPQQ else 1
         if out.shape[1] != npo or carry.numel() < out.shape[0] * npo:
             raise DspsrAmdError("dspsr_amd.FilterbankEngine.perform_search: out needs %d polarisation rows per channel and carry "
                                 "[nchan][%d] floats" % (npo, npo))
@@ -433,6 +435,12 @@ class FilterbankEngine(_Owned):
     def search_is_fused(self) -> bool:
         """perform_search runs detection and the time scrunch inside the inverse pass (else: separate launches, same numbers)."""
         return bool(lib.dspsr_amd_filterbank_search_is_fused(self.handle))
+
+    def search_fuses(self, state, tscrunch) -> bool:
+        """perform_search(state, tscrunch) runs inside the inverse pass.  False: separate launches on the object's own block,
+        the same numbers -- for COHERENCE wherever tscrunch * G > freq_res (G = ((nkeep + 2 tscrunch - 2) // tscrunch) | 1),
+        and for a state that is not a search-mode one."""
+        return bool(lib.dspsr_amd_filterbank_search_is_fused_state(self.handle, int(state), int(tscrunch)))
 
     def npass(self, raw_input: bool = True) -> int:
         """Transform passes of a call: 2 (short responses on the 8-bit block), 3, or 4 (two-pass inverse)."""

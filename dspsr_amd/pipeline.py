@@ -2335,6 +2335,8 @@ class SearchConfig:
     dedisperse: bool = False          # -K  remove the inter-channel dispersion delays (dsp::SampleDelay, LoadToFil.C:236-247)
     max_parts: int = 32               # parts per launch group
     fused: bool = True                # detection + time scrunch inside the inverse pass where the geometry allows it
+    fuse_coherence: bool = False      # ... also for the four Coherence products (npol 4): one perform_search per block in place of
+                                      #     perform_detect + TScrunch, the same bytes (not a reference option; off by default)
 
 
 def write_sigproc_header(f, *, source_name="unknown", rawdatafile="unknown", machine_id=0, telescope_id=0, src_raj=0.0, src_dej=0.0,
@@ -2414,7 +2416,8 @@ def _of(part, name):
 # refusal, no device), opens on the context its owner gives it, and writes its rows into a buffer of its own or, where the owner
 # hands a destination in, there.  An output stage turns those rows into what a format takes.  A driver is one of each on one shell.
 
-FRONT_OPTIONS = ("nchan", "tscrunch", "fscrunch", "npol", "dedisperse", "dispersion_measure", "freq_res", "parts_per_block", "max_parts", "fused")
+FRONT_OPTIONS = ("nchan", "tscrunch", "fscrunch", "npol", "dedisperse", "dispersion_measure", "freq_res", "parts_per_block", "max_parts", "fused",
+                 "fuse_coherence")
 
 
 class SearchFront:
@@ -2542,8 +2545,10 @@ class ConvolvingFront(SearchFront):
         return cfg.nchan, self.fb_rate, start, scale, None
 
     def _one_pass(self):
-        """the fused launch group holds the two square-law states, not the four Coherence products (those: perform_detect with ndim 1)"""
-        return self.cfg.fused and self.cfg.npol != 4
+        """the fused launch group holds the two square-law states; the four Coherence products only where the caller asks for it
+        (fuse_coherence: perform_search with COHERENCE -- the engine fuses where the staged tile fits and runs the operations one after
+        the other elsewhere, the same numbers), else perform_detect with ndim 1"""
+        return self.cfg.fused and (self.cfg.npol != 4 or self.cfg.fuse_coherence)
 
     def channel_delays(self, dispersion_measure, nchan, rate):
         """the -K delays of `nchan` channels of this filterbank's output at `rate` (Observation.C:80-87; Filterbank.C:358-364)"""
@@ -2583,7 +2588,7 @@ class ConvolvingFront(SearchFront):
 class ChannelisedFront(SearchFront):
     """No -F, on an already channelised complex 8-bit file (LoadToFil.C:233-304): Detection (Intensity / PPQQ / Coherence with
     ndim 1) -> [FScrunch] -> [TScrunch].  The block is detected and time-scrunched in ONE pass (dspsr_amd.detect_raw): the float
-    voltages are never written.  The channels are those of the file: nchan, freq_res, max_parts and fused are IGNORED;
+    voltages are never written.  The channels are those of the file: nchan, freq_res, max_parts, fused and fuse_coherence are IGNORED;
     parts_per_block is the largest number of time samples one call may bring.  A call takes n time samples in DADA order
     [n][nchan][npol][2] int8: any n up to parts_per_block, 0 included; no n: parts_per_block."""
 
@@ -2851,6 +2856,8 @@ class FitsConfig:
     parts_per_block: int = 64         # -F: parts (FFT blocks) per call; no -F: the most time samples per call
     max_parts: int = 32               # parts per launch group
     fused: bool = True                # detection + time scrunch inside the inverse pass where the geometry allows it
+    fuse_coherence: bool = False      # ... also for the four Coherence products (npol 4): one perform_search per block in place of
+                                      #     perform_detect + TScrunch, the same bytes (not a reference option; off by default)
 
 
 def _c_round(x):
@@ -3002,7 +3009,8 @@ class LoadToFITS(_SearchDriver):
                 if cfg.freq_res:
                     freq_res = cfg.freq_res * matched_response(info, dm, 0, cfg.nchan, input_nchan=info.nchan, ndim=info.ndim).minimum_ndat
         self.front = front_end(info, nchan=cfg.nchan, dispersion_measure=dm, freq_res=freq_res, tscrunch=self.tres_factor, fscrunch=0,
-                               npol=cfg.npol, dedisperse=False, parts_per_block=cfg.parts_per_block, max_parts=cfg.max_parts, fused=cfg.fused)
+                               npol=cfg.npol, dedisperse=False, parts_per_block=cfg.parts_per_block, max_parts=cfg.max_parts, fused=cfg.fused,
+                               fuse_coherence=cfg.fuse_coherence)
         self.out = FitsOutput(cfg, info, self.front, self.nblock)
 
     def _open(self):

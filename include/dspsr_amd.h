@@ -294,7 +294,9 @@ int dspsr_amd_filterbank_perform_fold(dspsr_amd_filterbank* fb, const float* in_
  * written at the filterbank's output rate.  The npart * nkeep detected samples of every channel continue a STREAM: TScrunch's
  * input buffering re-presents the ndat % tscrunch left-over samples in front of the next block (TScrunch.C:110-111); here the
  * partial sum of those samples stays in carry_dev -- the same sequential sum, out = in[0]; out += in[1]; ... , bit for bit.
- *   out_state       DSPSR_AMD_INTENSITY (npol_out 1) | DSPSR_AMD_PPQQ (npol_out 2)
+ *   out_state       DSPSR_AMD_INTENSITY (npol_out 1) | DSPSR_AMD_PPQQ (npol_out 2) | DSPSR_AMD_COHERENCE (npol_out 4: rows PP, QQ,
+ *                   Re PQ*, Im PQ* -- digifits -p 4, digifil -d 4; cross_detect.ic:23-43 as perform_detect(COHERENCE, ndim 1) rounds
+ *                   them).  PPQQ and Coherence need two polarisations; DSPSR_AMD_STOKES is refused by name (DSPSR_AMD_EINVAL)
  *   out_dev         rows [chan][npol_out] of *nout floats, FPT order like the reference's TimeSeries: any float-aligned address,
  *                   out_pol_stride >= *nout and out_chan_stride >= (npol_out-1)*out_pol_stride + *nout (else DSPSR_AMD_EINVAL,
  *                   nothing launched); only the *nout complete samples of a row are written -- the open one goes to carry_dev
@@ -302,7 +304,12 @@ int dspsr_amd_filterbank_perform_fold(dspsr_amd_filterbank* fb, const float* in_
  *   carry_count     in: samples already summed into carry_dev (< tscrunch); out: samples left over by this call
  *   nout            out: complete output samples written per row = (carry_in + npart * nkeep) / tscrunch
  * tscrunch = 1 writes the detected samples themselves.  Three-pass and two-pass geometries run it inside the inverse pass; the
- * others (freq_res > 8192, odd factors) through an internal detected block + dspsr_amd_tscrunch_fpt -- the same numbers. */
+ * others (freq_res > 8192, odd factors, matrix response) through an internal detected block + dspsr_amd_tscrunch_fpt -- the same
+ * numbers.  Coherence stages four floats per (channel, sample) in the tile the complex samples came from, so it runs inside the
+ * inverse pass only where, besides, tscrunch * G <= freq_res with G = ((nkeep + 2 * tscrunch - 2) / tscrunch) | 1 (roughly
+ * nfilt_pos + nfilt_neg >= 3 * tscrunch) and freq_res >= 16; elsewhere the object runs perform_detect(COHERENCE, ndim 1) into its
+ * own block and dspsr_amd_tscrunch_fpt (npol 4, ndim 1) behind it: the same numbers, *nout and *carry_count.
+ * dspsr_amd_filterbank_search_is_fused_state tells which. */
 #define DSPSR_AMD_INTENSITY 2
 #define DSPSR_AMD_PPQQ 3
 int dspsr_amd_filterbank_perform_search(dspsr_amd_filterbank* fb, const float* in_f32_dev, uint64_t in_chan_stride,
@@ -312,6 +319,10 @@ int dspsr_amd_filterbank_perform_search(dspsr_amd_filterbank* fb, const float* i
                                         uint64_t* nout);
 /* 1: dspsr_amd_filterbank_perform_search runs inside the inverse pass for this object; 0: through the internal detected block */
 int dspsr_amd_filterbank_search_is_fused(const dspsr_amd_filterbank* fb);
+/* 1: dspsr_amd_filterbank_perform_search(out_state, tscrunch) runs inside the inverse pass for this object; 0: through the internal
+ * detected block, and for a null object, an unknown state (Stokes included), tscrunch 0, or a state the object's polarisations do
+ * not give.  (dspsr_amd_filterbank_search_is_fused above is this query for PPQQ at a factor of 1, without the polarisation test.) */
+int dspsr_amd_filterbank_search_is_fused_state(const dspsr_amd_filterbank* fb, int out_state, uint32_t tscrunch);
 /* dsp::TScrunch::fpt_tscrunch (TScrunch.C:148-178; TScrunch::Engine::fpt_tscrunch, dsp/TScrunch.h:61-69, CUDA twin TScrunchCUDA.cu:
  * 204-300: ndim 1 or 2) on device rows [nchan][npol] of ndat_in samples of ndim floats each, every dimension on its own, as a stream:
  * carry / carry_count / nout as above.  Out of place only (digifil scrunches in place on the host, LoadToFil.C:296-304: here every

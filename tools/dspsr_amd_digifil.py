@@ -4,6 +4,7 @@ spellings (digifil.C:78-131) -- a thin driver over pipeline.LoadToFilDirect for 
 re-implementation of the digifil application.
 
   dspsr_amd_digifil.py file.dada [-b nbit] [-t T] [-f F] [-d npol] [-K [-D dm]] [-I secs] [-c] [-s fac] [-B MB] [-o out.fil]
+                       [--fuse-coherence]
 
 The file must be channelised complex voltages (NCHAN >= 1, NDIM 2, NBIT 8): there is no -F here, the channels of the output
 are those of the file (LoadToFil.C:233-234).  The blocks are read with dspsr_amd.dada, copied to the device, and the packed
@@ -30,6 +31,9 @@ def parse_args(argv=None):
     ap.add_argument("-s", dest="scale_fac", type=float, default=1.0, help="data scale factor to apply")
     ap.add_argument("-o", dest="output", default=None, help="output filename")
     ap.add_argument("--cuda", dest="device", type=int, default=0, help="device id (the reference's spelling)")
+    ap.add_argument("--fuse-coherence", dest="fuse_coherence", action="store_true",
+                    help="-d 4 behind a convolving filterbank: detection and time scrunch inside the inverse pass (not a reference "
+                         "spelling; SearchConfig.fuse_coherence -- this driver has no -F, its one-pass front end ignores it)")
     return ap.parse_args(argv)
 
 
@@ -43,7 +47,8 @@ def search_config(a, info, extras):
     ndat = max(1, int(a.block_mb * 1024 * 1024) // per_sample)
     return pipeline.SearchConfig(nchan=info.nchan, tscrunch=max(1, a.tscrunch), nbit=a.nbit, rescale_seconds=a.rescale_seconds,
                                  rescale_constant=a.constant, scale_fac=a.scale_fac, parts_per_block=ndat,
-                                 dispersion_measure=float(dm or 0.0), fscrunch=a.fscrunch, npol=a.npol, dedisperse=a.dedisperse)
+                                 dispersion_measure=float(dm or 0.0), fscrunch=a.fscrunch, npol=a.npol, dedisperse=a.dedisperse,
+                                 fuse_coherence=a.fuse_coherence)
 
 
 def write_header(f, lt, info, rawdatafile):

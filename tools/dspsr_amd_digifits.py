@@ -41,6 +41,9 @@ def parse_args(argv=None):
     ap.add_argument("-o", dest="output", default=None, help="output filename")
     ap.add_argument("--cuda", dest="device", type=int, default=0, help="device id (the reference's spelling)")
     ap.add_argument("--parts", dest="parts_per_block", type=int, default=0, help="parts (-F) or time samples (no -F) per call")
+    ap.add_argument("--fuse-coherence", dest="fuse_coherence", action="store_true",
+                    help="-F with -p 4: detection and time scrunch inside the inverse pass where the tile fits (not a reference spelling; "
+                         "the same bytes)")
     return ap.parse_args(argv)
 
 
@@ -59,7 +62,7 @@ def fits_config(a, extras):
     return pipeline.FitsConfig(nchan=nchan, convolve=convolve, freq_res=a.freq_res, dispersion_measure=float(dm or 0.0),
                                coherent_dedisp=a.coherent_dedisp, tsamp=a.tsamp, npol=a.npol, nbit=a.nbit, nsblk=a.nsblk,
                                rescale_seconds=a.rescale_seconds, rescale_constant=a.constant, dedisperse=a.dedisperse,
-                               integration_length=a.integration_length, **kw)
+                               integration_length=a.integration_length, fuse_coherence=a.fuse_coherence, **kw)
 
 
 def main(argv=None):

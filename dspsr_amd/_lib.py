@@ -16,6 +16,7 @@ H2D, D2H, D2D = 1, 2, 3
 RAW_GENERIC, RAW_CASPSR, RAW_UWB16 = 0, 1, 2
 RAW_MEERKAT, RAW_MEERKAT_SWAP = 3, 4      # heaps of 256 samples per (pol, chan) run; _SWAP: odd and even samples exchanged (MKBFRo)
 RAW_TWOBIT = 5                            # two-bit real samples, whole excision windows (FilterbankEngine.set_twobit; not a C-ABI layout)
+RAW_GUPPI = 6                             # GUPPI / PUPPI raw blocks, channel-major runs (FilterbankEngine.set_guppi; not a C-ABI layout)
 HEAP_NSAMP = 256
 HEAP_MACHINES = {"MKBF": RAW_MEERKAT, "MKBFRo": RAW_MEERKAT_SWAP}   # INSTRUMENT -> layout (kat/MeerKATUnpacker.C: sample_swap 2 for MKBFRo)
 TWOBIT_OFFSET_BINARY, TWOBIT_SIGN_MAGNITUDE, TWOBIT_TWOS_COMPLEMENT = 0, 1, 2      # DSPSR_AMD_TWOBIT_*: TwoBitTable's code map
@@ -52,6 +53,24 @@ def is_twobit(layout: int) -> bool:
     return layout >= 0 and (layout & 0xff) == RAW_TWOBIT
 
 
+def guppi_at(first_sample: int) -> int:
+    """The layout word of a block of GUPPI raw blocks whose first sample lies at `first_sample` of the runs of its first block (as
+    raw_at for heaps; RAW_GUPPI is a form of the Python engine alone: FilterbankEngine unpacks it and calls the float entry points)."""
+    if first_sample < 0:
+        raise ValueError("guppi_at: first_sample %d is negative" % first_sample)
+    return RAW_GUPPI | (first_sample << 8)
+
+
+def is_guppi(layout: int) -> bool:
+    return layout >= 0 and (layout & 0xff) == RAW_GUPPI
+
+
+def guppi_block_bytes(first_sample: int, nsamp: int, nchan: int, npol: int, block_nsamp: int, chan_stride: int, block_stride: int) -> int:
+    """Bytes from the data section of the block that holds the first sample to the last kept sample of the last block's last run."""
+    nblk = -(-(first_sample + nsamp) // block_nsamp)
+    return (nblk - 1) * block_stride + (nchan - 1) * chan_stride + block_nsamp * 2 * npol if nsamp > 0 else 0
+
+
 def heap_block_bytes(first_sample: int, nsamp: int, nchan: int, npol: int) -> int:
     """Bytes of the whole heaps that hold `nsamp` samples from `first_sample` of the first heap on."""
     return -(-(first_sample + nsamp) // HEAP_NSAMP) * npol * nchan * HEAP_NSAMP * 2
@@ -62,6 +81,11 @@ class FilterbankConfig(C.Structure):
                 ("nfilt_neg", C.c_uint32), ("input_nchan", C.c_uint32), ("npol", C.c_uint32),
                 ("real_input", C.c_uint32), ("max_parts", C.c_uint32), ("force_four_pass", C.c_uint32),
                 ("fused_fold", C.c_uint32), ("split_in_inverse", C.c_uint32)]
+
+
+class GuppiLayout(C.Structure):
+    _fields_ = [("nchan", C.c_uint32), ("npol", C.c_uint32), ("block_nsamp", C.c_uint32), ("first", C.c_uint32),
+                ("chan_stride", C.c_uint64), ("block_stride", C.c_uint64)]
 
 
 class TfpConfig(C.Structure):
@@ -143,6 +167,7 @@ SYMBOLS = {
     "dspsr_amd_detect_square_law": (_i, [_vp, _i, _vp, _u64, _u64, _vp, _u64, _u64, _u32, _u32, _u64]),
     "dspsr_amd_unpack_fpt": (_i, [_vp, _vp, _f, _u32, _u32, _u32, _u64, _vp, _u64, _u64]),
     "dspsr_amd_unpack_heaps_fpt": (_i, [_vp, _vp, _i, _f, _u32, _u32, _u64, _vp, _u64, _u64]),
+    "dspsr_amd_unpack_guppi_fpt": (_i, [_vp, _vp, C.POINTER(GuppiLayout), _u64, _vp, _u64, _u64]),
     "dspsr_amd_twobit_check": (_i, [_u64, _i, _u32, _u32, _u32, _u64, _u32, _u32, _u64, _u64, C.c_char_p, _sz]),
     "dspsr_amd_twobit_unpack": (_i, [_vp, _vp, _i, _u32, _u32, _u32, _u64, _u32, _u32, _vp, _vp, _u64, _vp, _vp]),
     "dspsr_amd_detect_raw": (_i, [_vp, _vp, _f, _u32, _u32, _u64, _i, _u32, _vp, _u64, _u64, _vp, C.POINTER(_u32), C.POINTER(_u64)]),

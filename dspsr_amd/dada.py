@@ -376,8 +376,9 @@ def fold_file(path, cfg, polyco=None, device=0, stream=None, reference_phase=0.0
     """The reference's `dspsr file.dada -F nchan:D ...` on one GPU: open the file, build the pipeline from its header,
     feed every block, close the last sub-integration.  Returns the LoadToFold (its .subints hold the results -- with several
     `targets` (pipeline.FoldTarget), .pulsars[k].subints; the caller closes it)."""
+    from .guppi import open_input
     from .pipeline import LoadToFold
-    f = DadaFile(path)
+    f = open_input(path)                                     # a DadaFile, or a guppi.GuppiFile where the file is GUPPI raw
     lt = LoadToFold(cfg, f.info, device=device, stream=stream, polyco=polyco, reference_phase=reference_phase,
                     dump_before=dump_before, dump_dir=dump_dir, targets=targets)
     if cfg.zap_rfi:
@@ -404,8 +405,9 @@ def search_blocks_file(path, cfg, device=0, stream=None, log=None):
     Returns (header_values, [(bytes, DAT_SCL, DAT_OFFS) on the host, ...]): what pipeline.write_search_blocks takes.  `log`: where the
     reference's `requested tsamp / actual tsamp` line goes."""
     import torch
+    from .guppi import open_input
     from .pipeline import LoadToFITS
-    f = DadaFile(path)
+    f = open_input(path)
     lt = LoadToFITS(cfg, f.info, device=device, stream=stream)
     if log is not None:
         print("digifits: requested tsamp=%g rate=%g\n             actual tsamp=%g (tscrunch=%d)" % (cfg.tsamp, f.info.rate, lt.tsamp, lt.tres_factor),

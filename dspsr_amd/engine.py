@@ -215,6 +215,8 @@ class FilterbankEngine(_Owned):
         self.fuse_heaps = bool(fuse_heaps)
         self._heap_rows = None      # float rows of an unpacked block of heaps: allocated by the first call that needs them
         self._twobit = None         # set_twobit: how a RAW_TWOBIT block is unpacked
+        self._guppi = None          # set_guppi: (block_nsamp, chan_stride, block_stride) of a RAW_GUPPI block
+        self._guppi_rows = None
         a, b, c, d = C.c_uint64(), C.c_uint64(), C.c_uint64(), C.c_uint32()
         lib.dspsr_amd_filterbank_sizes(h, C.byref(a), C.byref(b), C.byref(c), C.byref(d))
         self.nsamp_fft, self.nsamp_overlap, self.nsamp_step, self.nkeep = a.value, b.value, c.value, d.value
@@ -258,6 +260,9 @@ class FilterbankEngine(_Owned):
         if _lib.is_heaps(layout):
             # whole heaps from the one that holds the call's first sample on
             return _lib.heap_block_bytes(layout >> 8, nsamp, c.input_nchan, c.npol)
+        if _lib.is_guppi(layout):
+            # from the data section of the block that holds the call's first sample to the last kept sample of the last run
+            return _lib.guppi_block_bytes(layout >> 8, nsamp, c.input_nchan, c.npol, *self._guppi_geometry())
         if layout == _lib.RAW_CASPSR:
             # 4 samples of pol0 then 4 of pol1: the block must hold WHOLE 8-byte groups (its last samples' pol1 bytes lie
             # up to 4 bytes behind their pol0 bytes; CASPSRUnpacker.C:132-187 unpacks group by group)
@@ -272,9 +277,13 @@ class FilterbankEngine(_Owned):
         """A block of heaps this object does not read itself (or fuse_heaps=False), unpacked into float rows owned by the engine:
         (rows [input_nchan][npol][2 * nsamp], in_step), or None when the block goes to the library as it is.  The rows are
         allocated on first use for max_parts parts (a longer call allocates again).  A RAW_TWOBIT block (set_twobit) takes the same
-        way through unpack_twobit; its weights stay in self.twobit_weights."""
+        way through unpack_twobit; its weights stay in self.twobit_weights.  A RAW_GUPPI block (set_guppi) is unpacked by
+        unpack_guppi_fpt into rows of its own, allocated the same way; `scale` is IGNORED for it: the format's value is float(int8)
+        (GUPPIUnpacker.C:74-80)."""
         if raw is not None and _lib.is_twobit(layout):
             return self.unpack_twobit(raw, layout >> 8, npart)[:2]
+        if raw is not None and _lib.is_guppi(layout):
+            return self.unpack_guppi(raw, layout >> 8, npart)
         if raw is None or not _lib.is_heaps(layout) or (self.fuse_heaps and self.takes_heaps()):
             return None
         import torch
@@ -290,6 +299,47 @@ class FilterbankEngine(_Owned):
             unpack_heaps_fpt(self.ctx, raw, self._heap_rows, c.input_nchan, c.npol, layout, scale,
                              ndat=npart * self.nsamp_step + self.nsamp_overlap)
         return self._heap_rows, 2 * self.nsamp_step
+
+    def set_guppi(self, block_nsamp, chan_stride, block_stride):
+        """The GUPPI form of the raw entry points (layout RAW_GUPPI / guppi_at(first), next to the heap and two-bit forms): the
+        geometry of the raw blocks a RAW_GUPPI block is made of -- kept samples per run, bytes from a run to the next one of the
+        block, bytes from a block's data section to the next one's (dspsr_amd_guppi_layout).  nchan and npol are the object's
+        input_nchan and npol; complex samples.  The `scale` of the raw entry points is ignored for this layout."""
+        c = self.cfg
+        if c.real_input:
+            raise DspsrAmdError("dspsr_amd.FilterbankEngine.set_guppi: GUPPI raw blocks are complex samples; the object was set up for real input")
+        block_nsamp, chan_stride, block_stride = int(block_nsamp), int(chan_stride), int(block_stride)
+        sb = 2 * c.npol
+        if block_nsamp < 1 or chan_stride < block_nsamp * sb or chan_stride % sb or block_stride % sb:
+            raise DspsrAmdError("dspsr_amd.FilterbankEngine.set_guppi: block_nsamp=%d chan_stride=%d block_stride=%d contradict npol=%d "
+                                "(chan_stride >= block_nsamp * 2 * npol, strides multiples of 2 * npol)" % (block_nsamp, chan_stride, block_stride, c.npol))
+        if c.input_nchan > 1 and block_stride < (c.input_nchan - 1) * chan_stride + block_nsamp * sb:
+            raise DspsrAmdError("dspsr_amd.FilterbankEngine.set_guppi: block_stride=%d is shorter than the %d runs of input_nchan=%d "
+                                "(chan_stride=%d)" % (block_stride, c.input_nchan, c.input_nchan, chan_stride))
+        self._guppi = (block_nsamp, chan_stride, block_stride)
+        self._guppi_rows = None
+
+    def _guppi_geometry(self):
+        if getattr(self, "_guppi", None) is None:
+            raise DspsrAmdError("dspsr_amd.FilterbankEngine: a RAW_GUPPI block needs set_guppi() first")
+        return self._guppi
+
+    def unpack_guppi(self, raw, first_sample, npart):
+        """A RAW_GUPPI block (the data sections from the one that holds the call's first sample on, `first_sample` inside its runs)
+        unpacked into float rows owned by the engine: (rows [input_nchan][npol][2 * nsamp], in_step = 2 * nsamp_step) for the float
+        entry points.  The rows are allocated on first use for max_parts parts (a longer call allocates again), 16-byte aligned."""
+        import torch
+        geom = self._guppi_geometry()
+        c = self.cfg
+        parts = max(npart, self.max_parts)
+        need = 2 * (parts * self.nsamp_step + self.nsamp_overlap)
+        need += (-need) % 4                         # every row starts on a 16-byte boundary: float4 stores
+        if self._guppi_rows is None or self._guppi_rows.shape[2] < need or self._guppi_rows.device != raw.device:
+            self._guppi_rows = torch.empty((c.input_nchan, c.npol, need), dtype=torch.float32, device=raw.device)
+        if npart:
+            unpack_guppi_fpt(self.ctx, raw, self._guppi_rows, _lib.GuppiLayout(c.input_nchan, c.npol, geom[0], first_sample, geom[1], geom[2]),
+                             npart * self.nsamp_step + self.nsamp_overlap)
+        return self._guppi_rows, 2 * self.nsamp_step
 
     def set_twobit(self, nsample, nlow_min, nlow_max, levels, table_type=_lib.TWOBIT_OFFSET_BINARY):
         """The two-bit form of the raw entry points (layout RAW_TWOBIT, next to the heap form): how a two-bit block is unpacked --
@@ -565,6 +615,26 @@ def unpack_heaps_fpt(ctx: Context, raw, out, nchan, npol, layout, scale=1.0, nda
     _check(ctx.handle, lib.dspsr_amd_unpack_heaps_fpt(ctx.handle, raw.data_ptr(), layout, scale, nchan, npol, ndat, out.data_ptr(), ocs, ops),
            "dspsr_amd_unpack_heaps_fpt")
     return out
+
+
+def unpack_guppi_fpt(ctx: Context, raw, rows, layout, ndat):
+    """dsp::GUPPIUnpacker and the un-transpose of GUPPIBlockFile::load_bytes on the device: raw = device int8, the data sections of
+    GUPPI raw blocks as they lie in the file, from the block that holds the first sample on; layout = _lib.GuppiLayout (nchan, npol,
+    block_nsamp, first, chan_stride, block_stride: dspsr_amd_guppi_layout); rows = float32 device rows [nchan][npol][>= 2 * ndat]
+    (strided views allowed) that receive stream samples first ... first + ndat - 1 as float(int8)."""
+    nchan, npol = layout.nchan, layout.npol
+    if ndat < 0:
+        raise DspsrAmdError("dspsr_amd.unpack_guppi_fpt: ndat=%d" % ndat)
+    if ndat and layout.block_nsamp and npol:
+        need = _lib.guppi_block_bytes(layout.first, ndat, nchan, npol, layout.block_nsamp, layout.chan_stride, layout.block_stride)
+        if raw.numel() * raw.element_size() < need:
+            raise DspsrAmdError("dspsr_amd.unpack_guppi_fpt: block holds %d bytes, %d needed" % (raw.numel() * raw.element_size(), need))
+    if tuple(rows.shape[:2]) != (nchan, npol) or rows.shape[2] < 2 * ndat:
+        raise DspsrAmdError("dspsr_amd.unpack_guppi_fpt: rows are %s, [%d][%d][>= %d] needed" % (tuple(rows.shape), nchan, npol, 2 * ndat))
+    ocs, ops = _strides3(rows)
+    _check(ctx.handle, lib.dspsr_amd_unpack_guppi_fpt(ctx.handle, raw.data_ptr(), C.byref(layout), ndat, rows.data_ptr(), ocs, ops),
+           "dspsr_amd_unpack_guppi_fpt")
+    return rows
 
 
 def twobit_block_bytes(first_sample, ndat, nsample, npol):

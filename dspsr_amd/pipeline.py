@@ -149,6 +149,7 @@ class InputInfo:
     source: str = "unknown"
     telescope: str = "unknown"
     nbit: int = 8                     # NBIT of the file (every path here reads 8-bit samples)
+    guppi: tuple | None = None        # a GUPPI raw file (dspsr_amd.guppi.GuppiFile): (block_nsamp, chan_stride, block_stride) of its blocks
 
     @property
     def rate(self):
@@ -778,6 +779,9 @@ class FilterbankThenConvolution:
         self.front.perform_raw(raw, layout, scale, self.channelised, ndat)
         return self.channelised
 
+    def set_guppi(self, *geometry):
+        self.front.set_guppi(*geometry)                     # (the engine that reads the 8-bit block)
+
     def perform_raw(self, raw, layout, scale, out, npart, out_step=None):
         if self.conv is None:
             return self.front.perform_raw(raw, layout, scale, out, npart, out_step)
@@ -844,6 +848,9 @@ class ConvolutionThenFilterbank:
             self.dedispersed = _device_empty(self.ctx, (self.in_nchan, self.npol, 2 * n))
         self.conv.perform_raw(raw, layout, scale, self.dedispersed, ncv)
         return self.dedispersed, ndat // self.nsub
+
+    def set_guppi(self, *geometry):
+        self.conv.set_guppi(*geometry)                      # (the engine that reads the 8-bit block)
 
     def perform_raw(self, raw, layout, scale, out, npart, out_step=None):
         x, nfb = self._front(raw, layout, scale, npart)
@@ -1000,6 +1007,7 @@ def plfb_check(cfg: "Config", info: "InputInfo", ntargets=0, subband=None, dump_
 def rfi_check(cfg: "Config", info: "InputInfo", subband=None):
     """What a -R run refuses, before any device resource is opened."""
     who = "dspsr_amd.LoadToFold: the RFI filter (-R)"
+    refuse_guppi(who, info, "the Bandpass operator's integrate_raw reads the generic and CASPSR byte orders")
     if cfg.calibrator is not None:
         raise DspsrAmdError("%s with -pac (calibrator) is not built: the product of the mask, the chirp and a matrix response is open" % who)
     if info.nchan > 1:
@@ -1234,10 +1242,20 @@ def refuse_heaps(who, info, instead):
                             "built on this path; %s" % (who, info.machine, instead))
 
 
-def raw_block_bytes(layout, nsamp, nchan, npol, ndim, first_sample=0):
-    """Bytes of a block of `nsamp` samples in `layout` (heaps: from `first_sample` of the first heap on, whole heaps)."""
+def refuse_guppi(who, info, instead):
+    """Plan-time refusal of a driver that has no reader for GUPPI raw blocks."""
+    if getattr(info, "guppi", None) is not None:
+        raise DspsrAmdError("%s: the block order of a GUPPI raw file (BACKEND %s: time-ordered runs per channel inside every block) is not "
+                            "built on this path; %s" % (who, info.machine, instead))
+
+
+def raw_block_bytes(layout, nsamp, nchan, npol, ndim, first_sample=0, guppi=None):
+    """Bytes of a block of `nsamp` samples in `layout` (heaps: from `first_sample` of the first heap on, whole heaps; GUPPI raw
+    blocks of geometry `guppi`: from the data section that holds `first_sample` to the last kept sample of the last run)."""
     if _lib.is_heaps(layout):
         return _lib.heap_block_bytes(first_sample, nsamp, nchan, npol)
+    if _lib.is_guppi(layout):
+        return _lib.guppi_block_bytes(first_sample, nsamp, nchan, npol, *guppi)
     if first_sample:
         raise DspsrAmdError("dspsr_amd.pipeline: first_sample=%d given for a layout without heaps" % first_sample)
     if layout == _lib.RAW_CASPSR:
@@ -1251,6 +1269,13 @@ def _adopt_front(drv, fb):
     drv.nkeep, drv.nsamp_step, drv.nsamp_overlap = fb.nkeep, fb.nsamp_step, fb.nsamp_overlap
     drv.scale8 = eight_bit_scale()
     drv.layout = machine_layout(drv.info.machine)
+    drv.guppi = None
+    g = getattr(drv.info, "guppi", None)
+    if g is not None:
+        # a GUPPI raw file: the layout comes from the file, not from the machine; a sub-band rank reads one channel's runs
+        drv.guppi = (g[0], g[1], g[1] if getattr(drv, "subband", None) is not None else g[2])
+        drv.layout = _lib.RAW_GUPPI
+        fb.set_guppi(*drv.guppi)
 
 
 def _open_convolving_front(drv, r, nsub, in_nchan, kernel, **setup):
@@ -2028,7 +2053,7 @@ class LoadToFold:
         tb = getattr(self, "twobit", None)   # (the method is also borrowed by stand-ins that hold the geometry alone)
         if tb is not None:                   # whole excision windows from the one that holds the block's first sample
             return twobit_block_bytes(first_sample, nsamp, tb.nsample, self.info.npol)
-        return raw_block_bytes(self.layout, nsamp, self.in_nchan, self.info.npol, self.info.ndim, first_sample)
+        return raw_block_bytes(self.layout, nsamp, self.in_nchan, self.info.npol, self.info.ndim, first_sample, getattr(self, "guppi", None))
 
     def seek_block(self, k):
         """Time-slice replicas: the next block is block k of the stream (blocks of parts_per_block parts), not the one
@@ -2054,7 +2079,8 @@ class LoadToFold:
     def process_block(self, raw, npart=None, events=None, first_sample=0):
         """raw: device int8 tensor holding npart*nsamp_step + nsamp_overlap samples (the InputBuffering
         tail of the previous block already prepended, Filterbank.C:443-444).  A block of MeerKAT heaps holds the whole heaps
-        around those samples; first_sample: where in its first heap the block's first sample lies."""
+        around those samples; first_sample: where in its first heap the block's first sample lies.  A block of a GUPPI raw file
+        (info.guppi) holds the whole data sections around them; first_sample: where in the first one's runs that sample lies."""
         cfg = self.cfg
         npart = npart or cfg.parts_per_block
         if raw.numel() < self.block_bytes(npart, first_sample):
@@ -2062,6 +2088,8 @@ class LoadToFold:
                                 % (raw.numel(), self.block_bytes(npart, first_sample)))
         if _lib.is_heaps(self.layout):
             self.layout = _lib.raw_at(self.layout & 0xff, first_sample)      # the layout word of THIS block, for every path below
+        elif _lib.is_guppi(self.layout):
+            self.layout = _lib.guppi_at(first_sample)
         if cfg.zap_rfi and self.rfi_filter is None:
             raise DspsrAmdError("dspsr_amd.LoadToFold.process_block: zap_rfi (-R) is set and no filter has been given: "
                                 "call set_rfi_filter before the first block")
@@ -2258,7 +2286,7 @@ class LoadToFold:
             if item is None:
                 return None, None
             if isinstance(item, tuple):
-                return item[0], item[1:]                     # (npart,) or, for heaps, (npart, first_sample)
+                return item[0], item[1:]                     # (npart,) or, for heaps and GUPPI raw blocks, (npart, first_sample)
             return item, (npart,)
 
         def upload(k, host):
@@ -2568,11 +2596,13 @@ class ConvolvingFront(SearchFront):
 
     def block_bytes(self, npart=None, first_sample=0):
         nsamp = (npart or self.cfg.parts_per_block) * self.nsamp_step + self.nsamp_overlap
-        return raw_block_bytes(self.layout, nsamp, self.info.nchan, self.info.npol, self.info.ndim, first_sample)
+        return raw_block_bytes(self.layout, nsamp, self.info.nchan, self.info.npol, self.info.ndim, first_sample, getattr(self, "guppi", None))
 
     def _detect(self, raw, npart, first_sample, out, ts):
         if _lib.is_heaps(self.layout):
             self.layout = _lib.raw_at(self.layout & 0xff, first_sample)
+        elif _lib.is_guppi(self.layout):
+            self.layout = _lib.guppi_at(first_sample)
         block = dict(raw=raw, layout=self.layout, scale=self.scale8)
         if self.fused:
             return self.fb.perform_search(out, self.carry, self.carry_count, npart, ts, self.state, **block)
@@ -2606,6 +2636,7 @@ class ChannelisedFront(SearchFront):
         if info.machine == "CASPSR":
             raise DspsrAmdError("%s: the CASPSR byte order is not built on this path (generic DADA order only)" % who)
         refuse_heaps(who, info, "dspsr_amd.unpack_heaps_fpt gives the float rows, and -F N:D (dspsr_amd.LoadToFilCoherent) reads the heaps")
+        refuse_guppi(who, info, "dspsr_amd.unpack_guppi_fpt gives the float rows, and -F N:D (dspsr_amd.LoadToFilCoherent) reads the blocks")
         if cfg.npol not in (1, 2, 4):
             raise DspsrAmdError("%s: npol=%d (Intensity 1 / PPQQ 2 / Coherence 4 are built; NthPower 3 is not)" % (who, cfg.npol))
         if info.npol not in (1, 2):
@@ -2732,6 +2763,7 @@ class LoadToFil(_SearchDriver):
         cfg, info = self.cfg, self.info
         refuse_twobit("dspsr_amd.LoadToFil", info)
         refuse_heaps("dspsr_amd.LoadToFil", info, "channelised complex voltages take -F N:D (dspsr_amd.LoadToFilCoherent)")
+        refuse_guppi("dspsr_amd.LoadToFil", info, "channelised complex voltages take -F N:D (dspsr_amd.LoadToFilCoherent)")
         if info.npol != 2 or info.ndim != 1 or info.nchan != 1:
             raise DspsrAmdError("dspsr_amd.LoadToFil: 8-bit real dual-polarisation single-channel input only")
         if cfg.parts_per_block % cfg.tscrunch:

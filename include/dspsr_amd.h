@@ -369,6 +369,32 @@ int dspsr_amd_unpack_fpt(dspsr_amd_ctx* ctx, const int8_t* raw_dev, float scale,
  * (else DSPSR_AMD_EINVAL, nothing launched); nothing outside the 2 * ndat floats of a row is written.  ndat = 0: nothing to do. */
 int dspsr_amd_unpack_heaps_fpt(dspsr_amd_ctx* ctx, const int8_t* raw_dev, int raw_layout, float scale, uint32_t nchan, uint32_t npol,
                                uint64_t ndat, float* out_dev, uint64_t out_chan_stride, uint64_t out_pol_stride);
+/* dspsr_amd_unpack_guppi_fpt replaces dsp::GUPPIUnpacker AND the host un-transpose in front of it (GUPPIBlockFile::load_bytes,
+ * guppi/GUPPIBlockFile.C:214-234) on the device: GUPPI / PUPPI raw blocks, as they lie in the file, -> float FPT rows [nchan][npol]
+ * of ndat complex samples.  A block's data section is channel-major: run c holds the consecutive samples of channel c, 2 * npol
+ * bytes each ((re, im) of polarisation 0, then of polarisation 1, int8); only the first block_nsamp samples of a run are kept (the
+ * OVERLAP samples behind them repeat the next block).  raw_dev points at the data section of the block that holds the call's first
+ * sample, `first` says where in that block's runs the sample lies.  With u = first + t, stream sample t (0 <= t < ndat) of (chan c,
+ * pol p) is read at byte
+ *     (u / block_nsamp) * block_stride + c * chan_stride + ((u % block_nsamp) * npol + p) * 2 + d
+ * and stored as float(int8) -- no half step and no scale, GUPPIUnpacker.C:74-80, unlike the (int8 + 0.5) * scale of the readers
+ * above -- at out_dev[c * out_chan_stride + p * out_pol_stride + 2 t + d].  Nothing outside the 2 * ndat floats of a row is
+ * written; nothing outside the kept samples of the runs of the ceil((first + ndat) / block_nsamp) blocks is read.  raw_dev,
+ * chan_stride and block_stride are any multiples of one sample (2 * npol bytes): runs that are not 16-byte aligned take narrower
+ * loads.  Rows at any float-aligned address (16-byte aligned rows take float4 stores).  ndat = 0: nothing to do.
+ * DSPSR_AMD_EINVAL before any launch, the message naming the limit: a null layout; nchan = 0; npol not 1 | 2; block_nsamp = 0;
+ * first >= block_nsamp; chan_stride < block_nsamp * 2 * npol; nchan > 1 and block_stride < (nchan - 1) * chan_stride +
+ * block_nsamp * 2 * npol; a stride or raw_dev that is not a multiple of 2 * npol; ndat >= 2^60; out_pol_stride < 2 * ndat (npol 2) or
+ * out_chan_stride < (npol - 1) * out_pol_stride + 2 * ndat (nchan > 1); a null pointer with ndat > 0. */
+typedef struct {
+  uint32_t nchan, npol;          /* npol 1 | 2, complex samples */
+  uint32_t block_nsamp;          /* kept samples of a run (OVERLAP already taken off) */
+  uint32_t first;                /* where the call's first sample lies inside block 0 of raw_dev, < block_nsamp */
+  uint64_t chan_stride;          /* bytes from run c to run c+1 of a block  (BLOCSIZE / nchan) */
+  uint64_t block_stride;         /* bytes from a block's data section to the next one's */
+} dspsr_amd_guppi_layout;
+int dspsr_amd_unpack_guppi_fpt(dspsr_amd_ctx* ctx, const int8_t* raw_dev, const dspsr_amd_guppi_layout* layout, uint64_t ndat,
+                               float* out_dev, uint64_t out_chan_stride, uint64_t out_pol_stride);
 /* ---- two-bit voltages: dsp::TwoBitCorrection on the device (TwoBitCorrection.C, ExcisionUnpacker.C, TwoBitFour.h) -------------
  * One input channel of real samples from npol = 1 | 2 digitisers.  Byte k of the stream belongs to digitiser k % npol and holds four
  * consecutive samples of it, the first in the two most significant bits (ExcisionUnpacker::get_input_offset / get_input_incr,

@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """tools/dspsr_amd_fold.py : the path behind the reference's own option spellings (dspsr.C:207-510) -- a thin driver over
-dspsr_amd.dada.fold_file for trying the engine on a DADA file; not a re-implementation of the dspsr application.
+dspsr_amd.dada.fold_file for trying the engine on a DADA file, or on a GUPPI / PUPPI raw file (NBITS 8, several channels: recognised
+from the file, no option; dspsr_amd/guppi.py); not a re-implementation of the dspsr application.
 
   dspsr_amd_fold.py -F 1024:D -D 1000 -b 1024 -c 0.0893 [-x 4096] [-L 10 | -s | -turns N] [-P polyco] [-K] [-d 1|2|4] [-ndim 1|2|4] [-r]
                     (-d npol, dspsr.C:389: 1 total intensity, 2 PP and QQ -- files of STATE Intensity / PPQQ, NPOL 1 / 2, NDIM 1 --,
@@ -146,9 +147,13 @@ def main(argv=None):
         sys.exit("-F nchan:D (coherent dedispersion During the filterbank), -F nchan (After it) or -F nchan:B (Before it) are on this "
                  "path; not %s" % a.fb)
     import torch
-    from dspsr_amd import dada, pipeline
-    hdr, _ = dada.read_header(a.file)
-    info, extras = dada.observation(hdr)
+    from dspsr_amd import dada, guppi, pipeline
+    if guppi.is_valid(a.file):                              # a GUPPI / PUPPI raw file: recognised from the file, no option
+        f = guppi.GuppiFile(a.file)
+        info, extras = f.info, f.extras
+    else:
+        hdr, _ = dada.read_header(a.file)
+        info, extras = dada.observation(hdr)
     dm = a.dm if a.dm is not None else extras["dm"]
     if dm is None:
         sys.exit("no -D and no DM in the header")

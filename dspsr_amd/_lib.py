@@ -168,6 +168,7 @@ SYMBOLS = {
     "dspsr_amd_unpack_fpt": (_i, [_vp, _vp, _f, _u32, _u32, _u32, _u64, _vp, _u64, _u64]),
     "dspsr_amd_unpack_heaps_fpt": (_i, [_vp, _vp, _i, _f, _u32, _u32, _u64, _vp, _u64, _u64]),
     "dspsr_amd_unpack_guppi_fpt": (_i, [_vp, _vp, C.POINTER(GuppiLayout), _u64, _vp, _u64, _u64]),
+    "dspsr_amd_unpack_sigproc_fpt": (_i, [_vp, _vp, _u32, _u32, _u32, _u64, _vp, _u64, _u64]),
     "dspsr_amd_twobit_check": (_i, [_u64, _i, _u32, _u32, _u32, _u64, _u32, _u32, _u64, _u64, C.c_char_p, _sz]),
     "dspsr_amd_twobit_unpack": (_i, [_vp, _vp, _i, _u32, _u32, _u32, _u64, _u32, _u32, _vp, _vp, _u64, _vp, _vp]),
     "dspsr_amd_detect_raw": (_i, [_vp, _vp, _f, _u32, _u32, _u64, _i, _u32, _vp, _u64, _u64, _vp, C.POINTER(_u32), C.POINTER(_u64)]),

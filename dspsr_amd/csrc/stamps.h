@@ -1,6 +1,7 @@
 // Phase stamps (diagnostic builds only: make EXTRA=-DFB_STAMPS=<id> OUT=... OBJDIR=..., read by tools/stamps.py): where a tile of a
 // persistent kernel spends its cycles -- s_memtime per phase on lane 0 of wave 0 of every workgroup.
-//   ids: 1 k_fwd_cols, 2 k_fwd_rows, 3 k_inv_chan (fused fold), 4 k_inv_a, 6 k_fwd_col1q, 7 k_rows_inv, 8 k_tfp
+//   ids: 1 k_fwd_cols, 2 k_fwd_rows, 3 k_inv_chan (fused fold), 4 k_inv_a, 6 k_fwd_col1q, 7 k_rows_inv, 8 k_tfp, 9 k_unpack_sigproc
+//   (9: a row of the table is a column of tiles, blockIdx.x, summed over the workgroups that share it)
 // A kernel marks its phases in program order: FB_ST_BEGIN(id) in front of the tile loop, FB_ST(id, 0) at the top of a tile (it
 // first waits for the prefetched tile, so that the wait is timed on its own), FB_ST(id, k) behind phase k, FB_ST_TILE(id, n)
 // behind the last of the n phases, FB_ST_END(id) behind the loop.  Row b of the table = cycles of phases 0 .. n-1 summed over the

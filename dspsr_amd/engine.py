@@ -637,6 +637,24 @@ def unpack_guppi_fpt(ctx: Context, raw, rows, layout, ndat):
     return rows
 
 
+def unpack_sigproc_fpt(ctx: Context, raw, rows, nbit, nchan, npol, ndat):
+    """dsp::SigProcUnpacker (OrderFPT) on the device: raw = device bytes (any dtype), `ndat` spectra of a SIGPROC filterbank file as
+    they lie in it -- npol * nchan values of nbit bits each, polarisation by polarisation --, at any byte address (nbit 16 / 32: a
+    multiple of the value's size); rows = float32 device rows [nchan][npol][>= ndat] (strided views allowed) that receive
+    float(value), less 127.5 (nbit 8) or 32768 (nbit 16) in the rows of polarisations 2 and 3; nbit 32: the floats as they are."""
+    if ndat < 0:
+        raise DspsrAmdError("dspsr_amd.unpack_sigproc_fpt: ndat=%d" % ndat)
+    need = ndat * ((npol * nchan * nbit) // 8)
+    if raw.numel() * raw.element_size() < need:
+        raise DspsrAmdError("dspsr_amd.unpack_sigproc_fpt: block holds %d bytes, %d needed" % (raw.numel() * raw.element_size(), need))
+    if tuple(rows.shape[:2]) != (nchan, npol) or rows.shape[2] < ndat:
+        raise DspsrAmdError("dspsr_amd.unpack_sigproc_fpt: rows are %s, [%d][%d][>= %d] needed" % (tuple(rows.shape), nchan, npol, ndat))
+    ocs, ops = _strides3(rows)
+    _check(ctx.handle, lib.dspsr_amd_unpack_sigproc_fpt(ctx.handle, raw.data_ptr(), nbit, nchan, npol, ndat, rows.data_ptr(), ocs, ops),
+           "dspsr_amd_unpack_sigproc_fpt")
+    return rows
+
+
 def twobit_block_bytes(first_sample, ndat, nsample, npol):
     """Bytes of the whole windows that hold `ndat` samples from `first_sample` of the first window on."""
     return -(-(first_sample + ndat) // nsample) * (nsample // 4) * npol if ndat > 0 else 0

@@ -260,8 +260,11 @@ class GuppiFile:
 
 
 def open_input(path: str, log=None):
-    """The input factory of the drivers and tools: a GuppiFile where the file is GUPPI raw (is_valid), else a dada.DadaFile.  The format
-    is recognised from the file, never from its name."""
+    """The input factory of the drivers and tools: a sigproc.SigprocFile where the file is a SIGPROC filterbank file, a GuppiFile where
+    it is GUPPI raw (is_valid), else a dada.DadaFile.  The format is recognised from the file, never from its name."""
+    from . import sigproc
+    if sigproc.is_valid(path):
+        return sigproc.SigprocFile(path)
     if is_valid(path):
         return GuppiFile(path, log=log)
     from .dada import DadaFile

@@ -20,7 +20,7 @@ from dataclasses import dataclass
 import numpy as np
 
 from . import _lib
-from .engine import (Context, ConvolutionEngine, CyclicFoldEngine, Dedispersion, DetectionEngine, DspsrAmdError, SpectralKurtosisEngine, FilterbankEngine, FITSDigitizer, FoldEngine, PhaseLockedFilterbankEngine, plfb_check_shape, Rescale, SampleDelay, add_fpt, copy_data_fpt, fourth_moment,
+from .engine import (Context, ConvolutionEngine, CyclicFoldEngine, Dedispersion, DetectionEngine, DspsrAmdError, SpectralKurtosisEngine, FilterbankEngine, FITSDigitizer, FoldEngine, PhaseLockedFilterbankEngine, plfb_check_shape, Rescale, SampleDelay, add_fpt, copy_data_fpt, fourth_moment, unpack_sigproc_fpt,
                      dedispersion_sample_delays, detect_raw, eight_bit_scale, fscrunch_fpt, pscrunch_tfp, sigproc_digitize, sigproc_digitize_fpt,
                      tfp_filterbank, tscrunch_fpt, twobit_block_bytes)
 
@@ -150,6 +150,8 @@ class InputInfo:
     telescope: str = "unknown"
     nbit: int = 8                     # NBIT of the file (every path here reads 8-bit samples)
     guppi: tuple | None = None        # a GUPPI raw file (dspsr_amd.guppi.GuppiFile): (block_nsamp, chan_stride, block_stride) of its blocks
+    detected: str | None = None       # detected input (a SIGPROC filterbank file, dspsr_amd.sigproc.SigprocFile): the state of its rows --
+                                      # "Intensity", "PPQQ" or "Coherence" for npol 1, 2, 4; nchan channels, ndim 1, nbit bits per value
 
     @property
     def rate(self):
@@ -514,6 +516,8 @@ def write_phase_series(path, sub, info: "InputInfo", cfg: "Config", *, nchan=Non
     nchan = nchan or cfg.nchan
     hits = np.asarray(sub["hits"])
     nbin = hits.shape[-1]
+    if state is None and ndim is None and getattr(info, "detected", None) is not None:     # detected input: the file's own state
+        state, ndim = info.detected, 1
     if state is None and ndim is None and square_law_state(cfg, info, strict=False):       # -d 1 / -d 2 / one polarisation: rows of ndim 1
         state, ndim = square_law_state(cfg, info, strict=False)[0], 1
     ndim = ndim or cfg.ndim
@@ -1249,6 +1253,43 @@ def refuse_guppi(who, info, instead):
                             "built on this path; %s" % (who, info.machine, instead))
 
 
+def refuse_detected(who, info):
+    """Plan-time refusal of a driver that reads voltages: detected input (a SIGPROC filterbank file) has none."""
+    if getattr(info, "detected", None) is not None:
+        raise DspsrAmdError("%s: the input is detected already (STATE %s, %d channels of %d-bit values): this driver forms its spectra "
+                            "from voltages; dspsr_amd.LoadToFold folds such a file" % (who, info.detected, info.nchan, info.nbit))
+
+
+def detected_check(cfg: "Config", info: "InputInfo", subband=None, dump_before=()):
+    """What a fold of detected input (info.detected: the first branch of LoadToFold::construct, LoadToFold1.C:126-180) refuses by
+    name, before any device resource is opened, each with the option's spelling; returns the Config the chain is built with: the
+    file's own polarisations, rows of ndim 1.  The reference ignores -F silently on this branch; here a filterbank is refused
+    (SURVEY Appendix C).  cfg.npol = 4 is the option's default and reads as `not given`."""
+    who = "dspsr_amd.LoadToFold: detected input (STATE %s)" % info.detected
+    if info.ndim != 1 or info.npol not in (1, 2, 4):
+        raise DspsrAmdError("%s holds rows of ndim 1 in 1, 2 or 4 polarisations; the input says ndim=%d npol=%d" % (who, info.ndim, info.npol))
+    if cfg.nchan != info.nchan:
+        raise DspsrAmdError("%s has no voltages to filter: nchan=%d (-F %d) asks for a filterbank, the file holds %d channels "
+                            "(give no -F, or -F %d)" % (who, cfg.nchan, cfg.nchan, info.nchan, info.nchan))
+    for on, what in ((cfg.cyclic_nchan > 0, "cyclic_nchan (-cyclic): cyclic spectra are formed from voltages"),
+                     (cfg.plfb_nbin > 0, "plfb_nbin (-G): the phase-locked filterbank transforms voltages"),
+                     (cfg.fourth_moment, "fourth_moment (-4): the moments are formed from the Stokes parameters of voltages"),
+                     (cfg.sk_zap, "sk_zap (-skz): dsp::SpectralKurtosis reads voltages"),
+                     (cfg.zap_rfi, "zap_rfi (-R): the RFI filter is multiplied into a dedispersion kernel, and there is none"),
+                     (cfg.calibrator is not None, "calibrator (-pac): the Jones matrices multiply voltages")):
+        if on:
+            raise DspsrAmdError("%s is not built with %s" % (who, what))
+    if cfg.npol not in (4, info.npol):
+        raise DspsrAmdError("%s: npol=%d (-d %d) asks for another state than the file's %d polarisations; detected rows are folded "
+                            "as they are (give no -d, or -d %d)" % (who, cfg.npol, cfg.npol, info.npol, info.npol))
+    if dump_before:
+        raise DspsrAmdError("%s: the dump taps (--dump %s) are not built here: there is no Detection, and pre_Fold would hold the "
+                            "file's own values" % (who, ", ".join(dump_before)))
+    if subband is not None:
+        raise DspsrAmdError("%s is not built for sub-band sharded runs (subband=%d) / the multi-GPU exchange" % (who, subband))
+    return dataclasses.replace(cfg, npol=info.npol, ndim=1, stokes=False, fused_fold=False, force_fused=False)
+
+
 def raw_block_bytes(layout, nsamp, nchan, npol, ndim, first_sample=0, guppi=None):
     """Bytes of a block of `nsamp` samples in `layout` (heaps: from `first_sample` of the first heap on, whole heaps; GUPPI raw
     blocks of geometry `guppi`: from the data section that holds `first_sample` to the last kept sample of the last run)."""
@@ -1381,7 +1422,67 @@ def tap_check(cfg: "Config", dump_before):
     return dump_before
 
 
-class DetectFold:
+class _BackEnd:
+    """What every back end answers; a mode overrides what differs."""
+
+    fronted = True                       # a front end (filterbank / convolution) stands before it; False: the back end plans and opens the whole run
+
+    def __init__(self, lt):
+        self.lt = lt
+
+    def state_name(self):
+        """Observation::get_state of what the mode folds, where the mode and not Detection decides it (None: Detection's)"""
+        return None
+
+    def block_bytes(self, nsamp):
+        """bytes of a block of `nsamp` samples where the mode reads the file's bytes itself (None: the front end's layout)"""
+        return None
+
+    def vitals(self):
+        """the lines of LoadToFold.vitals where the run has no filter to report (None: the driver's)"""
+        return None
+
+
+class _RowFold(_BackEnd):
+    """The fold of detected float rows, shared by Detection + Fold and by detected input: the plan of a piece, several pulsars over
+    the same rows, the end of a sub-integration."""
+
+    def plan_piece(self, acc, phi, phase_per_sample, ndat_fold, idat_start):
+        """The host plan loop of Fold::fold (Fold.C:718-787) on the accumulator's fold: the driver's, or a pulsar's"""
+        acc.fold.set_nbin(self.lt.cfg.nbin if acc is self.lt else acc.nbin)
+        acc.fold.set_ndat(ndat_fold, idat_start)
+        if self.lt._weights is not None:             # two-bit input: samples of a zero weight are not folded
+            row, npw, widat = self.lt._weights
+            return acc.fold.set_bins(phi, phase_per_sample, ndat_fold, idat_start, acc.hits, weights=row, ndatperweight=npw, weight_idat=widat)
+        return acc.fold.set_bins(phi, phase_per_sample, ndat_fold, idat_start, acc.hits)
+
+    def _fold_pulsars(self, rows, ndat):
+        """Several pulsars over the same detected rows.  The pulsars whose share of the block is one piece of a sub-integration
+        fold together (FoldEngine.fold_many: the rows are read once for all of them); a pulsar with a sub-integration boundary
+        inside the block folds piece by piece and emits its sub-integration in between."""
+        lt = self.lt
+        pieces = [lt._pieces(ndat, p) for p in lt.pulsars]
+        group = [(p, pc[0]) for p, pc in zip(lt.pulsars, pieces) if len(pc) == 1]
+        folded = [lt._plan_piece(piece, p) for p, piece in group]
+        if group:
+            lt._op("Fold", lambda: FoldEngine.fold_many([p.fold for p, _ in group], rows))
+        for (p, piece), n in zip(group, folded):
+            lt._book_piece(piece, n, p)
+        for p, pc in zip(lt.pulsars, pieces):
+            if len(pc) > 1:
+                lt._fold_pieces(pc, lambda: lt._op("Fold", lambda: p.fold.fold(rows)), p)
+
+    def finish(self, *exchange):
+        """Several pulsars (one GPU): the open sub-integration of each that has folded samples since its last; one: the exchange"""
+        lt = self.lt
+        if not lt.pulsars:
+            return lt._exchange_subint(*exchange)
+        for p in lt.pulsars:
+            if p.ndat_total:
+                lt._finish_pulsar_subint(p)
+
+
+class DetectFold(_RowFold):
     """Detection + Fold: fused into the filterbank's last pass or on the detected block, with the dump taps, -4, several pulsars
     and -K."""
 
@@ -1389,9 +1490,6 @@ class DetectFold:
     fuses = True                         # the front end may fold in its last pass (cfg.fused_fold)
     engines = ("fold",)
     no_exchange = property(lambda self: "fourth_moment (-4) is" if self.lt.moments else None)
-
-    def __init__(self, lt):
-        self.lt = lt
 
     def plan(self, ntargets, subband, dump_before):
         """-K: dsp::SampleDelay on the filterbank output.  Detection acts sample by sample, so delaying the detected rows gives the
@@ -1516,31 +1614,6 @@ class DetectFold:
         finally:
             lt._weights = None
 
-    def plan_piece(self, acc, phi, phase_per_sample, ndat_fold, idat_start):
-        """The host plan loop of Fold::fold (Fold.C:718-787) on the accumulator's fold: the driver's, or a pulsar's"""
-        acc.fold.set_nbin(self.lt.cfg.nbin if acc is self.lt else acc.nbin)
-        acc.fold.set_ndat(ndat_fold, idat_start)
-        if self.lt._weights is not None:             # two-bit input: samples of a zero weight are not folded
-            row, npw, widat = self.lt._weights
-            return acc.fold.set_bins(phi, phase_per_sample, ndat_fold, idat_start, acc.hits, weights=row, ndatperweight=npw, weight_idat=widat)
-        return acc.fold.set_bins(phi, phase_per_sample, ndat_fold, idat_start, acc.hits)
-
-    def _fold_pulsars(self, rows, ndat):
-        """Several pulsars over the same detected rows.  The pulsars whose share of the block is one piece of a sub-integration
-        fold together (FoldEngine.fold_many: the rows are read once for all of them); a pulsar with a sub-integration boundary
-        inside the block folds piece by piece and emits its sub-integration in between."""
-        lt = self.lt
-        pieces = [lt._pieces(ndat, p) for p in lt.pulsars]
-        group = [(p, pc[0]) for p, pc in zip(lt.pulsars, pieces) if len(pc) == 1]
-        folded = [lt._plan_piece(piece, p) for p, piece in group]
-        if group:
-            lt._op("Fold", lambda: FoldEngine.fold_many([p.fold for p, _ in group], rows))
-        for (p, piece), n in zip(group, folded):
-            lt._book_piece(piece, n, p)
-        for p, pc in zip(lt.pulsars, pieces):
-            if len(pc) > 1:
-                lt._fold_pieces(pc, lambda: lt._op("Fold", lambda: p.fold.fold(rows)), p)
-
     def _fold_rows(self, rows):
         """Fold::fold of the pending plan over detected rows.  -4: the Stokes rows go to the moments fold, which forms the products
         in registers; with a pre_Fold tap the 14-float stream dsp::FourthMoment would write exists (`_moment_stream`) and is
@@ -1563,21 +1636,82 @@ class DetectFold:
         lt._moment_rows = out
         return out
 
-    def finish(self, *exchange):
-        """Several pulsars (one GPU): the open sub-integration of each that has folded samples since its last; one: the exchange"""
-        lt = self.lt
-        if not lt.pulsars:
-            return lt._exchange_subint(*exchange)
-        for p in lt.pulsars:
-            if p.ndat_total:
-                lt._finish_pulsar_subint(p)
-
     def shape(self, nbin):
         self.lt.fold.set_shape(self.lt.nchan_out, *self.lt._fold_dims(), nbin)
         self.lt.hits = np.zeros(nbin, dtype=np.uint32)
 
 
-class CyclicFold:
+class DetectedFold(_RowFold):
+    """Detected input (info.detected, a SIGPROC filterbank file): the first branch of LoadToFold::construct (LoadToFold1.C:126-180)
+    -- no filterbank, no convolution, no Detection: dsp::SigProcUnpacker writes the float rows, [dsp::SampleDelay of -K removes the
+    inter-channel delay,] Fold folds them, by piece or by pulsar.  A block is a run of whole spectra as they lie in the file: a
+    part is one spectrum (lt.nkeep = nsamp_step = 1, no overlap), so the books of every other mode carry over."""
+
+    detects = fuses = fronted = False
+    engines = ("fold",)
+    no_exchange = "detected input is"
+
+    def state_name(self):
+        return self.lt.info.detected
+
+    def block_bytes(self, nsamp):
+        return nsamp * self.lt.spectrum_bytes                # whole spectra
+
+    def vitals(self):
+        return ["dspsr: blocksize=%d samples or %g MB" % (self.lt.cfg.parts_per_block, self.lt.block_bytes() / (1024.0 * 1024.0))]
+
+    def plan(self, ntargets, subband, dump_before):
+        """No response and no front end; -K: dsp::SampleDelay on the file's own channels, the samples it gives up at the end of a
+        block wait in the head room in front of `detected` (DelayCarry: lt.sd), exactly as DetectFold.plan has it."""
+        lt, cfg, info = self.lt, self.lt.cfg, self.lt.info
+        lt.in_nchan = lt.nchan_out = info.nchan
+        lt.npol_out = info.npol
+        lt.response = None
+        lt.out_rate, lt.out_start, lt.scalefac = info.rate, info.start_seconds, 1.0
+        lt.nkeep, lt.nsamp_step, lt.nsamp_overlap = 1, 1, 0
+        lt.layout, lt.guppi, lt.scale8 = _lib.RAW_GENERIC, None, 1.0
+        lt.spectrum_bytes = info.npol * info.nchan * info.nbit // 8
+        if cfg.interchan_dedispersion:
+            lt._delays = dedispersion_sample_delays(info.centre_frequency, info.bandwidth, cfg.dispersion_measure, info.nchan, lt.out_rate)
+            lt.sd = DelayCarry(lt._delays)
+            lt.out_start += lt.sd.zero / lt.out_rate                                 # SampleDelay.C:159
+
+    def open(self, rows, dump_dir):
+        lt, cfg = self.lt, self.lt.cfg
+        lt.fold = FoldEngine(lt.ctx)
+        self.shape(cfg.nbin)
+        if cfg.interchan_dedispersion:
+            lt.sample_delay = SampleDelay(lt.ctx, lt._delays, lt.npol_out)
+            lt.sd.check_block("LoadToFold", rows)
+        # every row starts on a 16-byte boundary whatever the head room: float4 stores for whole tiles of a block
+        pad = (-lt.sd.head) % 4
+        span = pad + lt.sd.head + rows
+        self.buffer = _device_empty(lt.ctx, (lt.nchan_out, lt.npol_out, span + (-span) % 4))
+        lt.detected = self.buffer[:, :, pad:]
+
+    def shape(self, nbin):
+        self.lt.fold.set_shape(self.lt.nchan_out, self.lt.npol_out, 1, nbin)
+        self.lt.hits = np.zeros(nbin, dtype=np.uint32)
+
+    def process(self, raw, ndat, events):
+        """SigProcUnpacker behind the head room -> [SampleDelay in place over the carried tail and the new samples] -> Fold -> the
+        unshifted tail kept in front of the next block.  Without -K: no head room, nothing carried, every sample delivered."""
+        lt, info, sd = self.lt, self.lt.info, self.lt.sd
+        lt._filterbank_op("SigProcUnpacker", lambda: unpack_sigproc_fpt(lt.ctx, raw, sd.new(lt.detected), info.nbit, info.nchan, info.npol, ndat),
+                          events)
+        rows, nout = lt.detected[:, :, :ndat], ndat
+        if lt.sample_delay is not None:
+            rows = sd.rows(lt.detected, ndat)
+            nout = lt._op("SampleDelay", lambda: lt.sample_delay.transform(rows)) if rows.shape[2] else 0
+        if nout and lt.pulsars:
+            self._fold_pulsars(rows, nout)
+        elif nout:
+            lt._fold_pieces(lt._pieces(nout), lambda: lt._op("Fold", lambda: lt.fold.fold(rows)))
+        sd.keep_tail(lt.ctx, lt.detected, ndat, nout)
+        return nout
+
+
+class CyclicFold(_BackEnd):
     """`dspsr -cyclic N`: the convolving filterbank writes its complex rows, dsp::CyclicFold folds their lag products
     (LoadToFold1.C:534-539,999-1044); Detection and Fold are not built.  At a sub-integration the lag data come to the
     host and CyclicFoldEngine::synch turns them into spectra (once per sub-integration: host, as in the reference)."""
@@ -1625,7 +1759,7 @@ class CyclicFold:
         _emit(lt, _books(lt, profile=spectra[..., None]), lt.cyclic.zero)
 
 
-class PhaseLockedFold:
+class PhaseLockedFold(_BackEnd):
     """`dspsr -G nbin`: the convolving filterbank writes its complex rows and dsp::PhaseLockedFilterbank consumes them
     (LoadToFold1.C:386-456); Detection and Fold are not built.  One integration over the whole stream: the windows are those
     of ONE transformation call (PlfbPlan), whatever the block size.  The rows of a block sit behind a head room that holds the
@@ -1699,7 +1833,7 @@ class PhaseLockedFold:
         _emit(lt, _books(lt, profile=prof[..., None], **{k: lt.plfb_geometry[k] for k in ("state", "rate", "nsub_swap", "scale")}), lt.plfb.zero)
 
 
-class KurtosisFold:
+class KurtosisFold(_BackEnd):
     """`dspsr -skz`: the convolving filterbank writes its complex rows, dsp::SpectralKurtosis zeroes what it zaps in place,
     Detection and Fold follow; the fold counts its hits per channel on the device (Fold::Engine::zeroed_samples with
     hits_nchan == nchan, LoadToFold1.C:458-532, Fold.C:853-866).  The rows of a block sit behind a head room that holds the
@@ -1829,7 +1963,10 @@ class LoadToFold:
 
     def _plan(self, cfg, info, polyco, reference_phase, subband, dump_before, targets):
         """The host side of the constructor: what the run refuses, in the order it always has, and every number that needs no device."""
-        if getattr(info, "nbit", 8) == 2:
+        detected = getattr(info, "detected", None) is not None
+        if detected:                                     # a SIGPROC filterbank file: nbit counts bits per detected value
+            cfg = detected_check(cfg, info, subband, dump_before)
+        elif getattr(info, "nbit", 8) == 2:
             self.twobit = twobit_check(cfg, info, len(targets), subband, dump_before)
         if cfg.zap_rfi:
             rfi_check(cfg, info, subband)
@@ -1857,8 +1994,11 @@ class LoadToFold:
         if cfg.folding_period <= 0 and polyco is None:
             raise DspsrAmdError("dsp::Fold::fold no polynomial and no period specified")   # Fold.C:638-640
         # the back end of the run: every later question about the mode is put to it
-        self.mode = (CyclicFold if cfg.cyclic_nchan > 0 else PhaseLockedFold if cfg.plfb_nbin > 0 else KurtosisFold if cfg.sk_zap
-                     else DetectFold)(self)
+        self.mode = (DetectedFold if detected else CyclicFold if cfg.cyclic_nchan > 0 else PhaseLockedFold if cfg.plfb_nbin > 0
+                     else KurtosisFold if cfg.sk_zap else DetectFold)(self)
+        if not self.mode.fronted:                        # no front end, no response: the back end plans the whole run
+            self.square_law = None
+            return self.mode.plan(len(targets), subband, dump_before)
         # -d 1, -d 2, one polarisation: Detection::square_law, rows and profile of npol_out x ndim 1 (cfg.ndim, the layout of the
         # four products, then says 1 wherever this class reads it)
         self.square_law = square_law_state(cfg, info)
@@ -1927,6 +2067,8 @@ class LoadToFold:
         the block the two share."""
         cfg, info, r = self.cfg, self.info, self.response
         self.ctx = Context(device, stream)
+        if not self.mode.fronted:                        # detected input: self.fb stays None
+            return self.mode.open(cfg.parts_per_block, dump_dir)
         nsub, rows = cfg.nchan // info.nchan, cfg.parts_per_block
         setup = dict(max_parts=cfg.max_parts, force_four_pass=0 if cfg.two_pass else 2, fuse_heaps=cfg.fuse_heaps)
         fused = _lib.FUSED_NEVER if not (cfg.fused_fold and self.mode.fuses) else _lib.FUSED_ALWAYS if cfg.force_fused else _lib.FUSED_AUTO
@@ -1999,6 +2141,9 @@ class LoadToFold:
 
     def state_name(self):
         """Observation::get_state of the folded PhaseSeries (the STATE of its files and of the pre_Fold tap)"""
+        own = self.mode.state_name()                       # (detected input: the file's)
+        if own is not None:
+            return own
         return "FourthMoment" if self.moments else self.square_law[0] if self.square_law else "Stokes" if self.cfg.stokes else "Coherence"
 
     def _fold_dims(self):
@@ -2024,6 +2169,9 @@ class LoadToFold:
         """The lines `dspsr` prints while it prepares (report_vitals, LoadToFold1.C:773-792,874-879): dedispersion filter
         length, what the filterbank requires, the block size."""
         r, cfg = self.response, self.cfg
+        own = self.mode.vitals()                          # (detected input: no filter and no filterbank, the block alone)
+        if own is not None:
+            return own
         if r is None:                                     # Config::Never: no response
             from types import SimpleNamespace
             r = SimpleNamespace(ndat=1, minimum_ndat=0)
@@ -2050,7 +2198,11 @@ class LoadToFold:
         """first_sample: a block of heaps begins at that sample of its first heap (0 for every other layout)."""
         npart = npart or self.cfg.parts_per_block
         nsamp = npart * self.nsamp_step + self.nsamp_overlap
-        tb = getattr(self, "twobit", None)   # (the method is also borrowed by stand-ins that hold the geometry alone)
+        mode = getattr(self, "mode", None)   # (the method is also borrowed by stand-ins that hold the geometry alone)
+        own = mode.block_bytes(nsamp) if mode is not None else None
+        if own is not None:                  # (detected input: whole spectra)
+            return own
+        tb = getattr(self, "twobit", None)
         if tb is not None:                   # whole excision windows from the one that holds the block's first sample
             return twobit_block_bytes(first_sample, nsamp, tb.nsample, self.info.npol)
         return raw_block_bytes(self.layout, nsamp, self.in_nchan, self.info.npol, self.info.ndim, first_sample, getattr(self, "guppi", None))
@@ -2548,6 +2700,7 @@ class ConvolvingFront(SearchFront):
 
     def _geometry(self):
         cfg, info, who = self.cfg, self.info, self.who
+        refuse_detected(who, info)
         refuse_twobit(who, info)
         if cfg.npol not in (1, 2, 4):
             raise DspsrAmdError("%s: npol=%d (Intensity 1 / PPQQ 2 / Coherence 4 are built; NthPower 3 is not)" % (who, cfg.npol))
@@ -2628,6 +2781,7 @@ class ChannelisedFront(SearchFront):
 
     def _geometry(self):
         cfg, info, who = self.cfg, self.info, self.who
+        refuse_detected(who, info)
         refuse_twobit(who, info)
         if info.ndim != 2:
             raise DspsrAmdError("%s: NDIM=%d; complex (NDIM 2) channelised voltages only" % (who, info.ndim))
@@ -2761,6 +2915,7 @@ class LoadToFil(_SearchDriver):
 
     def _plan(self):
         cfg, info = self.cfg, self.info
+        refuse_detected("dspsr_amd.LoadToFil", info)
         refuse_twobit("dspsr_amd.LoadToFil", info)
         refuse_heaps("dspsr_amd.LoadToFil", info, "channelised complex voltages take -F N:D (dspsr_amd.LoadToFilCoherent)")
         refuse_guppi("dspsr_amd.LoadToFil", info, "channelised complex voltages take -F N:D (dspsr_amd.LoadToFilCoherent)")

@@ -395,6 +395,25 @@ typedef struct {
 } dspsr_amd_guppi_layout;
 int dspsr_amd_unpack_guppi_fpt(dspsr_amd_ctx* ctx, const int8_t* raw_dev, const dspsr_amd_guppi_layout* layout, uint64_t ndat,
                                float* out_dev, uint64_t out_chan_stride, uint64_t out_pol_stride);
+/* dspsr_amd_unpack_sigproc_fpt replaces dsp::SigProcUnpacker::unpack, OrderFPT branch (sigproc/SigProcUnpacker.C:96-156; the order
+ * the reference uses for the format, get_order_supported :23) on the device: the detected spectra of a SIGPROC filterbank file, as
+ * they lie in the file, -> float FPT rows [nchan][npol] of ndat floats.  Spectrum t is the S = npol * nchan * nbit / 8 bytes at
+ * raw_dev + t * S; value v = ipol * nchan + ichan of it goes to out_dev[ichan * out_chan_stride + ipol * out_pol_stride + t].
+ * nbit 8 / 16 / 32: element v as uint8 / uint16 / a float copied bit for bit.  nbit 1 / 2 / 4: byte v * nbit / 8, shifted right by
+ * (ichan mod 8 / nbit) * nbit and masked to nbit bits (the lowest bits are the first channel).  The value is float(x) - offset with
+ * offset = 127.5 (nbit 8) or 32768 (nbit 16) in the rows ipol > 1 -- the cross products of files dspsr wrote, :101-103 --, else 0:
+ * exact in float32.  The `signed` key of the header plays no part, as in the reference.
+ * raw_dev at any byte address for nbit <= 8, any 2-byte address for nbit 16, any 4-byte address for nbit 32 (a caller offsets the
+ * pointer to the first spectrum of its call, S is often odd): the widest load the address and S allow -- of 16, 8, 4, 2 and 1
+ * bytes, at most an eighth of a tile's 16 * nbit bytes -- is chosen once per call.  No byte outside raw_dev ... raw_dev + ndat * S is read.  Rows at any float-aligned address (a row whose
+ * address is 16-byte aligned takes float4 stores); nothing outside the ndat floats of a row is written.  ndat = 0: nothing to do.
+ * A transpose through LDS in tiles of 64 spectra by 128 values; nbit / 8 bytes read and 4 written per value.
+ * DSPSR_AMD_EINVAL before any launch, the message naming the limit: nbit not 1 | 2 | 4 | 8 | 16 | 32; nchan = 0; npol not 1 | 2 | 4;
+ * nbit < 8 and nchan * nbit not a multiple of 8 (a polarisation would start inside a byte, where the reference's own addressing
+ * goes wrong); raw_dev not a multiple of nbit / 8 bytes (nbit 16, 32); ndat * S > 2^62; out_pol_stride < ndat (npol > 1) or
+ * out_chan_stride < (npol - 1) * out_pol_stride + ndat (nchan > 1); a null pointer with ndat > 0. */
+int dspsr_amd_unpack_sigproc_fpt(dspsr_amd_ctx* ctx, const void* raw_dev, uint32_t nbit, uint32_t nchan, uint32_t npol, uint64_t ndat,
+                                 float* out_dev, uint64_t out_chan_stride, uint64_t out_pol_stride);
 /* ---- two-bit voltages: dsp::TwoBitCorrection on the device (TwoBitCorrection.C, ExcisionUnpacker.C, TwoBitFour.h) -------------
  * One input channel of real samples from npol = 1 | 2 digitisers.  Byte k of the stream belongs to digitiser k % npol and holds four
  * consecutive samples of it, the first in the two most significant bits (ExcisionUnpacker::get_input_offset / get_input_incr,

@@ -39,7 +39,13 @@ raw sums + hits; dsp::Archiver's normalisation is the reader's job).
 
 Several pulsars from the same data in one pass (dspsr -P a.polyco -P b.polyco): repeat -P and/or -c, one pulsar each (-P files
 first, then -c periods, each in the order given).  Pulsar k writes <prefix>_<k>_<n>.ps with its own folding period in the header.
-One -P, one -c or one of each is today's single pulsar (a -c given with a -P overrides its period)."""
+One -P, one -c or one of each is today's single pulsar (a -c given with a -P overrides its period).
+
+  dspsr_amd_fold.py -K -D 26.8 -c 0.7145 -b 256 file.fil   (a SIGPROC filterbank file, recognised from the file: detected input, the
+                    first branch of LoadToFold::construct.  No -F: the channels, the polarisations and the STATE of the files written
+                    are the file's own (nifs 1 Intensity, 2 PPQQ, 4 Coherence).  -D is needed only with -K, which removes the
+                    inter-channel delay with dsp::SampleDelay.  -L, -s, -turns, several -c / -P and -r work as above; -F N with
+                    another N, -cyclic, -G, -4, -skz, -R, -pac, --dump and a -d other than the file's are refused by name)"""
 import argparse
 import os
 import sys
@@ -50,7 +56,7 @@ sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."
 def parse_args(argv=None):
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("file")
-    ap.add_argument("-F", dest="fb", required=True, help="nchan:D (convolving filterbank, coherent dedispersion During) or nchan (filterbank, then dsp::Convolution: After)")
+    ap.add_argument("-F", dest="fb", default=None, help="(required for voltages; a SIGPROC filterbank file takes none) nchan:D (convolving filterbank, coherent dedispersion During) or nchan (filterbank, then dsp::Convolution: After)")
     ap.add_argument("-D", dest="dm", type=float, default=None, help="dispersion measure (default: DM of the header)")
     ap.add_argument("-b", dest="nbin", type=int, default=0, help="phase bins (default: dsp::Fold::choose_nbin)")
     ap.add_argument("-c", dest="period", type=float, action="append", default=[], help="constant folding period in seconds (repeat: one pulsar each)")
@@ -61,7 +67,7 @@ def parse_args(argv=None):
     ap.add_argument("-turns", dest="turns", type=float, default=0.0, help="turns per sub-integration")
     ap.add_argument("-K", dest="interchan", action="store_true", help="remove the inter-channel dispersion delay")
     # (the attribute keeps the name it had when -d spelled the layout; it holds the reference's npol)
-    ap.add_argument("-d", dest="ndim", type=int, default=4, choices=[1, 2, 3, 4],
+    ap.add_argument("-d", dest="ndim", type=int, default=None, choices=[1, 2, 3, 4],
                     help="output polarisations (dspsr -d npol): 1 Intensity, 2 PPQQ, 4 the four products; also with -cyclic and -G")
     # (dspsr spells it -n; here -n<text> must stay an unrecognised argument: -noskz_too is refused that way)
     ap.add_argument("-ndim", dest="layout", type=int, default=4, choices=[1, 2, 4], help="ndim of the detected rows when npol=4 (dspsr -n ndim, dspsr.C:392)")
@@ -87,6 +93,9 @@ def parse_args(argv=None):
     ap.add_argument("-O", dest="prefix", default="dspsr_amd", help="output file name prefix")
     ap.add_argument("--cuda", dest="device", type=int, default=0, help="device id (the reference's spelling)")
     a = ap.parse_args(argv)
+    a.d_given = a.ndim is not None
+    if a.ndim is None:
+        a.ndim = 4
     if a.ndim == 3 and (a.cyclic or a.plfb_nbin):              # nothing changed for -cyclic and -G: 1, 2 or 4
         ap.error("argument -d: invalid choice: 3 (choose from 1, 2, 4)")
     return a
@@ -140,8 +149,60 @@ def fold_targets(a, nbin, out_rate, mjd_day, mjd_sec):
     return out
 
 
+def fold_detected(a):
+    """A SIGPROC filterbank file: nchan and state come from the file, -D matters only with -K"""
+    import torch
+    from dspsr_amd import dada, pipeline, sigproc
+    f = sigproc.SigprocFile(a.file)
+    info = f.info
+    if a.fb is not None and ":" in a.fb:
+        sys.exit("-F %s: detected input has no voltages to dedisperse coherently (give no -F)" % a.fb)
+    if a.d_given and a.ndim != info.npol:
+        sys.exit("-d %d: the file holds %d polarisation(s), STATE %s; detected rows are folded as they are (give no -d)" % (a.ndim, info.npol, info.detected))
+    dm = a.dm if a.dm is not None else f.extras["dm"] or 0.0
+    if a.interchan and a.dm is None and f.extras["dm"] is None:
+        sys.exit("-K needs -D: no refdm in the header")
+    targets = fold_targets(a, a.nbin, info.rate, info.mjd_day, info.mjd_sec)
+    period = a.period[0] if len(a.period) == 1 else 0.0
+    polyco = pipeline.Polyco(open(a.polyco[0]).read()) if len(a.polyco) == 1 and not targets else None
+    if not targets and polyco is None and period <= 0:
+        sys.exit("dsp::Fold::fold no polynomial and no period specified (-c or -P)")
+    pfold = period if period > 0 else 1.0 / polyco.frequency(info.mjd_day, info.mjd_sec) if polyco else 0.0
+    nbin = a.nbin or (pipeline.choose_nbin(pfold, info.rate) if pfold else targets[0].nbin)
+    # a block of about 64 MiB of float rows, whole spectra
+    block = max(1, min(max(f.ndat, 1), (1 << 24) // (info.nchan * info.npol)))
+    cfg = pipeline.Config(nchan=int(a.fb) if a.fb is not None else info.nchan, dispersion_measure=dm, nbin=nbin, folding_period=period,
+                          subint_seconds=a.subint, subint_turns=1.0 if a.single else a.turns, plfb_nbin=a.plfb_nbin, cyclic_nchan=a.cyclic,
+                          interchan_dedispersion=a.interchan, record_time=a.record, fourth_moment=a.fourth, calibrator=a.pac,
+                          zap_rfi=a.zap_rfi, sk_zap=a.skz, parts_per_block=block)
+    torch.cuda.set_device(a.device)
+    lt = dada.fold_file(a.file, cfg, polyco=polyco, device=a.device, stream=torch.cuda.current_stream().cuda_stream,
+                        dump_before=tuple(a.dump), targets=targets or None)
+    for line in lt.vitals():
+        print(line, file=sys.stderr)
+    outputs = [("%s_%%04d.ps" % a.prefix, lt.subints, pfold)]
+    if targets:
+        outputs = [("%s_%d_%%04d.ps" % (a.prefix, k), p.subints,
+                    p.target.folding_period or 1.0 / p.target.polyco.frequency(info.mjd_day, info.mjd_sec))
+                   for k, p in enumerate(lt.pulsars)]
+    for pattern, subints, pf in outputs:
+        for n, sub in enumerate(subints):
+            path = pattern % n
+            pipeline.write_phase_series(path, sub, info, lt.cfg, nchan=info.nchan, npol=info.npol, scale=lt.scalefac, division=n,
+                                        start_seconds=lt.out_start, folding_period=pf)
+            print("dspsr_amd: %s  integration %.6f s  %d samples" % (path, sub["integration_length"], sub["ndat_total"]))
+    if a.record:
+        lt.report()
+    lt.close()
+
+
 def main(argv=None):
     a = parse_args(argv)
+    from dspsr_amd import sigproc
+    if sigproc.is_valid(a.file):                            # a SIGPROC filterbank file: recognised from the file, no option
+        return fold_detected(a)
+    if a.fb is None:
+        sys.exit("the following arguments are required: -F (the input holds voltages)")
     when = "during" if a.fb.endswith(":D") else "before" if a.fb.endswith(":B") else "after"
     if ":" in a.fb and when == "after":
         sys.exit("-F nchan:D (coherent dedispersion During the filterbank), -F nchan (After it) or -F nchan:B (Before it) are on this "

@@ -4,7 +4,8 @@
     DSPSR_AMD_LIB=build/lib_st8.so python tools/stamps.py 8 [workload]          (on the GPU box)
 
 ids / default workloads: 1 k_fwd_cols, 2 k_fwd_rows, 3 k_inv_chan fused (target | cfg2 | cfg3), 4 k_inv_a (cfg1opt | cfg1),
-6 k_fwd_col1q, 7 k_rows_inv (cfg4), 8 k_tfp (cfg5).  FUSED=0: the launch group that writes its detected output.
+6 k_fwd_col1q, 7 k_rows_inv (cfg4), 8 k_tfp (cfg5), 9 k_unpack_sigproc (sigproc8: 4096 channels x 2^16 spectra of 8 bits, the shape of
+tools/sigproc_unpack_probe.py; sigproc1 ... sigproc32: the other sample sizes).  FUSED=0: the launch group that writes its detected output.
 """
 import argparse
 import ctypes as C
@@ -28,7 +29,22 @@ KERNELS = {
                              "inverse transform (+ staging)", "fold phase / stores"]),
     8: ("tfp", "cfg5", ["wait prefetched tile", "image through LDS + decode", "issue next prefetch", "transform + staging",
                         "split, powers, tscrunch, stores"]),
+    9: ("unpack_sigproc", "sigproc8", ["wait for the stores of the tile before", "loads, unpack, LDS writes", "LDS reads, store issue"]),
 }
+
+
+class _SigprocUnpack:
+    """process_block = one dspsr_amd_unpack_sigproc_fpt call at the probe's shape"""
+
+    def __init__(self, nbit, nchan=4096, ndat=1 << 16):
+        import dspsr_amd
+        self.call, self.ctx = dspsr_amd.unpack_sigproc_fpt, dspsr_amd.Context(0, torch.cuda.current_stream().cuda_stream)
+        self.geom = (nbit, nchan, 1, ndat)
+        self.rows = torch.empty((nchan, 1, ndat), dtype=torch.float32, device="cuda")
+        self.raw = torch.randint(0, 0x70, (nchan * ndat * nbit // 8,), dtype=torch.uint8, device="cuda")
+
+    def process_block(self, raw):
+        self.call(self.ctx, raw, self.rows, *self.geom)
 
 
 def main():
@@ -40,8 +56,11 @@ def main():
         unit = "inv_chan"
     lib = C.CDLL(os.environ["DSPSR_AMD_LIB"])
     reader = getattr(lib, "dspsr_amd_debug_stamps_" + unit)
-    wl = bench.WORKLOADS[wl_name]
-    if wl_name == "cfg5":
+    wl = bench.WORKLOADS.get(wl_name)
+    if wl_name.startswith("sigproc"):
+        p = _SigprocUnpack(int(wl_name[7:]))
+        raw = p.raw
+    elif wl_name == "cfg5":
         info = pipeline.InputInfo(centre_frequency=wl["freq"], bandwidth=wl["bw"], nchan=1, npol=2, ndim=1, tsamp_us=wl["tsamp_us"], machine=wl["machine"])
         p = pipeline.LoadToFil(pipeline.SearchConfig(nchan=wl["nchan"], tscrunch=wl["tscrunch"], nbit=8, parts_per_block=wl["nparts"]), info, device=0,
                                stream=torch.cuda.current_stream().cuda_stream)

@@ -76,6 +76,21 @@ def heap_block_bytes(first_sample: int, nsamp: int, nchan: int, npol: int) -> in
     return -(-(first_sample + nsamp) // HEAP_NSAMP) * npol * nchan * HEAP_NSAMP * 2
 
 
+def raw_block_bytes(layout: int, nsamp: int, nchan: int, npol: int, ndim: int, first_sample: int = 0, geometry=None) -> int:
+    """Bytes of an 8-bit block of `nsamp` samples in `layout` (a layout without its first sample).  Heaps: the whole heaps from
+    `first_sample` of the first one on; GUPPI raw blocks of `geometry` = (block_nsamp, chan_stride, block_stride): from the data
+    section that holds `first_sample` to the last kept sample of the last run."""
+    if layout in (RAW_MEERKAT, RAW_MEERKAT_SWAP):
+        return heap_block_bytes(first_sample, nsamp, nchan, npol)
+    if layout == RAW_GUPPI:
+        return guppi_block_bytes(first_sample, nsamp, nchan, npol, *geometry)
+    if layout == RAW_CASPSR:
+        # 4 samples of pol0 then 4 of pol1: the block must hold WHOLE 8-byte groups (its last samples' pol1 bytes lie up to 4 bytes
+        # behind their pol0 bytes; CASPSRUnpacker.C:132-187 unpacks group by group)
+        return ((nsamp + 3) // 4) * 8
+    return nsamp * nchan * npol * ndim
+
+
 class FilterbankConfig(C.Structure):
     _fields_ = [("nchan_subband", C.c_uint32), ("freq_res", C.c_uint32), ("nfilt_pos", C.c_uint32),
                 ("nfilt_neg", C.c_uint32), ("input_nchan", C.c_uint32), ("npol", C.c_uint32),

@@ -17,6 +17,7 @@ import numpy as np
 
 from . import _lib
 from .engine import DspsrAmdError
+from .inputs import InputFile, open_input, raw_form
 
 DEFAULT_HEADER_SIZE = 4096            # DADAFile.C:44
 HEAP_NSAMP = _lib.HEAP_NSAMP          # samples of one (pol, chan) run of a MeerKAT heap (kat/MeerKATUnpacker.C:137-230)
@@ -248,35 +249,33 @@ def read_dump(path):
     return text, data[:(data.size // per) * per].reshape(-1, info.nchan, info.npol, info.ndim)
 
 
-class DadaFile:
-    """dsp::DADAFile (DADAFile.C:149-180) + the block loop of dsp::IOManager: an 8-bit DADA file, or CPSR2's two-bit one, cut
-    into the blocks LoadToFold consumes."""
+class DadaFile(InputFile):
+    """dsp::DADAFile (DADAFile.C:149-180) + the block loop of dsp::IOManager (inputs.InputFile): an 8-bit DADA file -- the generic
+    order, CASPSR's, or the MeerKAT beamformer's whole heaps of 256 samples per (pol, chan) run (MeerKATUnpacker::matches: MKBF /
+    MKBFRo) -- or CPSR2's two-bit one, cut into the blocks LoadToFold consumes.  The forms differ in the samples a whole unit of
+    the file holds: .data is the memory map of the whole units, .ndat their samples."""
 
     def __init__(self, path: str):
         self.path = path
         self.header, self.header_bytes = read_header(path)
         self.info, self.extras = observation(self.header)
-        self.twobit = self.extras["nbit"] == 2
-        if self.twobit:
-            self._open_twobit(path)
-            return
-        if self.extras["nbit"] != 8:
+        if self.extras["nbit"] == 2:
+            self._check_twobit()
+        elif self.extras["nbit"] != 8:
             raise DspsrAmdError("dspsr_amd.DadaFile: NBIT=%d; this path reads 8-bit samples" % self.extras["nbit"])
-        self.bytes_per_sample = self.info.nchan * self.info.npol * self.info.ndim
+        info, self.form = self.info, raw_form(self.info)
+        if self.heaps and (info.ndim != 2 or info.npol not in (1, 2)):
+            raise DspsrAmdError("dspsr_amd.DadaFile: INSTRUMENT %s is complex 8-bit with one or two polarisations (NDIM 2, NBIT 8, "
+                                "NPOL 1 | 2); the header says NDIM=%d NPOL=%d" % (info.machine, info.ndim, info.npol))
+        self.sample_bits = info.nchan * info.npol * info.ndim * info.nbit
+        self.bytes_per_sample = None if self.twobit else self.sample_bits // 8      # (two bits: a quarter of a byte per digitiser)
+        whole = 4 if self.twobit else self.form.granule                 # whole bytes of every digitiser; whole heaps
         nbytes = os.path.getsize(path) - self.header_bytes
-        self.ndat = nbytes // self.bytes_per_sample                     # File::open_fd: from the file size
-        # MeerKAT beamformer: whole heaps of 256 samples per (pol, chan) run (MeerKATUnpacker::matches: MKBF / MKBFRo, 8 bit)
-        self.heaps = self.info.machine in _lib.HEAP_MACHINES
-        if self.heaps:
-            if self.info.ndim != 2 or self.info.npol not in (1, 2):
-                raise DspsrAmdError("dspsr_amd.DadaFile: INSTRUMENT %s is complex 8-bit with one or two polarisations (NDIM 2, NBIT 8, "
-                                    "NPOL 1 | 2); the header says NDIM=%d NPOL=%d" % (self.info.machine, self.info.ndim, self.info.npol))
-            self.heap_bytes = self.bytes_per_sample * HEAP_NSAMP
-            self.ndat = (nbytes // self.heap_bytes) * HEAP_NSAMP        # whole heaps only
-        self._map = np.memmap(path, dtype=np.int8, mode="r", offset=self.header_bytes,
-                              shape=(self.ndat * self.bytes_per_sample,)) if self.ndat else np.zeros(0, np.int8)
+        self.ndat = (nbytes * 8 // (self.sample_bits * whole)) * whole  # File::open_fd: from the file size
+        self.data = np.memmap(path, dtype=np.int8, mode="r", offset=self.header_bytes,
+                              shape=(self.ndat * self.sample_bits // 8,)) if self.ndat else np.zeros(0, np.int8)
 
-    def _open_twobit(self, path):
+    def _check_twobit(self):
         """NBIT 2: CPSR2's two-bit real samples (CPSR2TwoBitCorrection::matches: INSTRUMENT CPSR2, NBIT 2, Nyquist; offset binary):
         one channel, one or two digitisers interleaved byte by byte, four samples per byte."""
         info = self.info
@@ -290,66 +289,25 @@ class DadaFile:
         import dataclasses
         self.info = dataclasses.replace(info, nbit=2)
         self.table_type = _lib.TWOBIT_MACHINES[info.machine]
-        self.heaps = False
-        self.bytes_per_sample = None                                    # a quarter of a byte per digitiser
-        nbytes = os.path.getsize(path) - self.header_bytes
-        self.ndat = (nbytes // info.npol) * 4                           # whole bytes of every digitiser
-        self._map = np.memmap(path, dtype=np.int8, mode="r", offset=self.header_bytes,
-                              shape=(self.ndat // 4 * info.npol,)) if self.ndat else np.zeros(0, np.int8)
 
-    def _usable(self, lt):
-        """Samples the block loop reads.  Two-bit: the whole excision windows (Input's resolution: the unpacker takes whole
-        windows, what follows the file's last one is dropped)."""
-        if not self.twobit:
-            return self.ndat
-        return (self.ndat // lt.twobit.nsample) * lt.twobit.nsample
+    def samples(self, s0, n):
+        if self.form.name not in ("generic", "caspsr"):                 # heaps, excision windows: no sample lies in bytes of its own
+            return InputFile.samples(self, s0, n)
+        return self.data[s0 * self.bytes_per_sample:(s0 + n) * self.bytes_per_sample]
 
-    def nblocks(self, lt):
-        """(whole blocks, parts of the ragged last block)."""
-        ndat = self._usable(lt)
-        if ndat < lt.nsamp_overlap + lt.nsamp_step:
-            return 0, 0
-        nparts = (ndat - lt.nsamp_overlap) // lt.nsamp_step
-        return divmod(nparts, lt.cfg.parts_per_block)
-
-    def blocks(self, lt, channel=None):
-        """Yield (int8 host array, npart) for LoadToFold `lt`; the last block may hold fewer parts.  Samples past the last
-        whole overlap-save part are not used (the reference leaves them in the input buffer at end of data).  The arrays
-        are views of the memory-mapped file (process_host_blocks stages them through its own pinned buffers).
-        channel = g: only input channel g's bytes ([t][pol][dim]), what rank g of a sub-band sharded run reads.
-        A file of heaps (MKBF / MKBFRo) yields (the whole heaps that hold the block, npart, first_sample): the block starts at
-        sample first_sample = (b * parts_per_block * nsamp_step) & 255 of its first heap; channel = g: that channel's runs, a block
-        of heaps with nchan = 1.
-        A two-bit file (NBIT 2) yields (the whole excision windows that hold the block, npart, first_sample) likewise; a file
-        shorter than one window gives no blocks."""
-        full, rest = self.nblocks(lt)
-        ppb, step, ovl, bps = lt.cfg.parts_per_block, lt.nsamp_step, lt.nsamp_overlap, self.bytes_per_sample
-        per_chan = self.info.npol * self.info.ndim
-        for b in range(full + (1 if rest else 0)):
-            npart = ppb if b < full else rest
-            nsamp = npart * step + ovl
-            s0 = b * ppb * step
-            if self.twobit:
-                if channel is not None:
-                    raise DspsrAmdError("dspsr_amd.DadaFile.blocks: a two-bit file holds one channel; channel=%d asked" % channel)
-                # whole windows from the one that holds the block's first sample; first_sample: where in it that sample lies
-                ns = lt.twobit.nsample
-                wb = (ns // 4) * self.info.npol
-                first = s0 % ns
-                yield self._map[(s0 // ns) * wb:-(-(s0 + nsamp) // ns) * wb], npart, first
-                continue
-            if self.heaps:
-                first = s0 % HEAP_NSAMP
-                h0, nheap = s0 // HEAP_NSAMP, -(-(first + nsamp) // HEAP_NSAMP)
-                src = self._map[h0 * self.heap_bytes:(h0 + nheap) * self.heap_bytes]
-                if channel is not None:
-                    src = np.ascontiguousarray(src.reshape(nheap, self.info.npol, self.info.nchan, HEAP_NSAMP * 2)[:, :, channel, :]).reshape(-1)
-                yield src, npart, first
-                continue
-            src = self._map[s0 * bps:(s0 + nsamp) * bps]
-            if channel is not None:
-                src = np.ascontiguousarray(src.reshape(nsamp, self.info.nchan, per_chan)[:, channel, :]).reshape(-1)
-            yield src, npart
+    def read_units(self, g0, n, channel, granule):
+        """Views of the memory-mapped file (process_host_blocks stages them through its own pinned buffers); channel = g: input
+        channel g's bytes, [t][pol][dim] -- of a file of heaps that channel's runs, a block of heaps with nchan = 1.  A two-bit file
+        holds one channel; one shorter than a window gives no blocks."""
+        unit = granule * self.sample_bits // 8
+        src = self.data[g0 * unit:(g0 + n) * unit]
+        if channel is None:
+            return src
+        if self.twobit:
+            raise DspsrAmdError("dspsr_amd.DadaFile.blocks: a two-bit file holds one channel; channel=%d asked" % channel)
+        info = self.info                                                # a heap is [pol][chan][256][2], a sample [chan][pol][dim]
+        shape = (n, info.npol, info.nchan, HEAP_NSAMP * 2) if self.heaps else (n, 1, info.nchan, info.npol * info.ndim)
+        return np.ascontiguousarray(src.reshape(shape)[:, :, channel, :]).reshape(-1)
 
 
 def rfi_filter_from_file(f, lt, log=None, chunk_blocks=4096, **kw):
@@ -362,7 +320,7 @@ def rfi_filter_from_file(f, lt, log=None, chunk_blocks=4096, **kw):
     pos, chunk = 0, chunk_blocks * rfi.BLOCK
     while not filt.complete and pos + rfi.BLOCK <= f.ndat:
         n = min(chunk, ((f.ndat - pos) // rfi.BLOCK) * rfi.BLOCK)
-        host = torch.from_numpy(np.array(f._map[pos * f.bytes_per_sample:(pos + n) * f.bytes_per_sample]))
+        host = torch.from_numpy(np.array(f.samples(pos, n)))
         dev = host.to("cuda:%d" % lt.ctx.device)
         torch.cuda.synchronize(lt.ctx.device)               # the copy ran on torch's stream, the kernel runs on the pipeline's
         pos += filt.integrate_raw(dev, n) or n
@@ -376,7 +334,6 @@ def fold_file(path, cfg, polyco=None, device=0, stream=None, reference_phase=0.0
     """The reference's `dspsr file.dada -F nchan:D ...` on one GPU: open the file, build the pipeline from its header,
     feed every block, close the last sub-integration.  Returns the LoadToFold (its .subints hold the results -- with several
     `targets` (pipeline.FoldTarget), .pulsars[k].subints; the caller closes it)."""
-    from .guppi import open_input
     from .pipeline import LoadToFold
     f = open_input(path)                                     # a DadaFile, or a guppi.GuppiFile where the file is GUPPI raw
     lt = LoadToFold(cfg, f.info, device=device, stream=stream, polyco=polyco, reference_phase=reference_phase,
@@ -392,7 +349,7 @@ def fold_file(path, cfg, polyco=None, device=0, stream=None, reference_phase=0.0
     if f.nblocks(lt) == (0, 0):
         lt.close()
         raise DspsrAmdError("dspsr_amd.fold_file: %s holds %d samples, fewer than one overlap-save part (%d)"
-                            % (path, f._usable(lt), lt.nsamp_overlap + lt.nsamp_step))
+                            % (path, f.usable(lt), lt.nsamp_overlap + lt.nsamp_step))
     lt.process_host_blocks(f.blocks(lt))
     if lt.ndat_total or lt.pulsars:
         lt.finish_subint()
@@ -405,7 +362,6 @@ def search_blocks_file(path, cfg, device=0, stream=None, log=None):
     Returns (header_values, [(bytes, DAT_SCL, DAT_OFFS) on the host, ...]): what pipeline.write_search_blocks takes.  `log`: where the
     reference's `requested tsamp / actual tsamp` line goes."""
     import torch
-    from .guppi import open_input
     from .pipeline import LoadToFITS
     f = open_input(path)
     lt = LoadToFITS(cfg, f.info, device=device, stream=stream)

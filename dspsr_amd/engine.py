@@ -255,19 +255,10 @@ class FilterbankEngine(_Owned):
             raise DspsrAmdError("dspsr_amd.FilterbankEngine: %s holds %d elements per row, %d needed" % (what, have, need))
 
     def _raw_bytes(self, npart, layout=_lib.RAW_GENERIC):
+        """bytes of a call of `npart` parts whose layout word (the call's first sample inside it) is `layout`"""
         c = self.cfg
-        nsamp = npart * self.nsamp_step + self.nsamp_overlap
-        if _lib.is_heaps(layout):
-            # whole heaps from the one that holds the call's first sample on
-            return _lib.heap_block_bytes(layout >> 8, nsamp, c.input_nchan, c.npol)
-        if _lib.is_guppi(layout):
-            # from the data section of the block that holds the call's first sample to the last kept sample of the last run
-            return _lib.guppi_block_bytes(layout >> 8, nsamp, c.input_nchan, c.npol, *self._guppi_geometry())
-        if layout == _lib.RAW_CASPSR:
-            # 4 samples of pol0 then 4 of pol1: the block must hold WHOLE 8-byte groups (its last samples' pol1 bytes lie
-            # up to 4 bytes behind their pol0 bytes; CASPSRUnpacker.C:132-187 unpacks group by group)
-            return ((nsamp + 3) // 4) * 8
-        return nsamp * c.input_nchan * c.npol * (1 if c.real_input else 2)
+        return _lib.raw_block_bytes(layout & 0xff if layout >= 0 else layout, npart * self.nsamp_step + self.nsamp_overlap, c.input_nchan, c.npol,
+                                    1 if c.real_input else 2, layout >> 8, self._guppi_geometry() if _lib.is_guppi(layout) else None)
 
     def takes_heaps(self) -> bool:
         """True: the raw entry points read a block of MeerKAT heaps inside their one tile pass (dspsr_amd_filterbank_takes_heaps)."""

@@ -11,13 +11,13 @@ Host logic only.  Built: 8-bit complex samples of several channels (PKTFMT 1SFA 
 PKTFMT VDIF and SIMPLE, OBSNCHAN 1, DIRECTIO headers, a BACKEND the unpacker does not match."""
 from __future__ import annotations
 
-import math
 import os
 import re
 
 import numpy as np
 
 from .engine import DspsrAmdError
+from .inputs import InputFile, open_input, raw_form, tsamp_us          # noqa: F401  (open_input: the factory's earlier home)
 
 CARD = 80                    # bytes of a header card
 MAX_CARDS = 2304             # GUPPIFile.C:49
@@ -80,17 +80,7 @@ def _number(cards, key, conv):
         return conv(float(m.group(0).replace("D", "E").replace("d", "e")))
 
 
-def _tsamp_us(tbin):
-    """TBIN in microseconds such that InputInfo.rate = 1e6 / tsamp_us is the reference's 1 / TBIN to the bit where a neighbour of
-    TBIN * 1e6 gives it (the product alone may round the other way)"""
-    rate, t = 1.0 / tbin, tbin * 1e6
-    for c in (t, math.nextafter(t, 0.0), math.nextafter(t, math.inf)):
-        if 1e6 / c == rate:
-            return c
-    return t
-
-
-class GuppiFile:
+class GuppiFile(InputFile):
     """dsp::GUPPIFile + the block loop of dsp::IOManager: an 8-bit GUPPI / PUPPI raw file cut into the blocks LoadToFold consumes.
     Opening indexes the file once -- header offset, data offset and PKTIDX of every block -- and applies the reference's rules:
     a first block of another BLOCSIZE is skipped (GUPPIFile.C:144-164); the stream holds nblocks * block_nsamp samples with nblocks from
@@ -100,9 +90,6 @@ class GuppiFile:
 
     .info is the pipeline.InputInfo of the stream (info.guppi = (block_nsamp, chan_stride, BLOCSIZE): the drivers take the layout
     from it), .stream the delivered blocks: a data offset in the file each, or None for a block of zeros."""
-
-    heaps = twobit = False
-    guppi = True
 
     def __init__(self, path: str, log=None):
         from .pipeline import InputInfo
@@ -132,7 +119,8 @@ class GuppiFile:
             self.ndat = nblocks * self.block_nsamp
             self.index = self._index(f, size)
         self.stream = self._stream(self.index, log)[:nblocks]
-        self._map = np.memmap(path, dtype=np.int8, mode="r") if size else np.zeros(0, np.int8)
+        self.data = np.memmap(path, dtype=np.int8, mode="r") if size else np.zeros(0, np.int8)
+        self.form = raw_form(self.info)
 
     def _parse(self, c, InputInfo):
         who = "dspsr_amd.GuppiFile"
@@ -175,7 +163,7 @@ class GuppiFile:
         self.basis = "Circular" if c["FD_POLN"].strip().upper().startswith("CIR") else "Linear"
         self.receiver, self.coordinates = c["FRONTEND"], (c["RA_STR"], c["DEC_STR"])
         self.info = InputInfo(centre_frequency=_number(c, "OBSFREQ", float), bandwidth=_number(c, "OBSBW", float), nchan=nchan, npol=npol,
-                              ndim=ndim, tsamp_us=_tsamp_us(tbin), machine=backend, start_seconds=0.0, mjd_day=_number(c, "STT_IMJD", int),
+                              ndim=ndim, tsamp_us=tsamp_us(tbin), machine=backend, start_seconds=0.0, mjd_day=_number(c, "STT_IMJD", int),
                               mjd_sec=_number(c, "STT_SMJD", int) + t_offset, source=c["SRC_NAME"], telescope=c["TELESCOP"], nbit=8,
                               guppi=(self.block_nsamp, self.chan_stride, self.blocsize))
         self.extras = {"nbit": 8, "ndat": 0, "offset_bytes": 0, "source": c["SRC_NAME"], "telescope": c["TELESCOP"], "dual_sideband": None,
@@ -218,16 +206,9 @@ class GuppiFile:
             last = idx
         return stream
 
-    def _usable(self, lt=None):
+    def usable(self, lt=None):
         """Samples the block loop reads: the stream's, never past ndat (skipped blocks leave the stream shorter than ndat)"""
         return min(self.ndat, len(self.stream) * self.block_nsamp)
-
-    def nblocks(self, lt):
-        """(whole pipeline blocks, parts of the ragged last block), as DadaFile.nblocks"""
-        ndat = self._usable(lt)
-        if ndat < lt.nsamp_overlap + lt.nsamp_step:
-            return 0, 0
-        return divmod((ndat - lt.nsamp_overlap) // lt.nsamp_step, lt.cfg.parts_per_block)
 
     def sections(self, k0, nblk, channel=None):
         """int8 host array: the data sections of stream blocks k0 ... k0 + nblk - 1, BLOCSIZE bytes each and contiguous (zeros for a
@@ -239,33 +220,12 @@ class GuppiFile:
                 out[i * per:(i + 1) * per] = 0
             else:
                 a = data if channel is None else data + channel * self.chan_stride
-                out[i * per:(i + 1) * per] = self._map[a:a + per]
+                out[i * per:(i + 1) * per] = self.data[a:a + per]
         return out
 
-    def blocks(self, lt, channel=None):
-        """Yield (int8 host array, npart, first) for the driver `lt` (its parts_per_block, nsamp_step, nsamp_overlap): the whole
-        stream blocks that hold the pipeline block -- overlap-save parts straddle GUPPI blocks freely -- with block_stride =
-        BLOCSIZE, and where in the first one's runs the pipeline block's first sample lies (guppi_at(first) is the layout word).
-        channel = g: channel g's runs only, a block with nchan = 1 and block_stride = chan_stride: what rank g of a sub-band sharded
-        run reads."""
+    def read_units(self, g0, n, channel, granule):
+        """The whole stream blocks that hold a pipeline block (InputFile.blocks), with block_stride = BLOCSIZE; channel = g: channel
+        g's runs only, a block with nchan = 1 and block_stride = chan_stride."""
         if channel is not None and not 0 <= channel < self.info.nchan:
             raise DspsrAmdError("dspsr_amd.GuppiFile.blocks: channel=%d outside the %d channels" % (channel, self.info.nchan))
-        full, rest = self.nblocks(lt)
-        ppb, step, ovl, bn = lt.cfg.parts_per_block, lt.nsamp_step, lt.nsamp_overlap, self.block_nsamp
-        for b in range(full + (1 if rest else 0)):
-            npart = ppb if b < full else rest
-            s0 = b * ppb * step
-            first = s0 % bn
-            yield self.sections(s0 // bn, -(-(first + npart * step + ovl) // bn), channel), npart, first
-
-
-def open_input(path: str, log=None):
-    """The input factory of the drivers and tools: a sigproc.SigprocFile where the file is a SIGPROC filterbank file, a GuppiFile where
-    it is GUPPI raw (is_valid), else a dada.DadaFile.  The format is recognised from the file, never from its name."""
-    from . import sigproc
-    if sigproc.is_valid(path):
-        return sigproc.SigprocFile(path)
-    if is_valid(path):
-        return GuppiFile(path, log=log)
-    from .dada import DadaFile
-    return DadaFile(path)
+        return self.sections(g0, n, channel)

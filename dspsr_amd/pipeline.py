@@ -22,7 +22,8 @@ import numpy as np
 from . import _lib
 from .engine import (Context, ConvolutionEngine, CyclicFoldEngine, Dedispersion, DetectionEngine, DspsrAmdError, SpectralKurtosisEngine, FilterbankEngine, FITSDigitizer, FoldEngine, PhaseLockedFilterbankEngine, plfb_check_shape, Rescale, SampleDelay, add_fpt, copy_data_fpt, fourth_moment, unpack_sigproc_fpt,
                      dedispersion_sample_delays, detect_raw, eight_bit_scale, fscrunch_fpt, pscrunch_tfp, sigproc_digitize, sigproc_digitize_fpt,
-                     tfp_filterbank, tscrunch_fpt, twobit_block_bytes)
+                     tfp_filterbank, tscrunch_fpt)
+from .inputs import FORMS, VOLTAGES, raw_form, refuse_forms
 
 
 def move_tail_fpt(ctx, buf, dst, src, n, unit=1):
@@ -516,7 +517,7 @@ def write_phase_series(path, sub, info: "InputInfo", cfg: "Config", *, nchan=Non
     nchan = nchan or cfg.nchan
     hits = np.asarray(sub["hits"])
     nbin = hits.shape[-1]
-    if state is None and ndim is None and getattr(info, "detected", None) is not None:     # detected input: the file's own state
+    if state is None and ndim is None and info.detected is not None:                       # detected input: the file's own state
         state, ndim = info.detected, 1
     if state is None and ndim is None and square_law_state(cfg, info, strict=False):       # -d 1 / -d 2 / one polarisation: rows of ndim 1
         state, ndim = square_law_state(cfg, info, strict=False)[0], 1
@@ -1010,8 +1011,8 @@ def plfb_check(cfg: "Config", info: "InputInfo", ntargets=0, subband=None, dump_
 
 def rfi_check(cfg: "Config", info: "InputInfo", subband=None):
     """What a -R run refuses, before any device resource is opened."""
-    who = "dspsr_amd.LoadToFold: the RFI filter (-R)"
-    refuse_guppi(who, info, "the Bandpass operator's integrate_raw reads the generic and CASPSR byte orders")
+    who, instead = "dspsr_amd.LoadToFold: the RFI filter (-R)", "the Bandpass operator's integrate_raw reads the generic and CASPSR byte orders"
+    refuse_forms(who, info, FORMS - {"guppi"}, instead)          # (GUPPI raw blocks are refused first and heaps last, as they always were)
     if cfg.calibrator is not None:
         raise DspsrAmdError("%s with -pac (calibrator) is not built: the product of the mask, the chirp and a matrix response is open" % who)
     if info.nchan > 1:
@@ -1026,9 +1027,9 @@ def rfi_check(cfg: "Config", info: "InputInfo", subband=None):
                             % (who, cfg.convolve_when, cfg.dispersion_measure))
     if subband is not None:
         raise DspsrAmdError("%s is not built for sub-band sharded runs (subband=%d)" % (who, subband))
-    if getattr(info, "nbit", 8) != 8:
+    if info.nbit != 8:
         raise DspsrAmdError("%s reads 8-bit input (info.nbit=%d): 16-bit input is not built" % (who, info.nbit))
-    refuse_heaps(who, info, "the Bandpass operator's integrate_raw reads the generic and CASPSR byte orders")
+    refuse_forms(who, info, FORMS - {"heaps"}, instead)
 
 
 def calibrator_response(cfg: "Config", info: "InputInfo", subband=None):
@@ -1094,7 +1095,7 @@ def square_law_check(cfg: "Config", info: "InputInfo"):
     not formed by Detection::square_law on this path yet (DESIGN.md section 11)."""
     who = "dspsr_amd.LoadToFold: npol=%d (-d %d)" % (cfg.npol, cfg.npol)
     for on, what in ((cfg.sk_zap, "spectral kurtosis (-skz): dsp::SpectralKurtosis hands its rows to Detection::polarimetry here"),
-                     (getattr(info, "nbit", 8) == 2, "two-bit input (NBIT 2): the unpacker's weights are carried to the Coherence fold alone"),
+                     (raw_form(info).name == "twobit", "two-bit input (NBIT 2): the unpacker's weights are carried to the Coherence fold alone"),
                      (cfg.calibrator is not None, "the calibrator (-pac): the matrix response has no square-law form"),
                      (cfg.convolve_when != "during", "convolve_when=%r (-F N, -F N:B): built for -F N:D (convolve_when = during)" % (cfg.convolve_when,))):
         if on:
@@ -1170,12 +1171,6 @@ def twobit_check(cfg: "Config", info: "InputInfo", ntargets=0, subband=None, dum
                       twobit.levels(nsample, nlow_min, nlow_max, threshold))
 
 
-def refuse_twobit(who, info):
-    """Plan-time refusal of a driver that has no two-bit unpacker."""
-    if getattr(info, "nbit", 8) == 2:
-        raise DspsrAmdError("%s: two-bit input (NBIT 2) is not built on this path; dspsr_amd.LoadToFold folds it with -F N:D" % who)
-
-
 def sk_check(cfg: "Config", info: "InputInfo", ntargets=0, subband=None, dump_before=()):
     """What a -skz run refuses, on the host, after every refusal the run had without it.  Returns the channel range the engine gets."""
     who = "dspsr_amd.LoadToFold: spectral kurtosis (-skz)"
@@ -1234,32 +1229,6 @@ def filterbank_output(info, r, nsub):
     return rate, info.start_seconds + r.impulse_pos / rate, float(n_fft) * float(r.ndat)
 
 
-def machine_layout(machine):
-    """The raw layout of the 8-bit blocks of INSTRUMENT `machine`."""
-    return _lib.HEAP_MACHINES.get(machine, _lib.RAW_CASPSR if machine == "CASPSR" else _lib.RAW_GENERIC)
-
-
-def refuse_heaps(who, info, instead):
-    """Plan-time refusal of a driver that has no reader for MeerKAT heaps."""
-    if info.machine in _lib.HEAP_MACHINES:
-        raise DspsrAmdError("%s: the heap order of INSTRUMENT %s (MeerKAT beamformer: 256-sample runs per polarisation and channel) is not "
-                            "built on this path; %s" % (who, info.machine, instead))
-
-
-def refuse_guppi(who, info, instead):
-    """Plan-time refusal of a driver that has no reader for GUPPI raw blocks."""
-    if getattr(info, "guppi", None) is not None:
-        raise DspsrAmdError("%s: the block order of a GUPPI raw file (BACKEND %s: time-ordered runs per channel inside every block) is not "
-                            "built on this path; %s" % (who, info.machine, instead))
-
-
-def refuse_detected(who, info):
-    """Plan-time refusal of a driver that reads voltages: detected input (a SIGPROC filterbank file) has none."""
-    if getattr(info, "detected", None) is not None:
-        raise DspsrAmdError("%s: the input is detected already (STATE %s, %d channels of %d-bit values): this driver forms its spectra "
-                            "from voltages; dspsr_amd.LoadToFold folds such a file" % (who, info.detected, info.nchan, info.nbit))
-
-
 def detected_check(cfg: "Config", info: "InputInfo", subband=None, dump_before=()):
     """What a fold of detected input (info.detected: the first branch of LoadToFold::construct, LoadToFold1.C:126-180) refuses by
     name, before any device resource is opened, each with the option's spelling; returns the Config the chain is built with: the
@@ -1290,33 +1259,21 @@ def detected_check(cfg: "Config", info: "InputInfo", subband=None, dump_before=(
     return dataclasses.replace(cfg, npol=info.npol, ndim=1, stokes=False, fused_fold=False, force_fused=False)
 
 
-def raw_block_bytes(layout, nsamp, nchan, npol, ndim, first_sample=0, guppi=None):
-    """Bytes of a block of `nsamp` samples in `layout` (heaps: from `first_sample` of the first heap on, whole heaps; GUPPI raw
-    blocks of geometry `guppi`: from the data section that holds `first_sample` to the last kept sample of the last run)."""
-    if _lib.is_heaps(layout):
-        return _lib.heap_block_bytes(first_sample, nsamp, nchan, npol)
-    if _lib.is_guppi(layout):
-        return _lib.guppi_block_bytes(first_sample, nsamp, nchan, npol, *guppi)
-    if first_sample:
-        raise DspsrAmdError("dspsr_amd.pipeline: first_sample=%d given for a layout without heaps" % first_sample)
-    if layout == _lib.RAW_CASPSR:
-        return ((nsamp + 3) // 4) * 8          # whole 4-sample groups (4 B pol0 | 4 B pol1)
-    return nsamp * nchan * npol * ndim
-
-
 def _adopt_front(drv, fb):
-    """`fb` (a FilterbankEngine, or one of the two wrappers above) becomes the front end of the driver: what every path reads of it."""
+    """`fb` (a FilterbankEngine, or one of the two wrappers above) becomes the front end of the driver: what every path reads of it.
+    The form of the blocks (drv.form) is the driver's plan; drv.layout is the layout word of the block in hand."""
     drv.fb = fb
     drv.nkeep, drv.nsamp_step, drv.nsamp_overlap = fb.nkeep, fb.nsamp_step, fb.nsamp_overlap
     drv.scale8 = eight_bit_scale()
-    drv.layout = machine_layout(drv.info.machine)
-    drv.guppi = None
-    g = getattr(drv.info, "guppi", None)
-    if g is not None:
-        # a GUPPI raw file: the layout comes from the file, not from the machine; a sub-band rank reads one channel's runs
-        drv.guppi = (g[0], g[1], g[1] if getattr(drv, "subband", None) is not None else g[2])
-        drv.layout = _lib.RAW_GUPPI
-        fb.set_guppi(*drv.guppi)
+    drv.layout, drv.guppi = drv.form.layout, drv.form.geometry
+    if drv.form.geometry is not None:                   # a GUPPI raw file: the engine takes the geometry of its blocks once
+        fb.set_guppi(*drv.form.geometry)
+
+
+def _block_layout(drv, first_sample):
+    """The layout word of THIS block, for every path below: it names the block's first sample where blocks start inside a heap, a
+    GUPPI raw block or an excision window, and refuses one where they do not."""
+    drv.layout = drv.form.layout_word(first_sample)
 
 
 def _open_convolving_front(drv, r, nsub, in_nchan, kernel, **setup):
@@ -1434,10 +1391,6 @@ class _BackEnd:
         """Observation::get_state of what the mode folds, where the mode and not Detection decides it (None: Detection's)"""
         return None
 
-    def block_bytes(self, nsamp):
-        """bytes of a block of `nsamp` samples where the mode reads the file's bytes itself (None: the front end's layout)"""
-        return None
-
     def vitals(self):
         """the lines of LoadToFold.vitals where the run has no filter to report (None: the driver's)"""
         return None
@@ -1540,7 +1493,7 @@ class DetectFold(_RowFold):
                 ndim=fold_ndim if det else 2, nbit=32, rate=lt.out_rate, mjd_day=info.mjd_day,
                 mjd_sec=info.mjd_sec + lt.out_start,
                 state=lt.state_name() if det else "Analytic",
-                source=getattr(info, "source", "unknown"), telescope=getattr(info, "telescope", "unknown"))
+                source=info.source, telescope=info.telescope)
         if "Fold" in lt.dumps:
             lt.fused_mode, lt.fused_fold = 0, False          # the detected samples must exist in HBM to be dumped
 
@@ -1654,9 +1607,6 @@ class DetectedFold(_RowFold):
     def state_name(self):
         return self.lt.info.detected
 
-    def block_bytes(self, nsamp):
-        return nsamp * self.lt.spectrum_bytes                # whole spectra
-
     def vitals(self):
         return ["dspsr: blocksize=%d samples or %g MB" % (self.lt.cfg.parts_per_block, self.lt.block_bytes() / (1024.0 * 1024.0))]
 
@@ -1669,8 +1619,7 @@ class DetectedFold(_RowFold):
         lt.response = None
         lt.out_rate, lt.out_start, lt.scalefac = info.rate, info.start_seconds, 1.0
         lt.nkeep, lt.nsamp_step, lt.nsamp_overlap = 1, 1, 0
-        lt.layout, lt.guppi, lt.scale8 = _lib.RAW_GENERIC, None, 1.0
-        lt.spectrum_bytes = info.npol * info.nchan * info.nbit // 8
+        lt.layout, lt.scale8 = lt.form.layout, 1.0
         if cfg.interchan_dedispersion:
             lt._delays = dedispersion_sample_delays(info.centre_frequency, info.bandwidth, cfg.dispersion_measure, info.nchan, lt.out_rate)
             lt.sd = DelayCarry(lt._delays)
@@ -1963,10 +1912,12 @@ class LoadToFold:
 
     def _plan(self, cfg, info, polyco, reference_phase, subband, dump_before, targets):
         """The host side of the constructor: what the run refuses, in the order it always has, and every number that needs no device."""
-        detected = getattr(info, "detected", None) is not None
+        # the form of the blocks: a sub-band rank reads one channel's runs of a GUPPI block, a two-bit run whole excision windows
+        self.form = raw_form(info, channel_sharded=subband is not None, excision_nsample=cfg.excision_nsample)
+        detected = self.form.name == "detected"
         if detected:                                     # a SIGPROC filterbank file: nbit counts bits per detected value
             cfg = detected_check(cfg, info, subband, dump_before)
-        elif getattr(info, "nbit", 8) == 2:
+        elif self.form.name == "twobit":
             self.twobit = twobit_check(cfg, info, len(targets), subband, dump_before)
         if cfg.zap_rfi:
             rfi_check(cfg, info, subband)
@@ -2195,17 +2146,9 @@ class LoadToFold:
 
     # bytes of one block of `npart` parts
     def block_bytes(self, npart=None, first_sample=0):
-        """first_sample: a block of heaps begins at that sample of its first heap (0 for every other layout)."""
-        npart = npart or self.cfg.parts_per_block
-        nsamp = npart * self.nsamp_step + self.nsamp_overlap
-        mode = getattr(self, "mode", None)   # (the method is also borrowed by stand-ins that hold the geometry alone)
-        own = mode.block_bytes(nsamp) if mode is not None else None
-        if own is not None:                  # (detected input: whole spectra)
-            return own
-        tb = getattr(self, "twobit", None)
-        if tb is not None:                   # whole excision windows from the one that holds the block's first sample
-            return twobit_block_bytes(first_sample, nsamp, tb.nsample, self.info.npol)
-        return raw_block_bytes(self.layout, nsamp, self.in_nchan, self.info.npol, self.info.ndim, first_sample, getattr(self, "guppi", None))
+        """first_sample: where in its first heap, GUPPI raw block or excision window the block begins (0 for every other form)."""
+        nsamp = (npart or self.cfg.parts_per_block) * self.nsamp_step + self.nsamp_overlap
+        return self.form.block_bytes(nsamp, self.in_nchan, self.info.npol, self.info.ndim, first_sample)
 
     def seek_block(self, k):
         """Time-slice replicas: the next block is block k of the stream (blocks of parts_per_block parts), not the one
@@ -2238,17 +2181,11 @@ class LoadToFold:
         if raw.numel() < self.block_bytes(npart, first_sample):
             raise DspsrAmdError("dspsr_amd.LoadToFold.process_block: block holds %d bytes, %d needed"
                                 % (raw.numel(), self.block_bytes(npart, first_sample)))
-        if _lib.is_heaps(self.layout):
-            self.layout = _lib.raw_at(self.layout & 0xff, first_sample)      # the layout word of THIS block, for every path below
-        elif _lib.is_guppi(self.layout):
-            self.layout = _lib.guppi_at(first_sample)
+        _block_layout(self, first_sample)
         if cfg.zap_rfi and self.rfi_filter is None:
             raise DspsrAmdError("dspsr_amd.LoadToFold.process_block: zap_rfi (-R) is set and no filter has been given: "
                                 "call set_rfi_filter before the first block")
         if self.twobit is not None:
-            if not 0 <= first_sample < self.twobit.nsample:
-                raise DspsrAmdError("dspsr_amd.LoadToFold.process_block: first_sample=%d is not inside a window of %d samples"
-                                    % (first_sample, self.twobit.nsample))
             self.twobit.first_sample = first_sample
         nout = self.mode.process(raw, npart, events)              # (the pieces were planned from ndat_out as it was)
         self.ndat_out += nout
@@ -2700,8 +2637,7 @@ class ConvolvingFront(SearchFront):
 
     def _geometry(self):
         cfg, info, who = self.cfg, self.info, self.who
-        refuse_detected(who, info)
-        refuse_twobit(who, info)
+        self.form = refuse_forms(who, info, VOLTAGES)
         if cfg.npol not in (1, 2, 4):
             raise DspsrAmdError("%s: npol=%d (Intensity 1 / PPQQ 2 / Coherence 4 are built; NthPower 3 is not)" % (who, cfg.npol))
         if cfg.npol >= 2 and info.npol != 2:
@@ -2749,13 +2685,10 @@ class ConvolvingFront(SearchFront):
 
     def block_bytes(self, npart=None, first_sample=0):
         nsamp = (npart or self.cfg.parts_per_block) * self.nsamp_step + self.nsamp_overlap
-        return raw_block_bytes(self.layout, nsamp, self.info.nchan, self.info.npol, self.info.ndim, first_sample, getattr(self, "guppi", None))
+        return self.form.block_bytes(nsamp, self.info.nchan, self.info.npol, self.info.ndim, first_sample)
 
     def _detect(self, raw, npart, first_sample, out, ts):
-        if _lib.is_heaps(self.layout):
-            self.layout = _lib.raw_at(self.layout & 0xff, first_sample)
-        elif _lib.is_guppi(self.layout):
-            self.layout = _lib.guppi_at(first_sample)
+        _block_layout(self, first_sample)
         block = dict(raw=raw, layout=self.layout, scale=self.scale8)
         if self.fused:
             return self.fb.perform_search(out, self.carry, self.carry_count, npart, ts, self.state, **block)
@@ -2781,16 +2714,14 @@ class ChannelisedFront(SearchFront):
 
     def _geometry(self):
         cfg, info, who = self.cfg, self.info, self.who
-        refuse_detected(who, info)
-        refuse_twobit(who, info)
+        refuse_forms(who, info, VOLTAGES)                # (the voltages it does not read are refused behind NDIM and NBIT, as they always were)
         if info.ndim != 2:
             raise DspsrAmdError("%s: NDIM=%d; complex (NDIM 2) channelised voltages only" % (who, info.ndim))
-        if getattr(info, "nbit", 8) != 8:
+        if info.nbit != 8:
             raise DspsrAmdError("%s: NBIT=%d; this path reads 8-bit samples" % (who, info.nbit))
-        if info.machine == "CASPSR":
-            raise DspsrAmdError("%s: the CASPSR byte order is not built on this path (generic DADA order only)" % who)
-        refuse_heaps(who, info, "dspsr_amd.unpack_heaps_fpt gives the float rows, and -F N:D (dspsr_amd.LoadToFilCoherent) reads the heaps")
-        refuse_guppi(who, info, "dspsr_amd.unpack_guppi_fpt gives the float rows, and -F N:D (dspsr_amd.LoadToFilCoherent) reads the blocks")
+        self.form = refuse_forms(who, info, {"generic"}, {
+            "heaps": "dspsr_amd.unpack_heaps_fpt gives the float rows, and -F N:D (dspsr_amd.LoadToFilCoherent) reads the heaps",
+            "guppi": "dspsr_amd.unpack_guppi_fpt gives the float rows, and -F N:D (dspsr_amd.LoadToFilCoherent) reads the blocks"})
         if cfg.npol not in (1, 2, 4):
             raise DspsrAmdError("%s: npol=%d (Intensity 1 / PPQQ 2 / Coherence 4 are built; NthPower 3 is not)" % (who, cfg.npol))
         if info.npol not in (1, 2):
@@ -2819,7 +2750,7 @@ class ChannelisedFront(SearchFront):
 
     def block_bytes(self, ndat=None, first_sample=0):
         ndat = self.cfg.parts_per_block if ndat is None else ndat
-        return raw_block_bytes(_lib.RAW_GENERIC, ndat, self.info.nchan, self.info.npol, 2, first_sample)
+        return self.form.block_bytes(ndat, self.info.nchan, self.info.npol, 2, first_sample)
 
     def _detect(self, raw, ndat, first_sample, out, ts):
         carry, count = (self.carry, self.carry_count) if self.fused else (None, None)
@@ -2827,10 +2758,10 @@ class ChannelisedFront(SearchFront):
 
     def file_calls(self, f):
         """DadaFile `f` cut into this front end's calls: runs of parts_per_block time samples, the last one shorter"""
-        bps, step = f.bytes_per_sample, self.cfg.parts_per_block
+        step = self.cfg.parts_per_block
         for s0 in range(0, f.ndat, step):
             ndat = min(step, f.ndat - s0)
-            yield f._map[s0 * bps:(s0 + ndat) * bps], ndat
+            yield f.samples(s0, ndat), ndat
 
 
 class SigprocOutput:
@@ -2915,17 +2846,14 @@ class LoadToFil(_SearchDriver):
 
     def _plan(self):
         cfg, info = self.cfg, self.info
-        refuse_detected("dspsr_amd.LoadToFil", info)
-        refuse_twobit("dspsr_amd.LoadToFil", info)
-        refuse_heaps("dspsr_amd.LoadToFil", info, "channelised complex voltages take -F N:D (dspsr_amd.LoadToFilCoherent)")
-        refuse_guppi("dspsr_amd.LoadToFil", info, "channelised complex voltages take -F N:D (dspsr_amd.LoadToFilCoherent)")
+        form = refuse_forms("dspsr_amd.LoadToFil", info, {"generic", "caspsr"}, "channelised complex voltages take -F N:D (dspsr_amd.LoadToFilCoherent)")
         if info.npol != 2 or info.ndim != 1 or info.nchan != 1:
             raise DspsrAmdError("dspsr_amd.LoadToFil: 8-bit real dual-polarisation single-channel input only")
         if cfg.parts_per_block % cfg.tscrunch:
             raise DspsrAmdError("dspsr_amd.LoadToFil: parts_per_block=%d is not a multiple of tscrunch=%d"
                                 % (cfg.parts_per_block, cfg.tscrunch))
         self.scale8 = eight_bit_scale()
-        self.layout = _lib.RAW_CASPSR if info.machine == "CASPSR" else _lib.RAW_GENERIC
+        self.layout = form.layout
         self.out_rate = info.rate / (2.0 * cfg.nchan) / cfg.tscrunch           # TFPFilterbank + TScrunch
         self.bytes_per_sample = cfg.nchan * _nbits(cfg.nbit) // 8
         self.ndat_out = 0
@@ -3002,7 +2930,7 @@ class _FrontToFil(_SearchDriver):
         return self.out.header_values(self.front.tsamp, self.front.out_start)
 
 
-for _name in ("response", "fb", "nkeep", "nsamp_step", "nsamp_overlap", "layout", "scale8", "fb_rate", "fused", "ts", "nchan_out", "out_rate",
+for _name in ("response", "fb", "nkeep", "nsamp_step", "nsamp_overlap", "form", "layout", "scale8", "fb_rate", "fused", "ts", "nchan_out", "out_rate",
               "out_start", "input_scale", "sd", "sample_delay", "carry_count", "block_bytes", "detect_scrunch", "file_calls"):
     setattr(_FrontToFil, _name, _of("front", _name))
 for _name in ("bytes_per_sample", "ndat_out", "rescale", "rescale_interval"):
@@ -3164,9 +3092,7 @@ class LoadToFITS(_SearchDriver):
 
     def _plan(self):
         who, cfg, info = "dspsr_amd.LoadToFITS", self.cfg, self.info
-        if getattr(info, "detected", False):
-            raise DspsrAmdError("%s: detected input (the PScrunch branch, LoadToFITS.C:501-514) is not built" % who)
-        refuse_twobit(who, info)
+        refuse_forms(who, info, VOLTAGES, own={"detected": "detected input (the PScrunch branch, LoadToFITS.C:501-514) is not built"})
         if cfg.integration_length:
             raise DspsrAmdError("%s: -L (splitting the output into files of integration_length seconds) is not built" % who)
         if cfg.npol not in (1, 2, 4):

@@ -22,6 +22,7 @@ import numpy as np
 from . import _lib
 from ._lib import lib
 from .engine import BandpassEngine, DspsrAmdError, eight_bit_scale
+from .inputs import raw_form
 
 BLOCK = 8 * 1024                      # RFIFilter.C:26: maximum_block_size, the unit the reference reads the interval in
 
@@ -98,7 +99,8 @@ class RfiFilter:
         self.log = log
         self.bandpass = BandpassEngine(ctx)
         self.bandpass.set_shape(info.nchan, info.npol, info.ndim, nchan_bandpass, info.npol)
-        self.layout = _lib.RAW_CASPSR if info.machine == "CASPSR" else _lib.RAW_GENERIC
+        self.form = raw_form(info)
+        self.layout = self.form.layout
         self.scale8 = eight_bit_scale()
         self.integration_length = 0.0
         self.result = None
@@ -117,7 +119,7 @@ class RfiFilter:
     def integrate_raw(self, raw_dev, ndat):
         """Adds the 8-bit block (device tensor in the stream's layout, `ndat` samples from its first) until integration_length >=
         interval; excess input is not used.  Returns the samples used, a whole number of 8192-sample blocks."""
-        if self.info.machine in _lib.HEAP_MACHINES:
+        if self.form.name == "heaps":
             raise DspsrAmdError("dspsr_amd.rfi.RfiFilter.integrate_raw: the heaps of INSTRUMENT %s are not read here (the Bandpass operator "
                                 "takes the generic and CASPSR byte orders): unpack with dspsr_amd.unpack_heaps_fpt and call integrate"
                                 % self.info.machine)

@@ -19,6 +19,7 @@ import struct
 import numpy as np
 
 from .engine import DspsrAmdError
+from .inputs import InputFile, raw_form, tsamp_us
 
 # read_header.c:50-125: the type of every keyword that carries a value
 INT_KEYS = ("nchans", "telescope_id", "machine_id", "data_type", "ibeam", "nbeams", "nbits", "barycentric", "pulsarcentric", "nbins",
@@ -99,17 +100,6 @@ def read_header(path: str):
         return values, f.tell()
 
 
-def _tsamp_us(tsamp):
-    """tsamp in microseconds such that InputInfo.rate = 1e6 / tsamp_us is the reference's 1 / tsamp to the bit where a neighbour of
-    tsamp * 1e6 gives it"""
-    import math
-    rate, t = 1.0 / tsamp, tsamp * 1e6
-    for c in (t, math.nextafter(t, 0.0), math.nextafter(t, math.inf)):
-        if 1e6 / c == rate:
-            return c
-    return t
-
-
 def check_geometry(who, nbits, nchans, nifs):
     """What dsp::SigProcUnpacker cannot unpack, by name"""
     if nbits not in NBITS:
@@ -124,15 +114,12 @@ def check_geometry(who, nbits, nchans, nifs):
                             "(SigProcUnpacker.C:90,107-110)" % (who, nchans, nbits))
 
 
-class SigprocFile:
+class SigprocFile(InputFile):
     """dsp::SigProcFile + the block loop of dsp::IOManager: a SIGPROC filterbank file cut into the blocks LoadToFold's detected
     back end (pipeline.DetectedFold) consumes: runs of whole spectra as they lie in the file, no overlap, no transposition.
 
     .info is the pipeline.InputInfo of the stream (info.detected names the state: the driver takes its back end from it), .header the
     values read_header found (the `signed` key among them: read and ignored, as the unpacker ignores it)."""
-
-    heaps = twobit = guppi = False
-    detected = True
 
     def __init__(self, path: str):
         from .pipeline import InputInfo
@@ -157,27 +144,22 @@ class SigprocFile:
         source = h.get("source_name", "")
         self.coordinates = (h.get("src_raj", 0.0), h.get("src_dej", 0.0))
         self.info = InputInfo(centre_frequency=fch1 + 0.5 * (foff * (nchans - 1)), bandwidth=foff * nchans, nchan=nchans, npol=nifs, ndim=1,
-                              tsamp_us=_tsamp_us(tsamp), machine=machine_name(machine_id, telescope_id), start_seconds=0.0, mjd_day=day,
+                              tsamp_us=tsamp_us(tsamp), machine=machine_name(machine_id, telescope_id), start_seconds=0.0, mjd_day=day,
                               mjd_sec=(tstart - day) * 86400.0, source=source, telescope=telescope_name(telescope_id), nbit=nbits,
                               detected=STATES[nifs])
         self.extras = {"nbit": nbits, "ndat": 0, "offset_bytes": 0, "source": source, "telescope": telescope_name(telescope_id),
                        "dual_sideband": None, "dm": h.get("refdm"), "resolution": 1}
-        self._map = np.memmap(path, dtype=np.int8, mode="r", offset=self.header_bytes,
+        self.form = raw_form(self.info)
+        self.data = np.memmap(path, dtype=np.int8, mode="r", offset=self.header_bytes,
                               shape=(self.ndat * self.spectrum_bytes,)) if self.ndat else np.zeros(0, np.int8)
 
-    def _usable(self, lt=None):
-        return self.ndat
+    def samples(self, s0, n):
+        """Spectra s0 ... s0 + n - 1 as they lie in the file: a view of the memory map"""
+        return self.data[s0 * self.spectrum_bytes:(s0 + n) * self.spectrum_bytes]
 
-    def nblocks(self, lt):
-        """(whole blocks of lt.cfg.parts_per_block spectra, spectra of the ragged last block), as DadaFile.nblocks"""
-        return divmod(self.ndat, lt.cfg.parts_per_block)
-
-    def blocks(self, lt, channel=None):
-        """Yield (int8 host array, number of spectra) for the driver `lt`: views of the memory-mapped file."""
+    def read_units(self, g0, n, channel, granule):
+        """A unit is one spectrum (for the detected back end a part is one spectrum, no overlap: InputFile.blocks yields blocks of
+        parts_per_block spectra, the last one shorter)."""
         if channel is not None:
             raise DspsrAmdError("dspsr_amd.SigprocFile.blocks: a detected file is not sharded by channel; channel=%d asked" % channel)
-        full, rest = self.nblocks(lt)
-        ppb, sb = lt.cfg.parts_per_block, self.spectrum_bytes
-        for b in range(full + (1 if rest else 0)):
-            n = ppb if b < full else rest
-            yield self._map[b * ppb * sb:(b * ppb + n) * sb], n
+        return self.samples(g0, n)

@@ -118,9 +118,11 @@ def stream_of_file(f, nchan, npol):
 
 
 class Driver:
-    """the geometry a driver shows to blocks(): parts_per_block parts of nsamp_step samples and nsamp_overlap behind them"""
+    """the geometry a driver shows to blocks(): parts_per_block parts of nsamp_step samples and nsamp_overlap behind them, of blocks
+    in the form `form` (dspsr_amd.inputs: the file's own)"""
 
-    def __init__(self, parts_per_block, nsamp_step, nsamp_overlap):
+    def __init__(self, parts_per_block, nsamp_step, nsamp_overlap, form):
         from types import SimpleNamespace
+        self.form = form
         self.cfg = SimpleNamespace(parts_per_block=parts_per_block)
         self.nsamp_step, self.nsamp_overlap = nsamp_step, nsamp_overlap

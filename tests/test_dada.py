@@ -7,7 +7,7 @@ import types
 import numpy as np
 import pytest
 
-from dspsr_amd import dada, synth
+from dspsr_amd import dada, inputs, synth
 from dspsr_amd.engine import DspsrAmdError
 
 REF_HEADER = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "header.dada")     # the reference's Benchmark/header.dada
@@ -61,7 +61,7 @@ def test_reference_benchmark_header():
 
 
 def _fake_lt(step, overlap, ppb):
-    return types.SimpleNamespace(nsamp_step=step, nsamp_overlap=overlap, cfg=types.SimpleNamespace(parts_per_block=ppb))
+    return types.SimpleNamespace(nsamp_step=step, nsamp_overlap=overlap, cfg=types.SimpleNamespace(parts_per_block=ppb), form=inputs.Form())
 
 
 def test_file_layout_and_blocks(tmp_path):
@@ -77,9 +77,10 @@ def test_file_layout_and_blocks(tmp_path):
     lt = _fake_lt(step=100, overlap=30, ppb=4)
     assert f.nblocks(lt) == (2, 1)                                # (1000-30)//100 = 9 parts = 2 blocks of 4 + 1
     got = list(f.blocks(lt))
-    assert [n for _, n in got] == [4, 4, 1]
-    for b, (blk, npart) in enumerate(got):
+    assert [n for _, n, _ in got] == [4, 4, 1]
+    for b, (blk, npart, first) in enumerate(got):
         s0 = b * 400
+        assert first == 0
         assert np.array_equal(blk, data[s0 * 8:(s0 + npart * 100 + 30) * 8])          # consecutive blocks share the overlap
     one = list(f.blocks(lt, channel=1))
     assert np.array_equal(one[2][0], data.reshape(ndat, 2, 4)[800:930, 1, :].reshape(-1))
@@ -90,7 +91,7 @@ def test_file_layout_and_blocks(tmp_path):
     text = hdr.split(b"\0", 1)[0].decode().replace("HDR_SIZE 8192\n", "")
     (tmp_path / "y.hdr").write_text(text + "\n")
     g = dada.DadaFile(str(q))
-    assert g.header_bytes == 0 and g.info.nchan == 2 and np.array_equal(np.asarray(g._map[:64]), data[:64])
+    assert g.header_bytes == 0 and g.info.nchan == 2 and np.array_equal(np.asarray(g.samples(0, 8)), data[:64])
     r = tmp_path / "z.dada"
     r.write_bytes(b"\0" * 100)
     assert not dada.is_valid(str(r))

@@ -53,7 +53,7 @@ def test_header_and_every_field_of_the_observation(guppi, tmp_path):
     assert (i.centre_frequency, i.bandwidth, i.source, i.telescope) == (820.0, -16.0, "B0329+54", "GBT")
     assert abs(i.rate - 4e6) <= 4e6 * 1e-15 and i.tsamp_us == pytest.approx(0.25, rel=1e-15)
     assert f.basis == "Circular" and f.receiver == "Rcvr_800"
-    assert (f.heaps, f.twobit, f.guppi) == (False, False, True)
+    assert (f.heaps, f.twobit, f.guppi) == (False, False, True) and f.form.granule == BN and f.form.geometry == i.guppi
     assert (f.block_nsamp, f.chan_stride, f.block_stride, f.overlap) == (BN, (BN + OVL) * 4, NCHAN * (BN + OVL) * 4, OVL)
     assert i.guppi == (f.block_nsamp, f.chan_stride, f.block_stride)
     # the start time, worked by hand: PKTSIZE = 259 * 4 * 3 / 4 = 777 bytes; 40 packets = 31080 bytes = 248640 bits;
@@ -113,9 +113,9 @@ def test_stream_of_a_file(guppi, tmp_path, case):
     exp = np.concatenate([np.zeros((NCHAN, NPOL, BN), np.complex64) if k is None else cx[:, :, k * BN:(k + 1) * BN] for k in want], axis=2)
     got = gc.stream_of_file(f, NCHAN, NPOL)
     assert got.shape == exp.shape and np.array_equal(got, exp)
-    assert f._usable() == min(f.ndat, len(want) * BN)
+    assert f.usable() == min(f.ndat, len(want) * BN)
     # through blocks(): parts of 100 samples and 37 behind them, 3 parts per pipeline block
-    lt = gc.Driver(3, 100, 37)
+    lt = gc.Driver(3, 100, 37, f.form)
     full, rest = f.nblocks(lt)
     nparts = (len(want) * BN - 37) // 100
     assert (full, rest) == divmod(nparts, 3)
@@ -154,7 +154,7 @@ def test_pipeline_blocks_start_everywhere_and_one_channels_runs(guppi, tmp_path)
     gc.write_raw(path, x, bn, ovl, packets_per_block=PPB)
     f = guppi.GuppiFile(path)
     cx = gc.complex_of(x)
-    lt = gc.Driver(2, 127, 40)                       # pipeline blocks start at 0, 254 (the last sample of block 0), 508, 762
+    lt = gc.Driver(2, 127, 40, f.form)                     # pipeline blocks start at 0, 254 (the last sample of block 0), 508, 762
     got, firsts = _delivered(f, lt, NCHAN, NPOL)
     assert firsts[:3] == [0, bn - 1, 253] and 0 in firsts and bn - 1 in firsts and any(0 < v < bn - 1 for v in firsts)
     nparts = (5 * bn - 40) // 127

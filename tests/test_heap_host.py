@@ -56,8 +56,8 @@ def test_lib_constants_and_raw_at():
         assert name in _lib.SYMBOLS and hasattr(_lib.lib, name)
 
 
-def _stand_in(ppb, step, ovl):
-    return SimpleNamespace(cfg=SimpleNamespace(parts_per_block=ppb), nsamp_step=step, nsamp_overlap=ovl)
+def _stand_in(ppb, step, ovl, form):
+    return SimpleNamespace(cfg=SimpleNamespace(parts_per_block=ppb), nsamp_step=step, nsamp_overlap=ovl, form=form)
 
 
 @pytest.mark.parametrize("machine", sorted(hc.MACHINES))
@@ -72,7 +72,8 @@ def test_dada_file_of_heaps(tmp_path, machine, nchan, npol):
     f = dada.DadaFile(path)
     assert f.heaps and f.info.machine == machine and f.ndat == nheap * hc.HEAP
     ppb, step, ovl = 2, 301, 211                                # odd step: blocks start at many places inside a heap
-    lt = _stand_in(ppb, step, ovl)
+    lt = _stand_in(ppb, step, ovl, f.form)
+    assert (f.form.name, f.form.granule) == ("heaps", hc.HEAP)
     full, rest = f.nblocks(lt)
     assert (full, rest) == divmod((f.ndat - ovl) // step, ppb) and full >= 3
     stream = hc.stream_from_heaps(block, nchan, npol, swap)
@@ -114,28 +115,30 @@ def test_dada_file_header_refusals(tmp_path):
     # the generic reader is as it was: the same bytes under INSTRUMENT DADA are TFP samples
     f = dada.DadaFile(hc.write_dada(tmp_path / "tfp.dada", block, machine="DADA", nchan=2, npol=2))
     assert not f.heaps and f.ndat == block.size // 8
-    view, npart = next(iter(f.blocks(_stand_in(1, 100, 20))))
-    assert npart == 1 and view.size == 120 * 8
+    view, npart, first = next(iter(f.blocks(_stand_in(1, 100, 20, f.form))))
+    assert npart == 1 and view.size == 120 * 8 and first == 0 and f.form.name == "generic"
 
 
 def test_block_bytes_of_the_drivers():
-    from dspsr_amd import _lib, pipeline
+    from dspsr_amd import _lib, inputs, pipeline
+    machine_layout = lambda machine: inputs.raw_form(pipeline.InputInfo(machine=machine)).layout
     for machine, layout in (("MKBF", _lib.RAW_MEERKAT), ("MKBFRo", _lib.RAW_MEERKAT_SWAP)):
-        assert pipeline.machine_layout(machine) == layout
-    assert pipeline.machine_layout("CASPSR") == _lib.RAW_CASPSR and pipeline.machine_layout("DADA") == _lib.RAW_GENERIC
+        assert machine_layout(machine) == layout
+    assert machine_layout("CASPSR") == _lib.RAW_CASPSR and machine_layout("DADA") == _lib.RAW_GENERIC
     info = pipeline.InputInfo(nchan=4, npol=2, ndim=2, machine="MKBF")
     drv = SimpleNamespace(cfg=SimpleNamespace(parts_per_block=3), nsamp_step=301, nsamp_overlap=211, layout=_lib.RAW_MEERKAT, in_nchan=4,
-                          info=info)
+                          info=info, form=inputs.raw_form(info))
     for cls in (pipeline.LoadToFold, pipeline.ConvolvingFront):             # (LoadToFilCoherent's and LoadToFITS's blocks with -F)
         for npart, first in ((None, 0), (3, 0), (1, 0), (2, 255), (3, 17), (1, 1)):
             nsamp = (npart or 3) * 301 + 211
             assert cls.block_bytes(drv, npart, first) == hc.heap_bytes(-(-(first + nsamp) // 256), 4, 2)
+            assert drv.form.block_bytes(nsamp, 4, 2, 2, first) == cls.block_bytes(drv, npart, first)
             # (a layout word that already carries a first sample sizes the same block)
             drv.layout = _lib.raw_at(_lib.RAW_MEERKAT, 9)
             assert cls.block_bytes(drv, npart, first) == hc.heap_bytes(-(-(first + nsamp) // 256), 4, 2)
             drv.layout = _lib.RAW_MEERKAT
     # the other layouts size their blocks as before, and take no first sample
-    drv.layout = _lib.RAW_GENERIC
+    drv.layout, drv.form = _lib.RAW_GENERIC, inputs.raw_form(pipeline.InputInfo(nchan=4, npol=2, ndim=2, machine="DADA"))
     assert pipeline.LoadToFold.block_bytes(drv, 2) == (2 * 301 + 211) * 4 * 2 * 2
     with pytest.raises(Exception, match="first_sample"):
         pipeline.LoadToFold.block_bytes(drv, 2, 5)

@@ -95,7 +95,7 @@ def _fakes(mp):
             super().__init__()
             self.device, self.handle = device, 1
 
-    @recorded(log, "perform", "perform_raw", "perform_detect", "perform_fold", "set_kernel")
+    @recorded(log, "perform", "perform_raw", "perform_detect", "perform_fold", "set_kernel", "set_guppi")
     class Filterbank(Fake):
         nkeep, nsamp_step, nsamp_overlap, nsamp_fft = 100, 3200, 320, 3520
 
@@ -105,13 +105,27 @@ def _fakes(mp):
         def fold_is_fused(self):
             return 1
 
+        def set_twobit(self, nsample, nlow_min, nlow_max, levels, table_type):
+            log.call(self, "set_twobit", nsample, nlow_min, nlow_max, np.asarray(levels).shape, table_type)
+            self.nsample, self.unpacked = nsample, 0
+
+        def unpack_twobit(self, raw, first_sample, npart):
+            """the rows and all-one weights of the windows the block touches; block ZERO_WEIGHT_BLOCK has one zero window"""
+            log.call(self, "unpack_twobit", raw, first_sample, npart)
+            nsamp = npart * self.nsamp_step + self.nsamp_overlap
+            weights = torch.ones((2, -(-(first_sample + nsamp) // self.nsample)), dtype=torch.int32)
+            if self.unpacked == ZERO_WEIGHT_BLOCK:
+                weights[0, 3] = 0
+            self.unpacked += 1
+            return torch.zeros((1, 2, nsamp)), self.nsamp_step, weights
+
     class Conv(Filterbank):
         nkeep, nsamp_step, nsamp_overlap, nsamp_fft = 100, 100, 20, 120
 
     @recorded(log, "set_shape", "set_nbin", "set_ndat", "fold", "fold_moments", "fold_zeroed", "zero")
     class Fold(Fake):
-        def set_bins(self, phi, phase_per_sample, ndat, idat_start=0, hits=None):
-            log.call(self, "set_bins", phi, phase_per_sample, ndat, idat_start, hits)
+        def set_bins(self, phi, phase_per_sample, ndat, idat_start=0, hits=None, **weights):
+            log.call(self, "set_bins", phi, phase_per_sample, ndat, idat_start, hits, **weights)
             if hits is not None:
                 hits[(ndat + idat_start) % len(hits)] += ndat             # (a count the books can be checked by)
             return ndat
@@ -181,11 +195,13 @@ def _fakes(mp):
                lambda ctx, shape, dtype="float32", zero=False: torch.zeros(shape, dtype=getattr(torch, dtype)))
     mp.setattr(pipeline, "move_tail_fpt", lambda ctx, buf, dst, src, n, unit=1: log.call("pipeline", "move_tail_fpt", buf, dst, src, n, unit))
     mp.setattr(pipeline, "fourth_moment", lambda ctx, inp, out, ndat=None: log.call("pipeline", "fourth_moment", inp, out, ndat))
+    mp.setattr(pipeline, "unpack_sigproc_fpt", lambda ctx, raw, rows, nbit, nchan, npol, ndat:
+               log.call("pipeline", "unpack_sigproc_fpt", raw, rows, nbit, nchan, npol, ndat))
 
     def profiles_tensor(self, pulsar=None):
         nbin = self.cfg.nbin if pulsar is None else pulsar.nbin
         log.call("LoadToFold", "profiles_tensor", None if pulsar is None else self.pulsars.index(pulsar))
-        return torch.zeros(self.nchan_out * nbin * (14 if self.moments else 4))
+        return torch.zeros(self.nchan_out * nbin * (14 if self.moments else self.npol_out * self.cfg.ndim))
     mp.setattr(pipeline.LoadToFold, "profiles_tensor", profiles_tensor)
     return log
 
@@ -196,6 +212,10 @@ INFO = dict(centre_frequency=1382.0, bandwidth=-16.0, tsamp_us=1.0 / 32.0, machi
 CFG = dict(nchan=16, dispersion_measure=3.0, nbin=64, folding_period=0.004, ndim=4, parts_per_block=3, max_parts=2, subint_seconds=0.00045)
 # -s: turns of 400 and of 230 samples -- in a block of 300, one pulsar has a single piece where the other has two
 TARGETS = [pipeline.FoldTarget("a", folding_period=0.0004, nbin=64), pipeline.FoldTarget("b", folding_period=0.00023, nbin=32)]
+# two complex channels of 16 MHz (the same 1 MHz output channels) as heaps and as GUPPI raw blocks; 16 detected channels of 1 MHz
+HEAPS = dict(INFO, centre_frequency=1400.0, bandwidth=-32.0, nchan=2, ndim=2, tsamp_us=1.0 / 16.0, machine="MKBF")
+GUPPI = dict(HEAPS, machine="GUPPI", guppi=(64, 288, 576))
+DETECTED = dict(INFO, nchan=16, tsamp_us=1.0, machine="FAKE", detected="PPQQ")
 
 
 def _fold(cfg=(), info=INFO, **kw):
@@ -213,7 +233,22 @@ MODES = {
     "cyclic": _fold(dict(nbin=32, cyclic_nchan=16, cyclic_mover=2, cyclic_npol=2)),
     "plfb": _fold(dict(nchan=8, folding_period=0.0004, plfb_nbin=8, plfb_nchan=64, subint_seconds=0.0)),
     "sk": _fold(dict(sk_zap=True)),
+    # every input form through process_block: MeerKAT heaps (two channels of 16 MHz; 32 output channels), GUPPI raw blocks of 64 kept
+    # samples per run (8 more overlap the next block), CPSR2's two-bit samples, and detected rows (a part is one spectrum)
+    "heaps": _fold(dict(nchan=32), HEAPS),
+    "heaps_subband": _fold(dict(nchan=32), HEAPS, subband=1),
+    "guppi": _fold(dict(nchan=32), GUPPI),
+    "guppi_subband": _fold(dict(nchan=32), GUPPI, subband=1),
+    "twobit": _fold(info=dict(INFO, nbit=2, machine="CPSR2")),
+    "detected": _fold(dict(parts_per_block=300, interchan_dedispersion=True), DETECTED),
+    "detected_plain": _fold(dict(parts_per_block=300), DETECTED),
 }
+# where in its first heap / raw block / excision window each of the four blocks begins (every other mode: at 0), and the parts of the
+# blocks of spectra
+FIRST = {"heaps": (0, 128, 0, 255), "heaps_subband": (0, 128, 0, 255), "guppi": (0, 63, 17, 5), "guppi_subband": (0, 63, 17, 5),
+         "twobit": (0, 384, 256, 128)}
+SPECTRA = (300, 300, 300, 200)
+ZERO_WEIGHT_BLOCK = 1                          # the two-bit block whose unpacker returns a zero weight (it also holds a boundary)
 
 
 def _books(acc):
@@ -230,14 +265,19 @@ def _run(mp, mode):
     lt = MODES[mode]()
     opened = [log.name(o) for o in log.opened]
     marks = []
-    for npart in PARTS:
+    for npart, first in zip(SPECTRA if mode.startswith("detected") else PARTS, FIRST.get(mode, (0, 0, 0, 0))):
         marks.append(len(log.calls))
-        raw = torch.zeros(lt.block_bytes(npart), dtype=torch.int8)
-        lt.process_block(raw, npart)
+        raw = torch.zeros(lt.block_bytes(npart, first) if first else lt.block_bytes(npart), dtype=torch.int8)
+        lt.process_block(raw, npart, first_sample=first)
     marks.append(len(log.calls))
     lt.finish_subint()
     result = {"opened": opened, "blocks": [log.calls[a:b] for a, b in zip(marks, marks[1:])], "finish": log.calls[marks[-1]:],
               "books": _books(lt), "pulsars": [_books(p) for p in lt.pulsars], "ndat_out": int(lt.ndat_out), "nsamples_in": int(lt.nsamples_in)}
+    forms = [c for c in log.calls[:marks[0]] if c[1] in ("set_guppi", "set_twobit")]
+    if forms:                                  # what the constructor told the front end about the input's form
+        result["form"] = forms
+    if lt.twobit is not None:
+        result["twobit"] ={k: int(getattr(lt.twobit, k)) for k in ("discarded_weights", "blocks_fused", "blocks_weighted")}
     lt.close()
     return json.loads(json.dumps(result))
 
@@ -255,6 +295,7 @@ def test_the_trace_of_four_blocks_is_the_recorded_one(monkeypatch, mode):
     assert got["finish"] == want["finish"]
     for key in ("books", "pulsars", "ndat_out", "nsamples_in"):
         assert got[key] == want[key], key
+    assert got.get("twobit") == want.get("twobit") and got.get("form") == want.get("form")
 
 
 def test_the_blocks_chosen_reach_the_branches():
@@ -274,6 +315,21 @@ def test_the_blocks_chosen_reach_the_branches():
         assert all("move_tail_fpt" in methods(b) for b in fixture(mode)["blocks"][:3]), mode
     assert fixture("sk")["ndat_out"] == (1100 // 128) * 128 and fixture("during_K")["ndat_out"] < 1100
     assert sum(methods(b).count("accumulate") for b in fixture("plfb")["blocks"]) >= 3
+    # the input forms: a layout word per block, a sub-band rank's own geometry and shorter blocks, fused and weighted two-bit blocks
+    layouts = lambda mode: [c[3]["layout"] for b in fixture(mode)["blocks"] for c in b if "layout" in c[3]]
+    raw = lambda mode: [next(c[3]["raw"]["tensor"][0] for c in b if "raw" in c[3]) for b in fixture(mode)["blocks"]]
+    for mode in ("heaps", "heaps_subband"):
+        assert layouts(mode) == [3, 3 | 128 << 8, 3, 3 | 255 << 8], mode
+    for mode in ("guppi", "guppi_subband"):
+        assert layouts(mode) == [6, 6 | 63 << 8, 6 | 17 << 8, 6 | 5 << 8], mode
+    assert fixture("guppi")["form"][0][2] == [64, 288, 576] and fixture("guppi_subband")["form"][0][2] == [64, 288, 288]
+    assert all(a > b for mode in ("heaps", "guppi") for a, b in zip(raw(mode), raw(mode + "_subband")))
+    two = fixture("twobit")
+    assert two["twobit"]["blocks_fused"] >= 1 and two["twobit"]["blocks_weighted"] == 1 == two["twobit"]["discarded_weights"]
+    assert any("weights" in c[3] for b in two["blocks"] for c in b if c[1] == "set_bins")
+    assert all(methods(b)[0] == "unpack_sigproc_fpt" for mode in ("detected", "detected_plain") for b in fixture(mode)["blocks"])
+    assert all("move_tail_fpt" in methods(b) for b in fixture("detected")["blocks"][:3])
+    assert not any("move_tail_fpt" in methods(b) for b in fixture("detected_plain")["blocks"])
 
 
 def regenerate():

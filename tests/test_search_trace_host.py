@@ -82,6 +82,9 @@ def _fakes(mp):
         def search_is_fused(self):
             return True
 
+        def set_guppi(self, *geometry):
+            log.call(self, "set_guppi", *geometry)
+
         def perform_search(self, out, carry, carry_count, npart, tscrunch, state, **k):
             log.call(self, "perform_search", out, carry, carry_count, npart, tscrunch, state, **k)
             return divmod(carry_count + npart * self.nkeep, tscrunch)
@@ -137,6 +140,7 @@ REAL = dict(centre_frequency=1382.0, bandwidth=-400.0, nchan=1, npol=2, ndim=1, 
 CHANS = dict(centre_frequency=1400.0, bandwidth=-8.0, nchan=8, npol=2, ndim=2, tsamp_us=1.0, machine="DADA", start_seconds=0.5,
              mjd_day=55299, mjd_sec=7545.0)
 HEAPS = dict(centre_frequency=1382.0, bandwidth=-16.0, nchan=4, npol=2, ndim=2, tsamp_us=0.25, machine="MKBFRo")
+GUPPI = dict(HEAPS, machine="GUPPI", guppi=(200, 832, 3328))          # (8 samples of every run overlap the next block)
 FITS_REAL = dict(centre_frequency=1400.0, bandwidth=-16.0, nchan=1, npol=2, ndim=1, tsamp_us=1.0 / 32.0, machine="DADA")
 FITS_CHANS = dict(centre_frequency=1400.0, bandwidth=4.0, nchan=4, npol=2, ndim=2, tsamp_us=1.0, machine="DADA", source="J0000+0000")
 TFP = dict(nchan=64, tscrunch=16, nbit=8, rescale_seconds=2e-4, parts_per_block=64)
@@ -163,6 +167,11 @@ CASES = {
     # -d 4 on heaps: blocks of 3 parts of 462 samples begin at samples 0, 106, 212, 62 of their first heaps
     "coherent_d4_heaps": (_search("LoadToFilCoherent", HEAPS, nchan=4, dispersion_measure=10.0, freq_res=1024, tscrunch=4, npol=4, nbit=8,
                                   rescale_seconds=0.0, parts_per_block=3, max_parts=2), (3, 3, 3, 2)),
+    # the same channels as GUPPI raw blocks of 200 kept samples per run: the blocks begin at samples 0, 186, 172, 158 of their first one
+    "coherent_guppi": (_search("LoadToFilCoherent", GUPPI, nchan=4, dispersion_measure=10.0, freq_res=1024, tscrunch=4, npol=2, nbit=8,
+                               rescale_seconds=0.0, parts_per_block=3, max_parts=2), (3, 3, 3, 2)),
+    "fits_F_guppi": (_fits(GUPPI, nchan=4, convolve=True, dispersion_measure=10.0, coherent_dedisp=True, tsamp=16e-6,
+                           parts_per_block=3, npol=2, nbit=8), (3, 3, 3, 2)),
     "direct_fused": (_search("LoadToFilDirect", CHANS, **DIRECT), (64, 64, 64, 30)),
     "direct_K_f": (_search("LoadToFilDirect", CHANS, dispersion_measure=2.0, dedisperse=True, fscrunch=2, npol=2, **DIRECT), (64, 64, 64, 30)),
     "direct_K_empty_call": (_search("LoadToFilDirect", CHANS, dispersion_measure=2.0, dedisperse=True, **{**DIRECT, "nbit": -32, "rescale_seconds": 0.0}),
@@ -178,10 +187,11 @@ CASES = {
 
 
 def _first_sample(drv, k, counts):
-    """where in its first heap call k begins (zero without heaps), as DadaFile.blocks counts it"""
-    if drv.info.machine != "MKBFRo":
+    """where in its first heap, or in the runs of its first GUPPI raw block, call k begins (zero for every other input), as the
+    readers' blocks() count it"""
+    if drv.info.machine != "MKBFRo" and drv.info.guppi is None:
         return 0
-    return (sum(counts[:k]) * drv.nsamp_step) % 256
+    return (sum(counts[:k]) * drv.front.nsamp_step) % (256 if drv.info.guppi is None else drv.info.guppi[0])
 
 
 def _run(mp, name):
@@ -248,6 +258,12 @@ def test_the_blocks_chosen_reach_the_branches():
     assert all(_methods(b)[:2] == ["perform_detect", "tscrunch_fpt"] for b in d4["blocks"])
     layouts = [b[0][3]["layout"] for b in d4["blocks"]]
     assert len(set(layouts)) > 1, "a block that begins inside a heap"
+    # GUPPI raw blocks: the geometry goes to the engine once, every call carries the layout word of its own first sample
+    for name in ("coherent_guppi", "fits_F_guppi"):
+        fx = _fixture(name)
+        assert fx["setup"][-1][1:3] == ["set_guppi", [200, 832, 3328]], name
+        words = [b[0][3]["layout"] for b in fx["blocks"]]
+        assert all(w & 0xff == 6 for w in words) and words[0] == 6 and len(set(words)) == 4, (name, words)
     # LoadToFilDirect: one pass; -K -f; an empty call between two others does nothing but carry the tail along
     assert all(_methods(b) == ["detect_raw", "digitize_fpt"] for b in _fixture("direct_fused")["blocks"])
     dkf = _fixture("direct_K_f")

@@ -74,9 +74,9 @@ class _Driver:
     """what blocks() / nblocks() read of a driver"""
 
     def __init__(self, parts_per_block):
-        from dspsr_amd import pipeline
+        from dspsr_amd import inputs, pipeline
         self.cfg = pipeline.Config(parts_per_block=parts_per_block)
-        self.nsamp_step, self.nsamp_overlap = 1, 0
+        self.nsamp_step, self.nsamp_overlap, self.form = 1, 0, inputs.Detected()
 
 
 @pytest.mark.parametrize("nifs", [1, 2, 4])
@@ -99,9 +99,9 @@ def test_round_trips_the_writer(sigproc, tmp_path, nbit, nifs):
     assert i.centre_frequency == 1500.25 + 0.5 * (-0.5 * 23) and i.bandwidth == -12.0 and i.rate == 1.0 / 6.4e-5
     assert (i.machine, i.telescope, i.source) == ("BPSR", "Parkes", "B1937+21")
     assert i.mjd_day == 60000 and i.mjd_sec == 0.75 * 86400.0 and i.start_seconds == 0.0
-    assert (f.heaps, f.twobit, f.guppi, f.detected) == (False, False, False, True)
-    from dspsr_amd import guppi
-    assert isinstance(guppi.open_input(path), sigproc.SigprocFile)
+    assert (f.heaps, f.twobit, f.guppi, f.detected) == (False, False, False, True) and (f.form.nbit, f.form.granule) == (nbit, 1)
+    from dspsr_amd import guppi, inputs
+    assert isinstance(guppi.open_input(path), sigproc.SigprocFile) and guppi.open_input is inputs.open_input
 
 
 def test_id_tables(sigproc):
@@ -166,10 +166,10 @@ def test_ndat_and_blocks(sigproc, tmp_path, nbit):
         f = sigproc.SigprocFile(path)
         assert f.ndat == ndat == (os.path.getsize(path) - f.header_bytes) * 8 // (nbit * nifs * nchan)
         lt = _Driver(8)
-        assert f.nblocks(lt) == (2, 7) and f._usable(lt) == ndat
+        assert f.nblocks(lt) == (2, 7) and f.usable(lt) == ndat
         got = list(f.blocks(lt))
-        assert [n for _b, n in got] == [8, 8, 7] and all(b.dtype == np.int8 and b.size == n * S for b, n in got)
-        assert np.array_equal(np.concatenate([b for b, _n in got]).view(np.uint8), data)
+        assert [n for _b, n, _f in got] == [8, 8, 7] and all(b.dtype == np.int8 and b.size == n * S and first == 0 for b, n, first in got)
+        assert np.array_equal(np.concatenate([b for b, _n, _f in got]).view(np.uint8), data)
     with pytest.raises(Exception, match="channel"):
         list(f.blocks(lt, channel=0))
 

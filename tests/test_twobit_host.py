@@ -187,7 +187,8 @@ class _Geometry:
 
     def __init__(self, nsample, step, overlap, ppb):
         from types import SimpleNamespace
-        self.twobit = SimpleNamespace(nsample=nsample)
+        from dspsr_amd import inputs
+        self.form = inputs.TwoBit(granule=nsample)
         self.nsamp_step, self.nsamp_overlap = step, overlap
         self.cfg = SimpleNamespace(parts_per_block=ppb)
 
@@ -207,7 +208,7 @@ def test_nbit2_header_cases(tmp_path):
     lt = _Geometry(nsample=64, step=100, overlap=30, ppb=3)
     f = dada.DadaFile(_write(tmp_path / "d.dada", data[:3990]))
     assert f.ndat == 7980
-    assert f._usable(lt) == 7936 and f.nblocks(lt) == divmod((7936 - 30) // 100, 3)
+    assert f.usable(lt) == 7936 and f.nblocks(lt) == divmod((7936 - 30) // 100, 3)
     got = list(f.blocks(lt))
     assert len(got) == 27 and got[-1][1] == 1
     for b, (block, npart, first) in enumerate(got):

@@ -61,8 +61,8 @@ def main(argv=None):
     a = parse_args(argv)
     import torch
 
-    from dspsr_amd import guppi, pipeline
-    df = guppi.open_input(a.file)                           # (a GUPPI raw file is recognised here and refused by LoadToFilDirect, by name)
+    from dspsr_amd import inputs, pipeline
+    df = inputs.open_input(a.file)                          # (a GUPPI raw file is recognised here and refused by LoadToFilDirect, by name)
     info = df.info
     info.nbit = df.extras["nbit"]
     cfg = search_config(a, info, df.extras)

@@ -67,8 +67,8 @@ def fits_config(a, extras):
 
 def main(argv=None):
     a = parse_args(argv)
-    from dspsr_amd import dada, guppi, pipeline
-    cfg = fits_config(a, guppi.open_input(a.file).extras)   # a DADA file, or a GUPPI raw file: recognised from the file
+    from dspsr_amd import dada, inputs, pipeline
+    cfg = fits_config(a, inputs.open_input(a.file).extras)   # a DADA file, or a GUPPI raw file: recognised from the file
     header, blocks = dada.search_blocks_file(a.file, cfg, device=a.device, log=sys.stderr)
     out = a.output or os.path.splitext(os.path.basename(a.file))[0] + ".sblk"
     pipeline.write_search_blocks(out, header, blocks)

@@ -149,10 +149,10 @@ def fold_targets(a, nbin, out_rate, mjd_day, mjd_sec):
     return out
 
 
-def fold_detected(a):
-    """A SIGPROC filterbank file: nchan and state come from the file, -D matters only with -K"""
-    import torch
-    from dspsr_amd import dada, pipeline, sigproc
+def detected_input(a):
+    """A SIGPROC filterbank file: nchan and state come from the file, -D matters only with -K.  Returns what main() takes of an
+    input: (info, the rate of the rows that are folded, dm, the Config fields of this input -- a function: built behind the refusals)."""
+    from dspsr_amd import sigproc
     f = sigproc.SigprocFile(a.file)
     info = f.info
     if a.fb is not None and ":" in a.fb:
@@ -162,53 +162,20 @@ def fold_detected(a):
     dm = a.dm if a.dm is not None else f.extras["dm"] or 0.0
     if a.interchan and a.dm is None and f.extras["dm"] is None:
         sys.exit("-K needs -D: no refdm in the header")
-    targets = fold_targets(a, a.nbin, info.rate, info.mjd_day, info.mjd_sec)
-    period = a.period[0] if len(a.period) == 1 else 0.0
-    polyco = pipeline.Polyco(open(a.polyco[0]).read()) if len(a.polyco) == 1 and not targets else None
-    if not targets and polyco is None and period <= 0:
-        sys.exit("dsp::Fold::fold no polynomial and no period specified (-c or -P)")
-    pfold = period if period > 0 else 1.0 / polyco.frequency(info.mjd_day, info.mjd_sec) if polyco else 0.0
-    nbin = a.nbin or (pipeline.choose_nbin(pfold, info.rate) if pfold else targets[0].nbin)
     # a block of about 64 MiB of float rows, whole spectra
     block = max(1, min(max(f.ndat, 1), (1 << 24) // (info.nchan * info.npol)))
-    cfg = pipeline.Config(nchan=int(a.fb) if a.fb is not None else info.nchan, dispersion_measure=dm, nbin=nbin, folding_period=period,
-                          subint_seconds=a.subint, subint_turns=1.0 if a.single else a.turns, plfb_nbin=a.plfb_nbin, cyclic_nchan=a.cyclic,
-                          interchan_dedispersion=a.interchan, record_time=a.record, fourth_moment=a.fourth, calibrator=a.pac,
-                          zap_rfi=a.zap_rfi, sk_zap=a.skz, parts_per_block=block)
-    torch.cuda.set_device(a.device)
-    lt = dada.fold_file(a.file, cfg, polyco=polyco, device=a.device, stream=torch.cuda.current_stream().cuda_stream,
-                        dump_before=tuple(a.dump), targets=targets or None)
-    for line in lt.vitals():
-        print(line, file=sys.stderr)
-    outputs = [("%s_%%04d.ps" % a.prefix, lt.subints, pfold)]
-    if targets:
-        outputs = [("%s_%d_%%04d.ps" % (a.prefix, k), p.subints,
-                    p.target.folding_period or 1.0 / p.target.polyco.frequency(info.mjd_day, info.mjd_sec))
-                   for k, p in enumerate(lt.pulsars)]
-    for pattern, subints, pf in outputs:
-        for n, sub in enumerate(subints):
-            path = pattern % n
-            pipeline.write_phase_series(path, sub, info, lt.cfg, nchan=info.nchan, npol=info.npol, scale=lt.scalefac, division=n,
-                                        start_seconds=lt.out_start, folding_period=pf)
-            print("dspsr_amd: %s  integration %.6f s  %d samples" % (path, sub["integration_length"], sub["ndat_total"]))
-    if a.record:
-        lt.report()
-    lt.close()
+    return info, info.rate, dm, lambda: dict(nchan=int(a.fb) if a.fb is not None else info.nchan, parts_per_block=block)
 
 
-def main(argv=None):
-    a = parse_args(argv)
-    from dspsr_amd import sigproc
-    if sigproc.is_valid(a.file):                            # a SIGPROC filterbank file: recognised from the file, no option
-        return fold_detected(a)
+def voltage_input(a):
+    """A DADA or GUPPI raw file: -F says where the coherent dedispersion goes.  Returns what detected_input returns."""
     if a.fb is None:
         sys.exit("the following arguments are required: -F (the input holds voltages)")
     when = "during" if a.fb.endswith(":D") else "before" if a.fb.endswith(":B") else "after"
     if ":" in a.fb and when == "after":
         sys.exit("-F nchan:D (coherent dedispersion During the filterbank), -F nchan (After it) or -F nchan:B (Before it) are on this "
                  "path; not %s" % a.fb)
-    import torch
-    from dspsr_amd import dada, guppi, pipeline
+    from dspsr_amd import dada, guppi
     if guppi.is_valid(a.file):                              # a GUPPI / PUPPI raw file: recognised from the file, no option
         f = guppi.GuppiFile(a.file)
         info, extras = f.info, f.extras
@@ -220,6 +187,19 @@ def main(argv=None):
         sys.exit("no -D and no DM in the header")
     nchan = int(a.fb.split(":")[0])
     out_rate = info.rate / (2 if info.ndim == 1 else 1) / (nchan // info.nchan)
+    return info, out_rate, dm, lambda: dict(
+        nchan=nchan, freq_res=a.nfft, cyclic_mover=a.cyclic_mover, **detection_options(a, info.npol), sk_m=a.skzm, sk_std_devs=a.skzs,
+        sk_chan_start=a.skz_start, sk_chan_end=a.skz_end, sk_no_fscr=a.skz_no_fscr, sk_no_tscr=a.skz_no_tscr, sk_no_ft=a.skz_no_ft,
+        **unpacker_options(a.unpack), convolve_when="never" if when == "after" and dm == 0.0 else when)
+
+
+def main(argv=None):
+    a = parse_args(argv)
+    from dspsr_amd import sigproc
+    detected = sigproc.is_valid(a.file)                     # a SIGPROC filterbank file: recognised from the file, no option
+    info, out_rate, dm, options = (detected_input if detected else voltage_input)(a)
+    import torch
+    from dspsr_amd import dada, pipeline
     targets = fold_targets(a, a.nbin, out_rate, info.mjd_day, info.mjd_sec)
     period = a.period[0] if len(a.period) == 1 else 0.0
     polyco = pipeline.Polyco(open(a.polyco[0]).read()) if len(a.polyco) == 1 and not targets else None
@@ -227,13 +207,10 @@ def main(argv=None):
         sys.exit("dsp::Fold::fold no polynomial and no period specified (-c or -P)")
     pfold = period if period > 0 else 1.0 / polyco.frequency(info.mjd_day, info.mjd_sec) if polyco else 0.0
     nbin = a.nbin or (pipeline.choose_nbin(pfold, out_rate) if pfold else targets[0].nbin)
-    cfg = pipeline.Config(nchan=nchan, dispersion_measure=dm, nbin=nbin, folding_period=period, freq_res=a.nfft,
-                          subint_seconds=a.subint, subint_turns=1.0 if a.single else a.turns, plfb_nbin=a.plfb_nbin,
-                          cyclic_nchan=a.cyclic, cyclic_mover=a.cyclic_mover, **detection_options(a, info.npol),
+    cfg = pipeline.Config(dispersion_measure=dm, nbin=nbin, folding_period=period, subint_seconds=a.subint,
+                          subint_turns=1.0 if a.single else a.turns, plfb_nbin=a.plfb_nbin, cyclic_nchan=a.cyclic,
                           interchan_dedispersion=a.interchan, record_time=a.record, fourth_moment=a.fourth, calibrator=a.pac, zap_rfi=a.zap_rfi,
-                          sk_zap=a.skz, sk_m=a.skzm, sk_std_devs=a.skzs, sk_chan_start=a.skz_start, sk_chan_end=a.skz_end, sk_no_fscr=a.skz_no_fscr,
-                          sk_no_tscr=a.skz_no_tscr, sk_no_ft=a.skz_no_ft, **unpacker_options(a.unpack),
-                          convolve_when="never" if when == "after" and dm == 0.0 else when)
+                          sk_zap=a.skz, **options())
     torch.cuda.set_device(a.device)
     lt = dada.fold_file(a.file, cfg, polyco=polyco, device=a.device, stream=torch.cuda.current_stream().cuda_stream,
                         dump_before=tuple(a.dump), targets=targets or None, rfi_log=sys.stderr)
@@ -244,18 +221,20 @@ def main(argv=None):
         outputs = [("%s_%d_%%04d.ps" % (a.prefix, k), p.subints,
                     p.target.folding_period or 1.0 / p.target.polyco.frequency(info.mjd_day, info.mjd_sec))
                    for k, p in enumerate(lt.pulsars)]
-    cyc = {}
+    series = {}                                             # what the mode, not Detection, says about the phase series
+    if detected:                                            # the file's own channels, under the Config of the detected back end
+        cfg, series = lt.cfg, {"nchan": info.nchan}
     if a.cyclic:                                            # nchan * nchan_spec / mover channels, ndim 1 (CyclicFold.C:96-119)
         g = pipeline.cyclic_geometry(cfg, info)
-        cyc = {"nchan": g["nchan"], "state": g["state"]}
+        series = {"nchan": g["nchan"], "state": g["state"]}
     if a.plfb_nbin:                                         # PhaseLockedFilterbank.C:123-159: what it sets on its output
         g = lt.plfb_geometry
-        cyc = {"nchan": g["nchan"], "state": g["state"], "rate": g["rate"], "nsub_swap": g["nsub_swap"]}
+        series = {"nchan": g["nchan"], "state": g["state"], "rate": g["rate"], "nsub_swap": g["nsub_swap"]}
     for pattern, subints, pf in outputs:
         for n, sub in enumerate(subints):
             path = pattern % n
             pipeline.write_phase_series(path, sub, info, cfg, npol=lt.npol_out, scale=sub.get("scale", lt.scalefac), division=n,
-                                        start_seconds=lt.out_start, folding_period=pf, **cyc)
+                                        start_seconds=lt.out_start, folding_period=pf, **series)
             print("dspsr_amd: %s  integration %.6f s  %d samples" % (path, sub["integration_length"], sub["ndat_total"]))
     if a.skz:                                               # SpectralKurtosis.C:53-69, the destructor's line
         st = lt.sk.get_statistics()
